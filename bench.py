@@ -16,6 +16,12 @@ the phi-resample sharded by atlas z-slab ("scaling": "strong").  Rank 0 prints O
 
 --dry-run: no GPU, no kernels: the launcher, the rendezvous and the collectives of oai_analysis_2_amd.parallel run on CPU
 tensors over gloo with a stand-in per-rank compute (CI check of the multi-process plumbing; "value" is null).
+
+A plain run sets up, warms up, times --steps steps and prints the result line (value, ms_per_step, roofline of the timed steps).
+--full adds what takes runs of its own: full-size parity against the reference goldens, the ICON step trees, the streamed-from-host
+leg, the same workload in the other arithmetic and the CPU baseline (each can still be left out with its --no-* option).
+--dump-outputs DIR writes what the last timed step returned (fc, tc, phi, fc_atlas, tc_atlas) as DIR/<name>.npy, float32; an
+array of more than DUMP_SAMPLE elements as a fixed seeded sample of them (see dump_outputs).
 """
 import argparse
 import json
@@ -41,6 +47,9 @@ DTYPE_OF = {"f32": "f32", "bf16x6": "bf16x6 (fp32 operands split into 3 bf16 ter
             "fp16x3": "fp16x3 (every fp32 value held as 2 fp16 terms = 22 mantissa bits, 3 MFMA passes per product, fp32 accumulate; "
                       "fp32 in and out of every entry point; full-size parity vs the reference in `parity`)"}
 TRAFFIC_FILE = {"f32": "profiles/r06_pmc_traffic_f32.json", "fp16x3": "profiles/r06_pmc_traffic_sres.json"}
+DUMP_OUTPUTS = ("fc", "tc", "phi", "fc_atlas", "tc_atlas")       # the arrays of pipeline.VolumeResult
+DUMP_SAMPLE = 1 << 21             # elements per dumped array (8 MB of float32; 40 MB for the five)
+DUMP_SEED = 0
 
 
 def physical_cores() -> int:
@@ -363,8 +372,24 @@ def streamed_from_host(pipe, n_volumes=24, resident_ms=None):
                     "fc_atlas, tc_atlas (566 MB per volume) -> caller-owned host tensors; upload / compute / download / host copy overlapped (cohort.CohortRunner)"}
 
 
+def dump_outputs(res, out_dir):
+    """The arrays the caller of the timed path received in the last timed step, as ``out_dir/<name>.npy`` in float32.  An array
+    of more than DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE flat indices drawn without replacement by a
+    generator seeded with DUMP_SEED, in increasing order: the same positions in every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name in DUMP_OUTPUTS:
+        t = getattr(res, name).detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.to(torch.float32).cpu().numpy())
+
+
 def measure(step, unet, steps, warmup, use_dist, dist):
-    """W untimed + K timed steps, barrier + synchronize on both sides; returns (seconds, conv ms, conv launches)."""
+    """W untimed + K timed steps, barrier + synchronize on both sides; returns (seconds, conv ms, conv launches, fp16 overflow,
+    the last timed step's result)."""
     import torch
     for i in range(warmup):
         step(i)
@@ -375,9 +400,11 @@ def measure(step, unet, steps, warmup, use_dist, dist):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    flags = []
+    flags, res = [], None
     for i in range(steps):
-        flags.append(step(i).overflow)
+        del res                                                           # the previous step's arrays go back to the allocator first
+        res = step(i)
+        flags.append(res.overflow)
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -386,7 +413,7 @@ def measure(step, unet, steps, warmup, use_dist, dist):
     conv_ms, conv_launches = unet.profile_read()
     unet.profile(False)
     overflow = any(int(f.item()) for f in flags if f is not None)      # the per-volume fp16 range flags, read after the timed region
-    return dt, conv_ms, conv_launches, overflow
+    return dt, conv_ms, conv_launches, overflow, res
 
 
 def main():
@@ -404,6 +431,11 @@ def main():
                          "is ONE volume whose 160 tiles are split over the ranks + one RCCL all_gather (strong scaling); cohort = "
                          "BASELINE config 5's form: --steps x N volumes (64 at --steps 8 --gpus 8) in ONE shared queue, every rank claims "
                          "the next volume when it is free (parallel.VolumeQueue) -- same work as replicas, dynamically assigned")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: full-size parity, ICON step trees, the streamed-from-host "
+                         "leg, the other arithmetic, the CPU baseline (the --no-* options below leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (float32; a fixed seeded sample of a larger array)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt", action="store_true", help="skip the second measurement in exact fp32 MFMA (full --steps) reported beside the primary")
     ap.add_argument("--no-parity", action="store_true", help="skip the full-size parity block (reference golden fixture)")
@@ -415,6 +447,8 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="registration after, not underneath, the segmentation (A/B of VolumePipeline.overlap_registration)")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo check of launcher + collectives, no GPU, no kernels")
     args = ap.parse_args()
+    if not args.full:                                                     # a plain run: the headline figure and nothing else
+        args.no_cpu_baseline = args.no_alt = args.no_parity = args.no_streamed = True
 
     launched = "WORLD_SIZE" in os.environ                                 # started by torch.distributed.run (also with one rank)
     if not launched and args.gpus > 1:
@@ -500,16 +534,18 @@ def main():
             # a rank claims its next volume when the one BEFORE the volume it has just queued is finished: the host runs one volume
             # ahead of its GPU (so the GPU never idles), not the whole queue ahead (kernel launches are asynchronous: unbounded, the
             # rank whose host thread is fastest would claim most of the cohort -- ADVICE r2)
-            flags, events = [], []
+            flags, events, res = [], [], None
             for i in q:
                 claimed.append(i)
-                flags.append(pipe.run(vols[i % n_distinct], meta, check=False).overflow)
+                del res
+                res = pipe.run(vols[i % n_distinct], meta, check=False)
+                flags.append(res.overflow)
                 ev = torch.cuda.Event()
                 ev.record()
                 events.append(ev)
                 if len(events) >= 2:
                     events[-2].synchronize()
-            return flags
+            return flags, res
 
         run_queue(warm_q)
         torch.cuda.synchronize()
@@ -520,7 +556,7 @@ def main():
         torch.cuda.synchronize()
         claimed.clear()
         t0 = time.perf_counter()
-        flags = run_queue(timed_q)
+        flags, last = run_queue(timed_q)
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
@@ -531,8 +567,10 @@ def main():
         overflow = any(int(f.item()) for f in flags if f is not None)
         my_volumes = len(claimed)
     else:
-        dt, conv_ms, conv_launches, overflow = measure(step, unet, args.steps, args.warmup, use_dist, dist)
+        dt, conv_ms, conv_launches, overflow, last = measure(step, unet, args.steps, args.warmup, use_dist, dist)
         my_volumes = args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)                             # before anything else runs on the device
     streamed_rows = None
     if args.mode == "cohort" and not args.no_streamed:
         # (outside the timed region) every rank streams 12 volumes out of ITS host memory through CohortRunner at the same time: the first multi-GPU line
@@ -659,7 +697,7 @@ def main():
             # a first-class measurement, so that a reader who only credits reference-precision arithmetic has a number
             alt = "f32" if args.precision != "f32" else "fp16x3"
             unet.set_precision(alt)
-            dta, ms_a, n_a, ov_a = measure(step, unet, args.steps, args.warmup, False, dist)
+            dta, ms_a, n_a, ov_a, _ = measure(step, unet, args.steps, args.warmup, False, dist)
             unet.set_precision(args.precision)
             out["fp32_mfma" if alt == "f32" else "alt_precision"] = {
                 "precision": alt, "dtype": DTYPE_OF[alt], "value": args.steps / dta, "unit": "volumes/s", "steps": args.steps,

@@ -19,7 +19,7 @@ tt = sum(float(x["TotalDurationNs"]) for x in rows if "conv3_igemm_sres" in x["N
 par = d.get("parity") or {}
 txt = f'''# profiles, round {tag[1:].lstrip("0")}
 
-`{tag}_bench_kernel_stats.csv` : `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1`
+`{tag}_bench_kernel_stats.csv` : `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1`
 on one MI355X (wrapper: `scripts/prof_round.sh {tag}`).  `{tag}_bench_line.json` : the JSON line that same run printed.  The run
 processes the default split-fp16 (fp16x3) arithmetic (1 warm-up + 3 timed volumes, + 2 segmentations for the `parity` block) and
 then the same again in exact fp32 MFMA (the `fp32_mfma` object, full --steps), so both kernel families appear in the CSV.  All 160

@@ -4,7 +4,7 @@
 # kernel (MFMA-busy share, effective clock = GRBM_GUI_ACTIVE / 8 / wall).   usage: bash scripts/prof_round.sh [round tag]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=${1:-r02}; O=$R/gpurun_out/round_$TAG; mkdir -p $O; cd $R
-rocprofv3 --kernel-trace --stats -d $O/bench -o bench --output-format csv -- python3 bench.py --steps 3 --warmup 1 > $O/bench_line.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/bench -o bench --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 > $O/bench_line.json 2> $O/bench.err
 tail -1 $O/bench_line.json | head -c 1500; echo
 export PREC=f32            # the exact-fp32 leg's HBM-side traffic (its own passes; counters + kernel-trace only)
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch32 -o f --output-format csv -- python3 scripts/perf_layers.py > $O/fetch32.log 2>&1
