@@ -442,6 +442,43 @@ int oai_mesh_point_distance_grid(const float* points_dev, long long n_points, co
                                  long long n_tris, const float grid_lo_xyz_host[3], float cell_size, const int grid_dims_xyz_host[3],
                                  void* workspace_dev, size_t workspace_bytes, float* dist_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Atlas thickness map: the step after get_thickness_mesh (SURVEY row L1'), oai_analysis/mesh_processing.py:400-534 as
+ * notebooks/FullDemo.ipynb calls it: map_attributes(distance_inner, atlas_inner_mesh), then project_thickness(mapped, mesh_type).
+ * Points are float32 [n][3] (x, y, z); sums are fp64 in a fixed order (block partials + one final block, no float atomics), so
+ * every result is the same bits from run to run.
+ * ---------------------------------------------------------------------------------------- */
+/* map_attributes (:400-408): vtkPointInterpolator with VTK 9 defaults (vtkLinearKernel, RADIUS footprint, NormalizeWeights on)
+ * and SetNullPointsStrategyToClosestPoint.  out[c][t] = float32(fp64 mean of vals[c][s] over the source points s with
+ * |p_s - q_t|^2 <= radius^2), or vals[c][s*] of the closest source point s* (ties: the smallest index) if there is none.
+ * vals [n_comp][n_src], out [n_comp][n_tgt].  Brute force over every source point (the cross-check). */
+int oai_map_attributes(const float* src_pts_dev, long long n_src, const float* src_vals_dev, int n_comp, const float* tgt_pts_dev,
+                       long long n_tgt, double radius, float* out_vals_dev, void* stream);
+/* Same result with the source points binned into a uniform grid (cells of `cell_size` >= radius from `grid_lo`, `grid_dims`
+ * cells per axis; points outside fall into the border cells), each cell's list ordered by point index; a target point sums the
+ * 27 cells around its own, and searches shells of cells for the closest point when that finds nothing.  Mesh_processing.py:400-408. */
+size_t oai_point_grid_workspace_bytes(const int grid_dims_xyz[3], long long n_src);
+int oai_map_attributes_grid(const float* src_pts_dev, long long n_src, const float* src_vals_dev, int n_comp, const float* tgt_pts_dev,
+                            long long n_tgt, double radius, const double grid_lo_xyz_host[3], double cell_size, const int grid_dims_xyz_host[3],
+                            void* workspace_dev, size_t workspace_bytes, float* out_vals_dev, void* stream);
+/* Workspace of the three calls below for n points (mesh_processing.py:411-534). */
+size_t oai_thickness_map_workspace_bytes(long long n_points);
+/* compute_least_square_circle (:411-447) on (x, y) = (p[col_x], p[col_y]): the centre minimising sum (R_i - mean R)^2, by
+ * Gauss-Newton with step halving from the centroid (the reference: scipy leastsq with the centred Jacobian); stops when the step
+ * is <= 1e-12 x the rms distance from the centroid, or after 100 steps.  radius = mean R_i.  Synchronises the stream. */
+int oai_fit_circle(const float* pts_dev, long long n, int col_x, int col_y, void* workspace_dev, size_t workspace_bytes, double centre_host[2],
+                   double* radius_host, int* iterations_host, void* stream);
+/* get_projection_from_circle_and_vertice (:459-478), embedded part: angle[i] = atan2(y - c_y, x - c_x), z[i] = p[i][2], fp64. */
+int oai_project_circle(const float* pts_dev, long long n, int col_x, int col_y, const double centre_host[2], double* angle_dev, double* z_dev,
+                       void* stream);
+/* project_thickness, mesh_type "TC" (:486-534): plateaus split at z < 50; per plateau the centred scores on the top-2 axes of its
+ * 3x3 scatter matrix (= KernelPCA(n_components=2), linear kernel), each axis signed as sklearn's svd_flip(u) does; the left
+ * plateau rotated by -50 degrees, the right one by -160 degrees, its x negated and 50 added to its y.  x, y, thickness_out
+ * [n_right + n_left]: the right plateau's points first, each plateau in point order.  An empty plateau is an error.
+ * Synchronises the stream. */
+int oai_project_plateaus(const float* pts_dev, const float* thickness_dev, long long n, void* workspace_dev, size_t workspace_bytes,
+                         double* x_dev, double* y_dev, double* thickness_out_dev, long long* n_right_host, long long* n_left_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,10 @@ int set_error(int code, const char* fmt, ...);
 // after a kernel launch: catches bad launch configurations without synchronising
 #define OAI_CHECK_LAUNCH() OAI_CHECK_HIP(hipGetLastError())
 
+// exclusive scan of int32 (csrc/mesh.hip): out[i] = sum in[0..i), in place allowed; scratch holds scan_scratch_bytes(n) bytes
+size_t scan_scratch_bytes(long long n);
+int exclusive_scan_i32(const int* in, int* out, long long n, int* scratch, hipStream_t st);
+
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
 // Diagnostics (in-kernel phase stamps, kernel-variant selection by environment -- nothing that changes a result) exist only in

@@ -475,6 +475,11 @@ McLayout mc_layout(long long n) {
 
 }  // namespace
 
+namespace oai {     // the scan, for the other sources of the library (common.h)
+size_t scan_scratch_bytes(long long n) { return scan_scratch_ints(n) * 4; }
+int exclusive_scan_i32(const int* in, int* out, long long n, int* scratch, hipStream_t st) { return exclusive_scan(in, out, n, scratch, st); }
+}  // namespace oai
+
 extern "C" {
 
 int oai_mc_table(signed char* out_256x16) {

@@ -1,0 +1,665 @@
+// Atlas thickness map for gfx950: the step after get_thickness_mesh (SURVEY row L1').
+//
+// Replaces, on the device, the two calls FullDemo.ipynb makes after the per-point thickness (oai_analysis/mesh_processing.py:400-534):
+//   map_attributes(source, target)        vtkPointInterpolator + SetNullPointsStrategyToClosestPoint   -> oai_map_attributes(_grid)
+//   project_thickness(mapped, mesh_type)  FC: least-squares circle (scipy leastsq) + angle             -> oai_fit_circle + oai_project_circle
+//                                         TC: KernelPCA(linear) per plateau, rotations, flip, offset   -> oai_project_plateaus
+//
+// map_attributes restates VTK 9's defaults (vtk is not installed, so this half is unpinned): vtkLinearKernel (every point inside the
+// footprint weighs the same), the RADIUS footprint with Radius 1.0, NormalizeWeights on -> the plain mean over source points with
+// |p - q|^2 <= r^2; no point inside -> the closest source point's value (ties: the smallest index).  Sums are fp64 in a fixed order
+// (grid: cell by cell, each cell's list in ascending point index; brute force: ascending index), stored as float32.
+//
+// project_thickness: a linear-kernel PCA equals the PCA of the 3x3 scatter matrix, so each plateau needs O(n) work (three
+// deterministic fp64 reductions) and a 3x3 eigen-decomposition on the host instead of sklearn's n x n kernel matrix.  The sign of each
+// component follows sklearn's svd_flip(u): the point with the largest |score| gets a positive score (first index on a tie).
+//
+// Reductions are block partials (a fixed number of blocks, a fixed tree in LDS) plus one final block: no float atomics, the same bits
+// on every run.  Everything here is latency- or gather-bound VALU work; nothing is GEMM-shaped.
+#include "common.h"
+
+#include <cmath>
+#include <utility>
+
+namespace {
+
+constexpr int kT = 256;              // threads per block
+constexpr int kRedBlocks = 256;      // blocks of every reduction (the partials' layout depends on nothing but n)
+constexpr int kMaxComp = 4;          // point-array components interpolated per launch
+constexpr int kSrcTile = 512;        // brute force: source points staged in LDS per step
+constexpr float kSplitZ = 50.0f;     // project_thickness TC: plateaus split at z < 50 (raw coordinate units, :489-493)
+
+// fp64 squared distance of two float32 points, without contraction: the bits numpy gets from dx*dx + dy*dy + dz*dz
+__device__ __forceinline__ double dist2(const float* __restrict__ a, const float* __restrict__ b) {
+#pragma clang fp contract(off)
+    const double dx = (double)a[0] - (double)b[0], dy = (double)a[1] - (double)b[1], dz = (double)a[2] - (double)b[2];
+    return dx * dx + dy * dy + dz * dz;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// point binning: cells of size h >= radius, count -> scan -> scatter, then each cell's list ordered by point index
+// ---------------------------------------------------------------------------------------------------------------------
+struct GridD {
+    double lo[3];
+    double h, inv_h;
+    int n[3];
+};
+
+__device__ __forceinline__ int cell_of_coord(float p, double lo, double inv_h, int n) {
+    double t = floor(((double)p - lo) * inv_h);
+    t = t >= 0.0 ? t : 0.0;                        // (NaN lands in cell 0)
+    t = t <= (double)(n - 1) ? t : (double)(n - 1);
+    return (int)t;
+}
+
+__global__ void __launch_bounds__(kT) bin_count_kernel(const float* __restrict__ src, long long n, GridD g, int* __restrict__ cell_of,
+                                                       int* __restrict__ count) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    const int x = cell_of_coord(src[3 * i], g.lo[0], g.inv_h, g.n[0]), y = cell_of_coord(src[3 * i + 1], g.lo[1], g.inv_h, g.n[1]);
+    const int z = cell_of_coord(src[3 * i + 2], g.lo[2], g.inv_h, g.n[2]);
+    const int c = (z * g.n[1] + y) * g.n[0] + x;
+    cell_of[i] = c;
+    atomicAdd(&count[c], 1);
+}
+
+__global__ void __launch_bounds__(kT) bin_scatter_kernel(const int* __restrict__ cell_of, long long n, const int* __restrict__ start,
+                                                         int* __restrict__ cursor, int* __restrict__ unordered) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    const int c = cell_of[i];
+    unordered[start[c] + atomicAdd(&cursor[c], 1)] = (int)i;
+}
+
+// a point's rank in its cell = the number of cell members with a smaller index (the indices are distinct): O(cell size) per point
+__global__ void __launch_bounds__(kT) bin_order_kernel(const int* __restrict__ unordered, long long n, const int* __restrict__ cell_of,
+                                                       const int* __restrict__ start, int* __restrict__ list) {
+    const long long p = (long long)blockIdx.x * kT + threadIdx.x;
+    if (p >= n) return;
+    const int idx = unordered[p], c = cell_of[idx], s = start[c], e = start[c + 1];
+    int rank = 0;
+    for (int k = s; k < e; ++k) rank += unordered[k] < idx;
+    list[s + rank] = idx;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// interpolation: mean over the radius footprint, else the closest source point
+// ---------------------------------------------------------------------------------------------------------------------
+struct Interp {
+    const float* vals;        // [nc][n_src] (already offset to the first component of this launch)
+    long long n_src;
+    int nc;                   // <= kMaxComp
+    float* out;               // [nc][n_tgt]
+    long long n_tgt;
+};
+
+struct Acc {
+    double sum[kMaxComp];
+    int cnt;
+    double best;              // closest squared distance so far, its source index
+    int best_j;
+};
+
+__device__ __forceinline__ void acc_point(Acc& a, const Interp& ip, double d2, double r2, int j) {
+    if (d2 <= r2) {
+        ++a.cnt;
+#pragma unroll
+        for (int m = 0; m < kMaxComp; ++m)
+            if (m < ip.nc) a.sum[m] += (double)ip.vals[m * ip.n_src + j];
+    }
+    if (d2 < a.best || (d2 == a.best && j < a.best_j)) { a.best = d2; a.best_j = j; }
+}
+
+__device__ __forceinline__ void acc_store(const Acc& a, const Interp& ip, long long i) {
+#pragma unroll
+    for (int m = 0; m < kMaxComp; ++m) {
+        if (m >= ip.nc) break;
+        float v;
+        if (a.cnt > 0) v = (float)(a.sum[m] / (double)a.cnt);
+        else v = a.best_j >= 0 ? ip.vals[m * ip.n_src + a.best_j] : __int_as_float(0x7fc00000);     // no finite source point: NaN
+        ip.out[m * ip.n_tgt + i] = v;
+    }
+}
+
+__global__ void __launch_bounds__(kT) interp_grid_kernel(const float* __restrict__ src, const float* __restrict__ tgt, GridD g, double r2,
+                                                         const int* __restrict__ start, const int* __restrict__ list, Interp ip) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= ip.n_tgt) return;
+    const float q[3] = {tgt[3 * i], tgt[3 * i + 1], tgt[3 * i + 2]};
+    // a target outside the grid starts from the clamped cell: the cells hold every source point, and the distance from q to a point of
+    // the grid box is at least the distance from q's projection onto the box, so the ring bound below still holds
+    const int cx = cell_of_coord(q[0], g.lo[0], g.inv_h, g.n[0]), cy = cell_of_coord(q[1], g.lo[1], g.inv_h, g.n[1]);
+    const int cz = cell_of_coord(q[2], g.lo[2], g.inv_h, g.n[2]);
+    Acc a;
+#pragma unroll
+    for (int m = 0; m < kMaxComp; ++m) a.sum[m] = 0.0;
+    a.cnt = 0; a.best = INFINITY; a.best_j = -1;
+    auto visit = [&](int x, int y, int z) {
+        const int cell = (z * g.n[1] + y) * g.n[0] + x;
+        for (int k = start[cell]; k < start[cell + 1]; ++k) {
+            const int j = list[k];
+            acc_point(a, ip, dist2(src + 3 * (long long)j, q), r2, j);
+        }
+    };
+    // the footprint: h >= radius, so every source point within the radius lies in the 27 cells around q's (clamping keeps that)
+    for (int z = max(cz - 1, 0); z <= min(cz + 1, g.n[2] - 1); ++z)
+        for (int y = max(cy - 1, 0); y <= min(cy + 1, g.n[1] - 1); ++y)
+            for (int x = max(cx - 1, 0); x <= min(cx + 1, g.n[0] - 1); ++x) visit(x, y, z);
+    if (a.cnt == 0) {
+        // closest point: shells of Chebyshev radius r >= 2 around q's cell.  A point not visited after shell r-1 is at least (r-1) h
+        // away; stop once the best is strictly closer than that (strict: an unvisited point at exactly that distance could win the
+        // tie by a smaller index)
+        // for q outside the grid box, |q - s|^2 >= |q - Pq|^2 + |Pq - s|^2 for every s in the box (Pq: q's projection onto it)
+        double out2 = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            const double lo = g.lo[k], hi = g.lo[k] + g.n[k] * g.h, v = (double)q[k];
+            const double e = v < lo ? lo - v : (v > hi ? v - hi : 0.0);
+            out2 += e * e;
+        }
+        const int rmax = max(max(max(cx, g.n[0] - 1 - cx), max(cy, g.n[1] - 1 - cy)), max(cz, g.n[2] - 1 - cz));
+        for (int r = 2; r <= rmax; ++r) {
+            const double covered = (double)(r - 1) * g.h;
+            if (a.best < out2 + covered * covered) break;
+            const int z0 = max(cz - r, 0), z1 = min(cz + r, g.n[2] - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.n[1] - 1);
+            const int x0 = max(cx - r, 0), x1 = min(cx + r, g.n[0] - 1);
+            for (int z = z0; z <= z1; ++z)
+                for (int y = y0; y <= y1; ++y) {
+                    if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {      // a face of the shell: the whole row
+                        for (int x = x0; x <= x1; ++x) visit(x, y, z);
+                    } else {                                                             // otherwise only the two end cells
+                        if (cx - r >= 0) visit(cx - r, y, z);
+                        if (cx + r < g.n[0]) visit(cx + r, y, z);
+                    }
+                }
+        }
+    }
+    acc_store(a, ip, i);
+}
+
+// the same result without a grid (broad_phase=False): every source point, ascending index -- the library's cross-check
+__global__ void __launch_bounds__(kT) interp_brute_kernel(const float* __restrict__ src, const float* __restrict__ tgt, double r2, Interp ip) {
+    __shared__ float tile[kSrcTile * 3];
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    const bool live = i < ip.n_tgt;
+    const float q[3] = {live ? tgt[3 * i] : 0.f, live ? tgt[3 * i + 1] : 0.f, live ? tgt[3 * i + 2] : 0.f};
+    Acc a;
+#pragma unroll
+    for (int m = 0; m < kMaxComp; ++m) a.sum[m] = 0.0;
+    a.cnt = 0; a.best = INFINITY; a.best_j = -1;
+    for (long long j0 = 0; j0 < ip.n_src; j0 += kSrcTile) {
+        const int cnt = (int)(ip.n_src - j0 < kSrcTile ? ip.n_src - j0 : kSrcTile);
+        __syncthreads();
+        for (int k = threadIdx.x; k < 3 * cnt; k += kT) tile[k] = src[3 * j0 + k];
+        __syncthreads();
+        if (live)
+            for (int k = 0; k < cnt; ++k) acc_point(a, ip, dist2(tile + 3 * k, q), r2, (int)(j0 + k));
+    }
+    if (live) acc_store(a, ip, i);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// deterministic fp64 reductions: kRedBlocks partials (grid-stride in a fixed pattern, fixed LDS tree), then one block
+// ---------------------------------------------------------------------------------------------------------------------
+template <int K>
+__device__ __forceinline__ void block_sum_store(const double (&v)[K], double* __restrict__ dst) {
+    __shared__ double sh[K][kT];
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int s = kT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+#pragma unroll
+            for (int k = 0; k < K; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < K) dst[threadIdx.x] = sh[threadIdx.x][0];
+}
+
+template <int K>
+__global__ void __launch_bounds__(kT) final_sum_kernel(const double* __restrict__ partials, double* __restrict__ out) {
+    double v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = (int)threadIdx.x < kRedBlocks ? partials[threadIdx.x * K + k] : 0.0;
+    block_sum_store<K>(v, out);
+}
+
+// mask: 0 every point, 1 z < kSplitZ (left plateau), 2 z >= kSplitZ (right plateau); a NaN z is in neither half, as in the reference
+__device__ __forceinline__ bool selected(float z, int mask) { return mask == 0 || (mask == 1 ? z < kSplitZ : z >= kSplitZ); }
+
+// {count, sum d (3), sum d d^T (xx xy xz yy yz zz)} with d = p - ref over the masked points
+__global__ void __launch_bounds__(kT) moments_kernel(const float* __restrict__ pts, long long n, int mask, double r0, double r1, double r2,
+                                                     double* __restrict__ partials) {
+    double v[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) v[k] = 0.0;
+    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)kRedBlocks * kT) {
+        if (!selected(pts[3 * i + 2], mask)) continue;
+        const double dx = (double)pts[3 * i] - r0, dy = (double)pts[3 * i + 1] - r1, dz = (double)pts[3 * i + 2] - r2;
+        v[0] += 1.0; v[1] += dx; v[2] += dy; v[3] += dz;
+        v[4] += dx * dx; v[5] += dx * dy; v[6] += dx * dz; v[7] += dy * dy; v[8] += dy * dz; v[9] += dz * dz;
+    }
+    block_sum_store<10>(v, partials + blockIdx.x * 10);
+}
+
+// the nine sums of one circle-fit step at centre c: R_i = |c - p_i|, d_i = (c - p_i) / R_i over (x, y) = (p[col_x], p[col_y]):
+// {sum R, sum R^2, sum d (2), sum d d^T (xx xy yy), sum d R (2)}
+__global__ void __launch_bounds__(kT) circle_sums_kernel(const float* __restrict__ pts, long long n, int col_x, int col_y, double c0, double c1,
+                                                         double* __restrict__ partials) {
+    double v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = 0.0;
+    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)kRedBlocks * kT) {
+        const double dx = c0 - (double)pts[3 * i + col_x], dy = c1 - (double)pts[3 * i + col_y];
+        const double R = sqrt(dx * dx + dy * dy);
+        const double ux = dx / R, uy = dy / R;
+        v[0] += R; v[1] += R * R; v[2] += ux; v[3] += uy;
+        v[4] += ux * ux; v[5] += ux * uy; v[6] += uy * uy; v[7] += ux * R; v[8] += uy * R;
+    }
+    block_sum_store<9>(v, partials + blockIdx.x * 9);
+}
+
+// svd_flip(u): per component, the masked point with the largest |score| (first index on a tie) and its signed score
+struct Ext {
+    double a, v;
+    long long i;
+};
+
+__device__ __forceinline__ bool ext_better(const Ext& x, const Ext& y) { return x.a > y.a || (x.a == y.a && x.i < y.i); }
+
+struct Axes {
+    double mean[3];
+    double u[2][3];
+};
+
+__device__ __forceinline__ double score(const float* __restrict__ p, const Axes& ax, int k) {
+    return ax.u[k][0] * ((double)p[0] - ax.mean[0]) + ax.u[k][1] * ((double)p[1] - ax.mean[1]) + ax.u[k][2] * ((double)p[2] - ax.mean[2]);
+}
+
+__device__ __forceinline__ void block_ext_store(Ext (&e)[2], Ext* __restrict__ dst) {
+    __shared__ Ext sh[2][kT];
+    sh[0][threadIdx.x] = e[0];
+    sh[1][threadIdx.x] = e[1];
+    __syncthreads();
+    for (int s = kT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int k = 0; k < 2; ++k)
+                if (ext_better(sh[k][threadIdx.x + s], sh[k][threadIdx.x])) sh[k][threadIdx.x] = sh[k][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) dst[threadIdx.x] = sh[threadIdx.x][0];
+}
+
+__global__ void __launch_bounds__(kT) score_extreme_kernel(const float* __restrict__ pts, long long n, int mask, Axes ax, Ext* __restrict__ partials) {
+    Ext e[2] = {{-1.0, 0.0, (long long)1 << 62}, {-1.0, 0.0, (long long)1 << 62}};
+    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)kRedBlocks * kT) {
+        if (!selected(pts[3 * i + 2], mask)) continue;
+        for (int k = 0; k < 2; ++k) {
+            const double s = score(pts + 3 * i, ax, k);
+            const Ext c = {fabs(s), s, i};
+            if (ext_better(c, e[k])) e[k] = c;
+        }
+    }
+    block_ext_store(e, partials + blockIdx.x * 2);
+}
+
+__global__ void __launch_bounds__(kT) final_ext_kernel(const Ext* __restrict__ partials, Ext* __restrict__ out) {
+    Ext e[2];
+    for (int k = 0; k < 2; ++k) e[k] = (int)threadIdx.x < kRedBlocks ? partials[threadIdx.x * 2 + k] : Ext{-1.0, 0.0, (long long)1 << 62};
+    block_ext_store(e, out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// per-point projections (fp64)
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kT) circle_project_kernel(const float* __restrict__ pts, long long n, int col_x, int col_y, double c0, double c1,
+                                                            double* __restrict__ angle, double* __restrict__ z) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    angle[i] = atan2((double)pts[3 * i + col_y] - c1, (double)pts[3 * i + col_x] - c0);
+    z[i] = (double)pts[3 * i + 2];
+}
+
+__global__ void __launch_bounds__(kT) half_flags_kernel(const float* __restrict__ pts, long long n, int* __restrict__ right, int* __restrict__ left) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i > n) return;
+    const float z = i < n ? pts[3 * i + 2] : NAN;       // element n: 0 in both, so that the scans end on the totals
+    right[i] = z >= kSplitZ;
+    left[i] = z < kSplitZ;
+}
+
+// a plateau's map: scores on its two (sign-fixed) axes, then (s0, s1) @ [[c, -s], [s, c]], x scaled by fx, oy added to y
+struct HalfMap {
+    Axes ax;
+    double c, s, fx, oy;
+};
+
+__global__ void __launch_bounds__(kT) plateau_project_kernel(const float* __restrict__ pts, const float* __restrict__ vals, long long n,
+                                                             HalfMap right, HalfMap left, const int* __restrict__ off_right,
+                                                             const int* __restrict__ off_left, long long n_right, double* __restrict__ ox,
+                                                             double* __restrict__ oy, double* __restrict__ ov) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    const float z = pts[3 * i + 2];
+    long long slot;
+    const HalfMap* m;
+    if (z >= kSplitZ) { slot = off_right[i]; m = &right; }                   // output: the right plateau first, then the left one
+    else if (z < kSplitZ) { slot = n_right + off_left[i]; m = &left; }
+    else return;
+    const double s0 = score(pts + 3 * i, m->ax, 0), s1 = score(pts + 3 * i, m->ax, 1);
+    ox[slot] = m->fx * (s0 * m->c + s1 * m->s);
+    oy[slot] = (-s0 * m->s + s1 * m->c) + m->oy;
+    ov[slot] = (double)vals[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+struct PointGridLayout { size_t cell_of, count, start, unordered, list, scratch, total; };
+PointGridLayout point_grid_layout(long long ncells, long long n_src) {
+    PointGridLayout l;
+    size_t o = 0;
+    l.cell_of = o; o += al256((size_t)n_src * 4);
+    l.count = o; o += al256((size_t)(ncells + 1) * 4);
+    l.start = o; o += al256((size_t)(ncells + 1) * 4);
+    l.unordered = o; o += al256((size_t)n_src * 4);
+    l.list = o; o += al256((size_t)n_src * 4);
+    l.scratch = o; o += al256(oai::scan_scratch_bytes(ncells + 1));
+    l.total = o;
+    return l;
+}
+
+struct MapLayout { size_t partials, sums, ext_partials, ext, right, left, off_right, off_left, scratch, total; };
+MapLayout map_layout(long long n) {
+    MapLayout l;
+    size_t o = 0;
+    l.partials = o; o += al256(kRedBlocks * 16 * sizeof(double));
+    l.sums = o; o += al256(16 * sizeof(double));
+    l.ext_partials = o; o += al256(kRedBlocks * 2 * sizeof(Ext));
+    l.ext = o; o += al256(2 * sizeof(Ext));
+    l.right = o; o += al256((size_t)(n + 1) * 4);
+    l.left = o; o += al256((size_t)(n + 1) * 4);
+    l.off_right = o; o += al256((size_t)(n + 1) * 4);
+    l.off_left = o; o += al256((size_t)(n + 1) * 4);
+    l.scratch = o; o += al256(oai::scan_scratch_bytes(n + 1));
+    l.total = o;
+    return l;
+}
+
+int launch_interp(bool grid, const float* src, long long n_src, const float* vals, int n_comp, const float* tgt, long long n_tgt, double radius,
+                  const GridD& g, const int* start, const int* list, float* out, hipStream_t st) {
+    const double r2 = radius * radius;
+    for (int c0 = 0; c0 < n_comp; c0 += kMaxComp) {
+        Interp ip{vals + (long long)c0 * n_src, n_src, n_comp - c0 < kMaxComp ? n_comp - c0 : kMaxComp, out + (long long)c0 * n_tgt, n_tgt};
+        if (grid) interp_grid_kernel<<<oai::cdiv(n_tgt, kT), kT, 0, st>>>(src, tgt, g, r2, start, list, ip);
+        else interp_brute_kernel<<<oai::cdiv(n_tgt, kT), kT, 0, st>>>(src, tgt, r2, ip);
+        OAI_CHECK_LAUNCH();
+    }
+    return OAI_OK;
+}
+
+// the reductions' results come back to the host: these calls synchronise the stream
+int read_sums(double* dev, double* host, int k, hipStream_t st) {
+    OAI_CHECK_HIP(hipMemcpyAsync(host, dev, k * sizeof(double), hipMemcpyDeviceToHost, st));
+    OAI_CHECK_HIP(hipStreamSynchronize(st));
+    return OAI_OK;
+}
+
+int moments(const float* pts, long long n, int mask, const double ref[3], const MapLayout& l, char* ws, double out[10], hipStream_t st) {
+    moments_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, mask, ref[0], ref[1], ref[2], (double*)(ws + l.partials));
+    OAI_CHECK_LAUNCH();
+    final_sum_kernel<10><<<1, kT, 0, st>>>((const double*)(ws + l.partials), (double*)(ws + l.sums));
+    OAI_CHECK_LAUNCH();
+    return read_sums((double*)(ws + l.sums), out, 10, st);
+}
+
+int circle_sums(const float* pts, long long n, int cx, int cy, const double c[2], const MapLayout& l, char* ws, double out[9], hipStream_t st) {
+    circle_sums_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, cx, cy, c[0], c[1], (double*)(ws + l.partials));
+    OAI_CHECK_LAUNCH();
+    final_sum_kernel<9><<<1, kT, 0, st>>>((const double*)(ws + l.partials), (double*)(ws + l.sums));
+    OAI_CHECK_LAUNCH();
+    return read_sums((double*)(ws + l.sums), out, 9, st);
+}
+
+// eigen-decomposition of a symmetric 3x3 matrix (cyclic Jacobi); columns of V are the eigenvectors, w descending
+void eig_sym3(const double S[3][3], double w[3], double V[3][3]) {
+    double A[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { A[i][j] = S[i][j]; V[i][j] = i == j; }
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+        const double diag = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+        if (off == 0.0 || off <= 1e-36 * diag) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (A[p][q] == 0.0) continue;
+                const double th = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+                const double t = (th >= 0.0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; ++k) {          // A <- A J
+                    const double akp = A[k][p], akq = A[k][q];
+                    A[k][p] = c * akp - s * akq;
+                    A[k][q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < 3; ++k) {          // A <- J^T A
+                    const double apk = A[p][k], aqk = A[q][k];
+                    A[p][k] = c * apk - s * aqk;
+                    A[q][k] = s * apk + c * aqk;
+                }
+                for (int k = 0; k < 3; ++k) {          // V <- V J
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = c * vkp - s * vkq;
+                    V[k][q] = s * vkp + c * vkq;
+                }
+            }
+    }
+    int order[3] = {0, 1, 2};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (A[order[j]][order[j]] > A[order[i]][order[i]]) std::swap(order[i], order[j]);
+    double W[3][3];
+    for (int k = 0; k < 3; ++k) {
+        w[k] = A[order[k]][order[k]];
+        for (int i = 0; i < 3; ++i) W[i][k] = V[i][order[k]];
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) V[i][j] = W[i][j];
+}
+
+// one plateau: mean, centred scatter, top-2 axes, svd_flip signs, then the rotation (degrees), x scale and y offset of :507-520
+int plateau_map(const float* pts, long long n, int mask, double angle_deg, double fx, double oy, const MapLayout& l, char* ws, HalfMap* m,
+                long long* count, hipStream_t st) {
+    const double zero[3] = {0.0, 0.0, 0.0};
+    double s1[10], s2[10];
+    if (int rc = moments(pts, n, mask, zero, l, ws, s1, st)) return rc;
+    const double cnt = s1[0];
+    *count = (long long)cnt;
+    if (*count == 0) return OAI_OK;
+    const double mean[3] = {s1[1] / cnt, s1[2] / cnt, s1[3] / cnt};
+    if (int rc = moments(pts, n, mask, mean, l, ws, s2, st)) return rc;            // second pass about the mean (no cancellation)
+    const double d[3] = {s2[1], s2[2], s2[3]};
+    const int ij[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    double S[3][3];
+    for (int k = 0; k < 6; ++k) {
+        const int i = ij[k][0], j = ij[k][1];
+        S[i][j] = S[j][i] = s2[4 + k] - d[i] * d[j] / cnt;
+    }
+    double w[3], V[3][3];
+    eig_sym3(S, w, V);
+    Axes ax;
+    for (int k = 0; k < 3; ++k) ax.mean[k] = mean[k];
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < 3; ++k) ax.u[c][k] = V[k][c];
+    score_extreme_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, mask, ax, (Ext*)(ws + l.ext_partials));
+    OAI_CHECK_LAUNCH();
+    final_ext_kernel<<<1, kT, 0, st>>>((const Ext*)(ws + l.ext_partials), (Ext*)(ws + l.ext));
+    OAI_CHECK_LAUNCH();
+    Ext e[2];
+    OAI_CHECK_HIP(hipMemcpyAsync(e, ws + l.ext, sizeof(e), hipMemcpyDeviceToHost, st));
+    OAI_CHECK_HIP(hipStreamSynchronize(st));
+    for (int c = 0; c < 2; ++c)
+        if (e[c].v < 0.0)
+            for (int k = 0; k < 3; ++k) ax.u[c][k] = -ax.u[c][k];
+    const double theta = (angle_deg / 180.0) * M_PI;
+    m->ax = ax;
+    m->c = std::cos(theta);
+    m->s = std::sin(theta);
+    m->fx = fx;
+    m->oy = oy;
+    return OAI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t oai_point_grid_workspace_bytes(const int grid_dims_xyz[3], long long n_src) {
+    if (!grid_dims_xyz || n_src <= 0 || grid_dims_xyz[0] <= 0 || grid_dims_xyz[1] <= 0 || grid_dims_xyz[2] <= 0) return 0;
+    return point_grid_layout((long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2], n_src).total;
+}
+
+int oai_map_attributes(const float* src_pts_dev, long long n_src, const float* src_vals_dev, int n_comp, const float* tgt_pts_dev,
+                       long long n_tgt, double radius, float* out_vals_dev, void* stream) {
+    OAI_CHECK_ARG(src_pts_dev && src_vals_dev && tgt_pts_dev && out_vals_dev, "oai_map_attributes: null pointer");
+    OAI_CHECK_ARG(n_src > 0 && n_src < (1LL << 31), "oai_map_attributes: needs 1 .. 2^31-1 source points (got %lld)", n_src);
+    OAI_CHECK_ARG(n_tgt >= 0 && n_comp >= 1, "oai_map_attributes: negative target count or no point array");
+    OAI_CHECK_ARG(radius >= 0.0 && std::isfinite(radius), "oai_map_attributes: radius must be finite and >= 0");
+    if (n_tgt == 0) return OAI_OK;
+    return launch_interp(false, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, GridD{}, nullptr, nullptr, out_vals_dev,
+                         (hipStream_t)stream);
+}
+
+int oai_map_attributes_grid(const float* src_pts_dev, long long n_src, const float* src_vals_dev, int n_comp, const float* tgt_pts_dev,
+                            long long n_tgt, double radius, const double grid_lo_xyz[3], double cell_size, const int grid_dims_xyz[3],
+                            void* workspace_dev, size_t workspace_bytes, float* out_vals_dev, void* stream) {
+    OAI_CHECK_ARG(src_pts_dev && src_vals_dev && tgt_pts_dev && out_vals_dev && grid_lo_xyz && grid_dims_xyz && workspace_dev,
+                  "oai_map_attributes_grid: null pointer");
+    OAI_CHECK_ARG(n_src > 0 && n_src < (1LL << 31), "oai_map_attributes_grid: needs 1 .. 2^31-1 source points (got %lld)", n_src);
+    OAI_CHECK_ARG(n_tgt >= 0 && n_comp >= 1, "oai_map_attributes_grid: negative target count or no point array");
+    OAI_CHECK_ARG(radius >= 0.0 && std::isfinite(radius), "oai_map_attributes_grid: radius must be finite and >= 0");
+    OAI_CHECK_ARG(cell_size > 0.0 && cell_size >= radius && std::isfinite(cell_size), "oai_map_attributes_grid: cell_size %g must be >= radius %g and > 0",
+                  cell_size, radius);
+    OAI_CHECK_ARG(grid_dims_xyz[0] > 0 && grid_dims_xyz[1] > 0 && grid_dims_xyz[2] > 0, "oai_map_attributes_grid: empty grid");
+    const long long ncells = (long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2];
+    OAI_CHECK_ARG(ncells < (1LL << 30), "oai_map_attributes_grid: grid too fine");
+    const PointGridLayout l = point_grid_layout(ncells, n_src);
+    if (workspace_bytes < l.total)
+        return oai::set_error(OAI_ERR_WORKSPACE, "oai_map_attributes_grid: workspace %zu B < %zu B", workspace_bytes, l.total);
+    if (n_tgt == 0) return OAI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace_dev;
+    int* cell_of = (int*)(ws + l.cell_of); int* count = (int*)(ws + l.count); int* start = (int*)(ws + l.start);
+    int* unordered = (int*)(ws + l.unordered); int* list = (int*)(ws + l.list);
+    GridD g;
+    for (int k = 0; k < 3; ++k) { g.lo[k] = grid_lo_xyz[k]; g.n[k] = grid_dims_xyz[k]; }
+    g.h = cell_size; g.inv_h = 1.0 / cell_size;
+    OAI_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)(ncells + 1) * 4, st));
+    bin_count_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(src_pts_dev, n_src, g, cell_of, count);
+    OAI_CHECK_LAUNCH();
+    if (int rc = oai::exclusive_scan_i32(count, start, ncells + 1, (int*)(ws + l.scratch), st)) return rc;
+    OAI_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)(ncells + 1) * 4, st));
+    bin_scatter_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(cell_of, n_src, start, count, unordered);
+    OAI_CHECK_LAUNCH();
+    bin_order_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(unordered, n_src, cell_of, start, list);
+    OAI_CHECK_LAUNCH();
+    return launch_interp(true, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, g, start, list, out_vals_dev, st);
+}
+
+size_t oai_thickness_map_workspace_bytes(long long n_points) {
+    if (n_points <= 0) return 0;
+    return map_layout(n_points).total;
+}
+
+int oai_fit_circle(const float* pts_dev, long long n, int col_x, int col_y, void* workspace_dev, size_t workspace_bytes, double centre_host[2],
+                   double* radius_host, int* iterations_host, void* stream) {
+    OAI_CHECK_ARG(pts_dev && workspace_dev && centre_host && radius_host, "oai_fit_circle: null pointer");
+    OAI_CHECK_ARG(n >= 3, "oai_fit_circle: needs at least 3 points (got %lld)", n);
+    OAI_CHECK_ARG(col_x >= 0 && col_x < 3 && col_y >= 0 && col_y < 3 && col_x != col_y, "oai_fit_circle: columns must be two distinct of 0, 1, 2");
+    const MapLayout l = map_layout(n);
+    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_fit_circle: workspace %zu B < %zu B", workspace_bytes, l.total);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace_dev;
+    // start at the centroid, as compute_least_square_circle does
+    const double zero[3] = {0.0, 0.0, 0.0};
+    double m[10];
+    if (int rc = moments(pts_dev, n, 0, zero, l, ws, m, st)) return rc;
+    double c[2] = {m[1 + col_x] / m[0], m[1 + col_y] / m[0]};
+    const double nn = (double)n;
+    double S[9];
+    if (int rc = circle_sums(pts_dev, n, col_x, col_y, c, l, ws, S, st)) return rc;
+    const double extent = std::sqrt(S[1] / nn);                              // rms distance of the points from their centroid
+    auto cost_of = [nn](const double* s) { return s[1] - s[0] * s[0] / nn; };  // sum (R_i - mean R)^2
+    double cost = cost_of(S);
+    int it = 0;
+    for (; it < 100; ++it) {
+        // Gauss-Newton on f_i = R_i - mean R, J_i = d_i - mean d (the reference's centred Jacobian Df_2b):
+        // J^T J = sum d d^T - n dbar dbar^T,  J^T f = sum d R - n dbar Rbar
+        const double db0 = S[2] / nn, db1 = S[3] / nn, rb = S[0] / nn;
+        const double a00 = S[4] - nn * db0 * db0, a01 = S[5] - nn * db0 * db1, a11 = S[6] - nn * db1 * db1;
+        const double g0 = S[7] - nn * db0 * rb, g1 = S[8] - nn * db1 * rb;
+        const double det = a00 * a11 - a01 * a01;
+        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) break;
+        double step[2] = {-(a11 * g0 - a01 * g1) / det, -(a00 * g1 - a01 * g0) / det};
+        bool accepted = false;
+        double cn[2], Sn[9];
+        for (int half = 0; half < 40; ++half) {                              // step halving keeps the cost from rising
+            cn[0] = c[0] + step[0];
+            cn[1] = c[1] + step[1];
+            if (int rc = circle_sums(pts_dev, n, col_x, col_y, cn, l, ws, Sn, st)) return rc;
+            if (cost_of(Sn) <= cost) { accepted = true; break; }
+            step[0] *= 0.5;
+            step[1] *= 0.5;
+        }
+        if (!accepted) break;
+        c[0] = cn[0]; c[1] = cn[1];
+        for (int k = 0; k < 9; ++k) S[k] = Sn[k];
+        cost = cost_of(S);
+        if (std::hypot(step[0], step[1]) <= 1e-12 * extent) { ++it; break; }
+    }
+    centre_host[0] = c[0];
+    centre_host[1] = c[1];
+    *radius_host = S[0] / nn;
+    if (iterations_host) *iterations_host = it;
+    return OAI_OK;
+}
+
+int oai_project_circle(const float* pts_dev, long long n, int col_x, int col_y, const double centre_host[2], double* angle_dev, double* z_dev,
+                       void* stream) {
+    OAI_CHECK_ARG(pts_dev && centre_host && angle_dev && z_dev, "oai_project_circle: null pointer");
+    OAI_CHECK_ARG(n >= 0, "oai_project_circle: negative size");
+    OAI_CHECK_ARG(col_x >= 0 && col_x < 3 && col_y >= 0 && col_y < 3 && col_x != col_y, "oai_project_circle: columns must be two distinct of 0, 1, 2");
+    if (n == 0) return OAI_OK;
+    circle_project_kernel<<<oai::cdiv(n, kT), kT, 0, (hipStream_t)stream>>>(pts_dev, n, col_x, col_y, centre_host[0], centre_host[1], angle_dev, z_dev);
+    OAI_CHECK_LAUNCH();
+    return OAI_OK;
+}
+
+int oai_project_plateaus(const float* pts_dev, const float* thickness_dev, long long n, void* workspace_dev, size_t workspace_bytes,
+                         double* x_dev, double* y_dev, double* thickness_out_dev, long long* n_right_host, long long* n_left_host, void* stream) {
+    OAI_CHECK_ARG(pts_dev && thickness_dev && workspace_dev && x_dev && y_dev && thickness_out_dev && n_right_host && n_left_host,
+                  "oai_project_plateaus: null pointer");
+    OAI_CHECK_ARG(n > 0 && n < (1LL << 31), "oai_project_plateaus: needs 1 .. 2^31-1 points (got %lld)", n);
+    const MapLayout l = map_layout(n);
+    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_project_plateaus: workspace %zu B < %zu B", workspace_bytes, l.total);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace_dev;
+    HalfMap right, left;
+    if (int rc = plateau_map(pts_dev, n, 2, -160.0, -1.0, 50.0, l, ws, &right, n_right_host, st)) return rc;
+    if (int rc = plateau_map(pts_dev, n, 1, -50.0, 1.0, 0.0, l, ws, &left, n_left_host, st)) return rc;
+    if (*n_right_host == 0 || *n_left_host == 0)
+        return oai::set_error(OAI_ERR_ARG, "oai_project_plateaus: the %s plateau is empty (no point with z %s 50)", *n_right_host == 0 ? "right" : "left",
+                              *n_right_host == 0 ? ">=" : "<");
+    int* fr = (int*)(ws + l.right); int* fl = (int*)(ws + l.left);
+    int* orr = (int*)(ws + l.off_right); int* ol = (int*)(ws + l.off_left);
+    half_flags_kernel<<<oai::cdiv(n + 1, kT), kT, 0, st>>>(pts_dev, n, fr, fl);
+    OAI_CHECK_LAUNCH();
+    if (int rc = oai::exclusive_scan_i32(fr, orr, n + 1, (int*)(ws + l.scratch), st)) return rc;
+    if (int rc = oai::exclusive_scan_i32(fl, ol, n + 1, (int*)(ws + l.scratch), st)) return rc;
+    plateau_project_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(pts_dev, thickness_dev, n, right, left, orr, ol, *n_right_host, x_dev, y_dev,
+                                                            thickness_out_dev);
+    OAI_CHECK_LAUNCH();
+    return OAI_OK;
+}
+
+}  // extern "C"

@@ -8,13 +8,21 @@ Reference functions mirrored (same names, argument meaning and return roles):
     get_distance(inner_mesh, outer_mesh)               :310-322   closest-point distance, both directions
     get_thickness_mesh(itk_image, mesh_type, ...)      :381-395
     get_cell_centroid / get_cell_normals               :26-46
+    map_attributes(source_mesh, target_mesh)           :400-408   vtkPointInterpolator (radius mean, closest-point fallback)
+    compute_least_square_circle(x, y)                  :411-447   circle fit (scipy leastsq in the reference)
+    get_cylinder(vertice)                              :450-455
+    get_projection_from_circle_and_vertice(v, circle)  :459-478
+    project_thickness(mapped_mesh, mesh_type="FC")     :483-534   2-D atlas thickness map (FC: cylinder angle; TC: plateau PCA)
 
 vtk / trimesh / skimage are not installed here, so meshes are ``Mesh`` objects (float32 vertices [n,3] in (x,y,z)*spacing,
 int32 faces [m,3], per-point data) instead of ``vtkPolyData``; ``Mesh.to_vtk()`` adapts when vtk imports.  The three heavy
 steps run in HIP kernels behind the C ABI (oai_mc_*, oai_mesh_smooth, oai_mesh_point_distance; csrc/mesh.hip); the edge
 graph, the connected-component filter (> 3000 cells, :119-137) and the KMeans split are host logic exactly as in the
 reference (sklearn is the reference's own dependency).  Parity is unpinned: see oracle/mesh.py for what is
-restated.  There is no CPU fallback for the kernels.
+restated.  The atlas thickness map runs in csrc/thickness_map.hip (oai_map_attributes*, oai_fit_circle, oai_project_circle,
+oai_project_plateaus): project_thickness and its circle helpers are pinned against the reference's own functions
+(tests/golden/thickness_projection.npz); map_attributes restates vtkPointInterpolator's defaults and is unpinned.  There is no CPU
+fallback for the kernels.
 """
 from __future__ import annotations
 
@@ -270,3 +278,160 @@ def get_thickness_mesh(itk_image, mesh_type: str = "FC", num_iterations: int = 1
     mesh = get_mesh(itk_image, num_iterations=150, min_cells=min_cells)
     inner, outer = split_mesh(mesh, mesh_type)
     return get_distance(inner, outer)
+
+
+# ---- atlas thickness map (mesh_processing.py:400-534) ----------------------------------------------------------------------------
+def _point_arrays(mesh: Mesh) -> Tuple[list, np.ndarray]:
+    """The mesh's point arrays as float32 component rows [n_comp][n] and (name, shape) of each array."""
+    n = len(mesh.verts)
+    names, rows = [], []
+    for name, arr in mesh.point_data.items():
+        a = np.asarray(arr)
+        if a.shape[:1] != (n,):
+            raise ValueError(f"point array {name!r} has shape {a.shape}, the mesh has {n} points")
+        names.append((name, a.shape))
+        rows.append(a.reshape(n, -1).T.astype(np.float32))
+    return names, (np.concatenate(rows, axis=0) if rows else np.zeros((0, n), np.float32))
+
+
+def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, broad_phase: bool = True) -> Mesh:
+    """mesh_processing.py:400-408: vtkPointInterpolator(SetNullPointsStrategyToClosestPoint), source arrays onto target points.
+
+    Restated from VTK 9's documented defaults (vtk is not installed here; this half of the step is unpinned): vtkLinearKernel,
+    the RADIUS footprint, Radius = 1.0, NormalizeWeights on.  For each target point, every source point array takes the unweighted
+    mean over the source points with ``|p - q|^2 <= radius^2``; with no source point that close, the value of the closest source
+    point (ties: the smallest index).  Sums are fp64, results float32 (as get_distance).  The output has the target's verts, faces
+    and point data plus the interpolated source arrays; on a name clash the source array wins.  ``broad_phase``: bin the source
+    points into a uniform grid (cells >= radius, at most 512 per axis); False = brute force over every source point (same result).
+    """
+    lib = _lib.load()
+    if len(source_mesh.verts) == 0:
+        raise ValueError("map_attributes: the source mesh has no points")
+    names, vals = _point_arrays(source_mesh)
+    out_data = dict(target_mesh.point_data)
+    n_tgt, n_src, n_comp = len(target_mesh.verts), len(source_mesh.verts), vals.shape[0]
+    if n_comp == 0:
+        return Mesh(target_mesh.verts, target_mesh.faces, out_data)
+    s, v, t = _dev(source_mesh.verts, np.float32), _dev(vals, np.float32), _dev(target_mesh.verts.reshape(-1, 3), np.float32)
+    out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=s.device)
+    with torch.cuda.device(s.device):
+        if broad_phase:
+            lo = source_mesh.verts.min(axis=0).astype(np.float64)
+            hi = source_mesh.verts.max(axis=0).astype(np.float64)
+            h = max(float(radius) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)          # at most 512 cells per axis
+            dims = np.maximum(np.ceil((hi - lo) / h).astype(np.int64) + 1, 1)
+            glo = (C.c_double * 3)(*[float(x) for x in lo - 0.5 * h * 1e-3])
+            gd = (C.c_int * 3)(*[int(x) for x in dims])
+            ws = torch.empty(int(lib.oai_point_grid_workspace_bytes(gd, n_src)), dtype=torch.uint8, device=s.device)
+            _lib.check(lib.oai_map_attributes_grid(s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), glo, float(h), gd,
+                                                   ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "oai_map_attributes_grid")
+        else:
+            _lib.check(lib.oai_map_attributes(s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr(), _stream()),
+                       "oai_map_attributes")
+    res = out.cpu().numpy()
+    row = 0
+    for name, shape in names:
+        k = int(np.prod(shape[1:], dtype=np.int64))
+        out_data[name] = res[row:row + k].T.reshape((n_tgt,) + tuple(shape[1:]))
+        row += k
+    return Mesh(target_mesh.verts, target_mesh.faces, out_data)
+
+
+def _fit_circle_dev(pts: torch.Tensor, col_x: int, col_y: int) -> Tuple[np.ndarray, float]:
+    lib = _lib.load()
+    n = int(pts.shape[0])
+    ws = torch.empty(max(int(lib.oai_thickness_map_workspace_bytes(n)), 1), dtype=torch.uint8, device=pts.device)
+    centre, radius, its = (C.c_double * 2)(), C.c_double(), C.c_int()
+    with torch.cuda.device(pts.device):
+        _lib.check(lib.oai_fit_circle(pts.data_ptr(), n, col_x, col_y, ws.data_ptr(), ws.numel(), centre, C.byref(radius), C.byref(its), _stream()),
+                   "oai_fit_circle")
+    return np.array([centre[0], centre[1]], dtype=np.float64), float(radius.value)
+
+
+def compute_least_square_circle(x, y) -> Tuple[np.ndarray, float]:
+    """mesh_processing.py:411-447: the centre minimising sum (R_i - mean R)^2 and the mean radius R = mean R_i.
+
+    The reference runs scipy leastsq with the centred Jacobian from the centroid; this is Gauss-Newton with step halving on the
+    2x2 normal equations from the centroid, fp64 sums on the device (the points are taken as float32, the mesh's precision).
+    Returns (centre float64 [2], R float64)."""
+    x, y = np.asarray(x).reshape(-1), np.asarray(y).reshape(-1)
+    if x.shape != y.shape:
+        raise ValueError("compute_least_square_circle: x and y differ in length")
+    pts = np.zeros((len(x), 3), np.float32)
+    pts[:, 0], pts[:, 1] = x, y
+    centre, r = _fit_circle_dev(_dev(pts, np.float32), 0, 1)
+    return centre, np.float64(r)
+
+
+def get_cylinder(vertice):
+    """mesh_processing.py:450-455: ((centre, r), (z_min, z_max)) of the circle fitted to columns 0 and 1."""
+    v = np.asarray(vertice)
+    centre, r = compute_least_square_circle(v[:, 0], v[:, 1])
+    return (centre, r), (np.min(v[:, 2]), np.max(v[:, 2]))
+
+
+def _project_circle_dev(pts: torch.Tensor, col_x: int, col_y: int, centre) -> Tuple[np.ndarray, np.ndarray]:
+    lib = _lib.load()
+    n = int(pts.shape[0])
+    angle = torch.empty(n, dtype=torch.float64, device=pts.device)
+    z = torch.empty(n, dtype=torch.float64, device=pts.device)
+    c = (C.c_double * 2)(float(centre[0]), float(centre[1]))
+    with torch.cuda.device(pts.device):
+        _lib.check(lib.oai_project_circle(pts.data_ptr(), n, col_x, col_y, c, angle.data_ptr(), z.data_ptr(), _stream()), "oai_project_circle")
+    return angle.cpu().numpy(), z.cpu().numpy()
+
+
+def get_projection_from_circle_and_vertice(vertice, circle) -> Tuple[np.ndarray, np.ndarray]:
+    """mesh_processing.py:459-478: embedded [n,2] = (atan2(y - c_y, x - c_x), z) (computed on the device in fp64) and plot_xy [n,2],
+    the angle in degrees rescaled to 1.5 x the z range (host)."""
+    v = np.asarray(vertice)
+    centre, _ = circle
+    angle, z = _project_circle_dev(_dev(v, np.float32), 0, 1, centre)
+    embedded = np.stack([angle, z], axis=1)
+    deg = angle / np.pi * 180
+    zz = v[:, 2]
+    deg = (deg - np.min(deg)) / (np.max(deg) - np.min(deg))
+    plot_xy = np.zeros_like(embedded)
+    plot_xy[:, 0] = deg * (np.max(zz) - np.min(zz)) * 1.5 + np.min(zz)
+    plot_xy[:, 1] = zz
+    return embedded, plot_xy
+
+
+def project_thickness(mapped_mesh: Mesh, mesh_type: str = "FC", embedded=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """mesh_processing.py:483-534: the 2-D thickness map of a mesh mapped to the atlas.  Returns float64 (x, y, thickness).
+
+    The thickness is ``point_data["Distance"]``, else the mesh's only point array.  ``embedded`` is unused, as in the reference.
+    FC: columns x and y swapped, circle fitted (compute_least_square_circle); x = atan2(y - c_y, x - c_x), y = z, thickness in point
+    order.  TC: plateaus split at z < 50 (raw units); per plateau the centred scores on the top-2 axes of its 3x3 scatter matrix
+    (equal to the reference's KernelPCA(n_components=2), linear kernel, which builds an n x n kernel matrix), each axis signed as
+    sklearn's svd_flip(u) does (the point with the largest |score| scores positive, first index on a tie); the left plateau rotated
+    by -50 degrees, the right one by -160 degrees with x negated and 50 added to y; the right plateau's points first.  An empty
+    plateau raises ValueError (the reference crashes there)."""
+    lib = _lib.load()
+    if "Distance" in mapped_mesh.point_data:
+        thickness = np.asarray(mapped_mesh.point_data["Distance"])
+    elif len(mapped_mesh.point_data) == 1:
+        thickness = np.asarray(next(iter(mapped_mesh.point_data.values())))
+    else:
+        raise ValueError(f"project_thickness: no 'Distance' array and not exactly one point array ({sorted(mapped_mesh.point_data)})")
+    verts = np.asarray(mapped_mesh.verts)
+    n = len(verts)
+    if thickness.shape != (n,):
+        raise ValueError(f"project_thickness: the thickness has shape {thickness.shape}, the mesh has {n} points")
+    pts = _dev(verts, np.float32)
+    if mesh_type == "FC":
+        centre, _ = _fit_circle_dev(pts, 1, 0)                        # vertices[:, [1, 0]] = vertices[:, [0, 1]]
+        angle, z = _project_circle_dev(pts, 1, 0, centre)
+        return angle, z, thickness.astype(np.float64)
+    z = verts[:, 2].astype(np.float32)
+    if not (z >= 50).any() or not (z < 50).any():
+        raise ValueError("project_thickness(TC): one tibial plateau is empty (no point with z < 50 or none with z >= 50)")
+    th = _dev(thickness, np.float32)
+    ws = torch.empty(int(lib.oai_thickness_map_workspace_bytes(n)), dtype=torch.uint8, device=pts.device)
+    out = torch.empty((3, n), dtype=torch.float64, device=pts.device)
+    n_right, n_left = C.c_longlong(), C.c_longlong()
+    with torch.cuda.device(pts.device):
+        _lib.check(lib.oai_project_plateaus(pts.data_ptr(), th.data_ptr(), n, ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(),
+                                            out[2].data_ptr(), C.byref(n_right), C.byref(n_left), _stream()), "oai_project_plateaus")
+    res = out[:, :n_right.value + n_left.value].cpu().numpy()
+    return res[0].copy(), res[1].copy(), res[2].copy()
