@@ -479,6 +479,39 @@ int oai_project_circle(const float* pts_dev, long long n, int col_x, int col_y, 
 int oai_project_plateaus(const float* pts_dev, const float* thickness_dev, long long n, void* workspace_dev, size_t workspace_bytes,
                          double* x_dev, double* y_dev, double* thickness_out_dev, long long* n_right_host, long long* n_left_host, void* stream);
 
+/* ---- inner / outer split of a cartilage surface (mesh_processing.py:197-294, 353-378; csrc/mesh_split.hip) ----
+ * KMeans(n_clusters=2, algorithm="lloyd") of scikit-learn >= 1.4 restated in fp64: FC = three x slabs of 9 features, n_init 5 each;
+ * TC = one fit of 6 features, n_init 1.  The host draws each fit's random numbers (numpy RandomState(5): choice, then uniform(size=2),
+ * per init) from the slab sizes that oai_mesh_split_features returns; no RNG runs on the device. */
+#define OAI_MESH_FC 0
+#define OAI_MESH_TC 1
+/* Workspace of oai_mesh_split_features + oai_mesh_split_kmeans with n_init runs per slab (one buffer, kept between the two calls):
+ * the slabs' features (n_faces rows, FC: + n_faces / 64 + 64 for faces on a slab seam) and n_init label / distance rows.  0 for bad
+ * arguments. */
+size_t oai_mesh_split_workspace_bytes(long long n_verts, long long n_faces, int mesh_type, int n_init);
+/* Per face: centroid (a + b + c) / 3 and unit normal cross(b - a, c - a) / |.| (0 for a degenerate face) as fp64 [n_faces][3],
+ * bit-identical to get_cell_centroid / get_cell_normals; then cn = (c - mean c) / (max c - min c), the features and the slabs
+ * (FC: lower <= cn_x < lower + step, a face in no slab keeps side 0).  slab_counts_host[s] = faces of slab s (TC: [n_faces, 0, 0]).
+ * Synchronises the stream once. */
+int oai_mesh_split_features(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, int mesh_type,
+                            void* workspace_dev, size_t workspace_bytes, double* centroids_dev, double* normals_dev,
+                            long long slab_counts_host[3], void* stream);
+/* The fits, after oai_mesh_split_features on the same workspace: one workgroup per (slab, init) run (k-means++ with 2 local trials,
+ * Lloyd to labels unchanged or sum |shift|^2 <= 1e-4 mean var, at most max_iter), fit()'s best-of-init rule, the orientation.
+ * first_centre_host[s * n_init + i] / uniforms_host[2 (s * n_init + i) + t]: run i of slab s.  side_dev: int8 [n_faces] in {-1, 0, +1}
+ * (-1 inner).  n_iter_host[s]: the chosen run's iteration count.  A slab with < 2 faces is an argument error; a cluster that empties
+ * during the iterations (sklearn relocates a point) is an error.  Synchronises the stream once. */
+int oai_mesh_split_kmeans(long long n_faces, int mesh_type, void* workspace_dev, size_t workspace_bytes, const double* normals_dev, int n_init,
+                          int max_iter, const long long slab_counts_host[3], const long long* first_centre_host, const double* uniforms_host,
+                          signed char* side_dev, int* n_iter_host, void* stream);
+/* get_vtk_sub_mesh (:150-194) of the faces with side_dev[i] == which: faces in ascending index order (face_idx_out), vertices in order of
+ * first use in the flattened face list, indices remapped.  Outputs sized for the worst case ([n_verts][3], [n_faces][3], [n_faces]);
+ * the counts come back to the host.  Synchronises the stream twice. */
+size_t oai_mesh_submesh_workspace_bytes(long long n_verts, long long n_faces);
+int oai_mesh_submesh(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, const signed char* side_dev, int which,
+                     void* workspace_dev, size_t workspace_bytes, float* verts_out_dev, int* faces_out_dev, int* face_idx_out_dev,
+                     long long* n_verts_out_host, long long* n_faces_out_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

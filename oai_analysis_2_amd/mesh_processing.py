@@ -4,7 +4,7 @@ Reference functions mirrored (same names, argument meaning and return roles):
 
     get_mesh(itk_image, num_iterations=150)            mesh_processing.py:325-340   marching cubes @0.5 + smoothing
     smooth_mesh(mesh, num_iterations=150)              :298-307
-    split_mesh(mesh, mesh_type="FC")                   :353-378   inner / outer surface (KMeans on centroids + normals)
+    split_mesh(mesh, mesh_type="FC", on_device=False)  :353-378   inner / outer surface (KMeans on centroids + normals)
     get_distance(inner_mesh, outer_mesh)               :310-322   closest-point distance, both directions
     get_thickness_mesh(itk_image, mesh_type, ...)      :381-395
     get_cell_centroid / get_cell_normals               :26-46
@@ -17,9 +17,11 @@ Reference functions mirrored (same names, argument meaning and return roles):
 vtk / trimesh / skimage are not installed here, so meshes are ``Mesh`` objects (float32 vertices [n,3] in (x,y,z)*spacing,
 int32 faces [m,3], per-point data) instead of ``vtkPolyData``; ``Mesh.to_vtk()`` adapts when vtk imports.  The three heavy
 steps run in HIP kernels behind the C ABI (oai_mc_*, oai_mesh_smooth, oai_mesh_point_distance; csrc/mesh.hip); the edge
-graph, the connected-component filter (> 3000 cells, :119-137) and the KMeans split are host logic exactly as in the
-reference (sklearn is the reference's own dependency).  Parity is unpinned: see oracle/mesh.py for what is
-restated.  The atlas thickness map runs in csrc/thickness_map.hip (oai_map_attributes*, oai_fit_circle, oai_project_circle,
+graph and the connected-component filter (> 3000 cells, :119-137) are host logic.  The KMeans split has two paths: by default
+the reference's own host code under the installed sklearn (its own dependency); with ``on_device=True`` csrc/mesh_split.hip
+(oai_mesh_split_*, oai_mesh_submesh) restates sklearn >= 1.4's KMeans in fp64 and builds both sub-meshes on the GPU, pinned face for
+face against the reference's split functions (tests/golden/mesh_split.npz); it does not import sklearn.  Marching cubes, smoothing
+and distance are unpinned: see oracle/mesh.py for what is restated.  The atlas thickness map runs in csrc/thickness_map.hip (oai_map_attributes*, oai_fit_circle, oai_project_circle,
 oai_project_plateaus): project_thickness and its circle helpers are pinned against the reference's own functions
 (tests/golden/thickness_projection.npz); map_attributes restates vtkPointInterpolator's defaults and is unpinned.  There is no CPU
 fallback for the kernels.
@@ -228,8 +230,109 @@ def split_femoral_cartilage_surface(mesh: Mesh, face_normal, face_centroid, num_
     return get_sub_mesh(mesh, inner), get_sub_mesh(mesh, outer), inner, outer
 
 
-def split_mesh(mesh: Mesh, mesh_type: str = "FC") -> Tuple[Mesh, Mesh]:
-    """mesh_processing.py:353-378"""
+# ---- the same split on the device (csrc/mesh_split.hip) -------------------------------------------------------------------------
+_MESH_TYPE = {"FC": 0, "TC": 1}
+_N_INIT = {"FC": 5, "TC": 1}                 # cluster_and_segment: n_init=5; the TC fit: n_init="auto" = 1 run (sklearn >= 1.4)
+_KMEANS_SEED, _KMEANS_MAX_ITER = 5, 300
+
+
+@dataclass
+class DeviceSplit:
+    """What the device split leaves on the GPU: the mesh, side per face (int8: -1 inner, +1 outer, 0 in no FC slab), the per-face
+    centroids / normals (fp64, bit-identical to get_cell_centroid / get_cell_normals) and each fit's iteration count (best run)."""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    side: torch.Tensor
+    centroids: torch.Tensor
+    normals: torch.Tensor
+    n_iter: np.ndarray
+
+
+def _kmeans_draws(counts, n_init: int, seed: int = _KMEANS_SEED):
+    """The random numbers sklearn's KMeans(random_state=seed).fit draws on an n-sample slab, fit by fit: per init, the first
+    k-means++ centre rs.choice(n, p=w / w.sum()) with w = ones(n), then rs.uniform(size=2) for the two local trials."""
+    first, uni = [], []
+    for n in counts:
+        n = int(n)
+        if n < 2:
+            raise ValueError(f"n_samples={n} should be >= n_clusters=2.")
+        rs = np.random.RandomState(seed)
+        w = np.ones(n, dtype=np.float64)
+        for _ in range(n_init):
+            first.append(int(rs.choice(n, p=w / w.sum())))
+            uni.extend(float(u) for u in rs.uniform(size=2))
+    return first, uni
+
+
+def split_mesh_device(mesh: Mesh, mesh_type: str = "FC") -> DeviceSplit:
+    """The KMeans labelling of split_femoral_cartilage_surface (FC) / split_tibial_cartilage_surface (anything else) on the GPU.
+    A slab with fewer than 2 faces raises the ValueError sklearn raises, as the reference does; the host path of this package skips
+    such an FC slab instead (its faces keep side 0)."""
+    lib = _lib.load()
+    kind = "FC" if mesh_type == "FC" else "TC"
+    nv, nf = len(mesh.verts), len(mesh.faces)
+    if nf < 2:
+        raise ValueError(f"n_samples={nf} should be >= n_clusters=2.")
+    v, f = _dev(mesh.verts.reshape(-1, 3), np.float32), _dev(mesh.faces.reshape(-1, 3), np.int32)
+    ws = torch.empty(int(lib.oai_mesh_split_workspace_bytes(nv, nf, _MESH_TYPE[kind], _N_INIT[kind])), dtype=torch.uint8, device=v.device)
+    cent = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
+    nrm = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
+    side = torch.empty(nf, dtype=torch.int8, device=v.device)
+    counts = (C.c_longlong * 3)()
+    with torch.cuda.device(v.device):
+        _lib.check(lib.oai_mesh_split_features(v.data_ptr(), nv, f.data_ptr(), nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), cent.data_ptr(),
+                                               nrm.data_ptr(), counts, _stream()), "oai_mesh_split_features")
+        n_slabs = 3 if kind == "FC" else 1
+        first, uni = _kmeans_draws(list(counts)[:n_slabs], _N_INIT[kind])
+        n_iter = (C.c_int * 3)()
+        _lib.check(lib.oai_mesh_split_kmeans(nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), nrm.data_ptr(), _N_INIT[kind], _KMEANS_MAX_ITER, counts,
+                                             (C.c_longlong * len(first))(*first), (C.c_double * len(uni))(*uni), side.data_ptr(), n_iter, _stream()),
+                   "oai_mesh_split_kmeans")
+    return DeviceSplit(v, f, side, cent, nrm, np.array(list(n_iter)[:n_slabs], dtype=np.int64))
+
+
+def get_sub_mesh_device(split: DeviceSplit, which: int) -> Tuple[Mesh, np.ndarray]:
+    """get_sub_mesh(mesh, np.where(side == which)[0]) built on the GPU: (sub-mesh, face list)."""
+    lib = _lib.load()
+    nv, nf = int(split.verts.shape[0]), int(split.faces.shape[0])
+    dev = split.verts.device
+    ws = torch.empty(int(lib.oai_mesh_submesh_workspace_bytes(nv, nf)), dtype=torch.uint8, device=dev)
+    vo = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    fo = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    io = torch.empty(nf, dtype=torch.int32, device=dev)
+    n_v, n_f = C.c_longlong(), C.c_longlong()
+    with torch.cuda.device(dev):
+        _lib.check(lib.oai_mesh_submesh(split.verts.data_ptr(), nv, split.faces.data_ptr(), nf, split.side.data_ptr(), int(which), ws.data_ptr(),
+                                        ws.numel(), vo.data_ptr(), fo.data_ptr(), io.data_ptr(), C.byref(n_v), C.byref(n_f), _stream()),
+                   "oai_mesh_submesh")
+    return (Mesh(vo[:n_v.value].cpu().numpy(), fo[:n_f.value].cpu().numpy()), io[:n_f.value].cpu().numpy().astype(np.int64))
+
+
+def _split_surface_device(mesh: Mesh, mesh_type: str):
+    sp = split_mesh_device(mesh, mesh_type)
+    inner, inner_list = get_sub_mesh_device(sp, -1)
+    outer, outer_list = get_sub_mesh_device(sp, 1)
+    return inner, outer, inner_list, outer_list
+
+
+def split_femoral_cartilage_surface_device(mesh: Mesh):
+    """split_femoral_cartilage_surface (:243-294) on the GPU: (inner mesh, outer mesh, inner face list, outer face list)."""
+    return _split_surface_device(mesh, "FC")
+
+
+def split_tibial_cartilage_surface_device(mesh: Mesh):
+    """split_tibial_cartilage_surface (:197-223) on the GPU: (inner mesh, outer mesh, inner face list, outer face list)."""
+    return _split_surface_device(mesh, "TC")
+
+
+def split_mesh(mesh: Mesh, mesh_type: str = "FC", on_device: bool = False) -> Tuple[Mesh, Mesh]:
+    """mesh_processing.py:353-378.  ``on_device``: the KMeans split and both sub-meshes on the GPU (sklearn >= 1.4 semantics,
+    split_femoral_cartilage_surface_device / split_tibial_cartilage_surface_device); the default is the reference's host code.
+    One difference besides the sklearn version: an FC slab with fewer than 2 faces raises ValueError on the device path (as the
+    reference's KMeans does), where the host path skips the slab and leaves its faces in neither sub-mesh."""
+    if on_device:
+        inner, outer, _, _ = _split_surface_device(mesh, mesh_type)
+        return inner, outer
     normals, centroids = get_cell_normals(mesh), get_cell_centroid(mesh)
     if mesh_type == "FC":
         inner, outer, _, _ = split_femoral_cartilage_surface(mesh, normals, centroids)
@@ -273,10 +376,12 @@ def get_distance(inner_mesh: Mesh, outer_mesh: Mesh) -> Tuple[Mesh, Mesh]:
             Mesh(outer_mesh.verts, outer_mesh.faces, {**outer_mesh.point_data, "Distance": d_out}))
 
 
-def get_thickness_mesh(itk_image, mesh_type: str = "FC", num_iterations: int = 150, min_cells: int = 3000) -> Tuple[Mesh, Mesh]:
-    """mesh_processing.py:381-395 (which, like this, always smooths with 150 iterations)."""
+def get_thickness_mesh(itk_image, mesh_type: str = "FC", num_iterations: int = 150, min_cells: int = 3000,
+                       split_on_device: bool = False) -> Tuple[Mesh, Mesh]:
+    """mesh_processing.py:381-395 (which, like this, always smooths with 150 iterations).  ``split_on_device``: see split_mesh (it
+    raises ValueError on a mesh with an FC slab of fewer than 2 faces, which the default path skips)."""
     mesh = get_mesh(itk_image, num_iterations=150, min_cells=min_cells)
-    inner, outer = split_mesh(mesh, mesh_type)
+    inner, outer = split_mesh(mesh, mesh_type, on_device=split_on_device)
     return get_distance(inner, outer)
 
 

@@ -37,3 +37,19 @@ timed("distance both directions (brute force)", lambda: (mp_point(inner.verts, o
 print("   median thickness", float(np.median(d[0].point_data["Distance"])), "(slab: 5 voxels x 0.36-0.7 mm)")
 pairs = len(inner.verts) * len(outer.faces) + len(outer.verts) * len(inner.faces)
 print(f"   brute force = {pairs/1e9:.2f} G point-triangle tests")
+
+# the inner / outer split: the reference's host KMeans (sklearn) against the device path (features -> both sub-meshes on the host)
+t = time.time(); h_in, h_out, h_il, h_ol = mp.split_femoral_cartilage_surface(sm, mp.get_cell_normals(sm), mp.get_cell_centroid(sm))
+t_host = time.time() - t
+print(f"{'split FC, host (sklearn KMeans, 3 slabs x n_init 5)':52s} {t_host*1e3:9.2f} ms")
+reps = 5
+mp.split_femoral_cartilage_surface_device(sm); torch.cuda.synchronize()
+t_dev = time.time()
+for _ in range(reps): d_res = mp.split_femoral_cartilage_surface_device(sm)
+torch.cuda.synchronize()
+t_dev = (time.time() - t_dev) / reps
+print(f"{'split FC, device (features, 15 runs, 2 sub-meshes)':52s} {t_dev*1e3:9.2f} ms   (mean of {reps})")
+n_iter = mp.split_mesh_device(sm, "FC").n_iter
+same = np.array_equal(d_res[2], h_il) and np.array_equal(d_res[3], h_ol)
+print(f"   {len(sm.faces)} faces; device n_iter per slab {n_iter.tolist()}; face lists agree with the host: {same}; "
+      f"host / device = {t_host / t_dev:.1f}x (both times as printed above)")
