@@ -512,6 +512,39 @@ int oai_mesh_submesh(const float* verts_dev, long long n_verts, const int* faces
                      void* workspace_dev, size_t workspace_bytes, float* verts_out_dev, int* faces_out_dev, int* face_idx_out_dev,
                      long long* n_verts_out_host, long long* n_faces_out_host, void* stream);
 
+/* ---- mesh graph steps of get_mesh / point_distance (mesh_processing.py:108-141; csrc/mesh_graph.hip) ----
+ * The host graph code between the mesh kernels, on the device: with these a caller goes from a probability map to a thickness mesh
+ * without a host round trip.  Faces are int32 [n_faces][3]; every face index must lie in [0, n_verts) (an index
+ * outside is an argument error, found before anything is written from it).  Results are exact, the same bits on every run. */
+/* Connected components of the face graph (two vertices are joined when they share a face): label_dev[v] = the smallest vertex index
+ * of v's component; an unreferenced vertex is its own component.  Hook / jump rounds, one launch each; the "changed" flags are read
+ * every 4 rounds (synchronises the stream once per 4 rounds).  rounds_host (may be null): hook / jump rounds up to and including the
+ * first that changed nothing (0 for n_faces = 0). */
+size_t oai_mesh_components_workspace_bytes(long long n_verts, long long n_faces);
+int oai_mesh_components(const int* faces_dev, long long n_faces, long long n_verts, void* workspace_dev, size_t workspace_bytes, int* label_dev,
+                        int* rounds_host, void* stream);
+/* keep_large_regions (get_vtk_mesh's connectivity loop, :114-141): the faces of components with more than min_cells faces (a face
+ * counts for the component of its first vertex), in their original order; the vertices they use in ascending original index,
+ * remapped.  Outputs sized for the worst case ([n_verts][3], [n_faces][3]); the counts come back to the host.  Synchronises the
+ * stream (as oai_mesh_components, then once). */
+size_t oai_mesh_keep_large_regions_workspace_bytes(long long n_verts, long long n_faces);
+int oai_mesh_keep_large_regions(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, long long min_cells,
+                                void* workspace_dev, size_t workspace_bytes, float* verts_out_dev, int* faces_out_dev, long long* n_verts_out_host,
+                                long long* n_faces_out_host, void* stream);
+/* vertex_adjacency (:108): the CSR edge graph of oai_mesh_smooth, offsets [n_verts + 1] and neighbours (capacity 6 n_faces), each
+ * vertex's neighbours ascending and unique; the self-loop of a degenerate face [a, a, b] is kept, an isolated vertex has degree 0.
+ * n_nbrs_host = offsets[n_verts].  Synchronises the stream once. */
+size_t oai_mesh_adjacency_workspace_bytes(long long n_verts, long long n_faces);
+int oai_mesh_adjacency(const int* faces_dev, long long n_faces, long long n_verts, void* workspace_dev, size_t workspace_bytes, int* offsets_dev,
+                       int* nbrs_dev, long long* n_nbrs_host, void* stream);
+/* What oai_mesh_point_distance_grid's caller derives from the mesh (point_distance): out7_dev (fp64, device) = the float32 bounding
+ * box lo xyz, hi xyz (min / max over every vertex), then the largest squared edge length over the faces' three edges in fp64,
+ * (dx*dx + dy*dy) + dz*dz with no contraction (numpy's norm before its sqrt; 0 for no faces, NaN if a face indexes outside the
+ * vertices).  Does not synchronise. */
+size_t oai_mesh_grid_params_workspace_bytes(void);
+int oai_mesh_grid_params(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, void* workspace_dev,
+                         size_t workspace_bytes, double* out7_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,15 @@ SIGNATURES = {
                                    C.POINTER(_I), _P]),
     "oai_mesh_submesh_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
     "oai_mesh_submesh": (_I, [_P, C.c_longlong, _P, C.c_longlong, _P, _I, _P, _Z, _P, _P, _P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _P]),
+    "oai_mesh_components_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_mesh_components": (_I, [_P, C.c_longlong, C.c_longlong, _P, _Z, _P, C.POINTER(_I), _P]),
+    "oai_mesh_keep_large_regions_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_mesh_keep_large_regions": (_I, [_P, C.c_longlong, _P, C.c_longlong, C.c_longlong, _P, _Z, _P, _P, C.POINTER(C.c_longlong),
+                                         C.POINTER(C.c_longlong), _P]),
+    "oai_mesh_adjacency_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_mesh_adjacency": (_I, [_P, C.c_longlong, C.c_longlong, _P, _Z, _P, _P, C.POINTER(C.c_longlong), _P]),
+    "oai_mesh_grid_params_workspace_bytes": (_Z, []),
+    "oai_mesh_grid_params": (_I, [_P, C.c_longlong, _P, C.c_longlong, _P, _Z, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

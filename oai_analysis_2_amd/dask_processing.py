@@ -98,13 +98,13 @@ def deform_probmap_delayed(phi_AB, image_A, image_B, prob, image_type="FC"):
     return deform_probmap(phi_AB, image_A, image_B, prob)
 
 
-def get_thickness(warped_image, mesh_type, split_on_device: bool = False):
+def get_thickness(warped_image, mesh_type, split_on_device: bool = False, on_device: bool = False):
     """dask_processing.py:114-122: the inner surface of the cartilage with per-point thickness ("Distance").  The reference converts the
     vtk mesh with mp.get_itk_mesh only "to make it serializable" for Dask's pickling (mesh_processing.py:57-98); there is no task graph
     to pickle for here, so the mesh is returned as mesh_processing produces it.  ``split_on_device``: the inner / outer KMeans split
-    on the GPU (mesh_processing.split_mesh)."""
+    on the GPU (mesh_processing.split_mesh).  ``on_device``: the whole step resident on the GPU (mesh_processing.get_thickness_mesh)."""
     from . import mesh_processing as mp
-    distance_inner, _ = mp.get_thickness_mesh(warped_image, mesh_type=mesh_type, split_on_device=split_on_device)
+    distance_inner, _ = mp.get_thickness_mesh(warped_image, mesh_type=mesh_type, split_on_device=split_on_device, on_device=on_device)
     return distance_inner
 
 

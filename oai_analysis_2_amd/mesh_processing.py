@@ -16,8 +16,11 @@ Reference functions mirrored (same names, argument meaning and return roles):
 
 vtk / trimesh / skimage are not installed here, so meshes are ``Mesh`` objects (float32 vertices [n,3] in (x,y,z)*spacing,
 int32 faces [m,3], per-point data) instead of ``vtkPolyData``; ``Mesh.to_vtk()`` adapts when vtk imports.  The three heavy
-steps run in HIP kernels behind the C ABI (oai_mc_*, oai_mesh_smooth, oai_mesh_point_distance; csrc/mesh.hip); the edge
-graph and the connected-component filter (> 3000 cells, :119-137) are host logic.  The KMeans split has two paths: by default
+steps run in HIP kernels behind the C ABI (oai_mc_*, oai_mesh_smooth, oai_mesh_point_distance; csrc/mesh.hip); by default the edge
+graph and the connected-component filter (> 3000 cells, :119-137) are host logic.  ``get_mesh(on_device=True)`` /
+``get_thickness_mesh(on_device=True)`` run them on the GPU too (csrc/mesh_graph.hip: oai_mesh_components, oai_mesh_keep_large_regions,
+oai_mesh_adjacency, oai_mesh_grid_params), so the whole thickness step stays resident until its result; bit-identical to the host
+graph code and to ``split_on_device=True``.  The KMeans split has two paths: by default
 the reference's own host code under the installed sklearn (its own dependency); with ``on_device=True`` csrc/mesh_split.hip
 (oai_mesh_split_*, oai_mesh_submesh) restates sklearn >= 1.4's KMeans in fp64 and builds both sub-meshes on the GPU, pinned face for
 face against the reference's split functions (tests/golden/mesh_split.npz); it does not import sklearn.  Marching cubes, smoothing
@@ -83,10 +86,9 @@ def _stream() -> int:
 
 
 # ---- marching cubes ----------------------------------------------------------------------------------------------------------
-def marching_cubes(volume_zyx, level: float = 0.5, spacing_xyz=(1.0, 1.0, 1.0)) -> Tuple[np.ndarray, np.ndarray]:
-    """(verts, faces) of the iso-surface; ``volume_zyx`` may be a numpy array or a float32 torch tensor already on the device."""
+def _marching_cubes_dev(vol: torch.Tensor, level: float, spacing_xyz) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(verts float32 [n,3], faces int32 [m,3]) of the iso-surface, left on the volume's device."""
     lib = _lib.load()
-    vol = volume_zyx if isinstance(volume_zyx, torch.Tensor) else _dev(np.asarray(volume_zyx), np.float32)
     vol = vol.to(torch.float32).contiguous()
     if not vol.is_cuda:
         vol = vol.cuda()
@@ -101,6 +103,14 @@ def marching_cubes(volume_zyx, level: float = 0.5, spacing_xyz=(1.0, 1.0, 1.0)) 
         sp = (C.c_float * 3)(*[float(v) for v in spacing_xyz])
         _lib.check(lib.oai_mc_emit(vol.data_ptr(), D, H, W, float(level), sp, ws.data_ptr(), verts.data_ptr(), faces.data_ptr(), _stream()),
                    "oai_mc_emit")
+    return verts, faces
+
+
+def marching_cubes(volume_zyx, level: float = 0.5, spacing_xyz=(1.0, 1.0, 1.0)) -> Tuple[np.ndarray, np.ndarray]:
+    """(verts, faces) of the iso-surface; ``volume_zyx`` may be a numpy array or a float32 torch tensor already on the device."""
+    _lib.load()
+    vol = volume_zyx if isinstance(volume_zyx, torch.Tensor) else _dev(np.asarray(volume_zyx), np.float32)
+    verts, faces = _marching_cubes_dev(vol, level, spacing_xyz)
     return verts.cpu().numpy(), faces.cpu().numpy()
 
 
@@ -138,24 +148,113 @@ def keep_large_regions(verts: np.ndarray, faces: np.ndarray, min_cells: int = 30
     return verts[used], remap[f].astype(np.int32)
 
 
+# ---- the same graph steps on the device (csrc/mesh_graph.hip) ------------------------------------------------------------------
+def _faces_dev(faces) -> torch.Tensor:
+    f = faces if isinstance(faces, torch.Tensor) else _dev(np.asarray(faces).reshape(-1, 3), np.int32)
+    return f.to(torch.int32).reshape(-1, 3).contiguous()
+
+
+def _verts_dev(verts) -> torch.Tensor:
+    v = verts if isinstance(verts, torch.Tensor) else _dev(np.asarray(verts).reshape(-1, 3), np.float32)
+    return v.to(torch.float32).reshape(-1, 3).contiguous()
+
+
+def mesh_components_device(faces, n_verts: int, return_rounds: bool = False):
+    """Connected components of the face graph on the GPU: int32 label per vertex = the smallest vertex index of its component (an
+    unreferenced vertex is its own component).  ``return_rounds``: also the number of hook / jump rounds it took."""
+    lib = _lib.load()
+    f = _faces_dev(faces)
+    nf, n = int(f.shape[0]), int(n_verts)
+    label = torch.empty(n, dtype=torch.int32, device=f.device)
+    ws = torch.empty(max(int(lib.oai_mesh_components_workspace_bytes(n, nf)), 1), dtype=torch.uint8, device=f.device)
+    rounds = C.c_int()
+    with torch.cuda.device(f.device):
+        _lib.check(lib.oai_mesh_components(f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), label.data_ptr(), C.byref(rounds), _stream()),
+                   "oai_mesh_components")
+    return (label, rounds.value) if return_rounds else label
+
+
+def keep_large_regions_device(verts, faces, min_cells: int = 3000) -> Tuple[torch.Tensor, torch.Tensor]:
+    """keep_large_regions on the GPU: torch tensors in (float32 [n,3], int32 [m,3]), device tensors out, equal to the host's."""
+    lib = _lib.load()
+    v, f = _verts_dev(verts), _faces_dev(faces)
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    ws = torch.empty(int(lib.oai_mesh_keep_large_regions_workspace_bytes(nv, nf)), dtype=torch.uint8, device=v.device)
+    vo, fo = torch.empty_like(v), torch.empty_like(f)
+    n_v, n_f = C.c_longlong(), C.c_longlong()
+    with torch.cuda.device(v.device):
+        _lib.check(lib.oai_mesh_keep_large_regions(v.data_ptr(), nv, f.data_ptr(), nf, int(min_cells), ws.data_ptr(), ws.numel(), vo.data_ptr(),
+                                                   fo.data_ptr(), C.byref(n_v), C.byref(n_f), _stream()), "oai_mesh_keep_large_regions")
+    return vo[:n_v.value], fo[:n_f.value]
+
+
+def vertex_adjacency_device(n_verts: int, faces) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vertex_adjacency on the GPU: int32 device tensors (offsets [n+1], neighbours), equal to the host's."""
+    lib = _lib.load()
+    f = _faces_dev(faces)
+    n, nf = int(n_verts), int(f.shape[0])
+    ws = torch.empty(int(lib.oai_mesh_adjacency_workspace_bytes(n, nf)), dtype=torch.uint8, device=f.device)
+    off = torch.empty(n + 1, dtype=torch.int32, device=f.device)
+    nbr = torch.empty(max(6 * nf, 1), dtype=torch.int32, device=f.device)
+    n_nbrs = C.c_longlong()
+    with torch.cuda.device(f.device):
+        _lib.check(lib.oai_mesh_adjacency(f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), off.data_ptr(), nbr.data_ptr(), C.byref(n_nbrs), _stream()),
+                   "oai_mesh_adjacency")
+    return off, nbr[:n_nbrs.value]
+
+
+def _smooth_dev(v: torch.Tensor, off: torch.Tensor, nbr: torch.Tensor, num_iterations: int, relaxation_factor: float) -> torch.Tensor:
+    lib = _lib.load()
+    n = int(v.shape[0])
+    tmp, out = torch.empty_like(v), torch.empty_like(v)
+    with torch.cuda.device(v.device):
+        _lib.check(lib.oai_mesh_smooth(v.data_ptr(), n, off.data_ptr(), nbr.data_ptr(), int(num_iterations), float(relaxation_factor),
+                                       tmp.data_ptr(), out.data_ptr(), _stream()), "oai_mesh_smooth")
+    return out
+
+
 def smooth_mesh(input_mesh: Mesh, num_iterations: int = 150, relaxation_factor: float = 0.01) -> Mesh:
     """vtkSmoothPolyDataFilter with its defaults (relaxation 0.01, boundary smoothing on, no feature edges)."""
-    lib = _lib.load()
+    _lib.load()
     n = len(input_mesh.verts)
     if n == 0 or num_iterations <= 0:
         return Mesh(input_mesh.verts.copy(), input_mesh.faces.copy(), dict(input_mesh.point_data))
     off, nbr = vertex_adjacency(n, input_mesh.faces)
-    v_in, d_off, d_nbr = _dev(input_mesh.verts, np.float32), _dev(off, np.int32), _dev(nbr, np.int32)
-    tmp, out = torch.empty_like(v_in), torch.empty_like(v_in)
-    with torch.cuda.device(v_in.device):
-        _lib.check(lib.oai_mesh_smooth(v_in.data_ptr(), n, d_off.data_ptr(), d_nbr.data_ptr(), int(num_iterations), float(relaxation_factor),
-                                       tmp.data_ptr(), out.data_ptr(), _stream()), "oai_mesh_smooth")
+    out = _smooth_dev(_dev(input_mesh.verts, np.float32), _dev(off, np.int32), _dev(nbr, np.int32), num_iterations, relaxation_factor)
     return Mesh(out.cpu().numpy(), input_mesh.faces.copy(), dict(input_mesh.point_data))
 
 
-def get_mesh(itk_image, num_iterations: int = 150, min_cells: int = 3000) -> Mesh:
+def _mesh_resident(vol: torch.Tensor, spacing_xyz, num_iterations: int, min_cells: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """get_mesh with every step on the device: marching cubes, large regions, edge graph, smoothing.  Device (verts, faces)."""
+    v, f = _marching_cubes_dev(vol, 0.5, spacing_xyz)
+    v, f = keep_large_regions_device(v, f, min_cells)
+    n = int(v.shape[0])
+    if n == 0 or num_iterations <= 0:
+        return v, f
+    off, nbr = vertex_adjacency_device(n, f)
+    return _smooth_dev(v, off, nbr, num_iterations, 0.01), f
+
+
+def _volume_dev(itk_image, spacing_xyz) -> Tuple[torch.Tensor, np.ndarray]:
+    """The probability map as a float32 [z,y,x] device tensor and its (x, y, z) spacing: an Image (or array / itk image), or a device
+    tensor with ``spacing_xyz`` (unit spacing if None)."""
+    if isinstance(itk_image, torch.Tensor):
+        if itk_image.dim() != 3:
+            raise ValueError(f"expected a [z,y,x] probability map, got shape {tuple(itk_image.shape)}")
+        sp = np.ones(3) if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
+        vol = itk_image if itk_image.is_cuda else itk_image.cuda()
+        return vol.to(torch.float32).contiguous(), sp
+    img = as_image(itk_image)
+    return _dev(np.asarray(img.array, dtype=np.float32), np.float32), img.spacing
+
+
+def get_mesh(itk_image, num_iterations: int = 150, min_cells: int = 3000, on_device: bool = False, spacing_xyz=None) -> Mesh:
     """mesh_processing.py:325-340: iso-surface of the probability map at 0.5 in (x,y,z)*spacing, small regions dropped
-    (get_vtk_mesh), then smoothed."""
+    (get_vtk_mesh), then smoothed.  ``on_device``: the region filter and the edge graph on the GPU too (csrc/mesh_graph.hip), one
+    download at the end, the same bits; ``itk_image`` may then also be a float32 [z,y,x] device tensor with ``spacing_xyz``."""
+    if on_device:
+        v, f = _mesh_resident(*_volume_dev(itk_image, spacing_xyz), num_iterations, min_cells)
+        return Mesh(v.cpu().numpy(), f.cpu().numpy())
     img = as_image(itk_image)
     verts, faces = marching_cubes(np.asarray(img.array, dtype=np.float32), 0.5, img.spacing)
     verts, faces = keep_large_regions(verts, faces, min_cells)
@@ -264,16 +363,12 @@ def _kmeans_draws(counts, n_init: int, seed: int = _KMEANS_SEED):
     return first, uni
 
 
-def split_mesh_device(mesh: Mesh, mesh_type: str = "FC") -> DeviceSplit:
-    """The KMeans labelling of split_femoral_cartilage_surface (FC) / split_tibial_cartilage_surface (anything else) on the GPU.
-    A slab with fewer than 2 faces raises the ValueError sklearn raises, as the reference does; the host path of this package skips
-    such an FC slab instead (its faces keep side 0)."""
+def _split_dev(v: torch.Tensor, f: torch.Tensor, mesh_type: str) -> DeviceSplit:
     lib = _lib.load()
     kind = "FC" if mesh_type == "FC" else "TC"
-    nv, nf = len(mesh.verts), len(mesh.faces)
+    nv, nf = int(v.shape[0]), int(f.shape[0])
     if nf < 2:
         raise ValueError(f"n_samples={nf} should be >= n_clusters=2.")
-    v, f = _dev(mesh.verts.reshape(-1, 3), np.float32), _dev(mesh.faces.reshape(-1, 3), np.int32)
     ws = torch.empty(int(lib.oai_mesh_split_workspace_bytes(nv, nf, _MESH_TYPE[kind], _N_INIT[kind])), dtype=torch.uint8, device=v.device)
     cent = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
     nrm = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
@@ -291,8 +386,19 @@ def split_mesh_device(mesh: Mesh, mesh_type: str = "FC") -> DeviceSplit:
     return DeviceSplit(v, f, side, cent, nrm, np.array(list(n_iter)[:n_slabs], dtype=np.int64))
 
 
-def get_sub_mesh_device(split: DeviceSplit, which: int) -> Tuple[Mesh, np.ndarray]:
-    """get_sub_mesh(mesh, np.where(side == which)[0]) built on the GPU: (sub-mesh, face list)."""
+def split_mesh_device(mesh: Mesh, mesh_type: str = "FC") -> DeviceSplit:
+    """The KMeans labelling of split_femoral_cartilage_surface (FC) / split_tibial_cartilage_surface (anything else) on the GPU.
+    A slab with fewer than 2 faces raises the ValueError sklearn raises, as the reference does; the host path of this package skips
+    such an FC slab instead (its faces keep side 0)."""
+    _lib.load()
+    nf = len(mesh.faces)
+    if nf < 2:
+        raise ValueError(f"n_samples={nf} should be >= n_clusters=2.")
+    return _split_dev(_dev(mesh.verts.reshape(-1, 3), np.float32), _dev(mesh.faces.reshape(-1, 3), np.int32), mesh_type)
+
+
+def _sub_mesh_dev(split: DeviceSplit, which: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """get_sub_mesh_device, left on the device: (verts, faces, face list int32)."""
     lib = _lib.load()
     nv, nf = int(split.verts.shape[0]), int(split.faces.shape[0])
     dev = split.verts.device
@@ -305,7 +411,13 @@ def get_sub_mesh_device(split: DeviceSplit, which: int) -> Tuple[Mesh, np.ndarra
         _lib.check(lib.oai_mesh_submesh(split.verts.data_ptr(), nv, split.faces.data_ptr(), nf, split.side.data_ptr(), int(which), ws.data_ptr(),
                                         ws.numel(), vo.data_ptr(), fo.data_ptr(), io.data_ptr(), C.byref(n_v), C.byref(n_f), _stream()),
                    "oai_mesh_submesh")
-    return (Mesh(vo[:n_v.value].cpu().numpy(), fo[:n_f.value].cpu().numpy()), io[:n_f.value].cpu().numpy().astype(np.int64))
+    return vo[:n_v.value], fo[:n_f.value], io[:n_f.value]
+
+
+def get_sub_mesh_device(split: DeviceSplit, which: int) -> Tuple[Mesh, np.ndarray]:
+    """get_sub_mesh(mesh, np.where(side == which)[0]) built on the GPU: (sub-mesh, face list)."""
+    v, f, io = _sub_mesh_dev(split, which)
+    return Mesh(v.cpu().numpy(), f.cpu().numpy()), io.cpu().numpy().astype(np.int64)
 
 
 def _split_surface_device(mesh: Mesh, mesh_type: str):
@@ -342,29 +454,58 @@ def split_mesh(mesh: Mesh, mesh_type: str = "FC", on_device: bool = False) -> Tu
 
 
 # ---- thickness -----------------------------------------------------------------------------------------------------------------
+def _grid_from_params(lo: np.ndarray, hi: np.ndarray, edge) -> Tuple[float, np.ndarray, np.ndarray]:
+    """point_distance's grid: cell h, dims and lower corner from the float64 bounds and the longest edge."""
+    h = max(float(edge) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)              # at most 512 cells per axis
+    dims = np.maximum(np.ceil((hi - lo) / h).astype(np.int64) + 1, 1)
+    return h, dims, lo - 0.5 * h * 1e-3
+
+
+def mesh_grid_params_device(verts, faces) -> Tuple[np.ndarray, np.ndarray, np.float64]:
+    """(lo, hi, longest edge) as point_distance computes them on the host -- float32 bounds as float64, the longest edge in fp64 --
+    from device tensors, with one 56-byte download."""
+    lib = _lib.load()
+    v, f = _verts_dev(verts), _faces_dev(faces)
+    out = torch.empty(7, dtype=torch.float64, device=v.device)
+    ws = torch.empty(int(lib.oai_mesh_grid_params_workspace_bytes()), dtype=torch.uint8, device=v.device)
+    with torch.cuda.device(v.device):
+        _lib.check(lib.oai_mesh_grid_params(v.data_ptr(), int(v.shape[0]), f.data_ptr(), int(f.shape[0]), ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                            _stream()), "oai_mesh_grid_params")
+    o = out.cpu().numpy()
+    return o[0:3].copy(), o[3:6].copy(), np.sqrt(o[6])          # sqrt is monotone and correctly rounded: the max of the host's norms
+
+
+def _point_distance_dev(p: torch.Tensor, v: torch.Tensor, f: torch.Tensor, grid=None) -> torch.Tensor:
+    """Distances from the points p to the mesh (v, f), all device tensors.  ``grid`` = (lo, hi, edge) selects the broad phase."""
+    lib = _lib.load()
+    n_points, n_tris = int(p.shape[0]), int(f.shape[0])
+    out = torch.empty(n_points, dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        if grid is not None:
+            h, dims, lo = _grid_from_params(*grid)
+            glo = (C.c_float * 3)(*[float(x) for x in lo])
+            gd = (C.c_int * 3)(*[int(x) for x in dims])
+            ws = torch.empty(int(lib.oai_mesh_grid_workspace_bytes(gd, n_tris)), dtype=torch.uint8, device=p.device)
+            _lib.check(lib.oai_mesh_point_distance_grid(p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, glo, float(h), gd,
+                                                        ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "oai_mesh_point_distance_grid")
+        else:
+            _lib.check(lib.oai_mesh_point_distance(p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, out.data_ptr(), _stream()),
+                       "oai_mesh_point_distance")
+    return out
+
+
 def point_distance(points: np.ndarray, mesh: Mesh, broad_phase: bool = True) -> np.ndarray:
     """Unsigned distance from each point to the mesh surface.  ``broad_phase``: bin the triangles into a uniform grid whose cell is
     the longest triangle edge (>= 2 voxels' worth) so that a point only tests the triangles around it; False = brute force."""
-    lib = _lib.load()
+    _lib.load()
     p, v, f = _dev(points, np.float32), _dev(mesh.verts, np.float32), _dev(mesh.faces, np.int32)
-    out = torch.empty(len(points), dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        if broad_phase and len(mesh.faces) > 0:
-            tri = mesh.verts[mesh.faces].astype(np.float64)
-            edge = max(np.linalg.norm(tri[:, 0] - tri[:, 1], axis=1).max(), np.linalg.norm(tri[:, 1] - tri[:, 2], axis=1).max(),
-                       np.linalg.norm(tri[:, 2] - tri[:, 0], axis=1).max())
-            lo, hi = mesh.verts.min(axis=0).astype(np.float64), mesh.verts.max(axis=0).astype(np.float64)
-            h = max(float(edge) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)              # at most 512 cells per axis
-            dims = np.maximum(np.ceil((hi - lo) / h).astype(np.int64) + 1, 1)
-            glo = (C.c_float * 3)(*[float(x) for x in lo - 0.5 * h * 1e-3])
-            gd = (C.c_int * 3)(*[int(x) for x in dims])
-            ws = torch.empty(int(lib.oai_mesh_grid_workspace_bytes(gd, len(mesh.faces))), dtype=torch.uint8, device=p.device)
-            _lib.check(lib.oai_mesh_point_distance_grid(p.data_ptr(), len(points), v.data_ptr(), f.data_ptr(), len(mesh.faces), glo, float(h), gd,
-                                                        ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "oai_mesh_point_distance_grid")
-        else:
-            _lib.check(lib.oai_mesh_point_distance(p.data_ptr(), len(points), v.data_ptr(), f.data_ptr(), len(mesh.faces), out.data_ptr(), _stream()),
-                       "oai_mesh_point_distance")
-    return out.cpu().numpy()
+    grid = None
+    if broad_phase and len(mesh.faces) > 0:
+        tri = mesh.verts[mesh.faces].astype(np.float64)
+        edge = max(np.linalg.norm(tri[:, 0] - tri[:, 1], axis=1).max(), np.linalg.norm(tri[:, 1] - tri[:, 2], axis=1).max(),
+                   np.linalg.norm(tri[:, 2] - tri[:, 0], axis=1).max())
+        grid = (mesh.verts.min(axis=0).astype(np.float64), mesh.verts.max(axis=0).astype(np.float64), edge)
+    return _point_distance_dev(p, v, f, grid).cpu().numpy()
 
 
 def get_distance(inner_mesh: Mesh, outer_mesh: Mesh) -> Tuple[Mesh, Mesh]:
@@ -376,13 +517,30 @@ def get_distance(inner_mesh: Mesh, outer_mesh: Mesh) -> Tuple[Mesh, Mesh]:
             Mesh(outer_mesh.verts, outer_mesh.faces, {**outer_mesh.point_data, "Distance": d_out}))
 
 
+def _distance_dev(p: torch.Tensor, v: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
+    """point_distance(p, Mesh(v, f)) with the grid parameters taken on the device."""
+    return _point_distance_dev(p, v, f, mesh_grid_params_device(v, f) if f.shape[0] > 0 else None)
+
+
 def get_thickness_mesh(itk_image, mesh_type: str = "FC", num_iterations: int = 150, min_cells: int = 3000,
-                       split_on_device: bool = False) -> Tuple[Mesh, Mesh]:
+                       split_on_device: bool = False, on_device: bool = False, spacing_xyz=None) -> Tuple[Mesh, Mesh]:
     """mesh_processing.py:381-395 (which, like this, always smooths with 150 iterations).  ``split_on_device``: see split_mesh (it
-    raises ValueError on a mesh with an FC slab of fewer than 2 faces, which the default path skips)."""
-    mesh = get_mesh(itk_image, num_iterations=150, min_cells=min_cells)
-    inner, outer = split_mesh(mesh, mesh_type, on_device=split_on_device)
-    return get_distance(inner, outer)
+    raises ValueError on a mesh with an FC slab of fewer than 2 faces, which the default path skips).
+
+    ``on_device``: the whole step stays on the GPU -- marching cubes, large regions, edge graph, smoothing, the device split and
+    the distance both ways -- and only the two result meshes are downloaded; the same bits as ``split_on_device=True``.
+    ``itk_image`` may then also be a float32 [z,y,x] device tensor (VolumeResult.fc_atlas / tc_atlas) with ``spacing_xyz``."""
+    if not on_device:
+        mesh = get_mesh(itk_image, num_iterations=150, min_cells=min_cells)
+        inner, outer = split_mesh(mesh, mesh_type, on_device=split_on_device)
+        return get_distance(inner, outer)
+    v, f = _mesh_resident(*_volume_dev(itk_image, spacing_xyz), 150, min_cells)
+    sp = _split_dev(v, f, mesh_type)
+    iv, if_, _ = _sub_mesh_dev(sp, -1)
+    ov, of, _ = _sub_mesh_dev(sp, 1)
+    d_in, d_out = _distance_dev(iv, ov, of), _distance_dev(ov, iv, if_)
+    return (Mesh(iv.cpu().numpy(), if_.cpu().numpy(), {"Distance": d_in.cpu().numpy()}),
+            Mesh(ov.cpu().numpy(), of.cpu().numpy(), {"Distance": d_out.cpu().numpy()}))
 
 
 # ---- atlas thickness map (mesh_processing.py:400-534) ----------------------------------------------------------------------------
