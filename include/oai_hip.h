@@ -545,6 +545,43 @@ size_t oai_mesh_grid_params_workspace_bytes(void);
 int oai_mesh_grid_params(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, void* workspace_dev,
                          size_t workspace_bytes, double* out7_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Cuberille iso-surface: get_mesh_from_probability_map (oai_analysis/mesh_processing.py:343-350), which calls
+ *   itk.cuberille_image_to_mesh_filter(image, generate_triangle_faces=True, iso_surface_value=0.5,
+ *       project_vertices_to_iso_surface=True, project_vertex_surface_distance_threshold=0.05)
+ * Restated, unpinned (ITK absent; DESIGN.md 1 lists the recalled points).  csrc/cuberille.hip, tests/cuberille_ref.py.
+ *   - volume [z][y][x] fp32; a voxel is inside when value >= iso; a neighbour off the grid is outside (closed surfaces).
+ *   - one quad per (inside voxel, outside face neighbour): voxels in raster order (x fastest), then neighbours -z -y -x +x +y +z.
+ *   - one vertex per lattice point a face uses; lattice point (i, j, k), i in [0, W] etc., lies at continuous index
+ *     (i - 1/2, j - 1/2, k - 1/2).  Vertices are numbered in order of first use (faces in order, corners in order) and are not
+ *     split where voxels touch at an edge or corner only: such contacts give non-manifold edges / vertices.
+ *   - a face on axis a with in-plane axes (b, c) = x:(y,z) y:(z,x) z:(x,y) has corners (b, c) = (0,0) (1,0) (1,1) (0,1) on the +a
+ *     side and (0,0) (0,1) (1,1) (1,0) on the -a side (normals point from inside to outside in index space).  Quad f = (q0 q1 q2 q3)
+ *     gives triangles 2f = (q0 q1 q2) and 2f+1 = (q0 q2 q3).  flip_winding (the caller sets it when det(direction) < 0) keeps each
+ *     polygon's first vertex and reverses the rest: (q0 q2 q1), (q0 q3 q2); quads (q0 q3 q2 q1).  Vertex numbering is unaffected.
+ *   - coordinates: u = spacing * c_xyz, p = origin + direction @ u, in fp64, stored fp32.
+ *   - projection (per vertex, fp64, no contraction): c = M (p - origin) with M = inv(direction diag(spacing)) as given; value =
+ *     trilinear interpolation at c clamped to [0, n-1] per axis; gradient = per-voxel central differences with replicated borders,
+ *     (f[i+1] - f[i-1]) / (2 s_axis), interpolated at the same c, then direction @ it.  With step = L, k = 0:
+ *       loop: g = grad(p); if |g| == 0 stop; m = value(p) - iso; done = |m| <= threshold;
+ *             if done and not move_after_converged stop; p += (m < 0 ? step : -step) * (g / |g|);
+ *             k += 1; done |= k > max_steps; step *= relaxation; if done stop
+ *     L = step_length, or 0.25 * max(spacing) when step_length < 0.  steps_dev[v] = k.
+ * geometry_host[24] = origin xyz, spacing xyz, direction (row-major 3x3), M (row-major 3x3).
+ * ---------------------------------------------------------------------------------------- */
+/* 0 when an axis is < 1 voxel or the volume is too large for 32-bit corner slots. */
+size_t oai_cuberille_workspace_bytes(int D, int H, int W);
+/* Classify, first use of every lattice point, vertex numbering; returns the vertex and quad counts (synchronises the stream). */
+int oai_cuberille_count(const float* vol_dev, int D, int H, int W, float iso, void* workspace_dev, size_t workspace_bytes,
+                        long long* n_verts_host, long long* n_faces_host, void* stream);
+/* After oai_cuberille_count on the same volume, iso and workspace, with the counts it returned: verts float32 [n_verts][3], faces int32
+ * [2 n_faces][3] (triangles != 0) or [n_faces][4]; steps_dev (may be null) int32 [n_verts].  threshold, step_length, relaxation and
+ * max_steps are checked and used only when project != 0.  Does not synchronise. */
+int oai_cuberille_emit(const float* vol_dev, int D, int H, int W, float iso, const double geometry_host[24], int flip_winding, int triangles,
+                       int project, double threshold, double step_length, double relaxation, int max_steps, int move_after_converged,
+                       void* workspace_dev, size_t workspace_bytes, long long n_verts, long long n_faces, float* verts_dev, int* faces_dev,
+                       int* steps_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

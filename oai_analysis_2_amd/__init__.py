@@ -19,3 +19,15 @@ def imwrite(image, path):
     from .image import as_image
     from .io_nifti import write_nifti
     write_nifti(path, as_image(image))
+
+
+def meshread(path):
+    """``itk.meshread(path)`` without ITK: a legacy VTK POLYDATA file (ASCII or BINARY) -> ``mesh_processing.Mesh``."""
+    from .io_vtk import read_vtk
+    return read_vtk(path)
+
+
+def meshwrite(mesh, path, binary=False):
+    """``itk.meshwrite(mesh, path)`` without ITK: legacy VTK POLYDATA, ASCII unless ``binary``."""
+    from .io_vtk import write_vtk
+    write_vtk(mesh, path, binary=binary)

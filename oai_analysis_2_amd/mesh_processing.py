@@ -3,6 +3,7 @@
 Reference functions mirrored (same names, argument meaning and return roles):
 
     get_mesh(itk_image, num_iterations=150)            mesh_processing.py:325-340   marching cubes @0.5 + smoothing
+    get_mesh_from_probability_map(image)               :343-350   itk cuberille @0.5, vertices projected to the iso-surface
     smooth_mesh(mesh, num_iterations=150)              :298-307
     split_mesh(mesh, mesh_type="FC", on_device=False)  :353-378   inner / outer surface (KMeans on centroids + normals)
     get_distance(inner_mesh, outer_mesh)               :310-322   closest-point distance, both directions
@@ -26,8 +27,9 @@ the reference's own host code under the installed sklearn (its own dependency); 
 face against the reference's split functions (tests/golden/mesh_split.npz); it does not import sklearn.  Marching cubes, smoothing
 and distance are unpinned: see oracle/mesh.py for what is restated.  The atlas thickness map runs in csrc/thickness_map.hip (oai_map_attributes*, oai_fit_circle, oai_project_circle,
 oai_project_plateaus): project_thickness and its circle helpers are pinned against the reference's own functions
-(tests/golden/thickness_projection.npz); map_attributes restates vtkPointInterpolator's defaults and is unpinned.  There is no CPU
-fallback for the kernels.
+(tests/golden/thickness_projection.npz); map_attributes restates vtkPointInterpolator's defaults and is unpinned.
+get_mesh_from_probability_map restates itk.cuberille_image_to_mesh_filter in csrc/cuberille.hip (oai_cuberille_*; unpinned)
+and returns ITK's physical points.  There is no CPU fallback for the kernels.
 """
 from __future__ import annotations
 
@@ -259,6 +261,86 @@ def get_mesh(itk_image, num_iterations: int = 150, min_cells: int = 3000, on_dev
     verts, faces = marching_cubes(np.asarray(img.array, dtype=np.float32), 0.5, img.spacing)
     verts, faces = keep_large_regions(verts, faces, min_cells)
     return smooth_mesh(Mesh(verts, faces), num_iterations=num_iterations)
+
+
+# ---- cuberille iso-surface (itk.cuberille_image_to_mesh_filter; csrc/cuberille.hip) --------------------------------------------
+def _probmap_geometry(image, spacing_xyz, origin_xyz, direction) -> Tuple[torch.Tensor, np.ndarray, np.ndarray, np.ndarray]:
+    """(float32 [z,y,x] device volume, spacing, origin, direction): the image's geometry (unit / zero / identity for a tensor), each
+    part replaced by the explicit argument when one is given."""
+    if isinstance(image, torch.Tensor):
+        if image.dim() != 3:
+            raise ValueError(f"expected a [z,y,x] probability map, got shape {tuple(image.shape)}")
+        vol = (image if image.is_cuda else image.cuda()).to(torch.float32).contiguous()
+        s, o, d = np.ones(3), np.zeros(3), np.eye(3)
+    else:
+        img = as_image(image)
+        if img.array.ndim != 3:
+            raise ValueError(f"expected a [z,y,x] probability map, got shape {img.array.shape}")
+        vol = _dev(np.asarray(img.array, dtype=np.float32), np.float32)
+        s, o, d = img.spacing, img.origin, img.direction
+    s = s if spacing_xyz is None else spacing_xyz
+    o = o if origin_xyz is None else origin_xyz
+    d = d if direction is None else direction
+    return (vol, np.asarray(s, np.float64).reshape(3).copy(), np.asarray(o, np.float64).reshape(3).copy(),
+            np.asarray(d, np.float64).reshape(3, 3).copy())
+
+
+def cuberille_device(image, iso_surface_value: float = 0.5, *, generate_triangle_faces: bool = True,
+                     project_vertices_to_iso_surface: bool = True, project_vertex_surface_distance_threshold: float = 0.05,
+                     project_vertex_step_length: float = -1.0, project_vertex_step_length_relaxation_factor: float = 0.95,
+                     project_vertex_maximum_number_of_steps: int = 50, move_after_converged: bool = True, spacing_xyz=None,
+                     origin_xyz=None, direction=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The cuberille surface left on the device: (verts float32 [n,3] physical points, faces int32 [2m,3] or [m,4] quads, steps int32
+    [n] = projection steps per vertex).  Contract: include/oai_hip.h, "Cuberille iso-surface"."""
+    lib = _lib.load()
+    vol, s, o, d = _probmap_geometry(image, spacing_xyz, origin_xyz, direction)
+    D, H, W = (int(v) for v in vol.shape)
+    geo = np.concatenate([o, s, d.reshape(-1), np.linalg.inv(d @ np.diag(s)).reshape(-1)])
+    flip = bool(np.linalg.det(d) < 0)
+    wsb = int(lib.oai_cuberille_workspace_bytes(D, H, W))
+    if wsb == 0:
+        raise ValueError(f"cuberille: volume {D}x{H}x{W} is empty or too large")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=vol.device)
+    nv, nf = C.c_longlong(), C.c_longlong()
+    iso = float(iso_surface_value)
+    with torch.cuda.device(vol.device):
+        _lib.check(lib.oai_cuberille_count(vol.data_ptr(), D, H, W, iso, ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nf), _stream()),
+                   "oai_cuberille_count")
+        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
+        faces = torch.empty((2 * nf.value, 3) if generate_triangle_faces else (nf.value, 4), dtype=torch.int32, device=vol.device)
+        steps = torch.empty(nv.value, dtype=torch.int32, device=vol.device)
+        if nv.value == 0:                                            # nothing inside: no faces either
+            return verts, faces, steps
+        _lib.check(lib.oai_cuberille_emit(vol.data_ptr(), D, H, W, iso, (C.c_double * 24)(*[float(x) for x in geo]), int(flip),
+                                          int(bool(generate_triangle_faces)), int(bool(project_vertices_to_iso_surface)),
+                                          float(project_vertex_surface_distance_threshold), float(project_vertex_step_length),
+                                          float(project_vertex_step_length_relaxation_factor), int(project_vertex_maximum_number_of_steps),
+                                          int(bool(move_after_converged)), ws.data_ptr(), ws.numel(), nv.value, nf.value, verts.data_ptr(),
+                                          faces.data_ptr(), steps.data_ptr(), _stream()), "oai_cuberille_emit")
+    return verts, faces, steps
+
+
+def get_mesh_from_probability_map(image, *, iso_surface_value: float = 0.5, generate_triangle_faces: bool = True,
+                                  project_vertices_to_iso_surface: bool = True, project_vertex_surface_distance_threshold: float = 0.05,
+                                  project_vertex_step_length: float = -1.0, project_vertex_step_length_relaxation_factor: float = 0.95,
+                                  project_vertex_maximum_number_of_steps: int = 50, move_after_converged: bool = True, spacing_xyz=None,
+                                  origin_xyz=None, direction=None) -> Mesh:
+    """mesh_processing.py:343-350: itk.cuberille_image_to_mesh_filter with the reference's settings (the defaults here) on the GPU.
+
+    Restated, unpinned (ITK is not installed): one quad per face between an inside voxel (value >= iso) and an outside
+    neighbour, one vertex per lattice point, numbered in order of first use, then each vertex walked to the iso-surface along the
+    interpolated gradient.  Vertices are ITK's physical points, origin + direction @ (spacing * index) -- unlike ``get_mesh``, which
+    returns skimage's (x, y, z) * spacing without the origin.  ``image`` is an ``Image``, an array, an ``itk.Image`` or a float32
+    [z,y,x] device tensor (e.g. VolumeResult.fc_atlas) with the optional ``spacing_xyz`` / ``origin_xyz`` / ``direction``.
+    ``move_after_converged``: the recalled form moves once more on the step that converges.  Faces are int32
+    triangles [2m,3], or quads [m,4] with ``generate_triangle_faces=False``."""
+    verts, faces, _ = cuberille_device(
+        image, iso_surface_value, generate_triangle_faces=generate_triangle_faces, project_vertices_to_iso_surface=project_vertices_to_iso_surface,
+        project_vertex_surface_distance_threshold=project_vertex_surface_distance_threshold, project_vertex_step_length=project_vertex_step_length,
+        project_vertex_step_length_relaxation_factor=project_vertex_step_length_relaxation_factor,
+        project_vertex_maximum_number_of_steps=project_vertex_maximum_number_of_steps, move_after_converged=move_after_converged,
+        spacing_xyz=spacing_xyz, origin_xyz=origin_xyz, direction=direction)
+    return Mesh(verts.cpu().numpy(), faces.cpu().numpy())
 
 
 # ---- per-cell attributes (trimesh in the reference) ------------------------------------------------------------------------------
