@@ -479,6 +479,29 @@ int oai_project_circle(const float* pts_dev, long long n, int col_x, int col_y, 
 int oai_project_plateaus(const float* pts_dev, const float* thickness_dev, long long n, void* workspace_dev, size_t workspace_bytes,
                          double* x_dev, double* y_dev, double* thickness_out_dev, long long* n_right_host, long long* n_left_host, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Thickness image (csrc/thickness_image.hip): map_attributes puts every knee's thickness on the atlas inner mesh, so all knees share
+ * the atlas' 2-D projection; it is rasterised once per atlas and each knee's image is one gather.  uv is float64 [n_pts][2] in mesh
+ * point order.  Pixel (j, i) of the [height][width] image has its centre at (lo[0] + (i + 0.5) step[0], lo[1] + (j + 0.5) step[1]); one
+ * step per axis (the axes need not share a unit).  All decisions in fp64 without contraction, restated in tests/thickness_image_ref.py.
+ * ---------------------------------------------------------------------------------------- */
+/* Workspace of oai_thickness_image_build (one box per face); 0 for no faces or an empty image. */
+size_t oai_thickness_image_workspace_bytes(long long n_faces, int height, int width);
+/* Face f = (a, b, c) with area = (B.u-A.u)(C.v-A.v) - (B.v-A.v)(C.u-A.u) is skipped if face_skip[f] (NULL: none), if an index lies
+ * outside [0, n_pts), if a coordinate is not finite or if area == 0.  Edge functions at the centre P:
+ * e0 = (C.u-B.u)(P.v-B.v) - (C.v-B.v)(P.u-B.u), e1 likewise on C->A, e2 on A->B, all negated when area < 0; f covers the pixel iff
+ * e0 >= 0 && e1 >= 0 && e2 >= 0 (edges inclusive).  owner = the SMALLEST covering face index (integer atomicMin: the same bits on every
+ * run) or -1; for the owner, corners = (a, b, c) and weights = e_k / ((e0 + e1) + e2); corners and weights are 0 where owner is -1.
+ * n_covered_host = the number of pixels with an owner.  Synchronises the stream. */
+int oai_thickness_image_build(const double* uv_dev, long long n_pts, const int* faces_dev, long long n_faces, const unsigned char* face_skip_dev,
+                              const double lo_host[2], const double step_host[2], int height, int width, void* workspace_dev,
+                              size_t workspace_bytes, int* owner_dev, int* corners_dev, double* weights_dev, long long* n_covered_host,
+                              void* stream);
+/* image[k][j][i] = (float)((w0 t[a] + w1 t[b]) + w2 t[c]) with t = values[k] widened to double, NaN (0x7fc00000) where owner < 0;
+ * values [n_knees][n_pts], image [n_knees][height][width].  A pure gather: one thread per pixel and knee. */
+int oai_thickness_image_apply(const int* owner_dev, const int* corners_dev, const double* weights_dev, int height, int width,
+                              const float* values_dev, long long n_pts, int n_knees, float* image_dev, void* stream);
+
 /* ---- inner / outer split of a cartilage surface (mesh_processing.py:197-294, 353-378; csrc/mesh_split.hip) ----
  * KMeans(n_clusters=2, algorithm="lloyd") of scikit-learn >= 1.4 restated in fp64: FC = three x slabs of 9 features, n_init 5 each;
  * TC = one fit of 6 features, n_init 1.  The host draws each fit's random numbers (numpy RandomState(5): choice, then uniform(size=2),

@@ -31,3 +31,11 @@ def meshwrite(mesh, path, binary=False):
     """``itk.meshwrite(mesh, path)`` without ITK: legacy VTK POLYDATA, ASCII unless ``binary``."""
     from .io_vtk import write_vtk
     write_vtk(mesh, path, binary=binary)
+
+
+def __getattr__(name):
+    """``ThicknessAtlas`` / ``KneeThickness`` (thickness.py), imported on first use: the package itself imports neither torch nor the library."""
+    if name in ("ThicknessAtlas", "KneeThickness"):
+        from . import thickness
+        return getattr(thickness, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -68,6 +68,10 @@ SIGNATURES = {
     "oai_fit_circle": (_I, [_P, C.c_longlong, _I, _I, _P, _Z, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I), _P]),
     "oai_project_circle": (_I, [_P, C.c_longlong, _I, _I, C.POINTER(_D), _P, _P, _P]),
     "oai_project_plateaus": (_I, [_P, _P, C.c_longlong, _P, _Z, _P, _P, _P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _P]),
+    "oai_thickness_image_workspace_bytes": (_Z, [C.c_longlong, _I, _I]),
+    "oai_thickness_image_build": (_I, [_P, C.c_longlong, _P, C.c_longlong, _P, C.POINTER(_D), C.POINTER(_D), _I, _I, _P, _Z, _P, _P, _P,
+                                       C.POINTER(C.c_longlong), _P]),
+    "oai_thickness_image_apply": (_I, [_P, _P, _P, _I, _I, _P, C.c_longlong, _I, _P, _P]),
     "oai_mesh_split_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong, _I, _I]),
     "oai_mesh_split_features": (_I, [_P, C.c_longlong, _P, C.c_longlong, _I, _P, _Z, _P, _P, C.POINTER(C.c_longlong), _P]),
     "oai_mesh_split_kmeans": (_I, [C.c_longlong, _I, _P, _Z, _P, _I, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(_D), _P,

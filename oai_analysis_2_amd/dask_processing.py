@@ -151,3 +151,66 @@ def process_cohort(images: Sequence, atlas_image, worker: Optional[Worker] = Non
                 return image_normalize(readimage(images[i]), 0.1, 99.9, 0, 1)
 
     return runner.run(_Lazy(), queue=VolumeQueue(len(images)))
+
+
+def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, keep_on_device: bool = False,
+                     results_complete: bool = False) -> Iterator[Tuple[int, object]]:
+    """(index, KneeThickness) for every (index, VolumeResult) of ``results`` whose ``fc_atlas`` / ``tc_atlas`` are on the device: the
+    thickness stage of the reference's task graph (get_thickness x2, then the notebook's map_attributes) behind a cohort, a few hundred
+    KB per knee instead of five tensors.
+
+    Each knee's ``ThicknessAtlas.measure`` runs on ONE worker thread with a stream of its own (the library's calls release the GIL, its
+    error text is thread-local), so that the stage's small kernels and count read-backs lie underneath the next volume's segmentation and
+    never block the thread that queues volumes -- the idea of VolumePipeline._run_overlapped's registration stream.  The worker's stream
+    never waits for an event ON THE GPU: a waiting stream parks a barrier packet at the head of an in-order hardware queue and holds
+    back whatever shares that queue (cohort.CohortRunner._queue_d2h, profiles/r06_cohort.md).  ``results_complete``: the results are
+    already finished on the host's side when they are handed over (CohortRunner(keep_on_device=True) synchronises each volume's event);
+    otherwise an event is recorded on the consumer's current stream as each result arrives and the worker waits for it on the host.
+    At most two knees are in flight; results come in input order; the worker is gone when the generator is exhausted or closed.
+    Measured (profiles/thickness_stage.md section 3): about nine tenths of the stage lie underneath the next volume, unless the runtime
+    deals the worker's stream onto the compute stream's own hardware queue (one creation order in four), where it runs serially."""
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    dev = thickness_atlas.device
+    caller = torch.cuda.current_stream(dev)
+    side = []                                                     # the worker's stream, created on the worker
+
+    def job(res, ev):
+        with torch.cuda.device(dev):
+            if not side:
+                side.append(torch.cuda.Stream(device=dev))
+            if ev is not None:
+                ev.synchronize()                                  # on the host, never a wait queued on the GPU
+            with torch.cuda.stream(side[0]):
+                res.fc_atlas.record_stream(side[0])
+                res.tc_atlas.record_stream(side[0])
+                knee = thickness_atlas.measure(res.fc_atlas, res.tc_atlas, keep_on_device=keep_on_device)
+                if keep_on_device:
+                    side[0].synchronize()                         # complete when handed over, like the input
+                    knee.fc.record_stream(caller)
+                    knee.tc.record_stream(caller)
+            return knee
+
+    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="oai-thickness")
+    pending: deque = deque()
+    try:
+        for index, res in results:
+            ev = None
+            if not results_complete:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(dev))
+            pending.append((index, pool.submit(job, res, ev)))
+            while len(pending) >= 2:                              # the newest runs while the one before it is handed out
+                i, fut = pending.popleft()
+                yield i, fut.result()
+        while pending:
+            i, fut = pending.popleft()
+            yield i, fut.result()
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+
+
+def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None) -> Iterator[Tuple[int, object]]:
+    """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the
+    probability maps never leave the device."""
+    return thickness_stream(process_cohort(images, atlas_image, worker, keep_on_device=True), thickness_atlas, results_complete=True)

@@ -29,7 +29,11 @@ and distance are unpinned: see oracle/mesh.py for what is restated
 oai_project_plateaus): project_thickness and its circle helpers are pinned against the reference's own functions
 (tests/golden/thickness_projection.npz); map_attributes restates vtkPointInterpolator's defaults and is unpinned.
 get_mesh_from_probability_map restates itk.cuberille_image_to_mesh_filter in csrc/cuberille.hip (oai_cuberille_*; unpinned)
-and returns ITK's physical points.  There is no CPU fallback for the kernels.
+and returns ITK's physical points.  The thickness image (thickness_image_build / thickness_image; csrc/thickness_image.hip, oai_thickness_image_*)
+rasterises a projected mesh once -- per pixel the smallest covering face index, its corners and barycentric weights, restated in
+tests/thickness_image_ref.py -- and gathers per-point values through it; _map_attributes_dev / _thickness_inner_dev are the device-tensor
+forms of map_attributes and of get_thickness_mesh's resident branch (inner mesh and inner -> outer distance only) that thickness.py chains
+without downloads.  There is no CPU fallback for the kernels.
 """
 from __future__ import annotations
 
@@ -625,6 +629,17 @@ def get_thickness_mesh(itk_image, mesh_type: str = "FC", num_iterations: int = 1
             Mesh(ov.cpu().numpy(), of.cpu().numpy(), {"Distance": d_out.cpu().numpy()}))
 
 
+def _thickness_inner_dev(vol: torch.Tensor, spacing_xyz, mesh_type: str, min_cells: int = 3000) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The resident branch of get_thickness_mesh without its second distance and without downloads: (inner verts, inner faces,
+    distance inner -> outer) as device tensors, the bits of ``get_thickness_mesh(..., on_device=True)[0]`` (a point's distance does not
+    depend on the other direction having been computed).  Raises the same ValueError on a map without a large region."""
+    v, f = _mesh_resident(vol, spacing_xyz, 150, min_cells)
+    sp = _split_dev(v, f, mesh_type)
+    iv, if_, _ = _sub_mesh_dev(sp, -1)
+    ov, of, _ = _sub_mesh_dev(sp, 1)
+    return iv, if_, _distance_dev(iv, ov, of)
+
+
 # ---- atlas thickness map (mesh_processing.py:400-534) ----------------------------------------------------------------------------
 def _point_arrays(mesh: Mesh) -> Tuple[list, np.ndarray]:
     """The mesh's point arrays as float32 component rows [n_comp][n] and (name, shape) of each array."""
@@ -637,6 +652,27 @@ def _point_arrays(mesh: Mesh) -> Tuple[list, np.ndarray]:
         names.append((name, a.shape))
         rows.append(a.reshape(n, -1).T.astype(np.float32))
     return names, (np.concatenate(rows, axis=0) if rows else np.zeros((0, n), np.float32))
+
+
+def _map_attributes_dev(src_verts: torch.Tensor, src_vals: torch.Tensor, tgt_verts: torch.Tensor, radius: float = 1.0, grid=None) -> torch.Tensor:
+    """map_attributes' grid broad phase on device tensors: float32 source points [n_src,3], values [n_comp,n_src], targets [n_tgt,3]
+    -> float32 [n_comp,n_tgt], nothing downloaded.  ``grid`` = (lo, hi), the float64 bounds of the source points as the host path takes
+    them (float32 minima / maxima widened; mesh_grid_params_device returns the same)."""
+    lib = _lib.load()
+    n_src, n_comp, n_tgt = int(src_verts.shape[0]), int(src_vals.shape[0]), int(tgt_verts.shape[0])
+    if n_src == 0:
+        raise ValueError("map_attributes: the source mesh has no points")
+    lo, hi = (np.asarray(x, dtype=np.float64).reshape(3) for x in grid)
+    out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=src_verts.device)
+    h = max(float(radius) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)          # at most 512 cells per axis
+    dims = np.maximum(np.ceil((hi - lo) / h).astype(np.int64) + 1, 1)
+    glo = (C.c_double * 3)(*[float(x) for x in lo - 0.5 * h * 1e-3])
+    gd = (C.c_int * 3)(*[int(x) for x in dims])
+    with torch.cuda.device(src_verts.device):
+        ws = torch.empty(int(lib.oai_point_grid_workspace_bytes(gd, n_src)), dtype=torch.uint8, device=src_verts.device)
+        _lib.check(lib.oai_map_attributes_grid(src_verts.data_ptr(), n_src, src_vals.data_ptr(), n_comp, tgt_verts.data_ptr(), n_tgt, float(radius), glo,
+                                               float(h), gd, ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "oai_map_attributes_grid")
+    return out
 
 
 def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, broad_phase: bool = True) -> Mesh:
@@ -658,19 +694,11 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
     if n_comp == 0:
         return Mesh(target_mesh.verts, target_mesh.faces, out_data)
     s, v, t = _dev(source_mesh.verts, np.float32), _dev(vals, np.float32), _dev(target_mesh.verts.reshape(-1, 3), np.float32)
-    out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=s.device)
-    with torch.cuda.device(s.device):
-        if broad_phase:
-            lo = source_mesh.verts.min(axis=0).astype(np.float64)
-            hi = source_mesh.verts.max(axis=0).astype(np.float64)
-            h = max(float(radius) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)          # at most 512 cells per axis
-            dims = np.maximum(np.ceil((hi - lo) / h).astype(np.int64) + 1, 1)
-            glo = (C.c_double * 3)(*[float(x) for x in lo - 0.5 * h * 1e-3])
-            gd = (C.c_int * 3)(*[int(x) for x in dims])
-            ws = torch.empty(int(lib.oai_point_grid_workspace_bytes(gd, n_src)), dtype=torch.uint8, device=s.device)
-            _lib.check(lib.oai_map_attributes_grid(s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), glo, float(h), gd,
-                                                   ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "oai_map_attributes_grid")
-        else:
+    if broad_phase:
+        out = _map_attributes_dev(s, v, t, radius, grid=(source_mesh.verts.min(axis=0).astype(np.float64), source_mesh.verts.max(axis=0).astype(np.float64)))
+    else:
+        out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=s.device)
+        with torch.cuda.device(s.device):
             _lib.check(lib.oai_map_attributes(s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr(), _stream()),
                        "oai_map_attributes")
     res = out.cpu().numpy()
@@ -780,3 +808,87 @@ def project_thickness(mapped_mesh: Mesh, mesh_type: str = "FC", embedded=None) -
                                             out[2].data_ptr(), C.byref(n_right), C.byref(n_left), _stream()), "oai_project_plateaus")
     res = out[:, :n_right.value + n_left.value].cpu().numpy()
     return res[0].copy(), res[1].copy(), res[2].copy()
+
+
+# ---- thickness image: the atlas' projection rasterised once, a gather per knee (csrc/thickness_image.hip) -------------------------
+@dataclass
+class ThicknessRaster:
+    """What thickness_image_build leaves on the GPU for an [H, W] image: per pixel the owning face (int32, -1 = none), its three point
+    indices (int32 [H,W,3]) and the barycentric weights of the pixel centre (float64 [H,W,3]).  Pixel (j, i) has its centre at
+    (lo[0] + (i + 0.5) * step[0], lo[1] + (j + 0.5) * step[1])."""
+    owner: torch.Tensor
+    corners: torch.Tensor
+    weights: torch.Tensor
+    lo: np.ndarray
+    step: np.ndarray
+    n_covered: int
+    n_points: int
+
+
+def thickness_image_grid(uv: np.ndarray, image_shape) -> Tuple[np.ndarray, np.ndarray]:
+    """(lo[2], step[2]) of an [H, W] raster over the finite points of uv [n,2]: lo = the minima, one step per axis = extent / W and
+    extent / H (the axes need not share a unit: FC has radians against mm).  An axis of zero extent raises ValueError."""
+    H, W = (int(x) for x in image_shape)
+    if H < 1 or W < 1:
+        raise ValueError(f"thickness image: image_shape {tuple(image_shape)} must be at least 1 x 1")
+    uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+    fin = uv[np.isfinite(uv).all(axis=1)]
+    if len(fin) == 0:
+        raise ValueError("thickness image: no finite projected point")
+    lo, hi = fin.min(axis=0), fin.max(axis=0)
+    step = np.array([(hi[0] - lo[0]) / W, (hi[1] - lo[1]) / H], dtype=np.float64)
+    if not (step > 0).all():
+        raise ValueError(f"thickness image: the projected points have no extent along an axis (min {lo}, max {hi})")
+    return lo, step
+
+
+def thickness_image_build(uv, faces, face_skip=None, image_shape=(256, 256)) -> ThicknessRaster:
+    """Rasterise a projected mesh once: ``uv`` float64 [n,2] in mesh point order (array or device tensor), ``faces`` int32 [m,3],
+    ``face_skip`` bool [m] (faces that must own nothing, e.g. those bridging the two tibial plateaus).  A pixel belongs to the smallest
+    face index whose triangle contains its centre (edges inclusive); contract in include/oai_hip.h, "Thickness image"."""
+    lib = _lib.load()
+    H, W = (int(x) for x in image_shape)
+    uv_host = uv.detach().cpu().numpy() if isinstance(uv, torch.Tensor) else np.asarray(uv)
+    lo, step = thickness_image_grid(uv_host, (H, W))
+    uv_d = uv.to(torch.float64).reshape(-1, 2).contiguous() if isinstance(uv, torch.Tensor) and uv.is_cuda else _dev(uv_host.reshape(-1, 2), np.float64)
+    f = _faces_dev(faces)
+    n_pts, n_faces = int(uv_d.shape[0]), int(f.shape[0])
+    if n_faces == 0:
+        raise ValueError("thickness image: the mesh has no faces")
+    skip = None
+    if face_skip is not None:
+        skip = (face_skip if isinstance(face_skip, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(face_skip, dtype=np.uint8))).to(uv_d.device).to(torch.uint8).contiguous()
+        if skip.shape != (n_faces,):
+            raise ValueError(f"thickness image: face_skip has shape {tuple(skip.shape)}, the mesh has {n_faces} faces")
+    dev = uv_d.device
+    owner = torch.empty((H, W), dtype=torch.int32, device=dev)
+    corners = torch.empty((H, W, 3), dtype=torch.int32, device=dev)
+    weights = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
+    ws = torch.empty(int(lib.oai_thickness_image_workspace_bytes(n_faces, H, W)), dtype=torch.uint8, device=dev)
+    n_cov = C.c_longlong()
+    with torch.cuda.device(dev):
+        _lib.check(lib.oai_thickness_image_build(uv_d.data_ptr(), n_pts, f.data_ptr(), n_faces, skip.data_ptr() if skip is not None else None,
+                                                 (C.c_double * 2)(*lo), (C.c_double * 2)(*step), H, W, ws.data_ptr(), ws.numel(), owner.data_ptr(),
+                                                 corners.data_ptr(), weights.data_ptr(), C.byref(n_cov), _stream()), "oai_thickness_image_build")
+    return ThicknessRaster(owner, corners, weights, lo, step, int(n_cov.value), n_pts)
+
+
+def thickness_image(raster: ThicknessRaster, values):
+    """The thickness image of per-point values on the rastered mesh: float32 [H,W] for values [n], [K,H,W] for [K,n]; NaN where no face
+    owns the pixel, and NaN spreads from a NaN point to the pixels of its faces.  A device tensor gives a device tensor, an array an array."""
+    lib = _lib.load()
+    on_dev = isinstance(values, torch.Tensor)
+    v = (values if on_dev else torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32))).to(raster.owner.device).to(torch.float32).contiguous()
+    if v.dim() not in (1, 2) or v.shape[-1] != raster.n_points:
+        raise ValueError(f"thickness image: values of shape {tuple(v.shape)} do not match the raster's {raster.n_points} points")
+    K = 1 if v.dim() == 1 else int(v.shape[0])
+    H, W = (int(x) for x in raster.owner.shape)
+    img = torch.empty((K, H, W), dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        for k0 in range(0, K, 65535):
+            k1 = min(K, k0 + 65535)
+            _lib.check(lib.oai_thickness_image_apply(raster.owner.data_ptr(), raster.corners.data_ptr(), raster.weights.data_ptr(), H, W,
+                                                     v.reshape(K, -1)[k0:k1].data_ptr(), raster.n_points, k1 - k0, img[k0:k1].data_ptr(), _stream()),
+                       "oai_thickness_image_apply")
+    img = img[0] if v.dim() == 1 else img
+    return img if on_dev else img.cpu().numpy()

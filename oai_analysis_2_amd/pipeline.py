@@ -10,7 +10,7 @@ Used by bench.py, the cohort driver and the multi-GPU sharding.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -19,6 +19,9 @@ from . import ops
 from .image import Image
 from .registration import IconEngine, resample_affines
 from .segmentation.engine import UNetEngine, tile_grid
+
+if TYPE_CHECKING:
+    from .thickness import KneeThickness, ThicknessAtlas
 
 TILE_ZYX = (32, 128, 128)        # patch_size (128,128,32) in x,y,z (a2)
 OVERLAP_ZYX = (8, 16, 16)        # overlap_size (16,16,8) in x,y,z (analysis_object.py:23)
@@ -35,6 +38,7 @@ class VolumeResult:
     overflow: Optional[torch.Tensor] = None    # int32[1] on the device: the fp16 range flag of THIS volume's segmentation
     #                                            (None with exact arithmetic).  Non-zero = the maps are invalid: repeat in fp32.
     repeated_f32: bool = False   # the fp16x3 run overflowed and these are the results of the fp32 repeat
+    thickness: Optional["KneeThickness"] = None    # cartilage thickness on the atlas inner vertices (run(..., thickness=atlas) only)
 
 
 class VolumePipeline:
@@ -89,13 +93,18 @@ class VolumePipeline:
         return ops.resample_maps_through_phi(maps, phi, b2n, n2a, shape)
 
     # ---- one volume, one GPU --------------------------------------------------------------------------------------------------
-    def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True) -> VolumeResult:
+    def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None) -> VolumeResult:
+        """``thickness``: a thickness.ThicknessAtlas -- the volume's cartilage thickness on the atlas inner vertices is measured from
+        ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
+        None (default): nothing more is launched."""
         res = self._run_overlapped(vol, meta_A) if self.overlap_registration else self._run_serial(vol, meta_A)
         if check and res.overflow is not None:
             raised = bool(int(res.overflow.item()))
             self.unet.note_volume_flag(raised)              # (a calibration FILE that keeps missing the data is dropped after three volumes in a row)
             if raised:
-                return self.rerun_f32(vol, meta_A)
+                res = self.rerun_f32(vol, meta_A)
+        if thickness is not None:
+            res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing)
         return res
 
     def rerun_f32(self, vol: torch.Tensor, meta_A: Image, sharded_group="none") -> VolumeResult:

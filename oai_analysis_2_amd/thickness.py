@@ -1,0 +1,212 @@
+"""The per-knee thickness stage: what the reference's task graph ends in (dask_processing.py:46-189: ... -> get_thickness x2) and what
+its demo notebook goes on to (FullDemo.ipynb: map_attributes onto the atlas inner meshes, project_thickness), as one device-resident
+step behind ``VolumeResult.fc_atlas`` / ``tc_atlas``, plus a thickness IMAGE on a fixed grid.
+
+    ThicknessAtlas(atlas_fc, atlas_tc)      once per process: the atlas inner meshes (resident map_attributes targets), their 2-D
+                                            projection in mesh point order, and its raster (csrc/thickness_image.hip)
+    atlas.measure(fc_atlas, tc_atlas)       per knee: marching cubes -> large regions -> edge graph -> smoothing -> device split ->
+                                            inner / outer sub-mesh -> distance inner -> outer -> map_attributes onto the atlas inner
+                                            vertices; one float32 vector per cartilage comes back
+    atlas.image(thickness, kind)            per knee: one gather through the raster; the same pixel is the same atlas location in
+                                            every knee, because map_attributes puts every knee on the atlas' vertices
+
+The inner / outer split of the atlas and of every knee is the DEVICE split (mesh_processing.split_mesh(on_device=True): scikit-learn
+>= 1.4's KMeans restated in fp64); it is the only split that keeps the stage resident.  The default host split of split_mesh runs the
+installed sklearn and may label differently under an older version.
+
+The host-side rules of the raster are exact, without thresholds (fc_cut, fc_face_skip, tc_face_skip below).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Dict, Optional, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import mesh_processing as mp
+
+KINDS = ("FC", "TC")
+_TC_SPLIT_Z = 50.0                  # project_thickness: the plateaus are split at z < 50 (raw coordinate units)
+
+
+# ---- host rules of the raster (numpy only) ----------------------------------------------------------------------------------------
+def wrap_angle(a):
+    """a folded once into (-pi, pi] (for |a| <= 3 pi)."""
+    a = np.asarray(a, dtype=np.float64)
+    a = np.where(a > np.pi, a - 2 * np.pi, a)
+    return np.where(a <= -np.pi, a + 2 * np.pi, a)
+
+
+def fc_cut(angle) -> float:
+    """The rotation that takes atan2's cut out of the femoral arc: the femoral surface is an arc, and nothing says the cut at +-pi lies
+    outside it.  The angles are sorted and the largest empty gap found (the gap that wraps from the last angle round to the first
+    included; the first of equal gaps); the returned ``cut`` in (-pi, pi] is such that ``u = wrap_angle(angle - cut)`` has its own
+    +-pi seam in the middle of that gap, i.e. the middle of the gap is the angle ``cut + pi``.  u is then contiguous over the arc (its
+    extent is 2 pi minus the gap), and ``wrap_angle(u + cut)`` is the raw angle again."""
+    a = np.sort(np.asarray(angle, dtype=np.float64)[np.isfinite(angle)])
+    if len(a) == 0:
+        raise ValueError("fc_cut: no finite angle")
+    gaps = np.append(np.diff(a), a[0] + 2 * np.pi - a[-1])
+    k = int(np.argmax(gaps))
+    return float(wrap_angle(a[k] + 0.5 * gaps[k] - np.pi))
+
+
+def fc_face_skip(u, faces) -> np.ndarray:
+    """Faces with an edge whose |du| > pi after the rotation: only a surface that closes the full circle has one (it would be drawn
+    across the whole image)."""
+    t = np.asarray(u, dtype=np.float64)[np.asarray(faces, dtype=np.int64).reshape(-1, 3)]
+    return (np.abs(t[:, 0] - t[:, 1]) > np.pi) | (np.abs(t[:, 1] - t[:, 2]) > np.pi) | (np.abs(t[:, 2] - t[:, 0]) > np.pi)
+
+
+def tc_face_skip(z, faces) -> np.ndarray:
+    """Faces whose three vertices are not on the same side of z = 50, project_thickness's plateau split: the two plateaus are
+    projected separately, a face between them means nothing in the image."""
+    side = (np.asarray(z, dtype=np.float32) >= _TC_SPLIT_Z)[np.asarray(faces, dtype=np.int64).reshape(-1, 3)]
+    return (side[:, 0] != side[:, 1]) | (side[:, 1] != side[:, 2])
+
+
+def tc_point_order(z) -> np.ndarray:
+    """project_thickness(TC) returns the right plateau (z >= 50) first, each plateau in point order: row k of its output is mesh
+    point ``tc_point_order(z)[k]``."""
+    z = np.asarray(z, dtype=np.float32)
+    return np.concatenate([np.nonzero(z >= _TC_SPLIT_Z)[0], np.nonzero(z < _TC_SPLIT_Z)[0]])
+
+
+@dataclass
+class KneeThickness:
+    """Cartilage thickness of one knee on the atlas inner vertices: float32 [n_fc], [n_tc] (numpy, or device tensors with
+    ``keep_on_device``).  A cartilage that could not be measured is all NaN and has its reason in ``errors["FC"]`` / ``errors["TC"]``."""
+    fc: Union[np.ndarray, torch.Tensor]
+    tc: Union[np.ndarray, torch.Tensor]
+    errors: Dict[str, str] = field(default_factory=dict)
+
+    def __getitem__(self, kind: str):
+        return {"FC": self.fc, "TC": self.tc}[kind]
+
+
+class ThicknessAtlas:
+    """Everything about the atlas that is the same for every knee, built once per process from the atlas' own FC and TC probability
+    maps (FullDemo.ipynb reads atlas_fc.nii.gz / atlas_tc.nii.gz): each an ``Image``, an array, or a [z,y,x] device tensor with
+    ``spacing_xyz``.
+
+    ``inner[kind]``      the atlas inner mesh (host ``Mesh``); its vertices stay on the device as the map_attributes targets
+    ``uv[kind]``         float64 [n,2], the 2-D projection in MESH POINT ORDER: vertex i of ``inner[kind]`` owns ``uv[kind][i]``.
+                         FC: (angle rotated by ``cut``, z); TC: project_thickness's (x, y) put back from its right-plateau-first order
+    ``point_order[kind]`` row k of project_thickness's output is mesh point ``point_order[kind][k]`` (FC: the identity)
+    ``raster[kind]``     the ThicknessRaster of ``image_shape``; ``cut`` = the FC rotation: pixel column i is the raw angle
+                         ``wrap_angle(lo[0] + (i + 0.5) * step[0] + cut)``
+    ``projection_errors[kind]``  a projection that does not exist (project_thickness's ValueError: a tibial atlas with an empty
+                         plateau): ``measure`` works all the same, ``image`` / ``scatter`` of that cartilage raise it.
+
+    Both the atlas and every knee are split on the device (sklearn >= 1.4 semantics, see mesh_processing.split_mesh): the only split
+    that keeps the stage resident.  ``min_cells`` (an int, or one per cartilage) is get_mesh's region filter, used for the atlas and
+    for every knee; ``radius`` is map_attributes'.  ``image_shape`` (H, W) is an API default, not a tuned number."""
+
+    def __init__(self, atlas_fc, atlas_tc, spacing_xyz=None, image_shape: Tuple[int, int] = (256, 256), min_cells=3000, radius: float = 1.0):
+        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
+        self.min_cells = {k: int(min_cells[k] if isinstance(min_cells, dict) else min_cells) for k in KINDS}
+        self.radius = float(radius)
+        self.inner: Dict[str, mp.Mesh] = {}
+        self.uv: Dict[str, np.ndarray] = {}
+        self.point_order: Dict[str, np.ndarray] = {}
+        self.raster: Dict[str, mp.ThicknessRaster] = {}
+        self.projection_errors: Dict[str, str] = {}
+        self.cut = 0.0
+        self._targets: Dict[str, torch.Tensor] = {}
+        self._scatter: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
+        self.spacing: Dict[str, np.ndarray] = {}            # each map's own (x, y, z) spacing: measure's default for that cartilage
+        self.device = None
+        for kind, probmap in zip(KINDS, (atlas_fc, atlas_tc)):
+            vol, sp = mp._volume_dev(probmap, spacing_xyz)
+            self.spacing[kind] = np.asarray(sp, dtype=np.float64).copy()
+            if self.device is None:
+                self.device = vol.device
+            v, f = mp._mesh_resident(vol, sp, 150, self.min_cells[kind])
+            iv, if_, _ = mp._sub_mesh_dev(mp._split_dev(v, f, kind), -1)
+            if iv.shape[0] == 0:
+                raise ValueError(f"ThicknessAtlas: the atlas {kind} map has no inner surface")
+            self._targets[kind] = iv
+            self.inner[kind] = mp.Mesh(iv.cpu().numpy(), if_.cpu().numpy())
+            try:
+                self._project(kind)
+            except ValueError as e:
+                self.projection_errors[kind] = str(e)
+
+    def _project(self, kind: str) -> None:
+        mesh = self.inner[kind]
+        n = len(mesh.verts)
+        x, y, _ = mp.project_thickness(mp.Mesh(mesh.verts, mesh.faces, {"Distance": np.zeros(n, np.float32)}), kind)
+        uv = np.empty((n, 2), dtype=np.float64)
+        if kind == "FC":
+            order = np.arange(n)
+            self.cut = fc_cut(x)
+            uv[:, 0], uv[:, 1] = wrap_angle(x - self.cut), y
+            skip = fc_face_skip(uv[:, 0], mesh.faces)
+        else:
+            order = tc_point_order(mesh.verts[:, 2])
+            uv[order, 0], uv[order, 1] = x, y
+            skip = tc_face_skip(mesh.verts[:, 2], mesh.faces)
+        self._scatter[kind], self.point_order[kind], self.uv[kind] = (x, y), order, uv
+        with torch.cuda.device(self.device):
+            self.raster[kind] = mp.thickness_image_build(uv, self._faces_dev(kind), skip, self.image_shape)
+
+    def _faces_dev(self, kind: str) -> torch.Tensor:
+        return torch.from_numpy(self.inner[kind].faces).to(self.device)
+
+    def n_points(self, kind: str) -> int:
+        return len(self.inner[kind].verts)
+
+    # ---- per knee -----------------------------------------------------------------------------------------------------------------
+    def _measure_one(self, vol: torch.Tensor, spacing, kind: str) -> torch.Tensor:
+        iv, if_, dist = mp._thickness_inner_dev(vol, spacing, kind, self.min_cells[kind])
+        if iv.shape[0] == 0:
+            raise ValueError("map_attributes: the source mesh has no points")
+        lo, hi, _ = mp.mesh_grid_params_device(iv, if_)
+        return mp._map_attributes_dev(iv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
+
+    def measure(self, fc_atlas: torch.Tensor, tc_atlas: torch.Tensor, spacing_xyz=None, keep_on_device: bool = False) -> KneeThickness:
+        """Thickness of one knee on the atlas inner vertices, from the two [z,y,x] float32 device tensors of a ``VolumeResult``
+        (``spacing_xyz``: the atlas grid's, default the spacing of the map this atlas was built from).  Everything stays on the device, on the
+        current stream, until the two vectors; only the inner -> outer distance is computed.  Per cartilage, bit for bit,
+
+            map_attributes(get_thickness_mesh(Image(map.cpu(), spacing), kind, min_cells=.., on_device=True)[0], atlas.inner[kind]).point_data["Distance"]
+
+        A map with no region above ``min_cells``, or an FC slab of fewer than 2 faces, raises ValueError inside those functions: that
+        is caught PER CARTILAGE, the vector filled with NaN and the message kept in ``errors`` -- one bad knee must not end a cohort.
+        Nothing else is caught."""
+        out, errors = {}, {}
+        for kind, vol in zip(KINDS, (fc_atlas, tc_atlas)):
+            sp = self.spacing[kind] if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
+            with torch.cuda.device(self.device):
+                vol_d, _ = mp._volume_dev(vol, sp)
+                try:
+                    out[kind] = self._measure_one(vol_d, sp, kind)
+                except ValueError as e:
+                    errors[kind] = str(e)
+                    out[kind] = torch.full((self.n_points(kind),), float("nan"), dtype=torch.float32, device=self.device)
+        if not keep_on_device:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        return KneeThickness(out["FC"], out["TC"], errors)
+
+    def _raster(self, kind: str) -> mp.ThicknessRaster:
+        if kind not in KINDS:
+            raise KeyError(f"kind must be one of {KINDS}, got {kind!r}")
+        if kind in self.projection_errors:
+            raise ValueError(f"the atlas {kind} mesh has no 2-D projection: {self.projection_errors[kind]}")
+        return self.raster[kind]
+
+    def image(self, thickness, kind: Optional[str] = None):
+        """The thickness image of one cartilage: float32 [H,W] for a vector [n], [K,H,W] for [K,n] (K knees at once); NaN where no
+        face of the atlas mesh owns the pixel, and NaN spreads from NaN vertices.  An array gives an array, a device tensor a device
+        tensor.  A ``KneeThickness`` gives {"FC": image, "TC": image}."""
+        if isinstance(thickness, KneeThickness):
+            return {k: self.image(thickness[k], k) for k in KINDS}
+        with torch.cuda.device(self.device):
+            return mp.thickness_image(self._raster(kind), thickness)
+
+    def scatter(self, kind: str) -> Tuple[np.ndarray, np.ndarray]:
+        """(x, y) exactly as ``project_thickness(mapped mesh, kind)`` returns them for any knee mapped onto this atlas (FC: the raw
+        angle; TC: the right plateau first): the notebook's plt.scatter coordinates, computed once."""
+        self._raster(kind)
+        return self._scatter[kind]
