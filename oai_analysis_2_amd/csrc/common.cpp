@@ -17,6 +17,12 @@ int set_error(int code, const char* fmt, ...) {
     return code;
 }
 
+int read_ints(int* host, std::initializer_list<const int*> dev, hipStream_t st) {
+    for (const int* d : dev) OAI_CHECK_HIP(hipMemcpyAsync(host++, d, sizeof(int), hipMemcpyDeviceToHost, st));
+    OAI_CHECK_HIP(hipStreamSynchronize(st));
+    return OAI_OK;
+}
+
 #ifdef OAI_DIAG
 int diag_env(const char* name, int dflt) {
     const char* v = getenv(name);

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include "../../include/oai_hip.h"
 
 namespace oai {
@@ -26,6 +27,33 @@ int set_error(int code, const char* fmt, ...);
 
 // after a kernel launch: catches bad launch configurations without synchronising
 #define OAI_CHECK_LAUNCH() OAI_CHECK_HIP(hipGetLastError())
+
+#define OAI_CHECK_WORKSPACE(who, have, need)                                                                              \
+    do {                                                                                                                  \
+        const size_t _have = (have), _need = (need);                                                                      \
+        if (_have < _need) return ::oai::set_error(OAI_ERR_WORKSPACE, who ": workspace %zu B < %zu B", _have, _need);     \
+    } while (0)
+
+static inline size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// A workspace handed out front to back in 256-byte steps.  The function that fills an entry point's struct of typed pointers with
+// take() is also its *_workspace_bytes: over a null base the pointers are null and `off` ends as the size that the same calls need.
+struct Ws {
+    char* base;
+    size_t off = 0;
+    explicit Ws(const void* workspace) : base((char*)workspace) {}
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += round256(count * sizeof(T));
+        return p;
+    }
+};
+
+// one int from each device address into host[0..), then a stream synchronise: how an entry point reads counts and flags back
+int read_ints(int* host, std::initializer_list<const int*> dev, hipStream_t st);
+
+constexpr long long kMaxFaces = 1LL << 28;     // 6 half-edges and 3 flattened corners per face stay below 2^31 - 1 (and the 0x7f7f7f7f fill)
 
 // exclusive scan of int32 (csrc/mesh.hip): out[i] = sum in[0..i), in place allowed; scratch holds scan_scratch_bytes(n) bytes
 size_t scan_scratch_bytes(long long n);

@@ -253,20 +253,18 @@ __global__ void __launch_bounds__(kT) cub_vertex_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-struct CubLayout { size_t mask, foff, voff, first, vid, scratch, total; };
-CubLayout cub_layout(long long n, long long lattice) {
-    CubLayout l;
-    size_t o = 0;
-    l.mask = o; o += al256((size_t)n);
-    l.foff = o; o += al256((size_t)(n + 1) * 4);
-    l.voff = o; o += al256((size_t)(n + 1) * 4);
-    l.first = o; o += al256((size_t)lattice * 4);
-    l.vid = o; o += al256((size_t)lattice * 4);
-    l.scratch = o; o += al256(oai::scan_scratch_bytes(n + 1));
-    l.total = o;
-    return l;
+// Workspaces: one struct of typed pointers per entry-point family, filled by one carve() that returns the bytes walked (oai::Ws,
+// common.h): over a null base that is the *_workspace_bytes answer, over the caller's buffer the carving.
+struct CubWs { unsigned char* mask; int *foff, *voff, *first, *vid, *scratch; };
+size_t carve(CubWs& w, const void* base, long long n, long long lattice) {
+    oai::Ws ws(base);
+    w.mask = ws.take<unsigned char>(n);
+    w.foff = ws.take<int>(n + 1);
+    w.voff = ws.take<int>(n + 1);
+    w.first = ws.take<int>(lattice);
+    w.vid = ws.take<int>(lattice);
+    w.scratch = ws.take<int>(oai::scan_scratch_bytes(n + 1) / 4);
+    return ws.off;
 }
 
 long long lattice_points(int D, int H, int W) { return (long long)(D + 1) * (H + 1) * (W + 1); }
@@ -285,7 +283,8 @@ extern "C" {
 
 size_t oai_cuberille_workspace_bytes(int D, int H, int W) {
     if (!size_ok(D, H, W)) return 0;
-    return cub_layout((long long)D * H * W, lattice_points(D, H, W)).total;
+    CubWs w;
+    return carve(w, nullptr, (long long)D * H * W, lattice_points(D, H, W));
 }
 
 int oai_cuberille_count(const float* vol_dev, int D, int H, int W, float iso, void* workspace_dev, size_t workspace_bytes,
@@ -295,26 +294,20 @@ int oai_cuberille_count(const float* vol_dev, int D, int H, int W, float iso, vo
     OAI_CHECK_ARG(size_ok(D, H, W), "oai_cuberille_count: volume %d x %d x %d too large for 32-bit corner slots", D, H, W);
     OAI_CHECK_ARG(!std::isnan(iso), "oai_cuberille_count: iso value is NaN");
     const long long n = (long long)D * H * W, lat = lattice_points(D, H, W);
-    const CubLayout l = cub_layout(n, lat);
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_cuberille_count: workspace %zu B < %zu B", workspace_bytes, l.total);
+    CubWs w;
+    OAI_CHECK_WORKSPACE("oai_cuberille_count", workspace_bytes, carve(w, workspace_dev, n, lat));
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    unsigned char* mask = (unsigned char*)(ws + l.mask);
-    int* foff = (int*)(ws + l.foff); int* voff = (int*)(ws + l.voff); int* first = (int*)(ws + l.first);
-    int* scratch = (int*)(ws + l.scratch);
-    cub_classify_kernel<<<oai::cdiv(n + 1, kT), kT, 0, st>>>(vol_dev, D, H, W, iso, mask, foff);
+    cub_classify_kernel<<<oai::cdiv(n + 1, kT), kT, 0, st>>>(vol_dev, D, H, W, iso, w.mask, w.foff);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(foff, foff, n + 1, scratch, st)) return rc;
-    OAI_CHECK_HIP(hipMemsetAsync(first, 0x7f, (size_t)lat * 4, st));          // 0x7f7f7f7f > every corner slot
-    cub_first_use_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(mask, foff, n, H, W, first);
+    if (int rc = oai::exclusive_scan_i32(w.foff, w.foff, n + 1, w.scratch, st)) return rc;
+    OAI_CHECK_HIP(hipMemsetAsync(w.first, 0x7f, (size_t)lat * 4, st));        // 0x7f7f7f7f > every corner slot
+    cub_first_use_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(w.mask, w.foff, n, H, W, w.first);
     OAI_CHECK_LAUNCH();
-    cub_new_count_kernel<<<oai::cdiv(n + 1, kT), kT, 0, st>>>(mask, foff, n, H, W, first, voff);
+    cub_new_count_kernel<<<oai::cdiv(n + 1, kT), kT, 0, st>>>(w.mask, w.foff, n, H, W, w.first, w.voff);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(voff, voff, n + 1, scratch, st)) return rc;
-    int tot[2];
-    OAI_CHECK_HIP(hipMemcpyAsync(&tot[0], voff + n, 4, hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipMemcpyAsync(&tot[1], foff + n, 4, hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipStreamSynchronize(st));                    // the caller sizes its output arrays from the counts
+    if (int rc = oai::exclusive_scan_i32(w.voff, w.voff, n + 1, w.scratch, st)) return rc;
+    int tot[2];                                                 // the caller sizes its output arrays from the counts
+    if (int rc = oai::read_ints(tot, {w.voff + n, w.foff + n}, st)) return rc;
     *n_verts = tot[0];
     *n_faces = tot[1];
     return OAI_OK;
@@ -329,8 +322,8 @@ int oai_cuberille_emit(const float* vol_dev, int D, int H, int W, float iso, con
     OAI_CHECK_ARG(size_ok(D, H, W), "oai_cuberille_emit: volume %d x %d x %d too large for 32-bit corner slots", D, H, W);
     OAI_CHECK_ARG(n_verts >= 0 && n_faces >= 0, "oai_cuberille_emit: negative vertex or face count");
     const long long n = (long long)D * H * W, lat = lattice_points(D, H, W);
-    const CubLayout l = cub_layout(n, lat);
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_cuberille_emit: workspace %zu B < %zu B", workspace_bytes, l.total);
+    CubWs w;
+    OAI_CHECK_WORKSPACE("oai_cuberille_emit", workspace_bytes, carve(w, workspace_dev, n, lat));
     Geo g;
     for (int k = 0; k < 3; ++k) { g.o[k] = geometry_host[k]; g.s[k] = geometry_host[3 + k]; }
     for (int k = 0; k < 9; ++k) { g.d[k] = geometry_host[6 + k]; g.m[k] = geometry_host[15 + k]; }
@@ -354,20 +347,16 @@ int oai_cuberille_emit(const float* vol_dev, int D, int H, int W, float iso, con
     g.project = project ? 1 : 0;
     g.D = D; g.H = H; g.W = W;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    const unsigned char* mask = (const unsigned char*)(ws + l.mask);
-    const int* foff = (const int*)(ws + l.foff); const int* voff = (const int*)(ws + l.voff); const int* first = (const int*)(ws + l.first);
-    int* vid = (int*)(ws + l.vid);
     if (n_verts > 0 || n_faces > 0) {
-        cub_vertex_ids_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(mask, foff, voff, n, H, W, first, vid, n_verts, reinterpret_cast<int*>(verts_dev));
+        cub_vertex_ids_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(w.mask, w.foff, w.voff, n, H, W, w.first, w.vid, n_verts, reinterpret_cast<int*>(verts_dev));
         OAI_CHECK_LAUNCH();
     }
     if (n_faces > 0) {
-        cub_faces_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(mask, foff, n, H, W, vid, triangles ? 1 : 0, flip_winding ? 1 : 0, n_faces, faces_dev);
+        cub_faces_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(w.mask, w.foff, n, H, W, w.vid, triangles ? 1 : 0, flip_winding ? 1 : 0, n_faces, faces_dev);
         OAI_CHECK_LAUNCH();
     }
     if (n_verts > 0) {
-        cub_vertex_kernel<<<oai::cdiv(n_verts, kT), kT, 0, st>>>(vol_dev, g, voff, n, n_verts, verts_dev, steps_dev);
+        cub_vertex_kernel<<<oai::cdiv(n_verts, kT), kT, 0, st>>>(vol_dev, g, w.voff, n, n_verts, verts_dev, steps_dev);
         OAI_CHECK_LAUNCH();
     }
     return OAI_OK;

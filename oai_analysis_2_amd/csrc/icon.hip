@@ -483,25 +483,25 @@ Dims level_dims(int D, int H, int W) {
     return r;
 }
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+// cat_0..cat_4 and the bottom tensor of one tallUNet2 forward, carved from ws; returns the floats they take (with ws = null: only that)
+size_t unet_carve(float* ws, const Dims& dm, float* cat[5], float*& bottom) {
+    oai::Ws w(ws);
+    for (int l = 0; l < 5; ++l) cat[l] = w.take<float>((size_t)(kUpOut[l] + kDown[l]) * dm.vox[l]);
+    bottom = w.take<float>((size_t)kDown[5] * dm.vox[5]);
+    return w.off / 4;
+}
 
-// floats needed by one tallUNet2 forward at (D,H,W): cat_0..cat_4 and the bottom tensor
 size_t unet_ws_floats(int D, int H, int W) {
-    const Dims dm = level_dims(D, H, W);
-    size_t n = 0;
-    for (int l = 0; l < 5; ++l) n += align256((size_t)(kUpOut[l] + kDown[l]) * dm.vox[l] * 4) / 4;
-    n += align256((size_t)kDown[5] * dm.vox[5] * 4) / 4;
-    return n;
+    float *cat[5], *bottom;
+    return unet_carve(nullptr, level_dims(D, H, W), cat, bottom);
 }
 
 int unet_forward(const NetWeights& nw, bool pad_front, const float* a, const float* b, int D, int H, int W, float* out,
                  float* ws, hipStream_t st) {
     const Dims dm = level_dims(D, H, W);
     // every axis must survive five halvings with a >= 2 input to each pooling (avg_pool3d needs size >= kernel)
-    float* cat[5];
-    size_t o = 0;
-    for (int l = 0; l < 5; ++l) { cat[l] = ws + o; o += align256((size_t)(kUpOut[l] + kDown[l]) * dm.vox[l] * 4) / 4; }
-    float* bottom = ws + o;
+    float *cat[5], *bottom;
+    unet_carve(ws, dm, cat, bottom);
     // x = cat([a, b], 1) lives in the skip slice of cat_0
     if (int rc = copy_f32(a, cat[0] + (size_t)kUpOut[0] * dm.vox[0], dm.vox[0], st)) return rc;
     if (int rc = copy_f32(b, cat[0] + (size_t)(kUpOut[0] + 1) * dm.vox[0], dm.vox[0], st)) return rc;
@@ -598,12 +598,12 @@ struct TreePlanner {
     oai_icon* h;
     long long vox[8];
     int gd[8][3];
-    size_t cur = 0;               // floats
+    oai::Ws ws{nullptr};          // sizes only: the plan holds offsets in floats
     std::vector<std::pair<std::pair<size_t, int>, size_t>> pooled;      // (source offset, source level) -> pooled buffer
     std::vector<char> node_used, net_used;
     int err = OAI_OK;
 
-    size_t take(size_t floats) { size_t o = cur; cur += align256(floats * 4) / 4; return o; }
+    size_t take(size_t floats) { const size_t o = ws.off / 4; ws.take<float>(floats); return o; }
 
     int fail(const char* msg, int v) { if (!err) err = oai::set_error(OAI_ERR_ARG, msg, v); return err; }
 
@@ -691,7 +691,7 @@ int plan_tree(oai_icon* h) {
     int top = 0;
     while (top < 8 && !h->nets_at_level[top]) ++top;          // the largest grid a U-Net runs on sizes the shared U-Net scratch
     h->off_unet = P.take(unet_ws_floats(P.gd[top][0], P.gd[top][1], P.gd[top][2]));
-    h->ws_floats = P.cur;
+    h->ws_floats = P.ws.off / 4;
     return OAI_OK;
 }
 
@@ -774,8 +774,7 @@ int oai_icon_unet_forward(oai_icon* h, int which, const float* a, const float* b
     OAI_CHECK_ARG(h && a && b && out && ws, "oai_icon_unet_forward: null pointer");
     OAI_CHECK_ARG(which >= 0 && which < (int)h->net.size(), "oai_icon_unet_forward: net index must be 0..%d", (int)h->net.size() - 1);
     OAI_CHECK_ARG(dims_ok(D, H, W), "oai_icon_unet_forward: %dx%dx%d too small for five 2x poolings (each axis >= 17)", D, H, W);
-    if (unet_ws_floats(D, H, W) * 4 > ws_bytes)
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_icon_unet_forward: workspace %zu B < %zu B", ws_bytes, unet_ws_floats(D, H, W) * 4);
+    OAI_CHECK_WORKSPACE("oai_icon_unet_forward", ws_bytes, unet_ws_floats(D, H, W) * 4);
     return unet_forward(h->net[which], h->pad_front, a, b, D, H, W, out, (float*)ws, (hipStream_t)stream);
 }
 
@@ -811,8 +810,7 @@ static int icon_forward_body(oai_icon* h, float* ws, hipStream_t st) {
 int oai_icon_forward(oai_icon* h, const float* A, const float* B, float* phi, void* ws, size_t ws_bytes, void* stream) {
     OAI_CHECK_ARG(h && A && B && phi && ws, "oai_icon_forward: null pointer");
     const long long vh = (long long)h->D * h->H * h->W;
-    if (h->ws_floats * sizeof(float) > ws_bytes)
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_icon_forward: workspace %zu B < %zu B", ws_bytes, h->ws_floats * sizeof(float));
+    OAI_CHECK_WORKSPACE("oai_icon_forward", ws_bytes, h->ws_floats * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* wsf = (float*)ws;
     if (int rc = copy_f32(A, wsf + h->off_A, vh, st)) return rc;

@@ -442,35 +442,28 @@ __global__ void __launch_bounds__(256) grid_distance_kernel(const float* __restr
     dist[i] = sqrtf(best);
 }
 
-struct GridLayout { size_t count, start, list, scratch, total; };
-GridLayout grid_layout(long long ncells, long long nt) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    GridLayout l;
-    size_t o = 0;
-    l.count = o; o += al((size_t)(ncells + 1) * 4);
-    l.start = o; o += al((size_t)(ncells + 1) * 4);
-    l.list = o; o += al((size_t)nt * 8 * 4);
-    l.scratch = o; o += al(scan_scratch_ints(ncells + 1) * 4);
-    l.total = o;
-    return l;
+// Workspaces: one struct of typed pointers per entry-point family, filled by one carve() that returns the bytes walked (oai::Ws,
+// common.h): over a null base that is the *_workspace_bytes answer, over the caller's buffer the carving.
+struct GridWs { int *count, *start, *list, *scratch; };
+size_t carve(GridWs& w, const void* base, long long ncells, long long nt) {
+    oai::Ws ws(base);
+    w.count = ws.take<int>(ncells + 1);
+    w.start = ws.take<int>(ncells + 1);
+    w.list = ws.take<int>(nt * 8);
+    w.scratch = ws.take<int>(scan_scratch_ints(ncells + 1));
+    return ws.off;
 }
 
-struct McLayout {
-    size_t flags, vcount, tcount, voff, toff, scratch, total;
-};
-
-McLayout mc_layout(long long n) {
-    McLayout l;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    size_t o = 0;
-    l.flags = o; o += al((size_t)n);
-    l.vcount = o; o += al((size_t)n * 4);
-    l.tcount = o; o += al((size_t)n * 4);
-    l.voff = o; o += al((size_t)n * 4);
-    l.toff = o; o += al((size_t)n * 4);
-    l.scratch = o; o += al(scan_scratch_ints(n) * 4);
-    l.total = o;
-    return l;
+struct McWs { unsigned char* flags; int *vcount, *tcount, *voff, *toff, *scratch; };
+size_t carve(McWs& w, const void* base, long long n) {
+    oai::Ws ws(base);
+    w.flags = ws.take<unsigned char>(n);
+    w.vcount = ws.take<int>(n);
+    w.tcount = ws.take<int>(n);
+    w.voff = ws.take<int>(n);
+    w.toff = ws.take<int>(n);
+    w.scratch = ws.take<int>(scan_scratch_ints(n));
+    return ws.off;
 }
 
 }  // namespace
@@ -490,7 +483,8 @@ int oai_mc_table(signed char* out_256x16) {
 
 size_t oai_mc_workspace_bytes(int D, int H, int W) {
     if (D < 2 || H < 2 || W < 2) return 0;
-    return mc_layout((long long)D * H * W).total;
+    McWs w;
+    return carve(w, nullptr, (long long)D * H * W);
 }
 
 int oai_mc_count(const float* vol_dev, int D, int H, int W, float iso, void* ws_dev, size_t ws_bytes,
@@ -499,23 +493,16 @@ int oai_mc_count(const float* vol_dev, int D, int H, int W, float iso, void* ws_
     OAI_CHECK_ARG(D >= 2 && H >= 2 && W >= 2, "oai_mc_count: every axis needs at least 2 voxels");
     const long long n = (long long)D * H * W;
     OAI_CHECK_ARG(n < (1LL << 31) / 3, "oai_mc_count: volume too large for 32-bit vertex ids");
-    const McLayout l = mc_layout(n);
-    if (ws_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_mc_count: workspace %zu B < %zu B", ws_bytes, l.total);
+    McWs w;
+    OAI_CHECK_WORKSPACE("oai_mc_count", ws_bytes, carve(w, ws_dev, n));
     if (int rc = upload_tables()) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)ws_dev;
-    int* vcount = (int*)(ws + l.vcount); int* tcount = (int*)(ws + l.tcount);
-    int* voff = (int*)(ws + l.voff); int* toff = (int*)(ws + l.toff);
-    mc_classify_kernel<<<oai::cdiv(n, 256), 256, 0, st>>>(vol_dev, D, H, W, iso, (unsigned char*)(ws + l.flags), vcount, tcount);
+    mc_classify_kernel<<<oai::cdiv(n, 256), 256, 0, st>>>(vol_dev, D, H, W, iso, w.flags, w.vcount, w.tcount);
     OAI_CHECK_LAUNCH();
-    if (int rc = exclusive_scan(vcount, voff, n, (int*)(ws + l.scratch), st)) return rc;
-    if (int rc = exclusive_scan(tcount, toff, n, (int*)(ws + l.scratch), st)) return rc;
-    int last[4];
-    OAI_CHECK_HIP(hipMemcpyAsync(&last[0], vcount + n - 1, 4, hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipMemcpyAsync(&last[1], voff + n - 1, 4, hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipMemcpyAsync(&last[2], tcount + n - 1, 4, hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipMemcpyAsync(&last[3], toff + n - 1, 4, hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipStreamSynchronize(st));                    // the caller sizes its output arrays from the counts
+    if (int rc = exclusive_scan(w.vcount, w.voff, n, w.scratch, st)) return rc;
+    if (int rc = exclusive_scan(w.tcount, w.toff, n, w.scratch, st)) return rc;
+    int last[4];                                                // the caller sizes its output arrays from the counts
+    if (int rc = oai::read_ints(last, {w.vcount + n - 1, w.voff + n - 1, w.tcount + n - 1, w.toff + n - 1}, st)) return rc;
     *n_verts = (long long)last[0] + last[1];
     *n_tris = (long long)last[2] + last[3];
     return OAI_OK;
@@ -526,11 +513,10 @@ int oai_mc_emit(const float* vol_dev, int D, int H, int W, float iso, const floa
     OAI_CHECK_ARG(vol_dev && ws_dev && spacing_xyz, "oai_mc_emit: null pointer");
     OAI_CHECK_ARG(D >= 2 && H >= 2 && W >= 2, "oai_mc_emit: every axis needs at least 2 voxels");
     const long long n = (long long)D * H * W;
-    const McLayout l = mc_layout(n);
-    const char* ws = (const char*)ws_dev;
+    McWs w;                                                     // read only: the kernel takes these pointers as const
+    carve(w, ws_dev, n);
     mc_emit_kernel<<<oai::cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(vol_dev, D, H, W, iso, spacing_xyz[0], spacing_xyz[1], spacing_xyz[2],
-                                                                        (const unsigned char*)(ws + l.flags), (const int*)(ws + l.voff),
-                                                                        (const int*)(ws + l.toff), verts_dev, faces_dev);
+                                                                        w.flags, w.voff, w.toff, verts_dev, faces_dev);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
@@ -568,7 +554,8 @@ int oai_mesh_point_distance(const float* points_dev, long long n_points, const f
 
 size_t oai_mesh_grid_workspace_bytes(const int grid_dims_xyz[3], long long n_tris) {
     if (!grid_dims_xyz || n_tris <= 0) return 0;
-    return grid_layout((long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2], n_tris).total;
+    GridWs w;
+    return carve(w, nullptr, (long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2], n_tris);
 }
 
 int oai_mesh_point_distance_grid(const float* points_dev, long long n_points, const float* verts_dev, const int* faces_dev, long long n_tris,
@@ -579,28 +566,25 @@ int oai_mesh_point_distance_grid(const float* points_dev, long long n_points, co
     OAI_CHECK_ARG(grid_dims_xyz[0] > 0 && grid_dims_xyz[1] > 0 && grid_dims_xyz[2] > 0, "oai_mesh_point_distance_grid: empty grid");
     const long long ncells = (long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2];
     OAI_CHECK_ARG(ncells < (1LL << 30), "oai_mesh_point_distance_grid: grid too fine");
-    const GridLayout l = grid_layout(ncells, n_tris);
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_point_distance_grid: workspace %zu B < %zu B", workspace_bytes, l.total);
+    GridWs w;
+    OAI_CHECK_WORKSPACE("oai_mesh_point_distance_grid", workspace_bytes, carve(w, workspace_dev, ncells, n_tris));
     if (n_points == 0) return OAI_OK;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    int* count = (int*)(ws + l.count); int* start = (int*)(ws + l.start); int* list = (int*)(ws + l.list);
     GridDesc g;
     for (int k = 0; k < 3; ++k) { g.lo[k] = grid_lo_xyz[k]; g.n[k] = grid_dims_xyz[k]; }
     g.h = cell_size; g.inv_h = 1.0f / cell_size;
-    OAI_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)(ncells + 1) * 4, st));
-    grid_bin_kernel<false><<<oai::cdiv(n_tris, 256), 256, 0, st>>>(verts_dev, faces_dev, n_tris, g, count, nullptr, nullptr);
+    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    grid_bin_kernel<false><<<oai::cdiv(n_tris, 256), 256, 0, st>>>(verts_dev, faces_dev, n_tris, g, w.count, nullptr, nullptr);
     OAI_CHECK_LAUNCH();
-    if (int rc = exclusive_scan(count, start, ncells + 1, (int*)(ws + l.scratch), st)) return rc;
+    if (int rc = exclusive_scan(w.count, w.start, ncells + 1, w.scratch, st)) return rc;
     int total = 0;
-    OAI_CHECK_HIP(hipMemcpyAsync(&total, start + ncells, 4, hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipStreamSynchronize(st));
+    if (int rc = oai::read_ints(&total, {w.start + ncells}, st)) return rc;
     if ((long long)total > n_tris * 8)          // a triangle longer than a cell overlaps more than 8 cells: the caller's cell size is too small
         return oai::set_error(OAI_ERR_ARG, "oai_mesh_point_distance_grid: %d triangle-cell pairs > 8 per triangle; cell_size must be >= the longest edge", total);
-    OAI_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)(ncells + 1) * 4, st));
-    grid_bin_kernel<true><<<oai::cdiv(n_tris, 256), 256, 0, st>>>(verts_dev, faces_dev, n_tris, g, count, start, list);
+    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    grid_bin_kernel<true><<<oai::cdiv(n_tris, 256), 256, 0, st>>>(verts_dev, faces_dev, n_tris, g, w.count, w.start, w.list);
     OAI_CHECK_LAUNCH();
-    grid_distance_kernel<<<oai::cdiv(n_points, 256), 256, 0, st>>>(points_dev, n_points, verts_dev, faces_dev, g, start, list, dist_dev);
+    grid_distance_kernel<<<oai::cdiv(n_points, 256), 256, 0, st>>>(points_dev, n_points, verts_dev, faces_dev, g, w.start, w.list, dist_dev);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }

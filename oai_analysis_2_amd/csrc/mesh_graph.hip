@@ -22,7 +22,7 @@
 namespace {
 
 constexpr int kT = 256;
-constexpr long long kMaxFaces = 1LL << 28;     // 6 half-edges per face stay below 2^31
+using oai::kMaxFaces;
 constexpr int kBatch = 4;                      // hook / jump rounds launched between two reads of the "changed" flags
 constexpr int kRedBlocks = 512;                // blocks of the grid-parameter reductions
 
@@ -75,20 +75,19 @@ __global__ void __launch_bounds__(kT) jump_kernel(int* parent, long long n) {
     if (p != p0) __hip_atomic_store(parent + i, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-struct CompLayout { size_t changed, bad, total; };
-CompLayout comp_layout() {
-    CompLayout l;
-    l.changed = 0;
-    l.bad = 256;
-    l.total = 512;
-    return l;
+// Workspaces: one struct of typed pointers per entry-point family, filled by one carve() that returns the bytes walked (oai::Ws,
+// common.h): over a null base that is the *_workspace_bytes answer, over the caller's buffer the carving.
+struct CompWs { int *changed, *bad; };
+size_t carve(CompWs& w, const void* base) {
+    oai::Ws ws(base);
+    w.changed = ws.take<int>(kBatch);
+    w.bad = ws.take<int>(1);
+    return ws.off;
 }
 
 // labels into label_dev (n_verts); reads the flags after every kBatch rounds (synchronises the stream)
-int components(const int* faces, long long n_faces, long long n_verts, char* ws, int* label, int* rounds_out, hipStream_t st, const char* who) {
-    const CompLayout l = comp_layout();
-    int* changed = (int*)(ws + l.changed);
-    int* bad = (int*)(ws + l.bad);
+int components(const int* faces, long long n_faces, long long n_verts, const CompWs& w, int* label, int* rounds_out, hipStream_t st, const char* who) {
+    int *changed = w.changed, *bad = w.bad;
     iota_kernel<<<oai::cdiv(n_verts, kT), kT, 0, st>>>(label, n_verts);
     OAI_CHECK_LAUNCH();
     int rounds = 0;
@@ -172,21 +171,18 @@ __global__ void __launch_bounds__(kT) keep_faces_scatter_kernel(const int* __res
     for (int k = 0; k < 3; ++k) faces_out[3 * o + k] = remap[faces[3 * i + k]];
 }
 
-struct KeepLayout { size_t comp, label, cells, keep, fpos, used, remap, scratch, total; };
-KeepLayout keep_layout(long long nv, long long nf) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    KeepLayout l;
-    size_t o = 0;
-    l.comp = o; o += al(comp_layout().total);
-    l.label = o; o += al((size_t)nv * 4);
-    l.cells = o; o += al((size_t)nv * 4);
-    l.keep = o; o += al((size_t)(nf + 1) * 4);
-    l.fpos = o; o += al((size_t)(nf + 1) * 4);
-    l.used = o; o += al((size_t)(nv + 1) * 4);
-    l.remap = o; o += al((size_t)(nv + 1) * 4);
-    l.scratch = o; o += al(std::max(oai::scan_scratch_bytes(nf + 1), oai::scan_scratch_bytes(nv + 1)));
-    l.total = o;
-    return l;
+struct KeepWs { CompWs comp; int *label, *cells, *keep, *fpos, *used, *remap, *scratch; };
+size_t carve(KeepWs& w, const void* base, long long nv, long long nf) {
+    oai::Ws ws(base);
+    ws.off = carve(w.comp, base);
+    w.label = ws.take<int>(nv);
+    w.cells = ws.take<int>(nv);
+    w.keep = ws.take<int>(nf + 1);
+    w.fpos = ws.take<int>(nf + 1);
+    w.used = ws.take<int>(nv + 1);
+    w.remap = ws.take<int>(nv + 1);
+    w.scratch = ws.take<int>(std::max(oai::scan_scratch_bytes(nf + 1), oai::scan_scratch_bytes(nv + 1)) / 4);
+    return ws.off;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -288,20 +284,17 @@ __global__ void __launch_bounds__(kT) compact_kernel(const int* __restrict__ sta
     for (int i = 0; i < u; ++i) dst[i] = src[i];
 }
 
-struct AdjLayout { size_t deg, start, cursor, half, ucount, bad, scratch, total; };
-AdjLayout adj_layout(long long nv, long long nf) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    AdjLayout l;
-    size_t o = 0;
-    l.deg = o; o += al((size_t)(nv + 1) * 4);
-    l.start = o; o += al((size_t)(nv + 1) * 4);
-    l.cursor = o; o += al((size_t)nv * 4);
-    l.half = o; o += al((size_t)nf * 6 * 4);
-    l.ucount = o; o += al((size_t)(nv + 1) * 4);
-    l.bad = o; o += 256;
-    l.scratch = o; o += al(oai::scan_scratch_bytes(nv + 1));
-    l.total = o;
-    return l;
+struct AdjWs { int *deg, *start, *cursor, *half, *ucount, *bad, *scratch; };
+size_t carve(AdjWs& w, const void* base, long long nv, long long nf) {
+    oai::Ws ws(base);
+    w.deg = ws.take<int>(nv + 1);
+    w.start = ws.take<int>(nv + 1);
+    w.cursor = ws.take<int>(nv);
+    w.half = ws.take<int>(nf * 6);
+    w.ucount = ws.take<int>(nv + 1);
+    w.bad = ws.take<int>(1);
+    w.scratch = ws.take<int>(oai::scan_scratch_bytes(nv + 1) / 4);
+    return ws.off;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -391,7 +384,8 @@ extern "C" {
 
 size_t oai_mesh_components_workspace_bytes(long long n_verts, long long n_faces) {
     if (n_verts <= 0 || n_verts >= (1LL << 31) || n_faces < 0 || n_faces >= kMaxFaces) return 0;
-    return comp_layout().total;
+    CompWs w;
+    return carve(w, nullptr);
 }
 
 int oai_mesh_components(const int* faces_dev, long long n_faces, long long n_verts, void* workspace_dev, size_t workspace_bytes, int* label_dev,
@@ -399,14 +393,15 @@ int oai_mesh_components(const int* faces_dev, long long n_faces, long long n_ver
     OAI_CHECK_ARG(workspace_dev && label_dev && (faces_dev || n_faces == 0), "oai_mesh_components: null pointer");
     OAI_CHECK_ARG(n_faces >= 0 && n_faces < kMaxFaces, "oai_mesh_components: needs 0 .. 2^28-1 faces (got %lld)", n_faces);
     OAI_CHECK_ARG(n_verts >= 1 && n_verts < (1LL << 31), "oai_mesh_components: needs 1 .. 2^31-1 vertices (got %lld)", n_verts);
-    const CompLayout l = comp_layout();
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_components: workspace %zu B < %zu B", workspace_bytes, l.total);
-    return components(faces_dev, n_faces, n_verts, (char*)workspace_dev, label_dev, rounds_host, (hipStream_t)stream, "oai_mesh_components");
+    CompWs w;
+    OAI_CHECK_WORKSPACE("oai_mesh_components", workspace_bytes, carve(w, workspace_dev));
+    return components(faces_dev, n_faces, n_verts, w, label_dev, rounds_host, (hipStream_t)stream, "oai_mesh_components");
 }
 
 size_t oai_mesh_keep_large_regions_workspace_bytes(long long n_verts, long long n_faces) {
     if (n_verts < 0 || n_verts >= (1LL << 31) || n_faces < 0 || n_faces >= kMaxFaces) return 0;
-    return keep_layout(n_verts, n_faces).total;
+    KeepWs w;
+    return carve(w, nullptr, n_verts, n_faces);
 }
 
 int oai_mesh_keep_large_regions(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, long long min_cells,
@@ -417,35 +412,28 @@ int oai_mesh_keep_large_regions(const float* verts_dev, long long n_verts, const
     OAI_CHECK_ARG(n_faces >= 0 && n_faces < kMaxFaces, "oai_mesh_keep_large_regions: needs 0 .. 2^28-1 faces (got %lld)", n_faces);
     OAI_CHECK_ARG(n_verts >= 0 && n_verts < (1LL << 31), "oai_mesh_keep_large_regions: needs 0 .. 2^31-1 vertices (got %lld)", n_verts);
     OAI_CHECK_ARG(n_faces == 0 || n_verts > 0, "oai_mesh_keep_large_regions: faces without vertices");
-    const KeepLayout l = keep_layout(n_verts, n_faces);
-    if (workspace_bytes < l.total)
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_keep_large_regions: workspace %zu B < %zu B", workspace_bytes, l.total);
+    KeepWs w;
+    OAI_CHECK_WORKSPACE("oai_mesh_keep_large_regions", workspace_bytes, carve(w, workspace_dev, n_verts, n_faces));
     *n_verts_out_host = 0;
     *n_faces_out_host = 0;
     if (n_faces == 0) return OAI_OK;                   // the host returns verts[:0] and the empty face list
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    int* label = (int*)(ws + l.label); int* cells = (int*)(ws + l.cells);
-    int* keep = (int*)(ws + l.keep); int* fpos = (int*)(ws + l.fpos);
-    int* used = (int*)(ws + l.used); int* remap = (int*)(ws + l.remap); int* scratch = (int*)(ws + l.scratch);
     // validates every face index (error before anything below reads one)
-    if (int rc = components(faces_dev, n_faces, n_verts, ws + l.comp, label, nullptr, st, "oai_mesh_keep_large_regions")) return rc;
-    OAI_CHECK_HIP(hipMemsetAsync(cells, 0, (size_t)n_verts * 4, st));
-    OAI_CHECK_HIP(hipMemsetAsync(used, 0, (size_t)(n_verts + 1) * 4, st));
-    region_cells_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, label, cells);
+    if (int rc = components(faces_dev, n_faces, n_verts, w.comp, w.label, nullptr, st, "oai_mesh_keep_large_regions")) return rc;
+    OAI_CHECK_HIP(hipMemsetAsync(w.cells, 0, (size_t)n_verts * 4, st));
+    OAI_CHECK_HIP(hipMemsetAsync(w.used, 0, (size_t)(n_verts + 1) * 4, st));
+    region_cells_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, w.label, w.cells);
     OAI_CHECK_LAUNCH();
-    keep_faces_kernel<<<oai::cdiv(n_faces + 1, kT), kT, 0, st>>>(faces_dev, n_faces, label, cells, min_cells, keep, used);
+    keep_faces_kernel<<<oai::cdiv(n_faces + 1, kT), kT, 0, st>>>(faces_dev, n_faces, w.label, w.cells, min_cells, w.keep, w.used);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(keep, fpos, n_faces + 1, scratch, st)) return rc;
-    if (int rc = oai::exclusive_scan_i32(used, remap, n_verts + 1, scratch, st)) return rc;
-    keep_verts_kernel<<<oai::cdiv(n_verts, kT), kT, 0, st>>>(verts_dev, n_verts, used, remap, verts_out_dev);
+    if (int rc = oai::exclusive_scan_i32(w.keep, w.fpos, n_faces + 1, w.scratch, st)) return rc;
+    if (int rc = oai::exclusive_scan_i32(w.used, w.remap, n_verts + 1, w.scratch, st)) return rc;
+    keep_verts_kernel<<<oai::cdiv(n_verts, kT), kT, 0, st>>>(verts_dev, n_verts, w.used, w.remap, verts_out_dev);
     OAI_CHECK_LAUNCH();
-    keep_faces_scatter_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, keep, fpos, remap, faces_out_dev);
+    keep_faces_scatter_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, w.keep, w.fpos, w.remap, faces_out_dev);
     OAI_CHECK_LAUNCH();
     int counts[2];
-    OAI_CHECK_HIP(hipMemcpyAsync(&counts[0], remap + n_verts, sizeof(int), hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipMemcpyAsync(&counts[1], fpos + n_faces, sizeof(int), hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipStreamSynchronize(st));
+    if (int rc = oai::read_ints(counts, {w.remap + n_verts, w.fpos + n_faces}, st)) return rc;
     *n_verts_out_host = counts[0];
     *n_faces_out_host = counts[1];
     return OAI_OK;
@@ -453,7 +441,8 @@ int oai_mesh_keep_large_regions(const float* verts_dev, long long n_verts, const
 
 size_t oai_mesh_adjacency_workspace_bytes(long long n_verts, long long n_faces) {
     if (n_verts < 0 || n_verts >= (1LL << 31) || n_faces < 0 || n_faces >= kMaxFaces) return 0;
-    return adj_layout(n_verts, n_faces).total;
+    AdjWs w;
+    return carve(w, nullptr, n_verts, n_faces);
 }
 
 int oai_mesh_adjacency(const int* faces_dev, long long n_faces, long long n_verts, void* workspace_dev, size_t workspace_bytes, int* offsets_dev,
@@ -461,35 +450,30 @@ int oai_mesh_adjacency(const int* faces_dev, long long n_faces, long long n_vert
     OAI_CHECK_ARG(workspace_dev && offsets_dev && n_nbrs_host && (n_faces == 0 || (faces_dev && nbrs_dev)), "oai_mesh_adjacency: null pointer");
     OAI_CHECK_ARG(n_faces >= 0 && n_faces < kMaxFaces, "oai_mesh_adjacency: needs 0 .. 2^28-1 faces (got %lld)", n_faces);
     OAI_CHECK_ARG(n_verts >= 0 && n_verts < (1LL << 31), "oai_mesh_adjacency: needs 0 .. 2^31-1 vertices (got %lld)", n_verts);
-    const AdjLayout l = adj_layout(n_verts, n_faces);
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_adjacency: workspace %zu B < %zu B", workspace_bytes, l.total);
+    AdjWs w;
+    OAI_CHECK_WORKSPACE("oai_mesh_adjacency", workspace_bytes, carve(w, workspace_dev, n_verts, n_faces));
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    int* deg = (int*)(ws + l.deg); int* start = (int*)(ws + l.start); int* cursor = (int*)(ws + l.cursor);
-    int* half = (int*)(ws + l.half); int* ucount = (int*)(ws + l.ucount); int* bad = (int*)(ws + l.bad);
-    OAI_CHECK_HIP(hipMemsetAsync(deg, 0, (size_t)(n_verts + 1) * 4, st));
-    OAI_CHECK_HIP(hipMemsetAsync(cursor, 0, (size_t)n_verts * 4, st));
-    OAI_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+    OAI_CHECK_HIP(hipMemsetAsync(w.deg, 0, (size_t)(n_verts + 1) * 4, st));
+    OAI_CHECK_HIP(hipMemsetAsync(w.cursor, 0, (size_t)n_verts * 4, st));
+    OAI_CHECK_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), st));
     if (n_faces > 0) {
-        degree_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, deg, bad);
+        degree_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, w.deg, w.bad);
         OAI_CHECK_LAUNCH();
     }
-    if (int rc = oai::exclusive_scan_i32(deg, start, n_verts + 1, (int*)(ws + l.scratch), st)) return rc;
+    if (int rc = oai::exclusive_scan_i32(w.deg, w.start, n_verts + 1, w.scratch, st)) return rc;
     if (n_faces > 0) {
-        scatter_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, start, cursor, half);
+        scatter_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, w.start, w.cursor, w.half);
         OAI_CHECK_LAUNCH();
     }
-    sort_unique_kernel<<<oai::cdiv(n_verts + 1, kT), kT, 0, st>>>(start, n_verts, half, ucount);
+    sort_unique_kernel<<<oai::cdiv(n_verts + 1, kT), kT, 0, st>>>(w.start, n_verts, w.half, w.ucount);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(ucount, offsets_dev, n_verts + 1, (int*)(ws + l.scratch), st)) return rc;
+    if (int rc = oai::exclusive_scan_i32(w.ucount, offsets_dev, n_verts + 1, w.scratch, st)) return rc;
     if (n_verts > 0) {
-        compact_kernel<<<oai::cdiv(n_verts, kT), kT, 0, st>>>(start, offsets_dev, n_verts, half, nbrs_dev);
+        compact_kernel<<<oai::cdiv(n_verts, kT), kT, 0, st>>>(w.start, offsets_dev, n_verts, w.half, nbrs_dev);
         OAI_CHECK_LAUNCH();
     }
     int h[2];
-    OAI_CHECK_HIP(hipMemcpyAsync(&h[0], offsets_dev + n_verts, sizeof(int), hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipMemcpyAsync(&h[1], bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipStreamSynchronize(st));
+    if (int rc = oai::read_ints(h, {offsets_dev + n_verts, w.bad}, st)) return rc;
     if (h[1]) return oai::set_error(OAI_ERR_ARG, "oai_mesh_adjacency: a face indexes outside the %lld vertices", n_verts);
     *n_nbrs_host = h[0];
     return OAI_OK;
@@ -503,7 +487,7 @@ int oai_mesh_grid_params(const float* verts_dev, long long n_verts, const int* f
     OAI_CHECK_ARG(n_verts >= 1 && n_verts < (1LL << 31), "oai_mesh_grid_params: needs 1 .. 2^31-1 vertices (got %lld)", n_verts);
     OAI_CHECK_ARG(n_faces >= 0 && n_faces < kMaxFaces, "oai_mesh_grid_params: needs 0 .. 2^28-1 faces (got %lld)", n_faces);
     static_assert(sizeof(GridAcc) <= 256, "grid accumulator outgrew its workspace");
-    if (workspace_bytes < 256) return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_grid_params: workspace %zu B < 256 B", workspace_bytes);
+    OAI_CHECK_WORKSPACE("oai_mesh_grid_params", workspace_bytes, oai_mesh_grid_params_workspace_bytes());
     hipStream_t st = (hipStream_t)stream;
     GridAcc* acc = (GridAcc*)workspace_dev;
     grid_init_kernel<<<1, 64, 0, st>>>(acc);

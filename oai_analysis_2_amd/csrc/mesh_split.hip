@@ -605,8 +605,6 @@ __global__ void __launch_bounds__(kT) submesh_scatter_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 int slabs_of(int mesh_type) { return mesh_type == OAI_MESH_FC ? kMaxSlabs : 1; }
 int dims_of(int mesh_type) { return mesh_type == OAI_MESH_FC ? 9 : 6; }
 
@@ -614,47 +612,49 @@ int dims_of(int mesh_type) { return mesh_type == OAI_MESH_FC ? 9 : 6; }
 // exactly at a seam; oai_mesh_split_features refuses a mesh with more of them than this)
 long long slab_capacity(long long n_faces, int mesh_type) { return mesh_type == OAI_MESH_FC ? n_faces + n_faces / 64 + 64 : n_faces; }
 
-// the features part first, the per-run part (labels, distances: one row set per init) last, so that the features call needs only
-// the layout of n_init = 1
-struct SplitLayout { size_t stats, partials, bad, mask, flags, pos, feat, face_of, runs, slabs, scratch, labels, dist, total; long long cap; };
-SplitLayout split_layout(long long n_faces, int mesh_type, int n_init) {
+// Workspaces: one struct of typed pointers per entry-point family, filled by one carve() that returns the bytes walked (oai::Ws,
+// common.h): over a null base that is the *_workspace_bytes answer, over the caller's buffer the carving.
+// The features part first, the per-run part (labels, distances: one row set per init) last, so that the features call needs only
+// the bytes of n_init = 1.
+struct SplitWs {
+    Stats* stats; MinMax* partials; int* bad; signed char* mask; int *flags, *pos; double* feat; int* face_of; RunOut* runs; SlabOut* slabs;
+    int* scratch; signed char* labels; double* dist;
+    long long cap;
+};
+size_t carve(SplitWs& w, const void* base, long long n_faces, int mesh_type, int n_init) {
     const int S = slabs_of(mesh_type), D = dims_of(mesh_type);
-    SplitLayout l;
-    l.cap = slab_capacity(n_faces, mesh_type);
-    size_t o = 0;
-    l.stats = o; o += al256(sizeof(Stats));
-    l.partials = o; o += al256(kRedBlocks * sizeof(MinMax));
-    l.bad = o; o += al256(sizeof(int));
-    l.mask = o; o += al256((size_t)n_faces);
-    l.flags = o; o += al256((size_t)S * (n_faces + 1) * 4);
-    l.pos = o; o += al256((size_t)S * (n_faces + 1) * 4);
-    l.feat = o; o += al256((size_t)l.cap * D * sizeof(double));
-    l.face_of = o; o += al256((size_t)l.cap * 4);
-    l.runs = o; o += al256(kMaxRuns * sizeof(RunOut));
-    l.slabs = o; o += al256(kMaxSlabs * sizeof(SlabOut));
-    l.scratch = o; o += al256(oai::scan_scratch_bytes(n_faces + 1));
-    l.labels = o; o += al256((size_t)n_init * l.cap);
-    l.dist = o; o += al256((size_t)n_init * l.cap * sizeof(double));
-    l.total = o;
-    return l;
+    oai::Ws ws(base);
+    w.cap = slab_capacity(n_faces, mesh_type);
+    w.stats = ws.take<Stats>(1);
+    w.partials = ws.take<MinMax>(kRedBlocks);
+    w.bad = ws.take<int>(1);
+    w.mask = ws.take<signed char>(n_faces);
+    w.flags = ws.take<int>((size_t)S * (n_faces + 1));
+    w.pos = ws.take<int>((size_t)S * (n_faces + 1));
+    w.feat = ws.take<double>((size_t)w.cap * D);
+    w.face_of = ws.take<int>(w.cap);
+    w.runs = ws.take<RunOut>(kMaxRuns);
+    w.slabs = ws.take<SlabOut>(kMaxSlabs);
+    w.scratch = ws.take<int>(oai::scan_scratch_bytes(n_faces + 1) / 4);
+    w.labels = ws.take<signed char>((size_t)n_init * w.cap);
+    w.dist = ws.take<double>((size_t)n_init * w.cap);
+    return ws.off;
 }
 
-struct SubLayout { size_t flag, fpos, first, occ, rank, bad, scratch, total; };
-SubLayout sub_layout(long long n_verts, long long n_faces) {
-    SubLayout l;
-    size_t o = 0;
-    l.flag = o; o += al256((size_t)(n_faces + 1) * 4);
-    l.fpos = o; o += al256((size_t)(n_faces + 1) * 4);
-    l.first = o; o += al256((size_t)n_verts * 4);
-    l.occ = o; o += al256((size_t)(3 * n_faces + 1) * 4);
-    l.rank = o; o += al256((size_t)(3 * n_faces + 1) * 4);
-    l.bad = o; o += al256(sizeof(int));
-    l.scratch = o; o += al256(oai::scan_scratch_bytes(3 * n_faces + 1));
-    l.total = o;
-    return l;
+struct SubWs { int *flag, *fpos, *first, *occ, *rank, *bad, *scratch; };
+size_t carve(SubWs& w, const void* base, long long n_verts, long long n_faces) {
+    oai::Ws ws(base);
+    w.flag = ws.take<int>(n_faces + 1);
+    w.fpos = ws.take<int>(n_faces + 1);
+    w.first = ws.take<int>(n_verts);
+    w.occ = ws.take<int>(3 * n_faces + 1);
+    w.rank = ws.take<int>(3 * n_faces + 1);
+    w.bad = ws.take<int>(1);
+    w.scratch = ws.take<int>(oai::scan_scratch_bytes(3 * n_faces + 1) / 4);
+    return ws.off;
 }
 
-constexpr long long kMaxFaces = 1LL << 28;     // 3 n flattened positions stay below 2^31 - 1 and below the 0x7f7f7f7f fill
+using oai::kMaxFaces;
 
 bool valid_type(int t) { return t == OAI_MESH_FC || t == OAI_MESH_TC; }
 
@@ -664,7 +664,8 @@ extern "C" {
 
 size_t oai_mesh_split_workspace_bytes(long long n_verts, long long n_faces, int mesh_type, int n_init) {
     if (n_verts <= 0 || n_faces < 2 || n_faces >= kMaxFaces || !valid_type(mesh_type) || n_init < 1 || n_init > kMaxInit) return 0;
-    return split_layout(n_faces, mesh_type, n_init).total;
+    SplitWs w;
+    return carve(w, nullptr, n_faces, mesh_type, n_init);
 }
 
 int oai_mesh_split_features(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, int mesh_type,
@@ -675,30 +676,25 @@ int oai_mesh_split_features(const float* verts_dev, long long n_verts, const int
     OAI_CHECK_ARG(valid_type(mesh_type), "oai_mesh_split_features: mesh_type must be OAI_MESH_FC (0) or OAI_MESH_TC (1), got %d", mesh_type);
     OAI_CHECK_ARG(n_faces >= 2 && n_faces < kMaxFaces, "oai_mesh_split_features: needs 2 .. 2^28-1 faces (got %lld)", n_faces);
     OAI_CHECK_ARG(n_verts >= 3 && n_verts < (1LL << 31), "oai_mesh_split_features: needs 3 .. 2^31-1 vertices (got %lld)", n_verts);
-    const SplitLayout l = split_layout(n_faces, mesh_type, 1);
-    if (workspace_bytes < l.total)
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_split_features: workspace %zu B < %zu B", workspace_bytes, l.total);
+    SplitWs w;
+    OAI_CHECK_WORKSPACE("oai_mesh_split_features", workspace_bytes, carve(w, workspace_dev, n_faces, mesh_type, 1));
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
     const int S = slabs_of(mesh_type), D = dims_of(mesh_type), fc = mesh_type == OAI_MESH_FC;
-    Stats* stats = (Stats*)(ws + l.stats);
-    int* bad = (int*)(ws + l.bad);
-    int* flags = (int*)(ws + l.flags);
-    int* pos = (int*)(ws + l.pos);
+    Stats* stats = w.stats;
+    int *bad = w.bad, *flags = w.flags, *pos = w.pos;
     OAI_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
     face_attr_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(verts_dev, n_verts, faces_dev, n_faces, centroids_dev, normals_dev, bad);
     OAI_CHECK_LAUNCH();
     col_sum_seq_kernel<<<1, kRT, 0, st>>>(centroids_dev, n_faces, stats->csum);
     OAI_CHECK_LAUNCH();
-    minmax_kernel<<<kRedBlocks, kT, 0, st>>>(centroids_dev, n_faces, verts_dev, n_verts, (MinMax*)(ws + l.partials));
+    minmax_kernel<<<kRedBlocks, kT, 0, st>>>(centroids_dev, n_faces, verts_dev, n_verts, w.partials);
     OAI_CHECK_LAUNCH();
-    minmax_final_kernel<<<1, kT, 0, st>>>((const MinMax*)(ws + l.partials), &stats->mm);
+    minmax_final_kernel<<<1, kT, 0, st>>>(w.partials, &stats->mm);
     OAI_CHECK_LAUNCH();
-    slab_flags_kernel<<<oai::cdiv(n_faces + 1, kT), kT, 0, st>>>(centroids_dev, normals_dev, n_faces, stats, fc, S, flags,
-                                                                 (signed char*)(ws + l.mask));
+    slab_flags_kernel<<<oai::cdiv(n_faces + 1, kT), kT, 0, st>>>(centroids_dev, normals_dev, n_faces, stats, fc, S, flags, w.mask);
     OAI_CHECK_LAUNCH();
     for (int s = 0; s < S; ++s)
-        if (int rc = oai::exclusive_scan_i32(flags + s * (n_faces + 1), pos + s * (n_faces + 1), n_faces + 1, (int*)(ws + l.scratch), st)) return rc;
+        if (int rc = oai::exclusive_scan_i32(flags + s * (n_faces + 1), pos + s * (n_faces + 1), n_faces + 1, w.scratch, st)) return rc;
     int counts[kMaxSlabs] = {0, 0, 0}, bad_host = 0;
     Stats st_host;
     for (int s = 0; s < S; ++s)
@@ -712,11 +708,10 @@ int oai_mesh_split_features(const float* verts_dev, long long n_verts, const int
             return oai::set_error(OAI_ERR_ARG, "oai_mesh_split_features: the centroids have no finite, non-zero extent along axis %d", k);
     long long total = 0;
     for (int s = 0; s < S; ++s) total += counts[s];
-    if (total > l.cap)
+    if (total > w.cap)
         return oai::set_error(OAI_ERR_ARG, "oai_mesh_split_features: %lld faces lie on a seam of two slabs (room for %lld)", total - n_faces,
-                              l.cap - n_faces);
-    compact_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(centroids_dev, normals_dev, n_faces, stats, fc, S, D, pos, (double*)(ws + l.feat),
-                                                          (int*)(ws + l.face_of));
+                              w.cap - n_faces);
+    compact_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(centroids_dev, normals_dev, n_faces, stats, fc, S, D, pos, w.feat, w.face_of);
     OAI_CHECK_LAUNCH();
     for (int s = 0; s < kMaxSlabs; ++s) slab_counts_host[s] = s < S ? counts[s] : 0;
     return OAI_OK;
@@ -731,9 +726,8 @@ int oai_mesh_split_kmeans(long long n_faces, int mesh_type, void* workspace_dev,
     OAI_CHECK_ARG(n_faces >= 2 && n_faces < kMaxFaces, "oai_mesh_split_kmeans: needs 2 .. 2^28-1 faces (got %lld)", n_faces);
     OAI_CHECK_ARG(n_init >= 1 && n_init <= kMaxInit, "oai_mesh_split_kmeans: n_init must be 1 .. %d (got %d)", kMaxInit, n_init);
     OAI_CHECK_ARG(max_iter >= 1, "oai_mesh_split_kmeans: max_iter must be >= 1 (got %d)", max_iter);
-    const SplitLayout l = split_layout(n_faces, mesh_type, n_init);
-    if (workspace_bytes < l.total)
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_split_kmeans: workspace %zu B < %zu B", workspace_bytes, l.total);
+    SplitWs w;
+    OAI_CHECK_WORKSPACE("oai_mesh_split_kmeans", workspace_bytes, carve(w, workspace_dev, n_faces, mesh_type, n_init));
     const int S = slabs_of(mesh_type), D = dims_of(mesh_type);
     KParams p{};
     long long off = 0;
@@ -744,7 +738,7 @@ int oai_mesh_split_kmeans(long long n_faces, int mesh_type, void* workspace_dev,
         p.off[s] = off;
         off += ns;
     }
-    OAI_CHECK_ARG(off <= l.cap, "oai_mesh_split_kmeans: the slab sizes add up to %lld > %lld", off, l.cap);
+    OAI_CHECK_ARG(off <= w.cap, "oai_mesh_split_kmeans: the slab sizes add up to %lld > %lld", off, w.cap);
     for (int r = 0; r < S * n_init; ++r) {
         const int s = r / n_init;
         OAI_CHECK_ARG(first_centre_host[r] >= 0 && first_centre_host[r] < p.n[s], "oai_mesh_split_kmeans: first centre %lld of run %d is outside slab %d",
@@ -755,25 +749,21 @@ int oai_mesh_split_kmeans(long long n_faces, int mesh_type, void* workspace_dev,
         p.u[r][0] = uniforms_host[2 * r];
         p.u[r][1] = uniforms_host[2 * r + 1];
     }
-    p.stride = l.cap;
+    p.stride = w.cap;
     p.n_slabs = S;
     p.n_init = n_init;
     p.max_iter = max_iter;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    RunOut* runs = (RunOut*)(ws + l.runs);
-    SlabOut* slabs = (SlabOut*)(ws + l.slabs);
     OAI_CHECK_HIP(hipMemsetAsync(side_dev, 0, (size_t)n_faces, st));
     if (D == 9)
-        kmeans_run_kernel<9><<<S * n_init, kRT, 0, st>>>((const double*)(ws + l.feat), p, 1e-4, (signed char*)(ws + l.labels), (double*)(ws + l.dist), runs);
+        kmeans_run_kernel<9><<<S * n_init, kRT, 0, st>>>(w.feat, p, 1e-4, w.labels, w.dist, w.runs);
     else
-        kmeans_run_kernel<6><<<S * n_init, kRT, 0, st>>>((const double*)(ws + l.feat), p, 1e-4, (signed char*)(ws + l.labels), (double*)(ws + l.dist), runs);
+        kmeans_run_kernel<6><<<S * n_init, kRT, 0, st>>>(w.feat, p, 1e-4, w.labels, w.dist, w.runs);
     OAI_CHECK_LAUNCH();
-    select_orient_kernel<<<S, kRT, 0, st>>>(runs, p, (const signed char*)(ws + l.labels), (const int*)(ws + l.face_of),
-                                            (const signed char*)(ws + l.mask), normals_dev, side_dev, slabs);
+    select_orient_kernel<<<S, kRT, 0, st>>>(w.runs, p, w.labels, w.face_of, w.mask, normals_dev, side_dev, w.slabs);
     OAI_CHECK_LAUNCH();
     SlabOut so[kMaxSlabs];
-    OAI_CHECK_HIP(hipMemcpyAsync(so, slabs, S * sizeof(SlabOut), hipMemcpyDeviceToHost, st));
+    OAI_CHECK_HIP(hipMemcpyAsync(so, w.slabs, S * sizeof(SlabOut), hipMemcpyDeviceToHost, st));
     OAI_CHECK_HIP(hipStreamSynchronize(st));
     for (int s = 0; s < S; ++s) {
         if (so[s].status)
@@ -786,7 +776,8 @@ int oai_mesh_split_kmeans(long long n_faces, int mesh_type, void* workspace_dev,
 
 size_t oai_mesh_submesh_workspace_bytes(long long n_verts, long long n_faces) {
     if (n_verts <= 0 || n_faces <= 0 || n_faces >= kMaxFaces || n_verts >= (1LL << 31)) return 0;
-    return sub_layout(n_verts, n_faces).total;
+    SubWs w;
+    return carve(w, nullptr, n_verts, n_faces);
 }
 
 int oai_mesh_submesh(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, const signed char* side_dev, int which,
@@ -797,37 +788,32 @@ int oai_mesh_submesh(const float* verts_dev, long long n_verts, const int* faces
     OAI_CHECK_ARG(n_faces >= 1 && n_faces < kMaxFaces, "oai_mesh_submesh: needs 1 .. 2^28-1 faces (got %lld)", n_faces);
     OAI_CHECK_ARG(n_verts >= 1 && n_verts < (1LL << 31), "oai_mesh_submesh: needs 1 .. 2^31-1 vertices (got %lld)", n_verts);
     OAI_CHECK_ARG(which >= -128 && which <= 127, "oai_mesh_submesh: side value %d is not an int8", which);
-    const SubLayout l = sub_layout(n_verts, n_faces);
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_mesh_submesh: workspace %zu B < %zu B", workspace_bytes, l.total);
+    SubWs w;
+    OAI_CHECK_WORKSPACE("oai_mesh_submesh", workspace_bytes, carve(w, workspace_dev, n_verts, n_faces));
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    int* flag = (int*)(ws + l.flag); int* fpos = (int*)(ws + l.fpos); int* first = (int*)(ws + l.first);
-    int* occ = (int*)(ws + l.occ); int* rank = (int*)(ws + l.rank); int* bad = (int*)(ws + l.bad);
-    select_flags_kernel<<<oai::cdiv(n_faces + 1, kT), kT, 0, st>>>(side_dev, n_faces, which, flag);
+    select_flags_kernel<<<oai::cdiv(n_faces + 1, kT), kT, 0, st>>>(side_dev, n_faces, which, w.flag);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(flag, fpos, n_faces + 1, (int*)(ws + l.scratch), st)) return rc;
-    OAI_CHECK_HIP(hipMemsetAsync(first, 0x7f, (size_t)n_verts * 4, st));          // 0x7f7f7f7f > every flattened position
-    OAI_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
-    first_use_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, flag, fpos, first, face_idx_out_dev, bad);
+    if (int rc = oai::exclusive_scan_i32(w.flag, w.fpos, n_faces + 1, w.scratch, st)) return rc;
+    OAI_CHECK_HIP(hipMemsetAsync(w.first, 0x7f, (size_t)n_verts * 4, st));        // 0x7f7f7f7f > every flattened position
+    OAI_CHECK_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), st));
+    first_use_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, w.flag, w.fpos, w.first, face_idx_out_dev, w.bad);
     OAI_CHECK_LAUNCH();
-    int m = 0, bad_host = 0;
-    OAI_CHECK_HIP(hipMemcpyAsync(&m, fpos + n_faces, sizeof(int), hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipMemcpyAsync(&bad_host, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipStreamSynchronize(st));
-    if (bad_host) return oai::set_error(OAI_ERR_ARG, "oai_mesh_submesh: a face indexes outside the %lld vertices", n_verts);
+    int h[2];                                                                     // selected faces, bad-index flag
+    if (int rc = oai::read_ints(h, {w.fpos + n_faces, w.bad}, st)) return rc;
+    if (h[1]) return oai::set_error(OAI_ERR_ARG, "oai_mesh_submesh: a face indexes outside the %lld vertices", n_verts);
+    const int m = h[0];
     *n_faces_out_host = m;
     *n_verts_out_host = 0;
     if (m == 0) return OAI_OK;
     const long long np = 3LL * m;
-    first_flags_kernel<<<oai::cdiv(np + 1, kT), kT, 0, st>>>(faces_dev, n_verts, face_idx_out_dev, m, first, occ);
+    first_flags_kernel<<<oai::cdiv(np + 1, kT), kT, 0, st>>>(faces_dev, n_verts, face_idx_out_dev, m, w.first, w.occ);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(occ, rank, np + 1, (int*)(ws + l.scratch), st)) return rc;
-    submesh_scatter_kernel<<<oai::cdiv(np, kT), kT, 0, st>>>(verts_dev, n_verts, faces_dev, face_idx_out_dev, m, first, occ, rank, verts_out_dev,
+    if (int rc = oai::exclusive_scan_i32(w.occ, w.rank, np + 1, w.scratch, st)) return rc;
+    submesh_scatter_kernel<<<oai::cdiv(np, kT), kT, 0, st>>>(verts_dev, n_verts, faces_dev, face_idx_out_dev, m, w.first, w.occ, w.rank, verts_out_dev,
                                                             faces_out_dev);
     OAI_CHECK_LAUNCH();
     int nv = 0;
-    OAI_CHECK_HIP(hipMemcpyAsync(&nv, rank + np, sizeof(int), hipMemcpyDeviceToHost, st));
-    OAI_CHECK_HIP(hipStreamSynchronize(st));
+    if (int rc = oai::read_ints(&nv, {w.rank + np}, st)) return rc;
     *n_verts_out_host = nv;
     return OAI_OK;
 }

@@ -135,7 +135,7 @@ void numpy_virtual_index(size_t n, float pct, unsigned long long& k0, unsigned l
 
 extern "C" {
 
-size_t oai_image_normalize_workspace_bytes(void) { return (sizeof(SelectState) + 255) / 256 * 256; }
+size_t oai_image_normalize_workspace_bytes(void) { return oai::round256(sizeof(SelectState)); }
 
 int oai_image_normalize(const float* in, size_t n, float pct_lo, float pct_hi, float out_min, float out_max,
                         float* out, float* window_out_dev, void* ws, size_t ws_bytes, void* stream) {
@@ -143,8 +143,7 @@ int oai_image_normalize(const float* in, size_t n, float pct_lo, float pct_hi, f
     OAI_CHECK_ARG(n >= 2, "oai_image_normalize: need at least 2 voxels");
     OAI_CHECK_ARG(pct_lo >= 0.0f && pct_hi <= 100.0f && pct_lo < pct_hi, "oai_image_normalize: percentiles must satisfy 0 <= lo < hi <= 100");
     OAI_CHECK_ARG((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0, "oai_image_normalize: buffers must be 16-byte aligned");
-    if (ws_bytes < oai_image_normalize_workspace_bytes())
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_image_normalize: workspace %zu B < %zu B", ws_bytes, oai_image_normalize_workspace_bytes());
+    OAI_CHECK_WORKSPACE("oai_image_normalize", ws_bytes, oai_image_normalize_workspace_bytes());
     hipStream_t st = (hipStream_t)stream;
     SelectState* s = reinterpret_cast<SelectState*>(ws);
     unsigned long long k[4];

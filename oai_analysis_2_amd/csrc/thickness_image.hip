@@ -180,8 +180,7 @@ int oai_thickness_image_build(const double* uv_dev, long long n_pts, const int* 
     OAI_CHECK_ARG(std::isfinite(lo_host[0]) && std::isfinite(lo_host[1]), "oai_thickness_image_build: the grid origin is not finite");
     OAI_CHECK_ARG(step_host[0] > 0.0 && step_host[1] > 0.0 && std::isfinite(step_host[0]) && std::isfinite(step_host[1]),
                   "oai_thickness_image_build: step (%g, %g) must be finite and > 0", step_host[0], step_host[1]);
-    if (workspace_bytes < build_bytes(n_faces))
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_thickness_image_build: workspace %zu B < %zu B", workspace_bytes, build_bytes(n_faces));
+    OAI_CHECK_WORKSPACE("oai_thickness_image_build", workspace_bytes, build_bytes(n_faces));
     hipStream_t st = (hipStream_t)stream;
     const Raster r{lo_host[0], lo_host[1], step_host[0], step_host[1], height, width};
     const long long n_px = (long long)height * width;

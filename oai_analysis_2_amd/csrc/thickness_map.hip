@@ -354,37 +354,33 @@ __global__ void __launch_bounds__(kT) plateau_project_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-struct PointGridLayout { size_t cell_of, count, start, unordered, list, scratch, total; };
-PointGridLayout point_grid_layout(long long ncells, long long n_src) {
-    PointGridLayout l;
-    size_t o = 0;
-    l.cell_of = o; o += al256((size_t)n_src * 4);
-    l.count = o; o += al256((size_t)(ncells + 1) * 4);
-    l.start = o; o += al256((size_t)(ncells + 1) * 4);
-    l.unordered = o; o += al256((size_t)n_src * 4);
-    l.list = o; o += al256((size_t)n_src * 4);
-    l.scratch = o; o += al256(oai::scan_scratch_bytes(ncells + 1));
-    l.total = o;
-    return l;
+// Workspaces: one struct of typed pointers per entry-point family, filled by one carve() that returns the bytes walked (oai::Ws,
+// common.h): over a null base that is the *_workspace_bytes answer, over the caller's buffer the carving.
+struct PointGridWs { int *cell_of, *count, *start, *unordered, *list, *scratch; };
+size_t carve(PointGridWs& w, const void* base, long long ncells, long long n_src) {
+    oai::Ws ws(base);
+    w.cell_of = ws.take<int>(n_src);
+    w.count = ws.take<int>(ncells + 1);
+    w.start = ws.take<int>(ncells + 1);
+    w.unordered = ws.take<int>(n_src);
+    w.list = ws.take<int>(n_src);
+    w.scratch = ws.take<int>(oai::scan_scratch_bytes(ncells + 1) / 4);
+    return ws.off;
 }
 
-struct MapLayout { size_t partials, sums, ext_partials, ext, right, left, off_right, off_left, scratch, total; };
-MapLayout map_layout(long long n) {
-    MapLayout l;
-    size_t o = 0;
-    l.partials = o; o += al256(kRedBlocks * 16 * sizeof(double));
-    l.sums = o; o += al256(16 * sizeof(double));
-    l.ext_partials = o; o += al256(kRedBlocks * 2 * sizeof(Ext));
-    l.ext = o; o += al256(2 * sizeof(Ext));
-    l.right = o; o += al256((size_t)(n + 1) * 4);
-    l.left = o; o += al256((size_t)(n + 1) * 4);
-    l.off_right = o; o += al256((size_t)(n + 1) * 4);
-    l.off_left = o; o += al256((size_t)(n + 1) * 4);
-    l.scratch = o; o += al256(oai::scan_scratch_bytes(n + 1));
-    l.total = o;
-    return l;
+struct MapWs { double *partials, *sums; Ext *ext_partials, *ext; int *right, *left, *off_right, *off_left, *scratch; };
+size_t carve(MapWs& w, const void* base, long long n) {
+    oai::Ws ws(base);
+    w.partials = ws.take<double>(kRedBlocks * 16);
+    w.sums = ws.take<double>(16);
+    w.ext_partials = ws.take<Ext>(kRedBlocks * 2);
+    w.ext = ws.take<Ext>(2);
+    w.right = ws.take<int>(n + 1);
+    w.left = ws.take<int>(n + 1);
+    w.off_right = ws.take<int>(n + 1);
+    w.off_left = ws.take<int>(n + 1);
+    w.scratch = ws.take<int>(oai::scan_scratch_bytes(n + 1) / 4);
+    return ws.off;
 }
 
 int launch_interp(bool grid, const float* src, long long n_src, const float* vals, int n_comp, const float* tgt, long long n_tgt, double radius,
@@ -406,20 +402,20 @@ int read_sums(double* dev, double* host, int k, hipStream_t st) {
     return OAI_OK;
 }
 
-int moments(const float* pts, long long n, int mask, const double ref[3], const MapLayout& l, char* ws, double out[10], hipStream_t st) {
-    moments_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, mask, ref[0], ref[1], ref[2], (double*)(ws + l.partials));
+int moments(const float* pts, long long n, int mask, const double ref[3], const MapWs& w, double out[10], hipStream_t st) {
+    moments_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, mask, ref[0], ref[1], ref[2], w.partials);
     OAI_CHECK_LAUNCH();
-    final_sum_kernel<10><<<1, kT, 0, st>>>((const double*)(ws + l.partials), (double*)(ws + l.sums));
+    final_sum_kernel<10><<<1, kT, 0, st>>>(w.partials, w.sums);
     OAI_CHECK_LAUNCH();
-    return read_sums((double*)(ws + l.sums), out, 10, st);
+    return read_sums(w.sums, out, 10, st);
 }
 
-int circle_sums(const float* pts, long long n, int cx, int cy, const double c[2], const MapLayout& l, char* ws, double out[9], hipStream_t st) {
-    circle_sums_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, cx, cy, c[0], c[1], (double*)(ws + l.partials));
+int circle_sums(const float* pts, long long n, int cx, int cy, const double c[2], const MapWs& w, double out[9], hipStream_t st) {
+    circle_sums_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, cx, cy, c[0], c[1], w.partials);
     OAI_CHECK_LAUNCH();
-    final_sum_kernel<9><<<1, kT, 0, st>>>((const double*)(ws + l.partials), (double*)(ws + l.sums));
+    final_sum_kernel<9><<<1, kT, 0, st>>>(w.partials, w.sums);
     OAI_CHECK_LAUNCH();
-    return read_sums((double*)(ws + l.sums), out, 9, st);
+    return read_sums(w.sums, out, 9, st);
 }
 
 // eigen-decomposition of a symmetric 3x3 matrix (cyclic Jacobi); columns of V are the eigenvectors, w descending
@@ -468,16 +464,16 @@ void eig_sym3(const double S[3][3], double w[3], double V[3][3]) {
 }
 
 // one plateau: mean, centred scatter, top-2 axes, svd_flip signs, then the rotation (degrees), x scale and y offset of :507-520
-int plateau_map(const float* pts, long long n, int mask, double angle_deg, double fx, double oy, const MapLayout& l, char* ws, HalfMap* m,
+int plateau_map(const float* pts, long long n, int mask, double angle_deg, double fx, double oy, const MapWs& w, HalfMap* m,
                 long long* count, hipStream_t st) {
     const double zero[3] = {0.0, 0.0, 0.0};
     double s1[10], s2[10];
-    if (int rc = moments(pts, n, mask, zero, l, ws, s1, st)) return rc;
+    if (int rc = moments(pts, n, mask, zero, w, s1, st)) return rc;
     const double cnt = s1[0];
     *count = (long long)cnt;
     if (*count == 0) return OAI_OK;
     const double mean[3] = {s1[1] / cnt, s1[2] / cnt, s1[3] / cnt};
-    if (int rc = moments(pts, n, mask, mean, l, ws, s2, st)) return rc;            // second pass about the mean (no cancellation)
+    if (int rc = moments(pts, n, mask, mean, w, s2, st)) return rc;                // second pass about the mean (no cancellation)
     const double d[3] = {s2[1], s2[2], s2[3]};
     const int ij[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
     double S[3][3];
@@ -485,18 +481,18 @@ int plateau_map(const float* pts, long long n, int mask, double angle_deg, doubl
         const int i = ij[k][0], j = ij[k][1];
         S[i][j] = S[j][i] = s2[4 + k] - d[i] * d[j] / cnt;
     }
-    double w[3], V[3][3];
-    eig_sym3(S, w, V);
+    double ev[3], V[3][3];
+    eig_sym3(S, ev, V);
     Axes ax;
     for (int k = 0; k < 3; ++k) ax.mean[k] = mean[k];
     for (int c = 0; c < 2; ++c)
         for (int k = 0; k < 3; ++k) ax.u[c][k] = V[k][c];
-    score_extreme_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, mask, ax, (Ext*)(ws + l.ext_partials));
+    score_extreme_kernel<<<kRedBlocks, kT, 0, st>>>(pts, n, mask, ax, w.ext_partials);
     OAI_CHECK_LAUNCH();
-    final_ext_kernel<<<1, kT, 0, st>>>((const Ext*)(ws + l.ext_partials), (Ext*)(ws + l.ext));
+    final_ext_kernel<<<1, kT, 0, st>>>(w.ext_partials, w.ext);
     OAI_CHECK_LAUNCH();
     Ext e[2];
-    OAI_CHECK_HIP(hipMemcpyAsync(e, ws + l.ext, sizeof(e), hipMemcpyDeviceToHost, st));
+    OAI_CHECK_HIP(hipMemcpyAsync(e, w.ext, sizeof(e), hipMemcpyDeviceToHost, st));
     OAI_CHECK_HIP(hipStreamSynchronize(st));
     for (int c = 0; c < 2; ++c)
         if (e[c].v < 0.0)
@@ -516,7 +512,8 @@ extern "C" {
 
 size_t oai_point_grid_workspace_bytes(const int grid_dims_xyz[3], long long n_src) {
     if (!grid_dims_xyz || n_src <= 0 || grid_dims_xyz[0] <= 0 || grid_dims_xyz[1] <= 0 || grid_dims_xyz[2] <= 0) return 0;
-    return point_grid_layout((long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2], n_src).total;
+    PointGridWs w;
+    return carve(w, nullptr, (long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2], n_src);
 }
 
 int oai_map_attributes(const float* src_pts_dev, long long n_src, const float* src_vals_dev, int n_comp, const float* tgt_pts_dev,
@@ -543,32 +540,29 @@ int oai_map_attributes_grid(const float* src_pts_dev, long long n_src, const flo
     OAI_CHECK_ARG(grid_dims_xyz[0] > 0 && grid_dims_xyz[1] > 0 && grid_dims_xyz[2] > 0, "oai_map_attributes_grid: empty grid");
     const long long ncells = (long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2];
     OAI_CHECK_ARG(ncells < (1LL << 30), "oai_map_attributes_grid: grid too fine");
-    const PointGridLayout l = point_grid_layout(ncells, n_src);
-    if (workspace_bytes < l.total)
-        return oai::set_error(OAI_ERR_WORKSPACE, "oai_map_attributes_grid: workspace %zu B < %zu B", workspace_bytes, l.total);
+    PointGridWs w;
+    OAI_CHECK_WORKSPACE("oai_map_attributes_grid", workspace_bytes, carve(w, workspace_dev, ncells, n_src));
     if (n_tgt == 0) return OAI_OK;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
-    int* cell_of = (int*)(ws + l.cell_of); int* count = (int*)(ws + l.count); int* start = (int*)(ws + l.start);
-    int* unordered = (int*)(ws + l.unordered); int* list = (int*)(ws + l.list);
     GridD g;
     for (int k = 0; k < 3; ++k) { g.lo[k] = grid_lo_xyz[k]; g.n[k] = grid_dims_xyz[k]; }
     g.h = cell_size; g.inv_h = 1.0 / cell_size;
-    OAI_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)(ncells + 1) * 4, st));
-    bin_count_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(src_pts_dev, n_src, g, cell_of, count);
+    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    bin_count_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(src_pts_dev, n_src, g, w.cell_of, w.count);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(count, start, ncells + 1, (int*)(ws + l.scratch), st)) return rc;
-    OAI_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)(ncells + 1) * 4, st));
-    bin_scatter_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(cell_of, n_src, start, count, unordered);
+    if (int rc = oai::exclusive_scan_i32(w.count, w.start, ncells + 1, w.scratch, st)) return rc;
+    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    bin_scatter_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.cell_of, n_src, w.start, w.count, w.unordered);
     OAI_CHECK_LAUNCH();
-    bin_order_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(unordered, n_src, cell_of, start, list);
+    bin_order_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.unordered, n_src, w.cell_of, w.start, w.list);
     OAI_CHECK_LAUNCH();
-    return launch_interp(true, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, g, start, list, out_vals_dev, st);
+    return launch_interp(true, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, g, w.start, w.list, out_vals_dev, st);
 }
 
 size_t oai_thickness_map_workspace_bytes(long long n_points) {
     if (n_points <= 0) return 0;
-    return map_layout(n_points).total;
+    MapWs w;
+    return carve(w, nullptr, n_points);
 }
 
 int oai_fit_circle(const float* pts_dev, long long n, int col_x, int col_y, void* workspace_dev, size_t workspace_bytes, double centre_host[2],
@@ -576,18 +570,17 @@ int oai_fit_circle(const float* pts_dev, long long n, int col_x, int col_y, void
     OAI_CHECK_ARG(pts_dev && workspace_dev && centre_host && radius_host, "oai_fit_circle: null pointer");
     OAI_CHECK_ARG(n >= 3, "oai_fit_circle: needs at least 3 points (got %lld)", n);
     OAI_CHECK_ARG(col_x >= 0 && col_x < 3 && col_y >= 0 && col_y < 3 && col_x != col_y, "oai_fit_circle: columns must be two distinct of 0, 1, 2");
-    const MapLayout l = map_layout(n);
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_fit_circle: workspace %zu B < %zu B", workspace_bytes, l.total);
+    MapWs w;
+    OAI_CHECK_WORKSPACE("oai_fit_circle", workspace_bytes, carve(w, workspace_dev, n));
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
     // start at the centroid, as compute_least_square_circle does
     const double zero[3] = {0.0, 0.0, 0.0};
     double m[10];
-    if (int rc = moments(pts_dev, n, 0, zero, l, ws, m, st)) return rc;
+    if (int rc = moments(pts_dev, n, 0, zero, w, m, st)) return rc;
     double c[2] = {m[1 + col_x] / m[0], m[1 + col_y] / m[0]};
     const double nn = (double)n;
     double S[9];
-    if (int rc = circle_sums(pts_dev, n, col_x, col_y, c, l, ws, S, st)) return rc;
+    if (int rc = circle_sums(pts_dev, n, col_x, col_y, c, w, S, st)) return rc;
     const double extent = std::sqrt(S[1] / nn);                              // rms distance of the points from their centroid
     auto cost_of = [nn](const double* s) { return s[1] - s[0] * s[0] / nn; };  // sum (R_i - mean R)^2
     double cost = cost_of(S);
@@ -606,7 +599,7 @@ int oai_fit_circle(const float* pts_dev, long long n, int col_x, int col_y, void
         for (int half = 0; half < 40; ++half) {                              // step halving keeps the cost from rising
             cn[0] = c[0] + step[0];
             cn[1] = c[1] + step[1];
-            if (int rc = circle_sums(pts_dev, n, col_x, col_y, cn, l, ws, Sn, st)) return rc;
+            if (int rc = circle_sums(pts_dev, n, col_x, col_y, cn, w, Sn, st)) return rc;
             if (cost_of(Sn) <= cost) { accepted = true; break; }
             step[0] *= 0.5;
             step[1] *= 0.5;
@@ -640,24 +633,21 @@ int oai_project_plateaus(const float* pts_dev, const float* thickness_dev, long 
     OAI_CHECK_ARG(pts_dev && thickness_dev && workspace_dev && x_dev && y_dev && thickness_out_dev && n_right_host && n_left_host,
                   "oai_project_plateaus: null pointer");
     OAI_CHECK_ARG(n > 0 && n < (1LL << 31), "oai_project_plateaus: needs 1 .. 2^31-1 points (got %lld)", n);
-    const MapLayout l = map_layout(n);
-    if (workspace_bytes < l.total) return oai::set_error(OAI_ERR_WORKSPACE, "oai_project_plateaus: workspace %zu B < %zu B", workspace_bytes, l.total);
+    MapWs w;
+    OAI_CHECK_WORKSPACE("oai_project_plateaus", workspace_bytes, carve(w, workspace_dev, n));
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace_dev;
     HalfMap right, left;
-    if (int rc = plateau_map(pts_dev, n, 2, -160.0, -1.0, 50.0, l, ws, &right, n_right_host, st)) return rc;
-    if (int rc = plateau_map(pts_dev, n, 1, -50.0, 1.0, 0.0, l, ws, &left, n_left_host, st)) return rc;
+    if (int rc = plateau_map(pts_dev, n, 2, -160.0, -1.0, 50.0, w, &right, n_right_host, st)) return rc;
+    if (int rc = plateau_map(pts_dev, n, 1, -50.0, 1.0, 0.0, w, &left, n_left_host, st)) return rc;
     if (*n_right_host == 0 || *n_left_host == 0)
         return oai::set_error(OAI_ERR_ARG, "oai_project_plateaus: the %s plateau is empty (no point with z %s 50)", *n_right_host == 0 ? "right" : "left",
                               *n_right_host == 0 ? ">=" : "<");
-    int* fr = (int*)(ws + l.right); int* fl = (int*)(ws + l.left);
-    int* orr = (int*)(ws + l.off_right); int* ol = (int*)(ws + l.off_left);
-    half_flags_kernel<<<oai::cdiv(n + 1, kT), kT, 0, st>>>(pts_dev, n, fr, fl);
+    half_flags_kernel<<<oai::cdiv(n + 1, kT), kT, 0, st>>>(pts_dev, n, w.right, w.left);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(fr, orr, n + 1, (int*)(ws + l.scratch), st)) return rc;
-    if (int rc = oai::exclusive_scan_i32(fl, ol, n + 1, (int*)(ws + l.scratch), st)) return rc;
-    plateau_project_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(pts_dev, thickness_dev, n, right, left, orr, ol, *n_right_host, x_dev, y_dev,
-                                                            thickness_out_dev);
+    if (int rc = oai::exclusive_scan_i32(w.right, w.off_right, n + 1, w.scratch, st)) return rc;
+    if (int rc = oai::exclusive_scan_i32(w.left, w.off_left, n + 1, w.scratch, st)) return rc;
+    plateau_project_kernel<<<oai::cdiv(n, kT), kT, 0, st>>>(pts_dev, thickness_dev, n, right, left, w.off_right, w.off_left, *n_right_host, x_dev,
+                                                            y_dev, thickness_out_dev);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }

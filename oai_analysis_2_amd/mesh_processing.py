@@ -81,42 +81,51 @@ class Mesh:
         return out
 
 
-def _dev(a: np.ndarray, dtype) -> torch.Tensor:
+def _dev(a, dtype, tail=(), device=None) -> torch.Tensor:
+    """An array or a tensor as a contiguous device tensor of the numpy ``dtype``, reshaped to [-1, *tail] when ``tail`` is given.  An
+    array is converted on the host and uploaded; a tensor that is already on a GPU stays there unless ``device`` names another."""
     if not torch.cuda.is_available():
         raise RuntimeError("oai_analysis_2_amd.mesh_processing runs on the GPU only (no CPU fallback)")
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))
+    if device is not None or not t.is_cuda:
+        t = t.to(device if device is not None else "cuda")
+    t = t.to(getattr(torch, np.dtype(dtype).name))
+    return (t.reshape(-1, *tail) if tail else t).contiguous()
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+def _call(name: str, device, *args) -> None:
+    """lib.<name>(*args, stream) on ``device`` and its current stream; a non-zero status raises OaiError under the symbol's name."""
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.load(), name)(*args, torch.cuda.current_stream().cuda_stream), name)
+
+
+def _workspace(family: str, device, *size_args, pad: bool = False) -> torch.Tensor:
+    """The uint8 device buffer that lib.<family>_workspace_bytes(*size_args) asks for.  The library answers 0 for sizes it refuses.
+    ``pad``: then one byte all the same, so that the entry point's own argument check names the fault instead of its null-pointer
+    check (components and the circle fit, whose callers may pass an empty mesh)."""
+    n = int(getattr(_lib.load(), family + "_workspace_bytes")(*size_args))
+    return torch.empty(max(n, 1) if pad else n, dtype=torch.uint8, device=device)
 
 
 # ---- marching cubes ----------------------------------------------------------------------------------------------------------
 def _marching_cubes_dev(vol: torch.Tensor, level: float, spacing_xyz) -> Tuple[torch.Tensor, torch.Tensor]:
     """(verts float32 [n,3], faces int32 [m,3]) of the iso-surface, left on the volume's device."""
-    lib = _lib.load()
-    vol = vol.to(torch.float32).contiguous()
-    if not vol.is_cuda:
-        vol = vol.cuda()
+    vol = _dev(vol, np.float32)
     D, H, W = (int(v) for v in vol.shape)
-    ws = torch.empty(int(lib.oai_mc_workspace_bytes(D, H, W)), dtype=torch.uint8, device=vol.device)
+    ws = _workspace("oai_mc", vol.device, D, H, W)
     nv, nt = C.c_longlong(), C.c_longlong()
-    with torch.cuda.device(vol.device):
-        _lib.check(lib.oai_mc_count(vol.data_ptr(), D, H, W, float(level), ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nt), _stream()),
-                   "oai_mc_count")
-        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
-        faces = torch.empty((nt.value, 3), dtype=torch.int32, device=vol.device)
-        sp = (C.c_float * 3)(*[float(v) for v in spacing_xyz])
-        _lib.check(lib.oai_mc_emit(vol.data_ptr(), D, H, W, float(level), sp, ws.data_ptr(), verts.data_ptr(), faces.data_ptr(), _stream()),
-                   "oai_mc_emit")
+    _call("oai_mc_count", vol.device, vol.data_ptr(), D, H, W, float(level), ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nt))
+    verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
+    faces = torch.empty((nt.value, 3), dtype=torch.int32, device=vol.device)
+    sp = (C.c_float * 3)(*[float(v) for v in spacing_xyz])
+    _call("oai_mc_emit", vol.device, vol.data_ptr(), D, H, W, float(level), sp, ws.data_ptr(), verts.data_ptr(), faces.data_ptr())
     return verts, faces
 
 
 def marching_cubes(volume_zyx, level: float = 0.5, spacing_xyz=(1.0, 1.0, 1.0)) -> Tuple[np.ndarray, np.ndarray]:
     """(verts, faces) of the iso-surface; ``volume_zyx`` may be a numpy array or a float32 torch tensor already on the device."""
     _lib.load()
-    vol = volume_zyx if isinstance(volume_zyx, torch.Tensor) else _dev(np.asarray(volume_zyx), np.float32)
-    verts, faces = _marching_cubes_dev(vol, level, spacing_xyz)
+    verts, faces = _marching_cubes_dev(volume_zyx, level, spacing_xyz)
     return verts.cpu().numpy(), faces.cpu().numpy()
 
 
@@ -155,67 +164,46 @@ def keep_large_regions(verts: np.ndarray, faces: np.ndarray, min_cells: int = 30
 
 
 # ---- the same graph steps on the device (csrc/mesh_graph.hip) ------------------------------------------------------------------
-def _faces_dev(faces) -> torch.Tensor:
-    f = faces if isinstance(faces, torch.Tensor) else _dev(np.asarray(faces).reshape(-1, 3), np.int32)
-    return f.to(torch.int32).reshape(-1, 3).contiguous()
-
-
-def _verts_dev(verts) -> torch.Tensor:
-    v = verts if isinstance(verts, torch.Tensor) else _dev(np.asarray(verts).reshape(-1, 3), np.float32)
-    return v.to(torch.float32).reshape(-1, 3).contiguous()
-
-
 def mesh_components_device(faces, n_verts: int, return_rounds: bool = False):
     """Connected components of the face graph on the GPU: int32 label per vertex = the smallest vertex index of its component (an
     unreferenced vertex is its own component).  ``return_rounds``: also the number of hook / jump rounds it took."""
-    lib = _lib.load()
-    f = _faces_dev(faces)
+    f = _dev(faces, np.int32, (3,))
     nf, n = int(f.shape[0]), int(n_verts)
     label = torch.empty(n, dtype=torch.int32, device=f.device)
-    ws = torch.empty(max(int(lib.oai_mesh_components_workspace_bytes(n, nf)), 1), dtype=torch.uint8, device=f.device)
+    ws = _workspace("oai_mesh_components", f.device, n, nf, pad=True)
     rounds = C.c_int()
-    with torch.cuda.device(f.device):
-        _lib.check(lib.oai_mesh_components(f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), label.data_ptr(), C.byref(rounds), _stream()),
-                   "oai_mesh_components")
+    _call("oai_mesh_components", f.device, f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), label.data_ptr(), C.byref(rounds))
     return (label, rounds.value) if return_rounds else label
 
 
 def keep_large_regions_device(verts, faces, min_cells: int = 3000) -> Tuple[torch.Tensor, torch.Tensor]:
     """keep_large_regions on the GPU: torch tensors in (float32 [n,3], int32 [m,3]), device tensors out, equal to the host's."""
-    lib = _lib.load()
-    v, f = _verts_dev(verts), _faces_dev(faces)
+    v, f = _dev(verts, np.float32, (3,)), _dev(faces, np.int32, (3,))
     nv, nf = int(v.shape[0]), int(f.shape[0])
-    ws = torch.empty(int(lib.oai_mesh_keep_large_regions_workspace_bytes(nv, nf)), dtype=torch.uint8, device=v.device)
+    ws = _workspace("oai_mesh_keep_large_regions", v.device, nv, nf)
     vo, fo = torch.empty_like(v), torch.empty_like(f)
     n_v, n_f = C.c_longlong(), C.c_longlong()
-    with torch.cuda.device(v.device):
-        _lib.check(lib.oai_mesh_keep_large_regions(v.data_ptr(), nv, f.data_ptr(), nf, int(min_cells), ws.data_ptr(), ws.numel(), vo.data_ptr(),
-                                                   fo.data_ptr(), C.byref(n_v), C.byref(n_f), _stream()), "oai_mesh_keep_large_regions")
+    _call("oai_mesh_keep_large_regions", v.device, v.data_ptr(), nv, f.data_ptr(), nf, int(min_cells), ws.data_ptr(), ws.numel(), vo.data_ptr(),
+          fo.data_ptr(), C.byref(n_v), C.byref(n_f))
     return vo[:n_v.value], fo[:n_f.value]
 
 
 def vertex_adjacency_device(n_verts: int, faces) -> Tuple[torch.Tensor, torch.Tensor]:
     """vertex_adjacency on the GPU: int32 device tensors (offsets [n+1], neighbours), equal to the host's."""
-    lib = _lib.load()
-    f = _faces_dev(faces)
+    f = _dev(faces, np.int32, (3,))
     n, nf = int(n_verts), int(f.shape[0])
-    ws = torch.empty(int(lib.oai_mesh_adjacency_workspace_bytes(n, nf)), dtype=torch.uint8, device=f.device)
+    ws = _workspace("oai_mesh_adjacency", f.device, n, nf)
     off = torch.empty(n + 1, dtype=torch.int32, device=f.device)
     nbr = torch.empty(max(6 * nf, 1), dtype=torch.int32, device=f.device)
     n_nbrs = C.c_longlong()
-    with torch.cuda.device(f.device):
-        _lib.check(lib.oai_mesh_adjacency(f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), off.data_ptr(), nbr.data_ptr(), C.byref(n_nbrs), _stream()),
-                   "oai_mesh_adjacency")
+    _call("oai_mesh_adjacency", f.device, f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), off.data_ptr(), nbr.data_ptr(), C.byref(n_nbrs))
     return off, nbr[:n_nbrs.value]
 
 
 def _smooth_dev(v: torch.Tensor, off: torch.Tensor, nbr: torch.Tensor, num_iterations: int, relaxation_factor: float) -> torch.Tensor:
-    lib = _lib.load()
-    n = int(v.shape[0])
     tmp, out = torch.empty_like(v), torch.empty_like(v)
-    with torch.cuda.device(v.device):
-        _lib.check(lib.oai_mesh_smooth(v.data_ptr(), n, off.data_ptr(), nbr.data_ptr(), int(num_iterations), float(relaxation_factor),
-                                       tmp.data_ptr(), out.data_ptr(), _stream()), "oai_mesh_smooth")
+    _call("oai_mesh_smooth", v.device, v.data_ptr(), int(v.shape[0]), off.data_ptr(), nbr.data_ptr(), int(num_iterations), float(relaxation_factor),
+          tmp.data_ptr(), out.data_ptr())
     return out
 
 
@@ -241,17 +229,28 @@ def _mesh_resident(vol: torch.Tensor, spacing_xyz, num_iterations: int, min_cell
     return _smooth_dev(v, off, nbr, num_iterations, 0.01), f
 
 
-def _volume_dev(itk_image, spacing_xyz) -> Tuple[torch.Tensor, np.ndarray]:
-    """The probability map as a float32 [z,y,x] device tensor and its (x, y, z) spacing: an Image (or array / itk image), or a device
-    tensor with ``spacing_xyz`` (unit spacing if None)."""
-    if isinstance(itk_image, torch.Tensor):
-        if itk_image.dim() != 3:
-            raise ValueError(f"expected a [z,y,x] probability map, got shape {tuple(itk_image.shape)}")
-        sp = np.ones(3) if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
-        vol = itk_image if itk_image.is_cuda else itk_image.cuda()
-        return vol.to(torch.float32).contiguous(), sp
-    img = as_image(itk_image)
-    return _dev(np.asarray(img.array, dtype=np.float32), np.float32), img.spacing
+def _probmap_dev(image, spacing_xyz=None, origin_xyz=None, direction=None, strict: bool = False):
+    """The probability map -- an Image, an array, an itk image or a device tensor -- as (float32 [z,y,x] device volume, spacing,
+    origin, direction): the image's own geometry, unit / zero / identity for a tensor.  The explicit arguments describe a tensor.
+    ``strict`` (the cuberille path): they also replace an Image's own geometry, and an Image that is not 3-D is refused here; without
+    it (get_mesh, get_thickness_mesh, ThicknessAtlas: ``spacing_xyz`` goes with a tensor) an Image keeps its own."""
+    if isinstance(image, torch.Tensor):
+        if image.dim() != 3:
+            raise ValueError(f"expected a [z,y,x] probability map, got shape {tuple(image.shape)}")
+        vol, explicit = _dev(image, np.float32), True
+        s, o, d = np.ones(3), np.zeros(3), np.eye(3)
+    else:
+        img = as_image(image)
+        if strict and img.array.ndim != 3:
+            raise ValueError(f"expected a [z,y,x] probability map, got shape {img.array.shape}")
+        vol, explicit = _dev(img.array, np.float32), strict
+        s, o, d = img.spacing, img.origin, img.direction
+    if explicit:
+        s = s if spacing_xyz is None else spacing_xyz
+        o = o if origin_xyz is None else origin_xyz
+        d = d if direction is None else direction
+    return (vol, np.asarray(s, np.float64).reshape(3).copy(), np.asarray(o, np.float64).reshape(3).copy(),
+            np.asarray(d, np.float64).reshape(3, 3).copy())
 
 
 def get_mesh(itk_image, num_iterations: int = 150, min_cells: int = 3000, on_device: bool = False, spacing_xyz=None) -> Mesh:
@@ -259,7 +258,7 @@ def get_mesh(itk_image, num_iterations: int = 150, min_cells: int = 3000, on_dev
     (get_vtk_mesh), then smoothed.  ``on_device``: the region filter and the edge graph on the GPU too (csrc/mesh_graph.hip), one
     download at the end, the same bits; ``itk_image`` may then also be a float32 [z,y,x] device tensor with ``spacing_xyz``."""
     if on_device:
-        v, f = _mesh_resident(*_volume_dev(itk_image, spacing_xyz), num_iterations, min_cells)
+        v, f = _mesh_resident(*_probmap_dev(itk_image, spacing_xyz)[:2], num_iterations, min_cells)
         return Mesh(v.cpu().numpy(), f.cpu().numpy())
     img = as_image(itk_image)
     verts, faces = marching_cubes(np.asarray(img.array, dtype=np.float32), 0.5, img.spacing)
@@ -268,27 +267,6 @@ def get_mesh(itk_image, num_iterations: int = 150, min_cells: int = 3000, on_dev
 
 
 # ---- cuberille iso-surface (itk.cuberille_image_to_mesh_filter; csrc/cuberille.hip) --------------------------------------------
-def _probmap_geometry(image, spacing_xyz, origin_xyz, direction) -> Tuple[torch.Tensor, np.ndarray, np.ndarray, np.ndarray]:
-    """(float32 [z,y,x] device volume, spacing, origin, direction): the image's geometry (unit / zero / identity for a tensor), each
-    part replaced by the explicit argument when one is given."""
-    if isinstance(image, torch.Tensor):
-        if image.dim() != 3:
-            raise ValueError(f"expected a [z,y,x] probability map, got shape {tuple(image.shape)}")
-        vol = (image if image.is_cuda else image.cuda()).to(torch.float32).contiguous()
-        s, o, d = np.ones(3), np.zeros(3), np.eye(3)
-    else:
-        img = as_image(image)
-        if img.array.ndim != 3:
-            raise ValueError(f"expected a [z,y,x] probability map, got shape {img.array.shape}")
-        vol = _dev(np.asarray(img.array, dtype=np.float32), np.float32)
-        s, o, d = img.spacing, img.origin, img.direction
-    s = s if spacing_xyz is None else spacing_xyz
-    o = o if origin_xyz is None else origin_xyz
-    d = d if direction is None else direction
-    return (vol, np.asarray(s, np.float64).reshape(3).copy(), np.asarray(o, np.float64).reshape(3).copy(),
-            np.asarray(d, np.float64).reshape(3, 3).copy())
-
-
 def cuberille_device(image, iso_surface_value: float = 0.5, *, generate_triangle_faces: bool = True,
                      project_vertices_to_iso_surface: bool = True, project_vertex_surface_distance_threshold: float = 0.05,
                      project_vertex_step_length: float = -1.0, project_vertex_step_length_relaxation_factor: float = 0.95,
@@ -296,31 +274,25 @@ def cuberille_device(image, iso_surface_value: float = 0.5, *, generate_triangle
                      origin_xyz=None, direction=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The cuberille surface left on the device: (verts float32 [n,3] physical points, faces int32 [2m,3] or [m,4] quads, steps int32
     [n] = projection steps per vertex).  Contract: include/oai_hip.h, "Cuberille iso-surface"."""
-    lib = _lib.load()
-    vol, s, o, d = _probmap_geometry(image, spacing_xyz, origin_xyz, direction)
+    vol, s, o, d = _probmap_dev(image, spacing_xyz, origin_xyz, direction, strict=True)
     D, H, W = (int(v) for v in vol.shape)
     geo = np.concatenate([o, s, d.reshape(-1), np.linalg.inv(d @ np.diag(s)).reshape(-1)])
     flip = bool(np.linalg.det(d) < 0)
-    wsb = int(lib.oai_cuberille_workspace_bytes(D, H, W))
-    if wsb == 0:
+    ws = _workspace("oai_cuberille", vol.device, D, H, W)
+    if ws.numel() == 0:
         raise ValueError(f"cuberille: volume {D}x{H}x{W} is empty or too large")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=vol.device)
     nv, nf = C.c_longlong(), C.c_longlong()
     iso = float(iso_surface_value)
-    with torch.cuda.device(vol.device):
-        _lib.check(lib.oai_cuberille_count(vol.data_ptr(), D, H, W, iso, ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nf), _stream()),
-                   "oai_cuberille_count")
-        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
-        faces = torch.empty((2 * nf.value, 3) if generate_triangle_faces else (nf.value, 4), dtype=torch.int32, device=vol.device)
-        steps = torch.empty(nv.value, dtype=torch.int32, device=vol.device)
-        if nv.value == 0:                                            # nothing inside: no faces either
-            return verts, faces, steps
-        _lib.check(lib.oai_cuberille_emit(vol.data_ptr(), D, H, W, iso, (C.c_double * 24)(*[float(x) for x in geo]), int(flip),
-                                          int(bool(generate_triangle_faces)), int(bool(project_vertices_to_iso_surface)),
-                                          float(project_vertex_surface_distance_threshold), float(project_vertex_step_length),
-                                          float(project_vertex_step_length_relaxation_factor), int(project_vertex_maximum_number_of_steps),
-                                          int(bool(move_after_converged)), ws.data_ptr(), ws.numel(), nv.value, nf.value, verts.data_ptr(),
-                                          faces.data_ptr(), steps.data_ptr(), _stream()), "oai_cuberille_emit")
+    _call("oai_cuberille_count", vol.device, vol.data_ptr(), D, H, W, iso, ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nf))
+    verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
+    faces = torch.empty((2 * nf.value, 3) if generate_triangle_faces else (nf.value, 4), dtype=torch.int32, device=vol.device)
+    steps = torch.empty(nv.value, dtype=torch.int32, device=vol.device)
+    if nv.value == 0:                                                # nothing inside: no faces either
+        return verts, faces, steps
+    _call("oai_cuberille_emit", vol.device, vol.data_ptr(), D, H, W, iso, (C.c_double * 24)(*[float(x) for x in geo]), int(flip),
+          int(bool(generate_triangle_faces)), int(bool(project_vertices_to_iso_surface)), float(project_vertex_surface_distance_threshold),
+          float(project_vertex_step_length), float(project_vertex_step_length_relaxation_factor), int(project_vertex_maximum_number_of_steps),
+          int(bool(move_after_converged)), ws.data_ptr(), ws.numel(), nv.value, nf.value, verts.data_ptr(), faces.data_ptr(), steps.data_ptr())
     return verts, faces, steps
 
 
@@ -450,25 +422,22 @@ def _kmeans_draws(counts, n_init: int, seed: int = _KMEANS_SEED):
 
 
 def _split_dev(v: torch.Tensor, f: torch.Tensor, mesh_type: str) -> DeviceSplit:
-    lib = _lib.load()
     kind = "FC" if mesh_type == "FC" else "TC"
     nv, nf = int(v.shape[0]), int(f.shape[0])
     if nf < 2:
         raise ValueError(f"n_samples={nf} should be >= n_clusters=2.")
-    ws = torch.empty(int(lib.oai_mesh_split_workspace_bytes(nv, nf, _MESH_TYPE[kind], _N_INIT[kind])), dtype=torch.uint8, device=v.device)
+    ws = _workspace("oai_mesh_split", v.device, nv, nf, _MESH_TYPE[kind], _N_INIT[kind])
     cent = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
     nrm = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
     side = torch.empty(nf, dtype=torch.int8, device=v.device)
     counts = (C.c_longlong * 3)()
-    with torch.cuda.device(v.device):
-        _lib.check(lib.oai_mesh_split_features(v.data_ptr(), nv, f.data_ptr(), nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), cent.data_ptr(),
-                                               nrm.data_ptr(), counts, _stream()), "oai_mesh_split_features")
-        n_slabs = 3 if kind == "FC" else 1
-        first, uni = _kmeans_draws(list(counts)[:n_slabs], _N_INIT[kind])
-        n_iter = (C.c_int * 3)()
-        _lib.check(lib.oai_mesh_split_kmeans(nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), nrm.data_ptr(), _N_INIT[kind], _KMEANS_MAX_ITER, counts,
-                                             (C.c_longlong * len(first))(*first), (C.c_double * len(uni))(*uni), side.data_ptr(), n_iter, _stream()),
-                   "oai_mesh_split_kmeans")
+    _call("oai_mesh_split_features", v.device, v.data_ptr(), nv, f.data_ptr(), nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), cent.data_ptr(),
+          nrm.data_ptr(), counts)
+    n_slabs = 3 if kind == "FC" else 1
+    first, uni = _kmeans_draws(list(counts)[:n_slabs], _N_INIT[kind])
+    n_iter = (C.c_int * 3)()
+    _call("oai_mesh_split_kmeans", v.device, nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), nrm.data_ptr(), _N_INIT[kind], _KMEANS_MAX_ITER, counts,
+          (C.c_longlong * len(first))(*first), (C.c_double * len(uni))(*uni), side.data_ptr(), n_iter)
     return DeviceSplit(v, f, side, cent, nrm, np.array(list(n_iter)[:n_slabs], dtype=np.int64))
 
 
@@ -480,23 +449,20 @@ def split_mesh_device(mesh: Mesh, mesh_type: str = "FC") -> DeviceSplit:
     nf = len(mesh.faces)
     if nf < 2:
         raise ValueError(f"n_samples={nf} should be >= n_clusters=2.")
-    return _split_dev(_dev(mesh.verts.reshape(-1, 3), np.float32), _dev(mesh.faces.reshape(-1, 3), np.int32), mesh_type)
+    return _split_dev(_dev(mesh.verts, np.float32, (3,)), _dev(mesh.faces, np.int32, (3,)), mesh_type)
 
 
 def _sub_mesh_dev(split: DeviceSplit, which: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """get_sub_mesh_device, left on the device: (verts, faces, face list int32)."""
-    lib = _lib.load()
     nv, nf = int(split.verts.shape[0]), int(split.faces.shape[0])
     dev = split.verts.device
-    ws = torch.empty(int(lib.oai_mesh_submesh_workspace_bytes(nv, nf)), dtype=torch.uint8, device=dev)
+    ws = _workspace("oai_mesh_submesh", dev, nv, nf)
     vo = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     fo = torch.empty((nf, 3), dtype=torch.int32, device=dev)
     io = torch.empty(nf, dtype=torch.int32, device=dev)
     n_v, n_f = C.c_longlong(), C.c_longlong()
-    with torch.cuda.device(dev):
-        _lib.check(lib.oai_mesh_submesh(split.verts.data_ptr(), nv, split.faces.data_ptr(), nf, split.side.data_ptr(), int(which), ws.data_ptr(),
-                                        ws.numel(), vo.data_ptr(), fo.data_ptr(), io.data_ptr(), C.byref(n_v), C.byref(n_f), _stream()),
-                   "oai_mesh_submesh")
+    _call("oai_mesh_submesh", dev, split.verts.data_ptr(), nv, split.faces.data_ptr(), nf, split.side.data_ptr(), int(which), ws.data_ptr(),
+          ws.numel(), vo.data_ptr(), fo.data_ptr(), io.data_ptr(), C.byref(n_v), C.byref(n_f))
     return vo[:n_v.value], fo[:n_f.value], io[:n_f.value]
 
 
@@ -540,9 +506,10 @@ def split_mesh(mesh: Mesh, mesh_type: str = "FC", on_device: bool = False) -> Tu
 
 
 # ---- thickness -----------------------------------------------------------------------------------------------------------------
-def _grid_from_params(lo: np.ndarray, hi: np.ndarray, edge) -> Tuple[float, np.ndarray, np.ndarray]:
-    """point_distance's grid: cell h, dims and lower corner from the float64 bounds and the longest edge."""
-    h = max(float(edge) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)              # at most 512 cells per axis
+def _grid_from_params(lo: np.ndarray, hi: np.ndarray, reach) -> Tuple[float, np.ndarray, np.ndarray]:
+    """The uniform grid of a broad phase: cell h, dims and lowered corner from the float64 bounds and the length a cell must cover
+    (point_distance: the longest edge; map_attributes: the radius)."""
+    h = max(float(reach) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)             # at most 512 cells per axis
     dims = np.maximum(np.ceil((hi - lo) / h).astype(np.int64) + 1, 1)
     return h, dims, lo - 0.5 * h * 1e-3
 
@@ -550,33 +517,27 @@ def _grid_from_params(lo: np.ndarray, hi: np.ndarray, edge) -> Tuple[float, np.n
 def mesh_grid_params_device(verts, faces) -> Tuple[np.ndarray, np.ndarray, np.float64]:
     """(lo, hi, longest edge) as point_distance computes them on the host -- float32 bounds as float64, the longest edge in fp64 --
     from device tensors, with one 56-byte download."""
-    lib = _lib.load()
-    v, f = _verts_dev(verts), _faces_dev(faces)
+    v, f = _dev(verts, np.float32, (3,)), _dev(faces, np.int32, (3,))
     out = torch.empty(7, dtype=torch.float64, device=v.device)
-    ws = torch.empty(int(lib.oai_mesh_grid_params_workspace_bytes()), dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        _lib.check(lib.oai_mesh_grid_params(v.data_ptr(), int(v.shape[0]), f.data_ptr(), int(f.shape[0]), ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                            _stream()), "oai_mesh_grid_params")
+    ws = _workspace("oai_mesh_grid_params", v.device)
+    _call("oai_mesh_grid_params", v.device, v.data_ptr(), int(v.shape[0]), f.data_ptr(), int(f.shape[0]), ws.data_ptr(), ws.numel(), out.data_ptr())
     o = out.cpu().numpy()
     return o[0:3].copy(), o[3:6].copy(), np.sqrt(o[6])          # sqrt is monotone and correctly rounded: the max of the host's norms
 
 
 def _point_distance_dev(p: torch.Tensor, v: torch.Tensor, f: torch.Tensor, grid=None) -> torch.Tensor:
     """Distances from the points p to the mesh (v, f), all device tensors.  ``grid`` = (lo, hi, edge) selects the broad phase."""
-    lib = _lib.load()
     n_points, n_tris = int(p.shape[0]), int(f.shape[0])
     out = torch.empty(n_points, dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        if grid is not None:
-            h, dims, lo = _grid_from_params(*grid)
-            glo = (C.c_float * 3)(*[float(x) for x in lo])
-            gd = (C.c_int * 3)(*[int(x) for x in dims])
-            ws = torch.empty(int(lib.oai_mesh_grid_workspace_bytes(gd, n_tris)), dtype=torch.uint8, device=p.device)
-            _lib.check(lib.oai_mesh_point_distance_grid(p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, glo, float(h), gd,
-                                                        ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "oai_mesh_point_distance_grid")
-        else:
-            _lib.check(lib.oai_mesh_point_distance(p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, out.data_ptr(), _stream()),
-                       "oai_mesh_point_distance")
+    if grid is not None:
+        h, dims, lo = _grid_from_params(*grid)
+        glo = (C.c_float * 3)(*[float(x) for x in lo])
+        gd = (C.c_int * 3)(*[int(x) for x in dims])
+        ws = _workspace("oai_mesh_grid", p.device, gd, n_tris)
+        _call("oai_mesh_point_distance_grid", p.device, p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, glo, float(h), gd, ws.data_ptr(),
+              ws.numel(), out.data_ptr())
+    else:
+        _call("oai_mesh_point_distance", p.device, p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, out.data_ptr())
     return out
 
 
@@ -608,6 +569,13 @@ def _distance_dev(p: torch.Tensor, v: torch.Tensor, f: torch.Tensor) -> torch.Te
     return _point_distance_dev(p, v, f, mesh_grid_params_device(v, f) if f.shape[0] > 0 else None)
 
 
+def _resident_split(vol: torch.Tensor, spacing_xyz, mesh_type: str, min_cells: int = 3000) -> DeviceSplit:
+    """The resident chain up to the split, the one place it is spelled out: marching cubes, large regions, edge graph, 150 smoothing
+    sweeps, device k-means.  A caller builds the sub-meshes (_sub_mesh_dev) and distances (_distance_dev) it needs from the result.
+    Raises ValueError on a map without a large region."""
+    return _split_dev(*_mesh_resident(vol, spacing_xyz, 150, min_cells), mesh_type)
+
+
 def get_thickness_mesh(itk_image, mesh_type: str = "FC", num_iterations: int = 150, min_cells: int = 3000,
                        split_on_device: bool = False, on_device: bool = False, spacing_xyz=None) -> Tuple[Mesh, Mesh]:
     """mesh_processing.py:381-395 (which, like this, always smooths with 150 iterations).  ``split_on_device``: see split_mesh (it
@@ -620,10 +588,8 @@ def get_thickness_mesh(itk_image, mesh_type: str = "FC", num_iterations: int = 1
         mesh = get_mesh(itk_image, num_iterations=150, min_cells=min_cells)
         inner, outer = split_mesh(mesh, mesh_type, on_device=split_on_device)
         return get_distance(inner, outer)
-    v, f = _mesh_resident(*_volume_dev(itk_image, spacing_xyz), 150, min_cells)
-    sp = _split_dev(v, f, mesh_type)
-    iv, if_, _ = _sub_mesh_dev(sp, -1)
-    ov, of, _ = _sub_mesh_dev(sp, 1)
+    sp = _resident_split(*_probmap_dev(itk_image, spacing_xyz)[:2], mesh_type, min_cells)
+    (iv, if_, _), (ov, of, _) = _sub_mesh_dev(sp, -1), _sub_mesh_dev(sp, 1)
     d_in, d_out = _distance_dev(iv, ov, of), _distance_dev(ov, iv, if_)
     return (Mesh(iv.cpu().numpy(), if_.cpu().numpy(), {"Distance": d_in.cpu().numpy()}),
             Mesh(ov.cpu().numpy(), of.cpu().numpy(), {"Distance": d_out.cpu().numpy()}))
@@ -633,10 +599,8 @@ def _thickness_inner_dev(vol: torch.Tensor, spacing_xyz, mesh_type: str, min_cel
     """The resident branch of get_thickness_mesh without its second distance and without downloads: (inner verts, inner faces,
     distance inner -> outer) as device tensors, the bits of ``get_thickness_mesh(..., on_device=True)[0]`` (a point's distance does not
     depend on the other direction having been computed).  Raises the same ValueError on a map without a large region."""
-    v, f = _mesh_resident(vol, spacing_xyz, 150, min_cells)
-    sp = _split_dev(v, f, mesh_type)
-    iv, if_, _ = _sub_mesh_dev(sp, -1)
-    ov, of, _ = _sub_mesh_dev(sp, 1)
+    sp = _resident_split(vol, spacing_xyz, mesh_type, min_cells)
+    (iv, if_, _), (ov, of, _) = _sub_mesh_dev(sp, -1), _sub_mesh_dev(sp, 1)
     return iv, if_, _distance_dev(iv, ov, of)
 
 
@@ -658,20 +622,17 @@ def _map_attributes_dev(src_verts: torch.Tensor, src_vals: torch.Tensor, tgt_ver
     """map_attributes' grid broad phase on device tensors: float32 source points [n_src,3], values [n_comp,n_src], targets [n_tgt,3]
     -> float32 [n_comp,n_tgt], nothing downloaded.  ``grid`` = (lo, hi), the float64 bounds of the source points as the host path takes
     them (float32 minima / maxima widened; mesh_grid_params_device returns the same)."""
-    lib = _lib.load()
     n_src, n_comp, n_tgt = int(src_verts.shape[0]), int(src_vals.shape[0]), int(tgt_verts.shape[0])
     if n_src == 0:
         raise ValueError("map_attributes: the source mesh has no points")
     lo, hi = (np.asarray(x, dtype=np.float64).reshape(3) for x in grid)
     out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=src_verts.device)
-    h = max(float(radius) * 1.0001, float((hi - lo).max()) / 512.0, 1e-6)          # at most 512 cells per axis
-    dims = np.maximum(np.ceil((hi - lo) / h).astype(np.int64) + 1, 1)
-    glo = (C.c_double * 3)(*[float(x) for x in lo - 0.5 * h * 1e-3])
+    h, dims, lo = _grid_from_params(lo, hi, radius)
+    glo = (C.c_double * 3)(*[float(x) for x in lo])
     gd = (C.c_int * 3)(*[int(x) for x in dims])
-    with torch.cuda.device(src_verts.device):
-        ws = torch.empty(int(lib.oai_point_grid_workspace_bytes(gd, n_src)), dtype=torch.uint8, device=src_verts.device)
-        _lib.check(lib.oai_map_attributes_grid(src_verts.data_ptr(), n_src, src_vals.data_ptr(), n_comp, tgt_verts.data_ptr(), n_tgt, float(radius), glo,
-                                               float(h), gd, ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "oai_map_attributes_grid")
+    ws = _workspace("oai_point_grid", src_verts.device, gd, n_src)
+    _call("oai_map_attributes_grid", src_verts.device, src_verts.data_ptr(), n_src, src_vals.data_ptr(), n_comp, tgt_verts.data_ptr(), n_tgt,
+          float(radius), glo, float(h), gd, ws.data_ptr(), ws.numel(), out.data_ptr())
     return out
 
 
@@ -685,7 +646,7 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
     and point data plus the interpolated source arrays; on a name clash the source array wins.  ``broad_phase``: bin the source
     points into a uniform grid (cells >= radius, at most 512 per axis); False = brute force over every source point (same result).
     """
-    lib = _lib.load()
+    _lib.load()
     if len(source_mesh.verts) == 0:
         raise ValueError("map_attributes: the source mesh has no points")
     names, vals = _point_arrays(source_mesh)
@@ -693,14 +654,12 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
     n_tgt, n_src, n_comp = len(target_mesh.verts), len(source_mesh.verts), vals.shape[0]
     if n_comp == 0:
         return Mesh(target_mesh.verts, target_mesh.faces, out_data)
-    s, v, t = _dev(source_mesh.verts, np.float32), _dev(vals, np.float32), _dev(target_mesh.verts.reshape(-1, 3), np.float32)
+    s, v, t = _dev(source_mesh.verts, np.float32), _dev(vals, np.float32), _dev(target_mesh.verts, np.float32, (3,))
     if broad_phase:
         out = _map_attributes_dev(s, v, t, radius, grid=(source_mesh.verts.min(axis=0).astype(np.float64), source_mesh.verts.max(axis=0).astype(np.float64)))
     else:
         out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=s.device)
-        with torch.cuda.device(s.device):
-            _lib.check(lib.oai_map_attributes(s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr(), _stream()),
-                       "oai_map_attributes")
+        _call("oai_map_attributes", s.device, s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr())
     res = out.cpu().numpy()
     row = 0
     for name, shape in names:
@@ -711,13 +670,10 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
 
 
 def _fit_circle_dev(pts: torch.Tensor, col_x: int, col_y: int) -> Tuple[np.ndarray, float]:
-    lib = _lib.load()
     n = int(pts.shape[0])
-    ws = torch.empty(max(int(lib.oai_thickness_map_workspace_bytes(n)), 1), dtype=torch.uint8, device=pts.device)
+    ws = _workspace("oai_thickness_map", pts.device, n, pad=True)
     centre, radius, its = (C.c_double * 2)(), C.c_double(), C.c_int()
-    with torch.cuda.device(pts.device):
-        _lib.check(lib.oai_fit_circle(pts.data_ptr(), n, col_x, col_y, ws.data_ptr(), ws.numel(), centre, C.byref(radius), C.byref(its), _stream()),
-                   "oai_fit_circle")
+    _call("oai_fit_circle", pts.device, pts.data_ptr(), n, col_x, col_y, ws.data_ptr(), ws.numel(), centre, C.byref(radius), C.byref(its))
     return np.array([centre[0], centre[1]], dtype=np.float64), float(radius.value)
 
 
@@ -744,13 +700,11 @@ def get_cylinder(vertice):
 
 
 def _project_circle_dev(pts: torch.Tensor, col_x: int, col_y: int, centre) -> Tuple[np.ndarray, np.ndarray]:
-    lib = _lib.load()
     n = int(pts.shape[0])
     angle = torch.empty(n, dtype=torch.float64, device=pts.device)
     z = torch.empty(n, dtype=torch.float64, device=pts.device)
     c = (C.c_double * 2)(float(centre[0]), float(centre[1]))
-    with torch.cuda.device(pts.device):
-        _lib.check(lib.oai_project_circle(pts.data_ptr(), n, col_x, col_y, c, angle.data_ptr(), z.data_ptr(), _stream()), "oai_project_circle")
+    _call("oai_project_circle", pts.device, pts.data_ptr(), n, col_x, col_y, c, angle.data_ptr(), z.data_ptr())
     return angle.cpu().numpy(), z.cpu().numpy()
 
 
@@ -780,7 +734,7 @@ def project_thickness(mapped_mesh: Mesh, mesh_type: str = "FC", embedded=None) -
     sklearn's svd_flip(u) does (the point with the largest |score| scores positive, first index on a tie); the left plateau rotated
     by -50 degrees, the right one by -160 degrees with x negated and 50 added to y; the right plateau's points first.  An empty
     plateau raises ValueError (the reference crashes there)."""
-    lib = _lib.load()
+    _lib.load()
     if "Distance" in mapped_mesh.point_data:
         thickness = np.asarray(mapped_mesh.point_data["Distance"])
     elif len(mapped_mesh.point_data) == 1:
@@ -800,12 +754,11 @@ def project_thickness(mapped_mesh: Mesh, mesh_type: str = "FC", embedded=None) -
     if not (z >= 50).any() or not (z < 50).any():
         raise ValueError("project_thickness(TC): one tibial plateau is empty (no point with z < 50 or none with z >= 50)")
     th = _dev(thickness, np.float32)
-    ws = torch.empty(int(lib.oai_thickness_map_workspace_bytes(n)), dtype=torch.uint8, device=pts.device)
+    ws = _workspace("oai_thickness_map", pts.device, n)
     out = torch.empty((3, n), dtype=torch.float64, device=pts.device)
     n_right, n_left = C.c_longlong(), C.c_longlong()
-    with torch.cuda.device(pts.device):
-        _lib.check(lib.oai_project_plateaus(pts.data_ptr(), th.data_ptr(), n, ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(),
-                                            out[2].data_ptr(), C.byref(n_right), C.byref(n_left), _stream()), "oai_project_plateaus")
+    _call("oai_project_plateaus", pts.device, pts.data_ptr(), th.data_ptr(), n, ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(),
+          out[2].data_ptr(), C.byref(n_right), C.byref(n_left))
     res = out[:, :n_right.value + n_left.value].cpu().numpy()
     return res[0].copy(), res[1].copy(), res[2].copy()
 
@@ -846,49 +799,45 @@ def thickness_image_build(uv, faces, face_skip=None, image_shape=(256, 256)) -> 
     """Rasterise a projected mesh once: ``uv`` float64 [n,2] in mesh point order (array or device tensor), ``faces`` int32 [m,3],
     ``face_skip`` bool [m] (faces that must own nothing, e.g. those bridging the two tibial plateaus).  A pixel belongs to the smallest
     face index whose triangle contains its centre (edges inclusive); contract in include/oai_hip.h, "Thickness image"."""
-    lib = _lib.load()
+    _lib.load()
     H, W = (int(x) for x in image_shape)
     uv_host = uv.detach().cpu().numpy() if isinstance(uv, torch.Tensor) else np.asarray(uv)
     lo, step = thickness_image_grid(uv_host, (H, W))
-    uv_d = uv.to(torch.float64).reshape(-1, 2).contiguous() if isinstance(uv, torch.Tensor) and uv.is_cuda else _dev(uv_host.reshape(-1, 2), np.float64)
-    f = _faces_dev(faces)
+    uv_d = _dev(uv, np.float64, (2,))
+    f = _dev(faces, np.int32, (3,))
     n_pts, n_faces = int(uv_d.shape[0]), int(f.shape[0])
     if n_faces == 0:
         raise ValueError("thickness image: the mesh has no faces")
     skip = None
     if face_skip is not None:
-        skip = (face_skip if isinstance(face_skip, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(face_skip, dtype=np.uint8))).to(uv_d.device).to(torch.uint8).contiguous()
+        skip = _dev(face_skip, np.uint8, device=uv_d.device)
         if skip.shape != (n_faces,):
             raise ValueError(f"thickness image: face_skip has shape {tuple(skip.shape)}, the mesh has {n_faces} faces")
     dev = uv_d.device
     owner = torch.empty((H, W), dtype=torch.int32, device=dev)
     corners = torch.empty((H, W, 3), dtype=torch.int32, device=dev)
     weights = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
-    ws = torch.empty(int(lib.oai_thickness_image_workspace_bytes(n_faces, H, W)), dtype=torch.uint8, device=dev)
+    ws = _workspace("oai_thickness_image", dev, n_faces, H, W)
     n_cov = C.c_longlong()
-    with torch.cuda.device(dev):
-        _lib.check(lib.oai_thickness_image_build(uv_d.data_ptr(), n_pts, f.data_ptr(), n_faces, skip.data_ptr() if skip is not None else None,
-                                                 (C.c_double * 2)(*lo), (C.c_double * 2)(*step), H, W, ws.data_ptr(), ws.numel(), owner.data_ptr(),
-                                                 corners.data_ptr(), weights.data_ptr(), C.byref(n_cov), _stream()), "oai_thickness_image_build")
+    _call("oai_thickness_image_build", dev, uv_d.data_ptr(), n_pts, f.data_ptr(), n_faces, skip.data_ptr() if skip is not None else None,
+          (C.c_double * 2)(*lo), (C.c_double * 2)(*step), H, W, ws.data_ptr(), ws.numel(), owner.data_ptr(), corners.data_ptr(), weights.data_ptr(),
+          C.byref(n_cov))
     return ThicknessRaster(owner, corners, weights, lo, step, int(n_cov.value), n_pts)
 
 
 def thickness_image(raster: ThicknessRaster, values):
     """The thickness image of per-point values on the rastered mesh: float32 [H,W] for values [n], [K,H,W] for [K,n]; NaN where no face
     owns the pixel, and NaN spreads from a NaN point to the pixels of its faces.  A device tensor gives a device tensor, an array an array."""
-    lib = _lib.load()
     on_dev = isinstance(values, torch.Tensor)
-    v = (values if on_dev else torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32))).to(raster.owner.device).to(torch.float32).contiguous()
+    v = _dev(values, np.float32, device=raster.owner.device)
     if v.dim() not in (1, 2) or v.shape[-1] != raster.n_points:
         raise ValueError(f"thickness image: values of shape {tuple(v.shape)} do not match the raster's {raster.n_points} points")
     K = 1 if v.dim() == 1 else int(v.shape[0])
     H, W = (int(x) for x in raster.owner.shape)
     img = torch.empty((K, H, W), dtype=torch.float32, device=v.device)
-    with torch.cuda.device(v.device):
-        for k0 in range(0, K, 65535):
-            k1 = min(K, k0 + 65535)
-            _lib.check(lib.oai_thickness_image_apply(raster.owner.data_ptr(), raster.corners.data_ptr(), raster.weights.data_ptr(), H, W,
-                                                     v.reshape(K, -1)[k0:k1].data_ptr(), raster.n_points, k1 - k0, img[k0:k1].data_ptr(), _stream()),
-                       "oai_thickness_image_apply")
+    for k0 in range(0, K, 65535):
+        k1 = min(K, k0 + 65535)
+        _call("oai_thickness_image_apply", v.device, raster.owner.data_ptr(), raster.corners.data_ptr(), raster.weights.data_ptr(), H, W,
+              v.reshape(K, -1)[k0:k1].data_ptr(), raster.n_points, k1 - k0, img[k0:k1].data_ptr())
     img = img[0] if v.dim() == 1 else img
     return img if on_dev else img.cpu().numpy()

@@ -118,12 +118,11 @@ class ThicknessAtlas:
         self.spacing: Dict[str, np.ndarray] = {}            # each map's own (x, y, z) spacing: measure's default for that cartilage
         self.device = None
         for kind, probmap in zip(KINDS, (atlas_fc, atlas_tc)):
-            vol, sp = mp._volume_dev(probmap, spacing_xyz)
-            self.spacing[kind] = np.asarray(sp, dtype=np.float64).copy()
+            vol, sp = mp._probmap_dev(probmap, spacing_xyz)[:2]
+            self.spacing[kind] = sp
             if self.device is None:
                 self.device = vol.device
-            v, f = mp._mesh_resident(vol, sp, 150, self.min_cells[kind])
-            iv, if_, _ = mp._sub_mesh_dev(mp._split_dev(v, f, kind), -1)
+            iv, if_, _ = mp._sub_mesh_dev(mp._resident_split(vol, sp, kind, self.min_cells[kind]), -1)
             if iv.shape[0] == 0:
                 raise ValueError(f"ThicknessAtlas: the atlas {kind} map has no inner surface")
             self._targets[kind] = iv
@@ -149,10 +148,7 @@ class ThicknessAtlas:
             skip = tc_face_skip(mesh.verts[:, 2], mesh.faces)
         self._scatter[kind], self.point_order[kind], self.uv[kind] = (x, y), order, uv
         with torch.cuda.device(self.device):
-            self.raster[kind] = mp.thickness_image_build(uv, self._faces_dev(kind), skip, self.image_shape)
-
-    def _faces_dev(self, kind: str) -> torch.Tensor:
-        return torch.from_numpy(self.inner[kind].faces).to(self.device)
+            self.raster[kind] = mp.thickness_image_build(uv, mesh.faces, skip, self.image_shape)
 
     def n_points(self, kind: str) -> int:
         return len(self.inner[kind].verts)
@@ -179,7 +175,7 @@ class ThicknessAtlas:
         for kind, vol in zip(KINDS, (fc_atlas, tc_atlas)):
             sp = self.spacing[kind] if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
             with torch.cuda.device(self.device):
-                vol_d, _ = mp._volume_dev(vol, sp)
+                vol_d = mp._probmap_dev(vol, sp)[0]
                 try:
                     out[kind] = self._measure_one(vol_d, sp, kind)
                 except ValueError as e:
