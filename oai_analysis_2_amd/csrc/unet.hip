@@ -63,35 +63,29 @@ struct oai_unet {
     // headroom below 65504 and a floor of 2^-35 of the maximum.  Exact: powers of two fold into the epilogue affine and the panels.
     int act_exp[18] = {0};
     bool calibrated = false;
-    int opt_wino_f32 = 1;               // option "winograd_f32": the plain k3 layers of the exact-fp32 path run conv3_wino_f32 (x axis in Winograd F(2,3) form: 2/3 of the fp32 MFMAs)
-    int opt_first_blocks = 24;          // option "first_blocks": workgroups per tile of the ec0 kernel conv3_first_sres_kernel (each walks the tile's voxel pairs with a grid stride, the next pair's gathers under the current pair's FMAs)
-    int opt_up_nbw = 0;                 // option "up_nbw": column blocks per workgroup of the k2s2 up-conv kernel: 0 = as many as keep >= 16 workgroups per slot, 1 = one (rounds 1-5), n = at most n
-    int opt_shared = 1;                 // option "shared_enc": ec0 -> ec1 computed ONCE over the reflect-padded volume + a 2-voxel shell per tile (oai_segment_tiles)
-    int opt_wide = 1;                   // option "wide": layers with Cout % 128 == 0 run conv3_igemm_sres2 (one 8-wave workgroup per CU, double-buffered halo)
-    int opt_wino = 19;                  // option "winograd": plain k3 layers with Cout % 64 == 0 run conv3_wino_sres (x axis in Winograd F(2,3) form: 2/3 of the MFMAs);
-                                        // bit 4 (round 4): the taps of the two-group form on v_mfma_f32_16x16x32_f16 (same cycles per FLOP, +14 % clock at the power wall);
-                                        // bit 5: the same for the 64-cout layer (dc2) -- ALL its launch shapes (specialised main blocks and x strip, slice-split y strip:
-                                        // wino_m16_64), so a voxel's bits do not depend on the shape that covers it; measured within noise of bit 4 alone (-0.2 %), not the default
-    int opt_wino_layers = 0x3FFFF;      // option "winograd_layers": bit k = layer k may take the Winograd kernel (A/B of single layers)
-    int opt_m16 = 1;                    // option "m16": the direct split-resident kernel (conv3_igemm_sres: ec1 + fused ec0, ec2, dc1 + fused head, ...) on
-                                        // v_mfma_f32_16x16x32_f16 tap pairs (round 5; another summation order) for every layer that can never take the bit-identical
-                                        // 128-cout form conv3_igemm_sres2 -- i.e. Cout % 128 != 0 -- so that a layer runs ONE order whatever shapes cover it and
-                                        // option "wide" stays bit-preserving
-    int opt_m16_layers = 0x3FFFF;       // option "m16_layers": bit k = layer k may take the tap-pair form (A/B of single layers)
-    int opt_dead_stores = 1;            // option "dead_stores": 1 = the encoder does not write the part of a skip tensor that the decoder never reads
-    int opt_census = 1;                 // option "census": 0 = the kernels do not record the per-layer maxima (A/B timing of the bookkeeping; no LOW flag)
-    unsigned char* zero_rec = nullptr;  // 64 zero bytes: source of halo voxels outside the tile for the LDS-DMA staging
-    int opt_persist = 0;                // option "persistent": bit 0 = the specialised 64-cout Winograd form (dc2) with persistent workgroups, the staging waves one block
-                                        // ahead (conv3_wino_sres<..., PS>; bit-identical maps)
-    int* ps_plan = nullptr;             // the block plan of a persistent launch (wino_plan_kernel): 288 + 8 x 256 ints
-    int n_cus = 256;                    // compute units of the device (persistent launches: one workgroup per CU)
-    int xcd_group = 32;                 // logical blocks per XCD deal (option "xcd_group"; 0 = launch order)
-    bool sres_ring = false;             // MREP 2 with the six-slot z-plane ring (option "sres_ring")
-    int b_lds = 0;                      // weight fragments through a three-slot LDS ring shared by the workgroup (option "b_lds")
-    int fuse_first = 1;                 // ec0 computed inside ec1's halo staging when ec1 is one main-shape launch (option "fuse_first")
-    int sres_mrep = 4;                  // z slices per block of the split-resident conv kernel (option "sres_mrep" 2|4; 2 runs three workgroups per CU: -2 % on 32 border tiles, +0.5 % on the whole volume)
+    // The tuning options and their defaults.  What each one does is written once, where it is set: kIntOptions / oai_unet_set_option.
+    int opt_wino_f32 = 1;               // option "winograd_f32"
+    int opt_first_blocks = 24;          // option "first_blocks"
+    int opt_up_nbw = 0;                 // option "up_nbw"
+    int opt_shared = 1;                 // option "shared_enc"
+    int opt_wide = 1;                   // option "wide"
+    int opt_wino = 19;                  // option "winograd"
+    int opt_wino_layers = 0x3FFFF;      // option "winograd_layers"
+    int opt_m16 = 1;                    // option "m16"
+    int opt_m16_layers = 0x3FFFF;       // option "m16_layers"
+    int opt_dead_stores = 1;            // option "dead_stores"
+    int opt_census = 1;                 // option "census"
+    int opt_persist = 0;                // option "persistent"
+    int xcd_group = 32;                 // option "xcd_group"
+    bool sres_ring = false;             // option "sres_ring"
+    int b_lds = 0;                      // option "b_lds"
+    int fuse_first = 1;                 // option "fuse_first"
+    int sres_mrep = 4;                  // option "sres_mrep"
     bool opt_sres = true;               // option "sres": fp16x3 uses the split-resident kernels
     bool sres = false;                  // fp16x3 runs split-resident (activations stored as fp16 term pairs, unet_sres.h)
+    unsigned char* zero_rec = nullptr;  // 64 zero bytes: source of halo voxels outside the tile for the LDS-DMA staging
+    int* ps_plan = nullptr;             // the block plan of a persistent launch (wino_plan_kernel): 288 + 8 x 256 ints
+    int n_cus = 256;                    // compute units of the device (persistent launches: one workgroup per CU)
     int n_classes = 0;
     std::vector<void*> allocs;
     bool profile = false;
@@ -135,6 +129,17 @@ static std::vector<float> canonical_k3(const oai_layer_params& p) {
     return w;
 }
 
+// Chunk `ch` of a k3 layer's K loop: the chunks of source 0 (C0 channels) come first, then those of source 1 (the skip tensor of a concat layer:
+// C1 channels, at offset C0 of the layer's input channels).  cl0 = the chunk's first channel inside its source.
+struct ChunkSrc {
+    bool first;
+    int Csrc, cofs, cl0;
+    ChunkSrc(int ch, int C0, int C1, int KC) {
+        const int nch0 = (C0 + KC - 1) / KC;
+        first = ch < nch0; Csrc = first ? C0 : C1; cofs = first ? 0 : C0; cl0 = (first ? ch : ch - nch0) * KC;
+    }
+};
+
 // Panel order = consumption order of conv3_igemm_f32: [cb][chunk][tap][kg][nr][lane] x float4, where the
 // float4 of lane (half h, column j) holds channels 4h..4h+3 of the k-group for cout cb*64+nr*32+j.
 static std::vector<float> pack_conv3_panel(const std::vector<float>& wk, int C0, int C1, int Cout, int KC) {
@@ -144,23 +149,31 @@ static std::vector<float> pack_conv3_panel(const std::vector<float>& wk, int C0,
     size_t o = 0;
     for (int cb = 0; cb < ncb; ++cb)
         for (int ch = 0; ch < nch0 + nch1; ++ch) {
-            const bool first = ch < nch0;
-            const int Csrc = first ? C0 : C1, cofs = first ? 0 : C0, cl0 = (first ? ch : ch - nch0) * KC;
+            const ChunkSrc cs(ch, C0, C1, KC);
             for (int t = 0; t < 27; ++t)
                 for (int kg = 0; kg < KG; ++kg)
                     for (int nr = 0; nr < 2; ++nr)
                         for (int lane = 0; lane < 64; ++lane)
                             for (int s = 0; s < 4; ++s, ++o) {
-                                const int cl = cl0 + kg * 8 + 4 * (lane >> 5) + s;
+                                const int cl = cs.cl0 + kg * 8 + 4 * (lane >> 5) + s;
                                 const int co = cb * 64 + nr * 32 + (lane & 31);
-                                if (cl < Csrc && co < Cout) out[o] = wk[((size_t)t * Cin + cofs + cl) * Cout + co];
+                                if (cl < cs.Csrc && co < Cout) out[o] = wk[((size_t)t * Cin + cs.cofs + cl) * Cout + co];
                             }
         }
     return out;
 }
 
-// conv3_wino_f32 (unet_wino_f32.h): the x-transformed weights u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2, u3 = g2 per (dz, dy, cin, cout), formed in double
-// and rounded to fp32 once; layout [cout block 64][frequency 4][chunk of 8 channels][tap (dz, dy) 9][cout half 2][lane 64][4]: lane (column = lane & 31, k half =
+// Frequency f of the Winograd F(2,3) weight transform along x: g0..g2 = the three x taps of one (dz, dy, cin, cout)
+static inline double wino_u(int f, double g0, double g1, double g2) { return f == 0 ? g0 : f == 1 ? 0.5 * (g0 + g1 + g2) : f == 2 ? 0.5 * (g0 - g1 + g2) : g2; }
+
+// ... of tap row t = dz * 3 + dy, input channel ci, output channel co of wk, the weights first multiplied by `scale` (an exact power of two): formed in double,
+// rounded to fp32 once
+static inline float wino_weight(const std::vector<float>& wk, int f, int t, int Cin, int ci, int Cout, int co, double scale = 1.0) {
+    const size_t i = ((size_t)(t * 3) * Cin + ci) * Cout + co, dx = (size_t)Cin * Cout;
+    return (float)wino_u(f, wk[i] * scale, wk[i + dx] * scale, wk[i + 2 * dx] * scale);
+}
+
+// conv3_wino_f32 (unet_wino_f32.h): the x-transformed weights (wino_weight) per (dz, dy, cin, cout); layout [cout block 64][frequency 4][chunk of 8 channels][tap (dz, dy) 9][cout half 2][lane 64][4]: lane (column = lane & 31, k half =
 // lane >> 5) holds channels 4 (lane >> 5) .. + 3 of cout 32 nr + column -- the B operands of four v_mfma_f32_32x32x2_f32 k-steps, like pack_conv3_panel.
 static std::vector<float> pack_wino_f32_panel(const std::vector<float>& wk, int C0, int C1, int Cout) {
     constexpr int KC = 8;
@@ -171,18 +184,14 @@ static std::vector<float> pack_wino_f32_panel(const std::vector<float>& wk, int 
     for (int cb = 0; cb < ncb; ++cb)
         for (int f = 0; f < 4; ++f)
             for (int ch = 0; ch < nch0 + nch1; ++ch) {
-                const bool first = ch < nch0;
-                const int Csrc = first ? C0 : C1, cofs = first ? 0 : C0, cl0 = (first ? ch : ch - nch0) * KC;
+                const ChunkSrc cs(ch, C0, C1, KC);
                 for (int q = 0; q < 9; ++q)
                     for (int nr = 0; nr < 2; ++nr)
                         for (int lane = 0; lane < 64; ++lane)
                             for (int s = 0; s < 4; ++s, ++o) {
-                                const int cl = cl0 + 4 * (lane >> 5) + s;
+                                const int cl = cs.cl0 + 4 * (lane >> 5) + s;
                                 const int co = cb * 64 + nr * 32 + (lane & 31);
-                                if (cl >= Csrc || co >= Cout) continue;
-                                const double g0 = wk[((size_t)(q * 3 + 0) * Cin + cofs + cl) * Cout + co], g1 = wk[((size_t)(q * 3 + 1) * Cin + cofs + cl) * Cout + co],
-                                             g2 = wk[((size_t)(q * 3 + 2) * Cin + cofs + cl) * Cout + co];
-                                out[o] = (float)(f == 0 ? g0 : f == 1 ? (g0 + g1 + g2) * 0.5 : f == 2 ? (g0 - g1 + g2) * 0.5 : g2);
+                                if (cl < cs.Csrc && co < Cout) out[o] = wino_weight(wk, f, q, Cin, cs.cofs + cl, Cout, co);
                             }
             }
     return out;
@@ -231,6 +240,13 @@ static inline float f16_to_f32(uint16_t h) {
     return f;
 }
 
+// Term `term` (0 = high, 1 = low, ...) of the fp16 split of r: every term is the RNE fp16 of what the terms before it left over
+static inline uint16_t f16_term(float r, int term) {
+    uint16_t b = 0;
+    for (int kk = 0; kk <= term; ++kk) { b = f32_to_f16_rne(r); r -= f16_to_f32(b); }
+    return b;
+}
+
 // Split-bf16 panel of conv3_igemm_bf16s: [cb][chunk of 16][tap][term][nr][lane] x 8 bf16, where lane (half h, column j)
 // holds channels 8h..8h+7 of the chunk for cout cb*64+nr*32+j.  Terms: w = t0 + t1 (+ t2), each the RNE bf16 of the rest.
 // fp16: `wscale[co]` (an exact power of two) multiplies every weight of output channel co before the split.
@@ -246,23 +262,19 @@ static std::vector<float> pack_conv3_panel_bf(const std::vector<float>& wk, int 
     size_t u = 0;
     for (int cb = 0; cb < ncb; ++cb)
         for (int ch = 0; ch < nch0 + nch1; ++ch) {
-            const bool first = ch < nch0;
-            const int Csrc = first ? C0 : C1, cofs = first ? 0 : C0, cl0 = (first ? ch : ch - nch0) * KC;
+            const ChunkSrc cs(ch, C0, C1, KC);
             for (int t = 0; t < 27; ++t)
                 for (int k = 0; k < NS; ++k)
                     for (int nr = 0; nr < 2; ++nr)
                         for (int lane = 0; lane < 64; ++lane, ++u)
                             for (int j = 0; j < 8; ++j) {
-                                const int cl = cl0 + 8 * (lane >> 5) + j;
+                                const int cl = cs.cl0 + 8 * (lane >> 5) + j;
                                 const int co = cb * 64 + nr * 32 + (lane & 31);
-                                if (cl < Csrc && co < Cout) {
-                                    float r = wk[((size_t)t * Cin + cofs + cl) * Cout + co] * (wscale ? (*wscale)[co] : 1.0f) * (first ? 1.0f : src1_factor);
+                                if (cl < cs.Csrc && co < Cout) {
+                                    float r = wk[((size_t)t * Cin + cs.cofs + cl) * Cout + co] * (wscale ? (*wscale)[co] : 1.0f) * (cs.first ? 1.0f : src1_factor);
                                     uint16_t b = 0;
-                                    for (int kk = 0; kk <= k; ++kk) {
-                                        if (fp16) { b = f32_to_f16_rne(r); r -= f16_to_f32(b); }
-                                        else { b = f32_to_bf16_rne(r); r -= bf16_to_f32(b); }
-                                    }
-                                    o16[u * 8 + j] = b;
+                                    for (int kk = 0; kk <= k && !fp16; ++kk) { b = f32_to_bf16_rne(r); r -= bf16_to_f32(b); }
+                                    o16[u * 8 + j] = fp16 ? f16_term(r, k) : b;
                                 }
                             }
         }
@@ -290,8 +302,7 @@ static std::vector<float> pack_conv3_m16_panel(const std::vector<float>& wk, int
     size_t u = 0;
     for (int cb = 0; cb < ncb; ++cb)
         for (int ch = 0; ch < nch0 + nch1; ++ch) {
-            const bool first = ch < nch0;
-            const int Csrc = first ? C0 : C1, cofs = first ? 0 : C0, cl0 = (first ? ch : ch - nch0) * KC;
+            const ChunkSrc cs(ch, C0, C1, KC);
             for (int j = 0; j < 14; ++j)
                 for (int kind = 0; kind < 2; ++kind)             // 0: X', 1: Y'
                     for (int n2 = 0; n2 < 4; ++n2)
@@ -302,12 +313,8 @@ static std::vector<float> pack_conv3_m16_panel(const std::vector<float>& wk, int
                             const int co = cb * 64 + n2 * 16 + (lane & 15);
                             if (co >= Cout) continue;
                             for (int e = 0; e < 8; ++e) {
-                                const int cl = cl0 + 8 * (g & 1) + e;
-                                if (cl >= Csrc) continue;
-                                float r = wk[((size_t)t * Cin + cofs + cl) * Cout + co] * wscale[co] * (first ? 1.0f : src1_factor);
-                                uint16_t b = 0;
-                                for (int kk = 0; kk <= term; ++kk) { b = f32_to_f16_rne(r); r -= f16_to_f32(b); }
-                                o16[u * 8 + e] = b;
+                                const int cl = cs.cl0 + 8 * (g & 1) + e;
+                                if (cl < cs.Csrc) o16[u * 8 + e] = f16_term(wk[((size_t)t * Cin + cs.cofs + cl) * Cout + co] * wscale[co] * (cs.first ? 1.0f : src1_factor), term);
                             }
                         }
         }
@@ -328,24 +335,15 @@ static std::vector<float> pack_wino_panel(const std::vector<float>& wk, int C0, 
     for (int cb = 0; cb < ncb; ++cb)
         for (int f = 0; f < 4; ++f)
             for (int ch = 0; ch < nch0 + nch1; ++ch) {
-                const bool first = ch < nch0;
-                const int Csrc = first ? C0 : C1, cofs = first ? 0 : C0, cl0 = (first ? ch : ch - nch0) * KC;
+                const ChunkSrc cs(ch, C0, C1, KC);
                 for (int t = 0; t < 9; ++t)                          // t = dz * 3 + dy
                     for (int k = 0; k < 2; ++k)
                         for (int nr = 0; nr < 2; ++nr)
                             for (int lane = 0; lane < 64; ++lane, ++u)
                                 for (int j = 0; j < 8; ++j) {
-                                    const int cl = cl0 + 8 * (lane >> 5) + j;
+                                    const int cl = cs.cl0 + 8 * (lane >> 5) + j;
                                     const int co = cb * 64 + nr * 32 + (lane & 31);
-                                    if (cl >= Csrc) continue;
-                                    double g[3];
-                                    for (int dx = 0; dx < 3; ++dx)
-                                        g[dx] = (double)wk[((size_t)(t * 3 + dx) * Cin + cofs + cl) * Cout + co] * (double)wscale[co] * (first ? 1.0 : (double)src1_factor);
-                                    const double uf = f == 0 ? g[0] : f == 1 ? 0.5 * (g[0] + g[1] + g[2]) : f == 2 ? 0.5 * (g[0] - g[1] + g[2]) : g[2];
-                                    float r = (float)uf;
-                                    uint16_t b = 0;
-                                    for (int kk = 0; kk <= k; ++kk) { b = f32_to_f16_rne(r); r -= f16_to_f32(b); }
-                                    o16[u * 8 + j] = b;
+                                    if (cl < cs.Csrc) o16[u * 8 + j] = f16_term(wino_weight(wk, f, t, Cin, cs.cofs + cl, Cout, co, (double)wscale[co] * (cs.first ? 1.0 : (double)src1_factor)), k);
                                 }
             }
     return out;
@@ -365,8 +363,7 @@ static std::vector<float> pack_wino16_panel(const std::vector<float>& wk, int C0
     for (int cb = 0; cb < ncb; ++cb)
         for (int f = 0; f < 4; ++f)
             for (int ch = 0; ch < nch0 + nch1; ++ch) {
-                const bool first = ch < nch0;
-                const int Csrc = first ? C0 : C1, cofs = first ? 0 : C0, cl0 = (first ? ch : ch - nch0) * KC;
+                const ChunkSrc cs(ch, C0, C1, KC);
                 for (int j = 0; j < 5; ++j)
                     for (int kind = 0; kind < 2; ++kind)             // 0: X', 1: Y'
                         for (int n2 = 0; n2 < 4; ++n2)
@@ -377,16 +374,8 @@ static std::vector<float> pack_wino16_panel(const std::vector<float>& wk, int C0
                                 else { t = 8; term = kind; if (kind == 1 && tsel == 1) continue; }     // step 4: X' = [b0 | b0], Y' = [b1 | 0]
                                 const int co = cb * 64 + n2 * 16 + (lane & 15);
                                 for (int e = 0; e < 8; ++e) {
-                                    const int cl = cl0 + 8 * (g & 1) + e;
-                                    if (cl >= Csrc) continue;
-                                    double gx[3];
-                                    for (int dx = 0; dx < 3; ++dx)
-                                        gx[dx] = (double)wk[((size_t)(t * 3 + dx) * Cin + cofs + cl) * Cout + co] * (double)wscale[co] * (first ? 1.0 : (double)src1_factor);
-                                    const double uf = f == 0 ? gx[0] : f == 1 ? 0.5 * (gx[0] + gx[1] + gx[2]) : f == 2 ? 0.5 * (gx[0] - gx[1] + gx[2]) : gx[2];
-                                    float r = (float)uf;
-                                    uint16_t b = 0;
-                                    for (int kk = 0; kk <= term; ++kk) { b = f32_to_f16_rne(r); r -= f16_to_f32(b); }
-                                    o16[u * 8 + e] = b;
+                                    const int cl = cs.cl0 + 8 * (g & 1) + e;
+                                    if (cl < cs.Csrc) o16[u * 8 + e] = f16_term(wino_weight(wk, f, t, Cin, cs.cofs + cl, Cout, co, (double)wscale[co] * (cs.first ? 1.0 : (double)src1_factor)), term);
                                 }
                             }
             }
@@ -431,10 +420,7 @@ static std::vector<float> pack_up_panel_f16(const float* w /*[ci][co][8]*/, int 
                             const int col = nb * 64 + nr * 32 + (lane & 31);
                             if (ci < cin && col < N) {
                                 const int par = col / cout, co = col % cout;
-                                float r = w[((size_t)ci * cout + co) * 8 + par] * wscale[co];
-                                uint16_t b = 0;
-                                for (int kk = 0; kk <= k; ++kk) { b = f32_to_f16_rne(r); r -= f16_to_f32(b); }
-                                o16[u * 8 + j] = b;
+                                o16[u * 8 + j] = f16_term(w[((size_t)ci * cout + co) * 8 + par] * wscale[co], k);
                             }
                         }
     return out;
@@ -565,15 +551,12 @@ __host__ __device__ static void plan_regions(const int tile[3], const int keep_l
     // dc9 and the encoder stay full: the bottleneck sees the whole tile
 }
 
-struct Plan {
-    size_t off[24];
-    size_t total;
-};
 constexpr int kMaxTilesPerTable = 4096;
-constexpr size_t kBoxTableBytes = ((size_t)18 * kMaxTilesPerTable * 6 * sizeof(int) + 255) / 256 * 256;
 enum Buf { B_E0, B_SYN0, B_P0, B_E2, B_SYN1, B_P1, B_E4, B_SYN2, B_P2, B_E6, B_E7, B_U9, B_D8, B_D7, B_U6, B_D5, B_D4, B_U3, B_D2, B_D1, B_COUNT };
 
-static Plan plan_workspace(const oai_unet* h, int td, int th, int tw, int batch) {
+// The workspace of one pass of `batch` tiles: the per-tile box table of the current oai_segment_tiles call at the start, then the activation
+// tensors.  Returns the bytes; over a null `base` the pointers are null and only the size counts (oai::Ws).
+static size_t carve_workspace(const oai_unet* h, int td, int th, int tw, int batch, const void* base, float* buf[B_COUNT], int*& table) {
     const size_t v0 = (size_t)td * th * tw, v1 = v0 / 8, v2 = v1 / 8, v3 = v2 / 8;
     const oai::Layer* L = h->L;
     auto pc = [&](int k) { return (size_t)((L[k].cout + 15) / 16 * 16); };   // channels padded to whole 16-chunks (format S)
@@ -582,14 +565,71 @@ static Plan plan_workspace(const oai_unet* h, int td, int th, int tw, int batch)
         v2 * pc(EC4), v2 * pc(EC5), v3 * pc(EC5), v3 * pc(EC6), v3 * pc(EC7), v2 * pc(DC9),
         v2 * pc(DC8), v2 * pc(DC7), v1 * pc(DC6), v1 * pc(DC5), v1 * pc(DC4), v0 * pc(DC3),
         v0 * pc(DC2), v0 * pc(DC1)};
-    Plan p;
-    size_t o = kBoxTableBytes;          // per-tile box table of the current oai_segment_tiles call lives at the start
-    for (int i = 0; i < B_COUNT; ++i) {
-        p.off[i] = o;
-        o += ((sizes[i] * batch * sizeof(float) + 255) / 256) * 256;
+    Ws ws(base);
+    table = ws.take<int>((size_t)18 * kMaxTilesPerTable * 6);
+    for (int i = 0; i < B_COUNT; ++i) buf[i] = ws.take<float>(sizes[i] * batch);
+    return ws.off;
+}
+static size_t workspace_bytes(const oai_unet* h, int td, int th, int tw, int batch) {
+    float* buf[B_COUNT];
+    int* table;
+    return carve_workspace(h, td, th, tw, batch, nullptr, buf, table);
+}
+
+// One timed launch: with profiling on (oai_unet_profile) the kernel sits between a start / stop pair of the handle's event pool, which grows as needed and
+// is reused after every oai_unet_profile_read.  launch_begin before the launch; launch_end after it checks the launch and records the stop event.
+static int launch_begin(const oai_unet* h, hipStream_t st) {
+    if (!h->profile) return OAI_OK;
+    oai_unet* hm = const_cast<oai_unet*>(h);
+    while (hm->ev_used + 2 > hm->ev_pool.size()) {
+        hipEvent_t e;
+        OAI_CHECK_HIP(hipEventCreate(&e));
+        hm->ev_pool.push_back(e);
     }
-    p.total = o;
-    return p;
+    OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used], st));
+    return OAI_OK;
+}
+static int launch_end(const oai_unet* h, hipStream_t st) {
+    OAI_CHECK_LAUNCH();
+    if (!h->profile) return OAI_OK;
+    oai_unet* hm = const_cast<oai_unet*>(h);
+    OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used + 1], st));
+    hm->ev_used += 2;
+    return OAI_OK;
+}
+
+// XCD-aware dealing of a launch's logical block list (xcd_block_id in the kernels): the kernel gets the number of real blocks and the grid is rounded up
+// to whole deals of xcd_group blocks to each of the 8 XCDs.  Option "xcd_group" 0: plain launch order, the grid as it is.
+static unsigned xcd_deal(const oai_unet* h, unsigned grid, int& nblocks, int& xcd_group) {
+    if (h->xcd_group <= 0) return grid;
+    nblocks = (int)grid; xcd_group = h->xcd_group;
+    const unsigned q = 8u * (unsigned)h->xcd_group;
+    return (grid + q - 1) / q * q;
+}
+
+// per-layer accessors: a layer's index in the schedule, its bit of a layer mask (options "winograd_layers", "m16_layers"), its 16 census words (null: option
+// "census" 0 -- callers add their own h->sres condition)
+static inline int layer_id(const oai_unet* h, const Layer& L) { return (int)(&L - h->L); }
+static inline bool layer_bit(const oai_unet* h, int mask, const Layer& L) { return (mask >> layer_id(h, L)) & 1; }
+static inline unsigned* census_of(const oai_unet* h, int k) { return h->opt_census ? h->census + 16 * k : nullptr; }
+#ifdef OAI_DIAG
+static unsigned long long* layer_stamps(const oai_unet* h, const Layer& L) {     // OAI_STAMP_LAYER: one layer's budget (EC1 = 1 ..., DC9 = 8, DC6 = 11, DC3 = 14)
+    static const int only = diag_env("OAI_STAMP_LAYER", -1);
+    return only >= 0 && layer_id(h, L) != only ? nullptr : diag_stamps();
+}
+#endif
+
+// the grid of an elementwise kernel: one thread per element in blocks of 256, at most `cap` blocks (the kernels walk the rest with a grid stride)
+static inline unsigned capped_blocks(size_t total, size_t cap) { return (unsigned)std::min<size_t>((total + 255) / 256, cap); }
+
+// conv3_igemm_sres2 in its variant `var`: 0 in the production library; -DOAI_DIAG builds also have the diagnostic variants 1..10 (OAI_WIDE_VAR)
+template <int RX, int RY, int WY, int WX, int V = 0>
+static void launch_sres2(int var, unsigned grid, hipStream_t st, const ConvArgs& a, const unsigned char* zero_rec) {
+#ifdef OAI_DIAG
+    if constexpr (V < 10)
+        if (var != V) return launch_sres2<RX, RY, WY, WX, V + 1>(var, grid, st, a, zero_rec);
+#endif
+    conv3_igemm_sres2<RX, RY, WY, WX, V><<<grid, 512, 0, st>>>(a, zero_rec);
 }
 
 template <int MREP, int KC, int RX, int RY, int WY, int WX>
@@ -617,22 +657,8 @@ static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int
     a.nby = cdiv(box.hi[1] - box.lo[1], WY * RY);
     a.nbx = cdiv(box.hi[2] - box.lo[2], WX * RX);
     unsigned grid = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-    if (KC == 8 && h->sres && h->xcd_group > 0) {          // XCD-aware dealing of the logical block list (xcd_block_id)
-        a.nblocks = (int)grid; a.xcd_group = h->xcd_group;
-        const unsigned q = 8u * (unsigned)h->xcd_group;
-        grid = (grid + q - 1) / q * q;
-    }
-    oai_unet* hm = const_cast<oai_unet*>(h);
-    if (h->profile) {
-        if (hm->ev_used + 2 > hm->ev_pool.size()) {
-            hipEvent_t e0, e1;
-            OAI_CHECK_HIP(hipEventCreate(&e0));
-            OAI_CHECK_HIP(hipEventCreate(&e1));
-            hm->ev_pool.push_back(e0);
-            hm->ev_pool.push_back(e1);
-        }
-        OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used], st));
-    }
+    if (KC == 8 && h->sres) grid = xcd_deal(h, grid, a.nblocks, a.xcd_group);
+    if (int rc = launch_begin(h, st)) return rc;
     if (KC == 8 && h->sres) {
         // (diagnostic builds: OAI_ONE_WG=1 asks for 24 KB of unused dynamic LDS, which leaves room for ONE workgroup per CU -- the tap
         // stream of a wave that has the SIMD to itself, scripts/stamp_phases.py)
@@ -652,21 +678,7 @@ static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int
         if constexpr (kWideShape) {
             if (wide) {
                 static const int var = diag_env("OAI_WIDE_VAR", 0);         // -DOAI_DIAG builds only; constant 0 otherwise
-#ifdef OAI_DIAG
-                if (var == 1) conv3_igemm_sres2<RX, RY, WY, WX, 1><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 2) conv3_igemm_sres2<RX, RY, WY, WX, 2><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 3) conv3_igemm_sres2<RX, RY, WY, WX, 3><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 4) conv3_igemm_sres2<RX, RY, WY, WX, 4><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 5) conv3_igemm_sres2<RX, RY, WY, WX, 5><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 6) conv3_igemm_sres2<RX, RY, WY, WX, 6><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 7) conv3_igemm_sres2<RX, RY, WY, WX, 7><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 8) conv3_igemm_sres2<RX, RY, WY, WX, 8><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 9) conv3_igemm_sres2<RX, RY, WY, WX, 9><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else if (var == 10) conv3_igemm_sres2<RX, RY, WY, WX, 10><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                else
-#endif
-                conv3_igemm_sres2<RX, RY, WY, WX, 0><<<grid, 512, 0, st>>>(a, h->zero_rec);
-                (void)var;
+                launch_sres2<RX, RY, WY, WX>(var >= 1 && var <= 10 ? var : 0, grid, st, a, h->zero_rec);
                 done = true;
             }
         }
@@ -683,34 +695,38 @@ static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int
     else if (KC == 8 && h->precision == OAI_PREC_BF16X6) conv3_igemm_bf16s<3, false, 2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
     else if (KC == 8 && h->precision == OAI_PREC_FP16X3) conv3_igemm_bf16s<2, true, 2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
     else conv3_igemm_f32<kF32Mrep, KC, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
-    OAI_CHECK_LAUNCH();
-    if (h->profile) {
-        OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used + 1], st));
-        hm->ev_used += 2;
-    }
-    return OAI_OK;
+    return launch_end(h, st);
 }
 
-// One conv layer = the main launch over the part of the output box that 8 x 16 (y, x) tiles cover exactly, plus up
-// to two thin remainder strips computed with tile shapes that fit them (trimmed boxes are e.g. 18 x 98 x 98).
-// how launch_conv3 covers a box: ny x nx main (8 x 16) tiles, plus an x strip of wr columns and a y strip of hr rows
-static void strip_plan(const oai_unet* h, const Box& box, int& ny, int& nx, int& hr, int& wr) {
-    const int ry = box.hi[1] - box.lo[1], rx = box.hi[2] - box.lo[2];
-    ny = ry / 8; nx = rx / 16;
-    hr = ry - 8 * ny; wr = rx - 16 * nx;
-    if (h->variant == 2 || ny == 0 || nx == 0) { ny = cdiv(ry, 8); nx = cdiv(rx, 16); hr = wr = 0; }   // no strips
-    if (hr > 4) { ++ny; hr = 0; }            // a tall remainder is cheaper as one more row of main tiles
-    if (wr > 8) { ++nx; wr = 0; }
+// One conv layer = the main launch over the part of the output box that 8 x `xunit` (y, x) tiles cover exactly, plus up to two thin remainder
+// strips computed with tile shapes that fit them (trimmed boxes are e.g. 18 x 98 x 98): the x strip = all y rows, the last wr columns; the y strip =
+// the last hr rows, main columns only.  A remainder of more than tall_y rows / tall_x columns is cheaper as one more row / column of main tiles.
+// hr == wr == 0: the main launch covers the whole box (also when the box is smaller than one main tile in y or x, or `no_strips`).
+struct Cover { Box main, xs, ys; int hr, wr; };
+static Cover cover_box(const Box& box, int xunit, int tall_y, int tall_x, bool no_strips) {
+    const int ry = box.hi[1] - box.lo[1], rx = box.hi[2] - box.lo[2], ny = ry / 8, nx = rx / xunit;
+    Cover c{box, box, box, ry - 8 * ny, rx - xunit * nx};
+    if (no_strips || ny == 0 || nx == 0) c.hr = c.wr = 0;
+    if (c.hr > tall_y) c.hr = 0;
+    if (c.wr > tall_x) c.wr = 0;
+    if (c.hr) c.main.hi[1] = box.lo[1] + 8 * ny;
+    if (c.wr) c.main.hi[2] = box.lo[2] + xunit * nx;
+    c.xs.lo[2] = c.main.hi[2];
+    c.ys.lo[1] = c.main.hi[1]; c.ys.hi[2] = c.main.hi[2];
+    return c;
 }
+// the cover of the direct kernels (launch_conv3): main tiles of 8 x 16
+static Cover direct_cover(const oai_unet* h, const Box& box) { return cover_box(box, 16, 4, 8, h->variant == 2); }
 
-// ec0 can be computed inside ec1's halo staging (conv3_igemm_sres<..., FIRST>) when ec1 runs as ONE launch of the main shape of the
-// default split-resident kernel and the channel counts are the reference's (1 -> 32 -> ...)
+// what fusing ec0 into ec1 asks of the configuration: the default split-resident kernel and the reference's channel counts (1 -> 32 -> ...)
+static bool first_fusion_ok(const oai_unet* h) {
+    return h->sres && h->fuse_first && h->variant == 0 && h->sres_mrep == 4 && !h->sres_ring && h->L[EC0].cout == 32 && h->L[EC1].c0 == 32;
+}
+// ec0 can be computed inside ec1's halo staging (conv3_igemm_sres<..., FIRST>) when ec1 runs as ONE launch of the main shape
 static bool first_fusable(const oai_unet* h, const Box& ec1_box) {
-    if (!h->sres || !h->fuse_first || h->variant != 0 || h->sres_mrep != 4 || h->sres_ring) return false;
-    if (h->L[EC0].cout != 32 || h->L[EC1].c0 != 32) return false;
-    int ny, nx, hr, wr;
-    strip_plan(h, ec1_box, ny, nx, hr, wr);
-    return hr == 0 && wr == 0;
+    if (!first_fusion_ok(h)) return false;
+    const Cover c = direct_cover(h, ec1_box);
+    return c.hr == 0 && c.wr == 0;
 }
 
 // shared encoder pass: where the copy-out of the volume-wide ec1 scatters its voxels (ConvArgs::sc_*)
@@ -724,7 +740,7 @@ static int fill_conv_args(const oai_unet* h, const Layer& L, const float* s0, co
     if (store_boxes && h->sres && h->opt_dead_stores) { a.store_boxes = store_boxes; a.store_grow = 1; }
     if (first) {                           // ec0 fused into this layer's staging (first_fusable)
         a.first_w = h->L[EC0].plain; a.first_scale = h->L[EC0].scale_f16; a.first_shift = h->L[EC0].shift_f16; a.first_src = *first;   // (sres => fp16x3)
-        a.first_census = h->opt_census ? h->census + 16 * EC0 : nullptr;
+        a.first_census = census_of(h, EC0);
     }
     if (sc) {
         a.sc_boxes = sc->boxes; a.sc_ntiles = sc->ntiles; a.sc_tile0 = sc->tile0;
@@ -734,15 +750,14 @@ static int fill_conv_args(const oai_unet* h, const Layer& L, const float* s0, co
     a.pool_out = pool_out;
     a.range_flag = h->range_flag;
 #ifdef OAI_DIAG
-    a.stamps = diag_stamps();
-    { static const int only = diag_env("OAI_STAMP_LAYER", -1); if (only >= 0 && &L != &h->L[only]) a.stamps = nullptr; }   // one layer's budget (EC1 = 1 ...)
+    a.stamps = layer_stamps(h, L);
 #endif
     a.src0 = s0; a.src1 = s1; a.C0 = L.c0; a.C1 = s1 ? L.c1 : 0;
     const bool f16 = h->precision == OAI_PREC_FP16X3;
     a.out = out; a.Cout = L.cout; a.scale = f16 ? L.scale_f16 : L.scale; a.shift = f16 ? L.shift_f16 : L.shift;
-    a.census = h->sres && h->opt_census ? h->census + 16 * (int)(&L - h->L) : nullptr;
+    a.census = h->sres ? census_of(h, layer_id(h, L)) : nullptr;
     a.wpanel = h->precision == OAI_PREC_F32 ? L.panel : L.panel_bf[h->precision == OAI_PREC_BF16X3 ? 0 : h->precision == OAI_PREC_BF16X6 ? 1 : 2];
-    a.wpanel16 = h->precision == OAI_PREC_FP16X3 && ((h->opt_m16_layers >> (int)(&L - h->L)) & 1) ? L.panel_m16 : nullptr;
+    a.wpanel16 = h->precision == OAI_PREC_FP16X3 && layer_bit(h, h->opt_m16_layers, L) ? L.panel_m16 : nullptr;
     a.D = dims[0]; a.H = dims[1]; a.W = dims[2];
     a.ncb = (L.cout + 63) / 64;
     a.relu = 1;
@@ -824,22 +839,8 @@ static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, cons
     a.ncb = a.Cout / (64 * ng);
     a.nbz = cdiv(box.hi[0] - box.lo[0], 4); a.nby = cdiv(box.hi[1] - box.lo[1], TY); a.nbx = cdiv(box.hi[2] - box.lo[2], 2 * NP);
     unsigned grid = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-    if (h->xcd_group > 0) {
-        a.nblocks = (int)grid; a.xcd_group = h->xcd_group;
-        const unsigned q = 8u * (unsigned)h->xcd_group;
-        grid = (grid + q - 1) / q * q;
-    }
-    oai_unet* hm = const_cast<oai_unet*>(h);
-    if (h->profile) {
-        if (hm->ev_used + 2 > hm->ev_pool.size()) {
-            hipEvent_t e0, e1;
-            OAI_CHECK_HIP(hipEventCreate(&e0));
-            OAI_CHECK_HIP(hipEventCreate(&e1));
-            hm->ev_pool.push_back(e0);
-            hm->ev_pool.push_back(e1);
-        }
-        OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used], st));
-    }
+    grid = xcd_deal(h, grid, a.nblocks, a.xcd_group);
+    if (int rc = launch_begin(h, st)) return rc;
     if (ng == 2 && (h->opt_wino & 16) && L.panel_wino16) {              // the taps on v_mfma_f32_16x16x32_f16 (higher clock at the power wall)
         a.wpanel = L.panel_wino16;
         conv3_wino_sres<2, TY, NP, 1, false, true><<<grid, 512, 0, st>>>(a, h->zero_rec);
@@ -862,12 +863,7 @@ static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, cons
         a.wpanel = L.panel_wino16;                                                     //  on the same tap pairs as the layer's other shapes: one summation order per layer)
         conv3_wino_sres<1, TY, NP, 2, false, true><<<grid, 512, 0, st>>>(a, h->zero_rec);
     } else conv3_wino_sres<1, TY, NP, 2><<<grid, 512, 0, st>>>(a, h->zero_rec);
-    OAI_CHECK_LAUNCH();
-    if (h->profile) {
-        OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used + 1], st));
-        hm->ev_used += 2;
-    }
-    return OAI_OK;
+    return launch_end(h, st);
 }
 
 // A plain layer (no fused ec0 / pool / head / scatter) of the default split-resident configuration through conv3_wino_sres: main blocks of
@@ -876,24 +872,12 @@ static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, cons
 // parity of its x only -- not on which launch or block computes it.
 static int launch_conv3_wino(const oai_unet* h, const Layer& L, const ConvArgs& a, Box box, int ntiles, hipStream_t st) {
     box.lo[2] &= ~1;
-    const int ry = box.hi[1] - box.lo[1], rx = box.hi[2] - box.lo[2];
-    int ny = ry / 8, nx = rx / 8, hr = ry - 8 * ny, wr = rx - 8 * nx;
-    if (ny == 0 || nx == 0) { ny = cdiv(ry, 8); nx = cdiv(rx, 8); hr = wr = 0; }
-    if (hr > 4) { ++ny; hr = 0; }
-    if (wr > 4) { ++nx; wr = 0; }
-    Box main = box, xs = box, ys = box;
-    main.hi[1] = hr ? box.lo[1] + 8 * ny : box.hi[1];
-    main.hi[2] = wr ? box.lo[2] + 8 * nx : box.hi[2];
-    if (int rc = launch_wino_shape<8, 4>(h, L, a, main, ntiles, st)) return rc;
-    if (wr) {                                 // x strip: all y rows, the last wr columns
-        xs.lo[2] = main.hi[2];
-        if (int rc = launch_wino_shape<16, 2>(h, L, a, xs, ntiles, st)) return rc;
-    }
-    if (hr) {                                 // y strip: the last hr rows, main columns only
-        ys.lo[1] = main.hi[1];
-        ys.hi[2] = main.hi[2];
-        if (int rc = launch_wino_shape<4, 8>(h, L, a, ys, ntiles, st)) return rc;
-    }
+    const Cover c = cover_box(box, 8, 4, 4, false);
+    if (int rc = launch_wino_shape<8, 4>(h, L, a, c.main, ntiles, st)) return rc;
+    if (c.wr)
+        if (int rc = launch_wino_shape<16, 2>(h, L, a, c.xs, ntiles, st)) return rc;
+    if (c.hr)
+        if (int rc = launch_wino_shape<4, 8>(h, L, a, c.ys, ntiles, st)) return rc;
     return OAI_OK;
 }
 
@@ -914,29 +898,10 @@ static int launch_wino_f32_shape(const oai_unet* h, const Layer& L, ConvArgs a, 
     a.ncb = (a.Cout + 63) / 64;
     a.nbz = cdiv(box.hi[0] - box.lo[0], 2); a.nby = cdiv(box.hi[1] - box.lo[1], TY); a.nbx = cdiv(box.hi[2] - box.lo[2], 2 * NP);
     unsigned grid = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-    if (h->xcd_group > 0) {                                // XCD-aware dealing of the logical block list (xcd_block_id), as the split-resident kernels
-        a.nblocks = (int)grid; a.xcd_group = h->xcd_group;
-        const unsigned q = 8u * (unsigned)h->xcd_group;
-        grid = (grid + q - 1) / q * q;
-    }
-    oai_unet* hm = const_cast<oai_unet*>(h);
-    if (h->profile) {
-        if (hm->ev_used + 2 > hm->ev_pool.size()) {
-            hipEvent_t e0, e1;
-            OAI_CHECK_HIP(hipEventCreate(&e0));
-            OAI_CHECK_HIP(hipEventCreate(&e1));
-            hm->ev_pool.push_back(e0);
-            hm->ev_pool.push_back(e1);
-        }
-        OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used], st));
-    }
+    grid = xcd_deal(h, grid, a.nblocks, a.xcd_group);         // (as the split-resident kernels)
+    if (int rc = launch_begin(h, st)) return rc;
     conv3_wino_f32<TY, NP><<<grid, 256, 0, st>>>(a, reinterpret_cast<const float*>(h->zero_rec));
-    OAI_CHECK_LAUNCH();
-    if (h->profile) {
-        OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used + 1], st));
-        hm->ev_used += 2;
-    }
-    return OAI_OK;
+    return launch_end(h, st);
 }
 
 // The exact-fp32 path's k3 layers through conv3_wino_f32: main blocks of 2 x 8 x 8, a y strip of 2 x 4 x 16 blocks for a remainder of <= 4 rows, an x strip
@@ -944,24 +909,12 @@ static int launch_wino_f32_shape(const oai_unet* h, const Layer& L, ConvArgs a, 
 // parity of its x only -- not on which launch or block computes it.  A fused MaxPool3d(2) rides in the main blocks (the host passes it for whole-tile boxes only).
 static int launch_conv3_wino_f32(const oai_unet* h, const Layer& L, const ConvArgs& a, Box box, int ntiles, hipStream_t st) {
     box.lo[2] &= ~1;
-    const int ry = box.hi[1] - box.lo[1], rx = box.hi[2] - box.lo[2];
-    int ny = ry / 8, nx = rx / 8, hr = ry - 8 * ny, wr = rx - 8 * nx;
-    if (ny == 0 || nx == 0 || a.pool_out) { ny = cdiv(ry, 8); nx = cdiv(rx, 8); hr = wr = 0; }
-    if (hr > 4) { ++ny; hr = 0; }
-    if (wr > 4) { ++nx; wr = 0; }
-    Box main = box, xs = box, ys = box;
-    main.hi[1] = hr ? box.lo[1] + 8 * ny : box.hi[1];
-    main.hi[2] = wr ? box.lo[2] + 8 * nx : box.hi[2];
-    if (int rc = launch_wino_f32_shape<8, 4>(h, L, a, main, ntiles, st)) return rc;
-    if (wr) {                                 // x strip: all y rows, the last wr columns
-        xs.lo[2] = main.hi[2];
-        if (int rc = launch_wino_f32_shape<16, 2>(h, L, a, xs, ntiles, st)) return rc;
-    }
-    if (hr) {                                 // y strip: the last hr rows, main columns only
-        ys.lo[1] = main.hi[1];
-        ys.hi[2] = main.hi[2];
-        if (int rc = launch_wino_f32_shape<4, 8>(h, L, a, ys, ntiles, st)) return rc;
-    }
+    const Cover c = cover_box(box, 8, 4, 4, a.pool_out != nullptr);
+    if (int rc = launch_wino_f32_shape<8, 4>(h, L, a, c.main, ntiles, st)) return rc;
+    if (c.wr)
+        if (int rc = launch_wino_f32_shape<16, 2>(h, L, a, c.xs, ntiles, st)) return rc;
+    if (c.hr)
+        if (int rc = launch_wino_f32_shape<4, 8>(h, L, a, c.ys, ntiles, st)) return rc;
     return OAI_OK;
 }
 
@@ -973,33 +926,21 @@ static int launch_conv3(const oai_unet* h, const Layer& L, const float* s0, cons
     if (int rc = fill_conv_args(h, L, s0, s1, out, dims, boxes, pool_out, head, first, store_boxes, sc, a)) return rc;
     if (h->variant == 1) return launch_conv3_shape<2, 16, 16, 2, 4, 1>(h, a, box, ntiles, st);
     if (h->precision == OAI_PREC_F32 && h->variant == 0 && h->opt_wino_f32 && L.panel_wino_f32 && a.Cout % 4 == 0 && !a.head_w && !a.first_w && !a.sc_boxes &&
-        (!a.pool_out || (wino_pool_box(box, dims) && dims[0] % 2 == 0)) && ((h->opt_wino_layers >> (int)(&L - h->L)) & 1))
+        (!a.pool_out || (wino_pool_box(box, dims) && dims[0] % 2 == 0)) && layer_bit(h, h->opt_wino_layers, L))
         return launch_conv3_wino_f32(h, L, a, box, ntiles, st);
     if (h->sres && h->opt_wino && L.panel_wino && h->sres_mrep == 4 && !h->sres_ring && !h->b_lds && !a.first_w && !a.head_w && !a.sc_boxes &&
-        (!a.pool_out || (a.Cout % 128 == 0 && a.relu && wino_pool_box(box, dims))) && a.Cout % 64 == 0 && (h->opt_wino & (a.Cout % 128 == 0 ? 1 : 2)) && (a.Cout % 128 == 0 || (a.C0 + 15) / 16 + (a.C1 + 15) / 16 >= 8) && ((h->opt_wino_layers >> (int)(&L - h->L)) & 1) && (size_t)dims[0] * dims[1] * dims[2] < (1u << 24))
+        (!a.pool_out || (a.Cout % 128 == 0 && a.relu && wino_pool_box(box, dims))) && a.Cout % 64 == 0 && (h->opt_wino & (a.Cout % 128 == 0 ? 1 : 2)) && (a.Cout % 128 == 0 || (a.C0 + 15) / 16 + (a.C1 + 15) / 16 >= 8) && layer_bit(h, h->opt_wino_layers, L) && (size_t)dims[0] * dims[1] * dims[2] < (1u << 24))
         return launch_conv3_wino(h, L, a, box, ntiles, st);
-    int ny, nx, hr, wr;
-    strip_plan(h, box, ny, nx, hr, wr);
-    Box main = box, xs = box, ys = box;
-    main.hi[1] = hr ? box.lo[1] + 8 * ny : box.hi[1];
-    main.hi[2] = wr ? box.lo[2] + 16 * nx : box.hi[2];
-    int rc = launch_conv3_shape<4, 8, 16, 2, 4, 1>(h, a, main, ntiles, st);
-    if (rc) return rc;
-    if (wr) {                                 // x strip: all y rows, the last wr columns
-        xs.lo[2] = main.hi[2];
-        if (wr <= 2) rc = launch_conv3_shape<4, 8, 2, 16, 4, 1>(h, a, xs, ntiles, st);
-        else if (wr <= 4) rc = launch_conv3_shape<4, 8, 4, 8, 4, 1>(h, a, xs, ntiles, st);
-        else rc = launch_conv3_shape<4, 8, 8, 4, 4, 1>(h, a, xs, ntiles, st);
+    const Cover c = direct_cover(h, box);
+    if (int rc = launch_conv3_shape<4, 8, 16, 2, 4, 1>(h, a, c.main, ntiles, st)) return rc;
+    if (c.wr) {
+        const int rc = c.wr <= 2 ? launch_conv3_shape<4, 8, 2, 16, 4, 1>(h, a, c.xs, ntiles, st)
+                     : c.wr <= 4 ? launch_conv3_shape<4, 8, 4, 8, 4, 1>(h, a, c.xs, ntiles, st)
+                                 : launch_conv3_shape<4, 8, 8, 4, 4, 1>(h, a, c.xs, ntiles, st);
         if (rc) return rc;
     }
-    if (hr) {                                 // y strip: the last hr rows, main columns only
-        ys.lo[1] = main.hi[1];
-        ys.hi[2] = main.hi[2];
-        if (hr <= 2) rc = launch_conv3_shape<4, 8, 16, 2, 1, 4>(h, a, ys, ntiles, st);
-        else rc = launch_conv3_shape<4, 8, 16, 2, 2, 2>(h, a, ys, ntiles, st);
-        if (rc) return rc;
-    }
-    return OAI_OK;
+    if (!c.hr) return OAI_OK;
+    return c.hr <= 2 ? launch_conv3_shape<4, 8, 16, 2, 1, 4>(h, a, c.ys, ntiles, st) : launch_conv3_shape<4, 8, 16, 2, 2, 2>(h, a, c.ys, ntiles, st);
 }
 
 static int launch_up(const oai_unet* h, const Layer& L, const float* src, float* out, const int in_dims[3], const Box& out_need,
@@ -1009,15 +950,14 @@ static int launch_up(const oai_unet* h, const Layer& L, const float* src, float*
     a.range_flag = h->range_flag;
     a.zero = h->zero_rec;
 #ifdef OAI_DIAG
-    a.stamps = diag_stamps();
-    { static const int only = diag_env("OAI_STAMP_LAYER", -1); if (only >= 0 && &L != &h->L[only]) a.stamps = nullptr; }   // DC9 = 8, DC6 = 11, DC3 = 14
+    a.stamps = layer_stamps(h, L);
 #endif
     const bool split = h->precision == OAI_PREC_FP16X3 && L.panel_bf[2];
     a.src = src; a.Cin = L.cin; a.out = out; a.Cout = L.cout;
     a.wpanel = split ? L.panel_bf[2] : L.panel;
     a.scale = split ? L.scale_f16 : L.scale;
     a.shift = split ? L.shift_f16 : L.shift;
-    a.census = h->sres && h->opt_census ? h->census + 16 * (int)(&L - h->L) : nullptr;
+    a.census = h->sres ? census_of(h, layer_id(h, L)) : nullptr;
     a.D = in_dims[0]; a.H = in_dims[1]; a.W = in_dims[2];
     for (int i = 0; i < 3; ++i) { a.lo[i] = out_need.lo[i] / 2; a.hi[i] = (out_need.hi[i] + 1) / 2; }
     const int nvox = (a.hi[0] - a.lo[0]) * (a.hi[1] - a.lo[1]) * (a.hi[2] - a.lo[2]);
@@ -1033,12 +973,7 @@ static int launch_up(const oai_unet* h, const Layer& L, const float* src, float*
             a.nbw = a.nnb;
             while (a.nbw > 1 && (size_t)ntiles * a.nmb * cdiv(a.nnb, a.nbw) < 8192) a.nbw = (a.nbw + 1) / 2;
         }
-        unsigned grid = (unsigned)((size_t)ntiles * a.nmb * cdiv(a.nnb, a.nbw));
-        if (h->xcd_group > 0) {                               // same dealing as the conv kernel's (launch_conv3_shape)
-            a.nblocks = (int)grid; a.xcd_group = h->xcd_group;
-            const unsigned q = 8u * (unsigned)h->xcd_group;
-            grid = (grid + q - 1) / q * q;
-        }
+        const unsigned grid = xcd_deal(h, (unsigned)((size_t)ntiles * a.nmb * cdiv(a.nnb, a.nbw)), a.nblocks, a.xcd_group);   // same dealing as the conv kernels'
         upconv2_igemm_sres<<<grid, 256, 0, st>>>(a);
     }
     else if (split) upconv2_igemm<true><<<(unsigned)((size_t)ntiles * a.nmb * a.nnb), 256, 0, st>>>(a);
@@ -1060,17 +995,13 @@ static int launch_pool(const oai_unet* h, const float* in, float* out, const int
         const size_t Do = dims[0] / 2, Ho = dims[1] / 2, Wo = dims[2] / 2;
         const size_t faces = Do * Ho * Wo - (Do - 2) * (Ho - 2) * (Wo - 2) - (shell_only == 2 ? 2 * Ho * Wo : 0);
         const size_t total = (size_t)ntiles * (shell_only ? faces : Do * Ho * Wo) * nch * 4;
-        size_t blocks = (total + 255) / 256;
-        if (blocks > 256 * 32) blocks = 256 * 32;
-        maxpool2_sres_kernel<<<(unsigned)blocks, 256, 0, st>>>(reinterpret_cast<const unsigned char*>(in), reinterpret_cast<unsigned char*>(out),
+        maxpool2_sres_kernel<<<capped_blocks(total, 256 * 32), 256, 0, st>>>(reinterpret_cast<const unsigned char*>(in), reinterpret_cast<unsigned char*>(out),
                                                                 dims[0], dims[1], dims[2], nch, total, shell_only);
         OAI_CHECK_LAUNCH();
         return OAI_OK;
     }
     const size_t total4 = (size_t)ntiles * (dims[0] / 2) * (dims[1] / 2) * (dims[2] / 2) * (C / 4);
-    size_t blocks = (total4 + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    maxpool2_kernel<<<(unsigned)blocks, 256, 0, st>>>(in, out, dims[0], dims[1], dims[2], C, total4);
+    maxpool2_kernel<<<capped_blocks(total4, 256 * 32), 256, 0, st>>>(in, out, dims[0], dims[1], dims[2], C, total4);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
@@ -1094,12 +1025,10 @@ struct SharedEnc {
 // `table` (device, may be null) = per-tile boxes [layer][table_tiles][6] of the whole call; this batch starts at tile
 // `t0` of it.  For up-convs the table row holds the INPUT box (the halved output box).
 static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[18], int out_mode,
-                     float* blocks_out, char* ws, const Plan& plan, hipStream_t st,
+                     float* blocks_out, float* const buf[B_COUNT], hipStream_t st,
                      const int* table = nullptr, int table_tiles = 0, int t0 = 0, const SharedEnc* se = nullptr) {
     auto tb = [&](int layer) -> const int* { return table ? table + ((size_t)layer * table_tiles + t0) * 6 : nullptr; };
     const Layer* L = h->L;
-    float* buf[B_COUNT];
-    for (int i = 0; i < B_COUNT; ++i) buf[i] = reinterpret_cast<float*>(ws + plan.off[i]);
     int d[4][3];
     for (int l = 0; l < 4; ++l) { d[l][0] = src.td >> l; d[l][1] = src.th >> l; d[l][2] = src.tw >> l; }
     const size_t v0 = (size_t)src.td * src.th * src.tw;
@@ -1155,9 +1084,7 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
         const int nch1 = (L[EC1].cout + 15) / 16;
         {
             const size_t total = (size_t)n * (d[1][0] * d[1][1] * d[1][2]) * nch1 * 4;
-            size_t blocks = (total + 255) / 256;
-            if (blocks > 256 * 64) blocks = 256 * 64;
-            pooled_gather_kernel<<<(unsigned)blocks, 256, 0, st>>>(reinterpret_cast<const unsigned char*>(se->SP0), reinterpret_cast<unsigned char*>(buf[B_P0]), src,
+            pooled_gather_kernel<<<capped_blocks(total, 256 * 64), 256, 0, st>>>(reinterpret_cast<const unsigned char*>(se->SP0), reinterpret_cast<unsigned char*>(buf[B_P0]), src,
                                                                    d[1][0], d[1][1], d[1][2], se->PD / 2, se->PH / 2, se->PW / 2, nch1, total);
             OAI_CHECK_LAUNCH();
         }
@@ -1165,7 +1092,7 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
             const size_t pairs = (size_t)6 * d[0][1] * (d[0][2] / 2) + (size_t)(d[0][0] - 6) * 6 * (d[0][2] / 2) + (size_t)(d[0][0] - 6) * (d[0][1] - 6) * 4;
             dim3 grid(std::min<unsigned>(cdiv(pairs, 256), (unsigned)h->opt_first_blocks), n);
             conv3_first_sres_kernel<32><<<grid, 256, 0, st>>>(src, L[EC0].plain, L[EC0].scale_f16, L[EC0].shift_f16, reinterpret_cast<unsigned char*>(buf[B_E0]), 1,
-                                                              h->range_flag, h->opt_census ? h->census + 16 * EC0 : nullptr, 3);
+                                                              h->range_flag, census_of(h, EC0), 3);
             OAI_CHECK_LAUNCH();
         }
         const int td = d[0][0], th = d[0][1], tw = d[0][2];
@@ -1192,7 +1119,7 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
         const bool f16 = h->precision == OAI_PREC_FP16X3;
         const float* sc0 = f16 ? L[EC0].scale_f16 : L[EC0].scale;
         const float* sh0 = f16 ? L[EC0].shift_f16 : L[EC0].shift;
-        unsigned* cen0 = h->opt_census ? h->census + 16 * EC0 : nullptr;
+        unsigned* cen0 = census_of(h, EC0);
         if (h->sres && c == 32) conv3_first_sres_kernel<32><<<grid, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, e0s, 1, h->range_flag, cen0, 0);
         else if (h->sres && c == 16) conv3_first_sres_kernel<16><<<grid, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, e0s, 1, h->range_flag, cen0, 0);
         else if (h->sres && c == 8) conv3_first_sres_kernel<8><<<grid, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, e0s, 1, h->range_flag, cen0, 0);
@@ -1323,6 +1250,33 @@ using namespace oai;
 static int stitch_impl(const float* blocks, int ncls, int D, int H, int W, const int tile[3], const int overlap[3],
                        const int crop[3], float* maps, void* stream, const StitchRanges& rg);
 
+// one zero-filled device block of the handle (freed by oai_unet_destroy)
+template <typename T>
+static int alloc_zeroed(oai_unet* h, size_t bytes, T** ptr) {
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) return set_error(OAI_ERR_HIP, "oai_unet_create: hipMalloc failed");
+    h->allocs.push_back(d);
+    (void)hipMemset(d, 0, bytes);
+    *ptr = reinterpret_cast<T*>(d);
+    return OAI_OK;
+}
+
+// k3 layers that run the implicit-GEMM conv kernels (ec0 and the 1x1x1 head have kernels of their own)
+static inline bool is_conv3_igemm(int k) { return k >= 1 && k < 17 && (kKind[k] == 0 || kKind[k] == 1); }
+
+static double tile_flops(const oai_unet* h, int td, int th, int tw, const int overlap[3], int trimmed, bool conv3_only) {
+    if (!h) return 0.0;
+    const int tile[3] = {td, th, tw};
+    int lo[3], hi[3];
+    for (int i = 0; i < 3; ++i) { lo[i] = overlap ? overlap[i] : 0; hi[i] = tile[i] - lo[i]; }
+    Box need[18];
+    plan_regions(tile, lo, hi, trimmed != 0, need);
+    double f = 0;
+    for (int k = 0; k < 18; ++k)
+        if (!conv3_only || is_conv3_igemm(k)) f += layer_flops(h, k, need[k]);
+    return f;
+}
+
 extern "C" {
 
 int oai_unet_create(const oai_layer_params layers[OAI_UNET_NUM_LAYERS], float bn_eps, oai_unet** out) {
@@ -1348,39 +1302,21 @@ int oai_unet_create(const oai_layer_params layers[OAI_UNET_NUM_LAYERS], float bn
     }
 
     oai_unet* h = new oai_unet();
+    int rc = alloc_zeroed(h, 256, &h->range_flag);
+    if (!rc) rc = alloc_zeroed(h, 256, &h->zero_rec);
+    if (!rc) rc = alloc_zeroed(h, (288 + 8 * kPsMaxTiles) * sizeof(int), &h->ps_plan);
+    if (!rc) rc = alloc_zeroed(h, 18 * 16 * sizeof(unsigned) + 256, &h->census);      // the census, then the scratch word of oai_unet_range_flag
+    if (rc) { oai_unet_destroy(h); return rc; }
+    h->eval_out = reinterpret_cast<int*>(h->census + 18 * 16);
     {
-        void* f = nullptr;
-        if (hipMalloc(&f, 256) != hipSuccess) { delete h; return set_error(OAI_ERR_HIP, "oai_unet_create: hipMalloc failed"); }
-        h->allocs.push_back(f);
-        h->range_flag = reinterpret_cast<int*>(f);
-        (void)hipMemset(f, 0, 256);
-        void* z = nullptr;
-        if (hipMalloc(&z, 256) != hipSuccess) { delete h; return set_error(OAI_ERR_HIP, "oai_unet_create: hipMalloc failed"); }
-        h->allocs.push_back(z);
-        h->zero_rec = reinterpret_cast<unsigned char*>(z);
-        (void)hipMemset(z, 0, 256);
-        void* pp = nullptr;
-        if (hipMalloc(&pp, (288 + 8 * kPsMaxTiles) * sizeof(int)) != hipSuccess) { delete h; return set_error(OAI_ERR_HIP, "oai_unet_create: hipMalloc failed"); }
-        h->allocs.push_back(pp);
-        h->ps_plan = reinterpret_cast<int*>(pp);
-        (void)hipMemset(pp, 0, (288 + 8 * kPsMaxTiles) * sizeof(int));
-        {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->n_cus = prop.multiProcessorCount;
-        }
-        void* c = nullptr;
-        if (hipMalloc(&c, 18 * 16 * sizeof(unsigned) + 256) != hipSuccess) { delete h; return set_error(OAI_ERR_HIP, "oai_unet_create: hipMalloc failed"); }
-        h->allocs.push_back(c);
-        h->census = reinterpret_cast<unsigned*>(c);
-        h->eval_out = reinterpret_cast<int*>(reinterpret_cast<char*>(c) + 18 * 16 * sizeof(unsigned));
-        (void)hipMemset(c, 0, 18 * 16 * sizeof(unsigned) + 256);
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->n_cus = prop.multiProcessorCount;
     }
     h->variant = diag_env("OAI_CONV_VARIANT", 0);
     if (h->variant < 0 || h->variant > 2) h->variant = 0;
     h->n_classes = layers[DC0].cout;
     const int KC = conv_kc(h->variant);
-    int rc = OAI_OK;
     for (int k = 0; k < 18 && rc == OAI_OK; ++k) {
         const oai_layer_params& p = layers[k];
         Layer& L = h->L[k];
@@ -1446,15 +1382,56 @@ int oai_unet_set_precision(oai_unet* h, int mode) {
     return OAI_OK;
 }
 
+// The options that are one int in a range, one row each: name, field, lo, hi, the message for a value outside [lo, hi] -- and what the option does.
+struct IntOption { const char* name; int oai_unet::*field; int lo, hi; const char* message; };
+static const IntOption kIntOptions[] = {
+    // weight fragments through a three-slot LDS ring shared by the workgroup
+    {"b_lds", &oai_unet::b_lds, 0, 1, "oai_unet_set_option: b_lds must be 0 or 1"},
+    // ec0 -> ec1 computed ONCE over the reflect-padded volume + a 2-voxel shell per tile (oai_segment_tiles)
+    {"shared_enc", &oai_unet::opt_shared, 0, 1, "oai_unet_set_option: shared_enc must be 0 or 1"},
+    // layers with Cout % 128 == 0 run conv3_igemm_sres2 (one 8-wave workgroup per CU, double-buffered halo)
+    {"wide", &oai_unet::opt_wide, 0, 2, "oai_unet_set_option: wide must be 0, 1 or 2 (2 = also for launches of fewer than 1024 workgroups)"},
+    // bit k = layer k may take the Winograd kernel (A/B of single layers)
+    {"winograd_layers", &oai_unet::opt_wino_layers, 0, 0x3FFFF, "oai_unet_set_option: winograd_layers is a mask over the 18 layers"},
+    // the direct split-resident kernel (conv3_igemm_sres: ec1 + fused ec0, ec2, dc1 + fused head, ...) on v_mfma_f32_16x16x32_f16 tap pairs (round 5; another
+    // summation order; default 1) for every layer that can never take the bit-identical 128-cout form conv3_igemm_sres2 -- i.e. Cout % 128 != 0 -- so that a
+    // layer runs ONE order whatever shapes cover it and option "wide" stays bit-preserving
+    {"m16", &oai_unet::opt_m16, 0, 1, "oai_unet_set_option: m16 must be 0 or 1"},
+    // bit 0 = the specialised 64-cout Winograd form (dc2) with persistent workgroups, the staging waves one block ahead (conv3_wino_sres<..., PS>; bit-identical maps)
+    {"persistent", &oai_unet::opt_persist, 0, 1, "oai_unet_set_option: persistent is a mask (bit 0)"},
+    // bit k = layer k may take the tap-pair form (A/B of single layers)
+    {"m16_layers", &oai_unet::opt_m16_layers, 0, 0x3FFFF, "oai_unet_set_option: m16_layers is a mask over the 18 layers"},
+    // 1 = the encoder does not write the part of a skip tensor that the decoder never reads
+    {"dead_stores", &oai_unet::opt_dead_stores, 0, 1, "oai_unet_set_option: dead_stores must be 0 or 1"},
+    // NOT bit-preserving: the plain k3 layers of the exact-fp32 path run conv3_wino_f32 (x axis in Winograd F(2,3) form: 2/3 of the fp32 MFMAs)
+    {"winograd_f32", &oai_unet::opt_wino_f32, 0, 1, "oai_unet_set_option: winograd_f32 must be 0 or 1"},
+    // bit-preserving: workgroups per tile of the ec0 kernel conv3_first_sres_kernel (each walks the tile's voxel pairs with a grid stride, the next pair's
+    // gathers under the current pair's FMAs)
+    {"first_blocks", &oai_unet::opt_first_blocks, 1, 4096, "oai_unet_set_option: first_blocks must be in [1, 4096]"},
+    // bit-preserving: column blocks per workgroup of the k2s2 up-conv kernel: 0 = as many as keep >= 16 workgroups per slot, 1 = one (rounds 1-5), n = at most n
+    {"up_nbw", &oai_unet::opt_up_nbw, 0, 64, "oai_unet_set_option: up_nbw must be in [0, 64]"},
+    // ec0 computed inside ec1's halo staging when ec1 is one main-shape launch
+    {"fuse_first", &oai_unet::fuse_first, 0, 1, "oai_unet_set_option: fuse_first must be 0 or 1"},
+    // logical blocks per XCD deal; 0 = plain launch order
+    {"xcd_group", &oai_unet::xcd_group, 0, 4096, "oai_unet_set_option: xcd_group must be in [0, 4096]"},
+};
+
 // Result-preserving tuning options of the fp16x3 path (every combination is parity-tested: tests/test_unet_gpu.py).  An explicit
 // call on the handle -- the production library does not read the environment.
 int oai_unet_set_option(oai_unet* h, const char* name, int value) {
     OAI_CHECK_ARG(h && name, "oai_unet_set_option: null pointer");
+    for (const IntOption& o : kIntOptions)
+        if (!strcmp(name, o.name)) {
+            OAI_CHECK_ARG(value >= o.lo && value <= o.hi, "%s", o.message);
+            h->*o.field = value;
+            return OAI_OK;
+        }
+    // the options with side effects or cross-checks
     if (!strcmp(name, "sres")) {                       // 1: activations resident as fp16 term pairs (default); 0: fp32-resident split kernels
         OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: sres must be 0 or 1");
         h->opt_sres = value != 0;
         h->sres = h->precision == OAI_PREC_FP16X3 && h->opt_sres;
-    } else if (!strcmp(name, "sres_mrep")) {           // z slices per block of the split-resident conv kernel
+    } else if (!strcmp(name, "sres_mrep")) {           // z slices per block of the split-resident conv kernel (2 runs three workgroups per CU: -2 % on 32 border tiles, +0.5 % on the whole volume)
         OAI_CHECK_ARG(value == 2 || value == 4, "oai_unet_set_option: sres_mrep must be 2 or 4");
         OAI_CHECK_ARG(!(h->sres_ring && value != 2), "oai_unet_set_option: the plane ring needs sres_mrep 2");
         h->sres_mrep = value;
@@ -1462,18 +1439,12 @@ int oai_unet_set_option(oai_unet* h, const char* name, int value) {
         OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: sres_ring must be 0 or 1");
         h->sres_ring = value != 0;
         if (h->sres_ring) h->sres_mrep = 2;
-    } else if (!strcmp(name, "b_lds")) {
-        OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: b_lds must be 0 or 1");
-        h->b_lds = value;
-    } else if (!strcmp(name, "shared_enc")) {
-        OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: shared_enc must be 0 or 1");
-        h->opt_shared = value;
-    } else if (!strcmp(name, "wide")) {
-        OAI_CHECK_ARG(value >= 0 && value <= 2, "oai_unet_set_option: wide must be 0, 1 or 2 (2 = also for launches of fewer than 1024 workgroups)");
-        h->opt_wide = value;
-    } else if (!strcmp(name, "winograd")) {            // bit 0: layers with Cout % 128 == 0 (two cout groups per workgroup), bit 1: one block of 64 couts and >= 8 chunks
-                                                       // (specialised waves); A/B only: bit 2 = the slice-split form instead, bit 3 = the specialised form for every layer;
-                                                       // bit 4 / bit 5: the two-group / the specialised form's taps on v_mfma_f32_16x16x32_f16 (tap pairs; another summation order)
+    } else if (!strcmp(name, "winograd")) {
+        // plain k3 layers with Cout % 64 == 0 run conv3_wino_sres (x axis in Winograd F(2,3) form: 2/3 of the MFMAs).  bit 0: layers with Cout % 128 == 0 (two cout
+        // groups per workgroup), bit 1: one block of 64 couts and >= 8 chunks (specialised waves); A/B only: bit 2 = the slice-split form instead, bit 3 = the
+        // specialised form for every layer; bit 4 (round 4): the taps of the two-group form on v_mfma_f32_16x16x32_f16 (tap pairs: another summation order; same
+        // cycles per FLOP, +14 % clock at the power wall); bit 5: the same for the 64-cout layer (dc2) -- ALL its launch shapes (specialised main blocks and x strip,
+        // slice-split y strip: wino_m16_64), so a voxel's bits do not depend on the shape that covers it; measured within noise of bit 4 alone (-0.2 %), not the default
         OAI_CHECK_ARG(value >= 0 && value <= 63, "oai_unet_set_option: winograd must be in [0, 63]");
         if (value && !h->opt_wino && h->L[EC0].scale_f16) {
             OAI_CHECK_HIP(hipDeviceSynchronize());
@@ -1482,46 +1453,16 @@ int oai_unet_set_option(oai_unet* h, const char* name, int value) {
                     if (int rc = pack_wino_layer(h, k)) return rc;
         }
         h->opt_wino = value;
-    } else if (!strcmp(name, "winograd_layers")) {
-        OAI_CHECK_ARG(value >= 0 && value <= 0x3FFFF, "oai_unet_set_option: winograd_layers is a mask over the 18 layers");
-        h->opt_wino_layers = value;
-    } else if (!strcmp(name, "m16")) {                 // the direct kernel's taps on v_mfma_f32_16x16x32_f16 tap pairs (another summation order; default 1)
-        OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: m16 must be 0 or 1");
-        h->opt_m16 = value;
-    } else if (!strcmp(name, "persistent")) {          // persistent workgroups with the staging one block ahead (bit 0: the specialised 64-cout Winograd form); bit-identical maps
-        OAI_CHECK_ARG(value >= 0 && value <= 1, "oai_unet_set_option: persistent is a mask (bit 0)");
-        h->opt_persist = value;
-    } else if (!strcmp(name, "m16_layers")) {
-        OAI_CHECK_ARG(value >= 0 && value <= 0x3FFFF, "oai_unet_set_option: m16_layers is a mask over the 18 layers");
-        h->opt_m16_layers = value;
-    } else if (!strcmp(name, "dead_stores")) {
-        OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: dead_stores must be 0 or 1");
-        h->opt_dead_stores = value;
-    } else if (!strcmp(name, "census")) {
+    } else if (!strcmp(name, "census")) {              // 0 = the kernels do not record the per-layer maxima (A/B timing of the bookkeeping; no LOW flag)
         OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: census must be 0 or 1");
         // without the census there is no LOW bit in the range flag and nothing to calibrate from: allowed on a calibrated handle only
         // (A/B timing of the bookkeeping), so that the subnormal low-term loss cannot come back silently
         OAI_CHECK_ARG(value == 1 || h->calibrated, "oai_unet_set_option: census 0 needs a calibrated handle (activation exponents set)");
         h->opt_census = value;
-    } else if (!strcmp(name, "winograd_f32")) {        // NOT bit-preserving: the exact-fp32 path's plain k3 layers in Winograd F(2,3) form along x
-        OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: winograd_f32 must be 0 or 1");
-        h->opt_wino_f32 = value;
-    } else if (!strcmp(name, "first_blocks")) {        // bit-preserving: workgroups per tile of the ec0 kernel (grid stride over the tile's voxel pairs)
-        OAI_CHECK_ARG(value >= 1 && value <= 4096, "oai_unet_set_option: first_blocks must be in [1, 4096]");
-        h->opt_first_blocks = value;
-    } else if (!strcmp(name, "up_nbw")) {              // bit-preserving: column blocks a workgroup of the k2s2 up-conv walks (0 = automatic)
-        OAI_CHECK_ARG(value >= 0 && value <= 64, "oai_unet_set_option: up_nbw must be in [0, 64]");
-        h->opt_up_nbw = value;
     } else if (!strcmp(name, "calibrated")) {          // only clearing: setting goes through oai_unet_set_act_exponents / a settled oai_unet_calibrate_step
         OAI_CHECK_ARG(value == 0, "oai_unet_set_option: calibrated can only be cleared (0)");
         OAI_CHECK_ARG(h->opt_census == 1, "oai_unet_set_option: an uncalibrated handle needs the census (option census is 0)");
         h->calibrated = false;
-    } else if (!strcmp(name, "fuse_first")) {
-        OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: fuse_first must be 0 or 1");
-        h->fuse_first = value;
-    } else if (!strcmp(name, "xcd_group")) {           // logical blocks per XCD deal; 0 = plain launch order
-        OAI_CHECK_ARG(value >= 0 && value <= 4096, "oai_unet_set_option: xcd_group must be in [0, 4096]");
-        h->xcd_group = value;
     } else {
         return set_error(OAI_ERR_ARG, "oai_unet_set_option: unknown option '%s'", name);
     }
@@ -1656,16 +1597,7 @@ int oai_unet_profile_read(oai_unet* h, double* conv3_ms, long long* conv3_launch
 }
 
 double oai_unet_tile_flops_conv3(const oai_unet* h, int td, int th, int tw, const int overlap[3], int trimmed) {
-    if (!h) return 0.0;
-    const int tile[3] = {td, th, tw};
-    int lo[3], hi[3];
-    for (int i = 0; i < 3; ++i) { lo[i] = overlap ? overlap[i] : 0; hi[i] = tile[i] - lo[i]; }
-    Box need[18];
-    plan_regions(tile, lo, hi, trimmed != 0, need);
-    double f = 0;
-    for (int k = 1; k < 17; ++k)
-        if (kKind[k] == 0 || kKind[k] == 1) f += layer_flops(h, k, need[k]);
-    return f;
+    return tile_flops(h, td, th, tw, overlap, trimmed, true);
 }
 
 void oai_unet_destroy(oai_unet* h) {
@@ -1677,19 +1609,11 @@ void oai_unet_destroy(oai_unet* h) {
 
 size_t oai_unet_workspace_bytes(const oai_unet* h, int td, int th, int tw, int batch) {
     if (!h || td <= 0 || th <= 0 || tw <= 0 || batch <= 0) return 0;
-    return plan_workspace(h, td, th, tw, batch).total;
+    return workspace_bytes(h, td, th, tw, batch);
 }
 
 double oai_unet_tile_flops(const oai_unet* h, int td, int th, int tw, const int overlap[3], int trimmed) {
-    if (!h) return 0.0;
-    const int tile[3] = {td, th, tw};
-    int lo[3], hi[3];
-    for (int i = 0; i < 3; ++i) { lo[i] = overlap ? overlap[i] : 0; hi[i] = tile[i] - lo[i]; }
-    Box need[18];
-    plan_regions(tile, lo, hi, trimmed != 0, need);
-    double f = 0;
-    for (int k = 0; k < 18; ++k) f += layer_flops(h, k, need[k]);
-    return f;
+    return tile_flops(h, td, th, tw, overlap, trimmed, false);
 }
 
 static int check_tile(int td, int th, int tw) {
@@ -1705,10 +1629,12 @@ int oai_unet_forward_tiles(oai_unet* h, const float* tiles, float* logits, int B
     if (int rc = check_tile(td, th, tw)) return rc;
     // as many tiles per pass as the workspace holds
     int batch = B;
-    while (batch > 1 && plan_workspace(h, td, th, tw, batch).total > ws_bytes) --batch;
-    const Plan plan = plan_workspace(h, td, th, tw, batch);
-    if (plan.total > ws_bytes)
-        return set_error(OAI_ERR_WORKSPACE, "oai_unet_forward_tiles: workspace %zu B < %zu B needed for one tile", ws_bytes, plan.total);
+    while (batch > 1 && workspace_bytes(h, td, th, tw, batch) > ws_bytes) --batch;
+    float* buf[B_COUNT];
+    int* table;
+    const size_t need_bytes = carve_workspace(h, td, th, tw, batch, ws, buf, table);
+    if (need_bytes > ws_bytes)
+        return set_error(OAI_ERR_WORKSPACE, "oai_unet_forward_tiles: workspace %zu B < %zu B needed for one tile", ws_bytes, need_bytes);
     const int tile[3] = {td, th, tw};
     const int lo[3] = {0, 0, 0};
     Box need[18];
@@ -1720,7 +1646,7 @@ int oai_unet_forward_tiles(oai_unet* h, const float* tiles, float* logits, int B
         const int n = B - s < batch ? B - s : batch;
         src.tiles = tiles + (size_t)s * v0;
         src.tile_begin = 0;
-        if (int rc = run_batch(h, src, n, need, 2, logits + (size_t)s * h->n_classes * v0, (char*)ws, plan, (hipStream_t)stream)) return rc;
+        if (int rc = run_batch(h, src, n, need, 2, logits + (size_t)s * h->n_classes * v0, buf, (hipStream_t)stream)) return rc;
     }
     return OAI_OK;
 }
@@ -1800,8 +1726,7 @@ static SegParams seg_params(int D, int H, int W, const int tile[3], const int ov
 
 // bytes of the two volume-wide tensors of the shared encoder pass, or 0 when its conditions do not hold for this geometry
 static size_t shared_enc_bytes(const oai_unet* h, const int tile[3], const int overlap[3], const SegGeom& g, int P[3]) {
-    if (!h->sres || !h->opt_shared || !h->fuse_first || h->variant != 0 || h->sres_mrep != 4 || h->sres_ring || h->b_lds) return 0;
-    if (h->L[EC0].cout != 32 || h->L[EC1].c0 != 32 || h->L[EC1].cout % 16 != 0) return 0;
+    if (!first_fusion_ok(h) || !h->opt_shared || h->b_lds || h->L[EC1].cout % 16 != 0) return 0;
     const int blk[3] = {4, 8, 16};                                         // the main block shape must tile the padded volume and the tile exactly
     for (int i = 0; i < 3; ++i) {
         P[i] = g.eff[i] * g.grid[i] + 2 * overlap[i];
@@ -1820,7 +1745,7 @@ size_t oai_segment_workspace_bytes(const oai_unet* h, int D, int H, int W, const
     SegGeom g;
     if (seg_geometry(D, H, W, tile, overlap, g)) return 0;
     int P[3];
-    return plan_workspace(h, tile[0], tile[1], tile[2], batch).total + shared_enc_bytes(h, tile, overlap, g, P);
+    return workspace_bytes(h, tile[0], tile[1], tile[2], batch) + shared_enc_bytes(h, tile, overlap, g, P);
 }
 
 int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const int tile[3], const int overlap[3],
@@ -1836,9 +1761,11 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
                   "oai_segment_tiles: tile range [%d,%d) outside [0,%d)", tile_begin, tile_end, g.ntiles);
     OAI_CHECK_ARG(batch > 0, "oai_segment_tiles: batch must be > 0");
     if (crop) for (int i = 0; i < 3; ++i) OAI_CHECK_ARG(crop[i] >= 0, "oai_segment_tiles: negative crop");
-    const Plan plan = plan_workspace(h, tile[0], tile[1], tile[2], batch);
-    if (plan.total > ws_bytes)
-        return set_error(OAI_ERR_WORKSPACE, "oai_segment_tiles: workspace %zu B < %zu B needed for batch %d", ws_bytes, plan.total, batch);
+    float* buf[B_COUNT];
+    int* table_dev;
+    const size_t need_bytes = carve_workspace(h, tile[0], tile[1], tile[2], batch, ws, buf, table_dev);
+    if (need_bytes > ws_bytes)
+        return set_error(OAI_ERR_WORKSPACE, "oai_segment_tiles: workspace %zu B < %zu B needed for batch %d", ws_bytes, need_bytes, batch);
     const bool trimmed = diag_env("OAI_NO_TRIM", 0) == 0;
     hipStream_t st = (hipStream_t)stream;
     TileSource src{};
@@ -1848,7 +1775,6 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
     src.oz = overlap[0]; src.oy = overlap[1]; src.ox = overlap[2];
     src.gy = g.grid[1]; src.gx = g.grid[2];
     const size_t bvox = (size_t)g.eff[0] * g.eff[1] * g.eff[2];
-    int* table_dev = reinterpret_cast<int*>(ws);
     const SegParams sp = seg_params(D, H, W, tile, overlap, crop, g, trimmed);
     Box need[18];
     // ---- shared encoder pass (run_batch: once per batch over the z range its tiles cover), when the geometry and the workspace allow it
@@ -1857,9 +1783,9 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
     if (trimmed && tile_end > tile_begin) {
         int P[3];
         const size_t sb = shared_enc_bytes(h, tile, overlap, g, P);
-        if (sb && plan.total + sb <= ws_bytes) {
+        if (sb && need_bytes + sb <= ws_bytes) {
             shared = true;
-            se.SP0 = reinterpret_cast<float*>((char*)ws + plan.total);
+            se.SP0 = reinterpret_cast<float*>((char*)ws + need_bytes);     // after the carved tensors
             se.PD = P[0]; se.PH = P[1]; se.PW = P[2];
             se.vol = vol; se.D = D; se.H = H; se.W = W;
             for (int i = 0; i < 3; ++i) { se.grid[i] = g.grid[i]; se.eff[i] = g.eff[i]; se.overlap[i] = overlap[i]; }
@@ -1887,7 +1813,7 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
             if (uni[0].hi[0] == 0) continue;                 // every tile of the batch is dead
             src.tile_begin = t;
             if (int rc = run_batch(h, src, n, uni, out_mode, blocks + (size_t)(t - tile_begin) * h->n_classes * bvox,
-                                   (char*)ws, plan, st, table_dev, nc, t - c0, shared ? &se : nullptr)) return rc;
+                                   buf, st, table_dev, nc, t - c0, shared ? &se : nullptr)) return rc;
         }
     }
     return OAI_OK;
@@ -1904,7 +1830,7 @@ double oai_unet_volume_flops(const oai_unet* h, int D, int H, int W, const int t
     for (int t = 0; t < g.ntiles; ++t) {
         tile_regions(t, sp, need);
         for (int k = 0; k < 18; ++k) {
-            if (conv3_only && !(k >= 1 && k < 17 && (kKind[k] == 0 || kKind[k] == 1))) continue;
+            if (conv3_only && !is_conv3_igemm(k)) continue;
             f += layer_flops(h, k, need[k]);
         }
     }
@@ -1974,9 +1900,7 @@ static int stitch_impl(const float* blocks, int ncls, int D, int H, int W, const
         OAI_CHECK_HIP(hipMemsetAsync(maps, 0, total * sizeof(float), (hipStream_t)stream));
         return OAI_OK;
     }
-    size_t nblk = (total + 255) / 256;
-    if (nblk > 256 * 32) nblk = 256 * 32;
-    stitch_kernel<<<(unsigned)nblk, 256, 0, (hipStream_t)stream>>>(blocks, ncls, D, H, W, eff[0], eff[1], eff[2], grid[1], grid[2],
+    stitch_kernel<<<capped_blocks(total, 256 * 32), 256, 0, (hipStream_t)stream>>>(blocks, ncls, D, H, W, eff[0], eff[1], eff[2], grid[1], grid[2],
                                                                 crop ? crop[0] : 0, crop ? crop[1] : 0, crop ? crop[2] : 0, maps, rg);
     OAI_CHECK_LAUNCH();
     return OAI_OK;

@@ -261,6 +261,43 @@ def test_split_fp16_kernel_variants_agree(golden_dir, opts):
     assert np.abs(got[0].astype(np.float64) - z["fc_prob"]).sum() < budget
 
 
+# Timed conv launches of one pass over the 24 x 72 x 72 volume below (batch 9, shared encoder pass).  Deterministic host logic: the constants were counted
+# with oai_unet_profile_read on an MI355X at the parent of the commit that gave the launchers of csrc/unet.hip one launch scope, one XCD deal and one cover.
+@pytest.mark.parametrize("precision,opts,launches", [("fp16x3", {"wide": 2}, 201),                      # launch_wino_shape + the 128-cout form
+                                                     ("fp16x3", {"wide": 2, "winograd": 0}, 172),     # every layer through launch_conv3_shape, strips included (72 % 16 != 0)
+                                                     ("f32", {}, 149)])                                  # launch_wino_f32_shape
+def test_profiled_launches_change_nothing_and_are_counted(golden_dir, precision, opts, launches):
+    """oai_unet_profile: every conv launch between a start / stop event pair of the handle's pool (what bench.py times its headline with).
+    Profiling changes no result; a read returns the pairs recorded since the last read and empties the count; the pool is reused."""
+    from oai_analysis_2_amd.segmentation.engine import UNetEngine
+    z = np.load(os.path.join(golden_dir, "segment_small.npz"))
+    vol = torch.from_numpy(make_volume(int(z["volume_seed"]), (24, 72, 72))).cuda()
+    patch, ovl = tuple(int(v) for v in z["patch"]), tuple(int(v) for v in z["overlap"])
+    tile_zyx, ovl_zyx, crop_zyx = patch[::-1], ovl[::-1], (ovl[2], ovl[0], ovl[1])
+    eng = UNetEngine(make_unet_state_dict(seed=int(z["weight_seed"])), precision=precision)
+    for k, v in opts.items():
+        eng.set_option(k, v)
+
+    def run():
+        return eng.stitch(eng.segment_tiles(vol, tile_zyx, ovl_zyx, out_mode=0, batch=9, crop_zyx=crop_zyx), vol.shape, tile_zyx, ovl_zyx, crop_zyx).cpu().numpy()
+
+    base = run()                                # (fp16x3: calibrates first; the passes below are plain ones)
+    eng.profile(True)
+    got = run()
+    ms, n = eng.profile_read()
+    print(f"[profile {precision} {opts}] {n} launches, {ms:.3f} ms")
+    assert np.array_equal(got, base)
+    assert n > 0 and ms > 0
+    assert eng.profile_read() == (0.0, 0)
+    run()
+    run()
+    assert eng.profile_read()[1] == 2 * n
+    assert n == launches
+    eng.profile(False)
+    run()
+    assert eng.profile_read() == (0.0, 0)
+
+
 @pytest.mark.parametrize("precision", ["f32", "fp16x3"])
 def test_mask_is_the_fp32_sigmoid_predicate_not_the_sign_test(precision):
     """`sigmoid(x) > 0.5` and `x > 0` DIFFER for 0 < x <= ~8.94e-8 (fp32 sigmoid rounds to exactly 0.5).
