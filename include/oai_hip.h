@@ -605,6 +605,24 @@ int oai_cuberille_emit(const float* vol_dev, int D, int H, int W, float iso, con
                        void* workspace_dev, size_t workspace_bytes, long long n_verts, long long n_faces, float* verts_dev, int* faces_dev,
                        int* steps_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Points pushed through phi: the point form of oai_resample_maps_through_phi (csrc/mesh_transform.hip, tests/mesh_transform_ref.py).
+ * phi maps atlas (B) points to patient (A) points, so the vertices of a mesh extracted on the atlas grid land on the patient's own
+ * surface.  The reference would do this step with itk.transform_mesh_filter and the registration's CompositeTransform, if at all;
+ * restated from ITK's documented composite-transform behaviour and unpinned (ITK absent), like the resample (oracle/resample.py).
+ * Per point p (float32 xyz), every coordinate in fp64 without contraction:
+ *   x = point_to_net(p);  inside = x in [-0.5, n - 0.5) on all three axes (the half-open test of the resample; false for a NaN);
+ *   d = the displacement at the 8 corners clamped to the buffer -- rebuilt from phi as fp32 (phi - identity_coord) * (n - 1), widened,
+ *       xyz components: at a lattice point the value oai_phi_to_itk_displacement stores -- lerped along x, then y, then z;
+ *   x2 = x + (inside ? d : 0)   (identity outside the field's buffer: ITK's DisplacementFieldTransform);  out = float32(net_to_out(x2)).
+ * phi_dev fp32 [3][Dn][Hn][Wn] in [0,1] units, channels z, y, x; out_dev float32 [n][3]; inside_dev (may be null) one byte per point,
+ * 1 = inside.  n = 0 is a successful no-op; an axis of phi below 2 voxels is an argument error.  out_dev may not alias pts_dev.  Does
+ * not synchronise.
+ * ---------------------------------------------------------------------------------------- */
+int oai_transform_points_through_phi(const float* pts_dev, long long n, const float* phi_dev, int Dn, int Hn, int Wn,
+                                     const oai_affine* point_to_net, const oai_affine* net_to_out, float* out_dev, unsigned char* inside_dev,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,13 @@ Reference functions mirrored (same names, argument meaning and return roles):
     get_cylinder(vertice)                              :450-455
     get_projection_from_circle_and_vertice(v, circle)  :459-478
     project_thickness(mapped_mesh, mesh_type="FC")     :483-534   2-D atlas thickness map (FC: cylinder angle; TC: plateau PCA)
+    transform_mesh(mesh, transform, ...)               --         mesh vertices pushed through phi, atlas -> patient space
+    mesh_point_affines(image_A, image_B, net_shape)    --         the two affine legs around phi for points, fp64 on the host
+
+transform_mesh has no line in the reference: it would do this step with itk.transform_mesh_filter and the registration's composite
+transform, if at all.  It is restated from ITK's documented composite-transform behaviour and unpinned, like the resample
+(oracle/resample.py); the kernel is csrc/mesh_transform.hip (oai_transform_points_through_phi), restated in fp64 in
+tests/mesh_transform_ref.py, and _transform_points_dev is its device-tensor form for the resident chain of thickness.py.
 
 vtk / trimesh / skimage are not installed here, so meshes are ``Mesh`` objects (float32 vertices [n,3] in (x,y,z)*spacing,
 int32 faces [m,3], per-point data) instead of ``vtkPolyData``; ``Mesh.to_vtk()`` adapts when vtk imports.  The three heavy
@@ -44,8 +51,9 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .image import as_image
+from .registration import DisplacementTransform, resample_affines
 
 
 @dataclass
@@ -602,6 +610,72 @@ def _thickness_inner_dev(vol: torch.Tensor, spacing_xyz, mesh_type: str, min_cel
     sp = _resident_split(vol, spacing_xyz, mesh_type, min_cells)
     (iv, if_, _), (ov, of, _) = _sub_mesh_dev(sp, -1), _sub_mesh_dev(sp, 1)
     return iv, if_, _distance_dev(iv, ov, of)
+
+
+# ---- mesh points pushed through phi (itk.transform_mesh_filter with the registration's transform; csrc/mesh_transform.hip) -----------
+_COORDS = ("spacing", "physical")
+
+
+def mesh_point_affines(image_A, image_B, net_shape, coords_in: str = "spacing", coords_out: str = "spacing"):
+    """The two affine legs around phi for POINTS, composed on the host in fp64 on top of registration.resample_affines:
+
+        point_to_net : ``coords_in`` on image_B's grid -> B index -> network index space
+        net_to_out   : network index space -> A continuous index -> ``coords_out`` on image_A's grid
+
+    "spacing" is get_mesh's convention, (x, y, z) * spacing with no origin or direction; "physical" is ITK's physical point,
+    origin + direction @ (spacing * index), what get_mesh_from_probability_map returns.  ``image_A`` / ``image_B``: Images (metadata is
+    enough: spacing, origin, direction and the array's shape); ``net_shape`` = phi's (D, H, W).  Returns ((A, b), (A, b))."""
+    for c in (coords_in, coords_out):
+        if c not in _COORDS:
+            raise ValueError(f"coords must be one of {_COORDS}, got {c!r}")
+    A, B = as_image(image_A), as_image(image_B)
+    (A1, b1), (A2, b2) = resample_affines(A, B, tuple(int(v) for v in net_shape))
+    if coords_in == "spacing":
+        C_in, c_in = np.diag(1.0 / B.spacing), np.zeros(3)
+    else:
+        P_B, o_B = B.index_to_physical_affine()
+        C_in = np.linalg.inv(P_B)
+        c_in = -C_in @ o_B
+    if coords_out == "spacing":
+        C_out, c_out = np.diag(A.spacing), np.zeros(3)
+    else:
+        C_out, c_out = A.index_to_physical_affine()
+    return (A1 @ C_in, A1 @ c_in + b1), (C_out @ A2, C_out @ b2 + c_out)
+
+
+def _transform_points_dev(points: torch.Tensor, phi: torch.Tensor, point_to_net, net_to_out, return_inside: bool = False):
+    """transform_mesh's vertex step on device tensors: float32 [n,3] in, float32 [n,3] out (and the uint8 inside mask), nothing
+    downloaded.  ``phi`` float32 [3,D,H,W] on the points' device; the affines from mesh_point_affines."""
+    return ops.transform_points_through_phi(points, phi, point_to_net, net_to_out, return_inside=return_inside)
+
+
+def transform_mesh(mesh: Mesh, transform, image_A=None, image_B=None, coords_in: str = "spacing", coords_out: str = "spacing") -> Mesh:
+    """The mesh with its vertices pushed through the registration's map: from image_B's (the atlas') space to image_A's (the patient's),
+    the direction phi provides.  What itk.transform_mesh_filter does with ``create_itk_transform``'s CompositeTransform -- the reference
+    has no such call; restated from ITK's documented composite-transform behaviour, unpinned like the resample (oracle/resample.py):
+    affine into network index space, + the trilinear displacement inside the field's buffer (identity outside it), affine out.
+
+    ``transform``: a registration.DisplacementTransform (it carries ``phi`` and both geometries), or a float32 [3,D,H,W] phi (array or
+    device tensor, VolumeResult.phi) with ``image_A`` and ``image_B``.  ``coords_in`` / ``coords_out``: see mesh_point_affines; a mesh
+    written with meshwrite in "physical" coordinates overlays the patient's image.  Faces and point data are carried over unchanged."""
+    _lib.load()
+    if isinstance(transform, DisplacementTransform):
+        if transform.phi is None:
+            raise ValueError("transform_mesh: the DisplacementTransform carries no phi")
+        phi = transform.phi
+        image_A = transform.image_A if image_A is None else image_A
+        image_B = transform.image_B if image_B is None else image_B
+    else:
+        phi = transform
+    if image_A is None or image_B is None:
+        raise ValueError("transform_mesh: a bare phi needs image_A and image_B (the geometries on either side of it)")
+    shape = tuple(phi.shape)
+    if len(shape) != 4 or shape[0] != 3:
+        raise ValueError(f"transform_mesh: phi must be [3,D,H,W], got {shape}")
+    p2n, n2o = mesh_point_affines(image_A, image_B, shape[1:], coords_in, coords_out)
+    phi_d = _dev(phi, np.float32)
+    out = _transform_points_dev(_dev(mesh.verts, np.float32, (3,), device=phi_d.device), phi_d, p2n, n2o)
+    return Mesh(out.cpu().numpy(), mesh.faces.copy(), dict(mesh.point_data))
 
 
 # ---- atlas thickness map (mesh_processing.py:400-534) ----------------------------------------------------------------------------

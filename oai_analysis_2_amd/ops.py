@@ -194,6 +194,31 @@ def resample_maps_through_phi(maps: torch.Tensor, phi: torch.Tensor, b_index_to_
 
 
 @_on_tensor_device
+def transform_points_through_phi(points: torch.Tensor, phi: torch.Tensor, point_to_net, net_to_out, return_inside: bool = False):
+    """points float32 [n,3] (x,y,z) pushed through the dense map phi [3,D,H,W]: ``net_to_out(x + displacement(x))`` with
+    ``x = point_to_net(p)``, the displacement trilinear inside phi's buffer and zero outside it (include/oai_hip.h, "Points pushed
+    through phi").  The affines are (A [3,3], b [3]) pairs in fp64.  Returns float32 [n,3]; with ``return_inside`` also the uint8 [n]
+    mask of the points that lay inside the buffer."""
+    lib = _lib.load()
+    points = _chk(points, "points")
+    phi = _chk(phi, "phi")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n,3], got {tuple(points.shape)}")
+    if phi.dim() != 4 or phi.shape[0] != 3:
+        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+    if phi.device != points.device:
+        raise ValueError(f"points ({points.device}) and phi ({phi.device}) must live on the same GPU")
+    n = int(points.shape[0])
+    _, Dn, Hn, Wn = (int(v) for v in phi.shape)
+    out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    inside = torch.empty(n, dtype=torch.uint8, device=points.device) if return_inside else None
+    a1, a2 = make_affine(*point_to_net), make_affine(*net_to_out)
+    _lib.check(lib.oai_transform_points_through_phi(points.data_ptr(), n, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), out.data_ptr(),
+                                                    inside.data_ptr() if return_inside else None, _stream()), "oai_transform_points_through_phi")
+    return (out, inside) if return_inside else out
+
+
+@_on_tensor_device
 def image_normalize(vol: torch.Tensor, window_min_perc: float = 0.1, window_max_perc: float = 99.9,
                     output_min: float = 0.0, output_max: float = 1.0, return_window: bool = False):
     """``image_normalize`` of oai_analysis/dask_processing.py:10-26 on the device (fp32 image)."""

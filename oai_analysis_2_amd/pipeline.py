@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from .image import Image
-from .registration import IconEngine, resample_affines
+from .registration import IconEngine, _meta_only, resample_affines
 from .segmentation.engine import UNetEngine, tile_grid
 
 if TYPE_CHECKING:
@@ -38,6 +38,7 @@ class VolumeResult:
     overflow: Optional[torch.Tensor] = None    # int32[1] on the device: the fp16 range flag of THIS volume's segmentation
     #                                            (None with exact arithmetic).  Non-zero = the maps are invalid: repeat in fp32.
     repeated_f32: bool = False   # the fp16x3 run overflowed and these are the results of the fp32 repeat
+    meta_A: Optional[Image] = None    # the patient image's geometry (metadata only, no voxel array): with phi, what takes atlas points to patient points
     thickness: Optional["KneeThickness"] = None    # cartilage thickness on the atlas inner vertices (run(..., thickness=atlas) only)
 
 
@@ -93,10 +94,15 @@ class VolumePipeline:
         return ops.resample_maps_through_phi(maps, phi, b2n, n2a, shape)
 
     # ---- one volume, one GPU --------------------------------------------------------------------------------------------------
-    def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None) -> VolumeResult:
+    def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None,
+            thickness_space: str = "atlas") -> VolumeResult:
         """``thickness``: a thickness.ThicknessAtlas -- the volume's cartilage thickness on the atlas inner vertices is measured from
         ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
-        None (default): nothing more is launched."""
+        None (default): nothing more is launched.  ``thickness_space``: "atlas" (default) = the distance on the atlas grid, as the
+        reference takes it; "patient" = on the meshes pushed through this volume's phi, in the patient's own millimetres
+        (ThicknessAtlas.measure(..., phi=, image_A=))."""
+        if thickness_space not in ("atlas", "patient"):
+            raise ValueError(f"thickness_space must be 'atlas' or 'patient', got {thickness_space!r}")
         res = self._run_overlapped(vol, meta_A) if self.overlap_registration else self._run_serial(vol, meta_A)
         if check and res.overflow is not None:
             raised = bool(int(res.overflow.item()))
@@ -104,7 +110,8 @@ class VolumePipeline:
             if raised:
                 res = self.rerun_f32(vol, meta_A)
         if thickness is not None:
-            res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing)
+            push = dict(phi=res.phi, image_A=res.meta_A) if thickness_space == "patient" else {}
+            res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, **push)
         return res
 
     def rerun_f32(self, vol: torch.Tensor, meta_A: Image, sharded_group="none") -> VolumeResult:
@@ -125,7 +132,7 @@ class VolumePipeline:
         flag = self._flag_snapshot()
         phi = self.register(vol)
         atlas_maps = self.resample(maps, phi, meta_A)
-        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag)
+        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A))
 
     def _run_overlapped(self, vol: torch.Tensor, meta_A: Image) -> VolumeResult:
         """Registration needs only the image, not its segmentation: its small, launch- and latency-bound kernels (a few dozen
@@ -141,7 +148,7 @@ class VolumePipeline:
         flag = self._flag_snapshot()
         main.wait_stream(self._side)
         atlas_maps = self.resample(maps, phi, meta_A)
-        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag)
+        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A))
 
     # ---- one volume, all ranks of a group (single-volume latency mode) ---------------------------------------------
     def segment_sharded(self, vol: torch.Tensor, group=None) -> torch.Tensor:
@@ -196,7 +203,7 @@ class VolumePipeline:
         nz = self.atlas.array.shape[0]
         local = self.resample(maps, phi, meta_A, parallel.slab_range_for_rank(nz, rank, world))
         atlas_maps = parallel.gather_slabs(local, nz, group)
-        res = VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag)
+        res = VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A))
         if check and flag is not None:
             raised = bool(int(flag.item()))                 # (the same verdict on every rank: the state was MAX-reduced)
             self.unet.note_volume_flag(raised)

@@ -7,12 +7,20 @@ step behind ``VolumeResult.fc_atlas`` / ``tc_atlas``, plus a thickness IMAGE on 
     atlas.measure(fc_atlas, tc_atlas)       per knee: marching cubes -> large regions -> edge graph -> smoothing -> device split ->
                                             inner / outer sub-mesh -> distance inner -> outer -> map_attributes onto the atlas inner
                                             vertices; one float32 vector per cartilage comes back
+    atlas.measure(.., phi=, image_A=)       the same in PATIENT millimetres: both sub-meshes are pushed through phi (atlas -> patient,
+                                            csrc/mesh_transform.hip) before the distance is taken; map_attributes still runs on the
+                                            atlas-space inner vertices, which is what puts every knee on the atlas' vertices
     atlas.image(thickness, kind)            per knee: one gather through the raster; the same pixel is the same atlas location in
                                             every knee, because map_attributes puts every knee on the atlas' vertices
 
 The inner / outer split of the atlas and of every knee is the DEVICE split (mesh_processing.split_mesh(on_device=True): scikit-learn
 >= 1.4's KMeans restated in fp64); it is the only split that keeps the stage resident.  The default host split of split_mesh runs the
 installed sklearn and may label differently under an older version.
+
+The atlas-space distance is what the reference measures, and it carries the registration's local stretch: a knee that had to be
+stretched 10 % to fit the atlas reads 10 % thick.  The iso-surface extracted on the atlas grid is {x_B : p(phi(x_B)) = 0.5}; its image
+under phi is the patient's own iso-surface, to interpolation accuracy, so the distance between the pushed sub-meshes is the patient's.
+The push is restated from ITK's documented composite-transform behaviour and unpinned (ITK is absent), like the resample.
 
 The host-side rules of the raster are exact, without thresholds (fc_cut, fc_face_skip, tc_face_skip below).
 """
@@ -25,6 +33,7 @@ import numpy as np
 import torch
 
 from . import mesh_processing as mp
+from .image import Image, as_image
 
 KINDS = ("FC", "TC")
 _TC_SPLIT_Z = 50.0                  # project_thickness: the plateaus are split at z < 50 (raw coordinate units)
@@ -73,13 +82,24 @@ def tc_point_order(z) -> np.ndarray:
     return np.concatenate([np.nonzero(z >= _TC_SPLIT_Z)[0], np.nonzero(z < _TC_SPLIT_Z)[0]])
 
 
+def _frame_of(atlas_image) -> Tuple[np.ndarray, np.ndarray]:
+    """(origin, direction) of the atlas grid, from an Image (or anything as_image takes)."""
+    img = as_image(atlas_image)
+    return img.origin.copy(), img.direction.copy()
+
+
 @dataclass
 class KneeThickness:
     """Cartilage thickness of one knee on the atlas inner vertices: float32 [n_fc], [n_tc] (numpy, or device tensors with
-    ``keep_on_device``).  A cartilage that could not be measured is all NaN and has its reason in ``errors["FC"]`` / ``errors["TC"]``."""
+    ``keep_on_device``).  A cartilage that could not be measured is all NaN and has its reason in ``errors["FC"]`` / ``errors["TC"]``.
+    ``space``: "atlas" = distances taken on the atlas grid (the reference's), "patient" = on the meshes pushed through phi, the patient's
+    own millimetres; then ``outside[kind]`` counts the pushed vertices (inner and outer) that fell outside phi's buffer and moved by the
+    affines alone."""
     fc: Union[np.ndarray, torch.Tensor]
     tc: Union[np.ndarray, torch.Tensor]
     errors: Dict[str, str] = field(default_factory=dict)
+    space: str = "atlas"
+    outside: Dict[str, int] = field(default_factory=dict)
 
     def __getitem__(self, kind: str):
         return {"FC": self.fc, "TC": self.tc}[kind]
@@ -101,9 +121,13 @@ class ThicknessAtlas:
 
     Both the atlas and every knee are split on the device (sklearn >= 1.4 semantics, see mesh_processing.split_mesh): the only split
     that keeps the stage resident.  ``min_cells`` (an int, or one per cartilage) is get_mesh's region filter, used for the atlas and
-    for every knee; ``radius`` is map_attributes'.  ``image_shape`` (H, W) is an API default, not a tuned number."""
+    for every knee; ``radius`` is map_attributes'.  ``image_shape`` (H, W) is an API default, not a tuned number.
 
-    def __init__(self, atlas_fc, atlas_tc, spacing_xyz=None, image_shape: Tuple[int, int] = (256, 256), min_cells=3000, radius: float = 1.0):
+    ``atlas_image``: the atlas grid's geometry (an Image; only its origin and direction are used) for patient-space ``measure``.  Maps
+    given as Images carry their own; a tensor or an array has none, and patient space then needs this argument here or at ``measure``."""
+
+    def __init__(self, atlas_fc, atlas_tc, spacing_xyz=None, image_shape: Tuple[int, int] = (256, 256), min_cells=3000, radius: float = 1.0,
+                 atlas_image=None):
         self.image_shape = (int(image_shape[0]), int(image_shape[1]))
         self.min_cells = {k: int(min_cells[k] if isinstance(min_cells, dict) else min_cells) for k in KINDS}
         self.radius = float(radius)
@@ -116,10 +140,15 @@ class ThicknessAtlas:
         self._targets: Dict[str, torch.Tensor] = {}
         self._scatter: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
         self.spacing: Dict[str, np.ndarray] = {}            # each map's own (x, y, z) spacing: measure's default for that cartilage
+        self.frame: Dict[str, Optional[Tuple[np.ndarray, np.ndarray]]] = {}     # each map's (origin, direction); None: built from a bare tensor or array
         self.device = None
         for kind, probmap in zip(KINDS, (atlas_fc, atlas_tc)):
-            vol, sp = mp._probmap_dev(probmap, spacing_xyz)[:2]
+            vol, sp, origin, direction = mp._probmap_dev(probmap, spacing_xyz)
             self.spacing[kind] = sp
+            if atlas_image is not None:
+                self.frame[kind] = _frame_of(atlas_image)
+            else:
+                self.frame[kind] = None if isinstance(probmap, (torch.Tensor, np.ndarray)) else (origin, direction)
             if self.device is None:
                 self.device = vol.device
             iv, if_, _ = mp._sub_mesh_dev(mp._resident_split(vol, sp, kind, self.min_cells[kind]), -1)
@@ -161,29 +190,73 @@ class ThicknessAtlas:
         lo, hi, _ = mp.mesh_grid_params_device(iv, if_)
         return mp._map_attributes_dev(iv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
 
-    def measure(self, fc_atlas: torch.Tensor, tc_atlas: torch.Tensor, spacing_xyz=None, keep_on_device: bool = False) -> KneeThickness:
+    def _measure_one_patient(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame) -> Tuple[torch.Tensor, int]:
+        """_measure_one with both sub-meshes pushed through phi before the distance: (vector, pushed vertices outside phi's buffer)."""
+        sp = mp._resident_split(vol, spacing, kind, self.min_cells[kind])
+        (iv, if_, _), (ov, of, _) = mp._sub_mesh_dev(sp, -1), mp._sub_mesh_dev(sp, 1)
+        image_B = Image(np.broadcast_to(np.zeros((), np.float32), tuple(vol.shape)), spacing, *frame)       # the grid of the maps, no voxels
+        p2n, n2o = mp.mesh_point_affines(image_A, image_B, phi.shape[1:])
+        (piv, in_i), (pov, in_o) = (mp._transform_points_dev(v, phi, p2n, n2o, return_inside=True) for v in (iv, ov))
+        dist = mp._distance_dev(piv, pov, of)                   # (the grid parameters are the pushed outer mesh's)
+        if iv.shape[0] == 0:
+            raise ValueError("map_attributes: the source mesh has no points")
+        lo, hi, _ = mp.mesh_grid_params_device(iv, if_)         # sources stay in atlas space: vertex correspondence across knees
+        vec = mp._map_attributes_dev(iv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
+        return vec, sum(int(m.numel()) - int(np.count_nonzero(m.cpu().numpy())) for m in (in_i, in_o))
+
+    def measure(self, fc_atlas: torch.Tensor, tc_atlas: torch.Tensor, spacing_xyz=None, keep_on_device: bool = False, phi=None, image_A=None,
+                atlas_image=None) -> KneeThickness:
         """Thickness of one knee on the atlas inner vertices, from the two [z,y,x] float32 device tensors of a ``VolumeResult``
         (``spacing_xyz``: the atlas grid's, default the spacing of the map this atlas was built from).  Everything stays on the device, on the
         current stream, until the two vectors; only the inner -> outer distance is computed.  Per cartilage, bit for bit,
 
             map_attributes(get_thickness_mesh(Image(map.cpu(), spacing), kind, min_cells=.., on_device=True)[0], atlas.inner[kind]).point_data["Distance"]
 
+        ``phi`` (float32 [3,D,H,W], VolumeResult.phi) with ``image_A`` (the patient image's geometry, VolumeResult.meta_A): the distance
+        in PATIENT space (``space == "patient"``).  The inner and outer sub-meshes are pushed through phi to the patient's "spacing"
+        coordinates and the distance taken between the pushed meshes; map_attributes keeps the atlas-space inner vertices as its
+        sources.  The atlas side of phi is the grid of the maps: their shape, ``spacing_xyz``, and the origin and direction of the
+        Image the atlas was built from, or of ``atlas_image`` (here or at construction; required for an atlas built from bare
+        tensors or arrays).  Per cartilage, bit for bit, with inner, outer = get_thickness_mesh(.., on_device=True) as above and
+        T = lambda m: transform_mesh(m, phi, image_A, image_B):
+
+            map_attributes(Mesh(inner.verts, inner.faces, {"Distance": point_distance(T(inner).verts, T(outer))}), atlas.inner[kind]).point_data["Distance"]
+
+        ``outside[kind]`` counts the pushed vertices outside phi's buffer.  Unpinned, like the resample: ITK is absent.
+
         A map with no region above ``min_cells``, or an FC slab of fewer than 2 faces, raises ValueError inside those functions: that
         is caught PER CARTILAGE, the vector filled with NaN and the message kept in ``errors`` -- one bad knee must not end a cohort.
         Nothing else is caught."""
-        out, errors = {}, {}
+        if (phi is None) != (image_A is None):
+            raise ValueError(f"patient-space thickness needs both phi and image_A: {'image_A' if image_A is None else 'phi'} is missing")
+        patient = phi is not None
+        if patient:
+            frames = {k: _frame_of(atlas_image) if atlas_image is not None else self.frame[k] for k in KINDS}
+            missing = [k for k in KINDS if frames[k] is None]
+            if missing:
+                raise ValueError(f"patient-space thickness needs atlas_image: the atlas {'/'.join(missing)} map was a bare tensor or array, which has no origin "
+                                 "or direction (pass atlas_image= here or to ThicknessAtlas)")
+            image_A = as_image(image_A)
+            with torch.cuda.device(self.device):
+                phi = mp._dev(phi, np.float32, device=self.device)
+            if phi.dim() != 4 or phi.shape[0] != 3:
+                raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+        out, errors, outside = {}, {}, {}
         for kind, vol in zip(KINDS, (fc_atlas, tc_atlas)):
             sp = self.spacing[kind] if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
             with torch.cuda.device(self.device):
                 vol_d = mp._probmap_dev(vol, sp)[0]
                 try:
-                    out[kind] = self._measure_one(vol_d, sp, kind)
+                    if patient:
+                        out[kind], outside[kind] = self._measure_one_patient(vol_d, sp, kind, phi, image_A, frames[kind])
+                    else:
+                        out[kind] = self._measure_one(vol_d, sp, kind)
                 except ValueError as e:
                     errors[kind] = str(e)
                     out[kind] = torch.full((self.n_points(kind),), float("nan"), dtype=torch.float32, device=self.device)
         if not keep_on_device:
             out = {k: v.cpu().numpy() for k, v in out.items()}
-        return KneeThickness(out["FC"], out["TC"], errors)
+        return KneeThickness(out["FC"], out["TC"], errors, "patient" if patient else "atlas", outside)
 
     def _raster(self, kind: str) -> mp.ThicknessRaster:
         if kind not in KINDS:

@@ -8,8 +8,11 @@
                      Synthetic weights produce no cartilage, so THIS SCRIPT (not the library) puts the slab / bowl tensors in place of
                      fc_atlas / tc_atlas before thickness_stream; the runner is the one process_cohort builds, without the NIfTI reads
     per_knee_wall    normalise -> segment + register + resample -> thickness -> thickness images of one volume, host array to images
+    patient          (--patient) ThicknessAtlas.measure(..., phi=, image_A=) -- both sub-meshes pushed through a smooth phi on the
+                     80x192x192 network grid before the distance -- beside the atlas-space measure on the same maps, alternated in this
+                     process, and the point transform alone (profiles/thickness_native.md)
 
-    python scripts/bench_thickness_stage.py [--repeats 3] [--volumes 24] [--no-cohort]
+    python scripts/bench_thickness_stage.py [--repeats 3] [--volumes 24] [--no-cohort] [--patient]
 """
 import argparse
 import dataclasses
@@ -67,6 +70,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--volumes", type=int, default=24)
     ap.add_argument("--no-cohort", action="store_true", help="the stage and the raster only (no U-Net / ICON engines are built)")
+    ap.add_argument("--patient", action="store_true", help="also time the patient-space measure against the atlas-space one (alternated)")
     args = ap.parse_args()
     reps = max(args.repeats, 3)
     knee = {"FC": slab(0.0), "TC": bowl(0.0)}
@@ -93,6 +97,30 @@ def main():
     out["parent_equivalent_chain_ms_per_knee"] = spread(t_chain)
     out["stage_equals_chain_bitwise"] = same
     out["median_thickness"] = {k: float(np.nanmedian(k0[k])) for k in ("FC", "TC")}
+
+    if args.patient:
+        net = (80, 192, 192)                                 # registration.NET_SHAPE
+        grids = np.mgrid[0:net[0], 0:net[1], 0:net[2]].astype(np.float64)
+        ident = np.stack([grids[d] * (1.0 / (net[d] - 1)) for d in range(3)]).astype(np.float32)
+        phi = torch.from_numpy((ident + 0.01 * np.sin(2 * np.pi * ident[[1, 2, 0]])).astype(np.float32)).cuda()      # smooth, up to 1 % of each extent
+        meta_A = Image(np.broadcast_to(np.zeros((), np.float32), VOL_SHAPE), [0.36, 0.36, 0.7], [2.0, -3.0, 1.0])
+        patient = lambda: atlas.measure(maps["FC"], maps["TC"], phi=phi, image_A=meta_A)
+        p0 = patient()                                       # warm
+        n_pat = max(reps, 10)
+        t_atl, t_pat = [], []
+        for _ in range(n_pat):                               # alternated in one process
+            t_atl.append(ms(stage)[0])
+            t_pat.append(ms(patient)[0])
+        diff = [b - a for a, b in zip(t_atl, t_pat)]
+        verts = torch.from_numpy(atlas.inner["FC"].verts).cuda()
+        legs = mp.mesh_point_affines(meta_A, Image(np.broadcast_to(np.zeros((), np.float32), VOL_SHAPE), knee["FC"].spacing), net)
+        push = lambda: [mp._transform_points_dev(verts, phi, *legs, return_inside=True) for _ in range(100)]
+        push()
+        out["patient"] = {"atlas_space_ms_per_knee": spread(t_atl), "patient_space_ms_per_knee": spread(t_pat), "extra_ms_per_knee_paired": spread(diff),
+                          "extra_share_of_stage": statistics.median(diff) / statistics.median(t_atl), "errors": p0.errors, "outside": p0.outside,
+                          "median_thickness": {k: float(np.nanmedian(p0[k])) for k in ("FC", "TC")},
+                          "transform_alone_ms_per_call": spread([ms(push)[0] / 100 for _ in range(5)]), "transform_points": int(verts.shape[0]),
+                          "phi": "identity + 0.01 sin(2 pi u) per channel on 80x192x192", "image_A": "160x384x384, spacing 0.36 0.36 0.7"}
 
     uv, faces = atlas.uv["FC"], torch.from_numpy(atlas.inner["FC"].faces).cuda()
     mp.thickness_image_build(uv, faces, None, atlas.image_shape)
