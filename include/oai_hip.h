@@ -623,6 +623,35 @@ int oai_transform_points_through_phi(const float* pts_dev, long long n, const fl
                                      const oai_affine* point_to_net, const oai_affine* net_to_out, float* out_dev, unsigned char* inside_dev,
                                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Registration QC (csrc/phi_jacobian.hip, tests/phi_jacobian_ref.py): the Jacobian determinant of phi, its fold count, and the overlap
+ * counts of two thresholded maps.  The fold definition is that of icon_registration.losses.flips (backward differences, negative
+ * determinant), restated as recalled and unpinned: icon_registration is absent.
+ *
+ * oai_phi_jacobian: phi_dev fp32 [3][D][H][W] in [0,1] units, channels z, y, x (ITK component c = channel 2 - c), identity =
+ * float32((double)i * 1/(n-1)).  One determinant per cell (z,y,x), z in [1,D), y in [1,H), x in [1,W), on the displacement in network
+ * voxels, contraction off:
+ *   u_c(p)  = (double)((phi[2-c][p] - identity_c(p)) * (float)(n_c - 1))          fp32 subtraction and product, as oai_phi_to_itk_displacement
+ *   J[r][k] = delta_rk + (u_r(p) - u_r(p - e_k))                                  fp64; r, k over (x, y, z)
+ *   det     = (J00*(J11*J22 - J12*J21) - J01*(J10*J22 - J12*J20)) + J02*(J10*J21 - J11*J20)
+ * (the displacement form reads exactly 1 on the identity map; raw phi differences do not, float32 coordinates not being equidistant).
+ * det_out_dev (may be null): float32 [D-1][H-1][W-1], the rounded determinant.  stats_dev: double[7] on the device --
+ *   [0] cells = (D-1)(H-1)(W-1)   [1] folds: det < 0 on the fp64 value   [2] cells with a non-finite determinant, left out of all the others
+ *   [3] min  [4] max  (+inf / -inf when no cell is finite)   [5] sum of det   [6] sum of det^2
+ * Per-block partials go to the workspace and a second kernel adds them in index order: no atomics, a block count that depends on the
+ * shape only, so the stats are bit-reproducible and do not depend on det_out_dev.  Does not synchronise.  Every axis must be >= 2.
+ * ---------------------------------------------------------------------------------------- */
+/* 0 when an axis is below 2 voxels. */
+size_t oai_phi_jacobian_workspace_bytes(int D, int H, int W);
+int oai_phi_jacobian(const float* phi_dev, int D, int H, int W, float* det_out_dev, void* workspace_dev, size_t workspace_bytes,
+                     double* stats_dev, void* stream);
+/* oai_mask_overlap: a_dev, b_dev float32 [n] (b_dev may be null: the set B is empty).  A value belongs to its set when it is finite and
+ * > threshold (the segmentation's rule); a non-finite value is in no set.  counts_dev: long long[4] on the device -- |A|, |B|, |A and B|,
+ * positions where a or b is non-finite.  Integer arithmetic: exact.  n = 0 gives zeros (and needs no workspace).  Does not synchronise. */
+size_t oai_mask_overlap_workspace_bytes(long long n);
+int oai_mask_overlap(const float* a_dev, const float* b_dev, long long n, float threshold, void* workspace_dev, size_t workspace_bytes,
+                     long long* counts_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

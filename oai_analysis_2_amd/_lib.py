@@ -92,6 +92,10 @@ SIGNATURES = {
     "oai_cuberille_emit": (_I, [_P, _I, _I, _I, _F, C.POINTER(_D), _I, _I, _I, _D, _D, _D, _I, _I, _P, _Z, C.c_longlong, C.c_longlong,
                                 _P, _P, _P, _P]),
     "oai_transform_points_through_phi": (_I, [_P, C.c_longlong, _P, _I, _I, _I, C.POINTER(Affine), C.POINTER(Affine), _P, _P, _P]),
+    "oai_phi_jacobian_workspace_bytes": (_Z, [_I, _I, _I]),
+    "oai_phi_jacobian": (_I, [_P, _I, _I, _I, _P, _P, _Z, _P, _P]),
+    "oai_mask_overlap_workspace_bytes": (_Z, [C.c_longlong]),
+    "oai_mask_overlap": (_I, [_P, _P, C.c_longlong, _F, _P, _Z, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

@@ -150,7 +150,8 @@ class CohortRunner:
             ev.record(self.down_stream)
         return k, ev, tuple((name, tuple(getattr(res, name).shape), getattr(res, name).dtype) for name in names)
 
-    def _collect(self, k: int, ev: torch.cuda.Event, keys: tuple, repeated: bool, held=None, meta_A: Optional[Image] = None) -> Optional[VolumeResult]:
+    def _collect(self, k: int, ev: torch.cuda.Event, keys: tuple, repeated: bool, held=None, meta_A: Optional[Image] = None,
+                 meta_B: Optional[Image] = None) -> Optional[VolumeResult]:
         """Download worker: wait for the D2H, copy the results out of the pinned set into memory the caller owns, free the set.  None = the
         fp16 range flag of the volume (4 bytes, rides along) is raised: the results must not be used.  ``held``: the device tensors being
         copied -- referenced until the copy is done."""
@@ -174,14 +175,14 @@ class CohortRunner:
             with self._lock:
                 self.stats["clone_bytes"] += sum(o.numel() * o.element_size() for o in outs)
                 self.stats["clone_s"] += dt
-            return VolumeResult(*outs, repeated_f32=repeated, meta_A=meta_A)
+            return VolumeResult(*outs, repeated_f32=repeated, meta_A=meta_A, meta_B=meta_B)
         finally:
             self._free_out.put(k)                                          # (the pinned buffers are reused by a later volume)
 
     def _download(self, res: VolumeResult, done: torch.cuda.Event) -> Optional[VolumeResult]:
         with torch.cuda.device(self.pipe.unet.device):
             k, ev, keys = self._queue_d2h(res, done)
-            return self._collect(k, ev, keys, res.repeated_f32, res, res.meta_A)
+            return self._collect(k, ev, keys, res.repeated_f32, res, res.meta_A, res.meta_B)
 
     def _download_async(self, res: VolumeResult, done: torch.cuda.Event) -> Future:
         return self._down.submit(self._download, res, done)

@@ -220,6 +220,16 @@ def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, kee
         pool.shutdown(wait=True, cancel_futures=True)
 
 
+def qc_stream(results: Iterable[Tuple[int, object]], reference=None) -> Iterator[Tuple[int, object]]:
+    """(index, qc.RegistrationQC) for every (index, VolumeResult) of ``results``: the registration QC record of each knee of a cohort
+    (folds and det J of its phi, volume scale, cartilage volume; Dice against ``reference``, a qc.QCReference).  The results must be
+    complete and on the device, as ``process_cohort(keep_on_device=True)`` hands them over.  A plain synchronous generator: a few small
+    launches and one download of a few dozen bytes per knee need no worker thread."""
+    from .qc import registration_qc
+    for index, res in results:
+        yield index, registration_qc(res, reference=reference)
+
+
 def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None,
                              space: str = "atlas") -> Iterator[Tuple[int, object]]:
     """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the

@@ -218,6 +218,55 @@ def transform_points_through_phi(points: torch.Tensor, phi: torch.Tensor, point_
     return (out, inside) if return_inside else out
 
 
+def _out_slot(out: Optional[torch.Tensor], n: int, dtype, device, name: str) -> torch.Tensor:
+    """The small device result of a QC entry point: a fresh tensor, or the caller's slot of a buffer that is downloaded in one piece."""
+    if out is None:
+        return torch.empty(n, dtype=dtype, device=device)
+    if out.device != device or out.dtype != dtype or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} [{n}] tensor on {device}")
+    return out
+
+
+@_on_tensor_device
+def phi_jacobian(phi: torch.Tensor, return_map: bool = False, out: Optional[torch.Tensor] = None):
+    """The Jacobian determinant of the dense map phi float32 [3,D,H,W] per cell (z,y,x) in [1,D) x [1,H) x [1,W), backward differences of
+    the displacement in network voxels (include/oai_hip.h, "Registration QC").  Returns the float64 [7] DEVICE tensor (cells, folds,
+    non-finite cells, min, max, sum, sum of squares; ``out``: written there instead of a new tensor); with ``return_map`` also the
+    float32 [D-1,H-1,W-1] map.  Does not synchronise: read the stats when they are needed (qc.registration_qc does, once)."""
+    lib = _lib.load()
+    phi = _chk(phi, "phi")
+    if phi.dim() != 4 or phi.shape[0] != 3:
+        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+    _, D, H, W = (int(v) for v in phi.shape)
+    stats = _out_slot(out, 7, torch.float64, phi.device, "out")
+    det = torch.empty((max(D - 1, 0), max(H - 1, 0), max(W - 1, 0)), dtype=torch.float32, device=phi.device) if return_map else None
+    ws = torch.empty(int(lib.oai_phi_jacobian_workspace_bytes(D, H, W)), dtype=torch.uint8, device=phi.device)
+    _lib.check(lib.oai_phi_jacobian(phi.data_ptr(), D, H, W, det.data_ptr() if return_map else None, ws.data_ptr(), ws.numel(),
+                                    stats.data_ptr(), _stream()), "oai_phi_jacobian")
+    return (stats, det) if return_map else stats
+
+
+@_on_tensor_device
+def mask_overlap(a: torch.Tensor, b: Optional[torch.Tensor] = None, threshold: float = 0.5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Overlap counts of two float32 device tensors of equal size under ``value > threshold`` (a non-finite value is in no set): the
+    int64 [4] DEVICE tensor |A|, |B|, |A and B|, positions with a non-finite value.  ``b`` None: |A| and zeros.  Exact; does not
+    synchronise."""
+    lib = _lib.load()
+    a = _chk(a, "a")
+    if b is not None:
+        b = _chk(b, "b")
+        if b.numel() != a.numel():
+            raise ValueError(f"a and b must have the same number of elements, got {a.numel()} and {b.numel()}")
+        if b.device != a.device:
+            raise ValueError(f"a ({a.device}) and b ({b.device}) must live on the same GPU")
+    n = int(a.numel())
+    counts = _out_slot(out, 4, torch.int64, a.device, "out")
+    ws = torch.empty(int(lib.oai_mask_overlap_workspace_bytes(n)), dtype=torch.uint8, device=a.device)
+    _lib.check(lib.oai_mask_overlap(a.data_ptr() if n else None, b.data_ptr() if (b is not None and n) else None, n, float(threshold),
+                                    ws.data_ptr() if n else None, ws.numel(), counts.data_ptr(), _stream()), "oai_mask_overlap")
+    return counts
+
+
 @_on_tensor_device
 def image_normalize(vol: torch.Tensor, window_min_perc: float = 0.1, window_max_perc: float = 99.9,
                     output_min: float = 0.0, output_max: float = 1.0, return_window: bool = False):

@@ -21,6 +21,7 @@ from .registration import IconEngine, _meta_only, resample_affines
 from .segmentation.engine import UNetEngine, tile_grid
 
 if TYPE_CHECKING:
+    from .qc import QCReference, RegistrationQC
     from .thickness import KneeThickness, ThicknessAtlas
 
 TILE_ZYX = (32, 128, 128)        # patch_size (128,128,32) in x,y,z (a2)
@@ -39,6 +40,8 @@ class VolumeResult:
     #                                            (None with exact arithmetic).  Non-zero = the maps are invalid: repeat in fp32.
     repeated_f32: bool = False   # the fp16x3 run overflowed and these are the results of the fp32 repeat
     meta_A: Optional[Image] = None    # the patient image's geometry (metadata only, no voxel array): with phi, what takes atlas points to patient points
+    meta_B: Optional[Image] = None    # the atlas image's geometry (metadata only): the other side of phi
+    qc: Optional["RegistrationQC"] = None          # registration QC: folds and det J of phi, Dice, cartilage volume (run(..., qc=...) only)
     thickness: Optional["KneeThickness"] = None    # cartilage thickness on the atlas inner vertices (run(..., thickness=atlas) only)
 
 
@@ -54,6 +57,7 @@ class VolumePipeline:
         self.tile_zyx, self.overlap_zyx, self.crop_zyx, self.batch = tuple(tile_zyx), tuple(overlap_zyx), tuple(crop_zyx), batch
         self.atlas_dev = torch.from_numpy(np.ascontiguousarray(atlas.array, dtype=np.float32)).to(unet.device)
         self._atlas_net = None
+        self._atlas_meta = _meta_only(atlas)
         self._side = None
         self.overlap_registration = True          # registration underneath the segmentation (+1.5 %); False serialises
 
@@ -95,12 +99,18 @@ class VolumePipeline:
 
     # ---- one volume, one GPU --------------------------------------------------------------------------------------------------
     def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None,
-            thickness_space: str = "atlas") -> VolumeResult:
+            thickness_space: str = "atlas", qc=None) -> VolumeResult:
         """``thickness``: a thickness.ThicknessAtlas -- the volume's cartilage thickness on the atlas inner vertices is measured from
         ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
         None (default): nothing more is launched.  ``thickness_space``: "atlas" (default) = the distance on the atlas grid, as the
         reference takes it; "patient" = on the meshes pushed through this volume's phi, in the patient's own millimetres
-        (ThicknessAtlas.measure(..., phi=, image_A=))."""
+        (ThicknessAtlas.measure(..., phi=, image_A=)).
+        ``qc``: True, or a qc.QCReference (the atlas' own maps, for Dice) -- the registration QC record of the volume
+        (qc.registration_qc: folds and det J of phi, volume scale, cartilage volume) in ``VolumeResult.qc``, computed where the thickness
+        is: after the range check and the fp32 repeat.  A few small launches and one more synchronisation.  None (default): nothing more
+        is launched and no bit changes."""
+        if qc is not None and qc is not True and not hasattr(qc, "maps"):
+            raise ValueError(f"qc must be None, True or a qc.QCReference, got {qc!r}")
         if thickness_space not in ("atlas", "patient"):
             raise ValueError(f"thickness_space must be 'atlas' or 'patient', got {thickness_space!r}")
         res = self._run_overlapped(vol, meta_A) if self.overlap_registration else self._run_serial(vol, meta_A)
@@ -112,6 +122,9 @@ class VolumePipeline:
         if thickness is not None:
             push = dict(phi=res.phi, image_A=res.meta_A) if thickness_space == "patient" else {}
             res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, **push)
+        if qc is not None:
+            from .qc import registration_qc
+            res.qc = registration_qc(res, reference=None if qc is True else qc)
         return res
 
     def rerun_f32(self, vol: torch.Tensor, meta_A: Image, sharded_group="none") -> VolumeResult:
@@ -132,7 +145,7 @@ class VolumePipeline:
         flag = self._flag_snapshot()
         phi = self.register(vol)
         atlas_maps = self.resample(maps, phi, meta_A)
-        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A))
+        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A), meta_B=self._atlas_meta)
 
     def _run_overlapped(self, vol: torch.Tensor, meta_A: Image) -> VolumeResult:
         """Registration needs only the image, not its segmentation: its small, launch- and latency-bound kernels (a few dozen
@@ -148,7 +161,7 @@ class VolumePipeline:
         flag = self._flag_snapshot()
         main.wait_stream(self._side)
         atlas_maps = self.resample(maps, phi, meta_A)
-        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A))
+        return VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A), meta_B=self._atlas_meta)
 
     # ---- one volume, all ranks of a group (single-volume latency mode) ---------------------------------------------
     def segment_sharded(self, vol: torch.Tensor, group=None) -> torch.Tensor:
@@ -168,7 +181,8 @@ class VolumePipeline:
     def run_sharded(self, vol: Optional[torch.Tensor], meta_A: Image, group=None, src: int = 0, check: bool = True) -> VolumeResult:
         """``vol`` is needed on rank ``src`` only (others may pass None): broadcast -> tile-sharded segmentation + all_gather ->
         registration replicated (0.1 TFLOP: cheaper than communicating) -> both resamples sharded by atlas z-slab + all_gather.
-        The fp16 range flag is all_reduce(MAX)ed: either every rank keeps the result or every rank repeats in fp32."""
+        The fp16 range flag is all_reduce(MAX)ed: either every rank keeps the result or every rank repeats in fp32.
+        Registration QC (``run(..., qc=...)``) is out of scope here: call qc.registration_qc on the result."""
         from . import parallel
         import torch.distributed as dist
         world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -203,7 +217,7 @@ class VolumePipeline:
         nz = self.atlas.array.shape[0]
         local = self.resample(maps, phi, meta_A, parallel.slab_range_for_rank(nz, rank, world))
         atlas_maps = parallel.gather_slabs(local, nz, group)
-        res = VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A))
+        res = VolumeResult(maps[0], maps[1], phi, atlas_maps[0], atlas_maps[1], flag, meta_A=_meta_only(meta_A), meta_B=self._atlas_meta)
         if check and flag is not None:
             raised = bool(int(flag.item()))                 # (the same verdict on every rank: the state was MAX-reduced)
             self.unet.note_volume_flag(raised)

@@ -68,6 +68,14 @@ class DisplacementTransform:
     def affines(self):
         return resample_affines(self.image_A, self.image_B, self.net_shape)
 
+    def jacobian(self, return_map: bool = False):
+        """The registration QC of this transform (qc.registration_qc on ``phi`` with both geometries): ``.jacobian`` holds the fold count
+        and the statistics of det J, ``.volume_scale`` the factor to physical volume change."""
+        from .qc import registration_qc
+        if self.phi is None:
+            raise ValueError("this DisplacementTransform carries no phi (the dense map the Jacobian is taken of)")
+        return registration_qc(self.phi, self.image_A, self.image_B, return_map=return_map)
+
     def to_itk(self):  # pragma: no cover - itk is absent in this environment
         import itk
         dim = 3
