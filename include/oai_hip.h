@@ -612,7 +612,8 @@ int oai_cuberille_emit(const float* vol_dev, int D, int H, int W, float iso, con
  * restated from ITK's documented composite-transform behaviour and unpinned (ITK absent), like the resample (oracle/resample.py).
  * Per point p (float32 xyz), every coordinate in fp64 without contraction:
  *   x = point_to_net(p);  inside = x in [-0.5, n - 0.5) on all three axes (the half-open test of the resample; false for a NaN);
- *   d = the displacement at the 8 corners clamped to the buffer -- rebuilt from phi as fp32 (phi - identity_coord) * (n - 1), widened,
+ *   d = the displacement at the 8 corners clamped to the buffer -- rebuilt from phi by itk_disp of csrc/phi_field.h, the function
+ *       behind every rebuild in the library (fp32 (phi - identity_coord) * (n - 1), widened),
  *       xyz components: at a lattice point the value oai_phi_to_itk_displacement stores -- lerped along x, then y, then z;
  *   x2 = x + (inside ? d : 0)   (identity outside the field's buffer: ITK's DisplacementFieldTransform);  out = float32(net_to_out(x2)).
  * phi_dev fp32 [3][Dn][Hn][Wn] in [0,1] units, channels z, y, x; out_dev float32 [n][3]; inside_dev (may be null) one byte per point,
@@ -631,7 +632,7 @@ int oai_transform_points_through_phi(const float* pts_dev, long long n, const fl
  * oai_phi_jacobian: phi_dev fp32 [3][D][H][W] in [0,1] units, channels z, y, x (ITK component c = channel 2 - c), identity =
  * float32((double)i * 1/(n-1)).  One determinant per cell (z,y,x), z in [1,D), y in [1,H), x in [1,W), on the displacement in network
  * voxels, contraction off:
- *   u_c(p)  = (double)((phi[2-c][p] - identity_c(p)) * (float)(n_c - 1))          fp32 subtraction and product, as oai_phi_to_itk_displacement
+ *   u_c(p)  = (double)((phi[2-c][p] - identity_c(p)) * (float)(n_c - 1))          itk_disp of csrc/phi_field.h, as oai_phi_to_itk_displacement
  *   J[r][k] = delta_rk + (u_r(p) - u_r(p - e_k))                                  fp64; r, k over (x, y, z)
  *   det     = (J00*(J11*J22 - J12*J21) - J01*(J10*J22 - J12*J20)) + J02*(J10*J21 - J11*J20)
  * (the displacement form reads exactly 1 on the identity map; raw phi differences do not, float32 coordinates not being equidistant).

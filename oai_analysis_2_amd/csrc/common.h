@@ -61,6 +61,12 @@ int exclusive_scan_i32(const int* in, int* out, long long n, int* scratch, hipSt
 
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
+// blocks of a grid-stride launch: one per `threads` items, at least one, at most `cap` (256 CUs x 16 blocks unless the caller says otherwise)
+static inline unsigned grid_stride_blocks(long long items, int threads, long long cap = 256LL * 16) {
+    const long long blocks = (items + threads - 1) / threads;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+
 // Diagnostics (in-kernel phase stamps, kernel-variant selection by environment -- nothing that changes a result) exist only in
 // builds compiled with -DOAI_DIAG (a separate .so that scripts/ load through OAI_LIB_PATH).  The production library never reads
 // the environment: diag_env() is the constant default.  The timing ablations with wrong results that rounds 2-5 kept behind

@@ -509,63 +509,45 @@ int unet_forward(const NetWeights& nw, bool pad_front, const float* a, const flo
         const float* src = cat[l] + (size_t)kUpOut[l] * dm.vox[l];
         float* dst = l < 4 ? cat[l + 1] + (size_t)kUpOut[l + 1] * dm.vox[l + 1] : bottom;
         const int res_ofs = pad_front ? kDown[l + 1] - kDown[l] : 0;
+        auto launch = [&](auto kernel, dim3 grid) {
+            kernel<<<grid, 256, 0, st>>>(src, kDown[l], dm.d[l][0], dm.d[l][1], dm.d[l][2], nw.down_w[l], nw.down_b[l], dst, kDown[l + 1],
+                                         dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2], 1.0f, res_ofs);
+        };
         if (dm.vox[l + 1] >= kSplitKBelow || kDown[l] < 8) {
-            dim3 grid(oai::cdiv(dm.vox[l + 1], 256), kDown[l + 1] / 16);
-            icon_conv3_kernel<2, 16, true, true, 1><<<grid, 256, 0, st>>>(src, kDown[l], dm.d[l][0], dm.d[l][1], dm.d[l][2],
-                                                                           nw.down_w[l], nw.down_b[l], dst, kDown[l + 1],
-                                                                           dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2], 1.0f, res_ofs);
+            launch(icon_conv3_kernel<2, 16, true, true, 1>, dim3(oai::cdiv(dm.vox[l + 1], 256), kDown[l + 1] / 16));
         } else if ((long long)oai::cdiv(dm.vox[l + 1], 32) * (kDown[l + 1] / 16) >= kFewBlocks) {
-            dim3 grid(oai::cdiv(dm.vox[l + 1], 32), kDown[l + 1] / 16);
-            icon_conv3_kernel<2, 16, true, true, 8><<<grid, 256, 0, st>>>(src, kDown[l], dm.d[l][0], dm.d[l][1], dm.d[l][2],
-                                                                           nw.down_w[l], nw.down_b[l], dst, kDown[l + 1],
-                                                                           dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2], 1.0f, res_ofs);
+            launch(icon_conv3_kernel<2, 16, true, true, 8>, dim3(oai::cdiv(dm.vox[l + 1], 32), kDown[l + 1] / 16));
         } else if ((long long)oai::cdiv(dm.vox[l + 1], 32) * (kDown[l + 1] / 16) < kFewBlocks / 16) {
-            dim3 grid(oai::cdiv(dm.vox[l + 1], 32), kDown[l + 1]);          // one cout per block
-            icon_conv3_kernel<2, 1, true, true, 8><<<grid, 256, 0, st>>>(src, kDown[l], dm.d[l][0], dm.d[l][1], dm.d[l][2],
-                                                                          nw.down_w[l], nw.down_b[l], dst, kDown[l + 1],
-                                                                          dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2], 1.0f, res_ofs);
+            launch(icon_conv3_kernel<2, 1, true, true, 8>, dim3(oai::cdiv(dm.vox[l + 1], 32), kDown[l + 1]));          // one cout per block
         } else {        // the deepest levels (a few dozen voxels): 4 couts per block instead of 16, four times the blocks
-            dim3 grid(oai::cdiv(dm.vox[l + 1], 32), kDown[l + 1] / 4);
-            icon_conv3_kernel<2, 4, true, true, 8><<<grid, 256, 0, st>>>(src, kDown[l], dm.d[l][0], dm.d[l][1], dm.d[l][2],
-                                                                          nw.down_w[l], nw.down_b[l], dst, kDown[l + 1],
-                                                                          dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2], 1.0f, res_ofs);
+            launch(icon_conv3_kernel<2, 4, true, true, 8>, dim3(oai::cdiv(dm.vox[l + 1], 32), kDown[l + 1] / 4));
         }
         OAI_CHECK_LAUNCH();
     }
     for (int l = 4; l >= 0; --l) {
         const float* src = l == 4 ? bottom : cat[l + 1];
         const long long per_par = (long long)((dm.d[l][0] + 1) / 2) * ((dm.d[l][1] + 1) / 2) * ((dm.d[l][2] + 1) / 2);
+        // `tail`: the two unit arguments that only the MFMA form takes
+        auto launch = [&](auto kernel, dim3 grid, auto... tail) {
+            kernel<<<grid, 256, 0, st>>>(src, kUpIn[l], dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2], nw.up_w[l], nw.up_b[l], nw.bn_s[l], nw.bn_t[l],
+                                         cat[l], kUpOut[l], dm.d[l][0], dm.d[l][1], dm.d[l][2], tail...);
+        };
         if (per_par >= kMfmaUpFrom) {                   // the big levels: MFMA (fp32 products), one wave per 32 tx of an output row
             constexpr int MB = 2;
             const int ntxb = (int)oai::cdiv((dm.d[l][2] + 1) / 2, 16 * MB);
             const long long nunits = (long long)dm.d[l][0] * dm.d[l][1] * ntxb;
-            dim3 grid(oai::cdiv(nunits, 4), kUpOut[l] / 16);
-            icon_up_mfma_kernel<MB, false><<<grid, 256, 0, st>>>(src, kUpIn[l], dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2],
-                                                                 nw.up_w[l], nw.up_b[l], nw.bn_s[l], nw.bn_t[l], cat[l], kUpOut[l],
-                                                                 dm.d[l][0], dm.d[l][1], dm.d[l][2], ntxb, nunits);
+            launch(icon_up_mfma_kernel<MB, false>, dim3(oai::cdiv(nunits, 4), kUpOut[l] / 16), ntxb, nunits);
         } else if (kUpOut[l] % 16 == 0 && kUpIn[l] % 4 == 0) {      // the small, K-deep levels: one block per unit, its waves split the (kz, ky) taps
             constexpr int MB = 1;
             const int ntxb = (int)oai::cdiv((dm.d[l][2] + 1) / 2, 16 * MB);
             const long long nunits = (long long)dm.d[l][0] * dm.d[l][1] * ntxb;
-            dim3 grid((unsigned)nunits, kUpOut[l] / 16);
-            icon_up_mfma_kernel<MB, true><<<grid, 256, 0, st>>>(src, kUpIn[l], dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2],
-                                                                nw.up_w[l], nw.up_b[l], nw.bn_s[l], nw.bn_t[l], cat[l], kUpOut[l],
-                                                                dm.d[l][0], dm.d[l][1], dm.d[l][2], ntxb, nunits);
+            launch(icon_up_mfma_kernel<MB, true>, dim3((unsigned)nunits, kUpOut[l] / 16), ntxb, nunits);
         } else if ((long long)oai::cdiv(per_par, 32) * (kUpOut[l] / 16) * 8 >= kFewBlocks) {
-            dim3 grid(oai::cdiv(per_par, 32), kUpOut[l] / 16, 8);
-            icon_up_kernel<16, 8><<<grid, 256, 0, st>>>(src, kUpIn[l], dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2],
-                                                         nw.up_w[l], nw.up_b[l], nw.bn_s[l], nw.bn_t[l], cat[l], kUpOut[l],
-                                                         dm.d[l][0], dm.d[l][1], dm.d[l][2]);
+            launch(icon_up_kernel<16, 8>, dim3(oai::cdiv(per_par, 32), kUpOut[l] / 16, 8));
         } else if ((long long)oai::cdiv(per_par, 32) * (kUpOut[l] / 16) * 8 < kFewBlocks / 16) {
-            dim3 grid(oai::cdiv(per_par, 32), kUpOut[l], 8);
-            icon_up_kernel<1, 8><<<grid, 256, 0, st>>>(src, kUpIn[l], dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2],
-                                                        nw.up_w[l], nw.up_b[l], nw.bn_s[l], nw.bn_t[l], cat[l], kUpOut[l],
-                                                        dm.d[l][0], dm.d[l][1], dm.d[l][2]);
+            launch(icon_up_kernel<1, 8>, dim3(oai::cdiv(per_par, 32), kUpOut[l], 8));
         } else {
-            dim3 grid(oai::cdiv(per_par, 32), kUpOut[l] / 4, 8);
-            icon_up_kernel<4, 8><<<grid, 256, 0, st>>>(src, kUpIn[l], dm.d[l + 1][0], dm.d[l + 1][1], dm.d[l + 1][2],
-                                                        nw.up_w[l], nw.up_b[l], nw.bn_s[l], nw.bn_t[l], cat[l], kUpOut[l],
-                                                        dm.d[l][0], dm.d[l][1], dm.d[l][2]);
+            launch(icon_up_kernel<4, 8>, dim3(oai::cdiv(per_par, 32), kUpOut[l] / 4, 8));
         }
         OAI_CHECK_LAUNCH();
     }

@@ -7,38 +7,23 @@
 // registration's CompositeTransform; restated from ITK's documented behaviour and unpinned, like the resample (oracle/resample.py).
 //   oai_transform_points_through_phi   one thread per point, grid-stride
 //
-// The displacement at the 8 clamped corners is rebuilt from phi's fp32 planes exactly as phi_to_disp_kernel / resample_maps_kernel do
-// (fp32 (phi - identity) * (n - 1), then widened), so at a lattice point it is the value oai_phi_to_itk_displacement stores.  Coordinates,
-// the lerp (x, then y, then z) and both affines are fp64 with contraction off, written so that a numpy restatement performs the same
-// operations in the same order (tests/mesh_transform_ref.py); the only rounding left open is the final one to float32.  A mesh has
+// The displacement at the 8 clamped corners is rebuilt from phi's fp32 planes by the function that phi_to_disp_kernel and
+// resample_maps_kernel call (itk_disp, csrc/phi_field.h), so at a lattice point it is the value oai_phi_to_itk_displacement stores.
+// Coordinates, the lerp (x, then y, then z) and both affines are fp64 with contraction off, written so that a numpy restatement performs
+// the same operations in the same order (tests/mesh_transform_ref.py); the only rounding left open is the final one to float32.  A mesh has
 // 10^4 .. 10^5 points: the launch is latency-bound, 24 scattered 4-byte loads per point out of a field that sits in L2 / Infinity Cache
 // after the resample.  No LDS, no atomics.
 #include "common.h"
 
 #pragma clang fp contract(off)
 
+#include "phi_field.h"      // after the pragma: compiled with contraction off here (see its leading comment)
+
 namespace {
 
+using namespace oai;
+
 constexpr int kT = 256;                       // threads per block
-
-__device__ __forceinline__ float identity_coord(int i, double inv_nm1) {      // csrc/warp.hip: float32(index * 1/(n-1)), the product in fp64
-    return (float)((double)i * inv_nm1);
-}
-
-__device__ __forceinline__ void apply(const oai_affine& t, double x, double y, double z, double& ox, double& oy, double& oz) {
-    ox = t.A[0] * x + t.A[1] * y + t.A[2] * z + t.b[0];
-    oy = t.A[3] * x + t.A[4] * y + t.A[5] * z + t.b[1];
-    oz = t.A[6] * x + t.A[7] * y + t.A[8] * z + t.b[2];
-}
-
-// c clamped to [0, n-1] (a NaN clamps to 0): corners i0 <= i1 <= n-1 and the weight of i1
-__device__ __forceinline__ void clamp_split(double c, int n, int& i0, int& i1, double& f) {
-    c = fmin(fmax(c, 0.0), (double)(n - 1));
-    const double fl = floor(c);
-    i0 = (int)fl;
-    i1 = min(i0 + 1, n - 1);
-    f = c - fl;
-}
 
 __global__ void __launch_bounds__(kT)
 transform_points_kernel(const float* __restrict__ pts, long long n, const float* __restrict__ phi, int Dn, int Hn, int Wn, oai_affine p2n,
@@ -48,7 +33,7 @@ transform_points_kernel(const float* __restrict__ pts, long long n, const float*
     for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
         double x, y, z;
         apply(p2n, (double)pts[3 * i], (double)pts[3 * i + 1], (double)pts[3 * i + 2], x, y, z);
-        const bool inside = x >= -0.5 && x < Wn - 0.5 && y >= -0.5 && y < Hn - 0.5 && z >= -0.5 && z < Dn - 0.5;      // (false for a NaN)
+        const bool inside = inside_buffer(x, y, z, Wn, Hn, Dn);
         if (inside) {
             int x0, x1, y0, y1, z0, z1;
             double fx, fy, fz;
@@ -64,17 +49,12 @@ transform_points_kernel(const float* __restrict__ pts, long long n, const float*
                 const float sc = (float)((c == 0 ? Wn : c == 1 ? Hn : Dn) - 1);
                 const float ia = c == 0 ? identity_coord(x0, inx) : c == 1 ? identity_coord(y0, iny) : identity_coord(z0, inz);
                 const float ib = c == 0 ? identity_coord(x1, inx) : c == 1 ? identity_coord(y1, iny) : identity_coord(z1, inz);
-                auto at = [&](long long row, int xx, bool zhi, bool yhi, bool xhi) {
+                auto at = [&](bool zhi, bool yhi, bool xhi) {
                     const float id = c == 0 ? (xhi ? ib : ia) : c == 1 ? (yhi ? ib : ia) : (zhi ? ib : ia);
-                    return (double)((p[row + xx] - id) * sc);
+                    const long long row = zhi ? (yhi ? o11 : o10) : (yhi ? o01 : o00);
+                    return itk_disp(p[row + (xhi ? x1 : x0)], id, sc);
                 };
-                const double c00 = at(o00, x0, 0, 0, 0) * (1 - fx) + at(o00, x1, 0, 0, 1) * fx;
-                const double c01 = at(o01, x0, 0, 1, 0) * (1 - fx) + at(o01, x1, 0, 1, 1) * fx;
-                const double c10 = at(o10, x0, 1, 0, 0) * (1 - fx) + at(o10, x1, 1, 0, 1) * fx;
-                const double c11 = at(o11, x0, 1, 1, 0) * (1 - fx) + at(o11, x1, 1, 1, 1) * fx;
-                const double c0 = c00 * (1 - fy) + c01 * fy;
-                const double c1 = c10 * (1 - fy) + c11 * fy;
-                acc[c] = c0 * (1 - fz) + c1 * fz;
+                acc[c] = lerp8(at, fx, fy, fz);
             }
             x += acc[0]; y += acc[1]; z += acc[2];
         }
@@ -97,10 +77,8 @@ int oai_transform_points_through_phi(const float* pts_dev, long long n, const fl
                   Dn, Hn, Wn);
     if (n == 0) return OAI_OK;
     OAI_CHECK_ARG(pts_dev && phi_dev && point_to_net && net_to_out && out_dev, "oai_transform_points_through_phi: null pointer");
-    const long long cap = 256LL * 16;                          // 256 CUs x 16 blocks: grid-stride beyond that
-    const long long blocks = (n + kT - 1) / kT;
-    transform_points_kernel<<<(unsigned)(blocks > cap ? cap : blocks), kT, 0, (hipStream_t)stream>>>(pts_dev, n, phi_dev, Dn, Hn, Wn, *point_to_net,
-                                                                                                      *net_to_out, out_dev, inside_dev);
+    transform_points_kernel<<<grid_stride_blocks(n, kT), kT, 0, (hipStream_t)stream>>>(pts_dev, n, phi_dev, Dn, Hn, Wn, *point_to_net, *net_to_out,
+                                                                                        out_dev, inside_dev);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }

@@ -76,10 +76,7 @@ int make_geom(int D, int H, int W, const int tile[3], const int overlap[3], Part
     return OAI_OK;
 }
 
-unsigned grid_for(long long n) {
-    long long b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 256 * 32 ? 256 * 32 : b));
-}
+constexpr long long kGridCap = 256 * 32;     // 256 CUs x 32 blocks: grid-stride beyond that
 
 }  // namespace
 
@@ -94,7 +91,7 @@ int oai_partition_tiles(const float* vol, int D, int H, int W, const int tile[3]
     OAI_CHECK_ARG(0 <= tile_begin && tile_begin <= tile_end && tile_end <= n_all, "oai_partition_tiles: tile range [%d,%d) outside [0,%d)", tile_begin, tile_end, n_all);
     if (tile_end == tile_begin) return OAI_OK;
     const long long total = (long long)(tile_end - tile_begin) * g.tz * g.ty * g.tx;
-    partition_kernel<<<grid_for(total), 256, 0, (hipStream_t)stream>>>(vol, g, tile_begin, tile_end - tile_begin, tiles_out);
+    partition_kernel<<<oai::grid_stride_blocks(total, 256, kGridCap), 256, 0, (hipStream_t)stream>>>(vol, g, tile_begin, tile_end - tile_begin, tiles_out);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
@@ -105,7 +102,7 @@ int oai_assemble_vote(const int* tile_labels, int n_labels, int D, int H, int W,
     OAI_CHECK_ARG(n_labels >= 1 && n_labels <= 16, "oai_assemble_vote: 1..16 label classes");
     PartGeom g;
     if (int rc = make_geom(D, H, W, tile, overlap, g)) return rc;
-    const unsigned grid = grid_for((long long)D * H * W);
+    const unsigned grid = oai::grid_stride_blocks((long long)D * H * W, 256, kGridCap);
     if (n_labels <= 4) vote_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(tile_labels, g, n_labels, out);
     else vote_kernel<16><<<grid, 256, 0, (hipStream_t)stream>>>(tile_labels, g, n_labels, out);
     OAI_CHECK_LAUNCH();

@@ -3,8 +3,8 @@
 //
 //   oai_phi_jacobian    one determinant per cell (z,y,x), z in [1,D), y in [1,H), x in [1,W): the backward-difference stencil of
 //                       icon_registration.losses.flips, restated from memory and unpinned (icon_registration is absent), on the
-//                       DISPLACEMENT u = (phi - identity) * (n - 1) rebuilt in fp32 exactly as phi_to_disp_kernel (csrc/warp.hip) and
-//                       transform_points_kernel (csrc/mesh_transform.hip) rebuild it:  J[r][k] = delta_rk + (u_r(p) - u_r(p - e_k)).
+//                       DISPLACEMENT u = (phi - identity) * (n - 1) rebuilt in fp32 by the function that phi_to_disp_kernel (csrc/warp.hip)
+//                       and transform_points_kernel (csrc/mesh_transform.hip) call (itk_disp, csrc/phi_field.h):  J[r][k] = delta_rk + (u_r(p) - u_r(p - e_k)).
 //                       The float32 identity coordinates do not difference exactly, so the raw-phi form of the identity map reads
 //                       det in [0.999977, 1.0000048] at (80,192,192); the displacement form reads exactly 1.
 //   oai_mask_overlap    |A|, |B|, |A and B| and the non-finite positions of two float32 arrays under `value > threshold`
@@ -25,17 +25,17 @@
 
 #pragma clang fp contract(off)
 
+#include "phi_field.h"      // after the pragma: compiled with contraction off here (see its leading comment)
+
 namespace {
+
+using namespace oai;
 
 constexpr int kT = 256;                       // threads per block
 constexpr int kTX = 64, kTY = 4, kZC = 8;     // phi_jacobian_kernel's block of cells: x (one wave per row), y, z
 constexpr int kJP = 6;                        // doubles per block partial: folds, non-finite, min, max, sum, sum of squares
 constexpr int kMP = 4;                        // counts per block partial of mask_overlap_kernel
 constexpr long long kMaskBlocks = 2048;       // 256 CUs x 8 blocks: grid-stride beyond that
-
-__device__ __forceinline__ float identity_coord(int i, double inv_nm1) {      // csrc/warp.hip: float32(index * 1/(n-1)), the product in fp64
-    return (float)((double)i * inv_nm1);
-}
 
 struct JacAcc {
     double v[kJP];
@@ -77,9 +77,9 @@ phi_jacobian_kernel(const float* __restrict__ phi, int D, int H, int W, int nbx,
     // ITK component c (x, y, z) = phi channel 2 - c (w, h, d)
     auto disp = [&](int zz, int yy, int xx, const float idz, double* u) {
         const long long o = ((long long)zz * H + yy) * W + xx;
-        u[0] = (double)((phi[2 * plane + o] - identity_coord(xx, inx)) * sx);
-        u[1] = (double)((phi[plane + o] - identity_coord(yy, iny)) * sy);
-        u[2] = (double)((phi[o] - idz) * sz);
+        u[0] = itk_disp(phi[2 * plane + o], identity_coord(xx, inx), sx);
+        u[1] = itk_disp(phi[plane + o], identity_coord(yy, iny), sy);
+        u[2] = itk_disp(phi[o], idz, sz);
     };
     JacAcc acc;
     acc.clear();

@@ -9,15 +9,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "phi_field.h"      // compiled in this file's contraction mode (on): see its leading comment
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace oai;
 
-__device__ __forceinline__ float identity_coord(int i, double inv_nm1) {
-    // mermaidlite.identity_map: float32(index * spacing) with spacing = 1/(n-1) in float64
-    return (float)((double)i * inv_nm1);
-}
+constexpr int kThreads = 256;
 
 // PyTorch grid_sampler_compute_source_index (align_corners=True) + border clip
 __device__ __forceinline__ float unnormalize_border(float c01, int size) {
@@ -29,61 +27,107 @@ __device__ __forceinline__ float unnormalize_border(float c01, int size) {
 // The 8 corners as 4 x-adjacent PAIRS: one 8-byte load fetches (x0, x0+1).  x0 is clamped to w-2 so that the pair
 // exists; at the upper border (ix == w-1 exactly) all weight moves to the second element, which is what PyTorch's
 // skipped out-of-range corner (weight 0) amounts to.  Same for y and z through clamped row/plane indices.
-struct Taps {
-    int o[4];      // offsets of the pairs (z0,y0) (z0,y1) (z1,y0) (z1,y1) inside one [d][h][w] plane
+struct Tap {
+    int x0, y0, y1, z0, z1;                       // x1 = x0 + 1
+    int o[4];                                     // offsets of the pairs (z0,y0) (z0,y1) (z1,y0) (z1,y1) inside one [d][h][w] plane
     float wx0, wx1, wy0, wy1, wz0, wz1;
 };
 
-__device__ __forceinline__ void make_taps(float cz, float cy, float cx, int d, int h, int w, Taps& t) {
+__device__ __forceinline__ void make_tap(float cz, float cy, float cx, int d, int h, int w, Tap& t) {
     const float iz = unnormalize_border(cz, d), iy = unnormalize_border(cy, h), ix = unnormalize_border(cx, w);
     const float fz0 = floorf(iz), fy0 = floorf(iy), fx0 = floorf(ix);
-    const int z0 = (int)fz0, y0 = (int)fy0;
+    t.z0 = (int)fz0; t.y0 = (int)fy0;
     int x0 = (int)fx0;
     float wx1 = ix - fx0, wx0 = (fx0 + 1.0f) - ix;      // PyTorch's weights: (ix - floor), (floor + 1 - ix)
     if (x0 > w - 2) { x0 = w - 2; wx0 = 0.0f; wx1 = 1.0f; }   // ix == w-1: the in-range corner carries weight 1
-    t.wx0 = wx0; t.wx1 = wx1;
+    t.x0 = x0; t.wx0 = wx0; t.wx1 = wx1;
     t.wy1 = iy - fy0; t.wy0 = (fy0 + 1.0f) - iy;
     t.wz1 = iz - fz0; t.wz0 = (fz0 + 1.0f) - iz;
-    const int z1 = min(z0 + 1, d - 1), y1 = min(y0 + 1, h - 1);   // clamped twin carries weight 0 at the border
-    t.o[0] = (z0 * h + y0) * w + x0;
-    t.o[1] = (z0 * h + y1) * w + x0;
-    t.o[2] = (z1 * h + y0) * w + x0;
-    t.o[3] = (z1 * h + y1) * w + x0;
+    t.z1 = min(t.z0 + 1, d - 1); t.y1 = min(t.y0 + 1, h - 1);   // clamped twin carries weight 0 at the border
+    t.o[0] = (t.z0 * h + t.y0) * w + x0; t.o[1] = (t.z0 * h + t.y1) * w + x0;
+    t.o[2] = (t.z1 * h + t.y0) * w + x0; t.o[3] = (t.z1 * h + t.y1) * w + x0;
 }
 
 struct __attribute__((packed, aligned(4))) pair_f32 { float a, b; };      // 8-byte load at 4-byte alignment (dwordx2)
 
+// the eight corners (a = x0, b = x0 + 1 of each pair) in PyTorch's order and weight products: tnw tne tsw tse bnw bne bsw bse,
+// weight = wx * wy * wz
+__device__ __forceinline__ float accumulate8(float a00, float b00, float a01, float b01, float a10, float b10, float a11, float b11, const Tap& t) {
+    float acc = 0.0f;
+    acc += a00 * (t.wx0 * t.wy0 * t.wz0);
+    acc += b00 * (t.wx1 * t.wy0 * t.wz0);
+    acc += a01 * (t.wx0 * t.wy1 * t.wz0);
+    acc += b01 * (t.wx1 * t.wy1 * t.wz0);
+    acc += a10 * (t.wx0 * t.wy0 * t.wz1);
+    acc += b10 * (t.wx1 * t.wy0 * t.wz1);
+    acc += a11 * (t.wx0 * t.wy1 * t.wz1);
+    acc += b11 * (t.wx1 * t.wy1 * t.wz1);
+    return acc;
+}
+
 // (Tried and rejected: fetching only x0 and taking x0+1 from the neighbour lane by ds_bpermute -- the cross-lane moves
 // and the masked fix-up load cost more than the second dword: 36 us instead of 23 us for the 160^3 warp.)
-__device__ __forceinline__ float gather8(const float* __restrict__ plane, const Taps& t) {
+__device__ __forceinline__ float gather8(const float* __restrict__ plane, const Tap& t) {
     const pair_f32 p00 = *reinterpret_cast<const pair_f32*>(plane + t.o[0]);
     const pair_f32 p01 = *reinterpret_cast<const pair_f32*>(plane + t.o[1]);
     const pair_f32 p10 = *reinterpret_cast<const pair_f32*>(plane + t.o[2]);
     const pair_f32 p11 = *reinterpret_cast<const pair_f32*>(plane + t.o[3]);
-    // PyTorch order and weight products: tnw tne tsw tse bnw bne bsw bse, weight = wx * wy * wz
-    float acc = 0.0f;
-    acc += p00.a * (t.wx0 * t.wy0 * t.wz0);
-    acc += p00.b * (t.wx1 * t.wy0 * t.wz0);
-    acc += p01.a * (t.wx0 * t.wy1 * t.wz0);
-    acc += p01.b * (t.wx1 * t.wy1 * t.wz0);
-    acc += p10.a * (t.wx0 * t.wy0 * t.wz1);
-    acc += p10.b * (t.wx1 * t.wy0 * t.wz1);
-    acc += p11.a * (t.wx0 * t.wy1 * t.wz1);
-    acc += p11.b * (t.wx1 * t.wy1 * t.wz1);
-    return acc;
+    return accumulate8(p00.a, p00.b, p01.a, p01.b, p10.a, p10.b, p11.a, p11.b, t);
+}
+
+// Workgroup ids are dealt round-robin to the 8 XCDs, each with its own L2.  Give every XCD one contiguous run of blocks (a z-slab of
+// the output, hence -- for the near-identity maps of registration -- of the source), so that a source line is fetched into ONE L2
+// instead of up to eight (17.8 -> 16.6 us on the 160^3 warp, scripts/micro/warp_probe.hip).  The grid is dealt_grid(nb) blocks;
+// false = this block has no work.
+template <typename T>
+__device__ __forceinline__ bool dealt_block(T nb, T& logical) {
+    const T bid = (T)blockIdx.x, per = (nb + 7) >> 3;
+    logical = (bid & 7) * per + (bid >> 3);
+    return (bid >> 3) < per && logical < nb;
+}
+
+inline unsigned dealt_grid(long long nb) { return (unsigned)(((nb + 7) / 8) * 8); }      // 8 XCD runs of ceil(nb/8) blocks
+
+// The output brick of sample_kernel and chain_kernel.  One lane = one output voxel, consecutive lanes = consecutive x: for
+// near-identity maps a wave's 64 pair loads fall in two or three 128-byte lines (a lane-per-4-voxels layout touches 8 lines per load
+// and is 3x slower).  A block is a 32(x) x 4(y) x 2(z) brick: lanes of a wave are 32 consecutive x on two rows (coalesced 128-byte
+// coordinate reads / result writes, pair loads falling in two or three lines), and the four waves' source rows overlap, so the 2x2
+// (y,z) re-use of every source row is served by the CU's L1 instead of L2.
+#ifndef OAI_WARP_U
+#define OAI_WARP_U 2
+#endif
+constexpr int kWarpU = OAI_WARP_U;      // z-adjacent bricks per block: their coordinate loads, then their gathers, are in flight
+                                        // together, and they share source rows in L1
+
+// This lane's place in output brick `logical`: x, y and, by voxel(u), its kWarpU voxels -- z, whether the voxel exists, and its offset
+// in an output plane (0 where it does not: a safe address).  One voxel per call: the kernels load voxel u's coordinates before voxel u + 1.
+struct BrickLane {
+    int x, y, bz, tz;
+    __device__ __forceinline__ BrickLane(int logical, int nbx, int nby) {
+        const int tx = threadIdx.x & 31, ty = (threadIdx.x >> 5) & 3;
+        const int bx = logical % nbx, by = (logical / nbx) % nby;
+        bz = logical / (nbx * nby); tz = threadIdx.x >> 7;
+        x = bx * 32 + tx; y = by * 4 + ty;
+    }
+    template <typename IDX>
+    __device__ __forceinline__ bool voxel(int u, int D, int H, int W, int& z, IDX& lin) const {
+        z = (bz * kWarpU + u) * 2 + tz;
+        const bool ok = x < W && y < H && z < D;
+        lin = ok ? ((IDX)z * H + y) * W + x : 0;
+        return ok;
+    }
+};
+
+struct BrickGrid { int nbx, nby, nbz; long long nb; };      // the 32 x 4 x 2 kWarpU bricks that cover a D x H x W output
+
+inline BrickGrid brick_grid(int D, int H, int W) {
+    const int nbx = (W + 31) / 32, nby = (H + 3) / 4, nbz = ((D + 1) / 2 + kWarpU - 1) / kWarpU;
+    return BrickGrid{nbx, nby, nbz, (long long)nbx * nby * nbz};
 }
 
 // MODE 0: out[c] = sample(src[c], coords)            (image / field warp, C channels)
 // MODE 1: out[c] = coords[c] + sample(src[c], coords) (compose, C == 3)
-// coords == nullptr -> identity map of the output grid.
-// One lane = one output voxel, consecutive lanes = consecutive x: for near-identity maps a wave's 64 pair loads fall in
-// two or three 128-byte lines (a lane-per-4-voxels layout touches 8 lines per load and is 3x slower).
-// One lane = one output voxel.  A block is a 32(x) x 4(y) x 2(z) brick: lanes of a wave are 32 consecutive x on two
-// rows (coalesced 128-byte coordinate reads / result writes, pair loads falling in two or three lines), and the four
-// waves' source rows overlap, so the 2x2 (y,z) re-use of every source row is served by the CU's L1 instead of L2.
-#ifndef OAI_WARP_U
-#define OAI_WARP_U 2
-#endif
+// coords == nullptr -> identity map of the output grid.  IDX: 32-bit offsets where both grids allow it.
 template <int MODE, typename IDX, int CT>
 __global__ void __launch_bounds__(kThreads)
 sample_kernel(const float* __restrict__ src, int C_rt, int d, int h, int w,
@@ -92,35 +136,26 @@ sample_kernel(const float* __restrict__ src, int C_rt, int d, int h, int w,
     const IDX plane_out = (IDX)D * H * W;
     const IDX plane_src = (IDX)d * h * w;
     const int C = CT > 0 ? CT : C_rt;              // 1 (image) and 3 (field) are compiled unrolled
-    const int tx = threadIdx.x & 31, ty = (threadIdx.x >> 5) & 3, tz = threadIdx.x >> 7;
-    constexpr int U = OAI_WARP_U;       // z-adjacent bricks per block: their coordinate loads, then their gathers, are in
-                                        // flight together, and they share source rows in L1.  32-bit offsets (IDX).
-    // Workgroup ids are dealt round-robin to the 8 XCDs, each with its own L2.  Give every XCD one contiguous run of
-    // bricks (a z-slab of the output, hence -- for the near-identity maps of registration -- of the source), so that a
-    // source line is fetched into ONE L2 instead of up to eight (17.8 -> 16.6 us on the 160^3 warp, scripts/micro/warp_probe.hip).
-    const int nb = nbx * nby * nbz;
-    const int per = (nb + 7) >> 3;
-    const int logical = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
-    if (((int)blockIdx.x >> 3) >= per || logical >= nb) return;
-    const int bx = logical % nbx, by = (logical / nbx) % nby, bz = logical / (nbx * nby);
-    const int x = bx * 32 + tx, y = by * 4 + ty;
+    constexpr int U = kWarpU;
+    int logical;
+    if (!dealt_block(nbx * nby * nbz, logical)) return;
+    const BrickLane v(logical, nbx, nby);
     IDX lin[U];
     bool ok[U];
     float cz[U], cy[U], cx[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const int z = (bz * U + u) * 2 + tz;
-        ok[u] = x < W && y < H && z < D;
-        lin[u] = ok[u] ? ((IDX)z * H + y) * W + x : 0;
+        int z;
+        ok[u] = v.voxel(u, D, H, W, z, lin[u]);
         if (coords) {
             cz[u] = coords[lin[u]]; cy[u] = coords[plane_out + lin[u]]; cx[u] = coords[2 * plane_out + lin[u]];
         } else {
-            cz[u] = identity_coord(z, inz); cy[u] = identity_coord(y, iny); cx[u] = identity_coord(x, inx);
+            cz[u] = identity_coord(z, inz); cy[u] = identity_coord(v.y, iny); cx[u] = identity_coord(v.x, inx);
         }
     }
-    Taps t[U];
+    Tap t[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) make_taps(cz[u], cy[u], cx[u], d, h, w, t[u]);
+    for (int u = 0; u < U; ++u) make_tap(cz[u], cy[u], cx[u], d, h, w, t[u]);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         float r[U];
@@ -140,25 +175,10 @@ sample_kernel(const float* __restrict__ src, int C_rt, int d, int h, int w,
 // reduces the bounding box of their corners over the block (DPP wave reductions + 24 words of LDS), and -- when the box fits kBrickCap floats
 // (a per-brick test; on the spec's field a 512-voxel brick's box is ~3.5 x the brick) -- copies the box into LDS by LDS-DMA (the box as one linear
 // list, 64 lanes per global_load_lds_dword: a row of the box is one or two cache lines, ~3 x fewer tag lookups per voxel than the gathers) and
-// takes the eight corners from LDS (ds_read2_b32 pairs), in gather8's order: bit-identical results.  A brick whose box does not fit (a fold, a
+// takes the eight corners from LDS (ds_read2_b32 pairs), in gather8's order (accumulate8): bit-identical results.  A brick whose box does not fit (a fold, a
 // strong shear) runs gather8 on global memory as before.  Brick 16 x 8 x 4: coordinate / result rows are 64-byte runs, four rows per wave.
 constexpr int kBrickX = 16, kBrickY = 8, kBrickZ = 4;
 constexpr int kBrickCap = 3584;                                  // floats of LDS per block for the box (14 KB: eight blocks = 32 waves per CU; 24 KB measured the same)
-
-struct Corner { int x0, y0, y1, z0, z1; float wx0, wx1, wy0, wy1, wz0, wz1; };
-
-__device__ __forceinline__ void make_corner(float cz, float cy, float cx, int d, int h, int w, Corner& t) {      // make_taps, keeping the indices
-    const float iz = unnormalize_border(cz, d), iy = unnormalize_border(cy, h), ix = unnormalize_border(cx, w);
-    const float fz0 = floorf(iz), fy0 = floorf(iy), fx0 = floorf(ix);
-    t.z0 = (int)fz0; t.y0 = (int)fy0;
-    int x0 = (int)fx0;
-    float wx1 = ix - fx0, wx0 = (fx0 + 1.0f) - ix;
-    if (x0 > w - 2) { x0 = w - 2; wx0 = 0.0f; wx1 = 1.0f; }
-    t.x0 = x0; t.wx0 = wx0; t.wx1 = wx1;
-    t.wy1 = iy - fy0; t.wy0 = (fy0 + 1.0f) - iy;
-    t.wz1 = iz - fz0; t.wz0 = (fz0 + 1.0f) - iz;
-    t.z1 = min(t.z0 + 1, d - 1); t.y1 = min(t.y0 + 1, h - 1);
-}
 
 // maximum of an int over the wave (every lane gets it): six DPP steps + a readlane (see wave_max_nonneg in unet_sres.h)
 __device__ __forceinline__ int wave_max_i32(int v) {
@@ -174,19 +194,6 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 
-__device__ __forceinline__ float corners8(float a00, float b00, float a01, float b01, float a10, float b10, float a11, float b11, const Corner& t) {
-    float acc = 0.0f;                                   // gather8's order and weight products
-    acc += a00 * (t.wx0 * t.wy0 * t.wz0);
-    acc += b00 * (t.wx1 * t.wy0 * t.wz0);
-    acc += a01 * (t.wx0 * t.wy1 * t.wz0);
-    acc += b01 * (t.wx1 * t.wy1 * t.wz0);
-    acc += a10 * (t.wx0 * t.wy0 * t.wz1);
-    acc += b10 * (t.wx1 * t.wy0 * t.wz1);
-    acc += a11 * (t.wx0 * t.wy1 * t.wz1);
-    acc += b11 * (t.wx1 * t.wy1 * t.wz1);
-    return acc;
-}
-
 template <int MODE, int CT>
 __global__ void __launch_bounds__(kThreads)
 sample_brick_kernel(const float* __restrict__ src, int d, int h, int w, const float* __restrict__ coords, int D, int H, int W,
@@ -195,17 +202,15 @@ sample_brick_kernel(const float* __restrict__ src, int d, int h, int w, const fl
     __shared__ int red[4][6];
     const int plane_out = D * H * W, plane_src = d * h * w;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nb = nbx * nby * nbz;
-    const int per = (nb + 7) >> 3;                                   // one contiguous run of bricks per XCD (see sample_kernel)
-    const int logical = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
-    if (((int)blockIdx.x >> 3) >= per || logical >= nb) return;
+    int logical;
+    if (!dealt_block(nbx * nby * nbz, logical)) return;
     const int bx = logical % nbx, by = (logical / nbx) % nby, bz = logical / (nbx * nby);
     const int x = bx * kBrickX + (tid & 15), y = by * kBrickY + ((tid >> 4) & 7);
     constexpr int U = 2;                                             // voxels per thread: z = 2 (tid >> 7) + u
     int lin[U];
     bool ok[U];
     float cz[U], cy[U], cx[U];
-    Corner t[U];
+    Tap t[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int z = bz * kBrickZ + 2 * (tid >> 7) + u;
@@ -215,7 +220,7 @@ sample_brick_kernel(const float* __restrict__ src, int d, int h, int w, const fl
         else { cz[u] = identity_coord(z, inz); cy[u] = identity_coord(y, iny); cx[u] = identity_coord(x, inx); }
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) make_corner(cz[u], cy[u], cx[u], d, h, w, t[u]);
+    for (int u = 0; u < U; ++u) make_tap(cz[u], cy[u], cx[u], d, h, w, t[u]);
     // ---- bounding box of the corners of the brick's REAL voxels: [xlo, xhi] x [ylo, yhi] x [zlo, zhi] (all maxima: lows negated)
     constexpr int kNone = -(1 << 30);
     int m[6] = {kNone, kNone, kNone, kNone, kNone, kNone};
@@ -276,16 +281,16 @@ sample_brick_kernel(const float* __restrict__ src, int d, int h, int w, const fl
                 const int bxo = t[u].x0 - xlo;
                 const int r00 = ((t[u].z0 - zlo) * ny + (t[u].y0 - ylo)) * nx + bxo, r01 = ((t[u].z0 - zlo) * ny + (t[u].y1 - ylo)) * nx + bxo;
                 const int r10 = ((t[u].z1 - zlo) * ny + (t[u].y0 - ylo)) * nx + bxo, r11 = ((t[u].z1 - zlo) * ny + (t[u].y1 - ylo)) * nx + bxo;
-                r[u] = ok[u] ? corners8(box[r00], box[r00 + 1], box[r01], box[r01 + 1], box[r10], box[r10 + 1], box[r11], box[r11 + 1], t[u]) : 0.0f;
+                r[u] = ok[u] ? accumulate8(box[r00], box[r00 + 1], box[r01], box[r01 + 1], box[r10], box[r10 + 1], box[r11], box[r11 + 1], t[u]) : 0.0f;
             }
-        } else {
+        } else {                                                     // gather8 with its addresses kept as two pointer steps per pair, as this kernel had them
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const pair_f32 p00 = *reinterpret_cast<const pair_f32*>(plane + (t[u].z0 * h + t[u].y0) * w + t[u].x0);
                 const pair_f32 p01 = *reinterpret_cast<const pair_f32*>(plane + (t[u].z0 * h + t[u].y1) * w + t[u].x0);
                 const pair_f32 p10 = *reinterpret_cast<const pair_f32*>(plane + (t[u].z1 * h + t[u].y0) * w + t[u].x0);
                 const pair_f32 p11 = *reinterpret_cast<const pair_f32*>(plane + (t[u].z1 * h + t[u].y1) * w + t[u].x0);
-                r[u] = corners8(p00.a, p00.b, p01.a, p01.b, p10.a, p10.b, p11.a, p11.b, t[u]);
+                r[u] = accumulate8(p00.a, p00.b, p01.a, p01.b, p10.a, p10.b, p11.a, p11.b, t[u]);
             }
         }
 #pragma unroll
@@ -321,25 +326,19 @@ struct ChainArgs {
 template <bool WARP>
 __global__ void __launch_bounds__(kThreads)
 chain_kernel(const ChainArgs a) {
-    constexpr int U = OAI_WARP_U;
-    const int D = a.D, H = a.H, W = a.W;
-    const int plane_out = D * H * W;
-    const int tx = threadIdx.x & 31, ty = (threadIdx.x >> 5) & 3, tz = threadIdx.x >> 7;
-    const int nb = a.nbx * a.nby * a.nbz;
-    const int per = (nb + 7) >> 3;
-    const int logical = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
-    if (((int)blockIdx.x >> 3) >= per || logical >= nb) return;
-    const int bx = logical % a.nbx, by = (logical / a.nbx) % a.nby, bz = logical / (a.nbx * a.nby);
-    const int x = bx * 32 + tx, y = by * 4 + ty;
+    constexpr int U = kWarpU;
+    const int plane_out = a.D * a.H * a.W;
+    int logical;
+    if (!dealt_block(a.nbx * a.nby * a.nbz, logical)) return;
+    const BrickLane v(logical, a.nbx, a.nby);
     int lin[U];
     bool ok[U];
     float c[3][U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const int z = (bz * U + u) * 2 + tz;
-        ok[u] = x < W && y < H && z < D;
-        lin[u] = ok[u] ? (z * H + y) * W + x : 0;
-        c[0][u] = identity_coord(z, a.inz); c[1][u] = identity_coord(y, a.iny); c[2][u] = identity_coord(x, a.inx);
+        int z;
+        ok[u] = v.voxel(u, a.D, a.H, a.W, z, lin[u]);
+        c[0][u] = identity_coord(z, a.inz); c[1][u] = identity_coord(v.y, a.iny); c[2][u] = identity_coord(v.x, a.inx);
         if (a.start) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) c[k][u] = c[k][u] + a.start[k * plane_out + lin[u]];      // add_identity_kernel: id + disp
@@ -351,9 +350,9 @@ chain_kernel(const ChainArgs a) {
     for (int i = 0; i < a.nf; ++i) {
         {
             const int plane = a.fd[i] * a.fh[i] * a.fw[i];
-            Taps t[U];
+            Tap t[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) make_taps(c[0][u], c[1][u], c[2][u], a.fd[i], a.fh[i], a.fw[i], t[u]);
+            for (int u = 0; u < U; ++u) make_tap(c[0][u], c[1][u], c[2][u], a.fd[i], a.fh[i], a.fw[i], t[u]);
             float g[3][U];
 #pragma unroll
             for (int k = 0; k < 3; ++k)
@@ -366,9 +365,9 @@ chain_kernel(const ChainArgs a) {
         }
     }
     if constexpr (WARP) {
-        Taps t[U];
+        Tap t[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) make_taps(c[0][u], c[1][u], c[2][u], a.id, a.ih, a.iw, t[u]);
+        for (int u = 0; u < U; ++u) make_tap(c[0][u], c[1][u], c[2][u], a.id, a.ih, a.iw, t[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const float r = gather8(a.image, t[u]);
@@ -459,36 +458,18 @@ phi_to_disp_kernel(const float* __restrict__ phi, int D, int H, int W, double* _
         const int x = (int)(lin % W);
         const int y = (int)((lin / W) % H);
         const int z = (int)(lin / ((long long)W * H));
-        // fp32 like the reference: (phi - ident) then *= (shape - 1), then .double()
-        const float dz = (phi[lin] - identity_coord(z, inz)) * (float)(D - 1);
-        const float dy = (phi[plane + lin] - identity_coord(y, iny)) * (float)(H - 1);
-        const float dx = (phi[2 * plane + lin] - identity_coord(x, inx)) * (float)(W - 1);
-        double* o = disp + 3 * lin;
-        o[0] = (double)dx; o[1] = (double)dy; o[2] = (double)dz;
+        double* o = disp + 3 * lin;                      // ITK component c (x, y, z) = phi channel 2 - c (w, h, d)
+        o[0] = itk_disp(phi[2 * plane + lin], identity_coord(x, inx), (float)(W - 1));
+        o[1] = itk_disp(phi[plane + lin], identity_coord(y, iny), (float)(H - 1));
+        o[2] = itk_disp(phi[lin], identity_coord(z, inz), (float)(D - 1));
     }
-}
-
-struct Affine { double A[9]; double b[3]; };
-
-__device__ __forceinline__ void apply(const Affine& t, double x, double y, double z, double& ox, double& oy, double& oz) {
-    ox = t.A[0] * x + t.A[1] * y + t.A[2] * z + t.b[0];
-    oy = t.A[3] * x + t.A[4] * y + t.A[5] * z + t.b[1];
-    oz = t.A[6] * x + t.A[7] * y + t.A[8] * z + t.b[2];
-}
-
-__device__ __forceinline__ void clamp_split(double c, int n, int& i0, int& i1, double& f) {
-    c = fmin(fmax(c, 0.0), (double)(n - 1));
-    const double fl = floor(c);
-    i0 = (int)fl;
-    i1 = min(i0 + 1, n - 1);
-    f = c - fl;
 }
 
 // fused K19: B index -> network space -> + trilinear(disp) -> A index -> trilinear(prob), fp64 coordinates
 __global__ void __launch_bounds__(kThreads)
 resample_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
                 const double* __restrict__ disp, int Dn, int Hn, int Wn,
-                Affine b2n, Affine n2a, float* __restrict__ out, int nzB, int nyB, int nxB) {
+                oai_affine b2n, oai_affine n2a, float* __restrict__ out, int nzB, int nyB, int nxB) {
     const long long n = (long long)nzB * nyB * nxB;
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
         const int xb = (int)(i % nxB);
@@ -496,8 +477,7 @@ resample_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
         const int zb = (int)(i / ((long long)nxB * nyB));
         double nx_, ny_, nz_;
         apply(b2n, (double)xb, (double)yb, (double)zb, nx_, ny_, nz_);
-        const bool inside = nx_ >= -0.5 && nx_ < Wn - 0.5 && ny_ >= -0.5 && ny_ < Hn - 0.5 && nz_ >= -0.5 && nz_ < Dn - 0.5;
-        if (inside) {
+        if (inside_buffer(nx_, ny_, nz_, Wn, Hn, Dn)) {
             int x0, x1, y0, y1, z0, z1;
             double fx, fy, fz;
             clamp_split(nx_, Wn, x0, x1, fx);
@@ -506,37 +486,33 @@ resample_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
             double acc[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                auto at = [&](int zz, int yy, int xx) { return disp[(((long long)zz * Hn + yy) * Wn + xx) * 3 + c]; };
-                const double c00 = at(z0, y0, x0) * (1 - fx) + at(z0, y0, x1) * fx;
-                const double c01 = at(z0, y1, x0) * (1 - fx) + at(z0, y1, x1) * fx;
-                const double c10 = at(z1, y0, x0) * (1 - fx) + at(z1, y0, x1) * fx;
-                const double c11 = at(z1, y1, x0) * (1 - fx) + at(z1, y1, x1) * fx;
-                acc[c] = (c00 * (1 - fy) + c01 * fy) * (1 - fz) + (c10 * (1 - fy) + c11 * fy) * fz;
+                auto at = [&](bool zhi, bool yhi, bool xhi) {
+                    return disp[(((long long)(zhi ? z1 : z0) * Hn + (yhi ? y1 : y0)) * Wn + (xhi ? x1 : x0)) * 3 + c];
+                };
+                acc[c] = lerp8(at, fx, fy, fz);
             }
             nx_ += acc[0]; ny_ += acc[1]; nz_ += acc[2];
         }
         double ax, ay, az;
         apply(n2a, nx_, ny_, nz_, ax, ay, az);
         float r = 0.0f;
-        if (ax >= -0.5 && ax < nxA - 0.5 && ay >= -0.5 && ay < nyA - 0.5 && az >= -0.5 && az < nzA - 0.5) {
+        if (inside_buffer(ax, ay, az, nxA, nyA, nzA)) {
             int x0, x1, y0, y1, z0, z1;
             double fx, fy, fz;
             clamp_split(ax, nxA, x0, x1, fx);
             clamp_split(ay, nyA, y0, y1, fy);
             clamp_split(az, nzA, z0, z1, fz);
-            auto at = [&](int zz, int yy, int xx) { return (double)prob[((long long)zz * nyA + yy) * nxA + xx]; };
-            const double c00 = at(z0, y0, x0) * (1 - fx) + at(z0, y0, x1) * fx;
-            const double c01 = at(z0, y1, x0) * (1 - fx) + at(z0, y1, x1) * fx;
-            const double c10 = at(z1, y0, x0) * (1 - fx) + at(z1, y0, x1) * fx;
-            const double c11 = at(z1, y1, x0) * (1 - fx) + at(z1, y1, x1) * fx;
-            r = (float)((c00 * (1 - fy) + c01 * fy) * (1 - fz) + (c10 * (1 - fy) + c11 * fy) * fz);
+            auto at = [&](bool zhi, bool yhi, bool xhi) {
+                return (double)prob[((long long)(zhi ? z1 : z0) * nyA + (yhi ? y1 : y0)) * nxA + (xhi ? x1 : x0)];
+            };
+            r = (float)lerp8(at, fx, fy, fz);
         }
         out[i] = r;
     }
 }
 
 // K18 fused into K19, for all maps of a volume at once: the displacement the ITK transform would hold,
-//   disp[zyx][c] = double( (phi[2-c] - identity) * (n - 1) )   (fp32 arithmetic, then widened: exactly phi_to_disp_kernel),
+//   disp[zyx][c] = double( (phi[2-c] - identity) * (n - 1) )   (itk_disp of phi_field.h, as in phi_to_disp_kernel),
 // is rebuilt from phi's fp32 planes at the 8 corners instead of being read back as 24-byte fp64 triples, and the NM probability
 // maps share one coordinate computation (fp64, same operations in the same order as resample_kernel: bit-identical results).
 // Algorithmic bytes per atlas voxel: NM x (4 read + 4 written) + 12 x (network voxels / atlas voxels) of phi.
@@ -568,10 +544,9 @@ template <int NM>
 __global__ void __launch_bounds__(kRsThreads)
 resample_maps_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
                      const float* __restrict__ phi, int Dn, int Hn, int Wn,
-                     Affine b2n, Affine n2a, float* __restrict__ out, int nzB, int nyB, int nxB, unsigned nblocks, unsigned nxblk, RsInv inv) {
-    const unsigned per = (nblocks + 7u) >> 3;
-    const unsigned logical = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per || logical >= nblocks) return;
+                     oai_affine b2n, oai_affine n2a, float* __restrict__ out, int nzB, int nyB, int nxB, unsigned nblocks, unsigned nxblk, RsInv inv) {
+    unsigned logical;
+    if (!dealt_block(nblocks, logical)) return;
     const unsigned rowid = logical / nxblk, xblk = logical - rowid * nxblk;       // wave-uniform
     const int zb = (int)(rowid / (unsigned)nyB), yb = (int)(rowid - (unsigned)zb * (unsigned)nyB);
     const int xb = (int)(xblk * kRsThreads + threadIdx.x);
@@ -580,8 +555,7 @@ resample_maps_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
     const long long i = (long long)rowid * nxB + xb;
     double nx_, ny_, nz_;
     apply(b2n, (double)xb, (double)yb, (double)zb, nx_, ny_, nz_);
-    const bool inside = nx_ >= -0.5 && nx_ < Wn - 0.5 && ny_ >= -0.5 && ny_ < Hn - 0.5 && nz_ >= -0.5 && nz_ < Dn - 0.5;
-    if (inside) {
+    if (inside_buffer(nx_, ny_, nz_, Wn, Hn, Dn)) {
         int x0, x1, y0, y1, z0, z1;
         double fx, fy, fz;
         clamp_split(nx_, Wn, x0, x1, fx);
@@ -604,16 +578,12 @@ resample_maps_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
             // identity coordinate of the corner along this component's axis: two values per axis
             const float ia = c == 0 ? identity_coord(x0, inx) : c == 1 ? identity_coord(y0, iny) : identity_coord(z0, inz);
             const float ib = c == 0 ? identity_coord(x1, inx) : c == 1 ? identity_coord(y1, iny) : identity_coord(z1, inz);
-            auto at = [&](int r, bool zhi, bool yhi, bool xhi) {
+            auto at = [&](bool zhi, bool yhi, bool xhi) {
                 const float id = c == 0 ? (xhi ? ib : ia) : c == 1 ? (yhi ? ib : ia) : (zhi ? ib : ia);
-                const float v = xhi ? (ps.hi_hi ? q[c][r].y : q[c][r].x) : (ps.lo_hi ? q[c][r].y : q[c][r].x);
-                return (double)((v - id) * sc);
+                const float2 p = q[c][2 * zhi + yhi];
+                return itk_disp(xhi ? (ps.hi_hi ? p.y : p.x) : (ps.lo_hi ? p.y : p.x), id, sc);
             };
-            const double c00 = at(0, 0, 0, 0) * (1 - fx) + at(0, 0, 0, 1) * fx;
-            const double c01 = at(1, 0, 1, 0) * (1 - fx) + at(1, 0, 1, 1) * fx;
-            const double c10 = at(2, 1, 0, 0) * (1 - fx) + at(2, 1, 0, 1) * fx;
-            const double c11 = at(3, 1, 1, 0) * (1 - fx) + at(3, 1, 1, 1) * fx;
-            acc[c] = (c00 * (1 - fy) + c01 * fy) * (1 - fz) + (c10 * (1 - fy) + c11 * fy) * fz;
+            acc[c] = lerp8(at, fx, fy, fz);
         }
         nx_ += acc[0]; ny_ += acc[1]; nz_ += acc[2];
     }
@@ -622,7 +592,7 @@ resample_maps_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
     float r[NM];
 #pragma unroll
     for (int m = 0; m < NM; ++m) r[m] = 0.0f;
-    if (ax >= -0.5 && ax < nxA - 0.5 && ay >= -0.5 && ay < nyA - 0.5 && az >= -0.5 && az < nzA - 0.5) {
+    if (inside_buffer(ax, ay, az, nxA, nyA, nzA)) {
         int x0, x1, y0, y1, z0, z1;
         double fx, fy, fz;
         clamp_split(ax, nxA, x0, x1, fx);
@@ -640,23 +610,15 @@ resample_maps_kernel(const float* __restrict__ prob, int nzA, int nyA, int nxA,
         }
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
-            auto lo = [&](int k) { return (double)(ps.lo_hi ? v[m][k].y : v[m][k].x); };
-            auto hi = [&](int k) { return (double)(ps.hi_hi ? v[m][k].y : v[m][k].x); };
-            const double c00 = lo(0) * (1 - fx) + hi(0) * fx;
-            const double c01 = lo(1) * (1 - fx) + hi(1) * fx;
-            const double c10 = lo(2) * (1 - fx) + hi(2) * fx;
-            const double c11 = lo(3) * (1 - fx) + hi(3) * fx;
-            r[m] = (float)((c00 * (1 - fy) + c01 * fy) * (1 - fz) + (c10 * (1 - fy) + c11 * fy) * fz);
+            auto at = [&](bool zhi, bool yhi, bool xhi) {
+                const float2 p = v[m][2 * zhi + yhi];
+                return (double)((xhi ? ps.hi_hi : ps.lo_hi) ? p.y : p.x);
+            };
+            r[m] = (float)lerp8(at, fx, fy, fz);
         }
     }
 #pragma unroll
     for (int m = 0; m < NM; ++m) __builtin_nontemporal_store(r[m], out + m * n + i);
-}
-
-inline unsigned grid_for(long long work_items) {
-    long long blocks = (work_items + kThreads - 1) / kThreads;
-    const long long cap = 256LL * 16;            // 256 CUs x 16 blocks: grid-stride beyond that
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
 }
 
 int g_warp_brick = 0;        // option "brick" (oai_warp_set_option): 1 = image warps / composes through sample_brick_kernel when the grids allow it
@@ -668,7 +630,7 @@ int launch_sample(const float* src, int C, int d, int h, int w, const float* coo
         const int nbx = (W + kBrickX - 1) / kBrickX, nby = (H + kBrickY - 1) / kBrickY, nbz = (D + kBrickZ - 1) / kBrickZ;
         const long long nb = (long long)nbx * nby * nbz;
         if (nb <= (1LL << 28)) {
-            const unsigned grid = (unsigned)(((nb + 7) / 8) * 8);
+            const unsigned grid = dealt_grid(nb);
             const double inz = 1.0 / (D - 1), iny = 1.0 / (H - 1), inx = 1.0 / (W - 1);
             if (C == 1) sample_brick_kernel<MODE, 1><<<grid, kThreads, 0, s>>>(src, d, h, w, coords, D, H, W, out, nbx, nby, nbz, inz, iny, inx);
             else sample_brick_kernel<MODE, 3><<<grid, kThreads, 0, s>>>(src, d, h, w, coords, D, H, W, out, nbx, nby, nbz, inz, iny, inx);
@@ -676,13 +638,12 @@ int launch_sample(const float* src, int C, int d, int h, int w, const float* coo
             return OAI_OK;
         }
     }
-    const int nbx = (W + 31) / 32, nby = (H + 3) / 4, nbz = ((D + 1) / 2 + OAI_WARP_U - 1) / OAI_WARP_U;
-    const long long nb = (long long)nbx * nby * nbz;
-    if (nb > (1LL << 28)) return oai::set_error(OAI_ERR_ARG, "volume too large for the sample grid");
-    const unsigned grid = (unsigned)(((nb + 7) / 8) * 8);                  // 8 XCD runs of ceil(nb/8) bricks
+    const BrickGrid g = brick_grid(D, H, W);
+    if (g.nb > (1LL << 28)) return oai::set_error(OAI_ERR_ARG, "volume too large for the sample grid");
+    const unsigned grid = dealt_grid(g.nb);
     const long long big = (long long)C * D * H * W > (long long)C * d * h * w ? (long long)C * D * H * W : (long long)C * d * h * w;
     const double inz = 1.0 / (D - 1), iny = 1.0 / (H - 1), inx = 1.0 / (W - 1);
-#define OAI_SAMPLE(IDX, CT) sample_kernel<MODE, IDX, CT><<<grid, kThreads, 0, s>>>(src, C, d, h, w, coords, D, H, W, out, nbx, nby, nbz, inz, iny, inx)
+#define OAI_SAMPLE(IDX, CT) sample_kernel<MODE, IDX, CT><<<grid, kThreads, 0, s>>>(src, C, d, h, w, coords, D, H, W, out, g.nbx, g.nby, g.nbz, inz, iny, inx)
     if (big < (1LL << 31)) { if (C == 1) OAI_SAMPLE(int, 1); else if (C == 3) OAI_SAMPLE(int, 3); else OAI_SAMPLE(int, 0); }
     else OAI_SAMPLE(long long, 0);
 #undef OAI_SAMPLE
@@ -716,7 +677,7 @@ int oai_compose(const float* disp, int d, int h, int w, const float* coords, int
     OAI_CHECK_ARG(disp && out, "oai_compose: null pointer");
     OAI_CHECK_ARG(d > 1 && h > 1 && w > 1 && D > 1 && H > 1 && W > 1, "oai_compose: sizes must be > 1");
     if (!coords && shortcut && d == D && h == H && w == W) {
-        add_identity_kernel<<<grid_for((long long)D * H * W), kThreads, 0, (hipStream_t)stream>>>(disp, D, H, W, out);
+        add_identity_kernel<<<grid_stride_blocks((long long)D * H * W, kThreads), kThreads, 0, (hipStream_t)stream>>>(disp, D, H, W, out);
         OAI_CHECK_LAUNCH();
         return OAI_OK;
     }
@@ -741,10 +702,10 @@ int oai_warp_chain(const float* start, int D, int H, int W, int n_fields, const 
     a.image = image; a.id = id; a.ih = ih; a.iw = iw;
     if (image) OAI_CHECK_ARG(id > 1 && ih > 1 && iw > 1 && (long long)id * ih * iw < (1LL << 31), "oai_warp_chain: bad image size");
     a.out = out; a.D = D; a.H = H; a.W = W;
-    a.nbx = (W + 31) / 32; a.nby = (H + 3) / 4; a.nbz = ((D + 1) / 2 + OAI_WARP_U - 1) / OAI_WARP_U;
+    const BrickGrid g = brick_grid(D, H, W);
+    a.nbx = g.nbx; a.nby = g.nby; a.nbz = g.nbz;
     a.inz = 1.0 / (D - 1); a.iny = 1.0 / (H - 1); a.inx = 1.0 / (W - 1);
-    const long long nb = (long long)a.nbx * a.nby * a.nbz;
-    const unsigned grid = (unsigned)(((nb + 7) / 8) * 8);
+    const unsigned grid = dealt_grid(g.nb);
     if (image) chain_kernel<true><<<grid, kThreads, 0, (hipStream_t)stream>>>(a);
     else chain_kernel<false><<<grid, kThreads, 0, (hipStream_t)stream>>>(a);
     OAI_CHECK_LAUNCH();
@@ -754,21 +715,21 @@ int oai_warp_chain(const float* start, int D, int H, int W, int n_fields, const 
 int oai_avgpool2_3d(const float* in, int C, int D, int H, int W, float* out, void* stream) {
     OAI_CHECK_ARG(in && out && C > 0 && D > 0 && H > 0 && W > 0, "oai_avgpool2_3d: bad arguments");
     const int Do = (D + 1) / 2, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    avgpool2_kernel<<<grid_for((long long)C * Do * Ho * Wo), kThreads, 0, (hipStream_t)stream>>>(in, C, D, H, W, out, Do, Ho, Wo);
+    avgpool2_kernel<<<grid_stride_blocks((long long)C * Do * Ho * Wo, kThreads), kThreads, 0, (hipStream_t)stream>>>(in, C, D, H, W, out, Do, Ho, Wo);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
 
 int oai_resize_trilinear(const float* in, int C, int d, int h, int w, float* out, int D, int H, int W, void* stream) {
     OAI_CHECK_ARG(in && out && C > 0 && d > 0 && h > 0 && w > 0 && D > 0 && H > 0 && W > 0, "oai_resize_trilinear: bad arguments");
-    resize_trilinear_kernel<<<grid_for((long long)C * D * H * W), kThreads, 0, (hipStream_t)stream>>>(in, C, d, h, w, out, D, H, W);
+    resize_trilinear_kernel<<<grid_stride_blocks((long long)C * D * H * W, kThreads), kThreads, 0, (hipStream_t)stream>>>(in, C, d, h, w, out, D, H, W);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
 
 int oai_phi_to_itk_displacement(const float* phi, int D, int H, int W, double* disp, void* stream) {
     OAI_CHECK_ARG(phi && disp && D > 1 && H > 1 && W > 1, "oai_phi_to_itk_displacement: bad arguments");
-    phi_to_disp_kernel<<<grid_for((long long)D * H * W), kThreads, 0, (hipStream_t)stream>>>(phi, D, H, W, disp);
+    phi_to_disp_kernel<<<grid_stride_blocks((long long)D * H * W, kThreads), kThreads, 0, (hipStream_t)stream>>>(phi, D, H, W, disp);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
@@ -779,11 +740,8 @@ int oai_resample_through_disp(const float* prob, int nzA, int nyA, int nxA, cons
     OAI_CHECK_ARG(prob && disp && b2n && n2a && out, "oai_resample_through_disp: null pointer");
     OAI_CHECK_ARG(nzA > 0 && nyA > 0 && nxA > 0 && Dn > 0 && Hn > 0 && Wn > 0 && nzB > 0 && nyB > 0 && nxB > 0,
                   "oai_resample_through_disp: bad sizes");
-    Affine a, b;
-    memcpy(&a, b2n, sizeof(Affine));
-    memcpy(&b, n2a, sizeof(Affine));
-    resample_kernel<<<grid_for((long long)nzB * nyB * nxB), kThreads, 0, (hipStream_t)stream>>>(
-        prob, nzA, nyA, nxA, disp, Dn, Hn, Wn, a, b, out, nzB, nyB, nxB);
+    resample_kernel<<<grid_stride_blocks((long long)nzB * nyB * nxB, kThreads), kThreads, 0, (hipStream_t)stream>>>(
+        prob, nzA, nyA, nxA, disp, Dn, Hn, Wn, *b2n, *n2a, out, nzB, nyB, nxB);
     OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
@@ -796,16 +754,13 @@ int oai_resample_maps_through_phi(const float* probs, int n_maps, int nzA, int n
                   "oai_resample_maps_through_phi: bad sizes");
     OAI_CHECK_ARG((long long)Dn * Hn * Wn < (1LL << 31), "oai_resample_maps_through_phi: network grid too large");
     OAI_CHECK_ARG(nxA >= 2, "oai_resample_maps_through_phi: maps need at least two voxels per row (the x corners are loaded as pairs)");
-    Affine a, b;
-    memcpy(&a, b2n, sizeof(Affine));
-    memcpy(&b, n2a, sizeof(Affine));
     const long long nxblk = (nxB + kRsThreads - 1) / kRsThreads;
     const long long nblocks = (long long)nzB * nyB * nxblk;                       // one block = <= kRsThreads voxels of one output row
     OAI_CHECK_ARG(nblocks < (1LL << 31) - 8 && (long long)nzB * nyB < (1LL << 31), "oai_resample_maps_through_phi: output grid too large");
-    const unsigned grid = (unsigned)(((nblocks + 7) / 8) * 8);
+    const unsigned grid = dealt_grid(nblocks);
     hipStream_t st = (hipStream_t)stream;
     const RsInv inv{1.0 / (Dn - 1), 1.0 / (Hn - 1), 1.0 / (Wn - 1)};             // mermaidlite.identity_map's spacing, in double
-#define OAI_RS(NM) resample_maps_kernel<NM><<<grid, kRsThreads, 0, st>>>(probs, nzA, nyA, nxA, phi, Dn, Hn, Wn, a, b, out, nzB, nyB, nxB, (unsigned)nblocks, (unsigned)nxblk, inv)
+#define OAI_RS(NM) resample_maps_kernel<NM><<<grid, kRsThreads, 0, st>>>(probs, nzA, nyA, nxA, phi, Dn, Hn, Wn, *b2n, *n2a, out, nzB, nyB, nxB, (unsigned)nblocks, (unsigned)nxblk, inv)
     if (n_maps == 1) OAI_RS(1); else if (n_maps == 2) OAI_RS(2); else if (n_maps == 3) OAI_RS(3); else OAI_RS(4);
 #undef OAI_RS
     OAI_CHECK_LAUNCH();

@@ -22,7 +22,11 @@ EPS32 = float(np.finfo(np.float32).eps)
 
 def det_ref(phi: np.ndarray) -> np.ndarray:
     """float64 [D-1,H-1,W-1]: J[r][k] = delta_rk + (u_r(p) - u_r(p - e_k)), r and k over (x, y, z); a NaN / Inf in phi goes where it goes."""
-    u = ref.displacement(phi)                                  # [D,H,W,3], xyz components
+    return det_of_displacement(ref.displacement(phi))
+
+
+def det_of_displacement(u: np.ndarray) -> np.ndarray:
+    """``det_ref`` after the rebuild: the same stencil on a given displacement float64 [D,H,W,3] (xyz components, network voxels)."""
     c = u[1:, 1:, 1:]
     with np.errstate(invalid="ignore", over="ignore"):
         dx, dy, dz = c - u[1:, 1:, :-1], c - u[1:, :-1, 1:], c - u[:-1, 1:, 1:]

@@ -74,6 +74,16 @@ def test_determinant_map_and_stats_against_the_restatement(shape, amp):
         assert s[1] == 0 and s[2] == 0 and s[3] == 1.0 and s[4] == 1.0 and s[5] == s[0] and s[6] == s[0]
 
 
+@pytest.mark.parametrize("shape", [(3, 4, 5), (17, 33, 29)])
+def test_determinant_map_is_the_stencil_on_the_stored_displacement(shape):
+    """The displacement that phi_jacobian_kernel rebuilds is the one oai_phi_to_itk_displacement stores: the numpy stencil on the stored
+    fp64 field rounds to the kernel's map bit for bit."""
+    phi = torch.from_numpy(pj.drawn_phi(shape, 0.45)).cuda()
+    u = ops.phi_to_itk_displacement(phi).cpu().numpy()
+    _, got = ops.phi_jacobian(phi, return_map=True)
+    assert np.array_equal(got.cpu().numpy(), pj.det_of_displacement(u).astype(np.float32))
+
+
 def test_production_shape(production):
     phi, det = production
     assert np.abs(det).min() >= 1e-5

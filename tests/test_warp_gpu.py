@@ -122,6 +122,37 @@ def test_phi_to_displacement_and_resample():
     assert np.abs(got - ref).max() < 1e-5
 
 
+@pytest.fixture(scope="module", params=[((5, 7, 9), 0.05), ((5, 7, 9), 0.4), ((20, 48, 44), 0.05), ((20, 48, 44), 0.4)],
+                ids=lambda p: f"net{p[0]}-amp{p[1]}")
+def separate_path(request):
+    """Four small maps on a rotated A / B pair pulled through a smooth phi by the separate path, once per (network shape, amplitude):
+    the stored displacement (phi_to_itk_displacement), then resample_through_disp per map.  B rows are 130 voxels: two x blocks of the
+    fused kernel with a two-voxel tail.  At amplitude 0.4 many corners clamp at the ends of A's rows."""
+    from oai_analysis_2_amd import ops
+    from oai_analysis_2_amd.image import Image
+    from oai_analysis_2_amd.registration import resample_affines
+    net, amp = request.param
+    phi = (oicon.identity_map(net) + torch.from_numpy(make_smooth_field(2, net, amp))[None])[0].cuda()
+    th = 0.1
+    rot = np.array([[np.cos(th), -np.sin(th), 0], [np.sin(th), np.cos(th), 0], [0, 0, 1.0]])
+    A = Image(np.zeros((9, 14, 13), np.float32), [1.0, 0.9, 1.4], [1.0, 2.0, 3.0])
+    B = Image(np.zeros((6, 5, 130), np.float32), [0.11, 2.4, 2.0], [0.0, 1.5, 3.5], rot)
+    b2n, n2a = resample_affines(A, B, net)
+    maps = _dev(np.stack([make_volume(10 + m, A.array.shape) for m in range(4)]))
+    disp = ops.phi_to_itk_displacement(phi)
+    want = torch.stack([ops.resample_through_disp(maps[m], disp, b2n, n2a, B.array.shape) for m in range(4)])
+    assert (want == 0).any() and (want != 0).any()      # the outside-buffer default pixel is among the outputs
+    return phi, maps, b2n, n2a, B.array.shape, want
+
+
+@pytest.mark.parametrize("n_maps", [1, 2, 3, 4])
+def test_resample_maps_through_phi_is_bit_identical_to_the_separate_path(separate_path, n_maps):
+    from oai_analysis_2_amd import ops
+    phi, maps, b2n, n2a, out_shape, want = separate_path
+    got = ops.resample_maps_through_phi(maps[:n_maps].contiguous(), phi, b2n, n2a, out_shape)
+    assert torch.equal(got, want[:n_maps])
+
+
 @pytest.mark.parametrize("shape", [(20, 44, 36), (17, 33, 29), (80, 192, 192)])
 def test_fused_warp_chain_is_bit_identical_to_the_op_by_op_closures(shape):
     """oai_warp_chain (SURVEY K15 "fuse chains", K18) against the sequence of compose / grid_sample3d launches it replaces in
