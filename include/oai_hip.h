@@ -653,6 +653,45 @@ size_t oai_mask_overlap_workspace_bytes(long long n);
 int oai_mask_overlap(const float* a_dev, const float* b_dev, long long n, float threshold, void* workspace_dev, size_t workspace_bytes,
                      long long* counts_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The inverse of phi (csrc/phi_inverse.hip, tests/phi_inverse_ref.py): patient (A) points taken to the atlas (B), the direction phi
+ * does not provide.  A numerical inverse of the map that is held, exact up to a stated residual: what itk.Transform.GetInverseTransform
+ * means for a displacement field, restated from ITK's documented behaviour and unpinned (ITK absent); not the network's phi_BA.
+ * The forward map in network index space is that of oai_transform_points_through_phi,
+ *   T(x) = x + (inside(x) ? u(x) : 0),   u = itk_disp at the 8 clamped corners lerped along x, then y, then z,
+ * and one device solver finds x with T(x) = y, in fp64 without contraction:
+ *   x = y;  at most max_iter times:
+ *     d, G = u(x), grad u(x) when inside(x), else zero; G is the exact gradient of the trilinear interpolant from the same 8 corners
+ *            (the column of an axis that clamp_split clamped is zero);
+ *     r = (x + d) - y;  converged when max_c |r_c| <= tol;
+ *     J = I + G;  det as in oai_phi_jacobian;  s = J^-1 r by the adjugate when |det| > 1e-3, else s = r (a fixed-point step);
+ *     stop as unconverged when a component of s is not finite, else x -= s.
+ * Status per point: 1 = converged with x inside the buffer; 2 = converged at an x outside it, where T is the identity; 0 = not
+ * converged within max_iter, and the result is then x = y: the point is moved by the affines alone, the forward transform's convention
+ * for "outside".  Newton, because the plain fixed point diverges wherever phi stretches by a factor of 2 or more.  tol is in network
+ * voxels (1e-7 is two orders below the float32 quantum of a stored map, 2^-24 (n - 1)); max_iter >= 1 and tol > 0 are checked.
+ *
+ * oai_inverse_points_through_phi: out = float32(net_to_out(solve(point_to_net(p)))) per point p (float32 xyz); out_dev float32 [n][3];
+ * status_dev (may be null) one byte per point.  n = 0 is a successful no-op; an axis of phi below 2 voxels is an argument error.
+ * out_dev may not alias pts_dev.  Does not synchronise.
+ *
+ * oai_invert_phi: the dense inverse on phi's own lattice.  For every lattice point y, psi[2-c][y] = float32(x_c * (1/(n_c - 1))), phi's
+ * storage convention: psi is a phi, and oai_resample_maps_through_phi, oai_transform_points_through_phi and oai_phi_jacobian read it
+ * unchanged.  An unconverged point holds its identity coordinate.  psi_out_dev fp32 [3][D][H][W] (may not alias phi_dev);
+ * status_out_dev (may be null) [D][H][W] bytes.  stats_dev: double[6] on the device --
+ *   [0] points = D H W   [1] unconverged   [2] converged outside the buffer   [3] max |r| over the converged points
+ *   [4] sum over all points of the evaluations of T   [5] their maximum
+ * Per-block partials go to the workspace and a second kernel adds them in index order: no atomics, a block count that depends on the
+ * shape only, so the stats are bit-reproducible and do not depend on status_out_dev.  Does not synchronise.
+ * ---------------------------------------------------------------------------------------- */
+int oai_inverse_points_through_phi(const float* pts_dev, long long n, const float* phi_dev, int Dn, int Hn, int Wn,
+                                   const oai_affine* point_to_net, const oai_affine* net_to_out, int max_iter, double tol, float* out_dev,
+                                   unsigned char* status_dev, void* stream);
+/* 0 when an axis is below 2 voxels. */
+size_t oai_invert_phi_workspace_bytes(int D, int H, int W);
+int oai_invert_phi(const float* phi_dev, int D, int H, int W, int max_iter, double tol, float* psi_out_dev, unsigned char* status_out_dev,
+                   void* workspace_dev, size_t workspace_bytes, double* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,9 @@ SIGNATURES = {
     "oai_transform_points_through_phi": (_I, [_P, C.c_longlong, _P, _I, _I, _I, C.POINTER(Affine), C.POINTER(Affine), _P, _P, _P]),
     "oai_phi_jacobian_workspace_bytes": (_Z, [_I, _I, _I]),
     "oai_phi_jacobian": (_I, [_P, _I, _I, _I, _P, _P, _Z, _P, _P]),
+    "oai_inverse_points_through_phi": (_I, [_P, C.c_longlong, _P, _I, _I, _I, C.POINTER(Affine), C.POINTER(Affine), _I, _D, _P, _P, _P]),
+    "oai_invert_phi_workspace_bytes": (_Z, [_I, _I, _I]),
+    "oai_invert_phi": (_I, [_P, _I, _I, _I, _I, _D, _P, _P, _P, _Z, _P, _P]),
     "oai_mask_overlap_workspace_bytes": (_Z, [C.c_longlong]),
     "oai_mask_overlap": (_I, [_P, _P, C.c_longlong, _F, _P, _Z, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),

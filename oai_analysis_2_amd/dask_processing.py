@@ -167,14 +167,16 @@ def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, kee
     already finished on the host's side when they are handed over (CohortRunner(keep_on_device=True) synchronises each volume's event);
     otherwise an event is recorded on the consumer's current stream as each result arrives and the worker waits for it on the host.
     ``space``: "atlas" (default) = the distance on the atlas grid; "patient" = each knee's meshes pushed through its own ``phi`` with its
-    ``meta_A`` (ThicknessAtlas.measure(..., phi=, image_A=): the patient's own millimetres); a result without ``meta_A`` raises ValueError.
+    ``meta_A`` (ThicknessAtlas.measure(..., phi=, image_A=): the patient's own millimetres); "patient_grid" = native thickness, measured on
+    each knee's patient-grid ``fc`` / ``tc`` and carried to the atlas through the inverse of its ``phi`` (ThicknessAtlas.measure(...,
+    space="patient_grid")); in both, a result without ``meta_A`` raises ValueError.
     At most two knees are in flight; results come in input order; the worker is gone when the generator is exhausted or closed.
     Measured (profiles/thickness_stage.md section 3): about nine tenths of the stage lie underneath the next volume, unless the runtime
     deals the worker's stream onto the compute stream's own hardware queue (one creation order in four), where it runs serially."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
-    if space not in ("atlas", "patient"):
-        raise ValueError(f"space must be 'atlas' or 'patient', got {space!r}")
+    if space not in ("atlas", "patient", "patient_grid"):
+        raise ValueError(f"space must be 'atlas', 'patient' or 'patient_grid', got {space!r}")
     dev = thickness_atlas.device
     caller = torch.cuda.current_stream(dev)
     side = []                                                     # the worker's stream, created on the worker
@@ -189,12 +191,17 @@ def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, kee
                 res.fc_atlas.record_stream(side[0])
                 res.tc_atlas.record_stream(side[0])
                 push = {}
-                if space == "patient":
+                if space != "atlas":
                     if res.meta_A is None:
-                        raise ValueError("thickness_stream(space='patient'): a result carries no meta_A (the patient image's geometry)")
+                        raise ValueError(f"thickness_stream(space='{space}'): a result carries no meta_A (the patient image's geometry)")
                     res.phi.record_stream(side[0])
                     push = dict(phi=res.phi, image_A=res.meta_A)
-                knee = thickness_atlas.measure(res.fc_atlas, res.tc_atlas, keep_on_device=keep_on_device, **push)
+                if space == "patient_grid":
+                    res.fc.record_stream(side[0])
+                    res.tc.record_stream(side[0])
+                    knee = thickness_atlas.measure(res.fc, res.tc, keep_on_device=keep_on_device, space="patient_grid", **push)
+                else:
+                    knee = thickness_atlas.measure(res.fc_atlas, res.tc_atlas, keep_on_device=keep_on_device, **push)
                 if keep_on_device:
                     side[0].synchronize()                         # complete when handed over, like the input
                     knee.fc.record_stream(caller)
@@ -233,5 +240,6 @@ def qc_stream(results: Iterable[Tuple[int, object]], reference=None) -> Iterator
 def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None,
                              space: str = "atlas") -> Iterator[Tuple[int, object]]:
     """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the
-    probability maps never leave the device.  ``space``: see thickness_stream ("patient": every knee through its own phi)."""
+    probability maps never leave the device.  ``space``: see thickness_stream ("patient": every knee through its own phi; "patient_grid":
+    native thickness on every knee's own grid)."""
     return thickness_stream(process_cohort(images, atlas_image, worker, keep_on_device=True), thickness_atlas, results_complete=True, space=space)

@@ -616,7 +616,7 @@ def _thickness_inner_dev(vol: torch.Tensor, spacing_xyz, mesh_type: str, min_cel
 _COORDS = ("spacing", "physical")
 
 
-def mesh_point_affines(image_A, image_B, net_shape, coords_in: str = "spacing", coords_out: str = "spacing"):
+def mesh_point_affines(image_A, image_B, net_shape, coords_in: str = "spacing", coords_out: str = "spacing", inverse: bool = False):
     """The two affine legs around phi for POINTS, composed on the host in fp64 on top of registration.resample_affines:
 
         point_to_net : ``coords_in`` on image_B's grid -> B index -> network index space
@@ -624,10 +624,20 @@ def mesh_point_affines(image_A, image_B, net_shape, coords_in: str = "spacing", 
 
     "spacing" is get_mesh's convention, (x, y, z) * spacing with no origin or direction; "physical" is ITK's physical point,
     origin + direction @ (spacing * index), what get_mesh_from_probability_map returns.  ``image_A`` / ``image_B``: Images (metadata is
-    enough: spacing, origin, direction and the array's shape); ``net_shape`` = phi's (D, H, W).  Returns ((A, b), (A, b))."""
+    enough: spacing, origin, direction and the array's shape); ``net_shape`` = phi's (D, H, W).  Returns ((A, b), (A, b)).
+
+    ``inverse``: the legs of the OTHER direction, for the point solver (oai_inverse_points_through_phi): ``coords_in`` then refers to
+    image_A's grid and ``coords_out`` to image_B's, and the pair is the fp64 host inverse of the forward pair with the coordinates swapped,
+
+        point_to_net : ``coords_in`` on image_A's grid -> network index space      (the inverse of the forward net_to_out)
+        net_to_out   : network index space -> ``coords_out`` on image_B's grid     (the inverse of the forward point_to_net)"""
     for c in (coords_in, coords_out):
         if c not in _COORDS:
             raise ValueError(f"coords must be one of {_COORDS}, got {c!r}")
+    if inverse:
+        (P, p), (Q, q) = mesh_point_affines(image_A, image_B, net_shape, coords_out, coords_in)
+        Qi, Pi = np.linalg.inv(Q), np.linalg.inv(P)
+        return (Qi, -Qi @ q), (Pi, -Pi @ p)
     A, B = as_image(image_A), as_image(image_B)
     (A1, b1), (A2, b2) = resample_affines(A, B, tuple(int(v) for v in net_shape))
     if coords_in == "spacing":
@@ -649,7 +659,16 @@ def _transform_points_dev(points: torch.Tensor, phi: torch.Tensor, point_to_net,
     return ops.transform_points_through_phi(points, phi, point_to_net, net_to_out, return_inside=return_inside)
 
 
-def transform_mesh(mesh: Mesh, transform, image_A=None, image_B=None, coords_in: str = "spacing", coords_out: str = "spacing") -> Mesh:
+def _inverse_points_dev(points: torch.Tensor, phi: torch.Tensor, point_to_net, net_to_out, max_iter: int = 30, tol: float = 1e-7,
+                        return_status: bool = False):
+    """transform_mesh(..., inverse=True)'s vertex step on device tensors: float32 [n,3] in, float32 [n,3] out (and the uint8 status: 1
+    converged inside phi's buffer, 2 outside it, 0 not converged and moved by the affines alone), nothing downloaded.  The affines
+    from mesh_point_affines(..., inverse=True)."""
+    return ops.inverse_points_through_phi(points, phi, point_to_net, net_to_out, max_iter=max_iter, tol=tol, return_status=return_status)
+
+
+def transform_mesh(mesh: Mesh, transform, image_A=None, image_B=None, coords_in: str = "spacing", coords_out: str = "spacing",
+                   inverse: bool = False, max_iter: int = 30, tol: float = 1e-7) -> Mesh:
     """The mesh with its vertices pushed through the registration's map: from image_B's (the atlas') space to image_A's (the patient's),
     the direction phi provides.  What itk.transform_mesh_filter does with ``create_itk_transform``'s CompositeTransform -- the reference
     has no such call; restated from ITK's documented composite-transform behaviour, unpinned like the resample (oracle/resample.py):
@@ -657,7 +676,13 @@ def transform_mesh(mesh: Mesh, transform, image_A=None, image_B=None, coords_in:
 
     ``transform``: a registration.DisplacementTransform (it carries ``phi`` and both geometries), or a float32 [3,D,H,W] phi (array or
     device tensor, VolumeResult.phi) with ``image_A`` and ``image_B``.  ``coords_in`` / ``coords_out``: see mesh_point_affines; a mesh
-    written with meshwrite in "physical" coordinates overlays the patient's image.  Faces and point data are carried over unchanged."""
+    written with meshwrite in "physical" coordinates overlays the patient's image.  Faces and point data are carried over unchanged.
+
+    ``inverse``: the other direction, from image_A's (the patient's) space to image_B's (the atlas'), with the same ``transform``:
+    every vertex is solved for by Newton's method on phi itself (csrc/phi_inverse.hip), exact to ``tol`` network voxels; no stored
+    inverse is interpolated.  ``coords_in`` then refers to image_A's grid and ``coords_out`` to image_B's.  A vertex that does not
+    converge within ``max_iter`` (inside a fold of phi) is moved by the affines alone; _inverse_points_dev(..., return_status=True)
+    counts them.  Unpinned like the forward push: ITK is absent."""
     _lib.load()
     if isinstance(transform, DisplacementTransform):
         if transform.phi is None:
@@ -672,9 +697,10 @@ def transform_mesh(mesh: Mesh, transform, image_A=None, image_B=None, coords_in:
     shape = tuple(phi.shape)
     if len(shape) != 4 or shape[0] != 3:
         raise ValueError(f"transform_mesh: phi must be [3,D,H,W], got {shape}")
-    p2n, n2o = mesh_point_affines(image_A, image_B, shape[1:], coords_in, coords_out)
+    p2n, n2o = mesh_point_affines(image_A, image_B, shape[1:], coords_in, coords_out, inverse=inverse)
     phi_d = _dev(phi, np.float32)
-    out = _transform_points_dev(_dev(mesh.verts, np.float32, (3,), device=phi_d.device), phi_d, p2n, n2o)
+    verts = _dev(mesh.verts, np.float32, (3,), device=phi_d.device)
+    out = _inverse_points_dev(verts, phi_d, p2n, n2o, max_iter, tol) if inverse else _transform_points_dev(verts, phi_d, p2n, n2o)
     return Mesh(out.cpu().numpy(), mesh.faces.copy(), dict(mesh.point_data))
 
 

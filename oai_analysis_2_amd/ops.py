@@ -7,6 +7,7 @@ used on the product path.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
@@ -216,6 +217,83 @@ def transform_points_through_phi(points: torch.Tensor, phi: torch.Tensor, point_
     _lib.check(lib.oai_transform_points_through_phi(points.data_ptr(), n, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), out.data_ptr(),
                                                     inside.data_ptr() if return_inside else None, _stream()), "oai_transform_points_through_phi")
     return (out, inside) if return_inside else out
+
+
+@dataclass
+class PhiInverseStats:
+    """What the solver behind ``invert_phi`` did over the lattice (include/oai_hip.h, "The inverse of phi")."""
+    points: int                 # lattice points D * H * W
+    unconverged: int            # status 0: left at their identity coordinate
+    outside: int                # status 2: converged at a point outside phi's buffer, where the forward map is the identity
+    max_residual: float         # max |T(x) - y| over the converged points, network voxels
+    mean_iterations: float      # evaluations of the forward map per point
+    max_iterations: int
+
+
+def _check_solver(max_iter, tol) -> None:
+    if int(max_iter) < 1:
+        raise ValueError(f"max_iter must be at least 1, got {max_iter}")
+    if not float(tol) > 0.0:
+        raise ValueError(f"tol must be positive, got {tol}")
+
+
+@_on_tensor_device
+def inverse_points_through_phi(points: torch.Tensor, phi: torch.Tensor, point_to_net, net_to_out, max_iter: int = 30, tol: float = 1e-7,
+                               return_status: bool = False):
+    """points float32 [n,3] (x,y,z) pulled back through the dense map phi [3,D,H,W]: ``net_to_out(x)`` with ``T(x) = point_to_net(p)``,
+    T the forward map of ``transform_points_through_phi`` in network index space, solved per point by Newton's method to ``tol``
+    network voxels in at most ``max_iter`` iterations (include/oai_hip.h, "The inverse of phi").  The affines are (A [3,3], b [3])
+    pairs in fp64.  Returns float32 [n,3]; with ``return_status`` also the uint8 [n] status: 1 = converged inside phi's buffer, 2 =
+    converged outside it, 0 = not converged (the point is then moved by the affines alone)."""
+    lib = _lib.load()
+    points = _chk(points, "points")
+    phi = _chk(phi, "phi")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n,3], got {tuple(points.shape)}")
+    if phi.dim() != 4 or phi.shape[0] != 3:
+        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+    if phi.device != points.device:
+        raise ValueError(f"points ({points.device}) and phi ({phi.device}) must live on the same GPU")
+    _check_solver(max_iter, tol)
+    n = int(points.shape[0])
+    _, Dn, Hn, Wn = (int(v) for v in phi.shape)
+    out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    status = torch.empty(n, dtype=torch.uint8, device=points.device) if return_status else None
+    a1, a2 = make_affine(*point_to_net), make_affine(*net_to_out)
+    _lib.check(lib.oai_inverse_points_through_phi(points.data_ptr(), n, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), int(max_iter),
+                                                  float(tol), out.data_ptr(), status.data_ptr() if return_status else None, _stream()),
+               "oai_inverse_points_through_phi")
+    return (out, status) if return_status else out
+
+
+@_on_tensor_device
+def invert_phi(phi: torch.Tensor, max_iter: int = 30, tol: float = 1e-7, return_status: bool = False, out: Optional[torch.Tensor] = None):
+    """The dense inverse psi of the dense map phi float32 [3,D,H,W] on the same lattice and in the same storage convention: psi is a
+    phi (``resample_maps_through_phi``, ``transform_points_through_phi`` and ``phi_jacobian`` read it unchanged) that takes patient
+    points to atlas points (include/oai_hip.h, "The inverse of phi").  Returns ``(psi, stats)`` -- psi a new float32 [3,D,H,W] device
+    tensor, or ``out``; stats a ``PhiInverseStats``, read back with one synchronisation -- and with ``return_status`` also the uint8
+    [D,H,W] status of every lattice point (1 converged inside the buffer, 2 converged outside it, 0 not converged)."""
+    lib = _lib.load()
+    phi = _chk(phi, "phi")
+    if phi.dim() != 4 or phi.shape[0] != 3:
+        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+    _check_solver(max_iter, tol)
+    _, D, H, W = (int(v) for v in phi.shape)
+    if out is None:
+        psi = torch.empty_like(phi)
+    else:
+        if out.device != phi.device or out.dtype != torch.float32 or tuple(out.shape) != tuple(phi.shape) or not out.is_contiguous() \
+                or out.data_ptr() == phi.data_ptr():
+            raise ValueError(f"out must be a contiguous float32 {tuple(phi.shape)} tensor on {phi.device} that is not phi itself")
+        psi = out
+    status = torch.empty((D, H, W), dtype=torch.uint8, device=phi.device) if return_status else None
+    stats = torch.empty(6, dtype=torch.float64, device=phi.device)
+    ws = torch.empty(int(lib.oai_invert_phi_workspace_bytes(D, H, W)), dtype=torch.uint8, device=phi.device)
+    _lib.check(lib.oai_invert_phi(phi.data_ptr(), D, H, W, int(max_iter), float(tol), psi.data_ptr(), status.data_ptr() if return_status else None,
+                                  ws.data_ptr(), ws.numel(), stats.data_ptr(), _stream()), "oai_invert_phi")
+    s = stats.cpu().numpy()
+    record = PhiInverseStats(int(s[0]), int(s[1]), int(s[2]), float(s[3]), float(s[4] / s[0]), int(s[5]))
+    return (psi, record, status) if return_status else (psi, record)
 
 
 def _out_slot(out: Optional[torch.Tensor], n: int, dtype, device, name: str) -> torch.Tensor:

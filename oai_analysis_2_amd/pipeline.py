@@ -104,15 +104,16 @@ class VolumePipeline:
         ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
         None (default): nothing more is launched.  ``thickness_space``: "atlas" (default) = the distance on the atlas grid, as the
         reference takes it; "patient" = on the meshes pushed through this volume's phi, in the patient's own millimetres
-        (ThicknessAtlas.measure(..., phi=, image_A=)).
+        (ThicknessAtlas.measure(..., phi=, image_A=)); "patient_grid" = native thickness: the mesh is taken from the patient-grid maps
+        ``fc`` / ``tc`` and its inner vertices pulled to the atlas through the inverse of phi (ThicknessAtlas.measure(..., space="patient_grid")).
         ``qc``: True, or a qc.QCReference (the atlas' own maps, for Dice) -- the registration QC record of the volume
         (qc.registration_qc: folds and det J of phi, volume scale, cartilage volume) in ``VolumeResult.qc``, computed where the thickness
         is: after the range check and the fp32 repeat.  A few small launches and one more synchronisation.  None (default): nothing more
         is launched and no bit changes."""
         if qc is not None and qc is not True and not hasattr(qc, "maps"):
             raise ValueError(f"qc must be None, True or a qc.QCReference, got {qc!r}")
-        if thickness_space not in ("atlas", "patient"):
-            raise ValueError(f"thickness_space must be 'atlas' or 'patient', got {thickness_space!r}")
+        if thickness_space not in ("atlas", "patient", "patient_grid"):
+            raise ValueError(f"thickness_space must be 'atlas', 'patient' or 'patient_grid', got {thickness_space!r}")
         res = self._run_overlapped(vol, meta_A) if self.overlap_registration else self._run_serial(vol, meta_A)
         if check and res.overflow is not None:
             raised = bool(int(res.overflow.item()))
@@ -120,8 +121,11 @@ class VolumePipeline:
             if raised:
                 res = self.rerun_f32(vol, meta_A)
         if thickness is not None:
-            push = dict(phi=res.phi, image_A=res.meta_A) if thickness_space == "patient" else {}
-            res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, **push)
+            if thickness_space == "patient_grid":
+                res.thickness = thickness.measure(res.fc, res.tc, spacing_xyz=res.meta_A.spacing, phi=res.phi, image_A=res.meta_A, space="patient_grid")
+            else:
+                push = dict(phi=res.phi, image_A=res.meta_A) if thickness_space == "patient" else {}
+                res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, **push)
         if qc is not None:
             from .qc import registration_qc
             res.qc = registration_qc(res, reference=None if qc is True else qc)

@@ -60,6 +60,7 @@ class DisplacementTransform:
     image_A: Image                      # metadata only (array may be dropped)
     image_B: Image
     phi: Optional[np.ndarray] = None    # float32 [3,D,H,W] dense map in [0,1] units (network grid)
+    inverse_stats: Optional["ops.PhiInverseStats"] = None    # set by inverse(): what the solver did over the lattice
 
     @property
     def net_shape(self):
@@ -75,6 +76,23 @@ class DisplacementTransform:
         if self.phi is None:
             raise ValueError("this DisplacementTransform carries no phi (the dense map the Jacobian is taken of)")
         return registration_qc(self.phi, self.image_A, self.image_B, return_map=return_map)
+
+    def inverse(self, max_iter: int = 30, tol: float = 1e-7, device=None) -> "DisplacementTransform":
+        """The inverse transform, A-physical -> B-physical: what itk.Transform.GetInverseTransform means -- a numerical inverse of the
+        field that is held, not a second registration -- restated from ITK's documented behaviour and unpinned (ITK is absent).  phi
+        is inverted on its own lattice (ops.invert_phi: Newton per lattice point, to ``tol`` network voxels), so the result is again a
+        DisplacementTransform, with ``image_A`` and ``image_B`` swapped, ``phi`` = psi and ``displacement`` rebuilt from it:
+        ``deform_probmap(T.inverse(), image_B, image_A, atlas_map)`` pulls an atlas-space map onto the patient grid, and
+        ``transform_mesh(mesh, T.inverse())`` takes a patient-space mesh to the atlas through the stored psi (interpolated between
+        lattice points; ``transform_mesh(mesh, T, inverse=True)`` solves per vertex instead).  ``inverse_stats`` holds the solver's
+        record: lattice points that did not converge (inside a fold) keep their identity coordinate and are counted there."""
+        if self.phi is None:
+            raise ValueError("this DisplacementTransform carries no phi (the dense map that is inverted)")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        phi = self.phi if torch.is_tensor(self.phi) else torch.from_numpy(np.ascontiguousarray(self.phi, dtype=np.float32))
+        psi, stats = ops.invert_phi(phi.to(dev), max_iter=max_iter, tol=tol)
+        disp = ops.phi_to_itk_displacement(psi)
+        return DisplacementTransform(disp.cpu().numpy(), self.image_B, self.image_A, psi.cpu().numpy(), stats)
 
     def to_itk(self):  # pragma: no cover - itk is absent in this environment
         import itk

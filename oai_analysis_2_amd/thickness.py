@@ -10,6 +10,10 @@ step behind ``VolumeResult.fc_atlas`` / ``tc_atlas``, plus a thickness IMAGE on 
     atlas.measure(.., phi=, image_A=)       the same in PATIENT millimetres: both sub-meshes are pushed through phi (atlas -> patient,
                                             csrc/mesh_transform.hip) before the distance is taken; map_attributes still runs on the
                                             atlas-space inner vertices, which is what puts every knee on the atlas' vertices
+    atlas.measure(fc, tc, phi=, image_A=, space="patient_grid")
+                                            NATIVE thickness: the mesh is extracted, split and measured on the patient-grid maps
+                                            themselves (no resample blur, the patient's own millimetres), then its inner vertices are
+                                            pulled to the atlas through the inverse of phi (csrc/phi_inverse.hip) for map_attributes
     atlas.image(thickness, kind)            per knee: one gather through the raster; the same pixel is the same atlas location in
                                             every knee, because map_attributes puts every knee on the atlas' vertices
 
@@ -94,12 +98,15 @@ class KneeThickness:
     ``keep_on_device``).  A cartilage that could not be measured is all NaN and has its reason in ``errors["FC"]`` / ``errors["TC"]``.
     ``space``: "atlas" = distances taken on the atlas grid (the reference's), "patient" = on the meshes pushed through phi, the patient's
     own millimetres; then ``outside[kind]`` counts the pushed vertices (inner and outer) that fell outside phi's buffer and moved by the
-    affines alone."""
+    affines alone.  "patient_grid" = distances taken on the mesh of the patient-grid maps, whose inner vertices were pulled to the atlas
+    through the inverse of phi: ``outside[kind]`` counts the pulled vertices whose preimage lies outside phi's buffer, ``unconverged[kind]``
+    those the solver could not place (inside a fold of phi), which moved by the affines alone."""
     fc: Union[np.ndarray, torch.Tensor]
     tc: Union[np.ndarray, torch.Tensor]
     errors: Dict[str, str] = field(default_factory=dict)
     space: str = "atlas"
     outside: Dict[str, int] = field(default_factory=dict)
+    unconverged: Dict[str, int] = field(default_factory=dict)
 
     def __getitem__(self, kind: str):
         return {"FC": self.fc, "TC": self.tc}[kind]
@@ -141,10 +148,12 @@ class ThicknessAtlas:
         self._scatter: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
         self.spacing: Dict[str, np.ndarray] = {}            # each map's own (x, y, z) spacing: measure's default for that cartilage
         self.frame: Dict[str, Optional[Tuple[np.ndarray, np.ndarray]]] = {}     # each map's (origin, direction); None: built from a bare tensor or array
+        self.shape: Dict[str, Tuple[int, int, int]] = {}    # each map's (z, y, x) shape: the atlas grid, for "patient_grid"
         self.device = None
         for kind, probmap in zip(KINDS, (atlas_fc, atlas_tc)):
             vol, sp, origin, direction = mp._probmap_dev(probmap, spacing_xyz)
             self.spacing[kind] = sp
+            self.shape[kind] = tuple(int(v) for v in vol.shape)
             if atlas_image is not None:
                 self.frame[kind] = _frame_of(atlas_image)
             else:
@@ -204,8 +213,22 @@ class ThicknessAtlas:
         vec = mp._map_attributes_dev(iv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
         return vec, sum(int(m.numel()) - int(np.count_nonzero(m.cpu().numpy())) for m in (in_i, in_o))
 
+    def _measure_one_patient_grid(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame) -> Tuple[torch.Tensor, int, int]:
+        """_measure_one on a patient-grid map, with the inner vertices pulled to the atlas through the inverse of phi as map_attributes'
+        sources: (vector, pulled vertices whose preimage lies outside phi's buffer, vertices that did not converge)."""
+        iv, if_, dist = mp._thickness_inner_dev(vol, spacing, kind, self.min_cells[kind])
+        if iv.shape[0] == 0:
+            raise ValueError("map_attributes: the source mesh has no points")
+        image_B = Image(np.broadcast_to(np.zeros((), np.float32), self.shape[kind]), self.spacing[kind], *frame)     # the atlas grid, no voxels
+        p2n, n2o = mp.mesh_point_affines(image_A, image_B, phi.shape[1:], inverse=True)
+        piv, status = mp._inverse_points_dev(iv, phi, p2n, n2o, return_status=True)
+        lo, hi, _ = mp.mesh_grid_params_device(piv, if_)
+        vec = mp._map_attributes_dev(piv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
+        counts = np.bincount(status.cpu().numpy(), minlength=3)
+        return vec, int(counts[2]), int(counts[0])
+
     def measure(self, fc_atlas: torch.Tensor, tc_atlas: torch.Tensor, spacing_xyz=None, keep_on_device: bool = False, phi=None, image_A=None,
-                atlas_image=None) -> KneeThickness:
+                atlas_image=None, space: Optional[str] = None) -> KneeThickness:
         """Thickness of one knee on the atlas inner vertices, from the two [z,y,x] float32 device tensors of a ``VolumeResult``
         (``spacing_xyz``: the atlas grid's, default the spacing of the map this atlas was built from).  Everything stays on the device, on the
         current stream, until the two vectors; only the inner -> outer distance is computed.  Per cartilage, bit for bit,
@@ -224,12 +247,28 @@ class ThicknessAtlas:
 
         ``outside[kind]`` counts the pushed vertices outside phi's buffer.  Unpinned, like the resample: ITK is absent.
 
+        ``space``: None (default) = "atlas" without phi, "patient" with it, as above.  "patient_grid" (with ``phi`` and ``image_A``):
+        NATIVE thickness.  The two maps are then the PATIENT-grid ``VolumeResult.fc`` / ``tc`` and ``spacing_xyz`` the patient's
+        (default ``image_A``'s): the mesh is extracted, split and measured on them at native resolution, with no resample blur and in
+        the patient's own millimetres; its inner vertices are then pulled to the atlas' "spacing" coordinates by the point solver
+        (mesh_processing.transform_mesh(..., inverse=True): Newton on phi per vertex, exact to 1e-7 network voxels) and are
+        map_attributes' sources, the atlas inner vertices its targets.  The atlas grid is the shape and spacing of the maps this
+        atlas was built from with the origin and direction as for "patient".  ``outside[kind]`` counts the vertices whose preimage
+        lies outside phi's buffer, ``unconverged[kind]`` those that did not converge and moved by the affines alone.  This space is
+        UNPINNED (ITK is absent, and the reference has no such step), and the inner / outer split heuristics have only ever been run
+        on atlas-grid meshes: the split assumes that the patient grid has the atlas' orientation.
+
         A map with no region above ``min_cells``, or an FC slab of fewer than 2 faces, raises ValueError inside those functions: that
         is caught PER CARTILAGE, the vector filled with NaN and the message kept in ``errors`` -- one bad knee must not end a cohort.
         Nothing else is caught."""
+        if space not in (None, "atlas", "patient", "patient_grid"):
+            raise ValueError(f"space must be None, 'atlas', 'patient' or 'patient_grid', got {space!r}")
         if (phi is None) != (image_A is None):
             raise ValueError(f"patient-space thickness needs both phi and image_A: {'image_A' if image_A is None else 'phi'} is missing")
         patient = phi is not None
+        if space is not None and (space != "atlas") != patient:
+            raise ValueError(f"space={space!r} " + ("takes no phi" if patient else "needs phi and image_A"))
+        native = space == "patient_grid"
         if patient:
             frames = {k: _frame_of(atlas_image) if atlas_image is not None else self.frame[k] for k in KINDS}
             missing = [k for k in KINDS if frames[k] is None]
@@ -241,13 +280,16 @@ class ThicknessAtlas:
                 phi = mp._dev(phi, np.float32, device=self.device)
             if phi.dim() != 4 or phi.shape[0] != 3:
                 raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
-        out, errors, outside = {}, {}, {}
+        out, errors, outside, unconverged = {}, {}, {}, {}
         for kind, vol in zip(KINDS, (fc_atlas, tc_atlas)):
-            sp = self.spacing[kind] if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
+            default = image_A.spacing if native else self.spacing[kind]
+            sp = default if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
             with torch.cuda.device(self.device):
                 vol_d = mp._probmap_dev(vol, sp)[0]
                 try:
-                    if patient:
+                    if native:
+                        out[kind], outside[kind], unconverged[kind] = self._measure_one_patient_grid(vol_d, sp, kind, phi, image_A, frames[kind])
+                    elif patient:
                         out[kind], outside[kind] = self._measure_one_patient(vol_d, sp, kind, phi, image_A, frames[kind])
                     else:
                         out[kind] = self._measure_one(vol_d, sp, kind)
@@ -256,7 +298,7 @@ class ThicknessAtlas:
                     out[kind] = torch.full((self.n_points(kind),), float("nan"), dtype=torch.float32, device=self.device)
         if not keep_on_device:
             out = {k: v.cpu().numpy() for k, v in out.items()}
-        return KneeThickness(out["FC"], out["TC"], errors, "patient" if patient else "atlas", outside)
+        return KneeThickness(out["FC"], out["TC"], errors, "patient_grid" if native else "patient" if patient else "atlas", outside, unconverged)
 
     def _raster(self, kind: str) -> mp.ThicknessRaster:
         if kind not in KINDS:
