@@ -692,6 +692,55 @@ size_t oai_invert_phi_workspace_bytes(int D, int H, int W);
 int oai_invert_phi(const float* phi_dev, int D, int H, int W, int max_iter, double tol, float* psi_out_dev, unsigned char* status_out_dev,
                    void* workspace_dev, size_t workspace_bytes, double* stats_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Surface-distance QC (csrc/edt.hip, tests/edt_ref.py): the exact Euclidean distance transform of a binary volume with anisotropic
+ * spacing, the surface of a thresholded map, and the surface-distance figures of two surfaces (ASSD, Hausdorff, HD95).  The
+ * definitions -- the surface rule and the pooled percentile -- are MedPy's (medpy.metric.binary: __surface_distances, assd, hd, hd95)
+ * on scipy.ndimage, restated and checked against scipy on the CPU (tests/test_edt_cpu.py); they are not tied to ITK's
+ * SignedMaurerDistanceMapImageFilter, ITK being absent.  All volumes are [z][y][x]; spacing_xyz is (x, y, z).
+ *
+ * oai_mask_surface: map_dev float32 [D][H][W], out_dev one byte per voxel.  A voxel is in the set when its value is finite and
+ * > threshold (oai_mask_overlap's rule).  mode 0: out = 1 for every voxel of the set, else 0.  mode 1: the surface -- a voxel of the set
+ * with at least one of its six face neighbours not in the set or outside the volume, which is A ^ binary_erosion(A, 6-connectivity,
+ * border_value=0).  mode 2: the complement of mode 0.  Every axis in [1, 32767].  Does not synchronise.
+ *
+ * oai_edt: feature_dev one byte per voxel, a feature where != 0.  For every voxel p the squared distance is the minimum over all
+ * feature voxels q of the canonical expression, in fp64 without contraction:
+ *   tx = (double)(px - qx) * sx;  ty = (double)(py - qy) * sy;  tz = (double)(pz - qz) * sz;      sq = (tx*tx + ty*ty) + tz*tz
+ * to the bit (what scipy.ndimage.distance_transform_edt(~features, sampling=(sz, sy, sx)) squares to within 1e-15 relative); +inf
+ * everywhere when there is no feature.  Computed separably with exhaustive line scans and an exact cut-off -- IEEE rounding is monotone,
+ * a <= b  =>  fl(a + c) <= fl(b + c), so the per-line minimum of the partial sum carries the minimum of the whole -- never by parabola
+ * intersections in floating point.
+ *   sq_out_dev[p] (may be null) = sq
+ *   dist_dev[p] = (accumulate ? dist_dev[p] : 0.0f) + scale * (float)sqrt(sq)          float32 operations, no contraction
+ *   n_features_dev (may be null): the number of feature voxels, on the device
+ * scale is 1 or -1: a second call on the complement with scale = -1, accumulate = 1 turns the first call's map of the set into the
+ * signed map, positive outside the set and negative inside, scipy's edt(~m) - edt(m).  Every axis in [1, 32767], every spacing finite
+ * and > 0.  The workspace holds the passes' integer offsets, 6 bytes per voxel and 4 per row.  Does not synchronise.
+ *
+ * oai_surface_distance: surf_*_dev one byte per voxel (oai_mask_surface, mode 1), dist_to_*_dev float32 (oai_edt of the other
+ * surface), n voxels.  The directed distances are d(A->B) = dist_to_b[p] for every p with surf_a[p] != 0, and likewise d(B->A).
+ * out_dev: double[8] on the device --
+ *   [0] n_A   [1] n_B   [2] sum d(A->B)   [3] sum d(B->A)   [4] max d(A->B)   [5] max d(B->A)   [6], [7] the requested percentiles
+ * The sums are fp64 sums of the widened float32 distances: per-block partials go to the workspace and a second kernel adds them in
+ * index order -- no float atomics and a block count that depends on n only, so they are bit-reproducible.  The percentiles
+ * (percentiles: n_percentiles = 0..2 host floats in [0, 100]) are np.percentile of the pooled array concat(d(A->B), d(B->A)), MedPy's
+ * hd95: exact order statistics by a masked 4-pass radix select and numpy's float32 interpolation, the rule of oai_image_normalize,
+ * with the ranks computed on the device because n_A + n_B is known there only.  When n_A = 0 or n_B = 0, [2]..[7] are NaN and the
+ * counts are still reported; a percentile slot that was not asked for is NaN.  ASSD = ([2] + [3]) / ([0] + [1]), Hausdorff =
+ * max([4], [5]).  Does not synchronise.
+ * ---------------------------------------------------------------------------------------- */
+int oai_mask_surface(const float* map_dev, int D, int H, int W, float threshold, int mode, unsigned char* out_dev, void* stream);
+/* 0 when an axis is outside [1, 32767]. */
+size_t oai_edt_workspace_bytes(int D, int H, int W);
+int oai_edt(const unsigned char* feature_dev, int D, int H, int W, const double spacing_xyz[3], float scale, int accumulate, float* dist_dev,
+            double* sq_out_dev, void* workspace_dev, size_t workspace_bytes, long long* n_features_dev, void* stream);
+/* 0 when n < 0. */
+size_t oai_surface_distance_workspace_bytes(long long n);
+int oai_surface_distance(const unsigned char* surf_a_dev, const float* dist_to_b_dev, const unsigned char* surf_b_dev, const float* dist_to_a_dev,
+                         long long n, const float* percentiles, int n_percentiles, void* workspace_dev, size_t workspace_bytes, double* out_dev,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

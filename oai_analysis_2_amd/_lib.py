@@ -99,6 +99,11 @@ SIGNATURES = {
     "oai_invert_phi": (_I, [_P, _I, _I, _I, _I, _D, _P, _P, _P, _Z, _P, _P]),
     "oai_mask_overlap_workspace_bytes": (_Z, [C.c_longlong]),
     "oai_mask_overlap": (_I, [_P, _P, C.c_longlong, _F, _P, _Z, _P, _P]),
+    "oai_mask_surface": (_I, [_P, _I, _I, _I, _F, _I, _P, _P]),
+    "oai_edt_workspace_bytes": (_Z, [_I, _I, _I]),
+    "oai_edt": (_I, [_P, _I, _I, _I, C.POINTER(_D), _F, _I, _P, _P, _P, _Z, _P, _P]),
+    "oai_surface_distance_workspace_bytes": (_Z, [C.c_longlong]),
+    "oai_surface_distance": (_I, [_P, _P, _P, _P, C.c_longlong, C.POINTER(_F), _I, _P, _Z, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

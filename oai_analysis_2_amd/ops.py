@@ -358,3 +358,91 @@ def image_normalize(vol: torch.Tensor, window_min_perc: float = 0.1, window_max_
                                        float(output_min), float(output_max), out.data_ptr(), win.data_ptr(),
                                        ws.data_ptr(), ws.numel(), _stream()), "oai_image_normalize")
     return (out, win) if return_window else out
+
+
+# ---- surface-distance QC (include/oai_hip.h, "Surface-distance QC"; csrc/edt.hip) --------------------------------------------------------
+SURFACE_MODES = {"set": 0, "surface": 1, "complement": 2}
+
+
+def _volume3(t: torch.Tensor, name: str, dtype) -> torch.Tensor:
+    t = _chk(t, name, dtype)
+    if t.dim() != 3:
+        raise ValueError(f"{name} must be a [z,y,x] volume, got shape {tuple(t.shape)}")
+    return t
+
+
+@_on_tensor_device
+def mask_surface(map: torch.Tensor, threshold: float = 0.5, mode: str = "surface") -> torch.Tensor:
+    """The set ``finite and > threshold`` of a float32 [z,y,x] device volume as a uint8 volume: ``mode`` "set" -- the set itself;
+    "surface" -- its voxels with a face neighbour outside the set or outside the volume (``A ^ binary_erosion(A)``, MedPy's rule);
+    "complement" -- everything else.  Does not synchronise."""
+    if mode not in SURFACE_MODES:
+        raise ValueError(f"mode must be one of {sorted(SURFACE_MODES)}, got {mode!r}")
+    map = _volume3(map, "map", torch.float32)
+    D, H, W = (int(v) for v in map.shape)
+    out = torch.empty((D, H, W), dtype=torch.uint8, device=map.device)
+    _lib.check(_lib.load().oai_mask_surface(map.data_ptr(), D, H, W, float(threshold), SURFACE_MODES[mode], out.data_ptr(), _stream()),
+               "oai_mask_surface")
+    return out
+
+
+def _edt(features: torch.Tensor, spacing_xyz, scale: float, into: Optional[torch.Tensor], squared: bool, count: bool):
+    """One oai_edt call: (dist, sq or None, n_features or None).  ``into``: the float32 map that ``scale * distance`` is added to."""
+    lib = _lib.load()
+    features = _volume3(features, "features", torch.uint8)
+    D, H, W = (int(v) for v in features.shape)
+    dist = torch.empty((D, H, W), dtype=torch.float32, device=features.device) if into is None else into
+    sq = torch.empty((D, H, W), dtype=torch.float64, device=features.device) if squared else None
+    n = torch.empty(1, dtype=torch.int64, device=features.device) if count else None
+    ws = torch.empty(int(lib.oai_edt_workspace_bytes(D, H, W)), dtype=torch.uint8, device=features.device)
+    spacing = (C.c_double * 3)(*[float(v) for v in np.asarray(spacing_xyz, np.float64).reshape(3)])
+    _lib.check(lib.oai_edt(features.data_ptr(), D, H, W, spacing, float(scale), int(into is not None), dist.data_ptr(),
+                           sq.data_ptr() if squared else None, ws.data_ptr(), ws.numel(), n.data_ptr() if count else None, _stream()), "oai_edt")
+    return dist, sq, n
+
+
+@_on_tensor_device
+def distance_transform(features: torch.Tensor, spacing_xyz=(1.0, 1.0, 1.0), return_squared: bool = False, return_count: bool = False):
+    """The exact Euclidean distance transform of a uint8 [z,y,x] device volume: per voxel the distance to the nearest voxel with a
+    non-zero byte, in the units of ``spacing_xyz`` (x, y, z) -- ``scipy.ndimage.distance_transform_edt(features == 0, sampling=
+    spacing_xyz[::-1])``, +inf when there is no feature.  Returns the float32 map; with ``return_squared`` also the float64 squared
+    distances (bit-equal to the brute-force minimum, include/oai_hip.h); with ``return_count`` also the int64 [1] DEVICE feature count.
+    Does not synchronise."""
+    dist, sq, n = _edt(features, spacing_xyz, 1.0, None, return_squared, return_count)
+    got = (dist,) + ((sq,) if return_squared else ()) + ((n,) if return_count else ())
+    return got if len(got) > 1 else dist
+
+
+@_on_tensor_device
+def signed_distance(map: torch.Tensor, spacing_xyz=(1.0, 1.0, 1.0), threshold: float = 0.5) -> torch.Tensor:
+    """The signed distance map of the set ``finite and > threshold`` of a float32 [z,y,x] device volume: positive outside the set (the
+    distance to it), negative inside (minus the distance to the complement) -- scipy's ``edt(~m) - edt(m)``.  Two oai_edt calls, the
+    second subtracting in place.  Does not synchronise."""
+    dist, _, _ = _edt(mask_surface(map, threshold, "set"), spacing_xyz, 1.0, None, False, False)
+    _edt(mask_surface(map, threshold, "complement"), spacing_xyz, -1.0, dist, False, False)
+    return dist
+
+
+@_on_tensor_device
+def surface_distance(surf_a: torch.Tensor, dist_to_b: torch.Tensor, surf_b: torch.Tensor, dist_to_a: torch.Tensor,
+                     percentiles: Sequence[float] = (95.0,), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The surface-distance figures of two surfaces (uint8 masks) given each one's distance map (float32, ``distance_transform`` of the
+    surface): the float64 [8] DEVICE tensor n_A, n_B, sum d(A->B), sum d(B->A), max d(A->B), max d(B->A) and up to two percentiles of
+    the pooled distances (``np.percentile`` bit for bit; NaN where not asked for).  With an empty surface everything but the counts is
+    NaN.  ``out``: written there instead of a new tensor.  Does not synchronise."""
+    lib = _lib.load()
+    surf_a, surf_b = _chk(surf_a, "surf_a", torch.uint8), _chk(surf_b, "surf_b", torch.uint8)
+    dist_to_b, dist_to_a = _chk(dist_to_b, "dist_to_b"), _chk(dist_to_a, "dist_to_a")
+    n = int(surf_a.numel())
+    for name, t in (("dist_to_b", dist_to_b), ("surf_b", surf_b), ("dist_to_a", dist_to_a)):
+        if int(t.numel()) != n or t.device != surf_a.device:
+            raise ValueError(f"{name} must have surf_a's {n} elements and live on its GPU")
+    pct = [float(p) for p in percentiles]
+    if len(pct) > 2:
+        raise ValueError(f"at most two percentiles per call, got {len(pct)}")
+    stats = _out_slot(out, 8, torch.float64, surf_a.device, "out")
+    ws = torch.empty(int(lib.oai_surface_distance_workspace_bytes(n)), dtype=torch.uint8, device=surf_a.device)
+    ptr = lambda t: t.data_ptr() if n else None
+    _lib.check(lib.oai_surface_distance(ptr(surf_a), ptr(dist_to_b), ptr(surf_b), ptr(dist_to_a), n, (C.c_float * 2)(*(pct + [0.0, 0.0])[:2]),
+                                        len(pct), ws.data_ptr(), ws.numel(), stats.data_ptr(), _stream()), "oai_surface_distance")
+    return stats
