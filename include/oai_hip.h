@@ -639,8 +639,8 @@ int oai_transform_points_through_phi(const float* pts_dev, long long n, const fl
  * det_out_dev (may be null): float32 [D-1][H-1][W-1], the rounded determinant.  stats_dev: double[7] on the device --
  *   [0] cells = (D-1)(H-1)(W-1)   [1] folds: det < 0 on the fp64 value   [2] cells with a non-finite determinant, left out of all the others
  *   [3] min  [4] max  (+inf / -inf when no cell is finite)   [5] sum of det   [6] sum of det^2
- * Per-block partials go to the workspace and a second kernel adds them in index order: no atomics, a block count that depends on the
- * shape only, so the stats are bit-reproducible and do not depend on det_out_dev.  Does not synchronise.  Every axis must be >= 2.
+ * Reduced in the fixed order of csrc/ordered_reduce.h (per-block partials in the workspace, a second kernel over them): no atomics, a
+ * block count that depends on the shape only, so the stats are bit-reproducible and do not depend on det_out_dev.  Does not synchronise.  Every axis must be >= 2.
  * ---------------------------------------------------------------------------------------- */
 /* 0 when an axis is below 2 voxels. */
 size_t oai_phi_jacobian_workspace_bytes(int D, int H, int W);
@@ -681,8 +681,8 @@ int oai_mask_overlap(const float* a_dev, const float* b_dev, long long n, float 
  * status_out_dev (may be null) [D][H][W] bytes.  stats_dev: double[6] on the device --
  *   [0] points = D H W   [1] unconverged   [2] converged outside the buffer   [3] max |r| over the converged points
  *   [4] sum over all points of the evaluations of T   [5] their maximum
- * Per-block partials go to the workspace and a second kernel adds them in index order: no atomics, a block count that depends on the
- * shape only, so the stats are bit-reproducible and do not depend on status_out_dev.  Does not synchronise.
+ * Reduced in the fixed order of csrc/ordered_reduce.h (per-block partials in the workspace, a second kernel over them): no atomics, a
+ * block count that depends on the shape only, so the stats are bit-reproducible and do not depend on status_out_dev.  Does not synchronise.
  * ---------------------------------------------------------------------------------------- */
 int oai_inverse_points_through_phi(const float* pts_dev, long long n, const float* phi_dev, int Dn, int Hn, int Wn,
                                    const oai_affine* point_to_net, const oai_affine* net_to_out, int max_iter, double tol, float* out_dev,
@@ -722,10 +722,10 @@ int oai_invert_phi(const float* phi_dev, int D, int H, int W, int max_iter, doub
  * surface), n voxels.  The directed distances are d(A->B) = dist_to_b[p] for every p with surf_a[p] != 0, and likewise d(B->A).
  * out_dev: double[8] on the device --
  *   [0] n_A   [1] n_B   [2] sum d(A->B)   [3] sum d(B->A)   [4] max d(A->B)   [5] max d(B->A)   [6], [7] the requested percentiles
- * The sums are fp64 sums of the widened float32 distances: per-block partials go to the workspace and a second kernel adds them in
- * index order -- no float atomics and a block count that depends on n only, so they are bit-reproducible.  The percentiles
+ * The sums are fp64 sums of the widened float32 distances in the fixed order of csrc/ordered_reduce.h, which tests/ordered_reduce_ref.py
+ * restates and tests/test_edt_gpu.py pins to the bit -- no float atomics and a block count that depends on n only.  The percentiles
  * (percentiles: n_percentiles = 0..2 host floats in [0, 100]) are np.percentile of the pooled array concat(d(A->B), d(B->A)), MedPy's
- * hd95: exact order statistics by a masked 4-pass radix select and numpy's float32 interpolation, the rule of oai_image_normalize,
+ * hd95: exact order statistics by the 4-pass radix select of csrc/radix_select.h and numpy's float32 interpolation, as oai_image_normalize,
  * with the ranks computed on the device because n_A + n_B is known there only.  When n_A = 0 or n_B = 0, [2]..[7] are NaN and the
  * counts are still reported; a percentile slot that was not asked for is NaN.  ASSD = ([2] + [3]) / ([0] + [1]), Hausdorff =
  * max([4], [5]).  Does not synchronise.

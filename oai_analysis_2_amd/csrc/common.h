@@ -1,4 +1,4 @@
-// Shared host-side helpers of liboai_hip.so (error reporting, launch checks).
+// Shared helpers of liboai_hip.so: error reporting, launch checks, workspaces, and the set rule of the QC kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -66,6 +66,10 @@ static inline unsigned grid_stride_blocks(long long items, int threads, long lon
     const long long blocks = (items + threads - 1) / threads;
     return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
 }
+
+// membership of the QC kernels' thresholded sets (oai_mask_overlap, oai_mask_surface): finite and above the threshold
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+__device__ __forceinline__ bool in_set(float v, float thr) { return finite_f32(v) && v > thr; }
 
 // Diagnostics (in-kernel phase stamps, kernel-variant selection by environment -- nothing that changes a result) exist only in
 // builds compiled with -DOAI_DIAG (a separate .so that scripts/ load through OAI_LIB_PATH).  The production library never reads

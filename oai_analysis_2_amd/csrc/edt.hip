@@ -27,6 +27,9 @@
 
 #pragma clang fp contract(off)
 
+#include "ordered_reduce.h"
+#include "radix_select.h"
+
 namespace {
 
 using namespace oai;
@@ -38,11 +41,8 @@ constexpr unsigned kNoneX = 0xffffu;
 constexpr unsigned kNoneXY = 0xffffffffu;
 constexpr size_t kSlabBytes = 64 * 1024;       // a staged slab above this is read from global memory instead
 constexpr int kSP = 6;                         // doubles per block partial of surface_partials_kernel: n_A, n_B, sums, maxima
-constexpr int kRanks = 4;                      // two percentiles, two order statistics each
+constexpr int kRanks = kSelectRanks;           // two percentiles, two order statistics each
 constexpr long long kStreamBlocks = 2048;      // 256 CUs x 8 blocks: grid-stride beyond that
-
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ bool in_set(float v, float thr) { return finite_f32(v) && v > thr; }
 
 // ---- oai_mask_surface ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kT)
@@ -110,19 +110,20 @@ edt_x_kernel(const unsigned char* __restrict__ feat, long long rows, int W, unsi
     if (lane == 0) row_count[row] = count;
 }
 
+struct CountAcc {
+    unsigned long long v[1];
+    __device__ __forceinline__ void clear() { v[0] = 0; }
+    __device__ __forceinline__ void merge(const unsigned long long* o) { v[0] += o[0]; }
+};
+
 // one block: the feature count of the volume from the per-row counts (integers: exact in any order)
 __global__ void __launch_bounds__(kT) edt_count_kernel(const unsigned* __restrict__ row_count, long long rows, long long* __restrict__ n_features) {
-    __shared__ unsigned long long lds[kT / 64];
-    unsigned long long acc = 0;
-    for (long long i = threadIdx.x; i < rows; i += kT) acc += row_count[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kT / 64; ++w) acc += lds[w];
-        *n_features = (long long)acc;
-    }
+    __shared__ unsigned long long lds[kT / 64][1];
+    CountAcc acc;
+    acc.clear();
+    for (long long i = threadIdx.x; i < rows; i += kT) acc.v[0] += row_count[i];
+    block_reduce<kT>(acc, lds);
+    if (threadIdx.x == 0) *n_features = (long long)acc.v[0];
 }
 
 // The outward scan of one line of `len` entries from position `pos`: k = 0, 1, 2, ..., entries pos - k and pos + k.  at(j, k, t2) takes
@@ -215,23 +216,6 @@ struct SurfAcc {
     }
 };
 
-// the block's kT accumulators into one, in a fixed order: shuffle tree inside each wave, then the waves in order.  Valid in thread 0.
-__device__ __forceinline__ void block_reduce(SurfAcc& a, double (*lds)[kSP]) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        double o[kSP];
-#pragma unroll
-        for (int i = 0; i < kSP; ++i) o[i] = __shfl_down(a.v[i], off, 64);
-        a.merge(o);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < kSP; ++i) lds[wave][i] = a.v[i];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kT / 64; ++w) a.merge(lds[w]);
-}
-
 __global__ void __launch_bounds__(kT)
 surface_partials_kernel(const unsigned char* __restrict__ sa, const float* __restrict__ db, const unsigned char* __restrict__ sb,
                         const float* __restrict__ da, long long n, double* __restrict__ partials) {
@@ -248,51 +232,26 @@ surface_partials_kernel(const unsigned char* __restrict__ sa, const float* __res
             acc.v[1] = acc.v[1] + 1.0; acc.v[3] = acc.v[3] + d; acc.v[5] = fmax(acc.v[5], d);
         }
     }
-    block_reduce(acc, lds);
+    block_reduce<kT>(acc, lds);
     if (threadIdx.x == 0)
         for (int i = 0; i < kSP; ++i) partials[(long long)blockIdx.x * kSP + i] = acc.v[i];
 }
 
-struct SelectState {                 // lives in the caller's workspace (the layout of csrc/normalize.hip's, plus the ranks' origin)
-    unsigned prefix[kRanks];         // key bits fixed so far (high bits)
-    unsigned long long rank[kRanks]; // remaining rank inside the current prefix bucket
-    unsigned hist[kRanks][256];
-    float value[kRanks];             // result: the order statistics
-    float gamma[kRanks / 2];
+struct SurfSelect {                  // lives in the caller's workspace
+    SelectState sel;
+    float gamma[kRanks / 2];         // numpy's interpolation weight of each percentile: known on the device only, like the pooled count
 };
 
-__device__ __forceinline__ unsigned key_of(float f) {      // monotone float -> uint map (csrc/normalize.hip)
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float float_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// np.percentile(a, q) on a float32 array of n elements: numpy_virtual_index of csrc/normalize.hip with the same float32 operations, on
-// the device because n is known there only
-__device__ void virtual_index(unsigned long long n, float pct, unsigned long long& k0, unsigned long long& k1, float& gamma) {
-    const float q = pct / 100.0f;
-    const float vi = (float)(n - 1) * q;
-    float fl = floorf(vi);
-    if (fl < 0.0f) fl = 0.0f;
-    unsigned long long k = (unsigned long long)fl;
-    gamma = vi - fl;
-    if (k >= n - 1) { k = n - 1; gamma = 0.0f; }
-    k0 = k;
-    k1 = k + 1 < n ? k + 1 : n - 1;
-}
-
-// one block: thread t adds up its run of consecutive slots in index order, then the fixed tree; thread 0 writes out[0..5] and the ranks
+// one block: the slots in the order of csrc/ordered_reduce.h; thread 0 writes out[0..5] and the ranks.  A rank not asked for is a copy of
+// rank 0: it shares rank 0's histogram row in every pass, and its value is never read.
 __global__ void __launch_bounds__(kT)
-surface_finish_kernel(const double* __restrict__ partials, long long nb, float p0, float p1, int n_percentiles, SelectState* st,
+surface_finish_kernel(const double* __restrict__ partials, long long nb, float p0, float p1, int n_percentiles, SurfSelect* st,
                       double* __restrict__ out) {
     __shared__ double lds[kT / 64][kSP];
-    const long long per = (nb + kT - 1) / kT;
-    const long long i0 = min(per * (long long)threadIdx.x, nb), i1 = min(i0 + per, nb);
     SurfAcc acc;
-    acc.clear();
-    for (long long i = i0; i < i1; ++i) acc.merge(partials + i * kSP);
-    block_reduce(acc, lds);
-    for (int i = threadIdx.x; i < kRanks * 256; i += kT) st->hist[i / 256][i % 256] = 0;
+    reduce_slots<kT>(partials, nb, acc);
+    block_reduce<kT>(acc, lds);
+    select_clear_hist(&st->sel);
     if (threadIdx.x == 0) {
         const bool empty = acc.v[0] == 0.0 || acc.v[1] == 0.0;
         out[0] = acc.v[0];
@@ -300,75 +259,39 @@ surface_finish_kernel(const double* __restrict__ partials, long long nb, float p
         for (int i = 2; i < kSP; ++i) out[i] = empty ? (double)NAN : acc.v[i];
         out[6] = out[7] = (double)NAN;                             // an empty surface or a percentile not asked for
         const unsigned long long total = (unsigned long long)(acc.v[0] + acc.v[1]);
+        unsigned long long first = 0;                              // rank 0
         for (int p = 0; p < kRanks / 2; ++p) {
-            unsigned long long k0 = 0, k1 = 0;
+            unsigned long long k0 = first, k1 = first;
             float g = 0.0f;
-            if (!empty && p < n_percentiles) virtual_index(total, p == 0 ? p0 : p1, k0, k1, g);
-            st->prefix[2 * p] = st->prefix[2 * p + 1] = 0;
-            st->rank[2 * p] = k0;
-            st->rank[2 * p + 1] = k1;
+            if (!empty && p < n_percentiles) numpy_virtual_index(total, p == 0 ? p0 : p1, k0, k1, g);
+            if (p == 0) first = k0;
+            st->sel.prefix[2 * p] = st->sel.prefix[2 * p + 1] = 0;
+            st->sel.rank[2 * p] = k0;
+            st->sel.rank[2 * p + 1] = k1;
             st->gamma[p] = g;
         }
     }
 }
 
-// pass p (0 = most significant byte): histogram of byte p among the pooled distances whose higher bytes equal prefix[r]
+// one pass of the select over the pooled directed distances
 __global__ void __launch_bounds__(kT)
 surface_hist_kernel(const unsigned char* __restrict__ sa, const float* __restrict__ db, const unsigned char* __restrict__ sb,
-                    const float* __restrict__ da, long long n, int pass, int n_ranks, SelectState* st) {
-    __shared__ unsigned h[kRanks][256];
-    for (int i = threadIdx.x; i < kRanks * 256; i += kT) h[i / 256][i % 256] = 0;
-    __syncthreads();
-    const int shift = 24 - 8 * pass;
-    const unsigned mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
-    unsigned pre[kRanks];
-#pragma unroll
-    for (int r = 0; r < kRanks; ++r) pre[r] = st->prefix[r];
-    auto add = [&](float v) {
-        const unsigned k = key_of(v), hi = k & mask, d = (k >> shift) & 255u;
-#pragma unroll
-        for (int r = 0; r < kRanks; ++r)
-            if (r < n_ranks && hi == pre[r]) atomicAdd(&h[r][d], 1u);
-    };
-    for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
-        if (sa[i]) add(db[i]);
-        if (sb[i]) add(da[i]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kRanks * 256; i += kT) {
-        const unsigned v = h[i / 256][i % 256];
-        if (v) atomicAdd(&st->hist[i / 256][i % 256], v);
-    }
-}
-
-// one block: per rank, find the bin holding the rank, extend the prefix, clear the histograms for the next pass
-__global__ void __launch_bounds__(kT) surface_scan_kernel(int pass, SelectState* st) {
-    if (threadIdx.x < kRanks) {
-        const int r = threadIdx.x;
-        unsigned long long rem = st->rank[r];
-        int d = 0;
-        for (; d < 255; ++d) {
-            const unsigned c = st->hist[r][d];
-            if (rem < c) break;
-            rem -= c;
+                    const float* __restrict__ da, long long n, int pass, SurfSelect* st) {
+    select_hist_pass<kT>(&st->sel, pass, [&](auto add) {
+        for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
+            if (sa[i]) add(db[i]);
+            if (sb[i]) add(da[i]);
         }
-        const int shift = 24 - 8 * pass;
-        st->rank[r] = rem;
-        st->prefix[r] |= (unsigned)d << shift;
-        if (pass == 3) st->value[r] = float_of(st->prefix[r]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kRanks * 256; i += kT) st->hist[i / 256][i % 256] = 0;
+    });
 }
 
-// numpy's _lerp in the array dtype (float32), as window_params_kernel of csrc/normalize.hip; an empty surface keeps its NaN
-__global__ void surface_percentiles_kernel(const SelectState* st, int n_percentiles, double* __restrict__ out) {
+__global__ void __launch_bounds__(kT) surface_scan_kernel(int pass, SurfSelect* st) { select_scan_step(&st->sel, pass); }
+
+// an empty surface keeps its NaN
+__global__ void surface_percentiles_kernel(const SurfSelect* st, int n_percentiles, double* __restrict__ out) {
     const int p = threadIdx.x;
-    if (p < n_percentiles && out[0] != 0.0 && out[1] != 0.0) {
-        const float a = st->value[2 * p], b = st->value[2 * p + 1], t = st->gamma[p];
-        const float diff = __fsub_rn(b, a);
-        out[6 + p] = (double)(t < 0.5f ? __fadd_rn(a, __fmul_rn(diff, t)) : __fsub_rn(b, __fmul_rn(diff, __fsub_rn(1.0f, t))));
-    }
+    if (p < n_percentiles && out[0] != 0.0 && out[1] != 0.0)
+        out[6 + p] = (double)numpy_lerp(st->sel.value[2 * p], st->sel.value[2 * p + 1], st->gamma[p]);
 }
 
 bool axes_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && D <= kMaxAxis && H <= kMaxAxis && W <= kMaxAxis; }
@@ -390,14 +313,14 @@ struct EdtWs {
 
 struct SurfWs {
     double* partials;
-    SelectState* select;
+    SurfSelect* select;
     long long blocks;
     size_t bytes;
     SurfWs(void* workspace, long long n) {
         Ws ws(workspace);
         blocks = n > 0 ? (long long)grid_stride_blocks(n, kT * 4, kStreamBlocks) : 0;
         partials = ws.take<double>((size_t)blocks * kSP);
-        select = ws.take<SelectState>(1);
+        select = ws.take<SurfSelect>(1);
         bytes = ws.off;
     }
 };
@@ -482,8 +405,7 @@ int oai_surface_distance(const unsigned char* surf_a_dev, const float* dist_to_b
     OAI_CHECK_LAUNCH();
     if (n_percentiles && ws.blocks) {
         for (int pass = 0; pass < 4; ++pass) {
-            surface_hist_kernel<<<(unsigned)ws.blocks, kT, 0, st>>>(surf_a_dev, dist_to_b_dev, surf_b_dev, dist_to_a_dev, n, pass, 2 * n_percentiles,
-                                                                    ws.select);
+            surface_hist_kernel<<<(unsigned)ws.blocks, kT, 0, st>>>(surf_a_dev, dist_to_b_dev, surf_b_dev, dist_to_a_dev, n, pass, ws.select);
             OAI_CHECK_LAUNCH();
             surface_scan_kernel<<<1, kT, 0, st>>>(pass, ws.select);
             OAI_CHECK_LAUNCH();

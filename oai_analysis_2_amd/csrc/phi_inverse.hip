@@ -17,13 +17,14 @@
 // operations in the same order (tests/phi_inverse_ref.py): iterates, status and iteration counts are reproducible to the bit.
 //
 // Latency-bound gather: 24 scattered 4-byte loads per iteration per point out of a field that sits in L2 / Infinity Cache after the
-// registration.  No LDS outside the statistics' block reduction, no atomics.  The statistics are reduced like oai_phi_jacobian's:
-// per-thread, wave64 shuffle tree, the block's four waves in order, one slot per block in the workspace, and a second one-block kernel
-// that adds the slots in index order; the block count depends on the shape only.
+// registration.  No LDS outside the statistics' block reduction, no atomics.  The statistics are reduced like oai_phi_jacobian's, by
+// the ordered block reduction of csrc/ordered_reduce.h: one slot per block in the workspace and a second one-block kernel over the
+// slots; the block count depends on the shape only.
 #include "common.h"
 
 #pragma clang fp contract(off)
 
+#include "ordered_reduce.h"
 #include "phi_field.h"      // after the pragma: compiled with contraction off here (see its leading comment)
 
 namespace {
@@ -148,23 +149,6 @@ struct InvAcc {
     }
 };
 
-// the block's kT accumulators into one, in a fixed order: shuffle tree inside each wave, then the waves in order.  Valid in thread 0.
-__device__ __forceinline__ void block_reduce(InvAcc& a, double (*lds)[kSP]) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        double o[kSP];
-#pragma unroll
-        for (int i = 0; i < kSP; ++i) o[i] = __shfl_down(a.v[i], off, 64);
-        a.merge(o);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < kSP; ++i) lds[wave][i] = a.v[i];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kT / 64; ++w) a.merge(lds[w]);
-}
-
 // one thread per lattice point, x fastest: block b owns points [b kT, (b + 1) kT)
 __global__ void __launch_bounds__(kT)
 invert_phi_kernel(const float* __restrict__ phi, int D, int H, int W, int max_iter, double tol, float* __restrict__ psi,
@@ -187,21 +171,18 @@ invert_phi_kernel(const float* __restrict__ phi, int D, int H, int W, int max_it
         acc.v[3] = (double)s.iters;
         acc.v[4] = (double)s.iters;
     }
-    block_reduce(acc, lds);
+    block_reduce<kT>(acc, lds);
     if (threadIdx.x == 0)
         for (int k = 0; k < kSP; ++k) partials[(long long)blockIdx.x * kSP + k] = acc.v[k];
 }
 
-// one block: thread t adds up its run of consecutive slots in index order, then the same fixed tree
+// one block: the slots in runs, then the same tree (csrc/ordered_reduce.h)
 __global__ void __launch_bounds__(kT)
 invert_phi_finish_kernel(const double* __restrict__ partials, long long nb, double points, double* __restrict__ stats) {
     __shared__ double lds[kT / 64][kSP];
-    const long long per = (nb + kT - 1) / kT;
-    const long long i0 = min(per * (long long)threadIdx.x, nb), i1 = min(i0 + per, nb);
     InvAcc acc;
-    acc.clear();
-    for (long long i = i0; i < i1; ++i) acc.merge(partials + i * kSP);
-    block_reduce(acc, lds);
+    reduce_slots<kT>(partials, nb, acc);
+    block_reduce<kT>(acc, lds);
     if (threadIdx.x == 0) {
         stats[0] = points;
         for (int k = 0; k < kSP; ++k) stats[1 + k] = acc.v[k];

@@ -16,15 +16,16 @@
 // written so that a numpy restatement performs the same operations in the same order (tests/phi_jacobian_ref.py).  Measured
 // (profiles/registration_qc.md): 16 us at 80x192x192, a third of the memory rate -- the 65 fp64 instructions per cell weigh about as
 // much as the 35 MB; requesting a thread's whole z-run up front changed nothing.  oai_mask_overlap runs at the memory rate.
-// Reductions: per-thread in z order, wave64 shuffle tree, the block's four waves in order, one slot per block in the workspace; a
-// second one-block kernel adds the slots up in index order.  No atomics, and the block count depends on the shape only: the stats are
-// bit-reproducible and the same whether or not the map is written.
+// Reductions: per-thread in z order, then the ordered block reduction of csrc/ordered_reduce.h (one slot per block in the workspace, a
+// second one-block kernel over the slots).  No atomics, and the block count depends on the shape only: the stats are bit-reproducible
+// and the same whether or not the map is written.
 #include "common.h"
 
 #include <cstdint>
 
 #pragma clang fp contract(off)
 
+#include "ordered_reduce.h"
 #include "phi_field.h"      // after the pragma: compiled with contraction off here (see its leading comment)
 
 namespace {
@@ -46,23 +47,6 @@ struct JacAcc {
         v[0] = v[0] + o[0]; v[1] = v[1] + o[1]; v[2] = fmin(v[2], o[2]); v[3] = fmax(v[3], o[3]); v[4] = v[4] + o[4]; v[5] = v[5] + o[5];
     }
 };
-
-// the block's kT accumulators into one, in a fixed order: shuffle tree inside each wave, then the waves in order.  Valid in thread 0.
-__device__ __forceinline__ void block_reduce(JacAcc& a, double (*lds)[kJP]) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        double o[kJP];
-#pragma unroll
-        for (int i = 0; i < kJP; ++i) o[i] = __shfl_down(a.v[i], off, 64);
-        a.merge(o);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < kJP; ++i) lds[wave][i] = a.v[i];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kT / 64; ++w) a.merge(lds[w]);
-}
 
 __global__ void __launch_bounds__(kT)
 phi_jacobian_kernel(const float* __restrict__ phi, int D, int H, int W, int nbx, int nby, float* __restrict__ det_out, double* __restrict__ partials) {
@@ -109,31 +93,28 @@ phi_jacobian_kernel(const float* __restrict__ phi, int D, int H, int W, int nbx,
             below[0] = c[0]; below[1] = c[1]; below[2] = c[2];
         }
     }
-    block_reduce(acc, lds);
+    block_reduce<kT>(acc, lds);
     if (threadIdx.x == 0)
         for (int i = 0; i < kJP; ++i) partials[b * kJP + i] = acc.v[i];
 }
 
-// one block: thread t adds up its run of consecutive slots in index order, then the same fixed tree
+// one block: the slots in runs, then the same tree (csrc/ordered_reduce.h)
 __global__ void __launch_bounds__(kT)
 phi_jacobian_finish_kernel(const double* __restrict__ partials, long long nb, double cells, double* __restrict__ stats) {
     __shared__ double lds[kT / 64][kJP];
-    const long long per = (nb + kT - 1) / kT;
-    const long long i0 = min(per * (long long)threadIdx.x, nb), i1 = min(i0 + per, nb);
     JacAcc acc;
-    acc.clear();
-    for (long long i = i0; i < i1; ++i) acc.merge(partials + i * kJP);
-    block_reduce(acc, lds);
+    reduce_slots<kT>(partials, nb, acc);
+    block_reduce<kT>(acc, lds);
     if (threadIdx.x == 0) {
         stats[0] = cells;
         for (int i = 0; i < kJP; ++i) stats[1 + i] = acc.v[i];
     }
 }
 
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 struct MaskAcc {
     unsigned long long v[kMP];                 // |A|, |B|, |A and B|, positions with a non-finite value
+    __device__ __forceinline__ void clear() { v[0] = 0; v[1] = 0; v[2] = 0; v[3] = 0; }
+    __device__ __forceinline__ void merge(const unsigned long long* o) { v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
     template <bool HAS_B>
     __device__ __forceinline__ void add(float a, float b, float thr) {
         const bool fa = finite_f32(a), fb = !HAS_B || finite_f32(b);
@@ -142,27 +123,14 @@ struct MaskAcc {
     }
 };
 
-__device__ __forceinline__ void block_reduce_counts(MaskAcc& a, unsigned long long (*lds)[kMP]) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < kMP; ++i) a.v[i] += __shfl_down(a.v[i], off, 64);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < kMP; ++i) lds[wave][i] = a.v[i];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kT / 64; ++w)
-            for (int i = 0; i < kMP; ++i) a.v[i] += lds[w][i];
-}
-
 // nvec float4 pieces (0 when a pointer is not 16-byte aligned), then the remaining elements one by one; both grid-stride
 template <bool HAS_B>
 __global__ void __launch_bounds__(kT)
 mask_overlap_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n, long long nvec, float thr,
                     unsigned long long* __restrict__ partials) {
     __shared__ unsigned long long lds[kT / 64][kMP];
-    MaskAcc acc = {{0, 0, 0, 0}};
+    MaskAcc acc;
+    acc.clear();
     const long long t = (long long)blockIdx.x * kT + threadIdx.x, stride = (long long)gridDim.x * kT;
     const float4* a4 = reinterpret_cast<const float4*>(a);
     const float4* b4 = reinterpret_cast<const float4*>(b);
@@ -172,7 +140,7 @@ mask_overlap_kernel(const float* __restrict__ a, const float* __restrict__ b, lo
         acc.add<HAS_B>(va.x, vb.x, thr); acc.add<HAS_B>(va.y, vb.y, thr); acc.add<HAS_B>(va.z, vb.z, thr); acc.add<HAS_B>(va.w, vb.w, thr);
     }
     for (long long i = 4 * nvec + t; i < n; i += stride) acc.add<HAS_B>(a[i], HAS_B ? b[i] : 0.0f, thr);
-    block_reduce_counts(acc, lds);
+    block_reduce<kT>(acc, lds);
     if (threadIdx.x == 0)
         for (int i = 0; i < kMP; ++i) partials[(long long)blockIdx.x * kMP + i] = acc.v[i];
 }
@@ -180,10 +148,9 @@ mask_overlap_kernel(const float* __restrict__ a, const float* __restrict__ b, lo
 __global__ void __launch_bounds__(kT)
 mask_overlap_finish_kernel(const unsigned long long* __restrict__ partials, int nb, long long* __restrict__ counts) {
     __shared__ unsigned long long lds[kT / 64][kMP];
-    MaskAcc acc = {{0, 0, 0, 0}};
-    for (int i = threadIdx.x; i < nb; i += kT)
-        for (int k = 0; k < kMP; ++k) acc.v[k] += partials[(long long)i * kMP + k];
-    block_reduce_counts(acc, lds);
+    MaskAcc acc;
+    reduce_slots<kT>(partials, nb, acc);
+    block_reduce<kT>(acc, lds);
     if (threadIdx.x == 0)
         for (int k = 0; k < kMP; ++k) counts[k] = (long long)acc.v[k];
 }

@@ -1,6 +1,7 @@
 """CPU: the numpy restatement of the surface-distance QC (tests/edt_ref.py) -- the exhaustive separable distance transform against
 the brute-force minimum bit for bit, both against scipy, the surface rule and the surface-distance figures against the MedPy recipe on
-scipy, analytic cases, and the argument checks of oai_mask_surface / oai_edt / oai_surface_distance (which touch no GPU)."""
+scipy, analytic cases, and the argument checks of oai_mask_surface / oai_edt / oai_surface_distance (which touch no GPU); and the restated summation order of csrc/ordered_reduce.h
+(tests/ordered_reduce_ref.py) on the inputs that tests/test_edt_gpu.py pins the device with."""
 import ctypes as C
 import math
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 
 import edt_ref as er
+import ordered_reduce_ref as orr
 
 DENSITIES = (0.003, 0.05)
 
@@ -145,3 +147,37 @@ def test_argument_checks_of_the_surface_distance_entry_points():
     assert need > 0 and lib.oai_surface_distance_workspace_bytes(-1) == 0
     assert lib.oai_surface_distance_workspace_bytes(384 * 384 * 160) == lib.oai_surface_distance_workspace_bytes(1 << 40)      # the grid is capped
     assert call(*four, ws=need - 1) != 0 and b"oai_surface_distance: workspace" in err()
+
+
+@pytest.mark.parametrize("n", orr.ORDER_SIZES)
+def test_restated_order_is_a_valid_sum_and_not_the_serial_one(n):
+    """The restated tree is a summation (within the any-order bound of the exactly rounded sum), and from two blocks on it is
+    distinguishable from the plain left-to-right sum: that is what lets the GPU test tell orders apart."""
+    (sa, db, sb, da), want, terms, exact, serial = orr.order_case(n)
+    assert (want[0], want[1]) == (int(sa.sum()), int(sb.sum())) == (terms[0].size, terms[1].size) and want[0] >= 1 and want[1] >= 1
+    assert (want[4], want[5]) == (terms[0].max(), terms[1].max())
+    for k in (0, 1):
+        got = float(want[2 + k])
+        print(n, "direction", k, "terms", terms[k].size, "restated", got.hex(), "serial", serial[k].hex(), "fsum", exact[k].hex())
+        assert abs(got - exact[k]) <= terms[k].size * 2.0 ** -52 * exact[k]
+        if n >= 1025:
+            assert got != serial[k]
+        if terms[k].size == 1:
+            assert got == exact[k] == serial[k]
+
+
+def test_restated_tree_on_a_hand_checked_block():
+    """A case small enough to write the order out by hand (lanes 0, 1, 32 and 33 of wave 0, and lane 0 of wave 2), sums of small
+    integers, which no order rounds, and the runs of the finish step."""
+    v = np.zeros((orr.KT, 1))
+    v[[0, 1, 32, 33, 128], 0] = [1.0, 2.0 ** -53, 2.0 ** -53, 2.0 ** -53, 2.0 ** -53]
+    # off = 32: lane 0 = 1 + 2^-53 = 1 (ties to even), lane 1 = 2^-53 + 2^-53 = 2^-52; off = 1: lane 0 = 1 + 2^-52; then wave 2: ties to even, up
+    assert orr.block_reduce(v, ("add",))[0] == (1.0 + 2.0 ** -52) + 2.0 ** -52
+    assert float(np.add.accumulate(v[:, 0])[-1]) == 1.0                    # left to right every 2^-53 is lost
+    ints = np.arange(orr.KT * 3, dtype=np.float64).reshape(orr.KT, 3)
+    assert np.array_equal(orr.block_reduce(ints, ("add", "min", "max")), [ints[:, 0].sum(), 1.0, ints[:, 2].max()])
+    slots = np.arange(600.0).reshape(300, 2)                               # 300 slots: runs of two, threads 150.. stay cleared
+    runs = orr.reduce_slots(slots, [0.0, -np.inf], ("add", "max"))
+    assert np.array_equal(runs[:150, 0], slots[0::2, 0] + slots[1::2, 0]) and np.array_equal(runs[:150, 1], slots[1::2, 1])
+    assert np.array_equal(runs[150:], np.tile([0.0, -np.inf], (orr.KT - 150, 1)))
+    assert np.array_equal(orr.finish(slots, [0.0, -np.inf], ("add", "max")), [slots[:, 0].sum(), 599.0])

@@ -1,7 +1,8 @@
 """GPU: surface-distance QC (csrc/edt.hip; ops.mask_surface / distance_transform / signed_distance / surface_distance;
 qc.surface_distance, segmentation_qc, QCReference(surface=True), registration_qc) -- the squared distances bit for bit against the
 brute-force restatement of tests/edt_ref.py, the float32 distances to one step, the surfaces exactly, the figures on the device's own
-maps (counts, maxima and percentiles exactly, sums within the summation bound), and the record through every layer."""
+maps (counts, maxima and percentiles exactly, sums within the summation bound), the sums bit for bit against the restated order of
+csrc/ordered_reduce.h (tests/ordered_reduce_ref.py), and the record through every layer."""
 import dataclasses
 import functools
 import itertools
@@ -12,6 +13,7 @@ import pytest
 import torch
 
 import edt_ref as er
+import ordered_reduce_ref as orr
 import phi_jacobian_ref as pj
 from oai_analysis_2_amd import _lib, ops
 from oai_analysis_2_amd.image import Image
@@ -156,6 +158,25 @@ def test_surface_distance_figures_on_the_devices_own_maps(shape, spacing):
     assert np.array_equal(one.view(np.int64), again.view(np.int64)) and np.array_equal(one[:6], none[:6])
     out = torch.zeros(8, dtype=torch.float64, device="cuda")
     assert ops.surface_distance(*dev4, (95.0,), out=out) is out and np.array_equal(out.cpu().numpy().view(np.int64), one.view(np.int64))
+
+
+@pytest.mark.parametrize("n", orr.ORDER_SIZES)
+def test_sums_follow_the_restated_order_bit_for_bit(n):
+    """The summation order is the contract (csrc/ordered_reduce.h): on terms spread over 17 decades, where any other order gives
+    other bits (tests/test_edt_cpu.py asserts that the restated sum is not the serial one), the device equals the restatement."""
+    host4, want, terms, exact, _ = orr.order_case(n)
+    dev4 = tuple(dev(a) for a in host4)
+    s = ops.surface_distance(*dev4, ()).cpu().numpy()
+    print(n, "device", [float(v).hex() for v in s[:6]], "restated", [float(v).hex() for v in want])
+    assert (s[0], s[1]) == (want[0], want[1]) == (terms[0].size, terms[1].size)
+    assert (s[4], s[5]) == (want[4], want[5]) == (terms[0].max(), terms[1].max())
+    assert np.array_equal(s[2:4].view(np.int64), want[2:4].view(np.int64))
+    for k in (0, 1):
+        assert abs(s[2 + k] - exact[k]) <= terms[k].size * 2.0 ** -52 * exact[k]
+    assert np.isnan(s[6:]).all()
+    again = ops.surface_distance(*dev4, (50.0,)).cpu().numpy()                          # the same bits with the select behind it
+    assert np.array_equal(again[:6].view(np.int64), s[:6].view(np.int64))
+    assert np.float32(again[6]).view(np.int32) == np.percentile(np.concatenate([t.astype(np.float32) for t in terms]), 50.0).view(np.int32)
 
 
 def test_surface_distance_with_empty_surfaces():
