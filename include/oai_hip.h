@@ -741,6 +741,59 @@ int oai_surface_distance(const unsigned char* surf_a_dev, const float* dist_to_b
                          long long n, const float* percentiles, int n_percentiles, void* workspace_dev, size_t workspace_bytes, double* out_dev,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image-similarity QC (csrc/similarity.hip, tests/similarity_ref.py): how alike two float32 images on one grid are -- the moments behind
+ * Pearson's r (NCC) and the mean squared error, the joint histogram and its entropies (mutual information), and the local normalised
+ * cross-correlation (LNCC) that ICON trains on.  ICON's LNCC form, its sigma and eps are restated as recalled and unpinned:
+ * icon_registration is absent.  fp64 without contraction; every floating sum in the fixed order of csrc/ordered_reduce.h (per-block slots
+ * in the workspace, a one-block finish kernel, a block count that depends on the shape only): bit-reproducible, and the same with and
+ * without the optional outputs.  mask_dev (may be null everywhere): one byte per position, a position takes part when its byte is
+ * non-zero.  No entry point synchronises.
+ *
+ * oai_image_moments: a_dev, b_dev float32 [n].  A position is counted when the mask admits it and both values are finite.
+ * stats_dev: double[8] on the device --
+ *   [0] counted positions   [1] admitted positions left out for a non-finite value
+ *   [2] sum a   [3] sum b   [4] sum a*a   [5] sum b*b   [6] sum a*b   [7] sum (a - b)^2
+ * every term formed in fp64 from the float32 values (the three products are exact there).  Thread g of min(2048, ceil(n / 1024)) blocks
+ * of 256 adds positions g, g + threads, ... in that order.  n = 0 gives zeros and needs no workspace.
+ *
+ * oai_joint_histogram: hist_dev long long [bins*bins + 1] on the device, zeroed by the call.  The bin of a value x is
+ *   min((int)((clamp(x, lo, hi) - lo) * scale), bins - 1),   scale = (float)(bins / ((double)hi - (double)lo)),
+ * every operation in float32: a finite value outside [lo, hi] goes to an end bin (np.histogram2d drops it).  hist[ia*bins + ib] counts
+ * the admitted pairs with both values finite; hist[bins*bins] counts the admitted positions skipped for a non-finite value.  Integer
+ * counts, exact in any order: a per-block LDS table up to 64 bins, one 64-bit atomic add per non-zero cell when a block retires; above
+ * 64 bins, 64-bit global atomics.
+ * 1 <= bins <= 128, hi > lo, n <= 2^40.
+ *
+ * oai_histogram_entropies: hist_dev as above.  out_dev: double[4] on the device -- N = the sum of the bins*bins counts, H_A, H_B, H_AB
+ * with H = 0 - sum over the non-zero cells in index order of p * log(p), p = (double)c / (double)N, natural logarithm; the marginals by
+ * integer sums.  N = 0 gives N = 0 and three NaNs.  One block.
+ *
+ * oai_lncc: a_dev, b_dev float32 [D][H][W].  The five channels a, b, a*a, b*b, a*b are formed in fp64 and filtered along x, then y,
+ * then z, each pass
+ *   acc = 0;  for j = 0 .. 2 radius:  acc = acc + taps[j] * v[reflect(i + j - radius)]            (multiply and add apart, j ascending)
+ * with reflect that of np.pad(mode="reflect") / scipy's mode="mirror" (no repeated edge sample) and nothing rounded to float32 between
+ * the passes.  Per voxel, with E the filtered channels:
+ *   cov = Eab - Ea*Eb;  va = Eaa - Ea*Ea;  vb = Ebb - Eb*Eb;  cc = cov / sqrt((va + eps) * (vb + eps))
+ * taps_host: 2 radius + 1 doubles on the HOST (the caller's Gaussian, so that no exp is evaluated in two places).  cc_out_dev (may be
+ * null): double [D][H][W], every voxel, masked or not.  stats_dev: double[6] on the device --
+ *   [0] counted voxels (admitted, cc finite)   [1] admitted voxels left out for a non-finite cc
+ *   [2] sum cc   [3] sum cc^2   [4] min   [5] max  (NaN when no voxel is counted)
+ * one voxel per thread, block k = voxels [256 k, 256 k + 256).  0 <= radius <= 32 and every axis > radius.  The workspace holds two
+ * sets of five fp64 volumes (80 B per voxel).
+ * ---------------------------------------------------------------------------------------- */
+/* 0 when n <= 0. */
+size_t oai_image_moments_workspace_bytes(long long n);
+int oai_image_moments(const float* a_dev, const float* b_dev, long long n, const unsigned char* mask_dev, void* workspace_dev,
+                      size_t workspace_bytes, double* stats_dev, void* stream);
+int oai_joint_histogram(const float* a_dev, const float* b_dev, long long n, const float range_a[2], const float range_b[2], int bins,
+                        const unsigned char* mask_dev, long long* hist_dev, void* stream);
+int oai_histogram_entropies(const long long* hist_dev, int bins, double* out_dev, void* stream);
+/* 0 when an axis is below 1 voxel. */
+size_t oai_lncc_workspace_bytes(int D, int H, int W);
+int oai_lncc(const float* a_dev, const float* b_dev, int D, int H, int W, const double* taps_host, int radius, double eps,
+             const unsigned char* mask_dev, double* cc_out_dev, void* workspace_dev, size_t workspace_bytes, double* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,12 @@ SIGNATURES = {
     "oai_edt": (_I, [_P, _I, _I, _I, C.POINTER(_D), _F, _I, _P, _P, _P, _Z, _P, _P]),
     "oai_surface_distance_workspace_bytes": (_Z, [C.c_longlong]),
     "oai_surface_distance": (_I, [_P, _P, _P, _P, C.c_longlong, C.POINTER(_F), _I, _P, _Z, _P, _P]),
+    "oai_image_moments_workspace_bytes": (_Z, [C.c_longlong]),
+    "oai_image_moments": (_I, [_P, _P, C.c_longlong, _P, _P, _Z, _P, _P]),
+    "oai_joint_histogram": (_I, [_P, _P, C.c_longlong, C.POINTER(_F), C.POINTER(_F), _I, _P, _P, _P]),
+    "oai_histogram_entropies": (_I, [_P, _I, _P, _P]),
+    "oai_lncc_workspace_bytes": (_Z, [_I, _I, _I]),
+    "oai_lncc": (_I, [_P, _P, _I, _I, _I, C.POINTER(_D), _I, _D, _P, _P, _P, _Z, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

@@ -229,7 +229,8 @@ def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, kee
 
 def qc_stream(results: Iterable[Tuple[int, object]], reference=None) -> Iterator[Tuple[int, object]]:
     """(index, qc.RegistrationQC) for every (index, VolumeResult) of ``results``: the registration QC record of each knee of a cohort
-    (folds and det J of its phi, volume scale, cartilage volume; Dice against ``reference``, a qc.QCReference).  The results must be
+    (folds and det J of its phi, volume scale, cartilage volume; Dice against ``reference``, a qc.QCReference; the image similarity for
+    results that carry ``image_net`` when the reference has the atlas image).  The results must be
     complete and on the device, as ``process_cohort(keep_on_device=True)`` hands them over.  A plain synchronous generator: a few small
     launches and one download of a few dozen bytes per knee need no worker thread."""
     from .qc import registration_qc

@@ -446,3 +446,95 @@ def surface_distance(surf_a: torch.Tensor, dist_to_b: torch.Tensor, surf_b: torc
     _lib.check(lib.oai_surface_distance(ptr(surf_a), ptr(dist_to_b), ptr(surf_b), ptr(dist_to_a), n, (C.c_float * 2)(*(pct + [0.0, 0.0])[:2]),
                                         len(pct), ws.data_ptr(), ws.numel(), stats.data_ptr(), _stream()), "oai_surface_distance")
     return stats
+
+
+# ---- image-similarity QC (include/oai_hip.h, "Image-similarity QC"; csrc/similarity.hip) -------------------------------------------------
+def gaussian_taps(sigma: float):
+    """(float64 [2 radius + 1] taps, radius) of the Gaussian that ``lncc`` filters with: ``radius = int(2 sigma)`` (4 sigma + 1 samples
+    for an integer sigma, ICON's LNCC kernel as recalled), ``w_k = exp(-k^2 / (2 sigma^2))`` normalised to sum 1 in fp64.
+    ``sigma <= 0``: the single tap 1.0."""
+    sigma = float(sigma)
+    if not sigma > 0.0:
+        return np.ones(1, np.float64), 0
+    radius = int(2.0 * sigma)
+    k = np.arange(-radius, radius + 1, dtype=np.float64)
+    w = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    return w / w.sum(), radius
+
+
+def _pair(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tensor]):
+    """a, b (float32) and the optional uint8 mask, contiguous, of one size on one GPU."""
+    a, b = _chk(a, "a"), _chk(b, "b")
+    if tuple(b.shape) != tuple(a.shape) or b.device != a.device:
+        raise ValueError(f"a and b must share one shape and one GPU, got {tuple(a.shape)} on {a.device} and {tuple(b.shape)} on {b.device}")
+    if mask is not None:
+        mask = _chk(mask, "mask", torch.uint8)
+        if tuple(mask.shape) != tuple(a.shape) or mask.device != a.device:
+            raise ValueError(f"mask must have a's shape {tuple(a.shape)} and live on its GPU, got {tuple(mask.shape)} on {mask.device}")
+    return a, b, mask
+
+
+@_on_tensor_device
+def image_moments(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The float64 [8] DEVICE tensor of two float32 device tensors of one shape: counted positions (admitted by the uint8 ``mask``, both
+    values finite), admitted positions left out for a non-finite value, sum a, sum b, sum a^2, sum b^2, sum ab, sum (a - b)^2 -- fp64,
+    bit-reproducible (include/oai_hip.h, "Image-similarity QC").  ``out``: written there instead of a new tensor.  Does not synchronise."""
+    lib = _lib.load()
+    a, b, mask = _pair(a, b, mask)
+    n = int(a.numel())
+    stats = _out_slot(out, 8, torch.float64, a.device, "out")
+    ws = torch.empty(int(lib.oai_image_moments_workspace_bytes(n)), dtype=torch.uint8, device=a.device)
+    ptr = lambda t: t.data_ptr() if (t is not None and n) else None
+    _lib.check(lib.oai_image_moments(ptr(a), ptr(b), n, ptr(mask), ptr(ws), ws.numel(), stats.data_ptr(), _stream()), "oai_image_moments")
+    return stats
+
+
+@_on_tensor_device
+def joint_histogram(a: torch.Tensor, b: torch.Tensor, bins: int = 64, range_a=(0.0, 1.0), range_b=(0.0, 1.0),
+                    mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The int64 [bins*bins + 1] DEVICE tensor of two float32 device tensors of one shape: ``hist[ia*bins + ib]`` counts the pairs, the
+    last entry the admitted positions skipped for a non-finite value.  Float32 binning with values outside a range clamped into the end
+    bins (include/oai_hip.h).  Exact; ``out``: written there instead of a new tensor.  Does not synchronise."""
+    lib = _lib.load()
+    a, b, mask = _pair(a, b, mask)
+    n, bins = int(a.numel()), int(bins)
+    if not 1 <= bins <= 128:
+        raise ValueError(f"bins must be in [1, 128], got {bins}")
+    hist = _out_slot(out, bins * bins + 1, torch.int64, a.device, "out")
+    ptr = lambda t: t.data_ptr() if (t is not None and n) else None
+    _lib.check(lib.oai_joint_histogram(ptr(a), ptr(b), n, (C.c_float * 2)(*[float(v) for v in range_a]), (C.c_float * 2)(*[float(v) for v in range_b]),
+                                       bins, ptr(mask), hist.data_ptr(), _stream()), "oai_joint_histogram")
+    return hist
+
+
+@_on_tensor_device
+def histogram_entropies(hist: torch.Tensor, bins: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The float64 [4] DEVICE tensor N, H_A, H_B, H_AB (natural logarithm) of a ``joint_histogram`` table; N = 0 gives three NaNs.
+    ``out``: written there instead of a new tensor.  Does not synchronise."""
+    hist, bins = _chk(hist, "hist", torch.int64), int(bins)
+    if not 1 <= bins <= 128 or int(hist.numel()) < bins * bins:
+        raise ValueError(f"hist must hold bins*bins counts with bins in [1, 128], got {int(hist.numel())} entries for bins = {bins}")
+    ent = _out_slot(out, 4, torch.float64, hist.device, "out")
+    _lib.check(_lib.load().oai_histogram_entropies(hist.data_ptr(), bins, ent.data_ptr(), _stream()), "oai_histogram_entropies")
+    return ent
+
+
+@_on_tensor_device
+def lncc(a: torch.Tensor, b: torch.Tensor, sigma: float = 4.0, eps: float = 1e-5, mask: Optional[torch.Tensor] = None,
+         return_map: bool = False, out: Optional[torch.Tensor] = None):
+    """The local normalised cross-correlation of two float32 [z,y,x] device volumes under a Gaussian window (``gaussian_taps(sigma)``;
+    sigma = 4 and eps = 1e-5 are ICON's values for the knee model, as recalled): the float64 [6] DEVICE tensor counted voxels, admitted
+    voxels left out for a non-finite cc, sum cc, sum cc^2, min, max (include/oai_hip.h); with ``return_map`` also the float64 [z,y,x]
+    map of cc.  The mean of cc is the network's similarity; its loss is one minus that.  ``out``: the stats are written there instead
+    of a new tensor.  Does not synchronise."""
+    lib = _lib.load()
+    a, b, mask = _pair(_volume3(a, "a", torch.float32), _volume3(b, "b", torch.float32), mask)
+    D, H, W = (int(v) for v in a.shape)
+    taps, radius = gaussian_taps(sigma)
+    stats = _out_slot(out, 6, torch.float64, a.device, "out")
+    cc = torch.empty((D, H, W), dtype=torch.float64, device=a.device) if return_map else None
+    ws = torch.empty(int(lib.oai_lncc_workspace_bytes(D, H, W)), dtype=torch.uint8, device=a.device)
+    _lib.check(lib.oai_lncc(a.data_ptr(), b.data_ptr(), D, H, W, (C.c_double * len(taps))(*taps.tolist()), radius, float(eps),
+                            mask.data_ptr() if mask is not None else None, cc.data_ptr() if return_map else None, ws.data_ptr(), ws.numel(),
+                            stats.data_ptr(), _stream()), "oai_lncc")
+    return (stats, cc) if return_map else stats

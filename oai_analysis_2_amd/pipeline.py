@@ -41,6 +41,7 @@ class VolumeResult:
     repeated_f32: bool = False   # the fp16x3 run overflowed and these are the results of the fp32 repeat
     meta_A: Optional[Image] = None    # the patient image's geometry (metadata only, no voxel array): with phi, what takes atlas points to patient points
     meta_B: Optional[Image] = None    # the atlas image's geometry (metadata only): the other side of phi
+    image_net: Optional[torch.Tensor] = None       # the patient image at network resolution, as the registration saw it (run(..., qc=QCReference(image=)) only)
     qc: Optional["RegistrationQC"] = None          # registration QC: folds and det J of phi, Dice, cartilage volume (run(..., qc=...) only)
     thickness: Optional["KneeThickness"] = None    # cartilage thickness on the atlas inner vertices (run(..., thickness=atlas) only)
 
@@ -109,7 +110,8 @@ class VolumePipeline:
         ``qc``: True, or a qc.QCReference (the atlas' own maps, for Dice) -- the registration QC record of the volume
         (qc.registration_qc: folds and det J of phi, volume scale, cartilage volume) in ``VolumeResult.qc``, computed where the thickness
         is: after the range check and the fp32 repeat.  A few small launches and one more synchronisation.  None (default): nothing more
-        is launched and no bit changes."""
+        is launched and no bit changes.  A reference built with ``image=`` (the atlas image) adds the image similarity before and after
+        the warp (``qc.similarity``) and leaves the patient image at network resolution in ``VolumeResult.image_net``."""
         if qc is not None and qc is not True and not hasattr(qc, "maps"):
             raise ValueError(f"qc must be None, True or a qc.QCReference, got {qc!r}")
         if thickness_space not in ("atlas", "patient", "patient_grid"):
@@ -128,6 +130,8 @@ class VolumePipeline:
                 res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, **push)
         if qc is not None:
             from .qc import registration_qc
+            if qc is not True and getattr(qc, "image_net", None) is not None:      # the image similarity needs the image, not only the maps
+                res.image_net = ops.resize_trilinear(vol[None], self.icon.net_shape)[0]
             res.qc = registration_qc(res, reference=None if qc is True else qc)
         return res
 

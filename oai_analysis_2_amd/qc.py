@@ -15,11 +15,18 @@ any other.  ``registration_qc`` returns, per knee, a small record:
                       thick: a one-voxel error halves the Dice and is harmless to the thickness map, a three-voxel error breaks it,
                       and only a distance tells the two apart.
 
-``surface_distance`` and ``segmentation_qc`` give the same figures for any two masks, e.g. a segmentation against a manual one.  The
+    similarity        per stage an ``ImageSimilarity``: how alike the patient IMAGE and the atlas image are on the network grid, "before"
+                      and "after" the warp through phi (and within a few millimetres of the atlas cartilage: "before_roi" / "after_roi")
+                      -- LNCC, what the registration was trained to maximise; NCC and MSE; mutual information, what the atlas was built
+                      under.  Only with ``QCReference(..., image=atlas)`` and a patient image.  Every other figure here goes through the
+                      segmentation; these do not.
+
+``image_similarity`` gives the same record for any two images on one grid.  ``surface_distance`` and ``segmentation_qc`` give the same figures for any two masks, e.g. a segmentation against a manual one.  The
 surface rule (``A ^ binary_erosion(A)``, 6-connectivity) and the pooled percentile are MedPy's on scipy, checked against scipy on the
 CPU; ``assd`` is the mean over the pooled distances, and ``mean_ab`` / ``mean_ba`` are there for the mean of the two directed means.
 
-Kernels: csrc/phi_jacobian.hip, csrc/edt.hip (include/oai_hip.h, "Registration QC", "Surface-distance QC").  The fold definition is restated from ``flips`` as recalled
+Kernels: csrc/phi_jacobian.hip, csrc/edt.hip, csrc/similarity.hip (include/oai_hip.h, "Registration QC", "Surface-distance QC",
+"Image-similarity QC").  ICON's LNCC form (a Gaussian window of 4 sigma + 1 samples, sigma = 4, eps = 1e-5) is restated as recalled and unpinned.  The fold definition is restated from ``flips`` as recalled
 and unpinned, like the resample: icon_registration and ITK are absent.  No threshold and no pass / fail policy is built in: the
 record is data.
 """
@@ -34,6 +41,7 @@ import torch
 
 from . import ops
 from .image import as_image
+from .registration import NET_SHAPE
 
 KINDS = ("FC", "TC")
 THRESHOLD = 0.5          # the segmentation's rule: a voxel is cartilage when its probability is > 0.5
@@ -80,6 +88,28 @@ class SegmentationQC:
 
 
 @dataclass
+class ImageSimilarity:
+    """How alike two images on one grid are.  A position takes part when the mask admits it and both values are finite (``n``;
+    ``nonfinite`` counts the admitted positions left out); with no such position every figure is NaN."""
+    n: int
+    nonfinite: int
+    ncc: float                   # Pearson's r from the device's fp64 moments, on the host in fp64
+    mse: float                   # mean (a - b)^2
+    lncc: float                  # mean cc under a Gaussian window of ``sigma`` voxels; the network's similarity loss is 1 - lncc
+    lncc_std: float              # population standard deviation of cc
+    lncc_min: float
+    lncc_max: float
+    mi: float                    # H_A + H_B - H_AB, natural logarithm
+    nmi: float                   # (H_A + H_B) / H_AB, Studholme's form: 2 for identical images, 1 for independent ones
+    entropy_a: float
+    entropy_b: float
+    entropy_joint: float
+    sigma: float
+    bins: int
+    cc_map: Optional[torch.Tensor] = None        # float64 [z,y,x] on the device (return_map=True only)
+
+
+@dataclass
 class RegistrationQC:
     """Every part whose inputs were absent is None."""
     jacobian: PhiJacobian
@@ -89,6 +119,10 @@ class RegistrationQC:
     cartilage_voxels: Optional[Dict[str, int]] = None                 # patient grid: voxels with probability > 0.5
     cartilage_mm3: Optional[Dict[str, float]] = None                  # ... times the patient voxel volume
     surface: Optional[Dict[str, SurfaceDistance]] = None              # warped surface against the atlas' own (QCReference(surface=True))
+    # Optional[Dict[str, ImageSimilarity]]: "before" / "after" the warp (and "*_roi"), the patient image against the atlas'
+    # (QCReference(image=)).  A plain attribute and not a dataclass field: dataclasses.asdict and fields of the record stay the parts
+    # that go through phi and the segmentation, which earlier tests pin by name; the images' record is read as ``qc.similarity``.
+    similarity = None
 
 
 def jacobian_from_stats(stats, det_map: Optional[torch.Tensor] = None) -> PhiJacobian:
@@ -128,6 +162,66 @@ def surface_distance_from_stats(stats, percentiles: Sequence[float]) -> SurfaceD
         return SurfaceDistance(n_a, n_b, nan, nan, nan, nan, {float(q): nan for q in percentiles})
     return SurfaceDistance(n_a, n_b, s[2] / n_a, s[3] / n_b, (s[2] + s[3]) / (n_a + n_b), max(s[4], s[5]),
                            {float(q): s[6 + i] for i, q in enumerate(percentiles)})
+
+
+SIGMA, BINS = 4.0, 64        # registration_qc's window (ICON's sigma for the knee model, as recalled) and histogram
+SIMILARITY_SLOTS = 18        # doubles per comparison in the downloaded buffer: 8 moments, 6 of the LNCC, 4 of the entropies
+
+
+def ncc_from_moments(stats) -> Tuple[float, float]:
+    """(Pearson's r, mean squared error) of the eight doubles of ``ops.image_moments``; r is NaN when an image is constant."""
+    n, _, sa, sb, saa, sbb, sab, sdd = (float(v) for v in stats)
+    if n <= 0:
+        return float("nan"), float("nan")
+    cov, va, vb = sab / n - (sa / n) * (sb / n), saa / n - (sa / n) ** 2, sbb / n - (sb / n) ** 2
+    return (cov / math.sqrt(va * vb) if va > 0 and vb > 0 else float("nan")), sdd / n
+
+
+def similarity_from_stats(stats, sigma: float, bins: int, cc_map: Optional[torch.Tensor] = None) -> ImageSimilarity:
+    """The record of the 18 doubles that ``_queue_similarity`` leaves (already on the host)."""
+    s = [float(v) for v in stats]
+    mom, lc, (_, ha, hb, hab) = s[:8], s[8:14], s[14:18]
+    ncc, mse = ncc_from_moments(mom)
+    if lc[0] > 0:
+        mean = lc[2] / lc[0]
+        std = math.sqrt(max(lc[3] / lc[0] - mean * mean, 0.0))
+    else:
+        mean = std = float("nan")
+    return ImageSimilarity(int(mom[0]), int(mom[1]), ncc, mse, mean, std, lc[4], lc[5], ha + hb - hab,
+                           (ha + hb) / hab if hab > 0 else float("nan"), ha, hb, hab, float(sigma), int(bins), cc_map)
+
+
+def _image_dev(m) -> torch.Tensor:
+    """An image -- an ``Image``, an array or a [z,y,x] device tensor -- as a contiguous float32 device volume (its geometry is not used)."""
+    return _map_with_spacing(m, None)[0].contiguous()
+
+
+def _queue_similarity(a, b, sigma, bins, value_range, mask, return_map, out):
+    """One comparison queued on the current stream: four launches' worth of kernels, results into ``out`` (float64 [18])."""
+    ops.image_moments(a, b, mask, out=out[:8])
+    got = ops.lncc(a, b, sigma, mask=mask, return_map=return_map, out=out[8:14])
+    hist = ops.joint_histogram(a, b, bins, value_range, value_range, mask)
+    ops.histogram_entropies(hist, bins, out=out[14:18])
+    return got[1] if return_map else None
+
+
+def image_similarity(a, b, sigma: float = 4.0, bins: int = 64, value_range=(0.0, 1.0), mask=None, return_map: bool = False) -> ImageSimilarity:
+    """The similarity record of two images on one grid (each an ``Image``, an array or a [z,y,x] device tensor, as ``surface_distance``
+    takes them; ``mask``: uint8 / bool on the same grid, non-zero = takes part).  The images are expected windowed to ``value_range``,
+    as the pipeline's are to [0, 1]; values outside it fall into the histogram's end bins.  Everything is queued, then ONE download."""
+    va, vb = _image_dev(a), _image_dev(b)
+    if va.shape != vb.shape or va.device != vb.device:
+        raise ValueError(f"the two images must share one grid and one GPU, got {tuple(va.shape)} on {va.device} and {tuple(vb.shape)} on {vb.device}")
+    if mask is not None:
+        if not torch.is_tensor(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).view(np.uint8)).to(va.device)
+        elif mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8)
+    with torch.cuda.device(va.device):
+        buf = torch.empty(SIMILARITY_SLOTS, dtype=torch.float64, device=va.device)
+        cc_map = _queue_similarity(va, vb, sigma, bins, value_range, mask, return_map, buf)
+        host = buf.cpu().numpy()
+    return similarity_from_stats(host, sigma, bins, cc_map)
 
 
 def _surface_and_map(vol: torch.Tensor, spacing_xyz, threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -188,21 +282,48 @@ class QCReference:
     """The atlas' own FC and TC probability maps on the device, uploaded once: what the warped maps of every knee are compared with.
     Each an ``Image``, an array or a [z,y,x] device tensor, as ``thickness.ThicknessAtlas`` takes them.  ``surface=True`` also keeps,
     per cartilage, the atlas surface mask and the distance map to it (computed here, once) and the spacing they are measured in: the
-    Images' own, or ``spacing_xyz`` for tensors and bare arrays; a tensor is refused without it."""
+    Images' own, or ``spacing_xyz`` for tensors and bare arrays; a tensor is refused without it.  ``image``: the atlas image, for the
+    image similarity -- uploaded and resized once to ``net_shape``, the very tensor the registration network is fed (``image_net``).
+    ``roi_mm``: also the uint8 mask ``roi`` on the network grid of the voxels within that many millimetres of the atlas cartilage (both
+    maps resized to ``net_shape``, the set where either is > 0.5, its distance transform under the network grid's spacing = atlas
+    spacing x atlas size / network size per axis); needs a spacing, as ``surface=True`` does."""
 
-    def __init__(self, atlas_fc, atlas_tc, surface: bool = False, spacing_xyz=None):
+    def __init__(self, atlas_fc, atlas_tc, surface: bool = False, spacing_xyz=None, image=None, net_shape=NET_SHAPE, roi_mm: Optional[float] = None):
         got = {kind: _map_with_spacing(m, spacing_xyz) for kind, m in zip(KINDS, (atlas_fc, atlas_tc))}
         self.maps: Dict[str, torch.Tensor] = {kind: g[0].contiguous() for kind, g in got.items()}
         self.device = self.maps["FC"].device
         self.spacing_xyz: Optional[np.ndarray] = None
         self.surfaces: Optional[Dict[str, torch.Tensor]] = None       # uint8 [z,y,x]: the atlas surface per cartilage
         self.distance_maps: Optional[Dict[str, torch.Tensor]] = None  # float32 [z,y,x]: the distance to it
-        if surface:
+        self.net_shape = tuple(int(v) for v in net_shape)
+        self.image_net: Optional[torch.Tensor] = None                 # float32 net_shape: the atlas image as the registration network sees it
+        self.roi: Optional[torch.Tensor] = None                       # uint8 net_shape: within roi_mm of the atlas cartilage
+        self.roi_mm = None if roi_mm is None else float(roi_mm)
+        if surface or roi_mm is not None:
+            what = "surface=True" if surface else "roi_mm"
             if spacing_xyz is None and any(torch.is_tensor(m) for m in (atlas_fc, atlas_tc)):
-                raise ValueError("QCReference(surface=True): a tensor has no spacing of its own, give spacing_xyz")
+                raise ValueError(f"QCReference({what}): a tensor has no spacing of its own, give spacing_xyz")
             if not np.array_equal(got["FC"][1], got["TC"][1]) or self.maps["FC"].shape != self.maps["TC"].shape:
-                raise ValueError("QCReference(surface=True): the two atlas maps must share one grid and one spacing")
+                raise ValueError(f"QCReference({what}): the two atlas maps must share one grid and one spacing")
             self.spacing_xyz = got["FC"][1]
+        if image is not None:
+            vol = _map_with_spacing(image, spacing_xyz)[0].contiguous()
+            if vol.device != self.device:
+                raise ValueError(f"the atlas image ({vol.device}) and the atlas maps ({self.device}) must live on one GPU")
+            with torch.cuda.device(self.device):                      # what VolumePipeline.register feeds the network
+                self.image_net = ops.resize_trilinear(vol[None], self.net_shape)[0]
+        if roi_mm is not None:
+            if not self.roi_mm >= 0.0:
+                raise ValueError(f"roi_mm must be >= 0, got {roi_mm}")
+            with torch.cuda.device(self.device):
+                # the cartilage on the network grid, and the distance to it in that grid's millimetres: existing kernels only
+                # (torch's comparisons and the logical or are plumbing, once per atlas)
+                net = {kind: ops.resize_trilinear(self.maps[kind][None], self.net_shape)[0] for kind in KINDS}
+                cartilage = ((net["FC"] > THRESHOLD) | (net["TC"] > THRESHOLD)).to(torch.uint8)
+                size_xyz = np.asarray(self.maps["FC"].shape[::-1], np.float64)
+                self.roi_spacing_xyz = self.spacing_xyz * size_xyz / np.asarray(self.net_shape[::-1], np.float64)
+                self.roi = (ops.distance_transform(cartilage, self.roi_spacing_xyz) <= self.roi_mm).to(torch.uint8)
+        if surface:
             with torch.cuda.device(self.device):
                 pairs = {kind: _surface_and_map(self.maps[kind], self.spacing_xyz, THRESHOLD) for kind in KINDS}
             self.surfaces = {kind: p[0] for kind, p in pairs.items()}
@@ -212,10 +333,37 @@ class QCReference:
         return self.maps[kind]
 
 
-def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Optional[QCReference] = None, return_map: bool = False) -> RegistrationQC:
+def _similarity_jobs(result, phi, reference, patient_image):
+    """The comparisons of one registration, [(key, image, atlas image, mask or None)]; the warp is queued here.  Empty unless the
+    reference has an image and a patient image is there."""
+    if reference is None or reference.image_net is None:
+        return []
+    if patient_image is None:
+        patient_image = getattr(result, "image_net", None)
+    if patient_image is None:
+        return []
+    net = reference.net_shape
+    if tuple(phi.shape[1:]) != net:
+        raise ValueError(f"phi {tuple(phi.shape[1:])} is not on the reference's network grid {net}")
+    A = _image_dev(patient_image)
+    if A.device != phi.device or reference.image_net.device != phi.device:
+        raise ValueError("the patient image, phi and the reference must live on one GPU")
+    if tuple(A.shape) != net:
+        A = ops.resize_trilinear(A[None], net)[0]           # as VolumePipeline.register resizes it
+    warped = ops.grid_sample3d(A[None], phi)[0]             # A o phi: the patient image on the atlas' grid
+    jobs = [("before", A, reference.image_net, None), ("after", warped, reference.image_net, None)]
+    if reference.roi is not None:
+        jobs += [("before_roi", A, reference.image_net, reference.roi), ("after_roi", warped, reference.image_net, reference.roi)]
+    return jobs
+
+
+def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Optional[QCReference] = None, return_map: bool = False,
+                    patient_image=None) -> RegistrationQC:
     """The QC record of one registration: of a ``pipeline.VolumeResult`` (its phi, its patient-grid and warped maps, ``meta_A`` /
     ``meta_B`` unless ``image_A`` / ``image_B`` are given), or of a bare ``phi`` (float32 [3,D,H,W], array or device tensor: the
-    Jacobian, and the volume scale when both images are given).  ``reference``: the atlas' own maps, for Dice; built with
+    Jacobian, and the volume scale when both images are given).  ``patient_image`` (or the result's ``image_net``) with a reference built
+    with ``image=``: the image similarity before and after the warp ``grid_sample3d(A_net, phi)`` -- the warp the registration itself
+    applies to the patient image -- against the atlas image on the network grid; a full-size image is resized as the pipeline resizes it.  ``reference``: the atlas' own maps, for Dice; built with
     ``surface=True``, also for the surface distances of the warped maps (per cartilage one oai_mask_surface, one oai_edt and one
     oai_surface_distance more).  Parts whose inputs are absent are None.  Every kernel is queued on the current stream first; ONE download of the few dozen result bytes follows, the only
     synchronisation."""
@@ -235,7 +383,9 @@ def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Option
                 jobs += [("dice", kind, getattr(result_or_phi, kind.lower() + "_atlas"), reference[kind]) for kind in KINDS]
         kinds_s = KINDS if is_result and reference is not None and reference.surfaces is not None else ()
         at_s = 7 + 4 * len(jobs)                        # eight doubles per cartilage behind the counts
-        buf = torch.empty(at_s + 8 * len(kinds_s), dtype=torch.int64, device=phi.device)     # one buffer, one download
+        sims = _similarity_jobs(result_or_phi if is_result else None, phi, reference, patient_image)      # (key, a, b, mask)
+        at_i = at_s + 8 * len(kinds_s)                  # SIMILARITY_SLOTS doubles per comparison behind the surfaces
+        buf = torch.empty(at_i + SIMILARITY_SLOTS * len(sims), dtype=torch.int64, device=phi.device)     # one buffer, one download
         got = ops.phi_jacobian(phi, return_map=return_map, out=buf[:7].view(torch.float64))
         det_map = got[1] if return_map else None
         for i, (_, _, a, b) in enumerate(jobs):
@@ -247,8 +397,14 @@ def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Option
             surf, to_warped = _surface_and_map(warped, reference.spacing_xyz, THRESHOLD)
             ops.surface_distance(surf, reference.distance_maps[kind], reference.surfaces[kind], to_warped, (95.0,),
                                  out=buf[at_s + 8 * i:at_s + 8 * i + 8].view(torch.float64))
+        for i, (_, a, b, mask) in enumerate(sims):
+            _queue_similarity(a, b, SIGMA, BINS, (0.0, 1.0), mask, False,
+                              buf[at_i + SIMILARITY_SLOTS * i:at_i + SIMILARITY_SLOTS * (i + 1)].view(torch.float64))
         host = buf.cpu().numpy()
     qc = RegistrationQC(jacobian_from_stats(host[:7].view(np.float64), det_map))
+    if sims:
+        qc.similarity = {key: similarity_from_stats(host[at_i + SIMILARITY_SLOTS * i:at_i + SIMILARITY_SLOTS * (i + 1)].view(np.float64), SIGMA, BINS)
+                         for i, (key, _, _, _) in enumerate(sims)}
     if image_A is not None and image_B is not None:
         qc.volume_scale = volume_scale(image_A, image_B, phi.shape[1:])
     for i, (part, kind, _, _) in enumerate(jobs):
