@@ -794,6 +794,53 @@ size_t oai_lncc_workspace_bytes(int D, int H, int W);
 int oai_lncc(const float* a_dev, const float* b_dev, int D, int H, int W, const double* taps_host, int radius, double eps,
              const unsigned char* mask_dev, double* cc_out_dev, void* workspace_dev, size_t workspace_bytes, double* stats_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Segmentation-shape QC (csrc/components.hip, tests/components_ref.py): 3-D connected-component labelling of a voxel set, the
+ * reference-free check of a segmentation -- how many pieces, how much of it in the largest, how much in islands, how many closed
+ * cavities -- and the primitive that cleans a mask.  The numbering is that of scipy.ndimage.label(mask,
+ * generate_binary_structure(3, r)), r = 1, 2, 3, checked against scipy on the CPU (tests/test_components_cpu.py).
+ *
+ * oai_label_components.  The set: exactly one of map_dev and mask_dev is non-null.  map_dev float32 [D][H][W]: a voxel is in the set
+ * when its value is finite and > threshold (the rule of oai_mask_overlap and oai_mask_surface; the threshold may not be NaN).
+ * mask_dev one byte per voxel: in the set when the byte is != 0.  complement != 0 labels the voxels that are NOT in the set; a
+ * non-finite value is then in the complement, as in mode 2 of oai_mask_surface.  connectivity is 6, 18 or 26: two voxels of the
+ * labelled set are joined when they share a face; a face or an edge; a face, an edge or a corner.  A component is a class of the
+ * transitive closure.
+ *   labels_dev (may be null) int32 [D][H][W]: 0 outside the labelled set; the components are numbered 1..K in raster order of each
+ *     component's first voxel (its voxel with the smallest index (z H + y) W + x).
+ *   size_dev (may be null) int32 [D][H][W]: the voxel count of the component that the voxel belongs to, 0 outside the labelled set --
+ *     so that "drop everything below n voxels" and "keep the largest" are element-wise operations on the device.
+ *   summary_dev: long long[12] on the device, integers and therefore exact --
+ *     [0] voxels = D H W   [1] voxels of the labelled set   [2] K, the number of components
+ *     [3] the size of the largest component (0 when K = 0)   [4] its label, on a tie the smallest (0 when K = 0)
+ *     [5] the size of the second largest (0 when K < 2; equal to [3] on a tie)
+ *     [6] components with size < min_voxels   [7] the voxels in them
+ *     [8] components that touch the border of the volume (a voxel with an index 0 or n - 1 on some axis)   [9] the voxels in them
+ *     [10] non-finite positions of map_dev (0 with mask_dev)   [11] 0
+ *   The summary does not depend on labels_dev or size_dev being null.
+ * How: a union-find over the voxels whose representative is the SMALLEST LINEAR INDEX of the component.  A parent link only ever
+ * moves to a smaller index of the same component (integer atomicMin), so every tree ends rooted at its component's first voxel
+ * whatever order the workgroups ran in: labels, sizes and summary are a function of the input alone, bit-identical from run to run.
+ * A brick of 4 x 4 x 64 voxels is merged in LDS; neighbouring bricks are merged across their faces (for 18 and 26 also across their
+ * edges and corners) in global memory, one returning atomic per pair of voxels whose roots still differ; parents are flattened, the
+ * size and the border flag of each component accumulated at its root's own index in the workspace (integer atomicAdd / atomicOr); the
+ * label is 1 + the exclusive scan of the root flags over the volume (per-block counts, one block over the block partials in the
+ * order of csrc/ordered_reduce.h, a last pass that writes labels_dev and size_dev).  No floating-point value is reduced.  No
+ * rounds: nothing can fail to converge, no flag is read back, and stream order is the only grid-wide synchronisation.  Does not
+ * synchronise.  Every axis in [1, 32767] and D H W <= 2^31 - 1 (indices are int32); min_voxels >= 0.  The workspace holds the parents
+ * and the per-root accumulators, 8 bytes per voxel, and about 0.1 byte per voxel of block partials.
+ *
+ * oai_component_sizes: labels_dev int32 [n].  sizes_dev[k - 1] = the number of positions with label k, k = 1..n_components, long long
+ * on the device; the call clears the table itself.  A label outside 0..n_components is ignored.  n = 0 or n_components = 0 is a
+ * successful no-op.  Integer atomicAdd: exact in any order.  Does not synchronise.
+ * ---------------------------------------------------------------------------------------- */
+/* 0 when an axis is outside [1, 32767] or D*H*W > 2^31 - 1. */
+size_t oai_label_components_workspace_bytes(int D, int H, int W);
+int oai_label_components(const float* map_dev, const unsigned char* mask_dev, int D, int H, int W, float threshold, int complement,
+                         int connectivity, long long min_voxels, int* labels_dev, int* size_dev, void* workspace_dev, size_t workspace_bytes,
+                         long long* summary_dev, void* stream);
+int oai_component_sizes(const int* labels_dev, long long n, long long n_components, long long* sizes_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,9 @@ SIGNATURES = {
     "oai_histogram_entropies": (_I, [_P, _I, _P, _P]),
     "oai_lncc_workspace_bytes": (_Z, [_I, _I, _I]),
     "oai_lncc": (_I, [_P, _P, _I, _I, _I, C.POINTER(_D), _I, _D, _P, _P, _P, _Z, _P, _P]),
+    "oai_label_components_workspace_bytes": (_Z, [_I, _I, _I]),
+    "oai_label_components": (_I, [_P, _P, _I, _I, _I, _F, _I, _I, C.c_longlong, _P, _P, _P, _Z, _P, _P]),
+    "oai_component_sizes": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

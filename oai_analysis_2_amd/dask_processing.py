@@ -238,6 +238,15 @@ def qc_stream(results: Iterable[Tuple[int, object]], reference=None) -> Iterator
         yield index, registration_qc(res, reference=reference)
 
 
+def seg_qc_stream(results: Iterable[Tuple[int, object]], **kwargs) -> Iterator[Tuple[int, object]]:
+    """(index, {"FC": qc.SegmentationShape, "TC": ...}) for every (index, VolumeResult) of ``results``: the reference-free shape record
+    of each knee's patient-grid maps (qc.result_segmentation_shapes; ``kwargs``: threshold, connectivity, min_voxels, band).  The results
+    must be complete and on the device, as for ``qc_stream``; like it a plain synchronous generator, one download per knee."""
+    from .qc import result_segmentation_shapes
+    for index, res in results:
+        yield index, result_segmentation_shapes(res, **kwargs)
+
+
 def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None,
                              space: str = "atlas") -> Iterator[Tuple[int, object]]:
     """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the

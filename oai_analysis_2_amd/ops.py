@@ -538,3 +538,51 @@ def lncc(a: torch.Tensor, b: torch.Tensor, sigma: float = 4.0, eps: float = 1e-5
                             mask.data_ptr() if mask is not None else None, cc.data_ptr() if return_map else None, ws.data_ptr(), ws.numel(),
                             stats.data_ptr(), _stream()), "oai_lncc")
     return (stats, cc) if return_map else stats
+
+
+# ---- segmentation-shape QC (include/oai_hip.h, "Segmentation-shape QC"; csrc/components.hip) ---------------------------------------------
+SUMMARY_SLOTS = 12           # int64 per labelling call: include/oai_hip.h, oai_label_components
+
+
+@_on_tensor_device
+def label_components(map_or_mask: torch.Tensor, threshold: float = 0.5, connectivity: int = 26, complement: bool = False, min_voxels: int = 0,
+                     return_labels: bool = True, return_sizes: bool = False, out: Optional[torch.Tensor] = None):
+    """The connected components of a [z,y,x] device volume under 6, 18 or 26 connectivity.  A float32 tensor is a map: the set is
+    ``finite and > threshold``; a uint8 or bool tensor is a mask: the set is ``!= 0``.  ``complement``: label what is NOT in the set.
+    Returns ``(summary, labels, sizes)``: the int64 [12] DEVICE summary (voxels, voxels of the set, K, largest size, its label, second
+    largest, components below ``min_voxels`` and their voxels, components touching the border and their voxels, non-finite positions,
+    0; ``out``: written there instead of a new tensor); int32 labels, 0 off the set and 1..K in raster order of each component's first
+    voxel -- ``scipy.ndimage.label`` to the element -- or None; the int32 per-voxel size of the voxel's component, or None.
+    Deterministic; does not synchronise."""
+    lib = _lib.load()
+    if map_or_mask.dtype == torch.bool:
+        map_or_mask = map_or_mask.view(torch.uint8)
+    if map_or_mask.dtype not in (torch.float32, torch.uint8):
+        raise _lib.OaiError(f"map_or_mask must be float32 (a map) or uint8 / bool (a mask), got {map_or_mask.dtype}")
+    is_map = map_or_mask.dtype == torch.float32
+    vol = _volume3(map_or_mask, "map_or_mask", map_or_mask.dtype)
+    D, H, W = (int(v) for v in vol.shape)
+    summary = _out_slot(out, SUMMARY_SLOTS, torch.int64, vol.device, "out")
+    labels = torch.empty((D, H, W), dtype=torch.int32, device=vol.device) if return_labels else None
+    sizes = torch.empty((D, H, W), dtype=torch.int32, device=vol.device) if return_sizes else None
+    ws = torch.empty(int(lib.oai_label_components_workspace_bytes(D, H, W)), dtype=torch.uint8, device=vol.device)
+    _lib.check(lib.oai_label_components(vol.data_ptr() if is_map else None, None if is_map else vol.data_ptr(), D, H, W, float(threshold),
+                                        int(bool(complement)), int(connectivity), int(min_voxels), labels.data_ptr() if return_labels else None,
+                                        sizes.data_ptr() if return_sizes else None, ws.data_ptr() if ws.numel() else None, ws.numel(),
+                                        summary.data_ptr(), _stream()), "oai_label_components")
+    return summary, labels, sizes
+
+
+@_on_tensor_device
+def component_sizes(labels: torch.Tensor, n_components: int) -> torch.Tensor:
+    """The int64 [n_components] DEVICE table of voxel counts per label 1..n_components of an int32 label volume (``np.bincount(labels)[1:]``);
+    labels outside 0..n_components are ignored.  Does not synchronise."""
+    labels = _chk(labels, "labels", torch.int32)
+    k = int(n_components)
+    if k < 0:
+        raise ValueError(f"n_components must be >= 0, got {n_components}")
+    n = int(labels.numel())
+    sizes = (torch.empty if n else torch.zeros)(k, dtype=torch.int64, device=labels.device)     # the call clears the table unless it is a no-op
+    _lib.check(_lib.load().oai_component_sizes(labels.data_ptr() if n else None, n, k, sizes.data_ptr() if k else None, _stream()),
+               "oai_component_sizes")
+    return sizes

@@ -44,6 +44,9 @@ class VolumeResult:
     image_net: Optional[torch.Tensor] = None       # the patient image at network resolution, as the registration saw it (run(..., qc=QCReference(image=)) only)
     qc: Optional["RegistrationQC"] = None          # registration QC: folds and det J of phi, Dice, cartilage volume (run(..., qc=...) only)
     thickness: Optional["KneeThickness"] = None    # cartilage thickness on the atlas inner vertices (run(..., thickness=atlas) only)
+    # Optional[Dict[str, qc.SegmentationShape]]: the shape record of the patient-grid maps ``fc`` / ``tc`` (run(..., seg_qc=True) only).  A
+    # plain attribute and not a dataclass field, like RegistrationQC.similarity: the fields of the result stay the ones earlier tests pin.
+    seg_qc = None
 
 
 class VolumePipeline:
@@ -100,7 +103,7 @@ class VolumePipeline:
 
     # ---- one volume, one GPU --------------------------------------------------------------------------------------------------
     def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None,
-            thickness_space: str = "atlas", qc=None) -> VolumeResult:
+            thickness_space: str = "atlas", qc=None, seg_qc: bool = False) -> VolumeResult:
         """``thickness``: a thickness.ThicknessAtlas -- the volume's cartilage thickness on the atlas inner vertices is measured from
         ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
         None (default): nothing more is launched.  ``thickness_space``: "atlas" (default) = the distance on the atlas grid, as the
@@ -111,7 +114,10 @@ class VolumePipeline:
         (qc.registration_qc: folds and det J of phi, volume scale, cartilage volume) in ``VolumeResult.qc``, computed where the thickness
         is: after the range check and the fp32 repeat.  A few small launches and one more synchronisation.  None (default): nothing more
         is launched and no bit changes.  A reference built with ``image=`` (the atlas image) adds the image similarity before and after
-        the warp (``qc.similarity``) and leaves the patient image at network resolution in ``VolumeResult.image_net``."""
+        the warp (``qc.similarity``) and leaves the patient image at network resolution in ``VolumeResult.image_net``.
+        ``seg_qc``: True -- the reference-free shape record of the patient-grid maps (qc.segmentation_shapes: components, islands,
+        cavities of ``fc`` and ``tc`` with ``meta_A``'s spacing) as ``{"FC": ..., "TC": ...}`` in ``VolumeResult.seg_qc``, computed where ``qc``
+        is; both cartilages are queued before the one download.  False (default): nothing more is launched and no bit changes."""
         if qc is not None and qc is not True and not hasattr(qc, "maps"):
             raise ValueError(f"qc must be None, True or a qc.QCReference, got {qc!r}")
         if thickness_space not in ("atlas", "patient", "patient_grid"):
@@ -133,6 +139,9 @@ class VolumePipeline:
             if qc is not True and getattr(qc, "image_net", None) is not None:      # the image similarity needs the image, not only the maps
                 res.image_net = ops.resize_trilinear(vol[None], self.icon.net_shape)[0]
             res.qc = registration_qc(res, reference=None if qc is True else qc)
+        if seg_qc:
+            from .qc import result_segmentation_shapes
+            res.seg_qc = result_segmentation_shapes(res)
         return res
 
     def rerun_f32(self, vol: torch.Tensor, meta_A: Image, sharded_group="none") -> VolumeResult:

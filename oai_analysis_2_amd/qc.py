@@ -21,12 +21,19 @@ any other.  ``registration_qc`` returns, per knee, a small record:
                       under.  Only with ``QCReference(..., image=atlas)`` and a patient image.  Every other figure here goes through the
                       segmentation; these do not.
 
+``segmentation_shape`` needs nothing to compare with: per map a ``SegmentationShape`` -- the connected pieces of the cartilage mask,
+the share of the largest, what sits in islands, the closed cavities, the voxels of uncertain probability.  A failed segmentation
+(cartilage in several pieces, a blob in the muscle, a sheet full of holes) shows there and nowhere else.  Two labelling calls per
+map (the set under ``connectivity``, its complement under the dual connectivity) and two overlap counts, queued and downloaded once;
+``clean_segmentation`` drops the islands on the device; ``VolumePipeline.run(seg_qc=True)`` returns the records of the patient-grid
+maps in ``VolumeResult.seg_qc``.  The labelling is ``scipy.ndimage.label``'s to the element, checked against scipy on the CPU.
+
 ``image_similarity`` gives the same record for any two images on one grid.  ``surface_distance`` and ``segmentation_qc`` give the same figures for any two masks, e.g. a segmentation against a manual one.  The
 surface rule (``A ^ binary_erosion(A)``, 6-connectivity) and the pooled percentile are MedPy's on scipy, checked against scipy on the
 CPU; ``assd`` is the mean over the pooled distances, and ``mean_ab`` / ``mean_ba`` are there for the mean of the two directed means.
 
-Kernels: csrc/phi_jacobian.hip, csrc/edt.hip, csrc/similarity.hip (include/oai_hip.h, "Registration QC", "Surface-distance QC",
-"Image-similarity QC").  ICON's LNCC form (a Gaussian window of 4 sigma + 1 samples, sigma = 4, eps = 1e-5) is restated as recalled and unpinned.  The fold definition is restated from ``flips`` as recalled
+Kernels: csrc/phi_jacobian.hip, csrc/edt.hip, csrc/similarity.hip, csrc/components.hip (include/oai_hip.h, "Registration QC",
+"Surface-distance QC", "Image-similarity QC", "Segmentation-shape QC").  ICON's LNCC form (a Gaussian window of 4 sigma + 1 samples, sigma = 4, eps = 1e-5) is restated as recalled and unpinned.  The fold definition is restated from ``flips`` as recalled
 and unpinned, like the resample: icon_registration and ITK are absent.  No threshold and no pass / fail policy is built in: the
 record is data.
 """
@@ -426,3 +433,127 @@ def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Option
         qc.surface = {kind: surface_distance_from_stats(host[at_s + 8 * i:at_s + 8 * i + 8].view(np.float64), (95.0,))
                       for i, kind in enumerate(kinds_s)}
     return qc
+
+
+# ---- segmentation-shape QC (include/oai_hip.h, "Segmentation-shape QC"; csrc/components.hip) ---------------------------------------------
+@dataclass
+class SegmentationShape:
+    """The shape of one segmentation map, with nothing to compare it with: the connected components of the set ``> threshold`` under
+    ``connectivity``, and the closed cavities -- the components of its complement, under the dual connectivity (6 for 18 and 26, 26 for
+    6), that do not touch the border of the volume.  All counts are exact."""
+    voxels: int                  # voxels of the set
+    mm3: Optional[float]         # ... times the voxel volume (None without a spacing)
+    components: int
+    largest_voxels: int
+    largest_fraction: float      # largest_voxels / voxels, NaN for an empty set
+    islands: int                 # components - 1, at least 0
+    island_voxels: int           # voxels - largest_voxels
+    small_components: int        # components below min_voxels
+    small_voxels: int
+    border_components: int       # components with a voxel on the border of the volume
+    cavities: int
+    cavity_voxels: int           # with a 6-connected background: binary_fill_holes(set).sum() - set.sum()
+    uncertain_voxels: int        # |p > band[0]| - |p > band[1]|: voxels the network was not sure about
+    nonfinite: int               # non-finite values of the map (in no set)
+    connectivity: int
+    min_voxels: int
+
+
+SHAPE_SLOTS = 2 * ops.SUMMARY_SLOTS + 8      # int64 per map in the downloaded buffer: two labelling summaries, two overlap counts
+
+
+def dual_connectivity(connectivity: int) -> int:
+    """The connectivity of the background that goes with a foreground connectivity (the digital Jordan theorem needs the pair)."""
+    if connectivity not in (6, 18, 26):
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity}")
+    return 26 if connectivity == 6 else 6
+
+
+def shape_from_summaries(fg, bg, n_over_lo: int, n_over_hi: int, connectivity: int, min_voxels: int,
+                         voxel_mm3: Optional[float] = None) -> SegmentationShape:
+    """The record of the summary of the set, the summary of its complement under the dual connectivity and the two band counts (already
+    on the host)."""
+    voxels, k, largest = int(fg[1]), int(fg[2]), int(fg[3])
+    return SegmentationShape(voxels, None if voxel_mm3 is None else voxels * float(voxel_mm3), k, largest,
+                             largest / voxels if voxels else float("nan"), max(k - 1, 0), voxels - largest, int(fg[6]), int(fg[7]), int(fg[8]),
+                             int(bg[2]) - int(bg[8]), int(bg[1]) - int(bg[9]), int(n_over_lo) - int(n_over_hi), int(fg[10]),
+                             int(connectivity), int(min_voxels))
+
+
+def _queue_shape(vol: torch.Tensor, threshold, connectivity, min_voxels, band, out: torch.Tensor) -> None:
+    """One map queued on the current stream, results into ``out`` (int64 [SHAPE_SLOTS]): nothing is returned to the host here."""
+    k = ops.SUMMARY_SLOTS
+    ops.label_components(vol, threshold, connectivity, False, min_voxels, return_labels=False, out=out[:k])
+    ops.label_components(vol, threshold, dual_connectivity(connectivity), True, 0, return_labels=False, out=out[k:2 * k])
+    ops.mask_overlap(vol, None, float(band[0]), out=out[2 * k:2 * k + 4])
+    ops.mask_overlap(vol, None, float(band[1]), out=out[2 * k + 4:2 * k + 8])
+
+
+def _shape_from_host(host, connectivity, min_voxels, spacing) -> SegmentationShape:
+    k = ops.SUMMARY_SLOTS
+    return shape_from_summaries(host[:k], host[k:2 * k], host[2 * k], host[2 * k + 4], connectivity, min_voxels,
+                                None if spacing is None else float(np.prod(np.asarray(spacing, np.float64))))
+
+
+def _check_shape_args(connectivity, min_voxels, band) -> None:
+    dual_connectivity(connectivity)
+    if int(min_voxels) < 0:
+        raise ValueError(f"min_voxels must be >= 0, got {min_voxels}")
+    if len(band) != 2 or not float(band[0]) <= float(band[1]):
+        raise ValueError(f"band must be (low, high) with low <= high, got {band!r}")
+
+
+def segmentation_shapes(maps: Dict[str, object], spacing_xyz=None, threshold: float = 0.5, connectivity: int = 26, min_voxels: int = 0,
+                        band=(0.1, 0.9)) -> Dict[str, SegmentationShape]:
+    """``segmentation_shape`` of several maps on one GPU, all queued before the ONE download."""
+    _check_shape_args(connectivity, min_voxels, band)
+    got = {key: _map_with_spacing(m, spacing_xyz) for key, m in maps.items()}
+    vols = {key: g[0].contiguous() for key, g in got.items()}
+    spacing = {key: (None if spacing_xyz is None and (torch.is_tensor(maps[key]) or isinstance(maps[key], np.ndarray)) else g[1])
+               for key, g in got.items()}
+    if not vols:
+        return {}
+    device = next(iter(vols.values())).device
+    if any(v.device != device for v in vols.values()):
+        raise ValueError("the maps must live on one GPU")
+    with torch.cuda.device(device):
+        buf = torch.empty(SHAPE_SLOTS * len(vols), dtype=torch.int64, device=device)
+        for i, vol in enumerate(vols.values()):
+            _queue_shape(vol, threshold, connectivity, min_voxels, band, buf[SHAPE_SLOTS * i:SHAPE_SLOTS * (i + 1)])
+        host = buf.cpu().numpy()
+    return {key: _shape_from_host(host[SHAPE_SLOTS * i:SHAPE_SLOTS * (i + 1)], connectivity, min_voxels, spacing[key])
+            for i, key in enumerate(vols)}
+
+
+def segmentation_shape(map, spacing_xyz=None, threshold: float = 0.5, connectivity: int = 26, min_voxels: int = 0,
+                       band=(0.1, 0.9)) -> SegmentationShape:
+    """The shape record of one probability map (an ``Image``, an array or a [z,y,x] device tensor, as ``surface_distance`` takes them;
+    ``spacing_xyz`` goes with arrays and tensors, and without it ``mm3`` is None): two ``ops.label_components`` -- the set ``> threshold``
+    under ``connectivity``, its complement under the dual connectivity -- and two ``ops.mask_overlap`` for the band of uncertain
+    probabilities, queued into one int64 buffer; ONE download, the only synchronisation.  No threshold for "bad" is built in: the
+    record is data."""
+    return segmentation_shapes({"map": map}, spacing_xyz, threshold, connectivity, min_voxels, band)["map"]
+
+
+def clean_segmentation(map, keep_largest: bool = True, min_voxels: int = 0, threshold: float = 0.5, connectivity: int = 26) -> torch.Tensor:
+    """The map as a float32 device tensor with the voxels of dropped components set to 0.  ``keep_largest``: only the largest
+    component of the set ``> threshold`` stays (on a tie the one that comes first in raster order: the summary's label); otherwise every
+    component of at least ``min_voxels`` voxels stays.  Voxels that are not in the set are left as they are.  One labelling call; the
+    choice is made on the device from the per-voxel sizes and the summary (the element-wise ``torch.where`` is plumbing): no host round
+    trip and no synchronisation."""
+    if int(min_voxels) < 0:
+        raise ValueError(f"min_voxels must be >= 0, got {min_voxels}")
+    vol = _image_dev(map)
+    with torch.cuda.device(vol.device):
+        summary, labels, sizes = ops.label_components(vol, threshold, connectivity, False, int(min_voxels), return_labels=bool(keep_largest),
+                                                      return_sizes=not keep_largest)
+        drop = (labels != 0) & (labels != summary[4].to(torch.int32)) if keep_largest else (sizes != 0) & (sizes < int(min_voxels))
+        return torch.where(drop, torch.zeros((), dtype=vol.dtype, device=vol.device), vol)
+
+
+def result_segmentation_shapes(result, **kwargs) -> Dict[str, SegmentationShape]:
+    """``{"FC": ..., "TC": ...}``: the shape records of the patient-grid maps ``fc`` / ``tc`` of a ``pipeline.VolumeResult``, with the
+    spacing of its ``meta_A`` (``mm3`` is None without one).  Both maps are queued before the one download."""
+    meta = getattr(result, "meta_A", None)
+    spacing = None if meta is None else np.asarray(as_image(meta).spacing, np.float64)
+    return segmentation_shapes({kind: getattr(result, kind.lower()) for kind in KINDS}, spacing, **kwargs)
