@@ -183,5 +183,35 @@ def check(status: int, what: str = "") -> None:
         raise OaiError(f"{what or 'liboai_hip'} failed ({status}): {msg.decode() if msg else '?'}")
 
 
+STREAM = object()          # among call()'s arguments: "the current stream of ``device``", wherever the entry point takes its stream
+
+
+def call(name: str, *args, device=None) -> None:
+    """``load().<name>(*args)`` under the calling convention every entry point of the C ABI shares, spelled here and nowhere else:
+    the library launches (and a create call allocates) on the current HIP device, so ``device`` is made current around the call; every
+    ``STREAM`` among ``args`` becomes that device's current stream; a non-zero status raises OaiError under the symbol's name with
+    ``oai_last_error()``.  ``device`` None: a host-only entry point, which touches no GPU and takes no stream."""
+    if name not in SIGNATURES:
+        raise OaiError(f"{name} is not an entry point of liboai_hip.so (include/oai_hip.h declares none of that name)")
+    if device is None:
+        if any(a is STREAM for a in args):
+            raise ValueError(f"{name}: STREAM stands for the current stream of a device, and no device was given")
+        check(getattr(load(), name)(*args), name)
+        return
+    import torch
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        check(getattr(load(), name)(*[stream if a is STREAM else a for a in args]), name)
+
+
+def workspace(family: str, device, *size_args, pad: bool = False):
+    """The uint8 device buffer that lib.<family>_workspace_bytes(*size_args) asks for.  The library answers 0 for sizes it refuses.
+    ``pad``: then one byte all the same, so that the entry point's own argument check names the fault instead of its null-pointer
+    check (components and the circle fit, whose callers may pass an empty mesh)."""
+    import torch
+    n = int(getattr(load(), family + "_workspace_bytes")(*size_args))
+    return torch.empty(max(n, 1) if pad else n, dtype=torch.uint8, device=device)
+
+
 def int3(v):
     return (C.c_int * 3)(int(v[0]), int(v[1]), int(v[2]))

@@ -101,32 +101,20 @@ def _dev(a, dtype, tail=(), device=None) -> torch.Tensor:
     return (t.reshape(-1, *tail) if tail else t).contiguous()
 
 
-def _call(name: str, device, *args) -> None:
-    """lib.<name>(*args, stream) on ``device`` and its current stream; a non-zero status raises OaiError under the symbol's name."""
-    with torch.cuda.device(device):
-        _lib.check(getattr(_lib.load(), name)(*args, torch.cuda.current_stream().cuda_stream), name)
-
-
-def _workspace(family: str, device, *size_args, pad: bool = False) -> torch.Tensor:
-    """The uint8 device buffer that lib.<family>_workspace_bytes(*size_args) asks for.  The library answers 0 for sizes it refuses.
-    ``pad``: then one byte all the same, so that the entry point's own argument check names the fault instead of its null-pointer
-    check (components and the circle fit, whose callers may pass an empty mesh)."""
-    n = int(getattr(_lib.load(), family + "_workspace_bytes")(*size_args))
-    return torch.empty(max(n, 1) if pad else n, dtype=torch.uint8, device=device)
-
-
 # ---- marching cubes ----------------------------------------------------------------------------------------------------------
 def _marching_cubes_dev(vol: torch.Tensor, level: float, spacing_xyz) -> Tuple[torch.Tensor, torch.Tensor]:
     """(verts float32 [n,3], faces int32 [m,3]) of the iso-surface, left on the volume's device."""
     vol = _dev(vol, np.float32)
     D, H, W = (int(v) for v in vol.shape)
-    ws = _workspace("oai_mc", vol.device, D, H, W)
+    ws = _lib.workspace("oai_mc", vol.device, D, H, W)
     nv, nt = C.c_longlong(), C.c_longlong()
-    _call("oai_mc_count", vol.device, vol.data_ptr(), D, H, W, float(level), ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nt))
+    _lib.call("oai_mc_count", vol.data_ptr(), D, H, W, float(level), ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nt), _lib.STREAM,
+              device=vol.device)
     verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
     faces = torch.empty((nt.value, 3), dtype=torch.int32, device=vol.device)
     sp = (C.c_float * 3)(*[float(v) for v in spacing_xyz])
-    _call("oai_mc_emit", vol.device, vol.data_ptr(), D, H, W, float(level), sp, ws.data_ptr(), verts.data_ptr(), faces.data_ptr())
+    _lib.call("oai_mc_emit", vol.data_ptr(), D, H, W, float(level), sp, ws.data_ptr(), verts.data_ptr(), faces.data_ptr(), _lib.STREAM,
+              device=vol.device)
     return verts, faces
 
 
@@ -178,9 +166,9 @@ def mesh_components_device(faces, n_verts: int, return_rounds: bool = False):
     f = _dev(faces, np.int32, (3,))
     nf, n = int(f.shape[0]), int(n_verts)
     label = torch.empty(n, dtype=torch.int32, device=f.device)
-    ws = _workspace("oai_mesh_components", f.device, n, nf, pad=True)
+    ws = _lib.workspace("oai_mesh_components", f.device, n, nf, pad=True)
     rounds = C.c_int()
-    _call("oai_mesh_components", f.device, f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), label.data_ptr(), C.byref(rounds))
+    _lib.call("oai_mesh_components", f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), label.data_ptr(), C.byref(rounds), _lib.STREAM, device=f.device)
     return (label, rounds.value) if return_rounds else label
 
 
@@ -188,11 +176,11 @@ def keep_large_regions_device(verts, faces, min_cells: int = 3000) -> Tuple[torc
     """keep_large_regions on the GPU: torch tensors in (float32 [n,3], int32 [m,3]), device tensors out, equal to the host's."""
     v, f = _dev(verts, np.float32, (3,)), _dev(faces, np.int32, (3,))
     nv, nf = int(v.shape[0]), int(f.shape[0])
-    ws = _workspace("oai_mesh_keep_large_regions", v.device, nv, nf)
+    ws = _lib.workspace("oai_mesh_keep_large_regions", v.device, nv, nf)
     vo, fo = torch.empty_like(v), torch.empty_like(f)
     n_v, n_f = C.c_longlong(), C.c_longlong()
-    _call("oai_mesh_keep_large_regions", v.device, v.data_ptr(), nv, f.data_ptr(), nf, int(min_cells), ws.data_ptr(), ws.numel(), vo.data_ptr(),
-          fo.data_ptr(), C.byref(n_v), C.byref(n_f))
+    _lib.call("oai_mesh_keep_large_regions", v.data_ptr(), nv, f.data_ptr(), nf, int(min_cells), ws.data_ptr(), ws.numel(), vo.data_ptr(),
+              fo.data_ptr(), C.byref(n_v), C.byref(n_f), _lib.STREAM, device=v.device)
     return vo[:n_v.value], fo[:n_f.value]
 
 
@@ -200,18 +188,19 @@ def vertex_adjacency_device(n_verts: int, faces) -> Tuple[torch.Tensor, torch.Te
     """vertex_adjacency on the GPU: int32 device tensors (offsets [n+1], neighbours), equal to the host's."""
     f = _dev(faces, np.int32, (3,))
     n, nf = int(n_verts), int(f.shape[0])
-    ws = _workspace("oai_mesh_adjacency", f.device, n, nf)
+    ws = _lib.workspace("oai_mesh_adjacency", f.device, n, nf)
     off = torch.empty(n + 1, dtype=torch.int32, device=f.device)
     nbr = torch.empty(max(6 * nf, 1), dtype=torch.int32, device=f.device)
     n_nbrs = C.c_longlong()
-    _call("oai_mesh_adjacency", f.device, f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), off.data_ptr(), nbr.data_ptr(), C.byref(n_nbrs))
+    _lib.call("oai_mesh_adjacency", f.data_ptr(), nf, n, ws.data_ptr(), ws.numel(), off.data_ptr(), nbr.data_ptr(), C.byref(n_nbrs), _lib.STREAM,
+              device=f.device)
     return off, nbr[:n_nbrs.value]
 
 
 def _smooth_dev(v: torch.Tensor, off: torch.Tensor, nbr: torch.Tensor, num_iterations: int, relaxation_factor: float) -> torch.Tensor:
     tmp, out = torch.empty_like(v), torch.empty_like(v)
-    _call("oai_mesh_smooth", v.device, v.data_ptr(), int(v.shape[0]), off.data_ptr(), nbr.data_ptr(), int(num_iterations), float(relaxation_factor),
-          tmp.data_ptr(), out.data_ptr())
+    _lib.call("oai_mesh_smooth", v.data_ptr(), int(v.shape[0]), off.data_ptr(), nbr.data_ptr(), int(num_iterations), float(relaxation_factor),
+              tmp.data_ptr(), out.data_ptr(), _lib.STREAM, device=v.device)
     return out
 
 
@@ -286,21 +275,23 @@ def cuberille_device(image, iso_surface_value: float = 0.5, *, generate_triangle
     D, H, W = (int(v) for v in vol.shape)
     geo = np.concatenate([o, s, d.reshape(-1), np.linalg.inv(d @ np.diag(s)).reshape(-1)])
     flip = bool(np.linalg.det(d) < 0)
-    ws = _workspace("oai_cuberille", vol.device, D, H, W)
+    ws = _lib.workspace("oai_cuberille", vol.device, D, H, W)
     if ws.numel() == 0:
         raise ValueError(f"cuberille: volume {D}x{H}x{W} is empty or too large")
     nv, nf = C.c_longlong(), C.c_longlong()
     iso = float(iso_surface_value)
-    _call("oai_cuberille_count", vol.device, vol.data_ptr(), D, H, W, iso, ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nf))
+    _lib.call("oai_cuberille_count", vol.data_ptr(), D, H, W, iso, ws.data_ptr(), ws.numel(), C.byref(nv), C.byref(nf), _lib.STREAM,
+              device=vol.device)
     verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
     faces = torch.empty((2 * nf.value, 3) if generate_triangle_faces else (nf.value, 4), dtype=torch.int32, device=vol.device)
     steps = torch.empty(nv.value, dtype=torch.int32, device=vol.device)
     if nv.value == 0:                                                # nothing inside: no faces either
         return verts, faces, steps
-    _call("oai_cuberille_emit", vol.device, vol.data_ptr(), D, H, W, iso, (C.c_double * 24)(*[float(x) for x in geo]), int(flip),
-          int(bool(generate_triangle_faces)), int(bool(project_vertices_to_iso_surface)), float(project_vertex_surface_distance_threshold),
-          float(project_vertex_step_length), float(project_vertex_step_length_relaxation_factor), int(project_vertex_maximum_number_of_steps),
-          int(bool(move_after_converged)), ws.data_ptr(), ws.numel(), nv.value, nf.value, verts.data_ptr(), faces.data_ptr(), steps.data_ptr())
+    _lib.call("oai_cuberille_emit", vol.data_ptr(), D, H, W, iso, (C.c_double * 24)(*[float(x) for x in geo]), int(flip),
+              int(bool(generate_triangle_faces)), int(bool(project_vertices_to_iso_surface)), float(project_vertex_surface_distance_threshold),
+              float(project_vertex_step_length), float(project_vertex_step_length_relaxation_factor), int(project_vertex_maximum_number_of_steps),
+              int(bool(move_after_converged)), ws.data_ptr(), ws.numel(), nv.value, nf.value, verts.data_ptr(), faces.data_ptr(), steps.data_ptr(),
+              _lib.STREAM, device=vol.device)
     return verts, faces, steps
 
 
@@ -434,18 +425,18 @@ def _split_dev(v: torch.Tensor, f: torch.Tensor, mesh_type: str) -> DeviceSplit:
     nv, nf = int(v.shape[0]), int(f.shape[0])
     if nf < 2:
         raise ValueError(f"n_samples={nf} should be >= n_clusters=2.")
-    ws = _workspace("oai_mesh_split", v.device, nv, nf, _MESH_TYPE[kind], _N_INIT[kind])
+    ws = _lib.workspace("oai_mesh_split", v.device, nv, nf, _MESH_TYPE[kind], _N_INIT[kind])
     cent = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
     nrm = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
     side = torch.empty(nf, dtype=torch.int8, device=v.device)
     counts = (C.c_longlong * 3)()
-    _call("oai_mesh_split_features", v.device, v.data_ptr(), nv, f.data_ptr(), nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), cent.data_ptr(),
-          nrm.data_ptr(), counts)
+    _lib.call("oai_mesh_split_features", v.data_ptr(), nv, f.data_ptr(), nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), cent.data_ptr(),
+              nrm.data_ptr(), counts, _lib.STREAM, device=v.device)
     n_slabs = 3 if kind == "FC" else 1
     first, uni = _kmeans_draws(list(counts)[:n_slabs], _N_INIT[kind])
     n_iter = (C.c_int * 3)()
-    _call("oai_mesh_split_kmeans", v.device, nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), nrm.data_ptr(), _N_INIT[kind], _KMEANS_MAX_ITER, counts,
-          (C.c_longlong * len(first))(*first), (C.c_double * len(uni))(*uni), side.data_ptr(), n_iter)
+    _lib.call("oai_mesh_split_kmeans", nf, _MESH_TYPE[kind], ws.data_ptr(), ws.numel(), nrm.data_ptr(), _N_INIT[kind], _KMEANS_MAX_ITER, counts,
+              (C.c_longlong * len(first))(*first), (C.c_double * len(uni))(*uni), side.data_ptr(), n_iter, _lib.STREAM, device=v.device)
     return DeviceSplit(v, f, side, cent, nrm, np.array(list(n_iter)[:n_slabs], dtype=np.int64))
 
 
@@ -464,13 +455,13 @@ def _sub_mesh_dev(split: DeviceSplit, which: int) -> Tuple[torch.Tensor, torch.T
     """get_sub_mesh_device, left on the device: (verts, faces, face list int32)."""
     nv, nf = int(split.verts.shape[0]), int(split.faces.shape[0])
     dev = split.verts.device
-    ws = _workspace("oai_mesh_submesh", dev, nv, nf)
+    ws = _lib.workspace("oai_mesh_submesh", dev, nv, nf)
     vo = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     fo = torch.empty((nf, 3), dtype=torch.int32, device=dev)
     io = torch.empty(nf, dtype=torch.int32, device=dev)
     n_v, n_f = C.c_longlong(), C.c_longlong()
-    _call("oai_mesh_submesh", dev, split.verts.data_ptr(), nv, split.faces.data_ptr(), nf, split.side.data_ptr(), int(which), ws.data_ptr(),
-          ws.numel(), vo.data_ptr(), fo.data_ptr(), io.data_ptr(), C.byref(n_v), C.byref(n_f))
+    _lib.call("oai_mesh_submesh", split.verts.data_ptr(), nv, split.faces.data_ptr(), nf, split.side.data_ptr(), int(which), ws.data_ptr(),
+              ws.numel(), vo.data_ptr(), fo.data_ptr(), io.data_ptr(), C.byref(n_v), C.byref(n_f), _lib.STREAM, device=dev)
     return vo[:n_v.value], fo[:n_f.value], io[:n_f.value]
 
 
@@ -527,8 +518,9 @@ def mesh_grid_params_device(verts, faces) -> Tuple[np.ndarray, np.ndarray, np.fl
     from device tensors, with one 56-byte download."""
     v, f = _dev(verts, np.float32, (3,)), _dev(faces, np.int32, (3,))
     out = torch.empty(7, dtype=torch.float64, device=v.device)
-    ws = _workspace("oai_mesh_grid_params", v.device)
-    _call("oai_mesh_grid_params", v.device, v.data_ptr(), int(v.shape[0]), f.data_ptr(), int(f.shape[0]), ws.data_ptr(), ws.numel(), out.data_ptr())
+    ws = _lib.workspace("oai_mesh_grid_params", v.device)
+    _lib.call("oai_mesh_grid_params", v.data_ptr(), int(v.shape[0]), f.data_ptr(), int(f.shape[0]), ws.data_ptr(), ws.numel(), out.data_ptr(),
+              _lib.STREAM, device=v.device)
     o = out.cpu().numpy()
     return o[0:3].copy(), o[3:6].copy(), np.sqrt(o[6])          # sqrt is monotone and correctly rounded: the max of the host's norms
 
@@ -541,11 +533,11 @@ def _point_distance_dev(p: torch.Tensor, v: torch.Tensor, f: torch.Tensor, grid=
         h, dims, lo = _grid_from_params(*grid)
         glo = (C.c_float * 3)(*[float(x) for x in lo])
         gd = (C.c_int * 3)(*[int(x) for x in dims])
-        ws = _workspace("oai_mesh_grid", p.device, gd, n_tris)
-        _call("oai_mesh_point_distance_grid", p.device, p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, glo, float(h), gd, ws.data_ptr(),
-              ws.numel(), out.data_ptr())
+        ws = _lib.workspace("oai_mesh_grid", p.device, gd, n_tris)
+        _lib.call("oai_mesh_point_distance_grid", p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, glo, float(h), gd, ws.data_ptr(),
+                  ws.numel(), out.data_ptr(), _lib.STREAM, device=p.device)
     else:
-        _call("oai_mesh_point_distance", p.device, p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, out.data_ptr())
+        _lib.call("oai_mesh_point_distance", p.data_ptr(), n_points, v.data_ptr(), f.data_ptr(), n_tris, out.data_ptr(), _lib.STREAM, device=p.device)
     return out
 
 
@@ -730,9 +722,9 @@ def _map_attributes_dev(src_verts: torch.Tensor, src_vals: torch.Tensor, tgt_ver
     h, dims, lo = _grid_from_params(lo, hi, radius)
     glo = (C.c_double * 3)(*[float(x) for x in lo])
     gd = (C.c_int * 3)(*[int(x) for x in dims])
-    ws = _workspace("oai_point_grid", src_verts.device, gd, n_src)
-    _call("oai_map_attributes_grid", src_verts.device, src_verts.data_ptr(), n_src, src_vals.data_ptr(), n_comp, tgt_verts.data_ptr(), n_tgt,
-          float(radius), glo, float(h), gd, ws.data_ptr(), ws.numel(), out.data_ptr())
+    ws = _lib.workspace("oai_point_grid", src_verts.device, gd, n_src)
+    _lib.call("oai_map_attributes_grid", src_verts.data_ptr(), n_src, src_vals.data_ptr(), n_comp, tgt_verts.data_ptr(), n_tgt, float(radius), glo,
+              float(h), gd, ws.data_ptr(), ws.numel(), out.data_ptr(), _lib.STREAM, device=src_verts.device)
     return out
 
 
@@ -759,7 +751,8 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
         out = _map_attributes_dev(s, v, t, radius, grid=(source_mesh.verts.min(axis=0).astype(np.float64), source_mesh.verts.max(axis=0).astype(np.float64)))
     else:
         out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=s.device)
-        _call("oai_map_attributes", s.device, s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr())
+        _lib.call("oai_map_attributes", s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr(), _lib.STREAM,
+                  device=s.device)
     res = out.cpu().numpy()
     row = 0
     for name, shape in names:
@@ -771,9 +764,10 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
 
 def _fit_circle_dev(pts: torch.Tensor, col_x: int, col_y: int) -> Tuple[np.ndarray, float]:
     n = int(pts.shape[0])
-    ws = _workspace("oai_thickness_map", pts.device, n, pad=True)
+    ws = _lib.workspace("oai_thickness_map", pts.device, n, pad=True)
     centre, radius, its = (C.c_double * 2)(), C.c_double(), C.c_int()
-    _call("oai_fit_circle", pts.device, pts.data_ptr(), n, col_x, col_y, ws.data_ptr(), ws.numel(), centre, C.byref(radius), C.byref(its))
+    _lib.call("oai_fit_circle", pts.data_ptr(), n, col_x, col_y, ws.data_ptr(), ws.numel(), centre, C.byref(radius), C.byref(its), _lib.STREAM,
+              device=pts.device)
     return np.array([centre[0], centre[1]], dtype=np.float64), float(radius.value)
 
 
@@ -804,7 +798,7 @@ def _project_circle_dev(pts: torch.Tensor, col_x: int, col_y: int, centre) -> Tu
     angle = torch.empty(n, dtype=torch.float64, device=pts.device)
     z = torch.empty(n, dtype=torch.float64, device=pts.device)
     c = (C.c_double * 2)(float(centre[0]), float(centre[1]))
-    _call("oai_project_circle", pts.device, pts.data_ptr(), n, col_x, col_y, c, angle.data_ptr(), z.data_ptr())
+    _lib.call("oai_project_circle", pts.data_ptr(), n, col_x, col_y, c, angle.data_ptr(), z.data_ptr(), _lib.STREAM, device=pts.device)
     return angle.cpu().numpy(), z.cpu().numpy()
 
 
@@ -854,11 +848,11 @@ def project_thickness(mapped_mesh: Mesh, mesh_type: str = "FC", embedded=None) -
     if not (z >= 50).any() or not (z < 50).any():
         raise ValueError("project_thickness(TC): one tibial plateau is empty (no point with z < 50 or none with z >= 50)")
     th = _dev(thickness, np.float32)
-    ws = _workspace("oai_thickness_map", pts.device, n)
+    ws = _lib.workspace("oai_thickness_map", pts.device, n)
     out = torch.empty((3, n), dtype=torch.float64, device=pts.device)
     n_right, n_left = C.c_longlong(), C.c_longlong()
-    _call("oai_project_plateaus", pts.device, pts.data_ptr(), th.data_ptr(), n, ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(),
-          out[2].data_ptr(), C.byref(n_right), C.byref(n_left))
+    _lib.call("oai_project_plateaus", pts.data_ptr(), th.data_ptr(), n, ws.data_ptr(), ws.numel(), out[0].data_ptr(), out[1].data_ptr(),
+              out[2].data_ptr(), C.byref(n_right), C.byref(n_left), _lib.STREAM, device=pts.device)
     res = out[:, :n_right.value + n_left.value].cpu().numpy()
     return res[0].copy(), res[1].copy(), res[2].copy()
 
@@ -917,11 +911,11 @@ def thickness_image_build(uv, faces, face_skip=None, image_shape=(256, 256)) -> 
     owner = torch.empty((H, W), dtype=torch.int32, device=dev)
     corners = torch.empty((H, W, 3), dtype=torch.int32, device=dev)
     weights = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
-    ws = _workspace("oai_thickness_image", dev, n_faces, H, W)
+    ws = _lib.workspace("oai_thickness_image", dev, n_faces, H, W)
     n_cov = C.c_longlong()
-    _call("oai_thickness_image_build", dev, uv_d.data_ptr(), n_pts, f.data_ptr(), n_faces, skip.data_ptr() if skip is not None else None,
-          (C.c_double * 2)(*lo), (C.c_double * 2)(*step), H, W, ws.data_ptr(), ws.numel(), owner.data_ptr(), corners.data_ptr(), weights.data_ptr(),
-          C.byref(n_cov))
+    _lib.call("oai_thickness_image_build", uv_d.data_ptr(), n_pts, f.data_ptr(), n_faces, skip.data_ptr() if skip is not None else None,
+              (C.c_double * 2)(*lo), (C.c_double * 2)(*step), H, W, ws.data_ptr(), ws.numel(), owner.data_ptr(), corners.data_ptr(),
+              weights.data_ptr(), C.byref(n_cov), _lib.STREAM, device=dev)
     return ThicknessRaster(owner, corners, weights, lo, step, int(n_cov.value), n_pts)
 
 
@@ -937,7 +931,7 @@ def thickness_image(raster: ThicknessRaster, values):
     img = torch.empty((K, H, W), dtype=torch.float32, device=v.device)
     for k0 in range(0, K, 65535):
         k1 = min(K, k0 + 65535)
-        _call("oai_thickness_image_apply", v.device, raster.owner.data_ptr(), raster.corners.data_ptr(), raster.weights.data_ptr(), H, W,
-              v.reshape(K, -1)[k0:k1].data_ptr(), raster.n_points, k1 - k0, img[k0:k1].data_ptr())
+        _lib.call("oai_thickness_image_apply", raster.owner.data_ptr(), raster.corners.data_ptr(), raster.weights.data_ptr(), H, W,
+                  v.reshape(K, -1)[k0:k1].data_ptr(), raster.n_points, k1 - k0, img[k0:k1].data_ptr(), _lib.STREAM, device=v.device)
     img = img[0] if v.dim() == 1 else img
     return img if on_dev else img.cpu().numpy()

@@ -1,8 +1,9 @@
 """Tensor-level wrappers over the C ABI (torch is plumbing: device memory + the current stream).
 
 Every function takes contiguous fp32 ``torch`` tensors on the HIP device, passes ``data_ptr()``
-and the current stream to liboai_hip.so, and returns the output tensor.  No torch compute op is
-used on the product path.
+to liboai_hip.so through ``_lib.call`` -- which makes the named device (the one the output is
+allocated on) current and fills in its current stream where ``_lib.STREAM`` stands -- and returns
+the output tensor.  No torch compute op is used on the product path.
 """
 from __future__ import annotations
 
@@ -16,28 +17,6 @@ import torch
 from . import _lib
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _on_tensor_device(fn):
-    """Run ``fn`` with the device of its first tensor argument current: the C ABI launches on the current HIP device and takes the
-    current stream, so a tensor on another GPU of the process must switch both."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(*args, **kwargs):
-        for a in list(args) + list(kwargs.values()):
-            if torch.is_tensor(a) and a.is_cuda:
-                with torch.cuda.device(a.device):
-                    return fn(*args, **kwargs)
-            if isinstance(a, (list, tuple)) and a and torch.is_tensor(a[0]) and a[0].is_cuda:
-                with torch.cuda.device(a[0].device):
-                    return fn(*args, **kwargs)
-        return fn(*args, **kwargs)
-    return wrapper
-
-
 def _chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     if not t.is_cuda:
         raise _lib.OaiError(f"{name} must live on the GPU (the HIP path has no CPU fallback)")
@@ -46,16 +25,42 @@ def _chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+check_tensor = _chk          # for the package's other modules (qc.py)
+
+
+def _ptr(t: Optional[torch.Tensor], n: int = 1):
+    """What the C ABI takes for an optional tensor: its address, or NULL for an absent one and for every tensor of a call over
+    ``n`` = 0 elements."""
+    return t.data_ptr() if (t is not None and n) else None
+
+
+def _is_phi(t: torch.Tensor) -> bool:
+    return t.dim() == 4 and t.shape[0] == 3
+
+
+def _check_phi(phi: torch.Tensor) -> None:
+    if not _is_phi(phi):
+        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+
+
+def _check_points(points: torch.Tensor) -> None:
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n,3], got {tuple(points.shape)}")
+
+
+def _check_same_gpu(name_a: str, a: torch.Tensor, name_b: str, b: torch.Tensor) -> None:
+    if b.device != a.device:
+        raise ValueError(f"{name_a} ({a.device}) and {name_b} ({b.device}) must live on the same GPU")
+
+
 def warp_set_option(name: str, value: int) -> None:
     """Process-wide tuning option of the warp kernels (include/oai_hip.h: oai_warp_set_option): "brick" 0|1 -- grid_sample3d / compose through
     the LDS-staged brick kernel; bit-identical outputs."""
-    _lib.check(_lib.load().oai_warp_set_option(name.encode(), int(value)), "oai_warp_set_option")
+    _lib.call("oai_warp_set_option", name.encode(), int(value))
 
 
-@_on_tensor_device
 def grid_sample3d(src: torch.Tensor, coords: Optional[torch.Tensor], out_shape: Optional[Sequence[int]] = None) -> torch.Tensor:
     """src [C,d,h,w], coords [3,D,H,W] in [0,1] (None = identity of out_shape) -> [C,D,H,W]."""
-    lib = _lib.load()
     src = _chk(src, "src")
     Cn, d, h, w = src.shape
     if coords is not None:
@@ -64,16 +69,13 @@ def grid_sample3d(src: torch.Tensor, coords: Optional[torch.Tensor], out_shape: 
     else:
         D, H, W = out_shape
     out = torch.empty((Cn, D, H, W), dtype=torch.float32, device=src.device)
-    _lib.check(lib.oai_grid_sample3d(src.data_ptr(), Cn, d, h, w, coords.data_ptr() if coords is not None else None,
-                                     D, H, W, out.data_ptr(), _stream()), "oai_grid_sample3d")
+    _lib.call("oai_grid_sample3d", src.data_ptr(), Cn, d, h, w, _ptr(coords), D, H, W, out.data_ptr(), _lib.STREAM, device=src.device)
     return out
 
 
-@_on_tensor_device
 def compose(disp: torch.Tensor, coords: Optional[torch.Tensor], out_shape: Optional[Sequence[int]] = None,
             shortcut: bool = True) -> torch.Tensor:
     """coords + sample(disp, coords); coords None = identity map of out_shape (or of disp's grid)."""
-    lib = _lib.load()
     disp = _chk(disp, "disp")
     _, d, h, w = disp.shape
     if coords is not None:
@@ -82,20 +84,17 @@ def compose(disp: torch.Tensor, coords: Optional[torch.Tensor], out_shape: Optio
     else:
         D, H, W = out_shape if out_shape is not None else (d, h, w)
     out = torch.empty((3, D, H, W), dtype=torch.float32, device=disp.device)
-    _lib.check(lib.oai_compose(disp.data_ptr(), d, h, w, coords.data_ptr() if coords is not None else None,
-                               D, H, W, int(shortcut), out.data_ptr(), _stream()), "oai_compose")
+    _lib.call("oai_compose", disp.data_ptr(), d, h, w, _ptr(coords), D, H, W, int(shortcut), out.data_ptr(), _lib.STREAM, device=disp.device)
     return out
 
 
-@_on_tensor_device
 def warp_chain(out_shape: Sequence[int], fields: Sequence[torch.Tensor] = (), start: Optional[torch.Tensor] = None,
                image: Optional[torch.Tensor] = None) -> torch.Tensor:
     """c = identity(out_shape) [+ start]; c = c + sample(f, c) for f in fields (<= 8 = OAI_WARP_CHAIN_MAX_FIELDS); returns sample(image, c) [D,H,W] when an
     image [d,h,w] is given, else c [3,D,H,W].  One launch, bit-identical to the compose / grid_sample3d calls it replaces."""
-    lib = _lib.load()
     D, H, W = (int(v) for v in out_shape)
     fields = [_chk(f, "field") for f in fields]
-    if len(fields) > 8 or any(f.dim() != 4 or f.shape[0] != 3 for f in fields):
+    if len(fields) > 8 or not all(_is_phi(f) for f in fields):
         raise ValueError("at most eight fields, each [3,d,h,w]")
     dev = (fields[0] if fields else start if start is not None else image).device
     if start is not None:
@@ -110,41 +109,33 @@ def warp_chain(out_shape: Sequence[int], fields: Sequence[torch.Tensor] = (), st
     dims = (C.c_int * max(3, 3 * len(fields)))(*[int(v) for f in fields for v in f.shape[1:]])
     out = torch.empty((D, H, W) if image is not None else (3, D, H, W), dtype=torch.float32, device=dev)
     idims = tuple(image.shape) if image is not None else (0, 0, 0)
-    with torch.cuda.device(dev):
-        _lib.check(lib.oai_warp_chain(start.data_ptr() if start is not None else None, D, H, W, len(fields), ptrs, dims,
-                                      image.data_ptr() if image is not None else None, *idims, out.data_ptr(), _stream()), "oai_warp_chain")
+    _lib.call("oai_warp_chain", _ptr(start), D, H, W, len(fields), ptrs, dims, _ptr(image), *idims, out.data_ptr(), _lib.STREAM, device=dev)
     return out
 
 
-@_on_tensor_device
 def avgpool2(x: torch.Tensor) -> torch.Tensor:
-    lib = _lib.load()
     x = _chk(x, "x")
     Cn, D, H, W = x.shape
     out = torch.empty((Cn, (D + 1) // 2, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device)
-    _lib.check(lib.oai_avgpool2_3d(x.data_ptr(), Cn, D, H, W, out.data_ptr(), _stream()), "oai_avgpool2_3d")
+    _lib.call("oai_avgpool2_3d", x.data_ptr(), Cn, D, H, W, out.data_ptr(), _lib.STREAM, device=x.device)
     return out
 
 
-@_on_tensor_device
 def resize_trilinear(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
-    lib = _lib.load()
     x = _chk(x, "x")
     Cn, d, h, w = x.shape
     D, H, W = (int(v) for v in size)
     out = torch.empty((Cn, D, H, W), dtype=torch.float32, device=x.device)
-    _lib.check(lib.oai_resize_trilinear(x.data_ptr(), Cn, d, h, w, out.data_ptr(), D, H, W, _stream()), "oai_resize_trilinear")
+    _lib.call("oai_resize_trilinear", x.data_ptr(), Cn, d, h, w, out.data_ptr(), D, H, W, _lib.STREAM, device=x.device)
     return out
 
 
-@_on_tensor_device
 def phi_to_itk_displacement(phi: torch.Tensor) -> torch.Tensor:
     """phi [3,D,H,W] -> float64 [D,H,W,3] (xyz components, network voxel units)."""
-    lib = _lib.load()
     phi = _chk(phi, "phi")
     _, D, H, W = phi.shape
     out = torch.empty((D, H, W, 3), dtype=torch.float64, device=phi.device)
-    _lib.check(lib.oai_phi_to_itk_displacement(phi.data_ptr(), D, H, W, out.data_ptr(), _stream()), "oai_phi_to_itk_displacement")
+    _lib.call("oai_phi_to_itk_displacement", phi.data_ptr(), D, H, W, out.data_ptr(), _lib.STREAM, device=phi.device)
     return out
 
 
@@ -155,10 +146,8 @@ def make_affine(A: np.ndarray, b: np.ndarray) -> _lib.Affine:
     return a
 
 
-@_on_tensor_device
 def resample_through_disp(prob: torch.Tensor, disp: torch.Tensor, b_index_to_net, net_to_a_index,
                           out_shape_zyx: Sequence[int]) -> torch.Tensor:
-    lib = _lib.load()
     prob = _chk(prob, "prob")
     disp = _chk(disp, "disp", torch.float64)
     nzA, nyA, nxA = prob.shape
@@ -166,56 +155,46 @@ def resample_through_disp(prob: torch.Tensor, disp: torch.Tensor, b_index_to_net
     nzB, nyB, nxB = (int(v) for v in out_shape_zyx)
     out = torch.empty((nzB, nyB, nxB), dtype=torch.float32, device=prob.device)
     a1, a2 = make_affine(*b_index_to_net), make_affine(*net_to_a_index)
-    _lib.check(lib.oai_resample_through_disp(prob.data_ptr(), nzA, nyA, nxA, disp.data_ptr(), Dn, Hn, Wn,
-                                             C.byref(a1), C.byref(a2), out.data_ptr(), nzB, nyB, nxB, _stream()),
-               "oai_resample_through_disp")
+    _lib.call("oai_resample_through_disp", prob.data_ptr(), nzA, nyA, nxA, disp.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), out.data_ptr(),
+              nzB, nyB, nxB, _lib.STREAM, device=prob.device)
     return out
 
 
-@_on_tensor_device
 def resample_maps_through_phi(maps: torch.Tensor, phi: torch.Tensor, b_index_to_net, net_to_a_index,
                               out_shape_zyx: Sequence[int]) -> torch.Tensor:
     """maps [n,zA,yA,xA] (n <= 4) pulled through the dense map phi [3,D,H,W] onto a grid of ``out_shape_zyx``: one launch,
     bit-identical to ``phi_to_itk_displacement`` + ``resample_through_disp`` per map."""
-    lib = _lib.load()
     maps = _chk(maps, "maps")
     phi = _chk(phi, "phi")
-    if maps.dim() != 4 or phi.dim() != 4 or phi.shape[0] != 3:
+    if maps.dim() != 4 or not _is_phi(phi):
         raise ValueError("maps must be [n,z,y,x] and phi [3,D,H,W]")
     n, nzA, nyA, nxA = maps.shape
     _, Dn, Hn, Wn = phi.shape
     nzB, nyB, nxB = (int(v) for v in out_shape_zyx)
     out = torch.empty((n, nzB, nyB, nxB), dtype=torch.float32, device=maps.device)
     a1, a2 = make_affine(*b_index_to_net), make_affine(*net_to_a_index)
-    with torch.cuda.device(maps.device):
-        _lib.check(lib.oai_resample_maps_through_phi(maps.data_ptr(), n, nzA, nyA, nxA, phi.data_ptr(), Dn, Hn, Wn,
-                                                     C.byref(a1), C.byref(a2), out.data_ptr(), nzB, nyB, nxB, _stream()),
-                   "oai_resample_maps_through_phi")
+    _lib.call("oai_resample_maps_through_phi", maps.data_ptr(), n, nzA, nyA, nxA, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2),
+              out.data_ptr(), nzB, nyB, nxB, _lib.STREAM, device=maps.device)
     return out
 
 
-@_on_tensor_device
 def transform_points_through_phi(points: torch.Tensor, phi: torch.Tensor, point_to_net, net_to_out, return_inside: bool = False):
     """points float32 [n,3] (x,y,z) pushed through the dense map phi [3,D,H,W]: ``net_to_out(x + displacement(x))`` with
     ``x = point_to_net(p)``, the displacement trilinear inside phi's buffer and zero outside it (include/oai_hip.h, "Points pushed
     through phi").  The affines are (A [3,3], b [3]) pairs in fp64.  Returns float32 [n,3]; with ``return_inside`` also the uint8 [n]
     mask of the points that lay inside the buffer."""
-    lib = _lib.load()
     points = _chk(points, "points")
     phi = _chk(phi, "phi")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [n,3], got {tuple(points.shape)}")
-    if phi.dim() != 4 or phi.shape[0] != 3:
-        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
-    if phi.device != points.device:
-        raise ValueError(f"points ({points.device}) and phi ({phi.device}) must live on the same GPU")
+    _check_points(points)
+    _check_phi(phi)
+    _check_same_gpu("points", points, "phi", phi)
     n = int(points.shape[0])
     _, Dn, Hn, Wn = (int(v) for v in phi.shape)
     out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
     inside = torch.empty(n, dtype=torch.uint8, device=points.device) if return_inside else None
     a1, a2 = make_affine(*point_to_net), make_affine(*net_to_out)
-    _lib.check(lib.oai_transform_points_through_phi(points.data_ptr(), n, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), out.data_ptr(),
-                                                    inside.data_ptr() if return_inside else None, _stream()), "oai_transform_points_through_phi")
+    _lib.call("oai_transform_points_through_phi", points.data_ptr(), n, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), out.data_ptr(),
+              _ptr(inside), _lib.STREAM, device=points.device)
     return (out, inside) if return_inside else out
 
 
@@ -237,7 +216,6 @@ def _check_solver(max_iter, tol) -> None:
         raise ValueError(f"tol must be positive, got {tol}")
 
 
-@_on_tensor_device
 def inverse_points_through_phi(points: torch.Tensor, phi: torch.Tensor, point_to_net, net_to_out, max_iter: int = 30, tol: float = 1e-7,
                                return_status: bool = False):
     """points float32 [n,3] (x,y,z) pulled back through the dense map phi [3,D,H,W]: ``net_to_out(x)`` with ``T(x) = point_to_net(p)``,
@@ -245,38 +223,30 @@ def inverse_points_through_phi(points: torch.Tensor, phi: torch.Tensor, point_to
     network voxels in at most ``max_iter`` iterations (include/oai_hip.h, "The inverse of phi").  The affines are (A [3,3], b [3])
     pairs in fp64.  Returns float32 [n,3]; with ``return_status`` also the uint8 [n] status: 1 = converged inside phi's buffer, 2 =
     converged outside it, 0 = not converged (the point is then moved by the affines alone)."""
-    lib = _lib.load()
     points = _chk(points, "points")
     phi = _chk(phi, "phi")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [n,3], got {tuple(points.shape)}")
-    if phi.dim() != 4 or phi.shape[0] != 3:
-        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
-    if phi.device != points.device:
-        raise ValueError(f"points ({points.device}) and phi ({phi.device}) must live on the same GPU")
+    _check_points(points)
+    _check_phi(phi)
+    _check_same_gpu("points", points, "phi", phi)
     _check_solver(max_iter, tol)
     n = int(points.shape[0])
     _, Dn, Hn, Wn = (int(v) for v in phi.shape)
     out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
     status = torch.empty(n, dtype=torch.uint8, device=points.device) if return_status else None
     a1, a2 = make_affine(*point_to_net), make_affine(*net_to_out)
-    _lib.check(lib.oai_inverse_points_through_phi(points.data_ptr(), n, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), int(max_iter),
-                                                  float(tol), out.data_ptr(), status.data_ptr() if return_status else None, _stream()),
-               "oai_inverse_points_through_phi")
+    _lib.call("oai_inverse_points_through_phi", points.data_ptr(), n, phi.data_ptr(), Dn, Hn, Wn, C.byref(a1), C.byref(a2), int(max_iter),
+              float(tol), out.data_ptr(), _ptr(status), _lib.STREAM, device=points.device)
     return (out, status) if return_status else out
 
 
-@_on_tensor_device
 def invert_phi(phi: torch.Tensor, max_iter: int = 30, tol: float = 1e-7, return_status: bool = False, out: Optional[torch.Tensor] = None):
     """The dense inverse psi of the dense map phi float32 [3,D,H,W] on the same lattice and in the same storage convention: psi is a
     phi (``resample_maps_through_phi``, ``transform_points_through_phi`` and ``phi_jacobian`` read it unchanged) that takes patient
     points to atlas points (include/oai_hip.h, "The inverse of phi").  Returns ``(psi, stats)`` -- psi a new float32 [3,D,H,W] device
     tensor, or ``out``; stats a ``PhiInverseStats``, read back with one synchronisation -- and with ``return_status`` also the uint8
     [D,H,W] status of every lattice point (1 converged inside the buffer, 2 converged outside it, 0 not converged)."""
-    lib = _lib.load()
     phi = _chk(phi, "phi")
-    if phi.dim() != 4 or phi.shape[0] != 3:
-        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+    _check_phi(phi)
     _check_solver(max_iter, tol)
     _, D, H, W = (int(v) for v in phi.shape)
     if out is None:
@@ -288,9 +258,9 @@ def invert_phi(phi: torch.Tensor, max_iter: int = 30, tol: float = 1e-7, return_
         psi = out
     status = torch.empty((D, H, W), dtype=torch.uint8, device=phi.device) if return_status else None
     stats = torch.empty(6, dtype=torch.float64, device=phi.device)
-    ws = torch.empty(int(lib.oai_invert_phi_workspace_bytes(D, H, W)), dtype=torch.uint8, device=phi.device)
-    _lib.check(lib.oai_invert_phi(phi.data_ptr(), D, H, W, int(max_iter), float(tol), psi.data_ptr(), status.data_ptr() if return_status else None,
-                                  ws.data_ptr(), ws.numel(), stats.data_ptr(), _stream()), "oai_invert_phi")
+    ws = _lib.workspace("oai_invert_phi", phi.device, D, H, W)
+    _lib.call("oai_invert_phi", phi.data_ptr(), D, H, W, int(max_iter), float(tol), psi.data_ptr(), _ptr(status), ws.data_ptr(), ws.numel(),
+              stats.data_ptr(), _lib.STREAM, device=phi.device)
     s = stats.cpu().numpy()
     record = PhiInverseStats(int(s[0]), int(s[1]), int(s[2]), float(s[3]), float(s[4] / s[0]), int(s[5]))
     return (psi, record, status) if return_status else (psi, record)
@@ -305,58 +275,48 @@ def _out_slot(out: Optional[torch.Tensor], n: int, dtype, device, name: str) -> 
     return out
 
 
-@_on_tensor_device
 def phi_jacobian(phi: torch.Tensor, return_map: bool = False, out: Optional[torch.Tensor] = None):
     """The Jacobian determinant of the dense map phi float32 [3,D,H,W] per cell (z,y,x) in [1,D) x [1,H) x [1,W), backward differences of
     the displacement in network voxels (include/oai_hip.h, "Registration QC").  Returns the float64 [7] DEVICE tensor (cells, folds,
     non-finite cells, min, max, sum, sum of squares; ``out``: written there instead of a new tensor); with ``return_map`` also the
     float32 [D-1,H-1,W-1] map.  Does not synchronise: read the stats when they are needed (qc.registration_qc does, once)."""
-    lib = _lib.load()
     phi = _chk(phi, "phi")
-    if phi.dim() != 4 or phi.shape[0] != 3:
-        raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
+    _check_phi(phi)
     _, D, H, W = (int(v) for v in phi.shape)
     stats = _out_slot(out, 7, torch.float64, phi.device, "out")
     det = torch.empty((max(D - 1, 0), max(H - 1, 0), max(W - 1, 0)), dtype=torch.float32, device=phi.device) if return_map else None
-    ws = torch.empty(int(lib.oai_phi_jacobian_workspace_bytes(D, H, W)), dtype=torch.uint8, device=phi.device)
-    _lib.check(lib.oai_phi_jacobian(phi.data_ptr(), D, H, W, det.data_ptr() if return_map else None, ws.data_ptr(), ws.numel(),
-                                    stats.data_ptr(), _stream()), "oai_phi_jacobian")
+    ws = _lib.workspace("oai_phi_jacobian", phi.device, D, H, W)
+    _lib.call("oai_phi_jacobian", phi.data_ptr(), D, H, W, _ptr(det), ws.data_ptr(), ws.numel(), stats.data_ptr(), _lib.STREAM, device=phi.device)
     return (stats, det) if return_map else stats
 
 
-@_on_tensor_device
 def mask_overlap(a: torch.Tensor, b: Optional[torch.Tensor] = None, threshold: float = 0.5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Overlap counts of two float32 device tensors of equal size under ``value > threshold`` (a non-finite value is in no set): the
     int64 [4] DEVICE tensor |A|, |B|, |A and B|, positions with a non-finite value.  ``b`` None: |A| and zeros.  Exact; does not
     synchronise."""
-    lib = _lib.load()
     a = _chk(a, "a")
     if b is not None:
         b = _chk(b, "b")
         if b.numel() != a.numel():
             raise ValueError(f"a and b must have the same number of elements, got {a.numel()} and {b.numel()}")
-        if b.device != a.device:
-            raise ValueError(f"a ({a.device}) and b ({b.device}) must live on the same GPU")
+        _check_same_gpu("a", a, "b", b)
     n = int(a.numel())
     counts = _out_slot(out, 4, torch.int64, a.device, "out")
-    ws = torch.empty(int(lib.oai_mask_overlap_workspace_bytes(n)), dtype=torch.uint8, device=a.device)
-    _lib.check(lib.oai_mask_overlap(a.data_ptr() if n else None, b.data_ptr() if (b is not None and n) else None, n, float(threshold),
-                                    ws.data_ptr() if n else None, ws.numel(), counts.data_ptr(), _stream()), "oai_mask_overlap")
+    ws = _lib.workspace("oai_mask_overlap", a.device, n)
+    _lib.call("oai_mask_overlap", _ptr(a, n), _ptr(b, n), n, float(threshold), _ptr(ws, n), ws.numel(), counts.data_ptr(), _lib.STREAM,
+              device=a.device)
     return counts
 
 
-@_on_tensor_device
 def image_normalize(vol: torch.Tensor, window_min_perc: float = 0.1, window_max_perc: float = 99.9,
                     output_min: float = 0.0, output_max: float = 1.0, return_window: bool = False):
     """``image_normalize`` of oai_analysis/dask_processing.py:10-26 on the device (fp32 image)."""
-    lib = _lib.load()
     vol = _chk(vol, "vol")
     out = torch.empty_like(vol)
-    ws = torch.empty(int(lib.oai_image_normalize_workspace_bytes()), dtype=torch.uint8, device=vol.device)
+    ws = _lib.workspace("oai_image_normalize", vol.device)
     win = torch.empty(2, dtype=torch.float32, device=vol.device)
-    _lib.check(lib.oai_image_normalize(vol.data_ptr(), vol.numel(), float(window_min_perc), float(window_max_perc),
-                                       float(output_min), float(output_max), out.data_ptr(), win.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), _stream()), "oai_image_normalize")
+    _lib.call("oai_image_normalize", vol.data_ptr(), vol.numel(), float(window_min_perc), float(window_max_perc), float(output_min),
+              float(output_max), out.data_ptr(), win.data_ptr(), ws.data_ptr(), ws.numel(), _lib.STREAM, device=vol.device)
     return (out, win) if return_window else out
 
 
@@ -371,7 +331,6 @@ def _volume3(t: torch.Tensor, name: str, dtype) -> torch.Tensor:
     return t
 
 
-@_on_tensor_device
 def mask_surface(map: torch.Tensor, threshold: float = 0.5, mode: str = "surface") -> torch.Tensor:
     """The set ``finite and > threshold`` of a float32 [z,y,x] device volume as a uint8 volume: ``mode`` "set" -- the set itself;
     "surface" -- its voxels with a face neighbour outside the set or outside the volume (``A ^ binary_erosion(A)``, MedPy's rule);
@@ -381,27 +340,24 @@ def mask_surface(map: torch.Tensor, threshold: float = 0.5, mode: str = "surface
     map = _volume3(map, "map", torch.float32)
     D, H, W = (int(v) for v in map.shape)
     out = torch.empty((D, H, W), dtype=torch.uint8, device=map.device)
-    _lib.check(_lib.load().oai_mask_surface(map.data_ptr(), D, H, W, float(threshold), SURFACE_MODES[mode], out.data_ptr(), _stream()),
-               "oai_mask_surface")
+    _lib.call("oai_mask_surface", map.data_ptr(), D, H, W, float(threshold), SURFACE_MODES[mode], out.data_ptr(), _lib.STREAM, device=map.device)
     return out
 
 
 def _edt(features: torch.Tensor, spacing_xyz, scale: float, into: Optional[torch.Tensor], squared: bool, count: bool):
     """One oai_edt call: (dist, sq or None, n_features or None).  ``into``: the float32 map that ``scale * distance`` is added to."""
-    lib = _lib.load()
     features = _volume3(features, "features", torch.uint8)
     D, H, W = (int(v) for v in features.shape)
     dist = torch.empty((D, H, W), dtype=torch.float32, device=features.device) if into is None else into
     sq = torch.empty((D, H, W), dtype=torch.float64, device=features.device) if squared else None
     n = torch.empty(1, dtype=torch.int64, device=features.device) if count else None
-    ws = torch.empty(int(lib.oai_edt_workspace_bytes(D, H, W)), dtype=torch.uint8, device=features.device)
+    ws = _lib.workspace("oai_edt", features.device, D, H, W)
     spacing = (C.c_double * 3)(*[float(v) for v in np.asarray(spacing_xyz, np.float64).reshape(3)])
-    _lib.check(lib.oai_edt(features.data_ptr(), D, H, W, spacing, float(scale), int(into is not None), dist.data_ptr(),
-                           sq.data_ptr() if squared else None, ws.data_ptr(), ws.numel(), n.data_ptr() if count else None, _stream()), "oai_edt")
+    _lib.call("oai_edt", features.data_ptr(), D, H, W, spacing, float(scale), int(into is not None), dist.data_ptr(), _ptr(sq), ws.data_ptr(),
+              ws.numel(), _ptr(n), _lib.STREAM, device=features.device)
     return dist, sq, n
 
 
-@_on_tensor_device
 def distance_transform(features: torch.Tensor, spacing_xyz=(1.0, 1.0, 1.0), return_squared: bool = False, return_count: bool = False):
     """The exact Euclidean distance transform of a uint8 [z,y,x] device volume: per voxel the distance to the nearest voxel with a
     non-zero byte, in the units of ``spacing_xyz`` (x, y, z) -- ``scipy.ndimage.distance_transform_edt(features == 0, sampling=
@@ -413,7 +369,6 @@ def distance_transform(features: torch.Tensor, spacing_xyz=(1.0, 1.0, 1.0), retu
     return got if len(got) > 1 else dist
 
 
-@_on_tensor_device
 def signed_distance(map: torch.Tensor, spacing_xyz=(1.0, 1.0, 1.0), threshold: float = 0.5) -> torch.Tensor:
     """The signed distance map of the set ``finite and > threshold`` of a float32 [z,y,x] device volume: positive outside the set (the
     distance to it), negative inside (minus the distance to the complement) -- scipy's ``edt(~m) - edt(m)``.  Two oai_edt calls, the
@@ -423,14 +378,12 @@ def signed_distance(map: torch.Tensor, spacing_xyz=(1.0, 1.0, 1.0), threshold: f
     return dist
 
 
-@_on_tensor_device
 def surface_distance(surf_a: torch.Tensor, dist_to_b: torch.Tensor, surf_b: torch.Tensor, dist_to_a: torch.Tensor,
                      percentiles: Sequence[float] = (95.0,), out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The surface-distance figures of two surfaces (uint8 masks) given each one's distance map (float32, ``distance_transform`` of the
     surface): the float64 [8] DEVICE tensor n_A, n_B, sum d(A->B), sum d(B->A), max d(A->B), max d(B->A) and up to two percentiles of
     the pooled distances (``np.percentile`` bit for bit; NaN where not asked for).  With an empty surface everything but the counts is
     NaN.  ``out``: written there instead of a new tensor.  Does not synchronise."""
-    lib = _lib.load()
     surf_a, surf_b = _chk(surf_a, "surf_a", torch.uint8), _chk(surf_b, "surf_b", torch.uint8)
     dist_to_b, dist_to_a = _chk(dist_to_b, "dist_to_b"), _chk(dist_to_a, "dist_to_a")
     n = int(surf_a.numel())
@@ -441,10 +394,9 @@ def surface_distance(surf_a: torch.Tensor, dist_to_b: torch.Tensor, surf_b: torc
     if len(pct) > 2:
         raise ValueError(f"at most two percentiles per call, got {len(pct)}")
     stats = _out_slot(out, 8, torch.float64, surf_a.device, "out")
-    ws = torch.empty(int(lib.oai_surface_distance_workspace_bytes(n)), dtype=torch.uint8, device=surf_a.device)
-    ptr = lambda t: t.data_ptr() if n else None
-    _lib.check(lib.oai_surface_distance(ptr(surf_a), ptr(dist_to_b), ptr(surf_b), ptr(dist_to_a), n, (C.c_float * 2)(*(pct + [0.0, 0.0])[:2]),
-                                        len(pct), ws.data_ptr(), ws.numel(), stats.data_ptr(), _stream()), "oai_surface_distance")
+    ws = _lib.workspace("oai_surface_distance", surf_a.device, n)
+    _lib.call("oai_surface_distance", _ptr(surf_a, n), _ptr(dist_to_b, n), _ptr(surf_b, n), _ptr(dist_to_a, n), n,
+              (C.c_float * 2)(*(pct + [0.0, 0.0])[:2]), len(pct), ws.data_ptr(), ws.numel(), stats.data_ptr(), _lib.STREAM, device=surf_a.device)
     return stats
 
 
@@ -474,40 +426,33 @@ def _pair(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tensor]):
     return a, b, mask
 
 
-@_on_tensor_device
 def image_moments(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The float64 [8] DEVICE tensor of two float32 device tensors of one shape: counted positions (admitted by the uint8 ``mask``, both
     values finite), admitted positions left out for a non-finite value, sum a, sum b, sum a^2, sum b^2, sum ab, sum (a - b)^2 -- fp64,
     bit-reproducible (include/oai_hip.h, "Image-similarity QC").  ``out``: written there instead of a new tensor.  Does not synchronise."""
-    lib = _lib.load()
     a, b, mask = _pair(a, b, mask)
     n = int(a.numel())
     stats = _out_slot(out, 8, torch.float64, a.device, "out")
-    ws = torch.empty(int(lib.oai_image_moments_workspace_bytes(n)), dtype=torch.uint8, device=a.device)
-    ptr = lambda t: t.data_ptr() if (t is not None and n) else None
-    _lib.check(lib.oai_image_moments(ptr(a), ptr(b), n, ptr(mask), ptr(ws), ws.numel(), stats.data_ptr(), _stream()), "oai_image_moments")
+    ws = _lib.workspace("oai_image_moments", a.device, n)
+    _lib.call("oai_image_moments", _ptr(a, n), _ptr(b, n), n, _ptr(mask, n), _ptr(ws, n), ws.numel(), stats.data_ptr(), _lib.STREAM, device=a.device)
     return stats
 
 
-@_on_tensor_device
 def joint_histogram(a: torch.Tensor, b: torch.Tensor, bins: int = 64, range_a=(0.0, 1.0), range_b=(0.0, 1.0),
                     mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The int64 [bins*bins + 1] DEVICE tensor of two float32 device tensors of one shape: ``hist[ia*bins + ib]`` counts the pairs, the
     last entry the admitted positions skipped for a non-finite value.  Float32 binning with values outside a range clamped into the end
     bins (include/oai_hip.h).  Exact; ``out``: written there instead of a new tensor.  Does not synchronise."""
-    lib = _lib.load()
     a, b, mask = _pair(a, b, mask)
     n, bins = int(a.numel()), int(bins)
     if not 1 <= bins <= 128:
         raise ValueError(f"bins must be in [1, 128], got {bins}")
     hist = _out_slot(out, bins * bins + 1, torch.int64, a.device, "out")
-    ptr = lambda t: t.data_ptr() if (t is not None and n) else None
-    _lib.check(lib.oai_joint_histogram(ptr(a), ptr(b), n, (C.c_float * 2)(*[float(v) for v in range_a]), (C.c_float * 2)(*[float(v) for v in range_b]),
-                                       bins, ptr(mask), hist.data_ptr(), _stream()), "oai_joint_histogram")
+    _lib.call("oai_joint_histogram", _ptr(a, n), _ptr(b, n), n, (C.c_float * 2)(*[float(v) for v in range_a]),
+              (C.c_float * 2)(*[float(v) for v in range_b]), bins, _ptr(mask, n), hist.data_ptr(), _lib.STREAM, device=a.device)
     return hist
 
 
-@_on_tensor_device
 def histogram_entropies(hist: torch.Tensor, bins: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The float64 [4] DEVICE tensor N, H_A, H_B, H_AB (natural logarithm) of a ``joint_histogram`` table; N = 0 gives three NaNs.
     ``out``: written there instead of a new tensor.  Does not synchronise."""
@@ -515,11 +460,10 @@ def histogram_entropies(hist: torch.Tensor, bins: int, out: Optional[torch.Tenso
     if not 1 <= bins <= 128 or int(hist.numel()) < bins * bins:
         raise ValueError(f"hist must hold bins*bins counts with bins in [1, 128], got {int(hist.numel())} entries for bins = {bins}")
     ent = _out_slot(out, 4, torch.float64, hist.device, "out")
-    _lib.check(_lib.load().oai_histogram_entropies(hist.data_ptr(), bins, ent.data_ptr(), _stream()), "oai_histogram_entropies")
+    _lib.call("oai_histogram_entropies", hist.data_ptr(), bins, ent.data_ptr(), _lib.STREAM, device=hist.device)
     return ent
 
 
-@_on_tensor_device
 def lncc(a: torch.Tensor, b: torch.Tensor, sigma: float = 4.0, eps: float = 1e-5, mask: Optional[torch.Tensor] = None,
          return_map: bool = False, out: Optional[torch.Tensor] = None):
     """The local normalised cross-correlation of two float32 [z,y,x] device volumes under a Gaussian window (``gaussian_taps(sigma)``;
@@ -527,16 +471,14 @@ def lncc(a: torch.Tensor, b: torch.Tensor, sigma: float = 4.0, eps: float = 1e-5
     voxels left out for a non-finite cc, sum cc, sum cc^2, min, max (include/oai_hip.h); with ``return_map`` also the float64 [z,y,x]
     map of cc.  The mean of cc is the network's similarity; its loss is one minus that.  ``out``: the stats are written there instead
     of a new tensor.  Does not synchronise."""
-    lib = _lib.load()
     a, b, mask = _pair(_volume3(a, "a", torch.float32), _volume3(b, "b", torch.float32), mask)
     D, H, W = (int(v) for v in a.shape)
     taps, radius = gaussian_taps(sigma)
     stats = _out_slot(out, 6, torch.float64, a.device, "out")
     cc = torch.empty((D, H, W), dtype=torch.float64, device=a.device) if return_map else None
-    ws = torch.empty(int(lib.oai_lncc_workspace_bytes(D, H, W)), dtype=torch.uint8, device=a.device)
-    _lib.check(lib.oai_lncc(a.data_ptr(), b.data_ptr(), D, H, W, (C.c_double * len(taps))(*taps.tolist()), radius, float(eps),
-                            mask.data_ptr() if mask is not None else None, cc.data_ptr() if return_map else None, ws.data_ptr(), ws.numel(),
-                            stats.data_ptr(), _stream()), "oai_lncc")
+    ws = _lib.workspace("oai_lncc", a.device, D, H, W)
+    _lib.call("oai_lncc", a.data_ptr(), b.data_ptr(), D, H, W, (C.c_double * len(taps))(*taps.tolist()), radius, float(eps), _ptr(mask), _ptr(cc),
+              ws.data_ptr(), ws.numel(), stats.data_ptr(), _lib.STREAM, device=a.device)
     return (stats, cc) if return_map else stats
 
 
@@ -544,7 +486,6 @@ def lncc(a: torch.Tensor, b: torch.Tensor, sigma: float = 4.0, eps: float = 1e-5
 SUMMARY_SLOTS = 12           # int64 per labelling call: include/oai_hip.h, oai_label_components
 
 
-@_on_tensor_device
 def label_components(map_or_mask: torch.Tensor, threshold: float = 0.5, connectivity: int = 26, complement: bool = False, min_voxels: int = 0,
                      return_labels: bool = True, return_sizes: bool = False, out: Optional[torch.Tensor] = None):
     """The connected components of a [z,y,x] device volume under 6, 18 or 26 connectivity.  A float32 tensor is a map: the set is
@@ -554,7 +495,6 @@ def label_components(map_or_mask: torch.Tensor, threshold: float = 0.5, connecti
     0; ``out``: written there instead of a new tensor); int32 labels, 0 off the set and 1..K in raster order of each component's first
     voxel -- ``scipy.ndimage.label`` to the element -- or None; the int32 per-voxel size of the voxel's component, or None.
     Deterministic; does not synchronise."""
-    lib = _lib.load()
     if map_or_mask.dtype == torch.bool:
         map_or_mask = map_or_mask.view(torch.uint8)
     if map_or_mask.dtype not in (torch.float32, torch.uint8):
@@ -565,15 +505,13 @@ def label_components(map_or_mask: torch.Tensor, threshold: float = 0.5, connecti
     summary = _out_slot(out, SUMMARY_SLOTS, torch.int64, vol.device, "out")
     labels = torch.empty((D, H, W), dtype=torch.int32, device=vol.device) if return_labels else None
     sizes = torch.empty((D, H, W), dtype=torch.int32, device=vol.device) if return_sizes else None
-    ws = torch.empty(int(lib.oai_label_components_workspace_bytes(D, H, W)), dtype=torch.uint8, device=vol.device)
-    _lib.check(lib.oai_label_components(vol.data_ptr() if is_map else None, None if is_map else vol.data_ptr(), D, H, W, float(threshold),
-                                        int(bool(complement)), int(connectivity), int(min_voxels), labels.data_ptr() if return_labels else None,
-                                        sizes.data_ptr() if return_sizes else None, ws.data_ptr() if ws.numel() else None, ws.numel(),
-                                        summary.data_ptr(), _stream()), "oai_label_components")
+    ws = _lib.workspace("oai_label_components", vol.device, D, H, W)
+    _lib.call("oai_label_components", vol.data_ptr() if is_map else None, None if is_map else vol.data_ptr(), D, H, W, float(threshold),
+              int(bool(complement)), int(connectivity), int(min_voxels), _ptr(labels), _ptr(sizes), _ptr(ws, ws.numel()), ws.numel(),
+              summary.data_ptr(), _lib.STREAM, device=vol.device)
     return summary, labels, sizes
 
 
-@_on_tensor_device
 def component_sizes(labels: torch.Tensor, n_components: int) -> torch.Tensor:
     """The int64 [n_components] DEVICE table of voxel counts per label 1..n_components of an int32 label volume (``np.bincount(labels)[1:]``);
     labels outside 0..n_components are ignored.  Does not synchronise."""
@@ -583,6 +521,5 @@ def component_sizes(labels: torch.Tensor, n_components: int) -> torch.Tensor:
         raise ValueError(f"n_components must be >= 0, got {n_components}")
     n = int(labels.numel())
     sizes = (torch.empty if n else torch.zeros)(k, dtype=torch.int64, device=labels.device)     # the call clears the table unless it is a no-op
-    _lib.check(_lib.load().oai_component_sizes(labels.data_ptr() if n else None, n, k, sizes.data_ptr() if k else None, _stream()),
-               "oai_component_sizes")
+    _lib.call("oai_component_sizes", _ptr(labels, n), n, k, _ptr(sizes, k), _lib.STREAM, device=labels.device)
     return sizes

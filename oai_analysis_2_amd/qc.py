@@ -198,6 +198,23 @@ def similarity_from_stats(stats, sigma: float, bins: int, cc_map: Optional[torch
                            (ha + hb) / hab if hab > 0 else float("nan"), ha, hb, hab, float(sigma), int(bins), cc_map)
 
 
+def _result_slots(device, layout):
+    """The ONE buffer behind "queue everything, then ONE download": ``layout`` is the ordered list of ``(key, n_slots, dtype)``, dtype
+    torch.int64 or torch.float64 (both eight bytes: one int64 buffer holds them all).  Returns ``(views, download)``: the device views by
+    key, each of its dtype, for the kernels to write into; ``download()`` copies the buffer to the host once -- the only synchronisation
+    -- and returns the host views by the same keys.  The layout is written here and nowhere else."""
+    spans, at = {}, 0
+    for key, n_slots, dtype in layout:
+        spans[key] = (at, at + n_slots, dtype)
+        at += n_slots
+    buf = torch.empty(at, dtype=torch.int64, device=device)
+
+    def download():
+        host = buf.cpu().numpy()
+        return {key: host[lo:hi].view(np.float64 if dtype == torch.float64 else np.int64) for key, (lo, hi, dtype) in spans.items()}
+    return {key: buf[lo:hi] if dtype == torch.int64 else buf[lo:hi].view(dtype) for key, (lo, hi, dtype) in spans.items()}, download
+
+
 def _image_dev(m) -> torch.Tensor:
     """An image -- an ``Image``, an array or a [z,y,x] device tensor -- as a contiguous float32 device volume (its geometry is not used)."""
     return _map_with_spacing(m, None)[0].contiguous()
@@ -225,10 +242,10 @@ def image_similarity(a, b, sigma: float = 4.0, bins: int = 64, value_range=(0.0,
         elif mask.dtype == torch.bool:
             mask = mask.to(torch.uint8)
     with torch.cuda.device(va.device):
-        buf = torch.empty(SIMILARITY_SLOTS, dtype=torch.float64, device=va.device)
-        cc_map = _queue_similarity(va, vb, sigma, bins, value_range, mask, return_map, buf)
-        host = buf.cpu().numpy()
-    return similarity_from_stats(host, sigma, bins, cc_map)
+        views, download = _result_slots(va.device, [("similarity", SIMILARITY_SLOTS, torch.float64)])
+        cc_map = _queue_similarity(va, vb, sigma, bins, value_range, mask, return_map, views["similarity"])
+        host = download()
+    return similarity_from_stats(host["similarity"], sigma, bins, cc_map)
 
 
 def _surface_and_map(vol: torch.Tensor, spacing_xyz, threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -277,12 +294,12 @@ def segmentation_qc(pred, truth, spacing_xyz=None, threshold: float = 0.5) -> Se
     surface distances, queued together and downloaded once."""
     va, vb, spacing = _two_volumes(pred, truth, spacing_xyz)
     with torch.cuda.device(va.device):
-        buf = torch.empty(12, dtype=torch.int64, device=va.device)
-        ops.mask_overlap(va, vb, threshold, out=buf[:4])
-        _queue_surface_distance(va, vb, spacing, threshold, (95.0,), buf[4:].view(torch.float64))
-        host = buf.cpu().numpy()
-    counts = tuple(int(v) for v in host[:4])
-    return SegmentationQC(dice_from_counts(*counts[:3]), counts, surface_distance_from_stats(host[4:].view(np.float64), (95.0,)))
+        views, download = _result_slots(va.device, [("counts", 4, torch.int64), ("surface", 8, torch.float64)])
+        ops.mask_overlap(va, vb, threshold, out=views["counts"])
+        _queue_surface_distance(va, vb, spacing, threshold, (95.0,), views["surface"])
+        host = download()
+    counts = tuple(int(v) for v in host["counts"])
+    return SegmentationQC(dice_from_counts(*counts[:3]), counts, surface_distance_from_stats(host["surface"], (95.0,)))
 
 
 class QCReference:
@@ -378,7 +395,7 @@ def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Option
     phi = result_or_phi.phi if is_result else result_or_phi
     if not torch.is_tensor(phi):
         phi = torch.from_numpy(np.ascontiguousarray(phi)).cuda()
-    phi = ops._chk(phi, "phi")
+    phi = ops.check_tensor(phi, "phi")
     if is_result:
         image_A = result_or_phi.meta_A if image_A is None else image_A
         image_B = getattr(result_or_phi, "meta_B", None) if image_B is None else image_B
@@ -389,33 +406,32 @@ def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Option
             if reference is not None:
                 jobs += [("dice", kind, getattr(result_or_phi, kind.lower() + "_atlas"), reference[kind]) for kind in KINDS]
         kinds_s = KINDS if is_result and reference is not None and reference.surfaces is not None else ()
-        at_s = 7 + 4 * len(jobs)                        # eight doubles per cartilage behind the counts
         sims = _similarity_jobs(result_or_phi if is_result else None, phi, reference, patient_image)      # (key, a, b, mask)
-        at_i = at_s + 8 * len(kinds_s)                  # SIMILARITY_SLOTS doubles per comparison behind the surfaces
-        buf = torch.empty(at_i + SIMILARITY_SLOTS * len(sims), dtype=torch.int64, device=phi.device)     # one buffer, one download
-        got = ops.phi_jacobian(phi, return_map=return_map, out=buf[:7].view(torch.float64))
+        views, download = _result_slots(phi.device,                                                      # one buffer, one download
+                                        [("jacobian", 7, torch.float64)]
+                                        + [((part, kind), 4, torch.int64) for part, kind, _, _ in jobs]
+                                        + [(("surface", kind), 8, torch.float64) for kind in kinds_s]
+                                        + [(("similarity", key), SIMILARITY_SLOTS, torch.float64) for key, _, _, _ in sims])
+        got = ops.phi_jacobian(phi, return_map=return_map, out=views["jacobian"])
         det_map = got[1] if return_map else None
-        for i, (_, _, a, b) in enumerate(jobs):
-            ops.mask_overlap(a, b, THRESHOLD, out=buf[7 + 4 * i:11 + 4 * i])
-        for i, kind in enumerate(kinds_s):
-            warped = ops._chk(getattr(result_or_phi, kind.lower() + "_atlas"), kind)
+        for part, kind, a, b in jobs:
+            ops.mask_overlap(a, b, THRESHOLD, out=views[part, kind])
+        for kind in kinds_s:
+            warped = ops.check_tensor(getattr(result_or_phi, kind.lower() + "_atlas"), kind)
             if warped.shape != reference.surfaces[kind].shape:
                 raise ValueError(f"the warped {kind} map {tuple(warped.shape)} is not on the reference's grid {tuple(reference.surfaces[kind].shape)}")
             surf, to_warped = _surface_and_map(warped, reference.spacing_xyz, THRESHOLD)
-            ops.surface_distance(surf, reference.distance_maps[kind], reference.surfaces[kind], to_warped, (95.0,),
-                                 out=buf[at_s + 8 * i:at_s + 8 * i + 8].view(torch.float64))
-        for i, (_, a, b, mask) in enumerate(sims):
-            _queue_similarity(a, b, SIGMA, BINS, (0.0, 1.0), mask, False,
-                              buf[at_i + SIMILARITY_SLOTS * i:at_i + SIMILARITY_SLOTS * (i + 1)].view(torch.float64))
-        host = buf.cpu().numpy()
-    qc = RegistrationQC(jacobian_from_stats(host[:7].view(np.float64), det_map))
+            ops.surface_distance(surf, reference.distance_maps[kind], reference.surfaces[kind], to_warped, (95.0,), out=views["surface", kind])
+        for key, a, b, mask in sims:
+            _queue_similarity(a, b, SIGMA, BINS, (0.0, 1.0), mask, False, views["similarity", key])
+        host = download()
+    qc = RegistrationQC(jacobian_from_stats(host["jacobian"], det_map))
     if sims:
-        qc.similarity = {key: similarity_from_stats(host[at_i + SIMILARITY_SLOTS * i:at_i + SIMILARITY_SLOTS * (i + 1)].view(np.float64), SIGMA, BINS)
-                         for i, (key, _, _, _) in enumerate(sims)}
+        qc.similarity = {key: similarity_from_stats(host["similarity", key], SIGMA, BINS) for key, _, _, _ in sims}
     if image_A is not None and image_B is not None:
         qc.volume_scale = volume_scale(image_A, image_B, phi.shape[1:])
-    for i, (part, kind, _, _) in enumerate(jobs):
-        n_a, n_b, n_both, n_bad = (int(v) for v in host[7 + 4 * i:11 + 4 * i])
+    for part, kind, _, _ in jobs:
+        n_a, n_b, n_both, n_bad = (int(v) for v in host[part, kind])
         if part == "patient":
             if qc.cartilage_voxels is None:
                 qc.cartilage_voxels = {}
@@ -430,8 +446,7 @@ def registration_qc(result_or_phi, image_A=None, image_B=None, reference: Option
             qc.dice[kind] = dice_from_counts(n_a, n_b, n_both)
             qc.overlap_counts[kind] = (n_a, n_b, n_both, n_bad)
     if kinds_s:
-        qc.surface = {kind: surface_distance_from_stats(host[at_s + 8 * i:at_s + 8 * i + 8].view(np.float64), (95.0,))
-                      for i, kind in enumerate(kinds_s)}
+        qc.surface = {kind: surface_distance_from_stats(host["surface", kind], (95.0,)) for kind in kinds_s}
     return qc
 
 
@@ -460,6 +475,12 @@ class SegmentationShape:
 
 
 SHAPE_SLOTS = 2 * ops.SUMMARY_SLOTS + 8      # int64 per map in the downloaded buffer: two labelling summaries, two overlap counts
+_SHAPE_PARTS = (("set", ops.SUMMARY_SLOTS), ("complement", ops.SUMMARY_SLOTS), ("over_low", 4), ("over_high", 4))
+assert sum(n for _, n in _SHAPE_PARTS) == SHAPE_SLOTS
+
+
+def _shape_layout(key):
+    return [((key, part), n, torch.int64) for part, n in _SHAPE_PARTS]
 
 
 def dual_connectivity(connectivity: int) -> int:
@@ -480,19 +501,17 @@ def shape_from_summaries(fg, bg, n_over_lo: int, n_over_hi: int, connectivity: i
                              int(connectivity), int(min_voxels))
 
 
-def _queue_shape(vol: torch.Tensor, threshold, connectivity, min_voxels, band, out: torch.Tensor) -> None:
-    """One map queued on the current stream, results into ``out`` (int64 [SHAPE_SLOTS]): nothing is returned to the host here."""
-    k = ops.SUMMARY_SLOTS
-    ops.label_components(vol, threshold, connectivity, False, min_voxels, return_labels=False, out=out[:k])
-    ops.label_components(vol, threshold, dual_connectivity(connectivity), True, 0, return_labels=False, out=out[k:2 * k])
-    ops.mask_overlap(vol, None, float(band[0]), out=out[2 * k:2 * k + 4])
-    ops.mask_overlap(vol, None, float(band[1]), out=out[2 * k + 4:2 * k + 8])
+def _queue_shape(vol: torch.Tensor, threshold, connectivity, min_voxels, band, views, key) -> None:
+    """One map queued on the current stream, results into the views of ``_shape_layout(key)``: nothing is returned to the host here."""
+    ops.label_components(vol, threshold, connectivity, False, min_voxels, return_labels=False, out=views[key, "set"])
+    ops.label_components(vol, threshold, dual_connectivity(connectivity), True, 0, return_labels=False, out=views[key, "complement"])
+    ops.mask_overlap(vol, None, float(band[0]), out=views[key, "over_low"])
+    ops.mask_overlap(vol, None, float(band[1]), out=views[key, "over_high"])
 
 
-def _shape_from_host(host, connectivity, min_voxels, spacing) -> SegmentationShape:
-    k = ops.SUMMARY_SLOTS
-    return shape_from_summaries(host[:k], host[k:2 * k], host[2 * k], host[2 * k + 4], connectivity, min_voxels,
-                                None if spacing is None else float(np.prod(np.asarray(spacing, np.float64))))
+def _shape_from_host(host, key, connectivity, min_voxels, spacing) -> SegmentationShape:
+    return shape_from_summaries(host[key, "set"], host[key, "complement"], host[key, "over_low"][0], host[key, "over_high"][0],
+                                connectivity, min_voxels, None if spacing is None else float(np.prod(np.asarray(spacing, np.float64))))
 
 
 def _check_shape_args(connectivity, min_voxels, band) -> None:
@@ -517,12 +536,11 @@ def segmentation_shapes(maps: Dict[str, object], spacing_xyz=None, threshold: fl
     if any(v.device != device for v in vols.values()):
         raise ValueError("the maps must live on one GPU")
     with torch.cuda.device(device):
-        buf = torch.empty(SHAPE_SLOTS * len(vols), dtype=torch.int64, device=device)
-        for i, vol in enumerate(vols.values()):
-            _queue_shape(vol, threshold, connectivity, min_voxels, band, buf[SHAPE_SLOTS * i:SHAPE_SLOTS * (i + 1)])
-        host = buf.cpu().numpy()
-    return {key: _shape_from_host(host[SHAPE_SLOTS * i:SHAPE_SLOTS * (i + 1)], connectivity, min_voxels, spacing[key])
-            for i, key in enumerate(vols)}
+        views, download = _result_slots(device, [slot for key in vols for slot in _shape_layout(key)])
+        for key, vol in vols.items():
+            _queue_shape(vol, threshold, connectivity, min_voxels, band, views, key)
+        host = download()
+    return {key: _shape_from_host(host, key, connectivity, min_voxels, spacing[key]) for key in vols}
 
 
 def segmentation_shape(map, spacing_xyz=None, threshold: float = 0.5, connectivity: int = 26, min_voxels: int = 0,

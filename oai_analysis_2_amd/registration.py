@@ -256,15 +256,14 @@ class IconEngine:
             p.last_w, p.last_b = ptr(f"{pre}lastConv.weight"), ptr(f"{pre}lastConv.bias")
         nodes = (_lib.IconNode * len(self.tree.nodes))(*[_lib.IconNode(*nd) for nd in self.tree.nodes])
         handle = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_icon_create(params, n_nets, nodes, len(self.tree.nodes), self.tree.root, *self.net_shape,
-                                                C.byref(handle)), "oai_icon_create")
+        _lib.call("oai_icon_create", params, n_nets, nodes, len(self.tree.nodes), self.tree.root, *self.net_shape, C.byref(handle),
+                  device=self.device)
         self._h = handle
         self.n_nets = n_nets
         self.apply_bn, self.pad_front = bool(apply_bn), bool(pad_front)
         if not pad_front:
-            _lib.check(self.lib.oai_icon_set_option(self._h, b"pad_front", 0), "oai_icon_set_option")
-        self._ws = torch.empty(int(self.lib.oai_icon_workspace_bytes(self._h)), dtype=torch.uint8, device=self.device)
+            _lib.call("oai_icon_set_option", self._h, b"pad_front", 0)
+        self._ws = _lib.workspace("oai_icon", self.device, self._h)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -276,18 +275,18 @@ class IconEngine:
         """(n_nets, U-Nets per halving level, length of the final compose chain) as the library compiled the tree."""
         import ctypes as C
         n, lv, cl = C.c_int(), (C.c_int * 8)(), C.c_int()
-        _lib.check(self.lib.oai_icon_describe(self._h, C.byref(n), lv, C.byref(cl)), "oai_icon_describe")
+        _lib.call("oai_icon_describe", self._h, C.byref(n), lv, C.byref(cl))
         return n.value, list(lv), cl.value
 
     def set_graph(self, enable: bool) -> None:
         """hipGraph replay of one direction's launches (default on); off = the same launches issued one by one."""
-        _lib.check(self.lib.oai_icon_set_graph(self._h, int(enable)), "oai_icon_set_graph")
+        _lib.call("oai_icon_set_graph", self._h, int(enable))
 
     def graph_info(self):
         """(captured, replays, direct_runs): captured 1 = graph in use, 0 = not captured yet, -1 = capture failed (direct launches)."""
         import ctypes as C
         cap, rep, dr = C.c_int(), C.c_longlong(), C.c_longlong()
-        _lib.check(self.lib.oai_icon_graph_info(self._h, C.byref(cap), C.byref(rep), C.byref(dr)), "oai_icon_graph_info")
+        _lib.call("oai_icon_graph_info", self._h, C.byref(cap), C.byref(rep), C.byref(dr))
         return cap.value, rep.value, dr.value
 
     def unet(self, which: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -296,10 +295,8 @@ class IconEngine:
         b = b.to(self.device, torch.float32).contiguous()
         D, H, W = a.shape
         out = torch.empty((3, D, H, W), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_icon_unet_forward(self._h, which, a.data_ptr(), b.data_ptr(), D, H, W, out.data_ptr(),
-                                                      self._ws.data_ptr(), self._ws.numel(),
-                                                      torch.cuda.current_stream().cuda_stream), "oai_icon_unet_forward")
+        _lib.call("oai_icon_unet_forward", self._h, which, a.data_ptr(), b.data_ptr(), D, H, W, out.data_ptr(), self._ws.data_ptr(),
+                  self._ws.numel(), _lib.STREAM, device=self.device)
         return out
 
     def phi(self, A_net: torch.Tensor, B_net: torch.Tensor) -> torch.Tensor:
@@ -309,10 +306,8 @@ class IconEngine:
         if tuple(A_net.shape) != self.net_shape or tuple(B_net.shape) != self.net_shape:
             raise ValueError(f"images must be resized to the network shape {self.net_shape}")
         out = torch.empty((3, *self.net_shape), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_icon_forward(self._h, A_net.data_ptr(), B_net.data_ptr(), out.data_ptr(),
-                                                 self._ws.data_ptr(), self._ws.numel(),
-                                                 torch.cuda.current_stream().cuda_stream), "oai_icon_forward")
+        _lib.call("oai_icon_forward", self._h, A_net.data_ptr(), B_net.data_ptr(), out.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                  _lib.STREAM, device=self.device)
         return out
 
     def register_pair(self, image_A: torch.Tensor, image_B: torch.Tensor, both: bool = False):

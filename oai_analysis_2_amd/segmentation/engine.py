@@ -91,8 +91,7 @@ class UNetEngine:
             raise KeyError(f"unexpected keys in state_dict (strict load): {sorted(extra)[:4]}")
         self.n_classes = int(params[17].cout)
         handle = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_create(params, C.c_float(bn_eps), C.byref(handle)), "oai_unet_create")
+        _lib.call("oai_unet_create", params, C.c_float(bn_eps), C.byref(handle), device=self.device)
         self._h = handle
         self._ws: Optional[torch.Tensor] = None
         self.precision = "f32"
@@ -177,7 +176,7 @@ class UNetEngine:
         file: the file's identity (path + content hash) is remembered and ``set_calibration_file`` does not read it again until it changes."""
         if self.calibration_source == "file" and self.calibration_file:
             self._dropped_file = (self.calibration_file, self._file_sha256(self.calibration_file))
-        _lib.check(self.lib.oai_unet_set_option(self._h, b"calibrated", 0), "oai_unet_set_option")
+        _lib.call("oai_unet_set_option", self._h, b"calibrated", 0)
         self._calibrated = False
         self.calibration_source = "none"
         self.calibration_census = None
@@ -191,8 +190,7 @@ class UNetEngine:
             raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)}")
         if precision == "fp16x3" and self._fp16_refused:
             precision = "f32"               # (warned when the calibration failed)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_set_precision(self._h, self.PRECISIONS[precision]), "oai_unet_set_precision")
+        _lib.call("oai_unet_set_precision", self._h, self.PRECISIONS[precision], device=self.device)
         self.precision = precision
 
     def __del__(self):
@@ -233,7 +231,7 @@ class UNetEngine:
         same parity gates; 0 = the direct form everywhere), "winograd_layers" (which layers), "m16" (default 1: the direct kernel of the layers with
         Cout % 128 != 0 on 16x16x32 tap pairs), "m16_layers" and "persistent" (default 0: dc2 with persistent workgroups, bit-identical, not faster); of the exact-fp32 path: "winograd_f32" (default 1: its
         k3 layers in x-axis Winograd form on exact fp32 products -- 2/3 of the fp32 MFMAs and closer to float64 than the direct form 0)."""
-        _lib.check(self.lib.oai_unet_set_option(self._h, name.encode(), int(value)), "oai_unet_set_option")
+        _lib.call("oai_unet_set_option", self._h, name.encode(), int(value))
         if name == "sres":
             # sres 0 = the superseded kernels that keep fp32 activations in memory and split them while staging: no range census, no
             # activation exponents, no LOW bit -- a comparison mode for tests and A/B timing, not a production setting
@@ -246,9 +244,7 @@ class UNetEngine:
         layer whose largest stored activation is below the calibrated window (include/oai_hip.h).  Non-zero = repeat that run in
         "f32".  Ordered on the current stream of this engine's device; synchronises that stream."""
         out = C.c_int(0)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_range_flag(self._h, int(reset), C.byref(out), torch.cuda.current_stream().cuda_stream),
-                       "oai_unet_range_flag")
+        _lib.call("oai_unet_range_flag", self._h, int(reset), C.byref(out), _lib.STREAM, device=self.device)
         return int(out.value)
 
     def range_overflow(self, reset: bool = True) -> bool:
@@ -259,22 +255,20 @@ class UNetEngine:
     def census(self, reset: bool = False):
         """max |stored activation| of each of the 18 layers since the last reset (0.0 = nothing stored); synchronises the stream."""
         out = (C.c_float * 18)()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_census(self._h, out, int(reset), torch.cuda.current_stream().cuda_stream), "oai_unet_census")
+        _lib.call("oai_unet_census", self._h, out, int(reset), _lib.STREAM, device=self.device)
         return list(out)
 
     def act_exponents(self):
         """(exponents of the 18 layers, calibrated?)"""
         e, cal = (C.c_int * 18)(), C.c_int(0)
-        _lib.check(self.lib.oai_unet_get_act_exponents(self._h, e, C.byref(cal)), "oai_unet_get_act_exponents")
+        _lib.call("oai_unet_get_act_exponents", self._h, e, C.byref(cal))
         return list(e), bool(cal.value)
 
     def set_act_exponents(self, exponents) -> None:
         """Explicit exponents (e.g. those of another rank, or saved next to a checkpoint); marks the engine calibrated."""
         if len(exponents) != 18:
             raise ValueError("need one exponent per layer (18)")
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_set_act_exponents(self._h, (C.c_int * 18)(*[int(v) for v in exponents])), "oai_unet_set_act_exponents")
+        _lib.call("oai_unet_set_act_exponents", self._h, (C.c_int * 18)(*[int(v) for v in exponents]), device=self.device)
         self._calibrated = True
         self.calibration_source = "set"
 
@@ -381,9 +375,7 @@ class UNetEngine:
         the flag of the segment calls queued so far, read later together with their results (cohort.py)."""
         if dst.dtype != torch.int32 or dst.device != self.device or dst.numel() < 1:
             raise ValueError("dst must be an int32 tensor on the engine's device")
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_range_flag_snapshot(self._h, dst.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                       "oai_unet_range_flag_snapshot")
+        _lib.call("oai_unet_range_flag_snapshot", self._h, dst.data_ptr(), _lib.STREAM, device=self.device)
 
     RANGE_STATE_WORDS = 19          # OAI_UNET_RANGE_STATE_WORDS
 
@@ -393,16 +385,12 @@ class UNetEngine:
         volume's tiles, then ``range_flag_from_state``: the flag of the whole volume, not of one rank's subset."""
         if dst.dtype != torch.int32 or dst.device != self.device or dst.numel() < self.RANGE_STATE_WORDS:
             raise ValueError("dst must be an int32 tensor of 19 words on the engine's device")
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_range_state_snapshot(self._h, dst.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                       "oai_unet_range_state_snapshot")
+        _lib.call("oai_unet_range_state_snapshot", self._h, dst.data_ptr(), _lib.STREAM, device=self.device)
 
     def range_flag_from_state(self, state: torch.Tensor) -> torch.Tensor:
         """int32[1] device tensor: the two-bit range flag of a (reduced) range state; queued on the current stream, no sync."""
         flag = torch.empty(1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_unet_range_flag_from_state(state.data_ptr(), flag.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                       "oai_unet_range_flag_from_state")
+        _lib.call("oai_unet_range_flag_from_state", state.data_ptr(), flag.data_ptr(), _lib.STREAM, device=self.device)
         return flag
 
     def tile_flops(self, tile_zyx, overlap_zyx, trimmed: bool) -> float:
@@ -412,12 +400,12 @@ class UNetEngine:
         return float(self.lib.oai_unet_tile_flops_conv3(self._h, *[int(v) for v in tile_zyx], _lib.int3(overlap_zyx), int(trimmed)))
 
     def profile(self, enable: bool) -> None:
-        _lib.check(self.lib.oai_unet_profile(self._h, int(enable)), "oai_unet_profile")
+        _lib.call("oai_unet_profile", self._h, int(enable))
 
     def profile_read(self):
         """(summed ms, launches) of the 3x3x3 implicit-GEMM kernel since the last read (HIP events on its stream)."""
         ms, n = C.c_double(), C.c_longlong()
-        _lib.check(self.lib.oai_unet_profile_read(self._h, C.byref(ms), C.byref(n)), "oai_unet_profile_read")
+        _lib.call("oai_unet_profile_read", self._h, C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def forward_tiles(self, tiles: torch.Tensor, batch: Optional[int] = None) -> torch.Tensor:
@@ -431,10 +419,8 @@ class UNetEngine:
 
         def launch():
             ws = self._workspace((d, h, w), nb)      # (sized per launch: a refused calibration switches the arithmetic in between; the C side loops over what the workspace holds)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.oai_unet_forward_tiles(self._h, tiles.data_ptr(), out.data_ptr(), B, d, h, w,
-                                                           ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-                           "oai_unet_forward_tiles")
+            _lib.call("oai_unet_forward_tiles", self._h, tiles.data_ptr(), out.data_ptr(), B, d, h, w, ws.data_ptr(), ws.numel(), _lib.STREAM,
+                      device=self.device)
         if self._needs_calibration():
             self.calibrate(launch)
         launch()
@@ -448,8 +434,8 @@ class UNetEngine:
         """FLOPs of each tile as ``segment_tiles`` computes it (list of floats, the reference's z-major tile order)."""
         _, _, n = tile_grid(size_zyx, tile_zyx, overlap_zyx)
         out = (C.c_double * n)()
-        _lib.check(self.lib.oai_unet_tile_costs(self._h, *[int(v) for v in size_zyx], _lib.int3(tile_zyx), _lib.int3(overlap_zyx),
-                                                _lib.int3(crop_zyx) if crop_zyx is not None else None, out, n), "oai_unet_tile_costs")
+        _lib.call("oai_unet_tile_costs", self._h, *[int(v) for v in size_zyx], _lib.int3(tile_zyx), _lib.int3(overlap_zyx),
+                  _lib.int3(crop_zyx) if crop_zyx is not None else None, out, n)
         return list(out)
 
     def segment_tiles(self, vol: torch.Tensor, tile_zyx, overlap_zyx, tile_range: Optional[Tuple[int, int]] = None,
@@ -483,12 +469,9 @@ class UNetEngine:
 
     def _launch_segment(self, vol, tile_zyx, overlap_zyx, crop_zyx, begin, end, out_mode, blocks, batch, ws) -> None:
         D, H, W = vol.shape
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_segment_tiles(self._h, vol.data_ptr(), D, H, W, _lib.int3(tile_zyx), _lib.int3(overlap_zyx),
-                                                  _lib.int3(crop_zyx) if crop_zyx is not None else None,
-                                                  int(begin), int(end), int(out_mode), blocks.data_ptr(), batch,
-                                                  ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-                       "oai_segment_tiles")
+        _lib.call("oai_segment_tiles", self._h, vol.data_ptr(), D, H, W, _lib.int3(tile_zyx), _lib.int3(overlap_zyx),
+                  _lib.int3(crop_zyx) if crop_zyx is not None else None, int(begin), int(end), int(out_mode), blocks.data_ptr(), batch,
+                  ws.data_ptr(), ws.numel(), _lib.STREAM, device=self.device)
 
     def calibrate_volume(self, vol: torch.Tensor, tile_zyx, overlap_zyx, crop_zyx=None, batch: Optional[int] = None) -> int:
         """calibrate() on all tiles of ``vol`` (the census is a maximum: the result does not depend on batching or tile order)."""
@@ -514,16 +497,12 @@ class UNetEngine:
             if not buf.is_contiguous() or buf.device != self.device or buf.dtype != torch.float32:
                 raise ValueError("the gather buffer must be a contiguous float32 tensor on the engine's device")
             bounds = (C.c_int * len(g.bounds))(*g.bounds)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.oai_stitch_blocks_ranged(buf.data_ptr(), self.n_classes, D, H, W, _lib.int3(tile_zyx), _lib.int3(overlap_zyx),
-                                                             crop, bounds, len(g.bounds) - 1, g.stride, maps.data_ptr(),
-                                                             torch.cuda.current_stream().cuda_stream), "oai_stitch_blocks_ranged")
+            _lib.call("oai_stitch_blocks_ranged", buf.data_ptr(), self.n_classes, D, H, W, _lib.int3(tile_zyx), _lib.int3(overlap_zyx), crop,
+                      bounds, len(g.bounds) - 1, g.stride, maps.data_ptr(), _lib.STREAM, device=self.device)
             return maps
         if blocks.shape[0] != ntiles:
             raise ValueError(f"stitch needs the blocks of all {ntiles} tiles, got {blocks.shape[0]}")
         blocks = blocks.contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.oai_stitch_blocks(blocks.data_ptr(), self.n_classes, D, H, W, _lib.int3(tile_zyx),
-                                                  _lib.int3(overlap_zyx), crop, maps.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream), "oai_stitch_blocks")
+        _lib.call("oai_stitch_blocks", blocks.data_ptr(), self.n_classes, D, H, W, _lib.int3(tile_zyx), _lib.int3(overlap_zyx), crop,
+                  maps.data_ptr(), _lib.STREAM, device=self.device)
         return maps

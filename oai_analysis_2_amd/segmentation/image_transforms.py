@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .. import _lib
 from ..image import Image, as_image
 from .engine import tile_grid
 
@@ -34,12 +35,10 @@ class Partition(object):
         vol = torch.from_numpy(np.ascontiguousarray(img.array, dtype=np.float32)).cuda()
         eff, grid, n = self.geometry(vol.shape)
         t, o = [int(v) for v in self.tile_size], [int(v) for v in self.overlap_size]
-        from .. import _lib
-        lib = _lib.load()
         tiles = torch.empty((n, 1, *t), dtype=torch.float32, device=vol.device)
-        with torch.cuda.device(vol.device):          # the gather is a HIP kernel (oai_partition_tiles), not torch indexing
-            _lib.check(lib.oai_partition_tiles(vol.data_ptr(), *[int(v) for v in vol.shape], _lib.int3(t), _lib.int3(o), 0, n,
-                                               tiles.data_ptr(), torch.cuda.current_stream().cuda_stream), "oai_partition_tiles")
+        # the gather is a HIP kernel (oai_partition_tiles), not torch indexing
+        _lib.call("oai_partition_tiles", vol.data_ptr(), *[int(v) for v in vol.shape], _lib.int3(t), _lib.int3(o), 0, n, tiles.data_ptr(),
+                  _lib.STREAM, device=vol.device)
         sample = dict(sample)
         sample["image"] = tiles
         return sample
@@ -49,10 +48,8 @@ class Partition(object):
         size, the outer frame of ``crop_size`` zeroed (``crop_size`` indexed like the reference: [2] is z, [0] lands on numpy
         axis 1, [1] on axis 2; a zero component zeroes everything, :509-513).  Runs on the device (oai_stitch_blocks);
         returns float64 like the reference unless ``data_type`` is given."""
-        from .. import _lib
-        lib = _lib.load()
         if is_vote:
-            return self._assemble_vote(lib, tiles, if_itk, crop_size, data_type)
+            return self._assemble_vote(tiles, if_itk, crop_size, data_type)
         t = torch.as_tensor(np.asarray(tiles) if not isinstance(tiles, torch.Tensor) else tiles).to(torch.float32)
         if t.dim() == 5:
             t = t[:, 0]
@@ -65,9 +62,8 @@ class Partition(object):
         blocks = t[:, oz:tz - oz, oy:ty - oy, ox:tx - ox].contiguous().cuda()            # [N][ez][ey][ex], one class
         maps = torch.empty((1, D, H, W), dtype=torch.float32, device=blocks.device)
         crop = _lib.int3((int(crop_size[2]), int(crop_size[0]), int(crop_size[1]))) if crop_size is not None and len(crop_size) else None
-        with torch.cuda.device(blocks.device):
-            _lib.check(lib.oai_stitch_blocks(blocks.data_ptr(), 1, D, H, W, _lib.int3((tz, ty, tx)), _lib.int3((oz, oy, ox)), crop,
-                                             maps.data_ptr(), torch.cuda.current_stream().cuda_stream), "oai_stitch_blocks")
+        _lib.call("oai_stitch_blocks", blocks.data_ptr(), 1, D, H, W, _lib.int3((tz, ty, tx)), _lib.int3((oz, oy, ox)), crop, maps.data_ptr(),
+                  _lib.STREAM, device=blocks.device)
         out = maps[0].cpu().numpy().astype(data_type if data_type else np.float64)
         return self._finish(out, if_itk)
 
@@ -79,10 +75,9 @@ class Partition(object):
             return img
         return out
 
-    def _assemble_vote(self, lib, tiles, if_itk, crop_size, data_type):
+    def _assemble_vote(self, tiles, if_itk, crop_size, data_type):
         """The vote branch (image_transforms.py:466-484) on the device: labels must be the integers 0..L-1 (the reference indexes its
         vote array with the label value); uint8 result, float64 once ``crop_size`` is applied (np.zeros canvas, :509-513)."""
-        from .. import _lib
         t = torch.as_tensor(np.asarray(tiles) if not isinstance(tiles, torch.Tensor) else tiles)
         if t.dim() == 5:
             t = t[:, 0]
@@ -102,9 +97,8 @@ class Partition(object):
         if nlab > 16:
             raise NotImplementedError("more than 16 label classes")
         out = torch.empty((D, H, W), dtype=torch.uint8, device=lab.device)
-        with torch.cuda.device(lab.device):
-            _lib.check(lib.oai_assemble_vote(lab.data_ptr(), nlab, D, H, W, _lib.int3((tz, ty, tx)), _lib.int3((oz, oy, ox)),
-                                             out.data_ptr(), torch.cuda.current_stream().cuda_stream), "oai_assemble_vote")
+        _lib.call("oai_assemble_vote", lab.data_ptr(), nlab, D, H, W, _lib.int3((tz, ty, tx)), _lib.int3((oz, oy, ox)), out.data_ptr(),
+                  _lib.STREAM, device=lab.device)
         res = out.cpu().numpy()
         if data_type:
             res = res.astype(data_type)

@@ -55,10 +55,10 @@ for c in (6, 18, 26):
 
 
 def both():
-    buf = torch.empty(2 * qc.SHAPE_SLOTS, dtype=torch.int64, device="cuda")
-    for i, k in enumerate(("FC", "TC")):
-        qc._queue_shape(dev[k], 0.5, 26, 0, (0.1, 0.9), buf[i * qc.SHAPE_SLOTS:(i + 1) * qc.SHAPE_SLOTS])
-    return buf
+    views, _ = qc._result_slots(dev["FC"].device, [slot for k in ("FC", "TC") for slot in qc._shape_layout(k)])
+    for k in ("FC", "TC"):
+        qc._queue_shape(dev[k], 0.5, 26, 0, (0.1, 0.9), views, k)
+    return views
 
 
 res["segmentation_shape_both_queued"] = timed(both)

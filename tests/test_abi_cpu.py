@@ -35,6 +35,27 @@ def test_bad_arguments_are_reported_not_crashed():
     assert rc != 0
 
 
+def test_the_one_call_path_reports_status_stream_and_symbol_faults():
+    """_lib.call, the one way the package reaches the C ABI: a non-zero status raises OaiError under the symbol's name; STREAM without a
+    device and an undeclared symbol are refused before the library is touched.  No GPU is touched."""
+    import pytest
+    with pytest.raises(_lib.OaiError) as exc:
+        _lib.call("oai_unet_set_precision", None, 3)
+    assert str(exc.value).startswith("oai_unet_set_precision failed")
+
+    class Untouchable:
+        def __getattr__(self, name):
+            raise AssertionError(f"the library was reached for {name}")
+    real, _lib._lib = _lib._lib, Untouchable()
+    try:
+        with pytest.raises(ValueError):
+            _lib.call("oai_grid_sample3d", None, 1, 4, 4, 4, None, 4, 4, 4, None, _lib.STREAM)
+        with pytest.raises(_lib.OaiError, match="oai_no_such_symbol"):
+            _lib.call("oai_no_such_symbol")
+    finally:
+        _lib._lib = real
+
+
 def test_argument_checks_of_the_later_entry_points():
     """Bad arguments come back as a non-zero status with a message -- no GPU is touched before the checks."""
     import ctypes as C
