@@ -102,16 +102,20 @@ const Tables& host_tables() {
 __constant__ signed char c_tri[256][16];
 __constant__ unsigned char c_ntri[256];
 
+// __constant__ memory is per device: the tables go once to every GPU that runs marching cubes, the current one of the calling entry point
 int upload_tables() {
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    // per device would be more general; the library targets one GPU per process
-    std::call_once(once, [] {
-        const Tables& t = host_tables();
-        err = hipMemcpyToSymbol(HIP_SYMBOL(c_tri), t.tri, sizeof(t.tri));
-        if (err == hipSuccess) err = hipMemcpyToSymbol(HIP_SYMBOL(c_ntri), t.ntri, sizeof(t.ntri));
-    });
+    static std::mutex mu;
+    static std::vector<char> done;                         // by device ordinal
+    int dev = 0;
+    OAI_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (dev < (int)done.size() && done[dev]) return OAI_OK;
+    const Tables& t = host_tables();
+    hipError_t err = hipMemcpyToSymbol(HIP_SYMBOL(c_tri), t.tri, sizeof(t.tri));
+    if (err == hipSuccess) err = hipMemcpyToSymbol(HIP_SYMBOL(c_ntri), t.ntri, sizeof(t.ntri));
     if (err != hipSuccess) return oai::set_error(OAI_ERR_HIP, "marching-cubes table upload failed: %s", hipGetErrorString(err));
+    if (dev >= (int)done.size()) done.resize(dev + 1, 0);
+    done[dev] = 1;
     return OAI_OK;
 }
 

@@ -40,19 +40,21 @@ __global__ void window_params_kernel(WindowState* st, float g_lo, float g_hi) {
 __global__ void __launch_bounds__(kThreads) window_apply_kernel(const float* __restrict__ x, size_t n, const WindowState* st,
                                                                 float omin, float omax, float* __restrict__ out) {
     const float wmin = st->window[0], wmax = st->window[1];
+    // the functor rounds the product and the sum one after the other; a fused multiply-add gives other bits (x == wmin would not map to
+    // out_min exactly), so nothing here may be contracted
     const double factor = ((double)omax - (double)omin) / ((double)wmax - (double)wmin);
-    const double offset = (double)omin - (double)wmin * factor;
+    const double offset = __dsub_rn((double)omin, __dmul_rn((double)wmin, factor));
     const size_t n4 = n / 4;
     for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)gridDim.x * kThreads) {
         const float4 v = reinterpret_cast<const float4*>(x)[i];
         float r[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) r[j] = r[j] < wmin ? omin : (r[j] > wmax ? omax : (float)((double)r[j] * factor + offset));
+        for (int j = 0; j < 4; ++j) r[j] = r[j] < wmin ? omin : (r[j] > wmax ? omax : (float)__dadd_rn(__dmul_rn((double)r[j], factor), offset));
         reinterpret_cast<float4*>(out)[i] = make_float4(r[0], r[1], r[2], r[3]);
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) {
         const float v = x[i];
-        out[i] = v < wmin ? omin : (v > wmax ? omax : (float)((double)v * factor + offset));
+        out[i] = v < wmin ? omin : (v > wmax ? omax : (float)__dadd_rn(__dmul_rn((double)v, factor), offset));
     }
 }
 
