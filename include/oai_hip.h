@@ -221,10 +221,8 @@ int oai_unet_set_act_exponents(oai_unet* h, const int e[OAI_UNET_NUM_LAYERS]);
  * (the library does not read the environment):
  *   "sres" 0|1 (1)      activations resident as fp16 term pairs (unet_sres.h) / fp32-resident split kernels
  *   "sres_mrep" 2|4 (4) z slices per workgroup of the split-resident conv kernel
- *   "sres_ring" 0|1 (0) six-slot z-plane ring staging (implies sres_mrep 2)
  *   "xcd_group" n (32)  logical blocks dealt to one XCD at a time; 0 = plain launch order
  *   "fuse_first" 0|1 (1) ec0 (networks.py:43) computed inside ec1's halo staging instead of as its own launch (when ec1 is one main-shape launch)
- *   "b_lds" 0|1 (0)     conv weight fragments through a three-slot LDS ring shared by the four waves of a workgroup
  *   "wide" 0|1|2 (1)    layers with Cout % 128 == 0 run conv3_igemm_sres2: one 8-wave workgroup per CU computes 128 couts of a
  *                       block from ONE double-buffered halo box (unet_sres2.h); 1 = launches of >= 1024 workgroups, 2 = always
  *   "shared_enc" 0|1 (1) oai_segment_tiles computes ec0 -> ec1 once over the padded volume + a 2-voxel shell per tile (needs the workspace
@@ -243,9 +241,6 @@ int oai_unet_set_act_exponents(oai_unet* h, const int e[OAI_UNET_NUM_LAYERS]);
  *                       stays bit-preserving); every launch shape of the kernel has the variant: one summation order per layer.  Same cycles per FLOP,
  *                       +12-14 % clock at the power wall: ec1 16.8 -> 14.6, ec2 4.9 -> 3.9, dc1 8.5 -> 7.2 ms per 160 tiles.  "m16_layers" (mask, all):
  *                       bit k = layer k may take it (A/B of single layers)
- *   "persistent" 0|1 (0) bit-preserving (round 5): the 64-cout Winograd layer (dc2) with ONE persistent workgroup per CU that pulls blocks from per-XCD counters
- *                       (a small plan kernel in front of every launch) while its staging waves run one block ahead.  Built for VERDICT r4 #1 (b) / (d); measured
- *                       +-0 ... +0.8 % per pass (profiles/r05_persistent.md): not the default
  *   "winograd_f32" 0|1 (1) NOT bit-preserving (round 6): every k3 layer of OAI_PREC_F32 (ec1 ... dc1; ec1 / ec3 / ec5 with their MaxPool3d fused where the launch is a
  *                       whole tile) runs conv3_wino_f32 (unet_wino_f32.h): the x axis in Winograd F(2,3) form, exact fp32 products, the direct kernel's two-level
  *                       accumulation = 2/3 of the fp32 MFMAs (pass 590 -> 445 ms), and 0.66-0.70 x the reference's own fp32 distance from its float64 run where the

@@ -75,17 +75,12 @@ struct oai_unet {
     int opt_m16_layers = 0x3FFFF;       // option "m16_layers"
     int opt_dead_stores = 1;            // option "dead_stores"
     int opt_census = 1;                 // option "census"
-    int opt_persist = 0;                // option "persistent"
     int xcd_group = 32;                 // option "xcd_group"
-    bool sres_ring = false;             // option "sres_ring"
-    int b_lds = 0;                      // option "b_lds"
     int fuse_first = 1;                 // option "fuse_first"
     int sres_mrep = 4;                  // option "sres_mrep"
     bool opt_sres = true;               // option "sres": fp16x3 uses the split-resident kernels
     bool sres = false;                  // fp16x3 runs split-resident (activations stored as fp16 term pairs, unet_sres.h)
     unsigned char* zero_rec = nullptr;  // 64 zero bytes: source of halo voxels outside the tile for the LDS-DMA staging
-    int* ps_plan = nullptr;             // the block plan of a persistent launch (wino_plan_kernel): 288 + 8 x 256 ints
-    int n_cus = 256;                    // compute units of the device (persistent launches: one workgroup per CU)
     int n_classes = 0;
     std::vector<void*> allocs;
     bool profile = false;
@@ -643,8 +638,7 @@ static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int
     constexpr bool kMainShape = RX == 16 && RY == 2 && WY == 4 && WX == 1;
     // + the 4-row y strip (dc5: 2.27 -> 1.89 ms); the 4-column x strip <4,8,4,1> measured slower there (2.05 -> 2.30 ms) and stays on the 4-wave kernel
     constexpr bool kWideShape = kMainShape || (RX == 16 && RY == 2 && WY == 2 && WX == 2);
-    bool wide = KC == 8 && kWideShape && h->sres && h->opt_wide && sres_mrep == 4 && !h->sres_ring &&
-                !h->b_lds && !a.first_w && !a.head_w && a.Cout % 128 == 0;
+    bool wide = KC == 8 && kWideShape && h->sres && h->opt_wide && sres_mrep == 4 && !a.first_w && !a.head_w && a.Cout % 128 == 0;
     if (wide && h->opt_wide == 1) {
         const size_t nwg = (size_t)ntiles * cdiv(box.hi[0] - box.lo[0], 4) * cdiv(box.hi[1] - box.lo[1], WY * RY) * cdiv(box.hi[2] - box.lo[2], WX * RX) * (a.Cout / 128);
         wide = nwg >= (kMainShape ? 1024 : 512);
@@ -666,12 +660,12 @@ static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int
         bool done = false;
         // the 16x16x32 tap pairs (option "m16"): a per-LAYER decision -- never for a layer that the bit-identical 128-cout form conv3_igemm_sres2 may
         // take for some of its launches (that choice depends on the launch size) -- and every shape of the kernel has the variant
-        const bool m16 = h->opt_m16 && a.wpanel16 && !h->sres_ring && !h->b_lds && a.Cout % 128 != 0 && !one_wg;
+        const bool m16 = h->opt_m16 && a.wpanel16 && a.Cout % 128 != 0 && !one_wg;
         if (m16) a.wpanel = a.wpanel16;
         if constexpr (RX == 16 && RY == 2 && WY == 4 && WX == 1) {
             if (a.first_w) {                                         // ec0 fused into ec1's halo staging (first_fusable guarantees mrep 4, no strips)
-                if (m16) conv3_igemm_sres<4, RX, RY, WY, WX, false, true, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
-                else conv3_igemm_sres<4, RX, RY, WY, WX, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
+                if (m16) conv3_igemm_sres<4, RX, RY, WY, WX, true, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
+                else conv3_igemm_sres<4, RX, RY, WY, WX, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
                 done = true;
             }
         }
@@ -684,11 +678,9 @@ static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int
         }
         if (done) { }
         else if (a.first_w) return set_error(OAI_ERR_ARG, "fused ec0 asked of a tile shape that has no such kernel");
-        else if (m16 && sres_mrep == 4) conv3_igemm_sres<4, RX, RY, WY, WX, false, false, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
-        else if (m16) conv3_igemm_sres<2, RX, RY, WY, WX, false, false, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
-        else if (sres_mrep == 4 && h->b_lds) conv3_igemm_sres<4, RX, RY, WY, WX, false, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
+        else if (m16 && sres_mrep == 4) conv3_igemm_sres<4, RX, RY, WY, WX, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
+        else if (m16) conv3_igemm_sres<2, RX, RY, WY, WX, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
         else if (sres_mrep == 4) conv3_igemm_sres<4, RX, RY, WY, WX><<<grid, 256, one_wg ? 24 * 1024 : 0, st>>>(a, h->zero_rec);
-        else if (h->sres_ring && !mrep_override) conv3_igemm_sres<2, RX, RY, WY, WX, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
         else conv3_igemm_sres<2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a, h->zero_rec);
     }
     else if (KC == 8 && h->precision == OAI_PREC_BF16X3) conv3_igemm_bf16s<2, false, 2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
@@ -720,7 +712,7 @@ static Cover direct_cover(const oai_unet* h, const Box& box) { return cover_box(
 
 // what fusing ec0 into ec1 asks of the configuration: the default split-resident kernel and the reference's channel counts (1 -> 32 -> ...)
 static bool first_fusion_ok(const oai_unet* h) {
-    return h->sres && h->fuse_first && h->variant == 0 && h->sres_mrep == 4 && !h->sres_ring && h->L[EC0].cout == 32 && h->L[EC1].c0 == 32;
+    return h->sres && h->fuse_first && h->variant == 0 && h->sres_mrep == 4 && h->L[EC0].cout == 32 && h->L[EC1].c0 == 32;
 }
 // ec0 can be computed inside ec1's halo staging (conv3_igemm_sres<..., FIRST>) when ec1 runs as ONE launch of the main shape
 static bool first_fusable(const oai_unet* h, const Box& ec1_box) {
@@ -794,41 +786,6 @@ static bool wino_m16_64(const oai_unet* h, const Layer& L, int cout) {
     return cout % 128 != 0 && (h->opt_wino & 32) && !(h->opt_wino & (4 | 8)) && L.panel_wino16 && wino_ws_fits();
 }
 
-// The block plan of one persistent launch of conv3_wino_sres<..., PS> (one workgroup): per tile the sub-box of the block grid that meets the tile's own
-// box, the number of blocks in front of every tile, the total -- and the XCDs' counters back at zero.  Layout: ConvArgs::ps_plan.
-constexpr int kPsMaxTiles = 256;
-__global__ void __launch_bounds__(kPsMaxTiles) wino_plan_kernel(int* __restrict__ plan, const int* __restrict__ boxes, int ntiles, int lo0, int lo1, int lo2, int hi0, int hi1, int hi2,
-                                                                 int tz, int ty, int tx, int nbz, int nby, int nbx, int ncb) {
-    __shared__ int cnt[kPsMaxTiles];
-    const int t = threadIdx.x;
-    int c = 0;
-    if (t < ntiles) {
-        const int llo[3] = {lo0, lo1, lo2}, lhi[3] = {hi0, hi1, hi2}, bs[3] = {tz, ty, tx}, nbk[3] = {nbz, nby, nbx};
-        int b0[3], nn[3];
-        bool any = true;
-        for (int i = 0; i < 3; ++i) {
-            int l = llo[i], h = lhi[i];
-            if (boxes) { l = max(l, boxes[6 * t + i]); h = min(h, boxes[6 * t + 3 + i]); }
-            any = any && l < h;
-            b0[i] = any ? (l - llo[i]) / bs[i] : 0;                                  // first block whose [o, o + bs) reaches l
-            const int b1 = any ? min(nbk[i], (h - llo[i] + bs[i] - 1) / bs[i]) : 0;     // one past the last block that starts below h
-            nn[i] = max(0, b1 - b0[i]);
-        }
-        c = any ? nn[0] * nn[1] * nn[2] * ncb : 0;
-        int* sb = plan + 288 + 8 * t;
-        sb[0] = b0[0]; sb[1] = nn[0]; sb[2] = b0[1]; sb[3] = nn[1]; sb[4] = b0[2]; sb[5] = nn[2];
-    }
-    cnt[t] = c;
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int i = 0; i < ntiles; ++i) { plan[16 + i] = run; run += cnt[i]; }
-        plan[16 + ntiles] = run;
-        plan[8] = run; plan[9] = ntiles;
-        for (int i = 0; i < 8; ++i) plan[i] = 0;
-    }
-}
-
 // One launch of conv3_wino_sres (unet_wino.h) with blocks of 4 x TY x 2 NP over `box` (box.lo[2] even)
 template <int TY, int NP>
 static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, const Box& box, int ntiles, hipStream_t st) {
@@ -850,14 +807,6 @@ static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, cons
         else if (wino_m16_64(h, L, a.Cout)) {                                                          // the multipliers' taps on v_mfma_f32_16x16x32_f16
             a.wpanel = L.panel_wino16;
             conv3_wino_sres<1, TY, NP, 1, true, true><<<grid, 512, 0, st>>>(a, h->zero_rec);
-        } else if (h->opt_persist && h->ps_plan && ntiles <= kPsMaxTiles && (a.C0 + 15) / 16 + (a.C1 + 15) / 16 >= 6) {
-            // persistent workgroups, one per CU, the staging waves one block ahead (unet_wino.h, PS): the plan first, same stream
-            wino_plan_kernel<<<1, kPsMaxTiles, 0, st>>>(h->ps_plan, a.boxes, ntiles, a.lo[0], a.lo[1], a.lo[2], a.hi[0], a.hi[1], a.hi[2], 4, TY, 2 * NP, a.nbz, a.nby, a.nbx, a.ncb);
-            OAI_CHECK_LAUNCH();
-            a.ps_plan = h->ps_plan;
-            const unsigned total = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-            const unsigned pgrid = total < (unsigned)h->n_cus ? total : (unsigned)h->n_cus;
-            conv3_wino_sres<1, TY, NP, 1, true, false, true><<<pgrid, 512, 0, st>>>(a, h->zero_rec);
         } else conv3_wino_sres<1, TY, NP, 1, true><<<grid, 512, 0, st>>>(a, h->zero_rec);              // one block of 64 couts: four waves multiply, four stage
     } else if (wino_m16_64(h, L, a.Cout)) {                                          // (the y strip's two T buffers would not fit: the eight waves split the z slices --
         a.wpanel = L.panel_wino16;                                                     //  on the same tap pairs as the layer's other shapes: one summation order per layer)
@@ -928,7 +877,7 @@ static int launch_conv3(const oai_unet* h, const Layer& L, const float* s0, cons
     if (h->precision == OAI_PREC_F32 && h->variant == 0 && h->opt_wino_f32 && L.panel_wino_f32 && a.Cout % 4 == 0 && !a.head_w && !a.first_w && !a.sc_boxes &&
         (!a.pool_out || (wino_pool_box(box, dims) && dims[0] % 2 == 0)) && layer_bit(h, h->opt_wino_layers, L))
         return launch_conv3_wino_f32(h, L, a, box, ntiles, st);
-    if (h->sres && h->opt_wino && L.panel_wino && h->sres_mrep == 4 && !h->sres_ring && !h->b_lds && !a.first_w && !a.head_w && !a.sc_boxes &&
+    if (h->sres && h->opt_wino && L.panel_wino && h->sres_mrep == 4 && !a.first_w && !a.head_w && !a.sc_boxes &&
         (!a.pool_out || (a.Cout % 128 == 0 && a.relu && wino_pool_box(box, dims))) && a.Cout % 64 == 0 && (h->opt_wino & (a.Cout % 128 == 0 ? 1 : 2)) && (a.Cout % 128 == 0 || (a.C0 + 15) / 16 + (a.C1 + 15) / 16 >= 8) && layer_bit(h, h->opt_wino_layers, L) && (size_t)dims[0] * dims[1] * dims[2] < (1u << 24))
         return launch_conv3_wino(h, L, a, box, ntiles, st);
     const Cover c = direct_cover(h, box);
@@ -1304,15 +1253,9 @@ int oai_unet_create(const oai_layer_params layers[OAI_UNET_NUM_LAYERS], float bn
     oai_unet* h = new oai_unet();
     int rc = alloc_zeroed(h, 256, &h->range_flag);
     if (!rc) rc = alloc_zeroed(h, 256, &h->zero_rec);
-    if (!rc) rc = alloc_zeroed(h, (288 + 8 * kPsMaxTiles) * sizeof(int), &h->ps_plan);
     if (!rc) rc = alloc_zeroed(h, 18 * 16 * sizeof(unsigned) + 256, &h->census);      // the census, then the scratch word of oai_unet_range_flag
     if (rc) { oai_unet_destroy(h); return rc; }
     h->eval_out = reinterpret_cast<int*>(h->census + 18 * 16);
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->n_cus = prop.multiProcessorCount;
-    }
     h->variant = diag_env("OAI_CONV_VARIANT", 0);
     if (h->variant < 0 || h->variant > 2) h->variant = 0;
     h->n_classes = layers[DC0].cout;
@@ -1385,8 +1328,6 @@ int oai_unet_set_precision(oai_unet* h, int mode) {
 // The options that are one int in a range, one row each: name, field, lo, hi, the message for a value outside [lo, hi] -- and what the option does.
 struct IntOption { const char* name; int oai_unet::*field; int lo, hi; const char* message; };
 static const IntOption kIntOptions[] = {
-    // weight fragments through a three-slot LDS ring shared by the workgroup
-    {"b_lds", &oai_unet::b_lds, 0, 1, "oai_unet_set_option: b_lds must be 0 or 1"},
     // ec0 -> ec1 computed ONCE over the reflect-padded volume + a 2-voxel shell per tile (oai_segment_tiles)
     {"shared_enc", &oai_unet::opt_shared, 0, 1, "oai_unet_set_option: shared_enc must be 0 or 1"},
     // layers with Cout % 128 == 0 run conv3_igemm_sres2 (one 8-wave workgroup per CU, double-buffered halo)
@@ -1397,8 +1338,6 @@ static const IntOption kIntOptions[] = {
     // summation order; default 1) for every layer that can never take the bit-identical 128-cout form conv3_igemm_sres2 -- i.e. Cout % 128 != 0 -- so that a
     // layer runs ONE order whatever shapes cover it and option "wide" stays bit-preserving
     {"m16", &oai_unet::opt_m16, 0, 1, "oai_unet_set_option: m16 must be 0 or 1"},
-    // bit 0 = the specialised 64-cout Winograd form (dc2) with persistent workgroups, the staging waves one block ahead (conv3_wino_sres<..., PS>; bit-identical maps)
-    {"persistent", &oai_unet::opt_persist, 0, 1, "oai_unet_set_option: persistent is a mask (bit 0)"},
     // bit k = layer k may take the tap-pair form (A/B of single layers)
     {"m16_layers", &oai_unet::opt_m16_layers, 0, 0x3FFFF, "oai_unet_set_option: m16_layers is a mask over the 18 layers"},
     // 1 = the encoder does not write the part of a skip tensor that the decoder never reads
@@ -1433,12 +1372,7 @@ int oai_unet_set_option(oai_unet* h, const char* name, int value) {
         h->sres = h->precision == OAI_PREC_FP16X3 && h->opt_sres;
     } else if (!strcmp(name, "sres_mrep")) {           // z slices per block of the split-resident conv kernel (2 runs three workgroups per CU: -2 % on 32 border tiles, +0.5 % on the whole volume)
         OAI_CHECK_ARG(value == 2 || value == 4, "oai_unet_set_option: sres_mrep must be 2 or 4");
-        OAI_CHECK_ARG(!(h->sres_ring && value != 2), "oai_unet_set_option: the plane ring needs sres_mrep 2");
         h->sres_mrep = value;
-    } else if (!strcmp(name, "sres_ring")) {           // six-slot z-plane ring (implies sres_mrep 2)
-        OAI_CHECK_ARG(value == 0 || value == 1, "oai_unet_set_option: sres_ring must be 0 or 1");
-        h->sres_ring = value != 0;
-        if (h->sres_ring) h->sres_mrep = 2;
     } else if (!strcmp(name, "winograd")) {
         // plain k3 layers with Cout % 64 == 0 run conv3_wino_sres (x axis in Winograd F(2,3) form: 2/3 of the MFMAs).  bit 0: layers with Cout % 128 == 0 (two cout
         // groups per workgroup), bit 1: one block of 64 couts and >= 8 chunks (specialised waves); A/B only: bit 2 = the slice-split form instead, bit 3 = the
@@ -1726,7 +1660,7 @@ static SegParams seg_params(int D, int H, int W, const int tile[3], const int ov
 
 // bytes of the two volume-wide tensors of the shared encoder pass, or 0 when its conditions do not hold for this geometry
 static size_t shared_enc_bytes(const oai_unet* h, const int tile[3], const int overlap[3], const SegGeom& g, int P[3]) {
-    if (!first_fusion_ok(h) || !h->opt_shared || h->b_lds || h->L[EC1].cout % 16 != 0) return 0;
+    if (!first_fusion_ok(h) || !h->opt_shared || h->L[EC1].cout % 16 != 0) return 0;
     const int blk[3] = {4, 8, 16};                                         // the main block shape must tile the padded volume and the tile exactly
     for (int i = 0; i < 3; ++i) {
         P[i] = g.eff[i] * g.grid[i] + 2 * overlap[i];

@@ -166,20 +166,14 @@ __device__ __forceinline__ f32x4m gload16m(const void* sbase, unsigned voff) {
 // while the other stages), but the halo arrives by LDS-DMA: no staging registers, no staging VALU.
 // MREP = z slices per block = accumulator row blocks per wave: 4 halves the weight-fragment bytes per MFMA (the L1 path
 // moving 4 KiB of B per wave per tap is what bounds the 3-pass kernel), at 128 accumulator VGPRs.
-// RING (MREP = 2 only): the halo lives in a ring of six z-plane slots instead of one 4-plane box.  A chunk's taps run in dz
-// order and touch planes (dz, dz+1), so the planes of chunk c+1 can be DMA'd into the two spare slots and into the slots chunk c
-// frees as it goes -- every plane is requested three dz-phases (~10 us) before its first use, nothing is ever waited for, and
-// the block synchronises once per phase.  Same footprint as the MREP = 4 box (6 x 11.5 KB), two workgroups per CU.
 // FIRST (ec1 of the network, Cin = 32 = two chunks): the input of this layer is ec0 = relu(Conv3d(1 -> 32, k3 p1)(tile)), which costs 27
 // FMAs per value.  Instead of a launch that writes it to memory (10.7 GB per 160-tile pass) and a halo box that reads it back by
 // LDS-DMA (2.1 x that, HBM-latency misses that occupy the CU's L1 in front of the epilogue's stores), the block stages the raw
 // (HZ+2) x (HY+2) x (HX+2) patch of the volume once (7.7 KB, gathered with the reflect padding of Partition.__call__) and every
 // thread computes its halo records on the VALU -- the same fmaf chain, scale/shift, ReLU and split as conv3_first_sres_kernel, so the
 // records are bit-identical to the ones that kernel writes -- while the partner workgroup of the CU owns the matrix pipe.
-// BLDS (MREP 4, not FIRST / RING): the weight fragments of a tap -- the same 4 KiB for the four waves of the workgroup, which today each
-// fetch all of it through the CU's L1, in order behind the halo misses and the partner's stores -- go through a three-slot LDS ring:
-// every wave LDS-DMAs one KiB of the slab two taps ahead, one s_barrier per tap publishes it, and the fragments are read from LDS one tap
-// ahead.  12 KB on top of the 68 KB halo box: two workgroups fill the CU's 160 KB exactly.
+// (Two more forms were measured without gain and removed: a six-slot z-plane ring for the halo, profiles/r01_pmc_sres.md, and an LDS ring for
+// the weight fragments, profiles/r02_conv_per_layer.md section 3.)
 // M16 (round 5): the taps on v_mfma_f32_16x16x32_f16 instead of 32x32x16 -- what conv3_wino_sres<..., M16> (unet_wino.h) did for the two-group
 // Winograd form, for the DIRECT kernel (ec1 with the fused ec0, ec2, dc1 with the fused head, and every layer with option winograd 0).  This
 // loop runs at the power wall (1.72-1.74 GHz, profiles/r04_sq_summary.md); at equal cycles per FLOP the 16x16x32 shape holds a ~12-14 % higher
@@ -196,21 +190,16 @@ __device__ __forceinline__ f32x4m gload16m(const void* sbase, unsigned voff) {
 // tile is the same MREP x 32 rows x 64 couts as MREP x 2 tiles of 32 x 32 = MREP x 8 tiles of 16 x 16 (the same accumulator registers): element
 // (p, q, i) of the old (m, n) tile at row 16 p + 4 (lane >> 4) + i, cout column 16 q + (lane & 15).  Another summation order than the 32x32x16
 // form's (two taps at once), same arithmetic class; EVERY shape of this kernel has the variant, so a layer runs one order whatever shapes cover it.
-template <int MREP, int RX, int RY, int WY, int WX, bool RING = false, bool FIRST = false, bool BLDS = false, bool M16 = false>
-__global__ void __launch_bounds__(256, (MREP == 2 && !RING) ? 3 : 2) conv3_igemm_sres(const ConvArgs a, const unsigned char* __restrict__ zero_rec) {
-    static_assert(RX * RY == 32 && WY * WX == 4 && (MREP == 2 || MREP == 4) && (!RING || MREP == 2) && (!FIRST || !RING), "bad tile shape");
-    static_assert(!BLDS || (MREP == 4 && !RING && !FIRST), "the weight ring is for the default kernel");
-    static_assert(!M16 || (!RING && !BLDS), "the 16x16x32 taps: the plain and the ec0-fused form");
+template <int MREP, int RX, int RY, int WY, int WX, bool FIRST = false, bool M16 = false>
+__global__ void __launch_bounds__(256, MREP == 2 ? 3 : 2) conv3_igemm_sres(const ConvArgs a, const unsigned char* __restrict__ zero_rec) {
+    static_assert(RX * RY == 32 && WY * WX == 4 && (MREP == 2 || MREP == 4), "bad tile shape");
     constexpr int NREP = 2, TZ = MREP;
     constexpr int kTY = WY * RY, kTX = WX * RX, HY = kTY + 2, HX = kTX + 2, HZ = TZ + 2;
     constexpr int HVOX = HZ * HY * HX;
     constexpr int PIECES = HVOX * 4;                            // 16-byte slots of the halo buffer
     constexpr int NIT = (PIECES + 255) / 256;                    // LDS-DMA instructions per thread per chunk
-    constexpr int NITP = (HY * HX * 4 + 255) / 256;              // RING: ... per thread per z plane
-    constexpr int PLB = NITP * 256 * 16;                         // RING: bytes of one plane slot (whole 1-KiB wave writes)
-    constexpr int BUF = RING ? 6 * PLB : NIT * 256 * 16;         // bytes
+    constexpr int BUF = NIT * 256 * 16;                          // bytes
     __shared__ __attribute__((aligned(16))) unsigned char lds[BUF];
-    __shared__ __attribute__((aligned(16))) unsigned char blds[BLDS ? 3 * 4096 : 16];     // BLDS: weight slabs of taps g, g+1, g+2 (slot = tap % 3)
     constexpr int PZ = HZ + 2, PY = HY + 2, PX = HX + 2;         // FIRST: raw patch = halo box + ec0's own halo
     __shared__ float raw[FIRST ? PZ * PY * PX : 1];
     __shared__ int rawidx[FIRST ? PZ + PY + PX : 1];             // per-axis source offsets (reflect-padded volume index) or -1
@@ -451,33 +440,6 @@ __global__ void __launch_bounds__(256, (MREP == 2 && !RING) ? 3 : 2) conv3_igemm
         // (an if / else over a <2> and a <1> group made hipcc hoist all 432 weight loads above the branch and spill them to VGPR lanes)
     };
 
-    // ---- RING staging plan: this thread's NITP pieces of each of the chunk's four z planes
-    int pvr[RING ? 4 : 1][RING ? NITP : 1];
-    if constexpr (RING) {
-#pragma unroll
-        for (int lp = 0; lp < 4; ++lp)
-#pragma unroll
-            for (int it = 0; it < NITP; ++it) {
-                const int r = (it * 256 + tid) >> 2;
-                const int hx = r % HX, hy = r / HX;
-                const int gz = oz0 - 1 + lp, gy = oy0 - 1 + hy, gx = ox0 - 1 + hx;
-                const bool ok = r < HY * HX && (unsigned)gz < (unsigned)a.D && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-                pvr[lp][it] = ok ? ((((gz * a.H + gy) * a.W + gx) << 2) | ((hx >> 2) & 3)) : -1;
-            }
-    }
-    auto issue_plane = [&](int ch, int lp) {              // logical plane lp of chunk ch -> slot (4 ch + lp) mod 6
-        const bool first = ch < nch0;
-        const unsigned char* sb = first ? s0 : s1;
-        const int c = first ? ch : ch - nch0;
-        unsigned char* dst = lds + ((4 * ch + lp) % 6) * PLB + wave * 1024;
-#pragma unroll
-        for (int it = 0; it < (RING ? NITP : 0); ++it) {
-            const int v = pvr[RING ? lp : 0][RING ? it : 0];
-            const unsigned char* g = v >= 0 ? sb + ((size_t)c * plane + (size_t)(v >> 2)) * 64 + (((tid & 3) ^ (v & 3)) << 4) : zero_rec;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                             (__attribute__((address_space(3))) void*)(dst + it * 4096), 16, 0, 0);
-        }
-    };
     // ---- A fragments: byte offset of this lane's voxel for tap (0,0,0), and its swizzled slot per dx and term
     const unsigned char* abase = lds + (ly * HX + lx) * 64;
     int sl[3][2];
@@ -489,21 +451,6 @@ __global__ void __launch_bounds__(256, (MREP == 2 && !RING) ? 3 : 2) conv3_igemm
     constexpr int STEP = 2 * NREP * 64;                             // 16-byte units of weights per tap: [term][nr][lane]
     const float4* wp = a.wpanel + (size_t)cb * nchunks * 27 * STEP + lane;
     float4 bcur[2][NREP], bnext[2][NREP];
-    // BLDS: this lane's 16 bytes of the slab this wave copies (wave w moves bytes [1024 w, 1024 w + 1024) of every slab); `gleft` = slabs
-    // not yet requested (the pointer sticks to the last slab when they run out, so that every tap issues exactly one piece)
-    const unsigned char* bsrc = reinterpret_cast<const unsigned char*>(a.wpanel + (size_t)cb * nchunks * 27 * STEP) + wave * 1024 + lane * 16;
-    int gleft = nchunks * 27;
-    const unsigned bl_addr = __builtin_amdgcn_readfirstlane(lds_addr_of(blds) + wave * 1024);
-    auto issue_b = [&](int slot) __attribute__((always_inline)) {
-        lds_dma16(bsrc, bl_addr + slot * 4096);               // (asm form: no compiler-made vmcnt(0) in front of the next LDS read, see lds_dma16)
-        if (--gleft > 0) bsrc += 4096;
-    };
-    auto read_b = [&](float4 (&dst)[2][NREP], int slot) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int n = 0; n < NREP; ++n) dst[k][n] = *reinterpret_cast<const float4*>(blds + slot * 4096 + ((k * NREP + n) * 64 + lane) * 16);
-    };
     // M16: the panel of pack_conv3_m16_panel, [cb][chunk][step 14][X' | Y'][n2 4][lane] x 16 B = 8 KiB per step; a wave-uniform base forced into an
     // SGPR pair + this lane's 16 bytes, loaded by gload16_asm (invisible to the compiler's wait counting: every use goes through m16_wait first)
     constexpr int STEP16 = 2 * 4 * 64 * 16;                         // bytes per step
@@ -522,8 +469,6 @@ __global__ void __launch_bounds__(256, (MREP == 2 && !RING) ? 3 : 2) conv3_igemm
         // (no request here: the fragments of a chunk's step 0 are requested at the chunk's top, see run_chunks -- an asm load must never be in
         // flight across a control-flow merge: the compiler believes its result register already holds the value and may COPY it on an edge)
         asm volatile("s_nop 4" : "+s"(wp16) :: "memory");          // wp16 has just been made uniform by v_readfirstlane: five wait states before a VMEM reads it
-    } else if constexpr (BLDS) {
-        issue_b(0); issue_b(1); issue_b(2);
     } else {
 #pragma unroll
         for (int k = 0; k < 2; ++k)
@@ -532,37 +477,174 @@ __global__ void __launch_bounds__(256, (MREP == 2 && !RING) ? 3 : 2) conv3_igemm
         wp += STEP;
     }
 
-    constexpr int PA[3] = {0, 0, 1}, PB[3] = {0, 1, 0};
     float4 acur[2][MREP];           // (a register prefetch of the next tap's A fragments was measured: no gain, and it costs MREP 2 its third workgroup per CU)
     OAI_STAMP(7);
-    if constexpr (RING) {
-        const int arel = (ly * HX + lx) * 64;                          // this lane's voxel inside a plane, tap (dy, dx) = (0, 0)
-        issue_plane(0, 0); issue_plane(0, 1); issue_plane(0, 2); issue_plane(0, 3);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        for (int ch = 0; ch < nchunks; ++ch) {
-            int sb[4];
+    // One chunk = 27 taps x 24 MFMAs.  Pass order per tap: a0.b0, a0.b1, a1.b0 -- so the registers of the a0 fragments are dead
+    // after the second pass and those of a1 before the third: the a1 fragments of tap t are read from LDS at the top of the tap
+    // (needed 16 MFMAs = 512 cycles later) and the a0 fragments of tap t+1 behind the second pass (needed 8 MFMAs later): the
+    // LDS latency never meets an MFMA that waits for it, at no extra register (a second set of A registers does not fit).
+    // Blocks whose four z slices are all inside the tile's box (the large majority) run a branch-free stream; the first
+    // version tested `m >= m_lo && m < m_hi` around every pair of MFMAs, which hipcc turned into twelve taken branches per tap
+    // with the MFMA pairs in out-of-line blocks behind `s_waitcnt lgkmcnt(0)`.
+    // ML = number of live z slices of the block (slices [0, ML) are inside the tile's box): a compile-time count, so that the
+    // tap stream is branch-free and the dead slices cost neither LDS reads nor MFMAs.  Blocks whose live slices do not start at
+    // 0 (rare: a border tile's box starting inside a block) run ML = MREP; their dead rows accumulate values that the
+    // epilogue never stores (rows of an MFMA are independent).
+    auto run_chunks = [&](auto ml_tag) __attribute__((always_inline)) {
+        constexpr int ML = decltype(ml_tag)::value;
+        auto load_a = [&](float4 (&dst)[MREP], int t, int k) __attribute__((always_inline)) {
+            const int dz = t / 9, dy = (t / 3) % 3, dx = t % 3;
 #pragma unroll
-            for (int lp = 0; lp < 4; ++lp) sb[lp] = ((4 * ch + lp) % 6) * PLB + arel;
+            for (int m = 0; m < ML; ++m)
+                dst[m] = *reinterpret_cast<const float4*>(abase + (((m + dz) * HY + dy) * HX + dx) * 64 + sl[dx][k]);
+        };
+        for (int ch = 0; ch < nchunks; ++ch) {
+            OAI_STAMP(0);
+            // every wave is done reading the previous chunk.  A bare barrier behind lgkmcnt(0): __syncthreads() would also wait (vmcnt(0)) for
+            // the weight fragments of the next tap, requested a moment ago
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            OAI_STAMP(1);
+            if constexpr (M16) {
+                // the weight fragments of this chunk's step 0, requested in front of the halo staging: they land under the same wait.  They
+                // are NOT requested during the previous chunk's last step: an inline-asm load is invisible to the compiler -- it believes
+                // the result register holds the value from the asm statement on -- so a load in flight across the loop's back edge, the
+                // dispatch over the live-slice variants or the loop exit can be COPIED (register re-assignment on an edge) or its register
+                // re-used before the data has arrived.  Found with blocks of 1 and 3 live slices: their loop pre-headers copied the
+                // prologue's in-flight fragments (v_mov of stale registers), intermittently wrong results at small tile levels.  Every asm
+                // load of this kernel is now requested AND waited for inside one basic block.
+                if constexpr (!FIRST) { m16_req_y(); m16_req_lo(); m16_req_hi(); }
+            }
+            if constexpr (FIRST) stage_first(ch);
+            else stage(ch);
+            if constexpr (M16 && FIRST) { m16_req_y(); m16_req_lo(); m16_req_hi(); }      // (behind ec0's arithmetic, which has branches: same basic block as the wait below)
+            OAI_STAMP(2);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this thread's DMA pieces have landed ...
+            OAI_STAMP(3);
+            __syncthreads();                                             // ... and everybody else's
+            OAI_STAMP(4);
+            if constexpr (M16) {
+                // ---- 14 steps of tap pairs on v_mfma_f32_16x16x32_f16 (see the kernel's header comment).  Vector-memory order per step:
+                // Y'(j+1) behind pass B | X' lo(j+1) behind pass C lo | X' hi(j+1) behind pass C hi; the counted waits leave exactly the
+                // younger requests in flight.  (The fragments of this chunk's step 0 were requested at the chunk's top, above, and have
+                // landed behind the staging wait: vmcnt(0) is global.  Invariant: every asm load is requested AND waited for inside one basic block.)
+                constexpr int SLB = HY * HX * 64;                           // bytes between the z slices of the halo box
+                constexpr int POFF = (RX >= 32 ? 16 : (16 / RX) * HX) * 64;  // ... between rows 0-15 and rows 16-31 of the wave's tile
+                auto tapc = [](int q) constexpr { return ((q / 3) * HY + q % 3) * HX * 64; };      // tap (dz, dy) = q, dx 0
+                // this lane's record slot per step: lane group g = lane >> 4 reads channel half g & 1 of the pair's tap g >> 1
+                int lq = lane;
+                asm volatile("" : "+v"(lq));                                 // (recomputed every chunk: not held -- or spilled -- across the staging)
+                const int r16 = lq & 15, hsel = (lq >> 4) & 1, tsel = lq >> 5;
+                const int lx0 = wx * RX + r16 % RX, ly0 = wy * RY + r16 / RX;
+                const unsigned vbase = (unsigned)((ly0 * HX + lx0) * 64);
+                unsigned oA[2], oB[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    oA[k] = vbase + (unsigned)(tsel * 64 + (((k * 2 + hsel) ^ (((lx0 + tsel) >> 2) & 3)) << 4));       // steps 0..8: dx = tsel
+                    oB[k] = vbase + (unsigned)(128 + (((k * 2 + hsel) ^ (((lx0 + 2) >> 2) & 3)) << 4));                // steps 9..12: dx = 2
+                }
+                const unsigned oC = vbase + (unsigned)(128 + (((tsel * 2 + hsel) ^ (((lx0 + 2) >> 2) & 3)) << 4));     // step 13: term = tsel
+                const unsigned tHX = (unsigned)(tsel * HX * 64);             // the second tap of a dx = 2 pair: one row (steps 9..11) / one slice (step 12) further
+                auto a_off = [&](int j, int k) __attribute__((always_inline)) -> unsigned {
+                    if (j < 9) return oA[k] + (unsigned)tapc(j);
+                    if (j < 12) return oB[k] + tHX + (unsigned)tapc(3 * (j - 9));
+                    if (j == 12) return oB[k] + tHX * (unsigned)HY + (unsigned)tapc(2);
+                    return oC + (unsigned)tapc(8);
+                };
+                auto lda = [&](unsigned off, int m, int p) __attribute__((always_inline)) {
+                    return *reinterpret_cast<const float4*>(lds + off + m * SLB + p * POFF);
+                };
+                auto mma = [&](const float4& av, const f32x4m& bv, f32x4m& c) __attribute__((always_inline)) {
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8m, av), __builtin_bit_cast(f16x8m, bv), c, 0, 0, 0);
+                };
+                // the staging wait was vmcnt(0): the fragments of step 0 are in their registers (tie them behind it)
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(bY[0]), "+v"(bY[1]), "+v"(bY[2]), "+v"(bY[3]) :: "memory");
+                asm volatile("" : "+v"(bXlo[0]), "+v"(bXlo[1]), "+v"(bXhi[0]), "+v"(bXhi[1]) :: "memory");
+                float4 af[MREP][2];                                          // [m][p]: the A fragments of the running pass
+#pragma unroll
+                for (int m = 0; m < ML; ++m)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) af[m][p] = lda(a_off(0, 0), m, p);
+                // one step, J a compile-time constant: the 14 steps are 14 explicit calls (a `#pragma unroll` loop is a request -- hipcc left the
+                // ML = 4 body rolled, with run-time tests of j, i.e. branches while fragment loads are in flight: tests/test_abi_cpu.py (g))
+                auto m16_step = [&](auto jtag) __attribute__((always_inline)) {
+                    constexpr int j = decltype(jtag)::value;
+                    if (j > 0) asm volatile("s_waitcnt vmcnt(4)" : "+v"(bY[0]), "+v"(bY[1]), "+v"(bY[2]), "+v"(bY[3]) :: "memory");      // Y'(j) has landed; younger: lo(j), hi(j)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int m = 0; m < ML; ++m)                              // pass B: a0 . Y'   (step 13: [a0 | a1] . [b1 | 0])
+#pragma unroll
+                        for (int p = 0; p < 2; ++p)
+#pragma unroll
+                            for (int n = 0; n < 4; ++n) mma(af[m][p], bY[n], acc4[m][n >> 1][p * 2 + (n & 1)]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    wp16 += STEP16;
+                    if (j < 13) m16_req_y();                                  // Y' of the next step (step 13 requests nothing: see the chunk's top)
+                    if (j > 0 && j < 13) asm volatile("s_waitcnt vmcnt(6)" : "+v"(bXlo[0]), "+v"(bXlo[1]) :: "memory");      // lo(j); younger: hi(j), Y'(j + 1)
+                    if (j == 13) asm volatile("s_waitcnt vmcnt(2)" : "+v"(bXlo[0]), "+v"(bXlo[1]) :: "memory");              // (step 13: only hi(13) is younger)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int m = 0; m < ML; ++m)                              // pass A, low couts: a0 . X'[0, 1] over all slices
+#pragma unroll
+                        for (int p = 0; p < 2; ++p)
+#pragma unroll
+                            for (int n = 0; n < 2; ++n) mma(af[m][p], bXlo[n], acc4[m][0][p * 2 + n]);
+                    __builtin_amdgcn_sched_barrier(0);                        // (the wait below must not rise above these MFMAs: they are its lead)
+                    if (j > 0 && j < 13) asm volatile("s_waitcnt vmcnt(4)" : "+v"(bXhi[0]), "+v"(bXhi[1]) :: "memory");      // hi(j); younger: Y'(j + 1)
+                    if (j == 13) asm volatile("s_waitcnt vmcnt(0)" : "+v"(bXhi[0]), "+v"(bXhi[1]) :: "memory");              // (step 13: nothing is younger)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int m = 0; m < ML; ++m) {                            // pass A, high couts; behind each slice the a1 fragments of pass C take its registers
+#pragma unroll
+                        for (int p = 0; p < 2; ++p)
+#pragma unroll
+                            for (int n = 0; n < 2; ++n) mma(af[m][p], bXhi[n], acc4[m][1][p * 2 + n]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (j < 13) {
+#pragma unroll
+                            for (int p = 0; p < 2; ++p) af[m][p] = lda(a_off(j, 1), m, p);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if (j < 13) {
+#pragma unroll
+                        for (int m = 0; m < ML; ++m)                          // pass C, low couts: a1 . X'[0, 1]
+#pragma unroll
+                            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                                for (int n = 0; n < 2; ++n) mma(af[m][p], bXlo[n], acc4[m][0][p * 2 + n]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if (j < 13) m16_req_lo();                                 // the low couts of the next step's X'
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (j < 13) {
+#pragma unroll
+                        for (int m = 0; m < ML; ++m) {                        // pass C, high couts; behind each slice the a0 fragments of the next step
+#pragma unroll
+                            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                                for (int n = 0; n < 2; ++n) mma(af[m][p], bXhi[n], acc4[m][1][p * 2 + n]);
+                            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                            for (int p = 0; p < 2; ++p) af[m][p] = lda(a_off(j + 1, 0), m, p);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                    if (j < 13) m16_req_hi();                                 // the high couts of the next step's X'
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                m16_step(std::integral_constant<int, 0>{}); m16_step(std::integral_constant<int, 1>{}); m16_step(std::integral_constant<int, 2>{});
+                m16_step(std::integral_constant<int, 3>{}); m16_step(std::integral_constant<int, 4>{}); m16_step(std::integral_constant<int, 5>{});
+                m16_step(std::integral_constant<int, 6>{}); m16_step(std::integral_constant<int, 7>{}); m16_step(std::integral_constant<int, 8>{});
+                m16_step(std::integral_constant<int, 9>{}); m16_step(std::integral_constant<int, 10>{}); m16_step(std::integral_constant<int, 11>{});
+                m16_step(std::integral_constant<int, 12>{}); m16_step(std::integral_constant<int, 13>{});
+                OAI_STAMP(5);
+            } else {                                                     // (discarded for M16: its accumulators have another type)
+            load_a(acur[0], 0, 0);
 #pragma unroll
             for (int t = 0; t < 27; ++t) {
-                const int dz = t / 9, dy = (t / 3) % 3, dx = t % 3;
-                if (t % 9 == 0) {                                        // a new dz phase
-                    if (t > 0 || ch > 0) {
-                        // every DMA requested in earlier phases is older than the 2*NREP weight loads in flight: it has landed
-                        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                        __syncthreads();                                 // ... for everybody; and the slots refilled below are read out
-                    }
-                    if (ch + 1 < nchunks) {
-                        if (dz == 0) { issue_plane(ch + 1, 0); issue_plane(ch + 1, 1); }
-                        else issue_plane(ch + 1, dz + 1);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int m = 0; m < MREP; ++m)
-                        acur[k][m] = *reinterpret_cast<const float4*>(lds + sb[m + dz] + (dy * HX + dx) * 64 + sl[dx][k]);
+                load_a(acur[1], t, 1);
 #pragma unroll
                 for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -570,242 +652,38 @@ __global__ void __launch_bounds__(256, (MREP == 2 && !RING) ? 3 : 2) conv3_igemm
                 wp += STEP;
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int p = 0; p < 3; ++p)
+                for (int p = 0; p < 2; ++p)                              // a0.b0, a0.b1
 #pragma unroll
-                    for (int m = 0; m < MREP; ++m) {
-                        if (m >= m_lo && m < m_hi) {
+                    for (int m = 0; m < ML; ++m)
 #pragma unroll
-                            for (int n = 0; n < NREP; ++n) acc[m][n] = mfma_16bit<true>(acur[PA[p]][m], bcur[PB[p]][n], acc[m][n]);
-                        }
-                    }
+                        for (int n = 0; n < NREP; ++n) acc[m][n] = mfma_16bit<true>(acur[0][m], bcur[p][n], acc[m][n]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (t + 1 < 27) load_a(acur[0], t + 1, 0);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int m = 0; m < ML; ++m)                             // a1.b0
+#pragma unroll
+                    for (int n = 0; n < NREP; ++n) acc[m][n] = mfma_16bit<true>(acur[1][m], bcur[0][n], acc[m][n]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int k = 0; k < 2; ++k)
 #pragma unroll
                     for (int n = 0; n < NREP; ++n) bcur[k][n] = bnext[k][n];
             }
-        }
-    } else {
-        // One chunk = 27 taps x 24 MFMAs.  Pass order per tap: a0.b0, a0.b1, a1.b0 -- so the registers of the a0 fragments are dead
-        // after the second pass and those of a1 before the third: the a1 fragments of tap t are read from LDS at the top of the tap
-        // (needed 16 MFMAs = 512 cycles later) and the a0 fragments of tap t+1 behind the second pass (needed 8 MFMAs later): the
-        // LDS latency never meets an MFMA that waits for it, at no extra register (a second set of A registers does not fit).
-        // Blocks whose four z slices are all inside the tile's box (the large majority) run a branch-free stream; the first
-        // version tested `m >= m_lo && m < m_hi` around every pair of MFMAs, which hipcc turned into twelve taken branches per tap
-        // with the MFMA pairs in out-of-line blocks behind `s_waitcnt lgkmcnt(0)`.
-        // ML = number of live z slices of the block (slices [0, ML) are inside the tile's box): a compile-time count, so that the
-        // tap stream is branch-free and the dead slices cost neither LDS reads nor MFMAs.  Blocks whose live slices do not start at
-        // 0 (rare: a border tile's box starting inside a block) run ML = MREP; their dead rows accumulate values that the
-        // epilogue never stores (rows of an MFMA are independent).
-        auto run_chunks = [&](auto ml_tag) __attribute__((always_inline)) {
-            constexpr int ML = decltype(ml_tag)::value;
-            auto load_a = [&](float4 (&dst)[MREP], int t, int k) __attribute__((always_inline)) {
-                const int dz = t / 9, dy = (t / 3) % 3, dx = t % 3;
-#pragma unroll
-                for (int m = 0; m < ML; ++m)
-                    dst[m] = *reinterpret_cast<const float4*>(abase + (((m + dz) * HY + dy) * HX + dx) * 64 + sl[dx][k]);
-            };
-            for (int ch = 0; ch < nchunks; ++ch) {
-                OAI_STAMP(0);
-                // every wave is done reading the previous chunk.  A bare barrier behind lgkmcnt(0): __syncthreads() would also wait (vmcnt(0)) for
-                // the weight fragments of the next tap, requested a moment ago
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                OAI_STAMP(1);
-                if constexpr (M16) {
-                    // the weight fragments of this chunk's step 0, requested in front of the halo staging: they land under the same wait.  They
-                    // are NOT requested during the previous chunk's last step: an inline-asm load is invisible to the compiler -- it believes
-                    // the result register holds the value from the asm statement on -- so a load in flight across the loop's back edge, the
-                    // dispatch over the live-slice variants or the loop exit can be COPIED (register re-assignment on an edge) or its register
-                    // re-used before the data has arrived.  Found with blocks of 1 and 3 live slices: their loop pre-headers copied the
-                    // prologue's in-flight fragments (v_mov of stale registers), intermittently wrong results at small tile levels.  Every asm
-                    // load of this kernel is now requested AND waited for inside one basic block.
-                    if constexpr (!FIRST) { m16_req_y(); m16_req_lo(); m16_req_hi(); }
-                }
-                if constexpr (FIRST) stage_first(ch);
-                else stage(ch);
-                if constexpr (M16 && FIRST) { m16_req_y(); m16_req_lo(); m16_req_hi(); }      // (behind ec0's arithmetic, which has branches: same basic block as the wait below)
-                OAI_STAMP(2);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this thread's DMA pieces have landed ...
-                OAI_STAMP(3);
-                __syncthreads();                                             // ... and everybody else's
-                OAI_STAMP(4);
-                if constexpr (M16) {
-                    // ---- 14 steps of tap pairs on v_mfma_f32_16x16x32_f16 (see the kernel's header comment).  Vector-memory order per step:
-                    // Y'(j+1) behind pass B | X' lo(j+1) behind pass C lo | X' hi(j+1) behind pass C hi; the counted waits leave exactly the
-                    // younger requests in flight.  (The fragments of this chunk's step 0 were requested at the chunk's top, above, and have
-                    // landed behind the staging wait: vmcnt(0) is global.  Invariant: every asm load is requested AND waited for inside one basic block.)
-                    constexpr int SLB = HY * HX * 64;                           // bytes between the z slices of the halo box
-                    constexpr int POFF = (RX >= 32 ? 16 : (16 / RX) * HX) * 64;  // ... between rows 0-15 and rows 16-31 of the wave's tile
-                    auto tapc = [](int q) constexpr { return ((q / 3) * HY + q % 3) * HX * 64; };      // tap (dz, dy) = q, dx 0
-                    // this lane's record slot per step: lane group g = lane >> 4 reads channel half g & 1 of the pair's tap g >> 1
-                    int lq = lane;
-                    asm volatile("" : "+v"(lq));                                 // (recomputed every chunk: not held -- or spilled -- across the staging)
-                    const int r16 = lq & 15, hsel = (lq >> 4) & 1, tsel = lq >> 5;
-                    const int lx0 = wx * RX + r16 % RX, ly0 = wy * RY + r16 / RX;
-                    const unsigned vbase = (unsigned)((ly0 * HX + lx0) * 64);
-                    unsigned oA[2], oB[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        oA[k] = vbase + (unsigned)(tsel * 64 + (((k * 2 + hsel) ^ (((lx0 + tsel) >> 2) & 3)) << 4));       // steps 0..8: dx = tsel
-                        oB[k] = vbase + (unsigned)(128 + (((k * 2 + hsel) ^ (((lx0 + 2) >> 2) & 3)) << 4));                // steps 9..12: dx = 2
-                    }
-                    const unsigned oC = vbase + (unsigned)(128 + (((tsel * 2 + hsel) ^ (((lx0 + 2) >> 2) & 3)) << 4));     // step 13: term = tsel
-                    const unsigned tHX = (unsigned)(tsel * HX * 64);             // the second tap of a dx = 2 pair: one row (steps 9..11) / one slice (step 12) further
-                    auto a_off = [&](int j, int k) __attribute__((always_inline)) -> unsigned {
-                        if (j < 9) return oA[k] + (unsigned)tapc(j);
-                        if (j < 12) return oB[k] + tHX + (unsigned)tapc(3 * (j - 9));
-                        if (j == 12) return oB[k] + tHX * (unsigned)HY + (unsigned)tapc(2);
-                        return oC + (unsigned)tapc(8);
-                    };
-                    auto lda = [&](unsigned off, int m, int p) __attribute__((always_inline)) {
-                        return *reinterpret_cast<const float4*>(lds + off + m * SLB + p * POFF);
-                    };
-                    auto mma = [&](const float4& av, const f32x4m& bv, f32x4m& c) __attribute__((always_inline)) {
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8m, av), __builtin_bit_cast(f16x8m, bv), c, 0, 0, 0);
-                    };
-                    // the staging wait was vmcnt(0): the fragments of step 0 are in their registers (tie them behind it)
-                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(bY[0]), "+v"(bY[1]), "+v"(bY[2]), "+v"(bY[3]) :: "memory");
-                    asm volatile("" : "+v"(bXlo[0]), "+v"(bXlo[1]), "+v"(bXhi[0]), "+v"(bXhi[1]) :: "memory");
-                    float4 af[MREP][2];                                          // [m][p]: the A fragments of the running pass
-#pragma unroll
-                    for (int m = 0; m < ML; ++m)
-#pragma unroll
-                        for (int p = 0; p < 2; ++p) af[m][p] = lda(a_off(0, 0), m, p);
-                    // one step, J a compile-time constant: the 14 steps are 14 explicit calls (a `#pragma unroll` loop is a request -- hipcc left the
-                    // ML = 4 body rolled, with run-time tests of j, i.e. branches while fragment loads are in flight: tests/test_abi_cpu.py (g))
-                    auto m16_step = [&](auto jtag) __attribute__((always_inline)) {
-                        constexpr int j = decltype(jtag)::value;
-                        if (j > 0) asm volatile("s_waitcnt vmcnt(4)" : "+v"(bY[0]), "+v"(bY[1]), "+v"(bY[2]), "+v"(bY[3]) :: "memory");      // Y'(j) has landed; younger: lo(j), hi(j)
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int m = 0; m < ML; ++m)                              // pass B: a0 . Y'   (step 13: [a0 | a1] . [b1 | 0])
-#pragma unroll
-                            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                for (int n = 0; n < 4; ++n) mma(af[m][p], bY[n], acc4[m][n >> 1][p * 2 + (n & 1)]);
-                        __builtin_amdgcn_sched_barrier(0);
-                        wp16 += STEP16;
-                        if (j < 13) m16_req_y();                                  // Y' of the next step (step 13 requests nothing: see the chunk's top)
-                        if (j > 0 && j < 13) asm volatile("s_waitcnt vmcnt(6)" : "+v"(bXlo[0]), "+v"(bXlo[1]) :: "memory");      // lo(j); younger: hi(j), Y'(j + 1)
-                        if (j == 13) asm volatile("s_waitcnt vmcnt(2)" : "+v"(bXlo[0]), "+v"(bXlo[1]) :: "memory");              // (step 13: only hi(13) is younger)
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int m = 0; m < ML; ++m)                              // pass A, low couts: a0 . X'[0, 1] over all slices
-#pragma unroll
-                            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                for (int n = 0; n < 2; ++n) mma(af[m][p], bXlo[n], acc4[m][0][p * 2 + n]);
-                        __builtin_amdgcn_sched_barrier(0);                        // (the wait below must not rise above these MFMAs: they are its lead)
-                        if (j > 0 && j < 13) asm volatile("s_waitcnt vmcnt(4)" : "+v"(bXhi[0]), "+v"(bXhi[1]) :: "memory");      // hi(j); younger: Y'(j + 1)
-                        if (j == 13) asm volatile("s_waitcnt vmcnt(0)" : "+v"(bXhi[0]), "+v"(bXhi[1]) :: "memory");              // (step 13: nothing is younger)
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int m = 0; m < ML; ++m) {                            // pass A, high couts; behind each slice the a1 fragments of pass C take its registers
-#pragma unroll
-                            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                for (int n = 0; n < 2; ++n) mma(af[m][p], bXhi[n], acc4[m][1][p * 2 + n]);
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (j < 13) {
-#pragma unroll
-                                for (int p = 0; p < 2; ++p) af[m][p] = lda(a_off(j, 1), m, p);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        if (j < 13) {
-#pragma unroll
-                            for (int m = 0; m < ML; ++m)                          // pass C, low couts: a1 . X'[0, 1]
-#pragma unroll
-                                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                    for (int n = 0; n < 2; ++n) mma(af[m][p], bXlo[n], acc4[m][0][p * 2 + n]);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        if (j < 13) m16_req_lo();                                 // the low couts of the next step's X'
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (j < 13) {
-#pragma unroll
-                            for (int m = 0; m < ML; ++m) {                        // pass C, high couts; behind each slice the a0 fragments of the next step
-#pragma unroll
-                                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                    for (int n = 0; n < 2; ++n) mma(af[m][p], bXhi[n], acc4[m][1][p * 2 + n]);
-                                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                                for (int p = 0; p < 2; ++p) af[m][p] = lda(a_off(j + 1, 0), m, p);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
-                        if (j < 13) m16_req_hi();                                 // the high couts of the next step's X'
-                        __builtin_amdgcn_sched_barrier(0);
-                    };
-                    m16_step(std::integral_constant<int, 0>{}); m16_step(std::integral_constant<int, 1>{}); m16_step(std::integral_constant<int, 2>{});
-                    m16_step(std::integral_constant<int, 3>{}); m16_step(std::integral_constant<int, 4>{}); m16_step(std::integral_constant<int, 5>{});
-                    m16_step(std::integral_constant<int, 6>{}); m16_step(std::integral_constant<int, 7>{}); m16_step(std::integral_constant<int, 8>{});
-                    m16_step(std::integral_constant<int, 9>{}); m16_step(std::integral_constant<int, 10>{}); m16_step(std::integral_constant<int, 11>{});
-                    m16_step(std::integral_constant<int, 12>{}); m16_step(std::integral_constant<int, 13>{});
-                    OAI_STAMP(5);
-                } else {                                                     // (discarded for M16: its accumulators have another type)
-                if constexpr (BLDS) { if (ch == 0) read_b(bcur, 0); }           // slab 0 (landed with the halo, behind the barrier above)
-                load_a(acur[0], 0, 0);
-#pragma unroll
-                for (int t = 0; t < 27; ++t) {
-                    if constexpr (BLDS) {
-                        // in flight: the slabs of taps t+1 (requested two taps ago) and t+2: the older one has landed -- for everybody behind
-                        // the barrier, which also says that everybody has read slab t (slot t % 3) into registers: it is refilled with t+3
-                        if (t > 0 || ch == 0) {          // (tap 0 stands right behind the chunk's own barrier -- except in chunk 0, where slab 0 has just been read from the slot refilled below)
-                            asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-                            __builtin_amdgcn_s_barrier();
-                            asm volatile("" ::: "memory");
-                        }
-                        issue_b(t % 3);
-                        read_b(bnext, (t + 1) % 3);
-                    }
-                    load_a(acur[1], t, 1);
-                    if constexpr (!BLDS) {
-#pragma unroll
-                        for (int k = 0; k < 2; ++k)
-#pragma unroll
-                            for (int n = 0; n < NREP; ++n) bnext[k][n] = wp[(k * NREP + n) * 64];
-                        wp += STEP;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)                              // a0.b0, a0.b1
-#pragma unroll
-                        for (int m = 0; m < ML; ++m)
-#pragma unroll
-                            for (int n = 0; n < NREP; ++n) acc[m][n] = mfma_16bit<true>(acur[0][m], bcur[p][n], acc[m][n]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (t + 1 < 27) load_a(acur[0], t + 1, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int m = 0; m < ML; ++m)                             // a1.b0
-#pragma unroll
-                        for (int n = 0; n < NREP; ++n) acc[m][n] = mfma_16bit<true>(acur[1][m], bcur[0][n], acc[m][n]);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < 2; ++k)
-#pragma unroll
-                        for (int n = 0; n < NREP; ++n) bcur[k][n] = bnext[k][n];
-                }
-                OAI_STAMP(5);
-                }
+            OAI_STAMP(5);
             }
-        };
-        const int ml = m_lo == 0 ? m_hi : MREP;                         // workgroup-uniform
-        if constexpr (FIRST) run_chunks(std::integral_constant<int, MREP>{});       // (one copy of the inlined ec0 code; dead slices are never stored)
-        else if constexpr (MREP == 4) {
-            if (ml == 4) run_chunks(std::integral_constant<int, 4>{});
-            else if (ml == 3) run_chunks(std::integral_constant<int, 3>{});
-            else if (ml == 2) run_chunks(std::integral_constant<int, 2>{});
-            else run_chunks(std::integral_constant<int, 1>{});
-        } else {
-            if (ml == 2) run_chunks(std::integral_constant<int, 2>{});
-            else run_chunks(std::integral_constant<int, 1>{});
         }
+    };
+    const int ml = m_lo == 0 ? m_hi : MREP;                         // workgroup-uniform
+    if constexpr (FIRST) run_chunks(std::integral_constant<int, MREP>{});       // (one copy of the inlined ec0 code; dead slices are never stored)
+    else if constexpr (MREP == 4) {
+        if (ml == 4) run_chunks(std::integral_constant<int, 4>{});
+        else if (ml == 3) run_chunks(std::integral_constant<int, 3>{});
+        else if (ml == 2) run_chunks(std::integral_constant<int, 2>{});
+        else run_chunks(std::integral_constant<int, 1>{});
+    } else {
+        if (ml == 2) run_chunks(std::integral_constant<int, 2>{});
+        else run_chunks(std::integral_constant<int, 1>{});
     }
 
     // (M16: nothing is in flight here -- step 13 requests nothing and waits for everything it uses)

@@ -132,8 +132,8 @@ def test_no_packed_fp32_valu_and_hot_kernels_are_mfma(tmp_path):
     # (c) the copy-out of the default conv kernel (and of its ec0-fused instantiation) is a run of stores with nothing in between that waits
     # for memory: `vmcnt` counts stores on this ISA, so a reload from scratch or a late load between them makes every store wait for all
     # earlier ones to reach memory (profiles/r02_conv_per_layer.md section 5).  Chunk loop: no scratch traffic at all.
-    for sym in ("_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb0ELb0ELb0ELb0EEEvNS_8ConvArgsEPKh",
-                "_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb0ELb1ELb0ELb0EEEvNS_8ConvArgsEPKh"):
+    for sym in ("_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb0ELb0EEEvNS_8ConvArgsEPKh",
+                "_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb1ELb0EEEvNS_8ConvArgsEPKh"):
         m = re.search(r"^[0-9a-f]+ <" + sym + r">:\n(.*?)(?=^[0-9a-f]+ <)", text, flags=re.S | re.M)
         assert m, f"{sym} not in the library"
         body = m.group(1).split("\n")
@@ -167,9 +167,8 @@ def test_no_packed_fp32_valu_and_hot_kernels_are_mfma(tmp_path):
         loads = [ln for ln in seg if "global_load_dwordx4" in ln or "global_load_lds_dwordx4" in ln]
         assert all("s[" in ln.split("//")[0] or "lds" in ln for ln in loads), "a weight-fragment load that is not the SGPR-base asm form"
     # (e) conv3_wino_sres (unet_wino.h) counts vmcnt by hand as well: 9 taps x 24 MFMAs per chunk for ML = 4; no scratch anywhere in the kernel
-    for sym, n_mf in (("_ZN3oai15conv3_wino_sresILi2ELi8ELi4ELi1ELb0ELb0ELb0EEEvNS_8ConvArgsEPKh", 540), ("_ZN3oai15conv3_wino_sresILi1ELi8ELi4ELi2ELb0ELb0ELb0EEEvNS_8ConvArgsEPKh", 162),
-                      ("_ZN3oai15conv3_wino_sresILi1ELi8ELi4ELi1ELb1ELb0ELb0EEEvNS_8ConvArgsEPKh", 540),
-                      ("_ZN3oai15conv3_wino_sresILi1ELi8ELi4ELi1ELb1ELb0ELb1EEEvNS_8ConvArgsEPKh", 540)):       # (the specialised form: four multiplying waves, ML = 4 .. 1; its persistent variant, option "persistent": the same tap streams)
+    for sym, n_mf in (("_ZN3oai15conv3_wino_sresILi2ELi8ELi4ELi1ELb0ELb0EEEvNS_8ConvArgsEPKh", 540), ("_ZN3oai15conv3_wino_sresILi1ELi8ELi4ELi2ELb0ELb0EEEvNS_8ConvArgsEPKh", 162),
+                      ("_ZN3oai15conv3_wino_sresILi1ELi8ELi4ELi1ELb1ELb0EEEvNS_8ConvArgsEPKh", 540)):       # (the specialised form: four multiplying waves, ML = 4 .. 1)
         m = re.search(r"^[0-9a-f]+ <" + sym + r">:\n(.*?)(?=^[0-9a-f]+ <)", text, flags=re.S | re.M)
         assert m, f"{sym} not in the library"
         body = m.group(1).split("\n")
@@ -181,7 +180,7 @@ def test_no_packed_fp32_valu_and_hot_kernels_are_mfma(tmp_path):
     # (f) the default two-group form (round 4): the same kernel with its taps on v_mfma_f32_16x16x32_f16, K = a pair of taps -- 14 steps x 32
     # MFMAs per chunk for ML = 4 (448 + 336 + 224 + 112); its counted waits need a tap stream free of compiler-made vector-memory operations
     # (a scratch reload drains vmcnt: every prefetched fragment with it), and its halo pieces come from an SGPR base + 32-bit offset
-    for sym in ("_ZN3oai15conv3_wino_sresILi2ELi8ELi4ELi1ELb0ELb1ELb0EEEvNS_8ConvArgsEPKh", "_ZN3oai15conv3_wino_sresILi1ELi8ELi4ELi1ELb1ELb1ELb0EEEvNS_8ConvArgsEPKh"):
+    for sym in ("_ZN3oai15conv3_wino_sresILi2ELi8ELi4ELi1ELb0ELb1EEEvNS_8ConvArgsEPKh", "_ZN3oai15conv3_wino_sresILi1ELi8ELi4ELi1ELb1ELb1EEEvNS_8ConvArgsEPKh"):
         m = re.search(r"^[0-9a-f]+ <" + sym + r">:\n(.*?)(?=^[0-9a-f]+ <)", text, flags=re.S | re.M)
         assert m, f"{sym} not in the library"
         body = m.group(1).split("\n")
@@ -195,15 +194,15 @@ def test_no_packed_fp32_valu_and_hot_kernels_are_mfma(tmp_path):
         loads = [ln for ln in body if "global_load_dwordx4" in ln and "lds" not in ln]
         assert len(loads) >= 40 and all("s[" in ln.split("//")[0] for ln in loads), "a fragment load that is not the SGPR-base asm form"
     # (the two-group form's halo pieces also come from an SGPR base + 32-bit offset; the specialised form's stagers keep the per-lane 64-bit form)
-    assert all("s[" in ln.split("//")[0] for ln in re.search(r"^[0-9a-f]+ <_ZN3oai15conv3_wino_sresILi2ELi8ELi4ELi1ELb0ELb1ELb0EEEvNS_8ConvArgsEPKh>:\n(.*?)(?=^[0-9a-f]+ <)", text, flags=re.S | re.M).group(1).split("\n") if "global_load_lds_dwordx4" in ln)
+    assert all("s[" in ln.split("//")[0] for ln in re.search(r"^[0-9a-f]+ <_ZN3oai15conv3_wino_sresILi2ELi8ELi4ELi1ELb0ELb1EEEvNS_8ConvArgsEPKh>:\n(.*?)(?=^[0-9a-f]+ <)", text, flags=re.S | re.M).group(1).split("\n") if "global_load_lds_dwordx4" in ln)
     # (g) round 5: the direct kernel on 16x16x32 tap pairs (conv3_igemm_sres<..., M16>, default for the layers with Cout % 128 != 0): 14 steps of
     # 96 / 64 MFMAs per chunk for ML = 4 (1312 + 984 + 656 + 328), no 32x32x16, no scratch in a tap stream, every fragment load the SGPR-base asm
     # form -- and NO BRANCH WHILE A FRAGMENT LOAD IS IN FLIGHT: an inline-asm load is invisible to the compiler (it believes the result register
     # holds the value from the asm statement on), so a load in flight across a control-flow edge can be copied (`v_mov` of a stale register) or its
     # register re-used.  A first version requested the next chunk's fragments during the last step and the first chunk's in the prologue: the
     # pre-headers of the ML = 1 / 3 loop variants copied the in-flight registers -- intermittently wrong results at small tile levels.
-    for sym, first in (("_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb0ELb0ELb0ELb1EEEvNS_8ConvArgsEPKh", False),
-                       ("_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb0ELb1ELb0ELb1EEEvNS_8ConvArgsEPKh", True)):
+    for sym, first in (("_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb0ELb1EEEvNS_8ConvArgsEPKh", False),
+                       ("_ZN3oai16conv3_igemm_sresILi4ELi16ELi2ELi4ELi1ELb1ELb1EEEvNS_8ConvArgsEPKh", True)):
         m = re.search(r"^[0-9a-f]+ <" + sym + r">:\n(.*?)(?=^[0-9a-f]+ <)", text, flags=re.S | re.M)
         assert m, f"{sym} not in the library"
         body = [ln.split("//")[0] for ln in m.group(1).split("\n")]
