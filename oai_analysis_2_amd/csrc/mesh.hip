@@ -300,7 +300,13 @@ __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b
 __device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
-// squared distance from p to triangle (a, a + ab, a + ac): Ericson, Real-Time Collision Detection 5.1.5
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+
+// squared distance from p to triangle (a, a + ab, a + ac): the Voronoi-region ladder of Ericson, Real-Time Collision Detection 5.1.5,
+// for the vertices and edges.  Over the interior it is the distance to the plane, (ap . n)^2 / |n|^2 with n = ab x ac, not
+// Ericson's |p - (a + v ab + w ac)|^2: his v and w divide by va + vb + vc -- |n|^2 again, but as a sum of cancelling products of size
+// |ap|^2 |ab| |ac| -- so their float32 error grows like 2^-24 |ap|^2 / sin^2 of the triangle's angle and moved the foot point along a
+// 1:100 needle by 1e-4 of its length; n loses 2^-24 / sin, once.  Only for well-shaped triangles: see kThin.
 __device__ __forceinline__ float tri_dist2(V3 p, V3 a, V3 ab, V3 ac) {
     const V3 ap = p - a;
     const float d1 = dot(ab, ap), d2 = dot(ac, ap);
@@ -326,8 +332,9 @@ __device__ __forceinline__ float tri_dist2(V3 p, V3 a, V3 ab, V3 ac) {
                             const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
                             q = a + ab + (ac - ab) * w;
                         } else {
-                            const float denom = 1.0f / (va + vb + vc);
-                            q = a + ab * (vb * denom) + ac * (vc * denom);
+                            const V3 n = cross(ab, ac);
+                            const float s = dot(ap, n);
+                            return s * s * __builtin_amdgcn_rcpf(dot(n, n));        // v_rcp_f32: 1 ulp on a squared distance
                         }
                     }
                 }
@@ -338,11 +345,54 @@ __device__ __forceinline__ float tri_dist2(V3 p, V3 a, V3 ab, V3 ac) {
     return dot(d, d);
 }
 
+// The ladder is float32 and assumes a triangle.  With a == b its edge parameter is 0/0 (fminf drops the NaN, and the triangle with it);
+// on a needle the signs of va, vb, vc that pick the region are noise.  A triangle with |ab x ac|^2 <= kThin |ab|^2 |ac|^2 -- the sine of
+// the angle at a at most 1e-2, zero area included -- takes tri_dist2_thin instead.  The test is made once per triangle, outside the hot
+// loops (by the lane that stages it for the brute-force kernel, by grid_bin_kernel for the grid), with every rounding spelled out so
+// that the two kernels class a borderline triangle alike.
+constexpr float kThin = 1e-4f;
+__device__ __forceinline__ float dot_rn(V3 a, V3 b) { return __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, __fmul_rn(a.x, b.x))); }
+__device__ __forceinline__ bool is_thin(V3 ab, V3 ac) {
+    const V3 n = {__fmaf_rn(ab.y, ac.z, -__fmul_rn(ab.z, ac.y)), __fmaf_rn(ab.z, ac.x, -__fmul_rn(ab.x, ac.z)), __fmaf_rn(ab.x, ac.y, -__fmul_rn(ab.y, ac.x))};
+    return dot_rn(n, n) <= __fmul_rn(kThin, __fmul_rn(dot_rn(ab, ab), dot_rn(ac, ac)));
+}
+
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+// squared distance from a point at `up` (relative to the segment's start) to the segment of direction e; no length: its start
+__device__ __forceinline__ double seg_dist2(D3 up, D3 e) {
+    const double ee = dot(e, e);
+    const double t = ee > 0.0 ? fmin(fmax(dot(up, e) / ee, 0.0), 1.0) : 0.0;
+    const D3 d = {up.x - t * e.x, up.y - t * e.y, up.z - t * e.z};
+    return dot(d, d);
+}
+
+// The same squared distance without the ladder, in double: the nearest of the three edges, and the plane distance where the triangle
+// has a normal and the point projects inside it (three same-side tests against n = ab x ac).  No division can be 0/0, so no triangle
+// yields NaN; a triangle without area is exactly its edges.  Rare, hence out of line.
+__device__ __noinline__ float tri_dist2_thin(V3 p, V3 a, V3 ab, V3 ac) {
+    const D3 AB = {ab.x, ab.y, ab.z}, AC = {ac.x, ac.y, ac.z};
+    const D3 ap = D3{p.x, p.y, p.z} - D3{a.x, a.y, a.z}, bp = ap - AB, cp = ap - AC, BC = AC - AB;
+    double best = fmin(fmin(seg_dist2(ap, AB), seg_dist2(ap, AC)), seg_dist2(bp, BC));
+    const D3 n = cross(AB, AC);
+    const double nn = dot(n, n);
+    if (nn > 0.0 && dot(cross(AB, ap), n) >= 0.0 && dot(cross(BC, bp), n) >= 0.0 && dot(cross(cp, AC), n) >= 0.0) {   // ca x cp = cp x ac
+        const double s = dot(ap, n);
+        best = fmin(best, s * s / nn);
+    }
+    return (float)best;
+}
+
 constexpr int kTriTile = 512;
 
 __global__ void __launch_bounds__(256) point_distance_kernel(const float* __restrict__ pts, long long np, const float* __restrict__ verts,
                                                              const int* __restrict__ faces, long long nt, float* __restrict__ dist) {
     __shared__ float tri[kTriTile][9];          // a, ab, ac
+    __shared__ float thin_edges[kTriTile][6];   // ab, ac of the tile's thin triangles, in the order they were claimed
+    __shared__ int thin_list[kTriTile];         // their positions in the tile
+    __shared__ int n_thin;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool live = i < np;
     const V3 p = live ? V3{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]} : V3{0.f, 0.f, 0.f};
@@ -350,19 +400,37 @@ __global__ void __launch_bounds__(256) point_distance_kernel(const float* __rest
     for (long long t0 = 0; t0 < nt; t0 += kTriTile) {
         const int cnt = (int)(nt - t0 < kTriTile ? nt - t0 : kTriTile);
         __syncthreads();
+        if (threadIdx.x == 0) n_thin = 0;
+        __syncthreads();
         for (int k = threadIdx.x; k < cnt; k += 256) {
             const int* f = faces + 3 * (t0 + k);
             const float* a = verts + 3 * (long long)f[0];
             const float* b = verts + 3 * (long long)f[1];
             const float* c = verts + 3 * (long long)f[2];
+            V3 ab = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+            if (is_thin(ab, ac)) {
+                // out of the hot loop, which then sees the one-point triangle (a, a, a): its distance, |p - a|, is no less than the
+                // real triangle's, so the minimum is unharmed, and the loop needs no branch
+                const int slot = atomicAdd(&n_thin, 1);
+                thin_list[slot] = k;
+                thin_edges[slot][0] = ab.x; thin_edges[slot][1] = ab.y; thin_edges[slot][2] = ab.z;
+                thin_edges[slot][3] = ac.x; thin_edges[slot][4] = ac.y; thin_edges[slot][5] = ac.z;
+                ab = ac = V3{0.f, 0.f, 0.f};
+            }
             tri[k][0] = a[0]; tri[k][1] = a[1]; tri[k][2] = a[2];
-            tri[k][3] = b[0] - a[0]; tri[k][4] = b[1] - a[1]; tri[k][5] = b[2] - a[2];
-            tri[k][6] = c[0] - a[0]; tri[k][7] = c[1] - a[1]; tri[k][8] = c[2] - a[2];
+            tri[k][3] = ab.x; tri[k][4] = ab.y; tri[k][5] = ab.z;
+            tri[k][6] = ac.x; tri[k][7] = ac.y; tri[k][8] = ac.z;
         }
         __syncthreads();
-        if (live)
+        if (live) {
             for (int k = 0; k < cnt; ++k)          // LDS broadcast reads: every lane wants the same triangle
                 best = fminf(best, tri_dist2(p, V3{tri[k][0], tri[k][1], tri[k][2]}, V3{tri[k][3], tri[k][4], tri[k][5]}, V3{tri[k][6], tri[k][7], tri[k][8]}));
+            for (int j = 0; j < n_thin; ++j) {     // (min is exact, so the order the slots were claimed in does not show)
+                const int k = thin_list[j];
+                best = fminf(best, tri_dist2_thin(p, V3{tri[k][0], tri[k][1], tri[k][2]}, V3{thin_edges[j][0], thin_edges[j][1], thin_edges[j][2]},
+                                                  V3{thin_edges[j][3], thin_edges[j][4], thin_edges[j][5]}));
+            }
+        }
     }
     if (live) dist[i] = sqrtf(best);
 }
@@ -371,8 +439,12 @@ __global__ void __launch_bounds__(256) point_distance_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------
 // the same distance with a uniform-grid broad phase: triangles are binned into the cells their bounding boxes overlap
 // (count -> prefix sum -> fill), a point walks the cells around it ring by ring and stops when the best distance found is
-// within the radius already covered.  Exact (same closest-point routine, every triangle that could be closer is visited).
+// within the radius already covered, less a slack for the float32 cell arithmetic (kRingSlack).  Same closest-point routine as the
+// brute-force kernel, and every triangle that could be the nearest is visited: the two agree up to the rounding of their own
+// (separately inlined) arithmetic, provided every triangle lies inside the grid box the caller describes.
 // ---------------------------------------------------------------------------------------------------------------------
+constexpr float kRingSlack = 1.0f / 1024.0f;       // cells
+
 struct GridDesc {
     float lo[3];
     float inv_h, h;
@@ -390,19 +462,25 @@ __global__ void __launch_bounds__(256) grid_bin_kernel(const float* __restrict__
                                                        int* __restrict__ tri_list) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= nt) return;
+    const float* va = verts + 3 * (long long)faces[3 * t];
+    const float* vb = verts + 3 * (long long)faces[3 * t + 1];
+    const float* vc = verts + 3 * (long long)faces[3 * t + 2];
     int lo[3], hi[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float a = verts[3 * (long long)faces[3 * t] + k], b = verts[3 * (long long)faces[3 * t + 1] + k], c = verts[3 * (long long)faces[3 * t + 2] + k];
+        const float a = va[k], b = vb[k], c = vc[k];
         lo[k] = cell_coord(fminf(a, fminf(b, c)), g.lo[k], g.inv_h, g.n[k]);
         hi[k] = cell_coord(fmaxf(a, fmaxf(b, c)), g.lo[k], g.inv_h, g.n[k]);
     }
+    // a thin triangle (is_thin) is listed as ~t, which is negative: the walk sets it aside for tri_dist2_thin without looking at it
+    int entry = (int)t;
+    if (FILL && is_thin(V3{vb[0] - va[0], vb[1] - va[1], vb[2] - va[2]}, V3{vc[0] - va[0], vc[1] - va[1], vc[2] - va[2]})) entry = ~entry;
     for (int z = lo[2]; z <= hi[2]; ++z)
         for (int y = lo[1]; y <= hi[1]; ++y)
             for (int x = lo[0]; x <= hi[0]; ++x) {
                 const int cell = (z * g.n[1] + y) * g.n[0] + x;
                 const int slot = atomicAdd(&cell_count[cell], 1);
-                if (FILL) tri_list[cell_start[cell] + slot] = (int)t;
+                if (FILL) tri_list[cell_start[cell] + slot] = entry;
             }
 }
 
@@ -415,17 +493,38 @@ __global__ void __launch_bounds__(256) grid_distance_kernel(const float* __restr
     const int cx = cell_coord(p.x, g.lo[0], g.inv_h, g.n[0]), cy = cell_coord(p.y, g.lo[1], g.inv_h, g.n[1]), cz = cell_coord(p.z, g.lo[2], g.inv_h, g.n[2]);
     const int rmax = max(max(max(cx, g.n[0] - 1 - cx), max(cy, g.n[1] - 1 - cy)), max(cz, g.n[2] - 1 - cz));
     float best = 3.4e38f;
+    // Lanes of a wave visit different triangles, so a thin one (a negative list entry) handled where it is met would make the whole
+    // wave step through the double path each time any lane meets one.  It waits in `pending` instead -- until the lane meets the next,
+    // or the ring ends -- which leaves the wave a few such steps per point rather than one per visited cell.  `best` is complete again
+    // before each stop test.
+    int pending = -1;
+    auto flush = [&]() {
+        if (pending < 0) return;
+        const int* f = faces + 3 * (long long)pending;
+        const float* a = verts + 3 * (long long)f[0];
+        const float* b = verts + 3 * (long long)f[1];
+        const float* c = verts + 3 * (long long)f[2];
+        const V3 A = {a[0], a[1], a[2]};
+        best = fminf(best, tri_dist2_thin(p, A, V3{b[0], b[1], b[2]} - A, V3{c[0], c[1], c[2]} - A));
+        pending = -1;
+    };
     for (int r = 0; r <= rmax; ++r) {
-        // triangles not visited after ring r-1 lie in cells at Chebyshev distance >= r: at least (r-1) * h away from the point's
-        // projection onto the grid box, hence from the point
-        const float covered = (float)(r - 1) * g.h;
+        flush();
+        // triangles not visited after ring r-1 lie in cells at Chebyshev distance >= r from the point's cell, AS cell_coord COMPUTES
+        // both: in float32, which can put a coordinate next to a cell boundary into the neighbouring cell.  The slip is below
+        // 3 * 2^-23 * 512 = 1.8e-4 cells per coordinate (the subtraction, 1 / h and the product each round once, on at most 512 cells),
+        // so such a triangle is at least (r - 1 - 2 * 1.8e-4) * h from the point's projection onto the grid box, hence from the point;
+        // kRingSlack = 2^-10 cells covers both slips with room to spare
+        const float covered = fmaxf((float)(r - 1) - kRingSlack, 0.0f) * g.h;
         if (r > 0 && best <= covered * covered) break;
         const int z0 = max(cz - r, 0), z1 = min(cz + r, g.n[2] - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.n[1] - 1);
         const int x0 = max(cx - r, 0), x1 = min(cx + r, g.n[0] - 1);
         auto visit = [&](int x, int y, int z) {
             const int cell = (z * g.n[1] + y) * g.n[0] + x;
             for (int k = cell_start[cell]; k < cell_start[cell + 1]; ++k) {
-                const int* f = faces + 3 * (long long)tri_list[k];
+                const int t = tri_list[k];
+                if (t < 0) { flush(); pending = ~t; continue; }
+                const int* f = faces + 3 * (long long)t;
                 const float* a = verts + 3 * (long long)f[0];
                 const float* b = verts + 3 * (long long)f[1];
                 const float* c = verts + 3 * (long long)f[2];
@@ -443,6 +542,7 @@ __global__ void __launch_bounds__(256) grid_distance_kernel(const float* __restr
                 }
             }
     }
+    flush();
     dist[i] = sqrtf(best);
 }
 
@@ -548,8 +648,8 @@ int oai_mesh_smooth(const float* verts_in_dev, long long n_verts, const int* off
 
 int oai_mesh_point_distance(const float* points_dev, long long n_points, const float* verts_dev, const int* faces_dev,
                             long long n_tris, float* dist_dev, void* stream) {
-    OAI_CHECK_ARG(points_dev && verts_dev && faces_dev && dist_dev, "oai_mesh_point_distance: null pointer");
     OAI_CHECK_ARG(n_points >= 0 && n_tris > 0, "oai_mesh_point_distance: needs at least one triangle");
+    OAI_CHECK_ARG(verts_dev && faces_dev && ((points_dev && dist_dev) || n_points == 0), "oai_mesh_point_distance: null pointer");
     if (n_points == 0) return OAI_OK;
     point_distance_kernel<<<oai::cdiv(n_points, 256), 256, 0, (hipStream_t)stream>>>(points_dev, n_points, verts_dev, faces_dev, n_tris, dist_dev);
     OAI_CHECK_LAUNCH();
@@ -565,8 +665,9 @@ size_t oai_mesh_grid_workspace_bytes(const int grid_dims_xyz[3], long long n_tri
 int oai_mesh_point_distance_grid(const float* points_dev, long long n_points, const float* verts_dev, const int* faces_dev, long long n_tris,
                                  const float grid_lo_xyz[3], float cell_size, const int grid_dims_xyz[3],
                                  void* workspace_dev, size_t workspace_bytes, float* dist_dev, void* stream) {
-    OAI_CHECK_ARG(points_dev && verts_dev && faces_dev && dist_dev && grid_lo_xyz && grid_dims_xyz && workspace_dev, "oai_mesh_point_distance_grid: null pointer");
     OAI_CHECK_ARG(n_points >= 0 && n_tris > 0 && cell_size > 0.0f, "oai_mesh_point_distance_grid: needs triangles and a positive cell size");
+    OAI_CHECK_ARG(verts_dev && faces_dev && grid_lo_xyz && grid_dims_xyz && workspace_dev && ((points_dev && dist_dev) || n_points == 0),
+                  "oai_mesh_point_distance_grid: null pointer");
     OAI_CHECK_ARG(grid_dims_xyz[0] > 0 && grid_dims_xyz[1] > 0 && grid_dims_xyz[2] > 0, "oai_mesh_point_distance_grid: empty grid");
     const long long ncells = (long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2];
     OAI_CHECK_ARG(ncells < (1LL << 30), "oai_mesh_point_distance_grid: grid too fine");
@@ -584,7 +685,8 @@ int oai_mesh_point_distance_grid(const float* points_dev, long long n_points, co
     int total = 0;
     if (int rc = oai::read_ints(&total, {w.start + ncells}, st)) return rc;
     if ((long long)total > n_tris * 8)          // a triangle longer than a cell overlaps more than 8 cells: the caller's cell size is too small
-        return oai::set_error(OAI_ERR_ARG, "oai_mesh_point_distance_grid: %d triangle-cell pairs > 8 per triangle; cell_size must be >= the longest edge", total);
+        return oai::set_error(OAI_ERR_ARG, "oai_mesh_point_distance_grid: %d triangle-cell pairs > 8 per triangle; cell_size %g must be >= the longest edge",
+                              total, (double)cell_size);
     OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
     grid_bin_kernel<true><<<oai::cdiv(n_tris, 256), 256, 0, st>>>(verts_dev, faces_dev, n_tris, g, w.count, w.start, w.list);
     OAI_CHECK_LAUNCH();

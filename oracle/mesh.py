@@ -238,7 +238,24 @@ def point_triangle_distance(p: np.ndarray, a: np.ndarray, b: np.ndarray, c: np.n
         closest = np.where(((d6 >= 0) & (d5 <= d6))[..., None], np.broadcast_to(c, closest.shape), closest)   # vertex c
         closest = np.where(((d3 >= 0) & (d4 <= d3))[..., None], np.broadcast_to(b, closest.shape), closest)   # vertex b
         closest = np.where(((d1 <= 0) & (d2 <= 0))[..., None], np.broadcast_to(a, closest.shape), closest)    # vertex a
-    return np.sqrt(((p - closest) ** 2).sum(-1))
+    dist = np.sqrt(((p - closest) ** 2).sum(-1))
+    # a triangle without area is the longest of its edges (or a point).  The ladder divides 0 by 0 there -- an edge parameter when two
+    # vertices coincide, the barycentric denominator when three are collinear -- and np.min would hand the NaN to the whole mesh.
+    # Those columns, and no other, take the distance to the three segments instead.
+    n = np.cross(ab, ac)
+    flat = np.flatnonzero(((n * n).sum(-1) == 0).reshape(-1))
+    if len(flat):
+        dist[:, flat] = np.minimum(np.minimum(_segment_distance(p, a[:, flat], b[:, flat]), _segment_distance(p, b[:, flat], c[:, flat])),
+                                   _segment_distance(p, c[:, flat], a[:, flat]))
+    return dist
+
+
+def _segment_distance(p: np.ndarray, u: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """distance from points p[n,1,3] to segments (u,v)[1,m,3]; a segment of no length is the point u"""
+    e, up = v - u, p - u
+    ee = (e * e).sum(-1)
+    t = np.clip((up * e).sum(-1) / np.where(ee > 0, ee, 1.0), 0.0, 1.0)
+    return np.sqrt(((up - t[..., None] * e) ** 2).sum(-1))
 
 
 def distance_to_mesh(points: np.ndarray, verts: np.ndarray, faces: np.ndarray, chunk: int = 256) -> np.ndarray:

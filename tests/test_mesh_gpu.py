@@ -47,6 +47,33 @@ def test_smoothing_matches_oracle():
     assert np.abs(one - om.smooth(v, f, 1, 0.05)).max() < 4e-6                                # 1-2 ulp at coordinates ~16 (fma contraction)
 
 
+def test_smoothing_production_setting_in_patient_space():
+    """150 sweeps at 0.01 (get_mesh's setting) on a mesh at coordinates ~140, cut open, with vertices no face uses, against a float64
+    Jacobi sweep: each sweep's final add rounds once at the coordinate's ulp, so the bound is iterations * ulp32(max|coordinate|)"""
+    from oai_analysis_2_amd import mesh_processing as mp
+    v, f = om.marching_cubes(_ellipsoid((30, 34, 32), (14.2, 16.9, 15.5), 9.0, (1.0, 1.3, 0.8)), 0.5, (0.5, 0.5, 0.7))
+    v = (v.astype(np.float64) + 130.0).astype(np.float32)
+    f = f[v[f][:, :, 0].mean(axis=1) < np.median(v[:, 0])]                                     # half the ellipsoid: an open boundary
+    v = np.concatenate([v, np.float32([[131.0, 132.0, 133.0]])])                               # and one vertex that never had a face
+    off, nbr = om.vertex_adjacency(len(v), f)
+    deg = np.diff(off)
+    used = deg > 0
+    boundary_edges = np.unique(np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1), axis=0, return_counts=True)[1] == 1
+    assert (~used).sum() > 100 and not used[-1] and boundary_edges.sum() > 20
+    rows = np.repeat(np.arange(len(v)), deg)
+    x, relax = v.astype(np.float64), np.float64(np.float32(0.01))
+    for _ in range(150):
+        s = np.zeros_like(x)
+        np.add.at(s, rows, x[nbr])
+        x = np.where(used[:, None], x + relax * (s / np.maximum(deg, 1)[:, None] - x), x)
+    got = mp.smooth_mesh(mp.Mesh(v, f), num_iterations=150, relaxation_factor=0.01).verts
+    bound = 150 * float(np.spacing(np.abs(v).max()))
+    print(f"smoothing 150 x 0.01 at +130: max|d| {np.abs(got - x).max():.3g}, bound {bound:.3g}")
+    assert np.abs(got - x).max() <= bound
+    assert np.array_equal(got[~used], v[~used])                                                # a vertex without neighbours stays put
+    assert np.abs(x[used] - v[used]).max() > 0.01                                              # (the sweeps did move the rest)
+
+
 def test_point_distance_matches_oracle():
     from oai_analysis_2_amd import mesh_processing as mp
     v, f = om.marching_cubes(_ellipsoid((30, 34, 32), (14.2, 16.9, 15.5), 9.0), 0.5)
