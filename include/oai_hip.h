@@ -836,6 +836,58 @@ int oai_label_components(const float* map_dev, const unsigned char* mask_dev, in
                          long long* summary_dev, void* stream);
 int oai_component_sizes(const int* labels_dev, long long n, long long n_components, long long* sizes_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Thickness QC (csrc/local_thickness.hip, tests/local_thickness_ref.py): the local thickness of a voxel set (Hildebrand and
+ * Ruegsegger 1997; what BoneJ and porespy implement) -- at a voxel the diameter of the largest ball that contains the voxel and stays
+ * inside the object -- and the statistics of a float32 field under a byte mask.  It needs no mesh, no inner/outer split, no atlas and
+ * no phi: an independent figure beside the mesh-based thickness.  All volumes are [z][y][x]; spacing_xyz is (x, y, z).
+ *
+ * oai_local_thickness: rsq_dev float64 [D][H][W], a squared-radius field from any source (the first is oai_edt's sq of the set's
+ * complement).  A voxel q is a centre when rsq[q] is finite and > 0; NaN, +-inf, zero and negative entries are not.  For every centre p
+ *   tx = (double)(px - qx) * sx;  ty = (double)(py - qy) * sy;  tz = (double)(pz - qz) * sz;      d2 = (tx*tx + ty*ty) + tz*tz
+ *   sq_out[p] = max over the centres q with d2 < rsq[q] of rsq[q]
+ *   thick[p]  = 2.0f * (float)sqrt(sq_out[p])
+ * d2 being oai_edt's canonical expression, in fp64 without contraction.  p covers itself, so sq_out[p] >= rsq[p].  sq_out[p] = 0 and
+ * thick[p] = 0 where p is not a centre.  The inequality is strict: with rsq the squared distance to the complement, the ball d < D(q)
+ * holds no background voxel, and <= would reach the nearest one.  Only fp64 compares and a max are involved, so the result does not
+ * depend on the order of execution and is bit-identical to the brute force over all pairs.
+ *   sq_out_dev (may be null) float64, thick_dev float32, both [D][H][W]
+ *   stats_dev (may be null): long long[4] on the device --
+ *     [0] centres   [1] voxel tests done: the sum of the clipped windows of the centres below the cap, and 1 for each capped centre
+ *     [2] capped centres   [3] the largest clipped window of any centre, capped or not
+ *   The maps do not depend on sq_out_dev or stats_dev being null.
+ * How: a scatter.  The centres are compacted into a list (the exclusive scan of the mesh kernels; the list's length stays on the
+ * device); each centre q walks its own window -- per axis the voxels within the largest k with fl((k s)^2) < rsq[q], clipped to the
+ * volume: the bounding box of its ball, found exactly -- and, where d2 < rsq[q] and p is a centre, raises the 64-bit key of p to the bit
+ * pattern of rsq[q] by an integer atomic max.  Positive doubles order like their bit patterns and a max is commutative and
+ * associative, so these atomics cost no reproducibility: this is the one place where the QC kernels use an atomic on a result.  The
+ * work is the sum of the centres' own windows ([1]), never the largest radius times the voxel count.
+ * max_window_voxels (> 0) caps the clipped window of one centre: a centre above it scatters onto itself only and is counted in [2];
+ * the map is then a lower bound, and the caller is told.  It guards shared machines against a blob that fills the volume (radius 80:
+ * 10^13 tests), and is not an accuracy knob.  Every axis in [1, 32767] and D H W <= 2^31 - 1 (the list is int32), every spacing finite
+ * and > 0.  The workspace holds the keys, the list, its scan and the centre bytes, 17 bytes per voxel.  Does not synchronise.
+ * Known bias of the voxel radius: a slab t voxels thick along an axis of spacing s gets 2 ceil(t / 2) s at every voxel, between t s
+ * and (t + 1) s; a sub-voxel radius (qc.local_thickness(radius="mesh")) removes it.
+ *
+ * oai_masked_stats: values_dev float32 [n]; mask_dev (may be null: every element) one byte per element, admitted where != 0.  An
+ * element is counted when the mask admits it and its value is finite.  out_dev: double[8] on the device --
+ *   [0] counted   [1] sum v   [2] sum v*v   [3] min   [4] max   [5], [6] the requested percentiles   [7] admitted non-finite values
+ * With nothing counted [1]..[6] are NaN; a percentile slot that was not asked for is NaN.  The sums are fp64 sums of the widened
+ * float32 values (v*v is exact there) in the fixed order of csrc/ordered_reduce.h, as oai_surface_distance: thread g of
+ * min(2048, ceil(n / 1024)) blocks of 256 takes the elements g, g + threads, ... in that order, one slot per block, a one-block
+ * finish.  The percentiles (n_percentiles = 0..2 host floats in [0, 100]) are np.percentile of the counted values as a float32 array,
+ * to the bit: the radix select of csrc/radix_select.h with the ranks computed on the device, where alone the count is known.
+ * n = 0 is allowed.  Does not synchronise.
+ * ---------------------------------------------------------------------------------------- */
+/* 0 when an axis is outside [1, 32767] or D*H*W > 2^31 - 1. */
+size_t oai_local_thickness_workspace_bytes(int D, int H, int W);
+int oai_local_thickness(const double* rsq_dev, int D, int H, int W, const double spacing_xyz[3], long long max_window_voxels,
+                        double* sq_out_dev, float* thick_dev, void* workspace_dev, size_t workspace_bytes, long long* stats_dev, void* stream);
+/* 0 when n < 0. */
+size_t oai_masked_stats_workspace_bytes(long long n);
+int oai_masked_stats(const float* values_dev, const unsigned char* mask_dev, long long n, const float* percentiles, int n_percentiles,
+                     void* workspace_dev, size_t workspace_bytes, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,10 @@ SIGNATURES = {
     "oai_label_components_workspace_bytes": (_Z, [_I, _I, _I]),
     "oai_label_components": (_I, [_P, _P, _I, _I, _I, _F, _I, _I, C.c_longlong, _P, _P, _P, _Z, _P, _P]),
     "oai_component_sizes": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P]),
+    "oai_local_thickness_workspace_bytes": (_Z, [_I, _I, _I]),
+    "oai_local_thickness": (_I, [_P, _I, _I, _I, C.POINTER(_D), C.c_longlong, _P, _P, _P, _Z, _P, _P]),
+    "oai_masked_stats_workspace_bytes": (_Z, [C.c_longlong]),
+    "oai_masked_stats": (_I, [_P, _P, C.c_longlong, C.POINTER(_F), _I, _P, _Z, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

@@ -247,6 +247,16 @@ def seg_qc_stream(results: Iterable[Tuple[int, object]], **kwargs) -> Iterator[T
         yield index, result_segmentation_shapes(res, **kwargs)
 
 
+def thickness_qc_stream(results: Iterable[Tuple[int, object]], **kwargs) -> Iterator[Tuple[int, object]]:
+    """(index, {"FC": qc.LocalThickness, "TC": ...}) for every (index, VolumeResult) of ``results``: the mesh-free local thickness of each
+    knee's patient-grid maps (qc.result_local_thicknesses; ``kwargs``: threshold, radius, return_map, max_window_voxels), the figure to
+    put beside the mesh-based thickness of a cohort.  The results must be complete and on the device, as for ``qc_stream``; like it a
+    plain synchronous generator, one download per knee."""
+    from .qc import result_local_thicknesses
+    for index, res in results:
+        yield index, result_local_thicknesses(res, **kwargs)
+
+
 def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None,
                              space: str = "atlas") -> Iterator[Tuple[int, object]]:
     """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the

@@ -523,3 +523,54 @@ def component_sizes(labels: torch.Tensor, n_components: int) -> torch.Tensor:
     sizes = (torch.empty if n else torch.zeros)(k, dtype=torch.int64, device=labels.device)     # the call clears the table unless it is a no-op
     _lib.call("oai_component_sizes", _ptr(labels, n), n, k, _ptr(sizes, k), _lib.STREAM, device=labels.device)
     return sizes
+
+
+# ---- thickness QC (include/oai_hip.h, "Thickness QC"; csrc/local_thickness.hip) ----------------------------------------------------------
+MAX_WINDOW_VOXELS = 262144   # 64^3: two orders of magnitude above a 6 mm cartilage at the DESS spacing (17 x 17 x 9 = 2601 voxels)
+THICKNESS_SLOTS = 4          # int64 per oai_local_thickness call: centres, voxel tests, capped centres, the largest window
+STATS_SLOTS = 8              # float64 per oai_masked_stats call
+
+
+def local_thickness(rsq: torch.Tensor, spacing_xyz=(1.0, 1.0, 1.0), max_window_voxels: int = MAX_WINDOW_VOXELS, return_squared: bool = False,
+                    return_stats: bool = False, out: Optional[torch.Tensor] = None):
+    """The local thickness of a float64 [z,y,x] device field of squared radii (``distance_transform(complement, return_squared=True)``,
+    or any other source): per centre -- a voxel whose entry is finite and > 0 -- twice the largest radius among the centres whose open
+    ball contains it, in the units of ``spacing_xyz`` (x, y, z); 0 elsewhere.  Bit-identical to the brute force over all pairs
+    (include/oai_hip.h).  Returns the float32 map; with ``return_squared`` also the float64 squared radii; with ``return_stats`` also the
+    int64 [4] DEVICE tensor centres, voxel tests done, capped centres, the largest window (``out``: written there instead of a new
+    tensor).  A centre whose clipped window holds more than ``max_window_voxels`` voxels covers only itself and is counted: a guard
+    against a blob that fills the volume, not an accuracy knob.  Does not synchronise."""
+    rsq = _volume3(rsq, "rsq", torch.float64)
+    D, H, W = (int(v) for v in rsq.shape)
+    thick = torch.empty((D, H, W), dtype=torch.float32, device=rsq.device)
+    sq = torch.empty((D, H, W), dtype=torch.float64, device=rsq.device) if return_squared else None
+    stats = _out_slot(out, THICKNESS_SLOTS, torch.int64, rsq.device, "out") if (return_stats or out is not None) else None
+    ws = _lib.workspace("oai_local_thickness", rsq.device, D, H, W, pad=True)
+    spacing = (C.c_double * 3)(*[float(v) for v in np.asarray(spacing_xyz, np.float64).reshape(3)])
+    _lib.call("oai_local_thickness", rsq.data_ptr(), D, H, W, spacing, int(max_window_voxels), _ptr(sq), thick.data_ptr(), ws.data_ptr(), ws.numel(),
+              _ptr(stats), _lib.STREAM, device=rsq.device)
+    got = (thick,) + ((sq,) if return_squared else ()) + ((stats,) if return_stats else ())
+    return got if len(got) > 1 else thick
+
+
+def masked_stats(values: torch.Tensor, mask: Optional[torch.Tensor] = None, percentiles: Sequence[float] = (50.0, 95.0),
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The statistics of a float32 device tensor under a uint8 / bool mask of its shape (None: every element): the float64 [8] DEVICE
+    tensor counted elements (admitted and finite), sum, sum of squares, min, max, up to two percentiles (``np.percentile`` of the
+    counted values bit for bit; NaN where not asked for) and the admitted non-finite values.  With nothing counted the sums, the
+    extremes and the percentiles are NaN.  fp64 sums in a fixed order: bit-reproducible (include/oai_hip.h, "Thickness QC").  ``out``:
+    written there instead of a new tensor.  Does not synchronise."""
+    values = _chk(values, "values")
+    if mask is not None:
+        mask = _chk(mask.view(torch.uint8) if mask.dtype == torch.bool else mask, "mask", torch.uint8)
+        if tuple(mask.shape) != tuple(values.shape) or mask.device != values.device:
+            raise ValueError(f"mask must have the values' shape {tuple(values.shape)} and live on their GPU, got {tuple(mask.shape)} on {mask.device}")
+    pct = [float(p) for p in percentiles]
+    if len(pct) > 2:
+        raise ValueError(f"at most two percentiles per call, got {len(pct)}")
+    n = int(values.numel())
+    stats = _out_slot(out, STATS_SLOTS, torch.float64, values.device, "out")
+    ws = _lib.workspace("oai_masked_stats", values.device, n)
+    _lib.call("oai_masked_stats", _ptr(values, n), _ptr(mask, n), n, (C.c_float * 2)(*(pct + [0.0, 0.0])[:2]), len(pct), ws.data_ptr(), ws.numel(),
+              stats.data_ptr(), _lib.STREAM, device=values.device)
+    return stats

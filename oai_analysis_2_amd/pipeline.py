@@ -47,6 +47,9 @@ class VolumeResult:
     # Optional[Dict[str, qc.SegmentationShape]]: the shape record of the patient-grid maps ``fc`` / ``tc`` (run(..., seg_qc=True) only).  A
     # plain attribute and not a dataclass field, like RegistrationQC.similarity: the fields of the result stay the ones earlier tests pin.
     seg_qc = None
+    # Optional[Dict[str, qc.LocalThickness]]: the mesh-free local thickness of the same maps (run(..., thickness_qc=True | "mesh") only); a
+    # plain attribute for the same reason
+    thickness_qc = None
 
 
 class VolumePipeline:
@@ -103,7 +106,7 @@ class VolumePipeline:
 
     # ---- one volume, one GPU --------------------------------------------------------------------------------------------------
     def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None,
-            thickness_space: str = "atlas", qc=None, seg_qc: bool = False) -> VolumeResult:
+            thickness_space: str = "atlas", qc=None, seg_qc: bool = False, thickness_qc=False) -> VolumeResult:
         """``thickness``: a thickness.ThicknessAtlas -- the volume's cartilage thickness on the atlas inner vertices is measured from
         ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
         None (default): nothing more is launched.  ``thickness_space``: "atlas" (default) = the distance on the atlas grid, as the
@@ -117,7 +120,13 @@ class VolumePipeline:
         the warp (``qc.similarity``) and leaves the patient image at network resolution in ``VolumeResult.image_net``.
         ``seg_qc``: True -- the reference-free shape record of the patient-grid maps (qc.segmentation_shapes: components, islands,
         cavities of ``fc`` and ``tc`` with ``meta_A``'s spacing) as ``{"FC": ..., "TC": ...}`` in ``VolumeResult.seg_qc``, computed where ``qc``
-        is; both cartilages are queued before the one download.  False (default): nothing more is launched and no bit changes."""
+        is; both cartilages are queued before the one download.  False (default): nothing more is launched and no bit changes.
+        ``thickness_qc``: True (or "voxel"), or "mesh" -- the mesh-free local thickness of the patient-grid maps (qc.local_thicknesses with
+        that ``radius``: the largest inscribed ball per voxel, mean / median / p95 per cartilage, with ``meta_A``'s spacing) as ``{"FC": ...,
+        "TC": ...}`` in ``VolumeResult.thickness_qc``, queued where ``seg_qc`` is; an independent figure to put beside ``thickness``.
+        False (default): nothing more is launched and no bit changes."""
+        if thickness_qc not in (False, True, "voxel", "mesh"):
+            raise ValueError(f"thickness_qc must be False, True, 'voxel' or 'mesh', got {thickness_qc!r}")
         if qc is not None and qc is not True and not hasattr(qc, "maps"):
             raise ValueError(f"qc must be None, True or a qc.QCReference, got {qc!r}")
         if thickness_space not in ("atlas", "patient", "patient_grid"):
@@ -142,6 +151,9 @@ class VolumePipeline:
         if seg_qc:
             from .qc import result_segmentation_shapes
             res.seg_qc = result_segmentation_shapes(res)
+        if thickness_qc:
+            from .qc import result_local_thicknesses
+            res.thickness_qc = result_local_thicknesses(res, radius="mesh" if thickness_qc == "mesh" else "voxel")
         return res
 
     def rerun_f32(self, vol: torch.Tensor, meta_A: Image, sharded_group="none") -> VolumeResult:

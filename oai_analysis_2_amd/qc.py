@@ -28,12 +28,19 @@ map (the set under ``connectivity``, its complement under the dual connectivity)
 ``clean_segmentation`` drops the islands on the device; ``VolumePipeline.run(seg_qc=True)`` returns the records of the patient-grid
 maps in ``VolumeResult.seg_qc``.  The labelling is ``scipy.ndimage.label``'s to the element, checked against scipy on the CPU.
 
+``local_thickness`` checks the one figure the pipeline exists to produce without any of the stages that produce it: per map a
+``LocalThickness`` -- at every voxel of the cartilage the diameter of the largest ball that contains it and stays inside (Hildebrand
+and Ruegsegger's local thickness), then mean / median / p95 over the set and over its surface voxels.  No mesh, no smoothing, no
+inner/outer split, no atlas, no phi: where the k-means split mislabels a patch the mesh-based thickness is the distance of a surface
+to itself or across the joint, and only a disagreement with this figure shows it.  ``VolumePipeline.run(thickness_qc=True)`` returns
+the records of the patient-grid maps in ``VolumeResult.thickness_qc``.
+
 ``image_similarity`` gives the same record for any two images on one grid.  ``surface_distance`` and ``segmentation_qc`` give the same figures for any two masks, e.g. a segmentation against a manual one.  The
 surface rule (``A ^ binary_erosion(A)``, 6-connectivity) and the pooled percentile are MedPy's on scipy, checked against scipy on the
 CPU; ``assd`` is the mean over the pooled distances, and ``mean_ab`` / ``mean_ba`` are there for the mean of the two directed means.
 
-Kernels: csrc/phi_jacobian.hip, csrc/edt.hip, csrc/similarity.hip, csrc/components.hip (include/oai_hip.h, "Registration QC",
-"Surface-distance QC", "Image-similarity QC", "Segmentation-shape QC").  ICON's LNCC form (a Gaussian window of 4 sigma + 1 samples, sigma = 4, eps = 1e-5) is restated as recalled and unpinned.  The fold definition is restated from ``flips`` as recalled
+Kernels: csrc/phi_jacobian.hip, csrc/edt.hip, csrc/similarity.hip, csrc/components.hip, csrc/local_thickness.hip (include/oai_hip.h,
+"Registration QC", "Surface-distance QC", "Image-similarity QC", "Segmentation-shape QC", "Thickness QC").  ICON's LNCC form (a Gaussian window of 4 sigma + 1 samples, sigma = 4, eps = 1e-5) is restated as recalled and unpinned.  The fold definition is restated from ``flips`` as recalled
 and unpinned, like the resample: icon_registration and ITK are absent.  No threshold and no pass / fail policy is built in: the
 record is data.
 """
@@ -575,3 +582,128 @@ def result_segmentation_shapes(result, **kwargs) -> Dict[str, SegmentationShape]
     meta = getattr(result, "meta_A", None)
     spacing = None if meta is None else np.asarray(as_image(meta).spacing, np.float64)
     return segmentation_shapes({kind: getattr(result, kind.lower()) for kind in KINDS}, spacing, **kwargs)
+
+
+# ---- thickness QC (include/oai_hip.h, "Thickness QC"; csrc/local_thickness.hip) ----------------------------------------------------------
+@dataclass
+class LocalThickness:
+    """The local thickness of the set ``> threshold`` of one map, in the units of the spacing: at a voxel the diameter of the largest
+    ball that contains the voxel and stays inside the set (Hildebrand and Ruegsegger).  No mesh, no inner/outer split, no atlas and no
+    phi take part.  ``radius`` "voxel": the balls' radii are the exact distances of the voxel centres to the nearest voxel outside the
+    set, so a slab of t voxels along an axis of spacing s reads 2 ceil(t / 2) s, between t s and (t + 1) s; "mesh": their distances to
+    the raw marching-cubes surface of the map, sub-voxel.  Without a centre (an empty set, or a set that fills the volume and has no
+    complement to measure to) every statistic is NaN and the counts stay."""
+    voxels: int                  # voxels of the set
+    mm3: Optional[float]         # ... times the voxel volume (None without a spacing)
+    mean: float                  # over the voxels of the set, from the device's two fp64 sums, on the host in fp64
+    std: float                   # population standard deviation
+    median: float                # np.percentile of the float32 map on the set, 50
+    p95: float
+    max: float
+    surface_mean: float          # the same map on the set's surface voxels (mask_surface "surface"): area-like weighting, closer to
+    surface_median: float        # what the mesh thickness averages over
+    capped_centres: int          # centres whose window was above max_window_voxels: not 0 = the map is a lower bound
+    work: int                    # voxel tests done
+    radius: str                  # "voxel" | "mesh"
+    thickness_map: Optional[torch.Tensor] = None     # float32 [z,y,x] on the device (return_map=True only)
+
+
+THICKNESS_RADII = ("voxel", "mesh")
+_THICKNESS_PARTS = (("scatter", ops.THICKNESS_SLOTS, torch.int64), ("set", ops.STATS_SLOTS, torch.float64),
+                    ("surface", ops.STATS_SLOTS, torch.float64))
+
+
+def _thickness_layout(key):
+    return [((key, part), n, dtype) for part, n, dtype in _THICKNESS_PARTS]
+
+
+def thickness_from_stats(scatter, over_set, over_surface, radius: str, voxel_mm3: Optional[float] = None,
+                         thickness_map: Optional[torch.Tensor] = None) -> LocalThickness:
+    """The record of the four integers of ``ops.local_thickness`` and the eight doubles of ``ops.masked_stats`` over the set and over
+    its surface (already on the host)."""
+    centres, work, capped = int(scatter[0]), int(scatter[1]), int(scatter[2])
+    s, f = [float(v) for v in over_set], [float(v) for v in over_surface]
+    voxels, nan = int(s[0]), float("nan")
+    if centres > 0 and voxels > 0:
+        mean = s[1] / voxels
+        std = 0.0 if s[3] == s[4] else math.sqrt(max(s[2] / voxels - mean * mean, 0.0))       # min == max: one value, whatever the sums rounded to
+        figures = (mean, std, s[5], s[6], s[4], f[1] / f[0] if f[0] > 0 else nan, f[5])
+    else:
+        figures = (nan,) * 7
+    return LocalThickness(voxels, None if voxel_mm3 is None else voxels * float(voxel_mm3), *figures, capped, work, radius, thickness_map)
+
+
+def mesh_radius_points(vol: torch.Tensor, spacing_xyz, threshold: float = 0.5):
+    """(idx int64 [n,3] (z,y,x) of the set's voxels, their centres float32 [n,3] (x,y,z) in physical units, verts, faces of the raw
+    marching cubes of the map at the threshold): what ``radius="mesh"`` measures from and to.  ``torch.nonzero`` is plumbing."""
+    from .mesh_processing import _marching_cubes_dev
+    idx = torch.nonzero(ops.mask_surface(vol, threshold, "set"))
+    pts = (idx.flip(1).to(torch.float32) * torch.tensor([float(v) for v in spacing_xyz], dtype=torch.float32, device=vol.device)).contiguous()
+    verts, faces = _marching_cubes_dev(vol, threshold, spacing_xyz)
+    return idx, pts, verts, faces
+
+
+def _radius_field(vol: torch.Tensor, spacing_xyz, threshold: float, radius: str) -> torch.Tensor:
+    """The float64 squared-radius field of the set ``> threshold``: zero outside the set."""
+    if radius == "voxel":       # the EDT to the complement is zero on the complement itself, and +inf everywhere when there is none
+        return ops.distance_transform(ops.mask_surface(vol, threshold, "complement"), spacing_xyz, return_squared=True)[1]
+    from .mesh_processing import _distance_dev
+    idx, pts, verts, faces = mesh_radius_points(vol, spacing_xyz, threshold)
+    rsq = torch.zeros(tuple(vol.shape), dtype=torch.float64, device=vol.device)
+    if int(idx.shape[0]) and int(faces.shape[0]):
+        d = _distance_dev(pts, verts, faces).to(torch.float64)
+        rsq[idx[:, 0], idx[:, 1], idx[:, 2]] = d * d
+    return rsq
+
+
+def _queue_thickness(vol: torch.Tensor, spacing_xyz, threshold, radius, max_window_voxels, views, key) -> torch.Tensor:
+    """One map queued on the current stream, results into the views of ``_thickness_layout(key)``; returns the device map."""
+    rsq = _radius_field(vol, spacing_xyz, threshold, radius)
+    thick = ops.local_thickness(rsq, spacing_xyz, max_window_voxels, out=views[key, "scatter"])
+    ops.masked_stats(thick, ops.mask_surface(vol, threshold, "set"), (50.0, 95.0), out=views[key, "set"])
+    ops.masked_stats(thick, ops.mask_surface(vol, threshold, "surface"), (50.0,), out=views[key, "surface"])
+    return thick
+
+
+def local_thicknesses(maps: Dict[str, object], spacing_xyz=None, threshold: float = 0.5, radius: str = "voxel", return_map: bool = False,
+                      max_window_voxels: int = ops.MAX_WINDOW_VOXELS) -> Dict[str, LocalThickness]:
+    """``local_thickness`` of several maps on one GPU, all queued before the ONE download."""
+    if radius not in THICKNESS_RADII:
+        raise ValueError(f"radius must be one of {THICKNESS_RADII}, got {radius!r}")
+    if int(max_window_voxels) <= 0:
+        raise ValueError(f"max_window_voxels must be > 0, got {max_window_voxels}")
+    got = {key: _map_with_spacing(m, spacing_xyz) for key, m in maps.items()}
+    vols = {key: g[0].contiguous() for key, g in got.items()}
+    if not vols:
+        return {}
+    has_spacing = {key: not (spacing_xyz is None and (torch.is_tensor(maps[key]) or isinstance(maps[key], np.ndarray))) for key in vols}
+    device = next(iter(vols.values())).device
+    if any(v.device != device for v in vols.values()):
+        raise ValueError("the maps must live on one GPU")
+    with torch.cuda.device(device):
+        views, download = _result_slots(device, [slot for key in vols for slot in _thickness_layout(key)])
+        thick = {key: _queue_thickness(vol, got[key][1], threshold, radius, int(max_window_voxels), views, key) for key, vol in vols.items()}
+        host = download()
+    return {key: thickness_from_stats(host[key, "scatter"], host[key, "set"], host[key, "surface"], radius,
+                                      float(np.prod(got[key][1])) if has_spacing[key] else None, thick[key] if return_map else None)
+            for key in vols}
+
+
+def local_thickness(map, spacing_xyz=None, threshold: float = 0.5, radius: str = "voxel", return_map: bool = False,
+                    max_window_voxels: int = ops.MAX_WINDOW_VOXELS) -> LocalThickness:
+    """The local-thickness record of one probability map (an ``Image``, an array or a [z,y,x] device tensor, as ``surface_distance``
+    takes them; ``spacing_xyz`` goes with arrays and tensors: unit without it, and ``mm3`` is None): the squared-radius field of the set
+    ``> threshold`` (``radius`` "voxel": one ``ops.mask_surface`` and one ``ops.distance_transform`` of the complement; "mesh": the
+    point-to-mesh distance of the set's voxel centres to the raw marching cubes of the map, which reads the mesh's size back), one
+    ``ops.local_thickness`` and two ``ops.masked_stats`` -- over the set and over its surface voxels -- queued into one buffer; ONE
+    download.  ``capped_centres`` not 0: centres above ``max_window_voxels`` were left out and the figures are lower bounds.  No
+    threshold for "bad" is built in: the record is data, to be put beside the mesh-based thickness."""
+    return local_thicknesses({"map": map}, spacing_xyz, threshold, radius, return_map, max_window_voxels)["map"]
+
+
+def result_local_thicknesses(result, **kwargs) -> Dict[str, LocalThickness]:
+    """``{"FC": ..., "TC": ...}``: the local-thickness records of the patient-grid maps ``fc`` / ``tc`` of a ``pipeline.VolumeResult``,
+    with the spacing of its ``meta_A`` (unit, and ``mm3`` None, without one).  Both maps are queued before the one download."""
+    meta = getattr(result, "meta_A", None)
+    spacing = None if meta is None else np.asarray(as_image(meta).spacing, np.float64)
+    return local_thicknesses({kind: getattr(result, kind.lower()) for kind in KINDS}, spacing, **kwargs)
