@@ -456,6 +456,20 @@ size_t oai_point_grid_workspace_bytes(const int grid_dims_xyz[3], long long n_sr
 int oai_map_attributes_grid(const float* src_pts_dev, long long n_src, const float* src_vals_dev, int n_comp, const float* tgt_pts_dev,
                             long long n_tgt, double radius, const double grid_lo_xyz_host[3], double cell_size, const int grid_dims_xyz_host[3],
                             void* workspace_dev, size_t workspace_bytes, float* out_vals_dev, void* stream);
+/* The footprint that decides mean versus fallback in oai_map_attributes(_grid), for the same arguments minus the values: per target t
+ *   count[t]       int32    the source points s with d2 = |p_s - q_t|^2 <= radius^2 (d2: fp64 dx*dx + dy*dy + dz*dz of the widened float32
+ *                           coordinates, without contraction: the expression map_attributes tests)
+ *   nearest_d2[t]  float64  the minimum d2 over all source points;  nearest_j[t] int32: the smallest index at that minimum
+ * map_attributes took the mean exactly where count > 0, and vals[c][nearest_j] where count == 0.  With no source point at a finite
+ * distance (NaN or infinite coordinates) nearest_j = -1 and nearest_d2 = +inf.  Integers, compares and a minimum: the grid form and
+ * the brute force agree to the bit.  The grid form visits what oai_map_attributes_grid visits (the 27 cells, then shells of cells while
+ * count == 0) and takes the same workspace; with count > 0 the nearest point lies inside the 27 cells.  n_src == 0 is an argument
+ * error.  Neither call synchronises. */
+int oai_point_footprint(const float* src_pts_dev, long long n_src, const float* tgt_pts_dev, long long n_tgt, double radius, int* count_dev,
+                        double* nearest_d2_dev, int* nearest_j_dev, void* stream);
+int oai_point_footprint_grid(const float* src_pts_dev, long long n_src, const float* tgt_pts_dev, long long n_tgt, double radius,
+                             const double grid_lo_xyz_host[3], double cell_size, const int grid_dims_xyz_host[3], void* workspace_dev,
+                             size_t workspace_bytes, int* count_dev, double* nearest_d2_dev, int* nearest_j_dev, void* stream);
 /* Workspace of the three calls below for n points (mesh_processing.py:411-534). */
 size_t oai_thickness_map_workspace_bytes(long long n_points);
 /* compute_least_square_circle (:411-447) on (x, y) = (p[col_x], p[col_y]): the centre minimising sum (R_i - mean R)^2, by
@@ -887,6 +901,45 @@ int oai_local_thickness(const double* rsq_dev, int D, int H, int W, const double
 size_t oai_masked_stats_workspace_bytes(long long n);
 int oai_masked_stats(const float* values_dev, const unsigned char* mask_dev, long long n, const float* percentiles, int n_percentiles,
                      void* workspace_dev, size_t workspace_bytes, double* out_dev, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------
+ * Cartilage morphometry (csrc/morphometry.hip, tests/morphometry_ref.py): what reduces the per-vertex thickness on the atlas inner mesh
+ * to per-knee figures -- mean thickness over the subchondral bone area, covered and denuded area, per region.  The reference has no
+ * such step and VTK is absent: the definitions are this library's own, unpinned.  fp64 without contraction, every sum in a stated
+ * order, no floating-point atomics: bit-reproducible.  With oai_point_footprint (above) these are its three primitives.
+ *
+ * oai_mesh_areas: verts_dev float32 [n_verts][3], faces_dev int32 [n_faces][3].  With a, b, c the corners of face f widened to double,
+ *   e1 = b - a;  e2 = c - a;  cx = e1y*e2z - e1z*e2y;  cy = e1z*e2x - e1x*e2z;  cz = e1x*e2y - e1y*e2x
+ *   face_area[f]   = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz)
+ *   vertex_area[v] = (sum of face_area[f] over the corners (f, k) that name v, in ascending 3 f + k) / 3.0
+ * so a face that names a vertex twice counts twice for it (its area is 0), a vertex that no face names gets 0.0, and non-finite
+ * coordinates propagate as IEEE gives them.  A face with an index outside [0, n_verts) has face_area NaN and is incident to no vertex.
+ * face_area_dev float64 [n_faces] (may be null), vertex_area_dev float64 [n_verts].  The vertex-to-corner incidence is built by count,
+ * exclusive scan and scatter (integer atomics for the slots); each vertex then adds its own corners smallest index first.  Does not
+ * synchronise.  n_verts <= 2^31 - 2, n_faces <= 2^28.
+ *
+ * oai_region_stats: values_dev float32 [n], weights_dev float64 [n], labels_dev int32 [n] (may be null: every element in region 0),
+ * covered_dev one byte per element (may be null: every element covered), 1 <= n_regions <= 64.  An element with a label outside
+ * [0, n_regions) belongs to no region; it is MEASURED when it is covered (byte != 0) and its value is finite.  With t = (double)value
+ * and w the weight, out_dev: double [n_regions][12] on the device, per region --
+ *   [0] elements   [1] covered elements   [2] measured elements
+ *   [3] sum w over all elements   [4] sum w over covered   [5] sum w over measured
+ *   [6] sum w*t over measured   [7] sum (w*t)*t over measured   [8] min t   [9] max t over measured   [10] sum t   [11] sum t*t over measured
+ * in the fixed order of csrc/ordered_reduce.h with oai_surface_distance's layout: thread g of max(1, min(2048, ceil(n / 1024))) blocks
+ * of 256 takes the elements g, g + threads, ... in that order, one slot row per block and region, a one-block finish per region.  An
+ * element outside a region performs no operation on that region's accumulator.  An empty region reads 0 for counts and sums, +inf
+ * for the minimum and -inf for the maximum (+0 and -0 compare equal: which of them a minimum keeps is not specified).  n = 0 is
+ * allowed.  Does not synchronise.
+ * ---------------------------------------------------------------------------------------- */
+/* 0 when n_verts is outside [0, 2^31 - 2] or n_faces outside [0, 2^28]. */
+size_t oai_mesh_areas_workspace_bytes(long long n_verts, long long n_faces);
+int oai_mesh_areas(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, void* workspace_dev, size_t workspace_bytes,
+                   double* face_area_dev, double* vertex_area_dev, void* stream);
+/* 0 when n < 0 or n_regions is outside [1, 64]. */
+size_t oai_region_stats_workspace_bytes(long long n, int n_regions);
+int oai_region_stats(const float* values_dev, const double* weights_dev, const int* labels_dev, const unsigned char* covered_dev, long long n,
+                     int n_regions, void* workspace_dev, size_t workspace_bytes, double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

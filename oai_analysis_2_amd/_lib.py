@@ -64,6 +64,8 @@ SIGNATURES = {
     "oai_map_attributes": (_I, [_P, C.c_longlong, _P, _I, _P, C.c_longlong, _D, _P, _P]),
     "oai_point_grid_workspace_bytes": (_Z, [C.POINTER(C.c_int), C.c_longlong]),
     "oai_map_attributes_grid": (_I, [_P, C.c_longlong, _P, _I, _P, C.c_longlong, _D, C.POINTER(_D), _D, C.POINTER(C.c_int), _P, _Z, _P, _P]),
+    "oai_point_footprint": (_I, [_P, C.c_longlong, _P, C.c_longlong, _D, _P, _P, _P, _P]),
+    "oai_point_footprint_grid": (_I, [_P, C.c_longlong, _P, C.c_longlong, _D, C.POINTER(_D), _D, C.POINTER(C.c_int), _P, _Z, _P, _P, _P, _P]),
     "oai_thickness_map_workspace_bytes": (_Z, [C.c_longlong]),
     "oai_fit_circle": (_I, [_P, C.c_longlong, _I, _I, _P, _Z, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I), _P]),
     "oai_project_circle": (_I, [_P, C.c_longlong, _I, _I, C.POINTER(_D), _P, _P, _P]),
@@ -117,6 +119,10 @@ SIGNATURES = {
     "oai_local_thickness": (_I, [_P, _I, _I, _I, C.POINTER(_D), C.c_longlong, _P, _P, _P, _Z, _P, _P]),
     "oai_masked_stats_workspace_bytes": (_Z, [C.c_longlong]),
     "oai_masked_stats": (_I, [_P, _P, C.c_longlong, C.POINTER(_F), _I, _P, _Z, _P, _P]),
+    "oai_mesh_areas_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_mesh_areas": (_I, [_P, C.c_longlong, _P, C.c_longlong, _P, _Z, _P, _P, _P]),
+    "oai_region_stats_workspace_bytes": (_Z, [C.c_longlong, _I]),
+    "oai_region_stats": (_I, [_P, _P, _P, _P, C.c_longlong, _I, _P, _Z, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

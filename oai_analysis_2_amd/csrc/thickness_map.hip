@@ -9,6 +9,8 @@
 // footprint weighs the same), the RADIUS footprint with Radius 1.0, NormalizeWeights on -> the plain mean over source points with
 // |p - q|^2 <= r^2; no point inside -> the closest source point's value (ties: the smallest index).  Sums are fp64 in a fixed order
 // (grid: cell by cell, each cell's list in ascending point index; brute force: ascending index), stored as float32.
+// oai_point_footprint(_grid) is the same walk with no point array: it returns what decides mean versus fallback -- the count inside the
+// radius, the closest squared distance and its source index -- so that a caller can tell "no cartilage here" from a thickness.
 //
 // project_thickness: a linear-kernel PCA equals the PCA of the 3x3 scatter matrix, so each plateau needs O(n) work (three
 // deterministic fp64 reductions) and a 3x3 eigen-decomposition on the host instead of sklearn's n x n kernel matrix.  The sign of each
@@ -91,6 +93,9 @@ struct Interp {
     int nc;                   // <= kMaxComp
     float* out;               // [nc][n_tgt]
     long long n_tgt;
+    int* count;               // oai_point_footprint (nc = 0, no values): the footprint itself, [n_tgt] each; null in map_attributes
+    double* nearest_d2;
+    int* nearest_j;
 };
 
 struct Acc {
@@ -119,6 +124,7 @@ __device__ __forceinline__ void acc_store(const Acc& a, const Interp& ip, long l
         else v = a.best_j >= 0 ? ip.vals[m * ip.n_src + a.best_j] : __int_as_float(0x7fc00000);     // no finite source point: NaN
         ip.out[m * ip.n_tgt + i] = v;
     }
+    if (ip.count) { ip.count[i] = a.cnt; ip.nearest_d2[i] = a.best; ip.nearest_j[i] = a.best_j; }
 }
 
 __global__ void __launch_bounds__(kT) interp_grid_kernel(const float* __restrict__ src, const float* __restrict__ tgt, GridD g, double r2,
@@ -387,11 +393,41 @@ int launch_interp(bool grid, const float* src, long long n_src, const float* val
                   const GridD& g, const int* start, const int* list, float* out, hipStream_t st) {
     const double r2 = radius * radius;
     for (int c0 = 0; c0 < n_comp; c0 += kMaxComp) {
-        Interp ip{vals + (long long)c0 * n_src, n_src, n_comp - c0 < kMaxComp ? n_comp - c0 : kMaxComp, out + (long long)c0 * n_tgt, n_tgt};
+        Interp ip{vals + (long long)c0 * n_src, n_src, n_comp - c0 < kMaxComp ? n_comp - c0 : kMaxComp, out + (long long)c0 * n_tgt, n_tgt,
+                  nullptr, nullptr, nullptr};
         if (grid) interp_grid_kernel<<<oai::cdiv(n_tgt, kT), kT, 0, st>>>(src, tgt, g, r2, start, list, ip);
         else interp_brute_kernel<<<oai::cdiv(n_tgt, kT), kT, 0, st>>>(src, tgt, r2, ip);
         OAI_CHECK_LAUNCH();
     }
+    return OAI_OK;
+}
+
+// the source points into their cells: count -> scan -> scatter -> each cell's list in ascending point index
+int bin_points(const float* src, long long n_src, const double lo[3], double cell_size, const int dims[3], const PointGridWs& w, GridD* grid,
+               hipStream_t st) {
+    GridD& g = *grid;
+    for (int k = 0; k < 3; ++k) { g.lo[k] = lo[k]; g.n[k] = dims[k]; }
+    g.h = cell_size; g.inv_h = 1.0 / cell_size;
+    const long long ncells = (long long)dims[0] * dims[1] * dims[2];
+    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    bin_count_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(src, n_src, g, w.cell_of, w.count);
+    OAI_CHECK_LAUNCH();
+    if (int rc = oai::exclusive_scan_i32(w.count, w.start, ncells + 1, w.scratch, st)) return rc;
+    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    bin_scatter_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.cell_of, n_src, w.start, w.count, w.unordered);
+    OAI_CHECK_LAUNCH();
+    bin_order_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.unordered, n_src, w.cell_of, w.start, w.list);
+    OAI_CHECK_LAUNCH();
+    return OAI_OK;
+}
+
+// oai_point_footprint: the interpolation kernels with no point array (nc = 0: nothing summed, nothing stored but the footprint)
+int launch_footprint(bool grid, const float* src, long long n_src, const float* tgt, long long n_tgt, double radius, const GridD& g, const int* start,
+                     const int* list, int* count, double* nearest_d2, int* nearest_j, hipStream_t st) {
+    const Interp ip{nullptr, n_src, 0, nullptr, n_tgt, count, nearest_d2, nearest_j};
+    if (grid) interp_grid_kernel<<<oai::cdiv(n_tgt, kT), kT, 0, st>>>(src, tgt, g, radius * radius, start, list, ip);
+    else interp_brute_kernel<<<oai::cdiv(n_tgt, kT), kT, 0, st>>>(src, tgt, radius * radius, ip);
+    OAI_CHECK_LAUNCH();
     return OAI_OK;
 }
 
@@ -545,18 +581,41 @@ int oai_map_attributes_grid(const float* src_pts_dev, long long n_src, const flo
     if (n_tgt == 0) return OAI_OK;
     hipStream_t st = (hipStream_t)stream;
     GridD g;
-    for (int k = 0; k < 3; ++k) { g.lo[k] = grid_lo_xyz[k]; g.n[k] = grid_dims_xyz[k]; }
-    g.h = cell_size; g.inv_h = 1.0 / cell_size;
-    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
-    bin_count_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(src_pts_dev, n_src, g, w.cell_of, w.count);
-    OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(w.count, w.start, ncells + 1, w.scratch, st)) return rc;
-    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
-    bin_scatter_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.cell_of, n_src, w.start, w.count, w.unordered);
-    OAI_CHECK_LAUNCH();
-    bin_order_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.unordered, n_src, w.cell_of, w.start, w.list);
-    OAI_CHECK_LAUNCH();
+    if (int rc = bin_points(src_pts_dev, n_src, grid_lo_xyz, cell_size, grid_dims_xyz, w, &g, st)) return rc;
     return launch_interp(true, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, g, w.start, w.list, out_vals_dev, st);
+}
+
+int oai_point_footprint(const float* src_pts_dev, long long n_src, const float* tgt_pts_dev, long long n_tgt, double radius, int* count_dev,
+                        double* nearest_d2_dev, int* nearest_j_dev, void* stream) {
+    OAI_CHECK_ARG(src_pts_dev && tgt_pts_dev && count_dev && nearest_d2_dev && nearest_j_dev, "oai_point_footprint: null pointer");
+    OAI_CHECK_ARG(n_src > 0 && n_src < (1LL << 31), "oai_point_footprint: needs 1 .. 2^31-1 source points (got %lld)", n_src);
+    OAI_CHECK_ARG(n_tgt >= 0, "oai_point_footprint: negative target count");
+    OAI_CHECK_ARG(radius >= 0.0 && std::isfinite(radius), "oai_point_footprint: radius must be finite and >= 0");
+    if (n_tgt == 0) return OAI_OK;
+    return launch_footprint(false, src_pts_dev, n_src, tgt_pts_dev, n_tgt, radius, GridD{}, nullptr, nullptr, count_dev, nearest_d2_dev, nearest_j_dev,
+                            (hipStream_t)stream);
+}
+
+int oai_point_footprint_grid(const float* src_pts_dev, long long n_src, const float* tgt_pts_dev, long long n_tgt, double radius,
+                             const double grid_lo_xyz[3], double cell_size, const int grid_dims_xyz[3], void* workspace_dev, size_t workspace_bytes,
+                             int* count_dev, double* nearest_d2_dev, int* nearest_j_dev, void* stream) {
+    OAI_CHECK_ARG(src_pts_dev && tgt_pts_dev && count_dev && nearest_d2_dev && nearest_j_dev && grid_lo_xyz && grid_dims_xyz && workspace_dev,
+                  "oai_point_footprint_grid: null pointer");
+    OAI_CHECK_ARG(n_src > 0 && n_src < (1LL << 31), "oai_point_footprint_grid: needs 1 .. 2^31-1 source points (got %lld)", n_src);
+    OAI_CHECK_ARG(n_tgt >= 0, "oai_point_footprint_grid: negative target count");
+    OAI_CHECK_ARG(radius >= 0.0 && std::isfinite(radius), "oai_point_footprint_grid: radius must be finite and >= 0");
+    OAI_CHECK_ARG(cell_size > 0.0 && cell_size >= radius && std::isfinite(cell_size), "oai_point_footprint_grid: cell_size %g must be >= radius %g and > 0",
+                  cell_size, radius);
+    OAI_CHECK_ARG(grid_dims_xyz[0] > 0 && grid_dims_xyz[1] > 0 && grid_dims_xyz[2] > 0, "oai_point_footprint_grid: empty grid");
+    const long long ncells = (long long)grid_dims_xyz[0] * grid_dims_xyz[1] * grid_dims_xyz[2];
+    OAI_CHECK_ARG(ncells < (1LL << 30), "oai_point_footprint_grid: grid too fine");
+    PointGridWs w;
+    OAI_CHECK_WORKSPACE("oai_point_footprint_grid", workspace_bytes, carve(w, workspace_dev, ncells, n_src));
+    if (n_tgt == 0) return OAI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    GridD g;
+    if (int rc = bin_points(src_pts_dev, n_src, grid_lo_xyz, cell_size, grid_dims_xyz, w, &g, st)) return rc;
+    return launch_footprint(true, src_pts_dev, n_src, tgt_pts_dev, n_tgt, radius, g, w.start, w.list, count_dev, nearest_d2_dev, nearest_j_dev, st);
 }
 
 size_t oai_thickness_map_workspace_bytes(long long n_points) {

@@ -40,7 +40,9 @@ and returns ITK's physical points.  The thickness image (thickness_image_build /
 rasterises a projected mesh once -- per pixel the smallest covering face index, its corners and barycentric weights, restated in
 tests/thickness_image_ref.py -- and gathers per-point values through it; _map_attributes_dev / _thickness_inner_dev are the device-tensor
 forms of map_attributes and of get_thickness_mesh's resident branch (inner mesh and inner -> outer distance only) that thickness.py chains
-without downloads.  There is no CPU fallback for the kernels.
+without downloads.  mesh_areas (per-face and per-vertex area, csrc/morphometry.hip) and point_footprint (what map_attributes saw of the source points:
+the count inside the radius, the nearest distance and index) have no line in the reference either; thickness.py builds the per-knee morphometry on
+them.  There is no CPU fallback for the kernels.
 """
 from __future__ import annotations
 
@@ -760,6 +762,67 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
         out_data[name] = res[row:row + k].T.reshape((n_tgt,) + tuple(shape[1:]))
         row += k
     return Mesh(target_mesh.verts, target_mesh.faces, out_data)
+
+
+# ---- cartilage morphometry: the footprint behind map_attributes and mesh areas (csrc/thickness_map.hip, csrc/morphometry.hip) --------
+def _point_footprint_dev(src_verts: torch.Tensor, tgt_verts: torch.Tensor, radius: float = 1.0, grid=None):
+    """What decided mean versus fallback in ``_map_attributes_dev(src_verts, .., tgt_verts, radius, grid)``, on the same arguments minus
+    the values: device tensors (count int32 [n_tgt], nearest squared distance float64, nearest source index int32), nothing downloaded.
+    ``grid`` = (lo, hi) as there; None: brute force over every source point (the same bits)."""
+    n_src, n_tgt = int(src_verts.shape[0]), int(tgt_verts.shape[0])
+    if n_src == 0:
+        raise ValueError("point_footprint: there are no source points")
+    dev = src_verts.device
+    count, d2, j = (torch.empty(n_tgt, dtype=t, device=dev) for t in (torch.int32, torch.float64, torch.int32))
+    if grid is None:
+        _lib.call("oai_point_footprint", src_verts.data_ptr(), n_src, tgt_verts.data_ptr(), n_tgt, float(radius), count.data_ptr(), d2.data_ptr(),
+                  j.data_ptr(), _lib.STREAM, device=dev)
+        return count, d2, j
+    h, dims, lo = _grid_from_params(*(np.asarray(x, dtype=np.float64).reshape(3) for x in grid), radius)
+    glo = (C.c_double * 3)(*[float(x) for x in lo])
+    gd = (C.c_int * 3)(*[int(x) for x in dims])
+    ws = _lib.workspace("oai_point_grid", dev, gd, n_src)
+    _lib.call("oai_point_footprint_grid", src_verts.data_ptr(), n_src, tgt_verts.data_ptr(), n_tgt, float(radius), glo, float(h), gd, ws.data_ptr(),
+              ws.numel(), count.data_ptr(), d2.data_ptr(), j.data_ptr(), _lib.STREAM, device=dev)
+    return count, d2, j
+
+
+def point_footprint(points: np.ndarray, source_points: np.ndarray, radius: float = 1.0, broad_phase: bool = True):
+    """Per point, what ``map_attributes(source, target, radius)`` saw of the source points: (count, nearest_distance, nearest_index) --
+    the number of source points within ``radius`` (int32; map_attributes took their mean exactly where it is > 0), the distance to the
+    closest source point (float64, the square root of the kernel's fp64 squared distance) and its index (int32, the smallest on a tie:
+    the point whose value the fallback took).  ``broad_phase`` as in map_attributes; both forms give the same bits."""
+    _lib.load()
+    src = np.ascontiguousarray(source_points, dtype=np.float32).reshape(-1, 3)
+    if len(src) == 0:
+        raise ValueError("point_footprint: there are no source points")
+    s, t = _dev(src, np.float32, (3,)), _dev(points, np.float32, (3,))
+    grid = (src.min(axis=0).astype(np.float64), src.max(axis=0).astype(np.float64)) if broad_phase else None
+    count, d2, j = _point_footprint_dev(s, t, radius, grid)
+    return count.cpu().numpy(), np.sqrt(d2.cpu().numpy()), j.cpu().numpy()
+
+
+def _mesh_areas_dev(verts: torch.Tensor, faces: torch.Tensor, return_face_area: bool = False):
+    """mesh_areas on device tensors (float32 [n,3], int32 [m,3]): the float64 [n] vertex areas (and the float64 [m] face areas), nothing
+    downloaded."""
+    n, m = int(verts.shape[0]), int(faces.shape[0])
+    va = torch.empty(n, dtype=torch.float64, device=verts.device)
+    fa = torch.empty(m, dtype=torch.float64, device=verts.device) if return_face_area else None
+    ws = _lib.workspace("oai_mesh_areas", verts.device, n, m, pad=True)
+    _lib.call("oai_mesh_areas", ops._ptr(verts, n), n, ops._ptr(faces, m), m, ws.data_ptr(), ws.numel(), ops._ptr(fa, m), ops._ptr(va, n), _lib.STREAM,
+              device=verts.device)
+    return (va, fa) if return_face_area else va
+
+
+def mesh_areas(mesh: Mesh) -> Tuple[np.ndarray, np.ndarray]:
+    """(vertex_area [n], face_area [m]) of a triangle mesh as float64 arrays, in the squared unit of its vertices.  A face's area is half
+    the norm of its edge cross product in fp64; a vertex owns a third of every face that names it, summed in ascending face index (then
+    corner), so the vertex areas add up to the surface area and weigh a per-vertex quantity by surface, not by sampling density.  A
+    vertex that no face names gets 0.0.  Bit-reproducible (include/oai_hip.h, "Cartilage morphometry")."""
+    _lib.load()
+    v, f = _dev(mesh.verts, np.float32, (3,)), _dev(mesh.faces, np.int32, (3,))
+    va, fa = _mesh_areas_dev(v, f, return_face_area=True)
+    return va.cpu().numpy(), fa.cpu().numpy()
 
 
 def _fit_circle_dev(pts: torch.Tensor, col_x: int, col_y: int) -> Tuple[np.ndarray, float]:

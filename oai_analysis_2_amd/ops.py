@@ -574,3 +574,35 @@ def masked_stats(values: torch.Tensor, mask: Optional[torch.Tensor] = None, perc
     _lib.call("oai_masked_stats", _ptr(values, n), _ptr(mask, n), n, (C.c_float * 2)(*(pct + [0.0, 0.0])[:2]), len(pct), ws.data_ptr(), ws.numel(),
               stats.data_ptr(), _lib.STREAM, device=values.device)
     return stats
+
+
+# ---- cartilage morphometry (include/oai_hip.h, "Cartilage morphometry"; csrc/morphometry.hip) ----------------------------------------------
+REGION_SLOTS = 12            # float64 per region of oai_region_stats
+MAX_REGIONS = 64
+
+
+def region_stats(values: torch.Tensor, weights: torch.Tensor, labels: Optional[torch.Tensor] = None, covered: Optional[torch.Tensor] = None,
+                 n_regions: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per region the twelve sums behind an area-weighted thickness summary: float32 ``values`` [n] and float64 ``weights`` [n] on the
+    device, int32 ``labels`` [n] (None: every element in region 0; a label outside [0, n_regions) belongs to no region) and a uint8 /
+    bool ``covered`` mask (None: every element).  An element is measured when it is covered and its value is finite.  Returns the float64
+    [n_regions, 12] DEVICE tensor: elements, covered, measured; sum w over all, covered, measured; sum w t, sum (w t) t, min t, max t,
+    sum t, sum t t over the measured elements.  An empty region reads 0, +inf for the minimum and -inf for the maximum.  fp64 sums in a
+    fixed order: bit-reproducible (include/oai_hip.h).  ``out``: written there instead of a new tensor.  Does not synchronise."""
+    values = _chk(values, "values").reshape(-1)
+    n, R = int(values.numel()), int(n_regions)
+    if not 1 <= R <= MAX_REGIONS:
+        raise ValueError(f"n_regions must be in [1, {MAX_REGIONS}], got {n_regions}")
+    weights = _chk(weights, "weights", torch.float64).reshape(-1)
+    if labels is not None:
+        labels = _chk(labels, "labels", torch.int32).reshape(-1)
+    if covered is not None:
+        covered = _chk(covered.view(torch.uint8) if covered.dtype == torch.bool else covered, "covered", torch.uint8).reshape(-1)
+    for name, t in (("weights", weights), ("labels", labels), ("covered", covered)):
+        if t is not None and (t.numel() != n or t.device != values.device):
+            raise ValueError(f"{name} must have the values' {n} elements and live on their GPU, got {t.numel()} on {t.device}")
+    stats = _out_slot(None if out is None else out.reshape(-1), R * REGION_SLOTS, torch.float64, values.device, "out")
+    ws = _lib.workspace("oai_region_stats", values.device, n, R)
+    _lib.call("oai_region_stats", _ptr(values, n), _ptr(weights, n), _ptr(labels, n), _ptr(covered, n), n, R, ws.data_ptr(), ws.numel(),
+              stats.data_ptr(), _lib.STREAM, device=values.device)
+    return stats.reshape(R, REGION_SLOTS)

@@ -106,13 +106,16 @@ class VolumePipeline:
 
     # ---- one volume, one GPU --------------------------------------------------------------------------------------------------
     def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None,
-            thickness_space: str = "atlas", qc=None, seg_qc: bool = False, thickness_qc=False) -> VolumeResult:
+            thickness_space: str = "atlas", qc=None, seg_qc: bool = False, thickness_qc=False, morphometry=False) -> VolumeResult:
         """``thickness``: a thickness.ThicknessAtlas -- the volume's cartilage thickness on the atlas inner vertices is measured from
         ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
         None (default): nothing more is launched.  ``thickness_space``: "atlas" (default) = the distance on the atlas grid, as the
         reference takes it; "patient" = on the meshes pushed through this volume's phi, in the patient's own millimetres
         (ThicknessAtlas.measure(..., phi=, image_A=)); "patient_grid" = native thickness: the mesh is taken from the patient-grid maps
         ``fc`` / ``tc`` and its inner vertices pulled to the atlas through the inverse of phi (ThicknessAtlas.measure(..., space="patient_grid")).
+        ``morphometry``: True or a coverage distance in mm, with ``thickness`` -- the knee's area-weighted regional thickness, covered and
+        denuded area in ``VolumeResult.thickness.morphometry`` (ThicknessAtlas.measure(..., morphometry=)).  False (default): nothing more is
+        launched.
         ``qc``: True, or a qc.QCReference (the atlas' own maps, for Dice) -- the registration QC record of the volume
         (qc.registration_qc: folds and det J of phi, volume scale, cartilage volume) in ``VolumeResult.qc``, computed where the thickness
         is: after the range check and the fp32 repeat.  A few small launches and one more synchronisation.  None (default): nothing more
@@ -139,10 +142,11 @@ class VolumePipeline:
                 res = self.rerun_f32(vol, meta_A)
         if thickness is not None:
             if thickness_space == "patient_grid":
-                res.thickness = thickness.measure(res.fc, res.tc, spacing_xyz=res.meta_A.spacing, phi=res.phi, image_A=res.meta_A, space="patient_grid")
+                res.thickness = thickness.measure(res.fc, res.tc, spacing_xyz=res.meta_A.spacing, phi=res.phi, image_A=res.meta_A, space="patient_grid",
+                                                  morphometry=morphometry)
             else:
                 push = dict(phi=res.phi, image_A=res.meta_A) if thickness_space == "patient" else {}
-                res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, **push)
+                res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, morphometry=morphometry, **push)
         if qc is not None:
             from .qc import registration_qc
             if qc is not True and getattr(qc, "image_net", None) is not None:      # the image similarity needs the image, not only the maps

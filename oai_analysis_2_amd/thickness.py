@@ -14,6 +14,10 @@ step behind ``VolumeResult.fc_atlas`` / ``tc_atlas``, plus a thickness IMAGE on 
                                             NATIVE thickness: the mesh is extracted, split and measured on the patient-grid maps
                                             themselves (no resample blur, the patient's own millimetres), then its inner vertices are
                                             pulled to the atlas through the inverse of phi (csrc/phi_inverse.hip) for map_attributes
+    atlas.measure(.., morphometry=True)     also the figures a study tabulates, per cartilage and region (KneeThickness.morphometry): bone
+                                            area, covered and denuded area, area-weighted mean thickness -- vertex areas of the atlas
+                                            inner mesh as weights, covered where map_attributes found a source point inside its radius
+                                            (csrc/morphometry.hip; morphometry_rows(knee) flattens a knee for a cohort table)
     atlas.image(thickness, kind)            per knee: one gather through the raster; the same pixel is the same atlas location in
                                             every knee, because map_attributes puts every knee on the atlas' vertices
 
@@ -30,13 +34,15 @@ The host-side rules of the raster are exact, without thresholds (fc_cut, fc_face
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
-from typing import Dict, Optional, Tuple, Union
+import math
+from dataclasses import asdict, dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import mesh_processing as mp
+from . import ops
 from .image import Image, as_image
 
 KINDS = ("FC", "TC")
@@ -92,6 +98,92 @@ def _frame_of(atlas_image) -> Tuple[np.ndarray, np.ndarray]:
     return img.origin.copy(), img.direction.copy()
 
 
+# ---- morphometry records (host arithmetic on the twelve slots of oai_region_stats) ------------------------------------------------------
+@dataclass
+class RegionMorphometry:
+    """The cartilage over one region of the atlas inner (subchondral bone) surface of one knee, derived on the host from the twelve fp64
+    slots of ``ops.region_stats`` (include/oai_hip.h, "Cartilage morphometry") with w = the vertex areas and t = the thickness vector:
+
+    ``area_mm2``               sum w over the region's vertices: the bone area (tAB)
+    ``covered_mm2``            sum w over its covered vertices (cAB); ``denuded_mm2`` = area - covered (dAB), ``denuded_fraction`` = denuded / area
+    ``mean_thickness_covered`` sum w t / sum w over the measured vertices (covered and finite): ThCcAB
+    ``mean_thickness_total``   sum w t / area: denuded bone counts as thickness 0 (ThCtAB)
+    ``std``                    area-weighted population standard deviation over the measured vertices; exactly 0 when min == max
+    ``min`` / ``max``          over the measured vertices
+    ``vertex_mean`` / ``vertex_std``  the unweighted figures over the measured vertices, for comparison: they weigh the surface by sampling density
+    ``n_vertices`` / ``n_covered`` / ``n_measured``  the three counts
+
+    ``space`` is the KneeThickness' ("atlas": mm2 on the atlas mesh; "patient" / "patient_grid": on the atlas mesh pushed through phi,
+    the patient's own mm2); ``cover`` the coverage rule: "footprint" (covered exactly where map_attributes took the mean: a source
+    point within the atlas' radius) or a distance in mm (covered where the closest source point is at most that far).  An empty
+    region, and a cartilage that could not be measured, have NaN figures; nothing raises."""
+    kind: str
+    region: str
+    space: str
+    cover: Union[str, float]
+    n_vertices: int
+    n_covered: int
+    n_measured: int
+    area_mm2: float
+    covered_mm2: float
+    denuded_mm2: float
+    denuded_fraction: float
+    mean_thickness_covered: float
+    mean_thickness_total: float
+    std: float
+    min: float
+    max: float
+    vertex_mean: float
+    vertex_std: float
+
+    @classmethod
+    def from_slots(cls, kind: str, region: str, slots, space: str = "atlas", cover: Union[str, float] = "footprint",
+                   failed: bool = False) -> "RegionMorphometry":
+        """``slots``: the region's row of ``ops.region_stats``.  ``failed``: the cartilage could not be measured -- the area and the vertex
+        count are kept, every other figure is NaN and the other counts 0."""
+        s = [float(v) for v in slots]
+        nan = float("nan")
+        area = s[3]
+        if failed:
+            return cls(kind, region, space, cover, int(s[0]), 0, 0, area, *([nan] * 10))
+        covered = s[4]
+        denuded = area - covered
+        mean_c = mean_t = std = lo = hi = v_mean = v_std = nan
+        if s[0] > 0:
+            mean_t = s[6] / area if area > 0 else nan
+        if s[2] > 0:
+            lo, hi = s[8], s[9]
+            mean_c = s[6] / s[5] if s[5] > 0 else nan
+            v_mean = s[10] / s[2]
+            if lo == hi:                                           # one value, whatever the sums rounded to
+                std = v_std = 0.0
+            else:
+                std = math.sqrt(max(s[7] / s[5] - mean_c * mean_c, 0.0)) if s[5] > 0 else nan
+                v_std = math.sqrt(max(s[11] / s[2] - v_mean * v_mean, 0.0))
+        return cls(kind, region, space, cover, int(s[0]), int(s[1]), int(s[2]), area, covered, denuded, denuded / area if area > 0 else nan,
+                   mean_c, mean_t, std, lo, hi, v_mean, v_std)
+
+
+@dataclass
+class CartilageMorphometry:
+    """One cartilage of one knee: ``all`` = the whole atlas inner surface, ``regions`` = one record per named region of
+    ``ThicknessAtlas.regions[kind]`` in label order (a vertex labelled -1 is in ``all`` only)."""
+    kind: str
+    all: RegionMorphometry
+    regions: Dict[str, RegionMorphometry] = field(default_factory=dict)
+
+    def __getitem__(self, region: str) -> RegionMorphometry:
+        return self.all if region == "all" else self.regions[region]
+
+
+def morphometry_rows(knee) -> List[dict]:
+    """A knee's morphometry as plain dicts, one per cartilage and region ("all" first): kind, region and every field of
+    RegionMorphometry.  ``knee``: a KneeThickness or its ``morphometry`` dict.  A cohort table is
+    ``[dict(row, knee=i) for i, k in knees for row in morphometry_rows(k)]``."""
+    morph = knee.morphometry if isinstance(knee, KneeThickness) else knee
+    return [asdict(r) for kind in KINDS if kind in morph for r in (morph[kind].all, *morph[kind].regions.values())]
+
+
 @dataclass
 class KneeThickness:
     """Cartilage thickness of one knee on the atlas inner vertices: float32 [n_fc], [n_tc] (numpy, or device tensors with
@@ -100,13 +192,17 @@ class KneeThickness:
     own millimetres; then ``outside[kind]`` counts the pushed vertices (inner and outer) that fell outside phi's buffer and moved by the
     affines alone.  "patient_grid" = distances taken on the mesh of the patient-grid maps, whose inner vertices were pulled to the atlas
     through the inverse of phi: ``outside[kind]`` counts the pulled vertices whose preimage lies outside phi's buffer, ``unconverged[kind]``
-    those the solver could not place (inside a fold of phi), which moved by the affines alone."""
+    those the solver could not place (inside a fold of phi), which moved by the affines alone.
+    ``morphometry`` ({"FC": CartilageMorphometry, "TC": ...}) and ``coverage`` (per cartilage a uint8 vector on the atlas vertices, 1 where
+    the vertex is covered under the rule used; numpy or device like the vectors) are filled by ``measure(..., morphometry=)`` only."""
     fc: Union[np.ndarray, torch.Tensor]
     tc: Union[np.ndarray, torch.Tensor]
     errors: Dict[str, str] = field(default_factory=dict)
     space: str = "atlas"
     outside: Dict[str, int] = field(default_factory=dict)
     unconverged: Dict[str, int] = field(default_factory=dict)
+    morphometry: Dict[str, CartilageMorphometry] = field(default_factory=dict)
+    coverage: Dict[str, Union[np.ndarray, torch.Tensor]] = field(default_factory=dict)
 
     def __getitem__(self, kind: str):
         return {"FC": self.fc, "TC": self.tc}[kind]
@@ -150,6 +246,9 @@ class ThicknessAtlas:
         self.frame: Dict[str, Optional[Tuple[np.ndarray, np.ndarray]]] = {}     # each map's (origin, direction); None: built from a bare tensor or array
         self.shape: Dict[str, Tuple[int, int, int]] = {}    # each map's (z, y, x) shape: the atlas grid, for "patient_grid"
         self.device = None
+        self.regions: Dict[str, Tuple[np.ndarray, Tuple[str, ...]]] = {}       # per cartilage (int32 label per inner vertex, region names): set_regions
+        self._region_labels: Dict[str, torch.Tensor] = {}                      # the labels on the device, and the atlas-space vertex areas:
+        self._area: Dict[str, torch.Tensor] = {}                               # both made at the first summary that needs them
         for kind, probmap in zip(KINDS, (atlas_fc, atlas_tc)):
             vol, sp, origin, direction = mp._probmap_dev(probmap, spacing_xyz)
             self.spacing[kind] = sp
@@ -165,6 +264,7 @@ class ThicknessAtlas:
                 raise ValueError(f"ThicknessAtlas: the atlas {kind} map has no inner surface")
             self._targets[kind] = iv
             self.inner[kind] = mp.Mesh(iv.cpu().numpy(), if_.cpu().numpy())
+            self._set_default_regions(kind)
             try:
                 self._project(kind)
             except ValueError as e:
@@ -191,15 +291,88 @@ class ThicknessAtlas:
     def n_points(self, kind: str) -> int:
         return len(self.inner[kind].verts)
 
+    # ---- regions of the morphometry ------------------------------------------------------------------------------------------------
+    def _set_default_regions(self, kind: str) -> None:
+        """No anatomy is invented: FC has no named region (the whole surface is reported as "all" in any case); TC has the two plateaus of
+        project_thickness's own split at z = 50 (a NaN z is in neither)."""
+        if kind == "FC":
+            self.set_regions(kind, np.full(self.n_points(kind), -1, np.int32), ())
+        else:
+            z = self.inner[kind].verts[:, 2]
+            self.set_regions(kind, np.where(z < _TC_SPLIT_Z, 0, np.where(z >= _TC_SPLIT_Z, 1, -1)), ("z_lt_50", "z_ge_50"))
+
+    def set_regions(self, kind: str, labels, names: Sequence[str]) -> None:
+        """The regions ``measure(..., morphometry=)`` reports for one cartilage besides "all": an integer label per atlas inner vertex
+        (vertex i of ``inner[kind]``; -1, or anything outside [0, len(names)): in no region) and the name of each label.  At most 64."""
+        if kind not in KINDS:
+            raise KeyError(f"kind must be one of {KINDS}, got {kind!r}")
+        labels, names = np.asarray(labels), tuple(str(n) for n in names)
+        if labels.shape != (self.n_points(kind),) or not np.issubdtype(labels.dtype, np.integer):
+            raise ValueError(f"set_regions: labels must be {self.n_points(kind)} integers (one per inner vertex of the atlas {kind} mesh), "
+                             f"got {labels.dtype} {labels.shape}")
+        if len(names) > ops.MAX_REGIONS or len(set(names)) != len(names) or "all" in names:
+            raise ValueError(f"set_regions: at most {ops.MAX_REGIONS} distinct names other than 'all', got {names}")
+        self.regions[kind] = (np.where((labels >= 0) & (labels < len(names)), labels, -1).astype(np.int32), names)
+        self._region_labels.pop(kind, None)
+
+    def regions_from_image(self, kind: str, label_image, names: Optional[Sequence[str]] = None) -> None:
+        """Regions painted on the 2-D thickness image: ``label_image`` is an [H, W] integer image on the grid of ``image`` (``image_shape``),
+        and vertex i takes the label of the pixel that holds ``uv[kind][i]`` (pixel (j, i) spans [lo + i step, lo + (i + 1) step) per
+        axis; the last pixel includes its upper edge).  Negative labels mean no region; ``names`` default to "label_0", "label_1", ..."""
+        r = self._raster(kind)
+        img = np.asarray(label_image)
+        if img.shape != self.image_shape or not np.issubdtype(img.dtype, np.integer):
+            raise ValueError(f"regions_from_image: label_image must be an integer image of shape {self.image_shape}, got {img.dtype} {img.shape}")
+        H, W = self.image_shape
+        uv = self.uv[kind]
+        fin = np.isfinite(uv).all(axis=1)
+        col = np.clip(np.floor((np.where(fin, uv[:, 0], r.lo[0]) - r.lo[0]) / r.step[0]), 0, W - 1).astype(np.int64)
+        row = np.clip(np.floor((np.where(fin, uv[:, 1], r.lo[1]) - r.lo[1]) / r.step[1]), 0, H - 1).astype(np.int64)
+        labels = np.where(fin, img[row, col], -1).astype(np.int64)
+        if names is None:
+            names = [f"label_{k}" for k in range(int(labels.max()) + 1)]
+        self.set_regions(kind, labels, names)
+
+    def _atlas_area(self, kind: str) -> torch.Tensor:
+        """The vertex areas of the atlas inner mesh (float64 [n] on the device), computed at the first summary that needs them."""
+        if kind not in self._area:
+            with torch.cuda.device(self.device):
+                self._area[kind] = mp._mesh_areas_dev(self._targets[kind], mp._dev(self.inner[kind].faces, np.int32, (3,), device=self.device))
+        return self._area[kind]
+
+    def _patient_area(self, kind: str, phi: torch.Tensor, image_A: Image, image_B: Image) -> torch.Tensor:
+        """The vertex areas of the atlas inner mesh with its vertices pushed through phi: the patient's own mm2."""
+        p2n, n2o = mp.mesh_point_affines(image_A, image_B, phi.shape[1:])
+        pushed = mp._transform_points_dev(self._targets[kind], phi, p2n, n2o)
+        return mp._mesh_areas_dev(pushed, mp._dev(self.inner[kind].faces, np.int32, (3,), device=self.device))
+
+    def _queue_stats(self, kind: str, vec: torch.Tensor, weights: torch.Tensor, covered: Optional[torch.Tensor], rows: torch.Tensor) -> None:
+        """Both region_stats calls of one cartilage into its rows of the knee's buffer: row 0 = the whole surface, then the named regions."""
+        ops.region_stats(vec, weights, None, covered, 1, out=rows[:1])
+        labels, names = self.regions[kind]
+        if names:
+            if kind not in self._region_labels:
+                self._region_labels[kind] = mp._dev(labels, np.int32, device=self.device)
+            ops.region_stats(vec, weights, self._region_labels[kind], covered, len(names), out=rows[1:])
+
+    def _map(self, kind: str, src: torch.Tensor, faces: torch.Tensor, dist: torch.Tensor, foot: Optional[dict]) -> torch.Tensor:
+        """map_attributes of one knee's inner vertices onto the atlas'; with ``foot`` also the footprint query on the same sources,
+        targets and grid (count, nearest squared distance)."""
+        lo, hi, _ = mp.mesh_grid_params_device(src, faces)
+        vec = mp._map_attributes_dev(src, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
+        if foot is not None:
+            foot[kind] = mp._point_footprint_dev(src, self._targets[kind], self.radius, grid=(lo, hi))[:2]
+        return vec
+
     # ---- per knee -----------------------------------------------------------------------------------------------------------------
-    def _measure_one(self, vol: torch.Tensor, spacing, kind: str) -> torch.Tensor:
+    def _measure_one(self, vol: torch.Tensor, spacing, kind: str, foot: Optional[dict] = None) -> torch.Tensor:
         iv, if_, dist = mp._thickness_inner_dev(vol, spacing, kind, self.min_cells[kind])
         if iv.shape[0] == 0:
             raise ValueError("map_attributes: the source mesh has no points")
-        lo, hi, _ = mp.mesh_grid_params_device(iv, if_)
-        return mp._map_attributes_dev(iv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
+        return self._map(kind, iv, if_, dist, foot)
 
-    def _measure_one_patient(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame) -> Tuple[torch.Tensor, int]:
+    def _measure_one_patient(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame,
+                             foot: Optional[dict] = None) -> Tuple[torch.Tensor, int]:
         """_measure_one with both sub-meshes pushed through phi before the distance: (vector, pushed vertices outside phi's buffer)."""
         sp = mp._resident_split(vol, spacing, kind, self.min_cells[kind])
         (iv, if_, _), (ov, of, _) = mp._sub_mesh_dev(sp, -1), mp._sub_mesh_dev(sp, 1)
@@ -209,11 +382,11 @@ class ThicknessAtlas:
         dist = mp._distance_dev(piv, pov, of)                   # (the grid parameters are the pushed outer mesh's)
         if iv.shape[0] == 0:
             raise ValueError("map_attributes: the source mesh has no points")
-        lo, hi, _ = mp.mesh_grid_params_device(iv, if_)         # sources stay in atlas space: vertex correspondence across knees
-        vec = mp._map_attributes_dev(iv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
+        vec = self._map(kind, iv, if_, dist, foot)              # sources stay in atlas space: vertex correspondence across knees
         return vec, sum(int(m.numel()) - int(np.count_nonzero(m.cpu().numpy())) for m in (in_i, in_o))
 
-    def _measure_one_patient_grid(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame) -> Tuple[torch.Tensor, int, int]:
+    def _measure_one_patient_grid(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame,
+                                  foot: Optional[dict] = None) -> Tuple[torch.Tensor, int, int]:
         """_measure_one on a patient-grid map, with the inner vertices pulled to the atlas through the inverse of phi as map_attributes'
         sources: (vector, pulled vertices whose preimage lies outside phi's buffer, vertices that did not converge)."""
         iv, if_, dist = mp._thickness_inner_dev(vol, spacing, kind, self.min_cells[kind])
@@ -222,13 +395,12 @@ class ThicknessAtlas:
         image_B = Image(np.broadcast_to(np.zeros((), np.float32), self.shape[kind]), self.spacing[kind], *frame)     # the atlas grid, no voxels
         p2n, n2o = mp.mesh_point_affines(image_A, image_B, phi.shape[1:], inverse=True)
         piv, status = mp._inverse_points_dev(iv, phi, p2n, n2o, return_status=True)
-        lo, hi, _ = mp.mesh_grid_params_device(piv, if_)
-        vec = mp._map_attributes_dev(piv, dist.reshape(1, -1), self._targets[kind], self.radius, grid=(lo, hi))[0]
+        vec = self._map(kind, piv, if_, dist, foot)
         counts = np.bincount(status.cpu().numpy(), minlength=3)
         return vec, int(counts[2]), int(counts[0])
 
     def measure(self, fc_atlas: torch.Tensor, tc_atlas: torch.Tensor, spacing_xyz=None, keep_on_device: bool = False, phi=None, image_A=None,
-                atlas_image=None, space: Optional[str] = None) -> KneeThickness:
+                atlas_image=None, space: Optional[str] = None, morphometry: Union[bool, float] = False) -> KneeThickness:
         """Thickness of one knee on the atlas inner vertices, from the two [z,y,x] float32 device tensors of a ``VolumeResult``
         (``spacing_xyz``: the atlas grid's, default the spacing of the map this atlas was built from).  Everything stays on the device, on the
         current stream, until the two vectors; only the inner -> outer distance is computed.  Per cartilage, bit for bit,
@@ -260,7 +432,23 @@ class ThicknessAtlas:
 
         A map with no region above ``min_cells``, or an FC slab of fewer than 2 faces, raises ValueError inside those functions: that
         is caught PER CARTILAGE, the vector filled with NaN and the message kept in ``errors`` -- one bad knee must not end a cohort.
-        Nothing else is caught."""
+        Nothing else is caught.
+
+        ``morphometry``: True, or a coverage distance in mm -- the knee's vectors reduced to the figures a study tabulates, in
+        ``KneeThickness.morphometry`` (per cartilage a CartilageMorphometry: the whole surface and every region of ``regions[kind]``), and the
+        coverage itself in ``KneeThickness.coverage``.  map_attributes never says "no cartilage here": a vertex with no source point
+        inside the radius takes the value of the closest one, however far.  So a footprint query (mesh_processing.point_footprint) runs on
+        the same sources, targets and grid as the map_attributes call beside it, and a vertex is COVERED exactly when map_attributes took
+        the mean there (True: a source point within ``radius``), or when the closest source point is at most ``morphometry`` mm away (a
+        float).  The weights are vertex areas (mesh_processing.mesh_areas) of the atlas inner mesh: in space "atlas" its own, computed
+        once at the first summary; in "patient" and "patient_grid" those of its vertices pushed through this knee's phi, the patient's
+        own mm2 as the thickness is the patient's mm.  The twelve-slot rows of both cartilages come down in one download.  A cartilage
+        in ``errors`` gets all-NaN figures and the atlas-space area.  "Denuded" here means: no inner-surface vertex of the warped patient
+        cartilage within the radius of the atlas bone surface -- that includes registration error; no pass / fail policy is built in,
+        and the figures are unpinned (the reference has no such step).  False (default): nothing more is launched, no bit changes."""
+        if morphometry is not False and morphometry is not True:
+            if isinstance(morphometry, bool) or not isinstance(morphometry, (int, float)) or not morphometry >= 0:
+                raise ValueError(f"morphometry must be False, True or a coverage distance >= 0 in mm, got {morphometry!r}")
         if space not in (None, "atlas", "patient", "patient_grid"):
             raise ValueError(f"space must be None, 'atlas', 'patient' or 'patient_grid', got {space!r}")
         if (phi is None) != (image_A is None):
@@ -281,6 +469,8 @@ class ThicknessAtlas:
             if phi.dim() != 4 or phi.shape[0] != 3:
                 raise ValueError(f"phi must be [3,D,H,W], got {tuple(phi.shape)}")
         out, errors, outside, unconverged = {}, {}, {}, {}
+        foot = None if morphometry is False else {}               # per cartilage (count, nearest squared distance) of the footprint query
+        weights = {}
         for kind, vol in zip(KINDS, (fc_atlas, tc_atlas)):
             default = image_A.spacing if native else self.spacing[kind]
             sp = default if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
@@ -288,17 +478,52 @@ class ThicknessAtlas:
                 vol_d = mp._probmap_dev(vol, sp)[0]
                 try:
                     if native:
-                        out[kind], outside[kind], unconverged[kind] = self._measure_one_patient_grid(vol_d, sp, kind, phi, image_A, frames[kind])
+                        out[kind], outside[kind], unconverged[kind] = self._measure_one_patient_grid(vol_d, sp, kind, phi, image_A, frames[kind], foot)
                     elif patient:
-                        out[kind], outside[kind] = self._measure_one_patient(vol_d, sp, kind, phi, image_A, frames[kind])
+                        out[kind], outside[kind] = self._measure_one_patient(vol_d, sp, kind, phi, image_A, frames[kind], foot)
                     else:
-                        out[kind] = self._measure_one(vol_d, sp, kind)
+                        out[kind] = self._measure_one(vol_d, sp, kind, foot)
                 except ValueError as e:
                     errors[kind] = str(e)
                     out[kind] = torch.full((self.n_points(kind),), float("nan"), dtype=torch.float32, device=self.device)
+                if foot is not None:
+                    if kind in errors or not patient:
+                        weights[kind] = self._atlas_area(kind)
+                    else:                                          # the atlas side of phi: the atlas grid ("patient": the grid of the maps, which is it)
+                        grid_B = (self.shape[kind], self.spacing[kind]) if native else (tuple(vol_d.shape), sp)
+                        image_B = Image(np.broadcast_to(np.zeros((), np.float32), grid_B[0]), grid_B[1], *frames[kind])
+                        weights[kind] = self._patient_area(kind, phi, image_A, image_B)
+        space = "patient_grid" if native else "patient" if patient else "atlas"
+        morph, coverage = {}, {}
+        if foot is not None:
+            morph, coverage = self._summarise(out, errors, foot, weights, space, "footprint" if morphometry is True else float(morphometry))
+            if not keep_on_device:
+                coverage = {k: v.cpu().numpy() for k, v in coverage.items()}
         if not keep_on_device:
             out = {k: v.cpu().numpy() for k, v in out.items()}
-        return KneeThickness(out["FC"], out["TC"], errors, "patient_grid" if native else "patient" if patient else "atlas", outside, unconverged)
+        return KneeThickness(out["FC"], out["TC"], errors, space, outside, unconverged, morph, coverage)
+
+    def _summarise(self, out, errors, foot, weights, space: str, cover) -> Tuple[Dict[str, CartilageMorphometry], Dict[str, torch.Tensor]]:
+        """The region sums of both cartilages queued into one buffer, one download, the records derived on the host."""
+        n_rows = {k: 1 + len(self.regions[k][1]) for k in KINDS}
+        with torch.cuda.device(self.device):
+            rows = torch.empty((sum(n_rows.values()), ops.REGION_SLOTS), dtype=torch.float64, device=self.device)
+            coverage, first = {}, 0
+            for kind in KINDS:
+                if kind in errors:
+                    coverage[kind] = torch.zeros(self.n_points(kind), dtype=torch.uint8, device=self.device)
+                else:
+                    count, d2 = foot[kind]
+                    coverage[kind] = (count > 0 if cover == "footprint" else d2 <= float(cover) * float(cover)).to(torch.uint8)
+                self._queue_stats(kind, out[kind], weights[kind], coverage[kind], rows[first:first + n_rows[kind]])
+                first += n_rows[kind]
+            host = rows.cpu().numpy()
+        morph, first = {}, 0
+        for kind in KINDS:
+            make = lambda name, row: RegionMorphometry.from_slots(kind, name, host[row], space, cover, failed=kind in errors)
+            morph[kind] = CartilageMorphometry(kind, make("all", first), {name: make(name, first + 1 + k) for k, name in enumerate(self.regions[kind][1])})
+            first += n_rows[kind]
+        return morph, coverage
 
     def _raster(self, kind: str) -> mp.ThicknessRaster:
         if kind not in KINDS:
