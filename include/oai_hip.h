@@ -252,6 +252,10 @@ int oai_unet_set_act_exponents(oai_unet* h, const int e[OAI_UNET_NUM_LAYERS]);
  *   "up_nbw" 0..64 (0)  bit-preserving (round 6): column blocks of 256 a workgroup of the k2s2 up-conv kernel (networks.py:56,59,62) walks one after the other over its
  *                       128 voxels -- the voxel table, the A-row plan and the workgroup launch are paid once per walk; 0 = as many as keep >= 16 workgroups per slot of
  *                       the chip, 1 = one column block per workgroup (rounds 1-5), n = at most n
+ *   "own_cover" 0|1 (1) bit-preserving: in oai_segment_tiles the trimmed decoder convs (dc8, dc7, dc5, dc4, dc2 on the Winograd kernel) place their blocks on every tile's
+ *                       OWN cover -- origin at the tile's own box corner (x rounded down to even), strips decided by its own remainders, one launch per block shape --
+ *                       and the k2s2 up-convs list the voxels of every tile's own input box; 0 = the cover / the voxels of the batch's union box (border tiles
+ *                       then pay for blocks that straddle the union's grid and for rows outside their box).  oai_unet_cover_stats counts both
  *   "dead_stores" 0|1 (1) the encoder does not write the part of a skip tensor that the trimmed decoder never reads
  *   "census" 0|1 (1)    the kernels record per-layer activation maxima (activation exponents, LOW bit of the range flag)
  *   "calibrated" 0      forget that the activation exponents were calibrated (they keep their values): oai_unet_get_act_exponents reports 0 until
@@ -335,6 +339,14 @@ double oai_unet_volume_flops(const oai_unet* h, int D, int H, int W, const int t
  * for splitting ONE volume's tiles over ranks (the reference's z-major order; oai_analysis_2_amd/parallel.py). */
 int oai_unet_tile_costs(const oai_unet* h, int D, int H, int W, const int tile_zyx[3], const int overlap_zyx[3],
                         const int crop_zyx[3], double* costs_host, int n_tiles);
+/* Host only, no device and no handle: what option "own_cover" changes for one layer of a volume segmented in batches of `batch` tiles.  `layer` is the
+ * schedule index of an own-cover conv layer (dc8 = 9, dc7 = 10, dc5 = 12, dc4 = 13, dc2 = 15) or of an up-conv (dc9 = 8, dc6 = 11, dc3 = 14).
+ * stats_host[0] = voxels the tiles need (up-convs: input voxels), [1] = executed with the union's placement (own_cover 0), [2] = executed with every tile's own
+ * cover (own_cover 1): a started conv block counts its live z slices x its y x x extent, a started up-conv workgroup its 128 rows.  Counted with the
+ * functions the launcher and the device table use.  pieces_host (optional, [n_tiles][4][6] ints, n_tiles = the volume's tile count): per tile the box
+ * (lo z y x, hi z y x) and the three pieces of its own cover -- main blocks, x strip, y strip; an up-conv's box is its one piece. */
+int oai_unet_cover_stats(int D, int H, int W, const int tile_zyx[3], const int overlap_zyx[3], const int crop_zyx[3], int batch, int layer,
+                         double stats_host[3], int* pieces_host, int n_tiles);
 /* Same as oai_unet_tile_flops, restricted to the layers the 3x3x3 implicit-GEMM kernel runs (ec1-ec7, dc8, dc7, dc5, dc4, dc2, dc1). */
 double oai_unet_tile_flops_conv3(const oai_unet* h, int td, int th, int tw, const int overlap_zyx[3], int trimmed);
 

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
@@ -67,6 +68,7 @@ struct oai_unet {
     int opt_wino_f32 = 1;               // option "winograd_f32"
     int opt_first_blocks = 24;          // option "first_blocks"
     int opt_up_nbw = 0;                 // option "up_nbw"
+    int opt_own_cover = 1;              // option "own_cover"
     int opt_shared = 1;                 // option "shared_enc"
     int opt_wide = 1;                   // option "wide"
     int opt_wino = 19;                  // option "winograd"
@@ -547,6 +549,10 @@ __host__ __device__ static void plan_regions(const int tile[3], const int keep_l
 }
 
 constexpr int kMaxTilesPerTable = 4096;
+// The layers whose blocks sit on every tile's OWN cover (option "own_cover"): the trimmed decoder convs.  After the 18 box rows of a tile the table holds
+// three more rows per such layer, one per block shape (tile_cover): rows 18 + 3 slot + shape, addressed like the layers' own.
+constexpr int kOwnLayers = 5, kTableRows = 18 + 3 * kOwnLayers;
+__host__ __device__ static inline int own_cover_slot(int k) { return k == DC8 ? 0 : k == DC7 ? 1 : k == DC5 ? 2 : k == DC4 ? 3 : k == DC2 ? 4 : -1; }
 enum Buf { B_E0, B_SYN0, B_P0, B_E2, B_SYN1, B_P1, B_E4, B_SYN2, B_P2, B_E6, B_E7, B_U9, B_D8, B_D7, B_U6, B_D5, B_D4, B_U3, B_D2, B_D1, B_COUNT };
 
 // The workspace of one pass of `batch` tiles: the per-tile box table of the current oai_segment_tiles call at the start, then the activation
@@ -561,7 +567,7 @@ static size_t carve_workspace(const oai_unet* h, int td, int th, int tw, int bat
         v2 * pc(DC8), v2 * pc(DC7), v1 * pc(DC6), v1 * pc(DC5), v1 * pc(DC4), v0 * pc(DC3),
         v0 * pc(DC2), v0 * pc(DC1)};
     Ws ws(base);
-    table = ws.take<int>((size_t)18 * kMaxTilesPerTable * 6);
+    table = ws.take<int>((size_t)kTableRows * kMaxTilesPerTable * 6);
     for (int i = 0; i < B_COUNT; ++i) buf[i] = ws.take<float>(sizes[i] * batch);
     return ws.off;
 }
@@ -595,10 +601,11 @@ static int launch_end(const oai_unet* h, hipStream_t st) {
 
 // XCD-aware dealing of a launch's logical block list (xcd_block_id in the kernels): the kernel gets the number of real blocks and the grid is rounded up
 // to whole deals of xcd_group blocks to each of the 8 XCDs.  Option "xcd_group" 0: plain launch order, the grid as it is.
-static unsigned xcd_deal(const oai_unet* h, unsigned grid, int& nblocks, int& xcd_group) {
+// `group` > 0: this launch's own granularity (balanced_xcd_group) instead of the option's.
+static unsigned xcd_deal(const oai_unet* h, unsigned grid, int& nblocks, int& xcd_group, int group = 0) {
     if (h->xcd_group <= 0) return grid;
-    nblocks = (int)grid; xcd_group = h->xcd_group;
-    const unsigned q = 8u * (unsigned)h->xcd_group;
+    nblocks = (int)grid; xcd_group = group > 0 ? group : h->xcd_group;
+    const unsigned q = 8u * (unsigned)xcd_group;
     return (grid + q - 1) / q * q;
 }
 
@@ -695,7 +702,7 @@ static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int
 // the last hr rows, main columns only.  A remainder of more than tall_y rows / tall_x columns is cheaper as one more row / column of main tiles.
 // hr == wr == 0: the main launch covers the whole box (also when the box is smaller than one main tile in y or x, or `no_strips`).
 struct Cover { Box main, xs, ys; int hr, wr; };
-static Cover cover_box(const Box& box, int xunit, int tall_y, int tall_x, bool no_strips) {
+__host__ __device__ static Cover cover_box(const Box& box, int xunit, int tall_y, int tall_x, bool no_strips) {
     const int ry = box.hi[1] - box.lo[1], rx = box.hi[2] - box.lo[2], ny = ry / 8, nx = rx / xunit;
     Cover c{box, box, box, ry - 8 * ny, rx - xunit * nx};
     if (no_strips || ny == 0 || nx == 0) c.hr = c.wr = 0;
@@ -707,6 +714,87 @@ static Cover cover_box(const Box& box, int xunit, int tall_y, int tall_x, bool n
     c.ys.lo[1] = c.main.hi[1]; c.ys.hi[2] = c.main.hi[2];
     return c;
 }
+// The cover of ONE tile's own box by the shapes of launch_conv3_wino (option "own_cover"): piece[0] main blocks of 8 x 8, piece[1] the x strip (16 x 4),
+// piece[2] the y strip (4 x 16) -- cover_box's rules on the box with its x start rounded down to even, which is where the tile's blocks start; the
+// pieces themselves keep the true start, are disjoint and make up the box; a piece may be empty.  Host (grid sizes, oai_unet_cover_stats) and device
+// (box_table_kernel) run this one function.
+__host__ __device__ static void tile_cover(const Box& box, Box piece[3]) {
+    Box even = box;
+    even.lo[2] &= ~1;
+    const Cover c = cover_box(even, 8, 4, 4, false);
+    piece[0] = c.main; piece[1] = c.xs; piece[2] = c.ys;
+    piece[0].lo[2] = piece[2].lo[2] = box.lo[2];
+}
+constexpr int kWinoTY[3] = {8, 16, 4}, kWinoTX[3] = {8, 4, 16};         // the block shapes of the three pieces (4 z slices each)
+__host__ __device__ static inline bool box_empty(const Box& b) { return b.hi[0] <= b.lo[0] || b.hi[1] <= b.lo[1] || b.hi[2] <= b.lo[2]; }
+// blocks of shape `s` that piece `p` of a tile takes from its own origin (0 0 0: empty piece)
+static void piece_blocks(const Box& p, int s, int nb[3]) {
+    nb[0] = nb[1] = nb[2] = 0;
+    if (box_empty(p)) return;
+    nb[0] = cdiv(p.hi[0] - p.lo[0], 4); nb[1] = cdiv(p.hi[1] - p.lo[1], kWinoTY[s]); nb[2] = cdiv(p.hi[2] - (p.lo[2] & ~1), kWinoTX[s]);
+}
+// what run_batch needs of the host's walk over a batch's tiles for option "own_cover": the grid of every shape of every own-cover layer (the largest
+// block counts of any tile, per axis), the largest input box of every up-conv in voxels, and every tile's own block counts [tile][slot][shape][3]
+// (all 0 for a dead tile), from which balanced_xcd_group deals a launch
+struct OwnPlan { int nb[kOwnLayers][3][3]; int up_nvox[18]; std::vector<int> tile_nb; };
+constexpr int kTileNbStride = kOwnLayers * 3 * 3;
+static void own_plan_add(OwnPlan& op, const Box need[18]) {
+    const size_t row = op.tile_nb.size();
+    op.tile_nb.resize(row + kTileNbStride, 0);
+    for (int k = 0; k < 18; ++k) {
+        if (box_empty(need[k])) continue;
+        if (layer_kind(k) == 2) {
+            int v = 1;
+            for (int i = 0; i < 3; ++i) v *= (need[k].hi[i] + 1) / 2 - need[k].lo[i] / 2;
+            op.up_nvox[k] = std::max(op.up_nvox[k], v);
+        }
+        const int slot = own_cover_slot(k);
+        if (slot < 0) continue;
+        Box piece[3];
+        tile_cover(need[k], piece);
+        for (int s = 0; s < 3; ++s) {
+            int nb[3];
+            piece_blocks(piece[s], s, nb);
+            for (int i = 0; i < 3; ++i) { op.nb[slot][s][i] = std::max(op.nb[slot][s][i], nb[i]); op.tile_nb[row + (slot * 3 + s) * 3 + i] = nb[i]; }
+        }
+    }
+}
+// one own-cover layer of one batch, as launch_conv3_wino takes it: the device rows of the three pieces, their grids and XCD dealing granularities (0: the option's)
+struct OwnCover { const int* rows[3]; int nb[3][3]; int xcd_group[3]; };
+
+// The XCD dealing of an own-cover launch.  Its grid is the LARGEST tile's, so a smaller tile's surplus workgroups return at once -- and xcd_block_id deals
+// logical ids, not work: with the option's 32 ids per deal and, e.g., 8 ids per tile (dc8's y strip of the 160-tile volume) XCD k gets the tiles of ONE y
+// row of the tile grid, four XCDs get every live block and four get none (kernel trace, profiles/own_cover.md: 2.22 ms, against 1.37 ms dealt 20 ids at a
+// time; dc7's y strip 0.83 -> 0.51 ms).  The host knows
+// every tile's live blocks (tile_nb: [tile] rows of kTileNbStride, this launch's three counts at the pointer), so it counts the live workgroups each XCD
+// would get for a few granularities and takes the one with the lightest heaviest XCD -- the option's own unless another is at least 2 % better.  Neighbours
+// in x and the cout blocks of one spatial block still share an L2 (>= 16 ids per deal).  Where a block runs does not change its bits.
+static int balanced_xcd_group(int configured, const int* tile_nb, int ntiles, const int nb[3], int ncb) {
+    if (configured <= 0) return configured;
+    auto heaviest = [&](int G) {
+        long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int t = 0; t < ntiles; ++t) {
+            const int* tn = tile_nb + (size_t)t * kTileNbStride;
+            for (int bz = 0; bz < tn[0]; ++bz)
+                for (int by = 0; by < tn[1]; ++by) {                            // the live ids of one block row are consecutive: bx and the cout block run fastest
+                    long long id = (((long long)t * nb[0] + bz) * nb[1] + by) * nb[2] * ncb, left = (long long)tn[2] * ncb;
+                    while (left > 0) {
+                        const long long g = id / G, take = std::min(left, (g + 1) * G - id);
+                        load[g & 7] += take; id += take; left -= take;
+                    }
+                }
+        }
+        return *std::max_element(load, load + 8);
+    };
+    int best = configured;
+    long long best_load = heaviest(configured);
+    for (int G = 30; G >= 16 && best_load > 0; G -= 2) {
+        const long long l = heaviest(G);
+        if (l * 100 < best_load * 98) { best = G; best_load = l; }
+    }
+    return best;
+}
+
 // the cover of the direct kernels (launch_conv3): main tiles of 8 x 16
 static Cover direct_cover(const oai_unet* h, const Box& box) { return cover_box(box, 16, 4, 8, h->variant == 2); }
 
@@ -786,17 +874,23 @@ static bool wino_m16_64(const oai_unet* h, const Layer& L, int cout) {
     return cout % 128 != 0 && (h->opt_wino & 32) && !(h->opt_wino & (4 | 8)) && L.panel_wino16 && wino_ws_fits();
 }
 
+// cout groups of 64 per workgroup of conv3_wino_sres for a layer and a block height
+static inline int wino_groups(const oai_unet* h, int cout, int TY) {
+    return (cout % 128 == 0 && !((h->opt_wino & 8) && TY != 4)) ? 2 : 1;      // (bit 3, A/B: the specialised 64-cout form for every layer)
+}
 // One launch of conv3_wino_sres (unet_wino.h) with blocks of 4 x TY x 2 NP over `box` (box.lo[2] even)
 template <int TY, int NP>
-static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, const Box& box, int ntiles, hipStream_t st) {
+static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, const Box& box, int ntiles, hipStream_t st, const int* own_nb = nullptr, int own_group = 0) {
     for (int i = 0; i < 3; ++i) { a.lo[i] = box.lo[i]; a.hi[i] = box.hi[i]; }
     if (box.hi[0] <= box.lo[0] || box.hi[1] <= box.lo[1] || box.hi[2] <= box.lo[2]) return OAI_OK;
-    const int ng = (a.Cout % 128 == 0 && !((h->opt_wino & 8) && TY != 4)) ? 2 : 1;      // (bit 3, A/B: the specialised 64-cout form for every layer)
+    a.own_origin = own_nb != nullptr;                                  // (own_nb: a.boxes = one piece of every tile's own cover, the grid counted from each row's start)
+    const int ng = wino_groups(h, a.Cout, TY);
     a.wpanel = L.panel_wino;
     a.ncb = a.Cout / (64 * ng);
     a.nbz = cdiv(box.hi[0] - box.lo[0], 4); a.nby = cdiv(box.hi[1] - box.lo[1], TY); a.nbx = cdiv(box.hi[2] - box.lo[2], 2 * NP);
+    if (own_nb) { a.nbz = own_nb[0]; a.nby = own_nb[1]; a.nbx = own_nb[2]; }
     unsigned grid = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-    grid = xcd_deal(h, grid, a.nblocks, a.xcd_group);
+    grid = xcd_deal(h, grid, a.nblocks, a.xcd_group, own_group);
     if (int rc = launch_begin(h, st)) return rc;
     if (ng == 2 && (h->opt_wino & 16) && L.panel_wino16) {              // the taps on v_mfma_f32_16x16x32_f16 (higher clock at the power wall)
         a.wpanel = L.panel_wino16;
@@ -819,7 +913,25 @@ static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, cons
 // 4 x 8 x 8, a y strip of 4 x 4 x 16 blocks for a remainder of <= 4 rows, an x strip of 4 x 16 x 4 blocks for a remainder of <= 4 columns
 // .  The box starts at an even x: an output's arithmetic depends on the
 // parity of its x only -- not on which launch or block computes it.
-static int launch_conv3_wino(const oai_unet* h, const Layer& L, const ConvArgs& a, Box box, int ntiles, hipStream_t st) {
+// `oc` (option "own_cover"; the trimmed decoder layers of oai_segment_tiles): the same three shapes, one launch each, over every tile's OWN cover
+// (tile_cover) instead of the cover of the batch's union box: a border tile's blocks start at its own corner, and its own remainders decide its
+// strips.  The launch box is the whole level; a shape that no tile of the batch needs is not launched.  Same bits.
+static int launch_conv3_wino(const oai_unet* h, const Layer& L, const ConvArgs& a, Box box, int ntiles, hipStream_t st, const OwnCover* oc = nullptr) {
+    if (oc && a.boxes) {
+        const int dims[3] = {a.D, a.H, a.W};
+        Box level;
+        full_box(level, dims);
+        ConvArgs b = a;
+        for (int s = 0; s < 3; ++s) {
+            if (oc->nb[s][0] == 0) continue;
+            b.boxes = oc->rows[s];
+            const int rc = s == 0 ? launch_wino_shape<8, 4>(h, L, b, level, ntiles, st, oc->nb[s], oc->xcd_group[s])
+                         : s == 1 ? launch_wino_shape<16, 2>(h, L, b, level, ntiles, st, oc->nb[s], oc->xcd_group[s])
+                                  : launch_wino_shape<4, 8>(h, L, b, level, ntiles, st, oc->nb[s], oc->xcd_group[s]);
+            if (rc) return rc;
+        }
+        return OAI_OK;
+    }
     box.lo[2] &= ~1;
     const Cover c = cover_box(box, 8, 4, 4, false);
     if (int rc = launch_wino_shape<8, 4>(h, L, a, c.main, ntiles, st)) return rc;
@@ -870,7 +982,7 @@ static int launch_conv3_wino_f32(const oai_unet* h, const Layer& L, const ConvAr
 static int launch_conv3(const oai_unet* h, const Layer& L, const float* s0, const float* s1, float* out,
                         const int dims[3], const Box& box, int ntiles, hipStream_t st, const int* boxes = nullptr,
                         float* pool_out = nullptr, const ConvArgs* head = nullptr, const TileSource* first = nullptr,
-                        const int* store_boxes = nullptr, const Scatter* sc = nullptr) {
+                        const int* store_boxes = nullptr, const Scatter* sc = nullptr, const OwnCover* oc = nullptr) {
     ConvArgs a;
     if (int rc = fill_conv_args(h, L, s0, s1, out, dims, boxes, pool_out, head, first, store_boxes, sc, a)) return rc;
     if (h->variant == 1) return launch_conv3_shape<2, 16, 16, 2, 4, 1>(h, a, box, ntiles, st);
@@ -879,7 +991,7 @@ static int launch_conv3(const oai_unet* h, const Layer& L, const float* s0, cons
         return launch_conv3_wino_f32(h, L, a, box, ntiles, st);
     if (h->sres && h->opt_wino && L.panel_wino && h->sres_mrep == 4 && !a.first_w && !a.head_w && !a.sc_boxes &&
         (!a.pool_out || (a.Cout % 128 == 0 && a.relu && wino_pool_box(box, dims))) && a.Cout % 64 == 0 && (h->opt_wino & (a.Cout % 128 == 0 ? 1 : 2)) && (a.Cout % 128 == 0 || (a.C0 + 15) / 16 + (a.C1 + 15) / 16 >= 8) && layer_bit(h, h->opt_wino_layers, L) && (size_t)dims[0] * dims[1] * dims[2] < (1u << 24))
-        return launch_conv3_wino(h, L, a, box, ntiles, st);
+        return launch_conv3_wino(h, L, a, box, ntiles, st, oc);
     const Cover c = direct_cover(h, box);
     if (int rc = launch_conv3_shape<4, 8, 16, 2, 4, 1>(h, a, c.main, ntiles, st)) return rc;
     if (c.wr) {
@@ -893,7 +1005,7 @@ static int launch_conv3(const oai_unet* h, const Layer& L, const float* s0, cons
 }
 
 static int launch_up(const oai_unet* h, const Layer& L, const float* src, float* out, const int in_dims[3], const Box& out_need,
-                     int ntiles, hipStream_t st, const int* in_boxes = nullptr) {
+                     int ntiles, hipStream_t st, const int* in_boxes = nullptr, int own_nvox = 0) {
     UpArgs a;
     a.boxes = in_boxes;
     a.range_flag = h->range_flag;
@@ -914,6 +1026,8 @@ static int launch_up(const oai_unet* h, const Layer& L, const float* src, float*
     a.nnb = cdiv(8 * L.cout, 256);
     a.relu = 1;
     if (split && h->sres) {
+        // option "own_cover": a tile's workgroups list the voxels of its own input box -- as many row blocks as the batch's largest tile box has
+        if (own_nvox > 0 && in_boxes) { a.own_box = 1; a.nmb = cdiv(own_nvox, 128); }
         // column blocks per workgroup (round 6): as many as leave >= 16 workgroups per workgroup slot of the chip (256 CUs x 2); narrow test networks
         // (the dword-store path of the kernel) keep one; option "up_nbw": 0 = this rule, n = at most n
         a.nbw = 1;
@@ -975,8 +1089,23 @@ struct SharedEnc {
 // `t0` of it.  For up-convs the table row holds the INPUT box (the halved output box).
 static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[18], int out_mode,
                      float* blocks_out, float* const buf[B_COUNT], hipStream_t st,
-                     const int* table = nullptr, int table_tiles = 0, int t0 = 0, const SharedEnc* se = nullptr) {
+                     const int* table = nullptr, int table_tiles = 0, int t0 = 0, const SharedEnc* se = nullptr, const OwnPlan* own = nullptr) {
     auto tb = [&](int layer) -> const int* { return table ? table + ((size_t)layer * table_tiles + t0) * 6 : nullptr; };
+    if (!table || !h->opt_own_cover) own = nullptr;
+    OwnCover ocs[kOwnLayers];
+    auto oc = [&](int layer) -> const OwnCover* {                     // the layer's own-cover rows and grids (option "own_cover"), or null
+        if (!own) return nullptr;
+        const int slot = own_cover_slot(layer);
+        for (int s = 0; s < 3; ++s) {
+            ocs[slot].rows[s] = tb(18 + 3 * slot + s);
+            for (int i = 0; i < 3; ++i) ocs[slot].nb[s][i] = own->nb[slot][s][i];
+            // (counted here, just before the layer's launches: under the device work queued so far)
+            const int ncb = h->L[layer].cout / (64 * wino_groups(h, h->L[layer].cout, kWinoTY[s]));
+            ocs[slot].xcd_group[s] = own->nb[slot][s][0] && ncb > 0 ? balanced_xcd_group(h->xcd_group, own->tile_nb.data() + (slot * 3 + s) * 3, n, own->nb[slot][s], ncb) : 0;
+        }
+        return &ocs[slot];
+    };
+    auto upv = [&](int layer) { return own ? own->up_nvox[layer] : 0; };
     const Layer* L = h->L;
     int d[4][3];
     for (int l = 0; l < 4; ++l) { d[l][0] = src.td >> l; d[l][1] = src.th >> l; d[l][2] = src.tw >> l; }
@@ -1101,14 +1230,14 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
     }
     RUN(launch_conv3(h, L[EC6], buf[B_P2], nullptr, buf[B_E6], d[3], need[EC6], n, st, tb(EC6)));
     RUN(launch_conv3(h, L[EC7], buf[B_E6], nullptr, buf[B_E7], d[3], need[EC7], n, st, tb(EC7)));
-    RUN(launch_up(h, L[DC9], buf[B_E7], buf[B_U9], d[3], need[DC9], n, st, tb(DC9)));
-    RUN(launch_conv3(h, L[DC8], buf[B_U9], buf[B_SYN2], buf[B_D8], d[2], need[DC8], n, st, tb(DC8)));   // cat(up, skip) :127
-    RUN(launch_conv3(h, L[DC7], buf[B_D8], nullptr, buf[B_D7], d[2], need[DC7], n, st, tb(DC7)));
-    RUN(launch_up(h, L[DC6], buf[B_D7], buf[B_U6], d[2], need[DC6], n, st, tb(DC6)));
-    RUN(launch_conv3(h, L[DC5], buf[B_U6], buf[B_SYN1], buf[B_D5], d[1], need[DC5], n, st, tb(DC5)));   // :134
-    RUN(launch_conv3(h, L[DC4], buf[B_D5], nullptr, buf[B_D4], d[1], need[DC4], n, st, tb(DC4)));
-    RUN(launch_up(h, L[DC3], buf[B_D4], buf[B_U3], d[1], need[DC3], n, st, tb(DC3)));
-    RUN(launch_conv3(h, L[DC2], buf[B_U3], buf[B_SYN0], buf[B_D2], d[0], need[DC2], n, st, tb(DC2)));   // :141
+    RUN(launch_up(h, L[DC9], buf[B_E7], buf[B_U9], d[3], need[DC9], n, st, tb(DC9), upv(DC9)));
+    RUN(launch_conv3(h, L[DC8], buf[B_U9], buf[B_SYN2], buf[B_D8], d[2], need[DC8], n, st, tb(DC8), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC8)));   // cat(up, skip) :127
+    RUN(launch_conv3(h, L[DC7], buf[B_D8], nullptr, buf[B_D7], d[2], need[DC7], n, st, tb(DC7), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC7)));
+    RUN(launch_up(h, L[DC6], buf[B_D7], buf[B_U6], d[2], need[DC6], n, st, tb(DC6), upv(DC6)));
+    RUN(launch_conv3(h, L[DC5], buf[B_U6], buf[B_SYN1], buf[B_D5], d[1], need[DC5], n, st, tb(DC5), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC5)));   // :134
+    RUN(launch_conv3(h, L[DC4], buf[B_D5], nullptr, buf[B_D4], d[1], need[DC4], n, st, tb(DC4), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC4)));
+    RUN(launch_up(h, L[DC3], buf[B_D4], buf[B_U3], d[1], need[DC3], n, st, tb(DC3), upv(DC3)));
+    RUN(launch_conv3(h, L[DC2], buf[B_U3], buf[B_SYN0], buf[B_D2], d[0], need[DC2], n, st, tb(DC2), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC2)));   // :141
     // dc0 + sigmoid/threshold + centre crop: blocks are laid out over the full kept centre.  In the split-resident path it rides
     // in dc1's epilogue (dc1's 64 output channels sit in one workgroup): no dc1 output round trip through HBM, no head launch.
     const int kz = src.vol ? src.oz : 0, ky = src.vol ? src.oy : 0, kx = src.vol ? src.ox : 0;
@@ -1349,6 +1478,9 @@ static const IntOption kIntOptions[] = {
     {"first_blocks", &oai_unet::opt_first_blocks, 1, 4096, "oai_unet_set_option: first_blocks must be in [1, 4096]"},
     // bit-preserving: column blocks per workgroup of the k2s2 up-conv kernel: 0 = as many as keep >= 16 workgroups per slot, 1 = one (rounds 1-5), n = at most n
     {"up_nbw", &oai_unet::opt_up_nbw, 0, 64, "oai_unet_set_option: up_nbw must be in [0, 64]"},
+    // bit-preserving: in oai_segment_tiles the trimmed decoder convs (dc8, dc7, dc5, dc4, dc2 on conv3_wino_sres) place their blocks on every tile's own cover
+    // (tile_cover) and the up-convs list every tile's own input voxels, instead of the cover / the voxels of the batch's union box; 0 = the union's (A/B)
+    {"own_cover", &oai_unet::opt_own_cover, 0, 1, "oai_unet_set_option: own_cover must be 0 or 1"},
     // ec0 computed inside ec1's halo staging when ec1 is one main-shape launch
     {"fuse_first", &oai_unet::fuse_first, 0, 1, "oai_unet_set_option: fuse_first must be 0 or 1"},
     // logical blocks per XCD deal; 0 = plain launch order
@@ -1631,7 +1763,7 @@ __host__ __device__ static void tile_regions(int t, const SegParams& p, Box need
 }
 
 // device table [layer][n][6] of tiles [t0, t0+n): computed on the device (no host copy: graph-capturable);
-// up-conv rows hold the INPUT box (the halved output box)
+// up-conv rows hold the INPUT box (the halved output box).  Behind the 18 layers: the three pieces of every own-cover layer's box (kTableRows)
 __global__ void box_table_kernel(SegParams p, int t0, int n, int* __restrict__ table) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
@@ -1643,6 +1775,14 @@ __global__ void box_table_kernel(SegParams p, int t0, int n, int* __restrict__ t
         for (int i = 0; i < 3; ++i) {
             row[i] = up ? need[k].lo[i] / 2 : need[k].lo[i];
             row[3 + i] = up ? (need[k].hi[i] + 1) / 2 : need[k].hi[i];
+        }
+        const int slot = own_cover_slot(k);
+        if (slot < 0) continue;
+        Box piece[3];
+        tile_cover(need[k], piece);
+        for (int s = 0; s < 3; ++s) {
+            int* prow = table + ((size_t)(18 + 3 * slot + s) * n + t) * 6;
+            for (int i = 0; i < 3; ++i) { prow[i] = piece[s].lo[i]; prow[3 + i] = piece[s].hi[i]; }
         }
     }
 }
@@ -1734,8 +1874,10 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
             // launch boxes of this batch = union over its tiles (host mirror of the same planning code)
             Box uni[18];
             for (int k = 0; k < 18; ++k) for (int i = 0; i < 3; ++i) { uni[k].lo[i] = 1 << 30; uni[k].hi[i] = 0; }
+            OwnPlan own{};
             for (int j = 0; j < n; ++j) {
                 tile_regions(t + j, sp, need);
+                own_plan_add(own, need);
                 for (int k = 0; k < 18; ++k) {
                     if (need[k].hi[0] <= need[k].lo[0]) continue;
                     for (int i = 0; i < 3; ++i) {
@@ -1747,7 +1889,7 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
             if (uni[0].hi[0] == 0) continue;                 // every tile of the batch is dead
             src.tile_begin = t;
             if (int rc = run_batch(h, src, n, uni, out_mode, blocks + (size_t)(t - tile_begin) * h->n_classes * bvox,
-                                   buf, st, table_dev, nc, t - c0, shared ? &se : nullptr)) return rc;
+                                   buf, st, table_dev, nc, t - c0, shared ? &se : nullptr, &own)) return rc;
         }
     }
     return OAI_OK;
@@ -1784,6 +1926,85 @@ int oai_unet_tile_costs(const oai_unet* h, int D, int H, int W, const int tile[3
         double f = 0.0;
         for (int k = 0; k < 18; ++k) f += layer_flops(h, k, need[k]);
         costs_host[t] = f;
+    }
+    return OAI_OK;
+}
+
+// blocks of TZ x TY x TX on the grid of `launch` that the kernels start for a tile with box `tb` (their start test), each at its live z slices x TY x TX
+static double started_block_voxels(const Box& launch, int TY, int TX, const Box& tb) {
+    if (box_empty(launch)) return 0.0;
+    Box b;
+    for (int i = 0; i < 3; ++i) { b.lo[i] = std::max(launch.lo[i], tb.lo[i]); b.hi[i] = std::min(launch.hi[i], tb.hi[i]); }
+    if (box_empty(b)) return 0.0;
+    auto started = [&](int i, int T) { int c = 0; for (int o = launch.lo[i]; o < launch.hi[i]; o += T) c += !(o >= b.hi[i] || o + T <= b.lo[i]); return c; };
+    const double yx = (double)started(1, TY) * started(2, TX) * TY * TX;
+    double v = 0.0;
+    for (int oz = launch.lo[0]; oz < launch.hi[0]; oz += 4) {
+        if (oz >= b.hi[0] || oz + 4 <= b.lo[0]) continue;
+        const int m_lo = std::max(0, b.lo[0] - oz), m_hi = std::min(4, b.hi[0] - oz);
+        v += (m_lo == 0 ? m_hi : 4) * yx;
+    }
+    return v;
+}
+
+int oai_unet_cover_stats(int D, int H, int W, const int tile[3], const int overlap[3], const int crop[3], int batch, int layer,
+                         double stats_host[3], int* pieces_host, int n_tiles) {
+    OAI_CHECK_ARG(tile && overlap && stats_host, "oai_unet_cover_stats: null pointer");
+    OAI_CHECK_ARG(batch > 0, "oai_unet_cover_stats: batch must be > 0");
+    const bool up = layer >= 0 && layer < 18 && layer_kind(layer) == 2;
+    OAI_CHECK_ARG(up || (layer >= 0 && layer < 18 && own_cover_slot(layer) >= 0), "oai_unet_cover_stats: layer %d is neither an own-cover conv layer nor an up-conv", layer);
+    if (int rc = check_tile(tile[0], tile[1], tile[2])) return rc;
+    SegGeom g;
+    if (int rc = seg_geometry(D, H, W, tile, overlap, g)) return rc;
+    OAI_CHECK_ARG(!pieces_host || n_tiles == g.ntiles, "oai_unet_cover_stats: the volume has %d tiles, not %d", g.ntiles, n_tiles);
+    const SegParams sp = seg_params(D, H, W, tile, overlap, crop, g, true);
+    auto in_box = [&](Box b) { if (up) for (int i = 0; i < 3; ++i) { b.lo[i] /= 2; b.hi[i] = (b.hi[i] + 1) / 2; } return b; };   // (up-convs: the input box, as the table rows)
+    auto voxels = [](const Box& b) { return box_empty(b) ? 0.0 : (double)(b.hi[0] - b.lo[0]) * (b.hi[1] - b.lo[1]) * (b.hi[2] - b.lo[2]); };
+    Box need[18];
+    stats_host[0] = stats_host[1] = stats_host[2] = 0.0;
+    for (int t0 = 0; t0 < g.ntiles; t0 += batch) {
+        const int n = std::min(batch, g.ntiles - t0);
+        Box uni;                                                             // the launch box of the batch, as oai_segment_tiles forms it
+        for (int i = 0; i < 3; ++i) { uni.lo[i] = 1 << 30; uni.hi[i] = 0; }
+        for (int j = 0; j < n; ++j) {
+            tile_regions(t0 + j, sp, need);
+            if (box_empty(need[layer])) continue;
+            for (int i = 0; i < 3; ++i) { uni.lo[i] = std::min(uni.lo[i], need[layer].lo[i]); uni.hi[i] = std::max(uni.hi[i], need[layer].hi[i]); }
+        }
+        Box launch = in_box(uni);
+        launch.lo[2] &= up ? ~0 : ~1;
+        const Cover c = cover_box(launch, 8, 4, 4, false);                   // (launch_conv3_wino)
+        for (int j = 0; j < n; ++j) {
+            tile_regions(t0 + j, sp, need);
+            const Box b = in_box(need[layer]);
+            Box piece[3] = {b, {}, {}};
+            stats_host[0] += voxels(b);
+            if (up) {                                                        // rows of 128 per started workgroup (upconv2_igemm_sres)
+                if (!box_empty(b) && !box_empty(launch)) {
+                    const int ryx = (launch.hi[1] - launch.lo[1]) * (launch.hi[2] - launch.lo[2]), nvox = (launch.hi[0] - launch.lo[0]) * ryx;
+                    for (int mb = 0; mb < cdiv(nvox, 128); ++mb) {
+                        const int zf = launch.lo[0] + (mb * 128) / ryx, zl = launch.lo[0] + std::min(mb * 128 + 127, nvox - 1) / ryx;
+                        if (!(zl < b.lo[0] || zf >= b.hi[0])) stats_host[1] += 128.0;
+                    }
+                    stats_host[2] += 128.0 * cdiv((int)voxels(b), 128);
+                }
+            } else {
+                stats_host[1] += started_block_voxels(c.main, 8, 8, b);
+                if (c.wr) stats_host[1] += started_block_voxels(c.xs, 16, 4, b);
+                if (c.hr) stats_host[1] += started_block_voxels(c.ys, 4, 16, b);
+                tile_cover(b, piece);
+                for (int s = 0; s < 3; ++s) {
+                    int nb[3];
+                    piece_blocks(piece[s], s, nb);
+                    if (nb[0]) stats_host[2] += (double)(piece[s].hi[0] - piece[s].lo[0]) * nb[1] * nb[2] * kWinoTY[s] * kWinoTX[s];   // (own origin: m_lo == 0, live slices add up to the extent)
+                }
+            }
+            if (pieces_host) {
+                int* row = pieces_host + (size_t)(t0 + j) * 24;
+                for (int i = 0; i < 3; ++i) { row[i] = b.lo[i]; row[3 + i] = b.hi[i]; }
+                for (int s = 0; s < 3; ++s) for (int i = 0; i < 3; ++i) { row[6 + 6 * s + i] = piece[s].lo[i]; row[9 + 6 * s + i] = piece[s].hi[i]; }
+            }
+        }
     }
     return OAI_OK;
 }

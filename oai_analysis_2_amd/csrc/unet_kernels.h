@@ -81,7 +81,9 @@ struct ConvArgs {
     unsigned* census = nullptr;              // split-resident kernels: 16 words of this layer's max |stored activation| (float bits, atomicMax;
                                              // see census_note).  Feeds the per-layer activation exponents and the low-range flag
     unsigned* first_census = nullptr;        // ... of the fused ec0 (instantiation FIRST)
-    int reserved0 = 0;                       // (keeps the kernel-argument layout of earlier rounds: the slot of the removed diagnostic switch word)
+    int own_origin = 0;                      // conv3_wino_sres, option "own_cover": 1 = `boxes` holds one piece of every tile's OWN cover (tile_cover in unet.hip) and a
+                                             // block sits at (bz, by, bx) from that row's lo (x rounded down to even), not from `lo` -- which is then the whole level.
+                                             // (In the slot of the removed diagnostic switch word: the kernel-argument layout of earlier rounds stays.)
     unsigned long long* stamps = nullptr;    // -DOAI_DIAG builds: device array of phase cycle sums (oai_diag_stamps); never set in production
     int nblocks = 0, xcd_group = 0;          // split-resident kernel: true workgroup count and the XCD dealing granularity (see xcd_block_id)
     int* reserved1 = nullptr;                // (keeps the kernel-argument layout of earlier rounds: the slot of the removed persistent form's block plan)
@@ -559,7 +561,8 @@ struct UpArgs {
     unsigned* census = nullptr;         // split-resident kernel: this layer's 16 census words (see ConvArgs::census)
     const unsigned char* zero = nullptr; // split-resident kernel: 64 zero bytes, the LDS-DMA source of rows / columns that do not exist
     unsigned long long* stamps = nullptr;   // -DOAI_DIAG builds: phase cycle sums of the up-conv kernel at stamps[16..31]
-    int reserved0 = 0;                  // (keeps the kernel-argument layout of earlier rounds)
+    int own_box = 0;                    // split-resident kernel, option "own_cover": 1 = a tile's workgroups list the voxels of its OWN box (`boxes` row), not of [lo, hi);
+                                        // nmb = row blocks of the batch's largest tile box (in the slot of a removed word: the kernel-argument layout of earlier rounds stays)
     int nblocks = 0, xcd_group = 0;     // split-resident kernel: true workgroup count and the XCD dealing granularity (xcd_block_id): the column
                                         // blocks of one row block read the same A rows and should meet in one L2
     int nbw = 1;                        // split-resident kernel: column blocks a workgroup walks one after the other (1 = one column block per workgroup)

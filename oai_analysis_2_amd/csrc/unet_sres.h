@@ -989,12 +989,16 @@ __global__ void __launch_bounds__(256, 2) upconv2_igemm_sres(const UpArgs a) {
     const int tile = id;
     const int N = 8 * a.Cout;
     const int row = lane & 31, half = lane >> 5;
-    const int rz = a.hi[0] - a.lo[0], ry = a.hi[1] - a.lo[1], rx = a.hi[2] - a.lo[2];
-    const int nvox = rz * ry * rx;
     int blo[3], bhi[3];
     if (!tile_box(a.boxes, tile, a.lo, a.hi, blo, bhi)) return;
+    // the voxels a tile's workgroups list, 128 each: those of the launch box -- or, own_box, of the tile's own box (no dead rows but the last workgroup's)
+    const bool own = a.own_box && a.boxes;
+    const int elo[3] = {own ? blo[0] : a.lo[0], own ? blo[1] : a.lo[1], own ? blo[2] : a.lo[2]};
+    const int rz = (own ? bhi[0] : a.hi[0]) - elo[0], ry = (own ? bhi[1] : a.hi[1]) - elo[1], rx = (own ? bhi[2] : a.hi[2]) - elo[2];
+    const int nvox = rz * ry * rx;
+    if (mb * 128 >= nvox) return;                                      // (own_box: nmb is the batch's largest tile's)
     {
-        const int zf = a.lo[0] + (mb * 128) / (rx * ry), zl = a.lo[0] + min(mb * 128 + 127, nvox - 1) / (rx * ry);
+        const int zf = elo[0] + (mb * 128) / (rx * ry), zl = elo[0] + min(mb * 128 + 127, nvox - 1) / (rx * ry);
         if (zl < blo[0] || zf >= bhi[0]) return;
     }
     const size_t plane = (size_t)a.D * a.H * a.W;
@@ -1007,7 +1011,7 @@ __global__ void __launch_bounds__(256, 2) upconv2_igemm_sres(const UpArgs a) {
         unsigned e = ~0u;
         if (v < nvox) {
             const int x = v % rx, t = v / rx, y = t % ry, z = t / ry;
-            const int iz = a.lo[0] + z, iy = a.lo[1] + y, ix = a.lo[2] + x;
+            const int iz = elo[0] + z, iy = elo[1] + y, ix = elo[2] + x;
             if (iz >= blo[0] && iz < bhi[0] && iy >= blo[1] && iy < bhi[1] && ix >= blo[2] && ix < bhi[2])
                 e = (unsigned)(((2 * iz) * Ho + 2 * iy) * Wo + 2 * ix);
         }
@@ -1023,7 +1027,7 @@ __global__ void __launch_bounds__(256, 2) upconv2_igemm_sres(const UpArgs a) {
         if (v < nvox) {
             const int x = v % rx, y = (v / rx) % ry, z = v / (rx * ry);
             asrc[it] = reinterpret_cast<const unsigned char*>(a.src) +
-                       srec(tile, nks, plane, 0, ((size_t)(a.lo[0] + z) * a.H + (a.lo[1] + y)) * a.W + (a.lo[2] + x)) + (((p & 3) ^ ((vl >> 2) & 3)) << 4);
+                       srec(tile, nks, plane, 0, ((size_t)(elo[0] + z) * a.H + (elo[1] + y)) * a.W + (elo[2] + x)) + (((p & 3) ^ ((vl >> 2) & 3)) << 4);
         } else asrc[it] = nullptr;
     }
     unsigned char* outb = reinterpret_cast<unsigned char*>(a.out) + srec(tile, nco, 8 * plane, 0, 0);      // chunk c of output voxel v at + (c * 8 plane + v) * 64

@@ -116,8 +116,9 @@ __global__ void __launch_bounds__(WS ? 512 : 256 * NG * MS, 1) conv3_wino_sres(c
     auto set_block = [&](int tile_, int bz, int by, int bx, int cbg) __attribute__((always_inline)) -> bool {
         tile = tile_;
         cb = cbg * NG + grp;                                      // this group's block of 64 couts
-        oz0 = a.lo[0] + bz * TZ; oy0 = a.lo[1] + by * TY; ox0 = a.lo[2] + bx * TX;      // a.lo[2] is even (host)
         if (!tile_box(a.boxes, tile, a.lo, a.hi, blo, bhi)) return false;
+        // the block grid starts at the launch box (a.lo[2] is even: host) -- or, own_origin, at this tile's own row: no block straddles the row's start
+        oz0 = (a.own_origin ? blo[0] : a.lo[0]) + bz * TZ; oy0 = (a.own_origin ? blo[1] : a.lo[1]) + by * TY; ox0 = (a.own_origin ? blo[2] & ~1 : a.lo[2]) + bx * TX;
         if (oz0 >= bhi[0] || oz0 + TZ <= blo[0] || oy0 >= bhi[1] || oy0 + TY <= blo[1] || ox0 >= bhi[2] || ox0 + TX <= blo[2]) return false;
         m_lo = max(0, blo[0] - oz0); m_hi = min(TZ, bhi[0] - oz0);
         s0 = reinterpret_cast<const unsigned char*>(a.src0) + srec(tile, nch0, plane, 0, 0);
