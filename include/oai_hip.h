@@ -953,6 +953,74 @@ size_t oai_region_stats_workspace_bytes(long long n, int n_regions);
 int oai_region_stats(const float* values_dev, const double* weights_dev, const int* labels_dev, const unsigned char* covered_dev, long long n,
                      int n_regions, void* workspace_dev, size_t workspace_bytes, double* out_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Mesh quality (csrc/mesh_quality.hip, tests/mesh_quality_ref.py): what can be asked of the surface that mesh-based thickness is measured
+ * on -- is it closed and consistently oriented, does it fold through itself, how long is the inner / outer interface of a split, what
+ * volume does it enclose.  The reference has no such step and VTK is absent: the definitions are this library's own, unpinned.  Every
+ * integer is exact and does not depend on the order atomics land in; fp64 without contraction, every sum in a stated order, no
+ * floating-point atomics: bit-reproducible.  verts_dev float32 [n_verts][3], faces_dev int32 [n_faces][3]; n_verts <= 2^31 - 2,
+ * n_faces <= 2^28; n_faces = 0 is allowed and yields zeros.  None of the three synchronises or reads anything back.
+ *
+ * A face with an index outside [0, n_verts) is an argument error that only the device can see: oai_mesh_topology counts such faces in
+ * record[14] (the caller refuses the mesh when it is not 0; mesh_processing.mesh_topology raises), and all three entry points read no
+ * vertex through such a face: it has no edges, no area and meets nothing.
+ *
+ * oai_mesh_topology.  A face with two equal indices is DEGENERATE: counted, no edges.  Half-edge (f, k) runs from faces[f][k] to
+ * faces[f][(k+1)%3]; an undirected edge is owned by its half-edge with the smallest 3 f + k.  With m the number of half-edges on an edge:
+ *   1 boundary (m = 1)   2 manifold (m = 2, opposite directions)   3 misoriented (m = 2, same direction)   4 non-manifold (m >= 3)
+ * side_dev (may be null): int8 per face, -1 / 0 / +1 as DeviceSplit.side; a manifold edge whose two faces have sides -1 and +1 is
+ * additionally an INTERFACE edge.  edge_class_dev: uint8 [n_faces][3], 0 where the half-edge is not the owner (or the face has no edges),
+ * otherwise the class, plus 16 on an interface edge.  record_dev: int64 [16] on the device --
+ *   [0] faces   [1] degenerate faces   [2] referenced vertices (named by a face that has edges)   [3] edges
+ *   [4] boundary   [5] misoriented   [6] non-manifold   [7] interface edges
+ *   [8] faces of side -1   [9] of side 0   [10] of side +1 (all faces; 0 0 0 without side_dev)
+ *   [11] Euler characteristic = [2] - [3] + ([0] - [1] - [14])
+ *   [12] boundary loops = connected components of the graph of boundary edges   [13] interface loops, likewise
+ *   [14] faces with an index outside the mesh   [15] manifold edges
+ * A CSR of half-edges keyed by the edge's smaller vertex (count, exclusive scan, scatter), then each half-edge walks its vertex's list:
+ * a vertex of valence v costs v^2 there, and nothing depends on the scatter order.  The loops are counted by one workgroup per edge set
+ * with the hook / jump rounds of oai_mesh_components, run to convergence inside the kernel.
+ *
+ * oai_mesh_geometry: edge_class_dev as written by oai_mesh_topology for the same faces.  With a, b, c the corners of face f widened to
+ * double and o = origin (host pointer, 3 doubles),
+ *   area  A    = oai_mesh_areas' face_area
+ *   l_k        = (dx*dx + dy*dy) + dz*dz of corner (k+1)%3 minus corner k;   edge length = sqrt(l_k)
+ *   q          = (6.928203230275509 * A) / ((l_0 + l_1) + l_2), 0 where the denominator is not > 0   (4 sqrt 3 A / sum l: 1 equilateral, 0 flat)
+ *   det(u,v,w) = (ux*(vy*wz - vz*wy) - uy*(vx*wz - vz*wx)) + uz*(vx*wy - vy*wx)   with u = a - o, v = b - o, w = c - o
+ * record_dev: float64 [16] on the device --
+ *   [0] surface area = sum A   [1] signed enclosed volume = (sum det) / 6.0 (positive for outward counter-clockwise faces of a closed mesh)
+ *   [2] boundary length   [3] interface length   [4] min   [5] max   [6] mean edge length over owned edges (sum / count)
+ *   [7] min   [8] max face area   [9] min q   [10] mean q (sum / faces)   [11] faces with q < q_min   [12] owned edges   [13] faces summed
+ * Sums run over faces in the fixed order of csrc/ordered_reduce.h with oai_region_stats' layout (thread g of max(1, min(2048,
+ * ceil(n_faces / 1024))) blocks of 256 takes the faces g, g + threads, ...; a face adds its figures, then its owned half-edges k = 0, 1, 2);
+ * minima and maxima are fmin / fmax.  Degenerate faces take part (area 0, q 0).  Figures over an empty set read 0.
+ *
+ * oai_mesh_self_intersections.  orient(a,b,c,d) = det(b - a, c - a, d - a) with the expansion above on the widened corners.  The edge
+ * pq PROPERLY PIERCES the triangle abc when orient(a,b,c,p) and orient(a,b,c,q) have strictly opposite signs and orient(p,q,a,b),
+ * orient(p,q,b,c), orient(p,q,c,a) are all > 0 or all < 0.  Faces f < g that share no vertex index INTERSECT when an edge (k, (k+1)%3) of
+ * one properly pierces the other.  Two limits follow: coplanar overlap and mere touching are not seen (strict signs), and neither is a fold
+ * between faces that share a vertex.  Broad phase: each face goes into every cell of the uniform grid (grid_lo, cell_size, grid_dims: host
+ * pointers; cell = floor((x - lo) / cell_size) clamped to the grid) that its bounding box spans -- count, scan, scatter -- and a pair is
+ * evaluated only in the cell that holds the lower corner of the two cell ranges' intersection, so once.  The result is the same for every
+ * valid grid.  The entry list lives in the workspace, sized by `capacity` entries: when the faces need more, nothing is tested, flag is
+ * all 0 and record[3] = 1.  flag_dev: uint8 [n_faces], 1 on a face of an intersecting pair.  record_dev: int64 [4] on the device --
+ *   [0] intersecting pairs   [1] flagged faces   [2] bin entries needed   [3] overflow
+ * ---------------------------------------------------------------------------------------- */
+/* 0 when n_verts is outside [0, 2^31 - 2] or n_faces outside [0, 2^28]. */
+size_t oai_mesh_topology_workspace_bytes(long long n_verts, long long n_faces);
+int oai_mesh_topology(const int* faces_dev, long long n_faces, long long n_verts, const signed char* side_dev, void* workspace_dev,
+                      size_t workspace_bytes, unsigned char* edge_class_dev, long long* record_dev, void* stream);
+/* 0 when n_faces is outside [0, 2^28]. */
+size_t oai_mesh_geometry_workspace_bytes(long long n_faces);
+int oai_mesh_geometry(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, const unsigned char* edge_class_dev,
+                      const double origin[3], double q_min, void* workspace_dev, size_t workspace_bytes, double* record_dev, void* stream);
+/* 0 when n_faces is outside [0, 2^28], an axis of the grid is < 1, it has more than 2^31 - 2 cells or capacity is outside [0, 2^31 - 2]. */
+size_t oai_mesh_self_intersections_workspace_bytes(long long n_faces, const int grid_dims[3], long long capacity);
+int oai_mesh_self_intersections(const float* verts_dev, long long n_verts, const int* faces_dev, long long n_faces, const double grid_lo[3],
+                                double cell_size, const int grid_dims[3], long long capacity, void* workspace_dev, size_t workspace_bytes,
+                                unsigned char* flag_dev, long long* record_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,7 +154,7 @@ def process_cohort(images: Sequence, atlas_image, worker: Optional[Worker] = Non
 
 
 def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, keep_on_device: bool = False,
-                     results_complete: bool = False, space: str = "atlas", morphometry=False) -> Iterator[Tuple[int, object]]:
+                     results_complete: bool = False, space: str = "atlas", morphometry=False, mesh_qc: bool = False) -> Iterator[Tuple[int, object]]:
     """(index, KneeThickness) for every (index, VolumeResult) of ``results`` whose ``fc_atlas`` / ``tc_atlas`` are on the device: the
     thickness stage of the reference's task graph (get_thickness x2, then the notebook's map_attributes) behind a cohort, a few hundred
     KB per knee instead of five tensors.
@@ -172,6 +172,8 @@ def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, kee
     space="patient_grid")); in both, a result without ``meta_A`` raises ValueError.
     ``morphometry``: True or a coverage distance in mm -- each knee's ``KneeThickness.morphometry`` and ``coverage`` as well
     (ThicknessAtlas.measure(..., morphometry=): area-weighted regional thickness, covered and denuded area).
+    ``mesh_qc``: True -- each knee's ``KneeThickness.mesh_qc`` as well (ThicknessAtlas.measure(..., mesh_qc=True): the qc.SplitQuality of
+    the mesh and split the thickness was measured on).
     At most two knees are in flight; results come in input order; the worker is gone when the generator is exhausted or closed.
     Measured (profiles/thickness_stage.md section 3): about nine tenths of the stage lie underneath the next volume, unless the runtime
     deals the worker's stream onto the compute stream's own hardware queue (one creation order in four), where it runs serially."""
@@ -201,9 +203,10 @@ def thickness_stream(results: Iterable[Tuple[int, object]], thickness_atlas, kee
                 if space == "patient_grid":
                     res.fc.record_stream(side[0])
                     res.tc.record_stream(side[0])
-                    knee = thickness_atlas.measure(res.fc, res.tc, keep_on_device=keep_on_device, space="patient_grid", morphometry=morphometry, **push)
+                    knee = thickness_atlas.measure(res.fc, res.tc, keep_on_device=keep_on_device, space="patient_grid", morphometry=morphometry,
+                                                   mesh_qc=mesh_qc, **push)
                 else:
-                    knee = thickness_atlas.measure(res.fc_atlas, res.tc_atlas, keep_on_device=keep_on_device, morphometry=morphometry, **push)
+                    knee = thickness_atlas.measure(res.fc_atlas, res.tc_atlas, keep_on_device=keep_on_device, morphometry=morphometry, mesh_qc=mesh_qc, **push)
                 if keep_on_device:
                     side[0].synchronize()                         # complete when handed over, like the input
                     knee.fc.record_stream(caller)
@@ -262,9 +265,9 @@ def thickness_qc_stream(results: Iterable[Tuple[int, object]], **kwargs) -> Iter
 
 
 def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None,
-                             space: str = "atlas", morphometry=False) -> Iterator[Tuple[int, object]]:
+                             space: str = "atlas", morphometry=False, mesh_qc: bool = False) -> Iterator[Tuple[int, object]]:
     """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the
     probability maps never leave the device.  ``space``: see thickness_stream ("patient": every knee through its own phi; "patient_grid":
-    native thickness on every knee's own grid); ``morphometry``: see there."""
+    native thickness on every knee's own grid); ``morphometry``, ``mesh_qc``: see there."""
     return thickness_stream(process_cohort(images, atlas_image, worker, keep_on_device=True), thickness_atlas, results_complete=True, space=space,
-                            morphometry=morphometry)
+                            morphometry=morphometry, mesh_qc=mesh_qc)

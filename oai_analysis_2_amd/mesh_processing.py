@@ -42,7 +42,8 @@ tests/thickness_image_ref.py -- and gathers per-point values through it; _map_at
 forms of map_attributes and of get_thickness_mesh's resident branch (inner mesh and inner -> outer distance only) that thickness.py chains
 without downloads.  mesh_areas (per-face and per-vertex area, csrc/morphometry.hip) and point_footprint (what map_attributes saw of the source points:
 the count inside the radius, the nearest distance and index) have no line in the reference either; thickness.py builds the per-knee morphometry on
-them.  There is no CPU fallback for the kernels.
+them.  mesh_topology, mesh_geometry and mesh_self_intersections (csrc/mesh_quality.hip) ask the questions of qc.mesh_quality about any mesh: edge
+classes and their counts, area / volume / triangle quality, faces that pass through each other; unpinned too.  There is no CPU fallback for the kernels.
 """
 from __future__ import annotations
 
@@ -601,7 +602,11 @@ def _thickness_inner_dev(vol: torch.Tensor, spacing_xyz, mesh_type: str, min_cel
     """The resident branch of get_thickness_mesh without its second distance and without downloads: (inner verts, inner faces,
     distance inner -> outer) as device tensors, the bits of ``get_thickness_mesh(..., on_device=True)[0]`` (a point's distance does not
     depend on the other direction having been computed).  Raises the same ValueError on a map without a large region."""
-    sp = _resident_split(vol, spacing_xyz, mesh_type, min_cells)
+    return _thickness_from_split(_resident_split(vol, spacing_xyz, mesh_type, min_cells))
+
+
+def _thickness_from_split(sp: DeviceSplit) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """_thickness_inner_dev from the split on: for a caller that also wants the split itself (the mesh QC of thickness.py)."""
     (iv, if_, _), (ov, of, _) = _sub_mesh_dev(sp, -1), _sub_mesh_dev(sp, 1)
     return iv, if_, _distance_dev(iv, ov, of)
 
@@ -823,6 +828,139 @@ def mesh_areas(mesh: Mesh) -> Tuple[np.ndarray, np.ndarray]:
     v, f = _dev(mesh.verts, np.float32, (3,)), _dev(mesh.faces, np.int32, (3,))
     va, fa = _mesh_areas_dev(v, f, return_face_area=True)
     return va.cpu().numpy(), fa.cpu().numpy()
+
+
+# ---- mesh QC: topology, geometry and self-intersections of a surface (csrc/mesh_quality.hip) ---------------------------------------------
+TOPOLOGY_FIELDS = ("faces", "degenerate_faces", "referenced_vertices", "edges", "boundary_edges", "misoriented_edges", "non_manifold_edges",
+                   "interface_edges", "faces_inner", "faces_unassigned", "faces_outer", "euler_characteristic", "boundary_loops", "interface_loops",
+                   "bad_faces", "manifold_edges")
+GEOMETRY_FIELDS = ("area", "signed_volume", "boundary_length", "interface_length", "min_edge", "max_edge", "mean_edge", "min_face_area",
+                   "max_face_area", "min_quality", "mean_quality", "low_quality_faces", "edges", "faces")
+INTERSECTION_FIELDS = ("pairs", "flagged_faces", "entries_needed", "overflow")
+TOPOLOGY_SLOTS, GEOMETRY_SLOTS, INTERSECTION_SLOTS = 16, 16, 4
+EDGE_BOUNDARY, EDGE_MANIFOLD, EDGE_MISORIENTED, EDGE_NON_MANIFOLD, EDGE_CLASS_MASK, EDGE_INTERFACE = 1, 2, 3, 4, 15, 16
+MAX_GRID_CELLS = 1 << 21         # cells of the self-intersection grid: the cell is enlarged until the grid has no more
+Q_MIN = 0.1                      # default of the low-quality count: a triangle with q < 0.1 is a sliver
+
+
+def _mesh_topology_dev(faces: torch.Tensor, n_verts: int, side: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """oai_mesh_topology on device tensors (faces int32 [m,3], side int8 [m] or None): (edge_class uint8 [m,3], record int64 [16]), both
+    on the device, nothing downloaded or checked -- record[14] counts the faces with an index outside the mesh."""
+    m, n = int(faces.shape[0]), int(n_verts)
+    if side is not None and (side.dtype != torch.int8 or side.numel() != m):
+        raise ValueError(f"side must be int8 with one entry per face ({m}), got {side.dtype} x {side.numel()}")
+    cls = torch.empty((m, 3), dtype=torch.uint8, device=faces.device)
+    rec = torch.empty(TOPOLOGY_SLOTS, dtype=torch.int64, device=faces.device) if out is None else out
+    ws = _lib.workspace("oai_mesh_topology", faces.device, n, m, pad=True)
+    _lib.call("oai_mesh_topology", ops._ptr(faces, m), m, n, ops._ptr(side, m), ws.data_ptr(), ws.numel(), ops._ptr(cls, m), rec.data_ptr(), _lib.STREAM,
+              device=faces.device)
+    return cls, rec
+
+
+def _mesh_geometry_dev(verts: torch.Tensor, faces: torch.Tensor, edge_class: torch.Tensor, origin=None, q_min: float = Q_MIN,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """oai_mesh_geometry on device tensors with the ``edge_class`` of _mesh_topology_dev: the float64 [16] record on the device.
+    ``origin``: the point the signed volume's tetrahedra are taken from (default (0, 0, 0); any point gives the same volume of a closed
+    mesh up to rounding)."""
+    n, m = int(verts.shape[0]), int(faces.shape[0])
+    o = (C.c_double * 3)(*([0.0, 0.0, 0.0] if origin is None else [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]))
+    rec = torch.empty(GEOMETRY_SLOTS, dtype=torch.float64, device=verts.device) if out is None else out
+    ws = _lib.workspace("oai_mesh_geometry", verts.device, m, pad=True)
+    _lib.call("oai_mesh_geometry", ops._ptr(verts, n), n, ops._ptr(faces, m), m, ops._ptr(edge_class, m), o, float(q_min), ws.data_ptr(), ws.numel(),
+              rec.data_ptr(), _lib.STREAM, device=verts.device)
+    return rec
+
+
+def _intersection_grid(lo: np.ndarray, hi: np.ndarray, cell: float) -> Tuple[float, np.ndarray]:
+    """(cell, dims) of the self-intersection grid over the bounds: the cell enlarged by quarters until there are at most MAX_GRID_CELLS."""
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("mesh_self_intersections: the mesh has non-finite vertices")
+    h = float(cell)
+    if not h > 0.0 or not np.isfinite(h):
+        raise ValueError(f"cell_size must be positive and finite, got {cell!r}")
+    while True:
+        dims = np.floor((hi - lo) / h).astype(np.int64) + 1
+        if int(dims.prod()) <= MAX_GRID_CELLS:
+            return h, dims
+        h *= 1.25
+
+
+def _mesh_self_intersections_dev(verts: torch.Tensor, faces: torch.Tensor, cell_size: Optional[float] = None, max_entries: Optional[int] = None,
+                                 out: Optional[torch.Tensor] = None):
+    """oai_mesh_self_intersections on device tensors: (flag uint8 [m], record int64 [4]) on the device; the record is not checked here
+    (record[3] = 1: the bin entries did not fit ``max_entries`` and nothing was tested).  The grid is derived from the mesh's bounds and
+    longest edge (mesh_grid_params_device: one 56-byte download).  ``cell_size`` None: a little over the longest edge, so a face's box
+    spans at most 2 cells per axis and the default ``max_entries`` = 8 per face cannot overflow."""
+    n, m = int(verts.shape[0]), int(faces.shape[0])
+    flag = torch.empty(m, dtype=torch.uint8, device=verts.device)
+    rec = torch.empty(INTERSECTION_SLOTS, dtype=torch.int64, device=verts.device) if out is None else out
+    if m == 0 or n == 0:
+        lo, h, dims = np.zeros(3), 1.0, np.ones(3, np.int64)
+    else:
+        lo, hi, edge = mesh_grid_params_device(verts, faces)
+        if np.isnan(edge):
+            raise ValueError(f"mesh_self_intersections: a face indexes outside the {n} vertices")
+        h, dims = _intersection_grid(lo, hi, max(float(edge) * 1.0001, 1e-30) if cell_size is None else cell_size)
+    cap = 8 * m if max_entries is None else int(max_entries)
+    gd = (C.c_int * 3)(*[int(x) for x in dims])
+    glo = (C.c_double * 3)(*[float(x) for x in lo])
+    ws = _lib.workspace("oai_mesh_self_intersections", verts.device, m, gd, cap, pad=True)
+    _lib.call("oai_mesh_self_intersections", ops._ptr(verts, n), n, ops._ptr(faces, m), m, glo, float(h), gd, cap, ws.data_ptr(), ws.numel(),
+              ops._ptr(flag, m), rec.data_ptr(), _lib.STREAM, device=verts.device)
+    return flag, rec
+
+
+def check_mesh_records(topology=None, intersections=None) -> None:
+    """What the device could only count: raise on a face index outside the mesh (topology record) and on an overflowed bin list."""
+    if topology is not None and int(topology[14]):
+        raise ValueError(f"mesh_topology: {int(topology[14])} face(s) index outside the vertices")
+    if intersections is not None and int(intersections[3]):
+        raise _lib.OaiError(f"mesh_self_intersections: the grid needs {int(intersections[2])} bin entries, more than max_entries: overflow "
+                            "(nothing was tested; pass a larger max_entries or cell_size)")
+
+
+def mesh_topology(mesh: Mesh, side=None) -> Tuple[Dict[str, int], np.ndarray]:
+    """Is this mesh closed and consistently oriented?  (record, edge_class): the counts named in TOPOLOGY_FIELDS and a uint8 [m,3] class
+    per half-edge -- 0 where it does not own its edge, else EDGE_BOUNDARY (the edge has one face), EDGE_MANIFOLD (two faces running
+    opposite ways), EDGE_MISORIENTED (two, the same way), EDGE_NON_MANIFOLD (three or more), plus EDGE_INTERFACE on a manifold edge
+    between a face of side -1 and one of side +1 (``side``: int8 per face, DeviceSplit.side).  Integer work on the GPU, exact and the same
+    on every run (include/oai_hip.h, "Mesh quality").  A face index outside the vertices raises ValueError."""
+    _lib.load()
+    f = _dev(mesh.faces, np.int32, (3,))
+    s = None if side is None else _dev(side, np.int8, device=f.device)
+    cls, rec = _mesh_topology_dev(f, len(mesh.verts), s)
+    rec = rec.cpu().numpy()
+    check_mesh_records(topology=rec)
+    return {k: int(rec[i]) for i, k in enumerate(TOPOLOGY_FIELDS)}, cls.cpu().numpy()
+
+
+def mesh_geometry(mesh: Mesh, side=None, origin=None, q_min: float = Q_MIN) -> Dict[str, float]:
+    """Area, signed enclosed volume ((sum of det(a-o, b-o, c-o)) / 6: positive for outward faces, meaningful on a closed mesh only),
+    boundary and interface length, edge-length, face-area and triangle-quality figures (GEOMETRY_FIELDS) in fp64, bit-reproducible.
+    The quality q = 4 sqrt(3) A / (sum of squared edge lengths) is 1 for an equilateral and 0 for a flat triangle; ``low_quality_faces``
+    counts q < ``q_min``.  ``side`` as in mesh_topology (for the interface length)."""
+    _lib.load()
+    v, f = _dev(mesh.verts, np.float32, (3,)), _dev(mesh.faces, np.int32, (3,))
+    s = None if side is None else _dev(side, np.int8, device=f.device)
+    cls, trec = _mesh_topology_dev(f, int(v.shape[0]), s)
+    rec = _mesh_geometry_dev(v, f, cls, origin, q_min).cpu().numpy()
+    check_mesh_records(topology=trec.cpu().numpy())
+    return {k: float(rec[i]) for i, k in enumerate(GEOMETRY_FIELDS)}
+
+
+def mesh_self_intersections(mesh: Mesh, cell_size: Optional[float] = None, max_entries: Optional[int] = None) -> Tuple[Dict[str, int], np.ndarray]:
+    """Does this mesh fold through itself?  (record, flag): INTERSECTION_FIELDS and a uint8 per face, 1 on every face of an intersecting
+    pair.  Two faces that share no vertex index intersect when an edge of one properly pierces the other (fp64 orientation determinants
+    with strict signs).  Two limits: coplanar overlap and mere touching are not counted, and a fold between faces that share a vertex is
+    not seen.  Faces are binned into a uniform grid first; the answer does not depend on it.  ``cell_size`` None: the mesh's longest
+    edge, which needs at most 8 bin entries per face; an explicit smaller cell takes its workspace from ``max_entries`` (default 8 per
+    face) and raises OaiError when the faces need more.  The grid has at most MAX_GRID_CELLS cells: the cell is enlarged when needed."""
+    _lib.load()
+    v, f = _dev(mesh.verts, np.float32, (3,)), _dev(mesh.faces, np.int32, (3,))
+    flag, rec = _mesh_self_intersections_dev(v, f, cell_size, max_entries)
+    rec = rec.cpu().numpy()
+    check_mesh_records(intersections=rec)
+    return {k: int(rec[i]) for i, k in enumerate(INTERSECTION_FIELDS)}, flag.cpu().numpy()
 
 
 def _fit_circle_dev(pts: torch.Tensor, col_x: int, col_y: int) -> Tuple[np.ndarray, float]:

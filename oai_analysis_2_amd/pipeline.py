@@ -106,7 +106,8 @@ class VolumePipeline:
 
     # ---- one volume, one GPU --------------------------------------------------------------------------------------------------
     def run(self, vol: torch.Tensor, meta_A: Image, check: bool = True, thickness: Optional["ThicknessAtlas"] = None,
-            thickness_space: str = "atlas", qc=None, seg_qc: bool = False, thickness_qc=False, morphometry=False) -> VolumeResult:
+            thickness_space: str = "atlas", qc=None, seg_qc: bool = False, thickness_qc=False, morphometry=False,
+            mesh_qc: bool = False) -> VolumeResult:
         """``thickness``: a thickness.ThicknessAtlas -- the volume's cartilage thickness on the atlas inner vertices is measured from
         ``fc_atlas`` / ``tc_atlas`` (after the range check and the fp32 repeat, if any) and returned in ``VolumeResult.thickness``.
         None (default): nothing more is launched.  ``thickness_space``: "atlas" (default) = the distance on the atlas grid, as the
@@ -116,6 +117,9 @@ class VolumePipeline:
         ``morphometry``: True or a coverage distance in mm, with ``thickness`` -- the knee's area-weighted regional thickness, covered and
         denuded area in ``VolumeResult.thickness.morphometry`` (ThicknessAtlas.measure(..., morphometry=)).  False (default): nothing more is
         launched.
+        ``mesh_qc``: True, with ``thickness`` -- per cartilage the qc.SplitQuality of the mesh and split the thickness was measured on
+        (topology, volume, self-intersections, the inner / outer interface) in ``VolumeResult.thickness.mesh_qc``
+        (ThicknessAtlas.measure(..., mesh_qc=True)).  False (default): nothing more is launched and no bit changes.
         ``qc``: True, or a qc.QCReference (the atlas' own maps, for Dice) -- the registration QC record of the volume
         (qc.registration_qc: folds and det J of phi, volume scale, cartilage volume) in ``VolumeResult.qc``, computed where the thickness
         is: after the range check and the fp32 repeat.  A few small launches and one more synchronisation.  None (default): nothing more
@@ -143,10 +147,11 @@ class VolumePipeline:
         if thickness is not None:
             if thickness_space == "patient_grid":
                 res.thickness = thickness.measure(res.fc, res.tc, spacing_xyz=res.meta_A.spacing, phi=res.phi, image_A=res.meta_A, space="patient_grid",
-                                                  morphometry=morphometry)
+                                                  morphometry=morphometry, mesh_qc=mesh_qc)
             else:
                 push = dict(phi=res.phi, image_A=res.meta_A) if thickness_space == "patient" else {}
-                res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, morphometry=morphometry, **push)
+                res.thickness = thickness.measure(res.fc_atlas, res.tc_atlas, spacing_xyz=self.atlas.spacing, morphometry=morphometry, mesh_qc=mesh_qc,
+                                                  **push)
         if qc is not None:
             from .qc import registration_qc
             if qc is not True and getattr(qc, "image_net", None) is not None:      # the image similarity needs the image, not only the maps

@@ -35,12 +35,18 @@ inner/outer split, no atlas, no phi: where the k-means split mislabels a patch t
 to itself or across the joint, and only a disagreement with this figure shows it.  ``VolumePipeline.run(thickness_qc=True)`` returns
 the records of the patient-grid maps in ``VolumeResult.thickness_qc``.
 
+``mesh_quality`` / ``split_quality`` check the stage in between: the surface that the mesh-based thickness is measured on, after marching
+cubes, the region filter, 150 smoothing sweeps and the k-means split -- is it closed and consistently oriented, does it fold through
+itself, how many pieces, how long and how ragged is the inner / outer interface, what volume does it enclose (``MeshQuality``,
+``SplitQuality``).  ``ThicknessAtlas.measure(..., mesh_qc=True)`` returns the records of the very split the distance was taken on in
+``KneeThickness.mesh_qc``.
+
 ``image_similarity`` gives the same record for any two images on one grid.  ``surface_distance`` and ``segmentation_qc`` give the same figures for any two masks, e.g. a segmentation against a manual one.  The
 surface rule (``A ^ binary_erosion(A)``, 6-connectivity) and the pooled percentile are MedPy's on scipy, checked against scipy on the
 CPU; ``assd`` is the mean over the pooled distances, and ``mean_ab`` / ``mean_ba`` are there for the mean of the two directed means.
 
-Kernels: csrc/phi_jacobian.hip, csrc/edt.hip, csrc/similarity.hip, csrc/components.hip, csrc/local_thickness.hip (include/oai_hip.h,
-"Registration QC", "Surface-distance QC", "Image-similarity QC", "Segmentation-shape QC", "Thickness QC").  ICON's LNCC form (a Gaussian window of 4 sigma + 1 samples, sigma = 4, eps = 1e-5) is restated as recalled and unpinned.  The fold definition is restated from ``flips`` as recalled
+Kernels: csrc/phi_jacobian.hip, csrc/edt.hip, csrc/similarity.hip, csrc/components.hip, csrc/local_thickness.hip, csrc/mesh_quality.hip
+(include/oai_hip.h, "Registration QC", "Surface-distance QC", "Image-similarity QC", "Segmentation-shape QC", "Thickness QC", "Mesh quality").  ICON's LNCC form (a Gaussian window of 4 sigma + 1 samples, sigma = 4, eps = 1e-5) is restated as recalled and unpinned.  The fold definition is restated from ``flips`` as recalled
 and unpinned, like the resample: icon_registration and ITK are absent.  No threshold and no pass / fail policy is built in: the
 record is data.
 """
@@ -707,3 +713,124 @@ def result_local_thicknesses(result, **kwargs) -> Dict[str, LocalThickness]:
     meta = getattr(result, "meta_A", None)
     spacing = None if meta is None else np.asarray(as_image(meta).spacing, np.float64)
     return local_thicknesses({kind: getattr(result, kind.lower()) for kind in KINDS}, spacing, **kwargs)
+
+
+# ---- mesh QC: the surface the mesh-based thickness is measured on (csrc/mesh_quality.hip) -------------------------------------------------
+@dataclass
+class MeshQuality:
+    """Topology and geometry of one triangle mesh (include/oai_hip.h, "Mesh quality").  ``topology``: the integer record of
+    mesh_processing.mesh_topology by name (mesh_processing.TOPOLOGY_FIELDS), ``geometry``: the fp64 record of mesh_geometry
+    (GEOMETRY_FIELDS; lengths, areas and the volume in the units of the vertices -- mm, mm2, mm3 for the pipeline's meshes).
+    ``components``: connected components of the face graph (mesh_components_device) less the vertices that no face with edges names;
+    exact on a mesh without degenerate faces.  ``intersecting_pairs`` /
+    ``intersecting_faces``: pairs of faces without a common vertex of which one's edge properly pierces the other, and the faces in such
+    pairs; None when not requested.  Folds between faces that share a vertex, coplanar overlap and mere touching are not seen."""
+    topology: Dict[str, int]
+    geometry: Dict[str, float]
+    components: int
+    intersecting_pairs: Optional[int] = None
+    intersecting_faces: Optional[int] = None
+
+    @property
+    def faces(self) -> int:
+        return self.topology["faces"]
+
+    @property
+    def closed(self) -> bool:
+        """A closed, consistently oriented 2-manifold as far as edges tell: no boundary, misoriented or non-manifold edge, no degenerate face."""
+        t = self.topology
+        return not (t["boundary_edges"] or t["misoriented_edges"] or t["non_manifold_edges"] or t["degenerate_faces"])
+
+    @property
+    def volume_mm3(self) -> Optional[float]:
+        """|signed volume| of a closed mesh; None when it is not closed (the sum then depends on the origin)."""
+        return abs(self.geometry["signed_volume"]) if self.closed else None
+
+    @property
+    def genus_sum(self) -> Optional[float]:
+        """The genera of a closed mesh's components added up: chi = 2 components - 2 genus_sum.  None when it is not closed."""
+        return (2 * self.components - self.topology["euler_characteristic"]) / 2 if self.closed else None
+
+
+@dataclass
+class SplitQuality:
+    """The mesh QC of an inner / outer split: the whole mesh (with the interface figures of its ``side``), each sub-mesh, and from the
+    whole mesh's record the faces in neither sub-mesh and the inner / outer interface -- its edges, its loops (connected components of
+    the interface-edge graph: one per sheet when the split is clean, more when a patch is mislabelled) and its length."""
+    whole: MeshQuality
+    inner: MeshQuality
+    outer: MeshQuality
+    unassigned_faces: int
+    interface_edges: int
+    interface_loops: int
+    interface_length: float
+
+
+_MQ_INTS = 16 + 4 + 1                     # topology record, intersection record, component roots
+_MQ_ROW = _MQ_INTS + 16                   # ... and the geometry record, its float64 bits carried as int64
+
+
+def _queue_mesh_quality(v: torch.Tensor, f: torch.Tensor, side: Optional[torch.Tensor], self_intersections: bool, q_min: float, row: torch.Tensor) -> None:
+    """Everything of one mesh into its int64 row of the caller's buffer, nothing downloaded besides what the grid parameters and the
+    component rounds read back."""
+    from . import mesh_processing as mp
+    n = int(v.shape[0])
+    cls, _ = mp._mesh_topology_dev(f, n, side, out=row[0:16])
+    if self_intersections:
+        mp._mesh_self_intersections_dev(v, f, out=row[16:20])
+    else:
+        row[16:20] = -1
+    if n:
+        label = mp.mesh_components_device(f, n)
+        roots = (label == torch.arange(n, dtype=torch.int32, device=v.device)).sum()
+        row[20] = torch.clamp(roots - (n - row[2]), min=0)       # a vertex that no face names is a component of its own there: left out
+    else:
+        row[20] = 0
+    geo = torch.empty(16, dtype=torch.float64, device=v.device)
+    mp._mesh_geometry_dev(v, f, cls, None, q_min, out=geo)
+    row[_MQ_INTS:] = geo.view(torch.int64)
+
+
+def _mesh_quality_from_host(row: np.ndarray) -> MeshQuality:
+    from . import mesh_processing as mp
+    si = None if row[16] < 0 else row[16:20]
+    mp.check_mesh_records(topology=row[0:16], intersections=si)
+    topo = {k: int(row[i]) for i, k in enumerate(mp.TOPOLOGY_FIELDS)}
+    g = row[_MQ_INTS:].view(np.float64)
+    geo = {k: float(g[i]) for i, k in enumerate(mp.GEOMETRY_FIELDS)}
+    return MeshQuality(topo, geo, int(row[20]), None if si is None else int(si[0]), None if si is None else int(si[1]))
+
+
+def _mesh_qualities(meshes, self_intersections: bool, q_min: float):
+    """[(verts, faces, side or None)] device tensors -> [MeshQuality]: all queued, one download."""
+    dev = meshes[0][0].device
+    with torch.cuda.device(dev):
+        rows = torch.zeros((len(meshes), _MQ_ROW), dtype=torch.int64, device=dev)
+        for (v, f, side), row in zip(meshes, rows):
+            _queue_mesh_quality(v, f, side, self_intersections, q_min, row)
+        host = rows.cpu().numpy()
+    return [_mesh_quality_from_host(r) for r in host]
+
+
+def mesh_quality(mesh, side=None, self_intersections: bool = True, q_min: float = 0.1) -> MeshQuality:
+    """The MeshQuality of a ``mesh_processing.Mesh``: is it closed and consistently oriented, how many pieces, what area and volume,
+    how ragged are its triangles, does it fold through itself.  ``side``: int8 per face (-1 / 0 / +1) for the interface figures.
+    No threshold
+    and no pass / fail policy.  Raises ValueError on a face index outside the vertices."""
+    from . import _lib, mesh_processing as mp
+    _lib.load()
+    v, f = mp._dev(mesh.verts, np.float32, (3,)), mp._dev(mesh.faces, np.int32, (3,))
+    s = None if side is None else mp._dev(side, np.int8, device=f.device)
+    return _mesh_qualities([(v, f, s)], self_intersections, q_min)[0]
+
+
+def split_quality(split, self_intersections: bool = True, q_min: float = 0.1) -> SplitQuality:
+    """The SplitQuality of a ``mesh_processing.DeviceSplit`` -- the mesh after marching cubes, the region filter, smoothing and the
+    k-means split, as the distance will see it: the whole mesh with ``split.side``, and each sub-mesh of ``_sub_mesh_dev``.  Queued on
+    the current stream, one download of the records at the end."""
+    from . import mesh_processing as mp
+    with torch.cuda.device(split.verts.device):
+        (iv, if_, _), (ov, of, _) = mp._sub_mesh_dev(split, -1), mp._sub_mesh_dev(split, 1)
+        whole, inner, outer = _mesh_qualities([(split.verts, split.faces, split.side), (iv, if_, None), (ov, of, None)], self_intersections, q_min)
+    return SplitQuality(whole, inner, outer, whole.topology["faces_unassigned"], whole.topology["interface_edges"],
+                        whole.topology["interface_loops"], whole.geometry["interface_length"])

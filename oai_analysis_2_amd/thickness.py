@@ -203,6 +203,7 @@ class KneeThickness:
     unconverged: Dict[str, int] = field(default_factory=dict)
     morphometry: Dict[str, CartilageMorphometry] = field(default_factory=dict)
     coverage: Dict[str, Union[np.ndarray, torch.Tensor]] = field(default_factory=dict)
+    mesh_qc: Optional[Dict[str, object]] = None          # {"FC": qc.SplitQuality, "TC": ...} with measure(..., mesh_qc=True)
 
     def __getitem__(self, kind: str):
         return {"FC": self.fc, "TC": self.tc}[kind]
@@ -365,16 +366,25 @@ class ThicknessAtlas:
         return vec
 
     # ---- per knee -----------------------------------------------------------------------------------------------------------------
-    def _measure_one(self, vol: torch.Tensor, spacing, kind: str, foot: Optional[dict] = None) -> torch.Tensor:
-        iv, if_, dist = mp._thickness_inner_dev(vol, spacing, kind, self.min_cells[kind])
+    def _split(self, vol: torch.Tensor, spacing, kind: str, mesh_qc: Optional[dict]):
+        """The resident split of one map, with its SplitQuality queued into ``mesh_qc`` when that is asked for: the record is of the very
+        split the distance is then taken on."""
+        sp = mp._resident_split(vol, spacing, kind, self.min_cells[kind])
+        if mesh_qc is not None:
+            from . import qc
+            mesh_qc[kind] = qc.split_quality(sp, **mesh_qc["options"])
+        return sp
+
+    def _measure_one(self, vol: torch.Tensor, spacing, kind: str, foot: Optional[dict] = None, mesh_qc: Optional[dict] = None) -> torch.Tensor:
+        iv, if_, dist = mp._thickness_from_split(self._split(vol, spacing, kind, mesh_qc))
         if iv.shape[0] == 0:
             raise ValueError("map_attributes: the source mesh has no points")
         return self._map(kind, iv, if_, dist, foot)
 
     def _measure_one_patient(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame,
-                             foot: Optional[dict] = None) -> Tuple[torch.Tensor, int]:
+                             foot: Optional[dict] = None, mesh_qc: Optional[dict] = None) -> Tuple[torch.Tensor, int]:
         """_measure_one with both sub-meshes pushed through phi before the distance: (vector, pushed vertices outside phi's buffer)."""
-        sp = mp._resident_split(vol, spacing, kind, self.min_cells[kind])
+        sp = self._split(vol, spacing, kind, mesh_qc)
         (iv, if_, _), (ov, of, _) = mp._sub_mesh_dev(sp, -1), mp._sub_mesh_dev(sp, 1)
         image_B = Image(np.broadcast_to(np.zeros((), np.float32), tuple(vol.shape)), spacing, *frame)       # the grid of the maps, no voxels
         p2n, n2o = mp.mesh_point_affines(image_A, image_B, phi.shape[1:])
@@ -386,10 +396,10 @@ class ThicknessAtlas:
         return vec, sum(int(m.numel()) - int(np.count_nonzero(m.cpu().numpy())) for m in (in_i, in_o))
 
     def _measure_one_patient_grid(self, vol: torch.Tensor, spacing, kind: str, phi: torch.Tensor, image_A: Image, frame,
-                                  foot: Optional[dict] = None) -> Tuple[torch.Tensor, int, int]:
+                                  foot: Optional[dict] = None, mesh_qc: Optional[dict] = None) -> Tuple[torch.Tensor, int, int]:
         """_measure_one on a patient-grid map, with the inner vertices pulled to the atlas through the inverse of phi as map_attributes'
         sources: (vector, pulled vertices whose preimage lies outside phi's buffer, vertices that did not converge)."""
-        iv, if_, dist = mp._thickness_inner_dev(vol, spacing, kind, self.min_cells[kind])
+        iv, if_, dist = mp._thickness_from_split(self._split(vol, spacing, kind, mesh_qc))
         if iv.shape[0] == 0:
             raise ValueError("map_attributes: the source mesh has no points")
         image_B = Image(np.broadcast_to(np.zeros((), np.float32), self.shape[kind]), self.spacing[kind], *frame)     # the atlas grid, no voxels
@@ -400,7 +410,7 @@ class ThicknessAtlas:
         return vec, int(counts[2]), int(counts[0])
 
     def measure(self, fc_atlas: torch.Tensor, tc_atlas: torch.Tensor, spacing_xyz=None, keep_on_device: bool = False, phi=None, image_A=None,
-                atlas_image=None, space: Optional[str] = None, morphometry: Union[bool, float] = False) -> KneeThickness:
+                atlas_image=None, space: Optional[str] = None, morphometry: Union[bool, float] = False, mesh_qc: bool = False) -> KneeThickness:
         """Thickness of one knee on the atlas inner vertices, from the two [z,y,x] float32 device tensors of a ``VolumeResult``
         (``spacing_xyz``: the atlas grid's, default the spacing of the map this atlas was built from).  Everything stays on the device, on the
         current stream, until the two vectors; only the inner -> outer distance is computed.  Per cartilage, bit for bit,
@@ -445,7 +455,13 @@ class ThicknessAtlas:
         own mm2 as the thickness is the patient's mm.  The twelve-slot rows of both cartilages come down in one download.  A cartilage
         in ``errors`` gets all-NaN figures and the atlas-space area.  "Denuded" here means: no inner-surface vertex of the warped patient
         cartilage within the radius of the atlas bone surface -- that includes registration error; no pass / fail policy is built in,
-        and the figures are unpinned (the reference has no such step).  False (default): nothing more is launched, no bit changes."""
+        and the figures are unpinned (the reference has no such step).  False (default): nothing more is launched, no bit changes.
+
+        ``mesh_qc``: True -- per cartilage a ``qc.SplitQuality`` in ``KneeThickness.mesh_qc``: topology, geometry and self-intersections
+        of the very mesh and split the distance was then taken on (in every space: the mesh of the maps given, before any push or pull
+        through phi), so that a thickness figure that is off can be traced to a surface that is open, folded, or split into patches.  A
+        cartilage in ``errors`` has no record.  No threshold and no pass / fail policy.  False (default): nothing more is launched, no
+        bit changes, and ``mesh_qc`` is None."""
         if morphometry is not False and morphometry is not True:
             if isinstance(morphometry, bool) or not isinstance(morphometry, (int, float)) or not morphometry >= 0:
                 raise ValueError(f"morphometry must be False, True or a coverage distance >= 0 in mm, got {morphometry!r}")
@@ -471,6 +487,7 @@ class ThicknessAtlas:
         out, errors, outside, unconverged = {}, {}, {}, {}
         foot = None if morphometry is False else {}               # per cartilage (count, nearest squared distance) of the footprint query
         weights = {}
+        mqc = {"options": {}} if mesh_qc else None
         for kind, vol in zip(KINDS, (fc_atlas, tc_atlas)):
             default = image_A.spacing if native else self.spacing[kind]
             sp = default if spacing_xyz is None else np.asarray(spacing_xyz, dtype=np.float64).reshape(3)
@@ -478,11 +495,11 @@ class ThicknessAtlas:
                 vol_d = mp._probmap_dev(vol, sp)[0]
                 try:
                     if native:
-                        out[kind], outside[kind], unconverged[kind] = self._measure_one_patient_grid(vol_d, sp, kind, phi, image_A, frames[kind], foot)
+                        out[kind], outside[kind], unconverged[kind] = self._measure_one_patient_grid(vol_d, sp, kind, phi, image_A, frames[kind], foot, mqc)
                     elif patient:
-                        out[kind], outside[kind] = self._measure_one_patient(vol_d, sp, kind, phi, image_A, frames[kind], foot)
+                        out[kind], outside[kind] = self._measure_one_patient(vol_d, sp, kind, phi, image_A, frames[kind], foot, mqc)
                     else:
-                        out[kind] = self._measure_one(vol_d, sp, kind, foot)
+                        out[kind] = self._measure_one(vol_d, sp, kind, foot, mqc)
                 except ValueError as e:
                     errors[kind] = str(e)
                     out[kind] = torch.full((self.n_points(kind),), float("nan"), dtype=torch.float32, device=self.device)
@@ -501,7 +518,9 @@ class ThicknessAtlas:
                 coverage = {k: v.cpu().numpy() for k, v in coverage.items()}
         if not keep_on_device:
             out = {k: v.cpu().numpy() for k, v in out.items()}
-        return KneeThickness(out["FC"], out["TC"], errors, space, outside, unconverged, morph, coverage)
+        if mqc is not None:
+            mqc = {k: mqc[k] for k in KINDS if k in mqc and k not in errors}
+        return KneeThickness(out["FC"], out["TC"], errors, space, outside, unconverged, morph, coverage, mqc)
 
     def _summarise(self, out, errors, foot, weights, space: str, cover) -> Tuple[Dict[str, CartilageMorphometry], Dict[str, torch.Tensor]]:
         """The region sums of both cartilages queued into one buffer, one download, the records derived on the host."""

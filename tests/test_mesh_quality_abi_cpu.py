@@ -1,0 +1,112 @@
+"""CPU: the mesh-QC entry points of the C ABI (include/oai_hip.h: oai_mesh_topology, oai_mesh_geometry, oai_mesh_self_intersections) are
+exported by the built library and refuse bad arguments with a status and a message -- no GPU is touched before the checks."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+from oai_analysis_2_amd import _lib, build
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("oai_mesh_topology_workspace_bytes", "oai_mesh_topology", "oai_mesh_geometry_workspace_bytes", "oai_mesh_geometry",
+       "oai_mesh_self_intersections_workspace_bytes", "oai_mesh_self_intersections")
+
+
+def test_the_header_declares_and_the_library_exports_the_new_symbols():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "oai_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
+    lib = C.CDLL(build.build_library(verbose=False))
+    for name in NEW:
+        assert name in declared, f"{name} is not declared in include/oai_hip.h"
+        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
+        assert name in _lib.SIGNATURES
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load()
+
+
+def _refused(lib, rc, *words):
+    msg = lib.oai_last_error()
+    assert rc != 0 and all(w in msg for w in words), (rc, msg)
+
+
+def test_mesh_topology_argument_checks(lib):
+    d = (C.c_float * 16)()                                            # a host buffer: every call below must fail before it is read
+    assert lib.oai_mesh_topology_workspace_bytes(-1, 4) == 0 and lib.oai_mesh_topology_workspace_bytes(4, -1) == 0
+    assert lib.oai_mesh_topology_workspace_bytes(4, (1 << 28) + 1) == 0
+    need = lib.oai_mesh_topology_workspace_bytes(100, 200)
+    assert need >= 3 * 101 * 4 + 9 * 200 * 4 + 2 * 100 * 4          # three vertex arrays, the CSR list and two edge lists, two parent arrays
+    assert lib.oai_mesh_topology_workspace_bytes(0, 0) > 0
+    _refused(lib, lib.oai_mesh_topology(None, 200, 100, None, d, need, d, d, None), b"oai_mesh_topology", b"null")
+    _refused(lib, lib.oai_mesh_topology(d, 200, 100, None, None, need, d, d, None), b"null")
+    _refused(lib, lib.oai_mesh_topology(d, 200, 100, None, d, need, None, d, None), b"null")
+    _refused(lib, lib.oai_mesh_topology(d, 200, 100, None, d, need, d, None, None), b"null")
+    _refused(lib, lib.oai_mesh_topology(d, -2, 100, None, d, need, d, d, None), b"oai_mesh_topology", b"-2")
+    _refused(lib, lib.oai_mesh_topology(d, 200, -1, None, d, need, d, d, None), b"oai_mesh_topology", b"-1")
+    _refused(lib, lib.oai_mesh_topology(d, 200, 100, None, d, 16, d, d, None), b"oai_mesh_topology", b"workspace")
+
+
+def test_mesh_geometry_argument_checks(lib):
+    d = (C.c_float * 16)()
+    o = (C.c_double * 3)(0, 0, 0)
+    assert lib.oai_mesh_geometry_workspace_bytes(-1) == 0 and lib.oai_mesh_geometry_workspace_bytes((1 << 28) + 1) == 0
+    assert lib.oai_mesh_geometry_workspace_bytes(0) >= 14 * 8
+    need = lib.oai_mesh_geometry_workspace_bytes(1024 * 257 + 3)
+    assert need >= 258 * 14 * 8
+    _refused(lib, lib.oai_mesh_geometry(None, 100, d, 200, d, o, 0.1, d, need, d, None), b"oai_mesh_geometry", b"null")
+    _refused(lib, lib.oai_mesh_geometry(d, 100, None, 200, d, o, 0.1, d, need, d, None), b"null")
+    _refused(lib, lib.oai_mesh_geometry(d, 100, d, 200, None, o, 0.1, d, need, d, None), b"null")
+    _refused(lib, lib.oai_mesh_geometry(d, 100, d, 200, d, None, 0.1, d, need, d, None), b"null")
+    _refused(lib, lib.oai_mesh_geometry(d, 100, d, 200, d, o, 0.1, None, need, d, None), b"null")
+    _refused(lib, lib.oai_mesh_geometry(d, 100, d, 200, d, o, 0.1, d, need, None, None), b"null")
+    _refused(lib, lib.oai_mesh_geometry(d, -1, d, 200, d, o, 0.1, d, need, d, None), b"oai_mesh_geometry", b"-1")
+    _refused(lib, lib.oai_mesh_geometry(d, 100, d, -2, d, o, 0.1, d, need, d, None), b"oai_mesh_geometry", b"-2")
+    _refused(lib, lib.oai_mesh_geometry(d, 100, d, 1024 * 257 + 3, d, o, 0.1, d, 16, d, None), b"oai_mesh_geometry", b"workspace")
+
+
+def test_mesh_self_intersections_argument_checks(lib):
+    d = (C.c_float * 16)()
+    lo, dims = (C.c_double * 3)(0, 0, 0), (C.c_int * 3)(4, 4, 4)
+    wsb = lib.oai_mesh_self_intersections_workspace_bytes
+    assert wsb(-1, dims, 100) == 0 and wsb((1 << 28) + 1, dims, 100) == 0 and wsb(10, dims, -1) == 0 and wsb(10, dims, 1 << 31) == 0
+    assert wsb(10, (C.c_int * 3)(4, 0, 4), 100) == 0 and wsb(10, (C.c_int * 3)(2048, 2048, 2048), 100) == 0 and wsb(10, None, 100) == 0
+    need = wsb(200, dims, 1600)
+    assert need >= 6 * 200 * 4 + 2 * 65 * 4 + 1600 * 4                # the cell ranges, the cell counts and starts, the entry list
+    big = 1 << 20
+    call = lib.oai_mesh_self_intersections
+    _refused(lib, call(None, 100, d, 200, lo, 1.0, dims, 1600, d, big, d, d, None), b"oai_mesh_self_intersections", b"null")
+    _refused(lib, call(d, 100, None, 200, lo, 1.0, dims, 1600, d, big, d, d, None), b"null")
+    _refused(lib, call(d, 100, d, 200, None, 1.0, dims, 1600, d, big, d, d, None), b"null")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, None, 1600, d, big, d, d, None), b"null")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, dims, 1600, None, big, d, d, None), b"null")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, dims, 1600, d, big, None, d, None), b"null")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, dims, 1600, d, big, d, None, None), b"null")
+    _refused(lib, call(d, -1, d, 200, lo, 1.0, dims, 1600, d, big, d, d, None), b"oai_mesh_self_intersections", b"-1")
+    _refused(lib, call(d, 100, d, -2, lo, 1.0, dims, 1600, d, big, d, d, None), b"oai_mesh_self_intersections", b"-2")
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        _refused(lib, call(d, 100, d, 200, lo, bad, dims, 1600, d, big, d, d, None), b"oai_mesh_self_intersections", b"cell_size")
+    _refused(lib, call(d, 100, d, 200, (C.c_double * 3)(0, float("nan"), 0), 1.0, dims, 1600, d, big, d, d, None), b"grid_lo")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, (C.c_int * 3)(4, 0, 4), 1600, d, big, d, d, None), b"empty grid")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, (C.c_int * 3)(2048, 2048, 2048), 1600, d, big, d, d, None), b"cells")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, dims, -5, d, big, d, d, None), b"capacity", b"-5")
+    _refused(lib, call(d, 100, d, 200, lo, 1.0, dims, 1600, d, 16, d, d, None), b"oai_mesh_self_intersections", b"workspace")
+
+
+def test_the_python_wrappers_refuse_before_the_library():
+    import numpy as np
+    from oai_analysis_2_amd import mesh_processing as mp
+    lo, hi = np.zeros(3), np.ones(3)
+    for bad in (0.0, -2.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="cell_size"):
+            mp._intersection_grid(lo, hi, bad)
+    with pytest.raises(ValueError, match="non-finite"):
+        mp._intersection_grid(lo, np.array([1.0, np.nan, 1.0]), 0.5)
+    h, dims = mp._intersection_grid(lo, hi * 1000.0, 1.0)             # 1001^3 cells would be too many: the cell grows until the grid fits
+    assert h > 1.0 and int(dims.prod()) <= mp.MAX_GRID_CELLS and (dims == np.floor(1000.0 / h) + 1).all()
+    h, dims = mp._intersection_grid(lo, hi, 0.25)
+    assert h == 0.25 and dims.tolist() == [5, 5, 5]
+    assert len(mp.TOPOLOGY_FIELDS) == mp.TOPOLOGY_SLOTS and len(mp.INTERSECTION_FIELDS) == mp.INTERSECTION_SLOTS
+    assert len(mp.GEOMETRY_FIELDS) <= mp.GEOMETRY_SLOTS
