@@ -1021,6 +1021,77 @@ int oai_mesh_self_intersections(const float* verts_dev, long long n_verts, const
                                 double cell_size, const int grid_dims[3], long long capacity, void* workspace_dev, size_t workspace_bytes,
                                 unsigned char* flag_dev, long long* record_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Cohort statistics (csrc/group_stats.hip, tests/group_stats_ref.py): permutation tests on N per-knee vectors that share the atlas
+ * inner vertices -- where do two groups of knees differ, where does a follow-up differ from baseline, with a family-wise error that
+ * holds over the surface.  The reference has no such step: the definitions are this library's own, pinned by the numpy restatement and
+ * scipy.  fp64 without contraction; EVERY SUM OVER KNEES RUNS IN ASCENDING KNEE INDEX WITH ONE ACCUMULATOR that starts at +0.0, and a
+ * knee that does not take part adds +0.0; no floating-point atomics; counts are integers: bit-reproducible.  None of the four
+ * synchronises or reads anything back.  2 <= n_knees <= 2^24, 1 <= n_verts <= 2^31 - 2, at most 2^20 rows per call.
+ *
+ * Layout.  y_dev float32 [n_knees][n_verts], knee-major.  mask_dev uint8 [n_knees][n_verts], non-zero = this knee has a value at this
+ * vertex; may be null: every entry is valid.  bits_dev uint32 [P][ceil(n_knees / 32)]: knee i of row p is bit i % 32 of word i / 32.
+ * Row 0 is the observed labelling by convention: oai_permutation_reduce treats the batch with p0 = 0 as the one that holds it.
+ *
+ * oai_group_prepare.  With m_i the mask and y_i = (double)y[i][v] where m_i, else 0.0 -- per vertex v, i = 0 .. n_knees - 1:
+ *   n    = sum m_i                 mean = (sum y_i) / (double)n                   (n = 0: NaN)
+ *   d_i  = y_i - mean where m_i, else 0.0
+ *   c_i  = d_i when centre = 1 (two-sample: centring does not change the statistic under permutation and keeps Q - S*S/n well
+ *          conditioned), y_i when centre = 0 (one-sample: the values are paired differences and their sign matters)
+ *   q_i  = c_i * c_i               S = sum c_i      Q = sum q_i
+ *   std  = sqrt((sum d_i * d_i) / (double)(n - 1)), NaN when n < 2: the descriptive figure, centred in both cases
+ * A NaN under a non-zero mask byte propagates.  The results fill the PREPARED BLOCK, workspace_dev, front to back, each array starting
+ * on the next multiple of 256 bytes: C float64 [n_knees][n_verts], Qm likewise, S, Q, mean, std float64 [n_verts], n int32 [n_verts].
+ * oai_permutation_t reads the block; it stays valid for as long as the caller keeps it.
+ *
+ * oai_permutation_t: rows [p0, p1) of bits_dev -> the t tile, float64 [p1 - p0][n_verts] at the start of workspace_dev.  b_i = bit i.
+ *   OAI_STATS_TWO_SAMPLE (prepared with centre = 1; bit = the knee is in group 1; mask_dev as given to oai_group_prepare):
+ *     n1 = sum b_i & m_i           S1 = sum (b_i ? c_i : 0.0)     Q1 = sum (b_i ? q_i : 0.0)
+ *     n2 = n - n1;  S2 = S - S1;  Q2 = Q - Q1
+ *     ss  = (Q1 - S1*S1/n1) + (Q2 - S2*S2/n2)          (a*a/b is (a*a)/b)
+ *     sp2 = ss / (n - 2)
+ *     t   = (S1/n1 - S2/n2) / sqrt(sp2 * (1.0/n1 + 1.0/n2))        valid iff n1 >= 2 && n2 >= 2 && sp2 > 0, otherwise NaN
+ *   Student's pooled t, the sign of mean(group 1) - mean(group 2).
+ *   OAI_STATS_ONE_SAMPLE (prepared with centre = 0; bit = flip the sign of the knee; mask_dev is not read):
+ *     Sf  = sum (b_i ? -c_i : c_i)
+ *     var = (Q - Sf*Sf/n) / (n - 1)
+ *     t   = (Sf/n) / sqrt(var/n)                                    valid iff n >= 2 && var > 0, otherwise NaN
+ * A thread owns one vertex and sixteen rows; a wave64 covers 64 consecutive vertices, so a label word is wave-uniform.  The kernel
+ * issues "s + (b ? c : 0.0)" as fma(c, b ? 1.0 : 0.0, s) and "s + (b ? -c : c)" as fma(c, b ? -1.0 : 1.0, s): the product is exact, so
+ * these are the bits of the stated adds for every finite c (with a non-finite c the t is NaN on either route).
+ *
+ * oai_permutation_reduce: the tile of rows [p0, p1).  max_abs_dev float64 [P]: entry p = max |t| of row p over its non-NaN entries, 0.0
+ * when it has none (an exact maximum: no order to state).  When p0 = 0, t0_dev float64 [n_verts] receives row 0 of the tile and
+ * exceed_dev int64 [n_verts] is STARTED; otherwise t0_dev is read and exceed_dev added to:
+ *   exceed[v] += number of rows p of the batch with |t_p(v)| >= |t_0(v)|, both not NaN        (row 0 counts itself)
+ *
+ * oai_graph_clusters: values_dev float64 [n_rows][n_verts] (any values: a t tile), the CSR vertex adjacency of oai_mesh_adjacency
+ * (offsets_dev int32 [n_verts + 1], neighbours_dev int32 [n_neighbours]; an offset outside [0, n_neighbours] is clamped, a neighbour
+ * outside [0, n_verts) is ignored), threshold t0 > 0.  Per row two vertex sets, {t > t0} and {t < -t0} (strict; NaN is in neither);
+ * connected components within each set, so two adjacent vertices of opposite sign never join.  A component's label is its smallest
+ * vertex index (as oai_label_components), a vertex in neither set has label -1 and size 0.  max_extent_dev int32 [n_rows]: the vertex
+ * count of the row's largest component over both signs, 0 if none.  label0_dev, size0_dev int32 [n_verts] (each may be null): row 0's
+ * labels and, per vertex, the size of its component.  One workgroup per row runs hook / jump rounds (oai_mesh_components) until a round
+ * changes nothing; labels and sizes live in the workspace, so n_verts is not bounded by LDS.  Integers only.
+ * ---------------------------------------------------------------------------------------- */
+#define OAI_STATS_TWO_SAMPLE 0
+#define OAI_STATS_ONE_SAMPLE 1
+/* All four: 0 for a shape the entry point refuses. */
+size_t oai_group_prepare_workspace_bytes(long long n_knees, long long n_verts);
+int oai_group_prepare(const float* y_dev, const unsigned char* mask_dev, long long n_knees, long long n_verts, int centre, void* workspace_dev,
+                      size_t workspace_bytes, void* stream);
+size_t oai_permutation_t_workspace_bytes(long long n_rows, long long n_verts);
+int oai_permutation_t(const void* prepared_dev, size_t prepared_bytes, const unsigned char* mask_dev, const unsigned* bits_dev, long long n_knees,
+                      long long n_verts, long long p0, long long p1, int mode, void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t oai_permutation_reduce_workspace_bytes(long long n_rows, long long n_verts);
+int oai_permutation_reduce(const double* tile_dev, long long n_verts, long long p0, long long p1, void* workspace_dev, size_t workspace_bytes,
+                           double* t0_dev, double* max_abs_dev, long long* exceed_dev, void* stream);
+size_t oai_graph_clusters_workspace_bytes(long long n_rows, long long n_verts);
+int oai_graph_clusters(const double* values_dev, long long n_rows, long long n_verts, const int* offsets_dev, const int* neighbours_dev,
+                       long long n_neighbours, double t0, void* workspace_dev, size_t workspace_bytes, int* max_extent_dev, int* label0_dev,
+                       int* size0_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,8 +34,12 @@ def meshwrite(mesh, path, binary=False):
 
 
 def __getattr__(name):
-    """``ThicknessAtlas`` / ``KneeThickness`` (thickness.py), imported on first use: the package itself imports neither torch nor the library."""
+    """``ThicknessAtlas`` / ``KneeThickness`` (thickness.py) and the cohort statistics (stats.py), imported on first use: the package itself
+    imports neither torch nor the library."""
     if name in ("ThicknessAtlas", "KneeThickness"):
         from . import thickness
         return getattr(thickness, name)
+    if name in ("ThicknessCohort", "PermutationResult", "two_sample_test", "paired_test", "label_permutations", "sign_flips"):
+        from . import stats
+        return getattr(stats, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -130,6 +130,14 @@ SIGNATURES = {
     "oai_mesh_geometry": (_I, [_P, C.c_longlong, _P, C.c_longlong, _P, C.POINTER(_D), _D, _P, _Z, _P, _P]),
     "oai_mesh_self_intersections_workspace_bytes": (_Z, [C.c_longlong, C.POINTER(C.c_int), C.c_longlong]),
     "oai_mesh_self_intersections": (_I, [_P, C.c_longlong, _P, C.c_longlong, C.POINTER(_D), _D, C.POINTER(C.c_int), C.c_longlong, _P, _Z, _P, _P, _P]),
+    "oai_group_prepare_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_group_prepare": (_I, [_P, _P, C.c_longlong, C.c_longlong, _I, _P, _Z, _P]),
+    "oai_permutation_t_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_permutation_t": (_I, [_P, _Z, _P, _P, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _I, _P, _Z, _P]),
+    "oai_permutation_reduce_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_permutation_reduce": (_I, [_P, C.c_longlong, C.c_longlong, C.c_longlong, _P, _Z, _P, _P, _P, _P]),
+    "oai_graph_clusters_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_graph_clusters": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, C.c_longlong, _D, _P, _Z, _P, _P, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

@@ -15,6 +15,7 @@
 //                                the largest squared edge length in fp64, numpy's norm order (dx*dx + dy*dy) + dz*dz.
 // Everything is integer work or exact min / max, so the results are the same bits as the host code's on every run.
 #include "common.h"
+#include "hook_jump.h"
 
 #include <algorithm>
 #include <climits>
@@ -23,10 +24,10 @@ namespace {
 
 constexpr int kT = 256;
 using oai::kMaxFaces;
+using oai::hook;
+using oai::load_agent;
 constexpr int kBatch = 4;                      // hook / jump rounds launched between two reads of the "changed" flags
 constexpr int kRedBlocks = 512;                // blocks of the grid-parameter reductions
-
-__device__ __forceinline__ int load_agent(const int* p) { return __hip_atomic_load(const_cast<int*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // connected components
@@ -34,15 +35,6 @@ __device__ __forceinline__ int load_agent(const int* p) { return __hip_atomic_lo
 __global__ void __launch_bounds__(kT) iota_kernel(int* __restrict__ parent, long long n) {
     const long long i = (long long)blockIdx.x * kT + threadIdx.x;
     if (i < n) parent[i] = (int)i;
-}
-
-// parent[] is read and written by other workgroups during the pass: every read is an agent-scope atomic load.  A stale value is
-// still an ancestor (parents only decrease), so a stale read costs at most one more round.
-__device__ __forceinline__ bool hook(int* parent, int u, int v) {
-    const int pu = load_agent(parent + u), pv = load_agent(parent + v);
-    if (pu == pv) return false;
-    atomicMin(parent + max(pu, pv), min(pu, pv));
-    return true;
 }
 
 __global__ void __launch_bounds__(kT) hook_kernel(const int* __restrict__ faces, long long n_faces, long long n_verts, int* parent,

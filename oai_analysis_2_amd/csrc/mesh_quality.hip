@@ -16,6 +16,7 @@
 
 #include <cmath>
 
+#include "hook_jump.h"
 #include "ordered_reduce.h"
 
 #pragma clang fp contract(off)
@@ -152,26 +153,6 @@ __global__ void __launch_bounds__(kT) topo_collect_kernel(const int* __restrict_
     lists[(long long)w * 3 * nf + atomicAdd(&n_list[w], 1)] = (int)h;
     parent[(long long)w * nv + a] = a;
     parent[(long long)w * nv + b] = b;
-}
-
-__device__ __forceinline__ int load_agent(const int* p) { return __hip_atomic_load(const_cast<int*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// hook / jump of csrc/mesh_graph.hip: a root only ever hooks onto a smaller index, so the components do not depend on the order
-__device__ __forceinline__ bool hook(int* parent, int u, int v) {
-    const int pu = load_agent(parent + u), pv = load_agent(parent + v);
-    if (pu == pv) return false;
-    atomicMin(parent + max(pu, pv), min(pu, pv));
-    return true;
-}
-__device__ __forceinline__ void jump(int* parent, int i) {
-    const int p0 = load_agent(parent + i);
-    int p = p0;
-    for (;;) {
-        const int q = load_agent(parent + p);
-        if (q == p) break;
-        p = q;
-    }
-    if (p != p0) __hip_atomic_store(parent + i, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // workgroup w: the connected components of edge list w.  Rounds of hook then jump with a barrier between, until a round hooks nothing

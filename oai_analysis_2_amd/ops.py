@@ -606,3 +606,129 @@ def region_stats(values: torch.Tensor, weights: torch.Tensor, labels: Optional[t
     _lib.call("oai_region_stats", _ptr(values, n), _ptr(weights, n), _ptr(labels, n), _ptr(covered, n), n, R, ws.data_ptr(), ws.numel(),
               stats.data_ptr(), _lib.STREAM, device=values.device)
     return stats.reshape(R, REGION_SLOTS)
+
+
+# ---- cohort statistics (include/oai_hip.h, "Cohort statistics"; csrc/group_stats.hip) -----------------------------------------------------
+STATS_TWO_SAMPLE, STATS_ONE_SAMPLE = 0, 1
+
+
+@dataclass
+class GroupPrepared:
+    """The prepared block of ``group_prepare`` and views of its arrays (include/oai_hip.h states the layout): ``C``, ``Qm`` float64 [N,V];
+    ``S``, ``Q``, ``mean``, ``std`` float64 [V]; ``n`` int32 [V].  ``mask``: the uint8 [N,V] mask it was prepared with, or None."""
+    block: torch.Tensor
+    n_knees: int
+    n_verts: int
+    centre: bool
+    mask: Optional[torch.Tensor]
+    C: torch.Tensor
+    Qm: torch.Tensor
+    S: torch.Tensor
+    Q: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    n: torch.Tensor
+
+
+def _stats_mask(mask: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
+    if mask is None:
+        return None
+    mask = _chk(mask.view(torch.uint8) if mask.dtype == torch.bool else mask, "mask", torch.uint8)
+    if tuple(mask.shape) != tuple(like.shape) or mask.device != like.device:
+        raise ValueError(f"mask must have the values' shape {tuple(like.shape)} and live on their GPU, got {tuple(mask.shape)} on {mask.device}")
+    return mask
+
+
+def group_prepare(values: torch.Tensor, mask: Optional[torch.Tensor] = None, centre: bool = True) -> GroupPrepared:
+    """What every permutation of a test re-sums, once per test: float32 ``values`` [N,V] (knee-major) and an optional uint8 / bool ``mask``
+    [N,V] (non-zero: the knee has a value at the vertex) -> per vertex n, mean, std, and the values c (centred on the mean unless
+    ``centre`` is False: the one-sample test's paired differences) with their squares and sums.  fp64, knees in ascending index:
+    bit-reproducible (include/oai_hip.h).  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or values.shape[0] < 2 or values.shape[1] < 1:
+        raise ValueError(f"values must be [N >= 2, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V = int(values.shape[0]), int(values.shape[1])
+    block = _lib.workspace("oai_group_prepare", values.device, N, V)
+    _lib.call("oai_group_prepare", values.data_ptr(), _ptr(mask), N, V, int(bool(centre)), block.data_ptr(), block.numel(), _lib.STREAM,
+              device=values.device)
+    off, parts = 0, {}
+    for name, dtype, shape in (("C", torch.float64, (N, V)), ("Qm", torch.float64, (N, V)), ("S", torch.float64, (V,)), ("Q", torch.float64, (V,)),
+                               ("mean", torch.float64, (V,)), ("std", torch.float64, (V,)), ("n", torch.int32, (V,))):
+        nbytes = int(np.prod(shape)) * (8 if dtype == torch.float64 else 4)
+        parts[name] = block[off:off + nbytes].view(dtype).reshape(shape)
+        off += (nbytes + 255) // 256 * 256
+    return GroupPrepared(block, N, V, bool(centre), mask, **parts)
+
+
+def _check_bits(bits: torch.Tensor, n_knees: int) -> torch.Tensor:
+    bits = _chk(bits.view(torch.int32) if bits.dtype == torch.uint32 else bits, "bits", torch.int32)
+    if bits.dim() != 2 or bits.shape[1] != (n_knees + 31) // 32:
+        raise ValueError(f"bits must be [P, {(n_knees + 31) // 32}] packed 32-bit words for {n_knees} knees, got {tuple(bits.shape)}")
+    return bits
+
+
+def permutation_t(prepared: GroupPrepared, bits: torch.Tensor, p0: int, p1: int, mode: int = STATS_TWO_SAMPLE,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The t tile of the labellings [p0, p1) of ``bits`` (packed 32-bit words [P, ceil(N/32)] on the device, int32 or uint32 storage): float64
+    [p1 - p0, V], NaN where no t exists.  ``mode`` STATS_TWO_SAMPLE: pooled t of the knees whose bit is set against the others;
+    STATS_ONE_SAMPLE: t of the values with the sign of every set knee flipped (``prepared`` with ``centre=False``).  ``workspace``: a uint8
+    device buffer to hold the tile (reused between batches) instead of a new one.  Does not synchronise."""
+    bits = _check_bits(bits, prepared.n_knees)
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 < p1 <= bits.shape[0]:
+        raise ValueError(f"rows [{p0}, {p1}) are not rows of the {bits.shape[0]} labellings")
+    if mode not in (STATS_TWO_SAMPLE, STATS_ONE_SAMPLE):
+        raise ValueError(f"mode must be STATS_TWO_SAMPLE or STATS_ONE_SAMPLE, got {mode!r}")
+    if prepared.centre != (mode == STATS_TWO_SAMPLE):
+        raise ValueError("the two-sample test needs group_prepare(centre=True), the one-sample test centre=False")
+    dev, V = prepared.block.device, prepared.n_verts
+    need = int(_lib.load().oai_permutation_t_workspace_bytes(p1 - p0, V))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if ws.numel() < need or ws.device != dev or ws.dtype != torch.uint8:
+        raise ValueError(f"workspace must be a uint8 buffer of at least {need} bytes on {dev}")
+    _lib.call("oai_permutation_t", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), bits.data_ptr(), prepared.n_knees, V, p0, p1,
+              int(mode), ws.data_ptr(), ws.numel(), _lib.STREAM, device=dev)
+    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+
+
+def permutation_reduce(tile: torch.Tensor, p0: int, t0: torch.Tensor, max_abs: torch.Tensor, exceed: torch.Tensor) -> None:
+    """Fold the t tile of rows [p0, p0 + len(tile)) into the test's running results, all on the device: ``max_abs`` float64 [P] gets each
+    row's max |t| (0.0 for a row without a valid t); ``exceed`` int64 [V] counts, per vertex, the rows with |t| >= |observed t|.  The
+    batch with ``p0`` = 0 holds the observed labelling as its row 0: it writes ``t0`` float64 [V] and starts ``exceed``; later batches
+    read ``t0`` and add.  Does not synchronise."""
+    tile = _chk(tile, "tile", torch.float64)
+    rows, V = int(tile.shape[0]), int(tile.shape[1])
+    p0 = int(p0)
+    t0, max_abs, exceed = _chk(t0, "t0", torch.float64), _chk(max_abs, "max_abs", torch.float64), _chk(exceed, "exceed", torch.int64)
+    if tuple(t0.shape) != (V,) or tuple(exceed.shape) != (V,) or max_abs.dim() != 1 or not 0 <= p0 <= max_abs.numel() - rows:
+        raise ValueError(f"t0 and exceed must be [{V}] and max_abs must hold rows [{p0}, {p0 + rows}), got {tuple(t0.shape)}, {tuple(exceed.shape)}, "
+                         f"{tuple(max_abs.shape)}")
+    ws = _lib.workspace("oai_permutation_reduce", tile.device, rows, V)
+    _lib.call("oai_permutation_reduce", tile.data_ptr(), V, p0, p0 + rows, ws.data_ptr(), ws.numel(), t0.data_ptr(), max_abs.data_ptr(),
+              exceed.data_ptr(), _lib.STREAM, device=tile.device)
+
+
+def graph_clusters(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.Tensor, threshold: float, max_extent: Optional[torch.Tensor] = None,
+                   return_labels: bool = False):
+    """Per row of the float64 ``values`` [R,V], the connected components of {value > threshold} and of {value < -threshold} on the graph
+    given as the CSR adjacency of ``mesh_processing.vertex_adjacency_device`` (int32 ``offsets`` [V+1], ``neighbours``).  Returns the int32
+    [R] DEVICE tensor of each row's largest component (vertices; both signs; 0 if none; ``max_extent``: written there); with
+    ``return_labels`` also row 0's int32 [V] labels (the component's smallest vertex index, -1 outside both sets) and per-vertex component
+    sizes.  Integers only.  Does not synchronise."""
+    values = _chk(values, "values", torch.float64)
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"values must be [R >= 1, V >= 1], got {tuple(values.shape)}")
+    R, V = int(values.shape[0]), int(values.shape[1])
+    offsets, neighbours = _chk(offsets, "offsets", torch.int32), _chk(neighbours, "neighbours", torch.int32)
+    if offsets.numel() != V + 1 or offsets.device != values.device or neighbours.device != values.device:
+        raise ValueError(f"offsets must be [{V + 1}] and live with neighbours on the values' GPU, got {offsets.numel()} on {offsets.device}")
+    if not float(threshold) > 0.0:
+        raise ValueError(f"threshold must be > 0, got {threshold!r}")
+    ext = _out_slot(max_extent, R, torch.int32, values.device, "max_extent")
+    label = torch.empty(V, dtype=torch.int32, device=values.device) if return_labels else None
+    size = torch.empty(V, dtype=torch.int32, device=values.device) if return_labels else None
+    ws = _lib.workspace("oai_graph_clusters", values.device, R, V)
+    _lib.call("oai_graph_clusters", values.data_ptr(), R, V, offsets.data_ptr(), _ptr(neighbours, neighbours.numel()), int(neighbours.numel()),
+              float(threshold), ws.data_ptr(), ws.numel(), ext.data_ptr(), _ptr(label), _ptr(size), _lib.STREAM, device=values.device)
+    return (ext, label, size) if return_labels else ext

@@ -1,0 +1,395 @@
+"""Cohort statistics on atlas thickness maps: permutation tests, vertex by vertex, with a family-wise error over the whole surface.
+
+The per-knee path ends in ``KneeThickness``: one float32 vector per cartilage on the atlas inner vertices, where the same vertex is the
+same anatomical location in every knee.  This module takes N such vectors and says where two groups of knees differ
+(``two_sample_test``: Student's pooled t under permutation of the group labels) or where a follow-up differs from baseline
+(``paired_test``: one-sample t of the differences under sign flips).  The reference has no such step; the definitions are stated in
+include/oai_hip.h ("Cohort statistics") and restated in tests/group_stats_ref.py.
+
+Everything heavy runs on the device (csrc/group_stats.hip): P labellings x V vertices x N knees of fp64 adds in a fixed order, and one
+connected-components pass over the atlas surface per labelling when a cluster threshold is given.  The p-values are formed on the host
+from integer counts and the null distribution of max |t|, after ONE download at the end.  No significance level is built in: the result
+holds p-values, and what counts as a finding is the study's decision.
+
+    cohort = ThicknessCohort.from_stream(thickness_stream(...), atlas, "FC")
+    res = two_sample_test(cohort, groups, n_permutations=10000, cluster_threshold=3.0)
+    res.p_fwer, res.clusters, res.image(atlas, "t")
+"""
+from __future__ import annotations
+
+import itertools
+import math
+from dataclasses import dataclass, field
+from typing import Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import mesh_processing as mp
+from . import ops
+
+WORKSPACE_BUDGET = 256 << 20          # bytes of t tile (and cluster labels) a default batch may take
+_ROW_GROUP = 16                       # labellings per thread of the t kernel: a batch is a multiple of it
+
+
+# ---- labellings ------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class Permutations:
+    """``bits``: uint32 [P, ceil(N / 32)] -- knee i of row p is bit i % 32 of word i // 32; row 0 is the observed labelling.  ``exact``:
+    the rows are ALL distinct labellings of the design, each once; otherwise rows 1.. are independent Monte Carlo draws, among which
+    duplicates (and the observed labelling itself) may occur -- the p-values are the usual Monte Carlo estimates either way."""
+    bits: np.ndarray
+    n_knees: int
+    exact: bool = False
+
+    def __len__(self) -> int:
+        return int(self.bits.shape[0])
+
+    def rows(self) -> np.ndarray:
+        """bool [P, N]."""
+        return unpack_bits(self.bits, self.n_knees)
+
+
+def pack_bits(rows) -> np.ndarray:
+    """bool [P, N] -> uint32 [P, ceil(N / 32)]."""
+    rows = np.atleast_2d(np.asarray(rows)).astype(bool)
+    P, N = rows.shape
+    padded = np.zeros((P, (N + 31) // 32 * 32), np.uint8)
+    padded[:, :N] = rows
+    return np.packbits(padded, axis=1, bitorder="little").view("<u4").astype(np.uint32).reshape(P, -1)
+
+
+def unpack_bits(bits, n_knees: int) -> np.ndarray:
+    """uint32 [P, ceil(N / 32)] -> bool [P, N]."""
+    bits = np.ascontiguousarray(np.atleast_2d(bits), dtype="<u4")
+    return np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little")[:, :int(n_knees)].astype(bool)
+
+
+def _as_groups(groups) -> np.ndarray:
+    g = np.asarray(groups)
+    if g.ndim != 1 or g.dtype == object or not np.isin(g, (0, 1)).all():
+        raise ValueError("groups must be one 0 / 1 (or bool) entry per knee: 1 = group 1, 0 = group 2")
+    return g.astype(bool)
+
+
+def label_permutations(groups, n_permutations: int, seed: int = 0, blocks=None) -> Permutations:
+    """Labellings for ``two_sample_test``: row 0 is ``groups`` itself (1 / True = group 1), every other row a rearrangement of the labels
+    that keeps both group sizes.  ``blocks``: an int label per knee (site, sex, ...); labels then move within a block only.  When the
+    design has at most ``n_permutations`` distinct labellings they are all enumerated, each once (``exact``); otherwise rows 1.. are
+    drawn from ``np.random.Generator(np.random.PCG64(seed))`` independently, so duplicates may occur."""
+    g = _as_groups(groups)
+    N, P = len(g), int(n_permutations)
+    if P < 1:
+        raise ValueError(f"n_permutations must be >= 1, got {n_permutations}")
+    b = np.zeros(N, np.int64) if blocks is None else np.asarray(blocks)
+    if b.shape != (N,):
+        raise ValueError(f"blocks must hold one label per knee ({N}), got shape {b.shape}")
+    members = [np.nonzero(b == lab)[0] for lab in np.unique(b)]
+    total = math.prod(math.comb(len(idx), int(g[idx].sum())) for idx in members)
+    if total <= P:
+        rows = [g.copy()]
+        per_block = [[np.asarray(c, np.int64) for c in itertools.combinations(range(len(idx)), int(g[idx].sum()))] for idx in members]
+        for choice in itertools.product(*per_block):
+            row = np.zeros(N, bool)
+            for idx, c in zip(members, choice):
+                row[idx[c]] = True
+            if not np.array_equal(row, g):
+                rows.append(row)
+        return Permutations(pack_bits(np.stack(rows)), N, exact=True)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    rows = np.empty((P, N), bool)
+    rows[0] = g
+    for idx in members:
+        rows[1:, idx] = rng.permuted(np.tile(g[idx], (P - 1, 1)), axis=1)
+    return Permutations(pack_bits(rows), N)
+
+
+def sign_flips(n_knees: int, n_permutations: int, seed: int = 0) -> Permutations:
+    """Sign vectors for ``paired_test``: a set bit flips the knee's difference; row 0 flips nothing.  All 2^N vectors, each once, when
+    there are at most ``n_permutations`` of them (``exact``); otherwise rows 1.. are independent draws from
+    ``np.random.Generator(np.random.PCG64(seed))``, so duplicates may occur."""
+    N, P = int(n_knees), int(n_permutations)
+    if N < 1 or P < 1:
+        raise ValueError(f"n_knees and n_permutations must be >= 1, got {n_knees}, {n_permutations}")
+    if N < 62 and (1 << N) <= P:
+        k = np.arange(1 << N, dtype=np.uint64)
+        return Permutations(pack_bits((k[:, None] >> np.arange(N, dtype=np.uint64)) & np.uint64(1)), N, exact=True)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    rows = np.zeros((P, N), bool)
+    rows[1:] = rng.integers(0, 2, size=(P - 1, N), dtype=np.uint8)
+    return Permutations(pack_bits(rows), N)
+
+
+# ---- the cohort matrix -----------------------------------------------------------------------------------------------------------------
+class ThicknessCohort:
+    """The knees of a study for one cartilage, as a float32 [N, V] matrix and its uint8 validity mask on the device, on the vertices of
+    ``atlas.inner[kind]`` (a ``ThicknessAtlas``, or any object with its ``inner``, ``device`` and ``image``).  An entry is MISSING
+    (mask 0) where the knee's value is NaN, in every entry of a cartilage listed in ``knee.errors``, and -- with ``use_coverage`` -- where
+    ``knee.coverage[kind]`` is 0, so that denuded bone is missing rather than a thickness.  The matrix grows in chunks of ``chunk`` knees."""
+
+    def __init__(self, atlas, kind: str, use_coverage: bool = False, chunk: int = 64):
+        self.atlas, self.kind, self.use_coverage, self.chunk = atlas, kind, bool(use_coverage), max(int(chunk), 1)
+        self.device = torch.device(atlas.device)
+        self.n_verts = len(atlas.inner[kind].verts)
+        self.ids: List[object] = []
+        self._values = torch.zeros((0, self.n_verts), dtype=torch.float32, device=self.device)
+        self._mask = torch.zeros((0, self.n_verts), dtype=torch.uint8, device=self.device)
+        self._graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self._areas: Optional[np.ndarray] = None
+
+    def surface_graph(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The CSR vertex adjacency of the atlas inner mesh on the device (``mesh_processing.vertex_adjacency_device``), built at the
+        first test that clusters and kept: it is the same for every test on this cohort."""
+        if self._graph is None:
+            faces = mp._dev(self.atlas.inner[self.kind].faces, np.int32, (3,), device=self.device)
+            self._graph = mp.vertex_adjacency_device(self.n_verts, faces)
+        return self._graph
+
+    def vertex_areas(self) -> np.ndarray:
+        """float64 [V]: ``mesh_processing.mesh_areas`` of the atlas inner mesh, in mm^2; computed once."""
+        if self._areas is None:
+            self._areas = mp.mesh_areas(self.atlas.inner[self.kind])[0]
+        return self._areas
+
+    def __len__(self) -> int:
+        return len(self.ids)
+
+    @property
+    def values(self) -> torch.Tensor:
+        return self._values[:len(self.ids)]
+
+    @property
+    def mask(self) -> torch.Tensor:
+        return self._mask[:len(self.ids)]
+
+    def _row(self) -> int:
+        n = len(self.ids)
+        if n == self._values.shape[0]:
+            for name, dtype in (("_values", torch.float32), ("_mask", torch.uint8)):
+                grown = torch.zeros((n + self.chunk, self.n_verts), dtype=dtype, device=self.device)
+                grown[:n] = getattr(self, name)
+                setattr(self, name, grown)
+        return n
+
+    def add_vector(self, vector, id=None, valid=None) -> None:
+        """One knee as a bare vector [V] (array or device tensor; NaN = missing) with an optional validity vector."""
+        vec = mp._dev(vector, np.float32, device=self.device).reshape(-1)
+        if vec.numel() != self.n_verts:
+            raise ValueError(f"the {self.kind} vector must have the atlas' {self.n_verts} vertices, got {vec.numel()}")
+        ok = ~torch.isnan(vec)
+        if valid is not None:
+            ok &= mp._dev(valid, np.uint8, device=self.device).reshape(-1) != 0
+        row = self._row()
+        self._values[row] = torch.where(ok, vec, torch.zeros_like(vec))
+        self._mask[row] = ok.to(torch.uint8)
+        self.ids.append(len(self.ids) if id is None else id)
+
+    def add(self, knee, id=None) -> None:
+        """One ``KneeThickness`` (numpy or device vectors).  ``id``: what ``paired_test`` matches rows by; default, the row index."""
+        if self.kind in knee.errors:
+            self.add_vector(torch.full((self.n_verts,), float("nan")), id)
+            return
+        cover = knee.coverage.get(self.kind) if self.use_coverage else None
+        if self.use_coverage and cover is None:
+            raise ValueError(f"use_coverage needs knee.coverage[{self.kind!r}]: measure the knee with morphometry")
+        self.add_vector(knee[self.kind], id, cover)
+
+    @classmethod
+    def from_stream(cls, stream: Iterable[Tuple[object, object]], atlas, kind: str, **kwargs) -> "ThicknessCohort":
+        """Collect the (index, KneeThickness) pairs of ``thickness_stream`` / ``process_cohort_thickness``; the index is the knee's id."""
+        cohort = cls(atlas, kind, **kwargs)
+        for index, knee in stream:
+            cohort.add(knee, index)
+        return cohort
+
+    def summary(self) -> dict:
+        """Per vertex: ``n`` (knees with a value), ``mean``, ``std`` (n - 1 in the denominator; NaN below two knees), as arrays."""
+        if len(self) < 2:
+            raise ValueError("a summary needs at least two knees")
+        prep = ops.group_prepare(self.values, self.mask)
+        return {"n": prep.n.cpu().numpy(), "mean": prep.mean.cpu().numpy(), "std": prep.std.cpu().numpy()}
+
+
+# ---- the tests -------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class Cluster:
+    label: int               # the cluster's smallest vertex index: its value in ``cluster_label``
+    sign: int                # +1: t > threshold, -1: t < -threshold
+    extent: int              # vertices
+    area: float              # mm^2 of the atlas inner surface (vertex areas summed in ascending vertex index)
+    p_cluster: float         # share of labellings whose largest cluster has at least this extent
+
+
+@dataclass
+class PermutationResult:
+    """``t`` float64 [V] (NaN where no t exists: fewer than two knees on a side, or no variance); ``n1``, ``n2`` the knees with a value
+    per vertex and side (paired: both the number of pairs); ``mean_difference`` group 1 - group 2 (paired: mean of a - b);
+    ``p_uncorrected`` = share of labellings with |t| at least the observed at that vertex; ``p_fwer`` = share of labellings whose max |t|
+    over the surface is at least the observed |t| at that vertex (both NaN where t is); ``max_abs`` the null distribution of max |t|,
+    one entry per labelling, entry 0 observed.  With a cluster threshold: ``cluster_label`` int32 [V] (-1 outside every cluster),
+    ``clusters`` in ascending label, ``max_extent`` the null distribution of the largest cluster's extent."""
+    kind: str
+    t: np.ndarray
+    n1: np.ndarray
+    n2: np.ndarray
+    mean_difference: np.ndarray
+    p_uncorrected: np.ndarray
+    p_fwer: np.ndarray
+    max_abs: np.ndarray
+    n_permutations: int
+    exact: bool
+    cluster_threshold: Optional[float] = None
+    cluster_label: Optional[np.ndarray] = None
+    clusters: List[Cluster] = field(default_factory=list)
+    max_extent: Optional[np.ndarray] = None
+
+    def image(self, atlas, what: str = "t"):
+        """``atlas.image`` of "t", "p_fwer", "p_uncorrected", "mean_difference" or "cluster_label" (float32 [H, W], NaN off the surface)."""
+        if what not in ("t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label"):
+            raise ValueError(f"no image of {what!r}")
+        vec = getattr(self, what)
+        if vec is None:
+            raise ValueError("the test ran without a cluster threshold")
+        return atlas.image(np.asarray(vec, np.float32), self.kind)
+
+
+def default_batch(n_verts: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET) -> int:
+    """Labellings per batch: what fits ``budget`` bytes of workspace -- 8 bytes per (labelling, vertex) of t tile, and 8 more of labels and
+    sizes with clusters -- rounded down to the t kernel's sixteen rows per thread, at least sixteen."""
+    rows = budget // (int(n_verts) * (16 if clusters else 8))
+    return int(min(max(rows // _ROW_GROUP * _ROW_GROUP, _ROW_GROUP), max(int(n_permutations), 1)))
+
+
+def _download(tensors: Sequence[torch.Tensor]) -> List[np.ndarray]:
+    """Every tensor in one device-to-host copy."""
+    flat = torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in tensors]).cpu().numpy()
+    out, off = [], 0
+    for t in tensors:
+        nbytes = t.numel() * t.element_size()
+        out.append(flat[off:off + nbytes].view(getattr(np, str(t.dtype).split(".")[1])).reshape(tuple(t.shape)).copy())
+        off += nbytes
+    return out
+
+
+def _run(cohort_like, values: torch.Tensor, mask: Optional[torch.Tensor], perms: Permutations, mode: int, cluster_threshold: Optional[float],
+         batch: Optional[int], extra):
+    """The batches of one test, queued without a synchronisation; returns the host arrays of (t0, max_abs, exceed, max_extent | None,
+    label | None, size | None, *extra) after one download.  ``extra``: device tensors to bring along, or a function of the prepared block
+    that names them."""
+    N, V = int(values.shape[0]), int(values.shape[1])
+    if perms.n_knees != N:
+        raise ValueError(f"the labellings are for {perms.n_knees} knees, the cohort has {N}")
+    P = len(perms)
+    dev = values.device
+    graph = None
+    if cluster_threshold is not None:
+        if not float(cluster_threshold) > 0.0:
+            raise ValueError(f"cluster_threshold must be > 0, got {cluster_threshold!r}")
+        graph = cohort_like.surface_graph()
+    rows = default_batch(V, P, graph is not None) if batch is None else int(batch)
+    if rows < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    with torch.cuda.device(dev):
+        bits = torch.from_numpy(np.ascontiguousarray(perms.bits).view(np.int32)).to(dev)
+        prepared = ops.group_prepare(values, mask, centre=mode == ops.STATS_TWO_SAMPLE)
+        t0 = torch.empty(V, dtype=torch.float64, device=dev)
+        max_abs = torch.empty(P, dtype=torch.float64, device=dev)
+        exceed = torch.empty(V, dtype=torch.int64, device=dev)
+        max_extent = torch.empty(P, dtype=torch.int32, device=dev) if graph is not None else None
+        label = size = None
+        tile_ws = _lib.workspace("oai_permutation_t", dev, min(rows, P), V)
+        for p0 in range(0, P, rows):
+            p1 = min(p0 + rows, P)
+            tile = ops.permutation_t(prepared, bits, p0, p1, mode, workspace=tile_ws)
+            ops.permutation_reduce(tile, p0, t0, max_abs, exceed)
+            if graph is not None:
+                got = ops.graph_clusters(tile, graph[0], graph[1], float(cluster_threshold), max_extent=max_extent[p0:p1], return_labels=p0 == 0)
+                if p0 == 0:
+                    _, label, size = got
+        out = [t0, max_abs, exceed] + ([max_extent, label, size] if graph is not None else []) + list(extra(prepared) if callable(extra) else extra)
+        host = _download(out)
+    if graph is None:
+        host[3:3] = [None, None, None]
+    return host
+
+
+def _finish(kind: str, cohort_like, perms: Permutations, host, n1, n2, mean_difference, cluster_threshold) -> PermutationResult:
+    t, max_abs, exceed, max_extent, label, size = host[:6]
+    P = len(perms)
+    valid = ~np.isnan(t)
+    p_unc = np.where(valid, exceed / float(P), np.nan)
+    null = np.sort(max_abs)
+    p_fwer = np.where(valid, (P - np.searchsorted(null, np.abs(np.where(valid, t, 0.0)), side="left")) / float(P), np.nan)
+    res = PermutationResult(kind, t, n1, n2, mean_difference, p_unc, p_fwer, max_abs, P, perms.exact)
+    if cluster_threshold is not None:
+        area = cohort_like.vertex_areas()
+        res.cluster_threshold, res.cluster_label, res.max_extent = float(cluster_threshold), label, max_extent
+        extents = np.sort(max_extent)
+        for lab in np.unique(label[label >= 0]):
+            members = np.nonzero(label == lab)[0]                          # ascending vertex index
+            extent = int(size[lab])
+            res.clusters.append(Cluster(int(lab), 1 if t[lab] > 0 else -1, extent, float(np.cumsum(area[members])[-1]),
+                                        float(P - np.searchsorted(extents, extent, side="left")) / float(P)))
+    return res
+
+
+def _permutations(perms, make, n_knees: int) -> Permutations:
+    if perms is None:
+        return make()
+    if isinstance(perms, Permutations):
+        return perms
+    bits = np.asarray(perms)
+    if bits.dtype == bool:
+        bits = pack_bits(bits)
+    return Permutations(np.ascontiguousarray(bits, dtype=np.uint32), n_knees)
+
+
+def two_sample_test(cohort: ThicknessCohort, groups, n_permutations: int = 10000, cluster_threshold: Optional[float] = None, seed: int = 0,
+                    blocks=None, permutations=None, batch: Optional[int] = None) -> PermutationResult:
+    """Where do the knees of group 1 (``groups[i]`` = 1) differ from those of group 2 (= 0)?  Student's pooled t per vertex; its null
+    distribution comes from ``label_permutations(groups, n_permutations, seed, blocks)``, or from ``permutations`` -- a ``Permutations``,
+    packed uint32 rows or bool [P, N] with the observed labelling as row 0 -- for designs that does not cover.  ``cluster_threshold``
+    (a |t| value): also clusters of supra-threshold vertices on the atlas surface and their extent-based p-values.  ``batch``: labellings
+    per launch; default ``default_batch``.  A vertex where a group has fewer than two knees with a value has no t (NaN)."""
+    g = _as_groups(groups)
+    if len(g) != len(cohort):
+        raise ValueError(f"groups must hold one entry per knee of the cohort ({len(cohort)}), got {len(g)}")
+    if g.sum() < 2 or (~g).sum() < 2:
+        raise ValueError("each group needs at least two knees")
+    perms = _permutations(permutations, lambda: label_permutations(g, n_permutations, seed, blocks), len(g))
+    if not np.array_equal(perms.rows()[0], g):
+        raise ValueError("row 0 of the permutations must be the observed labelling")
+    values, mask = cohort.values, cohort.mask
+    sides = []
+    for member in (g, ~g):                                                 # the descriptive side: n and mean of either group, per vertex
+        idx = torch.from_numpy(np.nonzero(member)[0]).to(values.device)
+        prep = ops.group_prepare(values.index_select(0, idx), mask.index_select(0, idx))
+        sides += [prep.n, prep.mean]
+    host = _run(cohort, values, mask, perms, ops.STATS_TWO_SAMPLE, cluster_threshold, batch, sides)
+    n1, mean1, n2, mean2 = host[6:10]
+    return _finish(cohort.kind, cohort, perms, host, n1, n2, mean1 - mean2, cluster_threshold)
+
+
+def paired_test(cohort_a: ThicknessCohort, cohort_b: ThicknessCohort, n_permutations: int = 10000, cluster_threshold: Optional[float] = None,
+                seed: int = 0, permutations=None, batch: Optional[int] = None) -> PermutationResult:
+    """Where does ``cohort_a`` differ from ``cohort_b`` within a knee (follow-up against baseline)?  Rows are matched by id (every id of
+    either cohort must be in the other, once); the difference a - b is taken on the device and is missing where either side is; the
+    statistic is the one-sample t of the differences and its null distribution comes from ``sign_flips``."""
+    if cohort_a.kind != cohort_b.kind or cohort_a.n_verts != cohort_b.n_verts or cohort_a.device != cohort_b.device:
+        raise ValueError("the two cohorts must hold the same cartilage of the same atlas on the same GPU")
+    where_b = {id_: k for k, id_ in enumerate(cohort_b.ids)}
+    if len(where_b) != len(cohort_b) or len(set(cohort_a.ids)) != len(cohort_a) or set(cohort_a.ids) != set(where_b):
+        raise ValueError("paired_test needs the same ids in both cohorts, each once")
+    N = len(cohort_a)
+    if N < 2:
+        raise ValueError("paired_test needs at least two pairs")
+    order = torch.tensor([where_b[id_] for id_ in cohort_a.ids], dtype=torch.int64, device=cohort_a.device)
+    mask = cohort_a.mask * cohort_b.mask.index_select(0, order)
+    diff = (cohort_a.values - cohort_b.values.index_select(0, order)) * mask        # missing entries hold 0 on either side
+    perms = _permutations(permutations, lambda: sign_flips(N, n_permutations, seed), N)
+    if perms.rows()[0].any():
+        raise ValueError("row 0 of the permutations must flip nothing")
+    host = _run(cohort_a, diff, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, batch, lambda prepared: [prepared.n, prepared.mean])
+    n, mean = host[6:8]
+    return _finish(cohort_a.kind, cohort_a, perms, host, n, n.copy(), mean, cluster_threshold)
