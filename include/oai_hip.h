@@ -256,6 +256,13 @@ int oai_unet_set_act_exponents(oai_unet* h, const int e[OAI_UNET_NUM_LAYERS]);
  *                       OWN cover -- origin at the tile's own box corner (x rounded down to even), strips decided by its own remainders, one launch per block shape --
  *                       and the k2s2 up-convs list the voxels of every tile's own input box; 0 = the cover / the voxels of the batch's union box (border tiles
  *                       then pay for blocks that straddle the union's grid and for rows outside their box).  oai_unet_cover_stats counts both
+ *   "one_launch" 0..7 (1) bit-preserving: an own-cover layer runs as ONE launch over a device list of the batch's live blocks -- all main blocks, then the x strips,
+ *                       then the y strips, so that the strips fill the main blocks' last round and the layer pays one tail instead of three (conv3_wino_list*,
+ *                       csrc/unet_wino.h; the blocks run the stand-alone kernels' own code).  bit 0: the layers with two cout groups (dc8, dc7, dc5, dc4), bit 1: the
+ *                       64-cout layer (dc2; not in the default: merged with its strips the specialised form spills more registers inside its chunk loop,
+ *                       profiles/one_launch.md), bit 2: force.  There is a SIZE GATE: without bit 2 a layer is merged only in a batch where its live blocks number
+ *                       at least the device's CUs.  Smaller batches keep the three launches: they have no tail worth saving, their launch structure is pinned by the
+ *                       tests, and they are not what the library is timed on.  0 = three launches per layer.  Needs "own_cover"; oai_unet_block_list gives the list
  *   "dead_stores" 0|1 (1) the encoder does not write the part of a skip tensor that the trimmed decoder never reads
  *   "census" 0|1 (1)    the kernels record per-layer activation maxima (activation exponents, LOW bit of the range flag)
  *   "calibrated" 0      forget that the activation exponents were calibrated (they keep their values): oai_unet_get_act_exponents reports 0 until
@@ -347,6 +354,14 @@ int oai_unet_tile_costs(const oai_unet* h, int D, int H, int W, const int tile_z
  * (lo z y x, hi z y x) and the three pieces of its own cover -- main blocks, x strip, y strip; an up-conv's box is its one piece. */
 int oai_unet_cover_stats(int D, int H, int W, const int tile_zyx[3], const int overlap_zyx[3], const int crop_zyx[3], int batch, int layer,
                          double stats_host[3], int* pieces_host, int n_tiles);
+/* Host only, no device and no handle: the live-block list of option "one_launch" for own-cover conv layer `layer` (indices as above) and the batch of `n` tiles
+ * starting at tile_begin, as oai_segment_tiles builds it on the device when it segments the volume in batches of `batch` (n <= batch).  *n_entries = its length
+ * (0: the batch does not fit the entry format and keeps its three launches); entries_host (optional, room for `capacity` words) = the entries in list order,
+ * one word each: tile index in the batch << 20 | shape << 18 | bz << 12 | by << 6 | bx, shape 0 = main block (4 x 8 x 8), 1 = x strip (4 x 16 x 4), 2 = y strip
+ * (4 x 4 x 16), (bz, by, bx) counted from the corner of that piece of the tile's own cover (oai_unet_cover_stats: pieces_host).  workspace_offset (optional): the
+ * byte offset in oai_segment_tiles' workspace at which that call leaves the layer's device list of its LAST batch (tests compare the two). */
+int oai_unet_block_list(int D, int H, int W, const int tile_zyx[3], const int overlap_zyx[3], const int crop_zyx[3], int batch, int tile_begin, int n, int layer,
+                        unsigned* entries_host, int capacity, int* n_entries, long long* workspace_offset);
 /* Same as oai_unet_tile_flops, restricted to the layers the 3x3x3 implicit-GEMM kernel runs (ec1-ec7, dc8, dc7, dc5, dc4, dc2, dc1). */
 double oai_unet_tile_flops_conv3(const oai_unet* h, int td, int th, int tw, const int overlap_zyx[3], int trimmed);
 

@@ -54,6 +54,8 @@ SIGNATURES = {
                                            _P, _I, _I, _I, _P]),
     "oai_unet_tile_costs": (_I, [_P, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), _I]),
     "oai_unet_cover_stats": (_I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_int), _I]),
+    "oai_unet_block_list": (_I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, C.POINTER(C.c_uint), _I,
+                                 C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "oai_mc_table": (_I, [_P]),
     "oai_mc_workspace_bytes": (_Z, [_I, _I, _I]),
     "oai_mc_count": (_I, [_P, _I, _I, _I, _F, _P, _Z, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _P]),

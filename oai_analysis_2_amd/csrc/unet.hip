@@ -69,7 +69,8 @@ struct oai_unet {
     int opt_first_blocks = 24;          // option "first_blocks"
     int opt_up_nbw = 0;                 // option "up_nbw"
     int opt_own_cover = 1;              // option "own_cover"
-    int opt_shared = 1;                 // option "shared_enc"
+    int opt_one_launch = 1;             // option "one_launch"
+    int opt_shared = 1;                // option "shared_enc"
     int opt_wide = 1;                   // option "wide"
     int opt_wino = 19;                  // option "winograd"
     int opt_wino_layers = 0x3FFFF;      // option "winograd_layers"
@@ -553,11 +554,23 @@ constexpr int kMaxTilesPerTable = 4096;
 // three more rows per such layer, one per block shape (tile_cover): rows 18 + 3 slot + shape, addressed like the layers' own.
 constexpr int kOwnLayers = 5, kTableRows = 18 + 3 * kOwnLayers;
 __host__ __device__ static inline int own_cover_slot(int k) { return k == DC8 ? 0 : k == DC7 ? 1 : k == DC5 ? 2 : k == DC4 ? 3 : k == DC2 ? 4 : -1; }
+constexpr int kOwnLayerOf[kOwnLayers] = {DC8, DC7, DC5, DC4, DC2};
 enum Buf { B_E0, B_SYN0, B_P0, B_E2, B_SYN1, B_P1, B_E4, B_SYN2, B_P2, B_E6, B_E7, B_U9, B_D8, B_D7, B_U6, B_D5, B_D4, B_U3, B_D2, B_D1, B_COUNT };
 
 // The workspace of one pass of `batch` tiles: the per-tile box table of the current oai_segment_tiles call at the start, then the activation
 // tensors.  Returns the bytes; over a null `base` the pointers are null and only the size counts (oai::Ws).
-static size_t carve_workspace(const oai_unet* h, int td, int th, int tw, int batch, const void* base, float* buf[B_COUNT], int*& table) {
+// entries that the live-block list of ONE own-cover layer can have for a batch (option "one_launch"): every layer gets the room of a whole tile at level 0
+// -- main blocks of 4 x 8 x 8, one column of x-strip blocks, one row of y-strip blocks (the x start rounded down to even may add a block column)
+static size_t block_list_capacity(int td, int th, int tw, int batch) {
+    return (size_t)batch * cdiv(td, 4) * ((size_t)cdiv(th, 8) * cdiv(tw + 1, 8) + cdiv(th, 16) + cdiv(tw + 1, 16));
+}
+// where the list of own-cover layer `slot` starts in the workspace, in bytes: behind the box table, one list after the other.  (Depends on the tile
+// shape and the batch only: oai_unet_block_list reports it without a handle.)
+static size_t block_list_offset(int td, int th, int tw, int batch, int slot) {
+    return round256((size_t)kTableRows * kMaxTilesPerTable * 6 * sizeof(int)) + slot * round256(block_list_capacity(td, th, tw, batch) * sizeof(unsigned));
+}
+
+static size_t carve_workspace(const oai_unet* h, int td, int th, int tw, int batch, const void* base, float* buf[B_COUNT], int*& table, unsigned** lists = nullptr) {
     const size_t v0 = (size_t)td * th * tw, v1 = v0 / 8, v2 = v1 / 8, v3 = v2 / 8;
     const oai::Layer* L = h->L;
     auto pc = [&](int k) { return (size_t)((L[k].cout + 15) / 16 * 16); };   // channels padded to whole 16-chunks (format S)
@@ -568,6 +581,10 @@ static size_t carve_workspace(const oai_unet* h, int td, int th, int tw, int bat
         v0 * pc(DC2), v0 * pc(DC1)};
     Ws ws(base);
     table = ws.take<int>((size_t)kTableRows * kMaxTilesPerTable * 6);
+    for (int slot = 0; slot < kOwnLayers; ++slot) {                    // (block_list_offset says where these are)
+        unsigned* list = ws.take<unsigned>(block_list_capacity(td, th, tw, batch));
+        if (lists) lists[slot] = list;
+    }
     for (int i = 0; i < B_COUNT; ++i) buf[i] = ws.take<float>(sizes[i] * batch);
     return ws.off;
 }
@@ -728,15 +745,17 @@ __host__ __device__ static void tile_cover(const Box& box, Box piece[3]) {
 constexpr int kWinoTY[3] = {8, 16, 4}, kWinoTX[3] = {8, 4, 16};         // the block shapes of the three pieces (4 z slices each)
 __host__ __device__ static inline bool box_empty(const Box& b) { return b.hi[0] <= b.lo[0] || b.hi[1] <= b.lo[1] || b.hi[2] <= b.lo[2]; }
 // blocks of shape `s` that piece `p` of a tile takes from its own origin (0 0 0: empty piece)
-static void piece_blocks(const Box& p, int s, int nb[3]) {
+__host__ __device__ static void piece_blocks(const Box& p, int s, int nb[3]) {
     nb[0] = nb[1] = nb[2] = 0;
     if (box_empty(p)) return;
-    nb[0] = cdiv(p.hi[0] - p.lo[0], 4); nb[1] = cdiv(p.hi[1] - p.lo[1], kWinoTY[s]); nb[2] = cdiv(p.hi[2] - (p.lo[2] & ~1), kWinoTX[s]);
+    const int ty = s == 0 ? 8 : s == 1 ? 16 : 4, tx = s == 0 ? 8 : s == 1 ? 4 : 16;      // (kWinoTY / kWinoTX: host arrays)
+    nb[0] = (p.hi[0] - p.lo[0] + 3) / 4; nb[1] = (p.hi[1] - p.lo[1] + ty - 1) / ty; nb[2] = (p.hi[2] - (p.lo[2] & ~1) + tx - 1) / tx;
 }
 // what run_batch needs of the host's walk over a batch's tiles for option "own_cover": the grid of every shape of every own-cover layer (the largest
 // block counts of any tile, per axis), the largest input box of every up-conv in voxels, and every tile's own block counts [tile][slot][shape][3]
 // (all 0 for a dead tile), from which balanced_xcd_group deals a launch
-struct OwnPlan { int nb[kOwnLayers][3][3]; int up_nvox[18]; std::vector<int> tile_nb; };
+// list / list_len (option "one_launch"): the device lists of the layers that run as one launch for this batch, 0 entries = three launches (one_launch_len)
+struct OwnPlan { int nb[kOwnLayers][3][3]; int up_nvox[18]; std::vector<int> tile_nb; const unsigned* list[kOwnLayers]; int list_len[kOwnLayers]; };
 constexpr int kTileNbStride = kOwnLayers * 3 * 3;
 static void own_plan_add(OwnPlan& op, const Box need[18]) {
     const size_t row = op.tile_nb.size();
@@ -760,7 +779,86 @@ static void own_plan_add(OwnPlan& op, const Box need[18]) {
     }
 }
 // one own-cover layer of one batch, as launch_conv3_wino takes it: the device rows of the three pieces, their grids and XCD dealing granularities (0: the option's)
-struct OwnCover { const int* rows[3]; int nb[3][3]; int xcd_group[3]; };
+// `list` (option "one_launch"): the layer's live-block list on the device and its length, or null / 0 = one launch per shape
+struct OwnCover { const int* rows[3]; int nb[3][3]; int xcd_group[3]; const unsigned* list; int list_len; };
+
+// ---- option "one_launch": the live-block list of an own-cover layer (unet_wino.h: conv3_wino_list*)
+// Entries of layer `slot` for a batch whose tiles' block counts are `tile_nb` (OwnPlan): every live block of every piece once -- or 0 where a field does
+// not fit the entry format (wino_list_entry) or the list its room in the workspace: that batch keeps its three launches.
+static int block_list_len(const int* tile_nb, int ntiles, int slot, size_t capacity) {
+    if (ntiles > (1 << kWinoListTileBits)) return 0;
+    long long len = 0;
+    for (int t = 0; t < ntiles; ++t)
+        for (int s = 0; s < 3; ++s) {
+            const int* nb = tile_nb + (size_t)t * kTileNbStride + (slot * 3 + s) * 3;
+            for (int i = 0; i < 3; ++i) if (nb[i] > (1 << kWinoListAxisBits)) return 0;
+            len += (long long)nb[0] * nb[1] * nb[2];
+        }
+    return len <= (long long)capacity && len < (1ll << 30) ? (int)len : 0;
+}
+// The list in its order, on the host (oai_unet_block_list; the device builds the same with block_list_kernel): all main blocks -- tile by tile, a tile's
+// blocks as the stand-alone launch numbers them, bx fastest -- then all x-strip blocks, then all y-strip blocks.  Hardware starts workgroups in id order:
+// the strips run in the main blocks' last round.
+static void block_list_host(const int* tile_nb, int ntiles, int slot, unsigned* out) {
+    for (int s = 0; s < 3; ++s)
+        for (int t = 0; t < ntiles; ++t) {
+            const int* nb = tile_nb + (size_t)t * kTileNbStride + (slot * 3 + s) * 3;
+            for (int bz = 0; bz < nb[0]; ++bz)
+                for (int by = 0; by < nb[1]; ++by)
+                    for (int bx = 0; bx < nb[2]; ++bx) *out++ = wino_list_entry(t, s, bz, by, bx);
+        }
+}
+// The same list on the device, from the piece rows that box_table_kernel wrote for the batch's tiles [t0, t0 + n) of a table of table_tiles tiles: per
+// (shape, tile) the block count (piece_blocks, the function the host counts with), ONE ordered exclusive scan over the 3 n counts in LDS -- every thread
+// sums its consecutive share, a Hillis-Steele scan orders the 256 shares -- then entry e is found by bisection in the offsets.  No atomics: the list is
+// the same in every run.  Workgroup = (layer slot, one of kListParts interleaved parts of the entries); every workgroup repeats the (cheap) scan.
+constexpr int kListParts = 8;
+__global__ void __launch_bounds__(256) block_list_kernel(const int* __restrict__ table, int table_tiles, int t0, int n, unsigned* __restrict__ lists, size_t stride,
+                                                          int capacity, int slot_mask) {
+    __shared__ int off[3 * kMaxTilesPerTable + 1];
+    __shared__ int share[256];
+    const int slot = blockIdx.x / kListParts, part = blockIdx.x % kListParts, tid = threadIdx.x;
+    if (!((slot_mask >> slot) & 1)) return;
+    auto blocks_of = [&](int item, int nb[3]) {
+        const int s = item / n, t = item - s * n;
+        const int* row = table + ((size_t)(18 + 3 * slot + s) * table_tiles + t0 + t) * 6;
+        Box p;
+        for (int i = 0; i < 3; ++i) { p.lo[i] = row[i]; p.hi[i] = row[3 + i]; }
+        piece_blocks(p, s, nb);
+    };
+    const int items = 3 * n, per = (items + 255) / 256;
+    for (int i = tid; i < items; i += 256) {
+        int nb[3];
+        blocks_of(i, nb);
+        off[i] = nb[0] * nb[1] * nb[2];
+    }
+    __syncthreads();
+    const int lo = min(items, tid * per), hi = min(items, lo + per);
+    int sum = 0;
+    for (int i = lo; i < hi; ++i) sum += off[i];
+    share[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int v = tid >= d ? share[tid - d] : 0;
+        __syncthreads();
+        share[tid] += v;
+        __syncthreads();
+    }
+    int run = share[tid] - sum;
+    for (int i = lo; i < hi; ++i) { const int c = off[i]; off[i] = run; run += c; }
+    if (tid == 255) off[items] = share[255];
+    __syncthreads();
+    const int total = min(off[items], capacity);                        // (the host launches this only for a list that fits: block_list_len)
+    unsigned* list = lists + (size_t)slot * stride;
+    for (int e = part * 256 + tid; e < total; e += kListParts * 256) {
+        int a = 0, b = items;                                           // the last item whose offset is <= e: the one with a block number e
+        while (b - a > 1) { const int m = (a + b) >> 1; if (off[m] <= e) a = m; else b = m; }
+        int nb[3];
+        blocks_of(a, nb);
+        const int r = e - off[a], s = a / n;
+        list[e] = wino_list_entry(a - s * n, s, r / (nb[2] * nb[1]), (r / nb[2]) % nb[1], r % nb[2]);
+    }
+}
 
 // The XCD dealing of an own-cover launch.  Its grid is the LARGEST tile's, so a smaller tile's surplus workgroups return at once -- and xcd_block_id deals
 // logical ids, not work: with the option's 32 ids per deal and, e.g., 8 ids per tile (dc8's y strip of the 160-tile volume) XCD k gets the tiles of ONE y
@@ -909,18 +1007,59 @@ static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, cons
     return launch_end(h, st);
 }
 
+// Which one-launch kernel an own-cover layer takes (option "one_launch"): 1 = conv3_wino_list2 (two cout groups), 2 = conv3_wino_list1 (one block of 64
+// couts), 0 = none -- the option's bit is off, or the configuration gives the layer's shapes kernels that these two do not combine (the A/B bits 2 and 3
+// of option "winograd", no room for the specialised form)
+static int one_launch_family(const oai_unet* h, const Layer& L) {
+    if (L.cout % 128 == 0) return (h->opt_one_launch & 1) && !(h->opt_wino & 8) ? 1 : 0;
+    return (h->opt_one_launch & 2) && L.cout % 64 == 0 && !(h->opt_wino & 4) && wino_ws_fits() ? 2 : 0;
+}
+// The size gate of option "one_launch": the entries of the layer's list, or 0 = three launches for this batch.  Without the force bit a layer runs as one
+// launch only when its live blocks number at least the device's CUs: below that the three launches are not even one round of the chip and there is no tail
+// to save -- and the launch structure of small batches is pinned by the tests (tests/test_unet_gpu.py counts the timed launches of batches of 9 tiles).
+// Small batches are not what the library is timed on.
+static int one_launch_len(const oai_unet* h, const int* tile_nb, int ntiles, int slot, size_t capacity) {
+    static const int cus = [] { int dev = 0, n = 0; return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? n : 1 << 30; }();
+    const int len = block_list_len(tile_nb, ntiles, slot, capacity);
+    return (h->opt_one_launch & 4) || len >= cus ? len : 0;
+}
+// One own-cover layer as ONE launch of conv3_wino_list2 / conv3_wino_list1 over its live-block list (option "one_launch"; unet_wino.h says what the kernels
+// read of ConvArgs); `level` = the whole level, as for the three launches.  One launch = one start / stop pair of oai_unet_profile.
+static int launch_wino_list(const oai_unet* h, const Layer& L, ConvArgs a, const Box& level, hipStream_t st, const OwnCover& oc, int family) {
+    for (int i = 0; i < 3; ++i) { a.lo[i] = level.lo[i]; a.hi[i] = level.hi[i]; }
+    a.own_origin = 1;
+    a.boxes = oc.rows[0]; a.nbz = (int)(oc.rows[1] - oc.rows[0]); a.nby = a.nbx = 0;      // the piece rows of the three shapes are equally spaced table rows
+    a.reserved1 = reinterpret_cast<int*>(const_cast<unsigned*>(oc.list));
+    a.ncb = a.Cout / (family == 1 ? 128 : 64);
+    const unsigned grid = xcd_deal(h, (unsigned)((size_t)oc.list_len * a.ncb), a.nblocks, a.xcd_group);      // only live blocks are dealt: the option's granularity balances
+    const bool m16 = family == 1 ? (h->opt_wino & 16) && L.panel_wino16 : wino_m16_64(h, L, a.Cout);          // (the tap form that launch_wino_shape picks for the layer)
+    a.wpanel = m16 ? L.panel_wino16 : L.panel_wino;
+    if (int rc = launch_begin(h, st)) return rc;
+    if (family == 1) {
+        if (m16) conv3_wino_list2<true><<<grid, 512, 0, st>>>(a, h->zero_rec);
+        else conv3_wino_list2<false><<<grid, 512, 0, st>>>(a, h->zero_rec);
+    } else {
+        if (m16) conv3_wino_list1<true><<<grid, 512, 0, st>>>(a, h->zero_rec);
+        else conv3_wino_list1<false><<<grid, 512, 0, st>>>(a, h->zero_rec);
+    }
+    return launch_end(h, st);
+}
+
 // A plain layer (no fused ec0 / pool / head / scatter) of the default split-resident configuration through conv3_wino_sres: main blocks of
 // 4 x 8 x 8, a y strip of 4 x 4 x 16 blocks for a remainder of <= 4 rows, an x strip of 4 x 16 x 4 blocks for a remainder of <= 4 columns
 // .  The box starts at an even x: an output's arithmetic depends on the
 // parity of its x only -- not on which launch or block computes it.
 // `oc` (option "own_cover"; the trimmed decoder layers of oai_segment_tiles): the same three shapes, one launch each, over every tile's OWN cover
 // (tile_cover) instead of the cover of the batch's union box: a border tile's blocks start at its own corner, and its own remainders decide its
-// strips.  The launch box is the whole level; a shape that no tile of the batch needs is not launched.  Same bits.
+// strips.  The launch box is the whole level; a shape that no tile of the batch needs is not launched.  Same bits.  With a live-block list (option
+// "one_launch") the three launches are one: launch_wino_list.
 static int launch_conv3_wino(const oai_unet* h, const Layer& L, const ConvArgs& a, Box box, int ntiles, hipStream_t st, const OwnCover* oc = nullptr) {
     if (oc && a.boxes) {
         const int dims[3] = {a.D, a.H, a.W};
         Box level;
         full_box(level, dims);
+        if (oc->list_len > 0)
+            if (const int family = one_launch_family(h, L)) return launch_wino_list(h, L, a, level, st, *oc, family);
         ConvArgs b = a;
         for (int s = 0; s < 3; ++s) {
             if (oc->nb[s][0] == 0) continue;
@@ -1096,12 +1235,13 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
     auto oc = [&](int layer) -> const OwnCover* {                     // the layer's own-cover rows and grids (option "own_cover"), or null
         if (!own) return nullptr;
         const int slot = own_cover_slot(layer);
+        ocs[slot].list = own->list[slot]; ocs[slot].list_len = own->list_len[slot];      // option "one_launch": one launch over the live blocks -- nothing to balance
         for (int s = 0; s < 3; ++s) {
             ocs[slot].rows[s] = tb(18 + 3 * slot + s);
             for (int i = 0; i < 3; ++i) ocs[slot].nb[s][i] = own->nb[slot][s][i];
             // (counted here, just before the layer's launches: under the device work queued so far)
             const int ncb = h->L[layer].cout / (64 * wino_groups(h, h->L[layer].cout, kWinoTY[s]));
-            ocs[slot].xcd_group[s] = own->nb[slot][s][0] && ncb > 0 ? balanced_xcd_group(h->xcd_group, own->tile_nb.data() + (slot * 3 + s) * 3, n, own->nb[slot][s], ncb) : 0;
+            ocs[slot].xcd_group[s] = own->nb[slot][s][0] && ncb > 0 && !ocs[slot].list_len ? balanced_xcd_group(h->xcd_group, own->tile_nb.data() + (slot * 3 + s) * 3, n, own->nb[slot][s], ncb) : 0;
         }
         return &ocs[slot];
     };
@@ -1481,6 +1621,10 @@ static const IntOption kIntOptions[] = {
     // bit-preserving: in oai_segment_tiles the trimmed decoder convs (dc8, dc7, dc5, dc4, dc2 on conv3_wino_sres) place their blocks on every tile's own cover
     // (tile_cover) and the up-convs list every tile's own input voxels, instead of the cover / the voxels of the batch's union box; 0 = the union's (A/B)
     {"own_cover", &oai_unet::opt_own_cover, 0, 1, "oai_unet_set_option: own_cover must be 0 or 1"},
+    // bit-preserving: an own-cover layer runs as ONE launch over the batch's live-block list (conv3_wino_list*, unet_wino.h) instead of one launch per block
+    // shape.  bit 0: the two-group layers (dc8, dc7, dc5, dc4), bit 1: the 64-cout layer (dc2), bit 2: also for a layer with fewer live blocks in the batch than
+    // the device has CUs (one_launch_len: small batches keep their three launches unless a test forces it); 0 = three launches
+    {"one_launch", &oai_unet::opt_one_launch, 0, 7, "oai_unet_set_option: one_launch must be in [0, 7] (bit 0 two-group layers, bit 1 the 64-cout layer, bit 2 force)"},
     // ec0 computed inside ec1's halo staging when ec1 is one main-shape launch
     {"fuse_first", &oai_unet::fuse_first, 0, 1, "oai_unet_set_option: fuse_first must be 0 or 1"},
     // logical blocks per XCD deal; 0 = plain launch order
@@ -1837,9 +1981,11 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
     if (crop) for (int i = 0; i < 3; ++i) OAI_CHECK_ARG(crop[i] >= 0, "oai_segment_tiles: negative crop");
     float* buf[B_COUNT];
     int* table_dev;
-    const size_t need_bytes = carve_workspace(h, tile[0], tile[1], tile[2], batch, ws, buf, table_dev);
+    unsigned* lists[kOwnLayers];
+    const size_t need_bytes = carve_workspace(h, tile[0], tile[1], tile[2], batch, ws, buf, table_dev, lists);
     if (need_bytes > ws_bytes)
         return set_error(OAI_ERR_WORKSPACE, "oai_segment_tiles: workspace %zu B < %zu B needed for batch %d", ws_bytes, need_bytes, batch);
+    const size_t list_cap = block_list_capacity(tile[0], tile[1], tile[2], batch);
     const bool trimmed = diag_env("OAI_NO_TRIM", 0) == 0;
     hipStream_t st = (hipStream_t)stream;
     TileSource src{};
@@ -1887,6 +2033,19 @@ int oai_segment_tiles(oai_unet* h, const float* vol, int D, int H, int W, const 
                 }
             }
             if (uni[0].hi[0] == 0) continue;                 // every tile of the batch is dead
+            // option "one_launch": the live-block lists of the own-cover layers that run as one launch for this batch, built on the device from the table
+            if (h->opt_own_cover && h->sres && (h->opt_one_launch & 3)) {
+                int mask = 0;
+                for (int slot = 0; slot < kOwnLayers; ++slot) {
+                    own.list[slot] = lists[slot];
+                    own.list_len[slot] = one_launch_family(h, h->L[kOwnLayerOf[slot]]) ? one_launch_len(h, own.tile_nb.data(), n, slot, list_cap) : 0;
+                    if (own.list_len[slot]) mask |= 1 << slot;
+                }
+                if (mask) {
+                    block_list_kernel<<<kOwnLayers * kListParts, 256, 0, st>>>(table_dev, nc, t - c0, n, lists[0], (size_t)(lists[1] - lists[0]), (int)std::min<size_t>(list_cap, 1u << 30), mask);
+                    OAI_CHECK_LAUNCH();
+                }
+            }
             src.tile_begin = t;
             if (int rc = run_batch(h, src, n, uni, out_mode, blocks + (size_t)(t - tile_begin) * h->n_classes * bvox,
                                    buf, st, table_dev, nc, t - c0, shared ? &se : nullptr, &own)) return rc;
@@ -2005,6 +2164,33 @@ int oai_unet_cover_stats(int D, int H, int W, const int tile[3], const int overl
                 for (int s = 0; s < 3; ++s) for (int i = 0; i < 3; ++i) { row[6 + 6 * s + i] = piece[s].lo[i]; row[9 + 6 * s + i] = piece[s].hi[i]; }
             }
         }
+    }
+    return OAI_OK;
+}
+
+int oai_unet_block_list(int D, int H, int W, const int tile[3], const int overlap[3], const int crop[3], int batch, int tile_begin, int n, int layer,
+                        unsigned* entries_host, int capacity, int* n_entries, long long* workspace_offset) {
+    OAI_CHECK_ARG(tile && overlap && n_entries, "oai_unet_block_list: null pointer");
+    OAI_CHECK_ARG(layer >= 0 && layer < 18 && own_cover_slot(layer) >= 0, "oai_unet_block_list: layer %d is not an own-cover conv layer", layer);
+    if (int rc = check_tile(tile[0], tile[1], tile[2])) return rc;
+    SegGeom g;
+    if (int rc = seg_geometry(D, H, W, tile, overlap, g)) return rc;
+    OAI_CHECK_ARG(batch > 0 && n > 0 && n <= batch && tile_begin >= 0 && tile_begin + n <= g.ntiles,
+                  "oai_unet_block_list: tiles [%d, %d + %d) are not a batch of at most %d of the volume's %d tiles", tile_begin, tile_begin, n, batch, g.ntiles);
+    const SegParams sp = seg_params(D, H, W, tile, overlap, crop, g, true);
+    const int slot = own_cover_slot(layer);
+    OwnPlan own{};
+    Box need[18];
+    for (int j = 0; j < n; ++j) {                                            // (the walk of oai_segment_tiles over the batch)
+        tile_regions(tile_begin + j, sp, need);
+        own_plan_add(own, need);
+    }
+    const int len = block_list_len(own.tile_nb.data(), n, slot, block_list_capacity(tile[0], tile[1], tile[2], batch));
+    *n_entries = len;
+    if (workspace_offset) *workspace_offset = (long long)block_list_offset(tile[0], tile[1], tile[2], batch, slot);
+    if (entries_host) {
+        OAI_CHECK_ARG(capacity >= len, "oai_unet_block_list: %d entries do not fit the %d given", len, capacity);
+        if (len > 0) block_list_host(own.tile_nb.data(), n, slot, entries_host);      // (0: the batch does not fit the entry format and keeps its three launches)
     }
     return OAI_OK;
 }

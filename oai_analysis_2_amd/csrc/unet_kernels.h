@@ -86,7 +86,8 @@ struct ConvArgs {
                                              // (In the slot of the removed diagnostic switch word: the kernel-argument layout of earlier rounds stays.)
     unsigned long long* stamps = nullptr;    // -DOAI_DIAG builds: device array of phase cycle sums (oai_diag_stamps); never set in production
     int nblocks = 0, xcd_group = 0;          // split-resident kernel: true workgroup count and the XCD dealing granularity (see xcd_block_id)
-    int* reserved1 = nullptr;                // (keeps the kernel-argument layout of earlier rounds: the slot of the removed persistent form's block plan)
+    int* reserved1 = nullptr;                // conv3_wino_list* (option "one_launch"): the layer's live-block list, one wino_list_entry word per block (unet_wino.h);
+                                             // unused by every other kernel.  (The slot of the removed persistent form's block plan: the kernel-argument layout stays.)
     // split-resident kernel only: dc0 (1x1x1 conv) + sigmoid / threshold + centre crop fused into dc1's epilogue.  When head_w is
     // set the layer's own output is NOT written; every block voxel inside head_boxes[tile] goes to the kept-centre blocks instead.
     const float* head_w = nullptr;           // [ncls][Cout]
