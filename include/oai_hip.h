@@ -1107,6 +1107,62 @@ int oai_graph_clusters(const double* values_dev, long long n_rows, long long n_v
                        long long n_neighbours, double t0, void* workspace_dev, size_t workspace_bytes, int* max_extent_dev, int* label0_dev,
                        int* size0_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Cohort regression (csrc/group_regression.hip, tests/group_regression_ref.py): how does thickness vary with one regressor of interest
+ * x, vertex by vertex, adjusted for nuisance covariates -- the model y ~ Z gamma + x beta over the knees that have a value at the vertex,
+ * the t of beta, and its null distribution under permutation.  Z has q nuisance columns, the intercept (if any) counted among them; the
+ * design D = [Z | x] has p = q + 1 columns WITH x LAST, 1 <= p <= 6.  The permutation scheme is Freedman and Lane's, as recalled from
+ * Winkler et al. 2014 (NeuroImage 92) and NOT pinned to any implementation: y is residualised on Z once, then the rows of the whole
+ * design are permuted against the fixed residuals and their fixed mask -- algebraically the same as permuting the residuals, and it keeps
+ * "missing" attached to the data.  The reference has no such step: the definitions are this library's own, pinned by the numpy
+ * restatement and scipy.  The rules of "Cohort statistics" hold: fp64 without contraction, no floating-point atomics, one accumulator
+ * per sum that starts at +0.0, EVERY SUM OVER KNEES IN ASCENDING KNEE INDEX: bit-reproducible.  Neither entry point synchronises or reads
+ * anything back.  2 <= n_knees <= 2^24, 1 <= n_verts <= 2^31 - 2, at most 2^20 rows per call.  y_dev and mask_dev as in "Cohort
+ * statistics"; nuisance_dev float64 [n_knees][q] and design_dev float64 [n_knees][p], knee-major; perm_dev int32 [P][n_knees].
+ *
+ * Cholesky, A = L L^T of a symmetric matrix given by its lower triangle, in this order: for a = 0 .. size-1 { s = A_aa;
+ * for k < a ascending: s = s - L_ak*L_ak;  PIVOT RULE (a condition, not a measurement): pivot s is accepted iff s > 1e-10 * A_aa;
+ * L_aa = sqrt(s);  for c = a+1 .. size-1 { s = A_ca; for k < a ascending: s = s - L_ck*L_ak;  L_ca = s / L_aa } }.  The arithmetic
+ * goes on after a pivot that is not accepted; what it then leaves in R and Q is IEEE arithmetic like the rest.
+ *
+ * oai_regression_prepare.  With m_i and y_i as in oai_group_prepare -- per vertex v, i = 0 .. n_knees - 1:
+ *   n    = sum m_i                 mean = (sum y_i) / (double)n
+ *   d_i  = y_i - mean where m_i and centre = 1;  y_i where m_i and centre = 0;  0.0 otherwise
+ *   q > 0:  A_ac = sum_i (m_i ? z_ia*z_ic : 0.0), c <= a       h_a = sum_i z_ia*d_i   (a product, then an add: two roundings)
+ *           A = L L^T;  L w = h forward (w_a = (h_a - sum_{k<a} L_ak*w_k) / L_aa, s = s - L_ak*w_k, k ascending);
+ *           L^T gamma = w backward, a = q-1 .. 0 (gamma_a = (w_a - sum_{k>a} L_ka*gamma_k) / L_aa, s = s - L_ka*gamma_k, k ascending)
+ *           r_i = m_i ? d_i - sum_a z_ia*gamma_a : 0.0        (from d_i, s = s - z_ia*gamma_a, a ascending)
+ *   q = 0:  r_i = d_i
+ *   Q    = sum r_i*r_i
+ *   ok   = every pivot of A accepted && n - p >= 1
+ * The PREPARED BLOCK, prepared_dev, front to back, each array starting on the next multiple of 256 bytes: R float64 [n_knees][n_verts],
+ * Q, mean float64 [n_verts], n int32 [n_verts], ok uint8 [n_verts].
+ *
+ * oai_regression_t: rows [p0, p1) of perm_dev -> the t tile, float64 [p1 - p0][n_verts] at the start of workspace_dev, which
+ * oai_permutation_reduce and oai_graph_clusters consume as they are.  Knee j of row pi takes design row perm[pi][j]; an index outside
+ * [0, n_knees) is clamped.  Row 0 is the identity by convention.  Per (row, vertex), g_j = D[perm[pi][j]] (p doubles), j ascending:
+ *   M_ac = sum_j (m_j ? g_ja*g_jc : 0.0), c <= a             b_a = sum_j g_ja*r_j   (a product, then an add)
+ *   M = L L^T, same order and pivot rule;   L z = b forward, as above
+ *   rss = Q - sum_a z_a*z_a                 (from Q, s = s - z_a*z_a, a ascending)
+ *   dof = n - p;   s2 = rss / (double)dof;   t = z_p / sqrt(s2)          (z_p: the last entry, that of x)
+ *   valid iff ok[v] && every pivot of M accepted && dof >= 1 && s2 > 0, otherwise NaN
+ * With p0 = 0 and slope0_dev (float64 [n_verts]) not null, row 0 also writes beta = z_p / L_pp there, NaN where its t is.
+ * mask_dev as given to oai_regression_prepare; null: every entry is valid, and the results are THE SAME BITS as with a mask of all ones.
+ * A thread owns one vertex and R rows (R depends on p and on whether there is a mask).  The product g_ja*g_jc is formed once, in fp64,
+ * by a gather kernel that writes the batch's permuted design into the workspace; the t kernel issues "M + (m ? G : 0.0)" as
+ * fma(G, m ? 1.0 : 0.0, M): the product is exact, so these are the bits of the stated add for every finite design.  Without a mask M
+ * and L do not depend on the vertex and are formed once per row, in the same order.
+ * ---------------------------------------------------------------------------------------- */
+/* Both: 0 for a shape the entry point refuses. */
+size_t oai_regression_prepare_workspace_bytes(long long n_knees, long long n_verts);
+int oai_regression_prepare(const float* y_dev, const unsigned char* mask_dev, const double* nuisance_dev, long long n_knees, long long n_verts,
+                           int n_nuisance, int centre, void* prepared_dev, size_t prepared_bytes, void* stream);
+size_t oai_regression_t_workspace_bytes(long long n_rows, long long n_verts, long long n_knees, int n_columns);
+int oai_regression_t(const void* prepared_dev, size_t prepared_bytes, const unsigned char* mask_dev, const double* design_dev, const int* perm_dev,
+                     long long n_knees, long long n_verts, int n_columns, long long p0, long long p1, void* workspace_dev, size_t workspace_bytes,
+                     double* slope0_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

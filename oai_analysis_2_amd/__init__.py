@@ -39,7 +39,8 @@ def __getattr__(name):
     if name in ("ThicknessAtlas", "KneeThickness"):
         from . import thickness
         return getattr(thickness, name)
-    if name in ("ThicknessCohort", "PermutationResult", "two_sample_test", "paired_test", "label_permutations", "sign_flips"):
+    if name in ("ThicknessCohort", "PermutationResult", "two_sample_test", "paired_test", "label_permutations", "sign_flips",
+                "RegressionResult", "IndexPermutations", "regression_test", "index_permutations"):
         from . import stats
         return getattr(stats, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

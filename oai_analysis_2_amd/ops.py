@@ -732,3 +732,87 @@ def graph_clusters(values: torch.Tensor, offsets: torch.Tensor, neighbours: torc
     _lib.call("oai_graph_clusters", values.data_ptr(), R, V, offsets.data_ptr(), _ptr(neighbours, neighbours.numel()), int(neighbours.numel()),
               float(threshold), ws.data_ptr(), ws.numel(), ext.data_ptr(), _ptr(label), _ptr(size), _lib.STREAM, device=values.device)
     return (ext, label, size) if return_labels else ext
+
+
+# ---- cohort regression (include/oai_hip.h, "Cohort regression"; csrc/group_regression.hip) ---------------------------------------------------
+MAX_DESIGN_COLUMNS = 6
+
+
+@dataclass
+class RegressionPrepared:
+    """The prepared block of ``regression_prepare`` and views of its arrays (include/oai_hip.h states the layout): ``R`` float64 [N,V], the
+    residuals of the (centred) values on the nuisance columns; ``Q``, ``mean`` float64 [V]; ``n`` int32 [V]; ``ok`` uint8 [V].  ``mask``:
+    the uint8 [N,V] mask it was prepared with, or None; ``n_nuisance``: the q it was prepared with."""
+    block: torch.Tensor
+    n_knees: int
+    n_verts: int
+    n_nuisance: int
+    centre: bool
+    mask: Optional[torch.Tensor]
+    R: torch.Tensor
+    Q: torch.Tensor
+    mean: torch.Tensor
+    n: torch.Tensor
+    ok: torch.Tensor
+
+
+def _design(design, name: str, n_knees: int, device, lo: int, hi: int) -> torch.Tensor:
+    design = _chk(design, name, torch.float64)
+    if design.dim() != 2 or design.shape[0] != n_knees or not lo <= design.shape[1] <= hi or design.device != device:
+        raise ValueError(f"{name} must be float64 [{n_knees}, {lo} .. {hi}] on {device}, got {tuple(design.shape)} on {design.device}")
+    return design
+
+
+def regression_prepare(values: torch.Tensor, mask: Optional[torch.Tensor] = None, nuisance: Optional[torch.Tensor] = None,
+                       centre: bool = True) -> RegressionPrepared:
+    """What every permutation of a regression re-uses, once per test: float32 ``values`` [N,V], an optional uint8 / bool ``mask`` [N,V] and
+    the float64 ``nuisance`` columns [N,q] (0 <= q <= 5, the intercept among them; None: q = 0) -> per vertex n, mean, the residuals of the
+    values (less their mean when ``centre``) on the nuisance columns over the knees with a value, their sum of squares Q, and ``ok``
+    (the nuisance system has full rank there and n - q - 1 >= 1).  fp64 in a stated order: bit-reproducible.  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or values.shape[0] < 2 or values.shape[1] < 1:
+        raise ValueError(f"values must be [N >= 2, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V = int(values.shape[0]), int(values.shape[1])
+    q = 0
+    if nuisance is not None and nuisance.numel() > 0:
+        nuisance = _design(nuisance, "nuisance", N, values.device, 1, MAX_DESIGN_COLUMNS - 1)
+        q = int(nuisance.shape[1])
+    block = _lib.workspace("oai_regression_prepare", values.device, N, V)
+    _lib.call("oai_regression_prepare", values.data_ptr(), _ptr(mask), nuisance.data_ptr() if q else None, N, V, q, int(bool(centre)),
+              block.data_ptr(), block.numel(), _lib.STREAM, device=values.device)
+    off, parts = 0, {}
+    for name, dtype, shape, size in (("R", torch.float64, (N, V), 8), ("Q", torch.float64, (V,), 8), ("mean", torch.float64, (V,), 8),
+                                     ("n", torch.int32, (V,), 4), ("ok", torch.uint8, (V,), 1)):
+        nbytes = int(np.prod(shape)) * size
+        parts[name] = block[off:off + nbytes].view(dtype).reshape(shape)
+        off += (nbytes + 255) // 256 * 256
+    return RegressionPrepared(block, N, V, q, bool(centre), mask, **parts)
+
+
+def regression_t(prepared: RegressionPrepared, design: torch.Tensor, perm: torch.Tensor, p0: int, p1: int, workspace: Optional[torch.Tensor] = None,
+                 slope0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The t tile of rows [p0, p1) of ``perm`` (int32 [P,N] on the device: knee j of a row takes design row ``perm[row, j]``; row 0 the
+    identity): float64 [p1 - p0, V], the t of the LAST column of the float64 ``design`` [N,p] (p = the prepared q + 1), NaN where no t
+    exists.  ``slope0`` float64 [V]: with ``p0`` = 0, receives row 0's coefficient of that column.  ``workspace``: a uint8 device buffer of
+    ``oai_regression_t_workspace_bytes`` (reused between batches) instead of a new one; the tile is its front.  Does not synchronise."""
+    dev, N, V = prepared.block.device, prepared.n_knees, prepared.n_verts
+    design = _design(design, "design", N, dev, prepared.n_nuisance + 1, prepared.n_nuisance + 1)
+    p = int(design.shape[1])
+    perm = _chk(perm, "perm", torch.int32)
+    if perm.dim() != 2 or perm.shape[1] != N or perm.device != dev:
+        raise ValueError(f"perm must be int32 [P, {N}] on {dev}, got {tuple(perm.shape)} on {perm.device}")
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 < p1 <= perm.shape[0]:
+        raise ValueError(f"rows [{p0}, {p1}) are not rows of the {perm.shape[0]} permutations")
+    if slope0 is not None:
+        slope0 = _chk(slope0, "slope0", torch.float64)
+        if tuple(slope0.shape) != (V,) or slope0.device != dev:
+            raise ValueError(f"slope0 must be float64 [{V}] on {dev}, got {tuple(slope0.shape)} on {slope0.device}")
+    need = int(_lib.load().oai_regression_t_workspace_bytes(p1 - p0, V, N, p))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if ws.numel() < need or ws.device != dev or ws.dtype != torch.uint8:
+        raise ValueError(f"workspace must be a uint8 buffer of at least {need} bytes on {dev}")
+    _lib.call("oai_regression_t", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p,
+              p0, p1, ws.data_ptr(), ws.numel(), _ptr(slope0), _lib.STREAM, device=dev)
+    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)

@@ -14,6 +14,13 @@ holds p-values, and what counts as a finding is the study's decision.
     cohort = ThicknessCohort.from_stream(thickness_stream(...), atlas, "FC")
     res = two_sample_test(cohort, groups, n_permutations=10000, cluster_threshold=3.0)
     res.p_fwer, res.clusters, res.image(atlas, "t")
+
+``regression_test`` asks how thickness varies with ONE continuous (or dummy) regressor, adjusted for nuisance covariates: the general
+linear model per vertex, the t of the regressor's coefficient, Freedman-Lane permutation (include/oai_hip.h, "Cohort regression";
+csrc/group_regression.hip; tests/group_regression_ref.py).
+
+    res = regression_test(cohort, kl_grade, covariates=np.stack([age, sex], axis=1), n_permutations=10000, cluster_threshold=3.0)
+    res.slope, res.partial_r, res.p_fwer
 """
 from __future__ import annotations
 
@@ -314,23 +321,36 @@ def _run(cohort_like, values: torch.Tensor, mask: Optional[torch.Tensor], perms:
     return host
 
 
-def _finish(kind: str, cohort_like, perms: Permutations, host, n1, n2, mean_difference, cluster_threshold) -> PermutationResult:
-    t, max_abs, exceed, max_extent, label, size = host[:6]
-    P = len(perms)
+def _p_values(t: np.ndarray, max_abs: np.ndarray, exceed: np.ndarray, P: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(p_uncorrected, p_fwer) from the integer counts and the null distribution of max |t|; NaN where t is.  A row whose t is NaN at a
+    vertex counts as not exceeding there: the denominator is P all the same."""
     valid = ~np.isnan(t)
     p_unc = np.where(valid, exceed / float(P), np.nan)
     null = np.sort(max_abs)
     p_fwer = np.where(valid, (P - np.searchsorted(null, np.abs(np.where(valid, t, 0.0)), side="left")) / float(P), np.nan)
+    return p_unc, p_fwer
+
+
+def _set_clusters(res, cohort_like, t, P: int, cluster_threshold, max_extent, label, size) -> None:
+    """The cluster fields of a result, when the test ran with a threshold."""
+    if cluster_threshold is None:
+        return
+    area = cohort_like.vertex_areas()
+    res.cluster_threshold, res.cluster_label, res.max_extent = float(cluster_threshold), label, max_extent
+    extents = np.sort(max_extent)
+    for lab in np.unique(label[label >= 0]):
+        members = np.nonzero(label == lab)[0]                              # ascending vertex index
+        extent = int(size[lab])
+        res.clusters.append(Cluster(int(lab), 1 if t[lab] > 0 else -1, extent, float(np.cumsum(area[members])[-1]),
+                                    float(P - np.searchsorted(extents, extent, side="left")) / float(P)))
+
+
+def _finish(kind: str, cohort_like, perms: Permutations, host, n1, n2, mean_difference, cluster_threshold) -> PermutationResult:
+    t, max_abs, exceed, max_extent, label, size = host[:6]
+    P = len(perms)
+    p_unc, p_fwer = _p_values(t, max_abs, exceed, P)
     res = PermutationResult(kind, t, n1, n2, mean_difference, p_unc, p_fwer, max_abs, P, perms.exact)
-    if cluster_threshold is not None:
-        area = cohort_like.vertex_areas()
-        res.cluster_threshold, res.cluster_label, res.max_extent = float(cluster_threshold), label, max_extent
-        extents = np.sort(max_extent)
-        for lab in np.unique(label[label >= 0]):
-            members = np.nonzero(label == lab)[0]                          # ascending vertex index
-            extent = int(size[lab])
-            res.clusters.append(Cluster(int(lab), 1 if t[lab] > 0 else -1, extent, float(np.cumsum(area[members])[-1]),
-                                        float(P - np.searchsorted(extents, extent, side="left")) / float(P)))
+    _set_clusters(res, cohort_like, t, P, cluster_threshold, max_extent, label, size)
     return res
 
 
@@ -393,3 +413,191 @@ def paired_test(cohort_a: ThicknessCohort, cohort_b: ThicknessCohort, n_permutat
     host = _run(cohort_a, diff, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, batch, lambda prepared: [prepared.n, prepared.mean])
     n, mean = host[6:8]
     return _finish(cohort_a.kind, cohort_a, perms, host, n, n.copy(), mean, cluster_threshold)
+
+
+# ---- regression ------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class IndexPermutations:
+    """``index``: int32 [P, N] -- knee j of row p takes the design row ``index[p, j]``; row 0 is the identity.  ``exact``: the rows are ALL
+    permutations of the design (within blocks), each once, in lexicographic order; otherwise rows 1.. are independent Monte Carlo draws."""
+    index: np.ndarray
+    exact: bool = False
+
+    def __len__(self) -> int:
+        return int(self.index.shape[0])
+
+
+def index_permutations(n_knees: int, n_permutations: int, seed: int = 0, blocks=None) -> IndexPermutations:
+    """Index rows for ``regression_test``: row 0 the identity, every other row a permutation of 0 .. N - 1.  ``blocks``: an int label per
+    knee (site, sex, ...); knees then move within a block only.  When there are at most ``n_permutations`` such permutations (the product
+    of n_b! over the blocks) they are all enumerated, each once, in lexicographic order (``exact``); otherwise rows 1.. are drawn from
+    ``np.random.Generator(np.random.PCG64(seed)).permuted`` independently, so duplicates (and the identity) may occur."""
+    N, P = int(n_knees), int(n_permutations)
+    if N < 1 or P < 1:
+        raise ValueError(f"n_knees and n_permutations must be >= 1, got {n_knees}, {n_permutations}")
+    b = np.zeros(N, np.int64) if blocks is None else np.asarray(blocks)
+    if b.shape != (N,):
+        raise ValueError(f"blocks must hold one label per knee ({N}), got shape {b.shape}")
+    members = [np.nonzero(b == lab)[0] for lab in np.unique(b)]
+    total = 1
+    for idx in members:
+        total *= math.factorial(len(idx)) if total <= P else 1             # stop multiplying once it is beyond P
+    if total <= P:
+        rows = []
+        for choice in itertools.product(*[itertools.permutations(idx.tolist()) for idx in members]):
+            row = np.empty(N, np.int32)
+            for idx, c in zip(members, choice):
+                row[idx] = c
+            rows.append(row)
+        return IndexPermutations(np.stack(rows), exact=True)               # the first product is the identity
+    rng = np.random.Generator(np.random.PCG64(seed))
+    index = np.tile(np.arange(N, dtype=np.int32), (P, 1))
+    for idx in members:
+        index[1:, idx] = rng.permuted(np.tile(idx.astype(np.int32), (P - 1, 1)), axis=1)
+    return IndexPermutations(index)
+
+
+@dataclass
+class RegressionResult:
+    """``t`` float64 [V]: the t of the regressor's coefficient (NaN where no t exists: too few knees with a value, a design that loses its
+    rank among them, no residual variance); ``n`` the knees with a value and ``dof`` = n - p per vertex; ``slope`` in mm per unit of ``x``;
+    ``partial_r`` = t / sqrt(t^2 + dof), the partial correlation of thickness and x given the covariates; the p-values, ``max_abs`` and the
+    cluster fields as in ``PermutationResult``."""
+    kind: str
+    t: np.ndarray
+    n: np.ndarray
+    dof: np.ndarray
+    slope: np.ndarray
+    partial_r: np.ndarray
+    p_uncorrected: np.ndarray
+    p_fwer: np.ndarray
+    max_abs: np.ndarray
+    n_permutations: int
+    exact: bool
+    cluster_threshold: Optional[float] = None
+    cluster_label: Optional[np.ndarray] = None
+    clusters: List[Cluster] = field(default_factory=list)
+    max_extent: Optional[np.ndarray] = None
+
+    def image(self, atlas, what: str = "t"):
+        """``atlas.image`` of "t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n" or "cluster_label" (float32 [H, W])."""
+        if what not in ("t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label"):
+            raise ValueError(f"no image of {what!r}")
+        vec = getattr(self, what)
+        if vec is None:
+            raise ValueError("the test ran without a cluster threshold")
+        return atlas.image(np.asarray(vec, np.float32), self.kind)
+
+
+def regression_batch(n_verts: int, n_knees: int, n_columns: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET) -> int:
+    """Index rows per batch of ``regression_test``: what fits ``budget`` bytes of its own workspace -- per row 8 bytes per vertex of t tile,
+    8 more of labels and sizes with clusters, and 8 (p + p (p + 1) / 2) bytes per knee of permuted design table -- rounded down to sixteen
+    rows (a multiple of every rows-per-thread of the t kernel), at least sixteen."""
+    p = int(n_columns)
+    per_row = int(n_verts) * (16 if clusters else 8) + int(n_knees) * 8 * (p + p * (p + 1) // 2)
+    rows = budget // per_row
+    return int(min(max(rows // _ROW_GROUP * _ROW_GROUP, _ROW_GROUP), max(int(n_permutations), 1)))
+
+
+def _design_columns(x, covariates, intercept: bool, n_knees: int) -> Tuple[np.ndarray, np.ndarray, float]:
+    """(nuisance [N, q], design [N, q + 1] with x last, the scale x was divided by); refuses what has no answer."""
+    x = np.asarray(x, np.float64)
+    if x.shape != (n_knees,):
+        raise ValueError(f"x must hold one entry per knee of the cohort ({n_knees}), got shape {x.shape}")
+    cov = np.zeros((n_knees, 0)) if covariates is None else np.asarray(covariates, np.float64)
+    cov = cov[:, None] if cov.ndim == 1 else cov
+    if cov.ndim != 2 or cov.shape[0] != n_knees:
+        raise ValueError(f"covariates must be [{n_knees}] or [{n_knees}, k], got shape {cov.shape}")
+    p = cov.shape[1] + 1 + int(bool(intercept))
+    if p > ops.MAX_DESIGN_COLUMNS:
+        raise ValueError(f"the design has {p} columns (intercept, covariates, x); at most {ops.MAX_DESIGN_COLUMNS} are supported")
+    if not (np.isfinite(x).all() and np.isfinite(cov).all()):
+        raise ValueError("the design holds a NaN or an infinity: x and the covariates must be finite for every knee")
+    cols = []
+    for name, c in [(f"covariate {k}", cov[:, k]) for k in range(cov.shape[1])] + [("x", x)]:
+        if (c == c[0]).all():
+            raise ValueError(f"{name} is constant over the knees")
+        c = c - c.mean() if intercept else c.copy()
+        norm = float(np.sqrt((c * c).sum()))
+        if not norm > 0.0:
+            raise ValueError(f"{name} is constant over the knees")
+        cols.append((c, norm))
+    scale = cols[-1][1]
+    Z = ([np.ones(n_knees)] if intercept else []) + [c / s for c, s in cols[:-1]]
+    nuisance = np.stack(Z, axis=1) if Z else np.zeros((n_knees, 0))
+    design = np.ascontiguousarray(np.concatenate([nuisance, (cols[-1][0] / scale)[:, None]], axis=1))
+    unit = design / np.sqrt((design * design).sum(axis=0))[None, :]
+    if n_knees < p or np.linalg.matrix_rank(unit) < p:
+        raise ValueError("the design (intercept, covariates, x) does not have full column rank over the knees")
+    return np.ascontiguousarray(nuisance), design, scale
+
+
+def _index_rows(permutations, make, n_knees: int) -> IndexPermutations:
+    perms = make() if permutations is None else permutations
+    if not isinstance(perms, IndexPermutations):
+        perms = IndexPermutations(np.asarray(perms))
+    index = np.atleast_2d(perms.index)
+    if index.ndim != 2 or index.shape[1] != n_knees or not np.issubdtype(index.dtype, np.integer):
+        raise ValueError(f"permutations must be integer rows [P, {n_knees}], got {index.dtype} {index.shape}")
+    if not np.array_equal(index[0], np.arange(n_knees)):
+        raise ValueError("row 0 of the permutations must be the identity")
+    if not np.array_equal(np.sort(index, axis=1), np.broadcast_to(np.arange(n_knees), index.shape)):
+        raise ValueError("every row of the permutations must be a permutation of 0 .. N - 1")
+    return IndexPermutations(np.ascontiguousarray(index, dtype=np.int32), perms.exact)
+
+
+def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool = True, n_permutations: int = 10000,
+                    cluster_threshold: Optional[float] = None, seed: int = 0, blocks=None, permutations=None,
+                    batch: Optional[int] = None) -> RegressionResult:
+    """How does thickness vary with ``x`` (one entry per knee: KL grade, BMI, years since baseline, or a 0 / 1 dummy), vertex by vertex,
+    adjusted for ``covariates`` ([N] or [N, k]: age, a sex dummy, ...) and, with ``intercept``, a constant?  Per vertex the general linear
+    model over the knees with a value there, and the t of the coefficient of ``x``; its null distribution comes from Freedman-Lane
+    permutation (include/oai_hip.h) with the rows of ``index_permutations(N, n_permutations, seed, blocks)``, or of ``permutations`` (an
+    ``IndexPermutations`` or int rows [P, N], row 0 the identity).  At most six design columns in all.  The columns are centred (with an
+    intercept) and scaled to unit length on the host, which changes neither t nor the p-values; ``slope`` is given per unit of the ``x``
+    that was passed.  ``cluster_threshold``, ``batch``: as in ``two_sample_test`` (default batch: ``regression_batch``)."""
+    N = len(cohort)
+    if N < 2:
+        raise ValueError("regression_test needs at least two knees")
+    nuisance, design, scale = _design_columns(x, covariates, bool(intercept), N)
+    perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
+    P, p = len(perms), design.shape[1]
+    values, mask = cohort.values, cohort.mask
+    V, dev = int(values.shape[1]), values.device
+    graph = None
+    if cluster_threshold is not None:
+        if not float(cluster_threshold) > 0.0:
+            raise ValueError(f"cluster_threshold must be > 0, got {cluster_threshold!r}")
+        graph = cohort.surface_graph()
+    rows = regression_batch(V, N, p, P, graph is not None) if batch is None else int(batch)
+    if rows < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    with torch.cuda.device(dev):
+        index = torch.from_numpy(perms.index).to(dev)
+        design_d = torch.from_numpy(design).to(dev)
+        prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
+        t0 = torch.empty(V, dtype=torch.float64, device=dev)
+        slope0 = torch.empty(V, dtype=torch.float64, device=dev)
+        max_abs = torch.empty(P, dtype=torch.float64, device=dev)
+        exceed = torch.empty(V, dtype=torch.int64, device=dev)
+        max_extent = torch.empty(P, dtype=torch.int32, device=dev) if graph is not None else None
+        label = size = None
+        ws = _lib.workspace("oai_regression_t", dev, min(rows, P), V, N, p)
+        for p0 in range(0, P, rows):
+            p1 = min(p0 + rows, P)
+            tile = ops.regression_t(prepared, design_d, index, p0, p1, workspace=ws, slope0=slope0 if p0 == 0 else None)
+            ops.permutation_reduce(tile, p0, t0, max_abs, exceed)
+            if graph is not None:
+                got = ops.graph_clusters(tile, graph[0], graph[1], float(cluster_threshold), max_extent=max_extent[p0:p1], return_labels=p0 == 0)
+                if p0 == 0:
+                    _, label, size = got
+        host = _download([t0, max_abs, exceed, slope0, prepared.n] + ([max_extent, label, size] if graph is not None else []))
+    t, max_abs, exceed, slope, n = host[:5]
+    max_extent, label, size = host[5:8] if graph is not None else (None, None, None)
+    dof = n.astype(np.int64) - p
+    with np.errstate(invalid="ignore", divide="ignore"):
+        partial_r = t / np.sqrt(t * t + dof.astype(np.float64))
+    p_unc, p_fwer = _p_values(t, max_abs, exceed, P)
+    res = RegressionResult(cohort.kind, t, n, dof, slope / scale, partial_r, p_unc, p_fwer, max_abs, P, perms.exact)
+    _set_clusters(res, cohort, t, P, cluster_threshold, max_extent, label, size)
+    return res
