@@ -1163,6 +1163,49 @@ int oai_regression_t(const void* prepared_dev, size_t prepared_bytes, const unsi
                      long long n_knees, long long n_verts, int n_columns, long long p0, long long p1, void* workspace_dev, size_t workspace_bytes,
                      double* slope0_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Threshold-free cluster enhancement (csrc/graph_tfce.hip, tests/graph_tfce_ref.py): a t tile in, a tile of the same shape out in which
+ * every vertex holds the integral, over all thresholds h at or below its |t|, of extent(h)^E * h^H -- extent(h) being the size of the
+ * vertex' connected component of {|t| >= h} on the surface.  It takes the place of a hand-picked cluster threshold: the family-wise p
+ * comes from the permutation distribution of the row maximum, which oai_permutation_reduce forms from the TFCE tile as it does from a t
+ * tile.  The scheme is Smith and Nichols' (NeuroImage 44, 2009), with PALM's surface setting (E = 1, H = 2, extent as area) as the
+ * default, AS RECALLED and NOT pinned to any implementation: the definition below is this library's own, pinned by the brute-force numpy
+ * restatement, which runs scipy's connected components from scratch at every level.  Its limits: the integral is a right-endpoint sum
+ * with a FIXED step dh; E is 1/2 or 1 and H is 1 or 2; the sum stops at max_steps levels and reports what it cut.  The rules of "Cohort
+ * statistics" hold: fp64 without contraction, no floating-point atomics, one accumulator per sum that starts at +0.0: bit-reproducible.
+ * The entry point does not synchronise and reads nothing back.  1 <= n_rows <= 2^20, 1 <= n_verts <= 2^31 - 2.
+ *
+ * Inputs.  values_dev float64 [n_rows][n_verts]; the CSR adjacency as in oai_graph_clusters (an offset outside [0, n_neighbours] is
+ * clamped, a neighbour outside [0, n_verts) is ignored).  weight_dev int64 [n_verts], each >= 0, or null: every weight is 1; the caller
+ * guarantees sum(weight) < 2^53.  unit > 0: what one unit of weight is worth (1 for vertex counts, 2^-20 mm^2 for areas in 2^-20 mm^2).
+ * dh finite and > 0.  e_mode OAI_TFCE_E_HALF | OAI_TFCE_E_ONE, h_mode OAI_TFCE_H_ONE | OAI_TFCE_H_TWO.  1 <= max_steps <= 65536.
+ * tfce_dev must not overlap values_dev.
+ *
+ * Per row and vertex v, with t = values[row][v]:
+ *   a = |t|;  side = +1 if t > 0, -1 if t < 0, 0 for +-0 and NaN
+ *   h_k = (double)k * dh, k = 1 .. max_steps                 (one multiplication: h_k does not decrease with k)
+ *   v is ACTIVE AT LEVEL k iff side != 0 and a >= h_k         (not strict; NaN is never active, +-inf is at every level)
+ *   at level k the graph keeps an edge u - v iff both ends are active and of the same side: adjacent vertices of opposite sign never join
+ *   W_k(v) = the int64 sum of the weights of v's component at level k     (an integer sum: no order to state)
+ *   e = (double)W_k(v) * unit;   eE = e (E = 1) or sqrt(e) (E = 1/2);   hH = h_k (H = 1) or h_k * h_k (H = 2);   c_k = (eE * hH) * dh
+ *   K(v) = the largest k <= max_steps at which v is active, 0 if there is none
+ *   acc = +0.0;  acc = acc + c_k for k = K(v) down to 1       (DESCENDING: the order is part of the contract.  Components only grow as
+ *                                                              the threshold falls, so one union-find per row serves every level.)
+ *   tfce(v) = NaN where t is NaN;  acc where side >= 0;  -acc where side < 0  (so -0.0 for a negative t below dh)
+ * clipped_dev int32 [n_rows]: the vertices of the row with a >= (double)(max_steps + 1) * dh, whose integral was cut; infinities count.
+ * One workgroup per row; parent, level and component weight live in the workspace, so n_verts is not bounded by LDS.
+ * ---------------------------------------------------------------------------------------- */
+#define OAI_TFCE_E_HALF 0
+#define OAI_TFCE_E_ONE 1
+#define OAI_TFCE_H_ONE 0
+#define OAI_TFCE_H_TWO 1
+/* 0 for a shape the entry point refuses. */
+size_t oai_graph_tfce_workspace_bytes(long long n_rows, long long n_verts);
+int oai_graph_tfce(const double* values_dev, long long n_rows, long long n_verts, const int* offsets_dev, const int* neighbours_dev,
+                   long long n_neighbours, const long long* weight_dev, double unit, double dh, int e_mode, int h_mode, int max_steps,
+                   void* workspace_dev, size_t workspace_bytes, double* tfce_dev, int* clipped_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

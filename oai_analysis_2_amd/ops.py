@@ -8,6 +8,7 @@ the output tensor.  No torch compute op is used on the product path.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -610,6 +611,10 @@ def region_stats(values: torch.Tensor, weights: torch.Tensor, labels: Optional[t
 
 # ---- cohort statistics (include/oai_hip.h, "Cohort statistics"; csrc/group_stats.hip) -----------------------------------------------------
 STATS_TWO_SAMPLE, STATS_ONE_SAMPLE = 0, 1
+OAI_TFCE_E_HALF, OAI_TFCE_E_ONE = 0, 1
+OAI_TFCE_H_ONE, OAI_TFCE_H_TWO = 0, 1
+TFCE_E_MODES = {0.5: OAI_TFCE_E_HALF, 1.0: OAI_TFCE_E_ONE}
+TFCE_H_MODES = {1.0: OAI_TFCE_H_ONE, 2.0: OAI_TFCE_H_TWO}
 
 
 @dataclass
@@ -732,6 +737,47 @@ def graph_clusters(values: torch.Tensor, offsets: torch.Tensor, neighbours: torc
     _lib.call("oai_graph_clusters", values.data_ptr(), R, V, offsets.data_ptr(), _ptr(neighbours, neighbours.numel()), int(neighbours.numel()),
               float(threshold), ws.data_ptr(), ws.numel(), ext.data_ptr(), _ptr(label), _ptr(size), _lib.STREAM, device=values.device)
     return (ext, label, size) if return_labels else ext
+
+
+def graph_tfce(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.Tensor, dh: float = 0.1, E: float = 1.0, H: float = 2.0,
+               weights: Optional[torch.Tensor] = None, unit: float = 1.0, max_steps: int = 1000, out: Optional[torch.Tensor] = None,
+               clipped: Optional[torch.Tensor] = None):
+    """Threshold-free cluster enhancement of every row of the float64 ``values`` [R,V] on the graph given as in ``graph_clusters``
+    (include/oai_hip.h, "Threshold-free cluster enhancement"): per vertex the sum over the levels k * ``dh`` <= |value| of
+    extent^E * level^H * dh, with the sign of the value.  The extent of a vertex at a level is the summed int64 ``weights`` [V] of its
+    component times ``unit``, or the component's vertex count without weights.  E is 0.5 or 1, H is 1 or 2.  Returns the float64 [R,V]
+    and int32 [R] DEVICE tensors (tfce, clipped): ``clipped`` counts the row's vertices whose |value| reaches past ``max_steps`` levels
+    (``out``, ``clipped``: written there).  Bit-reproducible.  Does not synchronise."""
+    values = _chk(values, "values", torch.float64)
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"values must be [R >= 1, V >= 1], got {tuple(values.shape)}")
+    R, V = int(values.shape[0]), int(values.shape[1])
+    offsets, neighbours = _chk(offsets, "offsets", torch.int32), _chk(neighbours, "neighbours", torch.int32)
+    if offsets.numel() != V + 1 or offsets.device != values.device or neighbours.device != values.device:
+        raise ValueError(f"offsets must be [{V + 1}] and live with neighbours on the values' GPU, got {offsets.numel()} on {offsets.device}")
+    if float(E) not in TFCE_E_MODES or float(H) not in TFCE_H_MODES:
+        raise ValueError(f"E must be 0.5 or 1 and H must be 1 or 2, got E = {E!r}, H = {H!r}")
+    if not (float(dh) > 0.0 and math.isfinite(float(dh))):
+        raise ValueError(f"dh must be finite and > 0, got {dh!r}")
+    if not float(unit) > 0.0:
+        raise ValueError(f"unit must be > 0, got {unit!r}")
+    if not 1 <= int(max_steps) <= 65536:
+        raise ValueError(f"max_steps must be 1 .. 65536, got {max_steps!r}")
+    if weights is not None:
+        weights = _chk(weights, "weights", torch.int64)
+        if tuple(weights.shape) != (V,) or weights.device != values.device:
+            raise ValueError(f"weights must be int64 [{V}] on the values' GPU, got {tuple(weights.shape)} on {weights.device}")
+    if out is None:
+        out = torch.empty((R, V), dtype=torch.float64, device=values.device)
+    elif (out.device != values.device or out.dtype != torch.float64 or tuple(out.shape) != (R, V) or not out.is_contiguous()
+          or out.data_ptr() == values.data_ptr()):
+        raise ValueError(f"out must be a contiguous float64 [{R}, {V}] tensor on {values.device} other than values")
+    clip = _out_slot(clipped, R, torch.int32, values.device, "clipped")
+    ws = _lib.workspace("oai_graph_tfce", values.device, R, V)
+    _lib.call("oai_graph_tfce", values.data_ptr(), R, V, offsets.data_ptr(), _ptr(neighbours, neighbours.numel()), int(neighbours.numel()),
+              _ptr(weights), float(unit), float(dh), TFCE_E_MODES[float(E)], TFCE_H_MODES[float(H)], int(max_steps), ws.data_ptr(), ws.numel(),
+              out.data_ptr(), clip.data_ptr(), _lib.STREAM, device=values.device)
+    return out, clip
 
 
 # ---- cohort regression (include/oai_hip.h, "Cohort regression"; csrc/group_regression.hip) ---------------------------------------------------

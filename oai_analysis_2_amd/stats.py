@@ -21,6 +21,10 @@ csrc/group_regression.hip; tests/group_regression_ref.py).
 
     res = regression_test(cohort, kl_grade, covariates=np.stack([age, sex], axis=1), n_permutations=10000, cluster_threshold=3.0)
     res.slope, res.partial_r, res.p_fwer
+
+``tfce=True`` (or a ``TFCE``) on any of the three adds threshold-free cluster enhancement (include/oai_hip.h, "Threshold-free cluster
+enhancement"; csrc/graph_tfce.hip; tests/graph_tfce_ref.py): every labelling's t tile is integrated over all thresholds on the device and
+``res.p_tfce`` is the family-wise p of the enhanced statistic -- sensitive to broad weak effects without a hand-picked threshold.
 """
 from __future__ import annotations
 
@@ -219,6 +223,83 @@ class ThicknessCohort:
 
 
 # ---- the tests -------------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class TFCE:
+    """The settings of threshold-free cluster enhancement (include/oai_hip.h): the step ``dh`` of the threshold in units of t, the exponents
+    ``E`` (0.5 or 1) of the extent and ``H`` (1 or 2) of the height, what ``extent`` is -- "area": mm^2 of the atlas inner surface, kept
+    as integers in units of 2^-20 mm^2; "vertices": a count -- and ``max_steps``, the number of levels after which the integral is cut
+    (``tfce_clipped`` reports it).  The defaults are the surface defaults of PALM as recalled (E = 1, H = 2, area)."""
+    dh: float = 0.1
+    E: float = 1.0
+    H: float = 2.0
+    extent: str = "area"
+    max_steps: int = 1000
+
+
+_TFCE_AREA_UNIT = 2.0 ** -20          # mm^2 per unit of integer vertex weight: a power of two, so weight * unit is exact
+_TFCE_BYTES = 8 + 16                  # per (labelling, vertex): the TFCE tile and oai_graph_tfce_workspace_bytes
+
+
+def _tfce_settings(tfce) -> Optional[TFCE]:
+    """None / False -> None, True -> the defaults, a ``TFCE`` -> itself; refuses what the kernel would, before anything is launched."""
+    if tfce is None or tfce is False:
+        return None
+    settings = TFCE() if tfce is True else tfce
+    if not isinstance(settings, TFCE):
+        raise ValueError(f"tfce must be None, True or a TFCE, got {tfce!r}")
+    if settings.E not in (0.5, 1.0) or settings.H not in (1.0, 2.0):
+        raise ValueError(f"TFCE: E must be 0.5 or 1 and H must be 1 or 2, got E = {settings.E!r}, H = {settings.H!r}")
+    if not (isinstance(settings.dh, (int, float)) and settings.dh > 0.0 and math.isfinite(settings.dh)):
+        raise ValueError(f"TFCE: dh must be finite and > 0, got {settings.dh!r}")
+    if settings.extent not in ("area", "vertices"):
+        raise ValueError(f'TFCE: extent must be "area" or "vertices", got {settings.extent!r}')
+    if not 1 <= int(settings.max_steps) <= 65536:
+        raise ValueError(f"TFCE: max_steps must be 1 .. 65536, got {settings.max_steps!r}")
+    return settings
+
+
+def tfce_weights(areas: np.ndarray) -> np.ndarray:
+    """int64 [V]: vertex areas in mm^2 as integers in units of 2^-20 mm^2 (round half to even), what ``extent="area"`` sums."""
+    weights = np.rint(np.asarray(areas, np.float64) * 2.0 ** 20).astype(np.int64)
+    if not (weights >= 0).all() or not sum(weights.tolist()) < 2 ** 53:          # Python ints: no wrap
+        raise ValueError("TFCE: the vertex areas must be >= 0 and sum to less than 2^53 units of 2^-20 mm^2")
+    return weights
+
+
+class _Tfce:
+    """The device side of one test's TFCE: the settings, the graph, the weights (uploaded once) and the running results."""
+
+    def __init__(self, settings: TFCE, cohort_like, P: int, V: int, rows: int, dev):
+        self.settings = settings
+        self.graph = cohort_like.surface_graph()
+        self.weights, self.unit = None, 1.0
+        if settings.extent == "area":
+            self.weights, self.unit = torch.from_numpy(tfce_weights(cohort_like.vertex_areas())).to(dev), _TFCE_AREA_UNIT
+        self.tile = torch.empty((min(rows, P), V), dtype=torch.float64, device=dev)
+        self.tfce0 = torch.empty(V, dtype=torch.float64, device=dev)
+        self.max_tfce = torch.empty(P, dtype=torch.float64, device=dev)
+        self.exceed = torch.empty(V, dtype=torch.int64, device=dev)
+        self.clipped = torch.empty(P, dtype=torch.int32, device=dev)
+
+    def batch(self, tile: torch.Tensor, p0: int, p1: int) -> None:
+        s = self.settings
+        enhanced, _ = ops.graph_tfce(tile, self.graph[0], self.graph[1], dh=s.dh, E=s.E, H=s.H, weights=self.weights, unit=self.unit,
+                                     max_steps=int(s.max_steps), out=self.tile[:p1 - p0], clipped=self.clipped[p0:p1])
+        ops.permutation_reduce(enhanced, p0, self.tfce0, self.max_tfce, self.exceed)
+
+    def tensors(self) -> List[torch.Tensor]:
+        return [self.tfce0, self.max_tfce, self.exceed, self.clipped]
+
+
+def _set_tfce(res, settings: Optional[TFCE], host, P: int) -> None:
+    """The TFCE fields of a result, from the downloaded (tfce0, max_tfce, exceed, clipped)."""
+    if settings is None:
+        return
+    tfce0, max_tfce, exceed, clipped = host
+    res.tfce, res.max_tfce, res.tfce_clipped, res.tfce_settings = tfce0, max_tfce, int(np.count_nonzero(clipped)), settings
+    res.p_tfce_uncorrected, res.p_tfce = _p_values(tfce0, max_tfce, exceed, P)
+
+
 @dataclass
 class Cluster:
     label: int               # the cluster's smallest vertex index: its value in ``cluster_label``
@@ -235,7 +316,11 @@ class PermutationResult:
     ``p_uncorrected`` = share of labellings with |t| at least the observed at that vertex; ``p_fwer`` = share of labellings whose max |t|
     over the surface is at least the observed |t| at that vertex (both NaN where t is); ``max_abs`` the null distribution of max |t|,
     one entry per labelling, entry 0 observed.  With a cluster threshold: ``cluster_label`` int32 [V] (-1 outside every cluster),
-    ``clusters`` in ascending label, ``max_extent`` the null distribution of the largest cluster's extent."""
+    ``clusters`` in ascending label, ``max_extent`` the null distribution of the largest cluster's extent.  With ``tfce``: ``tfce`` float64
+    [V], the enhanced statistic with the sign of t (NaN where t is); ``p_tfce`` = share of labellings whose max |TFCE| over the surface is
+    at least the observed |TFCE| at that vertex, ``p_tfce_uncorrected`` the vertex-wise share; ``max_tfce`` the null distribution of
+    max |TFCE|; ``tfce_clipped`` the number of labellings with a vertex whose |t| reached past ``max_steps`` levels (0 unless t is huge or
+    infinite: raise ``max_steps`` or ``dh`` otherwise); ``tfce_settings`` the ``TFCE`` that was used."""
     kind: str
     t: np.ndarray
     n1: np.ndarray
@@ -250,21 +335,29 @@ class PermutationResult:
     cluster_label: Optional[np.ndarray] = None
     clusters: List[Cluster] = field(default_factory=list)
     max_extent: Optional[np.ndarray] = None
+    tfce: Optional[np.ndarray] = None
+    p_tfce: Optional[np.ndarray] = None
+    p_tfce_uncorrected: Optional[np.ndarray] = None
+    max_tfce: Optional[np.ndarray] = None
+    tfce_clipped: int = 0
+    tfce_settings: Optional["TFCE"] = None
 
     def image(self, atlas, what: str = "t"):
-        """``atlas.image`` of "t", "p_fwer", "p_uncorrected", "mean_difference" or "cluster_label" (float32 [H, W], NaN off the surface)."""
-        if what not in ("t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label"):
+        """``atlas.image`` of "t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label", "tfce" or "p_tfce" (float32 [H, W], NaN off
+        the surface)."""
+        if what not in ("t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label", "tfce", "p_tfce"):
             raise ValueError(f"no image of {what!r}")
         vec = getattr(self, what)
         if vec is None:
-            raise ValueError("the test ran without a cluster threshold")
+            raise ValueError("the test ran without tfce" if "tfce" in what else "the test ran without a cluster threshold")
         return atlas.image(np.asarray(vec, np.float32), self.kind)
 
 
-def default_batch(n_verts: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET) -> int:
-    """Labellings per batch: what fits ``budget`` bytes of workspace -- 8 bytes per (labelling, vertex) of t tile, and 8 more of labels and
-    sizes with clusters -- rounded down to the t kernel's sixteen rows per thread, at least sixteen."""
-    rows = budget // (int(n_verts) * (16 if clusters else 8))
+def default_batch(n_verts: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET, tfce: bool = False) -> int:
+    """Labellings per batch: what fits ``budget`` bytes of workspace -- 8 bytes per (labelling, vertex) of t tile, 8 more of labels and
+    sizes with clusters, and 24 more of TFCE tile and union-find with ``tfce`` -- rounded down to the t kernel's sixteen rows per thread,
+    at least sixteen."""
+    rows = budget // (int(n_verts) * ((16 if clusters else 8) + (_TFCE_BYTES if tfce else 0)))
     return int(min(max(rows // _ROW_GROUP * _ROW_GROUP, _ROW_GROUP), max(int(n_permutations), 1)))
 
 
@@ -280,10 +373,10 @@ def _download(tensors: Sequence[torch.Tensor]) -> List[np.ndarray]:
 
 
 def _run(cohort_like, values: torch.Tensor, mask: Optional[torch.Tensor], perms: Permutations, mode: int, cluster_threshold: Optional[float],
-         batch: Optional[int], extra):
+         batch: Optional[int], extra, tfce: Optional[TFCE] = None):
     """The batches of one test, queued without a synchronisation; returns the host arrays of (t0, max_abs, exceed, max_extent | None,
-    label | None, size | None, *extra) after one download.  ``extra``: device tensors to bring along, or a function of the prepared block
-    that names them."""
+    label | None, size | None, *extra) after one download, and those of TFCE (tfce0, max_tfce, exceed, clipped), or None without
+    ``tfce``.  ``extra``: device tensors to bring along, or a function of the prepared block that names them."""
     N, V = int(values.shape[0]), int(values.shape[1])
     if perms.n_knees != N:
         raise ValueError(f"the labellings are for {perms.n_knees} knees, the cohort has {N}")
@@ -294,10 +387,11 @@ def _run(cohort_like, values: torch.Tensor, mask: Optional[torch.Tensor], perms:
         if not float(cluster_threshold) > 0.0:
             raise ValueError(f"cluster_threshold must be > 0, got {cluster_threshold!r}")
         graph = cohort_like.surface_graph()
-    rows = default_batch(V, P, graph is not None) if batch is None else int(batch)
+    rows = default_batch(V, P, graph is not None, tfce=tfce is not None) if batch is None else int(batch)
     if rows < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
     with torch.cuda.device(dev):
+        enhance = _Tfce(tfce, cohort_like, P, V, rows, dev) if tfce is not None else None
         bits = torch.from_numpy(np.ascontiguousarray(perms.bits).view(np.int32)).to(dev)
         prepared = ops.group_prepare(values, mask, centre=mode == ops.STATS_TWO_SAMPLE)
         t0 = torch.empty(V, dtype=torch.float64, device=dev)
@@ -314,11 +408,14 @@ def _run(cohort_like, values: torch.Tensor, mask: Optional[torch.Tensor], perms:
                 got = ops.graph_clusters(tile, graph[0], graph[1], float(cluster_threshold), max_extent=max_extent[p0:p1], return_labels=p0 == 0)
                 if p0 == 0:
                     _, label, size = got
+            if enhance is not None:
+                enhance.batch(tile, p0, p1)
         out = [t0, max_abs, exceed] + ([max_extent, label, size] if graph is not None else []) + list(extra(prepared) if callable(extra) else extra)
-        host = _download(out)
+        host = _download(out + (enhance.tensors() if enhance is not None else []))
+    host, tfce_host = (host[:len(out)], host[len(out):]) if enhance is not None else (host, None)
     if graph is None:
         host[3:3] = [None, None, None]
-    return host
+    return host, tfce_host
 
 
 def _p_values(t: np.ndarray, max_abs: np.ndarray, exceed: np.ndarray, P: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -345,12 +442,14 @@ def _set_clusters(res, cohort_like, t, P: int, cluster_threshold, max_extent, la
                                     float(P - np.searchsorted(extents, extent, side="left")) / float(P)))
 
 
-def _finish(kind: str, cohort_like, perms: Permutations, host, n1, n2, mean_difference, cluster_threshold) -> PermutationResult:
+def _finish(kind: str, cohort_like, perms: Permutations, host, n1, n2, mean_difference, cluster_threshold, tfce=None,
+            tfce_host=None) -> PermutationResult:
     t, max_abs, exceed, max_extent, label, size = host[:6]
     P = len(perms)
     p_unc, p_fwer = _p_values(t, max_abs, exceed, P)
     res = PermutationResult(kind, t, n1, n2, mean_difference, p_unc, p_fwer, max_abs, P, perms.exact)
     _set_clusters(res, cohort_like, t, P, cluster_threshold, max_extent, label, size)
+    _set_tfce(res, tfce, tfce_host, P)
     return res
 
 
@@ -366,12 +465,15 @@ def _permutations(perms, make, n_knees: int) -> Permutations:
 
 
 def two_sample_test(cohort: ThicknessCohort, groups, n_permutations: int = 10000, cluster_threshold: Optional[float] = None, seed: int = 0,
-                    blocks=None, permutations=None, batch: Optional[int] = None) -> PermutationResult:
+                    blocks=None, permutations=None, batch: Optional[int] = None, tfce=None) -> PermutationResult:
     """Where do the knees of group 1 (``groups[i]`` = 1) differ from those of group 2 (= 0)?  Student's pooled t per vertex; its null
     distribution comes from ``label_permutations(groups, n_permutations, seed, blocks)``, or from ``permutations`` -- a ``Permutations``,
     packed uint32 rows or bool [P, N] with the observed labelling as row 0 -- for designs that does not cover.  ``cluster_threshold``
     (a |t| value): also clusters of supra-threshold vertices on the atlas surface and their extent-based p-values.  ``batch``: labellings
-    per launch; default ``default_batch``.  A vertex where a group has fewer than two knees with a value has no t (NaN)."""
+    per launch; default ``default_batch``.  ``tfce``: True or a ``TFCE`` adds threshold-free cluster enhancement of every labelling's t
+    and the ``tfce`` fields of the result; it may be given together with ``cluster_threshold``.  A vertex where a group has fewer than two
+    knees with a value has no t (NaN)."""
+    tfce = _tfce_settings(tfce)
     g = _as_groups(groups)
     if len(g) != len(cohort):
         raise ValueError(f"groups must hold one entry per knee of the cohort ({len(cohort)}), got {len(g)}")
@@ -386,16 +488,18 @@ def two_sample_test(cohort: ThicknessCohort, groups, n_permutations: int = 10000
         idx = torch.from_numpy(np.nonzero(member)[0]).to(values.device)
         prep = ops.group_prepare(values.index_select(0, idx), mask.index_select(0, idx))
         sides += [prep.n, prep.mean]
-    host = _run(cohort, values, mask, perms, ops.STATS_TWO_SAMPLE, cluster_threshold, batch, sides)
+    host, tfce_host = _run(cohort, values, mask, perms, ops.STATS_TWO_SAMPLE, cluster_threshold, batch, sides, tfce)
     n1, mean1, n2, mean2 = host[6:10]
-    return _finish(cohort.kind, cohort, perms, host, n1, n2, mean1 - mean2, cluster_threshold)
+    return _finish(cohort.kind, cohort, perms, host, n1, n2, mean1 - mean2, cluster_threshold, tfce, tfce_host)
 
 
 def paired_test(cohort_a: ThicknessCohort, cohort_b: ThicknessCohort, n_permutations: int = 10000, cluster_threshold: Optional[float] = None,
-                seed: int = 0, permutations=None, batch: Optional[int] = None) -> PermutationResult:
+                seed: int = 0, permutations=None, batch: Optional[int] = None, tfce=None) -> PermutationResult:
     """Where does ``cohort_a`` differ from ``cohort_b`` within a knee (follow-up against baseline)?  Rows are matched by id (every id of
     either cohort must be in the other, once); the difference a - b is taken on the device and is missing where either side is; the
-    statistic is the one-sample t of the differences and its null distribution comes from ``sign_flips``."""
+    statistic is the one-sample t of the differences and its null distribution comes from ``sign_flips``.  ``tfce``: as in
+    ``two_sample_test``."""
+    tfce = _tfce_settings(tfce)
     if cohort_a.kind != cohort_b.kind or cohort_a.n_verts != cohort_b.n_verts or cohort_a.device != cohort_b.device:
         raise ValueError("the two cohorts must hold the same cartilage of the same atlas on the same GPU")
     where_b = {id_: k for k, id_ in enumerate(cohort_b.ids)}
@@ -410,9 +514,10 @@ def paired_test(cohort_a: ThicknessCohort, cohort_b: ThicknessCohort, n_permutat
     perms = _permutations(permutations, lambda: sign_flips(N, n_permutations, seed), N)
     if perms.rows()[0].any():
         raise ValueError("row 0 of the permutations must flip nothing")
-    host = _run(cohort_a, diff, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, batch, lambda prepared: [prepared.n, prepared.mean])
+    host, tfce_host = _run(cohort_a, diff, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, batch, lambda prepared: [prepared.n, prepared.mean],
+                           tfce)
     n, mean = host[6:8]
-    return _finish(cohort_a.kind, cohort_a, perms, host, n, n.copy(), mean, cluster_threshold)
+    return _finish(cohort_a.kind, cohort_a, perms, host, n, n.copy(), mean, cluster_threshold, tfce, tfce_host)
 
 
 # ---- regression ------------------------------------------------------------------------------------------------------------------------
@@ -462,7 +567,7 @@ class RegressionResult:
     """``t`` float64 [V]: the t of the regressor's coefficient (NaN where no t exists: too few knees with a value, a design that loses its
     rank among them, no residual variance); ``n`` the knees with a value and ``dof`` = n - p per vertex; ``slope`` in mm per unit of ``x``;
     ``partial_r`` = t / sqrt(t^2 + dof), the partial correlation of thickness and x given the covariates; the p-values, ``max_abs`` and the
-    cluster fields as in ``PermutationResult``."""
+    cluster and TFCE fields as in ``PermutationResult``."""
     kind: str
     t: np.ndarray
     n: np.ndarray
@@ -478,23 +583,30 @@ class RegressionResult:
     cluster_label: Optional[np.ndarray] = None
     clusters: List[Cluster] = field(default_factory=list)
     max_extent: Optional[np.ndarray] = None
+    tfce: Optional[np.ndarray] = None
+    p_tfce: Optional[np.ndarray] = None
+    p_tfce_uncorrected: Optional[np.ndarray] = None
+    max_tfce: Optional[np.ndarray] = None
+    tfce_clipped: int = 0
+    tfce_settings: Optional["TFCE"] = None
 
     def image(self, atlas, what: str = "t"):
-        """``atlas.image`` of "t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n" or "cluster_label" (float32 [H, W])."""
-        if what not in ("t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label"):
+        """``atlas.image`` of "t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce" or "p_tfce" (float32 [H, W])."""
+        if what not in ("t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce", "p_tfce"):
             raise ValueError(f"no image of {what!r}")
         vec = getattr(self, what)
         if vec is None:
-            raise ValueError("the test ran without a cluster threshold")
+            raise ValueError("the test ran without tfce" if "tfce" in what else "the test ran without a cluster threshold")
         return atlas.image(np.asarray(vec, np.float32), self.kind)
 
 
-def regression_batch(n_verts: int, n_knees: int, n_columns: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET) -> int:
+def regression_batch(n_verts: int, n_knees: int, n_columns: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET,
+                     tfce: bool = False) -> int:
     """Index rows per batch of ``regression_test``: what fits ``budget`` bytes of its own workspace -- per row 8 bytes per vertex of t tile,
-    8 more of labels and sizes with clusters, and 8 (p + p (p + 1) / 2) bytes per knee of permuted design table -- rounded down to sixteen
-    rows (a multiple of every rows-per-thread of the t kernel), at least sixteen."""
+    8 more of labels and sizes with clusters, 24 more of TFCE tile and union-find with ``tfce``, and 8 (p + p (p + 1) / 2) bytes per knee of
+    permuted design table -- rounded down to sixteen rows (a multiple of every rows-per-thread of the t kernel), at least sixteen."""
     p = int(n_columns)
-    per_row = int(n_verts) * (16 if clusters else 8) + int(n_knees) * 8 * (p + p * (p + 1) // 2)
+    per_row = int(n_verts) * ((16 if clusters else 8) + (_TFCE_BYTES if tfce else 0)) + int(n_knees) * 8 * (p + p * (p + 1) // 2)
     rows = budget // per_row
     return int(min(max(rows // _ROW_GROUP * _ROW_GROUP, _ROW_GROUP), max(int(n_permutations), 1)))
 
@@ -548,14 +660,15 @@ def _index_rows(permutations, make, n_knees: int) -> IndexPermutations:
 
 def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool = True, n_permutations: int = 10000,
                     cluster_threshold: Optional[float] = None, seed: int = 0, blocks=None, permutations=None,
-                    batch: Optional[int] = None) -> RegressionResult:
+                    batch: Optional[int] = None, tfce=None) -> RegressionResult:
     """How does thickness vary with ``x`` (one entry per knee: KL grade, BMI, years since baseline, or a 0 / 1 dummy), vertex by vertex,
     adjusted for ``covariates`` ([N] or [N, k]: age, a sex dummy, ...) and, with ``intercept``, a constant?  Per vertex the general linear
     model over the knees with a value there, and the t of the coefficient of ``x``; its null distribution comes from Freedman-Lane
     permutation (include/oai_hip.h) with the rows of ``index_permutations(N, n_permutations, seed, blocks)``, or of ``permutations`` (an
     ``IndexPermutations`` or int rows [P, N], row 0 the identity).  At most six design columns in all.  The columns are centred (with an
     intercept) and scaled to unit length on the host, which changes neither t nor the p-values; ``slope`` is given per unit of the ``x``
-    that was passed.  ``cluster_threshold``, ``batch``: as in ``two_sample_test`` (default batch: ``regression_batch``)."""
+    that was passed.  ``cluster_threshold``, ``batch``, ``tfce``: as in ``two_sample_test`` (default batch: ``regression_batch``)."""
+    tfce = _tfce_settings(tfce)
     N = len(cohort)
     if N < 2:
         raise ValueError("regression_test needs at least two knees")
@@ -569,10 +682,11 @@ def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool
         if not float(cluster_threshold) > 0.0:
             raise ValueError(f"cluster_threshold must be > 0, got {cluster_threshold!r}")
         graph = cohort.surface_graph()
-    rows = regression_batch(V, N, p, P, graph is not None) if batch is None else int(batch)
+    rows = regression_batch(V, N, p, P, graph is not None, tfce=tfce is not None) if batch is None else int(batch)
     if rows < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
     with torch.cuda.device(dev):
+        enhance = _Tfce(tfce, cohort, P, V, rows, dev) if tfce is not None else None
         index = torch.from_numpy(perms.index).to(dev)
         design_d = torch.from_numpy(design).to(dev)
         prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
@@ -591,7 +705,10 @@ def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool
                 got = ops.graph_clusters(tile, graph[0], graph[1], float(cluster_threshold), max_extent=max_extent[p0:p1], return_labels=p0 == 0)
                 if p0 == 0:
                     _, label, size = got
-        host = _download([t0, max_abs, exceed, slope0, prepared.n] + ([max_extent, label, size] if graph is not None else []))
+            if enhance is not None:
+                enhance.batch(tile, p0, p1)
+        host = _download([t0, max_abs, exceed, slope0, prepared.n] + ([max_extent, label, size] if graph is not None else [])
+                         + (enhance.tensors() if enhance is not None else []))
     t, max_abs, exceed, slope, n = host[:5]
     max_extent, label, size = host[5:8] if graph is not None else (None, None, None)
     dof = n.astype(np.int64) - p
@@ -600,4 +717,5 @@ def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool
     p_unc, p_fwer = _p_values(t, max_abs, exceed, P)
     res = RegressionResult(cohort.kind, t, n, dof, slope / scale, partial_r, p_unc, p_fwer, max_abs, P, perms.exact)
     _set_clusters(res, cohort, t, P, cluster_threshold, max_extent, label, size)
+    _set_tfce(res, tfce, host[-4:] if tfce is not None else None, P)
     return res

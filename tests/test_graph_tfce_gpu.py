@@ -1,0 +1,376 @@
+"""GPU: threshold-free cluster enhancement (csrc/graph_tfce.hip) against its brute-force restatement (tests/graph_tfce_ref.py), to the bit
+-- every float64 is the result of IEEE multiply, add and sqrt in a stated order and every extent an integer sum -- and ``tfce=`` of
+oai_analysis_2_amd.stats end to end on a small sphere."""
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import graph_tfce_ref as tref
+import group_stats_ref as gref
+
+pytestmark = pytest.mark.gpu
+
+DH, STEPS = 0.25, 40                              # levels 0.25 .. 10.0; a value from 10.25 on is clipped
+MODES = ((1.0, 2.0), (1.0, 1.0), (0.5, 2.0), (0.5, 1.0))
+UNIT = 2.0 ** -20
+
+
+def _same_bits(got, want, what):
+    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
+    if got.dtype == np.float64:
+        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
+        got, want = np.where(np.isnan(got), 0.0, got).view(np.int64), np.where(np.isnan(want), 0.0, want).view(np.int64)
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
+
+
+@functools.lru_cache(maxsize=None)
+def _icosphere(level=3):
+    """(verts float32 [n, 3] on the unit sphere, faces int32 [m, 3]): 642 vertices and 1280 faces at level 3."""
+    g = (1 + 5 ** 0.5) / 2
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
+    for _ in range(level):
+        mid, nf = {}, []
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                p = v[a] + v[b]
+                v.append(p / np.linalg.norm(p))
+                mid[key] = len(v) - 1
+            return mid[key]
+        for a, b, c in f:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    return np.asarray(v, np.float32), np.asarray(f, np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def _graph(name):
+    """(offsets, neighbours) on the host; the sphere's are those of ``mesh_processing.vertex_adjacency_device``."""
+    from oai_analysis_2_amd import mesh_processing as mp
+    if name == "path_3000":
+        return tref.path_graph(3000)
+    verts, faces = _icosphere()
+    off_d, nbr_d = mp.vertex_adjacency_device(len(verts), torch.from_numpy(faces).cuda())
+    return off_d.cpu().numpy(), nbr_d.cpu().numpy()
+
+
+def _hand_tile(V, seed):
+    """Eight rows written by hand (vertex indices; on the path index neighbours are graph neighbours):
+    0  nested plateaus (3.0 inside 1.5), a value exactly at a level (2.0) and the double below it side by side, a NaN that splits a run,
+       a negative run touching a positive one, +inf, -inf and 1e300 (the three clipped values), +0.0, -0.0 and +-0.1 (below dh);
+    1  everything below dh;   2  all NaN;
+    3  a ramp rising with the vertex index: the top vertex activates first and every level adds smaller indices, so the component's
+       root moves at every level;
+    4  a ramp falling with the vertex index: vertex 0 is the root from the top level on while the component grows;
+    5  two hills that merge at a saddle, the hill of larger indices the heavier one;   6  alternating signs;   7  N(0, 2) noise."""
+    rng = np.random.default_rng(seed)
+    tile = np.zeros((8, V))
+    row = tile[0]
+    row[:] = np.where(rng.random(V) < 0.5, 0.1, -0.1)
+    row[10:40] = 1.5
+    row[18:28] = 3.0
+    row[50], row[51] = 2.0, np.nextafter(2.0, 0.0)
+    row[60:80] = 2.5
+    row[70] = np.nan
+    row[80:95] = -2.5
+    row[100], row[102], row[104] = np.inf, -np.inf, 1e300
+    row[110], row[111], row[112], row[113] = 0.0, -0.0, 0.1, -0.1
+    tile[1] = rng.uniform(-0.24, 0.24, V)
+    tile[2] = np.nan
+    tile[3] = np.linspace(0.3, 9.9, V)
+    tile[4] = tile[3][::-1]
+    tile[5] = 0.2
+    tile[5, 100:120], tile[5, 120:130], tile[5, 130:180] = 4.0, 1.0, 6.0
+    tile[6] = np.where(np.arange(V) % 2 == 0, 3.0, -3.0)
+    tile[7] = rng.normal(0.0, 2.0, V)
+    tile.setflags(write=False)
+    return tile
+
+
+@functools.lru_cache(maxsize=None)
+def _weights(V):
+    w = np.random.default_rng(V).integers(0, 1 << 33, V)                   # sums pass 2^32 at once
+    w.setflags(write=False)
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(graph, weighted, E, H):
+    off, nbr = _graph(graph)
+    V = len(off) - 1
+    out, clipped = tref.tfce(_hand_tile(V, 11), off, nbr, dh=DH, E=E, H=H, weights=_weights(V) if weighted else None,
+                             unit=UNIT if weighted else 1.0, max_steps=STEPS)
+    out.setflags(write=False)
+    return out, clipped
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["counts", "weights"])
+@pytest.mark.parametrize("graph", ["path_3000", "icosphere"])
+def test_tfce_equals_the_restatement_to_the_bit(graph, weighted):
+    from oai_analysis_2_amd import ops
+    off, nbr = _graph(graph)
+    V = len(off) - 1
+    off_d, nbr_d = torch.from_numpy(off).cuda(), torch.from_numpy(nbr).cuda()
+    tile = _hand_tile(V, 11)
+    tile_d = torch.from_numpy(tile.copy()).cuda()
+    w_d = torch.from_numpy(_weights(V).copy()).cuda() if weighted else None
+    kwargs = dict(dh=DH, weights=w_d, unit=UNIT if weighted else 1.0, max_steps=STEPS)
+    for E, H in MODES:
+        want, want_clipped = _reference(graph, weighted, E, H)
+        # the planted cases are really there (conditions on the restatement)
+        assert want_clipped.tolist() == [3, 0, 0, 0, 0, 0, 0, 0]
+        assert np.signbit(want[0, 110:114]).tolist() == [False, False, False, True] and (want[0, 110:114] == 0).all()
+        assert np.isnan(want[2]).all() and (want[1] == 0).all() and np.isnan(want[0, 70]) and (want[0, 80:95] < 0).all()
+        if graph == "path_3000" and not weighted:
+            assert want[0, 50] > want[0, 51] > 0 and want[0, 69] == want[0, 60] != want[0, 71] == want[0, 79] and want[0, 20] > want[0, 12]
+            assert len(np.unique(want[6])) == 2 and len(np.unique(want[3])) >= STEPS - 2 and want[5, 110] < want[5, 150]
+        got, clipped = ops.graph_tfce(tile_d, off_d, nbr_d, E=E, H=H, **kwargs)
+        where = f"{graph} E={E} H={H}"
+        _same_bits(got, want, f"{where} tfce")
+        _same_bits(clipped, want_clipped, f"{where} clipped")
+        for r in range(len(tile)):                                         # every row as a tile of its own
+            got, clipped = ops.graph_tfce(tile_d[r:r + 1], off_d, nbr_d, E=E, H=H, **kwargs)
+            _same_bits(got, want[r:r + 1], f"{where} tfce of row {r} alone")
+            _same_bits(clipped, want_clipped[r:r + 1], f"{where} clipped of row {r} alone")
+    # into the caller's buffers
+    out, clip = torch.full((8, V), 7.0, dtype=torch.float64, device="cuda"), torch.full((8,), -5, dtype=torch.int32, device="cuda")
+    got, clipped = ops.graph_tfce(tile_d, off_d, nbr_d, E=1.0, H=2.0, out=out, clipped=clip, **kwargs)
+    assert got.data_ptr() == out.data_ptr() and clipped.data_ptr() == clip.data_ptr()
+    _same_bits(out, _reference(graph, weighted, 1.0, 2.0)[0], "out")
+
+
+@pytest.mark.parametrize("V", [1, 65])
+def test_one_row_of_one_and_of_sixty_five_vertices(V):
+    from oai_analysis_2_amd import ops
+    off, nbr = tref.path_graph(V)
+    tile = np.random.default_rng(V).normal(0.0, 2.0, (1, V))
+    tile[0, 0] = -3.3
+    w = _weights(V)
+    off_d, nbr_d = torch.from_numpy(off).cuda(), torch.from_numpy(nbr).cuda() if V > 1 else torch.zeros(0, dtype=torch.int32, device="cuda")
+    for E, H in MODES:
+        for weights in (None, w):
+            want, want_clipped = tref.tfce(tile, off, nbr, dh=DH, E=E, H=H, weights=weights, unit=UNIT if weights is not None else 1.0, max_steps=STEPS)
+            got, clipped = ops.graph_tfce(torch.from_numpy(tile).cuda(), off_d, nbr_d, dh=DH, E=E, H=H, max_steps=STEPS,
+                                          weights=None if weights is None else torch.from_numpy(weights.copy()).cuda(),
+                                          unit=UNIT if weights is not None else 1.0)
+            _same_bits(got, want, f"V={V} E={E} H={H} tfce")
+            _same_bits(clipped, want_clipped, f"V={V} clipped")
+            assert want[0, 0] < 0
+
+
+def test_renumbering_the_vertices_permutes_the_device_output_bit_for_bit():
+    from oai_analysis_2_amd import ops
+    off, nbr = _graph("icosphere")
+    V = len(off) - 1
+    rng = np.random.default_rng(3)
+    new_of_old = rng.permutation(V)
+    off2, nbr2 = tref.relabel(off, nbr, new_of_old)
+    tile, w = _hand_tile(V, 11), _weights(V)
+    tile2, w2 = np.empty_like(tile), np.empty_like(w)
+    tile2[:, new_of_old], w2[new_of_old] = tile, w
+    up = lambda a: torch.from_numpy(np.array(a)).cuda()
+    for weights, weights2 in ((None, None), (w, w2)):
+        kwargs = dict(dh=DH, E=0.5, H=2.0, unit=UNIT, max_steps=STEPS)
+        got, clip = ops.graph_tfce(up(tile), up(off), up(nbr), weights=None if weights is None else up(weights), **kwargs)
+        got2, clip2 = ops.graph_tfce(up(tile2), up(off2), up(nbr2), weights=None if weights2 is None else up(weights2), **kwargs)
+        _same_bits(got2.cpu().numpy()[:, new_of_old], got.cpu().numpy(), "renumbered tfce")
+        _same_bits(clip2, clip.cpu().numpy(), "renumbered clipped")
+
+
+def test_the_wrapper_refuses_what_the_kernel_would():
+    from oai_analysis_2_amd import ops
+    off, nbr = (torch.from_numpy(a).cuda() for a in tref.path_graph(10))
+    tile = torch.zeros((2, 10), dtype=torch.float64, device="cuda")
+    for kwargs, match in ((dict(E=0.7), "E must be"), (dict(H=3.0), "H must be"), (dict(dh=0.0), "dh"), (dict(dh=float("nan")), "dh"),
+                          (dict(dh=float("inf")), "dh"), (dict(unit=0.0), "unit"), (dict(max_steps=0), "max_steps"), (dict(max_steps=65537), "max_steps"),
+                          (dict(weights=torch.zeros(9, dtype=torch.int64, device="cuda")), "weights must be"), (dict(out=tile), "out must be")):
+        with pytest.raises(ValueError, match=match):
+            ops.graph_tfce(tile, off, nbr, **kwargs)
+    with pytest.raises(Exception, match="int64"):
+        ops.graph_tfce(tile, off, nbr, weights=torch.zeros(10, dtype=torch.int32, device="cuda"))
+
+
+# ---- the public interface --------------------------------------------------------------------------------------------------------------
+def _sphere_atlas():
+    from oai_analysis_2_amd import mesh_processing as mp
+    verts, faces = _icosphere()
+    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0))
+
+
+def _cohort(atlas, Y, ids=None):
+    from oai_analysis_2_amd import stats
+    cohort = stats.ThicknessCohort(atlas, "FC", chunk=5)
+    for i, row in enumerate(Y):
+        cohort.add_vector(row, None if ids is None else ids[i])
+    return cohort
+
+
+N_E2E, P_E2E, P_SMALL = 24, 200, 100
+TFCE_FIELDS = ("tfce", "p_tfce", "p_tfce_uncorrected", "max_tfce")
+
+
+@functools.lru_cache(maxsize=None)
+def _painted(offset):
+    """24 knees on the sphere: 2 mm + 0.1 mm noise, and ``offset`` mm more on the cap z > 0.8 for group 1 (the first twelve)."""
+    verts, _ = _icosphere()
+    cap = verts[:, 2] > 0.8
+    rng = np.random.default_rng(2024)
+    Y = (2.0 + 0.1 * rng.normal(size=(N_E2E, len(verts)))).astype(np.float32)
+    groups = np.arange(N_E2E) < N_E2E // 2
+    Y[np.ix_(groups, cap)] += np.float32(offset)
+    return Y, groups, cap
+
+
+@functools.lru_cache(maxsize=None)
+def _two_sample_t(offset, seed):
+    """The restated t of every labelling of the painted cohort."""
+    from oai_analysis_2_amd import stats
+    Y, groups, _ = _painted(offset)
+    t = gref.permutation_t(gref.prepare(Y, None), None, stats.label_permutations(groups, P_E2E, seed=seed).rows(), gref.TWO_SAMPLE)
+    t.setflags(write=False)
+    return t
+
+
+def _area_weights(atlas):
+    from oai_analysis_2_amd import mesh_processing as mp
+    return np.rint(mp.mesh_areas(atlas.inner["FC"])[0] * 2 ** 20).astype(np.int64)
+
+
+def _check_against(res, t_ref, P, what, **ref_kwargs):
+    """The TFCE fields of a result against the restatement run on the restated t tile."""
+    off, nbr = _graph("icosphere")
+    want, clipped = tref.tfce(t_ref, off, nbr, **ref_kwargs)
+    want_max, want_exceed = gref.reduce_tiles(want)
+    _same_bits(res.tfce, want[0], f"{what} tfce")
+    _same_bits(res.max_tfce, want_max, f"{what} max_tfce")
+    assert np.array_equal(np.rint(res.p_tfce_uncorrected * P).astype(np.int64), want_exceed), what
+    null = np.sort(want_max)
+    assert np.array_equal(res.p_tfce, (P - np.searchsorted(null, np.abs(want[0]), side="left")) / float(P)), what
+    assert res.tfce_clipped == np.count_nonzero(clipped), what
+    return want
+
+
+def test_two_sample_tfce_finds_the_weak_cap_that_max_t_misses():
+    from oai_analysis_2_amd import stats
+    Y, groups, cap = _painted(0.10)
+    atlas = _sphere_atlas()
+    settings = stats.TFCE(extent="vertices")
+    res = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings, batch=48)
+    assert res.tfce_settings == settings and res.max_tfce.shape == (P_E2E,) and res.tfce.shape == cap.shape and res.cluster_label is None
+    _check_against(res, _two_sample_t(0.10, 1), P_E2E, "vertices", dh=0.1, E=1.0, H=2.0)
+    n_tfce, n_fwer = int((res.p_tfce[cap] <= 0.05).sum()), int((res.p_fwer[cap] <= 0.05).sum())
+    print(f"cap vertices (of {cap.sum()}) with p <= 0.05: p_tfce {n_tfce}, p_fwer {n_fwer}; outside the cap: p_tfce "
+          f"{int((res.p_tfce[~cap] <= 0.05).sum())}, p_fwer {int((res.p_fwer[~cap] <= 0.05).sum())}")
+    assert n_tfce > n_fwer
+    assert res.p_tfce.min() == 1.0 / P_E2E and res.tfce_clipped == 0
+    assert res.max_tfce[0] == np.abs(res.tfce).max() and (np.signbit(res.tfce) == np.signbit(res.t)).all()
+    # a second run and a run with the default batch: the same bits in every TFCE field
+    again = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings, batch=48)
+    other = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings)
+    for name in TFCE_FIELDS:
+        _same_bits(getattr(again, name), getattr(res, name), name)
+        _same_bits(getattr(other, name), getattr(res, name), name + " (default batch)")
+    assert again.tfce_clipped == other.tfce_clipped == 0
+    # nothing else changes: the other fields are those of a run without tfce, and clusters may be asked for as well
+    plain = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, batch=48)
+    assert plain.tfce is None and plain.p_tfce is None and plain.max_tfce is None and plain.tfce_clipped == 0 and plain.tfce_settings is None
+    both = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings, batch=48, cluster_threshold=2.5)
+    only = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, batch=48, cluster_threshold=2.5)
+    for name in ("t", "n1", "n2", "mean_difference", "p_uncorrected", "p_fwer", "max_abs"):
+        _same_bits(getattr(res, name), getattr(plain, name), name + " (with and without tfce)")
+        _same_bits(getattr(both, name), getattr(plain, name), name + " (with tfce and clusters)")
+    for name in ("cluster_label", "max_extent"):
+        _same_bits(getattr(both, name), getattr(only, name), name)
+    assert both.clusters == only.clusters
+    for name in TFCE_FIELDS:
+        _same_bits(getattr(both, name), getattr(res, name), name + " (with clusters)")
+    assert res.image(SimpleNamespace(image=lambda vec, kind: vec), "p_tfce").dtype == np.float32
+
+
+def test_extent_as_area_sums_integer_areas():
+    from oai_analysis_2_amd import stats
+    Y, groups, cap = _painted(0.10)
+    atlas = _sphere_atlas()
+    res = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=True, batch=64)
+    assert res.tfce_settings == stats.TFCE() and res.tfce_settings.extent == "area"
+    w = _area_weights(atlas)
+    assert w.min() > 1 << 20 and np.array_equal(w, stats.tfce_weights(mp_areas(atlas)))
+    _check_against(res, _two_sample_t(0.10, 1), P_E2E, "area", dh=0.1, E=1.0, H=2.0, weights=w, unit=UNIT)
+    assert res.p_tfce[cap].min() == 1.0 / P_E2E and res.tfce_clipped == 0
+
+
+def mp_areas(atlas):
+    from oai_analysis_2_amd import mesh_processing as mp
+    return mp.mesh_areas(atlas.inner["FC"])[0]
+
+
+def test_paired_test_with_tfce_finds_the_cap():
+    from oai_analysis_2_amd import stats
+    Y, _, cap = _painted(0.0)
+    atlas = _sphere_atlas()
+    rng = np.random.default_rng(77)
+    follow = (Y + 0.1 * rng.normal(size=Y.shape)).astype(np.float32)
+    follow[:, cap] += np.float32(0.15)
+    res = stats.paired_test(_cohort(atlas, follow), _cohort(atlas, Y), n_permutations=P_SMALL, seed=3, batch=32, tfce=True)
+    assert res.p_tfce[cap].min() == 1.0 / P_SMALL and res.n_permutations == P_SMALL
+    diff = follow - Y
+    t_ref = gref.permutation_t(gref.prepare(diff, None, centre=False), None, stats.sign_flips(N_E2E, P_SMALL, seed=3).rows(), gref.ONE_SAMPLE)
+    _same_bits(res.t, t_ref[0], "t")
+    _check_against(res, t_ref, P_SMALL, "paired", dh=0.1, E=1.0, H=2.0, weights=_area_weights(atlas), unit=UNIT)
+
+
+def test_regression_test_with_tfce_finds_the_cap():
+    import group_regression_ref as rref
+    from oai_analysis_2_amd import stats
+    Y, _, cap = _painted(0.0)
+    atlas = _sphere_atlas()
+    rng = np.random.default_rng(78)
+    x, age = rng.normal(0.0, 1.0, N_E2E), rng.uniform(45, 80, N_E2E)
+    Y = Y.astype(np.float64)
+    Y[:, cap] += 0.1 * x[:, None]
+    Y = Y.astype(np.float32)
+    res = stats.regression_test(_cohort(atlas, Y), x, covariates=age, n_permutations=P_SMALL, seed=5, batch=32, tfce=True)
+    assert res.p_tfce[cap].min() == 1.0 / P_SMALL and res.n_permutations == P_SMALL and res.tfce_settings == stats.TFCE()
+    Z, D, _ = rref.design_columns(x, age, True)
+    t_ref = rref.regression_t(rref.prepare(Y, None, Z), None, D, stats.index_permutations(N_E2E, P_SMALL, seed=5).index)
+    _same_bits(res.t, t_ref[0], "t")
+    _check_against(res, t_ref, P_SMALL, "regression", dh=0.1, E=1.0, H=2.0, weights=_area_weights(atlas), unit=UNIT)
+    again = stats.regression_test(_cohort(atlas, Y), x, covariates=age, n_permutations=P_SMALL, seed=5, tfce=True)
+    plain = stats.regression_test(_cohort(atlas, Y), x, covariates=age, n_permutations=P_SMALL, seed=5, batch=32)
+    for name in TFCE_FIELDS:
+        _same_bits(getattr(again, name), getattr(res, name), name + " (default batch)")
+    for name in ("t", "n", "dof", "slope", "partial_r", "p_uncorrected", "p_fwer", "max_abs"):
+        _same_bits(getattr(res, name), getattr(plain, name), name + " (with and without tfce)")
+    assert plain.tfce is None and plain.tfce_settings is None
+
+
+def test_without_an_effect_the_tfce_p_is_the_rank_of_the_observed_maximum():
+    from oai_analysis_2_amd import stats
+    Y, groups, _ = _painted(0.0)
+    res = stats.two_sample_test(_cohort(_sphere_atlas(), Y), groups, n_permutations=P_E2E, seed=2, batch=64, tfce=True)
+    assert not np.isnan(res.tfce).any()
+    assert res.p_tfce.min() == (res.max_tfce >= res.max_tfce[0]).sum() / P_E2E
+    assert (res.p_tfce >= res.p_tfce_uncorrected).all()
+    assert res.max_tfce[0] == np.abs(res.tfce).max()
+
+
+def test_bad_settings_are_refused_before_anything_is_launched():
+    """The cohort is None: a refusal that came after the first look at it would be another error."""
+    from oai_analysis_2_amd import stats
+    for bad in (stats.TFCE(E=0.7), stats.TFCE(dh=0), stats.TFCE(extent="volume")):
+        with pytest.raises(ValueError, match="TFCE"):
+            stats.two_sample_test(None, [0, 1], tfce=bad)
+        with pytest.raises(ValueError, match="TFCE"):
+            stats.paired_test(None, None, tfce=bad)
+        with pytest.raises(ValueError, match="TFCE"):
+            stats.regression_test(None, [0, 1], tfce=bad)
