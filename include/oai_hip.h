@@ -1206,6 +1206,49 @@ int oai_graph_tfce(const double* values_dev, long long n_rows, long long n_verts
                    long long n_neighbours, const long long* weight_dev, double unit, double dh, int e_mode, int h_mode, int max_steps,
                    void* workspace_dev, size_t workspace_bytes, double* tfce_dev, int* clipped_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Surface smoothing (csrc/graph_smooth.hip, tests/graph_smooth_ref.py): every row of a float64 tile -- one knee's scalar field on the
+ * atlas vertices -- is smoothed ALONG THE SURFACE by K sweeps of normalised neighbourhood averaging on a weighted vertex graph, the
+ * step a study takes before the tests above so that its maps have a stated FWHM.  Entries may be MISSING: a validity mask travels with
+ * the values, a missing entry is never read into a sum and (in keep mode) never invented, so the operator is a normalised average whose
+ * denominator depends on row and vertex, not one fixed sparse matrix power.  Iterated nearest-neighbour averaging as an approximation
+ * of the heat kernel on a surface is common practice in surface-based analysis AS RECALLED; the definition below is this library's own
+ * and is pinned to no implementation, only to the numpy restatement.  Its limits: weights are the caller's (finite and >= 0: the
+ * caller's guarantee, the device does not check it); distances along edges, not geodesics; what FWHM K sweeps amount to is the caller's
+ * calibration (oai_analysis_2_amd.stats.sweeps_for_fwhm).  The rules of "Cohort statistics" hold: fp64 without contraction (every
+ * product is rounded before it is added), no floating-point atomics, one accumulator per sum that starts at +0.0: bit-reproducible and
+ * independent of the launch geometry.  The entry point launches all sweeps on the given stream itself (plain launches), does not
+ * synchronise and reads nothing back.  1 <= n_rows <= 2^20, 1 <= n_verts <= 2^31 - 2.
+ *
+ * Inputs.  values_dev float64 [n_rows][n_verts]; mask_dev uint8 [n_rows][n_verts], non-zero = valid, or null: every entry is valid.
+ * The CSR adjacency as in oai_graph_clusters (an offset outside [0, n_neighbours] is clamped, a neighbour outside [0, n_verts) is
+ * ignored; a vertex listed among its own neighbours is a neighbour like any other).  edge_weight_dev float64 [n_neighbours], aligned
+ * with neighbours_dev: entry e is the weight w_e with which the vertex that owns slot e reads neighbour nbr[e]; w_ij and w_ji may
+ * differ.  self_weight_dev float64 [n_verts], or null: every self weight is 1.0.  1 <= sweeps <= 4096.  fill 0 (keep) or 1 (fill).
+ *
+ * One sweep, for every row and vertex i, reads (x_s, m_s) and writes (x_s+1, m_s+1); (x_0, m_0) are the inputs:
+ *   num = +0.0;  den = +0.0
+ *   if m_s[i]:                                     num = num + self_w[i] * x_s[i];   den = den + self_w[i]
+ *   for e = off[i] .. off[i+1] - 1 ascending, j = nbr[e], if m_s[j]:
+ *                                                  num = num + w[e] * x_s[j];        den = den + w[e]
+ *   ok = (fill ? 1 : m_s[i]) && den > 0
+ *   x_s+1[i] = ok ? num / den : +0.0;              m_s+1[i] = ok
+ * An invalid entry is skipped by a select, never multiplied by 0: a NaN, an infinity or anything else stored under a 0 mask byte
+ * reaches no sum.  What is stored at a VALID entry propagates as IEEE says (a valid NaN spreads one ring per sweep).  Keep mode: a
+ * missing entry stays missing and gives nothing; a valid entry whose self weight and valid neighbours' weights sum to 0 drops out.  Fill
+ * mode: a missing entry with a valid neighbour of positive weight becomes valid, so the valid set grows by one ring per sweep.
+ * out_values_dev float64 [n_rows][n_verts] receives x_K, +0.0 where m_K is 0; out_mask_dev uint8 [n_rows][n_verts] receives m_K as 0 / 1
+ * and may be null.  out_values_dev may be values_dev and out_mask_dev may be mask_dev: the inputs are consumed before the outputs are
+ * written.  The workspace holds the tile transposed to [n_verts][n_rows] twice over (values and masks, ping and pong), so that the
+ * gather of a neighbour is a contiguous run over rows: 2 * (8 + 1) bytes per entry.
+ * ---------------------------------------------------------------------------------------- */
+/* 0 for a shape the entry point refuses. */
+size_t oai_graph_smooth_workspace_bytes(long long n_rows, long long n_verts);
+int oai_graph_smooth(const double* values_dev, const unsigned char* mask_dev, long long n_rows, long long n_verts, const int* offsets_dev,
+                     const int* neighbours_dev, long long n_neighbours, const double* edge_weight_dev, const double* self_weight_dev, int sweeps,
+                     int fill, void* workspace_dev, size_t workspace_bytes, double* out_values_dev, unsigned char* out_mask_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,8 @@ SIGNATURES = {
     "oai_regression_t": (_I, [_P, _Z, _P, _P, _P, C.c_longlong, C.c_longlong, _I, C.c_longlong, C.c_longlong, _P, _Z, _P, _P]),
     "oai_graph_tfce_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
     "oai_graph_tfce": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, C.c_longlong, _P, _D, _D, _I, _I, _I, _P, _Z, _P, _P, _P]),
+    "oai_graph_smooth_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_graph_smooth": (_I, [_P, _P, C.c_longlong, C.c_longlong, _P, _P, C.c_longlong, _P, _P, _I, _I, _P, _Z, _P, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

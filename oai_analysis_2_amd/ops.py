@@ -780,6 +780,54 @@ def graph_tfce(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.Te
     return out, clip
 
 
+MAX_SMOOTH_SWEEPS = 4096
+
+
+def graph_smooth(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.Tensor, edge_weights: torch.Tensor,
+                 mask: Optional[torch.Tensor] = None, self_weights: Optional[torch.Tensor] = None, sweeps: int = 1, fill: bool = False,
+                 out: Optional[torch.Tensor] = None, out_mask: Optional[torch.Tensor] = None):
+    """``sweeps`` sweeps of normalised neighbourhood averaging of every row of the float64 ``values`` [R,V] on the graph given as in
+    ``graph_clusters``, with the float64 ``edge_weights`` aligned with ``neighbours`` and the float64 ``self_weights`` [V] (None: 1.0)
+    (include/oai_hip.h, "Surface smoothing").  ``mask`` uint8 / bool [R,V]: non-zero = the entry is valid (None: all are); an invalid entry
+    is never read into a sum.  ``fill`` False: a missing entry stays missing; True: it takes the average of its valid neighbours, so the
+    valid set grows by one ring per sweep.  Weights must be finite and >= 0: not checked.  Returns the float64 [R,V] and uint8 [R,V]
+    DEVICE tensors (values, mask): +0.0 and 0 where the result is missing (``out``, ``out_mask``: written there; ``out`` may be
+    ``values`` and ``out_mask`` may be ``mask``).  Bit-reproducible.  Does not synchronise."""
+    values = _chk(values, "values", torch.float64)
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"values must be [R >= 1, V >= 1], got {tuple(values.shape)}")
+    R, V = int(values.shape[0]), int(values.shape[1])
+    dev = values.device
+    offsets, neighbours = _chk(offsets, "offsets", torch.int32), _chk(neighbours, "neighbours", torch.int32)
+    if offsets.numel() != V + 1 or offsets.device != dev or neighbours.device != dev:
+        raise ValueError(f"offsets must be [{V + 1}] and live with neighbours on the values' GPU, got {offsets.numel()} on {offsets.device}")
+    edge_weights = _chk(edge_weights, "edge_weights", torch.float64)
+    if edge_weights.numel() != neighbours.numel() or edge_weights.device != dev:
+        raise ValueError(f"edge_weights must be float64 [{neighbours.numel()}] on the values' GPU, got {tuple(edge_weights.shape)} on "
+                         f"{edge_weights.device}")
+    if self_weights is not None:
+        self_weights = _chk(self_weights, "self_weights", torch.float64)
+        if tuple(self_weights.shape) != (V,) or self_weights.device != dev:
+            raise ValueError(f"self_weights must be float64 [{V}] on the values' GPU, got {tuple(self_weights.shape)} on {self_weights.device}")
+    if not 1 <= int(sweeps) <= MAX_SMOOTH_SWEEPS:
+        raise ValueError(f"sweeps must be 1 .. {MAX_SMOOTH_SWEEPS}, got {sweeps!r}")
+    mask = _stats_mask(mask, values)
+    if out is None:
+        out = torch.empty((R, V), dtype=torch.float64, device=dev)
+    elif out.device != dev or out.dtype != torch.float64 or tuple(out.shape) != (R, V) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float64 [{R}, {V}] tensor on {dev}")
+    if out_mask is None:
+        out_mask = torch.empty((R, V), dtype=torch.uint8, device=dev)
+    elif out_mask.device != dev or out_mask.dtype != torch.uint8 or tuple(out_mask.shape) != (R, V) or not out_mask.is_contiguous():
+        raise ValueError(f"out_mask must be a contiguous uint8 [{R}, {V}] tensor on {dev}")
+    ws = _lib.workspace("oai_graph_smooth", dev, R, V)
+    n_nbrs = int(neighbours.numel())
+    _lib.call("oai_graph_smooth", values.data_ptr(), _ptr(mask), R, V, offsets.data_ptr(), _ptr(neighbours, n_nbrs), n_nbrs,
+              _ptr(edge_weights, n_nbrs), _ptr(self_weights), int(sweeps), int(bool(fill)), ws.data_ptr(), ws.numel(), out.data_ptr(),
+              out_mask.data_ptr(), _lib.STREAM, device=dev)
+    return out, out_mask
+
+
 # ---- cohort regression (include/oai_hip.h, "Cohort regression"; csrc/group_regression.hip) ---------------------------------------------------
 MAX_DESIGN_COLUMNS = 6
 

@@ -25,6 +25,10 @@ csrc/group_regression.hip; tests/group_regression_ref.py).
 ``tfce=True`` (or a ``TFCE``) on any of the three adds threshold-free cluster enhancement (include/oai_hip.h, "Threshold-free cluster
 enhancement"; csrc/graph_tfce.hip; tests/graph_tfce_ref.py): every labelling's t tile is integrated over all thresholds on the device and
 ``res.p_tfce`` is the family-wise p of the enhanced statistic -- sensitive to broad weak effects without a hand-picked threshold.
+
+``cohort.smoothed(fwhm_mm=5.0)`` smooths every knee's map ALONG the atlas surface before any of the tests (include/oai_hip.h, "Surface
+smoothing"; csrc/graph_smooth.hip; tests/graph_smooth_ref.py): iterated Gaussian-weighted neighbourhood averaging on the device that
+neither reads nor invents a missing entry, with the sweep count calibrated on the mesh's own discrete kernel (``SurfaceSmoother``).
 """
 from __future__ import annotations
 
@@ -148,6 +152,7 @@ class ThicknessCohort:
         self._mask = torch.zeros((0, self.n_verts), dtype=torch.uint8, device=self.device)
         self._graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self._areas: Optional[np.ndarray] = None
+        self.smoothing: Optional["Smoothing"] = None       # set on the result of ``smoothed``
 
     def surface_graph(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """The CSR vertex adjacency of the atlas inner mesh on the device (``mesh_processing.vertex_adjacency_device``), built at the
@@ -220,6 +225,236 @@ class ThicknessCohort:
             raise ValueError("a summary needs at least two knees")
         prep = ops.group_prepare(self.values, self.mask)
         return {"n": prep.n.cpu().numpy(), "mean": prep.mean.cpu().numpy(), "std": prep.std.cpu().numpy()}
+
+    def smoothed(self, fwhm_mm: Optional[float] = None, *, sweeps: Optional[int] = None, sigma_step: Optional[float] = None,
+                 missing: str = "keep", batch: Optional[int] = None) -> "ThicknessCohort":
+        """A NEW cohort on the same atlas, cartilage and ids whose maps are these smoothed along the atlas surface (``SurfaceSmoother``,
+        whose arguments these are: exactly one of ``fwhm_mm`` and ``sweeps``); this cohort is untouched.  The float32 values are widened
+        to float64 (exact), all sweeps run in float64 on the device, and the result is rounded to float32 once at the end.  Knees go
+        through in batches of ``batch`` rows -- default ``smoothing_batch``, so that the workspace stays within ``WORKSPACE_BUDGET``.  ``missing="keep"``: an
+        entry that is missing stays missing; "fill": it takes the average of what surrounds it, ring by ring.  The settings are kept on
+        the result as ``.smoothing`` (a ``Smoothing``); the three tests take the result as they take any cohort."""
+        _check_smoothing_arguments(fwhm_mm, sweeps, sigma_step, missing)
+        N, V = len(self), self.n_verts
+        if N < 1:
+            raise ValueError("the cohort holds no knee to smooth")
+        smoother = SurfaceSmoother(self.atlas, self.kind, fwhm_mm, sweeps=sweeps, sigma_step=sigma_step, missing=missing, graph=self.surface_graph())
+        out = ThicknessCohort(self.atlas, self.kind, self.use_coverage, self.chunk)
+        out.ids, out._graph, out._areas, out.smoothing = list(self.ids), self._graph, self._areas, smoother.settings
+        out._values = torch.zeros((N, V), dtype=torch.float32, device=self.device)
+        out._mask = torch.zeros((N, V), dtype=torch.uint8, device=self.device)
+        rows = smoothing_batch(V, N) if batch is None else int(batch)
+        if rows < 1:
+            raise ValueError(f"batch must be >= 1, got {batch}")
+        for r0 in range(0, N, rows):
+            r1 = min(r0 + rows, N)
+            wide = self.values[r0:r1].to(torch.float64)
+            smoother.smooth_tile(wide, self.mask[r0:r1], out=wide, out_mask=out._mask[r0:r1])
+            out._values[r0:r1] = wide.to(torch.float32)
+        return out
+
+
+# ---- surface smoothing -----------------------------------------------------------------------------------------------------------------
+_FWHM_PER_SIGMA = math.sqrt(8.0 * math.log(2.0))
+_SMOOTH_BYTES = 8 + 1 + 18            # per (knee, vertex) of a batch: the float64 tile, its mask and oai_graph_smooth_workspace_bytes
+
+
+@dataclass(frozen=True)
+class Smoothing:
+    """What a smoothed cohort was smoothed with: the nominal ``fwhm_mm`` (None when the sweeps were given), the ``achieved_fwhm_mm`` that
+    the mesh's own discrete kernel amounts to after ``sweeps`` sweeps, the ``sigma_step`` (mm) of the edge weights, and ``missing``."""
+    fwhm_mm: Optional[float]
+    achieved_fwhm_mm: float
+    sweeps: int
+    sigma_step: float
+    missing: str
+
+
+def _csr_slots(offsets, neighbours, n_verts: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(owner, neighbour, slot) of every CSR slot that the kernel reads: offsets clamped into [0, E], neighbours outside [0, V) left out."""
+    off, nbr = np.asarray(offsets, np.int64).reshape(-1), np.asarray(neighbours, np.int64).reshape(-1)
+    V, E = int(n_verts), len(nbr)
+    if len(off) != V + 1:
+        raise ValueError(f"offsets must hold {V + 1} entries, got {len(off)}")
+    lo, hi = np.clip(off[:-1], 0, E), np.clip(off[1:], 0, E)
+    count = np.maximum(hi - lo, 0)
+    owner = np.repeat(np.arange(V, dtype=np.int64), count)
+    slot = np.repeat(lo - (np.cumsum(count) - count), count) + np.arange(int(count.sum()), dtype=np.int64)
+    ok = (nbr[slot] >= 0) & (nbr[slot] < V)
+    return owner[ok], nbr[slot][ok], slot[ok]
+
+
+def surface_edge_d2(verts, offsets, neighbours) -> np.ndarray:
+    """float64 [E]: the squared length of every directed edge of the CSR adjacency, dx*dx + dy*dy + dz*dz added left to right on the
+    coordinates promoted to float64; 0.0 in a slot that the kernel does not read."""
+    v = np.asarray(verts).astype(np.float64).reshape(-1, 3)
+    owner, nbr, slot = _csr_slots(offsets, neighbours, len(v))
+    d = v[nbr] - v[owner]
+    d2 = np.zeros(len(np.asarray(neighbours).reshape(-1)), np.float64)
+    d2[slot] = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+    return d2
+
+
+def mean_edge_length(verts, offsets, neighbours) -> float:
+    """The mean length of the directed edges of the mesh: the default ``sigma_step``."""
+    _, _, slot = _csr_slots(offsets, neighbours, len(np.asarray(verts).reshape(-1, 3)))
+    if len(slot) == 0:
+        raise ValueError("the mesh has no edge")
+    return float(np.sqrt(surface_edge_d2(verts, offsets, neighbours)[slot]).mean())
+
+
+def surface_edge_weights(verts, offsets, neighbours, sigma_step: float) -> np.ndarray:
+    """float64 [E], aligned with ``neighbours``: w = exp(-d2 / (2 * sigma_step**2)) per directed edge, d2 as ``surface_edge_d2``; the self
+    weight that goes with it is 1, the same Gaussian at distance 0.  0.0 in a slot that the kernel does not read."""
+    sigma_step = float(sigma_step)
+    if not (sigma_step > 0.0 and math.isfinite(sigma_step)):
+        raise ValueError(f"sigma_step must be finite and > 0, got {sigma_step!r}")
+    _, _, slot = _csr_slots(offsets, neighbours, len(np.asarray(verts).reshape(-1, 3)))
+    d2 = surface_edge_d2(verts, offsets, neighbours)
+    w = np.zeros_like(d2)
+    w[slot] = np.exp(-d2[slot] / (2 * sigma_step ** 2))
+    return w
+
+
+def surface_step_variance(offsets, neighbours, weights, d2) -> np.ndarray:
+    """float64 [V]: s_i = sum_j w_ij d2_ij / (1 + sum_j w_ij), the second moment of ONE sweep's kernel around vertex i (self weight 1).
+    0.0 for a vertex without a neighbour."""
+    V = len(np.asarray(offsets).reshape(-1)) - 1
+    owner, _, slot = _csr_slots(offsets, neighbours, V)
+    w, d2 = np.asarray(weights, np.float64).reshape(-1), np.asarray(d2, np.float64).reshape(-1)
+    if len(w) != len(d2) or len(w) != len(np.asarray(neighbours).reshape(-1)):
+        raise ValueError("weights and d2 must be aligned with neighbours")
+    return np.bincount(owner, w[slot] * d2[slot], minlength=V) / (1.0 + np.bincount(owner, w[slot], minlength=V))
+
+
+def sweeps_for_fwhm(fwhm_mm: float, step_variance, has_neighbour=None) -> int:
+    """The number K of sweeps whose kernel has the second moment of a Gaussian of ``fwhm_mm``: sigma = fwhm / sqrt(8 ln 2), K = 2 sigma^2
+    / s_mean rounded half to even, at least 1.  ``step_variance``: ``surface_step_variance`` (or one number, s_mean itself); s_mean is
+    its plain mean over the vertices that have a neighbour (``has_neighbour`` bool [V]; default: those with s_i > 0).  On a regular
+    lattice the second moment of the impulse response after K sweeps is exactly K s, because the variances of the steps add: the only
+    error left is the rounding of K.  On an irregular mesh s varies from vertex to vertex and the calibration is approximate."""
+    fwhm_mm = float(fwhm_mm)
+    if not (fwhm_mm > 0.0 and math.isfinite(fwhm_mm)):
+        raise ValueError(f"fwhm_mm must be finite and > 0, got {fwhm_mm!r}")
+    s_mean = _mean_step_variance(step_variance, has_neighbour)
+    sigma = fwhm_mm / _FWHM_PER_SIGMA
+    ratio = 2.0 * sigma * sigma / s_mean
+    if not math.isfinite(ratio) or round(ratio) > ops.MAX_SMOOTH_SWEEPS:
+        raise ValueError(f"a FWHM of {fwhm_mm} mm needs about {ratio:.0f} sweeps of this step, more than {ops.MAX_SMOOTH_SWEEPS}: "
+                         "give a larger sigma_step")
+    return max(int(round(ratio)), 1)
+
+
+def _mean_step_variance(step_variance, has_neighbour=None) -> float:
+    s = np.atleast_1d(np.asarray(step_variance, np.float64))
+    keep = s > 0.0 if has_neighbour is None else np.asarray(has_neighbour, bool)
+    if not keep.any() or not float(s[keep].mean()) > 0.0:
+        raise ValueError("the step variance is 0 everywhere: the graph has no edge of positive length and weight")
+    return float(s[keep].mean())
+
+
+def _check_smoothing_arguments(fwhm_mm, sweeps, sigma_step, missing) -> None:
+    """Refuses what the smoother would, before anything is looked at or launched."""
+    if (fwhm_mm is None) == (sweeps is None):
+        raise ValueError("give exactly one of fwhm_mm and sweeps")
+    if missing not in ("keep", "fill"):
+        raise ValueError(f'missing must be "keep" or "fill", got {missing!r}')
+    if fwhm_mm is not None and not (float(fwhm_mm) > 0.0 and math.isfinite(float(fwhm_mm))):
+        raise ValueError(f"fwhm_mm must be finite and > 0, got {fwhm_mm!r}")
+    if sweeps is not None and not 1 <= int(sweeps) <= ops.MAX_SMOOTH_SWEEPS:
+        raise ValueError(f"sweeps must be 1 .. {ops.MAX_SMOOTH_SWEEPS}, got {sweeps!r}")
+    if sigma_step is not None and not (float(sigma_step) > 0.0 and math.isfinite(float(sigma_step))):
+        raise ValueError(f"sigma_step must be finite and > 0, got {sigma_step!r}")
+
+
+def smoothing_batch(n_verts: int, n_rows: int, budget: int = WORKSPACE_BUDGET) -> int:
+    """Knees per batch of ``ThicknessCohort.smoothed``: what fits ``budget`` bytes -- per (knee, vertex) 8 of float64 tile, 1 of mask and
+    the 18 of the kernel's transposed ping and pong -- at least one."""
+    return int(min(max(budget // (int(n_verts) * _SMOOTH_BYTES), 1), max(int(n_rows), 1)))
+
+
+class SurfaceSmoother:
+    """Smoothing of scalar fields ALONG the inner surface of ``atlas.inner[kind]`` (include/oai_hip.h, "Surface smoothing";
+    csrc/graph_smooth.hip): K sweeps of Gaussian-weighted neighbourhood averaging over the mesh edges, the weight of an edge being
+    exp(-d^2 / (2 sigma_step^2)) of its length d and that of the vertex itself 1.  Exactly one of ``fwhm_mm`` (then K =
+    ``sweeps_for_fwhm``, calibrated on this mesh's own step variance) and ``sweeps`` is given.  ``sigma_step`` (mm): default, the mean
+    edge length.  ``missing``: "keep" -- a missing entry stays missing and gives nothing to its neighbours; "fill" -- it takes the
+    average of its valid neighbours, ring by ring.  ``graph``: the (offsets, neighbours) device tensors of
+    ``ThicknessCohort.surface_graph()``, to share them; default: built here.  The graph, the weights and K are formed once and the
+    weights uploaded once.  ``fwhm_mm`` is the nominal figure; ``achieved_fwhm_mm`` = sqrt(8 ln 2 * K s_mean / 2) is what K whole sweeps
+    amount to.  Distances are edge lengths, not geodesics, and on an irregular mesh the calibration is approximate: ``impulse`` shows the
+    kernel that is actually applied."""
+
+    def __init__(self, atlas, kind: str, fwhm_mm: Optional[float] = None, *, sweeps: Optional[int] = None, sigma_step: Optional[float] = None,
+                 missing: str = "keep", graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        _check_smoothing_arguments(fwhm_mm, sweeps, sigma_step, missing)
+        mesh = atlas.inner[kind]
+        self.atlas, self.kind, self.missing = atlas, kind, missing
+        self.device = torch.device(atlas.device)
+        self.n_verts = len(mesh.verts)
+        if graph is None:
+            graph = mp.vertex_adjacency_device(self.n_verts, mp._dev(mesh.faces, np.int32, (3,), device=self.device))
+        self.graph = graph
+        off, nbr = graph[0].cpu().numpy(), graph[1].cpu().numpy()
+        self.sigma_step = mean_edge_length(mesh.verts, off, nbr) if sigma_step is None else float(sigma_step)
+        weights = surface_edge_weights(mesh.verts, off, nbr, self.sigma_step)
+        s = surface_step_variance(off, nbr, weights, surface_edge_d2(mesh.verts, off, nbr))
+        owner, _, slot = _csr_slots(off, nbr, self.n_verts)
+        has_neighbour = np.bincount(owner, minlength=self.n_verts) > 0
+        self.step_variance = _mean_step_variance(s, has_neighbour)
+        self.fwhm_mm = None if fwhm_mm is None else float(fwhm_mm)
+        self.sweeps = int(sweeps) if fwhm_mm is None else sweeps_for_fwhm(fwhm_mm, s, has_neighbour)
+        self.achieved_fwhm_mm = math.sqrt(8.0 * math.log(2.0) * self.sweeps * self.step_variance / 2.0)
+        self.weights = torch.from_numpy(weights).to(self.device)
+        self._vertex_sum = 1.0 + np.bincount(owner, weights[slot], minlength=self.n_verts)      # d_i of ``impulse``
+
+    @property
+    def settings(self) -> Smoothing:
+        return Smoothing(self.fwhm_mm, self.achieved_fwhm_mm, self.sweeps, self.sigma_step, self.missing)
+
+    def smooth_tile(self, values: torch.Tensor, mask: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
+                    out_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``ops.graph_smooth`` of a float64 device tile [R, V] and its uint8 mask with this smoother's graph, weights and sweeps."""
+        return ops.graph_smooth(values, self.graph[0], self.graph[1], self.weights, mask=mask, sweeps=self.sweeps, fill=self.missing == "fill",
+                                out=out, out_mask=out_mask)
+
+    def __call__(self, field, valid=None):
+        """One knee [V] or a matrix [N, V], numpy or a device tensor, NaN = missing (``valid``: also missing where it is 0) -> the same
+        kind, shape and floating dtype, smoothed in float64 and NaN where the result is missing."""
+        is_tensor = isinstance(field, torch.Tensor)
+        if is_tensor:
+            dtype = field.dtype if field.dtype.is_floating_point else torch.float64
+        else:
+            dtype = np.asarray(field).dtype if np.asarray(field).dtype.kind == "f" else np.dtype(np.float64)
+        x = (field.to(self.device) if is_tensor else torch.from_numpy(np.ascontiguousarray(field, dtype=np.float64)).to(self.device)).to(torch.float64)
+        if x.dim() not in (1, 2) or x.shape[-1] != self.n_verts or x.numel() == 0:
+            raise ValueError(f"the field must be [{self.n_verts}] or [N >= 1, {self.n_verts}], got {tuple(x.shape)}")
+        tile = x.reshape(-1, self.n_verts).contiguous()
+        ok = ~torch.isnan(tile)
+        if valid is not None:
+            ok &= mp._dev(valid, np.uint8, device=self.device).reshape(tile.shape) != 0
+        N = int(tile.shape[0])
+        out, out_mask = torch.empty_like(tile), torch.empty(tile.shape, dtype=torch.uint8, device=self.device)
+        mask = ok.to(torch.uint8)
+        rows = smoothing_batch(self.n_verts, N)
+        for r0 in range(0, N, rows):
+            r1 = min(r0 + rows, N)
+            self.smooth_tile(tile[r0:r1], mask[r0:r1], out=out[r0:r1], out_mask=out_mask[r0:r1])
+        out = torch.where(out_mask != 0, out, torch.full_like(out, float("nan"))).reshape(x.shape)
+        return out.to(dtype) if is_tensor else out.cpu().numpy().astype(dtype)
+
+    def impulse(self, vertex: int) -> np.ndarray:
+        """float64 [V]: the kernel that is actually applied at ``vertex`` with nothing missing -- entry j is the weight with which the
+        smoothed value at ``vertex`` averages the input at j, so the entries are >= 0 and sum to 1.  It is formed as the response to an
+        impulse: with d_i = 1 + sum_j w_ij and symmetric edge weights, the response at i to a value 1 / d_vertex at ``vertex``, times d_i.
+        Where every vertex has the same d (a regular mesh) that IS the response to a unit value at ``vertex``; elsewhere the response
+        differs from it by the factor d_vertex / d_i."""
+        vertex = int(vertex)
+        if not 0 <= vertex < self.n_verts:
+            raise ValueError(f"vertex must be in [0, {self.n_verts}), got {vertex}")
+        unit = torch.zeros((1, self.n_verts), dtype=torch.float64, device=self.device)
+        unit[0, vertex] = 1.0 / float(self._vertex_sum[vertex])
+        return self.smooth_tile(unit, None)[0][0].cpu().numpy() * self._vertex_sum
 
 
 # ---- the tests -------------------------------------------------------------------------------------------------------------------------
