@@ -20,7 +20,8 @@
 //     workspace, whatever the caller stored under its 0 mask byte: it is loaded (the loads are unconditional, so that they can all be
 //     in flight together) and then dropped by the select.
 // Measured (profiles/surface_smoothing.md).
-#include "common.h"
+#include "cohort.h"
+#include "csr_graph.h"
 
 #pragma clang fp contract(off)
 
@@ -31,8 +32,6 @@ using namespace oai;
 constexpr int kSmoothT = 256;
 constexpr int kTile = 32;                          // the transposes move 32 x 32 tiles through LDS
 constexpr int kGather = 8;                        // neighbour slots whose loads are in flight together
-constexpr long long kMaxRows = 1LL << 20;          // of one call
-constexpr long long kMaxVerts = (1LL << 31) - 2;
 constexpr int kMaxSweeps = 4096;
 
 struct SmoothWs {
@@ -46,8 +45,6 @@ struct SmoothWs {
         bytes = ws.off;
     }
 };
-
-bool shape_ok(long long rows, long long V) { return rows >= 1 && rows <= kMaxRows && V >= 1 && V <= kMaxVerts; }
 
 // values [R][V] (+ mask or null) -> x [V][R], m [V][R]; an invalid entry becomes +0.0 / 0.  blockDim = (32, 8).
 __global__ void __launch_bounds__(kTile * 8) smooth_in_kernel(const double* __restrict__ values, const unsigned char* __restrict__ mask, long long R,
@@ -111,9 +108,8 @@ __global__ void __launch_bounds__(kSmoothT) smooth_sweep_kernel(const double* __
             if (++i >= V) break;
         }
         const long long at = i * R + r;
-        long long a = offsets[i], b = offsets[i + 1];
-        a = a < 0 ? 0 : a;
-        b = b > n_nbrs ? n_nbrs : b;
+        const CsrSlots slots = csr_slots(offsets, i, n_nbrs);
+        const long long a = slots.a, b = slots.b;
         const bool mi = m[at] != 0;
         const double xi = x[at], sw = self_w ? self_w[i] : 1.0;
         double num = 0.0, den = 0.0;
@@ -125,7 +121,8 @@ __global__ void __launch_bounds__(kSmoothT) smooth_sweep_kernel(const double* __
         // kGather slots at a time: their indices and weights are loaded together, then their values and masks, and only the adds run
         // one after the other -- a slot's two dependent loads are paid once per group, not once per neighbour (a hub of degree 200
         // would otherwise be a chain of 400 load latencies).  A slot past the end or with a neighbour out of range reads the
-        // vertex' own entry and is dropped by the select.
+        // vertex' own entry and is dropped by the select.  Of csrc/csr_graph.h this loop shares the slot range only, not the test of
+        // a neighbour: a vertex among its own neighbours counts here, and the range test feeds a select, not a branch.
         for (long long e0 = a; e0 < b; e0 += kGather) {
             double w[kGather], xj[kGather];
             int j[kGather];
@@ -162,16 +159,14 @@ __global__ void __launch_bounds__(kSmoothT) smooth_sweep_kernel(const double* __
 extern "C" {
 
 size_t oai_graph_smooth_workspace_bytes(long long n_rows, long long n_verts) {
-    if (!shape_ok(n_rows, n_verts)) return 0;
+    if (!tile_shape_ok(n_rows, n_verts)) return 0;
     return SmoothWs(nullptr, n_rows, n_verts).bytes;
 }
 
 int oai_graph_smooth(const double* values_dev, const unsigned char* mask_dev, long long n_rows, long long n_verts, const int* offsets_dev,
                      const int* neighbours_dev, long long n_neighbours, const double* edge_weight_dev, const double* self_weight_dev, int sweeps,
                      int fill, void* workspace_dev, size_t workspace_bytes, double* out_values_dev, unsigned char* out_mask_dev, void* stream) {
-    OAI_CHECK_ARG(n_rows >= 1 && n_rows <= kMaxRows, "oai_graph_smooth: needs 1 .. 2^20 rows (got %lld)", n_rows);
-    OAI_CHECK_ARG(n_verts >= 1 && n_verts <= kMaxVerts, "oai_graph_smooth: needs 1 .. 2^31-2 vertices (got %lld)", n_verts);
-    OAI_CHECK_ARG(n_neighbours >= 0, "oai_graph_smooth: negative neighbour count (%lld)", n_neighbours);
+    OAI_CHECK_GRAPH_TILE("oai_graph_smooth", n_rows, n_verts, n_neighbours);
     OAI_CHECK_ARG(sweeps >= 1 && sweeps <= kMaxSweeps, "oai_graph_smooth: sweeps must be 1 .. 4096, got %d", sweeps);
     OAI_CHECK_ARG(fill == 0 || fill == 1, "oai_graph_smooth: fill must be 0 (keep) or 1 (fill), got %d", fill);
     OAI_CHECK_ARG(workspace_dev && out_values_dev && values_dev && offsets_dev && (n_neighbours == 0 || (neighbours_dev && edge_weight_dev)),

@@ -21,7 +21,7 @@
 //   parent[] and weight[] are read by other threads between barriers: agent-scope relaxed atomics, as in oai_graph_clusters.  level[]
 //     is written once before the first barrier and only read afterwards.
 // Measured (profiles/group_tfce.md).
-#include "common.h"
+#include "cohort.h"
 
 #include <cmath>
 
@@ -34,8 +34,6 @@ namespace {
 using namespace oai;
 
 constexpr int kTfceT = 1024;                       // the workgroup of one row
-constexpr long long kMaxRows = 1LL << 20;          // of one call
-constexpr long long kMaxVerts = (1LL << 31) - 2;
 constexpr int kMaxSteps = 1 << 16;
 
 struct TfceWs {
@@ -50,8 +48,6 @@ struct TfceWs {
         bytes = ws.off;
     }
 };
-
-bool shape_ok(long long rows, long long V) { return rows >= 1 && rows <= kMaxRows && V >= 1 && V <= kMaxVerts; }
 
 // K(v): the largest k in 1 .. max_steps with (double)k * dh <= a, 0 if there is none (a NaN included).  The quotient only says where to
 // look; the answer is decided by the stated products, which do not decrease with k.
@@ -74,7 +70,7 @@ __global__ void __launch_bounds__(kTfceT) graph_tfce_kernel(const double* __rest
                                                             const long long* __restrict__ weight_in, double unit, double dh, int e_mode, int h_mode,
                                                             int max_steps, int* parent_all, int* level_all, unsigned long long* weight_all,
                                                             double* tfce_all, int* __restrict__ clipped) {
-    __shared__ int changed, top, next, n_clipped;
+    __shared__ int top, next, n_clipped;
     const double* val = values + (long long)blockIdx.x * V;
     int* parent = parent_all + (long long)blockIdx.x * V;
     int* level = level_all + (long long)blockIdx.x * V;
@@ -114,34 +110,12 @@ __global__ void __launch_bounds__(kTfceT) graph_tfce_kernel(const double* __rest
         }
         if (my_next) atomicMax(&next, my_next);
         __syncthreads();
-        // every round that hooks removes a root: at most V + 1 rounds
-        for (long long it = 0; it <= V + 1; ++it) {
-            if (threadIdx.x == 0) changed = 0;
-            __syncthreads();
-            for (int i = threadIdx.x; i < n; i += kTfceT) {
-                const int l = level[i];
-                if (l != k && l != -k) continue;                           // only an edge with a new vertex at one end is new
-                long long a = offsets[i], b = offsets[i + 1];
-                a = a < 0 ? 0 : a;
-                b = b > n_nbrs ? n_nbrs : b;
-                bool ch = false;
-                for (long long e = a; e < b; ++e) {
-                    const int u = neighbours[e];
-                    if (u < 0 || u >= n || u == i) continue;
-                    const int lu = level[u];
-                    if (l > 0 ? lu >= k : lu <= -k) ch = hook(parent, i, u) || ch;      // active at this level and of the same side
-                }
-                if (ch) changed = 1;
-            }
-            __syncthreads();
-            const int c = changed;
-            for (int i = threadIdx.x; i < n; i += kTfceT) {
-                const int l = level[i];
-                if (l >= k || l <= -k) jump(parent, i);
-            }
-            __syncthreads();
-            if (!c) break;
-        }
+        // only the vertices of this level hook, since every edge the level adds has a new vertex at one end; a neighbour counts when it is
+        // active at this level and of the same side
+        hook_jump_rounds<kTfceT>(
+            parent, V, offsets, neighbours, n_nbrs,
+            [&](int i) { const int l = level[i]; return l == k || l == -k ? l : 0; },
+            [&](int l, int u) { const int lu = level[u]; return l > 0 ? lu >= k : lu <= -k; });
         for (int i = threadIdx.x; i < n; i += kTfceT) {
             const int l = level[i];
             if (l >= k || l <= -k) atomicAdd(weight + load_agent(parent + i), weight_in ? (unsigned long long)weight_in[i] : 1ull);
@@ -175,16 +149,14 @@ __global__ void __launch_bounds__(kTfceT) graph_tfce_kernel(const double* __rest
 extern "C" {
 
 size_t oai_graph_tfce_workspace_bytes(long long n_rows, long long n_verts) {
-    if (!shape_ok(n_rows, n_verts)) return 0;
+    if (!tile_shape_ok(n_rows, n_verts)) return 0;
     return TfceWs(nullptr, n_rows, n_verts).bytes;
 }
 
 int oai_graph_tfce(const double* values_dev, long long n_rows, long long n_verts, const int* offsets_dev, const int* neighbours_dev,
                    long long n_neighbours, const long long* weight_dev, double unit, double dh, int e_mode, int h_mode, int max_steps,
                    void* workspace_dev, size_t workspace_bytes, double* tfce_dev, int* clipped_dev, void* stream) {
-    OAI_CHECK_ARG(n_rows >= 1 && n_rows <= kMaxRows, "oai_graph_tfce: needs 1 .. 2^20 rows (got %lld)", n_rows);
-    OAI_CHECK_ARG(n_verts >= 1 && n_verts <= kMaxVerts, "oai_graph_tfce: needs 1 .. 2^31-2 vertices (got %lld)", n_verts);
-    OAI_CHECK_ARG(n_neighbours >= 0, "oai_graph_tfce: negative neighbour count (%lld)", n_neighbours);
+    OAI_CHECK_GRAPH_TILE("oai_graph_tfce", n_rows, n_verts, n_neighbours);
     OAI_CHECK_ARG(dh > 0.0 && dh < (double)INFINITY, "oai_graph_tfce: the step dh must be finite and > 0 (got %g)", dh);
     OAI_CHECK_ARG(unit > 0.0, "oai_graph_tfce: the unit of extent must be > 0 (got %g)", unit);
     OAI_CHECK_ARG(e_mode == OAI_TFCE_E_HALF || e_mode == OAI_TFCE_E_ONE, "oai_graph_tfce: e_mode must be 0 (E = 1/2) or 1 (E = 1), got %d", e_mode);

@@ -38,7 +38,7 @@
 //   Measured (profiles/group_regression.md): N = 200, V = 30 002, 1000 rows: p = 4 without a mask 1.81 ms (68 % of the fp64 vector issue
 //     rate), with one 4.91 ms (56 %); p = 6 with a mask 10.7 ms (47 %).
 // prepare_kernel streams over the knees three times with one thread per vertex, as group_stats.hip's.
-#include "common.h"
+#include "cohort.h"
 
 #include <cmath>
 
@@ -50,9 +50,6 @@ using namespace oai;
 
 constexpr int kT = 256;                            // vertices of a block
 constexpr int kMaxCols = 6;                        // p
-constexpr long long kMaxKnees = 1LL << 24;
-constexpr long long kMaxRows = 1LL << 20;          // of one batch
-constexpr long long kMaxVerts = (1LL << 31) - 2;
 constexpr double kPivot = 1e-10;
 
 __host__ __device__ constexpr int tri(int p) { return p * (p + 1) / 2; }               // entries of a lower triangle; index of (a, 0)
@@ -76,8 +73,6 @@ struct Prepared {
         bytes = ws.off;
     }
 };
-
-bool shape_ok(long long N, long long V) { return N >= 2 && N <= kMaxKnees && V >= 1 && V <= kMaxVerts; }
 
 // In place: the packed lower triangle A (entry (a, c), c <= a, at tri(a) + c) becomes its Cholesky factor L, column by column, inner sums
 // in ascending k as s = s - L_ak * L_ck.  Returns whether every pivot passed; the arithmetic goes on after one that did not.
@@ -122,14 +117,9 @@ __global__ void __launch_bounds__(kT) prepare_kernel(const float* __restrict__ Y
                                                      long long N, long long V, int centre, Prepared out) {
     const long long v = (long long)blockIdx.x * kT + threadIdx.x;
     if (v >= V) return;
-    int n = 0;
-    double sum = 0.0;
-    for (long long i = 0; i < N; ++i) {
-        const bool m = mask ? mask[i * V + v] != 0 : true;
-        n += m ? 1 : 0;
-        sum = sum + (m ? (double)Y[i * V + v] : 0.0);
-    }
-    const double mu = sum / (double)n;
+    const CountedMean counted = counted_mean(Y, mask, N, V, v);
+    const int n = counted.n;
+    const double mu = counted.mean;
     constexpr int QA = QN > 0 ? QN : 1;
     double A[tri(QA)], h[QA];
     bool pass = true;
@@ -357,13 +347,13 @@ int launch_t(const Prepared& in, const unsigned char* mask, const double* design
 extern "C" {
 
 size_t oai_regression_prepare_workspace_bytes(long long n_knees, long long n_verts) {
-    if (!shape_ok(n_knees, n_verts)) return 0;
+    if (!cohort_shape_ok(n_knees, n_verts)) return 0;
     return Prepared(nullptr, n_knees, n_verts).bytes;
 }
 
 int oai_regression_prepare(const float* y_dev, const unsigned char* mask_dev, const double* nuisance_dev, long long n_knees, long long n_verts,
                            int n_nuisance, int centre, void* prepared_dev, size_t prepared_bytes, void* stream) {
-    OAI_CHECK_ARG(shape_ok(n_knees, n_verts), "oai_regression_prepare: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
+    OAI_CHECK_ARG(cohort_shape_ok(n_knees, n_verts), "oai_regression_prepare: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
     OAI_CHECK_ARG(n_nuisance >= 0 && n_nuisance <= kMaxCols - 1, "oai_regression_prepare: needs 0 .. 5 nuisance columns, got %d", n_nuisance);
     OAI_CHECK_ARG(centre == 0 || centre == 1, "oai_regression_prepare: centre must be 0 or 1, got %d", centre);
     OAI_CHECK_ARG(prepared_dev && y_dev && (n_nuisance == 0 || nuisance_dev), "oai_regression_prepare: null pointer");
@@ -382,14 +372,14 @@ int oai_regression_prepare(const float* y_dev, const unsigned char* mask_dev, co
 }
 
 size_t oai_regression_t_workspace_bytes(long long n_rows, long long n_verts, long long n_knees, int n_columns) {
-    if (n_rows < 1 || n_rows > kMaxRows || !shape_ok(n_knees, n_verts) || n_columns < 1 || n_columns > kMaxCols) return 0;
+    if (n_rows < 1 || n_rows > kMaxRows || !cohort_shape_ok(n_knees, n_verts) || n_columns < 1 || n_columns > kMaxCols) return 0;
     return TWs(nullptr, n_rows, n_verts, n_knees, n_columns).bytes;
 }
 
 int oai_regression_t(const void* prepared_dev, size_t prepared_bytes, const unsigned char* mask_dev, const double* design_dev, const int* perm_dev,
                      long long n_knees, long long n_verts, int n_columns, long long p0, long long p1, void* workspace_dev, size_t workspace_bytes,
                      double* slope0_dev, void* stream) {
-    OAI_CHECK_ARG(shape_ok(n_knees, n_verts), "oai_regression_t: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
+    OAI_CHECK_ARG(cohort_shape_ok(n_knees, n_verts), "oai_regression_t: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
     OAI_CHECK_ARG(n_columns >= 1 && n_columns <= kMaxCols, "oai_regression_t: needs 1 .. 6 design columns, got %d", n_columns);
     OAI_CHECK_ARG(p0 >= 0 && p1 > p0 && p1 - p0 <= kMaxRows, "oai_regression_t: rows [p0, p1) must hold 1 .. 2^20 rows from p0 >= 0 (got %lld, %lld)", p0, p1);
     OAI_CHECK_ARG(prepared_dev && design_dev && perm_dev && workspace_dev, "oai_regression_t: null pointer");

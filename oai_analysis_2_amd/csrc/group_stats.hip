@@ -24,7 +24,7 @@
 //   Knee tile = 32 = one label word: R scalar loads, then 32 knees of vector work.
 //   Measured (profiles/group_stats.md): N = 200, V = 30 002, 1000 labellings in 1.37 ms, 22 % of the fp64 vector issue rate.
 // The other kernels are latency-bound integer or streaming work: one element per thread or one workgroup per row.
-#include "common.h"
+#include "cohort.h"
 
 #include <cmath>
 
@@ -40,9 +40,6 @@ using namespace oai;
 constexpr int kT = 256;                            // vertices of a block (prepare, t, exceed)
 constexpr int kR = 16;                             // labellings per thread of the t kernel
 constexpr int kClusterT = 1024;                    // the workgroup of one row of oai_graph_clusters
-constexpr long long kMaxKnees = 1LL << 24;
-constexpr long long kMaxRows = 1LL << 20;          // of one batch
-constexpr long long kMaxVerts = (1LL << 31) - 2;
 constexpr long long kMaxBlocks = 1024;             // of a row's max |t| partials
 
 // ---- the prepared block ----------------------------------------------------------------------------------------------------------------
@@ -63,21 +60,14 @@ struct Prepared {
     }
 };
 
-bool shape_ok(long long N, long long V) { return N >= 2 && N <= kMaxKnees && V >= 1 && V <= kMaxVerts; }
-
 // one thread per vertex, knees in ascending index: the counted sum, then the (centred) values and their sums
 __global__ void __launch_bounds__(kT) prepare_kernel(const float* __restrict__ Y, const unsigned char* __restrict__ mask, long long N, long long V,
                                                      int centre, Prepared out) {
     const long long v = (long long)blockIdx.x * kT + threadIdx.x;
     if (v >= V) return;
-    int n = 0;
-    double sum = 0.0;
-    for (long long i = 0; i < N; ++i) {
-        const bool m = mask ? mask[i * V + v] != 0 : true;
-        n += m ? 1 : 0;
-        sum = sum + (m ? (double)Y[i * V + v] : 0.0);
-    }
-    const double mu = sum / (double)n;
+    const CountedMean counted = counted_mean(Y, mask, N, V, v);
+    const int n = counted.n;
+    const double mu = counted.mean;
     double s = 0.0, q = 0.0, qd = 0.0;
     for (long long i = 0; i < N; ++i) {
         const bool m = mask ? mask[i * V + v] != 0 : true;
@@ -244,13 +234,13 @@ struct ClusterWs {
 
 __device__ __forceinline__ int side_of(double t, double t0) { return t > t0 ? 1 : (t < -t0 ? -1 : 0); }      // NaN: 0
 
-// workgroup = one row.  Rounds of hook then jump with a barrier between, until a round hooks nothing (every round that hooks removes a
-// root: at most V + 1 rounds), as topo_loops_kernel (csrc/mesh_quality.hip); then every vertex counts itself at its root.
+// workgroup = one row.  Every vertex of either set hooks to its neighbours of the same set until nothing hooks (csrc/hook_jump.h); then
+// every vertex counts itself at its root.
 __global__ void __launch_bounds__(kClusterT) graph_clusters_kernel(const double* __restrict__ values, long long V, const int* __restrict__ offsets,
                                                                    const int* __restrict__ neighbours, long long n_nbrs, double t0, int* parent_all,
                                                                    int* count_all, int* __restrict__ max_extent, int* __restrict__ label0,
                                                                    int* __restrict__ size0) {
-    __shared__ int changed, largest;
+    __shared__ int largest;
     const double* val = values + (long long)blockIdx.x * V;
     int* parent = parent_all + (long long)blockIdx.x * V;
     int* count = count_all + (long long)blockIdx.x * V;
@@ -261,30 +251,10 @@ __global__ void __launch_bounds__(kClusterT) graph_clusters_kernel(const double*
     }
     if (threadIdx.x == 0) largest = 0;
     __syncthreads();
-    for (long long it = 0; it <= V + 1; ++it) {
-        if (threadIdx.x == 0) changed = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += kClusterT) {
-            const int s = side_of(val[i], t0);
-            if (s == 0) continue;
-            long long a = offsets[i], b = offsets[i + 1];
-            a = a < 0 ? 0 : a;
-            b = b > n_nbrs ? n_nbrs : b;
-            bool ch = false;
-            for (long long k = a; k < b; ++k) {
-                const int u = neighbours[k];
-                if (u < 0 || u >= n || u == i) continue;
-                if (side_of(val[u], t0) == s) ch = hook(parent, i, u) || ch;
-            }
-            if (ch) changed = 1;
-        }
-        __syncthreads();
-        const int c = changed;
-        for (int i = threadIdx.x; i < n; i += kClusterT)
-            if (load_agent(parent + i) >= 0) jump(parent, i);
-        __syncthreads();
-        if (!c) break;
-    }
+    hook_jump_rounds<kClusterT>(
+        parent, V, offsets, neighbours, n_nbrs,
+        [&](int i) { return side_of(val[i], t0); },
+        [&](int s, int u) { return side_of(val[u], t0) == s; });
     for (int i = threadIdx.x; i < n; i += kClusterT) {
         const int p = load_agent(parent + i);
         if (p >= 0) atomicAdd(count + p, 1);
@@ -306,13 +276,13 @@ __global__ void __launch_bounds__(kClusterT) graph_clusters_kernel(const double*
 extern "C" {
 
 size_t oai_group_prepare_workspace_bytes(long long n_knees, long long n_verts) {
-    if (!shape_ok(n_knees, n_verts)) return 0;
+    if (!cohort_shape_ok(n_knees, n_verts)) return 0;
     return Prepared(nullptr, n_knees, n_verts).bytes;
 }
 
 int oai_group_prepare(const float* y_dev, const unsigned char* mask_dev, long long n_knees, long long n_verts, int centre, void* workspace_dev,
                       size_t workspace_bytes, void* stream) {
-    OAI_CHECK_ARG(shape_ok(n_knees, n_verts), "oai_group_prepare: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
+    OAI_CHECK_ARG(cohort_shape_ok(n_knees, n_verts), "oai_group_prepare: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
     OAI_CHECK_ARG(centre == 0 || centre == 1, "oai_group_prepare: centre must be 0 or 1, got %d", centre);
     OAI_CHECK_ARG(workspace_dev && y_dev, "oai_group_prepare: null pointer");
     OAI_CHECK_WORKSPACE("oai_group_prepare", workspace_bytes, oai_group_prepare_workspace_bytes(n_knees, n_verts));
@@ -323,13 +293,13 @@ int oai_group_prepare(const float* y_dev, const unsigned char* mask_dev, long lo
 }
 
 size_t oai_permutation_t_workspace_bytes(long long n_rows, long long n_verts) {
-    if (n_rows < 1 || n_rows > kMaxRows || n_verts < 1 || n_verts > kMaxVerts) return 0;
+    if (!tile_shape_ok(n_rows, n_verts)) return 0;
     return round256((size_t)n_rows * (size_t)n_verts * sizeof(double));
 }
 
 int oai_permutation_t(const void* prepared_dev, size_t prepared_bytes, const unsigned char* mask_dev, const unsigned* bits_dev, long long n_knees,
                       long long n_verts, long long p0, long long p1, int mode, void* workspace_dev, size_t workspace_bytes, void* stream) {
-    OAI_CHECK_ARG(shape_ok(n_knees, n_verts), "oai_permutation_t: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
+    OAI_CHECK_ARG(cohort_shape_ok(n_knees, n_verts), "oai_permutation_t: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
     OAI_CHECK_ARG(p0 >= 0 && p1 > p0 && p1 - p0 <= kMaxRows, "oai_permutation_t: rows [p0, p1) must hold 1 .. 2^20 rows from p0 >= 0 (got %lld, %lld)", p0, p1);
     OAI_CHECK_ARG(mode == OAI_STATS_TWO_SAMPLE || mode == OAI_STATS_ONE_SAMPLE, "oai_permutation_t: mode must be 0 (two-sample) or 1 (one-sample), got %d", mode);
     OAI_CHECK_ARG(prepared_dev && bits_dev && workspace_dev, "oai_permutation_t: null pointer");
@@ -354,7 +324,7 @@ int oai_permutation_t(const void* prepared_dev, size_t prepared_bytes, const uns
 }
 
 size_t oai_permutation_reduce_workspace_bytes(long long n_rows, long long n_verts) {
-    if (n_rows < 1 || n_rows > kMaxRows || n_verts < 1 || n_verts > kMaxVerts) return 0;
+    if (!tile_shape_ok(n_rows, n_verts)) return 0;
     return ReduceWs(nullptr, n_rows, n_verts).bytes;
 }
 
@@ -377,16 +347,14 @@ int oai_permutation_reduce(const double* tile_dev, long long n_verts, long long 
 }
 
 size_t oai_graph_clusters_workspace_bytes(long long n_rows, long long n_verts) {
-    if (n_rows < 1 || n_rows > kMaxRows || n_verts < 1 || n_verts > kMaxVerts) return 0;
+    if (!tile_shape_ok(n_rows, n_verts)) return 0;
     return ClusterWs(nullptr, n_rows, n_verts).bytes;
 }
 
 int oai_graph_clusters(const double* values_dev, long long n_rows, long long n_verts, const int* offsets_dev, const int* neighbours_dev,
                        long long n_neighbours, double t0, void* workspace_dev, size_t workspace_bytes, int* max_extent_dev, int* label0_dev,
                        int* size0_dev, void* stream) {
-    OAI_CHECK_ARG(n_rows >= 1 && n_rows <= kMaxRows, "oai_graph_clusters: needs 1 .. 2^20 rows (got %lld)", n_rows);
-    OAI_CHECK_ARG(n_verts >= 1 && n_verts <= kMaxVerts, "oai_graph_clusters: needs 1 .. 2^31-2 vertices (got %lld)", n_verts);
-    OAI_CHECK_ARG(n_neighbours >= 0, "oai_graph_clusters: negative neighbour count (%lld)", n_neighbours);
+    OAI_CHECK_GRAPH_TILE("oai_graph_clusters", n_rows, n_verts, n_neighbours);
     OAI_CHECK_ARG(t0 > 0.0, "oai_graph_clusters: the threshold must be > 0 (got %g)", t0);
     OAI_CHECK_ARG(workspace_dev && max_extent_dev && values_dev && offsets_dev && (n_neighbours == 0 || neighbours_dev),
                   "oai_graph_clusters: null pointer");

@@ -635,6 +635,50 @@ class GroupPrepared:
     n: torch.Tensor
 
 
+def _block_views(block: torch.Tensor, layout) -> dict:
+    """Views of the arrays of a prepared block: ``layout`` names them front to back as (name, dtype, shape), each starting on the next
+    multiple of 256 bytes, as csrc/common.h hands a workspace out."""
+    off, parts = 0, {}
+    for name, dtype, shape in layout:
+        nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+        parts[name] = block[off:off + nbytes].view(dtype).reshape(shape)
+        off += (nbytes + 255) // 256 * 256
+    return parts
+
+
+def _tile_workspace(workspace: Optional[torch.Tensor], need: int, device) -> torch.Tensor:
+    """The caller's buffer for a t tile (reused between batches) once it is checked, or a new one of ``need`` bytes."""
+    ws = torch.empty(need, dtype=torch.uint8, device=device) if workspace is None else workspace
+    if ws.numel() < need or ws.device != device or ws.dtype != torch.uint8:
+        raise ValueError(f"workspace must be a uint8 buffer of at least {need} bytes on {device}")
+    return ws
+
+
+def _graph_tile(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.Tensor):
+    """What the graph kernels take: a float64 tile [R >= 1, V >= 1] and the int32 CSR adjacency of its V vertices on the same GPU.
+    Returns (values, offsets, neighbours, R, V), the tensors contiguous."""
+    values = _chk(values, "values", torch.float64)
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"values must be [R >= 1, V >= 1], got {tuple(values.shape)}")
+    R, V = int(values.shape[0]), int(values.shape[1])
+    offsets, neighbours = _chk(offsets, "offsets", torch.int32), _chk(neighbours, "neighbours", torch.int32)
+    if offsets.numel() != V + 1 or offsets.device != values.device or neighbours.device != values.device:
+        raise ValueError(f"offsets must be [{V + 1}] and live with neighbours on the values' GPU, got {offsets.numel()} on {offsets.device}")
+    return values, offsets, neighbours, R, V
+
+
+def _out_tile(out: Optional[torch.Tensor], name: str, dtype, values: torch.Tensor, may_alias: bool) -> torch.Tensor:
+    """The caller's output tile of a graph kernel once it is checked -- contiguous, of ``dtype``, with the shape and GPU of ``values``
+    and, unless the kernel ``may_alias`` its input, not ``values`` itself -- or a new one."""
+    if out is None:
+        return torch.empty(tuple(values.shape), dtype=dtype, device=values.device)
+    if (out.device != values.device or out.dtype != dtype or tuple(out.shape) != tuple(values.shape) or not out.is_contiguous()
+            or (not may_alias and out.data_ptr() == values.data_ptr())):
+        raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[1]} [{values.shape[0]}, {values.shape[1]}] tensor on {values.device}"
+                         + ("" if may_alias else " other than values"))
+    return out
+
+
 def _stats_mask(mask: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
     if mask is None:
         return None
@@ -657,12 +701,8 @@ def group_prepare(values: torch.Tensor, mask: Optional[torch.Tensor] = None, cen
     block = _lib.workspace("oai_group_prepare", values.device, N, V)
     _lib.call("oai_group_prepare", values.data_ptr(), _ptr(mask), N, V, int(bool(centre)), block.data_ptr(), block.numel(), _lib.STREAM,
               device=values.device)
-    off, parts = 0, {}
-    for name, dtype, shape in (("C", torch.float64, (N, V)), ("Qm", torch.float64, (N, V)), ("S", torch.float64, (V,)), ("Q", torch.float64, (V,)),
-                               ("mean", torch.float64, (V,)), ("std", torch.float64, (V,)), ("n", torch.int32, (V,))):
-        nbytes = int(np.prod(shape)) * (8 if dtype == torch.float64 else 4)
-        parts[name] = block[off:off + nbytes].view(dtype).reshape(shape)
-        off += (nbytes + 255) // 256 * 256
+    parts = _block_views(block, (("C", torch.float64, (N, V)), ("Qm", torch.float64, (N, V)), ("S", torch.float64, (V,)), ("Q", torch.float64, (V,)),
+                                 ("mean", torch.float64, (V,)), ("std", torch.float64, (V,)), ("n", torch.int32, (V,))))
     return GroupPrepared(block, N, V, bool(centre), mask, **parts)
 
 
@@ -689,9 +729,7 @@ def permutation_t(prepared: GroupPrepared, bits: torch.Tensor, p0: int, p1: int,
         raise ValueError("the two-sample test needs group_prepare(centre=True), the one-sample test centre=False")
     dev, V = prepared.block.device, prepared.n_verts
     need = int(_lib.load().oai_permutation_t_workspace_bytes(p1 - p0, V))
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if ws.numel() < need or ws.device != dev or ws.dtype != torch.uint8:
-        raise ValueError(f"workspace must be a uint8 buffer of at least {need} bytes on {dev}")
+    ws = _tile_workspace(workspace, need, dev)
     _lib.call("oai_permutation_t", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), bits.data_ptr(), prepared.n_knees, V, p0, p1,
               int(mode), ws.data_ptr(), ws.numel(), _lib.STREAM, device=dev)
     return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
@@ -721,13 +759,7 @@ def graph_clusters(values: torch.Tensor, offsets: torch.Tensor, neighbours: torc
     [R] DEVICE tensor of each row's largest component (vertices; both signs; 0 if none; ``max_extent``: written there); with
     ``return_labels`` also row 0's int32 [V] labels (the component's smallest vertex index, -1 outside both sets) and per-vertex component
     sizes.  Integers only.  Does not synchronise."""
-    values = _chk(values, "values", torch.float64)
-    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
-        raise ValueError(f"values must be [R >= 1, V >= 1], got {tuple(values.shape)}")
-    R, V = int(values.shape[0]), int(values.shape[1])
-    offsets, neighbours = _chk(offsets, "offsets", torch.int32), _chk(neighbours, "neighbours", torch.int32)
-    if offsets.numel() != V + 1 or offsets.device != values.device or neighbours.device != values.device:
-        raise ValueError(f"offsets must be [{V + 1}] and live with neighbours on the values' GPU, got {offsets.numel()} on {offsets.device}")
+    values, offsets, neighbours, R, V = _graph_tile(values, offsets, neighbours)
     if not float(threshold) > 0.0:
         raise ValueError(f"threshold must be > 0, got {threshold!r}")
     ext = _out_slot(max_extent, R, torch.int32, values.device, "max_extent")
@@ -748,13 +780,7 @@ def graph_tfce(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.Te
     component times ``unit``, or the component's vertex count without weights.  E is 0.5 or 1, H is 1 or 2.  Returns the float64 [R,V]
     and int32 [R] DEVICE tensors (tfce, clipped): ``clipped`` counts the row's vertices whose |value| reaches past ``max_steps`` levels
     (``out``, ``clipped``: written there).  Bit-reproducible.  Does not synchronise."""
-    values = _chk(values, "values", torch.float64)
-    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
-        raise ValueError(f"values must be [R >= 1, V >= 1], got {tuple(values.shape)}")
-    R, V = int(values.shape[0]), int(values.shape[1])
-    offsets, neighbours = _chk(offsets, "offsets", torch.int32), _chk(neighbours, "neighbours", torch.int32)
-    if offsets.numel() != V + 1 or offsets.device != values.device or neighbours.device != values.device:
-        raise ValueError(f"offsets must be [{V + 1}] and live with neighbours on the values' GPU, got {offsets.numel()} on {offsets.device}")
+    values, offsets, neighbours, R, V = _graph_tile(values, offsets, neighbours)
     if float(E) not in TFCE_E_MODES or float(H) not in TFCE_H_MODES:
         raise ValueError(f"E must be 0.5 or 1 and H must be 1 or 2, got E = {E!r}, H = {H!r}")
     if not (float(dh) > 0.0 and math.isfinite(float(dh))):
@@ -767,11 +793,7 @@ def graph_tfce(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.Te
         weights = _chk(weights, "weights", torch.int64)
         if tuple(weights.shape) != (V,) or weights.device != values.device:
             raise ValueError(f"weights must be int64 [{V}] on the values' GPU, got {tuple(weights.shape)} on {weights.device}")
-    if out is None:
-        out = torch.empty((R, V), dtype=torch.float64, device=values.device)
-    elif (out.device != values.device or out.dtype != torch.float64 or tuple(out.shape) != (R, V) or not out.is_contiguous()
-          or out.data_ptr() == values.data_ptr()):
-        raise ValueError(f"out must be a contiguous float64 [{R}, {V}] tensor on {values.device} other than values")
+    out = _out_tile(out, "out", torch.float64, values, may_alias=False)
     clip = _out_slot(clipped, R, torch.int32, values.device, "clipped")
     ws = _lib.workspace("oai_graph_tfce", values.device, R, V)
     _lib.call("oai_graph_tfce", values.data_ptr(), R, V, offsets.data_ptr(), _ptr(neighbours, neighbours.numel()), int(neighbours.numel()),
@@ -793,14 +815,8 @@ def graph_smooth(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.
     valid set grows by one ring per sweep.  Weights must be finite and >= 0: not checked.  Returns the float64 [R,V] and uint8 [R,V]
     DEVICE tensors (values, mask): +0.0 and 0 where the result is missing (``out``, ``out_mask``: written there; ``out`` may be
     ``values`` and ``out_mask`` may be ``mask``).  Bit-reproducible.  Does not synchronise."""
-    values = _chk(values, "values", torch.float64)
-    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
-        raise ValueError(f"values must be [R >= 1, V >= 1], got {tuple(values.shape)}")
-    R, V = int(values.shape[0]), int(values.shape[1])
+    values, offsets, neighbours, R, V = _graph_tile(values, offsets, neighbours)
     dev = values.device
-    offsets, neighbours = _chk(offsets, "offsets", torch.int32), _chk(neighbours, "neighbours", torch.int32)
-    if offsets.numel() != V + 1 or offsets.device != dev or neighbours.device != dev:
-        raise ValueError(f"offsets must be [{V + 1}] and live with neighbours on the values' GPU, got {offsets.numel()} on {offsets.device}")
     edge_weights = _chk(edge_weights, "edge_weights", torch.float64)
     if edge_weights.numel() != neighbours.numel() or edge_weights.device != dev:
         raise ValueError(f"edge_weights must be float64 [{neighbours.numel()}] on the values' GPU, got {tuple(edge_weights.shape)} on "
@@ -812,14 +828,8 @@ def graph_smooth(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.
     if not 1 <= int(sweeps) <= MAX_SMOOTH_SWEEPS:
         raise ValueError(f"sweeps must be 1 .. {MAX_SMOOTH_SWEEPS}, got {sweeps!r}")
     mask = _stats_mask(mask, values)
-    if out is None:
-        out = torch.empty((R, V), dtype=torch.float64, device=dev)
-    elif out.device != dev or out.dtype != torch.float64 or tuple(out.shape) != (R, V) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float64 [{R}, {V}] tensor on {dev}")
-    if out_mask is None:
-        out_mask = torch.empty((R, V), dtype=torch.uint8, device=dev)
-    elif out_mask.device != dev or out_mask.dtype != torch.uint8 or tuple(out_mask.shape) != (R, V) or not out_mask.is_contiguous():
-        raise ValueError(f"out_mask must be a contiguous uint8 [{R}, {V}] tensor on {dev}")
+    out = _out_tile(out, "out", torch.float64, values, may_alias=True)
+    out_mask = _out_tile(out_mask, "out_mask", torch.uint8, values, may_alias=True)
     ws = _lib.workspace("oai_graph_smooth", dev, R, V)
     n_nbrs = int(neighbours.numel())
     _lib.call("oai_graph_smooth", values.data_ptr(), _ptr(mask), R, V, offsets.data_ptr(), _ptr(neighbours, n_nbrs), n_nbrs,
@@ -875,12 +885,8 @@ def regression_prepare(values: torch.Tensor, mask: Optional[torch.Tensor] = None
     block = _lib.workspace("oai_regression_prepare", values.device, N, V)
     _lib.call("oai_regression_prepare", values.data_ptr(), _ptr(mask), nuisance.data_ptr() if q else None, N, V, q, int(bool(centre)),
               block.data_ptr(), block.numel(), _lib.STREAM, device=values.device)
-    off, parts = 0, {}
-    for name, dtype, shape, size in (("R", torch.float64, (N, V), 8), ("Q", torch.float64, (V,), 8), ("mean", torch.float64, (V,), 8),
-                                     ("n", torch.int32, (V,), 4), ("ok", torch.uint8, (V,), 1)):
-        nbytes = int(np.prod(shape)) * size
-        parts[name] = block[off:off + nbytes].view(dtype).reshape(shape)
-        off += (nbytes + 255) // 256 * 256
+    parts = _block_views(block, (("R", torch.float64, (N, V)), ("Q", torch.float64, (V,)), ("mean", torch.float64, (V,)), ("n", torch.int32, (V,)),
+                                 ("ok", torch.uint8, (V,))))
     return RegressionPrepared(block, N, V, q, bool(centre), mask, **parts)
 
 
@@ -904,9 +910,7 @@ def regression_t(prepared: RegressionPrepared, design: torch.Tensor, perm: torch
         if tuple(slope0.shape) != (V,) or slope0.device != dev:
             raise ValueError(f"slope0 must be float64 [{V}] on {dev}, got {tuple(slope0.shape)} on {slope0.device}")
     need = int(_lib.load().oai_regression_t_workspace_bytes(p1 - p0, V, N, p))
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if ws.numel() < need or ws.device != dev or ws.dtype != torch.uint8:
-        raise ValueError(f"workspace must be a uint8 buffer of at least {need} bytes on {dev}")
+    ws = _tile_workspace(workspace, need, dev)
     _lib.call("oai_regression_t", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p,
               p0, p1, ws.data_ptr(), ws.numel(), _ptr(slope0), _lib.STREAM, device=dev)
     return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)

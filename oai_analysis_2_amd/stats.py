@@ -88,6 +88,14 @@ def _as_groups(groups) -> np.ndarray:
     return g.astype(bool)
 
 
+def _block_members(blocks, n_knees: int) -> List[np.ndarray]:
+    """The knee indices of every block, ascending, in ascending block label; without ``blocks`` all knees are one block."""
+    b = np.zeros(n_knees, np.int64) if blocks is None else np.asarray(blocks)
+    if b.shape != (n_knees,):
+        raise ValueError(f"blocks must hold one label per knee ({n_knees}), got shape {b.shape}")
+    return [np.nonzero(b == lab)[0] for lab in np.unique(b)]
+
+
 def label_permutations(groups, n_permutations: int, seed: int = 0, blocks=None) -> Permutations:
     """Labellings for ``two_sample_test``: row 0 is ``groups`` itself (1 / True = group 1), every other row a rearrangement of the labels
     that keeps both group sizes.  ``blocks``: an int label per knee (site, sex, ...); labels then move within a block only.  When the
@@ -97,10 +105,7 @@ def label_permutations(groups, n_permutations: int, seed: int = 0, blocks=None) 
     N, P = len(g), int(n_permutations)
     if P < 1:
         raise ValueError(f"n_permutations must be >= 1, got {n_permutations}")
-    b = np.zeros(N, np.int64) if blocks is None else np.asarray(blocks)
-    if b.shape != (N,):
-        raise ValueError(f"blocks must hold one label per knee ({N}), got shape {b.shape}")
-    members = [np.nonzero(b == lab)[0] for lab in np.unique(b)]
+    members = _block_members(blocks, N)
     total = math.prod(math.comb(len(idx), int(g[idx].sum())) for idx in members)
     if total <= P:
         rows = [g.copy()]
@@ -501,40 +506,6 @@ def tfce_weights(areas: np.ndarray) -> np.ndarray:
     return weights
 
 
-class _Tfce:
-    """The device side of one test's TFCE: the settings, the graph, the weights (uploaded once) and the running results."""
-
-    def __init__(self, settings: TFCE, cohort_like, P: int, V: int, rows: int, dev):
-        self.settings = settings
-        self.graph = cohort_like.surface_graph()
-        self.weights, self.unit = None, 1.0
-        if settings.extent == "area":
-            self.weights, self.unit = torch.from_numpy(tfce_weights(cohort_like.vertex_areas())).to(dev), _TFCE_AREA_UNIT
-        self.tile = torch.empty((min(rows, P), V), dtype=torch.float64, device=dev)
-        self.tfce0 = torch.empty(V, dtype=torch.float64, device=dev)
-        self.max_tfce = torch.empty(P, dtype=torch.float64, device=dev)
-        self.exceed = torch.empty(V, dtype=torch.int64, device=dev)
-        self.clipped = torch.empty(P, dtype=torch.int32, device=dev)
-
-    def batch(self, tile: torch.Tensor, p0: int, p1: int) -> None:
-        s = self.settings
-        enhanced, _ = ops.graph_tfce(tile, self.graph[0], self.graph[1], dh=s.dh, E=s.E, H=s.H, weights=self.weights, unit=self.unit,
-                                     max_steps=int(s.max_steps), out=self.tile[:p1 - p0], clipped=self.clipped[p0:p1])
-        ops.permutation_reduce(enhanced, p0, self.tfce0, self.max_tfce, self.exceed)
-
-    def tensors(self) -> List[torch.Tensor]:
-        return [self.tfce0, self.max_tfce, self.exceed, self.clipped]
-
-
-def _set_tfce(res, settings: Optional[TFCE], host, P: int) -> None:
-    """The TFCE fields of a result, from the downloaded (tfce0, max_tfce, exceed, clipped)."""
-    if settings is None:
-        return
-    tfce0, max_tfce, exceed, clipped = host
-    res.tfce, res.max_tfce, res.tfce_clipped, res.tfce_settings = tfce0, max_tfce, int(np.count_nonzero(clipped)), settings
-    res.p_tfce_uncorrected, res.p_tfce = _p_values(tfce0, max_tfce, exceed, P)
-
-
 @dataclass
 class Cluster:
     label: int               # the cluster's smallest vertex index: its value in ``cluster_label``
@@ -544,8 +515,37 @@ class Cluster:
     p_cluster: float         # share of labellings whose largest cluster has at least this extent
 
 
+@dataclass(kw_only=True)
+class _SurfaceResult:
+    """What the results of the three tests share: the cluster and TFCE fields (keyword-only, after the test's own fields) and ``image``,
+    which takes the names in ``IMAGES``.  A result class declares its own fields -- ``kind``, the cartilage, among them -- and ``IMAGES``."""
+    cluster_threshold: Optional[float] = None
+    cluster_label: Optional[np.ndarray] = None
+    clusters: List[Cluster] = field(default_factory=list)
+    max_extent: Optional[np.ndarray] = None
+    tfce: Optional[np.ndarray] = None
+    p_tfce: Optional[np.ndarray] = None
+    p_tfce_uncorrected: Optional[np.ndarray] = None
+    max_tfce: Optional[np.ndarray] = None
+    tfce_clipped: int = 0
+    tfce_settings: Optional["TFCE"] = None
+
+    IMAGES = ()
+
+    def image(self, atlas, what: str = "t"):
+        """``atlas.image`` of one of the result's ``IMAGES`` (float32 [H, W], NaN off the surface) -- of a ``PermutationResult``: "t", "p_fwer",
+        "p_uncorrected", "mean_difference", "cluster_label", "tfce" or "p_tfce"; of a ``RegressionResult``: "t", "slope", "partial_r",
+        "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce" or "p_tfce"."""
+        if what not in self.IMAGES:
+            raise ValueError(f"no image of {what!r}")
+        vec = getattr(self, what)
+        if vec is None:
+            raise ValueError("the test ran without tfce" if "tfce" in what else "the test ran without a cluster threshold")
+        return atlas.image(np.asarray(vec, np.float32), self.kind)
+
+
 @dataclass
-class PermutationResult:
+class PermutationResult(_SurfaceResult):
     """``t`` float64 [V] (NaN where no t exists: fewer than two knees on a side, or no variance); ``n1``, ``n2`` the knees with a value
     per vertex and side (paired: both the number of pairs); ``mean_difference`` group 1 - group 2 (paired: mean of a - b);
     ``p_uncorrected`` = share of labellings with |t| at least the observed at that vertex; ``p_fwer`` = share of labellings whose max |t|
@@ -566,34 +566,21 @@ class PermutationResult:
     max_abs: np.ndarray
     n_permutations: int
     exact: bool
-    cluster_threshold: Optional[float] = None
-    cluster_label: Optional[np.ndarray] = None
-    clusters: List[Cluster] = field(default_factory=list)
-    max_extent: Optional[np.ndarray] = None
-    tfce: Optional[np.ndarray] = None
-    p_tfce: Optional[np.ndarray] = None
-    p_tfce_uncorrected: Optional[np.ndarray] = None
-    max_tfce: Optional[np.ndarray] = None
-    tfce_clipped: int = 0
-    tfce_settings: Optional["TFCE"] = None
 
-    def image(self, atlas, what: str = "t"):
-        """``atlas.image`` of "t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label", "tfce" or "p_tfce" (float32 [H, W], NaN off
-        the surface)."""
-        if what not in ("t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label", "tfce", "p_tfce"):
-            raise ValueError(f"no image of {what!r}")
-        vec = getattr(self, what)
-        if vec is None:
-            raise ValueError("the test ran without tfce" if "tfce" in what else "the test ran without a cluster threshold")
-        return atlas.image(np.asarray(vec, np.float32), self.kind)
+    IMAGES = ("t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label", "tfce", "p_tfce")
+
+
+def _batch_rows(n_verts: int, n_permutations: int, clusters: bool, tfce: bool, budget: int, row_bytes: int = 0) -> int:
+    """Rows per batch: what fits ``budget`` bytes of workspace -- per row 8 bytes per vertex of t tile, 8 more of labels and sizes with
+    clusters, 24 more of TFCE tile and union-find with ``tfce``, and ``row_bytes`` of the test's own -- rounded down to sixteen rows (a
+    multiple of every rows-per-thread of the t kernels), at least sixteen."""
+    rows = budget // (int(n_verts) * ((16 if clusters else 8) + (_TFCE_BYTES if tfce else 0)) + row_bytes)
+    return int(min(max(rows // _ROW_GROUP * _ROW_GROUP, _ROW_GROUP), max(int(n_permutations), 1)))
 
 
 def default_batch(n_verts: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET, tfce: bool = False) -> int:
-    """Labellings per batch: what fits ``budget`` bytes of workspace -- 8 bytes per (labelling, vertex) of t tile, 8 more of labels and
-    sizes with clusters, and 24 more of TFCE tile and union-find with ``tfce`` -- rounded down to the t kernel's sixteen rows per thread,
-    at least sixteen."""
-    rows = budget // (int(n_verts) * ((16 if clusters else 8) + (_TFCE_BYTES if tfce else 0)))
-    return int(min(max(rows // _ROW_GROUP * _ROW_GROUP, _ROW_GROUP), max(int(n_permutations), 1)))
+    """Labellings per batch of ``two_sample_test`` and ``paired_test``: ``_batch_rows`` with nothing of the test's own per row."""
+    return _batch_rows(n_verts, n_permutations, clusters, tfce, budget)
 
 
 def _download(tensors: Sequence[torch.Tensor]) -> List[np.ndarray]:
@@ -607,50 +594,79 @@ def _download(tensors: Sequence[torch.Tensor]) -> List[np.ndarray]:
     return out
 
 
-def _run(cohort_like, values: torch.Tensor, mask: Optional[torch.Tensor], perms: Permutations, mode: int, cluster_threshold: Optional[float],
-         batch: Optional[int], extra, tfce: Optional[TFCE] = None):
-    """The batches of one test, queued without a synchronisation; returns the host arrays of (t0, max_abs, exceed, max_extent | None,
-    label | None, size | None, *extra) after one download, and those of TFCE (tfce0, max_tfce, exceed, clipped), or None without
-    ``tfce``.  ``extra``: device tensors to bring along, or a function of the prepared block that names them."""
-    N, V = int(values.shape[0]), int(values.shape[1])
-    if perms.n_knees != N:
-        raise ValueError(f"the labellings are for {perms.n_knees} knees, the cohort has {N}")
-    P = len(perms)
-    dev = values.device
-    graph = None
-    if cluster_threshold is not None:
-        if not float(cluster_threshold) > 0.0:
+class _Batches:
+    """The batches of one test: the device side of what the three tests share -- the graph, the TFCE weights (uploaded once), the running
+    results -- then the loop over ``rows`` rows at a time, ONE download, and the result fields that do not depend on the test.
+    ``row_bytes``: what a row of a batch takes beyond its tiles, for the default of ``batch`` (``_batch_rows``)."""
+
+    def __init__(self, cohort_like, P: int, V: int, dev, cluster_threshold: Optional[float], tfce: Optional[TFCE], batch: Optional[int],
+                 row_bytes: int = 0):
+        if cluster_threshold is not None and not float(cluster_threshold) > 0.0:
             raise ValueError(f"cluster_threshold must be > 0, got {cluster_threshold!r}")
-        graph = cohort_like.surface_graph()
-    rows = default_batch(V, P, graph is not None, tfce=tfce is not None) if batch is None else int(batch)
-    if rows < 1:
-        raise ValueError(f"batch must be >= 1, got {batch}")
-    with torch.cuda.device(dev):
-        enhance = _Tfce(tfce, cohort_like, P, V, rows, dev) if tfce is not None else None
-        bits = torch.from_numpy(np.ascontiguousarray(perms.bits).view(np.int32)).to(dev)
-        prepared = ops.group_prepare(values, mask, centre=mode == ops.STATS_TWO_SAMPLE)
-        t0 = torch.empty(V, dtype=torch.float64, device=dev)
-        max_abs = torch.empty(P, dtype=torch.float64, device=dev)
-        exceed = torch.empty(V, dtype=torch.int64, device=dev)
-        max_extent = torch.empty(P, dtype=torch.int32, device=dev) if graph is not None else None
-        label = size = None
-        tile_ws = _lib.workspace("oai_permutation_t", dev, min(rows, P), V)
-        for p0 in range(0, P, rows):
-            p1 = min(p0 + rows, P)
-            tile = ops.permutation_t(prepared, bits, p0, p1, mode, workspace=tile_ws)
-            ops.permutation_reduce(tile, p0, t0, max_abs, exceed)
-            if graph is not None:
-                got = ops.graph_clusters(tile, graph[0], graph[1], float(cluster_threshold), max_extent=max_extent[p0:p1], return_labels=p0 == 0)
-                if p0 == 0:
-                    _, label, size = got
-            if enhance is not None:
-                enhance.batch(tile, p0, p1)
-        out = [t0, max_abs, exceed] + ([max_extent, label, size] if graph is not None else []) + list(extra(prepared) if callable(extra) else extra)
-        host = _download(out + (enhance.tensors() if enhance is not None else []))
-    host, tfce_host = (host[:len(out)], host[len(out):]) if enhance is not None else (host, None)
-    if graph is None:
-        host[3:3] = [None, None, None]
-    return host, tfce_host
+        rows = _batch_rows(V, P, cluster_threshold is not None, tfce is not None, WORKSPACE_BUDGET, row_bytes) if batch is None else int(batch)
+        if rows < 1:
+            raise ValueError(f"batch must be >= 1, got {batch}")
+        self.cohort, self.P, self.V, self.dev, self.rows = cohort_like, P, V, dev, min(rows, P)
+        self.threshold, self.tfce = cluster_threshold, tfce
+        self.graph = cohort_like.surface_graph() if cluster_threshold is not None or tfce is not None else None
+
+        def empty(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=dev)
+
+        self.out = {"t": empty(V, torch.float64), "max_abs": empty(P, torch.float64), "exceed": empty(V, torch.int64)}
+        if cluster_threshold is not None:
+            self.out["max_extent"] = empty(P, torch.int32)
+        if tfce is not None:
+            self.weights, self.unit = None, 1.0
+            if tfce.extent == "area":
+                self.weights, self.unit = torch.from_numpy(tfce_weights(cohort_like.vertex_areas())).to(dev), _TFCE_AREA_UNIT
+            self.tfce_tile = empty((self.rows, V), torch.float64)
+            self.out.update(tfce=empty(V, torch.float64), max_tfce=empty(P, torch.float64), tfce_exceed=empty(V, torch.int64),
+                            tfce_clipped=empty(P, torch.int32))
+
+    def run(self, tile_of, extras) -> Tuple[dict, dict]:
+        """Queues every batch without a synchronisation -- ``tile_of(p0, p1)``: the float64 [p1 - p0, V] t tile of rows [p0, p1), then the
+        reduce, the clusters and the TFCE of that tile -- and downloads once.  Returns the host arrays by name (the running results and
+        ``extras``, a dict of named device tensors to bring along) and the keyword arguments of the result that every test shares."""
+        out, P, graph, s = self.out, self.P, self.graph, self.tfce
+        with torch.cuda.device(self.dev):
+            for p0 in range(0, P, self.rows):
+                p1 = min(p0 + self.rows, P)
+                tile = tile_of(p0, p1)
+                ops.permutation_reduce(tile, p0, out["t"], out["max_abs"], out["exceed"])
+                if self.threshold is not None:
+                    got = ops.graph_clusters(tile, graph[0], graph[1], float(self.threshold), max_extent=out["max_extent"][p0:p1],
+                                             return_labels=p0 == 0)
+                    if p0 == 0:
+                        _, out["label"], out["size"] = got
+                if s is not None:
+                    enhanced, _ = ops.graph_tfce(tile, graph[0], graph[1], dh=s.dh, E=s.E, H=s.H, weights=self.weights, unit=self.unit,
+                                                 max_steps=int(s.max_steps), out=self.tfce_tile[:p1 - p0], clipped=out["tfce_clipped"][p0:p1])
+                    ops.permutation_reduce(enhanced, p0, out["tfce"], out["max_tfce"], out["tfce_exceed"])
+            names = list(out) + list(extras)
+            assert len(set(names)) == len(names), f"an extra tensor takes the name of a running result: {sorted(extras)}"
+            host = dict(zip(names, _download([*out.values(), *extras.values()])))
+        return host, self._fields(host)
+
+    def _fields(self, host: dict) -> dict:
+        t, P = host["t"], self.P
+        p_unc, p_fwer = _p_values(t, host["max_abs"], host["exceed"], P)
+        res = dict(t=t, p_uncorrected=p_unc, p_fwer=p_fwer, max_abs=host["max_abs"], n_permutations=P)
+        if self.threshold is not None:
+            label, size, area = host["label"], host["size"], self.cohort.vertex_areas()
+            extents = np.sort(host["max_extent"])
+            clusters = []
+            for lab in np.unique(label[label >= 0]):
+                members = np.nonzero(label == lab)[0]                          # ascending vertex index
+                extent = int(size[lab])
+                clusters.append(Cluster(int(lab), 1 if t[lab] > 0 else -1, extent, float(np.cumsum(area[members])[-1]),
+                                        float(P - np.searchsorted(extents, extent, side="left")) / float(P)))
+            res.update(cluster_threshold=float(self.threshold), cluster_label=label, max_extent=host["max_extent"], clusters=clusters)
+        if self.tfce is not None:
+            p_tfce_unc, p_tfce = _p_values(host["tfce"], host["max_tfce"], host["tfce_exceed"], P)
+            res.update(tfce=host["tfce"], max_tfce=host["max_tfce"], tfce_clipped=int(np.count_nonzero(host["tfce_clipped"])), tfce_settings=self.tfce,
+                       p_tfce_uncorrected=p_tfce_unc, p_tfce=p_tfce)
+        return res
 
 
 def _p_values(t: np.ndarray, max_abs: np.ndarray, exceed: np.ndarray, P: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -663,29 +679,18 @@ def _p_values(t: np.ndarray, max_abs: np.ndarray, exceed: np.ndarray, P: int) ->
     return p_unc, p_fwer
 
 
-def _set_clusters(res, cohort_like, t, P: int, cluster_threshold, max_extent, label, size) -> None:
-    """The cluster fields of a result, when the test ran with a threshold."""
-    if cluster_threshold is None:
-        return
-    area = cohort_like.vertex_areas()
-    res.cluster_threshold, res.cluster_label, res.max_extent = float(cluster_threshold), label, max_extent
-    extents = np.sort(max_extent)
-    for lab in np.unique(label[label >= 0]):
-        members = np.nonzero(label == lab)[0]                              # ascending vertex index
-        extent = int(size[lab])
-        res.clusters.append(Cluster(int(lab), 1 if t[lab] > 0 else -1, extent, float(np.cumsum(area[members])[-1]),
-                                    float(P - np.searchsorted(extents, extent, side="left")) / float(P)))
-
-
-def _finish(kind: str, cohort_like, perms: Permutations, host, n1, n2, mean_difference, cluster_threshold, tfce=None,
-            tfce_host=None) -> PermutationResult:
-    t, max_abs, exceed, max_extent, label, size = host[:6]
-    P = len(perms)
-    p_unc, p_fwer = _p_values(t, max_abs, exceed, P)
-    res = PermutationResult(kind, t, n1, n2, mean_difference, p_unc, p_fwer, max_abs, P, perms.exact)
-    _set_clusters(res, cohort_like, t, P, cluster_threshold, max_extent, label, size)
-    _set_tfce(res, tfce, tfce_host, P)
-    return res
+def _bit_tiles(cohort_like, values: torch.Tensor, mask: Optional[torch.Tensor], perms: Permutations, mode: int, cluster_threshold, tfce, batch):
+    """What ``two_sample_test`` and ``paired_test`` share: the ``_Batches`` of the labellings ``perms``, the prepared block of ``values``
+    and the function that makes a batch's t tile from them in one reused workspace."""
+    N, V = int(values.shape[0]), int(values.shape[1])
+    if perms.n_knees != N:
+        raise ValueError(f"the labellings are for {perms.n_knees} knees, the cohort has {N}")
+    dev = values.device
+    batches = _Batches(cohort_like, len(perms), V, dev, cluster_threshold, tfce, batch)
+    bits = torch.from_numpy(np.ascontiguousarray(perms.bits).view(np.int32)).to(dev)
+    prepared = ops.group_prepare(values, mask, centre=mode == ops.STATS_TWO_SAMPLE)
+    ws = _lib.workspace("oai_permutation_t", dev, batches.rows, V)
+    return batches, prepared, lambda p0, p1: ops.permutation_t(prepared, bits, p0, p1, mode, workspace=ws)
 
 
 def _permutations(perms, make, n_knees: int) -> Permutations:
@@ -718,14 +723,15 @@ def two_sample_test(cohort: ThicknessCohort, groups, n_permutations: int = 10000
     if not np.array_equal(perms.rows()[0], g):
         raise ValueError("row 0 of the permutations must be the observed labelling")
     values, mask = cohort.values, cohort.mask
-    sides = []
-    for member in (g, ~g):                                                 # the descriptive side: n and mean of either group, per vertex
+    sides = {}
+    for side, member in (("1", g), ("2", ~g)):                             # the descriptive side: n and mean of either group, per vertex
         idx = torch.from_numpy(np.nonzero(member)[0]).to(values.device)
         prep = ops.group_prepare(values.index_select(0, idx), mask.index_select(0, idx))
-        sides += [prep.n, prep.mean]
-    host, tfce_host = _run(cohort, values, mask, perms, ops.STATS_TWO_SAMPLE, cluster_threshold, batch, sides, tfce)
-    n1, mean1, n2, mean2 = host[6:10]
-    return _finish(cohort.kind, cohort, perms, host, n1, n2, mean1 - mean2, cluster_threshold, tfce, tfce_host)
+        sides.update({"n" + side: prep.n, "mean" + side: prep.mean})
+    batches, _, tile_of = _bit_tiles(cohort, values, mask, perms, ops.STATS_TWO_SAMPLE, cluster_threshold, tfce, batch)
+    host, shared = batches.run(tile_of, sides)
+    return PermutationResult(kind=cohort.kind, n1=host["n1"], n2=host["n2"], mean_difference=host["mean1"] - host["mean2"], exact=perms.exact,
+                             **shared)
 
 
 def paired_test(cohort_a: ThicknessCohort, cohort_b: ThicknessCohort, n_permutations: int = 10000, cluster_threshold: Optional[float] = None,
@@ -749,10 +755,9 @@ def paired_test(cohort_a: ThicknessCohort, cohort_b: ThicknessCohort, n_permutat
     perms = _permutations(permutations, lambda: sign_flips(N, n_permutations, seed), N)
     if perms.rows()[0].any():
         raise ValueError("row 0 of the permutations must flip nothing")
-    host, tfce_host = _run(cohort_a, diff, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, batch, lambda prepared: [prepared.n, prepared.mean],
-                           tfce)
-    n, mean = host[6:8]
-    return _finish(cohort_a.kind, cohort_a, perms, host, n, n.copy(), mean, cluster_threshold, tfce, tfce_host)
+    batches, prepared, tile_of = _bit_tiles(cohort_a, diff, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, tfce, batch)
+    host, shared = batches.run(tile_of, {"n": prepared.n, "mean": prepared.mean})
+    return PermutationResult(kind=cohort_a.kind, n1=host["n"], n2=host["n"].copy(), mean_difference=host["mean"], exact=perms.exact, **shared)
 
 
 # ---- regression ------------------------------------------------------------------------------------------------------------------------
@@ -775,10 +780,7 @@ def index_permutations(n_knees: int, n_permutations: int, seed: int = 0, blocks=
     N, P = int(n_knees), int(n_permutations)
     if N < 1 or P < 1:
         raise ValueError(f"n_knees and n_permutations must be >= 1, got {n_knees}, {n_permutations}")
-    b = np.zeros(N, np.int64) if blocks is None else np.asarray(blocks)
-    if b.shape != (N,):
-        raise ValueError(f"blocks must hold one label per knee ({N}), got shape {b.shape}")
-    members = [np.nonzero(b == lab)[0] for lab in np.unique(b)]
+    members = _block_members(blocks, N)
     total = 1
     for idx in members:
         total *= math.factorial(len(idx)) if total <= P else 1             # stop multiplying once it is beyond P
@@ -798,7 +800,7 @@ def index_permutations(n_knees: int, n_permutations: int, seed: int = 0, blocks=
 
 
 @dataclass
-class RegressionResult:
+class RegressionResult(_SurfaceResult):
     """``t`` float64 [V]: the t of the regressor's coefficient (NaN where no t exists: too few knees with a value, a design that loses its
     rank among them, no residual variance); ``n`` the knees with a value and ``dof`` = n - p per vertex; ``slope`` in mm per unit of ``x``;
     ``partial_r`` = t / sqrt(t^2 + dof), the partial correlation of thickness and x given the covariates; the p-values, ``max_abs`` and the
@@ -814,36 +816,20 @@ class RegressionResult:
     max_abs: np.ndarray
     n_permutations: int
     exact: bool
-    cluster_threshold: Optional[float] = None
-    cluster_label: Optional[np.ndarray] = None
-    clusters: List[Cluster] = field(default_factory=list)
-    max_extent: Optional[np.ndarray] = None
-    tfce: Optional[np.ndarray] = None
-    p_tfce: Optional[np.ndarray] = None
-    p_tfce_uncorrected: Optional[np.ndarray] = None
-    max_tfce: Optional[np.ndarray] = None
-    tfce_clipped: int = 0
-    tfce_settings: Optional["TFCE"] = None
 
-    def image(self, atlas, what: str = "t"):
-        """``atlas.image`` of "t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce" or "p_tfce" (float32 [H, W])."""
-        if what not in ("t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce", "p_tfce"):
-            raise ValueError(f"no image of {what!r}")
-        vec = getattr(self, what)
-        if vec is None:
-            raise ValueError("the test ran without tfce" if "tfce" in what else "the test ran without a cluster threshold")
-        return atlas.image(np.asarray(vec, np.float32), self.kind)
+    IMAGES = ("t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce", "p_tfce")
+
+
+def _table_bytes(n_knees: int, n_columns: int) -> int:
+    """Per index row, the permuted design table of ``oai_regression_t``: 8 (p + p (p + 1) / 2) bytes per knee."""
+    p = int(n_columns)
+    return int(n_knees) * 8 * (p + p * (p + 1) // 2)
 
 
 def regression_batch(n_verts: int, n_knees: int, n_columns: int, n_permutations: int, clusters: bool, budget: int = WORKSPACE_BUDGET,
                      tfce: bool = False) -> int:
-    """Index rows per batch of ``regression_test``: what fits ``budget`` bytes of its own workspace -- per row 8 bytes per vertex of t tile,
-    8 more of labels and sizes with clusters, 24 more of TFCE tile and union-find with ``tfce``, and 8 (p + p (p + 1) / 2) bytes per knee of
-    permuted design table -- rounded down to sixteen rows (a multiple of every rows-per-thread of the t kernel), at least sixteen."""
-    p = int(n_columns)
-    per_row = int(n_verts) * ((16 if clusters else 8) + (_TFCE_BYTES if tfce else 0)) + int(n_knees) * 8 * (p + p * (p + 1) // 2)
-    rows = budget // per_row
-    return int(min(max(rows // _ROW_GROUP * _ROW_GROUP, _ROW_GROUP), max(int(n_permutations), 1)))
+    """Index rows per batch of ``regression_test``: ``_batch_rows`` with the row's ``_table_bytes`` of permuted design table."""
+    return _batch_rows(n_verts, n_permutations, clusters, tfce, budget, _table_bytes(n_knees, n_columns))
 
 
 def _design_columns(x, covariates, intercept: bool, n_knees: int) -> Tuple[np.ndarray, np.ndarray, float]:
@@ -912,45 +898,16 @@ def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool
     P, p = len(perms), design.shape[1]
     values, mask = cohort.values, cohort.mask
     V, dev = int(values.shape[1]), values.device
-    graph = None
-    if cluster_threshold is not None:
-        if not float(cluster_threshold) > 0.0:
-            raise ValueError(f"cluster_threshold must be > 0, got {cluster_threshold!r}")
-        graph = cohort.surface_graph()
-    rows = regression_batch(V, N, p, P, graph is not None, tfce=tfce is not None) if batch is None else int(batch)
-    if rows < 1:
-        raise ValueError(f"batch must be >= 1, got {batch}")
-    with torch.cuda.device(dev):
-        enhance = _Tfce(tfce, cohort, P, V, rows, dev) if tfce is not None else None
-        index = torch.from_numpy(perms.index).to(dev)
-        design_d = torch.from_numpy(design).to(dev)
-        prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
-        t0 = torch.empty(V, dtype=torch.float64, device=dev)
-        slope0 = torch.empty(V, dtype=torch.float64, device=dev)
-        max_abs = torch.empty(P, dtype=torch.float64, device=dev)
-        exceed = torch.empty(V, dtype=torch.int64, device=dev)
-        max_extent = torch.empty(P, dtype=torch.int32, device=dev) if graph is not None else None
-        label = size = None
-        ws = _lib.workspace("oai_regression_t", dev, min(rows, P), V, N, p)
-        for p0 in range(0, P, rows):
-            p1 = min(p0 + rows, P)
-            tile = ops.regression_t(prepared, design_d, index, p0, p1, workspace=ws, slope0=slope0 if p0 == 0 else None)
-            ops.permutation_reduce(tile, p0, t0, max_abs, exceed)
-            if graph is not None:
-                got = ops.graph_clusters(tile, graph[0], graph[1], float(cluster_threshold), max_extent=max_extent[p0:p1], return_labels=p0 == 0)
-                if p0 == 0:
-                    _, label, size = got
-            if enhance is not None:
-                enhance.batch(tile, p0, p1)
-        host = _download([t0, max_abs, exceed, slope0, prepared.n] + ([max_extent, label, size] if graph is not None else [])
-                         + (enhance.tensors() if enhance is not None else []))
-    t, max_abs, exceed, slope, n = host[:5]
-    max_extent, label, size = host[5:8] if graph is not None else (None, None, None)
+    batches = _Batches(cohort, P, V, dev, cluster_threshold, tfce, batch, _table_bytes(N, p))
+    index = torch.from_numpy(perms.index).to(dev)
+    design_d = torch.from_numpy(design).to(dev)
+    prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
+    slope0 = torch.empty(V, dtype=torch.float64, device=dev)
+    ws = _lib.workspace("oai_regression_t", dev, batches.rows, V, N, p)
+    host, shared = batches.run(lambda p0, p1: ops.regression_t(prepared, design_d, index, p0, p1, workspace=ws, slope0=slope0 if p0 == 0 else None),
+                               {"slope": slope0, "n": prepared.n})
+    t, n = host["t"], host["n"]
     dof = n.astype(np.int64) - p
     with np.errstate(invalid="ignore", divide="ignore"):
         partial_r = t / np.sqrt(t * t + dof.astype(np.float64))
-    p_unc, p_fwer = _p_values(t, max_abs, exceed, P)
-    res = RegressionResult(cohort.kind, t, n, dof, slope / scale, partial_r, p_unc, p_fwer, max_abs, P, perms.exact)
-    _set_clusters(res, cohort, t, P, cluster_threshold, max_extent, label, size)
-    _set_tfce(res, tfce, host[-4:] if tfce is not None else None, P)
-    return res
+    return RegressionResult(kind=cohort.kind, n=n, dof=dof, slope=host["slope"] / scale, partial_r=partial_r, exact=perms.exact, **shared)

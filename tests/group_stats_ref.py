@@ -96,14 +96,18 @@ def reduce_tiles(t):
 
 
 def clusters(values, offsets, neighbours, t0):
-    """(label int32 [R, V], size int32 [R, V], max_extent int32 [R])."""
+    """(label int32 [R, V], size int32 [R, V], max_extent int32 [R]).  The CSR adjacency is read as the header states it: an offset outside
+    [0, len(neighbours)] is clamped, a neighbour outside [0, V) or equal to its owner is ignored."""
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
     values = np.atleast_2d(np.asarray(values, np.float64))
     R, V = values.shape
     offsets, neighbours = np.asarray(offsets, np.int64), np.asarray(neighbours, np.int64)
-    src = np.repeat(np.arange(V), np.diff(offsets))
-    dst = neighbours[:offsets[-1]]
+    lo, hi = np.clip(offsets[:-1], 0, len(neighbours)), np.clip(offsets[1:], 0, len(neighbours))
+    src = np.repeat(np.arange(V), np.maximum(hi - lo, 0))
+    dst = np.concatenate([neighbours[a:b] for a, b in zip(lo, hi)] + [np.zeros(0, np.int64)])
+    ok = (dst >= 0) & (dst < V) & (dst != src)
+    src, dst = src[ok], dst[ok]
     label, size, extent = np.full((R, V), -1, np.int32), np.zeros((R, V), np.int32), np.zeros(R, np.int32)
     for r in range(R):
         with np.errstate(invalid="ignore"):
@@ -121,3 +125,22 @@ def clusters(values, offsets, neighbours, t0):
         size[r, inside] = counts[comp[inside]]
         extent[r] = counts.max()
     return label, size, extent
+
+
+def hostile_graph(V=40):
+    """(offsets int32 [V + 1], neighbours int32) of a symmetric random graph on the vertices 1 .. V - 2 that is then bent in every way the
+    header allows for: offsets[0] below 0 and offsets[V] beyond the neighbour count (vertices 0 and V - 1 have no neighbour: after the
+    clamp their ranges are empty), and among the neighbours of vertex 5 a negative index, V itself, V + 1 and vertex 5.  What is left
+    after the clamp is the symmetric graph."""
+    rng = np.random.default_rng(V)
+    lists = [[] for _ in range(V)]
+    for a, b in rng.integers(1, V - 1, (3 * V // 2, 2)).tolist():
+        if a != b and b not in lists[a]:
+            lists[a].append(b)
+            lists[b].append(a)
+    lists[5] = [-1] + lists[5][:1] + [V, 5] + lists[5][1:] + [V + 1]
+    off = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
+    nbr = np.asarray([u for x in lists for u in x], np.int32)
+    assert not lists[0] and not lists[V - 1] and len(lists[5]) > 4
+    off[0], off[V] = -3, off[V] + 5
+    return off, nbr

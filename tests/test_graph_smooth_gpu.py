@@ -54,6 +54,10 @@ def _graph(name):
         off, nbr = sref.from_lists(lists)
         off[-1] += 5
         return off, nbr
+    if name == "hostile_40":                          # odd_40's faults and a first offset below 0: the graph that the cluster and TFCE tests use
+        off, nbr = gref.hostile_graph()
+        assert off[0] < 0 and off[-1] > len(nbr) and (nbr < 0).any() and (nbr >= len(off) - 1).any() and 5 in nbr[off[5]:off[6]]
+        return off, nbr
     verts, faces = _sphere()
     off_d, nbr_d = mp.vertex_adjacency_device(len(verts), torch.from_numpy(faces).cuda())
     return off_d.cpu().numpy(), nbr_d.cpu().numpy()
@@ -83,7 +87,7 @@ def _case(graph, R):
 
 
 @pytest.mark.parametrize("R", [1, 5, 17, 33])
-@pytest.mark.parametrize("graph", ["path_3000", "star_700", "odd_40", "icosphere"])
+@pytest.mark.parametrize("graph", ["path_3000", "star_700", "odd_40", "hostile_40", "icosphere"])
 def test_smoothing_equals_the_restatement_to_the_bit(graph, R):
     from oai_analysis_2_amd import ops
     off, nbr = _graph(graph)

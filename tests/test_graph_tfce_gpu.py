@@ -149,6 +149,27 @@ def test_tfce_equals_the_restatement_to_the_bit(graph, weighted):
     _same_bits(out, _reference(graph, weighted, 1.0, 2.0)[0], "out")
 
 
+def test_a_hostile_graph_is_read_as_the_restatement_reads_it():
+    """Offsets below 0 and beyond the neighbour count, neighbours below 0 and at or above V, a vertex among its own neighbours: the kernel
+    clamps the first and ignores the others, as csrc/csr_graph.h states once for every graph kernel."""
+    from oai_analysis_2_amd import ops
+    off, nbr = gref.hostile_graph()
+    V = len(off) - 1
+    assert off[0] < 0 and off[V] > len(nbr) and (nbr < 0).any() and (nbr >= V).any() and 5 in nbr[off[5]:off[6]]
+    tile = np.random.default_rng(5).normal(0.0, 2.0, (6, V))
+    tile[0, 7], tile[1, :] = np.nan, np.abs(tile[1])                       # row 1: one side, so what is connected is one component
+    w = _weights(V)
+    off_d, nbr_d, tile_d = torch.from_numpy(off).cuda(), torch.from_numpy(nbr).cuda(), torch.from_numpy(tile).cuda()
+    for E, H in MODES:
+        for weights in (None, w):
+            kwargs = dict(dh=DH, E=E, H=H, unit=UNIT if weights is not None else 1.0, max_steps=STEPS)
+            want, want_clipped = tref.tfce(tile, off, nbr, weights=weights, **kwargs)
+            got, clipped = ops.graph_tfce(tile_d, off_d, nbr_d, weights=None if weights is None else torch.from_numpy(weights.copy()).cuda(), **kwargs)
+            _same_bits(got, want, f"hostile E={E} H={H} tfce")
+            _same_bits(clipped, want_clipped, "hostile clipped")
+    assert len(np.unique(want[1])) > 3                                     # more than one component and an isolated vertex
+
+
 @pytest.mark.parametrize("V", [1, 65])
 def test_one_row_of_one_and_of_sixty_five_vertices(V):
     from oai_analysis_2_amd import ops
@@ -260,6 +281,18 @@ def _check_against(res, t_ref, P, what, **ref_kwargs):
     return want
 
 
+def _same_result(got, want, what):
+    """Every field of two results of the same test: arrays to the bit, everything else (the ``clusters`` list among it) equal."""
+    import dataclasses
+    assert type(got) is type(want)
+    for f in dataclasses.fields(want):
+        a, b = getattr(got, f.name), getattr(want, f.name)
+        if isinstance(b, np.ndarray):
+            _same_bits(a, b, f"{what}: {f.name}")
+        else:
+            assert a == b, f"{what}: {f.name}"
+
+
 def test_two_sample_tfce_finds_the_weak_cap_that_max_t_misses():
     from oai_analysis_2_amd import stats
     Y, groups, cap = _painted(0.10)
@@ -295,6 +328,11 @@ def test_two_sample_tfce_finds_the_weak_cap_that_max_t_misses():
     for name in TFCE_FIELDS:
         _same_bits(getattr(both, name), getattr(res, name), name + " (with clusters)")
     assert res.image(SimpleNamespace(image=lambda vec, kind: vec), "p_tfce").dtype == np.float32
+    # the batches are one loop for every option: several batches with a ragged last one, and the default batch, give the bits of ``both``
+    assert both.clusters and both.tfce is not None and both.max_extent is not None
+    for batch, what in ((16, "batch 16"), (None, "default batch")):
+        _same_result(stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings, batch=batch, cluster_threshold=2.5),
+                     both, what)
 
 
 def test_extent_as_area_sums_integer_areas():
@@ -327,6 +365,13 @@ def test_paired_test_with_tfce_finds_the_cap():
     t_ref = gref.permutation_t(gref.prepare(diff, None, centre=False), None, stats.sign_flips(N_E2E, P_SMALL, seed=3).rows(), gref.ONE_SAMPLE)
     _same_bits(res.t, t_ref[0], "t")
     _check_against(res, t_ref, P_SMALL, "paired", dh=0.1, E=1.0, H=2.0, weights=_area_weights(atlas), unit=UNIT)
+    # clusters and tfce together: batch 16 (a ragged last batch of 4) gives the bits of batch 32
+    both = [stats.paired_test(_cohort(atlas, follow), _cohort(atlas, Y), n_permutations=P_SMALL, seed=3, batch=batch, tfce=True, cluster_threshold=2.5)
+            for batch in (32, 16)]
+    assert both[0].max_extent is not None and both[0].cluster_label is not None
+    _same_result(both[1], both[0], "paired, batch 16 against batch 32")
+    for name in TFCE_FIELDS:
+        _same_bits(getattr(both[0], name), getattr(res, name), name + " (with clusters)")
 
 
 def test_regression_test_with_tfce_finds_the_cap():
@@ -352,6 +397,13 @@ def test_regression_test_with_tfce_finds_the_cap():
     for name in ("t", "n", "dof", "slope", "partial_r", "p_uncorrected", "p_fwer", "max_abs"):
         _same_bits(getattr(res, name), getattr(plain, name), name + " (with and without tfce)")
     assert plain.tfce is None and plain.tfce_settings is None
+    # clusters and tfce together: batch 16 (a ragged last batch of 4) gives the bits of batch 32
+    both = [stats.regression_test(_cohort(atlas, Y), x, covariates=age, n_permutations=P_SMALL, seed=5, batch=batch, tfce=True, cluster_threshold=2.5)
+            for batch in (32, 16)]
+    assert both[0].max_extent is not None and both[0].cluster_label is not None
+    _same_result(both[1], both[0], "regression, batch 16 against batch 32")
+    for name in TFCE_FIELDS:
+        _same_bits(getattr(both[0], name), getattr(res, name), name + " (with clusters)")
 
 
 def test_without_an_effect_the_tfce_p_is_the_rank_of_the_observed_maximum():

@@ -141,3 +141,47 @@ def test_a_result_hands_its_maps_to_the_atlas_image():
         res.image(Atlas(), "cluster_label")
     with pytest.raises(ValueError, match="no image"):
         res.image(Atlas(), "n1")
+
+
+def test_the_results_keep_their_field_names_and_defaults():
+    """``PermutationResult`` and ``RegressionResult`` share the cluster and TFCE fields through one base: the public names, their
+    defaults, the order of the fields that may be given by position, and the two refusals of ``image`` are what they were."""
+    import dataclasses
+    import numpy as np
+    from oai_analysis_2_amd import stats
+
+    shared = {"cluster_threshold": None, "cluster_label": None, "clusters": [], "max_extent": None, "tfce": None, "p_tfce": None,
+              "p_tfce_uncorrected": None, "max_tfce": None, "tfce_clipped": 0, "tfce_settings": None}
+    own = {stats.PermutationResult: ("kind", "t", "n1", "n2", "mean_difference", "p_uncorrected", "p_fwer", "max_abs", "n_permutations", "exact"),
+           stats.RegressionResult: ("kind", "t", "n", "dof", "slope", "partial_r", "p_uncorrected", "p_fwer", "max_abs", "n_permutations", "exact")}
+    images = {stats.PermutationResult: {"t", "p_fwer", "p_uncorrected", "mean_difference", "cluster_label", "tfce", "p_tfce"},
+              stats.RegressionResult: {"t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce", "p_tfce"}}
+
+    class Atlas:
+        def image(self, vector, kind):
+            return kind, vector
+
+    v = np.array([1.0, np.nan, -2.0])
+    for cls, names in own.items():
+        fields = {f.name: f for f in dataclasses.fields(cls)}
+        assert set(fields) == set(names) | set(shared), cls.__name__
+        assert [f.name for f in dataclasses.fields(cls) if f.name in names] == list(names)
+        for name in names:                                                 # the test's own fields: required
+            assert fields[name].default is dataclasses.MISSING and fields[name].default_factory is dataclasses.MISSING, name
+        by_position = cls(*([v] * (len(names) - 2)), 10, False)            # and positional, in this order
+        assert by_position.kind is v and by_position.n_permutations == 10 and by_position.exact is False
+        for name, default in shared.items():
+            assert getattr(by_position, name) == default, name
+        assert by_position.clusters is not cls(*([v] * (len(names) - 2)), 10, False).clusters       # a list of its own
+        by_keyword = cls(**{name: v for name in names}, **{name: 7 for name in shared})
+        assert all(getattr(by_keyword, name) == 7 for name in shared)
+        res = cls(**{name: v for name in names[1:]}, kind="FC")
+        for what in images[cls]:
+            if what in shared:
+                with pytest.raises(ValueError, match="the test ran without tfce" if "tfce" in what else "the test ran without a cluster threshold"):
+                    res.image(Atlas(), what)
+            else:
+                assert res.image(Atlas(), what)[0] == "FC"
+        for what in (set(names) | set(shared)) - images[cls]:
+            with pytest.raises(ValueError, match="no image"):
+                res.image(Atlas(), what)

@@ -206,6 +206,27 @@ def test_clusters_equal_the_restatement_to_the_element(graph):
         _same_bits(siz, size[r], f"size of row {r}")
 
 
+def test_clusters_read_a_hostile_graph_as_the_restatement_reads_it():
+    """Offsets below 0 and beyond the neighbour count, neighbours below 0 and at or above V, a vertex among its own neighbours: the kernel
+    clamps the first and ignores the others, as csrc/csr_graph.h states once for every graph kernel."""
+    from oai_analysis_2_amd import ops
+    off, nbr = gref.hostile_graph()
+    V = len(off) - 1
+    assert off[0] < 0 and off[V] > len(nbr) and (nbr < 0).any() and (nbr >= V).any() and 5 in nbr[off[5]:off[6]]
+    t0 = 1.0
+    tile = np.random.default_rng(5).normal(0.0, 2.0, (6, V))
+    tile[0, 7], tile[1, :] = np.nan, np.abs(tile[1]) + 2 * t0              # row 1: every vertex in the positive set
+    label, size, extent = gref.clusters(tile, off, nbr, t0)
+    assert 1 < extent[1] < V - 2 and size[1, 0] == 1 and size[1, V - 1] == 1 and len(np.unique(label[1])) > 3
+    off_d, nbr_d, tile_d = torch.from_numpy(off).cuda(), torch.from_numpy(nbr).cuda(), torch.from_numpy(tile).cuda()
+    _same_bits(ops.graph_clusters(tile_d, off_d, nbr_d, t0), extent, "max_extent")
+    for r in range(len(tile)):
+        e, lab, siz = ops.graph_clusters(tile_d[r:r + 1], off_d, nbr_d, t0, return_labels=True)
+        _same_bits(e, extent[r:r + 1], f"max_extent of row {r}")
+        _same_bits(lab, label[r], f"label of row {r}")
+        _same_bits(siz, size[r], f"size of row {r}")
+
+
 # ---- the public interface --------------------------------------------------------------------------------------------------------------
 def _sphere_atlas():
     from oai_analysis_2_amd import mesh_processing as mp
