@@ -1165,6 +1165,47 @@ int oai_regression_t(const void* prepared_dev, size_t prepared_bytes, const unsi
 
 
 /* ------------------------------------------------------------------------------------------
+ * Cohort F test (csrc/group_regression.hip, tests/group_f_ref.py): do SEVERAL design columns explain thickness jointly, vertex by
+ * vertex, adjusted for the columns before them -- a one-way ANOVA over a factor with k + 1 levels (k dummy columns), an interaction
+ * together with its main effect, a quadratic term with the linear one.  The design is D = [Z | X] with p = n_columns columns,
+ * 1 <= p <= 6, of which THE k = n_interest COLUMNS OF INTEREST COME LAST, 1 <= k <= p; the first q = p - k columns are nuisance, the
+ * intercept (if any) among them.  Everything that is not restated here is as in "Cohort regression": Freedman and Lane's permutation
+ * of the design rows against the residuals (Winkler et al. 2014, as recalled, NOT pinned to any implementation), the layouts, the
+ * clamping of an index outside [0, n_knees), row 0 the identity by convention, the limits on knees, vertices and rows, fp64 without
+ * contraction, no floating-point atomics, one accumulator per sum that starts at +0.0, EVERY SUM OVER KNEES IN ASCENDING KNEE INDEX:
+ * bit-reproducible.  Nothing synchronises or reads anything back.  The definitions are this library's own, pinned by the numpy
+ * restatement and, through it, scipy's one-way F and numpy's least squares.
+ *
+ * prepared_dev is the block of oai_regression_prepare called with n_nuisance = q = n_columns - n_interest, an entry point that is used
+ * as it is.  THE CALLER IS RESPONSIBLE FOR HAVING PREPARED WITH THE MATCHING q: the block does not record it and oai_regression_f
+ * cannot check it.  Its ok only guarantees n - (q + 1) >= 1, so oai_regression_f applies its own dof >= 1, as oai_regression_t does.
+ *
+ * oai_regression_f: rows [p0, p1) of perm_dev -> the F tile, float64 [p1 - p0][n_verts] at the start of workspace_dev (the workspace is
+ * laid out as oai_regression_t's: the tile, then the table, then the factors, and the size is the same).  F >= 0, so
+ * oai_permutation_reduce (max |.| and exceedance counts), oai_graph_clusters and oai_graph_tfce take the tile as it is.  Per (row,
+ * vertex):
+ *   M, b, L, z   as in oai_regression_t
+ *   rss = Q - sum_a z_a*z_a                        (from Q, s = s - z_a*z_a, a = 0 .. p-1 ascending)
+ *   ess = sum_{a=q}^{p-1} z_a*z_a                  (from +0.0, s = s + z_a*z_a, a ascending)
+ *   dof = n - p;  s2 = rss / (double)dof;  F = (ess / (double)k) / s2
+ *   valid iff ok[v] && every pivot of M accepted && dof >= 1 && s2 > 0, otherwise NaN
+ * ess is the extra sum of squares that the last k columns explain given the first q: L z = b orthogonalises the columns in their
+ * order.  With k = 1, F is the square of oai_regression_t's t up to rounding (z_p*z_p / s2 against (z_p / sqrt(s2))^2).
+ * With p0 = 0 and coef0_dev (float64 [k][n_verts]) not null, row 0 also writes the coefficients of the columns of interest there, entry
+ * a - q for column a, NaN where its F is NaN -- back substitution on the trailing block of L:
+ *   for a = p-1 down to q { s = z_a;  for j = a+1 .. p-1 ascending: s = s - L_ja*beta_j;  beta_a = s / L_aa }
+ * A later batch (p0 > 0) leaves coef0_dev alone.  mask_dev as given to oai_regression_prepare; null: every entry is valid, and the
+ * results are THE SAME BITS as with a mask of all ones.  The kernel is oai_regression_t's with another epilogue: same rows per thread,
+ * same gather and row-factor kernels, the same fma(G, m ? 1.0 : 0.0, M) for the stated add.
+ * ---------------------------------------------------------------------------------------- */
+/* 0 for a shape the entry point refuses; equal to oai_regression_t_workspace_bytes otherwise. */
+size_t oai_regression_f_workspace_bytes(long long n_rows, long long n_verts, long long n_knees, int n_columns);
+int oai_regression_f(const void* prepared_dev, size_t prepared_bytes, const unsigned char* mask_dev, const double* design_dev, const int* perm_dev,
+                     long long n_knees, long long n_verts, int n_columns, int n_interest, long long p0, long long p1, void* workspace_dev,
+                     size_t workspace_bytes, double* coef0_dev, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free cluster enhancement (csrc/graph_tfce.hip, tests/graph_tfce_ref.py): a t tile in, a tile of the same shape out in which
  * every vertex holds the integral, over all thresholds h at or below its |t|, of extent(h)^E * h^H -- extent(h) being the size of the
  * vertex' connected component of {|t| >= h} on the surface.  It takes the place of a hand-picked cluster threshold: the family-wise p

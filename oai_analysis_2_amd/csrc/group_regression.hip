@@ -3,6 +3,10 @@
 // null distribution under Freedman-Lane permutation of the design rows.
 //   oai_regression_prepare   per vertex: n, mean, the residuals r of the (centred) values on the nuisance columns Z, Q = sum r r, ok
 //   oai_regression_t         a batch of index rows -> one t per (row, vertex); row 0 also the slope beta
+//   oai_regression_f         ("Cohort F test"; tests/group_f_ref.py) the same batch -> one F of the LAST k design columns, tested jointly,
+//                            per (row, vertex); row 0 also their k coefficients.  The hot loop is the t kernel's: after L z = b the extra
+//                            sum of squares of the last k columns given those before them is the sum of their z_a^2, so F differs from t in
+//                            its epilogue alone (regression_rows<P, MASKED, FSTAT>), and k is a runtime argument of that epilogue.
 // The tile feeds oai_permutation_reduce and oai_graph_clusters (csrc/group_stats.hip) as it is.
 //
 // fp64 without contraction; the order IS the contract, as in csrc/group_stats.hip: every sum over knees runs in ascending knee index
@@ -25,9 +29,11 @@
 //         p            1     2     3     4     5     6
 //     R   masked      16     8     2     2     1     1         accumulators: 18 .. 40 doubles
 //     R   no mask     16    16     8     8     8     8         accumulators: 16 .. 48 doubles
-//     VGPRs / waves per SIMD from the compiler's kernel-resource remarks on the gfx950 build; scratch is 0 for all twelve instances:
-//         masked      94/5  126/4  67/7  91/5  75/6  92/5
-//         no mask     62/8  94/5   70/7  94/5  126/4 126/4
+//     VGPRs / waves per SIMD from the compiler's kernel-resource remarks on the gfx950 build; scratch is 0 for all 24 instances:
+//       t masked      94/5  126/4  67/7  91/5  76/6  94/5
+//       t no mask     62/8  94/5   70/7  94/5  126/4 128/4
+//       F masked      94/5  126/4  66/7  90/5  70/7  92/5      the F kernel takes the same R in every instance
+//       F no mask     62/8  94/5   78/6  94/5  126/4 128/4
 //     With a mask the R x E table doubles of a knee must all sit in SGPRs at once (scalar loads return out of order, so the wave waits
 //     for all of them before the first use) and nothing can be loaded ahead within the ~100 SGPRs: a knee's latency is hidden by other
 //     waves only.  R = 4 at p = 4 (158 VGPRs, 3 waves) took 6.39 ms for the shape below, R = 2 (5 waves) takes 4.91 ms; R = 2 against
@@ -242,13 +248,14 @@ __global__ void __launch_bounds__(64) row_factor_kernel(const double* __restrict
 
 // Block b of a one-dimensional grid is row group b % groups of vertex span b / groups (group_stats.hip says why).  Thread = one vertex
 // x R rows of the batch; a lane past V works on vertex V - 1 and stores nothing; a padded row is worked on and not stored.  Rows here are
-// relative to the batch.
-template <int P, bool MASKED>
-__global__ void __launch_bounds__(kT) regression_t_kernel(const double* __restrict__ res, const double* __restrict__ Qv, const int* __restrict__ nv,
-                                                          const unsigned char* __restrict__ okv, const unsigned char* __restrict__ mask,
-                                                          const double* __restrict__ table, const double* __restrict__ factor, long long N, long long V,
-                                                          long long rows, long long padded, unsigned groups, int first, double* __restrict__ tile,
-                                                          double* __restrict__ slope0) {
+// relative to the batch.  The body of both hot kernels: the accumulate loop, the factor and the forward solve are one text, and FSTAT
+// picks the epilogue -- the t of the last column (out0: its coefficient), or the F of the last k columns (out0: their k coefficients).
+template <int P, bool MASKED, bool FSTAT>
+__device__ __forceinline__ void regression_rows(const double* __restrict__ res, const double* __restrict__ Qv, const int* __restrict__ nv,
+                                                const unsigned char* __restrict__ okv, const unsigned char* __restrict__ mask,
+                                                const double* __restrict__ table, const double* __restrict__ factor, long long N, long long V,
+                                                long long rows, long long padded, unsigned groups, int first, int ki, double* __restrict__ tile,
+                                                double* __restrict__ out0) {
     constexpr int R = rows_per_thread(P, MASKED);
     constexpr int T = tri(P);
     constexpr int E = MASKED ? P + T : P;
@@ -313,32 +320,96 @@ __global__ void __launch_bounds__(kT) regression_t_kernel(const double* __restri
 #pragma unroll
         for (int a = 0; a < P; ++a) rss = rss - b[r][a] * b[r][a];
         const double s2 = rss / (double)dof;
-        const double t = b[r][P - 1] / sqrt(s2);
         const bool valid = ok && pass && s2 > 0.0;
-        tile[(r0 + r) * V + v] = valid ? t : (double)NAN;
-        if (first && slope0 && r0 + r == 0) slope0[v] = valid ? b[r][P - 1] / L[T - 1] : (double)NAN;
+        if (!FSTAT) {
+            const double t = b[r][P - 1] / sqrt(s2);
+            tile[(r0 + r) * V + v] = valid ? t : (double)NAN;
+            if (first && out0 && r0 + r == 0) out0[v] = valid ? b[r][P - 1] / L[T - 1] : (double)NAN;
+        } else {
+            const int q = P - ki;                                                 // the columns of interest are q .. P - 1
+            double ess = 0.0;
+#pragma unroll
+            for (int a = 0; a < P; ++a) ess = a >= q ? ess + b[r][a] * b[r][a] : ess;
+            const double F = (ess / (double)ki) / s2;
+            tile[(r0 + r) * V + v] = valid ? F : (double)NAN;
+            if (r == 0 && first && out0 && r0 == 0) {                             // L^T beta = z on the trailing block, from the last row up
+                double beta[P];
+#pragma unroll
+                for (int a = P - 1; a >= 0; --a) {
+                    if (a < q) continue;
+                    double s = b[r][a];
+#pragma unroll
+                    for (int j = a + 1; j < P; ++j) s = s - L[tri(j) + a] * beta[j];
+                    beta[a] = s / L[tri(a) + a];
+                    out0[(long long)(a - q) * V + v] = valid ? beta[a] : (double)NAN;
+                }
+            }
+        }
     }
 }
 
 template <int P, bool MASKED>
-int launch_t(const Prepared& in, const unsigned char* mask, const double* design, const int* perm, long long N, long long V, long long p0, long long p1,
-             const TWs& ws, double* slope0, hipStream_t st) {
+__global__ void __launch_bounds__(kT) regression_t_kernel(const double* __restrict__ res, const double* __restrict__ Qv, const int* __restrict__ nv,
+                                                          const unsigned char* __restrict__ okv, const unsigned char* __restrict__ mask,
+                                                          const double* __restrict__ table, const double* __restrict__ factor, long long N, long long V,
+                                                          long long rows, long long padded, unsigned groups, int first, double* __restrict__ tile,
+                                                          double* __restrict__ slope0) {
+    regression_rows<P, MASKED, false>(res, Qv, nv, okv, mask, table, factor, N, V, rows, padded, groups, first, 1, tile, slope0);
+}
+
+// k, 1 <= k <= P, is the caller's to guarantee: coef0 is [k][V] and entry a - (P - k) is column a's.  The four-wave hint keeps every
+// instance within the 128 VGPRs of its t twin: without it hipcc spreads the epilogue of <6, no mask> over 166 VGPRs (3 waves); with it
+// that instance takes 128 (4 waves) and no instance has scratch, so R stays as rows_per_thread gives it.
+template <int P, bool MASKED>
+__global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4)))
+regression_f_kernel(const double* __restrict__ res, const double* __restrict__ Qv, const int* __restrict__ nv, const unsigned char* __restrict__ okv,
+                    const unsigned char* __restrict__ mask, const double* __restrict__ table, const double* __restrict__ factor, long long N,
+                    long long V, long long rows, long long padded, unsigned groups, int first, int k, double* __restrict__ tile,
+                    double* __restrict__ coef0) {
+    regression_rows<P, MASKED, true>(res, Qv, nv, okv, mask, table, factor, N, V, rows, padded, groups, first, k, tile, coef0);
+}
+
+// the launches of a batch; k = 0: the t kernel (out0 = slope0), k >= 1: the F kernel of the last k columns (out0 = coef0)
+template <int P, bool MASKED>
+int launch(const char* name, const Prepared& in, const unsigned char* mask, const double* design, const int* perm, long long N, long long V,
+           long long p0, long long p1, const TWs& ws, int k, double* out0, hipStream_t st) {
     constexpr int R = rows_per_thread(P, MASKED);
     const long long rows = p1 - p0;
     const unsigned groups = cdiv(rows, R);
     const long long padded = (long long)groups * R;
     const long long blocks = (long long)cdiv(V, kT) * groups;
     OAI_CHECK_ARG(blocks < (1LL << 31) && padded * N < (1LL << 31) * kT,
-                  "oai_regression_t: %lld rows of %lld vertices and %lld knees are more than one launch takes: use smaller batches", rows, V, N);
+                  "%s: %lld rows of %lld vertices and %lld knees are more than one launch takes: use smaller batches", name, rows, V, N);
     gather_kernel<P, MASKED><<<cdiv(padded * N, kT), kT, 0, st>>>(design, perm, N, p0, rows, padded, ws.table);
     OAI_CHECK_LAUNCH();
     if (!MASKED) {
         row_factor_kernel<P><<<cdiv(padded, 64), 64, 0, st>>>(ws.table, N, padded, ws.factor);
         OAI_CHECK_LAUNCH();
     }
-    regression_t_kernel<P, MASKED><<<(unsigned)blocks, kT, 0, st>>>(in.R, in.Q, in.n, in.ok, mask, ws.table, ws.factor, N, V, rows, padded, groups,
-                                                                    p0 == 0 ? 1 : 0, ws.tile, slope0);
+    if (k == 0)
+        regression_t_kernel<P, MASKED><<<(unsigned)blocks, kT, 0, st>>>(in.R, in.Q, in.n, in.ok, mask, ws.table, ws.factor, N, V, rows, padded, groups,
+                                                                        p0 == 0 ? 1 : 0, ws.tile, out0);
+    else
+        regression_f_kernel<P, MASKED><<<(unsigned)blocks, kT, 0, st>>>(in.R, in.Q, in.n, in.ok, mask, ws.table, ws.factor, N, V, rows, padded, groups,
+                                                                        p0 == 0 ? 1 : 0, k, ws.tile, out0);
     OAI_CHECK_LAUNCH();
+    return OAI_OK;
+}
+
+// what oai_regression_t and oai_regression_f share once their own arguments are checked
+int run(const char* name, const void* prepared_dev, const unsigned char* mask_dev, const double* design_dev, const int* perm_dev, long long n_knees,
+        long long n_verts, int n_columns, long long p0, long long p1, void* workspace_dev, int k, double* out0, void* stream) {
+    const Prepared in(prepared_dev, n_knees, n_verts);
+    const TWs ws(workspace_dev, p1 - p0, n_verts, n_knees, n_columns);
+    const hipStream_t st = (hipStream_t)stream;
+    switch (n_columns) {
+#define OAI_CASE(P)                                                                                                                      \
+    case P:                                                                                                                              \
+        return mask_dev ? launch<P, true>(name, in, mask_dev, design_dev, perm_dev, n_knees, n_verts, p0, p1, ws, k, out0, st)           \
+                        : launch<P, false>(name, in, nullptr, design_dev, perm_dev, n_knees, n_verts, p0, p1, ws, k, out0, st);
+        OAI_CASE(1) OAI_CASE(2) OAI_CASE(3) OAI_CASE(4) OAI_CASE(5) OAI_CASE(6)
+#undef OAI_CASE
+    }
     return OAI_OK;
 }
 
@@ -385,18 +456,26 @@ int oai_regression_t(const void* prepared_dev, size_t prepared_bytes, const unsi
     OAI_CHECK_ARG(prepared_dev && design_dev && perm_dev && workspace_dev, "oai_regression_t: null pointer");
     OAI_CHECK_WORKSPACE("oai_regression_t (prepared block)", prepared_bytes, oai_regression_prepare_workspace_bytes(n_knees, n_verts));
     OAI_CHECK_WORKSPACE("oai_regression_t", workspace_bytes, oai_regression_t_workspace_bytes(p1 - p0, n_verts, n_knees, n_columns));
-    const Prepared in(prepared_dev, n_knees, n_verts);
-    const TWs ws(workspace_dev, p1 - p0, n_verts, n_knees, n_columns);
-    const hipStream_t st = (hipStream_t)stream;
-    switch (n_columns) {
-#define OAI_CASE(P)                                                                                                                      \
-    case P:                                                                                                                              \
-        return mask_dev ? launch_t<P, true>(in, mask_dev, design_dev, perm_dev, n_knees, n_verts, p0, p1, ws, slope0_dev, st)            \
-                        : launch_t<P, false>(in, nullptr, design_dev, perm_dev, n_knees, n_verts, p0, p1, ws, slope0_dev, st);
-        OAI_CASE(1) OAI_CASE(2) OAI_CASE(3) OAI_CASE(4) OAI_CASE(5) OAI_CASE(6)
-#undef OAI_CASE
-    }
-    return OAI_OK;
+    return run("oai_regression_t", prepared_dev, mask_dev, design_dev, perm_dev, n_knees, n_verts, n_columns, p0, p1, workspace_dev, 0, slope0_dev, stream);
+}
+
+size_t oai_regression_f_workspace_bytes(long long n_rows, long long n_verts, long long n_knees, int n_columns) {
+    return oai_regression_t_workspace_bytes(n_rows, n_verts, n_knees, n_columns);
+}
+
+int oai_regression_f(const void* prepared_dev, size_t prepared_bytes, const unsigned char* mask_dev, const double* design_dev, const int* perm_dev,
+                     long long n_knees, long long n_verts, int n_columns, int n_interest, long long p0, long long p1, void* workspace_dev,
+                     size_t workspace_bytes, double* coef0_dev, void* stream) {
+    OAI_CHECK_ARG(cohort_shape_ok(n_knees, n_verts), "oai_regression_f: needs 2 .. 2^24 knees and 1 .. 2^31-2 vertices (got %lld, %lld)", n_knees, n_verts);
+    OAI_CHECK_ARG(n_columns >= 1 && n_columns <= kMaxCols, "oai_regression_f: needs 1 .. 6 design columns, got %d", n_columns);
+    OAI_CHECK_ARG(n_interest >= 1 && n_interest <= n_columns, "oai_regression_f: needs 1 .. %d columns of interest (n_interest), got %d", n_columns,
+                  n_interest);
+    OAI_CHECK_ARG(p0 >= 0 && p1 > p0 && p1 - p0 <= kMaxRows, "oai_regression_f: rows [p0, p1) must hold 1 .. 2^20 rows from p0 >= 0 (got %lld, %lld)", p0, p1);
+    OAI_CHECK_ARG(prepared_dev && design_dev && perm_dev && workspace_dev, "oai_regression_f: null pointer");
+    OAI_CHECK_WORKSPACE("oai_regression_f (prepared block)", prepared_bytes, oai_regression_prepare_workspace_bytes(n_knees, n_verts));
+    OAI_CHECK_WORKSPACE("oai_regression_f", workspace_bytes, oai_regression_f_workspace_bytes(p1 - p0, n_verts, n_knees, n_columns));
+    return run("oai_regression_f", prepared_dev, mask_dev, design_dev, perm_dev, n_knees, n_verts, n_columns, p0, p1, workspace_dev, n_interest, coef0_dev,
+               stream);
 }
 
 }  // extern "C"

@@ -890,6 +890,24 @@ def regression_prepare(values: torch.Tensor, mask: Optional[torch.Tensor] = None
     return RegressionPrepared(block, N, V, q, bool(centre), mask, **parts)
 
 
+def _regression_batch(prepared: RegressionPrepared, design, perm, p0, p1, lo: int, hi: int, out0, out0_name: str, out0_shape):
+    """What ``regression_t`` and ``regression_f`` check alike: the design with ``lo`` .. ``hi`` columns, the index rows, the row range and
+    the optional float64 output of row 0.  Returns (design, perm, p0, p1, out0)."""
+    dev, N = prepared.block.device, prepared.n_knees
+    design = _design(design, "design", N, dev, lo, hi)
+    perm = _chk(perm, "perm", torch.int32)
+    if perm.dim() != 2 or perm.shape[1] != N or perm.device != dev:
+        raise ValueError(f"perm must be int32 [P, {N}] on {dev}, got {tuple(perm.shape)} on {perm.device}")
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 < p1 <= perm.shape[0]:
+        raise ValueError(f"rows [{p0}, {p1}) are not rows of the {perm.shape[0]} permutations")
+    if out0 is not None:
+        out0 = _chk(out0, out0_name, torch.float64)
+        if tuple(out0.shape) != tuple(out0_shape) or out0.device != dev:
+            raise ValueError(f"{out0_name} must be float64 {list(out0_shape)} on {dev}, got {tuple(out0.shape)} on {out0.device}")
+    return design, perm, p0, p1, out0
+
+
 def regression_t(prepared: RegressionPrepared, design: torch.Tensor, perm: torch.Tensor, p0: int, p1: int, workspace: Optional[torch.Tensor] = None,
                  slope0: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The t tile of rows [p0, p1) of ``perm`` (int32 [P,N] on the device: knee j of a row takes design row ``perm[row, j]``; row 0 the
@@ -897,20 +915,32 @@ def regression_t(prepared: RegressionPrepared, design: torch.Tensor, perm: torch
     exists.  ``slope0`` float64 [V]: with ``p0`` = 0, receives row 0's coefficient of that column.  ``workspace``: a uint8 device buffer of
     ``oai_regression_t_workspace_bytes`` (reused between batches) instead of a new one; the tile is its front.  Does not synchronise."""
     dev, N, V = prepared.block.device, prepared.n_knees, prepared.n_verts
-    design = _design(design, "design", N, dev, prepared.n_nuisance + 1, prepared.n_nuisance + 1)
-    p = int(design.shape[1])
-    perm = _chk(perm, "perm", torch.int32)
-    if perm.dim() != 2 or perm.shape[1] != N or perm.device != dev:
-        raise ValueError(f"perm must be int32 [P, {N}] on {dev}, got {tuple(perm.shape)} on {perm.device}")
-    p0, p1 = int(p0), int(p1)
-    if not 0 <= p0 < p1 <= perm.shape[0]:
-        raise ValueError(f"rows [{p0}, {p1}) are not rows of the {perm.shape[0]} permutations")
-    if slope0 is not None:
-        slope0 = _chk(slope0, "slope0", torch.float64)
-        if tuple(slope0.shape) != (V,) or slope0.device != dev:
-            raise ValueError(f"slope0 must be float64 [{V}] on {dev}, got {tuple(slope0.shape)} on {slope0.device}")
+    p = prepared.n_nuisance + 1
+    design, perm, p0, p1, slope0 = _regression_batch(prepared, design, perm, p0, p1, p, p, slope0, "slope0", (V,))
     need = int(_lib.load().oai_regression_t_workspace_bytes(p1 - p0, V, N, p))
     ws = _tile_workspace(workspace, need, dev)
     _lib.call("oai_regression_t", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p,
               p0, p1, ws.data_ptr(), ws.numel(), _ptr(slope0), _lib.STREAM, device=dev)
+    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+
+
+def regression_f(prepared: RegressionPrepared, design: torch.Tensor, perm: torch.Tensor, p0: int, p1: int, n_interest: int,
+                 workspace: Optional[torch.Tensor] = None, coef0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The F tile of rows [p0, p1) of ``perm`` (as in ``regression_t``): float64 [p1 - p0, V], the F of the LAST ``n_interest`` columns of
+    the float64 ``design`` [N,p], tested jointly given the columns before them (include/oai_hip.h, "Cohort F test"), NaN where no F
+    exists.  ``prepared`` must have been prepared with the first p - ``n_interest`` columns as its nuisance: p = the prepared q +
+    ``n_interest``.  ``coef0`` float64 [n_interest, V]: with ``p0`` = 0, receives row 0's coefficients of those columns.  ``workspace``: a
+    uint8 device buffer of ``oai_regression_f_workspace_bytes`` (reused between batches) instead of a new one; the tile is its front.
+    Does not synchronise."""
+    dev, N, V = prepared.block.device, prepared.n_knees, prepared.n_verts
+    k = int(n_interest)
+    if not 1 <= k <= MAX_DESIGN_COLUMNS - prepared.n_nuisance:
+        raise ValueError(f"n_interest must be 1 .. {MAX_DESIGN_COLUMNS - prepared.n_nuisance} beside the {prepared.n_nuisance} nuisance columns "
+                         f"of the prepared block, got {n_interest!r}")
+    p = prepared.n_nuisance + k
+    design, perm, p0, p1, coef0 = _regression_batch(prepared, design, perm, p0, p1, p, p, coef0, "coef0", (k, V))
+    need = int(_lib.load().oai_regression_f_workspace_bytes(p1 - p0, V, N, p))
+    ws = _tile_workspace(workspace, need, dev)
+    _lib.call("oai_regression_f", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p,
+              k, p0, p1, ws.data_ptr(), ws.numel(), _ptr(coef0), _lib.STREAM, device=dev)
     return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)

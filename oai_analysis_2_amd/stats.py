@@ -22,7 +22,14 @@ csrc/group_regression.hip; tests/group_regression_ref.py).
     res = regression_test(cohort, kl_grade, covariates=np.stack([age, sex], axis=1), n_permutations=10000, cluster_threshold=3.0)
     res.slope, res.partial_r, res.p_fwer
 
-``tfce=True`` (or a ``TFCE``) on any of the three adds threshold-free cluster enhancement (include/oai_hip.h, "Threshold-free cluster
+``f_test`` asks whether SEVERAL columns explain thickness jointly, and ``anova_test`` whether it differs across the levels of a factor (a
+one-way analysis of variance, or of covariance with ``covariates``): the F of the last k design columns under the same permutation
+scheme (include/oai_hip.h, "Cohort F test"; csrc/group_regression.hip; tests/group_f_ref.py).
+
+    res = anova_test(cohort, kl_grade, covariates=age, n_permutations=10000, tfce=True)
+    res.f, res.coefficients, res.group_mean, res.p_fwer
+
+``tfce=True`` (or a ``TFCE``) on any of the tests adds threshold-free cluster enhancement (include/oai_hip.h, "Threshold-free cluster
 enhancement"; csrc/graph_tfce.hip; tests/graph_tfce_ref.py): every labelling's t tile is integrated over all thresholds on the device and
 ``res.p_tfce`` is the family-wise p of the enhanced statistic -- sensitive to broad weak effects without a hand-picked threshold.
 
@@ -535,7 +542,8 @@ class _SurfaceResult:
     def image(self, atlas, what: str = "t"):
         """``atlas.image`` of one of the result's ``IMAGES`` (float32 [H, W], NaN off the surface) -- of a ``PermutationResult``: "t", "p_fwer",
         "p_uncorrected", "mean_difference", "cluster_label", "tfce" or "p_tfce"; of a ``RegressionResult``: "t", "slope", "partial_r",
-        "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce" or "p_tfce"."""
+        "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce" or "p_tfce"; of an ``FResult``: "f", "partial_eta2", "p_fwer",
+        "p_uncorrected", "n", "cluster_label", "tfce" or "p_tfce"."""
         if what not in self.IMAGES:
             raise ValueError(f"no image of {what!r}")
         vec = getattr(self, what)
@@ -911,3 +919,170 @@ def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool
     with np.errstate(invalid="ignore", divide="ignore"):
         partial_r = t / np.sqrt(t * t + dof.astype(np.float64))
     return RegressionResult(kind=cohort.kind, n=n, dof=dof, slope=host["slope"] / scale, partial_r=partial_r, exact=perms.exact, **shared)
+
+
+# ---- F tests ---------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class FResult(_SurfaceResult):
+    """``f`` float64 [V]: the F of the columns tested jointly, given the covariates (NaN where no F exists: too few knees with a value, a
+    design that loses its rank among them -- a level of the factor without a knee there --, no residual variance); ``n`` the knees with a
+    value, ``dof1`` = k, the number of columns tested, and ``dof2`` = n - p per vertex; ``coefficients`` float64 [k, V] in mm per unit of
+    the column as passed -- of ``anova_test``: the level's adjusted difference from the first level; ``partial_eta2`` = k f / (k f + dof2),
+    the share of the variance left by the covariates that the tested columns explain; ``p_uncorrected`` = share of permutations with an F
+    at least the observed at that vertex, ``p_fwer`` = share of permutations whose maximal F over the surface is at least the observed F
+    at that vertex (both NaN where f is); ``max_f`` the null distribution of the surface maximum, entry 0 observed.  ``levels`` (the sorted
+    labels), ``group_n`` int32 [G, V] and ``group_mean`` float64 [G, V] (the counted, unadjusted mean of each level's knees per vertex) are
+    filled by ``anova_test`` and None from ``f_test``.  The cluster and TFCE fields are as in ``PermutationResult``, with two differences that
+    follow from F >= 0: ``cluster_threshold`` is an F value and every cluster has sign +1; and TFCE is applied to the F tile AS IT IS.  F
+    scales like t squared, so the height exponent H = 1 on F weighs height roughly as H = 2 does on |t|, and ``TFCE.dh`` is a step in units
+    of F; ``tfce_clipped`` counts the permutations with an F beyond ``max_steps * dh``.  Neither is adjusted behind the caller's back:
+    ``tfce=True`` means the same ``TFCE()`` as in the other tests."""
+    kind: str
+    f: np.ndarray
+    n: np.ndarray
+    dof1: int
+    dof2: np.ndarray
+    coefficients: np.ndarray
+    partial_eta2: np.ndarray
+    p_uncorrected: np.ndarray
+    p_fwer: np.ndarray
+    max_f: np.ndarray
+    n_permutations: int
+    exact: bool
+    levels: Optional[np.ndarray] = None
+    group_n: Optional[np.ndarray] = None
+    group_mean: Optional[np.ndarray] = None
+
+    IMAGES = ("f", "partial_eta2", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce", "p_tfce")
+
+
+def _design_matrix(X, covariates, intercept: bool, n_knees: int, names: Optional[Sequence[str]] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The multi-column form of ``_design_columns``: (nuisance [N, q], design [N, q + k] with the k columns of ``X`` last, the k scales
+    those columns were divided by); refuses what has no answer and names the column at fault (``names``: what the columns of ``X`` are
+    called; default "X column j")."""
+    X = np.asarray(X, np.float64)
+    X = X[:, None] if X.ndim == 1 else X
+    if X.ndim != 2 or X.shape[0] != n_knees or X.shape[1] < 1:
+        raise ValueError(f"X must be [{n_knees}] or [{n_knees}, k >= 1], got shape {X.shape}")
+    cov = np.zeros((n_knees, 0)) if covariates is None else np.asarray(covariates, np.float64)
+    cov = cov[:, None] if cov.ndim == 1 else cov
+    if cov.ndim != 2 or cov.shape[0] != n_knees:
+        raise ValueError(f"covariates must be [{n_knees}] or [{n_knees}, c], got shape {cov.shape}")
+    k = X.shape[1]
+    names = [f"X column {j}" for j in range(k)] if names is None else list(names)
+    p = cov.shape[1] + k + int(bool(intercept))
+    if p > ops.MAX_DESIGN_COLUMNS:
+        raise ValueError(f"the design has {p} columns ({'the intercept, ' if intercept else ''}{cov.shape[1]} covariates, {k} tested columns); at most "
+                         f"{ops.MAX_DESIGN_COLUMNS} are supported")
+    named = [(f"covariate {j}", cov[:, j]) for j in range(cov.shape[1])] + list(zip(names, X.T))
+    cols = []
+    for name, c in named:
+        if not np.isfinite(c).all():
+            raise ValueError(f"{name} holds a NaN or an infinity: the design must be finite for every knee")
+        if (c == c[0]).all():
+            raise ValueError(f"{name} is constant over the knees")
+        c = c - c.mean() if intercept else c.copy()
+        norm = float(np.sqrt((c * c).sum()))
+        if not norm > 0.0:
+            raise ValueError(f"{name} is constant over the knees")
+        cols.append((c, norm))
+    Z = ([np.ones(n_knees)] if intercept else []) + [c / s for c, s in cols[:cov.shape[1]]]
+    nuisance = np.stack(Z, axis=1) if Z else np.zeros((n_knees, 0))
+    design = np.ascontiguousarray(np.concatenate([nuisance] + [(c / s)[:, None] for c, s in cols[cov.shape[1]:]], axis=1))
+    unit = design / np.sqrt((design * design).sum(axis=0))[None, :]
+    every = (["the intercept"] if intercept else []) + [name for name, _ in named]
+    for j in range(p):                                                     # the first column that the ones before it already span
+        if n_knees < j + 1 or np.linalg.matrix_rank(unit[:, :j + 1]) < j + 1:
+            raise ValueError(f"the design does not have full column rank over the knees: {every[j]} is a combination of the columns before it")
+    return np.ascontiguousarray(nuisance), design, np.asarray([s for _, s in cols[cov.shape[1]:]], np.float64)
+
+
+def _f_run(cohort: ThicknessCohort, what: str, X, names, covariates, intercept: bool, n_permutations: int, cluster_threshold, seed: int, blocks,
+           permutations, batch, tfce, groups: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> FResult:
+    """What ``f_test`` and ``anova_test`` share.  ``groups``: (levels, the level index of every knee) -- then also the counted means."""
+    tfce = _tfce_settings(tfce)
+    N = len(cohort)
+    if N < 2:
+        raise ValueError(f"{what} needs at least two knees")
+    nuisance, design, scales = _design_matrix(X, covariates, bool(intercept), N, names)
+    perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
+    P, p, k = len(perms), design.shape[1], len(scales)
+    values, mask = cohort.values, cohort.mask
+    V, dev = int(values.shape[1]), values.device
+    batches = _Batches(cohort, P, V, dev, cluster_threshold, tfce, batch, _table_bytes(N, p))
+    index = torch.from_numpy(perms.index).to(dev)
+    design_d = torch.from_numpy(design).to(dev)
+    prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
+    coef0 = torch.empty((k, V), dtype=torch.float64, device=dev)
+    extras = {"coef": coef0, "n": prepared.n}
+    if groups is not None:
+        for g in range(len(groups[0])):                                    # the descriptive side: n and mean of every level, per vertex
+            idx = torch.from_numpy(np.nonzero(groups[1] == g)[0]).to(dev)
+            prep = ops.group_prepare(values.index_select(0, idx), mask.index_select(0, idx))
+            extras.update({f"n{g}": prep.n, f"mean{g}": prep.mean})
+    ws = _lib.workspace("oai_regression_f", dev, batches.rows, V, N, p)
+    host, shared = batches.run(lambda p0, p1: ops.regression_f(prepared, design_d, index, p0, p1, k, workspace=ws, coef0=coef0 if p0 == 0 else None),
+                               extras)
+    f, n = shared.pop("t"), host["n"]
+    dof2 = n.astype(np.int64) - p
+    with np.errstate(invalid="ignore", divide="ignore"):
+        partial_eta2 = (k * f) / (k * f + dof2.astype(np.float64))
+    described = {}
+    if groups is not None:
+        G = len(groups[0])
+        described = dict(levels=groups[0], group_n=np.stack([host[f"n{g}"] for g in range(G)]), group_mean=np.stack([host[f"mean{g}"] for g in range(G)]))
+    return FResult(kind=cohort.kind, f=f, n=n, dof1=k, dof2=dof2, coefficients=host["coef"] / scales[:, None], partial_eta2=partial_eta2,
+                   max_f=shared.pop("max_abs"), exact=perms.exact, **described, **shared)
+
+
+def f_test(cohort: ThicknessCohort, X, covariates=None, intercept: bool = True, n_permutations: int = 10000,
+           cluster_threshold: Optional[float] = None, seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None,
+           tfce=None) -> FResult:
+    """Do the columns of ``X`` ([N] or [N, k]: the dummies of a factor, an interaction with its main effect, a linear and a quadratic
+    term) explain thickness JOINTLY, vertex by vertex, adjusted for ``covariates`` ([N] or [N, c]) and, with ``intercept``, a constant?  Per
+    vertex the general linear model over the knees with a value there and the F of the k columns given the others (include/oai_hip.h,
+    "Cohort F test"; csrc/group_regression.hip; tests/group_f_ref.py); its null distribution comes from Freedman-Lane permutation with the
+    rows of ``index_permutations(N, n_permutations, seed, blocks)``, or of ``permutations``, as in ``regression_test``.  At most six design
+    columns in all.  The columns are centred (with an intercept) and scaled to unit length on the host, which changes neither F nor the
+    p-values; ``coefficients`` are given per unit of the columns that were passed.  Refused before anything is launched: a NaN or an
+    infinity, a constant column, more than six columns, a design without full column rank -- the message names the column.
+    ``cluster_threshold`` is an F value; ``batch`` as in ``regression_test``; ``tfce``: True or a ``TFCE``, applied to F as it is -- F scales
+    like t squared, so H = 1 on F weighs height roughly as H = 2 does on |t|, and ``dh`` and ``max_steps * dh`` are in units of F
+    (``FResult`` says more).  With k = 1, F is the square of ``regression_test``'s t and the p-values are those of its two-sided test."""
+    return _f_run(cohort, "f_test", X, None, covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce)
+
+
+def _anova_levels(groups, n_knees: int, n_covariates: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(the sorted labels, the level index of every knee); refuses what ``anova_test`` does."""
+    g = np.asarray(groups)
+    if g.shape != (n_knees,):
+        raise ValueError(f"groups must hold one label per knee of the cohort ({n_knees}), got shape {g.shape}")
+    if g.dtype.kind not in "iuf" or (g.dtype.kind == "f" and not (np.isfinite(g).all() and (g == np.rint(g)).all())):
+        raise ValueError(f"groups must be integer labels, got {g.dtype}" + (" with values that are not whole numbers" if g.dtype.kind == "f" else ""))
+    levels, where, count = np.unique(g.astype(np.int64), return_inverse=True, return_counts=True)
+    if len(levels) < 2:
+        raise ValueError(f"groups holds a single level ({int(levels[0])}): an analysis of variance needs at least two")
+    p = 1 + n_covariates + len(levels) - 1
+    if len(levels) > ops.MAX_DESIGN_COLUMNS or p > ops.MAX_DESIGN_COLUMNS:
+        raise ValueError(f"{len(levels)} levels and {n_covariates} covariates make a design of {p} columns (the intercept, the covariates, a dummy "
+                         f"for every level after the first); at most {ops.MAX_DESIGN_COLUMNS} are supported")
+    if count.min() < 2:
+        raise ValueError(f"level {int(levels[count.argmin()])} has {int(count.min())} knee: every level needs at least two")
+    return levels, where.reshape(-1)
+
+
+def anova_test(cohort: ThicknessCohort, groups, covariates=None, n_permutations: int = 10000, cluster_threshold: Optional[float] = None,
+               seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None, tfce=None) -> FResult:
+    """Does thickness differ ACROSS the levels of a factor (``groups``: an integer label per knee with 2 to 6 distinct levels -- KL grade,
+    site, treatment arm), vertex by vertex, adjusted for ``covariates``?  One-way analysis of (co)variance: the design is an intercept, the
+    covariates and a 0 / 1 dummy for every level after the smallest one, and the dummies are tested jointly as in ``f_test``, whose other
+    arguments these are.  The six-column limit holds: levels - 1 + covariates + 1 <= 6.  Every level needs at least two knees.
+    ``coefficients[j]`` is the adjusted difference of level ``levels[j + 1]`` from level ``levels[0]``; ``group_n`` and ``group_mean`` are the
+    counted, unadjusted figures of every level.  Which level is the first changes the coefficients and not F."""
+    N = len(cohort)
+    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
+    levels, where = _anova_levels(groups, N, n_cov)
+    dummies = np.stack([(where == g).astype(np.float64) for g in range(1, len(levels))], axis=1)
+    names = [f"the dummy of level {int(lab)}" for lab in levels[1:]]
+    return _f_run(cohort, "anova_test", dummies, names, covariates, True, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
+                  groups=(levels, where))
