@@ -54,10 +54,24 @@ struct Ws {
 int read_ints(int* host, std::initializer_list<const int*> dev, hipStream_t st);
 
 constexpr long long kMaxFaces = 1LL << 28;     // 6 half-edges and 3 flattened corners per face stay below 2^31 - 1 (and the 0x7f7f7f7f fill)
+// the sizes the mesh QC and morphometry entry points accept: 0 .. 2^31-2 vertices, 0 .. 2^28 faces
+static inline bool mesh_ok(long long n_verts, long long n_faces) { return n_verts >= 0 && n_verts < (1LL << 31) - 1 && n_faces >= 0 && n_faces <= kMaxFaces; }
+// the three corners of face f name vertices of the mesh
+__device__ __forceinline__ bool face_ok(const int* __restrict__ f, long long n_verts) {
+    return f[0] >= 0 && f[0] < n_verts && f[1] >= 0 && f[1] < n_verts && f[2] >= 0 && f[2] < n_verts;
+}
 
 // exclusive scan of int32 (csrc/mesh.hip): out[i] = sum in[0..i), in place allowed; scratch holds scan_scratch_bytes(n) bytes
 size_t scan_scratch_bytes(long long n);
 int exclusive_scan_i32(const int* in, int* out, long long n, int* scratch, hipStream_t st);
+
+// Bucket lists (csrc/mesh.hip): the members of n buckets stored bucket after bucket, bucket b's at list[start[b] .. start[b + 1]).
+// count and start hold n + 1 ints each (the last count stays 0, so that start[n] is the total); scratch holds
+// scan_scratch_bytes(n + 1) bytes.  bucket_clear, then a kernel that counts with atomicAdd(&count[b], k); bucket_starts scans the
+// counts into start and clears count again, which is then the fill cursor of the scatter kernel:
+// list[start[b] + atomicAdd(&count[b], k)].
+int bucket_clear(int* count, long long n, hipStream_t st);
+int bucket_starts(int* count, int* start, long long n, int* scratch, hipStream_t st);
 
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 

@@ -10,6 +10,7 @@
 //
 // All three are HBM / VALU streaming kernels; nothing here is GEMM-shaped.
 #include "common.h"
+#include "uniform_grid.h"
 
 #include <mutex>
 #include <vector>
@@ -439,25 +440,16 @@ __global__ void __launch_bounds__(256) point_distance_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------
 // the same distance with a uniform-grid broad phase: triangles are binned into the cells their bounding boxes overlap
 // (count -> prefix sum -> fill), a point walks the cells around it ring by ring and stops when the best distance found is
-// within the radius already covered, less a slack for the float32 cell arithmetic (kRingSlack).  Same closest-point routine as the
+// within the radius already covered, less a slack for the cell arithmetic (kRingSlack).  Same closest-point routine as the
 // brute-force kernel, and every triangle that could be the nearest is visited: the two agree up to the rounding of their own
 // (separately inlined) arithmetic, provided every triangle lies inside the grid box the caller describes.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr float kRingSlack = 1.0f / 1024.0f;       // cells
 
-struct GridDesc {
-    float lo[3];
-    float inv_h, h;
-    int n[3];
-};
-
-__device__ __forceinline__ int cell_coord(float p, float lo, float inv_h, int n) {
-    const int c = (int)floorf((p - lo) * inv_h);
-    return c < 0 ? 0 : (c >= n ? n - 1 : c);
-}
+using oai::UniformGrid;
 
 template <bool FILL>
-__global__ void __launch_bounds__(256) grid_bin_kernel(const float* __restrict__ verts, const int* __restrict__ faces, long long nt, GridDesc g,
+__global__ void __launch_bounds__(256) grid_bin_kernel(const float* __restrict__ verts, const int* __restrict__ faces, long long nt, UniformGrid g,
                                                        int* __restrict__ cell_count /*FILL: running fill cursor*/, const int* __restrict__ cell_start,
                                                        int* __restrict__ tri_list) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -469,29 +461,28 @@ __global__ void __launch_bounds__(256) grid_bin_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float a = va[k], b = vb[k], c = vc[k];
-        lo[k] = cell_coord(fminf(a, fminf(b, c)), g.lo[k], g.inv_h, g.n[k]);
-        hi[k] = cell_coord(fmaxf(a, fmaxf(b, c)), g.lo[k], g.inv_h, g.n[k]);
+        lo[k] = oai::grid_cell(g, k, fminf(a, fminf(b, c)));
+        hi[k] = oai::grid_cell(g, k, fmaxf(a, fmaxf(b, c)));
     }
     // a thin triangle (is_thin) is listed as ~t, which is negative: the walk sets it aside for tri_dist2_thin without looking at it
     int entry = (int)t;
     if (FILL && is_thin(V3{vb[0] - va[0], vb[1] - va[1], vb[2] - va[2]}, V3{vc[0] - va[0], vc[1] - va[1], vc[2] - va[2]})) entry = ~entry;
-    for (int z = lo[2]; z <= hi[2]; ++z)
-        for (int y = lo[1]; y <= hi[1]; ++y)
-            for (int x = lo[0]; x <= hi[0]; ++x) {
-                const int cell = (z * g.n[1] + y) * g.n[0] + x;
-                const int slot = atomicAdd(&cell_count[cell], 1);
-                if (FILL) tri_list[cell_start[cell] + slot] = entry;
-            }
+    oai::grid_walk_box(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], [&](int x, int y, int z) {
+        const int cell = oai::grid_index(g, x, y, z);
+        const int slot = atomicAdd(&cell_count[cell], 1);
+        if (FILL) tri_list[cell_start[cell] + slot] = entry;
+    });
 }
 
 __global__ void __launch_bounds__(256) grid_distance_kernel(const float* __restrict__ pts, long long np, const float* __restrict__ verts,
-                                                            const int* __restrict__ faces, GridDesc g, const int* __restrict__ cell_start,
+                                                            const int* __restrict__ faces, UniformGrid g, const int* __restrict__ cell_start,
                                                             const int* __restrict__ tri_list, float* __restrict__ dist) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= np) return;
     const V3 p = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    const int cx = cell_coord(p.x, g.lo[0], g.inv_h, g.n[0]), cy = cell_coord(p.y, g.lo[1], g.inv_h, g.n[1]), cz = cell_coord(p.z, g.lo[2], g.inv_h, g.n[2]);
-    const int rmax = max(max(max(cx, g.n[0] - 1 - cx), max(cy, g.n[1] - 1 - cy)), max(cz, g.n[2] - 1 - cz));
+    const int cx = oai::grid_cell(g, 0, p.x), cy = oai::grid_cell(g, 1, p.y), cz = oai::grid_cell(g, 2, p.z);
+    const int rmax = oai::grid_rmax(g, cx, cy, cz);
+    const float h = (float)g.h;                     // exact: the entry point's cell size is a float
     float best = 3.4e38f;
     // Lanes of a wave visit different triangles, so a thin one (a negative list entry) handled where it is met would make the whole
     // wave step through the double path each time any lane meets one.  It waits in `pending` instead -- until the lane meets the next,
@@ -510,17 +501,15 @@ __global__ void __launch_bounds__(256) grid_distance_kernel(const float* __restr
     };
     for (int r = 0; r <= rmax; ++r) {
         flush();
-        // triangles not visited after ring r-1 lie in cells at Chebyshev distance >= r from the point's cell, AS cell_coord COMPUTES
-        // both: in float32, which can put a coordinate next to a cell boundary into the neighbouring cell.  The slip is below
-        // 3 * 2^-23 * 512 = 1.8e-4 cells per coordinate (the subtraction, 1 / h and the product each round once, on at most 512 cells),
-        // so such a triangle is at least (r - 1 - 2 * 1.8e-4) * h from the point's projection onto the grid box, hence from the point;
-        // kRingSlack = 2^-10 cells covers both slips with room to spare
-        const float covered = fmaxf((float)(r - 1) - kRingSlack, 0.0f) * g.h;
+        // triangles not visited after ring r-1 lie in cells at Chebyshev distance >= r from the point's cell, AS grid_cell COMPUTES
+        // both: in float64 with a rounded 1 / h, which can put a coordinate next to a cell boundary into the neighbouring cell.  The
+        // slip is below 3 * 2^-52 * 512 = 3.5e-13 cells per coordinate (the subtraction, 1 / h and the product each round once, on at
+        // most 512 cells), so such a triangle is at least (r - 1 - 2 * 3.5e-13) * h from the point's projection onto the grid box,
+        // hence from the point; kRingSlack = 2^-10 cells covers both slips, and the float32 rounding of `covered`, with room to spare
+        const float covered = fmaxf((float)(r - 1) - kRingSlack, 0.0f) * h;
         if (r > 0 && best <= covered * covered) break;
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, g.n[2] - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.n[1] - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, g.n[0] - 1);
-        auto visit = [&](int x, int y, int z) {
-            const int cell = (z * g.n[1] + y) * g.n[0] + x;
+        oai::grid_walk_shell(g, cx, cy, cz, r, [&](int x, int y, int z) {
+            const int cell = oai::grid_index(g, x, y, z);
             for (int k = cell_start[cell]; k < cell_start[cell + 1]; ++k) {
                 const int t = tri_list[k];
                 if (t < 0) { flush(); pending = ~t; continue; }
@@ -531,16 +520,7 @@ __global__ void __launch_bounds__(256) grid_distance_kernel(const float* __restr
                 const V3 A = {a[0], a[1], a[2]};
                 best = fminf(best, tri_dist2(p, A, V3{b[0], b[1], b[2]} - A, V3{c[0], c[1], c[2]} - A));
             }
-        };
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y) {
-                if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {      // a face of the ring's cube: the whole row
-                    for (int x = x0; x <= x1; ++x) visit(x, y, z);
-                } else {                                                             // otherwise only the two end cells are new
-                    if (cx - r >= 0) visit(cx - r, y, z);
-                    if (cx + r < g.n[0]) visit(cx + r, y, z);
-                }
-            }
+        });
     }
     flush();
     dist[i] = sqrtf(best);
@@ -572,9 +552,18 @@ size_t carve(McWs& w, const void* base, long long n) {
 
 }  // namespace
 
-namespace oai {     // the scan, for the other sources of the library (common.h)
+namespace oai {     // the scan and the bucket lists built on it, for every source of the library (common.h)
 size_t scan_scratch_bytes(long long n) { return scan_scratch_ints(n) * 4; }
 int exclusive_scan_i32(const int* in, int* out, long long n, int* scratch, hipStream_t st) { return exclusive_scan(in, out, n, scratch, st); }
+
+int bucket_clear(int* count, long long n, hipStream_t st) {
+    OAI_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)(n + 1) * 4, st));
+    return OAI_OK;
+}
+int bucket_starts(int* count, int* start, long long n, int* scratch, hipStream_t st) {
+    if (int rc = exclusive_scan(count, start, n + 1, scratch, st)) return rc;
+    return bucket_clear(count, n, st);
+}
 }  // namespace oai
 
 extern "C" {
@@ -675,19 +664,17 @@ int oai_mesh_point_distance_grid(const float* points_dev, long long n_points, co
     OAI_CHECK_WORKSPACE("oai_mesh_point_distance_grid", workspace_bytes, carve(w, workspace_dev, ncells, n_tris));
     if (n_points == 0) return OAI_OK;
     hipStream_t st = (hipStream_t)stream;
-    GridDesc g;
-    for (int k = 0; k < 3; ++k) { g.lo[k] = grid_lo_xyz[k]; g.n[k] = grid_dims_xyz[k]; }
-    g.h = cell_size; g.inv_h = 1.0f / cell_size;
-    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    const double lo[3] = {grid_lo_xyz[0], grid_lo_xyz[1], grid_lo_xyz[2]};          // widened exactly: the ABI stays float
+    const UniformGrid g = oai::make_uniform_grid(lo, (double)cell_size, grid_dims_xyz);
+    if (int rc = oai::bucket_clear(w.count, ncells, st)) return rc;
     grid_bin_kernel<false><<<oai::cdiv(n_tris, 256), 256, 0, st>>>(verts_dev, faces_dev, n_tris, g, w.count, nullptr, nullptr);
     OAI_CHECK_LAUNCH();
-    if (int rc = exclusive_scan(w.count, w.start, ncells + 1, w.scratch, st)) return rc;
+    if (int rc = oai::bucket_starts(w.count, w.start, ncells, w.scratch, st)) return rc;
     int total = 0;
     if (int rc = oai::read_ints(&total, {w.start + ncells}, st)) return rc;
     if ((long long)total > n_tris * 8)          // a triangle longer than a cell overlaps more than 8 cells: the caller's cell size is too small
         return oai::set_error(OAI_ERR_ARG, "oai_mesh_point_distance_grid: %d triangle-cell pairs > 8 per triangle; cell_size %g must be >= the longest edge",
                               total, (double)cell_size);
-    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
     grid_bin_kernel<true><<<oai::cdiv(n_tris, 256), 256, 0, st>>>(verts_dev, faces_dev, n_tris, g, w.count, w.start, w.list);
     OAI_CHECK_LAUNCH();
     grid_distance_kernel<<<oai::cdiv(n_points, 256), 256, 0, st>>>(points_dev, n_points, verts_dev, faces_dev, g, w.start, w.list, dist_dev);

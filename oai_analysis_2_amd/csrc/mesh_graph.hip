@@ -24,6 +24,7 @@ namespace {
 
 constexpr int kT = 256;
 using oai::kMaxFaces;
+using oai::face_ok;
 using oai::hook;
 using oai::load_agent;
 constexpr int kBatch = 4;                      // hook / jump rounds launched between two reads of the "changed" flags
@@ -42,12 +43,12 @@ __global__ void __launch_bounds__(kT) hook_kernel(const int* __restrict__ faces,
     const long long i = (long long)blockIdx.x * kT + threadIdx.x;
     bool ch = false;
     if (i < n_faces) {
-        const int a = faces[3 * i], b = faces[3 * i + 1], c = faces[3 * i + 2];
-        if (a < 0 || a >= n_verts || b < 0 || b >= n_verts || c < 0 || c >= n_verts) {
+        const int* f = faces + 3 * i;
+        if (!face_ok(f, n_verts)) {
             atomicOr(bad_index, 1);
         } else {
-            ch = hook(parent, a, b);                   // the host's edges f0-f1 and f1-f2
-            ch = hook(parent, b, c) || ch;
+            ch = hook(parent, f[0], f[1]);             // the host's edges f0-f1 and f1-f2
+            ch = hook(parent, f[1], f[2]) || ch;
         }
     }
     if (__ballot(ch) && (threadIdx.x & 63) == 0) *changed = 1;     // one store per wave
@@ -185,11 +186,9 @@ __global__ void __launch_bounds__(kT) degree_kernel(const int* __restrict__ face
                                                     int* __restrict__ bad_index) {
     const long long i = (long long)blockIdx.x * kT + threadIdx.x;
     if (i >= n_faces) return;
-    const int a = faces[3 * i], b = faces[3 * i + 1], c = faces[3 * i + 2];
-    if (a < 0 || a >= n_verts || b < 0 || b >= n_verts || c < 0 || c >= n_verts) { atomicOr(bad_index, 1); return; }
-    atomicAdd(deg + a, 2);
-    atomicAdd(deg + b, 2);
-    atomicAdd(deg + c, 2);
+    const int* f = faces + 3 * i;
+    if (!face_ok(f, n_verts)) { atomicOr(bad_index, 1); return; }
+    for (int k = 0; k < 3; ++k) atomicAdd(deg + f[k], 2);
 }
 
 __global__ void __launch_bounds__(kT) scatter_kernel(const int* __restrict__ faces, long long n_faces, long long n_verts, const int* __restrict__ start,
@@ -197,7 +196,7 @@ __global__ void __launch_bounds__(kT) scatter_kernel(const int* __restrict__ fac
     const long long i = (long long)blockIdx.x * kT + threadIdx.x;
     if (i >= n_faces) return;
     const int f[3] = {faces[3 * i], faces[3 * i + 1], faces[3 * i + 2]};
-    if (f[0] < 0 || f[0] >= n_verts || f[1] < 0 || f[1] >= n_verts || f[2] < 0 || f[2] >= n_verts) return;
+    if (!face_ok(f, n_verts)) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const long long p = (long long)start[f[k]] + atomicAdd(cursor + f[k], 2);
@@ -276,12 +275,12 @@ __global__ void __launch_bounds__(kT) compact_kernel(const int* __restrict__ sta
     for (int i = 0; i < u; ++i) dst[i] = src[i];
 }
 
-struct AdjWs { int *deg, *start, *cursor, *half, *ucount, *bad, *scratch; };
+struct AdjWs { int *deg, *start, *half, *ucount, *bad, *scratch; };
 size_t carve(AdjWs& w, const void* base, long long nv, long long nf) {
     oai::Ws ws(base);
     w.deg = ws.take<int>(nv + 1);
     w.start = ws.take<int>(nv + 1);
-    w.cursor = ws.take<int>(nv);
+    ws.take<int>(nv);                              // unused (deg is its own fill cursor): keeps oai_mesh_adjacency_workspace_bytes where it was
     w.half = ws.take<int>(nf * 6);
     w.ucount = ws.take<int>(nv + 1);
     w.bad = ws.take<int>(1);
@@ -349,9 +348,9 @@ __global__ void __launch_bounds__(kT) edge_kernel(const float* __restrict__ vert
     unsigned long long m = 0;
     bool bad = false;
     for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n_faces; i += (long long)gridDim.x * kT) {
-        const int a = faces[3 * i], b = faces[3 * i + 1], c = faces[3 * i + 2];
-        if (a < 0 || a >= n_verts || b < 0 || b >= n_verts || c < 0 || c >= n_verts) { bad = true; continue; }
-        const float *pa = verts + 3LL * a, *pb = verts + 3LL * b, *pc = verts + 3LL * c;
+        const int* f = faces + 3 * i;
+        if (!face_ok(f, n_verts)) { bad = true; continue; }
+        const float *pa = verts + 3LL * f[0], *pb = verts + 3LL * f[1], *pc = verts + 3LL * f[2];
         const double e = fmax(fmax(sq_edge(pa, pb), sq_edge(pb, pc)), sq_edge(pc, pa));
         m = max(m, (unsigned long long)__double_as_longlong(e));
     }
@@ -445,16 +444,15 @@ int oai_mesh_adjacency(const int* faces_dev, long long n_faces, long long n_vert
     AdjWs w;
     OAI_CHECK_WORKSPACE("oai_mesh_adjacency", workspace_bytes, carve(w, workspace_dev, n_verts, n_faces));
     hipStream_t st = (hipStream_t)stream;
-    OAI_CHECK_HIP(hipMemsetAsync(w.deg, 0, (size_t)(n_verts + 1) * 4, st));
-    OAI_CHECK_HIP(hipMemsetAsync(w.cursor, 0, (size_t)n_verts * 4, st));
+    if (int rc = oai::bucket_clear(w.deg, n_verts, st)) return rc;
     OAI_CHECK_HIP(hipMemsetAsync(w.bad, 0, sizeof(int), st));
     if (n_faces > 0) {
         degree_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, w.deg, w.bad);
         OAI_CHECK_LAUNCH();
     }
-    if (int rc = oai::exclusive_scan_i32(w.deg, w.start, n_verts + 1, w.scratch, st)) return rc;
+    if (int rc = oai::bucket_starts(w.deg, w.start, n_verts, w.scratch, st)) return rc;
     if (n_faces > 0) {
-        scatter_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, w.start, w.cursor, w.half);
+        scatter_kernel<<<oai::cdiv(n_faces, kT), kT, 0, st>>>(faces_dev, n_faces, n_verts, w.start, w.deg, w.half);
         OAI_CHECK_LAUNCH();
     }
     sort_unique_kernel<<<oai::cdiv(n_verts + 1, kT), kT, 0, st>>>(w.start, n_verts, w.half, w.ucount);

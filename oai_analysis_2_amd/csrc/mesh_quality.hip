@@ -18,6 +18,7 @@
 
 #include "hook_jump.h"
 #include "ordered_reduce.h"
+#include "uniform_grid.h"
 
 #pragma clang fp contract(off)
 
@@ -44,9 +45,6 @@ __device__ __forceinline__ void wave_count(u64* c, bool p) {
     if (p && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) atomicAdd(c, (u64)__popcll(b));
 }
 
-__device__ __forceinline__ bool face_ok(const int* __restrict__ f, long long n) {
-    return f[0] >= 0 && f[0] < n && f[1] >= 0 && f[1] < n && f[2] >= 0 && f[2] < n;
-}
 // 0: an index outside the mesh, 1: degenerate (two equal indices), 2: a triangle
 __device__ __forceinline__ int face_state(const int* __restrict__ f, long long n) {
     if (!face_ok(f, n)) return 0;
@@ -223,8 +221,6 @@ struct TopoWs {
     }
 };
 
-bool mesh_ok(long long n, long long m) { return n >= 0 && n < (1LL << 31) - 1 && m >= 0 && m <= kMaxFaces; }
-
 // ---- oai_mesh_geometry ---------------------------------------------------------------------------------------------------------------
 constexpr int kGA = 14;
 // sum area, sum det, min area, max area, min q, sum q, faces with q < q_min, faces | boundary length, interface length, min, max, sum edge length, edges
@@ -334,17 +330,10 @@ struct GeoWs {
 };
 
 // ---- oai_mesh_self_intersections -----------------------------------------------------------------------------------------------------
-struct SiGrid { double lo[3]; double h; int dims[3]; };
 enum { kPairs, kFlagged, kNeeded, kOverflow };
 
-// cell of a coordinate along axis k, clamped to the grid (a NaN lands in cell 0)
-__device__ __forceinline__ int cell_of(const SiGrid& g, int k, float x) {
-    const double t = floor(((double)x - g.lo[k]) / g.h);
-    return !(t >= 0.0) ? 0 : (t > (double)(g.dims[k] - 1) ? g.dims[k] - 1 : (int)t);
-}
-
 // one thread per face: the cells its bounding box spans (range[f] = lo xyz, hi xyz; hi < lo for a face with a bad index), and their number
-__global__ void __launch_bounds__(kT) si_range_kernel(const float* __restrict__ verts, long long nv, const int* __restrict__ faces, long long nf, SiGrid g,
+__global__ void __launch_bounds__(kT) si_range_kernel(const float* __restrict__ verts, long long nv, const int* __restrict__ faces, long long nf, UniformGrid g,
                                                       int* __restrict__ range, u64* __restrict__ cnt) {
     const long long f = (long long)blockIdx.x * kT + threadIdx.x;
     u64 cells = 0;
@@ -355,8 +344,8 @@ __global__ void __launch_bounds__(kT) si_range_kernel(const float* __restrict__ 
             const float *a = verts + 3 * (long long)c[0], *b = verts + 3 * (long long)c[1], *d = verts + 3 * (long long)c[2];
             cells = 1;
             for (int k = 0; k < 3; ++k) {
-                r[k] = cell_of(g, k, fminf(fminf(a[k], b[k]), d[k]));
-                r[3 + k] = max(r[k], cell_of(g, k, fmaxf(fmaxf(a[k], b[k]), d[k])));
+                r[k] = grid_cell(g, k, fminf(fminf(a[k], b[k]), d[k]));
+                r[3 + k] = max(r[k], grid_cell(g, k, fmaxf(fmaxf(a[k], b[k]), d[k])));
                 cells *= (u64)(r[3 + k] - r[k] + 1);
             }
         }
@@ -367,18 +356,16 @@ __global__ void __launch_bounds__(kT) si_range_kernel(const float* __restrict__ 
 }
 
 // count (cursor null) or scatter the (cell, face) entries; nothing when they would not fit
-__global__ void __launch_bounds__(kT) si_bin_kernel(const int* __restrict__ range, long long nf, SiGrid g, const u64* __restrict__ cnt, long long capacity,
+__global__ void __launch_bounds__(kT) si_bin_kernel(const int* __restrict__ range, long long nf, UniformGrid g, const u64* __restrict__ cnt, long long capacity,
                                                     int* __restrict__ count, const int* __restrict__ start, int* __restrict__ entries) {
     const long long f = (long long)blockIdx.x * kT + threadIdx.x;
     if (f >= nf || cnt[kNeeded] > (u64)capacity) return;
     const int* r = range + 6 * f;
-    for (int z = r[2]; z <= r[5]; ++z)
-        for (int y = r[1]; y <= r[4]; ++y)
-            for (int x = r[0]; x <= r[3]; ++x) {
-                const long long cell = ((long long)z * g.dims[1] + y) * g.dims[0] + x;
-                const int slot = atomicAdd(&count[cell], 1);
-                if (entries) entries[start[cell] + slot] = (int)f;
-            }
+    grid_walk_box(r[0], r[1], r[2], r[3], r[4], r[5], [&](int x, int y, int z) {
+        const int cell = grid_index(g, x, y, z);
+        const int slot = atomicAdd(&count[cell], 1);
+        if (entries) entries[start[cell] + slot] = (int)f;
+    });
 }
 
 // orient(a, b, c, d) = det(b - a, c - a, d - a)
@@ -395,7 +382,7 @@ __device__ __forceinline__ bool pierces(const double* p, const double* q, const 
 
 // one thread per face f: in each of its cells the faces g > f of the cell's list, tested only where the cell is the one that holds the
 // lower corner of the two cell ranges' intersection
-__global__ void __launch_bounds__(kT) si_pairs_kernel(const float* __restrict__ verts, const int* __restrict__ faces, long long nf, SiGrid g,
+__global__ void __launch_bounds__(kT) si_pairs_kernel(const float* __restrict__ verts, const int* __restrict__ faces, long long nf, UniformGrid g,
                                                       const int* __restrict__ range, const int* __restrict__ start, const int* __restrict__ entries,
                                                       long long capacity, unsigned char* __restrict__ flag, u64* __restrict__ cnt) {
     const long long f = (long long)blockIdx.x * kT + threadIdx.x;
@@ -411,37 +398,35 @@ __global__ void __launch_bounds__(kT) si_pairs_kernel(const float* __restrict__ 
             phi[k] = fmax(fmax(P[0][k], P[1][k]), P[2][k]);
         }
         bool mine = false;
-        for (int z = r[2]; z <= r[5]; ++z)
-            for (int y = r[1]; y <= r[4]; ++y)
-                for (int x = r[0]; x <= r[3]; ++x) {
-                    const long long cell = ((long long)z * g.dims[1] + y) * g.dims[0] + x;
-                    for (int t = start[cell], e = start[cell + 1]; t < e; ++t) {
-                        const int gf = entries[t];
-                        if (gf <= f) continue;
-                        const int* s = range + 6 * (long long)gf;
-                        if (max(r[0], s[0]) != x || max(r[1], s[1]) != y || max(r[2], s[2]) != z) continue;
-                        const int gi[3] = {faces[3 * (long long)gf], faces[3 * (long long)gf + 1], faces[3 * (long long)gf + 2]};
-                        bool shared = false;
-                        for (int i = 0; i < 3; ++i)
-                            for (int j = 0; j < 3; ++j) shared = shared || fi[i] == gi[j];
-                        if (shared) continue;
-                        double Q[3][3];
-                        for (int k = 0; k < 3; ++k) corner(verts, gi[k], Q[k]);
-                        bool apart = false;                        // disjoint boxes cannot pierce: skips the determinants, changes no answer
-                        for (int k = 0; k < 3; ++k) {
-                            const double qlo = fmin(fmin(Q[0][k], Q[1][k]), Q[2][k]), qhi = fmax(fmax(Q[0][k], Q[1][k]), Q[2][k]);
-                            apart = apart || qhi < plo[k] || phi[k] < qlo;
-                        }
-                        if (apart) continue;
-                        bool hit = false;
-                        for (int k = 0; k < 3 && !hit; ++k) hit = pierces(P[k], P[k == 2 ? 0 : k + 1], Q[0], Q[1], Q[2]);
-                        for (int k = 0; k < 3 && !hit; ++k) hit = pierces(Q[k], Q[k == 2 ? 0 : k + 1], P[0], P[1], P[2]);
-                        if (!hit) continue;
-                        ++pairs;
-                        mine = true;
-                        flag[gf] = 1;
-                    }
+        grid_walk_box(r[0], r[1], r[2], r[3], r[4], r[5], [&](int x, int y, int z) {
+            const int cell = grid_index(g, x, y, z);
+            for (int t = start[cell], e = start[cell + 1]; t < e; ++t) {
+                const int gf = entries[t];
+                if (gf <= f) continue;
+                const int* s = range + 6 * (long long)gf;
+                if (max(r[0], s[0]) != x || max(r[1], s[1]) != y || max(r[2], s[2]) != z) continue;
+                const int gi[3] = {faces[3 * (long long)gf], faces[3 * (long long)gf + 1], faces[3 * (long long)gf + 2]};
+                bool shared = false;
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 3; ++j) shared = shared || fi[i] == gi[j];
+                if (shared) continue;
+                double Q[3][3];
+                for (int k = 0; k < 3; ++k) corner(verts, gi[k], Q[k]);
+                bool apart = false;                        // disjoint boxes cannot pierce: skips the determinants, changes no answer
+                for (int k = 0; k < 3; ++k) {
+                    const double qlo = fmin(fmin(Q[0][k], Q[1][k]), Q[2][k]), qhi = fmax(fmax(Q[0][k], Q[1][k]), Q[2][k]);
+                    apart = apart || qhi < plo[k] || phi[k] < qlo;
                 }
+                if (apart) continue;
+                bool hit = false;
+                for (int k = 0; k < 3 && !hit; ++k) hit = pierces(P[k], P[k == 2 ? 0 : k + 1], Q[0], Q[1], Q[2]);
+                for (int k = 0; k < 3 && !hit; ++k) hit = pierces(Q[k], Q[k == 2 ? 0 : k + 1], P[0], P[1], P[2]);
+                if (!hit) continue;
+                ++pairs;
+                mine = true;
+                flag[gf] = 1;
+            }
+        });
         if (mine) flag[f] = 1;
     }
     for (int off = 32; off >= 1; off >>= 1) pairs += __shfl_xor(pairs, off, 64);
@@ -504,12 +489,11 @@ int oai_mesh_topology(const int* faces_dev, long long n_faces, long long n_verts
     OAI_CHECK_HIP(hipMemsetAsync(ws.cnt, 0, kTopoRec * sizeof(u64), st));
     if (nf) {
         OAI_CHECK_HIP(hipMemsetAsync(ws.n_list, 0, 2 * sizeof(int), st));
-        OAI_CHECK_HIP(hipMemsetAsync(ws.count, 0, (size_t)(nv + 1) * 4, st));
+        if (int rc = bucket_clear(ws.count, nv, st)) return rc;
         OAI_CHECK_HIP(hipMemsetAsync(ws.used, 0, (size_t)(nv + 1) * 4, st));
         topo_face_kernel<<<cdiv(nf, kT), kT, 0, st>>>(faces_dev, nf, nv, side_dev, ws.count, ws.used, ws.cnt);
         OAI_CHECK_LAUNCH();
-        if (int rc = exclusive_scan_i32(ws.count, ws.start, nv + 1, ws.scratch, st)) return rc;
-        OAI_CHECK_HIP(hipMemsetAsync(ws.count, 0, (size_t)(nv + 1) * 4, st));
+        if (int rc = bucket_starts(ws.count, ws.start, nv, ws.scratch, st)) return rc;
         topo_scatter_kernel<<<cdiv(3 * nf, kT), kT, 0, st>>>(faces_dev, nf, nv, ws.start, ws.count, ws.list);
         OAI_CHECK_LAUNCH();
         topo_classify_kernel<<<cdiv(3 * nf, kT), kT, 0, st>>>(faces_dev, nf, nv, side_dev, ws.start, ws.list, edge_class_dev, ws.cnt);
@@ -573,19 +557,16 @@ int oai_mesh_self_intersections(const float* verts_dev, long long n_verts, const
     const SiWs ws(workspace_dev, n_faces, grid_dims, capacity);
     const hipStream_t st = (hipStream_t)stream;
     const long long nf = n_faces;
-    SiGrid g;
-    for (int k = 0; k < 3; ++k) { g.lo[k] = grid_lo[k]; g.dims[k] = grid_dims[k]; }
-    g.h = cell_size;
+    const UniformGrid g = make_uniform_grid(grid_lo, cell_size, grid_dims);
     OAI_CHECK_HIP(hipMemsetAsync(ws.cnt, 0, kSiRec * sizeof(u64), st));
     if (nf) {
         OAI_CHECK_HIP(hipMemsetAsync(flag_dev, 0, (size_t)nf, st));
-        OAI_CHECK_HIP(hipMemsetAsync(ws.count, 0, (size_t)(ws.cells + 1) * 4, st));
+        if (int rc = bucket_clear(ws.count, ws.cells, st)) return rc;
         si_range_kernel<<<cdiv(nf, kT), kT, 0, st>>>(verts_dev, n_verts, faces_dev, nf, g, ws.range, ws.cnt);
         OAI_CHECK_LAUNCH();
         si_bin_kernel<<<cdiv(nf, kT), kT, 0, st>>>(ws.range, nf, g, ws.cnt, capacity, ws.count, nullptr, nullptr);
         OAI_CHECK_LAUNCH();
-        if (int rc = exclusive_scan_i32(ws.count, ws.start, ws.cells + 1, ws.scratch, st)) return rc;
-        OAI_CHECK_HIP(hipMemsetAsync(ws.count, 0, (size_t)(ws.cells + 1) * 4, st));
+        if (int rc = bucket_starts(ws.count, ws.start, ws.cells, ws.scratch, st)) return rc;
         si_bin_kernel<<<cdiv(nf, kT), kT, 0, st>>>(ws.range, nf, g, ws.cnt, capacity, ws.count, ws.start, ws.entries);
         OAI_CHECK_LAUNCH();
         si_pairs_kernel<<<cdiv(nf, kT), kT, 0, st>>>(verts_dev, faces_dev, nf, g, ws.range, ws.start, ws.entries, capacity, flag_dev, ws.cnt);

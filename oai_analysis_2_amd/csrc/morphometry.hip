@@ -28,10 +28,6 @@ constexpr int kRS = 12;                            // doubles per region of oai_
 constexpr int kMaxRegions = 64;
 
 // ---- oai_mesh_areas ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool face_ok(const int* __restrict__ f, long long n) {
-    return f[0] >= 0 && f[0] < n && f[1] >= 0 && f[1] < n && f[2] >= 0 && f[2] < n;
-}
-
 // one thread per face: its area, and one count per corner at the vertex the corner names
 __global__ void __launch_bounds__(kT) face_area_kernel(const float* __restrict__ verts, long long n, const int* __restrict__ faces, long long m,
                                                        double* __restrict__ area, int* __restrict__ count) {
@@ -91,8 +87,6 @@ struct AreaWs {
         bytes = ws.off;
     }
 };
-
-bool mesh_ok(long long n, long long m) { return n >= 0 && n < (1LL << 31) - 1 && m >= 0 && m <= kMaxFaces; }
 
 // ---- oai_region_stats ----------------------------------------------------------------------------------------------------------------
 struct RegionAcc {
@@ -173,14 +167,13 @@ int oai_mesh_areas(const float* verts_dev, long long n_verts, const int* faces_d
     const AreaWs ws(workspace_dev, n_verts, n_faces);
     const hipStream_t st = (hipStream_t)stream;
     double* area = face_area_dev ? face_area_dev : ws.area;
-    OAI_CHECK_HIP(hipMemsetAsync(ws.count, 0, (size_t)(n_verts + 1) * 4, st));
+    if (int rc = bucket_clear(ws.count, n_verts, st)) return rc;
     if (n_faces) {
         face_area_kernel<<<cdiv(n_faces, kT), kT, 0, st>>>(verts_dev, n_verts, faces_dev, n_faces, area, ws.count);
         OAI_CHECK_LAUNCH();
     }
     if (n_verts == 0) return OAI_OK;
-    if (int rc = exclusive_scan_i32(ws.count, ws.start, n_verts + 1, ws.scratch, st)) return rc;
-    OAI_CHECK_HIP(hipMemsetAsync(ws.count, 0, (size_t)(n_verts + 1) * 4, st));
+    if (int rc = bucket_starts(ws.count, ws.start, n_verts, ws.scratch, st)) return rc;
     if (n_faces) {
         corner_scatter_kernel<<<cdiv(3 * n_faces, kT), kT, 0, st>>>(faces_dev, n_verts, n_faces, ws.start, ws.count, ws.corners);
         OAI_CHECK_LAUNCH();

@@ -19,6 +19,7 @@
 // Reductions are block partials (a fixed number of blocks, a fixed tree in LDS) plus one final block: no float atomics, the same bits
 // on every run.  Everything here is latency- or gather-bound VALU work; nothing is GEMM-shaped.
 #include "common.h"
+#include "uniform_grid.h"
 
 #include <cmath>
 #include <utility>
@@ -41,26 +42,13 @@ __device__ __forceinline__ double dist2(const float* __restrict__ a, const float
 // ---------------------------------------------------------------------------------------------------------------------
 // point binning: cells of size h >= radius, count -> scan -> scatter, then each cell's list ordered by point index
 // ---------------------------------------------------------------------------------------------------------------------
-struct GridD {
-    double lo[3];
-    double h, inv_h;
-    int n[3];
-};
+using oai::UniformGrid;
 
-__device__ __forceinline__ int cell_of_coord(float p, double lo, double inv_h, int n) {
-    double t = floor(((double)p - lo) * inv_h);
-    t = t >= 0.0 ? t : 0.0;                        // (NaN lands in cell 0)
-    t = t <= (double)(n - 1) ? t : (double)(n - 1);
-    return (int)t;
-}
-
-__global__ void __launch_bounds__(kT) bin_count_kernel(const float* __restrict__ src, long long n, GridD g, int* __restrict__ cell_of,
+__global__ void __launch_bounds__(kT) bin_count_kernel(const float* __restrict__ src, long long n, UniformGrid g, int* __restrict__ cell_of,
                                                        int* __restrict__ count) {
     const long long i = (long long)blockIdx.x * kT + threadIdx.x;
     if (i >= n) return;
-    const int x = cell_of_coord(src[3 * i], g.lo[0], g.inv_h, g.n[0]), y = cell_of_coord(src[3 * i + 1], g.lo[1], g.inv_h, g.n[1]);
-    const int z = cell_of_coord(src[3 * i + 2], g.lo[2], g.inv_h, g.n[2]);
-    const int c = (z * g.n[1] + y) * g.n[0] + x;
+    const int c = oai::grid_index(g, oai::grid_cell(g, 0, src[3 * i]), oai::grid_cell(g, 1, src[3 * i + 1]), oai::grid_cell(g, 2, src[3 * i + 2]));
     cell_of[i] = c;
     atomicAdd(&count[c], 1);
 }
@@ -127,30 +115,28 @@ __device__ __forceinline__ void acc_store(const Acc& a, const Interp& ip, long l
     if (ip.count) { ip.count[i] = a.cnt; ip.nearest_d2[i] = a.best; ip.nearest_j[i] = a.best_j; }
 }
 
-__global__ void __launch_bounds__(kT) interp_grid_kernel(const float* __restrict__ src, const float* __restrict__ tgt, GridD g, double r2,
+__global__ void __launch_bounds__(kT) interp_grid_kernel(const float* __restrict__ src, const float* __restrict__ tgt, UniformGrid g, double r2,
                                                          const int* __restrict__ start, const int* __restrict__ list, Interp ip) {
     const long long i = (long long)blockIdx.x * kT + threadIdx.x;
     if (i >= ip.n_tgt) return;
     const float q[3] = {tgt[3 * i], tgt[3 * i + 1], tgt[3 * i + 2]};
     // a target outside the grid starts from the clamped cell: the cells hold every source point, and the distance from q to a point of
     // the grid box is at least the distance from q's projection onto the box, so the ring bound below still holds
-    const int cx = cell_of_coord(q[0], g.lo[0], g.inv_h, g.n[0]), cy = cell_of_coord(q[1], g.lo[1], g.inv_h, g.n[1]);
-    const int cz = cell_of_coord(q[2], g.lo[2], g.inv_h, g.n[2]);
+    const int cx = oai::grid_cell(g, 0, q[0]), cy = oai::grid_cell(g, 1, q[1]), cz = oai::grid_cell(g, 2, q[2]);
     Acc a;
 #pragma unroll
     for (int m = 0; m < kMaxComp; ++m) a.sum[m] = 0.0;
     a.cnt = 0; a.best = INFINITY; a.best_j = -1;
     auto visit = [&](int x, int y, int z) {
-        const int cell = (z * g.n[1] + y) * g.n[0] + x;
+        const int cell = oai::grid_index(g, x, y, z);
         for (int k = start[cell]; k < start[cell + 1]; ++k) {
             const int j = list[k];
             acc_point(a, ip, dist2(src + 3 * (long long)j, q), r2, j);
         }
     };
-    // the footprint: h >= radius, so every source point within the radius lies in the 27 cells around q's (clamping keeps that)
-    for (int z = max(cz - 1, 0); z <= min(cz + 1, g.n[2] - 1); ++z)
-        for (int y = max(cy - 1, 0); y <= min(cy + 1, g.n[1] - 1); ++y)
-            for (int x = max(cx - 1, 0); x <= min(cx + 1, g.n[0] - 1); ++x) visit(x, y, z);
+    // the footprint: h >= radius, so every source point within the radius lies in the 27 cells around q's (clamping keeps that).
+    // One box walk, not shell 0 then shell 1: the sums are accumulated in visit order
+    oai::grid_walk_box(max(cx - 1, 0), max(cy - 1, 0), max(cz - 1, 0), min(cx + 1, g.n[0] - 1), min(cy + 1, g.n[1] - 1), min(cz + 1, g.n[2] - 1), visit);
     if (a.cnt == 0) {
         // closest point: shells of Chebyshev radius r >= 2 around q's cell.  A point not visited after shell r-1 is at least (r-1) h
         // away; stop once the best is strictly closer than that (strict: an unvisited point at exactly that distance could win the
@@ -162,21 +148,11 @@ __global__ void __launch_bounds__(kT) interp_grid_kernel(const float* __restrict
             const double e = v < lo ? lo - v : (v > hi ? v - hi : 0.0);
             out2 += e * e;
         }
-        const int rmax = max(max(max(cx, g.n[0] - 1 - cx), max(cy, g.n[1] - 1 - cy)), max(cz, g.n[2] - 1 - cz));
+        const int rmax = oai::grid_rmax(g, cx, cy, cz);
         for (int r = 2; r <= rmax; ++r) {
             const double covered = (double)(r - 1) * g.h;
             if (a.best < out2 + covered * covered) break;
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, g.n[2] - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.n[1] - 1);
-            const int x0 = max(cx - r, 0), x1 = min(cx + r, g.n[0] - 1);
-            for (int z = z0; z <= z1; ++z)
-                for (int y = y0; y <= y1; ++y) {
-                    if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {      // a face of the shell: the whole row
-                        for (int x = x0; x <= x1; ++x) visit(x, y, z);
-                    } else {                                                             // otherwise only the two end cells
-                        if (cx - r >= 0) visit(cx - r, y, z);
-                        if (cx + r < g.n[0]) visit(cx + r, y, z);
-                    }
-                }
+            oai::grid_walk_shell(g, cx, cy, cz, r, visit);
         }
     }
     acc_store(a, ip, i);
@@ -390,7 +366,7 @@ size_t carve(MapWs& w, const void* base, long long n) {
 }
 
 int launch_interp(bool grid, const float* src, long long n_src, const float* vals, int n_comp, const float* tgt, long long n_tgt, double radius,
-                  const GridD& g, const int* start, const int* list, float* out, hipStream_t st) {
+                  const UniformGrid& g, const int* start, const int* list, float* out, hipStream_t st) {
     const double r2 = radius * radius;
     for (int c0 = 0; c0 < n_comp; c0 += kMaxComp) {
         Interp ip{vals + (long long)c0 * n_src, n_src, n_comp - c0 < kMaxComp ? n_comp - c0 : kMaxComp, out + (long long)c0 * n_tgt, n_tgt,
@@ -403,17 +379,12 @@ int launch_interp(bool grid, const float* src, long long n_src, const float* val
 }
 
 // the source points into their cells: count -> scan -> scatter -> each cell's list in ascending point index
-int bin_points(const float* src, long long n_src, const double lo[3], double cell_size, const int dims[3], const PointGridWs& w, GridD* grid,
-               hipStream_t st) {
-    GridD& g = *grid;
-    for (int k = 0; k < 3; ++k) { g.lo[k] = lo[k]; g.n[k] = dims[k]; }
-    g.h = cell_size; g.inv_h = 1.0 / cell_size;
-    const long long ncells = (long long)dims[0] * dims[1] * dims[2];
-    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+int bin_points(const float* src, long long n_src, const UniformGrid& g, const PointGridWs& w, hipStream_t st) {
+    const long long ncells = (long long)g.n[0] * g.n[1] * g.n[2];
+    if (int rc = oai::bucket_clear(w.count, ncells, st)) return rc;
     bin_count_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(src, n_src, g, w.cell_of, w.count);
     OAI_CHECK_LAUNCH();
-    if (int rc = oai::exclusive_scan_i32(w.count, w.start, ncells + 1, w.scratch, st)) return rc;
-    OAI_CHECK_HIP(hipMemsetAsync(w.count, 0, (size_t)(ncells + 1) * 4, st));
+    if (int rc = oai::bucket_starts(w.count, w.start, ncells, w.scratch, st)) return rc;
     bin_scatter_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.cell_of, n_src, w.start, w.count, w.unordered);
     OAI_CHECK_LAUNCH();
     bin_order_kernel<<<oai::cdiv(n_src, kT), kT, 0, st>>>(w.unordered, n_src, w.cell_of, w.start, w.list);
@@ -422,7 +393,7 @@ int bin_points(const float* src, long long n_src, const double lo[3], double cel
 }
 
 // oai_point_footprint: the interpolation kernels with no point array (nc = 0: nothing summed, nothing stored but the footprint)
-int launch_footprint(bool grid, const float* src, long long n_src, const float* tgt, long long n_tgt, double radius, const GridD& g, const int* start,
+int launch_footprint(bool grid, const float* src, long long n_src, const float* tgt, long long n_tgt, double radius, const UniformGrid& g, const int* start,
                      const int* list, int* count, double* nearest_d2, int* nearest_j, hipStream_t st) {
     const Interp ip{nullptr, n_src, 0, nullptr, n_tgt, count, nearest_d2, nearest_j};
     if (grid) interp_grid_kernel<<<oai::cdiv(n_tgt, kT), kT, 0, st>>>(src, tgt, g, radius * radius, start, list, ip);
@@ -559,7 +530,7 @@ int oai_map_attributes(const float* src_pts_dev, long long n_src, const float* s
     OAI_CHECK_ARG(n_tgt >= 0 && n_comp >= 1, "oai_map_attributes: negative target count or no point array");
     OAI_CHECK_ARG(radius >= 0.0 && std::isfinite(radius), "oai_map_attributes: radius must be finite and >= 0");
     if (n_tgt == 0) return OAI_OK;
-    return launch_interp(false, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, GridD{}, nullptr, nullptr, out_vals_dev,
+    return launch_interp(false, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, UniformGrid{}, nullptr, nullptr, out_vals_dev,
                          (hipStream_t)stream);
 }
 
@@ -580,8 +551,8 @@ int oai_map_attributes_grid(const float* src_pts_dev, long long n_src, const flo
     OAI_CHECK_WORKSPACE("oai_map_attributes_grid", workspace_bytes, carve(w, workspace_dev, ncells, n_src));
     if (n_tgt == 0) return OAI_OK;
     hipStream_t st = (hipStream_t)stream;
-    GridD g;
-    if (int rc = bin_points(src_pts_dev, n_src, grid_lo_xyz, cell_size, grid_dims_xyz, w, &g, st)) return rc;
+    const UniformGrid g = oai::make_uniform_grid(grid_lo_xyz, cell_size, grid_dims_xyz);
+    if (int rc = bin_points(src_pts_dev, n_src, g, w, st)) return rc;
     return launch_interp(true, src_pts_dev, n_src, src_vals_dev, n_comp, tgt_pts_dev, n_tgt, radius, g, w.start, w.list, out_vals_dev, st);
 }
 
@@ -592,7 +563,7 @@ int oai_point_footprint(const float* src_pts_dev, long long n_src, const float* 
     OAI_CHECK_ARG(n_tgt >= 0, "oai_point_footprint: negative target count");
     OAI_CHECK_ARG(radius >= 0.0 && std::isfinite(radius), "oai_point_footprint: radius must be finite and >= 0");
     if (n_tgt == 0) return OAI_OK;
-    return launch_footprint(false, src_pts_dev, n_src, tgt_pts_dev, n_tgt, radius, GridD{}, nullptr, nullptr, count_dev, nearest_d2_dev, nearest_j_dev,
+    return launch_footprint(false, src_pts_dev, n_src, tgt_pts_dev, n_tgt, radius, UniformGrid{}, nullptr, nullptr, count_dev, nearest_d2_dev, nearest_j_dev,
                             (hipStream_t)stream);
 }
 
@@ -613,8 +584,8 @@ int oai_point_footprint_grid(const float* src_pts_dev, long long n_src, const fl
     OAI_CHECK_WORKSPACE("oai_point_footprint_grid", workspace_bytes, carve(w, workspace_dev, ncells, n_src));
     if (n_tgt == 0) return OAI_OK;
     hipStream_t st = (hipStream_t)stream;
-    GridD g;
-    if (int rc = bin_points(src_pts_dev, n_src, grid_lo_xyz, cell_size, grid_dims_xyz, w, &g, st)) return rc;
+    const UniformGrid g = oai::make_uniform_grid(grid_lo_xyz, cell_size, grid_dims_xyz);
+    if (int rc = bin_points(src_pts_dev, n_src, g, w, st)) return rc;
     return launch_footprint(true, src_pts_dev, n_src, tgt_pts_dev, n_tgt, radius, g, w.start, w.list, count_dev, nearest_d2_dev, nearest_j_dev, st);
 }
 

@@ -1,5 +1,5 @@
 """An independent float64 reference for csrc/mesh.hip's point-to-mesh distance (tri_dist2, point_distance_kernel,
-grid_distance_kernel), the float32 restatement of its cell_coord and of the grid's ring walk, and the seeded inputs the CPU and GPU
+grid_distance_kernel), a float32 restatement of the grid's cell arithmetic and ring walk, and the seeded inputs the CPU and GPU
 tests share.  The reference is NOT Ericson's branch ladder (oracle/mesh.py restates that one): it is the minimum of the three
 point-segment distances and, where the triangle has a normal and the projection falls inside it, the plane distance -- exact for
 zero-area triangles by construction.  Not collected as a test."""
@@ -55,9 +55,11 @@ def ulp32(x):
     return (np.nextafter(x, np.float32(np.inf)) - x).astype(np.float64)
 
 
-# ---- the kernel's float32 cell arithmetic and the ring walk built on it ---------------------------------------------------------
+# ---- float32 cell arithmetic and the ring walk built on it ------------------------------------------------------------------------
+# The kernel bins with csrc/uniform_grid.h's grid_cell, the same formula in float64, whose slip is 2^29 times smaller: float32 is the
+# coarse case, where the slip can be constructed in float32 coordinates (stop_rule_case) and a walk without slack stops too early.
 def cell_coord_f32(p, lo, h, n):
-    """csrc/mesh.hip cell_coord in numpy float32: floorf((p - lo) * inv_h) clamped to [0, n), inv_h = 1.0f / h"""
+    """floorf((p - lo) * inv_h) clamped to [0, n), inv_h = 1.0f / h, in numpy float32"""
     p, lo, h = np.asarray(p, np.float32), np.float32(lo), np.float32(h)
     inv_h = np.float32(1.0) / h
     c = np.floor(((p - lo).astype(np.float32) * inv_h).astype(np.float32)).astype(np.int64)
@@ -71,7 +73,7 @@ def cell_coord_exact(p, lo, h, n):
 
 
 def grid_walk_emulated(point, verts, faces, lo, h, dims, slack_cells=0.0):
-    """grid_distance_kernel's ring walk for ONE point with the kernel's float32 binning (cell_coord_f32 for the triangles' bounding
+    """grid_distance_kernel's ring walk for ONE point with float32 binning (cell_coord_f32 for the triangles' bounding
     boxes and for the point) and float64 triangle distances; the stop is best <= (max(0, (r - 1) - slack_cells) * h)^2 in float32, as
     in the kernel.  Returns (distance, index of the triangle that gave it)."""
     verts, faces = np.asarray(verts, np.float32), np.asarray(faces)

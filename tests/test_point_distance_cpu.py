@@ -1,6 +1,6 @@
 """CPU: the independent float64 point-to-mesh reference (tests/point_distance_ref.py) against closed forms -- every Voronoi region of a
 triangle and every kind of zero-area triangle -- and against the oracle's Ericson ladder on a well-conditioned mesh; the oracle on
-zero-area triangles; the float32 restatement of the kernel's cell_coord against exact flooring; and the stopping-rule construction
+zero-area triangles; float32 cell arithmetic (coarser than the kernel's float64) against exact flooring; and the stopping-rule construction
 that tests/test_point_distance_gpu.py runs on the device, verified here on the emulated ring walk."""
 import numpy as np
 import pytest

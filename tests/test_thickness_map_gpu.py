@@ -61,6 +61,32 @@ def test_map_attributes_matches_restatement(seed, n_src, n_tgt, box, radius, far
     assert np.array_equal(got.view(np.int32), results[0].view(np.int32))                                   # run to run: same bits
 
 
+def test_map_attributes_grid_sums_in_cell_order():
+    """The grid path's fp64 sums run over the 27 cells in (z, y, x) order, each cell in ascending point index: bit for bit against that
+    restatement.  The values make the order show in the float32 result: 300 source points and, 300 indices later, a partner within 0.05
+    with the opposite value, magnitudes log-uniform over 24 decades -- a footprint's exact sum is mostly 0, and what is left of it is
+    the rounding of the partial sums, which depends on when each value was added."""
+    from oai_analysis_2_amd import mesh_processing as mp
+    rng = np.random.default_rng(4)
+    a = rng.uniform(0.0, 6.0, (300, 3))
+    src = np.concatenate([a, np.clip(a + rng.uniform(-0.05, 0.05, (300, 3)), 0.0, 6.0)]).astype(np.float32)
+    tgt = rng.uniform(-0.5, 6.5, (200, 3)).astype(np.float32)
+    v = (10.0 ** rng.uniform(-12.0, 12.0, 300) * rng.choice([-1.0, 1.0], 300)).astype(np.float32)
+    vals = np.concatenate([v, -v])
+    grid = mp._grid_from_params(src.min(axis=0).astype(np.float64), src.max(axis=0).astype(np.float64), 1.0)
+    ref, ascending, count = tref.map_attributes_grid_order(src, vals, tgt, grid, 1.0)
+    # the inputs tell the two orders apart: the restatement summed in ascending index gives other bits on >= 10 % of the targets
+    many = count >= 2
+    told_apart = (ref.view(np.int32) != ascending.view(np.int32))[many].mean()
+    print(f"grid order != ascending order on {told_apart:.1%} of {many.sum()} targets; {int((count == 0).sum())} empty footprints")
+    assert many.sum() >= 150 and told_apart >= 0.10
+    out = mp.map_attributes(mp.Mesh(src, EMPTY_FACES, {"v": vals}), mp.Mesh(tgt, EMPTY_FACES), radius=1.0, broad_phase=True).point_data["v"]
+    assert out.dtype == np.float32 and out.shape == (200,)
+    full = count > 0
+    differ = np.flatnonzero(out.view(np.int32)[full] != ref.view(np.int32)[full])
+    assert len(differ) == 0, (len(differ), differ[:5])
+
+
 def test_map_attributes_empty_source_raises():
     from oai_analysis_2_amd import mesh_processing as mp
     with pytest.raises(ValueError):

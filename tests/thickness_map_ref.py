@@ -37,6 +37,45 @@ def map_attributes(src_pts, src_vals, tgt_pts, radius=1.0):
     return out, margin
 
 
+def grid_cells(pts, h, dims, lo):
+    """cell (x, y, z) of float32 points in the grid (h, dims, lo) of mesh_processing._grid_from_params, as csrc/uniform_grid.h bins
+    them: floor((p - lo) * (1 / h)) in float64, clamped to [0, dims - 1]"""
+    t = np.floor((np.asarray(pts, np.float32).astype(np.float64) - np.asarray(lo, np.float64)) * (1.0 / float(h)))
+    return np.clip(t, 0, np.asarray(dims) - 1).astype(np.int64)
+
+
+def map_attributes_grid_order(src_pts, src_vals, tgt_pts, grid, radius=1.0):
+    """One component through the grid path of map_attributes, in ITS summation order: per target the 27 cells around the target's
+    cell in (z, y, x) order (clipped to the grid), within a cell ascending point index, one fp64 accumulator, then the mean as float32.
+    ``grid`` = (h, dims, lo).  Returns (out, ascending, count): the same mean summed in ascending point index over the whole footprint
+    (the brute-force order) beside it; both are NaN where ``count`` is 0 (the closest-point fallback is not restated here)."""
+    h, dims, lo = grid
+    vals = np.asarray(src_vals, np.float32).astype(np.float64)
+    r2 = float(radius) * float(radius)
+    d2 = pairwise_d2(tgt_pts, src_pts)
+    sc, tc = grid_cells(src_pts, h, dims, lo), grid_cells(tgt_pts, h, dims, lo)
+    out = np.full(len(tgt_pts), np.nan, np.float32)
+    ascending = out.copy()
+    count = np.zeros(len(tgt_pts), np.int64)
+    for i, c in enumerate(tc):
+        inside = np.flatnonzero(d2[i] <= r2)                                 # ascending point index
+        count[i] = len(inside)
+        if len(inside) == 0:
+            continue
+        s_grid, n_grid = 0.0, 0
+        for z in range(max(c[2] - 1, 0), min(c[2] + 1, dims[2] - 1) + 1):
+            for y in range(max(c[1] - 1, 0), min(c[1] + 1, dims[1] - 1) + 1):
+                for x in range(max(c[0] - 1, 0), min(c[0] + 1, dims[0] - 1) + 1):
+                    for j in inside[(sc[inside] == (x, y, z)).all(axis=1)]:
+                        s_grid, n_grid = s_grid + vals[j], n_grid + 1
+        assert n_grid == len(inside)                                         # h >= radius: the 27 cells hold the whole footprint
+        s_asc = 0.0
+        for j in inside:
+            s_asc = s_asc + vals[j]
+        out[i], ascending[i] = np.float32(s_grid / len(inside)), np.float32(s_asc / len(inside))
+    return out, ascending, count
+
+
 def fit_circle(x, y, iters=100):
     """centre minimising sum (R_i - mean R)^2 (Gauss-Newton on the centred Jacobian, from the centroid) and mean R_i"""
     x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
