@@ -1290,6 +1290,56 @@ int oai_graph_smooth(const double* values_dev, const unsigned char* mask_dev, lo
                      const int* neighbours_dev, long long n_neighbours, const double* edge_weight_dev, const double* self_weight_dev, int sweeps,
                      int fill, void* workspace_dev, size_t workspace_bytes, double* out_values_dev, unsigned char* out_mask_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Longitudinal change (csrc/visit_slopes.hip, tests/visit_slopes_ref.py): stage one of the two-stage (summary-measures) analysis of a
+ * longitudinal study.  Every SUBJECT (one knee followed over time) has several VISITS, each a row of the visit matrix with a time in
+ * years; per (subject, vertex) a straight line is fitted by least squares through the visits that have a value at that vertex, and its
+ * slope -- mm per year -- is the map that stage two tests across subjects like any other ("Cohort statistics" and after).  Visits may
+ * be unevenly spaced, a subject may miss a visit, and a vertex may be missing in some of a subject's visits: the fit at a vertex uses
+ * what is valid THERE, so n, the mean time and the span differ from vertex to vertex.  Fitting a line per subject and carrying the
+ * slopes forward is the summary-measures approach; FreeSurfer's long_mris_slopes does it for cortical thickness and names the measures
+ * rate, avg, pc1 and spc AS RECALLED; the definition below is this library's own and is pinned to no implementation, only to the numpy
+ * restatement, scipy.stats.linregress and numpy.polyfit.  The rules of "Cohort statistics" hold: fp64 without contraction (every
+ * product is rounded before it is added), one accumulator per sum that starts at +0.0, THE SLOTS OF A SUBJECT IN ASCENDING CSR
+ * POSITION, no floating-point atomics: bit-reproducible and independent of the launch geometry.  The entry point launches on the given
+ * stream, does not synchronise and reads nothing back.  1 <= n_rows <= 2^24, 1 <= n_verts <= 2^31 - 2, 1 <= n_subjects <= 2^24,
+ * 0 <= n_visits <= 2^24.
+ *
+ * Inputs.  values_dev float32 [n_rows][n_verts], the visit matrix: every row is one knee at one visit, in any order.  mask_dev uint8
+ * [n_rows][n_verts], non-zero = valid, or null: every entry is valid.  subject_offsets_dev int32 [n_subjects + 1]: subject s owns the
+ * CSR slots off[s] .. off[s+1] - 1; an offset outside [0, n_visits] is clamped.  visit_row_dev int32 [n_visits]: the row of values_dev
+ * of each slot; a slot whose row is outside [0, n_rows) is skipped as if it were missing at every vertex.  visit_time_dev float64
+ * [n_visits]: the time of each slot in years (finite: the caller's guarantee, the device does not check it).  reference_time_dev float64
+ * [n_subjects]: the time at which fit_ref is evaluated, typically the subject's first visit.  min_visits >= 2.  min_span >= 0, finite.
+ *
+ * For subject s and vertex v, over the slots e of s that are valid at v, t_e = time[e], y_e = values[row[e]][v]:
+ *   pass 1:  n = count;  St = St + t_e;  Sy = Sy + (double)y_e;  tmin, tmax over the valid slots
+ *            tb = St / n;  yb = Sy / n
+ *   pass 2:  dt = t_e - tb;  dy = (double)y_e - yb;  Sxx = Sxx + dt*dt;  Sxy = Sxy + dt*dy
+ *            ok = n >= min_visits && Sxx > 0 && (tmax - tmin) >= min_span
+ *            rate = Sxy / Sxx
+ *   pass 3:  r = dy - rate*dt;  rss = rss + r*r
+ *            avg = yb;  fit_ref = yb + rate * (tref_s - tb)
+ *            resid_sd = n >= 3 ? sqrt(rss / (double)(n - 2)) : NaN
+ * Sums centred on the means of pass 1: no cancelling formula.  A slot that is not valid at v is skipped by a select, never multiplied
+ * by 0: a NaN, an infinity or anything else stored under a 0 mask byte reaches no sum.  What is stored at a VALID entry propagates as
+ * IEEE says.  Two visits at the same time give Sxx = 0 and no slope; so does one visit, or none.
+ *
+ * Outputs, every one nullable and [n_subjects][n_verts]: rate_dev, avg_dev, fit_ref_dev, resid_sd_dev float64; n_dev int32, ALWAYS the
+ * count, also where ok is false; out_mask_dev uint8, ok as 0 or 1.  Where ok is false the float outputs hold +0.0.  resid_sd holds NaN
+ * exactly where ok is true and n == 2: two points have no residual.  A null output is neither computed nor written beyond what the
+ * others need: pass 3 runs for resid_sd_dev alone.  The workspace holds the slot table that the first launch writes: per subject its
+ * clamped slot run (two int32), per slot its row or -1.
+ * ---------------------------------------------------------------------------------------- */
+/* 0 for a shape the entry point refuses. */
+size_t oai_visit_slopes_workspace_bytes(long long n_rows, long long n_verts, long long n_subjects, long long n_visits);
+int oai_visit_slopes(const float* values_dev, const unsigned char* mask_dev, long long n_rows, long long n_verts, const int* subject_offsets_dev,
+                     long long n_subjects, const int* visit_row_dev, const double* visit_time_dev, long long n_visits,
+                     const double* reference_time_dev, int min_visits, double min_span, void* workspace_dev, size_t workspace_bytes,
+                     double* rate_dev, double* avg_dev, double* fit_ref_dev, double* resid_sd_dev, int* n_dev, unsigned char* out_mask_dev,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

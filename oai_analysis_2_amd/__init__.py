@@ -40,7 +40,8 @@ def __getattr__(name):
         from . import thickness
         return getattr(thickness, name)
     if name in ("ThicknessCohort", "PermutationResult", "two_sample_test", "paired_test", "label_permutations", "sign_flips",
-                "RegressionResult", "IndexPermutations", "regression_test", "index_permutations", "FResult", "f_test", "anova_test"):
+                "RegressionResult", "IndexPermutations", "regression_test", "index_permutations", "FResult", "f_test", "anova_test",
+                "LongitudinalCohort", "visit_table", "one_sample_test", "VisitSlopes"):
         from . import stats
         return getattr(stats, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -838,6 +838,63 @@ def graph_smooth(values: torch.Tensor, offsets: torch.Tensor, neighbours: torch.
     return out, out_mask
 
 
+# ---- longitudinal change (include/oai_hip.h, "Longitudinal change"; csrc/visit_slopes.hip) --------------------------------------------------
+SLOPE_OUTPUTS = ("rate", "avg", "fit_ref", "resid_sd", "n", "mask")
+MAX_VISIT_ROWS = 1 << 24             # rows, subjects and slots of one oai_visit_slopes call
+
+
+@dataclass
+class VisitSlopes:
+    """The per-subject line fits of ``visit_slopes``, device tensors [S, V] (None for an output that was not asked for): ``rate``, ``avg``,
+    ``fit_ref``, ``resid_sd`` float64 -- +0.0 where ``mask`` is 0, ``resid_sd`` NaN where the fit rests on two visits; ``n`` int32, the
+    visits with a value at the vertex, also where ``mask`` is 0; ``mask`` uint8, 1 where the fit exists."""
+    rate: Optional[torch.Tensor] = None
+    avg: Optional[torch.Tensor] = None
+    fit_ref: Optional[torch.Tensor] = None
+    resid_sd: Optional[torch.Tensor] = None
+    n: Optional[torch.Tensor] = None
+    mask: Optional[torch.Tensor] = None
+    min_visits: int = 2
+    min_span: float = 0.0
+
+
+def visit_slopes(values: torch.Tensor, offsets: torch.Tensor, rows: torch.Tensor, times: torch.Tensor, reference_time: torch.Tensor,
+                 mask: Optional[torch.Tensor] = None, min_visits: int = 2, min_span: float = 0.0, want: Sequence[str] = SLOPE_OUTPUTS) -> VisitSlopes:
+    """A straight line through every subject's visits at every vertex (include/oai_hip.h, "Longitudinal change"): float32 ``values`` [R,V],
+    one row per knee and visit in any order, with an optional uint8 / bool ``mask`` [R,V] (non-zero: valid); subject s owns the slots
+    ``offsets[s] .. offsets[s+1] - 1`` (int32 [S+1]) of ``rows`` (int32 [E]: the row of ``values``) and ``times`` (float64 [E]: years);
+    ``reference_time`` float64 [S] is where ``fit_ref`` is evaluated.  A fit exists where at least ``min_visits`` (>= 2) visits are valid
+    at the vertex, they are not all at one time, and they span at least ``min_span`` years.  ``want``: which of ``SLOPE_OUTPUTS`` are
+    allocated and computed.  fp64, slots in ascending position: bit-reproducible.  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or not 1 <= values.shape[0] <= MAX_VISIT_ROWS or values.shape[1] < 1:
+        raise ValueError(f"values must be [1 <= R <= 2^24, V >= 1], got {tuple(values.shape)}")
+    R, V, dev = int(values.shape[0]), int(values.shape[1]), values.device
+    mask = _stats_mask(mask, values)
+    offsets, rows = _chk(offsets, "offsets", torch.int32).reshape(-1), _chk(rows, "rows", torch.int32).reshape(-1)
+    times, reference_time = _chk(times, "times", torch.float64).reshape(-1), _chk(reference_time, "reference_time", torch.float64).reshape(-1)
+    S, E = int(offsets.numel()) - 1, int(rows.numel())
+    if not 1 <= S <= MAX_VISIT_ROWS or E > MAX_VISIT_ROWS or times.numel() != E or reference_time.numel() != S:
+        raise ValueError(f"offsets must hold S + 1 entries for 1 <= S <= 2^24 subjects, rows and times one entry per slot (at most 2^24) and "
+                         f"reference_time S, got {offsets.numel()}, {E}, {times.numel()}, {reference_time.numel()}")
+    for name, t in (("offsets", offsets), ("rows", rows), ("times", times), ("reference_time", reference_time)):
+        _check_same_gpu("values", values, name, t)
+    if int(min_visits) < 2:
+        raise ValueError(f"min_visits must be at least 2, got {min_visits!r}")
+    if not (float(min_span) >= 0.0 and math.isfinite(float(min_span))):
+        raise ValueError(f"min_span must be finite and >= 0, got {min_span!r}")
+    want = tuple(want)
+    if not want or len(set(want)) != len(want) or not set(want) <= set(SLOPE_OUTPUTS):
+        raise ValueError(f"want must name some of {SLOPE_OUTPUTS}, each once, got {want!r}")
+    dtypes = {"n": torch.int32, "mask": torch.uint8}
+    out = {name: torch.empty((S, V), dtype=dtypes.get(name, torch.float64), device=dev) for name in want}
+    ws = _lib.workspace("oai_visit_slopes", dev, R, V, S, E)
+    _lib.call("oai_visit_slopes", values.data_ptr(), _ptr(mask), R, V, offsets.data_ptr(), S, _ptr(rows, E), _ptr(times, E), E,
+              reference_time.data_ptr(), int(min_visits), float(min_span), ws.data_ptr(), ws.numel(),
+              *[_ptr(out.get(name)) for name in SLOPE_OUTPUTS], _lib.STREAM, device=dev)
+    return VisitSlopes(min_visits=int(min_visits), min_span=float(min_span), **out)
+
+
 # ---- cohort regression (include/oai_hip.h, "Cohort regression"; csrc/group_regression.hip) ---------------------------------------------------
 MAX_DESIGN_COLUMNS = 6
 

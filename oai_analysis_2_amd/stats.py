@@ -36,6 +36,15 @@ enhancement"; csrc/graph_tfce.hip; tests/graph_tfce_ref.py): every labelling's t
 ``cohort.smoothed(fwhm_mm=5.0)`` smooths every knee's map ALONG the atlas surface before any of the tests (include/oai_hip.h, "Surface
 smoothing"; csrc/graph_smooth.hip; tests/graph_smooth_ref.py): iterated Gaussian-weighted neighbourhood averaging on the device that
 neither reads nor invents a missing entry, with the sweep count calibrated on the mesh's own discrete kernel (``SurfaceSmoother``).
+
+``LongitudinalCohort`` holds the visits of a longitudinal study -- several per knee, unevenly spaced, some missing -- and ``change`` fits a
+straight line through each knee's own visits at every vertex on the device (include/oai_hip.h, "Longitudinal change";
+csrc/visit_slopes.hip; tests/visit_slopes_ref.py).  The slopes are a ``ThicknessCohort`` again, one row per subject, for any of the tests
+above and for ``one_sample_test``: is there loss at all, and where?
+
+    visits = LongitudinalCohort.from_stream(thickness_stream(...), atlas, "FC", visits={index: (subject, years), ...})
+    rate = visits.change("rate", min_visits=3)                          # mm / year per subject and vertex
+    one_sample_test(rate, tfce=True).p_tfce, regression_test(rate, baseline_kl_grade).p_fwer
 """
 from __future__ import annotations
 
@@ -165,6 +174,7 @@ class ThicknessCohort:
         self._graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self._areas: Optional[np.ndarray] = None
         self.smoothing: Optional["Smoothing"] = None       # set on the result of ``smoothed``
+        self.change: Optional["Change"] = None             # set on the result of ``LongitudinalCohort.change``
 
     def surface_graph(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """The CSR vertex adjacency of the atlas inner mesh on the device (``mesh_processing.vertex_adjacency_device``), built at the
@@ -252,7 +262,7 @@ class ThicknessCohort:
             raise ValueError("the cohort holds no knee to smooth")
         smoother = SurfaceSmoother(self.atlas, self.kind, fwhm_mm, sweeps=sweeps, sigma_step=sigma_step, missing=missing, graph=self.surface_graph())
         out = ThicknessCohort(self.atlas, self.kind, self.use_coverage, self.chunk)
-        out.ids, out._graph, out._areas, out.smoothing = list(self.ids), self._graph, self._areas, smoother.settings
+        out.ids, out._graph, out._areas, out.smoothing, out.change = list(self.ids), self._graph, self._areas, smoother.settings, self.change
         out._values = torch.zeros((N, V), dtype=torch.float32, device=self.device)
         out._mask = torch.zeros((N, V), dtype=torch.uint8, device=self.device)
         rows = smoothing_batch(V, N) if batch is None else int(batch)
@@ -467,6 +477,221 @@ class SurfaceSmoother:
         unit = torch.zeros((1, self.n_verts), dtype=torch.float64, device=self.device)
         unit[0, vertex] = 1.0 / float(self._vertex_sum[vertex])
         return self.smooth_tile(unit, None)[0][0].cpu().numpy() * self._vertex_sum
+
+
+# ---- longitudinal change ---------------------------------------------------------------------------------------------------------------
+VisitSlopes = ops.VisitSlopes
+CHANGE_MEASURES = {"rate": ("rate",), "avg": ("avg",), "pc1": ("rate", "fit_ref"), "spc": ("rate", "avg")}     # what each reads of the fit
+
+
+@dataclass
+class VisitTable:
+    """The visits of a study grouped by subject, as ``ops.visit_slopes`` takes them: ``subjects`` in order of first appearance; subject s
+    owns the slots ``offsets[s] .. offsets[s+1] - 1`` (int32 [S+1]) of ``rows`` (int32 [E]: the position of the visit in the input) and
+    ``times`` (float64 [E]: its years), in ascending time with ties in input order; ``reference_time`` float64 [S]."""
+    subjects: List[object]
+    offsets: np.ndarray
+    rows: np.ndarray
+    times: np.ndarray
+    reference_time: np.ndarray
+
+
+def visit_table(subjects, years, reference="first") -> VisitTable:
+    """Group visits by subject: ``subjects[i]`` (any hashable) and ``years[i]`` (a float, years since whatever origin the study uses)
+    describe visit i.  ``reference``: the time at which a subject's fitted value is read off (``fit_ref``, the denominator of "pc1") --
+    "first": the subject's earliest visit over ALL its visits, not only those valid at a vertex; a float: the same time for every
+    subject; a mapping from subject to time.  Refuses a time that is not finite and a (subject, time) pair given twice."""
+    subjects = list(subjects)
+    times = np.asarray(years, np.float64).reshape(-1)
+    if len(times) != len(subjects):
+        raise ValueError(f"subjects and years must hold one entry per visit, got {len(subjects)} and {len(times)}")
+    index: dict = {}
+    owner = np.array([index.setdefault(s, len(index)) for s in subjects], np.int64)
+    names = list(index)
+    for i in np.nonzero(~np.isfinite(times))[0][:1]:
+        raise ValueError(f"the time of visit {int(i)} of subject {subjects[i]!r} is not finite: {float(times[i])!r}")
+    order = np.lexsort((np.arange(len(times)), times, owner))              # by subject, then time, then input order
+    same = (owner[order][1:] == owner[order][:-1]) & (times[order][1:] == times[order][:-1])
+    for k in np.nonzero(same)[0][:1]:
+        raise ValueError(f"subject {subjects[order[k]]!r} has two visits at {float(times[order[k]])!r} years (visits {int(order[k])} and {int(order[k + 1])})")
+    S = len(names)
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(owner, minlength=S))]).astype(np.int32)
+    sorted_times = times[order]
+    if isinstance(reference, str):
+        if reference != "first":
+            raise ValueError(f'reference must be "first", a time or a mapping from subject to time, got {reference!r}')
+        tref = sorted_times[offsets[:-1]] if S else np.zeros(0)
+    elif hasattr(reference, "keys"):
+        missing = [s for s in names if s not in reference]
+        if missing:
+            raise ValueError(f"reference has no time for subject {missing[0]!r}")
+        tref = np.array([float(reference[s]) for s in names], np.float64)
+    else:
+        tref = np.full(S, float(reference), np.float64)
+    if not np.isfinite(tref).all():
+        raise ValueError(f"the reference time of subject {names[int(np.nonzero(~np.isfinite(tref))[0][0])]!r} is not finite")
+    return VisitTable(names, offsets, order.astype(np.int32), sorted_times, np.ascontiguousarray(tref, np.float64))
+
+
+@dataclass(frozen=True)
+class Change:
+    """What a cohort of ``LongitudinalCohort.change`` holds: the ``measure`` ("rate" mm / year, "avg" mm, "pc1" or "spc" % / year), the
+    least number of valid visits and the least span in years a fit needed, and the ``reference`` time ("first", a float, or "per subject"
+    for a mapping)."""
+    measure: str
+    min_visits: int
+    min_span_years: float
+    reference: object
+
+
+class LongitudinalCohort:
+    """The visits of a longitudinal study for one cartilage: every row is one knee at one visit, with the subject it belongs to and the
+    time of the visit in years.  The rows live in a ``ThicknessCohort`` (``.rows``), so MISSING means exactly what it means there: NaN, an
+    errored cartilage, or -- with ``use_coverage`` -- denuded bone.  Subjects may have different numbers of visits at different times.
+
+    ``change`` is stage one of the two-stage (summary-measures) analysis: a straight line through each subject's own visits at every
+    vertex (include/oai_hip.h, "Longitudinal change"; csrc/visit_slopes.hip), and the slopes come back as a ``ThicknessCohort`` with one
+    row per subject that ``one_sample_test`` (is there loss at all?), ``two_sample_test``, ``regression_test``, ``f_test`` and
+    ``anova_test`` (in whom is it faster?) take like any other.  A vertex that is missing in some of a subject's visits is fitted through
+    the others.  Smoothing may come before the fit (``smoothed``: every visit's map) or after it (``change(...).smoothed(...)``: the
+    rate maps); smoothing and fitting are both linear, so the two agree where nothing is missing, and differ where entries are missing:
+    before, a missing entry leaves its neighbours' averages in that visit alone; after, it has already changed n and the slope at its own
+    vertex."""
+
+    def __init__(self, atlas, kind: str, use_coverage: bool = False, chunk: int = 64):
+        self.rows = ThicknessCohort(atlas, kind, use_coverage, chunk)
+        self._subject: List[object] = []
+        self._years: List[float] = []
+        self._label: List[object] = []
+        self._seen: set = set()
+
+    atlas = property(lambda self: self.rows.atlas)
+    kind = property(lambda self: self.rows.kind)
+    device = property(lambda self: self.rows.device)
+    n_verts = property(lambda self: self.rows.n_verts)
+
+    def __len__(self) -> int:
+        return len(self._subject)
+
+    def _note(self, subject, years) -> float:
+        years = float(years)
+        if not math.isfinite(years):
+            raise ValueError(f"the time of a visit of subject {subject!r} is not finite: {years!r}")
+        if (subject, years) in self._seen:
+            raise ValueError(f"subject {subject!r} already has a visit at {years!r} years")
+        return years
+
+    def _noted(self, subject, years: float, visit) -> None:
+        self._seen.add((subject, years))
+        self._subject.append(subject)
+        self._years.append(years)
+        self._label.append(visit)
+
+    def add_vector(self, vector, subject, years, valid=None, visit=None) -> None:
+        """One knee at one visit as a bare vector [V] (NaN = missing) with an optional validity vector; ``visit``: a label ("V03")."""
+        years = self._note(subject, years)
+        self.rows.add_vector(vector, (subject, years), valid)
+        self._noted(subject, years, visit)
+
+    def add(self, knee, subject, years, visit=None) -> None:
+        """One ``KneeThickness`` of ``subject`` at ``years``."""
+        years = self._note(subject, years)
+        self.rows.add(knee, (subject, years))
+        self._noted(subject, years, visit)
+
+    @classmethod
+    def from_stream(cls, stream: Iterable[Tuple[object, object]], atlas, kind: str, visits, **kwargs) -> "LongitudinalCohort":
+        """Collect the (index, KneeThickness) pairs of ``thickness_stream`` / ``process_cohort_thickness``; ``visits[index]`` (or
+        ``visits(index)``) is the knee's (subject, years) or (subject, years, label)."""
+        cohort = cls(atlas, kind, **kwargs)
+        for index, knee in stream:
+            cohort.add(knee, *(visits(index) if callable(visits) else visits[index]))
+        return cohort
+
+    @classmethod
+    def from_cohorts(cls, cohorts, **kwargs) -> "LongitudinalCohort":
+        """From one ``ThicknessCohort`` per visit, ``{years: cohort, ...}``: a cohort's ids are the subjects, its rows their knees at that
+        time.  The cohorts must hold the same cartilage of the same atlas on the same GPU; their rows are copied."""
+        cohorts = dict(cohorts)
+        if not cohorts:
+            raise ValueError("from_cohorts needs at least one cohort")
+        first = next(iter(cohorts.values()))
+        out = cls(first.atlas, first.kind, kwargs.pop("use_coverage", first.use_coverage), kwargs.pop("chunk", first.chunk), **kwargs)
+        for years, c in cohorts.items():
+            if c.kind != out.kind or c.n_verts != out.n_verts or c.device != out.device:
+                raise ValueError("the cohorts must hold the same cartilage of the same atlas on the same GPU")
+            for i, subject in enumerate(c.ids):
+                out.add_vector(c.values[i], subject, years, valid=c.mask[i])
+        return out
+
+    @property
+    def subjects(self) -> List[object]:
+        """In order of first appearance: the ids of what ``change`` returns."""
+        return list(dict.fromkeys(self._subject))
+
+    def visits_of(self, subject) -> List[Tuple[float, object]]:
+        """The (years, label) of the subject's visits in ascending time."""
+        return sorted(((y, lab) for s, y, lab in zip(self._subject, self._years, self._label) if s == subject), key=lambda p: p[0])
+
+    def at_visit(self, visit) -> ThicknessCohort:
+        """The rows of one visit as a ``ThicknessCohort`` whose ids are the subjects -- what ``paired_test`` matches rows by: the rows
+        labelled ``visit``, or, where no row carries that label, those at ``visit`` years.  A copy."""
+        picked = [i for i, lab in enumerate(self._label) if lab is not None and lab == visit]
+        if not picked and isinstance(visit, (int, float)) and not isinstance(visit, bool):
+            picked = [i for i, y in enumerate(self._years) if y == float(visit)]
+        if not picked:
+            raise ValueError(f"no row is labelled or timed {visit!r}")
+        ids = [self._subject[i] for i in picked]
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"a subject has more than one row at visit {visit!r}")
+        return self._derived(ids, *(t.index_select(0, torch.tensor(picked, dtype=torch.int64, device=self.device))
+                                    for t in (self.rows.values, self.rows.mask)))
+
+    def _derived(self, ids, values: torch.Tensor, mask: torch.Tensor) -> ThicknessCohort:
+        out = ThicknessCohort(self.atlas, self.kind, self.rows.use_coverage, self.rows.chunk)
+        out.ids, out._graph, out._areas, out.smoothing = list(ids), self.rows._graph, self.rows._areas, self.rows.smoothing
+        out._values, out._mask = values.contiguous(), mask.contiguous()
+        return out
+
+    def smoothed(self, *args, **kwargs) -> "LongitudinalCohort":
+        """A NEW longitudinal cohort whose every visit is smoothed along the atlas surface (``ThicknessCohort.smoothed``, whose arguments
+        these are): smoothing BEFORE the fit."""
+        out = LongitudinalCohort.__new__(LongitudinalCohort)
+        out.rows = self.rows.smoothed(*args, **kwargs)
+        out._subject, out._years, out._label, out._seen = list(self._subject), list(self._years), list(self._label), set(self._seen)
+        return out
+
+    def trajectories(self, min_visits: int = 2, min_span_years: float = 0.0, reference="first", want: Sequence[str] = ops.SLOPE_OUTPUTS) -> VisitSlopes:
+        """``ops.visit_slopes`` of the rows grouped by ``visit_table``: the fits of every subject (in the order of ``subjects``) at every
+        vertex, on the device.  A fit exists where at least ``min_visits`` visits are valid at the vertex and span at least
+        ``min_span_years``.  ``reference``: as in ``visit_table``."""
+        if not len(self):
+            raise ValueError("the cohort holds no visit")
+        table = visit_table(self._subject, self._years, reference)
+        dev = self.device
+        return ops.visit_slopes(self.rows.values, *(torch.from_numpy(a).to(dev) for a in (table.offsets, table.rows, table.times, table.reference_time)),
+                                mask=self.rows.mask, min_visits=min_visits, min_span=min_span_years, want=want)
+
+    def change(self, measure: str = "rate", min_visits: int = 2, min_span_years: float = 0.0, reference="first") -> ThicknessCohort:
+        """A NEW ``ThicknessCohort`` with one row per subject (ids = ``subjects``): "rate", the fitted slope in mm / year; "avg", the mean
+        over the valid visits in mm; "pc1", the rate in per cent of the fitted value at the reference time, 100 * rate / fit_ref; "spc", in
+        per cent of the mean, 100 * rate / avg (both % / year; the quotient is taken in float64 on the device, rate / denominator first and
+        times 100 after, and the entry is missing where the denominator is not > 0).  An entry is missing where the subject has no fit at
+        the vertex (``trajectories``).  The float64 plane is rounded to float32 once.  The settings are kept on the result as ``.change``
+        (a ``Change``)."""
+        if measure not in CHANGE_MEASURES:
+            raise ValueError(f"measure must be one of {tuple(CHANGE_MEASURES)}, got {measure!r}")
+        reads = CHANGE_MEASURES[measure]
+        fits = self.trajectories(min_visits, min_span_years, reference, want=tuple(dict.fromkeys(reads + ("mask",))))
+        ok, plane = fits.mask != 0, getattr(fits, reads[0])
+        if len(reads) == 2:
+            den = getattr(fits, reads[1])
+            ok = ok & (den > 0)
+            plane = (plane / torch.where(ok, den, torch.ones_like(den))) * 100.0
+        out = self._derived(self.subjects, torch.where(ok, plane, torch.zeros_like(plane)).to(torch.float32), ok.to(torch.uint8))
+        kept = reference if isinstance(reference, str) else ("per subject" if hasattr(reference, "keys") else float(reference))
+        out.change = Change(measure, int(min_visits), float(min_span_years), kept)
+        return out
 
 
 # ---- the tests -------------------------------------------------------------------------------------------------------------------------
@@ -760,12 +985,32 @@ def paired_test(cohort_a: ThicknessCohort, cohort_b: ThicknessCohort, n_permutat
     order = torch.tensor([where_b[id_] for id_ in cohort_a.ids], dtype=torch.int64, device=cohort_a.device)
     mask = cohort_a.mask * cohort_b.mask.index_select(0, order)
     diff = (cohort_a.values - cohort_b.values.index_select(0, order)) * mask        # missing entries hold 0 on either side
+    return _one_sample(cohort_a, diff, mask, n_permutations, cluster_threshold, seed, permutations, batch, tfce)
+
+
+def _one_sample(cohort_like, values: torch.Tensor, mask: torch.Tensor, n_permutations: int, cluster_threshold, seed: int, permutations, batch,
+                tfce: Optional[TFCE]) -> PermutationResult:
+    """What ``paired_test`` and ``one_sample_test`` share: the one-sample t of the rows of ``values`` under sign flips."""
+    N = int(values.shape[0])
     perms = _permutations(permutations, lambda: sign_flips(N, n_permutations, seed), N)
     if perms.rows()[0].any():
         raise ValueError("row 0 of the permutations must flip nothing")
-    batches, prepared, tile_of = _bit_tiles(cohort_a, diff, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, tfce, batch)
+    batches, prepared, tile_of = _bit_tiles(cohort_like, values, mask, perms, ops.STATS_ONE_SAMPLE, cluster_threshold, tfce, batch)
     host, shared = batches.run(tile_of, {"n": prepared.n, "mean": prepared.mean})
-    return PermutationResult(kind=cohort_a.kind, n1=host["n"], n2=host["n"].copy(), mean_difference=host["mean"], exact=perms.exact, **shared)
+    return PermutationResult(kind=cohort_like.kind, n1=host["n"], n2=host["n"].copy(), mean_difference=host["mean"], exact=perms.exact, **shared)
+
+
+def one_sample_test(cohort: ThicknessCohort, n_permutations: int = 10000, cluster_threshold: Optional[float] = None, seed: int = 0,
+                    permutations=None, batch: Optional[int] = None, tfce=None) -> PermutationResult:
+    """Where do the cohort's own values differ from zero -- of a rate cohort (``LongitudinalCohort.change``): is there loss at all, and
+    where?  The one-sample t of the values per vertex; its null distribution comes from ``sign_flips`` (under the null a subject's change is
+    as likely to be a gain as a loss), or from ``permutations`` with a first row that flips nothing.  It is ``paired_test`` of the cohort
+    against zeros, without the zeros: ``n1`` = ``n2`` = the subjects with a value at the vertex, ``mean_difference`` their mean.
+    ``cluster_threshold``, ``batch`` and ``tfce``: as in ``two_sample_test``."""
+    tfce = _tfce_settings(tfce)
+    if len(cohort) < 2:
+        raise ValueError("one_sample_test needs at least two knees")
+    return _one_sample(cohort, cohort.values, cohort.mask, n_permutations, cluster_threshold, seed, permutations, batch, tfce)
 
 
 # ---- regression ------------------------------------------------------------------------------------------------------------------------

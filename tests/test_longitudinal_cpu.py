@@ -1,0 +1,144 @@
+"""CPU: the restatement of the longitudinal line fit (tests/visit_slopes_ref.py) -- its loop form against its vectorised form to the bit,
+both against scipy.stats.linregress and np.polyfit -- and the host side of oai_analysis_2_amd.stats: ``visit_table``."""
+import functools
+
+import numpy as np
+import pytest
+
+import visit_slopes_ref as vref
+
+N_KNEES = 20000
+
+
+def _same_bits(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
+    if got.dtype.kind == "f":
+        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
+        got, want = np.where(np.isnan(got), 0, got).view(np.int64), np.where(np.isnan(want), 0, want).view(np.int64)
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
+
+
+@pytest.mark.parametrize("with_mask", [True, False])
+@pytest.mark.parametrize("V", [1, 7])
+def test_the_loop_form_equals_the_vectorised_form_to_the_bit(V, with_mask):
+    case = vref.hostile_case(11 + V, V, with_mask=with_mask)
+    for kwargs in ({}, dict(min_visits=3), dict(min_span=2.5), dict(min_visits=4, min_span=1.0)):
+        fast, slow = vref.fit(*case, **kwargs), vref.fit_loop(*case, **kwargs)
+        for name in vref.OUTPUTS:
+            _same_bits(fast[name], slow[name], f"V={V} mask={with_mask} {kwargs} {name}")
+        assert np.isfinite(fast["rate"]).all() and np.abs(fast["avg"]).max() <= 4.0           # nothing of what lay under a 0 mask byte
+    fast = vref.fit(*case)
+    assert (fast["n"][0] == 0).all() and (fast["mask"][:3] == 0).all() and fast["mask"][3].all()
+    assert np.isnan(fast["resid_sd"][(fast["mask"] == 1) & (fast["n"] == 2)]).all()
+    assert not np.isnan(fast["resid_sd"][(fast["mask"] == 0) | (fast["n"] >= 3)]).any()
+
+
+@functools.lru_cache(maxsize=None)
+def _knees():
+    case = vref.oai_like_knees(2024, N_KNEES)
+    return case, vref.fit(case[0], None, *case[1:])
+
+
+@functools.lru_cache(maxsize=None)
+def _linregress():
+    """(slope, intercept, stderr) of scipy.stats.linregress per knee, computed once for the tests that compare with it."""
+    from scipy.stats import linregress
+    (Y, offsets, rows, times, tref), _ = _knees()
+    fits = [linregress(times[a:b], Y[a:b, 0].astype(np.float64)) for a, b in zip(offsets[:-1], offsets[1:])]
+    return tuple(np.array([getattr(f, name) for f in fits]) for name in ("slope", "intercept", "stderr"))
+
+
+def test_the_fit_is_linregress_and_polyfit():
+    """Measured on these 20 000 knees of 2 to 7 visits: rate 1.6e-16 of max|y| / span and fit_ref 2.3e-16 of max|y| against linregress,
+    rate 1.6e-15 against polyfit; the gate of 1e-10 is the project's usual margin over an agreement of that class."""
+    (Y, offsets, rows, times, tref), got = _knees()
+    slope, intercept, _ = _linregress()
+    worst = {"rate": 0.0, "fit_ref": 0.0, "rate_polyfit": 0.0}
+    assert got["mask"].all() and np.array_equal(got["n"][:, 0], np.diff(offsets))
+    for s in range(N_KNEES):
+        t, y = times[offsets[s]:offsets[s + 1]], Y[offsets[s]:offsets[s + 1], 0].astype(np.float64)
+        ymax, span = np.abs(y).max(), t[-1] - t[0]
+        worst["rate"] = max(worst["rate"], abs(got["rate"][s, 0] - slope[s]) / (ymax / span))
+        worst["fit_ref"] = max(worst["fit_ref"], abs(got["fit_ref"][s, 0] - (intercept[s] + slope[s] * tref[s])) / ymax)
+        assert got["avg"][s, 0] == y.sum() / len(y) or abs(got["avg"][s, 0] - y.mean()) <= 1e-15 * ymax
+        if s % 10 == 0:
+            worst["rate_polyfit"] = max(worst["rate_polyfit"], abs(got["rate"][s, 0] - np.polyfit(t, y, 1)[0]) / (ymax / span))
+    print("worst differences:", worst)
+    assert worst["rate"] <= 1e-10 and worst["fit_ref"] <= 1e-10 and worst["rate_polyfit"] <= 1e-10, worst
+
+
+RESID_SD_MEASURED = 1.3e-8                # the worst relative difference to linregress measured on these knees (profiles/longitudinal.md)
+
+
+def test_the_residual_sd_is_linregress_standard_error():
+    """stderr * sqrt(Sxx) of linregress is the residual standard deviation.  scipy forms it from 1 - r^2, which cancels on a tight line:
+    measured on these 20 000 knees, scipy's figure is off by up to 1.29e-8 (relative) from the same three passes in extended precision --
+    on a knee of three visits with r = -0.99999999 -- and the restatement by up to 1.1e-13.  So the margin is scipy's: gated at 100
+    times the measured worst case.  Against the extended-precision passes the gate is the project's 1e-10 of max|y|."""
+    (Y, offsets, rows, times, tref), got = _knees()
+    stderr = _linregress()[2]
+    worst, worst_long, seen = 0.0, 0.0, 0
+    for s in np.nonzero(np.diff(offsets) >= 3)[0]:
+        t, y = times[offsets[s]:offsets[s + 1]].astype(np.longdouble), Y[offsets[s]:offsets[s + 1], 0].astype(np.longdouble)
+        dt, dy = t - t.mean(), y - y.mean()
+        r = dy - (dt * dy).sum() / (dt * dt).sum() * dt
+        worst_long = max(worst_long, abs(float(got["resid_sd"][s, 0] - np.sqrt((r * r).sum() / (len(t) - 2)))) / float(np.abs(y).max()))
+        ref = stderr[s] * np.sqrt(float((dt * dt).sum()))
+        if ref > 0:
+            worst, seen = max(worst, abs(got["resid_sd"][s, 0] - ref) / ref), seen + 1
+    print("worst relative difference of resid_sd to linregress:", worst, "over", seen, "knees; to extended precision, of max|y|:", worst_long)
+    assert seen > N_KNEES // 2 and worst <= 100 * RESID_SD_MEASURED and worst_long <= 1e-10, (worst, worst_long)
+    two = np.diff(offsets) == 2
+    assert two.any() and np.isnan(got["resid_sd"][two, 0]).all()
+
+
+def test_the_measures():
+    (Y, offsets, rows, times, tref), got = _knees()
+    for name, den in (("pc1", "fit_ref"), ("spc", "avg")):
+        x, m = vref.measure(got, name)
+        assert m.all() and x.dtype == np.float32
+        assert np.array_equal(x, ((got["rate"] / got[den]) * 100.0).astype(np.float32))
+    few = {k: v[:4].copy() for k, v in got.items()}
+    few["fit_ref"][1], few["avg"][2], few["mask"][3] = 0.0, -1.0, 0
+    assert vref.measure(few, "pc1")[1][:, 0].tolist() == [1, 0, 1, 0] and vref.measure(few, "spc")[1][:, 0].tolist() == [1, 1, 0, 0]
+    assert vref.measure(few, "pc1")[0][1, 0] == 0 and vref.measure(few, "rate")[1][:, 0].tolist() == [1, 1, 1, 0]
+
+
+# ---- visit_table -----------------------------------------------------------------------------------------------------------------------
+def test_visit_table_groups_sorts_and_refers():
+    from oai_analysis_2_amd import stats
+    subjects = ["b", "a", "b", "c", "a", "b", "a"]
+    years = [4.0, 1.0, 0.0, 2.0, 0.5, 4.0 - 1e-9, 1.0 + 1e-9]
+    tab = stats.visit_table(subjects, years)
+    assert tab.subjects == ["b", "a", "c"]                                 # first appearance
+    assert tab.offsets.dtype == np.int32 and tab.offsets.tolist() == [0, 3, 6, 7]
+    assert tab.rows.dtype == np.int32 and tab.rows.tolist() == [2, 5, 0, 4, 1, 6, 3]
+    assert tab.times.dtype == np.float64 and np.array_equal(tab.times, np.asarray(years)[tab.rows])
+    assert tab.reference_time.dtype == np.float64 and tab.reference_time.tolist() == [0.0, 0.5, 2.0]      # c has one visit
+    assert stats.visit_table(subjects, years, reference=1.5).reference_time.tolist() == [1.5, 1.5, 1.5]
+    assert stats.visit_table(subjects, years, reference={"a": 1.0, "b": 2.0, "c": 3.0, "d": 9.0}).reference_time.tolist() == [2.0, 1.0, 3.0]
+    empty = stats.visit_table([], [])
+    assert empty.subjects == [] and empty.offsets.tolist() == [0] and len(empty.rows) == 0
+    # ties cannot occur within a subject (they are refused), so stability shows across equal times of DIFFERENT subjects only; the sort
+    # key is (subject, time, input order) and tuples as subjects work like any hashable
+    tab = stats.visit_table([(1, "L"), (1, "R"), (1, "L")], [2, 2, 1])
+    assert tab.subjects == [(1, "L"), (1, "R")] and tab.rows.tolist() == [2, 0, 1]
+
+
+def test_visit_table_refuses():
+    from oai_analysis_2_amd import stats
+    with pytest.raises(ValueError, match="'k7'.*not finite"):
+        stats.visit_table(["k1", "k7"], [0.0, float("nan")])
+    with pytest.raises(ValueError, match="'k7'.*not finite"):
+        stats.visit_table(["k7", "k1"], [float("inf"), 1.0])
+    with pytest.raises(ValueError, match="'k7' has two visits at 2.0"):
+        stats.visit_table(["k1", "k7", "k1", "k7"], [0.0, 2.0, 1.0, 2.0])
+    with pytest.raises(ValueError, match="one entry per visit"):
+        stats.visit_table(["k1"], [0.0, 1.0])
+    with pytest.raises(ValueError, match="no time for subject 'k7'"):
+        stats.visit_table(["k1", "k7"], [0.0, 1.0], reference={"k1": 0.0})
+    with pytest.raises(ValueError, match="reference must be"):
+        stats.visit_table(["k1"], [0.0], reference="last")
+    with pytest.raises(ValueError, match="reference time of subject 'k1' is not finite"):
+        stats.visit_table(["k1"], [0.0], reference=float("nan"))
