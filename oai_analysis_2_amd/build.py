@@ -7,9 +7,11 @@ box with the repo snapshot (``*.so`` is git-ignored, not gpurun-ignored).
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
+import time
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,7 +43,28 @@ def _stale(target: str, deps) -> bool:
     if not os.path.exists(target):
         return True
     t = os.path.getmtime(target)
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in deps)
+
+
+def _deps(obj: str):
+    """What the object was compiled from, as hipcc's -MMD wrote it next to it (a make rule: the source and every header it included);
+    None without such a file: the object is rebuilt."""
+    try:
+        words = open(obj[:-2] + ".d").read().replace("\\\n", " ").split()
+    except OSError:
+        return None
+    return words[1:]                                     # words[0] is the target
+
+
+def _weight(src: str, seen=None) -> int:
+    """Bytes of a source and of the headers of csrc/ that it includes, directly or not: the order in which a build starts its
+    compiles -- the kernel files that include the most first, so that the longest compile is not the last to start."""
+    seen = set() if seen is None else seen
+    if src in seen or not os.path.exists(src):
+        return 0
+    seen.add(src)
+    text = open(src, errors="replace").read()
+    return len(text) + sum(_weight(os.path.join(CSRC, inc), seen) for inc in re.findall(r'^\s*#\s*include\s+"([^"/]+)"', text, flags=re.M))
 
 
 def build_library(force: bool = False, verbose: bool = True, extra_flags=(), lib_path: str = None, obj_dir: str = None) -> str:
@@ -49,14 +72,14 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), lib
     ablations with wrong results, variant selection by environment) is a separate file that only scripts/ load via OAI_LIB_PATH."""
     OBJ, LIB = obj_dir or globals()["OBJ"], lib_path or globals()["LIB"]
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))]
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "oai_hip.h"))
     hipcc = _hipcc()
     jobs = []
     for src in sources():
         obj = os.path.join(OBJ, os.path.basename(src) + ".o")
-        if force or _stale(obj, [src] + headers):
+        deps = _deps(obj)
+        if force or deps is None or _stale(obj, [src] + deps):
             jobs.append((src, obj))
+    jobs.sort(key=lambda job: -_weight(job[0]))
 
     # diagnostic builds only: OAI_PACKED_TU=warp.hip compiles the named sources WITH packed fp32 ops (hipcc's default), to re-measure
     # the hazard of profiles/r02_packed_fp32_hazard.md against the current kernels (scripts/stress_overlap.py)
@@ -65,19 +88,22 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), lib
     def compile_one(job):
         src, obj = job
         flags = [f for f in FLAGS if f not in ("-Xclang", "-target-feature", "-packed-fp32-ops")] if os.path.basename(src) in packed_tu else FLAGS
-        cmd = [hipcc, *flags, *extra_flags, "-x", "hip", "-c", src, "-o", obj]
+        cmd = [hipcc, *flags, *extra_flags, "-MMD", "-MF", obj[:-2] + ".d", "-x", "hip", "-c", src, "-o", obj]
+        t0 = time.time()
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
         err = "\n".join(ln for ln in r.stderr.splitlines() if "not a recognized feature for this target" not in ln)
         if verbose and err.strip():
             print(err, file=sys.stderr)
+        if verbose:
+            print(f"[oai build] {os.path.basename(src)} {time.time() - t0:.1f} s", file=sys.stderr)
         return obj
 
     if jobs:
         if verbose:
             print(f"[oai build] compiling {len(jobs)} source(s) for {ARCH}", file=sys.stderr)
-        with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), 16)) as ex:
             list(ex.map(compile_one, jobs))
     objs = [os.path.join(OBJ, os.path.basename(s) + ".o") for s in sources()]
     if force or jobs or _stale(LIB, objs):

@@ -1,6 +1,7 @@
-// Host side of the segmentation path: weight ingest (reference layouts -> MFMA panels),
-// workspace planning, the layer schedule of UNet.forward (networks.py:109-149) with the
-// bit-identical dead-output trim, and the C ABI.
+// Host side of the segmentation path: tile geometry and workspace planning, the layer schedule of UNet.forward
+// (networks.py:109-149) with the bit-identical dead-output trim, the options and the C ABI.
+// Weight ingest is unet_pack.hip; the launchers of the kernel families are in unet_direct.hip (+ unet_direct_m16.hip),
+// unet_wino.hip and unet_small.hip (unet_host.h); the two kernels here build the box table and the block lists.
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -8,88 +9,8 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
-#include "unet_kernels.h"
-#include "unet_sres.h"
-#include "unet_sres2.h"
-#include "unet_wino.h"
-#include "unet_wino_f32.h"
-
-namespace oai {
-
-enum LayerId { EC0, EC1, EC2, EC3, EC4, EC5, EC6, EC7, DC9, DC8, DC7, DC6, DC5, DC4, DC3, DC2, DC1, DC0 };
-__host__ __device__ static inline int layer_level(int k) { const int v[18] = {0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 2, 1, 1, 1, 0, 0, 0, 0}; return v[k]; }   // OUTPUT level
-__host__ __device__ static inline int layer_kind(int k) { const int v[18] = {0, 0, 0, 0, 0, 0, 0, 0, 2, 1, 1, 2, 1, 1, 2, 1, 1, 3}; return v[k]; }
-static const int kKind[18] = {0, 0, 0, 0, 0, 0, 0, 0, 2, 1, 1, 2, 1, 1, 2, 1, 1, 3};
-
-struct Layer {
-    int kind = 0, cin = 0, cout = 0;
-    int c0 = 0, c1 = 0;                 // concat split of cin (c1 = skip channels)
-    float4* panel = nullptr;            // MFMA weight panel (kinds 0,1,2 except ec0)
-    float4* panel_bf[3] = {nullptr, nullptr, nullptr};   // split panels of the k3 layers: bf16 x2 terms, bf16 x3 terms, fp16 x2 terms
-    // fp16x3 epilogue affine (refresh_fp16_affine): scale / ws * 2^(e_out - e_in0), shift * 2^e_out with ws = the fp16 panel's per-cout
-    // power-of-two weight scale and e = the activation exponents of the layer's output / first input tensor (oai_unet::act_exp)
-    float* scale_f16 = nullptr;
-    float* shift_f16 = nullptr;
-    float* plain_f16 = nullptr;         // dc0 in fp16x3: head weights * 2^-e(dc1)
-    std::vector<float> ws;              // per-cout weight scale of the fp16 panel (exact powers of two)
-    int rel1 = 0;                       // exponent folded into the source-1 (skip) weights of the current fp16 panel: e(src0) - e(src1)
-    size_t panel_f16_floats = 0;
-    float4* panel_wino_f32 = nullptr;   // fp32 panel of conv3_wino_f32 (pack_wino_f32_panel): the x axis in Winograd F(2,3) form, exact-fp32 path
-    float4* panel_wino = nullptr;       // fp16 panel of conv3_wino_sres (pack_wino_panel): the x axis in Winograd F(2,3) form; packed with the same ws / rel1
-    size_t panel_wino_floats = 0;
-    float4* panel_wino16 = nullptr;     // the same weights laid out for the 16x16x32 taps of conv3_wino_sres<..., M16> (pack_wino16_panel; Cout % 128 == 0 only)
-    size_t panel_wino16_floats = 0;
-    float4* panel_m16 = nullptr;        // the fp16 panel laid out for the 16x16x32 tap pairs of conv3_igemm_sres<..., M16> (pack_conv3_m16_panel): same values as panel_bf[2]
-    size_t panel_m16_floats = 0;
-    std::vector<float> wk_host;         // canonical [27][cin][cout] weights of the k3 layers (for re-packing)
-    std::vector<float> scale_host, shift_host, plain_host;
-    float* plain = nullptr;             // ec0: [27][cout]; dc0: [ncls][cin]
-    float* scale = nullptr;
-    float* shift = nullptr;
-};
-
-}  // namespace oai
-
-struct oai_unet {
-    oai::Layer L[18];
-    int variant = 0;                    // 0: MREP4/KC8, 1: MREP2/KC16
-    int precision = OAI_PREC_F32;
-    int* range_flag = nullptr;          // device word set by the split-fp16 kernels when an activation exceeds fp16's range
-    unsigned* census = nullptr;         // [18][16] float bits: max |stored activation| per layer since the last reset (census_note)
-    int* eval_out = nullptr;            // device scratch of oai_unet_range_flag
-    // Per-tensor activation exponents of the fp16x3 path: layer k stores x * 2^act_exp[k].  fp16's low split term needs |x| >= 2^-3 to be
-    // normal; below that the pair (h0, h1) has an ABSOLUTE error floor of 2^-25, so a tensor whose values sit near 2^-10 would carry
-    // 1e-5 relative error.  Calibration (oai_unet_calibrate_step) puts every layer's maximum in [2^10, 2^11): 5 bits of
-    // headroom below 65504 and a floor of 2^-35 of the maximum.  Exact: powers of two fold into the epilogue affine and the panels.
-    int act_exp[18] = {0};
-    bool calibrated = false;
-    // The tuning options and their defaults.  What each one does is written once, where it is set: kIntOptions / oai_unet_set_option.
-    int opt_wino_f32 = 1;               // option "winograd_f32"
-    int opt_first_blocks = 24;          // option "first_blocks"
-    int opt_up_nbw = 0;                 // option "up_nbw"
-    int opt_own_cover = 1;              // option "own_cover"
-    int opt_one_launch = 1;             // option "one_launch"
-    int opt_shared = 1;                // option "shared_enc"
-    int opt_wide = 1;                   // option "wide"
-    int opt_wino = 19;                  // option "winograd"
-    int opt_wino_layers = 0x3FFFF;      // option "winograd_layers"
-    int opt_m16 = 1;                    // option "m16"
-    int opt_m16_layers = 0x3FFFF;       // option "m16_layers"
-    int opt_dead_stores = 1;            // option "dead_stores"
-    int opt_census = 1;                 // option "census"
-    int xcd_group = 32;                 // option "xcd_group"
-    int fuse_first = 1;                 // option "fuse_first"
-    int sres_mrep = 4;                  // option "sres_mrep"
-    bool opt_sres = true;               // option "sres": fp16x3 uses the split-resident kernels
-    bool sres = false;                  // fp16x3 runs split-resident (activations stored as fp16 term pairs, unet_sres.h)
-    unsigned char* zero_rec = nullptr;  // 64 zero bytes: source of halo voxels outside the tile for the LDS-DMA staging
-    int n_classes = 0;
-    std::vector<void*> allocs;
-    bool profile = false;
-    std::vector<hipEvent_t> ev_pool;      // reused start/stop pairs
-    size_t ev_used = 0;
-};
+#include "unet_host.h"
+#include "unet_wino.h"      // the entry format of the live-block lists (wino_list_entry); no kernel of it is named here
 
 #ifdef OAI_DIAG
 static unsigned long long* g_diag_stamps = nullptr;
@@ -109,424 +30,6 @@ extern "C" int oai_diag_stamps(unsigned long long out[32], int reset) {      // 
 #endif
 
 namespace oai {
-
-static int conv_kc(int variant) { return variant == 1 ? 16 : 8; }
-
-// Wk[tap][cin][cout] of the equivalent correlation (Conv3d as is; ConvTranspose3d k3 s1 p1 = conv with
-// the kernel flipped and in/out swapped).
-static std::vector<float> canonical_k3(const oai_layer_params& p) {
-    std::vector<float> w((size_t)27 * p.cin * p.cout);
-    for (int t = 0; t < 27; ++t)
-        for (int ci = 0; ci < p.cin; ++ci)
-            for (int co = 0; co < p.cout; ++co) {
-                float v;
-                if (p.kind == 0) v = p.weight_host[((size_t)co * p.cin + ci) * 27 + t];
-                else v = p.weight_host[((size_t)ci * p.cout + co) * 27 + (26 - t)];   // flip all three axes
-                w[((size_t)t * p.cin + ci) * p.cout + co] = v;
-            }
-    return w;
-}
-
-// Chunk `ch` of a k3 layer's K loop: the chunks of source 0 (C0 channels) come first, then those of source 1 (the skip tensor of a concat layer:
-// C1 channels, at offset C0 of the layer's input channels).  cl0 = the chunk's first channel inside its source.
-struct ChunkSrc {
-    bool first;
-    int Csrc, cofs, cl0;
-    ChunkSrc(int ch, int C0, int C1, int KC) {
-        const int nch0 = (C0 + KC - 1) / KC;
-        first = ch < nch0; Csrc = first ? C0 : C1; cofs = first ? 0 : C0; cl0 = (first ? ch : ch - nch0) * KC;
-    }
-};
-
-// Panel order = consumption order of conv3_igemm_f32: [cb][chunk][tap][kg][nr][lane] x float4, where the
-// float4 of lane (half h, column j) holds channels 4h..4h+3 of the k-group for cout cb*64+nr*32+j.
-static std::vector<float> pack_conv3_panel(const std::vector<float>& wk, int C0, int C1, int Cout, int KC) {
-    const int Cin = C0 + C1, KG = KC / 8;
-    const int ncb = (Cout + 63) / 64, nch0 = (C0 + KC - 1) / KC, nch1 = (C1 + KC - 1) / KC;
-    std::vector<float> out(((size_t)ncb * (nch0 + nch1) * 27 * KG * 2 + 2) * 64 * 4, 0.0f);   // +1 step of prefetch slack
-    size_t o = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int ch = 0; ch < nch0 + nch1; ++ch) {
-            const ChunkSrc cs(ch, C0, C1, KC);
-            for (int t = 0; t < 27; ++t)
-                for (int kg = 0; kg < KG; ++kg)
-                    for (int nr = 0; nr < 2; ++nr)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int s = 0; s < 4; ++s, ++o) {
-                                const int cl = cs.cl0 + kg * 8 + 4 * (lane >> 5) + s;
-                                const int co = cb * 64 + nr * 32 + (lane & 31);
-                                if (cl < cs.Csrc && co < Cout) out[o] = wk[((size_t)t * Cin + cs.cofs + cl) * Cout + co];
-                            }
-        }
-    return out;
-}
-
-// Frequency f of the Winograd F(2,3) weight transform along x: g0..g2 = the three x taps of one (dz, dy, cin, cout)
-static inline double wino_u(int f, double g0, double g1, double g2) { return f == 0 ? g0 : f == 1 ? 0.5 * (g0 + g1 + g2) : f == 2 ? 0.5 * (g0 - g1 + g2) : g2; }
-
-// ... of tap row t = dz * 3 + dy, input channel ci, output channel co of wk, the weights first multiplied by `scale` (an exact power of two): formed in double,
-// rounded to fp32 once
-static inline float wino_weight(const std::vector<float>& wk, int f, int t, int Cin, int ci, int Cout, int co, double scale = 1.0) {
-    const size_t i = ((size_t)(t * 3) * Cin + ci) * Cout + co, dx = (size_t)Cin * Cout;
-    return (float)wino_u(f, wk[i] * scale, wk[i + dx] * scale, wk[i + 2 * dx] * scale);
-}
-
-// conv3_wino_f32 (unet_wino_f32.h): the x-transformed weights (wino_weight) per (dz, dy, cin, cout); layout [cout block 64][frequency 4][chunk of 8 channels][tap (dz, dy) 9][cout half 2][lane 64][4]: lane (column = lane & 31, k half =
-// lane >> 5) holds channels 4 (lane >> 5) .. + 3 of cout 32 nr + column -- the B operands of four v_mfma_f32_32x32x2_f32 k-steps, like pack_conv3_panel.
-static std::vector<float> pack_wino_f32_panel(const std::vector<float>& wk, int C0, int C1, int Cout) {
-    constexpr int KC = 8;
-    const int Cin = C0 + C1;
-    const int ncb = (Cout + 63) / 64, nch0 = (C0 + KC - 1) / KC, nch1 = (C1 + KC - 1) / KC;
-    std::vector<float> out(((size_t)ncb * 4 * (nch0 + nch1) * 9 * 2 + 6) * 64 * 4, 0.0f);     // + three taps of prefetch slack
-    size_t o = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int f = 0; f < 4; ++f)
-            for (int ch = 0; ch < nch0 + nch1; ++ch) {
-                const ChunkSrc cs(ch, C0, C1, KC);
-                for (int q = 0; q < 9; ++q)
-                    for (int nr = 0; nr < 2; ++nr)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int s = 0; s < 4; ++s, ++o) {
-                                const int cl = cs.cl0 + 4 * (lane >> 5) + s;
-                                const int co = cb * 64 + nr * 32 + (lane & 31);
-                                if (cl < cs.Csrc && co < Cout) out[o] = wino_weight(wk, f, q, Cin, cs.cofs + cl, Cout, co);
-                            }
-            }
-    return out;
-}
-
-static inline uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float bf16_to_f32(uint16_t b) {
-    uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-static inline uint16_t f32_to_f16_rne(float f) {            // IEEE binary16, round to nearest even, subnormals kept
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    u &= 0x7fffffffu;
-    if (u >= 0x7f800000u) return (uint16_t)(sign | (u > 0x7f800000u ? 0x7e00u : 0x7c00u));
-    if (u >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                    // rounds to >= 65520 -> inf
-    if (u < 0x33000001u) return (uint16_t)sign;                                 // < 2^-25 -> 0
-    int e = (int)(u >> 23) - 127;
-    uint32_t m = (u & 0x7fffffu) | 0x800000u;
-    int shift = e < -14 ? (-14 - e) + 13 : 13;                                  // subnormal: extra shift
-    uint32_t half = m >> shift, rem = m & ((1u << shift) - 1), mid = 1u << (shift - 1);
-    if (rem > mid || (rem == mid && (half & 1))) ++half;
-    uint32_t out = e < -14 ? half : (((uint32_t)(e + 15) << 10) + (half - 0x400u));   // carry propagates into the exponent
-    return (uint16_t)(sign | out);
-}
-static inline float f16_to_f32(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    uint32_t e = (h >> 10) & 31u, m = h & 0x3ffu, u;
-    if (e == 0) {
-        if (m == 0) u = sign;
-        else { int s = 0; while (!(m & 0x400u)) { m <<= 1; ++s; } u = sign | ((uint32_t)(113 - s) << 23) | ((m & 0x3ffu) << 13); }
-    } else if (e == 31) u = sign | 0x7f800000u | (m << 13);
-    else u = sign | ((e + 112) << 23) | (m << 13);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// Term `term` (0 = high, 1 = low, ...) of the fp16 split of r: every term is the RNE fp16 of what the terms before it left over
-static inline uint16_t f16_term(float r, int term) {
-    uint16_t b = 0;
-    for (int kk = 0; kk <= term; ++kk) { b = f32_to_f16_rne(r); r -= f16_to_f32(b); }
-    return b;
-}
-
-// Split-bf16 panel of conv3_igemm_bf16s: [cb][chunk of 16][tap][term][nr][lane] x 8 bf16, where lane (half h, column j)
-// holds channels 8h..8h+7 of the chunk for cout cb*64+nr*32+j.  Terms: w = t0 + t1 (+ t2), each the RNE bf16 of the rest.
-// fp16: `wscale[co]` (an exact power of two) multiplies every weight of output channel co before the split.
-// `src1_factor` (an exact power of two) multiplies the weights of the source-1 (skip) channels: the two sources of a concat layer are stored
-// with different activation exponents and the panel carries their ratio.
-static std::vector<float> pack_conv3_panel_bf(const std::vector<float>& wk, int C0, int C1, int Cout, int NS,
-                                              bool fp16 = false, const std::vector<float>* wscale = nullptr, float src1_factor = 1.0f) {
-    const int Cin = C0 + C1, KC = 16;
-    const int ncb = (Cout + 63) / 64, nch0 = (C0 + KC - 1) / KC, nch1 = (C1 + KC - 1) / KC;
-    const size_t units = ((size_t)ncb * (nch0 + nch1) * 27 + 1) * NS * 2 * 64;      // 16-byte units, +1 tap of prefetch slack
-    std::vector<float> out(units * 4, 0.0f);
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(out.data());
-    size_t u = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int ch = 0; ch < nch0 + nch1; ++ch) {
-            const ChunkSrc cs(ch, C0, C1, KC);
-            for (int t = 0; t < 27; ++t)
-                for (int k = 0; k < NS; ++k)
-                    for (int nr = 0; nr < 2; ++nr)
-                        for (int lane = 0; lane < 64; ++lane, ++u)
-                            for (int j = 0; j < 8; ++j) {
-                                const int cl = cs.cl0 + 8 * (lane >> 5) + j;
-                                const int co = cb * 64 + nr * 32 + (lane & 31);
-                                if (cl < cs.Csrc && co < Cout) {
-                                    float r = wk[((size_t)t * Cin + cs.cofs + cl) * Cout + co] * (wscale ? (*wscale)[co] : 1.0f) * (cs.first ? 1.0f : src1_factor);
-                                    uint16_t b = 0;
-                                    for (int kk = 0; kk <= k && !fp16; ++kk) { b = f32_to_bf16_rne(r); r -= bf16_to_f32(b); }
-                                    o16[u * 8 + j] = fp16 ? f16_term(r, k) : b;
-                                }
-                            }
-        }
-    return out;
-}
-
-// Tap of step j (0..13), lane half tsel, of conv3_igemm_sres<..., M16>: 27 taps = 13 pairs + 1 (see the kernel's header comment).  t = (dz * 3 + dy) * 3 + dx.
-static inline int m16_step_tap(int j, int tsel) {
-    if (j < 9) return 3 * j + tsel;                          // (q = j, dx 0) | (q, dx 1)
-    if (j < 12) return 3 * (3 * (j - 9) + tsel) + 2;         // (q, dx 2) | (q + 1, dx 2), q = 0, 3, 6
-    if (j == 12) return 3 * (2 + 3 * tsel) + 2;              // (2, dx 2) | (5, dx 2)
-    return 26;                                               // (8, dx 2) alone
-}
-
-// Panel of conv3_igemm_sres<..., M16> (v_mfma_f32_16x16x32_f16, K = a PAIR of taps x 16 channels): [cb][chunk of 16][step 14][X' | Y'][n2 4][lane] x 8 fp16.
-// Lane (column c = lane & 15, group g = lane >> 4) of tile n2 holds cout cb * 64 + n2 * 16 + c, channels 8 (g & 1) .. + 7 of tap m16_step_tap(j, g >> 1):
-// X' = the HIGH terms b0 of both taps, Y' = the LOW terms b1.  Step 13 (the 27th tap alone, A = [a0 | a1]): X' = [b0 | b0], Y' = [b1 | 0].  The values are
-// pack_conv3_panel_bf's fp16 terms (same scales, same split).  + 1 step of prefetch slack (the kernel requests one step past its last).
-static std::vector<float> pack_conv3_m16_panel(const std::vector<float>& wk, int C0, int C1, int Cout, const std::vector<float>& wscale, float src1_factor) {
-    const int Cin = C0 + C1, KC = 16;
-    const int ncb = (Cout + 63) / 64, nch0 = (C0 + KC - 1) / KC, nch1 = (C1 + KC - 1) / KC;
-    const size_t units = ((size_t)ncb * (nch0 + nch1) * 14 + 1) * 2 * 4 * 64;          // 16-byte units
-    std::vector<float> out(units * 4, 0.0f);
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(out.data());
-    size_t u = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int ch = 0; ch < nch0 + nch1; ++ch) {
-            const ChunkSrc cs(ch, C0, C1, KC);
-            for (int j = 0; j < 14; ++j)
-                for (int kind = 0; kind < 2; ++kind)             // 0: X', 1: Y'
-                    for (int n2 = 0; n2 < 4; ++n2)
-                        for (int lane = 0; lane < 64; ++lane, ++u) {
-                            const int g = lane >> 4, tsel = g >> 1;
-                            if (j == 13 && kind == 1 && tsel == 1) continue;           // step 13: Y' = [b1 | 0]
-                            const int t = m16_step_tap(j, tsel), term = kind;
-                            const int co = cb * 64 + n2 * 16 + (lane & 15);
-                            if (co >= Cout) continue;
-                            for (int e = 0; e < 8; ++e) {
-                                const int cl = cs.cl0 + 8 * (g & 1) + e;
-                                if (cl < cs.Csrc) o16[u * 8 + e] = f16_term(wk[((size_t)t * Cin + cs.cofs + cl) * Cout + co] * wscale[co] * (cs.first ? 1.0f : src1_factor), term);
-                            }
-                        }
-        }
-    return out;
-}
-
-// Panel of conv3_wino_sres (unet_wino.h): [cb][frequency f][chunk of 16][tap (dz, dy)][term][nr][lane] x 8 fp16, lane (half h, column j) =
-// channels 8h..8h+7 of the chunk for cout cb*64+nr*32+j, of the x-transformed weights
-//   u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2, u3 = g2     (g = the three x taps of (dz, dy, cin, cout)),
-// formed in double from the scaled weights (wscale, src1_factor: see pack_conv3_panel_bf), rounded to fp32 once, then split.
-static std::vector<float> pack_wino_panel(const std::vector<float>& wk, int C0, int C1, int Cout, const std::vector<float>& wscale, float src1_factor) {
-    const int Cin = C0 + C1, KC = 16;
-    const int ncb = Cout / 64, nch0 = (C0 + KC - 1) / KC, nch1 = (C1 + KC - 1) / KC;
-    const size_t units = ((size_t)ncb * 4 * (nch0 + nch1) * 9 + 2) * 2 * 2 * 64;      // 16-byte units, +2 taps of prefetch slack (one is read)
-    std::vector<float> out(units * 4, 0.0f);
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(out.data());
-    size_t u = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int f = 0; f < 4; ++f)
-            for (int ch = 0; ch < nch0 + nch1; ++ch) {
-                const ChunkSrc cs(ch, C0, C1, KC);
-                for (int t = 0; t < 9; ++t)                          // t = dz * 3 + dy
-                    for (int k = 0; k < 2; ++k)
-                        for (int nr = 0; nr < 2; ++nr)
-                            for (int lane = 0; lane < 64; ++lane, ++u)
-                                for (int j = 0; j < 8; ++j) {
-                                    const int cl = cs.cl0 + 8 * (lane >> 5) + j;
-                                    const int co = cb * 64 + nr * 32 + (lane & 31);
-                                    if (cl < cs.Csrc) o16[u * 8 + j] = f16_term(wino_weight(wk, f, t, Cin, cs.cofs + cl, Cout, co, (double)wscale[co] * (cs.first ? 1.0 : (double)src1_factor)), k);
-                                }
-            }
-    return out;
-}
-
-// Panel of conv3_wino_sres<.., M16> (v_mfma_f32_16x16x32_f16, K = a PAIR of taps x 16 channels): [cb][frequency f][chunk of 16][step 5][X' | Y'][n2 4][lane]
-// x 8 fp16.  Lane (column c = lane & 15, group g = lane >> 4) of tile n2 holds cout cb * 64 + n2 * 16 + c, channels 8 (g & 1) .. + 7 of tap
-// 2 j + (g >> 1) (steps j < 4): X' = the HIGH terms b0 of both taps, Y' = the LOW terms b1.  Step 4 (the ninth tap alone, A = [a0 | a1]):
-// X' = [b0(8) | b0(8)], Y' = [b1(8) | 0].  The values are pack_wino_panel's (same transformed weights, same scales, same split).
-static std::vector<float> pack_wino16_panel(const std::vector<float>& wk, int C0, int C1, int Cout, const std::vector<float>& wscale, float src1_factor) {
-    const int Cin = C0 + C1, KC = 16;
-    const int ncb = Cout / 64, nch0 = (C0 + KC - 1) / KC, nch1 = (C1 + KC - 1) / KC;
-    const size_t units = ((size_t)ncb * 4 * (nch0 + nch1) * 5 + 2) * 2 * 4 * 64;       // 16-byte units, + 2 steps of prefetch slack
-    std::vector<float> out(units * 4, 0.0f);
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(out.data());
-    size_t u = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int f = 0; f < 4; ++f)
-            for (int ch = 0; ch < nch0 + nch1; ++ch) {
-                const ChunkSrc cs(ch, C0, C1, KC);
-                for (int j = 0; j < 5; ++j)
-                    for (int kind = 0; kind < 2; ++kind)             // 0: X', 1: Y'
-                        for (int n2 = 0; n2 < 4; ++n2)
-                            for (int lane = 0; lane < 64; ++lane, ++u) {
-                                const int g = lane >> 4, tsel = g >> 1;
-                                int t, term;
-                                if (j < 4) { t = 2 * j + tsel; term = kind; }
-                                else { t = 8; term = kind; if (kind == 1 && tsel == 1) continue; }     // step 4: X' = [b0 | b0], Y' = [b1 | 0]
-                                const int co = cb * 64 + n2 * 16 + (lane & 15);
-                                for (int e = 0; e < 8; ++e) {
-                                    const int cl = cs.cl0 + 8 * (g & 1) + e;
-                                    if (cl < cs.Csrc) o16[u * 8 + e] = f16_term(wino_weight(wk, f, t, Cin, cs.cofs + cl, Cout, co, (double)wscale[co] * (cs.first ? 1.0 : (double)src1_factor)), term);
-                                }
-                            }
-            }
-    return out;
-}
-
-// [N/64][Cin/8][2][lane] x float4 for upconv2_igemm_f32; column n = parity*Cout + co
-static std::vector<float> pack_up_panel(const oai_layer_params& p) {
-    const int N = 8 * p.cout, nnb = (N + 63) / 64, nkg = (p.cin + 7) / 8;
-    std::vector<float> out((size_t)nnb * nkg * 2 * 64 * 4, 0.0f);
-    size_t o = 0;
-    for (int nb = 0; nb < nnb; ++nb)
-        for (int kg = 0; kg < nkg; ++kg)
-            for (int nr = 0; nr < 2; ++nr)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s = 0; s < 4; ++s, ++o) {
-                        const int ci = kg * 8 + 4 * (lane >> 5) + s;
-                        const int col = nb * 64 + nr * 32 + (lane & 31);
-                        if (ci < p.cin && col < N) {
-                            const int par = col / p.cout, co = col % p.cout;
-                            out[o] = p.weight_host[((size_t)ci * p.cout + co) * 8 + par];   // [ci][co][a][b][c]
-                        }
-                    }
-    return out;
-}
-
-// split-fp16 panel of upconv2_igemm<true>: [N/64][Cin/16][term 2][nr 2][lane] x 8 fp16; lane (half h, column j) holds
-// channels 16*ks + 8h .. +7 for column nb*64 + nr*32 + j (column n = parity*Cout + co); weights of output channel co are
-// first multiplied by wscale[co] (exact power of two)
-static std::vector<float> pack_up_panel_f16(const float* w /*[ci][co][8]*/, int cin, int cout, const std::vector<float>& wscale) {
-    const int N = 8 * cout, nnb = (N + 63) / 64, nks = (cin + 15) / 16;
-    std::vector<float> out((size_t)nnb * nks * 4 * 64 * 4, 0.0f);
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(out.data());
-    size_t u = 0;
-    for (int nb = 0; nb < nnb; ++nb)
-        for (int ks = 0; ks < nks; ++ks)
-            for (int k = 0; k < 2; ++k)
-                for (int nr = 0; nr < 2; ++nr)
-                    for (int lane = 0; lane < 64; ++lane, ++u)
-                        for (int j = 0; j < 8; ++j) {
-                            const int ci = ks * 16 + 8 * (lane >> 5) + j;
-                            const int col = nb * 64 + nr * 32 + (lane & 31);
-                            if (ci < cin && col < N) {
-                                const int par = col / cout, co = col % cout;
-                                o16[u * 8 + j] = f16_term(w[((size_t)ci * cout + co) * 8 + par] * wscale[co], k);
-                            }
-                        }
-    return out;
-}
-
-template <typename T>
-static int upload(oai_unet* h, const std::vector<float>& v, T** dst) {
-    void* d = nullptr;
-    OAI_CHECK_HIP(hipMalloc(&d, v.size() * sizeof(float)));
-    h->allocs.push_back(d);
-    OAI_CHECK_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    *dst = reinterpret_cast<T*>(d);
-    return OAI_OK;
-}
-
-// (re)fill a device array that already exists (same size) or create it
-template <typename T>
-static int upload_into(oai_unet* h, const std::vector<float>& v, T** dst) {
-    if (!*dst) return upload(h, v, dst);
-    OAI_CHECK_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    return OAI_OK;
-}
-
-// tensors a layer reads: its first source is the previous layer of the schedule (a pooled tensor keeps its producer's exponent);
-// dc8 / dc5 / dc2 also read the skips ec5 / ec3 / ec1
-static inline int layer_src0(int k) { return k - 1; }
-static inline int layer_src1(int k) { return k == DC8 ? EC5 : k == DC5 ? EC3 : k == DC2 ? EC1 : -1; }
-
-// The Winograd panel of layer k (k3 layers with whole blocks of 64 couts) for the weight scales / skip exponent of its current fp16 panel
-static int pack_wino_layer(oai_unet* h, int k) {
-    Layer& L = h->L[k];
-    if (L.kind == 2 || L.wk_host.empty() || L.cout % 64 != 0 || L.ws.empty()) return OAI_OK;
-    const std::vector<float> panel = pack_wino_panel(L.wk_host, L.c0, L.c1, L.cout, L.ws, ldexpf(1.0f, L.rel1));
-    if (L.panel_wino && panel.size() != L.panel_wino_floats) return set_error(OAI_ERR_ARG, "Winograd panel of layer %d changed size", k);
-    L.panel_wino_floats = panel.size();
-    if (int rc = upload_into(h, panel, &L.panel_wino)) return rc;
-    const std::vector<float> p16 = pack_wino16_panel(L.wk_host, L.c0, L.c1, L.cout, L.ws, ldexpf(1.0f, L.rel1));
-    if (L.panel_wino16 && p16.size() != L.panel_wino16_floats) return set_error(OAI_ERR_ARG, "16x16x32 Winograd panel of layer %d changed size", k);
-    L.panel_wino16_floats = p16.size();
-    return upload_into(h, p16, &L.panel_wino16);
-}
-
-// The fp16 panel of layer k (k3 conv or k2s2 up-conv) for the current activation exponents.  Every output channel's weights are scaled
-// by the power of two that puts max|w| in [2^7, 2^8) -- exact, undone by the epilogue scale -- so that the low split term of all
-// weights down to 2^-11 of the largest stays in fp16's normal range.
-static int pack_fp16_layer(oai_unet* h, int k) {
-    Layer& L = h->L[k];
-    const int s1 = layer_src1(k);
-    const int rel1 = s1 >= 0 ? h->act_exp[layer_src0(k)] - h->act_exp[s1] : 0;
-    const float f1 = ldexpf(1.0f, rel1);
-    L.ws.assign(L.cout, 1.0f);
-    std::vector<float> panel;
-    if (L.kind == 2) {
-        for (int co = 0; co < L.cout; ++co) {
-            float amax = 0.0f;
-            for (int ci = 0; ci < L.cin; ++ci)
-                for (int q = 0; q < 8; ++q) amax = fmaxf(amax, fabsf(L.wk_host[((size_t)ci * L.cout + co) * 8 + q]));
-            if (amax > 0.0f && std::isfinite(amax)) { int e; frexpf(amax, &e); L.ws[co] = ldexpf(1.0f, 8 - e); }   // amax = m 2^e, m in [0.5,1)
-        }
-        panel = pack_up_panel_f16(L.wk_host.data(), L.cin, L.cout, L.ws);
-    } else {
-        const int Cin = L.c0 + L.c1;
-        const size_t per = L.wk_host.size() / L.cout;                 // index i = tap * Cin + ci
-        for (int co = 0; co < L.cout; ++co) {
-            float amax = 0.0f;
-            for (size_t i = 0; i < per; ++i)
-                amax = fmaxf(amax, fabsf(L.wk_host[i * L.cout + co]) * ((int)(i % Cin) >= L.c0 ? f1 : 1.0f));
-            if (amax > 0.0f && std::isfinite(amax)) { int e; frexpf(amax, &e); L.ws[co] = ldexpf(1.0f, 8 - e); }
-        }
-        panel = pack_conv3_panel_bf(L.wk_host, L.c0, L.c1, L.cout, 2, true, &L.ws, f1);
-    }
-    if (L.panel_bf[2] && panel.size() != L.panel_f16_floats) return set_error(OAI_ERR_ARG, "fp16 panel of layer %d changed size", k);
-    L.panel_f16_floats = panel.size();
-    L.rel1 = rel1;
-    if (int rc = upload_into(h, panel, &L.panel_bf[2])) return rc;
-    if (L.kind != 2) {                                               // the same terms in the order of the 16x16x32 tap pairs (conv3_igemm_sres<..., M16>)
-        const std::vector<float> p16 = pack_conv3_m16_panel(L.wk_host, L.c0, L.c1, L.cout, L.ws, f1);
-        if (L.panel_m16 && p16.size() != L.panel_m16_floats) return set_error(OAI_ERR_ARG, "16x16x32 panel of layer %d changed size", k);
-        L.panel_m16_floats = p16.size();
-        if (int rc = upload_into(h, p16, &L.panel_m16)) return rc;
-    }
-    return (h->opt_wino || L.panel_wino) ? pack_wino_layer(h, k) : OAI_OK;
-}
-
-// The fp16x3 epilogue arrays of every layer for the current activation exponents (see Layer::scale_f16).  ec0 reads the raw volume
-// (exponent 0) and has no panel; dc0 reads dc1's records and produces logits (exponent 0): its weights carry 2^-e(dc1).
-static int refresh_fp16_affine(oai_unet* h) {
-    for (int k = 0; k < 17; ++k) {
-        Layer& L = h->L[k];
-        const int e_out = h->act_exp[k], e_in = k == EC0 ? 0 : h->act_exp[layer_src0(k)];
-        std::vector<float> sc(L.cout), sh(L.cout);
-        for (int co = 0; co < L.cout; ++co) {
-            const float ws = L.ws.empty() ? 1.0f : L.ws[co];
-            sc[co] = ldexpf(L.scale_host[co] / ws, e_out - e_in);
-            sh[co] = ldexpf(L.shift_host[co], e_out);
-        }
-        if (int rc = upload_into(h, sc, &L.scale_f16)) return rc;
-        if (int rc = upload_into(h, sh, &L.shift_f16)) return rc;
-    }
-    Layer& H = h->L[DC0];
-    std::vector<float> w(H.plain_host.size());
-    for (size_t i = 0; i < w.size(); ++i) w[i] = ldexpf(H.plain_host[i], -h->act_exp[DC1]);
-    return upload_into(h, w, &H.plain_f16);
-}
-
-struct Box { int lo[3], hi[3]; };
-
-__host__ __device__ static void full_box(Box& b, const int dims[3]) { for (int i = 0; i < 3; ++i) { b.lo[i] = 0; b.hi[i] = dims[i]; } }
 
 // Output box each layer must produce so that the kept centre is unchanged (oracle/seg.py:trim_regions)
 __host__ __device__ static void plan_regions(const int tile[3], const int keep_lo[3], const int keep_hi[3], bool trimmed, Box need[18]) {
@@ -552,10 +55,9 @@ __host__ __device__ static void plan_regions(const int tile[3], const int keep_l
 constexpr int kMaxTilesPerTable = 4096;
 // The layers whose blocks sit on every tile's OWN cover (option "own_cover"): the trimmed decoder convs.  After the 18 box rows of a tile the table holds
 // three more rows per such layer, one per block shape (tile_cover): rows 18 + 3 slot + shape, addressed like the layers' own.
-constexpr int kOwnLayers = 5, kTableRows = 18 + 3 * kOwnLayers;
+constexpr int kTableRows = 18 + 3 * kOwnLayers;
 __host__ __device__ static inline int own_cover_slot(int k) { return k == DC8 ? 0 : k == DC7 ? 1 : k == DC5 ? 2 : k == DC4 ? 3 : k == DC2 ? 4 : -1; }
 constexpr int kOwnLayerOf[kOwnLayers] = {DC8, DC7, DC5, DC4, DC2};
-enum Buf { B_E0, B_SYN0, B_P0, B_E2, B_SYN1, B_P1, B_E4, B_SYN2, B_P2, B_E6, B_E7, B_U9, B_D8, B_D7, B_U6, B_D5, B_D4, B_U3, B_D2, B_D1, B_COUNT };
 
 // The workspace of one pass of `batch` tiles: the per-tile box table of the current oai_segment_tiles call at the start, then the activation
 // tensors.  Returns the bytes; over a null `base` the pointers are null and only the size counts (oai::Ws).
@@ -596,7 +98,7 @@ static size_t workspace_bytes(const oai_unet* h, int td, int th, int tw, int bat
 
 // One timed launch: with profiling on (oai_unet_profile) the kernel sits between a start / stop pair of the handle's event pool, which grows as needed and
 // is reused after every oai_unet_profile_read.  launch_begin before the launch; launch_end after it checks the launch and records the stop event.
-static int launch_begin(const oai_unet* h, hipStream_t st) {
+int launch_begin(const oai_unet* h, hipStream_t st) {
     if (!h->profile) return OAI_OK;
     oai_unet* hm = const_cast<oai_unet*>(h);
     while (hm->ev_used + 2 > hm->ev_pool.size()) {
@@ -607,7 +109,7 @@ static int launch_begin(const oai_unet* h, hipStream_t st) {
     OAI_CHECK_HIP(hipEventRecord(hm->ev_pool[hm->ev_used], st));
     return OAI_OK;
 }
-static int launch_end(const oai_unet* h, hipStream_t st) {
+int launch_end(const oai_unet* h, hipStream_t st) {
     OAI_CHECK_LAUNCH();
     if (!h->profile) return OAI_OK;
     oai_unet* hm = const_cast<oai_unet*>(h);
@@ -619,118 +121,20 @@ static int launch_end(const oai_unet* h, hipStream_t st) {
 // XCD-aware dealing of a launch's logical block list (xcd_block_id in the kernels): the kernel gets the number of real blocks and the grid is rounded up
 // to whole deals of xcd_group blocks to each of the 8 XCDs.  Option "xcd_group" 0: plain launch order, the grid as it is.
 // `group` > 0: this launch's own granularity (balanced_xcd_group) instead of the option's.
-static unsigned xcd_deal(const oai_unet* h, unsigned grid, int& nblocks, int& xcd_group, int group = 0) {
+unsigned xcd_deal(const oai_unet* h, unsigned grid, int& nblocks, int& xcd_group, int group) {
     if (h->xcd_group <= 0) return grid;
     nblocks = (int)grid; xcd_group = group > 0 ? group : h->xcd_group;
     const unsigned q = 8u * (unsigned)xcd_group;
     return (grid + q - 1) / q * q;
 }
 
-// per-layer accessors: a layer's index in the schedule, its bit of a layer mask (options "winograd_layers", "m16_layers"), its 16 census words (null: option
-// "census" 0 -- callers add their own h->sres condition)
-static inline int layer_id(const oai_unet* h, const Layer& L) { return (int)(&L - h->L); }
-static inline bool layer_bit(const oai_unet* h, int mask, const Layer& L) { return (mask >> layer_id(h, L)) & 1; }
-static inline unsigned* census_of(const oai_unet* h, int k) { return h->opt_census ? h->census + 16 * k : nullptr; }
 #ifdef OAI_DIAG
-static unsigned long long* layer_stamps(const oai_unet* h, const Layer& L) {     // OAI_STAMP_LAYER: one layer's budget (EC1 = 1 ..., DC9 = 8, DC6 = 11, DC3 = 14)
+unsigned long long* layer_stamps(const oai_unet* h, const Layer& L) {    // OAI_STAMP_LAYER: one layer's budget (EC1 = 1 ..., DC9 = 8, DC6 = 11, DC3 = 14)
     static const int only = diag_env("OAI_STAMP_LAYER", -1);
     return only >= 0 && layer_id(h, L) != only ? nullptr : diag_stamps();
 }
 #endif
 
-// the grid of an elementwise kernel: one thread per element in blocks of 256, at most `cap` blocks (the kernels walk the rest with a grid stride)
-static inline unsigned capped_blocks(size_t total, size_t cap) { return (unsigned)std::min<size_t>((total + 255) / 256, cap); }
-
-// conv3_igemm_sres2 in its variant `var`: 0 in the production library; -DOAI_DIAG builds also have the diagnostic variants 1..10 (OAI_WIDE_VAR)
-template <int RX, int RY, int WY, int WX, int V = 0>
-static void launch_sres2(int var, unsigned grid, hipStream_t st, const ConvArgs& a, const unsigned char* zero_rec) {
-#ifdef OAI_DIAG
-    if constexpr (V < 10)
-        if (var != V) return launch_sres2<RX, RY, WY, WX, V + 1>(var, grid, st, a, zero_rec);
-#endif
-    conv3_igemm_sres2<RX, RY, WY, WX, V><<<grid, 512, 0, st>>>(a, zero_rec);
-}
-
-template <int MREP, int KC, int RX, int RY, int WY, int WX>
-static int launch_conv3_shape(const oai_unet* h, ConvArgs a, const Box& box, int ntiles, hipStream_t st, int mrep_override = 0) {   // a.boxes set by the caller
-    for (int i = 0; i < 3; ++i) { a.lo[i] = box.lo[i]; a.hi[i] = box.hi[i]; }
-    if (box.hi[0] <= box.lo[0] || box.hi[1] <= box.lo[1] || box.hi[2] <= box.lo[2]) return OAI_OK;
-    // conv3_igemm_sres2 (unet_sres2.h): main shape of the default split-resident configuration, 128 couts per workgroup
-    // ... when the launch is at least four rounds of its one-workgroup-per-CU blocks (ec6 of the reference network: 2.5 rounds, 13 % slower
-    // than as twice as many 4-wave workgroups)
-    const int sres_mrep = mrep_override ? mrep_override : h->sres_mrep;       // z slices per block of the split-resident kernel for THIS launch
-    constexpr bool kMainShape = RX == 16 && RY == 2 && WY == 4 && WX == 1;
-    // + the 4-row y strip (dc5: 2.27 -> 1.89 ms); the 4-column x strip <4,8,4,1> measured slower there (2.05 -> 2.30 ms) and stays on the 4-wave kernel
-    constexpr bool kWideShape = kMainShape || (RX == 16 && RY == 2 && WY == 2 && WX == 2);
-    bool wide = KC == 8 && kWideShape && h->sres && h->opt_wide && sres_mrep == 4 && !a.first_w && !a.head_w && a.Cout % 128 == 0;
-    if (wide && h->opt_wide == 1) {
-        const size_t nwg = (size_t)ntiles * cdiv(box.hi[0] - box.lo[0], 4) * cdiv(box.hi[1] - box.lo[1], WY * RY) * cdiv(box.hi[2] - box.lo[2], WX * RX) * (a.Cout / 128);
-        wide = nwg >= (kMainShape ? 1024 : 512);
-    }
-    if (wide) a.ncb = a.Cout / 128;
-    const bool bf = KC == 8 && h->precision != OAI_PREC_F32;       // the split kernels use 2 z slices per block (4: split-resident)
-    // exact fp32: two z slices per block -- the registers of the other two hold the per-chunk partial sums of its two-level accumulation (conv3_igemm_f32)
-    constexpr int kF32Mrep = MREP > 2 ? 2 : MREP;
-    a.nbz = cdiv(box.hi[0] - box.lo[0], bf ? (h->sres ? sres_mrep : 2) : kF32Mrep);
-    a.nby = cdiv(box.hi[1] - box.lo[1], WY * RY);
-    a.nbx = cdiv(box.hi[2] - box.lo[2], WX * RX);
-    unsigned grid = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-    if (KC == 8 && h->sres) grid = xcd_deal(h, grid, a.nblocks, a.xcd_group);
-    if (int rc = launch_begin(h, st)) return rc;
-    if (KC == 8 && h->sres) {
-        // (diagnostic builds: OAI_ONE_WG=1 asks for 24 KB of unused dynamic LDS, which leaves room for ONE workgroup per CU -- the tap
-        // stream of a wave that has the SIMD to itself, scripts/stamp_phases.py)
-        static const int one_wg = diag_env("OAI_ONE_WG", 0);
-        bool done = false;
-        // the 16x16x32 tap pairs (option "m16"): a per-LAYER decision -- never for a layer that the bit-identical 128-cout form conv3_igemm_sres2 may
-        // take for some of its launches (that choice depends on the launch size) -- and every shape of the kernel has the variant
-        const bool m16 = h->opt_m16 && a.wpanel16 && a.Cout % 128 != 0 && !one_wg;
-        if (m16) a.wpanel = a.wpanel16;
-        if constexpr (RX == 16 && RY == 2 && WY == 4 && WX == 1) {
-            if (a.first_w) {                                         // ec0 fused into ec1's halo staging (first_fusable guarantees mrep 4, no strips)
-                if (m16) conv3_igemm_sres<4, RX, RY, WY, WX, true, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
-                else conv3_igemm_sres<4, RX, RY, WY, WX, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
-                done = true;
-            }
-        }
-        if constexpr (kWideShape) {
-            if (wide) {
-                static const int var = diag_env("OAI_WIDE_VAR", 0);         // -DOAI_DIAG builds only; constant 0 otherwise
-                launch_sres2<RX, RY, WY, WX>(var >= 1 && var <= 10 ? var : 0, grid, st, a, h->zero_rec);
-                done = true;
-            }
-        }
-        if (done) { }
-        else if (a.first_w) return set_error(OAI_ERR_ARG, "fused ec0 asked of a tile shape that has no such kernel");
-        else if (m16 && sres_mrep == 4) conv3_igemm_sres<4, RX, RY, WY, WX, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
-        else if (m16) conv3_igemm_sres<2, RX, RY, WY, WX, false, true><<<grid, 256, 0, st>>>(a, h->zero_rec);
-        else if (sres_mrep == 4) conv3_igemm_sres<4, RX, RY, WY, WX><<<grid, 256, one_wg ? 24 * 1024 : 0, st>>>(a, h->zero_rec);
-        else conv3_igemm_sres<2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a, h->zero_rec);
-    }
-    else if (KC == 8 && h->precision == OAI_PREC_BF16X3) conv3_igemm_bf16s<2, false, 2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
-    else if (KC == 8 && h->precision == OAI_PREC_BF16X6) conv3_igemm_bf16s<3, false, 2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
-    else if (KC == 8 && h->precision == OAI_PREC_FP16X3) conv3_igemm_bf16s<2, true, 2, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
-    else conv3_igemm_f32<kF32Mrep, KC, RX, RY, WY, WX><<<grid, 256, 0, st>>>(a);
-    return launch_end(h, st);
-}
-
-// One conv layer = the main launch over the part of the output box that 8 x `xunit` (y, x) tiles cover exactly, plus up to two thin remainder
-// strips computed with tile shapes that fit them (trimmed boxes are e.g. 18 x 98 x 98): the x strip = all y rows, the last wr columns; the y strip =
-// the last hr rows, main columns only.  A remainder of more than tall_y rows / tall_x columns is cheaper as one more row / column of main tiles.
-// hr == wr == 0: the main launch covers the whole box (also when the box is smaller than one main tile in y or x, or `no_strips`).
-struct Cover { Box main, xs, ys; int hr, wr; };
-__host__ __device__ static Cover cover_box(const Box& box, int xunit, int tall_y, int tall_x, bool no_strips) {
-    const int ry = box.hi[1] - box.lo[1], rx = box.hi[2] - box.lo[2], ny = ry / 8, nx = rx / xunit;
-    Cover c{box, box, box, ry - 8 * ny, rx - xunit * nx};
-    if (no_strips || ny == 0 || nx == 0) c.hr = c.wr = 0;
-    if (c.hr > tall_y) c.hr = 0;
-    if (c.wr > tall_x) c.wr = 0;
-    if (c.hr) c.main.hi[1] = box.lo[1] + 8 * ny;
-    if (c.wr) c.main.hi[2] = box.lo[2] + xunit * nx;
-    c.xs.lo[2] = c.main.hi[2];
-    c.ys.lo[1] = c.main.hi[1]; c.ys.hi[2] = c.main.hi[2];
-    return c;
-}
 // The cover of ONE tile's own box by the shapes of launch_conv3_wino (option "own_cover"): piece[0] main blocks of 8 x 8, piece[1] the x strip (16 x 4),
 // piece[2] the y strip (4 x 16) -- cover_box's rules on the box with its x start rounded down to even, which is where the tile's blocks start; the
 // pieces themselves keep the true start, are disjoint and make up the box; a piece may be empty.  Host (grid sizes, oai_unet_cover_stats) and device
@@ -743,7 +147,6 @@ __host__ __device__ static void tile_cover(const Box& box, Box piece[3]) {
     piece[0].lo[2] = piece[2].lo[2] = box.lo[2];
 }
 constexpr int kWinoTY[3] = {8, 16, 4}, kWinoTX[3] = {8, 4, 16};         // the block shapes of the three pieces (4 z slices each)
-__host__ __device__ static inline bool box_empty(const Box& b) { return b.hi[0] <= b.lo[0] || b.hi[1] <= b.lo[1] || b.hi[2] <= b.lo[2]; }
 // blocks of shape `s` that piece `p` of a tile takes from its own origin (0 0 0: empty piece)
 __host__ __device__ static void piece_blocks(const Box& p, int s, int nb[3]) {
     nb[0] = nb[1] = nb[2] = 0;
@@ -751,11 +154,6 @@ __host__ __device__ static void piece_blocks(const Box& p, int s, int nb[3]) {
     const int ty = s == 0 ? 8 : s == 1 ? 16 : 4, tx = s == 0 ? 8 : s == 1 ? 4 : 16;      // (kWinoTY / kWinoTX: host arrays)
     nb[0] = (p.hi[0] - p.lo[0] + 3) / 4; nb[1] = (p.hi[1] - p.lo[1] + ty - 1) / ty; nb[2] = (p.hi[2] - (p.lo[2] & ~1) + tx - 1) / tx;
 }
-// what run_batch needs of the host's walk over a batch's tiles for option "own_cover": the grid of every shape of every own-cover layer (the largest
-// block counts of any tile, per axis), the largest input box of every up-conv in voxels, and every tile's own block counts [tile][slot][shape][3]
-// (all 0 for a dead tile), from which balanced_xcd_group deals a launch
-// list / list_len (option "one_launch"): the device lists of the layers that run as one launch for this batch, 0 entries = three launches (one_launch_len)
-struct OwnPlan { int nb[kOwnLayers][3][3]; int up_nvox[18]; std::vector<int> tile_nb; const unsigned* list[kOwnLayers]; int list_len[kOwnLayers]; };
 constexpr int kTileNbStride = kOwnLayers * 3 * 3;
 static void own_plan_add(OwnPlan& op, const Box need[18]) {
     const size_t row = op.tile_nb.size();
@@ -778,14 +176,11 @@ static void own_plan_add(OwnPlan& op, const Box need[18]) {
         }
     }
 }
-// one own-cover layer of one batch, as launch_conv3_wino takes it: the device rows of the three pieces, their grids and XCD dealing granularities (0: the option's)
-// `list` (option "one_launch"): the layer's live-block list on the device and its length, or null / 0 = one launch per shape
-struct OwnCover { const int* rows[3]; int nb[3][3]; int xcd_group[3]; const unsigned* list; int list_len; };
 
 // ---- option "one_launch": the live-block list of an own-cover layer (unet_wino.h: conv3_wino_list*)
 // Entries of layer `slot` for a batch whose tiles' block counts are `tile_nb` (OwnPlan): every live block of every piece once -- or 0 where a field does
 // not fit the entry format (wino_list_entry) or the list its room in the workspace: that batch keeps its three launches.
-static int block_list_len(const int* tile_nb, int ntiles, int slot, size_t capacity) {
+int block_list_len(const int* tile_nb, int ntiles, int slot, size_t capacity) {
     if (ntiles > (1 << kWinoListTileBits)) return 0;
     long long len = 0;
     for (int t = 0; t < ntiles; ++t)
@@ -893,39 +288,21 @@ static int balanced_xcd_group(int configured, const int* tile_nb, int ntiles, co
     return best;
 }
 
-// the cover of the direct kernels (launch_conv3): main tiles of 8 x 16
-static Cover direct_cover(const oai_unet* h, const Box& box) { return cover_box(box, 16, 4, 8, h->variant == 2); }
-
-// what fusing ec0 into ec1 asks of the configuration: the default split-resident kernel and the reference's channel counts (1 -> 32 -> ...)
-static bool first_fusion_ok(const oai_unet* h) {
-    return h->sres && h->fuse_first && h->variant == 0 && h->sres_mrep == 4 && h->L[EC0].cout == 32 && h->L[EC1].c0 == 32;
-}
-// ec0 can be computed inside ec1's halo staging (conv3_igemm_sres<..., FIRST>) when ec1 runs as ONE launch of the main shape
-static bool first_fusable(const oai_unet* h, const Box& ec1_box) {
-    if (!first_fusion_ok(h)) return false;
-    const Cover c = direct_cover(h, ec1_box);
-    return c.hr == 0 && c.wr == 0;
-}
-
-// shared encoder pass: where the copy-out of the volume-wide ec1 scatters its voxels (ConvArgs::sc_*)
-struct Scatter { const int* boxes; int ntiles, tile0; int g[3], e[3], t[3]; };
 
 // everything of ConvArgs that does not depend on the tile shape
-static int fill_conv_args(const oai_unet* h, const Layer& L, const float* s0, const float* s1, float* out, const int dims[3],
-                          const int* boxes, float* pool_out, const ConvArgs* head, const TileSource* first, const int* store_boxes,
-                          const Scatter* sc, ConvArgs& a) {
-    if (head) a = *head;                   // the fused dc0 fields (see ConvArgs); everything else is set below
-    if (store_boxes && h->sres && h->opt_dead_stores) { a.store_boxes = store_boxes; a.store_grow = 1; }
-    if (first) {                           // ec0 fused into this layer's staging (first_fusable)
-        a.first_w = h->L[EC0].plain; a.first_scale = h->L[EC0].scale_f16; a.first_shift = h->L[EC0].shift_f16; a.first_src = *first;   // (sres => fp16x3)
+int fill_conv_args(const oai_unet* h, const Layer& L, const float* s0, const float* s1, float* out, const int dims[3], const ConvOpt& o, ConvArgs& a) {
+    if (o.head) a = *o.head;               // the fused dc0 fields (see ConvArgs); everything else is set below
+    if (o.store_boxes && h->sres && h->opt_dead_stores) { a.store_boxes = o.store_boxes; a.store_grow = 1; }
+    if (o.first) {                         // ec0 fused into this layer's staging (first_fusable)
+        a.first_w = h->L[EC0].plain; a.first_scale = h->L[EC0].scale_f16; a.first_shift = h->L[EC0].shift_f16; a.first_src = *o.first;   // (sres => fp16x3)
         a.first_census = census_of(h, EC0);
     }
-    if (sc) {
+    if (const Scatter* sc = o.sc) {
         a.sc_boxes = sc->boxes; a.sc_ntiles = sc->ntiles; a.sc_tile0 = sc->tile0;
         for (int i = 0; i < 3; ++i) { a.sc_g[i] = sc->g[i]; a.sc_e[i] = sc->e[i]; a.sc_t[i] = sc->t[i]; }
     }
-    a.boxes = boxes;
-    a.pool_out = pool_out;
+    a.boxes = o.boxes;
+    a.pool_out = o.pool_out;
     a.range_flag = h->range_flag;
 #ifdef OAI_DIAG
     a.stamps = layer_stamps(h, L);
@@ -944,244 +321,19 @@ static int fill_conv_args(const oai_unet* h, const Layer& L, const float* s0, co
     return OAI_OK;
 }
 
-// one launch of ONE given tile shape over `box` (the faces of the per-tile shell pass, where launch_conv3's main + strips cover does not fit)
-// `pool_only` (main shape): the max-pooled tensor is all this launch leaves behind -- fused pool into pool_only, 2 z slices per block (both
-// slices of a block are then inside the 2-voxel face), the copy-out of the layer's own output suppressed through an empty store box
-template <int RX, int RY, int WY, int WX>
-static int launch_conv3_one(const oai_unet* h, const Layer& L, const float* s0, float* out, const int dims[3], const Box& box, int ntiles,
-                            hipStream_t st, const int* boxes, float* pool_only = nullptr) {
-    ConvArgs a;
-    if (int rc = fill_conv_args(h, L, s0, nullptr, out, dims, boxes, pool_only, nullptr, nullptr, nullptr, nullptr, a)) return rc;
-    if (pool_only) { a.store_boxes = boxes; a.store_grow = -(1 << 20); }          // consumer box "grown" by -2^20: nothing of the output tensor is written
-    return launch_conv3_shape<4, 8, RX, RY, WY, WX>(h, a, box, ntiles, st, pool_only ? 2 : 0);
-}
-
-// The specialised 64-cout form takes ALL of a CU's LDS (160 KB): asked once whether a workgroup of it (both block shapes, both tap forms) fits this
-// device / driver at all
-static bool wino_ws_fits() {
-    static const bool fits = [] {
-        auto one = [](auto kern) { int n = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 512, 0) == hipSuccess && n >= 1; };
-        return one(conv3_wino_sres<1, 8, 4, 1, true>) && one(conv3_wino_sres<1, 16, 2, 1, true>) &&
-               one(conv3_wino_sres<1, 8, 4, 1, true, true>) && one(conv3_wino_sres<1, 16, 2, 1, true, true>);
-    }();
-    return fits;
-}
-// a 64-cout layer on the 16x16x32 taps (option "winograd" bit 5): its main blocks and x strip run the specialised form's tap-pair variant, its y strip
-// the slice-split form's -- ALL its launch shapes or none: a voxel's bits must not depend on which shape covers it
-static bool wino_m16_64(const oai_unet* h, const Layer& L, int cout) {
-    return cout % 128 != 0 && (h->opt_wino & 32) && !(h->opt_wino & (4 | 8)) && L.panel_wino16 && wino_ws_fits();
-}
-
-// cout groups of 64 per workgroup of conv3_wino_sres for a layer and a block height
-static inline int wino_groups(const oai_unet* h, int cout, int TY) {
-    return (cout % 128 == 0 && !((h->opt_wino & 8) && TY != 4)) ? 2 : 1;      // (bit 3, A/B: the specialised 64-cout form for every layer)
-}
-// One launch of conv3_wino_sres (unet_wino.h) with blocks of 4 x TY x 2 NP over `box` (box.lo[2] even)
-template <int TY, int NP>
-static int launch_wino_shape(const oai_unet* h, const Layer& L, ConvArgs a, const Box& box, int ntiles, hipStream_t st, const int* own_nb = nullptr, int own_group = 0) {
-    for (int i = 0; i < 3; ++i) { a.lo[i] = box.lo[i]; a.hi[i] = box.hi[i]; }
-    if (box.hi[0] <= box.lo[0] || box.hi[1] <= box.lo[1] || box.hi[2] <= box.lo[2]) return OAI_OK;
-    a.own_origin = own_nb != nullptr;                                  // (own_nb: a.boxes = one piece of every tile's own cover, the grid counted from each row's start)
-    const int ng = wino_groups(h, a.Cout, TY);
-    a.wpanel = L.panel_wino;
-    a.ncb = a.Cout / (64 * ng);
-    a.nbz = cdiv(box.hi[0] - box.lo[0], 4); a.nby = cdiv(box.hi[1] - box.lo[1], TY); a.nbx = cdiv(box.hi[2] - box.lo[2], 2 * NP);
-    if (own_nb) { a.nbz = own_nb[0]; a.nby = own_nb[1]; a.nbx = own_nb[2]; }
-    unsigned grid = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-    grid = xcd_deal(h, grid, a.nblocks, a.xcd_group, own_group);
-    if (int rc = launch_begin(h, st)) return rc;
-    if (ng == 2 && (h->opt_wino & 16) && L.panel_wino16) {              // the taps on v_mfma_f32_16x16x32_f16 (higher clock at the power wall)
-        a.wpanel = L.panel_wino16;
-        conv3_wino_sres<2, TY, NP, 1, false, true><<<grid, 512, 0, st>>>(a, h->zero_rec);
-    } else if (ng == 2) conv3_wino_sres<2, TY, NP><<<grid, 512, 0, st>>>(a, h->zero_rec);
-    else if constexpr (TY != 4) {
-        if ((h->opt_wino & 4) || !wino_ws_fits()) conv3_wino_sres<1, TY, NP, 2><<<grid, 512, 0, st>>>(a, h->zero_rec);        // (A/B, or no room: the eight waves split the z slices)
-        else if (wino_m16_64(h, L, a.Cout)) {                                                          // the multipliers' taps on v_mfma_f32_16x16x32_f16
-            a.wpanel = L.panel_wino16;
-            conv3_wino_sres<1, TY, NP, 1, true, true><<<grid, 512, 0, st>>>(a, h->zero_rec);
-        } else conv3_wino_sres<1, TY, NP, 1, true><<<grid, 512, 0, st>>>(a, h->zero_rec);              // one block of 64 couts: four waves multiply, four stage
-    } else if (wino_m16_64(h, L, a.Cout)) {                                          // (the y strip's two T buffers would not fit: the eight waves split the z slices --
-        a.wpanel = L.panel_wino16;                                                     //  on the same tap pairs as the layer's other shapes: one summation order per layer)
-        conv3_wino_sres<1, TY, NP, 2, false, true><<<grid, 512, 0, st>>>(a, h->zero_rec);
-    } else conv3_wino_sres<1, TY, NP, 2><<<grid, 512, 0, st>>>(a, h->zero_rec);
-    return launch_end(h, st);
-}
-
-// Which one-launch kernel an own-cover layer takes (option "one_launch"): 1 = conv3_wino_list2 (two cout groups), 2 = conv3_wino_list1 (one block of 64
-// couts), 0 = none -- the option's bit is off, or the configuration gives the layer's shapes kernels that these two do not combine (the A/B bits 2 and 3
-// of option "winograd", no room for the specialised form)
-static int one_launch_family(const oai_unet* h, const Layer& L) {
-    if (L.cout % 128 == 0) return (h->opt_one_launch & 1) && !(h->opt_wino & 8) ? 1 : 0;
-    return (h->opt_one_launch & 2) && L.cout % 64 == 0 && !(h->opt_wino & 4) && wino_ws_fits() ? 2 : 0;
-}
-// The size gate of option "one_launch": the entries of the layer's list, or 0 = three launches for this batch.  Without the force bit a layer runs as one
-// launch only when its live blocks number at least the device's CUs: below that the three launches are not even one round of the chip and there is no tail
-// to save -- and the launch structure of small batches is pinned by the tests (tests/test_unet_gpu.py counts the timed launches of batches of 9 tiles).
-// Small batches are not what the library is timed on.
-static int one_launch_len(const oai_unet* h, const int* tile_nb, int ntiles, int slot, size_t capacity) {
-    static const int cus = [] { int dev = 0, n = 0; return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? n : 1 << 30; }();
-    const int len = block_list_len(tile_nb, ntiles, slot, capacity);
-    return (h->opt_one_launch & 4) || len >= cus ? len : 0;
-}
-// One own-cover layer as ONE launch of conv3_wino_list2 / conv3_wino_list1 over its live-block list (option "one_launch"; unet_wino.h says what the kernels
-// read of ConvArgs); `level` = the whole level, as for the three launches.  One launch = one start / stop pair of oai_unet_profile.
-static int launch_wino_list(const oai_unet* h, const Layer& L, ConvArgs a, const Box& level, hipStream_t st, const OwnCover& oc, int family) {
-    for (int i = 0; i < 3; ++i) { a.lo[i] = level.lo[i]; a.hi[i] = level.hi[i]; }
-    a.own_origin = 1;
-    a.boxes = oc.rows[0]; a.nbz = (int)(oc.rows[1] - oc.rows[0]); a.nby = a.nbx = 0;      // the piece rows of the three shapes are equally spaced table rows
-    a.reserved1 = reinterpret_cast<int*>(const_cast<unsigned*>(oc.list));
-    a.ncb = a.Cout / (family == 1 ? 128 : 64);
-    const unsigned grid = xcd_deal(h, (unsigned)((size_t)oc.list_len * a.ncb), a.nblocks, a.xcd_group);      // only live blocks are dealt: the option's granularity balances
-    const bool m16 = family == 1 ? (h->opt_wino & 16) && L.panel_wino16 : wino_m16_64(h, L, a.Cout);          // (the tap form that launch_wino_shape picks for the layer)
-    a.wpanel = m16 ? L.panel_wino16 : L.panel_wino;
-    if (int rc = launch_begin(h, st)) return rc;
-    if (family == 1) {
-        if (m16) conv3_wino_list2<true><<<grid, 512, 0, st>>>(a, h->zero_rec);
-        else conv3_wino_list2<false><<<grid, 512, 0, st>>>(a, h->zero_rec);
-    } else {
-        if (m16) conv3_wino_list1<true><<<grid, 512, 0, st>>>(a, h->zero_rec);
-        else conv3_wino_list1<false><<<grid, 512, 0, st>>>(a, h->zero_rec);
-    }
-    return launch_end(h, st);
-}
-
-// A plain layer (no fused ec0 / pool / head / scatter) of the default split-resident configuration through conv3_wino_sres: main blocks of
-// 4 x 8 x 8, a y strip of 4 x 4 x 16 blocks for a remainder of <= 4 rows, an x strip of 4 x 16 x 4 blocks for a remainder of <= 4 columns
-// .  The box starts at an even x: an output's arithmetic depends on the
-// parity of its x only -- not on which launch or block computes it.
-// `oc` (option "own_cover"; the trimmed decoder layers of oai_segment_tiles): the same three shapes, one launch each, over every tile's OWN cover
-// (tile_cover) instead of the cover of the batch's union box: a border tile's blocks start at its own corner, and its own remainders decide its
-// strips.  The launch box is the whole level; a shape that no tile of the batch needs is not launched.  Same bits.  With a live-block list (option
-// "one_launch") the three launches are one: launch_wino_list.
-static int launch_conv3_wino(const oai_unet* h, const Layer& L, const ConvArgs& a, Box box, int ntiles, hipStream_t st, const OwnCover* oc = nullptr) {
-    if (oc && a.boxes) {
-        const int dims[3] = {a.D, a.H, a.W};
-        Box level;
-        full_box(level, dims);
-        if (oc->list_len > 0)
-            if (const int family = one_launch_family(h, L)) return launch_wino_list(h, L, a, level, st, *oc, family);
-        ConvArgs b = a;
-        for (int s = 0; s < 3; ++s) {
-            if (oc->nb[s][0] == 0) continue;
-            b.boxes = oc->rows[s];
-            const int rc = s == 0 ? launch_wino_shape<8, 4>(h, L, b, level, ntiles, st, oc->nb[s], oc->xcd_group[s])
-                         : s == 1 ? launch_wino_shape<16, 2>(h, L, b, level, ntiles, st, oc->nb[s], oc->xcd_group[s])
-                                  : launch_wino_shape<4, 8>(h, L, b, level, ntiles, st, oc->nb[s], oc->xcd_group[s]);
-            if (rc) return rc;
-        }
-        return OAI_OK;
-    }
-    box.lo[2] &= ~1;
-    const Cover c = cover_box(box, 8, 4, 4, false);
-    if (int rc = launch_wino_shape<8, 4>(h, L, a, c.main, ntiles, st)) return rc;
-    if (c.wr)
-        if (int rc = launch_wino_shape<16, 2>(h, L, a, c.xs, ntiles, st)) return rc;
-    if (c.hr)
-        if (int rc = launch_wino_shape<4, 8>(h, L, a, c.ys, ntiles, st)) return rc;
-    return OAI_OK;
-}
-
-// the fused max-pool of conv3_wino_sres pools whole 2 x 2 x 2 windows of a block's own image: the box must be the whole (even-sized) tile
-// level, so that every block (any shape) starts at even coordinates and lies inside it
-static bool wino_pool_box(const Box& box, const int dims[3]) {
-    for (int i = 0; i < 3; ++i)
-        if (box.lo[i] != 0 || box.hi[i] != dims[i] || (dims[i] & 1)) return false;
-    return dims[0] % 4 == 0 && dims[1] % 8 == 0 && dims[2] % 8 == 0;      // main blocks only: no strips
-}
-
-// One launch of conv3_wino_f32 (unet_wino_f32.h) with blocks of 2 x TY x 2 NP over `box` (box.lo[2] even)
-template <int TY, int NP>
-static int launch_wino_f32_shape(const oai_unet* h, const Layer& L, ConvArgs a, const Box& box, int ntiles, hipStream_t st) {
-    for (int i = 0; i < 3; ++i) { a.lo[i] = box.lo[i]; a.hi[i] = box.hi[i]; }
-    if (box.hi[0] <= box.lo[0] || box.hi[1] <= box.lo[1] || box.hi[2] <= box.lo[2]) return OAI_OK;
-    a.wpanel = L.panel_wino_f32;
-    a.ncb = (a.Cout + 63) / 64;
-    a.nbz = cdiv(box.hi[0] - box.lo[0], 2); a.nby = cdiv(box.hi[1] - box.lo[1], TY); a.nbx = cdiv(box.hi[2] - box.lo[2], 2 * NP);
-    unsigned grid = (unsigned)((size_t)ntiles * a.nbz * a.nby * a.nbx * a.ncb);
-    grid = xcd_deal(h, grid, a.nblocks, a.xcd_group);         // (as the split-resident kernels)
-    if (int rc = launch_begin(h, st)) return rc;
-    conv3_wino_f32<TY, NP><<<grid, 256, 0, st>>>(a, reinterpret_cast<const float*>(h->zero_rec));
-    return launch_end(h, st);
-}
-
-// The exact-fp32 path's k3 layers through conv3_wino_f32: main blocks of 2 x 8 x 8, a y strip of 2 x 4 x 16 blocks for a remainder of <= 4 rows, an x strip
-// of 2 x 16 x 4 blocks for a remainder of <= 4 columns (the cover of launch_conv3_wino).  The box starts at an even x: an output's arithmetic depends on the
-// parity of its x only -- not on which launch or block computes it.  A fused MaxPool3d(2) rides in the main blocks (the host passes it for whole-tile boxes only).
-static int launch_conv3_wino_f32(const oai_unet* h, const Layer& L, const ConvArgs& a, Box box, int ntiles, hipStream_t st) {
-    box.lo[2] &= ~1;
-    const Cover c = cover_box(box, 8, 4, 4, a.pool_out != nullptr);
-    if (int rc = launch_wino_f32_shape<8, 4>(h, L, a, c.main, ntiles, st)) return rc;
-    if (c.wr)
-        if (int rc = launch_wino_f32_shape<16, 2>(h, L, a, c.xs, ntiles, st)) return rc;
-    if (c.hr)
-        if (int rc = launch_wino_f32_shape<4, 8>(h, L, a, c.ys, ntiles, st)) return rc;
-    return OAI_OK;
-}
-
+// One k3 conv layer: fills its arguments and picks the kernel family that runs it -- Winograd in exact fp32 (unet_wino.hip), Winograd split-resident
+// (the same file), or the direct kernels (unet_direct.hip), which take whatever the first two leave
 static int launch_conv3(const oai_unet* h, const Layer& L, const float* s0, const float* s1, float* out,
-                        const int dims[3], const Box& box, int ntiles, hipStream_t st, const int* boxes = nullptr,
-                        float* pool_out = nullptr, const ConvArgs* head = nullptr, const TileSource* first = nullptr,
-                        const int* store_boxes = nullptr, const Scatter* sc = nullptr, const OwnCover* oc = nullptr) {
+                        const int dims[3], const Box& box, int ntiles, hipStream_t st, const ConvOpt& o = {}) {
     ConvArgs a;
-    if (int rc = fill_conv_args(h, L, s0, s1, out, dims, boxes, pool_out, head, first, store_boxes, sc, a)) return rc;
-    if (h->variant == 1) return launch_conv3_shape<2, 16, 16, 2, 4, 1>(h, a, box, ntiles, st);
+    if (int rc = fill_conv_args(h, L, s0, s1, out, dims, o, a)) return rc;
     if (h->precision == OAI_PREC_F32 && h->variant == 0 && h->opt_wino_f32 && L.panel_wino_f32 && a.Cout % 4 == 0 && !a.head_w && !a.first_w && !a.sc_boxes &&
         (!a.pool_out || (wino_pool_box(box, dims) && dims[0] % 2 == 0)) && layer_bit(h, h->opt_wino_layers, L))
         return launch_conv3_wino_f32(h, L, a, box, ntiles, st);
     if (h->sres && h->opt_wino && L.panel_wino && h->sres_mrep == 4 && !a.first_w && !a.head_w && !a.sc_boxes &&
         (!a.pool_out || (a.Cout % 128 == 0 && a.relu && wino_pool_box(box, dims))) && a.Cout % 64 == 0 && (h->opt_wino & (a.Cout % 128 == 0 ? 1 : 2)) && (a.Cout % 128 == 0 || (a.C0 + 15) / 16 + (a.C1 + 15) / 16 >= 8) && layer_bit(h, h->opt_wino_layers, L) && (size_t)dims[0] * dims[1] * dims[2] < (1u << 24))
-        return launch_conv3_wino(h, L, a, box, ntiles, st, oc);
-    const Cover c = direct_cover(h, box);
-    if (int rc = launch_conv3_shape<4, 8, 16, 2, 4, 1>(h, a, c.main, ntiles, st)) return rc;
-    if (c.wr) {
-        const int rc = c.wr <= 2 ? launch_conv3_shape<4, 8, 2, 16, 4, 1>(h, a, c.xs, ntiles, st)
-                     : c.wr <= 4 ? launch_conv3_shape<4, 8, 4, 8, 4, 1>(h, a, c.xs, ntiles, st)
-                                 : launch_conv3_shape<4, 8, 8, 4, 4, 1>(h, a, c.xs, ntiles, st);
-        if (rc) return rc;
-    }
-    if (!c.hr) return OAI_OK;
-    return c.hr <= 2 ? launch_conv3_shape<4, 8, 16, 2, 1, 4>(h, a, c.ys, ntiles, st) : launch_conv3_shape<4, 8, 16, 2, 2, 2>(h, a, c.ys, ntiles, st);
-}
-
-static int launch_up(const oai_unet* h, const Layer& L, const float* src, float* out, const int in_dims[3], const Box& out_need,
-                     int ntiles, hipStream_t st, const int* in_boxes = nullptr, int own_nvox = 0) {
-    UpArgs a;
-    a.boxes = in_boxes;
-    a.range_flag = h->range_flag;
-    a.zero = h->zero_rec;
-#ifdef OAI_DIAG
-    a.stamps = layer_stamps(h, L);
-#endif
-    const bool split = h->precision == OAI_PREC_FP16X3 && L.panel_bf[2];
-    a.src = src; a.Cin = L.cin; a.out = out; a.Cout = L.cout;
-    a.wpanel = split ? L.panel_bf[2] : L.panel;
-    a.scale = split ? L.scale_f16 : L.scale;
-    a.shift = split ? L.shift_f16 : L.shift;
-    a.census = h->sres ? census_of(h, layer_id(h, L)) : nullptr;
-    a.D = in_dims[0]; a.H = in_dims[1]; a.W = in_dims[2];
-    for (int i = 0; i < 3; ++i) { a.lo[i] = out_need.lo[i] / 2; a.hi[i] = (out_need.hi[i] + 1) / 2; }
-    const int nvox = (a.hi[0] - a.lo[0]) * (a.hi[1] - a.lo[1]) * (a.hi[2] - a.lo[2]);
-    a.nmb = cdiv(nvox, split && h->sres ? 128 : 64);       // voxels per workgroup: 128 in the split-resident kernel
-    a.nnb = cdiv(8 * L.cout, 256);
-    a.relu = 1;
-    if (split && h->sres) {
-        // option "own_cover": a tile's workgroups list the voxels of its own input box -- as many row blocks as the batch's largest tile box has
-        if (own_nvox > 0 && in_boxes) { a.own_box = 1; a.nmb = cdiv(own_nvox, 128); }
-        // column blocks per workgroup (round 6): as many as leave >= 16 workgroups per workgroup slot of the chip (256 CUs x 2); narrow test networks
-        // (the dword-store path of the kernel) keep one; option "up_nbw": 0 = this rule, n = at most n
-        a.nbw = 1;
-        if (L.cout % 16 == 0 && h->opt_up_nbw > 1) a.nbw = std::min(h->opt_up_nbw, a.nnb);
-        else if (L.cout % 16 == 0 && h->opt_up_nbw == 0) {
-            a.nbw = a.nnb;
-            while (a.nbw > 1 && (size_t)ntiles * a.nmb * cdiv(a.nnb, a.nbw) < 8192) a.nbw = (a.nbw + 1) / 2;
-        }
-        const unsigned grid = xcd_deal(h, (unsigned)((size_t)ntiles * a.nmb * cdiv(a.nnb, a.nbw)), a.nblocks, a.xcd_group);   // same dealing as the conv kernels'
-        upconv2_igemm_sres<<<grid, 256, 0, st>>>(a);
-    }
-    else if (split) upconv2_igemm<true><<<(unsigned)((size_t)ntiles * a.nmb * a.nnb), 256, 0, st>>>(a);
-    else upconv2_igemm<false><<<(unsigned)((size_t)ntiles * a.nmb * a.nnb), 256, 0, st>>>(a);
-    OAI_CHECK_LAUNCH();
-    return OAI_OK;
+        return launch_conv3_wino(h, L, a, box, ntiles, st, o.oc);
+    return launch_conv3_direct(h, a, box, ntiles, st);
 }
 
 // MaxPool3d(2) can ride in the conv epilogue when the (full) box is tiled exactly by the main 4 x 8 x 16 shape
@@ -1189,23 +341,6 @@ static bool pool_fusable(const oai_unet* h, const int dims[3], const Box& box) {
     if (h->variant != 0) return false;
     for (int i = 0; i < 3; ++i) if (box.lo[i] != 0 || box.hi[i] != dims[i]) return false;
     return dims[0] % 4 == 0 && dims[1] % 8 == 0 && dims[2] % 16 == 0;
-}
-
-static int launch_pool(const oai_unet* h, const float* in, float* out, const int dims[3], int C, int ntiles, hipStream_t st, int shell_only = 0) {
-    if (h->sres) {
-        const int nch = (C + 15) / 16;
-        const size_t Do = dims[0] / 2, Ho = dims[1] / 2, Wo = dims[2] / 2;
-        const size_t faces = Do * Ho * Wo - (Do - 2) * (Ho - 2) * (Wo - 2) - (shell_only == 2 ? 2 * Ho * Wo : 0);
-        const size_t total = (size_t)ntiles * (shell_only ? faces : Do * Ho * Wo) * nch * 4;
-        maxpool2_sres_kernel<<<capped_blocks(total, 256 * 32), 256, 0, st>>>(reinterpret_cast<const unsigned char*>(in), reinterpret_cast<unsigned char*>(out),
-                                                                dims[0], dims[1], dims[2], nch, total, shell_only);
-        OAI_CHECK_LAUNCH();
-        return OAI_OK;
-    }
-    const size_t total4 = (size_t)ntiles * (dims[0] / 2) * (dims[1] / 2) * (dims[2] / 2) * (C / 4);
-    maxpool2_kernel<<<capped_blocks(total4, 256 * 32), 256, 0, st>>>(in, out, dims[0], dims[1], dims[2], C, total4);
-    OAI_CHECK_LAUNCH();
-    return OAI_OK;
 }
 
 // Shared encoder pass.  Tiles overlap 2 x in z and 1.33 x in y and x, so ec0 / ec1 evaluate every input voxel ~3.6 x.  An ec1
@@ -1216,12 +351,6 @@ static int launch_pool(const oai_unet* h, const float* in, float* out, const int
 // whose dc2 reads it (the skip read [need - 1, need + 1) lies inside the interior).  Per tile only the 2-voxel shell of ec1 is recomputed
 // (ec0 on a 3-voxel shell, six thin face launches, the pooled faces) and the interior of the tile's pooled tensor is copied out of SP0.
 // ec1 is 22 ms of a 169 ms volume at 0.167 of the MFMA peak; the shared pass takes 8.7 ms.
-struct SharedEnc {
-    float* SP0;                         // [cout / 16 chunks][PD / 2][PH / 2][PW / 2]: the max-pooled ec1 of the padded volume
-    int PD, PH, PW;                     // reflect-padded volume = eff * grid + 2 * overlap
-    const float* vol; int D, H, W;      // the volume itself (the pass gathers it with Partition's reflect padding)
-    int grid[3], eff[3], overlap[3];
-};
 
 // One batch of `n` tiles through the whole network; kept-centre blocks go to blocks_out.
 // `table` (device, may be null) = per-tile boxes [layer][table_tiles][6] of the whole call; this batch starts at tile
@@ -1249,7 +378,6 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
     const Layer* L = h->L;
     int d[4][3];
     for (int l = 0; l < 4; ++l) { d[l][0] = src.td >> l; d[l][1] = src.th >> l; d[l][2] = src.tw >> l; }
-    const size_t v0 = (size_t)src.td * src.th * src.tw;
 
     int rc;
 #define RUN(x) do { rc = (x); if (rc) return rc; } while (0)
@@ -1293,26 +421,14 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
                     prev.hi[0] = bx.hi[0];                                      // same footprint as the slab below: one launch for both
                     continue;
                 }
-                if (have_prev) RUN(launch_conv3(h, L[EC1], nullptr, nullptr, buf[B_SYN0], P, prev, 1, st, nullptr, se->SP0, nullptr, &vs, nullptr, &sc));
+                if (have_prev) RUN(launch_conv3(h, L[EC1], nullptr, nullptr, buf[B_SYN0], P, prev, 1, st, {.pool_out = se->SP0, .first = &vs, .sc = &sc}));
                 prev = bx; have_prev = true;
             }
-            if (have_prev) RUN(launch_conv3(h, L[EC1], nullptr, nullptr, buf[B_SYN0], P, prev, 1, st, nullptr, se->SP0, nullptr, &vs, nullptr, &sc));
+            if (have_prev) RUN(launch_conv3(h, L[EC1], nullptr, nullptr, buf[B_SYN0], P, prev, 1, st, {.pool_out = se->SP0, .first = &vs, .sc = &sc}));
         }
         // ---- the interior of this batch's pooled tensors is a copy, their faces are computed
-        const int nch1 = (L[EC1].cout + 15) / 16;
-        {
-            const size_t total = (size_t)n * (d[1][0] * d[1][1] * d[1][2]) * nch1 * 4;
-            pooled_gather_kernel<<<capped_blocks(total, 256 * 64), 256, 0, st>>>(reinterpret_cast<const unsigned char*>(se->SP0), reinterpret_cast<unsigned char*>(buf[B_P0]), src,
-                                                                   d[1][0], d[1][1], d[1][2], se->PD / 2, se->PH / 2, se->PW / 2, nch1, total);
-            OAI_CHECK_LAUNCH();
-        }
-        {   // ec0 where ec1's shell reads it: closer than 3 voxels to a face (voxel pairs along x, enumerated slab by slab)
-            const size_t pairs = (size_t)6 * d[0][1] * (d[0][2] / 2) + (size_t)(d[0][0] - 6) * 6 * (d[0][2] / 2) + (size_t)(d[0][0] - 6) * (d[0][1] - 6) * 4;
-            dim3 grid(std::min<unsigned>(cdiv(pairs, 256), (unsigned)h->opt_first_blocks), n);
-            conv3_first_sres_kernel<32><<<grid, 256, 0, st>>>(src, L[EC0].plain, L[EC0].scale_f16, L[EC0].shift_f16, reinterpret_cast<unsigned char*>(buf[B_E0]), 1,
-                                                              h->range_flag, census_of(h, EC0), 3);
-            OAI_CHECK_LAUNCH();
-        }
+        RUN(launch_pooled_gather(h, *se, src, buf[B_P0], d[1], n, st));
+        RUN(launch_first_shell(h, src, buf[B_E0], d[0], n, st));        // ec0 where ec1's shell reads it
         const int td = d[0][0], th = d[0][1], tw = d[0][2];
         const Box zlo = {{0, 0, 0}, {2, th, tw}}, zhi = {{td - 2, 0, 0}, {td, th, tw}};                      // the six faces, 2 voxels thick, disjoint
         const Box ylo = {{2, 0, 0}, {td - 2, 2, tw}}, yhi = {{2, th - 2, 0}, {td - 2, th, tw}};
@@ -1329,59 +445,42 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
     } else {
     const bool fuse_first = first_fusable(h, need[EC1]);
     const TileSource* fsrc = fuse_first ? &src : nullptr;
-    if (!fuse_first) {   // ec0 (+ gather)
-        const dim3 grid_all(cdiv(v0 / 2, 256), n);                                          // one workgroup per 256 voxel pairs (the fp32 kernel)
-        const dim3 grid(std::min<unsigned>(cdiv(v0 / 2, 256), (unsigned)h->opt_first_blocks), n);     // the split-resident kernel walks the pairs with a grid stride
-        const int c = L[EC0].cout;
-        unsigned char* e0s = reinterpret_cast<unsigned char*>(buf[B_E0]);
-        const bool f16 = h->precision == OAI_PREC_FP16X3;
-        const float* sc0 = f16 ? L[EC0].scale_f16 : L[EC0].scale;
-        const float* sh0 = f16 ? L[EC0].shift_f16 : L[EC0].shift;
-        unsigned* cen0 = census_of(h, EC0);
-        if (h->sres && c == 32) conv3_first_sres_kernel<32><<<grid, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, e0s, 1, h->range_flag, cen0, 0);
-        else if (h->sres && c == 16) conv3_first_sres_kernel<16><<<grid, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, e0s, 1, h->range_flag, cen0, 0);
-        else if (h->sres && c == 8) conv3_first_sres_kernel<8><<<grid, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, e0s, 1, h->range_flag, cen0, 0);
-        else if (c == 32) conv3_first_kernel<32><<<grid_all, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, buf[B_E0], 1);
-        else if (c == 16) conv3_first_kernel<16><<<grid_all, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, buf[B_E0], 1);
-        else if (c == 8) conv3_first_kernel<8><<<grid_all, 256, 0, st>>>(src, L[EC0].plain, sc0, sh0, buf[B_E0], 1);
-        else return set_error(OAI_ERR_ARG, "ec0 cout %d unsupported (8, 16 or 32)", c);
-        OAI_CHECK_LAUNCH();
-    }
+    if (!fuse_first) RUN(launch_first(h, src, buf[B_E0], n, st));   // ec0 (+ gather)
     if (pool_fusable(h, d[0], need[EC1])) {
-        RUN(launch_conv3(h, L[EC1], buf[B_E0], nullptr, buf[B_SYN0], d[0], need[EC1], n, st, tb(EC1), buf[B_P0], nullptr, fsrc, tb(DC2)));
+        RUN(launch_conv3(h, L[EC1], buf[B_E0], nullptr, buf[B_SYN0], d[0], need[EC1], n, st, {.boxes = tb(EC1), .pool_out = buf[B_P0], .first = fsrc, .store_boxes = tb(DC2)}));
     } else {
-        RUN(launch_conv3(h, L[EC1], buf[B_E0], nullptr, buf[B_SYN0], d[0], need[EC1], n, st, tb(EC1), nullptr, nullptr, fsrc));
+        RUN(launch_conv3(h, L[EC1], buf[B_E0], nullptr, buf[B_SYN0], d[0], need[EC1], n, st, {.boxes = tb(EC1), .first = fsrc}));
         RUN(launch_pool(h, buf[B_SYN0], buf[B_P0], d[0], L[EC1].cout, n, st));
     }
     }
-    RUN(launch_conv3(h, L[EC2], buf[B_P0], nullptr, buf[B_E2], d[1], need[EC2], n, st, tb(EC2)));
+    RUN(launch_conv3(h, L[EC2], buf[B_P0], nullptr, buf[B_E2], d[1], need[EC2], n, st, {.boxes = tb(EC2)}));
     if (pool_fusable(h, d[1], need[EC3])) {
-        RUN(launch_conv3(h, L[EC3], buf[B_E2], nullptr, buf[B_SYN1], d[1], need[EC3], n, st, tb(EC3), buf[B_P1], nullptr, nullptr, tb(DC5)));
+        RUN(launch_conv3(h, L[EC3], buf[B_E2], nullptr, buf[B_SYN1], d[1], need[EC3], n, st, {.boxes = tb(EC3), .pool_out = buf[B_P1], .store_boxes = tb(DC5)}));
     } else {
-        RUN(launch_conv3(h, L[EC3], buf[B_E2], nullptr, buf[B_SYN1], d[1], need[EC3], n, st, tb(EC3)));
+        RUN(launch_conv3(h, L[EC3], buf[B_E2], nullptr, buf[B_SYN1], d[1], need[EC3], n, st, {.boxes = tb(EC3)}));
         RUN(launch_pool(h, buf[B_SYN1], buf[B_P1], d[1], L[EC3].cout, n, st));
     }
-    RUN(launch_conv3(h, L[EC4], buf[B_P1], nullptr, buf[B_E4], d[2], need[EC4], n, st, tb(EC4)));
+    RUN(launch_conv3(h, L[EC4], buf[B_P1], nullptr, buf[B_E4], d[2], need[EC4], n, st, {.boxes = tb(EC4)}));
     if (pool_fusable(h, d[2], need[EC5])) {
-        RUN(launch_conv3(h, L[EC5], buf[B_E4], nullptr, buf[B_SYN2], d[2], need[EC5], n, st, tb(EC5), buf[B_P2], nullptr, nullptr, tb(DC8)));
+        RUN(launch_conv3(h, L[EC5], buf[B_E4], nullptr, buf[B_SYN2], d[2], need[EC5], n, st, {.boxes = tb(EC5), .pool_out = buf[B_P2], .store_boxes = tb(DC8)}));
     } else {
-        RUN(launch_conv3(h, L[EC5], buf[B_E4], nullptr, buf[B_SYN2], d[2], need[EC5], n, st, tb(EC5)));
+        RUN(launch_conv3(h, L[EC5], buf[B_E4], nullptr, buf[B_SYN2], d[2], need[EC5], n, st, {.boxes = tb(EC5)}));
         RUN(launch_pool(h, buf[B_SYN2], buf[B_P2], d[2], L[EC5].cout, n, st));
     }
-    RUN(launch_conv3(h, L[EC6], buf[B_P2], nullptr, buf[B_E6], d[3], need[EC6], n, st, tb(EC6)));
-    RUN(launch_conv3(h, L[EC7], buf[B_E6], nullptr, buf[B_E7], d[3], need[EC7], n, st, tb(EC7)));
+    RUN(launch_conv3(h, L[EC6], buf[B_P2], nullptr, buf[B_E6], d[3], need[EC6], n, st, {.boxes = tb(EC6)}));
+    RUN(launch_conv3(h, L[EC7], buf[B_E6], nullptr, buf[B_E7], d[3], need[EC7], n, st, {.boxes = tb(EC7)}));
     RUN(launch_up(h, L[DC9], buf[B_E7], buf[B_U9], d[3], need[DC9], n, st, tb(DC9), upv(DC9)));
-    RUN(launch_conv3(h, L[DC8], buf[B_U9], buf[B_SYN2], buf[B_D8], d[2], need[DC8], n, st, tb(DC8), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC8)));   // cat(up, skip) :127
-    RUN(launch_conv3(h, L[DC7], buf[B_D8], nullptr, buf[B_D7], d[2], need[DC7], n, st, tb(DC7), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC7)));
+    RUN(launch_conv3(h, L[DC8], buf[B_U9], buf[B_SYN2], buf[B_D8], d[2], need[DC8], n, st, {.boxes = tb(DC8), .oc = oc(DC8)}));   // cat(up, skip) :127
+    RUN(launch_conv3(h, L[DC7], buf[B_D8], nullptr, buf[B_D7], d[2], need[DC7], n, st, {.boxes = tb(DC7), .oc = oc(DC7)}));
     RUN(launch_up(h, L[DC6], buf[B_D7], buf[B_U6], d[2], need[DC6], n, st, tb(DC6), upv(DC6)));
-    RUN(launch_conv3(h, L[DC5], buf[B_U6], buf[B_SYN1], buf[B_D5], d[1], need[DC5], n, st, tb(DC5), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC5)));   // :134
-    RUN(launch_conv3(h, L[DC4], buf[B_D5], nullptr, buf[B_D4], d[1], need[DC4], n, st, tb(DC4), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC4)));
+    RUN(launch_conv3(h, L[DC5], buf[B_U6], buf[B_SYN1], buf[B_D5], d[1], need[DC5], n, st, {.boxes = tb(DC5), .oc = oc(DC5)}));   // :134
+    RUN(launch_conv3(h, L[DC4], buf[B_D5], nullptr, buf[B_D4], d[1], need[DC4], n, st, {.boxes = tb(DC4), .oc = oc(DC4)}));
     RUN(launch_up(h, L[DC3], buf[B_D4], buf[B_U3], d[1], need[DC3], n, st, tb(DC3), upv(DC3)));
-    RUN(launch_conv3(h, L[DC2], buf[B_U3], buf[B_SYN0], buf[B_D2], d[0], need[DC2], n, st, tb(DC2), nullptr, nullptr, nullptr, nullptr, nullptr, oc(DC2)));   // :141
+    RUN(launch_conv3(h, L[DC2], buf[B_U3], buf[B_SYN0], buf[B_D2], d[0], need[DC2], n, st, {.boxes = tb(DC2), .oc = oc(DC2)}));   // :141
     // dc0 + sigmoid/threshold + centre crop: blocks are laid out over the full kept centre.  In the split-resident path it rides
     // in dc1's epilogue (dc1's 64 output channels sit in one workgroup): no dc1 output round trip through HBM, no head launch.
-    const int kz = src.vol ? src.oz : 0, ky = src.vol ? src.oy : 0, kx = src.vol ? src.ox : 0;
-    const int ez = src.vol ? src.ez : src.td, ey = src.vol ? src.ey : src.th, ex = src.vol ? src.ex : src.tw;
+    const int hk[3] = {src.vol ? src.oz : 0, src.vol ? src.oy : 0, src.vol ? src.ox : 0};
+    const int he[3] = {src.vol ? src.ez : src.td, src.vol ? src.ey : src.th, src.vol ? src.ex : src.tw};
     static const bool no_fuse = diag_env("OAI_NO_HEAD_FUSE", 0) != 0;
     const bool fuse_head = h->sres && !no_fuse && L[DC1].cout <= 64 && L[DC0].cin == L[DC1].cout && h->n_classes <= 4 &&
                            need[DC1].lo[0] <= need[DC0].lo[0] && need[DC1].hi[0] >= need[DC0].hi[0];
@@ -1390,83 +489,27 @@ static int run_batch(oai_unet* h, const TileSource& src, int n, const Box need[1
         ha.head_w = L[DC0].plain_f16; ha.head_b = L[DC0].shift;       // (fuse_head => sres => fp16x3: head weights carry 2^-e(dc1))
         ha.head_boxes = tb(DC0); ha.head_out = blocks_out;
         ha.head_ncls = h->n_classes; ha.head_mode = out_mode;
-        ha.head_k[0] = kz; ha.head_k[1] = ky; ha.head_k[2] = kx; ha.head_e[0] = ez; ha.head_e[1] = ey; ha.head_e[2] = ex;
-        RUN(launch_conv3(h, L[DC1], buf[B_D2], nullptr, buf[B_D1], d[0], need[DC0], n, st, tb(DC0), nullptr, &ha));
+        for (int i = 0; i < 3; ++i) { ha.head_k[i] = hk[i]; ha.head_e[i] = he[i]; }
+        RUN(launch_conv3(h, L[DC1], buf[B_D2], nullptr, buf[B_D1], d[0], need[DC0], n, st, {.boxes = tb(DC0), .head = &ha}));
         return OAI_OK;
     }
-    RUN(launch_conv3(h, L[DC1], buf[B_D2], nullptr, buf[B_D1], d[0], need[DC1], n, st, tb(DC1)));
+    RUN(launch_conv3(h, L[DC1], buf[B_D2], nullptr, buf[B_D1], d[0], need[DC1], n, st, {.boxes = tb(DC1)}));
+    RUN(launch_head(h, buf[B_D1], d[0], need[DC0], hk, he, out_mode, blocks_out, tb(DC0), n, st));
 #undef RUN
-    {
-        const Box& k = need[DC0];
-        const float* hw = h->precision == OAI_PREC_FP16X3 ? L[DC0].plain_f16 : L[DC0].plain;
-        const int bz = k.hi[0] - k.lo[0], by = k.hi[1] - k.lo[1], bx = k.hi[2] - k.lo[2];
-        dim3 grid(cdiv((size_t)bz * by * bx, 256), n);
-        if (h->sres)
-            head_sres_kernel<<<grid, 256, 0, st>>>(reinterpret_cast<const unsigned char*>(buf[B_D1]), L[DC0].cin, d[0][0], d[0][1], d[0][2],
-                                                   k.lo[0], k.lo[1], k.lo[2], bz, by, bx, kz, ky, kx, ez, ey, ex, hw,
-                                                   L[DC0].shift, h->n_classes, out_mode, blocks_out, tb(DC0));
-        else
-        head_kernel<<<grid, 256, 0, st>>>(buf[B_D1], L[DC0].cin, d[0][0], d[0][1], d[0][2], k.lo[0], k.lo[1], k.lo[2],
-                                          bz, by, bx, kz, ky, kx, ez, ey, ex, hw, L[DC0].shift, h->n_classes,
-                                          out_mode, blocks_out, tb(DC0));
-        OAI_CHECK_LAUNCH();
-    }
     return OAI_OK;
 }
 
 static double layer_flops(const oai_unet* h, int k, const Box& b) {
     const double vox = (double)(b.hi[0] - b.lo[0]) * (b.hi[1] - b.lo[1]) * (b.hi[2] - b.lo[2]);
-    const int taps = (kKind[k] == 0 || kKind[k] == 1) ? 27 : 1;
+    const int taps = (layer_kind(k) == 0 || layer_kind(k) == 1) ? 27 : 1;
     return 2.0 * vox * taps * h->L[k].cin * h->L[k].cout;
 }
 
-// Lower edge of the calibrated range: a layer whose largest stored activation is below kLowRange (and not zero) is at least 128 x smaller
-// than at calibration time (or was never calibrated): its low split terms are subnormal and the result is no longer fp32 grade.
-constexpr float kLowRange = 8.0f;
 constexpr int kTargetExp = 10;            // calibration puts a layer's maximum in [2^10, 2^11)
-
-// dst[0] = range flag of the work queued so far: bit 0 = an activation beyond fp16's range (set by the kernels), bit 1 = a layer's
-// maximum below kLowRange (from the census).  One wave; `reset` clears the flag and the census for the next volume.
-__global__ void range_eval_kernel(int* __restrict__ flag, unsigned* __restrict__ census, int* __restrict__ dst, int reset, float low) {
-    const int t = threadIdx.x;
-    unsigned m = 0;
-    if (t < 18)
-        for (int i = 0; i < 16; ++i) m = max(m, census[t * 16 + i]);
-    const bool lowhit = t < 17 && m != 0 && __uint_as_float(m) < low;
-    const unsigned long long any = __ballot(lowhit);
-    if (t == 0) {
-        dst[0] = flag[0] | (any ? 2 : 0);
-        if (reset) flag[0] = 0;
-    }
-    if (reset && t < 18)
-        for (int i = 0; i < 16; ++i) census[t * 16 + i] = 0;
-}
-
-// the raw form of range_eval_kernel: [0] = overflow bit, [1 + k] = layer k's maximum (float bits); clears flag and census
-__global__ void range_state_kernel(int* __restrict__ flag, unsigned* __restrict__ census, int* __restrict__ dst) {
-    const int t = threadIdx.x;
-    if (t < 18) {
-        unsigned m = 0;
-        for (int i = 0; i < 16; ++i) { m = max(m, census[t * 16 + i]); census[t * 16 + i] = 0; }
-        dst[1 + t] = (int)m;
-    }
-    if (t == 0) { dst[0] = flag[0] & 1; flag[0] = 0; }
-}
-
-__global__ void range_flag_from_state_kernel(const int* __restrict__ state, int* __restrict__ dst, float low) {
-    const int t = threadIdx.x;
-    const unsigned m = t < 17 ? (unsigned)state[1 + t] : 0u;
-    const bool lowhit = t < 17 && m != 0 && __uint_as_float(m) < low;
-    const unsigned long long any = __ballot(lowhit);
-    if (t == 0) dst[0] = (state[0] & 1) | (any ? 2 : 0);
-}
 
 }  // namespace oai
 
 using namespace oai;
-
-static int stitch_impl(const float* blocks, int ncls, int D, int H, int W, const int tile[3], const int overlap[3],
-                       const int crop[3], float* maps, void* stream, const StitchRanges& rg);
 
 // one zero-filled device block of the handle (freed by oai_unet_destroy)
 template <typename T>
@@ -1480,7 +523,7 @@ static int alloc_zeroed(oai_unet* h, size_t bytes, T** ptr) {
 }
 
 // k3 layers that run the implicit-GEMM conv kernels (ec0 and the 1x1x1 head have kernels of their own)
-static inline bool is_conv3_igemm(int k) { return k >= 1 && k < 17 && (kKind[k] == 0 || kKind[k] == 1); }
+static inline bool is_conv3_igemm(int k) { return k >= 1 && k < 17 && (layer_kind(k) == 0 || layer_kind(k) == 1); }
 
 static double tile_flops(const oai_unet* h, int td, int th, int tw, const int overlap[3], int trimmed, bool conv3_only) {
     if (!h) return 0.0;
@@ -1501,7 +544,7 @@ int oai_unet_create(const oai_layer_params layers[OAI_UNET_NUM_LAYERS], float bn
     OAI_CHECK_ARG(layers && out, "oai_unet_create: null pointer");
     for (int k = 0; k < 18; ++k) {
         OAI_CHECK_ARG(layers[k].weight_host, "oai_unet_create: layer %d has no weight (strict load)", k);
-        OAI_CHECK_ARG(layers[k].kind == kKind[k], "oai_unet_create: layer %d kind %d, expected %d", k, layers[k].kind, kKind[k]);
+        OAI_CHECK_ARG(layers[k].kind == layer_kind(k), "oai_unet_create: layer %d kind %d, expected %d", k, layers[k].kind, layer_kind(k));
         OAI_CHECK_ARG(layers[k].cin > 0 && layers[k].cout > 0, "oai_unet_create: layer %d bad channels", k);
     }
     // channel wiring of UNet.__init__ (networks.py:43-66)
@@ -1684,8 +727,7 @@ int oai_unet_range_flag(oai_unet* h, int reset, int* out, void* stream) {
     // ordered on the caller's stream (the one the segment calls were queued on): torch's side streams are non-blocking, so
     // the null stream would not wait for them and a flag could be read -- and reset -- before the kernels that set it ran
     hipStream_t st = (hipStream_t)stream;
-    range_eval_kernel<<<1, 64, 0, st>>>(h->range_flag, h->census, h->eval_out, reset, kLowRange);
-    OAI_CHECK_LAUNCH();
+    if (int rc = launch_range_eval(h, h->eval_out, reset, st)) return rc;
     OAI_CHECK_HIP(hipMemcpyAsync(out, h->eval_out, sizeof(int), hipMemcpyDeviceToHost, st));
     OAI_CHECK_HIP(hipStreamSynchronize(st));
     return OAI_OK;
@@ -1693,24 +735,17 @@ int oai_unet_range_flag(oai_unet* h, int reset, int* out, void* stream) {
 
 int oai_unet_range_flag_snapshot(oai_unet* h, int* dst_dev, void* stream) {
     OAI_CHECK_ARG(h && dst_dev, "oai_unet_range_flag_snapshot: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    range_eval_kernel<<<1, 64, 0, st>>>(h->range_flag, h->census, dst_dev, 1, kLowRange);   // a kernel: stream-ordered with the conv launches around it
-    OAI_CHECK_LAUNCH();
-    return OAI_OK;
+    return launch_range_eval(h, dst_dev, 1, (hipStream_t)stream);   // a kernel: stream-ordered with the conv launches around it
 }
 
 int oai_unet_range_state_snapshot(oai_unet* h, int* state_dev, void* stream) {
     OAI_CHECK_ARG(h && state_dev, "oai_unet_range_state_snapshot: null pointer");
-    range_state_kernel<<<1, 64, 0, (hipStream_t)stream>>>(h->range_flag, h->census, state_dev);
-    OAI_CHECK_LAUNCH();
-    return OAI_OK;
+    return launch_range_state(h, state_dev, (hipStream_t)stream);
 }
 
 int oai_unet_range_flag_from_state(const int* state_dev, int* flag_dev, void* stream) {
     OAI_CHECK_ARG(state_dev && flag_dev, "oai_unet_range_flag_from_state: null pointer");
-    range_flag_from_state_kernel<<<1, 64, 0, (hipStream_t)stream>>>(state_dev, flag_dev, kLowRange);
-    OAI_CHECK_LAUNCH();
-    return OAI_OK;
+    return launch_range_flag_from_state(state_dev, flag_dev, (hipStream_t)stream);
 }
 
 int oai_unet_census(oai_unet* h, float max_out[OAI_UNET_NUM_LAYERS], int reset, void* stream) {
@@ -2223,26 +1258,3 @@ int oai_stitch_blocks_ranged(const float* blocks, int ncls, int D, int H, int W,
 }
 
 }  // extern "C"
-
-static int stitch_impl(const float* blocks, int ncls, int D, int H, int W, const int tile[3], const int overlap[3],
-                       const int crop[3], float* maps, void* stream, const StitchRanges& rg) {
-    OAI_CHECK_ARG(blocks && maps && tile && overlap, "oai_stitch_blocks: null pointer");
-    int eff[3], grid[3];
-    const int size[3] = {D, H, W};
-    for (int i = 0; i < 3; ++i) {
-        eff[i] = tile[i] - 2 * overlap[i];
-        OAI_CHECK_ARG(eff[i] > 0, "oai_stitch_blocks: overlap too large for the tile");
-        grid[i] = (size[i] + eff[i] - 1) / eff[i];
-    }
-    const size_t total = (size_t)ncls * D * H * W;
-    if (crop && (crop[0] == 0 || crop[1] == 0 || crop[2] == 0)) {
-        // image_transforms.py:509-513 copies [c:-c] per axis into a zero array; with c == 0 the numpy slice 0:-0 is EMPTY, so a
-        // crop_size with a zero component (an overlap of 0 on some axis) yields an all-zero map in the reference.  Reproduced.
-        OAI_CHECK_HIP(hipMemsetAsync(maps, 0, total * sizeof(float), (hipStream_t)stream));
-        return OAI_OK;
-    }
-    stitch_kernel<<<capped_blocks(total, 256 * 32), 256, 0, (hipStream_t)stream>>>(blocks, ncls, D, H, W, eff[0], eff[1], eff[2], grid[1], grid[2],
-                                                                crop ? crop[0] : 0, crop ? crop[1] : 0, crop ? crop[2] : 0, maps, rg);
-    OAI_CHECK_LAUNCH();
-    return OAI_OK;
-}

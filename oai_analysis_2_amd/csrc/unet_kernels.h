@@ -1,4 +1,7 @@
-// Device kernels of the 3D U-Net segmentation path (gfx950).  Included by unet.hip only.
+// Device kernels of the 3D U-Net segmentation path (gfx950).  Who includes it: unet_host.h.
+// Several sources include this header.  Its kernel templates are emitted where a launcher names them; the kernels that are NOT templates
+// (maxpool2_kernel, head_kernel, stitch_kernel) exist only under OAI_UNET_PLAIN_KERNELS, which the one source that emits them defines
+// (unet_small.hip): otherwise every includer would define them.
 //
 // Layout: every activation is channels-last  [tile][z][y][x][c]  fp32, so that the GEMM K
 // dimension (input channels of one tap) is contiguous and an output row of 32 couts is one
@@ -151,7 +154,7 @@ __device__ __forceinline__ void pooled_store(const ConvArgs& a, int tile, int co
 
 // Tile shape: a 32-row MFMA block is RX x RY voxels (x, y); the 4 waves are arranged WY x WX, so a workgroup covers
 // MREP x (WY*RY) x (WX*RX) voxels.  The main shape is <16,2,4,1> (4 x 8 x 16); the other shapes exist for the thin
-// remainder strips of trimmed output boxes (e.g. 98 = 6*16 + 2), see launch_conv3 in unet.hip.  Every shape
+// remainder strips of trimmed output boxes (e.g. 98 = 6*16 + 2), see launch_conv3_direct in unet_direct.hip.  Every shape
 // accumulates each output voxel in the same k order, so the result does not depend on the shape used.
 template <int MREP, int KC, int RX, int RY, int WY, int WX>
 __global__ void __launch_bounds__(256, 2) conv3_igemm_f32(const ConvArgs a) {
@@ -850,6 +853,7 @@ __global__ void __launch_bounds__(256) conv3_first_kernel(const TileSource s, co
 }
 
 // MaxPool3d(2) on channels-last: one thread = one output voxel x 4 channels
+#ifdef OAI_UNET_PLAIN_KERNELS      // maxpool2_kernel, head_kernel, stitch_kernel are no templates: emitted by the one file that defines this macro (unet_small.hip)
 __global__ void __launch_bounds__(256) maxpool2_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                        int D, int H, int W, int C, size_t total4) {
     const int Do = D / 2, Ho = H / 2, Wo = W / 2, C4 = C / 4;
@@ -912,6 +916,7 @@ __global__ void __launch_bounds__(256) head_kernel(const float* __restrict__ in,
         blocks[((size_t)tile * ncls + k) * evox + o] = r;
     }
 }
+#endif
 
 // Where the block of tile t lives in a buffer that an all_gather of per-rank tile ranges left behind (oai_stitch_blocks_ranged): rank r's
 // range [bound[r], bound[r + 1]) sits in slots [r * stride, r * stride + its length) -- ragged ranges are padded to `stride` blocks per rank
@@ -925,6 +930,7 @@ __device__ __forceinline__ size_t stitch_slot(const StitchRanges& rg, size_t t) 
 }
 
 // Partition.assemble: blocks of all tiles -> maps[class][D][H][W] with trim + zeroed frame
+#ifdef OAI_UNET_PLAIN_KERNELS
 __global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ blocks, int ncls, int D, int H, int W,
                                                      int ez, int ey, int ex, int gy, int gx, int cz, int cy, int cx,
                                                      float* __restrict__ maps, const StitchRanges rg) {
@@ -945,5 +951,6 @@ __global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ b
         maps[i] = r;
     }
 }
+#endif
 
 }  // namespace oai

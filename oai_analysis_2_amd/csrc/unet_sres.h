@@ -15,6 +15,10 @@
 // key(hx) = (hx >> 2) & 3 so that the 16 lanes of a ds_read_b128 group (16 consecutive x, or 2 rows of 8) hit 16 different
 // 16-byte bank groups.  global_load_lds writes lane-linearly, so the swizzle is applied to the SOURCE address (rule 21 of the
 // CDNA guide): LDS slot p of record r receives logical slot p ^ key.
+//
+// Several sources include this header.  Its kernel templates are emitted where a launcher names them; the kernels that are NOT templates
+// (f32_to_sres_kernel, upconv2_igemm_sres, maxpool2_sres_kernel, pooled_gather_kernel, head_sres_kernel) exist only under
+// OAI_UNET_PLAIN_KERNELS, which the one source that emits them defines (unet_small.hip): otherwise every includer would define them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -132,6 +136,7 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {      // LDS byt
 }
 
 // ---- converters (bring-up / B3 seam only): fp32 channels-last <-> format S ------------------------------------------------
+#ifdef OAI_UNET_PLAIN_KERNELS      // not a template: emitted by the one file that defines this macro (unet_small.hip)
 __global__ void __launch_bounds__(256) f32_to_sres_kernel(const float* __restrict__ in, unsigned char* __restrict__ out, size_t nvox, int C) {
     const int nch = (C + 15) / 16;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvox * nch * 4; i += (size_t)gridDim.x * 256) {
@@ -150,6 +155,7 @@ __global__ void __launch_bounds__(256) f32_to_sres_kernel(const float* __restric
         *reinterpret_cast<u16x4*>(o + 32 + q * 8) = lo;
     }
 }
+#endif
 
 typedef float f32x4m __attribute__((ext_vector_type(4)));         // a native vector: inline asm can tie it to a 128-bit VGPR tuple (= f32x4 of unet_sres2.h)
 typedef _Float16 f16x8m __attribute__((ext_vector_type(8)));
@@ -965,6 +971,7 @@ __global__ void __launch_bounds__(256, MREP == 2 ? 3 : 2) conv3_igemm_sres(const
 // conv halo, + the four 4-KiB weight slabs of the workgroup's 256 columns, already in fragment order), two steps ahead of the
 // MFMAs with counted vmcnt waits and ONE barrier per step: with direct register loads each of the 8-32 k steps waited a
 // full L2 round trip with only two waves per SIMD to hide it (1.9 TB/s of writes on dc3).
+#ifdef OAI_UNET_PLAIN_KERNELS      // not a template: emitted by the one file that defines this macro (unet_small.hip)
 __global__ void __launch_bounds__(256, 2) upconv2_igemm_sres(const UpArgs a) {
 #ifdef OAI_DIAG
     // phase stamps (scripts/stamp_phases.py): [16] prologue, [17] k loop, [18] epilogue barriers, [19] split + LDS image, [20] copy-out stores, [24] waves
@@ -1234,6 +1241,7 @@ __global__ void __launch_bounds__(256, 2) upconv2_igemm_sres(const UpArgs a) {
             }
     }
 }
+#endif
 
 // ---- ec0 (1 -> COUT, gather-fused) writing format S ---------------------------------------------------------------------------
 template <int COUT>
@@ -1368,6 +1376,7 @@ __global__ void __launch_bounds__(256) conv3_first_sres_kernel(const TileSource 
     census_note(census, range_flag, rmax);
 }
 
+#ifdef OAI_UNET_PLAIN_KERNELS      // the three kernels to the end of the file are no templates: emitted by the one file that defines this macro (unet_small.hip)
 // ---- MaxPool3d(2) on format S (fallback when the pooling cannot ride in the conv epilogue) -----------------------------------
 // shell_only: just the pooled voxels on the faces of the tile (their 2 x 2 x 2 windows are what the per-tile shell launches of ec1 wrote)
 __global__ void __launch_bounds__(256) maxpool2_sres_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
@@ -1482,5 +1491,6 @@ __global__ void __launch_bounds__(256) head_sres_kernel(const unsigned char* __r
         blocks[((size_t)tile * ncls + k) * evox + o] = r;
     }
 }
+#endif
 
 }  // namespace oai

@@ -122,7 +122,7 @@ def test_no_packed_fp32_valu_and_hot_kernels_are_mfma(tmp_path):
     work = str(tmp_path)
     shutil.copy(path, os.path.join(work, "lib.so"))
     subprocess.run([objdump, "--offloading", "lib.so"], cwd=work, check=True, capture_output=True)      # extracts the bundles next to the copy
-    objs = glob.glob(os.path.join(work, "lib.so.*gfx950*"))
+    objs = sorted(glob.glob(os.path.join(work, "lib.so.*gfx950*")))      # (one order everywhere: the searches below end a kernel at the next symbol)
     assert objs, "no gfx950 code object in the library"
     text = "".join(subprocess.run([objdump, "-d", o], check=True, capture_output=True, text=True).stdout for o in objs)
     packed = re.findall(r"\bv_pk_(?:fma|mul|add)_f32\b", text)
@@ -261,3 +261,28 @@ def test_no_packed_fp32_valu_and_hot_kernels_are_mfma(tmp_path):
         assert not [ln for ln in body if "scratch_" in ln], f"{sym}: scratch traffic"
         assert not [ln for ln in loop if "s_waitcnt" in ln and "vmcnt(0)" in ln], f"{sym}: a full vmcnt wait inside the chunk loop"
         assert len([ln for ln in loop if "s_barrier" in ln]) == 1, f"{sym}: more than one barrier per chunk"
+
+
+def test_every_kernel_is_emitted_by_one_translation_unit(tmp_path):
+    """The U-Net kernel headers are included by several sources (unet.hip, unet_direct.hip, unet_direct_m16.hip, unet_wino.hip, unet_small.hip): a kernel is compiled
+    where its launcher names it, and nowhere else -- no kernel symbol of the whole library is in more than one gfx950 code object (a second copy
+    of an instantiation would cost its compile time again and could differ from the first)."""
+    import collections
+    import glob
+    import shutil
+    import subprocess
+    llvm = os.path.dirname(shutil.which("llvm-objdump") or "/opt/rocm/lib/llvm/bin/llvm-objdump")
+    assert os.path.exists(os.path.join(llvm, "llvm-readelf")), "no llvm-readelf: the code-object checks cannot run (a skipped guard is a failed guard)"
+    work = str(tmp_path)
+    shutil.copy(build.build_library(verbose=False), os.path.join(work, "lib.so"))
+    subprocess.run([os.path.join(llvm, "llvm-objdump"), "--offloading", "lib.so"], cwd=work, check=True, capture_output=True)
+    where = collections.defaultdict(set)                                 # kernel symbol -> the code objects whose metadata list it
+    for o in glob.glob(os.path.join(work, "lib.so.*gfx950*")):
+        notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", o], check=True, capture_output=True, text=True).stdout
+        for name in re.findall(r"^\s*\.name:\s+(\S+)$", notes, flags=re.M):
+            if re.search(r"^\s*\.symbol:\s+" + re.escape(name) + r"\.kd$", notes, flags=re.M):      # (.name is also a key of kernel arguments)
+                where[name].add(o)
+    assert len(where) > 300, f"only {len(where)} kernels found in the library's metadata"
+    twice = sorted(k for k, objs in where.items() if len(objs) > 1)
+    assert not twice, f"kernels in more than one code object: {twice[:5]}"
+    assert any("conv3_wino_sres" in k for k in where) and any("conv3_igemm_sres2" in k for k in where) and any("upconv2_igemm_sres" in k for k in where)
