@@ -1340,6 +1340,72 @@ int oai_visit_slopes(const float* values_dev, const unsigned char* mask_dev, lon
                      double* rate_dev, double* avg_dev, double* fit_ref_dev, double* resid_sd_dev, int* n_dev, unsigned char* out_mask_dev,
                      void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Normative deviation (csrc/normative.hip, tests/normative_ref.py): where is ONE knee abnormally thin or thick for its age, sex and BMI,
+ * and is that more than chance over the whole surface?  A linear model y ~ Z gamma is fitted per vertex on a reference cohort (healthy
+ * knees, or the rate maps of non-progressors), and a knee is scored against it vertex by vertex: its residual over the standard error of
+ * a NEW observation, which accounts for the covariates, for the uncertainty of the fitted mean (the leverage of the knee's design row)
+ * and -- for a knee that belongs to the reference -- for the knee's own share in the fit.  The reference has no such step: the
+ * definitions are this library's own, pinned by the numpy restatement and by refits with numpy.linalg.lstsq.  The design Z is float64
+ * [n_knees][p], knee-major, 1 <= p <= 6 WITH THE INTERCEPT (if any) COUNTED IN p.  The rules of "Cohort statistics" hold: fp64 without
+ * contraction, one accumulator per sum that starts at +0.0, EVERY SUM OVER KNEES IN ASCENDING KNEE INDEX, a missing entry skipped by a
+ * select (what lies under a 0 mask byte reaches no sum), no floating-point atomics: bit-reproducible.  Nothing synchronises or reads
+ * anything back.  2 <= n_knees <= 2^24, 1 <= n_verts <= 2^31 - 2, at most 2^20 rows per call.  y_dev and mask_dev as in "Cohort
+ * statistics"; a null mask: every entry is valid, and the results are THE SAME BITS as with a mask of all ones.
+ *
+ * oai_normative_fit.  Per vertex v, with m_i the mask and y_i = (double)y[i][v], i = 0 .. n_knees - 1:
+ *   n    = sum m_i
+ *   A_ac = sum_i (m_i ? z_ia*z_ic : 0.0), c <= a             h_a = sum_i (m_i ? z_ia*y_i : 0.0)
+ *   A = L L^T, with the order and the PIVOT RULE of "Cohort regression": pivot s is accepted iff s > 1e-10 * A_aa
+ *   L w = h forward and L^T gamma = w backward, as stated there
+ *   e_i  = y_i - sum_a z_ia*gamma_a                           (from y_i, s = s - z_ia*gamma_a, a ascending)
+ *   rss  = sum_i (m_i ? e_i*e_i : 0.0)
+ *   ok   = every pivot accepted && n - p >= 1
+ * The values are NOT centred: centre the covariate columns instead.  The MODEL BLOCK, model_dev, front to back, each array starting on
+ * the next multiple of 256 bytes, COMPONENT-MAJOR so that a wave's 64 consecutive vertices load contiguously: gamma float64 [p][n_verts],
+ * L float64 [p (p + 1) / 2][n_verts] (entry (a, c), c <= a, is component a (a + 1) / 2 + c), rss float64 [n_verts], n int32 [n_verts],
+ * ok uint8 [n_verts].  It does not depend on n_knees and stays valid for as long as the caller keeps it; a caller may also fill it from
+ * arrays that it stored.  A thread owns one vertex; the sum over knees is not split.
+ *
+ * oai_normative_score: n_rows knees -> the z tile, float64 [n_rows][n_verts] at the start of workspace_dev, in the layout that
+ * oai_graph_clusters and oai_graph_tfce consume (rows = knees).  x_dev float32 [n_rows][n_verts]; x_mask_dev uint8 [n_rows][n_verts] or
+ * null (every entry valid); design_rows_dev float64 [n_rows][p], the design row g of each knee, built as the columns of Z were.  Per
+ * (row k, vertex v), with x = (double)x[k][v], mx the row's mask byte there, and the per-call flag loo:
+ *   e   = x - sum_a g_a*gamma_a                               (from x, s = s - g_a*gamma_a, a ascending)
+ *   L u = g forward                                           (u_a = (g_a - sum_{k<a} L_ak*u_k) / L_aa, s = s - L_ak*u_k, k ascending)
+ *   lev = sum_a u_a*u_a                                       (from +0.0, a ascending: the leverage g^T (Z^T Z)^-1 g)
+ *   loo = 0 (a knee that is NOT in the fit; the prediction-interval t):
+ *     dof = n - p;  s2 = rss/dof;  se2 = s2*(1.0 + lev)
+ *   loo = 1 (row k is the fit's own row k, x and mask as fitted; the externally studentised residual, identical to scoring the knee
+ *            against a fit without it):
+ *     den = 1.0 - lev;  dof = n - p - 1;  s2 = (rss - (e*e)/den)/dof;  se2 = s2*den
+ *   z   = e / sqrt(se2)
+ *   z is valid iff mx && ok && dof >= 1 && s2 > 0 && (loo == 0 || den > 1e-10), otherwise NaN
+ * den > 1e-10 is A CONDITION and part of the contract, like the pivot rule: a knee that alone carries a design direction (the only
+ * member of a dummy level) has leverage 1 and no leave-one-out score.  diff_dev float64 [n_rows][n_verts], or null: receives e, the
+ * deviation in mm, where mx && ok and NaN elsewhere.  There is no float32 output of z.  A thread owns one vertex and eight rows, so that
+ * gamma, L, rss, n and ok are loaded once per eight rows; the design rows are wave-uniform.
+ *
+ * oai_deviation_summary: per row of a z tile (tile_dev float64 [n_rows][n_verts]) at a threshold z0 > 0, over the entries that are not
+ * NaN: stats_dev float64 [n_rows][3] = (max |z|, min z, max z) -- 0.0, NaN, NaN for a row without a valid entry; counts_dev int64
+ * [n_rows][6] = (n_valid, the vertex of max |z|: THE SMALLEST INDEX AT A TIE, -1 without a valid entry; the vertex count of {z < -z0} and
+ * its area; the vertex count of {z > z0} and its area).  Both sets are strict.  An area is the int64 sum of weight_dev int64 [n_verts]
+ * over the set (the integer vertex areas in units of 2^-20 mm^2 that "Threshold-free cluster enhancement" takes; null: every weight is
+ * 1): an integer sum, so no order needs stating; maxima and minima are exact.
+ * ---------------------------------------------------------------------------------------- */
+/* All three: 0 for a shape the entry point refuses.  oai_normative_fit_workspace_bytes is the size of the model block. */
+size_t oai_normative_fit_workspace_bytes(long long n_verts, int n_columns);
+int oai_normative_fit(const float* y_dev, const unsigned char* mask_dev, const double* design_dev, long long n_knees, long long n_verts, int n_columns,
+                      void* model_dev, size_t model_bytes, void* stream);
+size_t oai_normative_score_workspace_bytes(long long n_rows, long long n_verts);
+int oai_normative_score(const void* model_dev, size_t model_bytes, const float* x_dev, const unsigned char* x_mask_dev, const double* design_rows_dev,
+                        long long n_rows, long long n_verts, int n_columns, int loo, void* workspace_dev, size_t workspace_bytes, double* diff_dev,
+                        void* stream);
+size_t oai_deviation_summary_workspace_bytes(long long n_rows, long long n_verts);
+int oai_deviation_summary(const double* tile_dev, long long n_rows, long long n_verts, const long long* weight_dev, double z0, void* workspace_dev,
+                          size_t workspace_bytes, double* stats_dev, long long* counts_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,15 +50,15 @@
 
 #pragma clang fp contract(off)
 
+#include "regression_solve.h"
+
 namespace {
 
 using namespace oai;
 
 constexpr int kT = 256;                            // vertices of a block
-constexpr int kMaxCols = 6;                        // p
-constexpr double kPivot = 1e-10;
+// kMaxCols (p), kPivot, tri(), cholesky<P> and forward_solve<P>: csrc/regression_solve.h, shared with csrc/normative.hip
 
-__host__ __device__ constexpr int tri(int p) { return p * (p + 1) / 2; }               // entries of a lower triangle; index of (a, 0)
 __host__ __device__ constexpr int rows_per_thread(int p, bool masked) {
     return masked ? (p == 1 ? 16 : p == 2 ? 8 : p <= 4 ? 2 : 1) : (p <= 2 ? 16 : 8);
 }
@@ -79,43 +79,6 @@ struct Prepared {
         bytes = ws.off;
     }
 };
-
-// In place: the packed lower triangle A (entry (a, c), c <= a, at tri(a) + c) becomes its Cholesky factor L, column by column, inner sums
-// in ascending k as s = s - L_ak * L_ck.  Returns whether every pivot passed; the arithmetic goes on after one that did not.
-template <int P>
-__device__ __forceinline__ bool cholesky(double* A) {
-    bool pass = true;
-#pragma unroll
-    for (int a = 0; a < P; ++a) {
-        const double diag = A[tri(a) + a];
-        double s = diag;
-#pragma unroll
-        for (int k = 0; k < a; ++k) s = s - A[tri(a) + k] * A[tri(a) + k];
-        pass = pass && s > kPivot * diag;
-        const double l = sqrt(s);
-        A[tri(a) + a] = l;
-#pragma unroll
-        for (int c = a + 1; c < P; ++c) {
-            double u = A[tri(c) + a];
-#pragma unroll
-            for (int k = 0; k < a; ++k) u = u - A[tri(c) + k] * A[tri(a) + k];
-            A[tri(c) + a] = u / l;
-        }
-    }
-    return pass;
-}
-
-// L z = b in place, ascending rows, s = s - L_ak * z_k
-template <int P>
-__device__ __forceinline__ void forward_solve(const double* L, double* b) {
-#pragma unroll
-    for (int a = 0; a < P; ++a) {
-        double s = b[a];
-#pragma unroll
-        for (int k = 0; k < a; ++k) s = s - L[tri(a) + k] * b[k];
-        b[a] = s / L[tri(a) + a];
-    }
-}
 
 // one thread per vertex, knees in ascending index: the counted sum; the normal equations of the nuisance columns; the residuals
 template <int QN>

@@ -264,6 +264,24 @@ def thickness_qc_stream(results: Iterable[Tuple[int, object]], **kwargs) -> Iter
         yield index, result_local_thicknesses(res, **kwargs)
 
 
+def deviation_stream(stream: Iterable[Tuple[int, object]], models, covariates=None, z_threshold: float = 2.0,
+                     return_maps: bool = False) -> Iterator[Tuple[int, object]]:
+    """(index, {"FC": stats.DeviationResult, "TC": ...}) for every (index, KneeThickness) of ``stream`` (``thickness_stream`` /
+    ``process_cohort_thickness``): each knee scored against the normative model of each cartilage in ``models`` ({"FC":
+    stats.NormativeModel, ...}) as it arrives.  ``covariates``: what ``covariates[index]`` gives is the knee's covariate row (a mapping or
+    a sequence by index; None for models without covariates).  A cartilage that could not be measured has no score anywhere (``n_valid``
+    0).  Like ``qc_stream`` a plain synchronous generator: a few small launches and one download per knee and cartilage."""
+    from .stats import ThicknessCohort
+    for index, knee in stream:
+        row = None if covariates is None else covariates[index]
+        found = {}
+        for kind, model in models.items():
+            one = ThicknessCohort(model.atlas, kind, use_coverage=model.surface.use_coverage, chunk=1)
+            one.add(knee, index)
+            found[kind] = model.deviation(one, covariates=row, z_threshold=z_threshold, return_maps=return_maps)
+        yield index, found
+
+
 def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None,
                              space: str = "atlas", morphometry=False, mesh_qc: bool = False) -> Iterator[Tuple[int, object]]:
     """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the

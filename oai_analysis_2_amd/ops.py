@@ -1001,3 +1001,94 @@ def regression_f(prepared: RegressionPrepared, design: torch.Tensor, perm: torch
     _lib.call("oai_regression_f", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p,
               k, p0, p1, ws.data_ptr(), ws.numel(), _ptr(coef0), _lib.STREAM, device=dev)
     return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+
+
+# ---- normative deviation (include/oai_hip.h, "Normative deviation"; csrc/normative.hip) ------------------------------------------------------
+NORMATIVE_SCORE_ROWS = 8             # rows per thread of the score kernel
+
+
+@dataclass
+class NormativeFit:
+    """The model block of ``normative_fit`` and views of its arrays (include/oai_hip.h states the layout, component-major): ``gamma``
+    float64 [p,V], ``L`` float64 [p (p + 1) / 2, V], ``rss`` float64 [V], ``n`` int32 [V], ``ok`` uint8 [V]."""
+    block: torch.Tensor
+    n_verts: int
+    n_columns: int
+    gamma: torch.Tensor
+    L: torch.Tensor
+    rss: torch.Tensor
+    n: torch.Tensor
+    ok: torch.Tensor
+
+
+def normative_block(n_verts: int, n_columns: int, device) -> NormativeFit:
+    """An UNFILLED model block for ``n_verts`` vertices and ``n_columns`` design columns on ``device``: what ``normative_fit`` writes, and
+    what a caller that kept the arrays of a model copies them back into."""
+    V, p = int(n_verts), int(n_columns)
+    if V < 1 or not 1 <= p <= MAX_DESIGN_COLUMNS:
+        raise ValueError(f"a model block needs V >= 1 vertices and 1 .. {MAX_DESIGN_COLUMNS} design columns, got {n_verts!r}, {n_columns!r}")
+    block = _lib.workspace("oai_normative_fit", device, V, p)
+    parts = _block_views(block, (("gamma", torch.float64, (p, V)), ("L", torch.float64, (p * (p + 1) // 2, V)), ("rss", torch.float64, (V,)),
+                                 ("n", torch.int32, (V,)), ("ok", torch.uint8, (V,))))
+    return NormativeFit(block, V, p, **parts)
+
+
+def normative_fit(values: torch.Tensor, design: torch.Tensor, mask: Optional[torch.Tensor] = None) -> NormativeFit:
+    """The per-vertex linear model of a reference cohort: float32 ``values`` [N,V], an optional uint8 / bool ``mask`` [N,V] and the float64
+    ``design`` [N,p] (1 <= p <= 6, the intercept among its columns) -> per vertex the coefficients, the Cholesky factor of the normal
+    equations over the knees with a value, the residual sum of squares, n and ok.  fp64 in a stated order: bit-reproducible.  Does not
+    synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or values.shape[0] < 2 or values.shape[1] < 1:
+        raise ValueError(f"values must be [N >= 2, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V = int(values.shape[0]), int(values.shape[1])
+    design = _design(design, "design", N, values.device, 1, MAX_DESIGN_COLUMNS)
+    model = normative_block(V, int(design.shape[1]), values.device)
+    _lib.call("oai_normative_fit", values.data_ptr(), _ptr(mask), design.data_ptr(), N, V, model.n_columns, model.block.data_ptr(),
+              model.block.numel(), _lib.STREAM, device=values.device)
+    return model
+
+
+def normative_score(model: NormativeFit, values: torch.Tensor, design_rows: torch.Tensor, mask: Optional[torch.Tensor] = None, loo: bool = False,
+                    workspace: Optional[torch.Tensor] = None, diff: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The z tile of the knees ``values`` (float32 [R,V], optional uint8 / bool ``mask``) against ``model``, each with its design row
+    (float64 ``design_rows`` [R,p]): float64 [R,V], NaN where no score exists.  ``loo`` False: the knees are not in the fit (the
+    prediction-interval t); True: row k is the fit's own row k (the externally studentised residual).  ``diff`` float64 [R,V]: receives the
+    deviation in mm.  ``workspace``: a uint8 device buffer to hold the tile instead of a new one.  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] != model.n_verts or values.device != model.block.device:
+        raise ValueError(f"values must be [R >= 1, {model.n_verts}] on {model.block.device}, got {tuple(values.shape)} on {values.device}")
+    mask = _stats_mask(mask, values)
+    R, V, dev = int(values.shape[0]), model.n_verts, values.device
+    design_rows = _design(design_rows, "design_rows", R, dev, model.n_columns, model.n_columns)
+    if diff is not None:
+        diff = _out_tile(diff, "diff", torch.float64, values, may_alias=True)
+    need = int(_lib.load().oai_normative_score_workspace_bytes(R, V))
+    ws = _tile_workspace(workspace, need, dev)
+    _lib.call("oai_normative_score", model.block.data_ptr(), model.block.numel(), values.data_ptr(), _ptr(mask), design_rows.data_ptr(), R, V,
+              model.n_columns, int(bool(loo)), ws.data_ptr(), ws.numel(), _ptr(diff), _lib.STREAM, device=dev)
+    return ws[:R * V * 8].view(torch.float64).reshape(R, V)
+
+
+def deviation_summary(tile: torch.Tensor, z_threshold: float, weights: Optional[torch.Tensor] = None):
+    """Per row of the float64 z ``tile`` [R,V], over its entries that are not NaN: the float64 [R,3] and int64 [R,6] DEVICE tensors (stats,
+    counts) -- stats = (max |z|, min z, max z); counts = (valid entries, the vertex of max |z| -- the smallest at a tie --, the vertex count
+    and the summed int64 ``weights`` [V] of {z < -z_threshold}, the same of {z > z_threshold}); without ``weights`` every weight is 1.
+    Exact maxima and integer sums.  Does not synchronise."""
+    tile = _chk(tile, "tile", torch.float64)
+    if tile.dim() != 2 or tile.shape[0] < 1 or tile.shape[1] < 1:
+        raise ValueError(f"tile must be [R >= 1, V >= 1], got {tuple(tile.shape)}")
+    if not float(z_threshold) > 0.0:
+        raise ValueError(f"z_threshold must be > 0, got {z_threshold!r}")
+    R, V, dev = int(tile.shape[0]), int(tile.shape[1]), tile.device
+    if weights is not None:
+        weights = _chk(weights, "weights", torch.int64)
+        if tuple(weights.shape) != (V,) or weights.device != dev:
+            raise ValueError(f"weights must be int64 [{V}] on the tile's GPU, got {tuple(weights.shape)} on {weights.device}")
+    stats = torch.empty((R, 3), dtype=torch.float64, device=dev)
+    counts = torch.empty((R, 6), dtype=torch.int64, device=dev)
+    ws = _lib.workspace("oai_deviation_summary", dev, R, V)
+    _lib.call("oai_deviation_summary", tile.data_ptr(), R, V, _ptr(weights), float(z_threshold), ws.data_ptr(), ws.numel(), stats.data_ptr(),
+              counts.data_ptr(), _lib.STREAM, device=dev)
+    return stats, counts

@@ -45,6 +45,15 @@ above and for ``one_sample_test``: is there loss at all, and where?
     visits = LongitudinalCohort.from_stream(thickness_stream(...), atlas, "FC", visits={index: (subject, years), ...})
     rate = visits.change("rate", min_visits=3)                          # mm / year per subject and vertex
     one_sample_test(rate, tfce=True).p_tfce, regression_test(rate, baseline_kl_grade).p_fwer
+
+``NormativeModel`` answers the question about ONE knee: where is it abnormally thin for its age, sex and BMI, and is that more than chance
+over the whole surface?  A linear model per vertex on a reference cohort, new knees scored by the prediction-interval t and the members
+themselves by the externally studentised residual, per-knee family-wise p-values as ranks among the reference's own leave-one-out
+statistics (include/oai_hip.h, "Normative deviation"; csrc/normative.hip; tests/normative_ref.py).
+
+    model = NormativeModel.fit(healthy, covariates=np.stack([age, sex, bmi], axis=1), names=["age", "sex", "bmi"])
+    res = model.deviation(knee_vector, covariates=[71.0, 1.0, 31.2], return_maps=True)
+    res.p_max, res.area_below_mm2, res.clusters(0), res.image(atlas, "z")
 """
 from __future__ import annotations
 
@@ -1331,3 +1340,314 @@ def anova_test(cohort: ThicknessCohort, groups, covariates=None, n_permutations:
     names = [f"the dummy of level {int(lab)}" for lab in levels[1:]]
     return _f_run(cohort, "anova_test", dummies, names, covariates, True, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
                   groups=(levels, where))
+
+
+# ---- normative deviation ---------------------------------------------------------------------------------------------------------------
+_DEVIATION_BYTES = 8 + 8              # per (knee, vertex) of a batch: the z tile and oai_graph_clusters_workspace_bytes
+_MODEL_ARRAYS = ("gamma", "L", "rss", "n", "ok")
+
+
+def _rank_p(stat, reference, member: bool) -> np.ndarray:
+    """The family-wise p of each knee's statistic against the reference knees' own leave-one-out statistics:
+    (1 + #{reference knees j: stat_j >= stat}) / (N' + 1).  For a ``member`` of the reference, itself is left out of the count (it is one of
+    the j, and stat_j >= stat holds for it) and N' = N - 1; for any other knee N' = N.  The smallest possible p is 1 / (N' + 1)."""
+    ref = np.sort(np.asarray(reference))
+    ge = len(ref) - np.searchsorted(ref, np.asarray(stat), side="left")
+    return ge / float(len(ref)) if member else (1.0 + ge) / float(len(ref) + 1)
+
+
+def _normative_design(covariates, intercept: bool, n_knees: int, names: Optional[Sequence[str]] = None):
+    """(design [N, p], means [c], scales [c], names) of a reference cohort: the intercept (if any) first, then every covariate column less
+    its mean over the reference (with an intercept) and divided by its length, as ``_design_matrix`` makes them -- whose refusals, by
+    name and before anything is launched, these are: a NaN or an infinity, a constant or a collinear column, more than six columns."""
+    if covariates is None or np.size(covariates) == 0:
+        if not intercept:
+            raise ValueError("a model without covariates needs the intercept: there is no column left")
+        return np.ones((n_knees, 1)), np.zeros(0), np.ones(0), []
+    cov = np.asarray(covariates, np.float64)
+    cov = cov[:, None] if cov.ndim == 1 else cov
+    if cov.ndim != 2 or cov.shape[0] != n_knees:
+        raise ValueError(f"covariates must be [{n_knees}] or [{n_knees}, c], got shape {cov.shape}")
+    names = [f"covariate {j}" for j in range(cov.shape[1])] if names is None else [str(n) for n in names]
+    if len(names) != cov.shape[1]:
+        raise ValueError(f"names must hold one entry per covariate column ({cov.shape[1]}), got {len(names)}")
+    _, _, scales = _design_matrix(cov, None, intercept, n_knees, names)
+    means = np.array([cov[:, j].mean() for j in range(cov.shape[1])]) if intercept else np.zeros(cov.shape[1])
+    return _design_rows(cov, intercept, means, scales), means, scales, names
+
+
+def _design_rows(cov: np.ndarray, intercept: bool, means: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """[M, p]: the design rows of knees with the covariates ``cov`` [M, c], centred and scaled as the reference's columns were."""
+    cols = ([np.ones(cov.shape[0])] if intercept else []) + [(cov[:, j] - means[j]) / scales[j] for j in range(cov.shape[1])]
+    return np.ascontiguousarray(np.stack(cols, axis=1))
+
+
+@dataclass
+class DeviationResult:
+    """One entry per knee (``ids``), scored against a ``NormativeModel`` at ``z_threshold``; ``loo``: the knees are the model's own members,
+    each scored as if the model had been fitted without it.  ``max_abs`` = max |z| over the surface at vertex ``max_vertex`` (-1: the knee
+    has no score anywhere), ``min_z``, ``max_z``; ``n_valid`` the vertices with a score; ``n_below`` / ``area_below_mm2`` the vertex count
+    and atlas area of {z < -z_threshold} -- abnormally thin --, ``n_above`` / ``area_above_mm2`` of {z > z_threshold}; ``max_extent`` the
+    vertex count of the largest connected cluster of either set.  ``dof`` int64 [V]: the degrees of freedom of z per vertex (n - p, or
+    n - p - 1 for members).  The family-wise per-knee p-values ``p_max``, ``p_extent`` and ``p_area_below`` are ranks of ``max_abs``,
+    ``max_extent`` and the area below among the reference knees' own leave-one-out statistics (``_rank_p``): is this knee's worst place,
+    largest cluster, thin area more than a healthy knee shows SOMEWHERE on its surface?  No significance level is built in.  With
+    ``return_maps``: ``z`` and ``diff_mm`` float64 [M, V] (NaN where there is no score) and ``p_uncorrected``, the two-sided Student t
+    p of z at ``dof``, vertex by vertex."""
+    kind: str
+    ids: List[object]
+    loo: bool
+    z_threshold: float
+    n_valid: np.ndarray
+    max_abs: np.ndarray
+    max_vertex: np.ndarray
+    min_z: np.ndarray
+    max_z: np.ndarray
+    n_below: np.ndarray
+    n_above: np.ndarray
+    area_below_mm2: np.ndarray
+    area_above_mm2: np.ndarray
+    max_extent: np.ndarray
+    dof: np.ndarray
+    p_max: np.ndarray
+    p_extent: np.ndarray
+    p_area_below: np.ndarray
+    z: Optional[np.ndarray] = None
+    diff_mm: Optional[np.ndarray] = None
+    p_uncorrected: Optional[np.ndarray] = None
+    model: Optional["NormativeModel"] = field(default=None, repr=False, compare=False)
+
+    IMAGES = ("z", "diff_mm", "p_uncorrected")
+
+    def __len__(self) -> int:
+        return len(self.ids)
+
+    def _map(self, what: str, knee: int) -> np.ndarray:
+        if what not in self.IMAGES:
+            raise ValueError(f"no image of {what!r}")
+        if getattr(self, what) is None:
+            raise ValueError("the knees were scored without return_maps")
+        if not 0 <= int(knee) < len(self):
+            raise ValueError(f"knee must be 0 .. {len(self) - 1}, got {knee!r}")
+        return getattr(self, what)[int(knee)]
+
+    def image(self, atlas, what: str = "z", knee: int = 0):
+        """``atlas.image`` of knee ``knee``'s "z", "diff_mm" or "p_uncorrected" map (float32 [H, W], NaN off the surface)."""
+        return atlas.image(np.asarray(self._map(what, knee), np.float32), self.kind)
+
+    def clusters(self, knee: int = 0) -> List[Cluster]:
+        """The connected clusters of {z < -z_threshold} and {z > z_threshold} of knee ``knee`` in ascending label, from a one-row
+        ``ops.graph_clusters`` call; ``p_cluster``: the rank of the extent among the reference's largest leave-one-out clusters."""
+        z = self._map("z", knee)
+        model = self.model
+        offsets, neighbours = model.surface.surface_graph()
+        _, label, size = ops.graph_clusters(torch.from_numpy(np.ascontiguousarray(z[None, :])).to(model.device), offsets, neighbours,
+                                            self.z_threshold, return_labels=True)
+        label, size = _download([label, size])
+        area, reference = model.surface.vertex_areas(), model.reference(self.z_threshold)["max_extent"]
+        found = []
+        for lab in np.unique(label[label >= 0]):
+            members = np.nonzero(label == lab)[0]
+            found.append(Cluster(int(lab), 1 if z[lab] > 0 else -1, int(size[lab]), float(np.cumsum(area[members])[-1]),
+                                 float(_rank_p(int(size[lab]), reference, self.loo))))
+        return found
+
+
+class NormativeModel:
+    """Where is ONE knee abnormally thin for its age, sex and BMI?  A linear model of thickness on covariates, fitted per vertex on a
+    reference cohort (include/oai_hip.h, "Normative deviation"; csrc/normative.hip; tests/normative_ref.py), against which single knees are
+    scored: z = the knee's residual over the standard error of a new observation, which holds the residual variance of the reference AND
+    the uncertainty of the fitted mean at the knee's covariates.  ``deviation`` scores knees that are not in the fit, ``loo`` the members
+    themselves, each against the fit without it (the externally studentised residual, in closed form).  Fitted on the rate maps of
+    non-progressors (``LongitudinalCohort.change("rate")``), the same model gives per-knee progressor maps.
+
+    Limits.  At most six design columns, the intercept among them.  A knee without a value at a vertex has no score there.  Reference
+    knees are scored against N - 1 others and a new knee against N, so their statistics are t variables with one degree of freedom less
+    and exchangeable with the new knee's only approximately.  The smallest possible p is 1 / (N + 1).  No TFCE of the z tile, no float32 z."""
+
+    def __init__(self, surface: ThicknessCohort, block: "ops.NormativeFit", n_knees: int, intercept: bool, names, means, scales):
+        self.surface, self.block, self.n_knees, self.intercept = surface, block, int(n_knees), bool(intercept)
+        self.names, self.means, self.scales = list(names), np.asarray(means, np.float64), np.asarray(scales, np.float64)
+        self.atlas, self.kind, self.device, self.n_verts = surface.atlas, surface.kind, surface.device, surface.n_verts
+        self.n_columns = int(block.n_columns)
+        self.cohort: Optional[ThicknessCohort] = None          # the reference itself; None on a model that was loaded
+        self.design: Optional[np.ndarray] = None               # its design [N, p]
+        self._reference: dict = {}                             # z_threshold -> the reference's own leave-one-out statistics
+        self._weights: Optional[torch.Tensor] = None
+
+    @classmethod
+    def fit(cls, cohort: ThicknessCohort, covariates=None, intercept: bool = True, names: Optional[Sequence[str]] = None) -> "NormativeModel":
+        """The model of the reference ``cohort`` on ``covariates`` ([N] or [N, c]; None: the mean alone) and, with ``intercept``, a constant.
+        Every covariate column is centred on its mean over the reference and scaled to unit length; the means and scales are kept for the
+        knees to come.  Refused by name before anything is launched: a NaN or an infinity, a constant or a collinear column (``names``: what
+        the columns are called), more than six columns, fewer than p + 2 knees."""
+        N = len(cohort)
+        design, means, scales, names = _normative_design(covariates, bool(intercept), N, names)
+        p = design.shape[1]
+        if N < p + 2:
+            raise ValueError(f"a reference of {N} knees is too small for {p} design columns: a leave-one-out score needs at least p + 2 = {p + 2}")
+        block = ops.normative_fit(cohort.values, torch.from_numpy(design).to(cohort.device), cohort.mask)
+        model = cls(cohort, block, N, bool(intercept), names, means, scales)
+        model.cohort, model.design = cohort, design
+        return model
+
+    # -- the host side of a model ---------------------------------------------------------------------------------------------------------
+    def rows(self, covariates, n_rows: int) -> np.ndarray:
+        """float64 [M, p]: the design rows of ``n_rows`` knees with ``covariates`` ([M, c]; [c] or a scalar for one knee; None for a model
+        without covariates), centred and scaled as the reference's were."""
+        c = len(self.means)
+        cov = np.zeros((n_rows, 0)) if covariates is None else np.asarray(covariates, np.float64)
+        if cov.ndim < 2:
+            cov = cov.reshape(n_rows, -1) if cov.size == n_rows * c and c > 0 else cov.reshape(1, -1)
+        if cov.shape != (n_rows, c):
+            raise ValueError(f"covariates must hold the model's {c} columns ({', '.join(self.names) or 'none'}) for each of the {n_rows} knees, "
+                             f"got shape {np.shape(covariates) if covariates is not None else None}")
+        if not np.isfinite(cov).all():
+            raise ValueError("covariates hold a NaN or an infinity")
+        return _design_rows(cov, self.intercept, self.means, self.scales)
+
+    def state(self) -> dict:
+        """What ``save`` writes, as host arrays: the model block's ``gamma``, ``L``, ``rss``, ``n``, ``ok``; ``means``, ``scales``, ``names``,
+        ``intercept``, ``kind``, ``n_knees``; and the reference's leave-one-out statistics at every threshold computed so far."""
+        host = dict(zip(_MODEL_ARRAYS, _download([getattr(self.block, name) for name in _MODEL_ARRAYS])))
+        z0 = sorted(self._reference)
+        host.update(means=self.means, scales=self.scales, names=np.asarray(self.names, dtype=np.str_), intercept=np.asarray(self.intercept),
+                    kind=np.asarray(self.kind), n_knees=np.asarray(self.n_knees, np.int64), ref_z_threshold=np.asarray(z0, np.float64))
+        for name, dtype in (("max_abs", np.float64), ("max_extent", np.int32), ("area_below", np.int64)):
+            host["ref_" + name] = np.asarray([self._reference[t][name] for t in z0], dtype).reshape(len(z0), self.n_knees)
+        return host
+
+    @staticmethod
+    def write_state(path, state: dict) -> None:
+        with open(path, "wb") as f:
+            np.savez(f, **state)
+
+    @staticmethod
+    def read_state(path) -> dict:
+        with np.load(path, allow_pickle=False) as f:
+            return {name: f[name] for name in f.files}
+
+    def save(self, path, z_thresholds: Sequence[float] = (2.0,)) -> None:
+        """Write the model as one ``.npz``: everything ``deviation`` needs for new knees -- the per-vertex fit, the centring of the
+        covariates and the reference's own leave-one-out statistics at ``z_thresholds`` (and at every threshold used so far) -- without the
+        reference's thickness maps, so that a model built once from a healthy cohort can be shipped."""
+        if self.cohort is not None:
+            for t in z_thresholds:
+                self.reference(t)
+        self.write_state(path, self.state())
+
+    @classmethod
+    def load(cls, path, atlas) -> "NormativeModel":
+        """The model that ``save`` wrote, on ``atlas`` (whose inner mesh of the model's cartilage must have the model's vertices).  It scores
+        new knees at the thresholds it was saved with; ``loo`` needs the reference and is not available."""
+        s = cls.read_state(path)
+        kind = str(s["kind"])
+        surface = ThicknessCohort(atlas, kind)
+        p, V = int(s["gamma"].shape[0]), int(s["gamma"].shape[1])
+        if V != surface.n_verts:
+            raise ValueError(f"the model has {V} vertices, the atlas' {kind} inner mesh {surface.n_verts}")
+        block = ops.normative_block(V, p, surface.device)
+        for name in _MODEL_ARRAYS:
+            getattr(block, name).copy_(torch.from_numpy(np.ascontiguousarray(s[name])))
+        model = cls(surface, block, int(s["n_knees"]), bool(s["intercept"]), [str(n) for n in s["names"]], s["means"], s["scales"])
+        for k, t in enumerate(s["ref_z_threshold"].tolist()):
+            model._reference[float(t)] = {name: s["ref_" + name][k] for name in ("max_abs", "max_extent", "area_below")}
+        return model
+
+    def predict(self, covariates=None, n_rows: int = 1) -> np.ndarray:
+        """float64 [M, V]: the expected map in mm of knees with ``covariates`` ([M, c]; M = ``n_rows`` without covariates), NaN where the
+        model has no fit."""
+        M = int(n_rows) if covariates is None or np.ndim(covariates) < 2 else int(np.shape(covariates)[0])
+        gamma, ok = _download([self.block.gamma, self.block.ok])
+        return np.where(ok[None, :] != 0, self.rows(covariates, M) @ gamma, np.nan)
+
+    # -- scoring ----------------------------------------------------------------------------------------------------------------------------
+    def _area_weights(self) -> torch.Tensor:
+        if self._weights is None:
+            self._weights = torch.from_numpy(tfce_weights(self.surface.vertex_areas())).to(self.device)
+        return self._weights
+
+    def _score(self, values: torch.Tensor, mask: torch.Tensor, design: np.ndarray, loo: bool, z_threshold: float, return_maps: bool) -> dict:
+        """The device side of both scorings, in batches of rows within ``WORKSPACE_BUDGET``: score, summary, clusters; ONE download."""
+        if not float(z_threshold) > 0.0:
+            raise ValueError(f"z_threshold must be > 0, got {z_threshold!r}")
+        M, V, dev = int(values.shape[0]), self.n_verts, self.device
+        offsets, neighbours = self.surface.surface_graph()
+        weights, design_d = self._area_weights(), torch.from_numpy(design).to(dev)
+        rows = int(max(1, min(M, WORKSPACE_BUDGET // (V * _DEVIATION_BYTES))))
+        # with maps the tiles of all batches lie behind one another in one buffer, which is the z map; 256 bytes more: a tile's size is rounded up
+        buffer = torch.empty((M if return_maps else rows) * V * 8 + 256, dtype=torch.uint8, device=dev)
+        diff = torch.empty((M, V), dtype=torch.float64, device=dev) if return_maps else None
+        extent = torch.empty(M, dtype=torch.int32, device=dev)
+        stats, counts = [], []
+        with torch.cuda.device(dev):
+            for r0 in range(0, M, rows):
+                r1 = min(r0 + rows, M)
+                tile = ops.normative_score(self.block, values[r0:r1], design_d[r0:r1], mask[r0:r1], loo=loo,
+                                           workspace=buffer[r0 * V * 8:] if return_maps else buffer, diff=diff[r0:r1] if return_maps else None)
+                s, c = ops.deviation_summary(tile, z_threshold, weights)
+                stats.append(s)
+                counts.append(c)
+                ops.graph_clusters(tile, offsets, neighbours, float(z_threshold), max_extent=extent[r0:r1])
+            bring = {"stats": torch.cat(stats), "counts": torch.cat(counts), "max_extent": extent, "n": self.block.n}
+            if return_maps:
+                bring.update(z=buffer[:M * V * 8].view(torch.float64).reshape(M, V), diff_mm=diff)
+            return dict(zip(bring, _download(list(bring.values()))))
+
+    def reference(self, z_threshold: float = 2.0) -> dict:
+        """The reference knees' own leave-one-out statistics at ``z_threshold`` -- ``max_abs`` float64, ``max_extent`` int32 and
+        ``area_below`` int64 (units of 2^-20 mm^2), [N] each -- which every p-value is a rank among; computed once and kept."""
+        key = float(z_threshold)
+        if key not in self._reference:
+            if self.cohort is None:
+                raise ValueError(f"the model was saved without the reference's statistics at z_threshold = {key}: it has them at "
+                                 f"{sorted(self._reference)}")
+            host = self._score(self.cohort.values, self.cohort.mask, self.design, True, key, False)
+            self._reference[key] = {"max_abs": host["stats"][:, 0].copy(), "max_extent": host["max_extent"], "area_below": host["counts"][:, 3].copy(),
+                                    "host": host}
+        return self._reference[key]
+
+    def _result(self, host: dict, ids, loo: bool, z_threshold: float) -> DeviationResult:
+        ref = self.reference(z_threshold)
+        stats, counts = host["stats"], host["counts"]
+        dof = host["n"].astype(np.int64) - self.n_columns - (1 if loo else 0)
+        maps = {}
+        if "z" in host:
+            from scipy import stats as scipy_stats
+            with np.errstate(invalid="ignore"):
+                p_unc = 2.0 * scipy_stats.t.sf(np.abs(host["z"]), np.maximum(dof, 1)[None, :])
+            maps = dict(z=host["z"], diff_mm=host["diff_mm"], p_uncorrected=np.where(np.isnan(host["z"]), np.nan, p_unc))
+        return DeviationResult(kind=self.kind, ids=list(ids), loo=loo, z_threshold=float(z_threshold), n_valid=counts[:, 0], max_abs=stats[:, 0],
+                               max_vertex=counts[:, 1], min_z=stats[:, 1], max_z=stats[:, 2], n_below=counts[:, 2], n_above=counts[:, 4],
+                               area_below_mm2=counts[:, 3] * _TFCE_AREA_UNIT, area_above_mm2=counts[:, 5] * _TFCE_AREA_UNIT,
+                               max_extent=host["max_extent"], dof=dof, p_max=_rank_p(stats[:, 0], ref["max_abs"], loo),
+                               p_extent=_rank_p(host["max_extent"], ref["max_extent"], loo),
+                               p_area_below=_rank_p(counts[:, 3], ref["area_below"], loo), model=self, **maps)
+
+    def loo(self, z_threshold: float = 2.0, return_maps: bool = False) -> DeviationResult:
+        """The reference's own knees, each scored against the fit WITHOUT it -- the externally studentised residual, which needs no refit --
+        and ranked among the other N - 1."""
+        ref = self.reference(z_threshold)
+        if self.cohort is None:
+            raise ValueError("a loaded model does not hold its reference: loo needs the model that was fitted")
+        host = self._score(self.cohort.values, self.cohort.mask, self.design, True, z_threshold, True) if return_maps else ref["host"]
+        return self._result(host, self.cohort.ids, True, z_threshold)
+
+    def deviation(self, cohort_or_vectors, covariates=None, z_threshold: float = 2.0, return_maps: bool = False) -> DeviationResult:
+        """Knees that are NOT in the fit -- a ``ThicknessCohort`` on the model's atlas and cartilage, or vectors [M, V] / [V] (arrays or
+        device tensors, NaN = missing) -- with their ``covariates`` ([M, c]; [c] for one knee), scored vertex by vertex and ranked among
+        the reference's N knees."""
+        knees = cohort_or_vectors
+        if not isinstance(knees, ThicknessCohort):
+            vectors = knees if isinstance(knees, torch.Tensor) else np.asarray(knees, np.float32)
+            vectors = vectors.reshape(1, -1) if vectors.ndim == 1 else vectors
+            knees = ThicknessCohort(self.atlas, self.kind, chunk=max(len(vectors), 1))
+            for row in vectors:
+                knees.add_vector(row)
+        if knees.kind != self.kind or knees.n_verts != self.n_verts:
+            raise ValueError(f"the knees are {knees.kind} maps on {knees.n_verts} vertices, the model is for {self.kind} on {self.n_verts}")
+        if len(knees) < 1:
+            raise ValueError("there is no knee to score")
+        self.reference(z_threshold)                                        # refuses a threshold a loaded model does not hold, before any launch
+        host = self._score(knees.values, knees.mask, self.rows(covariates, len(knees)), False, z_threshold, return_maps)
+        return self._result(host, knees.ids, False, z_threshold)
