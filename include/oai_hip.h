@@ -1406,6 +1406,73 @@ size_t oai_deviation_summary_workspace_bytes(long long n_rows, long long n_verts
 int oai_deviation_summary(const double* tile_dev, long long n_rows, long long n_verts, const long long* weight_dev, double z0, void* workspace_dev,
                           size_t workspace_bytes, double* stats_dev, long long* counts_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Bootstrap intervals (csrc/bootstrap.hip, tests/bootstrap_ref.py): how large is an effect, give or take what -- the coefficient of the
+ * LAST column of the per-vertex general linear model of "Cohort regression", re-estimated on resamples of the knees, and what a
+ * percentile, basic or BCa interval and a simultaneous sup-t band need from the replicates.  BCa (Efron 1987) and the sup-t band (Davison
+ * and Hinkley 1997) are as recalled and NOT pinned to any implementation; the reference has no such step, and the definitions are this
+ * library's own, pinned by the numpy restatement and, through it, scipy.stats.bootstrap.  The rules of "Cohort statistics" hold: fp64
+ * without contraction, no floating-point atomics, one accumulator per sum that starts at +0.0, EVERY SUM OVER KNEES AND OVER REPLICATES IN
+ * ASCENDING INDEX: bit-reproducible.  Nothing synchronises or reads anything back.  2 <= n_knees <= 2^24, 1 <= n_verts <= 2^31 - 2, at
+ * most 2^20 rows per call.  y_dev and mask_dev as in "Cohort statistics"; design_dev float64 [n_knees][p], knee-major, 1 <= p <= 6.
+ *
+ * oai_bootstrap_coef: one resample is a row of integer weights on the knees, counts_dev uint16 [R][n_knees]: how often knee i enters
+ * row r.  Rows [r0, r1) on the vertex span [v0, v1) -> the tile float64 [r1 - r0][v1 - v0] at the start of workspace_dev.  Per
+ * (row r, vertex v), knees i ascending, g_i the design row of knee i and G_iac = g_ia*g_ic (formed once per call, in fp64):
+ *   w_i  = m_iv ? (double)c_ri : 0.0          the weight is chosen by a select; a missing entry is never multiplied in: y enters as
+ *   u_i  = w_i * (double)y_iv                   m_iv ? (double)y_iv : 0.0.  The product is exact: 24 + 16 bits
+ *   h_a  = h_a + g_ia * u_i                   a product THEN an add
+ *   M_ac = M_ac + w_i * G_iac, c <= a         a product THEN an add, not an fma: w*G is not exact for w > 1
+ *   M = L L^T with the order and the pivot rule of "Cohort regression";  L z = h forward;  theta = z_p / L_pp
+ *   theta is NaN when a pivot was not accepted: a resample that lost the rank among the valid knees, a group drawn empty, a vertex
+ *   without values.
+ * With r0 = 0, n_dev and ok_dev (int32 [n_verts], entries [v0, v1) written; either may be null) receive n_v = sum_i m_iv and ok_v = every
+ * pivot of row 0 accepted.  mask_dev null: every entry is valid, M_r = sum_i c_ri*G_i does not depend on the vertex and is formed and
+ * factored once per row, in the same order, and the results are THE SAME BITS as with a mask of all ones.  A thread owns one vertex and
+ * R rows (R depends on p and on whether there is a mask).
+ *
+ * oai_bootstrap_moments: per vertex of a tile [n_rows][n_verts] whose row 0 is the observed data, over rows 1 .. n_rows - 1 ascending:
+ *   B' = the number of finite entries;  mean* = (sum theta*) / (double)B';  se = sqrt(sum (theta* - mean*)^2 / (double)(B' - 1)), two
+ *   passes, centred on the mean of pass 1, NaN for B' < 2;  below = #{theta* < theta^}, equal = #{theta* == theta^} among the finite
+ *   entries, theta^ the entry of row 0.  All five outputs [n_verts]: n_finite, below, equal int32; mean, se float64.
+ *
+ * oai_column_quantiles: exact order statistics per vertex of rows [first_row, n_rows) of a tile, K <= 4 probabilities, either shared
+ * (probs_host, K host doubles) or per vertex (probs_dev float64 [K][n_verts]); exactly one of the two is not null.  out_dev float64
+ * [K][n_verts], count_dev int32 [n_verts] = n', the entries that are not NaN.  Over those n' entries this is numpy >= 2's
+ * method="linear" in float64: vi = (double)(n' - 1) * q;  fl = floor(vi);  gamma = vi - fl;  at or past n' - 1 the last element with
+ * gamma = 0;  then numpy's _lerp: a + (b - a)*t for t < 0.5, else b - (b - a)*(1 - t).  n' = 0, a NaN probability or one outside [0, 1]
+ * gives NaN.  The order is the total order of the order-preserving 64-bit key map (u with the sign bit set: ~u, otherwise u | 2^63), so
+ * -0.0 sorts before +0.0: the value of np.quantile everywhere, and its bits except for the sign of a zero.  ONE PATH FOR EVERY
+ * 1 <= n_rows <= 2^20: the tile is transposed to vertex-major keys in the workspace, then an 8-pass radix select per vertex.
+ *
+ * oai_bootstrap_sup: per row r of a tile, sup_r = max over the vertices of |theta*_rv - theta^_v| / se_v -- a subtract, an abs and a
+ * divide -- where theta^_v is finite and se_v > 0, skipping NaN entries by a select; sup_dev float64 [n_rows] is a running maximum that
+ * the caller starts at 0.0 and the call raises: sup[r] = max(sup[r], sup_r), so it folds across vertex spans.  A max is exact in any
+ * order.
+ *
+ * oai_jackknife_acceleration: jack_dev float64 [n_knees][v1 - v0] is the tile of oai_bootstrap_coef for the n_knees count rows "all
+ * ones except a 0 at knee i"; stratum_dev int32 [n_knees] labels 0 .. n_strata - 1 (a knee with another label is in no stratum).  Per
+ * vertex, strata s ascending, over the knees of s valid at v, ascending:
+ *   n_s;  mean_s = (sum theta_(i)) / (double)n_s;  U_i = (double)(n_s - 1) * (mean_s - theta_(i));  sum U_i*U_i and sum (U_i*U_i)*U_i
+ *   num = num + (sum U^3) / (n_s*n_s*n_s);  den = den + (sum U^2) / (n_s*n_s)         (n_s as a double; an empty stratum is skipped)
+ *   a = (num / (den * sqrt(den))) / 6.0       the acceleration scipy.stats.bootstrap uses, the textbook one for a single stratum
+ *   a is NaN where den > 0 does not hold or any theta_(i) of a valid knee is NaN.  accel_dev float64 [v1 - v0].
+ * ---------------------------------------------------------------------------------------- */
+/* Both *_workspace_bytes: 0 for a shape the entry point refuses, a multiple of 256 otherwise. */
+size_t oai_bootstrap_coef_workspace_bytes(long long n_rows, long long n_span, long long n_knees, int n_columns);
+int oai_bootstrap_coef(const float* y_dev, const unsigned char* mask_dev, const double* design_dev, const unsigned short* counts_dev, long long n_knees,
+                       long long n_verts, int n_columns, long long v0, long long v1, long long r0, long long r1, void* workspace_dev,
+                       size_t workspace_bytes, int* n_dev, int* ok_dev, void* stream);
+int oai_bootstrap_moments(const double* tile_dev, long long n_rows, long long n_verts, int* n_finite_dev, double* mean_dev, double* se_dev,
+                          int* below_dev, int* equal_dev, void* stream);
+size_t oai_column_quantiles_workspace_bytes(long long n_rows, long long n_verts);
+int oai_column_quantiles(const double* tile_dev, long long n_rows, long long n_verts, long long first_row, int n_probs, const double* probs_host,
+                         const double* probs_dev, void* workspace_dev, size_t workspace_bytes, double* out_dev, int* count_dev, void* stream);
+int oai_bootstrap_sup(const double* tile_dev, long long n_rows, long long n_verts, const double* se_dev, double* sup_dev, void* stream);
+int oai_jackknife_acceleration(const double* jack_dev, const unsigned char* mask_dev, const int* stratum_dev, long long n_knees, long long n_verts,
+                               long long v0, long long v1, int n_strata, double* accel_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

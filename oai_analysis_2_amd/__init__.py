@@ -41,7 +41,8 @@ def __getattr__(name):
         return getattr(thickness, name)
     if name in ("ThicknessCohort", "PermutationResult", "two_sample_test", "paired_test", "label_permutations", "sign_flips",
                 "RegressionResult", "IndexPermutations", "regression_test", "index_permutations", "FResult", "f_test", "anova_test",
-                "LongitudinalCohort", "visit_table", "one_sample_test", "VisitSlopes"):
+                "LongitudinalCohort", "visit_table", "one_sample_test", "VisitSlopes",
+                "BootstrapCounts", "BootstrapResult", "bootstrap_counts", "bootstrap_ci"):
         from . import stats
         return getattr(stats, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -159,6 +159,14 @@ SIGNATURES = {
     "oai_normative_score": (_I, [_P, _Z, _P, _P, _P, C.c_longlong, C.c_longlong, _I, _I, _P, _Z, _P, _P]),
     "oai_deviation_summary_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
     "oai_deviation_summary": (_I, [_P, C.c_longlong, C.c_longlong, _P, _D, _P, _Z, _P, _P, _P]),
+    "oai_bootstrap_coef_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong, C.c_longlong, _I]),
+    "oai_bootstrap_coef": (_I, [_P, _P, _P, _P, C.c_longlong, C.c_longlong, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _P, _Z,
+                                _P, _P, _P]),
+    "oai_bootstrap_moments": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, _P, _P, _P, _P]),
+    "oai_column_quantiles_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_column_quantiles": (_I, [_P, C.c_longlong, C.c_longlong, C.c_longlong, _I, C.POINTER(_D), _P, _P, _Z, _P, _P, _P]),
+    "oai_bootstrap_sup": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, _P]),
+    "oai_jackknife_acceleration": (_I, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _I, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

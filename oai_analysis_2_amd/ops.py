@@ -1092,3 +1092,145 @@ def deviation_summary(tile: torch.Tensor, z_threshold: float, weights: Optional[
     _lib.call("oai_deviation_summary", tile.data_ptr(), R, V, _ptr(weights), float(z_threshold), ws.data_ptr(), ws.numel(), stats.data_ptr(),
               counts.data_ptr(), _lib.STREAM, device=dev)
     return stats, counts
+
+
+# ---- bootstrap intervals (include/oai_hip.h, "Bootstrap intervals"; csrc/bootstrap.hip) -----------------------------------------------------
+MAX_QUANTILES = 4                    # probabilities per call of column_quantiles
+
+
+def _span_vector(t: Optional[torch.Tensor], name: str, dtype, n: int, device) -> torch.Tensor:
+    """The caller's contiguous [n] output of ``dtype`` on ``device`` once it is checked, or a new one."""
+    if t is None:
+        return torch.empty(n, dtype=dtype, device=device)
+    if t.dtype != dtype or tuple(t.shape) != (n,) or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[1]} [{n}] tensor on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _replicate_tile(tile: torch.Tensor, name: str = "tile"):
+    tile = _chk(tile, name, torch.float64)
+    if tile.dim() != 2 or tile.shape[0] < 1 or tile.shape[1] < 1:
+        raise ValueError(f"{name} must be [R >= 1, V >= 1], got {tuple(tile.shape)}")
+    return tile, int(tile.shape[0]), int(tile.shape[1])
+
+
+def bootstrap_coef(values: torch.Tensor, design: torch.Tensor, counts: torch.Tensor, r0: int, r1: int, mask: Optional[torch.Tensor] = None,
+                   v0: int = 0, v1: Optional[int] = None, workspace: Optional[torch.Tensor] = None, n: Optional[torch.Tensor] = None,
+                   ok: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The coefficient tile of rows [r0, r1) of ``counts`` (uint16 [R,N] on the device: how often knee i enters resample r; row 0 all ones
+    by convention) on the vertex span [v0, v1): float64 [r1 - r0, v1 - v0], the coefficient of the LAST column of the float64 ``design``
+    [N,p] (1 <= p <= 6) in the per-vertex weighted least squares of the float32 ``values`` [N,V] over the knees that the uint8 / bool
+    ``mask`` [N,V] calls valid (None: all), NaN where the resample has no full rank there.  ``n``, ``ok`` int32 [V]: with ``r0`` = 0 their
+    entries [v0, v1) receive the valid knees and whether row 0 has a coefficient.  ``workspace``: a uint8 device buffer of
+    ``oai_bootstrap_coef_workspace_bytes`` (reused between spans) instead of a new one; the tile is its front.  fp64 in a stated order:
+    bit-reproducible.  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or values.shape[0] < 2 or values.shape[1] < 1:
+        raise ValueError(f"values must be [N >= 2, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V, dev = int(values.shape[0]), int(values.shape[1]), values.device
+    design = _design(design, "design", N, dev, 1, MAX_DESIGN_COLUMNS)
+    p = int(design.shape[1])
+    counts = _chk(counts, "counts", torch.uint16)
+    if counts.dim() != 2 or counts.shape[1] != N or counts.device != dev:
+        raise ValueError(f"counts must be uint16 [R, {N}] on {dev}, got {tuple(counts.shape)} on {counts.device}")
+    r0, r1, v0, v1 = int(r0), int(r1), int(v0), V if v1 is None else int(v1)
+    if not 0 <= r0 < r1 <= counts.shape[0]:
+        raise ValueError(f"rows [{r0}, {r1}) are not rows of the {counts.shape[0]} resamples")
+    if not 0 <= v0 < v1 <= V:
+        raise ValueError(f"the span [{v0}, {v1}) does not lie in the {V} vertices")
+    n = None if n is None else _span_vector(n, "n", torch.int32, V, dev)
+    ok = None if ok is None else _span_vector(ok, "ok", torch.int32, V, dev)
+    need = int(_lib.load().oai_bootstrap_coef_workspace_bytes(r1 - r0, v1 - v0, N, p))
+    ws = _tile_workspace(workspace, need, dev)
+    _lib.call("oai_bootstrap_coef", values.data_ptr(), _ptr(mask), design.data_ptr(), counts.data_ptr(), N, V, p, v0, v1, r0, r1, ws.data_ptr(),
+              ws.numel(), _ptr(n), _ptr(ok), _lib.STREAM, device=dev)
+    return ws[:(r1 - r0) * (v1 - v0) * 8].view(torch.float64).reshape(r1 - r0, v1 - v0)
+
+
+@dataclass
+class BootstrapMoments:
+    """Per vertex of a replicate tile, over rows 1..: ``n_finite`` int32 (B'), ``mean``, ``se`` float64, and the int32 counts ``below``,
+    ``equal`` of the finite replicates below / equal to row 0's entry.  DEVICE tensors [V]."""
+    n_finite: torch.Tensor
+    mean: torch.Tensor
+    se: torch.Tensor
+    below: torch.Tensor
+    equal: torch.Tensor
+
+
+def bootstrap_moments(tile: torch.Tensor) -> BootstrapMoments:
+    """What an interval needs from the replicates of the float64 ``tile`` [R,V] (row 0 the observed data, rows 1.. the resamples) besides
+    their order statistics: see ``BootstrapMoments``.  Two passes in ascending row, fp64: bit-reproducible.  Does not synchronise."""
+    tile, R, V = _replicate_tile(tile)
+    dev = tile.device
+    out = BootstrapMoments(torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.float64, device=dev),
+                           torch.empty(V, dtype=torch.float64, device=dev), torch.empty(V, dtype=torch.int32, device=dev),
+                           torch.empty(V, dtype=torch.int32, device=dev))
+    _lib.call("oai_bootstrap_moments", tile.data_ptr(), R, V, out.n_finite.data_ptr(), out.mean.data_ptr(), out.se.data_ptr(), out.below.data_ptr(),
+              out.equal.data_ptr(), _lib.STREAM, device=dev)
+    return out
+
+
+def column_quantiles(tile: torch.Tensor, probabilities, first_row: int = 0, workspace: Optional[torch.Tensor] = None):
+    """Exact quantiles per vertex of rows [first_row, R) of the float64 ``tile`` [R,V], over the entries that are not NaN, as
+    ``np.quantile(..., method="linear")`` in float64 (-0.0 sorts before +0.0).  ``probabilities``: a sequence of K <= 4 floats shared by all
+    vertices, or a float64 DEVICE tensor [K,V] of per-vertex ones.  Returns (float64 [K,V], int32 [V] = the entries that are not NaN),
+    DEVICE tensors; NaN for a vertex without entries and for a probability that is NaN or outside [0, 1].  ``workspace``: a uint8 device
+    buffer of ``oai_column_quantiles_workspace_bytes`` instead of a new one.  Does not synchronise."""
+    tile, R, V = _replicate_tile(tile)
+    dev = tile.device
+    first_row = int(first_row)
+    if not 0 <= first_row <= R:
+        raise ValueError(f"first_row must be 0 .. {R}, got {first_row}")
+    if isinstance(probabilities, torch.Tensor):
+        probs = _chk(probabilities, "probabilities", torch.float64)
+        if probs.dim() != 2 or not 1 <= probs.shape[0] <= MAX_QUANTILES or probs.shape[1] != V or probs.device != dev:
+            raise ValueError(f"per-vertex probabilities must be float64 [1 .. {MAX_QUANTILES}, {V}] on {dev}, got {tuple(probs.shape)} on {probs.device}")
+        K, host, device_ptr = int(probs.shape[0]), None, probs.data_ptr()
+    else:
+        q = [float(x) for x in np.asarray(probabilities, np.float64).reshape(-1)]
+        if not 1 <= len(q) <= MAX_QUANTILES:
+            raise ValueError(f"needs 1 .. {MAX_QUANTILES} probabilities, got {len(q)}")
+        K, host, device_ptr = len(q), (C.c_double * len(q))(*q), None
+    out = torch.empty((K, V), dtype=torch.float64, device=dev)
+    count = torch.empty(V, dtype=torch.int32, device=dev)
+    need = int(_lib.load().oai_column_quantiles_workspace_bytes(R, V))
+    ws = _tile_workspace(workspace, need, dev)
+    _lib.call("oai_column_quantiles", tile.data_ptr(), R, V, first_row, K, host, device_ptr, ws.data_ptr(), ws.numel(), out.data_ptr(),
+              count.data_ptr(), _lib.STREAM, device=dev)
+    return out, count
+
+
+def bootstrap_sup(tile: torch.Tensor, se: torch.Tensor, sup: torch.Tensor) -> None:
+    """Raise the running ``sup`` float64 [R] (started at 0.0 by the caller) by each row's max over the vertices of
+    |tile[r, v] - tile[0, v]| / se[v], taken where row 0's entry is finite and ``se`` > 0 and the entry is not NaN: the sup-t statistic of
+    a simultaneous band, folded across vertex spans.  A max: exact in any order.  Does not synchronise."""
+    tile, R, V = _replicate_tile(tile)
+    dev = tile.device
+    se, sup = _span_vector(se, "se", torch.float64, V, dev), _span_vector(sup, "sup", torch.float64, R, dev)
+    _lib.call("oai_bootstrap_sup", tile.data_ptr(), R, V, se.data_ptr(), sup.data_ptr(), _lib.STREAM, device=dev)
+
+
+def jackknife_acceleration(jack: torch.Tensor, strata: torch.Tensor, n_strata: int, mask: Optional[torch.Tensor] = None, v0: int = 0) -> torch.Tensor:
+    """The BCa acceleration per vertex from the float64 jackknife tile ``jack`` [N, span] (``bootstrap_coef`` of the N count rows "all
+    ones except a 0 at knee i" on the span that starts at ``v0``), the int32 stratum label of every knee (0 .. ``n_strata`` - 1) and the
+    cohort's uint8 / bool ``mask`` [N,V] (None: every knee valid): float64 [span] on the device, NaN where it does not exist
+    (include/oai_hip.h has the formula; a single stratum gives the textbook one).  Does not synchronise."""
+    jack, N, span = _replicate_tile(jack, "jack")
+    dev = jack.device
+    strata = _span_vector(strata, "strata", torch.int32, N, dev)
+    v0 = int(v0)
+    if mask is not None:
+        mask = _chk(mask.view(torch.uint8) if mask.dtype == torch.bool else mask, "mask", torch.uint8)
+        if mask.dim() != 2 or mask.shape[0] != N or mask.device != dev:
+            raise ValueError(f"mask must be [{N}, V] on {dev}, got {tuple(mask.shape)} on {mask.device}")
+    V = int(mask.shape[1]) if mask is not None else v0 + span
+    if N < 2 or not 0 <= v0 <= V - span:
+        raise ValueError(f"the jackknife tile needs N >= 2 rows and a span [{v0}, {v0 + span}) within the {V} vertices")
+    if not 1 <= int(n_strata) <= 1 << 16:
+        raise ValueError(f"n_strata must be 1 .. 65536, got {n_strata!r}")
+    accel = torch.empty(span, dtype=torch.float64, device=dev)
+    _lib.call("oai_jackknife_acceleration", jack.data_ptr(), _ptr(mask), strata.data_ptr(), N, V, v0, v0 + span, int(n_strata), accel.data_ptr(),
+              _lib.STREAM, device=dev)
+    return accel

@@ -54,6 +54,13 @@ statistics (include/oai_hip.h, "Normative deviation"; csrc/normative.hip; tests/
     model = NormativeModel.fit(healthy, covariates=np.stack([age, sex, bmi], axis=1), names=["age", "sex", "bmi"])
     res = model.deviation(knee_vector, covariates=[71.0, 1.0, 31.2], return_maps=True)
     res.p_max, res.area_below_mm2, res.clusters(0), res.image(atlas, "z")
+
+``bootstrap_ci`` says how large an effect is, give or take what: the nonparametric bootstrap of the mean map, of an adjusted group
+difference or of a slope, with percentile, basic or BCa intervals per vertex and a simultaneous sup-t band over the surface
+(include/oai_hip.h, "Bootstrap intervals"; csrc/bootstrap.hip; tests/bootstrap_ref.py).
+
+    ci = bootstrap_ci(rate, n_bootstrap=2000, method="bca", simultaneous=True)      # mm / year [lower, upper]
+    ci.estimate, ci.lower, ci.upper, ci.lower_simultaneous, ci.image(atlas, "se")
 """
 from __future__ import annotations
 
@@ -1651,3 +1658,230 @@ class NormativeModel:
         self.reference(z_threshold)                                        # refuses a threshold a loaded model does not hold, before any launch
         host = self._score(knees.values, knees.mask, self.rows(covariates, len(knees)), False, z_threshold, return_maps)
         return self._result(host, knees.ids, False, z_threshold)
+
+
+# ---- bootstrap intervals ---------------------------------------------------------------------------------------------------------------
+BOOTSTRAP_METHODS = ("percentile", "basic", "bca")
+MAX_BOOTSTRAP_ROWS = 1 << 20          # rows of one call of the bootstrap kernels: the observed row and the resamples
+
+
+@dataclass
+class BootstrapCounts:
+    """``counts``: uint16 [B + 1, N] -- how often knee i enters resample r; row 0 is all ones, the observed data."""
+    counts: np.ndarray
+
+    def __len__(self) -> int:
+        return int(self.counts.shape[0])
+
+
+def bootstrap_counts(n_knees: int, n_bootstrap: int, seed: int = 0, blocks=None) -> BootstrapCounts:
+    """Resamples for ``bootstrap_ci``: row 0 all ones, every other row the multiplicities of N draws with replacement.  ``blocks``: an int
+    label per knee (group, site, ...); knees are then resampled WITHIN a block only, so every row keeps every block's size.  Per block,
+    in ascending block label, rows 1.. come from ``np.random.Generator(np.random.PCG64(seed)).integers(0, n_b, size=(B, n_b))``, binned.
+    A multiplicity above 65535 is refused."""
+    N, B = int(n_knees), int(n_bootstrap)
+    if N < 1 or B < 1:
+        raise ValueError(f"n_knees and n_bootstrap must be >= 1, got {n_knees}, {n_bootstrap}")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    counts = np.zeros((B + 1, N), np.int64)
+    counts[0] = 1
+    for idx in _block_members(blocks, N):
+        nb = len(idx)
+        draws = rng.integers(0, nb, size=(B, nb))
+        counts[1:, idx] = np.bincount((draws + np.arange(B)[:, None] * nb).ravel(), minlength=B * nb).reshape(B, nb)
+    if counts.max() > 65535:
+        raise ValueError("a knee enters a resample more than 65535 times: the counts are 16-bit")
+    return BootstrapCounts(counts.astype(np.uint16))
+
+
+def _count_rows(counts, make, n_knees: int) -> BootstrapCounts:
+    rows = make() if counts is None else counts
+    c = np.atleast_2d(rows.counts if isinstance(rows, BootstrapCounts) else np.asarray(rows))
+    if c.ndim != 2 or c.shape[1] != n_knees or not np.issubdtype(c.dtype, np.integer) or c.shape[0] < 2:
+        raise ValueError(f"counts must be integer rows [B + 1 >= 2, {n_knees}], got {c.dtype} {c.shape}")
+    if c.min() < 0 or c.max() > 65535:
+        raise ValueError("every count must be 0 .. 65535")
+    if not (c[0] == 1).all():
+        raise ValueError("row 0 of the counts must be all ones: the observed data")
+    return BootstrapCounts(np.ascontiguousarray(c, dtype=np.uint16))
+
+
+def bootstrap_span(n_rows: int, n_verts: int, budget: int = WORKSPACE_BUDGET) -> int:
+    """Vertices per span of ``bootstrap_ci``: what keeps the replicate tile [B + 1][span] within ``budget`` bytes, in whole blocks of 256
+    vertices where that leaves one, at least one vertex.  (The quantile step holds a second buffer of the tile's size.)"""
+    span = max(int(budget) // (8 * int(n_rows)), 1)
+    span = span // 256 * 256 if span >= 256 else span
+    return int(min(span, int(n_verts)))
+
+
+def _bca_probabilities(below, equal, n_finite, acceleration, level: float):
+    """(z0 [V], probabilities [2, V]) of the BCa interval, float64 on the host: z0 = Phi^-1((below + (below + equal)) / (2 B')), and with
+    z_alpha = Phi^-1((1 - level) / 2) the adjusted probabilities Phi(z0 + (z0 -+ z_alpha) / (1 - a (z0 -+ z_alpha)))."""
+    from scipy import special
+    alpha = (1.0 - float(level)) / 2.0
+    with np.errstate(all="ignore"):
+        z0 = special.ndtri((below + (below + equal)).astype(np.float64) / (2.0 * n_finite.astype(np.float64)))
+        z_alpha = special.ndtri(alpha)
+        z_1alpha = -z_alpha
+        num1 = z0 + z_alpha
+        p_low = special.ndtr(z0 + num1 / (1.0 - acceleration * num1))
+        num2 = z0 + z_1alpha
+        p_high = special.ndtr(z0 + num2 / (1.0 - acceleration * num2))
+    return z0, np.ascontiguousarray(np.stack([p_low, p_high]))
+
+
+@dataclass
+class BootstrapResult:
+    """``estimate`` float64 [V]: the mean ("mean"), the adjusted difference of the larger group label from the smaller ("difference") or the
+    slope per unit of ``x`` ("slope"), NaN where the model has no full rank among the knees with a value; ``se`` the standard deviation of
+    its finite replicates (n - 1 in the denominator); ``lower``, ``upper`` the ``level`` interval by ``method``; ``n`` the knees with a
+    value and ``n_finite`` the finite replicates B' per vertex.  ``z0``, ``acceleration``: the bias correction and the jackknife
+    acceleration of "bca", otherwise None.  With ``simultaneous``: ``sup`` the sup-t statistic of every row (entry 0 observed: 0.0),
+    ``critical`` its ``level`` quantile over the resamples, and ``lower_simultaneous``, ``upper_simultaneous`` = estimate -+ critical * se,
+    a band that covers the whole surface at once; otherwise None."""
+    kind: str
+    what: str
+    estimate: np.ndarray
+    se: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+    level: float
+    method: str
+    n: np.ndarray
+    n_finite: np.ndarray
+    n_bootstrap: int
+    z0: Optional[np.ndarray] = None
+    acceleration: Optional[np.ndarray] = None
+    sup: Optional[np.ndarray] = None
+    critical: Optional[float] = None
+    lower_simultaneous: Optional[np.ndarray] = None
+    upper_simultaneous: Optional[np.ndarray] = None
+
+    IMAGES = ("estimate", "se", "lower", "upper", "n", "n_finite", "z0", "acceleration", "lower_simultaneous", "upper_simultaneous")
+
+    def image(self, atlas, what: str = "estimate"):
+        """``atlas.image`` of one of ``IMAGES`` (float32 [H, W], NaN off the surface)."""
+        if what not in self.IMAGES:
+            raise ValueError(f"no image of {what!r}")
+        vec = getattr(self, what)
+        if vec is None:
+            raise ValueError("the interval is not a bca one" if what in ("z0", "acceleration") else "the interval was computed without simultaneous")
+        return atlas.image(np.asarray(vec, np.float32), self.kind)
+
+
+def _bootstrap_design(x, groups, covariates, intercept: bool, blocks, n_knees: int):
+    """(what, design [N, p], the scale the last column was divided by, the int block label of every knee for resampling and strata)."""
+    N = n_knees
+    if blocks is not None and np.shape(blocks) != (N,):
+        raise ValueError(f"blocks must hold one label per knee ({N}), got shape {np.shape(blocks)}")
+    labels = np.zeros(N, np.int64) if blocks is None else np.unique(np.asarray(blocks), return_inverse=True)[1].reshape(-1).astype(np.int64)
+    if x is not None and groups is not None:
+        raise ValueError("give x (a slope) or groups (a difference), not both")
+    if x is None and groups is None:
+        if covariates is not None or not intercept:
+            raise ValueError("the mean map is the intercept alone: covariates and intercept=False need x or groups")
+        return "mean", np.ones((N, 1)), 1.0, labels
+    if groups is not None:
+        g = np.asarray(groups)
+        if g.shape != (N,):
+            raise ValueError(f"groups must hold one label per knee of the cohort ({N}), got shape {g.shape}")
+        levels, which = np.unique(g, return_inverse=True)
+        if len(levels) != 2:
+            raise ValueError(f"groups must hold exactly two labels, got {len(levels)}")
+        _, design, scale = _design_columns(which.reshape(-1).astype(np.float64), covariates, intercept, N)
+        return "difference", design, scale, labels * 2 + which.reshape(-1)               # resampled within block and group
+    _, design, scale = _design_columns(x, covariates, intercept, N)
+    return "slope", design, scale, labels
+
+
+def bootstrap_ci(cohort: ThicknessCohort, x=None, groups=None, covariates=None, intercept: bool = True, n_bootstrap: int = 2000,
+                 level: float = 0.95, method: str = "percentile", simultaneous: bool = False, blocks=None, seed: int = 0, counts=None,
+                 batch: Optional[int] = None) -> BootstrapResult:
+    """How large is the effect, give or take what?  The nonparametric bootstrap of one coefficient of the per-vertex linear model, over the
+    knees with a value at the vertex (include/oai_hip.h, "Bootstrap intervals"; csrc/bootstrap.hip; tests/bootstrap_ref.py).
+
+    With neither ``x`` nor ``groups``: the mean map (the design is the intercept alone) -- on ``LongitudinalCohort.change("rate")`` the loss
+    in mm per year with its interval.  With ``groups`` (two labels): the difference of the larger label from the smaller, adjusted for
+    ``covariates``; knees are resampled within a group, so no group is ever drawn empty.  With ``x``: the slope per unit of ``x`` as passed.
+    ``covariates``, ``intercept`` and the design checks are ``regression_test``'s.  ``blocks``: an int label per knee; knees are resampled
+    within a block only.  The resamples are ``bootstrap_counts(N, n_bootstrap, seed, blocks)`` or ``counts`` (a ``BootstrapCounts`` or
+    integer rows [B + 1, N], row 0 all ones).
+
+    ``method``: "percentile" (the ``level`` quantiles of the replicates), "basic" (those reflected about the estimate) or "bca" (Efron's
+    bias-corrected and accelerated percentiles, the acceleration from a leave-one-knee-out jackknife per resampling stratum).
+    ``simultaneous``: also the sup-t band estimate -+ critical * se, which covers all vertices at once.
+
+    The work runs in vertex spans of ``batch`` vertices (default ``bootstrap_span``: the tile [B + 1][span] fits ``WORKSPACE_BUDGET``),
+    because a vertex's order statistics need all its replicates at once; the result does not depend on the span.  "percentile" and
+    "basic" download once, at the end.  "bca" adds per span one small download (below, equal, B', a) and one upload of [2][span]
+    probabilities, since the adjusted probabilities are formed on the host with ``scipy.special``.
+
+    Limits: at most six design columns and one coefficient; percentile-type intervals only (no studentised bootstrap-t); a missing entry
+    travels with its knee, so missingness is resampled with the data; the replicates are Monte Carlo, so two seeds give two intervals;
+    no significance level or coverage claim is built in."""
+    if method not in BOOTSTRAP_METHODS:
+        raise ValueError(f"method must be one of {BOOTSTRAP_METHODS}, got {method!r}")
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"level must lie in (0, 1), got {level!r}")
+    N = len(cohort)
+    if N < 2:
+        raise ValueError("bootstrap_ci needs at least two knees")
+    what, design, scale, labels = _bootstrap_design(x, groups, covariates, bool(intercept), blocks, N)
+    rows = _count_rows(counts, lambda: bootstrap_counts(N, n_bootstrap, seed, labels), N)
+    R = len(rows)
+    if R > MAX_BOOTSTRAP_ROWS:
+        raise ValueError(f"at most {MAX_BOOTSTRAP_ROWS - 1} resamples are supported, got {R - 1}")
+    values, mask = cohort.values, cohort.mask
+    V, dev = int(values.shape[1]), values.device
+    span = bootstrap_span(R, V) if batch is None else int(batch)
+    if span < 1:
+        raise ValueError(f"batch must be >= 1 vertices, got {batch!r}")
+    span = min(span, V)
+    p = design.shape[1]
+    design_d, counts_d = torch.from_numpy(np.ascontiguousarray(design)).to(dev), torch.from_numpy(rows.counts).to(dev)
+    ws = _lib.workspace("oai_bootstrap_coef", dev, R, span, N, p)
+    ws_q = _lib.workspace("oai_column_quantiles", dev, R, span)
+    bca = method == "bca"
+    if bca:
+        strata, n_strata = np.unique(labels, return_inverse=True)[1].reshape(-1).astype(np.int32), len(np.unique(labels))
+        strata_d = torch.from_numpy(strata).to(dev)
+        jack_d = torch.from_numpy((1 - np.eye(N, dtype=np.int64)).astype(np.uint16)).to(dev)
+        ws_j = _lib.workspace("oai_bootstrap_coef", dev, N, span, N, p)
+        z0, accel = np.empty(V), np.empty(V)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    estimate, se, quant = f64(V), f64(V), f64(2, V)
+    n_valid = torch.empty(V, dtype=torch.int32, device=dev)
+    n_finite = torch.empty(V, dtype=torch.int32, device=dev)
+    sup = torch.zeros(R, dtype=torch.float64, device=dev) if simultaneous else None
+    alpha = (1.0 - level) / 2.0
+    for a in range(0, V, span):
+        b = min(a + span, V)
+        tile = ops.bootstrap_coef(values, design_d, counts_d, 0, R, mask=mask, v0=a, v1=b, workspace=ws, n=n_valid)
+        mom = ops.bootstrap_moments(tile)
+        estimate[a:b].copy_(tile[0])
+        se[a:b].copy_(mom.se)
+        n_finite[a:b].copy_(mom.n_finite)
+        if simultaneous:
+            ops.bootstrap_sup(tile, mom.se, sup)
+        if bca:
+            jack = ops.bootstrap_coef(values, design_d, jack_d, 0, N, mask=mask, v0=a, v1=b, workspace=ws_j)
+            acc = ops.jackknife_acceleration(jack, strata_d, n_strata, mask=mask, v0=a)
+            below, equal, finite, accel[a:b] = _download([mom.below, mom.equal, mom.n_finite, acc])
+            z0[a:b], probs = _bca_probabilities(below, equal, finite, accel[a:b], level)
+            q, _ = ops.column_quantiles(tile, torch.from_numpy(probs).to(dev), first_row=1, workspace=ws_q)
+        else:
+            q, _ = ops.column_quantiles(tile, (alpha, 1.0 - alpha), first_row=1, workspace=ws_q)
+        quant[:, a:b].copy_(q)
+    host = _download([estimate, se, quant, n_valid, n_finite] + ([sup] if simultaneous else []))
+    est, q = host[0], host[2]
+    low, high = (2.0 * est - q[1], 2.0 * est - q[0]) if method == "basic" else (q[0], q[1])
+    res = BootstrapResult(kind=cohort.kind, what=what, estimate=est / scale, se=host[1] / scale, lower=low / scale, upper=high / scale, level=level,
+                          method=method, n=host[3], n_finite=host[4], n_bootstrap=R - 1)
+    if bca:
+        res.z0, res.acceleration = z0, accel
+    if simultaneous:
+        res.sup = host[5]
+        res.critical = float(np.quantile(res.sup[1:], level))
+        res.lower_simultaneous, res.upper_simultaneous = res.estimate - res.critical * res.se, res.estimate + res.critical * res.se
+    return res
