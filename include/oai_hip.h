@@ -1473,6 +1473,65 @@ int oai_bootstrap_sup(const double* tile_dev, long long n_rows, long long n_vert
 int oai_jackknife_acceleration(const double* jack_dev, const unsigned char* mask_dev, const int* stratum_dev, long long n_knees, long long n_verts,
                                long long v0, long long v1, int n_strata, double* accel_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Rank transform (csrc/rank_transform.hip, tests/rank_transform_ref.py): per vertex the midranks of the knees that have a value there,
+ * the rank sums of groups of knees, and scores of the ranks -- what Mann-Whitney, Wilcoxon signed-rank, Kruskal-Wallis, Spearman and
+ * the rank-based inverse-normal transform start from.  The reference has no such step; the definitions are this library's own, pinned
+ * by a restatement through scipy.stats.rankdata and, through it, scipy's own tests.  values_dev float32 [n_knees][n_verts] (knee-major,
+ * the cohort's own layout) and mask_dev uint8 [n_knees][n_verts] or null, as in "Cohort statistics".  Nothing synchronises or reads
+ * anything back.  1 <= n_knees <= 2^22, so a midrank is exact in float32; 1 <= n_verts <= 2^31 - 2.
+ *
+ * oai_column_ranks, mode OAI_RANK_PLAIN or OAI_RANK_SIGNED.
+ *   Validity.  An entry is valid iff its mask is non-zero (every entry, with a null mask) and its value is not NaN.  In signed mode the
+ *     value must also be != 0.0f: scipy's zero_method="wilcox" drops zeros before ranking.
+ *   Key.  The key is y in plain mode and fabsf(y) in signed mode.  Comparison is float < and ==, so -0.0 ties +0.0, and +-inf are
+ *     ordinary values.
+ *   Rank.  For a valid entry i at vertex v, over the valid j at v:
+ *     less_i  = #{j: k_j < k_i}
+ *     equal_i = #{j: k_j == k_i}                 (i itself included)
+ *     twice_rank_i = 2*less_i + equal_i + 1      twice the midrank of scipy.stats.rankdata(method="average")
+ *     In signed mode the result is negated where y < 0.
+ *   Outputs.  twice_rank_dev int32 [n_knees][n_verts], 0 where the entry is not valid; n_valid_dev int32 [n_verts];
+ *     tie_term_dev int64 [n_verts] = sum over valid i of (equal_i^2 - 1), which equals the sum over tie groups of (t^3 - t), the
+ *     correction that Kruskal-Wallis and the asymptotic variances use.
+ *   Everything is an integer count, so the result does not depend on launch geometry or on the order anything ran in (the one atomic
+ *   is a 64-bit integer add).  The form is O(n_knees^2 n_verts) compares: a lane owns a vertex and sixteen of its rows and walks all
+ *   rows once per sixteen.
+ *
+ * oai_rank_sums: labels_host uint8 [n_knees], A HOST ARRAY, the group 0 .. n_groups - 1 of every knee, 1 <= n_groups <= 16; a label
+ * >= n_groups is refused before any launch, which is why the labels are not a device array.  n_g_dev int32 [n_groups][n_verts] = the
+ * valid entries (twice_rank != 0) of group g; twice_sum_g_dev int64 [n_groups][n_verts] = sum of |twice_rank| over them.  labels_host
+ * null: n_groups must be 2, and group 0 is the negative entries and group 1 the positive ones -- 2 W- and 2 W+ of the signed ranks.
+ * Integer sums: exact in any order.
+ *
+ * oai_rank_scores: twice_rank_dev and n_valid_dev as oai_column_ranks wrote them, a kind and a constant c in [0, 1/2] (read by
+ * OAI_SCORE_NORMAL alone) -> score_dev float64 [n_knees][n_verts] and mask_dev uint8 [n_knees][n_verts] = (twice_rank != 0); the score
+ * of an entry that is not valid is 0.0.
+ *   OAI_SCORE_RANK:     0.5 * twice_rank, sign kept.  Exact.
+ *   OAI_SCORE_CENTRED:  0.5 * twice_rank - 0.5 * (n_valid + 1).  Exact.
+ *   OAI_SCORE_NORMAL:   Phi^-1((r - c) / (n_valid - 2c + 1)) with r = 0.5 * |twice_rank|, the sign of twice_rank re-applied (signed
+ *     mode); the probability is formed in float64 as (r - c) / ((n - 2.0*c) + 1.0).  The named constants: Blom 3/8 (the default of
+ *     the Python layer), Tukey 1/3, Bliss-Rankit 1/2, van der Waerden 0.  The default is as recalled from PALM's -inormal and is
+ *     pinned to no implementation.
+ *   Phi^-1 on the device: work on the lower tail, q = min(p, 1 - p); start from x = -sqrt(-2 ln q), or from 2.5 (q - 1/2) when
+ *   q > 0.2; four Halley steps on erfc(-x / sqrt 2) / 2 - q: u = (F - q) / phi(x), x <- x - u / (1 + x u / 2); mirror for p > 1/2.  Four
+ *   is the smallest count at which the comparison with scipy.special.ndtri no longer improves.  The device erfc, exp and log are not
+ *   numpy's: this ONE output is held to a tolerance, not to the bit (tests/test_rank_transform_gpu.py states the measured error and the
+ *   gate).
+ * ---------------------------------------------------------------------------------------- */
+#define OAI_RANK_PLAIN 0
+#define OAI_RANK_SIGNED 1
+#define OAI_SCORE_RANK 0
+#define OAI_SCORE_CENTRED 1
+#define OAI_SCORE_NORMAL 2
+int oai_column_ranks(const float* values_dev, const unsigned char* mask_dev, long long n_knees, long long n_verts, int mode, int* twice_rank_dev,
+                     int* n_valid_dev, long long* tie_term_dev, void* stream);
+int oai_rank_sums(const int* twice_rank_dev, const unsigned char* labels_host, long long n_knees, long long n_verts, int n_groups, int* n_g_dev,
+                  long long* twice_sum_g_dev, void* stream);
+int oai_rank_scores(const int* twice_rank_dev, const int* n_valid_dev, long long n_knees, long long n_verts, int kind, double c, double* score_dev,
+                    unsigned char* mask_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

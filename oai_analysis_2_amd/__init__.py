@@ -42,7 +42,9 @@ def __getattr__(name):
     if name in ("ThicknessCohort", "PermutationResult", "two_sample_test", "paired_test", "label_permutations", "sign_flips",
                 "RegressionResult", "IndexPermutations", "regression_test", "index_permutations", "FResult", "f_test", "anova_test",
                 "LongitudinalCohort", "visit_table", "one_sample_test", "VisitSlopes",
-                "BootstrapCounts", "BootstrapResult", "bootstrap_counts", "bootstrap_ci"):
+                "BootstrapCounts", "BootstrapResult", "bootstrap_counts", "bootstrap_ci",
+                "Ranking", "RankSumResult", "SignedRankResult", "KruskalResult", "SpearmanResult", "rank_sum_test", "signed_rank_test",
+                "kruskal_test", "spearman_test"):
         from . import stats
         return getattr(stats, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

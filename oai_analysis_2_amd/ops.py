@@ -1234,3 +1234,90 @@ def jackknife_acceleration(jack: torch.Tensor, strata: torch.Tensor, n_strata: i
     _lib.call("oai_jackknife_acceleration", jack.data_ptr(), _ptr(mask), strata.data_ptr(), N, V, v0, v0 + span, int(n_strata), accel.data_ptr(),
               _lib.STREAM, device=dev)
     return accel
+
+
+# ---- rank transform (include/oai_hip.h, "Rank transform"; csrc/rank_transform.hip) ------------------------------------------------------------
+OAI_RANK_PLAIN, OAI_RANK_SIGNED = 0, 1
+SCORE_KINDS = {"rank": 0, "centred": 1, "normal": 2}
+MAX_RANK_KNEES = 1 << 22             # a midrank up to N is exact in float32
+MAX_RANK_GROUPS = 16
+
+
+@dataclass
+class ColumnRanks:
+    """``twice_rank`` int32 [N,V]: twice the midrank of every valid entry among the valid entries of its vertex, 0 where the entry is not
+    valid, negative in signed mode where the value is; ``n_valid`` int32 [V]; ``tie_term`` int64 [V], the sum over the vertex's tie
+    groups of t^3 - t.  DEVICE tensors."""
+    twice_rank: torch.Tensor
+    n_valid: torch.Tensor
+    tie_term: torch.Tensor
+
+
+def _rank_tile(twice_rank: torch.Tensor):
+    twice_rank = _chk(twice_rank, "twice_rank", torch.int32)
+    if twice_rank.dim() != 2 or not 1 <= twice_rank.shape[0] <= MAX_RANK_KNEES or twice_rank.shape[1] < 1:
+        raise ValueError(f"twice_rank must be [1 <= N <= 2^22, V >= 1], got {tuple(twice_rank.shape)}")
+    return twice_rank, int(twice_rank.shape[0]), int(twice_rank.shape[1])
+
+
+def column_ranks(values: torch.Tensor, mask: Optional[torch.Tensor] = None, signed: bool = False) -> ColumnRanks:
+    """Per vertex the midranks of the float32 ``values`` [N,V] (knee-major) among the entries that the uint8 / bool ``mask`` [N,V] calls
+    valid (None: all) and that are not NaN: see ``ColumnRanks``.  ``signed``: the ranks of |value| with the value's sign, zeros dropped
+    before ranking (Wilcoxon's signed ranks).  Float ``<`` and ``==``: -0.0 ties +0.0, infinities are ordinary values.  Integer counts
+    throughout: the result depends on no order.  O(N^2 V) compares.  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or not 1 <= values.shape[0] <= MAX_RANK_KNEES or values.shape[1] < 1:
+        raise ValueError(f"values must be [1 <= N <= 2^22, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V, dev = int(values.shape[0]), int(values.shape[1]), values.device
+    out = ColumnRanks(torch.empty((N, V), dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev),
+                      torch.empty(V, dtype=torch.int64, device=dev))
+    _lib.call("oai_column_ranks", values.data_ptr(), _ptr(mask), N, V, OAI_RANK_SIGNED if signed else OAI_RANK_PLAIN, out.twice_rank.data_ptr(),
+              out.n_valid.data_ptr(), out.tie_term.data_ptr(), _lib.STREAM, device=dev)
+    return out
+
+
+def rank_sums(twice_rank: torch.Tensor, labels=None, n_groups: int = 2):
+    """Per group of knees and vertex the number of valid entries and twice the sum of their |ranks|: (int32 [G,V], int64 [G,V]), DEVICE
+    tensors, from the int32 ``twice_rank`` [N,V] of ``column_ranks``.  ``labels``: a HOST sequence of N integers 0 .. ``n_groups`` - 1
+    (1 <= n_groups <= 16), checked before anything is launched; None: two groups by the sign of the entry, the negative ones first --
+    2 W- and 2 W+ of signed ranks.  Integer sums: exact in any order.  Does not synchronise."""
+    twice_rank, N, V = _rank_tile(twice_rank)
+    dev, G = twice_rank.device, int(n_groups)
+    if not 1 <= G <= MAX_RANK_GROUPS:
+        raise ValueError(f"n_groups must be 1 .. {MAX_RANK_GROUPS}, got {n_groups!r}")
+    host = None
+    if labels is None:
+        if G != 2:
+            raise ValueError(f"without labels the two groups are the signs of the entries: n_groups must be 2, got {G}")
+    else:
+        lab = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)
+        if lab.shape != (N,) or lab.dtype.kind not in "iub" or (lab.astype(np.int64) < 0).any() or (lab.astype(np.int64) >= G).any():
+            raise ValueError(f"labels must hold one integer 0 .. {G - 1} per knee ({N}), got {lab.dtype} {lab.shape}")
+        host = np.ascontiguousarray(lab, dtype=np.uint8)
+    n_g = torch.empty((G, V), dtype=torch.int32, device=dev)
+    twice_sum = torch.empty((G, V), dtype=torch.int64, device=dev)
+    _lib.call("oai_rank_sums", twice_rank.data_ptr(), None if host is None else host.ctypes.data, N, V, G, n_g.data_ptr(), twice_sum.data_ptr(),
+              _lib.STREAM, device=dev)
+    return n_g, twice_sum
+
+
+def rank_scores(twice_rank: torch.Tensor, n_valid: torch.Tensor, kind: str = "rank", c: float = 0.375):
+    """Scores of the ranks of ``column_ranks``: (float64 [N,V], uint8 [N,V] = the entry is valid), DEVICE tensors; 0.0 where the entry is
+    not valid.  ``kind`` "rank": the midrank itself (signed ranks keep their sign); "centred": the midrank minus (n_valid + 1) / 2; both
+    exact.  "normal": Phi^-1((r - c) / (n_valid - 2 c + 1)) of the midrank r, the rank-based inverse-normal transform, with ``c`` in
+    [0, 1/2] -- Blom 3/8 (the default), Tukey 1/3, Bliss-Rankit 1/2, van der Waerden 0; that one is held to a tolerance against
+    scipy.special.ndtri, not to the bit (include/oai_hip.h).  Does not synchronise."""
+    twice_rank, N, V = _rank_tile(twice_rank)
+    dev = twice_rank.device
+    n_valid = _span_vector(n_valid, "n_valid", torch.int32, V, dev)
+    if kind not in SCORE_KINDS:
+        raise ValueError(f"kind must be one of {sorted(SCORE_KINDS)}, got {kind!r}")
+    c = float(c)
+    if not 0.0 <= c <= 0.5:
+        raise ValueError(f"c must lie in [0, 1/2], got {c!r}")
+    score = torch.empty((N, V), dtype=torch.float64, device=dev)
+    mask = torch.empty((N, V), dtype=torch.uint8, device=dev)
+    _lib.call("oai_rank_scores", twice_rank.data_ptr(), n_valid.data_ptr(), N, V, SCORE_KINDS[kind], c, score.data_ptr(), mask.data_ptr(), _lib.STREAM,
+              device=dev)
+    return score, mask

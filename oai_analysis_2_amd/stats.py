@@ -61,6 +61,16 @@ difference or of a slope, with percentile, basic or BCa intervals per vertex and
 
     ci = bootstrap_ci(rate, n_bootstrap=2000, method="bca", simultaneous=True)      # mm / year [lower, upper]
     ci.estimate, ci.lower, ci.upper, ci.lower_simultaneous, ci.image(atlas, "se")
+
+``cohort.ranked()`` replaces every knee's value by its RANK among the knees that have a value at the vertex (or by the rank-based
+inverse-normal score, or by Wilcoxon's signed rank) on the device, so that one mislabelled patch no longer inflates the variance of a
+whole vertex (include/oai_hip.h, "Rank transform"; csrc/rank_transform.hip; tests/rank_transform_ref.py).  The result is a cohort again,
+for any of the tests above; ``rank_sum_test``, ``signed_rank_test``, ``kruskal_test`` and ``spearman_test`` name the classical tests and
+return their classical statistics beside the permutation result.
+
+    res = rank_sum_test(cohort, groups, tfce=True)                                  # Mann-Whitney under permutation
+    res.u1, res.auc, res.test.p_fwer, res.test.p_tfce
+    signed_rank_test(rate).rank_biserial, two_sample_test(cohort.ranked("inormal"), groups).p_fwer
 """
 from __future__ import annotations
 
@@ -191,6 +201,7 @@ class ThicknessCohort:
         self._areas: Optional[np.ndarray] = None
         self.smoothing: Optional["Smoothing"] = None       # set on the result of ``smoothed``
         self.change: Optional["Change"] = None             # set on the result of ``LongitudinalCohort.change``
+        self.ranking: Optional["Ranking"] = None           # set on the result of ``ranked``
 
     def surface_graph(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """The CSR vertex adjacency of the atlas inner mesh on the device (``mesh_processing.vertex_adjacency_device``), built at the
@@ -291,6 +302,68 @@ class ThicknessCohort:
             out._values[r0:r1] = wide.to(torch.float32)
         return out
 
+    def _derived_like(self, values: torch.Tensor, mask: torch.Tensor) -> "ThicknessCohort":
+        """A new cohort on this one's atlas, cartilage, ids and graph with ``.smoothing`` and ``.change`` carried over, as ``smoothed``
+        builds its result, holding the float32 ``values`` and uint8 ``mask`` [N, V]."""
+        out = ThicknessCohort(self.atlas, self.kind, self.use_coverage, self.chunk)
+        out.ids, out._graph, out._areas, out.smoothing, out.change = list(self.ids), self._graph, self._areas, self.smoothing, self.change
+        out._values, out._mask = values, mask
+        return out
+
+    def _ranked(self, method: str, c) -> Tuple["ThicknessCohort", "ops.ColumnRanks"]:
+        """``ranked`` and the ranks it was made from, which the four rank tests take their classical statistics from."""
+        if self.ranking is not None:
+            raise ValueError(f"this cohort is already ranked ({self.ranking.method!r}): ranks of ranks are the same ranks, and normal scores of "
+                             "normal scores are not what anyone means")
+        if method not in _RANK_METHODS:
+            raise ValueError(f"method must be one of {sorted(_RANK_METHODS)}, got {method!r}")
+        if len(self) < 1:
+            raise ValueError("the cohort holds no knee to rank")
+        signed, kind = _RANK_METHODS[method]
+        constant = rank_constant(c)
+        ranks = ops.column_ranks(self.values, self.mask, signed=signed)
+        score, mask = ops.rank_scores(ranks.twice_rank, ranks.n_valid, kind, constant)
+        out = self._derived_like(score.to(torch.float32), mask)
+        out.ranking = Ranking(method, constant if kind == "normal" else None, ranks.n_valid, ranks.tie_term)
+        return out, ranks
+
+    def ranked(self, method: str = "rank", c="blom") -> "ThicknessCohort":
+        """A NEW cohort on the same atlas, cartilage and ids whose values are scores of the RANKS of these, taken per vertex among the
+        knees that have a value there (include/oai_hip.h, "Rank transform"; csrc/rank_transform.hip; tests/rank_transform_ref.py); this
+        cohort is untouched, and ``.smoothing`` and ``.change`` are carried over.  ``method``:
+          "rank"            the midrank (ties share the average of their ranks), exact in float32;
+          "centred"         the midrank minus (n + 1) / 2, n the knees with a value at the vertex; exact;
+          "inormal"         the rank-based inverse-normal transform Phi^-1((r - c) / (n - 2 c + 1)), computed in float64 and rounded
+                            to float32 once;
+          "signed"          Wilcoxon's signed ranks: the midrank of |value| with the value's sign; a value of exactly zero is dropped
+                            before ranking and BECOMES MISSING in the result;
+          "signed_inormal"  the normal score of the signed rank's size, with the value's sign.
+        ``c``: "blom" (3/8, the default, as recalled from PALM's -inormal and pinned to no implementation), "tukey" (1/3), "rankit"
+        (1/2, Bliss), "waerden" (0), or a number in [0, 1/2]; read by the two inormal methods alone.  The result's mask is the
+        transform's; it carries ``.ranking`` (a ``Ranking``), and every test takes it as it takes a smoothed cohort.  Ranking a cohort
+        that is already ranked is refused.  Ranks are taken over the whole cohort: the tests' ``blocks`` restrict the permutations and
+        never the ranking."""
+        return self._ranked(method, c)[0]
+
+    def difference(self, other: "ThicknessCohort") -> "ThicknessCohort":
+        """A NEW cohort holding this cohort minus ``other`` within a knee: rows are matched by id exactly as ``paired_test`` matches them
+        (every id of either cohort in the other, once), the row order and ids are this cohort's, the difference a - b is taken on the
+        device in float32 and is missing where either side is.  ``.smoothing`` and ``.change`` are carried over where both sides agree
+        on them."""
+        if self.kind != other.kind or self.n_verts != other.n_verts or self.device != other.device:
+            raise ValueError("the two cohorts must hold the same cartilage of the same atlas on the same GPU")
+        where_b = {id_: k for k, id_ in enumerate(other.ids)}
+        if len(where_b) != len(other) or len(set(self.ids)) != len(self) or set(self.ids) != set(where_b):
+            raise ValueError("difference needs the same ids in both cohorts, each once")
+        if self.ranking is not None or other.ranking is not None:
+            raise ValueError("a difference of ranks is not a rank: take the difference first, then rank it")
+        order = torch.tensor([where_b[id_] for id_ in self.ids], dtype=torch.int64, device=self.device)
+        mask = self.mask * other.mask.index_select(0, order)
+        out = self._derived_like((self.values - other.values.index_select(0, order)) * mask, mask)      # missing entries hold 0 on either side
+        out.smoothing = self.smoothing if self.smoothing == other.smoothing else None
+        out.change = self.change if self.change == other.change else None
+        return out
+
 
 # ---- surface smoothing -----------------------------------------------------------------------------------------------------------------
 _FWHM_PER_SIGMA = math.sqrt(8.0 * math.log(2.0))
@@ -306,6 +379,34 @@ class Smoothing:
     sweeps: int
     sigma_step: float
     missing: str
+
+
+RANK_CONSTANTS = {"blom": 0.375, "tukey": 1.0 / 3.0, "rankit": 0.5, "waerden": 0.0}
+_RANK_METHODS = {"rank": (False, "rank"), "centred": (False, "centred"), "inormal": (False, "normal"), "signed": (True, "rank"),
+                 "signed_inormal": (True, "normal")}          # method -> (signed ranks, the kind of ops.rank_scores)
+
+
+def rank_constant(c) -> float:
+    """The constant c of the normal score Phi^-1((r - c) / (n - 2 c + 1)): one of ``RANK_CONSTANTS`` by name, or a number in [0, 1/2]."""
+    if isinstance(c, str):
+        if c not in RANK_CONSTANTS:
+            raise ValueError(f"c must be one of {sorted(RANK_CONSTANTS)} or a number in [0, 1/2], got {c!r}")
+        return RANK_CONSTANTS[c]
+    c = float(c)
+    if not 0.0 <= c <= 0.5:
+        raise ValueError(f"c must lie in [0, 1/2], got {c!r}")
+    return c
+
+
+@dataclass(frozen=True)
+class Ranking:
+    """What a ranked cohort was ranked with: the ``method`` of ``ThicknessCohort.ranked``, the constant ``c`` of its normal scores (None
+    for the methods without), and per vertex, as DEVICE tensors [V], ``n_valid`` int32 -- the knees that were ranked there -- and
+    ``tie_term`` int64, the sum over the tie groups of t^3 - t."""
+    method: str
+    c: Optional[float]
+    n_valid: torch.Tensor
+    tie_term: torch.Tensor
 
 
 def _csr_slots(offsets, neighbours, n_verts: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -1885,3 +1986,174 @@ def bootstrap_ci(cohort: ThicknessCohort, x=None, groups=None, covariates=None, 
         res.critical = float(np.quantile(res.sup[1:], level))
         res.lower_simultaneous, res.upper_simultaneous = res.estimate - res.critical * res.se, res.estimate + res.critical * res.se
     return res
+
+
+# ---- rank tests ------------------------------------------------------------------------------------------------------------------------
+# What is and is not classical, for all four tests below:
+#   * Where nothing is missing, the t (or F) of the ranks is a monotone function of U (or W, H, rho) under every relabelling, so the
+#     permutation p-values are those of the classical exact test.
+#   * Where entries are missing, the group sizes at a vertex vary with the labelling; the statistic is then Conover and Iman's t (or F) on
+#     ranks (1981), which is still a valid permutation test, and the classical figures are those of the valid knees of the vertex.
+#   * Ranks are taken over the whole cohort and never within ``blocks``: blocks restrict the permutations only.  A van Elteren test, which
+#     ranks within strata, is not provided.
+#   * No asymptotic or exact-table p-value is formed: the permutation p of ``.test`` is the product, and no significance level is built in.
+def _rank_scores_method(scores: str, signed: bool = False) -> str:
+    if scores not in ("rank", "inormal"):
+        raise ValueError(f'scores must be "rank" or "inormal", got {scores!r}')
+    return {("rank", False): "rank", ("inormal", False): "inormal", ("rank", True): "signed", ("inormal", True): "signed_inormal"}[(scores, signed)]
+
+
+def _midranks(x) -> np.ndarray:
+    """The midranks of a host vector, float64: scipy.stats.rankdata(method="average") from sorted unique values and their counts."""
+    x = np.asarray(x, np.float64)
+    if x.ndim != 1 or not np.isfinite(x).all():
+        raise ValueError("a vector to rank must be one finite number per knee")
+    _, inverse, counts = np.unique(x, return_inverse=True, return_counts=True)
+    last = np.cumsum(counts)                                               # the largest rank of every tie group
+    return (last - 0.5 * (counts - 1))[inverse.reshape(-1)]
+
+
+def _sums_to_host(ranks: "ops.ColumnRanks", labels, n_groups: int):
+    """(n_g [G, V], rank sums float64 [G, V] -- a multiple of 1/2, exact --, n_valid [V], tie_term [V]) from ONE ``rank_sums`` call and
+    one download."""
+    n_g, twice = ops.rank_sums(ranks.twice_rank, labels, n_groups)
+    n_g, twice, n_valid, tie_term = _download([n_g, twice, ranks.n_valid, ranks.tie_term])
+    return n_g, 0.5 * twice.astype(np.float64), n_valid, tie_term
+
+
+@dataclass(frozen=True)
+class RankSumResult:
+    """``test``: the ``PermutationResult`` of ``two_sample_test`` on the ranked cohort, untouched.  Per vertex, over the knees with a value
+    there: ``n1``, ``n2`` int32; ``u1`` = R1 - n1 (n1 + 1) / 2, the Mann-Whitney U of group 1 (R1 the sum of its midranks: scipy's
+    ``mannwhitneyu(group1, group2).statistic``); ``auc`` = u1 / (n1 n2), the probability of superiority P(a knee of group 1 > one of group 2)
+    + P(tie) / 2, NaN where a side is empty; ``tie_term`` int64, the sum over tie groups of t^3 - t."""
+    test: PermutationResult
+    u1: np.ndarray
+    auc: np.ndarray
+    n1: np.ndarray
+    n2: np.ndarray
+    tie_term: np.ndarray
+
+
+def rank_sum_test(cohort: ThicknessCohort, groups, scores: str = "rank", n_permutations: int = 10000, cluster_threshold: Optional[float] = None,
+                  seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None, tfce=None) -> RankSumResult:
+    """The Wilcoxon rank-sum (Mann-Whitney) test per vertex: ``two_sample_test`` of ``cohort.ranked()`` -- robust against the gross outliers
+    of an automatic pipeline, which inflate the pooled variance of the plain t -- with the classical U and the probability of superiority
+    beside it.  ``scores="inormal"`` runs the test on the rank-based inverse-normal scores instead (``ranked("inormal")``, Blom); ``u1`` and
+    ``auc`` are those of the ranks either way.  Every other argument is ``two_sample_test``'s and is passed through.
+    Where nothing is missing, the t of the ranks is a monotone function of U under every relabelling, so ``test.p_uncorrected`` is the
+    p of the exact Mann-Whitney test (two-sided, over the labellings drawn).  Where entries are missing, n1 and n2 at a vertex vary with
+    the labelling, and the statistic is Conover and Iman's t on ranks, still a valid permutation test.  Ranking is over the whole cohort
+    and never within ``blocks``; a van Elteren test is not provided.  No asymptotic p-value is formed."""
+    g = _as_groups(groups)
+    ranked, ranks = cohort._ranked(_rank_scores_method(scores), "blom")
+    test = two_sample_test(ranked, g, n_permutations=n_permutations, cluster_threshold=cluster_threshold, seed=seed, blocks=blocks,
+                           permutations=permutations, batch=batch, tfce=tfce)
+    n_g, R, _, tie_term = _sums_to_host(ranks, np.where(g, 0, 1).astype(np.uint8), 2)
+    n1, n2 = n_g[0], n_g[1]
+    u1 = R[0] - 0.5 * n1.astype(np.float64) * (n1.astype(np.float64) + 1.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        auc = np.where((n1 > 0) & (n2 > 0), u1 / (n1.astype(np.float64) * n2.astype(np.float64)), np.nan)
+    return RankSumResult(test, u1, auc, n1, n2, tie_term)
+
+
+@dataclass(frozen=True)
+class SignedRankResult:
+    """``test``: the ``PermutationResult`` of ``one_sample_test`` on the signed ranks, untouched.  Per vertex: ``w_plus`` and ``w_minus``, the
+    sums of the midranks of |value| over the positive and the negative values (scipy's ``wilcoxon(zero_method="wilcox").statistic`` is the
+    smaller of the two); ``n_nonzero`` int32, the knees with a value other than zero, which are the ones ranked;
+    ``rank_biserial`` = (W+ - W-) / (W+ + W-), NaN where no knee is ranked."""
+    test: PermutationResult
+    w_plus: np.ndarray
+    w_minus: np.ndarray
+    n_nonzero: np.ndarray
+    rank_biserial: np.ndarray
+
+
+def signed_rank_test(cohort_a: ThicknessCohort, cohort_b: Optional[ThicknessCohort] = None, scores: str = "rank", n_permutations: int = 10000,
+                     cluster_threshold: Optional[float] = None, seed: int = 0, permutations=None, batch: Optional[int] = None,
+                     tfce=None) -> SignedRankResult:
+    """Wilcoxon's signed-rank test per vertex: ``one_sample_test`` of ``ranked("signed")`` of ``cohort_a`` -- a rate cohort, whose two-visit
+    slopes are heavy-tailed -- or, with ``cohort_b``, of ``cohort_a.difference(cohort_b)`` (rows matched by id as ``paired_test`` matches
+    them).  A value of exactly zero is dropped before ranking, as scipy's ``zero_method="wilcox"`` does, and is missing in the test.
+    ``scores="inormal"``: the test runs on the normal scores of the signed ranks; W+ and W- are those of the ranks either way.  Every
+    other argument is ``one_sample_test``'s.  Where nothing is missing (and nothing is zero), the t of the signed ranks is a monotone
+    function of W+ under every sign flip, so ``test.p_uncorrected`` is the p of the exact signed-rank test; otherwise the number of ranked
+    knees varies from vertex to vertex and not with the flip, and the same holds per vertex.  No asymptotic p-value is formed."""
+    base = cohort_a if cohort_b is None else cohort_a.difference(cohort_b)
+    ranked, ranks = base._ranked(_rank_scores_method(scores, signed=True), "blom")
+    test = one_sample_test(ranked, n_permutations=n_permutations, cluster_threshold=cluster_threshold, seed=seed, permutations=permutations,
+                           batch=batch, tfce=tfce)
+    _, W, n_valid, _ = _sums_to_host(ranks, None, 2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        biserial = np.where(n_valid > 0, (W[1] - W[0]) / (W[1] + W[0]), np.nan)
+    return SignedRankResult(test, W[1], W[0], n_valid, biserial)
+
+
+@dataclass(frozen=True)
+class KruskalResult:
+    """``test``: the ``FResult`` of ``anova_test`` on the ranked cohort, untouched.  ``h`` float64 [V]: the Kruskal-Wallis statistic over the
+    knees with a value at the vertex, tie-corrected -- (12 / (n (n + 1)) sum_g R_g^2 / n_g - 3 (n + 1)) / (1 - T / (n^3 - n)), T the tie
+    term -- as ``scipy.stats.kruskal`` gives it; NaN where every valid value ties or a level has no knee there.  ``levels``: the sorted
+    labels; ``group_n`` int32 [G, V] and ``rank_sum`` float64 [G, V] per level; ``tie_term`` int64 [V]."""
+    test: FResult
+    h: np.ndarray
+    levels: np.ndarray
+    group_n: np.ndarray
+    rank_sum: np.ndarray
+    tie_term: np.ndarray
+
+
+def kruskal_test(cohort: ThicknessCohort, groups, covariates=None, scores: str = "rank", n_permutations: int = 10000,
+                 cluster_threshold: Optional[float] = None, seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None,
+                 tfce=None) -> KruskalResult:
+    """The Kruskal-Wallis test per vertex: ``anova_test`` of ``cohort.ranked()`` across the levels of ``groups``, with the classical H beside
+    it.  ``covariates`` are passed to ``anova_test`` AS THEY ARE (an analysis of covariance of the ranks); H ignores them.
+    ``scores="inormal"``: the F runs on the normal scores; H is that of the ranks either way.  Every other argument is ``anova_test``'s.
+    Where nothing is missing and there are no covariates, the F of the ranks is a monotone function of H under every relabelling, so
+    ``test.p_uncorrected`` is the p of the exact Kruskal-Wallis test; where entries are missing the level sizes at a vertex vary with the
+    labelling and the statistic is Conover and Iman's F on ranks, still a valid permutation test.  Ranking is over the whole cohort and
+    never within ``blocks``.  No asymptotic p-value is formed."""
+    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
+    levels, where = _anova_levels(groups, len(cohort), n_cov)
+    ranked, ranks = cohort._ranked(_rank_scores_method(scores), "blom")
+    test = anova_test(ranked, groups, covariates=covariates, n_permutations=n_permutations, cluster_threshold=cluster_threshold, seed=seed,
+                      blocks=blocks, permutations=permutations, batch=batch, tfce=tfce)
+    n_g, R, n_valid, tie_term = _sums_to_host(ranks, where.astype(np.uint8), len(levels))
+    n, ng = n_valid.astype(np.float64), n_g.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        h = 12.0 / (n * (n + 1.0)) * (R * R / ng).sum(axis=0) - 3.0 * (n + 1.0)
+        h = h / (1.0 - tie_term.astype(np.float64) / (n * n * n - n))
+    bad = (n_g == 0).any(axis=0) | (tie_term.astype(np.float64) == n * n * n - n)
+    return KruskalResult(test, np.where(bad, np.nan, h), levels, n_g, R, tie_term)
+
+
+@dataclass(frozen=True)
+class SpearmanResult:
+    """``test``: the ``RegressionResult`` of ``regression_test`` on the ranked cohort and the ranked regressor, untouched.  ``rho`` float64 [V]
+    = ``test.partial_r``: Spearman's rank correlation of thickness and x where no covariates are given and nothing is missing, the partial
+    rank correlation given the (ranked) covariates otherwise."""
+    test: RegressionResult
+    rho: np.ndarray
+
+
+def spearman_test(cohort: ThicknessCohort, x, covariates=None, scores: str = "rank", n_permutations: int = 10000,
+                  cluster_threshold: Optional[float] = None, seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None,
+                  tfce=None) -> SpearmanResult:
+    """Spearman's rank correlation per vertex: ``regression_test`` of ``cohort.ranked()`` on the midranks of ``x``, adjusted for the midranks
+    of every column of ``covariates`` (a partial rank correlation).  ``scores="inormal"``: thickness enters as normal scores; ``x`` and the
+    covariates stay midranks.  Every other argument is ``regression_test``'s.
+    ``x`` (and every covariate) is ranked ONCE over all knees and not per vertex: where nothing is missing, ``rho`` is exactly Spearman's
+    coefficient, and the t of the ranks is a monotone function of it under every permutation, so ``test.p_uncorrected`` is the p of the
+    exact test; where entries are missing, the ranks of x among the valid knees of a vertex are no longer 1 .. n, and ``rho`` is a rank
+    regression, not exactly Spearman's coefficient -- still a valid permutation test.  Ranking is over the whole cohort and never within
+    ``blocks``.  No asymptotic p-value is formed."""
+    rx = _midranks(x)
+    cov = None
+    if covariates is not None:
+        cov = np.asarray(covariates, np.float64)
+        cov = _midranks(cov) if cov.ndim == 1 else np.stack([_midranks(cov[:, k]) for k in range(cov.shape[1])], axis=1)
+    ranked = cohort.ranked(_rank_scores_method(scores))
+    test = regression_test(ranked, rx, covariates=cov, n_permutations=n_permutations, cluster_threshold=cluster_threshold, seed=seed, blocks=blocks,
+                           permutations=permutations, batch=batch, tfce=tfce)
+    return SpearmanResult(test, test.partial_r)
