@@ -1532,6 +1532,61 @@ int oai_rank_sums(const int* twice_rank_dev, const unsigned char* labels_host, l
 int oai_rank_scores(const int* twice_rank_dev, const int* n_valid_dev, long long n_knees, long long n_verts, int kind, double c, double* score_dev,
                     unsigned char* mask_dev, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Cohort PCA (csrc/cohort_pca.hip, tests/cohort_pca_ref.py): the area-weighted, missing-aware principal components of a cohort's
+ * thickness maps by way of the N x N Gram matrix of the whitened knees (the snapshot method), and what scoring a knee against the
+ * model needs: Hotelling's T2 inside it and the residual Q (squared prediction error) outside it.  The reference has no such step;
+ * the definitions are this library's own, pinned by a numpy restatement that is held to np.linalg.svd and sklearn.  The eigen-
+ * decomposition itself is N x N and runs on the host (np.linalg.eigh); the three entry points below are what is O(N V) and O(N^2 V).
+ * Nothing synchronises or reads anything back.
+ *
+ * The inputs.
+ *   Y: float32 [N][V], knee-major.
+ *   M: uint8 mask, may be null.  Validity is as everywhere else: the mask is non-zero and the value is not NaN.
+ *   mean: float64 [V].
+ *   rw: float64 [V], the root weights, sqrt(area in mm^2).  The host takes the square root with np.sqrt, so the device takes no
+ *     square root.
+ *
+ * Whitening.  a_iv = ((double)Y_iv - mean_v) * rw_v is one subtraction followed by one product.  Where the entry is missing or
+ *   rw_v == 0, a_iv is exactly 0.0 by a select, never by a product.  A vertex with no valid knee has a NaN mean and must not leak.
+ *
+ * Ordered dot.  C_ij = sum over v of a_iv * b_jv.  The order is the contract:
+ *   The vertex axis is cut into chunks of 512 consecutive vertices.  The last chunk is short.
+ *   Inside a chunk, the terms are added in ascending v into one accumulator that starts at 0.0.  It is a product, then an add, with
+ *     no FMA.
+ *   The chunk sums are then added in ascending chunk index into one accumulator that starts at 0.0.
+ *   The float64 product is commutative, so C of (A, A) is symmetric to the bit.
+ *   The vector fp64 MFMA is deliberately not used.  Its internal summation order cannot be restated in numpy.
+ *
+ * Ordered combine.  R_cv = sum over i of k_ci * a_iv, summed over ascending i into one accumulator, product then add.
+ *
+ * oai_cohort_whiten writes A = out_dev float64 [n_knees][n_verts] and, where norm2_dev is not null, norm2_i = sum over v of a_iv^2
+ *   in the ordered-dot order, float64 [n_knees]: the diagonal of oai_rows_cross(A, A), from which the Q of a new knee is read without
+ *   an N' x N' product.  1 <= n_knees <= 2^24 (one knee is scored against a model alone), 1 <= n_verts <= 2^31 - 2.
+ * oai_rows_cross writes out_dev float64 [n_a][n_b], C of the rows a_dev [n_a][n_verts] and b_dev [n_b][n_verts];
+ *   1 <= n_a, n_b <= 2^20.  With b_dev == a_dev (and n_b == n_a) it computes only the tiles on or above the diagonal and mirrors
+ *   them.  Two execution forms of one device body.  Walk: one workgroup per 64 x 64 output tile walks all chunks, no workspace.
+ *   Split: a grid of tiles x chunks, each workgroup writes its tile's chunk sum to the workspace and a finish kernel adds the chunk
+ *   sums in ascending chunk index.  The split form runs when workspace_dev is not null and ceil(n_a / 64) * ceil(n_b / 64) <= 256;
+ *   it needs oai_rows_cross_workspace_bytes(n_a, n_b, n_verts) bytes (0 for shapes it refuses and for tile counts above 256) and a
+ *   smaller workspace is refused.  Both forms give the same bits by construction.
+ * oai_rows_combine writes out_dev float64 [n_out][n_verts] = R of coef_dev float64 [n_out][n_rows] and rows_dev float64
+ *   [n_rows][n_verts]; 1 <= n_out, n_rows <= 2^20.
+ * Both product entry points are plain row-matrix primitives on float64 rows and know nothing of thickness.
+ *
+ * Limits.  Mean imputation: a missing entry contributes 0 after centring; the Python layer reports it through n_missing and
+ * n_excluded.  No leave-one-out member scores.  No choice of K and no parallel analysis.  eigh on the host.  Degenerate (equal)
+ * eigenvalues leave their modes defined only up to rotation.  No fp64 MFMA path.  No thresholds.
+ * ---------------------------------------------------------------------------------------- */
+int oai_cohort_whiten(const float* values_dev, const unsigned char* mask_dev, const double* mean_dev, const double* root_weight_dev,
+                      long long n_knees, long long n_verts, double* out_dev, double* norm2_dev, void* stream);
+size_t oai_rows_cross_workspace_bytes(long long n_a, long long n_b, long long n_verts);
+int oai_rows_cross(const double* a_dev, long long n_a, const double* b_dev, long long n_b, long long n_verts, double* out_dev,
+                   void* workspace_dev, size_t workspace_bytes, void* stream);
+int oai_rows_combine(const double* coef_dev, const double* rows_dev, long long n_out, long long n_rows, long long n_verts, double* out_dev,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

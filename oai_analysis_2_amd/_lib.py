@@ -170,6 +170,10 @@ SIGNATURES = {
     "oai_column_ranks": (_I, [_P, _P, C.c_longlong, C.c_longlong, _I, _P, _P, _P, _P]),
     "oai_rank_sums": (_I, [_P, _P, C.c_longlong, C.c_longlong, _I, _P, _P, _P]),
     "oai_rank_scores": (_I, [_P, _P, C.c_longlong, C.c_longlong, _I, _D, _P, _P, _P]),
+    "oai_cohort_whiten": (_I, [_P, _P, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _P]),
+    "oai_rows_cross_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong, C.c_longlong]),
+    "oai_rows_cross": (_I, [_P, C.c_longlong, _P, C.c_longlong, C.c_longlong, _P, _P, _Z, _P]),
+    "oai_rows_combine": (_I, [_P, _P, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P]),
     "oai_image_normalize_workspace_bytes": (_Z, []),
     "oai_image_normalize": (_I, [_P, _Z, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "oai_partition_tiles": (_I, [_P, _I, _I, _I, _I3, _I3, _I, _I, _P, _P]),

@@ -1,4 +1,4 @@
-// What the cohort statistics sources share (csrc/group_stats.hip, group_regression.hip, graph_tfce.hip, graph_smooth.hip): the limits of
+// What the cohort statistics sources share (csrc/group_stats.hip, group_regression.hip, graph_tfce.hip, graph_smooth.hip, cohort_pca.hip): the limits of
 // their entry points and the argument checks of the graph ones, stated once, and the counted mean that both prepare kernels start with.
 #pragma once
 #include "common.h"
@@ -8,6 +8,7 @@ namespace oai {
 constexpr long long kMaxKnees = 1LL << 24;
 constexpr long long kMaxRows = 1LL << 20;          // of one batch or call
 constexpr long long kMaxVerts = (1LL << 31) - 2;
+constexpr int kDotChunk = 512;                     // vertices per chunk of the ordered dot (csrc/cohort_pca.hip): part of its stated order
 
 // a cohort matrix [N][V], and a tile [rows][V] of per-row values on its vertices
 static inline bool cohort_shape_ok(long long N, long long V) { return N >= 2 && N <= kMaxKnees && V >= 1 && V <= kMaxVerts; }

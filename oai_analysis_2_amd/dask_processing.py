@@ -282,6 +282,22 @@ def deviation_stream(stream: Iterable[Tuple[int, object]], models, covariates=No
         yield index, found
 
 
+def pca_stream(stream: Iterable[Tuple[int, object]], models) -> Iterator[Tuple[int, object]]:
+    """(index, {"FC": stats.PCAScores, "TC": ...}) for every (index, KneeThickness) of ``stream`` (``thickness_stream`` /
+    ``process_cohort_thickness``): each knee scored against the cohort PCA of each cartilage in ``models`` ({"FC": stats.ThicknessPCA,
+    ...}) as it arrives -- its scores, T2 inside the model and the residual Q outside it.  A cartilage that could not be measured lies on
+    the mean everywhere (``n_missing`` = the model's vertices, q = 0).  Like ``deviation_stream`` a plain synchronous generator: two small
+    launches and one download per knee and cartilage."""
+    from .stats import ThicknessCohort
+    for index, knee in stream:
+        found = {}
+        for kind, model in models.items():
+            one = ThicknessCohort(model.atlas, kind, use_coverage=model.surface.use_coverage, chunk=1)
+            one.add(knee, index)
+            found[kind] = model.transform(one)
+        yield index, found
+
+
 def process_cohort_thickness(images: Sequence, atlas_image, thickness_atlas, worker: Optional[Worker] = None,
                              space: str = "atlas", morphometry=False, mesh_qc: bool = False) -> Iterator[Tuple[int, object]]:
     """process_cohort with the thickness stage behind it: yields (index, KneeThickness) for the volumes this rank processed; the

@@ -1321,3 +1321,83 @@ def rank_scores(twice_rank: torch.Tensor, n_valid: torch.Tensor, kind: str = "ra
     _lib.call("oai_rank_scores", twice_rank.data_ptr(), n_valid.data_ptr(), N, V, SCORE_KINDS[kind], c, score.data_ptr(), mask.data_ptr(), _lib.STREAM,
               device=dev)
     return score, mask
+
+
+# ---- cohort PCA (include/oai_hip.h, "Cohort PCA"; csrc/cohort_pca.hip) ------------------------------------------------------------------------
+DOT_CHUNK = 512                      # vertices per chunk of the ordered dot
+CROSS_TILE = 64                      # edge of a workgroup's tile of rows_cross
+CROSS_SPLIT_MAX_TILES = 256          # the split form of rows_cross runs up to this many tiles of the full rectangle
+MAX_CROSS_ROWS = 1 << 20
+
+
+def _rows_matrix(t: torch.Tensor, name: str):
+    t = _chk(t, name, torch.float64)
+    if t.dim() != 2 or not 1 <= t.shape[0] <= MAX_CROSS_ROWS or t.shape[1] < 1:
+        raise ValueError(f"{name} must be [1 <= n <= 2^20, V >= 1], got {tuple(t.shape)}")
+    return t, int(t.shape[0]), int(t.shape[1])
+
+
+def cohort_whiten(values: torch.Tensor, mask: Optional[torch.Tensor], mean: torch.Tensor, root_weights: torch.Tensor, return_norm2: bool = False):
+    """The whitened knees of the float32 ``values`` [N,V] (knee-major): float64 [N,V] with a_iv = (y_iv - mean_v) * root_weights_v, one
+    subtraction then one product, and exactly 0.0 -- by a select -- where the uint8 / bool ``mask`` [N,V] (None: all valid) is zero, the
+    value is NaN or the root weight is 0.  ``mean``, ``root_weights``: float64 [V] on the values' GPU.  ``return_norm2``: also the float64
+    [N] squared norms of the rows, summed in the ordered-dot order (chunks of 512 vertices): the diagonal of ``rows_cross`` of the result.
+    Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"values must be [N >= 1, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V, dev = int(values.shape[0]), int(values.shape[1]), values.device
+    mean, root_weights = _chk(mean, "mean", torch.float64), _chk(root_weights, "root_weights", torch.float64)
+    for name, t in (("mean", mean), ("root_weights", root_weights)):
+        _check_same_gpu("values", values, name, t)
+        if tuple(t.shape) != (V,):
+            raise ValueError(f"{name} must be [{V}], got {tuple(t.shape)}")
+    out = torch.empty((N, V), dtype=torch.float64, device=dev)
+    norm2 = torch.empty(N, dtype=torch.float64, device=dev) if return_norm2 else None
+    _lib.call("oai_cohort_whiten", values.data_ptr(), _ptr(mask), mean.data_ptr(), root_weights.data_ptr(), N, V, out.data_ptr(), _ptr(norm2),
+              _lib.STREAM, device=dev)
+    return (out, norm2) if return_norm2 else out
+
+
+def rows_cross_workspace(n_a: int, n_b: int, n_verts: int, device) -> Optional[torch.Tensor]:
+    """The uint8 workspace with which ``rows_cross`` runs its split form at this shape, or None where it would walk all the same (more
+    than 256 tiles of 64 x 64)."""
+    ws = _lib.workspace("oai_rows_cross", device, int(n_a), int(n_b), int(n_verts))
+    return ws if ws.numel() else None
+
+
+def rows_cross(a: torch.Tensor, b: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 [n_a, n_b]: the ordered dot of every row of the float64 ``a`` [n_a,V] with every row of ``b`` [n_b,V] -- chunks of 512
+    vertices, ascending v inside a chunk, ascending chunks, a product then an add (include/oai_hip.h).  ``b`` None: the Gram matrix of
+    ``a``, of which only the tiles on or above the diagonal are computed and the rest mirrored; symmetric to the bit.  ``workspace``: a
+    uint8 tensor of ``rows_cross_workspace``; with it, and at most 256 tiles, the work is split over the chunks as well (the form for a few
+    hundred rows), without it one workgroup walks all chunks of a tile.  The same bits either way.  Does not synchronise."""
+    a, n_a, V = _rows_matrix(a, "a")
+    if b is None:
+        b, n_b = a, n_a
+    else:
+        b, n_b, Vb = _rows_matrix(b, "b")
+        _check_same_gpu("a", a, "b", b)
+        if Vb != V:
+            raise ValueError(f"a and b must have the same vertices, got {V} and {Vb}")
+    if workspace is not None:
+        workspace = _chk(workspace, "workspace", torch.uint8)
+        _check_same_gpu("a", a, "workspace", workspace)
+    out = torch.empty((n_a, n_b), dtype=torch.float64, device=a.device)
+    _lib.call("oai_rows_cross", a.data_ptr(), n_a, b.data_ptr(), n_b, V, out.data_ptr(), _ptr(workspace), 0 if workspace is None else workspace.numel(),
+              _lib.STREAM, device=a.device)
+    return out
+
+
+def rows_combine(coef: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """float64 [K, V]: row c is the sum over i of coef[c, i] * rows[i], in ascending i with one accumulator, a product then an add
+    (include/oai_hip.h, "Ordered combine").  ``coef`` float64 [K,N], ``rows`` float64 [N,V].  Does not synchronise."""
+    coef, K, N = _rows_matrix(coef, "coef")
+    rows, Nr, V = _rows_matrix(rows, "rows")
+    _check_same_gpu("coef", coef, "rows", rows)
+    if Nr != N:
+        raise ValueError(f"coef [{K}, {N}] needs {N} rows, got {Nr}")
+    out = torch.empty((K, V), dtype=torch.float64, device=rows.device)
+    _lib.call("oai_rows_combine", coef.data_ptr(), rows.data_ptr(), K, N, V, out.data_ptr(), _lib.STREAM, device=rows.device)
+    return out

@@ -71,6 +71,14 @@ return their classical statistics beside the permutation result.
     res = rank_sum_test(cohort, groups, tfce=True)                                  # Mann-Whitney under permutation
     res.u1, res.auc, res.test.p_fwer, res.test.p_tfce
     signed_rank_test(rate).rank_biserial, two_sample_test(cohort.ranked("inormal"), groups).p_fwer
+
+``cohort.pca()`` describes patterns over the whole surface and judges a knee against the cohort as a whole: an area-weighted,
+missing-aware principal component analysis through the Gram matrix of the whitened knees, with Hotelling's T2 inside the model and the
+residual Q outside it per knee (include/oai_hip.h, "Cohort PCA"; csrc/cohort_pca.hip; tests/cohort_pca_ref.py).
+
+    pca = cohort.pca(10)                                                            # modes_mm, explained_variance_ratio, scores
+    screen = pca.member_scores(); screen.q_fraction, screen.t2                      # a registration failure stands out in q
+    regression_test(cohort, x=pca.scores[:, 0]), pca.transform(new_knee).q
 """
 from __future__ import annotations
 
@@ -363,6 +371,12 @@ class ThicknessCohort:
         out.smoothing = self.smoothing if self.smoothing == other.smoothing else None
         out.change = self.change if self.change == other.change else None
         return out
+
+    def pca(self, n_components: int = 10, weights="area", min_valid: int = 2) -> "ThicknessPCA":
+        """``ThicknessPCA.fit(self, ...)``: the modes of variation of this cohort's maps and its knees' outlier scores (T2 inside the
+        model, Q outside it).  On a derived cohort the settings travel with the model: ``cohort.ranked("inormal").pca()`` is the
+        correlation-type analysis."""
+        return ThicknessPCA.fit(self, n_components, weights, min_valid)
 
 
 # ---- surface smoothing -----------------------------------------------------------------------------------------------------------------
@@ -2157,3 +2171,194 @@ def spearman_test(cohort: ThicknessCohort, x, covariates=None, scores: str = "ra
     test = regression_test(ranked, rx, covariates=cov, n_permutations=n_permutations, cluster_threshold=cluster_threshold, seed=seed, blocks=blocks,
                            permutations=permutations, batch=batch, tfce=tfce)
     return SpearmanResult(test, test.partial_r)
+
+
+# ---- cohort PCA ------------------------------------------------------------------------------------------------------------------------
+PCA_DROP = 1e-12                      # a component is kept where lambda > 0 and lambda > PCA_DROP * lambda_1: part of the contract
+_PCA_ARRAYS = ("mean", "root_weights", "weights", "modes_w", "singular_values", "explained_variance", "explained_variance_ratio")
+
+
+@dataclass
+class PCAScores:
+    """One entry per knee scored against a ``ThicknessPCA``: ``scores`` float64 [N', K] (the knee's coordinates on the modes, in
+    mm * sqrt(mm^2)); ``t2`` = sum_c score_c^2 / explained_variance_c, Hotelling's T2 INSIDE the model; ``q`` = norm2 - sum_c score_c^2, the
+    residual outside it (the squared prediction error of process monitoring), in mm^2 * mm^2, where norm2 is the squared whitened norm of
+    the centred knee; ``q_fraction`` = q / norm2; ``n_missing``: the model's vertices at which the knee has no value and was taken to lie
+    on the mean.  ``member``: the knees are the model's own (``member_scores``) and their figures optimistic.  No threshold is applied."""
+    kind: str
+    ids: List[object]
+    scores: np.ndarray
+    t2: np.ndarray
+    q: np.ndarray
+    q_fraction: np.ndarray
+    n_missing: np.ndarray
+    member: bool = False
+
+    def __len__(self) -> int:
+        return len(self.ids)
+
+
+def _pca_record(kind, ids, scores, norm2, explained_variance, n_missing, member) -> PCAScores:
+    inside = (scores * scores).sum(axis=1)
+    q = norm2 - inside
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return PCAScores(kind, list(ids), scores, (scores * scores / explained_variance[None, :]).sum(axis=1), q, q / norm2,
+                         np.asarray(n_missing, np.int64), member)
+
+
+class ThicknessPCA:
+    """The modes of thickness variation of a cohort and, per knee, two outlier scores: an area-weighted, missing-aware principal
+    component analysis of the maps by way of the N x N Gram matrix of the whitened knees (include/oai_hip.h, "Cohort PCA";
+    csrc/cohort_pca.hip; tests/cohort_pca_ref.py).  ``fit`` keeps ``mean`` [V] (mm), ``modes_mm`` [K, V] (orthonormal under the weighted
+    inner product sum_v w_v x_v y_v; NaN at excluded vertices), ``singular_values`` [K], ``explained_variance`` = lambda / (N - 1),
+    ``explained_variance_ratio`` = lambda / trace G, ``scores`` [N, K], ``ids``, ``n_excluded``, ``weights`` [V], and the settings of a
+    derived cohort (``smoothing``, ``ranking``, ``change``): ``cohort.ranked("inormal").pca()`` is the correlation-type analysis.
+
+    Limits.  A missing entry contributes 0 after centring -- mean imputation -- and is counted in ``n_missing`` (per knee) and
+    ``n_excluded`` (vertices with fewer than ``min_valid`` knees).  ``member_scores`` is not leave-one-out.  K is the caller's choice: no
+    parallel analysis.  The eigendecomposition runs on the host.  Equal eigenvalues leave their modes defined only up to rotation.  No
+    fp64 MFMA path.  No thresholds."""
+
+    def __init__(self, surface: ThicknessCohort, mean, root_weights, weights, modes_w, singular_values, explained_variance,
+                 explained_variance_ratio, n_knees: int, n_excluded: int, min_valid: int):
+        self.surface = surface
+        self.atlas, self.kind, self.device, self.n_verts = surface.atlas, surface.kind, surface.device, surface.n_verts
+        self.mean, self.root_weights, self.weights = (np.asarray(a, np.float64) for a in (mean, root_weights, weights))
+        self.modes_w = np.ascontiguousarray(modes_w, np.float64)           # the root-weighted modes R [K, V], orthonormal rows
+        self.singular_values, self.explained_variance, self.explained_variance_ratio = (
+            np.asarray(a, np.float64) for a in (singular_values, explained_variance, explained_variance_ratio))
+        self.n_knees, self.n_excluded, self.min_valid = int(n_knees), int(n_excluded), int(min_valid)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.modes_mm = np.where(self.root_weights[None, :] != 0.0, self.modes_w / self.root_weights[None, :], np.nan)
+        self.smoothing, self.ranking, self.change = surface.smoothing, surface.ranking, surface.change
+        self.ids: List[object] = []
+        self.scores: Optional[np.ndarray] = None          # [N, K] of the members; None on a model that was loaded
+        self.gram_diagonal: Optional[np.ndarray] = None
+        self.member_missing: Optional[np.ndarray] = None
+        self.eigh_seconds = 0.0                           # the host eigendecomposition of the last fit
+        self._device: dict = {}
+
+    @property
+    def n_components(self) -> int:
+        return int(self.modes_w.shape[0])
+
+    def _dev(self, name: str) -> torch.Tensor:
+        if name not in self._device:
+            self._device[name] = torch.from_numpy(np.ascontiguousarray(getattr(self, name))).to(self.device)
+        return self._device[name]
+
+    @classmethod
+    def fit(cls, cohort: ThicknessCohort, n_components: int = 10, weights="area", min_valid: int = 2) -> "ThicknessPCA":
+        """The model of ``cohort``.  ``weights``: "area" (``cohort.vertex_areas()``, mm^2), "uniform" (ones) or an array [V] of finite
+        values >= 0.  A vertex at which fewer than ``min_valid`` (>= 1) knees have a value gets weight 0 and is counted in ``n_excluded``.
+        Components are kept where lambda_c > 0 and lambda_c > 1e-12 lambda_1, and K = min(n_components, kept).  On the device: the mean
+        (``ops.group_prepare``), the whitening, the Gram matrix and the modes; on the host, after ONE download of the [N, N] Gram matrix
+        (with the per-vertex counts behind it), ``np.linalg.eigh``; the modes come back in a second, final download."""
+        import time
+        N, V, dev = len(cohort), cohort.n_verts, cohort.device
+        if N < 2:
+            raise ValueError("a PCA needs at least two knees")
+        if int(n_components) < 1 or int(min_valid) < 1:
+            raise ValueError(f"n_components and min_valid must be >= 1, got {n_components!r}, {min_valid!r}")
+        if isinstance(weights, str):
+            if weights not in ("area", "uniform"):
+                raise ValueError(f"weights must be 'area', 'uniform' or an array [{V}], got {weights!r}")
+            w = np.asarray(cohort.vertex_areas(), np.float64) if weights == "area" else np.ones(V)
+        else:
+            w = np.asarray(weights, np.float64)
+        if w.shape != (V,) or not np.isfinite(w).all() or (w < 0.0).any():
+            raise ValueError(f"weights must be {V} finite values >= 0")
+        prep = ops.group_prepare(cohort.values, cohort.mask)
+        out = prep.n < int(min_valid)                                      # a select on the device: the counts are not brought to the host first
+        rw_d = torch.where(out, torch.zeros((), dtype=torch.float64, device=dev), torch.from_numpy(np.sqrt(w)).to(dev))
+        A = ops.cohort_whiten(cohort.values, cohort.mask, prep.mean, rw_d)
+        missing = ((cohort.mask == 0) & (rw_d != 0.0)[None, :]).sum(dim=1)
+        G, mean, rw, missing, n_excluded = _download([ops.rows_cross(A, workspace=ops.rows_cross_workspace(N, N, V, dev)), prep.mean, rw_d, missing,
+                                                      out.sum().reshape(1)])
+        t0 = time.perf_counter()
+        lam, U = np.linalg.eigh(G)
+        seconds = time.perf_counter() - t0
+        lam, U = lam[::-1], U[:, ::-1]
+        kept = int(((lam > 0.0) & (lam > PCA_DROP * lam[0])).sum())
+        K = min(int(n_components), kept)
+        if K < 1:
+            raise ValueError("the cohort has no variance: every whitened knee is zero")
+        lam, U = lam[:K].copy(), np.ascontiguousarray(U[:, :K])
+        s = np.sqrt(lam)
+        R = ops.rows_combine(torch.from_numpy(np.ascontiguousarray(U.T / s[:, None])).to(dev), A).cpu().numpy()
+        for c in range(K):                                                  # the sign rule; the lowest vertex wins ties (np.argmax)
+            if R[c, int(np.argmax(np.abs(R[c])))] < 0.0:
+                R[c], U[:, c] = -R[c], -U[:, c]
+        model = cls(cohort, mean, rw, w, R, s, lam / (N - 1), lam / G.diagonal().sum(), N, int(n_excluded[0]), int(min_valid))
+        model.ids, model.scores, model.gram_diagonal, model.member_missing = list(cohort.ids), s[None, :] * U, G.diagonal().copy(), missing
+        model.eigh_seconds = seconds
+        return model
+
+    # -- scoring ----------------------------------------------------------------------------------------------------------------------------
+    def transform(self, cohort_or_vectors) -> PCAScores:
+        """Knees scored against the model -- a ``ThicknessCohort`` on the model's atlas and cartilage, or vectors [M, V] / [V] (arrays or
+        device tensors, NaN = missing): each is whitened with the model's mean and root weights, its scores are its ordered dots with the
+        root-weighted modes, and Q is read from its squared norm.  Two small launches and ONE download."""
+        knees = cohort_or_vectors
+        if not isinstance(knees, ThicknessCohort):
+            vectors = knees if isinstance(knees, torch.Tensor) else np.asarray(knees, np.float32)
+            vectors = vectors.reshape(1, -1) if vectors.ndim == 1 else vectors
+            knees = ThicknessCohort(self.atlas, self.kind, chunk=max(len(vectors), 1))
+            for row in vectors:
+                knees.add_vector(row)
+        if knees.kind != self.kind or knees.n_verts != self.n_verts:
+            raise ValueError(f"the knees are {knees.kind} maps on {knees.n_verts} vertices, the model is for {self.kind} on {self.n_verts}")
+        if len(knees) < 1:
+            raise ValueError("there is no knee to score")
+        rw_d = self._dev("root_weights")
+        A, norm2 = ops.cohort_whiten(knees.values, knees.mask, self._dev("mean"), rw_d, return_norm2=True)
+        # the split form: one knee against K modes is a single tile, which one workgroup would otherwise walk chunk by chunk
+        scores = ops.rows_cross(A, self._dev("modes_w"), workspace=ops.rows_cross_workspace(len(knees), self.n_components, self.n_verts, self.device))
+        missing = ((knees.mask == 0) & (rw_d != 0.0)[None, :]).sum(dim=1)
+        scores, norm2, missing = _download([scores, norm2, missing])
+        return _pca_record(self.kind, knees.ids, scores, norm2, self.explained_variance, missing, False)
+
+    def member_scores(self) -> PCAScores:
+        """The record of ``transform`` for the model's own knees, from the Gram matrix' diagonal and ``scores``, with no launch.  OPTIMISTIC:
+        every knee helped to shape the modes it is scored on; there is no leave-one-out."""
+        if self.scores is None:
+            raise ValueError("a loaded model does not hold its members: member_scores needs the model that was fitted")
+        return _pca_record(self.kind, self.ids, self.scores, self.gram_diagonal, self.explained_variance, self.member_missing, True)
+
+    def reconstruct(self, scores) -> np.ndarray:
+        """float64 [N', V]: the maps in mm that ``scores`` [N', K] (or [K]) stand for, mean + sum_c score_c modes_mm_c by way of
+        ``ops.rows_combine``; NaN at excluded vertices."""
+        sc = np.asarray(scores, np.float64)
+        sc = np.ascontiguousarray(sc.reshape(1, -1) if sc.ndim == 1 else sc)
+        if sc.ndim != 2 or sc.shape[1] != self.n_components or sc.shape[0] < 1:
+            raise ValueError(f"scores must be [N', {self.n_components}], got {sc.shape}")
+        part = ops.rows_combine(torch.from_numpy(sc).to(self.device), self._dev("modes_w")).cpu().numpy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.root_weights[None, :] != 0.0, self.mean[None, :] + part / self.root_weights[None, :], np.nan)
+
+    def image(self, atlas, mode: int = 0):
+        """``atlas.image`` of physical mode ``mode`` (float32 [H, W], NaN off the surface and at excluded vertices)."""
+        if not 0 <= int(mode) < self.n_components:
+            raise ValueError(f"no mode {mode!r}: the model has {self.n_components}")
+        return atlas.image(np.asarray(self.modes_mm[int(mode)], np.float32), self.kind)
+
+    # -- persistence --------------------------------------------------------------------------------------------------------------------------
+    def save(self, path) -> None:
+        """Write the model as one ``.npz`` -- everything ``transform`` and ``reconstruct`` need -- without the thickness maps and the
+        members' scores."""
+        state = {name: getattr(self, name) for name in _PCA_ARRAYS}
+        state.update(kind=np.asarray(self.kind), n_knees=np.asarray(self.n_knees, np.int64), n_excluded=np.asarray(self.n_excluded, np.int64),
+                     min_valid=np.asarray(self.min_valid, np.int64))
+        NormativeModel.write_state(path, state)
+
+    @classmethod
+    def load(cls, path, atlas) -> "ThicknessPCA":
+        """The model that ``save`` wrote, on ``atlas`` (whose inner mesh of the model's cartilage must have the model's vertices).  It scores
+        new knees; ``member_scores`` needs the members and is not available."""
+        s = NormativeModel.read_state(path)
+        kind = str(s["kind"])
+        surface = ThicknessCohort(atlas, kind)
+        if int(s["mean"].shape[0]) != surface.n_verts:
+            raise ValueError(f"the model has {int(s['mean'].shape[0])} vertices, the atlas' {kind} inner mesh {surface.n_verts}")
+        return cls(surface, *(s[name] for name in _PCA_ARRAYS), int(s["n_knees"]), int(s["n_excluded"]), int(s["min_valid"]))
+
