@@ -1206,6 +1206,77 @@ int oai_regression_f(const void* prepared_dev, size_t prepared_bytes, const unsi
 
 
 /* ------------------------------------------------------------------------------------------
+ * Vertex-wise design columns (csrc/group_regression_vx.hip, tests/vertex_regression_ref.py): the models of "Cohort regression" and
+ * "Cohort F test" in which S = 1 or 2 of the design columns are MAPS on the atlas -- one number per (knee, vertex) and not one per
+ * knee: baseline thickness at the same vertex as the adjustment of a rate of change (regression to the mean), the normative z-score or
+ * the previous visit at the vertex as the regressor.  FSL randomise has such columns as voxel-wise EVs and PALM as -evperdat, AS
+ * RECALLED and NOT pinned to any implementation; the reference has no such step: the definitions are this library's own, pinned by the
+ * numpy restatement and, through it, numpy's least squares.  Everything that is not restated here is as in "Cohort regression" and
+ * "Cohort F test": Freedman and Lane's permutation of the design rows against the residuals, fp64 without contraction, no
+ * floating-point atomics, one accumulator per sum that starts at +0.0, EVERY SUM OVER KNEES IN ASCENDING KNEE INDEX, the Cholesky order
+ * and the PIVOT RULE s > 1e-10 * A_aa, the clamping of an index outside [0, n_knees), row 0 the identity by convention, the limits on
+ * knees, vertices and rows.  Nothing synchronises or reads anything back.
+ *
+ * THE DESIGN AT VERTEX v has p <= 6 columns IN THIS ORDER: [ vertex nuisance (s_n) | global nuisance (q_g) | global interest (k_g) |
+ * vertex interest (s_i) ], with S = s_n + s_i in {1, 2}, s_i in {0, 1}, and s_i = 1 only with k_g = 0: the per-vertex column is then the
+ * one regressor of interest.  The intercept, if any, is among the global nuisance columns.  The per-vertex nuisance columns come first
+ * so that their position is a compile-time constant; the order of nuisance columns changes no statistic mathematically and is part of
+ * the bit contract.
+ *
+ * Inputs.  y_dev float32 and mask_dev uint8 [n_knees][n_verts] as in "Cohort regression" (mask_dev null: every entry is valid).  w_dev
+ * float32 [S][n_knees][n_verts], the per-vertex columns in the design's order; wmask_dev uint8 [S][n_knees][n_verts], or null: every
+ * entry is valid.  nuisance_dev float64 [n_knees][q_g]; global_dev float64 [n_knees][q_g + k_g], the global columns in the design's
+ * order; perm_dev int32 [P][n_knees].
+ *
+ * oai_regression_vx_prepare.  Per vertex v, with my_i the validity of y and mw_si that of column s at knee i, every sum in ascending i:
+ *   m_i  = my_i && mw_0i (&& mw_1i)           the EFFECTIVE MASK: complete cases
+ *   n    = sum m_i            n_dropped = sum (my_i && !m_i)
+ *   wbar_s = (sum_{m_i} (double)w_si) / (double)n            per column s
+ *   wc_si  = (double)w_si - c where mw_si (valid at that knee in its own right), otherwise wbar_s - c;  c = wbar_s if centre, else 0.0
+ *            THE COMPLETED VALUE: a missing covariate entry sits on the complete-case mean, and a centred missing entry is exactly 0.0
+ *            (a select, not a subtraction).  With n = 0 every wc is 0.0.
+ *   mean, d_i, A, h, gamma, r_i, Q, ok   as oai_regression_prepare states them, over the q = s_n + q_g nuisance columns
+ *            z_i = [wc_0i .. | nuisance_i ..], with the effective mask standing in for m; a product with a per-vertex entry is one
+ *            rounding, then the add.
+ * The prepared block is that of "Cohort regression" (R, Q, mean, n, ok) followed by n_dropped int32 [n_verts], the effective mask uint8
+ * [n_knees][n_verts] and WC float64 [S][n_knees][n_verts], each array starting on the next multiple of 256 bytes.
+ *
+ * oai_regression_vx_t and oai_regression_vx_f: rows [p0, p1) of perm_dev -> the tile, float64 [p1 - p0][n_verts] at the start of
+ * workspace_dev, which oai_permutation_reduce, oai_graph_clusters and oai_graph_tfce take as it is.  KNEE j OF ROW pi TAKES THE WHOLE
+ * DESIGN ROW perm[pi][j]: the global entries of that knee, and WC[s][perm[pi][j]][v] for the per-vertex ones.  Missingness stays
+ * attached to the data: entry j counts iff the effective m_j, whichever row it is dealt; a dealt row whose own covariate was missing
+ * contributes its completed value.  UNDER THE IDENTITY ROW a completed value never enters a sum with a non-zero weight (m_j is 0 and r_j
+ * is 0.0 there), so the observed statistic is the exact complete-case fit; only the null distribution sees the mean-imputed entries.
+ * n, dof = n - p and Q do not depend on the row.  Per (row, vertex), g_j the dealt design row (p doubles), j ascending:
+ *   M_ac = sum_j (m_j ? g_ja*g_jc : 0.0), c <= a     the product rounded once; global x global products are formed once per batch by a
+ *          gather kernel, a product with a per-vertex factor is formed in the thread; either way the add is issued as
+ *          fma(prod, m ? 1.0 : 0.0, M), which gives the bits of the stated add for every finite design
+ *   b_a  = sum_j g_ja*r_j                            (a product, then an add)
+ *   L, z, rss, dof, s2, t, F, ess, validity, slope0 and coef0 exactly as oai_regression_t and oai_regression_f state them; t is that of
+ *   the LAST column (the per-vertex one when s_i = 1), F that of the last k = n_interest columns, which are global (s_i = 0).
+ * There is no unmasked fast path: M depends on the vertex.  A null mask_dev together with a null wmask_dev gives THE SAME BITS as masks
+ * of all ones.  The result does not depend on the rows per thread or on the batch; a later batch (p0 > 0) leaves slope0_dev / coef0_dev
+ * alone.  THE CALLER IS RESPONSIBLE FOR HAVING PREPARED WITH THE MATCHING s_n, s_i and q_g = n_columns - S - (k_g).
+ * Refused, with a status and a message that names the entry point, before anything is launched: null pointers, n_columns outside
+ * [1, 6], S outside {1, 2}, s_i = 1 with n_interest > 0, n_interest < 1 for F, no column of interest left for t, bad row ranges, a short
+ * workspace or prepared block.
+ * ---------------------------------------------------------------------------------------- */
+/* All three: 0 for a shape the entry point refuses. */
+size_t oai_regression_vx_prepare_workspace_bytes(long long n_knees, long long n_verts, int n_vertex_columns);
+int oai_regression_vx_prepare(const float* y_dev, const unsigned char* mask_dev, const float* w_dev, const unsigned char* wmask_dev,
+                              const double* nuisance_dev, long long n_knees, long long n_verts, int n_vertex_nuisance, int n_vertex_interest,
+                              int n_global_nuisance, int centre, void* prepared_dev, size_t prepared_bytes, void* stream);
+size_t oai_regression_vx_t_workspace_bytes(long long n_rows, long long n_verts, long long n_knees, int n_columns, int n_vertex_columns);
+int oai_regression_vx_t(const void* prepared_dev, size_t prepared_bytes, const double* global_dev, const int* perm_dev, long long n_knees,
+                        long long n_verts, int n_columns, int n_vertex_nuisance, int n_vertex_interest, long long p0, long long p1, void* workspace_dev,
+                        size_t workspace_bytes, double* slope0_dev, void* stream);
+size_t oai_regression_vx_f_workspace_bytes(long long n_rows, long long n_verts, long long n_knees, int n_columns, int n_vertex_columns);
+int oai_regression_vx_f(const void* prepared_dev, size_t prepared_bytes, const double* global_dev, const int* perm_dev, long long n_knees,
+                        long long n_verts, int n_columns, int n_vertex_nuisance, int n_vertex_interest, int n_interest, long long p0, long long p1,
+                        void* workspace_dev, size_t workspace_bytes, double* coef0_dev, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free cluster enhancement (csrc/graph_tfce.hip, tests/graph_tfce_ref.py): a t tile in, a tile of the same shape out in which
  * every vertex holds the integral, over all thresholds h at or below its |t|, of extent(h)^E * h^H -- extent(h) being the size of the
  * vertex' connected component of {|t| >= h} on the surface.  It takes the place of a hand-picked cluster threshold: the family-wise p

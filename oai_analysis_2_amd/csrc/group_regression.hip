@@ -51,6 +51,7 @@
 #pragma clang fp contract(off)
 
 #include "regression_solve.h"
+#include "regression_rows.h"
 
 namespace {
 
@@ -58,27 +59,13 @@ using namespace oai;
 
 constexpr int kT = 256;                            // vertices of a block
 // kMaxCols (p), kPivot, tri(), cholesky<P> and forward_solve<P>: csrc/regression_solve.h, shared with csrc/normative.hip
+// Prepared (the prepared block): csrc/regression_rows.h; the epilogue of a row: csrc/regression_epilogue_body.h -- both shared with
+// csrc/group_regression_vx.hip.  The 24 instances of the hot kernels were compared before and after the two moved there: the same VGPR,
+// SGPR and scratch figures, instance by instance (code-object metadata and the compiler's kernel-resource remarks for gfx950).
 
 __host__ __device__ constexpr int rows_per_thread(int p, bool masked) {
     return masked ? (p == 1 ? 16 : p == 2 ? 8 : p <= 4 ? 2 : 1) : (p <= 2 ? 16 : 8);
 }
-
-// ---- the prepared block ----------------------------------------------------------------------------------------------------------------
-struct Prepared {
-    double *R, *Q, *mean;
-    int* n;
-    unsigned char* ok;
-    size_t bytes;
-    Prepared(const void* base, long long N, long long V) {
-        Ws ws(base);
-        R = ws.take<double>((size_t)(N * V));
-        Q = ws.take<double>((size_t)V);
-        mean = ws.take<double>((size_t)V);
-        n = ws.take<int>((size_t)V);
-        ok = ws.take<unsigned char>((size_t)V);
-        bytes = ws.off;
-    }
-};
 
 // one thread per vertex, knees in ascending index: the counted sum; the normal equations of the nuisance columns; the residuals
 template <int QN>
@@ -278,36 +265,7 @@ __device__ __forceinline__ void regression_rows(const double* __restrict__ res, 
             for (int k = 0; k < T; ++k) L[k] = fr[k];
             pass = fr[T] != 0.0;
         }
-        forward_solve<P>(L, b[r]);
-        double rss = Q;
-#pragma unroll
-        for (int a = 0; a < P; ++a) rss = rss - b[r][a] * b[r][a];
-        const double s2 = rss / (double)dof;
-        const bool valid = ok && pass && s2 > 0.0;
-        if (!FSTAT) {
-            const double t = b[r][P - 1] / sqrt(s2);
-            tile[(r0 + r) * V + v] = valid ? t : (double)NAN;
-            if (first && out0 && r0 + r == 0) out0[v] = valid ? b[r][P - 1] / L[T - 1] : (double)NAN;
-        } else {
-            const int q = P - ki;                                                 // the columns of interest are q .. P - 1
-            double ess = 0.0;
-#pragma unroll
-            for (int a = 0; a < P; ++a) ess = a >= q ? ess + b[r][a] * b[r][a] : ess;
-            const double F = (ess / (double)ki) / s2;
-            tile[(r0 + r) * V + v] = valid ? F : (double)NAN;
-            if (r == 0 && first && out0 && r0 == 0) {                             // L^T beta = z on the trailing block, from the last row up
-                double beta[P];
-#pragma unroll
-                for (int a = P - 1; a >= 0; --a) {
-                    if (a < q) continue;
-                    double s = b[r][a];
-#pragma unroll
-                    for (int j = a + 1; j < P; ++j) s = s - L[tri(j) + a] * beta[j];
-                    beta[a] = s / L[tri(a) + a];
-                    out0[(long long)(a - q) * V + v] = valid ? beta[a] : (double)NAN;
-                }
-            }
-        }
+#include "regression_epilogue_body.h"
     }
 }
 

@@ -1003,6 +1003,119 @@ def regression_f(prepared: RegressionPrepared, design: torch.Tensor, perm: torch
     return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
 
 
+# ---- vertex-wise design columns (include/oai_hip.h, "Vertex-wise design columns"; csrc/group_regression_vx.hip) ------------------------------
+MAX_VERTEX_COLUMNS = 2
+
+
+@dataclass
+class RegressionVxPrepared:
+    """The prepared block of ``regression_vx_prepare`` and views of its arrays (include/oai_hip.h states the layout): ``R``, ``Q``, ``mean``,
+    ``n``, ``ok`` as in ``RegressionPrepared`` -- ``n`` counts the COMPLETE cases --, then ``n_dropped`` int32 [V] (knees with a value whose
+    covariate is missing), ``m`` uint8 [N,V] (the effective mask) and ``WC`` float64 [S,N,V] (the completed per-vertex columns).
+    ``n_vertex_nuisance``, ``n_vertex_interest``, ``n_global_nuisance``: the s_n, s_i and q_g it was prepared with."""
+    block: torch.Tensor
+    n_knees: int
+    n_verts: int
+    n_vertex_nuisance: int
+    n_vertex_interest: int
+    n_global_nuisance: int
+    centre: bool
+    R: torch.Tensor
+    Q: torch.Tensor
+    mean: torch.Tensor
+    n: torch.Tensor
+    ok: torch.Tensor
+    n_dropped: torch.Tensor
+    m: torch.Tensor
+    WC: torch.Tensor
+
+
+def regression_vx_prepare(values: torch.Tensor, mask: Optional[torch.Tensor], vertex_columns: torch.Tensor,
+                          vertex_mask: Optional[torch.Tensor] = None, nuisance: Optional[torch.Tensor] = None, n_vertex_interest: int = 0,
+                          centre: bool = True) -> RegressionVxPrepared:
+    """What every permutation of a regression with per-vertex design columns re-uses, once per test: float32 ``values`` [N,V] with an
+    optional uint8 / bool ``mask``; float32 ``vertex_columns`` [S,N,V] (S = 1 or 2, in the design's order: nuisance first, and with
+    ``n_vertex_interest`` = 1 the regressor of interest last) with an optional ``vertex_mask`` [S,N,V]; the float64 global ``nuisance``
+    columns [N,q_g] (the intercept among them; None: q_g = 0) -> per vertex the complete cases, the completed columns and the residuals of
+    the values on the nuisance columns over them.  fp64 in a stated order: bit-reproducible.  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or values.shape[0] < 2 or values.shape[1] < 1:
+        raise ValueError(f"values must be [N >= 2, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V = int(values.shape[0]), int(values.shape[1])
+    w = _chk(vertex_columns, "vertex_columns")
+    if w.dim() != 3 or not 1 <= w.shape[0] <= MAX_VERTEX_COLUMNS or tuple(w.shape[1:]) != (N, V) or w.device != values.device:
+        raise ValueError(f"vertex_columns must be float32 [1 .. {MAX_VERTEX_COLUMNS}, {N}, {V}] on {values.device}, got {tuple(w.shape)} on {w.device}")
+    S, si = int(w.shape[0]), int(n_vertex_interest)
+    if si not in (0, 1):
+        raise ValueError(f"n_vertex_interest must be 0 or 1, got {n_vertex_interest!r}")
+    wmask = None
+    if vertex_mask is not None:
+        wmask = _chk(vertex_mask.view(torch.uint8) if vertex_mask.dtype == torch.bool else vertex_mask, "vertex_mask", torch.uint8)
+        if tuple(wmask.shape) != tuple(w.shape) or wmask.device != w.device:
+            raise ValueError(f"vertex_mask must have the shape of vertex_columns {tuple(w.shape)} and live on their GPU, got {tuple(wmask.shape)} "
+                             f"on {wmask.device}")
+    qg = 0
+    if nuisance is not None and nuisance.numel() > 0:
+        nuisance = _design(nuisance, "nuisance", N, values.device, 1, MAX_DESIGN_COLUMNS - 1 - (S - si))
+        qg = int(nuisance.shape[1])
+    block = _lib.workspace("oai_regression_vx_prepare", values.device, N, V, S)
+    _lib.call("oai_regression_vx_prepare", values.data_ptr(), _ptr(mask), w.data_ptr(), _ptr(wmask), nuisance.data_ptr() if qg else None, N, V, S - si,
+              si, qg, int(bool(centre)), block.data_ptr(), block.numel(), _lib.STREAM, device=values.device)
+    parts = _block_views(block, (("R", torch.float64, (N, V)), ("Q", torch.float64, (V,)), ("mean", torch.float64, (V,)), ("n", torch.int32, (V,)),
+                                 ("ok", torch.uint8, (V,)), ("n_dropped", torch.int32, (V,)), ("m", torch.uint8, (N, V)),
+                                 ("WC", torch.float64, (S, N, V))))
+    return RegressionVxPrepared(block, N, V, S - si, si, qg, bool(centre), **parts)
+
+
+def _regression_vx_batch(name: str, prepared: RegressionVxPrepared, design, perm, p0, p1, n_global: int, extra, workspace, out0, out0_name: str,
+                         out0_shape) -> torch.Tensor:
+    """The one call path of ``regression_vx_t`` and ``regression_vx_f``: the global columns [N, n_global] (None where there are none), the
+    index rows, the row range, the optional output of row 0, the workspace; ``extra``: the entry point's own arguments after s_i."""
+    dev, N, V = prepared.block.device, prepared.n_knees, prepared.n_verts
+    sn, si = prepared.n_vertex_nuisance, prepared.n_vertex_interest
+    p = sn + si + n_global
+    if n_global == 0 and (design is None or design.numel() == 0):
+        design = torch.empty((N, 1), dtype=torch.float64, device=dev)         # checked like any design; never read
+        lo = 1
+    else:
+        lo = n_global
+    design, perm, p0, p1, out0 = _regression_batch(prepared, design, perm, p0, p1, lo, lo, out0, out0_name, out0_shape)
+    need = int(getattr(_lib.load(), name + "_workspace_bytes")(p1 - p0, V, N, p, sn + si))
+    ws = _tile_workspace(workspace, need, dev)
+    _lib.call(name, prepared.block.data_ptr(), prepared.block.numel(), design.data_ptr() if n_global else None, perm.data_ptr(), N, V, p, sn, si, *extra,
+              p0, p1, ws.data_ptr(), ws.numel(), _ptr(out0), _lib.STREAM, device=dev)
+    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+
+
+def regression_vx_t(prepared: RegressionVxPrepared, design: Optional[torch.Tensor], perm: torch.Tensor, p0: int, p1: int,
+                    workspace: Optional[torch.Tensor] = None, slope0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The t tile of rows [p0, p1) of ``perm`` (as in ``regression_t``): float64 [p1 - p0, V], the t of the LAST design column -- the
+    per-vertex regressor when the block was prepared with ``n_vertex_interest`` = 1, otherwise the last column of the float64 global
+    ``design`` [N, q_g + 1] (None when there are no global columns at all).  Knee j of a row takes the WHOLE design row ``perm[row, j]``,
+    the per-vertex entries included.  ``slope0`` float64 [V]: with ``p0`` = 0, receives row 0's coefficient of that column.  ``workspace``:
+    a uint8 device buffer of ``oai_regression_vx_t_workspace_bytes``, reused between batches; the tile is its front.  Does not synchronise."""
+    n_global = prepared.n_global_nuisance + (0 if prepared.n_vertex_interest else 1)
+    return _regression_vx_batch("oai_regression_vx_t", prepared, design, perm, p0, p1, n_global, (), workspace, slope0, "slope0", (prepared.n_verts,))
+
+
+def regression_vx_f(prepared: RegressionVxPrepared, design: torch.Tensor, perm: torch.Tensor, p0: int, p1: int, n_interest: int,
+                    workspace: Optional[torch.Tensor] = None, coef0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The F tile of rows [p0, p1) of ``perm``: float64 [p1 - p0, V], the F of the LAST ``n_interest`` columns of the float64 global
+    ``design`` [N, q_g + n_interest], tested jointly given the per-vertex nuisance columns and the global ones before them.  The block must
+    have been prepared with ``n_vertex_interest`` = 0.  ``coef0`` float64 [n_interest, V]: with ``p0`` = 0, receives row 0's coefficients of
+    those columns.  ``workspace``: as in ``regression_vx_t``.  Does not synchronise."""
+    k = int(n_interest)
+    most = MAX_DESIGN_COLUMNS - prepared.n_vertex_nuisance - prepared.n_global_nuisance
+    if prepared.n_vertex_interest:
+        raise ValueError("regression_vx_f tests global columns: the block was prepared with a per-vertex column of interest, which regression_vx_t tests")
+    if not 1 <= k <= most:
+        raise ValueError(f"n_interest must be 1 .. {most} beside the {prepared.n_vertex_nuisance} + {prepared.n_global_nuisance} nuisance columns of "
+                         f"the prepared block, got {n_interest!r}")
+    return _regression_vx_batch("oai_regression_vx_f", prepared, design, perm, p0, p1, prepared.n_global_nuisance + k, (k,), workspace, coef0, "coef0",
+                                (k, prepared.n_verts))
+
+
 # ---- normative deviation (include/oai_hip.h, "Normative deviation"; csrc/normative.hip) ------------------------------------------------------
 NORMATIVE_SCORE_ROWS = 8             # rows per thread of the score kernel
 

@@ -79,6 +79,12 @@ residual Q outside it per knee (include/oai_hip.h, "Cohort PCA"; csrc/cohort_pca
     pca = cohort.pca(10)                                                            # modes_mm, explained_variance_ratio, scores
     screen = pca.member_scores(); screen.q_fraction, screen.t2                      # a registration failure stands out in q
     regression_test(cohort, x=pca.scores[:, 0]), pca.transform(new_knee).q
+
+``vertex_covariates=`` on ``regression_test``, ``f_test`` and ``anova_test`` puts MAPS into the design -- one number per knee and vertex,
+baseline thickness at the same vertex above all, without which a rate of change regresses to the mean -- and ``x`` of ``regression_test``
+may itself be a map (include/oai_hip.h, "Vertex-wise design columns"; csrc/group_regression_vx.hip; tests/vertex_regression_ref.py).
+
+    regression_test(visits.change("rate"), x=kl_grade, covariates=np.stack([age, sex], axis=1), vertex_covariates=visits.first_visit()).p_fwer
 """
 from __future__ import annotations
 
@@ -778,6 +784,16 @@ class LongitudinalCohort:
         return self._derived(ids, *(t.index_select(0, torch.tensor(picked, dtype=torch.int64, device=self.device))
                                     for t in (self.rows.values, self.rows.mask)))
 
+    def first_visit(self) -> ThicknessCohort:
+        """Every subject's EARLIEST row as a ``ThicknessCohort`` whose ids are ``subjects`` (so the rows match those of ``change``), missing
+        where that row is -- baseline thickness at the same vertex, the adjustment a rate of change needs against regression to the mean:
+        ``regression_test(visits.change("rate"), x=kl_grade, covariates=np.stack([age, sex], axis=1), vertex_covariates=visits.first_visit())``.  A copy."""
+        if not len(self):
+            raise ValueError("the cohort holds no visit")
+        table = visit_table(self._subject, self._years)
+        picked = torch.from_numpy(table.rows[table.offsets[:-1]].astype(np.int64)).to(self.device)
+        return self._derived(table.subjects, self.rows.values.index_select(0, picked), self.rows.mask.index_select(0, picked))
+
     def _derived(self, ids, values: torch.Tensor, mask: torch.Tensor) -> ThicknessCohort:
         out = ThicknessCohort(self.atlas, self.kind, self.rows.use_coverage, self.rows.chunk)
         out.ids, out._graph, out._areas, out.smoothing = list(ids), self.rows._graph, self.rows._areas, self.rows.smoothing
@@ -1202,6 +1218,9 @@ class RegressionResult(_SurfaceResult):
     exact: bool
 
     IMAGES = ("t", "slope", "partial_r", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce", "p_tfce")
+    # With per-vertex design columns (``vertex_covariates``, or ``x`` as a map): int32 [V], the knees with a value at the vertex that a
+    # missing covariate dropped -- ``n`` and ``dof`` then count the complete cases.  None otherwise; set on the instance, not a field.
+    n_dropped = None
 
 
 def _table_bytes(n_knees: int, n_columns: int) -> int:
@@ -1263,16 +1282,130 @@ def _index_rows(permutations, make, n_knees: int) -> IndexPermutations:
     return IndexPermutations(np.ascontiguousarray(index, dtype=np.int32), perms.exact)
 
 
+# ---- vertex-wise design columns (include/oai_hip.h, "Vertex-wise design columns"; csrc/group_regression_vx.hip) ------------------------------
+def _is_map(x) -> bool:
+    """Is ``x`` one number per (knee, vertex) -- a ``ThicknessCohort`` or a two-dimensional array or tensor -- and not one per knee?"""
+    return isinstance(x, ThicknessCohort) or (not isinstance(x, (list, tuple)) and getattr(x, "ndim", 1) == 2)
+
+
+def _vertex_maps(cohort: ThicknessCohort, maps, name: str) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """The per-vertex columns that ``name`` (``vertex_covariates`` or ``x``) passes, each as (float32 values [N, V], uint8 mask [N, V]) on
+    the cohort's GPU in the cohort's row order: a ``ThicknessCohort`` on the same atlas, cartilage and device whose rows are matched BY ID
+    as ``paired_test`` matches them, or an [N, V] array or tensor in row order with NaN for a missing entry; or a list of such."""
+    if maps is None:
+        return []
+    N, V, dev = len(cohort), cohort.n_verts, cohort.device
+    out = []
+    for k, one in enumerate(maps if isinstance(maps, (list, tuple)) else [maps]):
+        what = name if not isinstance(maps, (list, tuple)) else f"{name}[{k}]"
+        if isinstance(one, ThicknessCohort):
+            if one.kind != cohort.kind or one.n_verts != V or one.device != dev:
+                raise ValueError(f"{what} must hold the same cartilage of the same atlas on the same GPU as the cohort ({cohort.kind!r}, {V} vertices, "
+                                 f"{dev}), got {one.kind!r}, {one.n_verts} vertices, {one.device}")
+            where = {id_: i for i, id_ in enumerate(one.ids)}
+            if len(where) != len(one) or len(set(cohort.ids)) != N or set(cohort.ids) != set(where):
+                raise ValueError(f"{what} needs the same ids as the cohort, each once")
+            order = torch.tensor([where[id_] for id_ in cohort.ids], dtype=torch.int64, device=dev)
+            out.append((one.values.index_select(0, order), one.mask.index_select(0, order)))
+            continue
+        if isinstance(one, torch.Tensor):
+            if one.device != dev:
+                raise ValueError(f"{what} must live on the cohort's GPU ({dev}), got {one.device}")
+            vec = one.to(torch.float32)
+        else:
+            vec = torch.from_numpy(np.ascontiguousarray(np.asarray(one, np.float32))).to(dev)
+        if tuple(vec.shape) != (N, V):
+            raise ValueError(f"{what} must be a ThicknessCohort or [{N}, {V}] (one row per knee of the cohort, one entry per vertex), got shape "
+                             f"{tuple(vec.shape)}")
+        ok = ~torch.isnan(vec)
+        out.append((torch.where(ok, vec, torch.zeros_like(vec)), ok.to(torch.uint8)))
+    return out
+
+
+def _vx_setup(cohort: ThicknessCohort, what: str, vertex_covariates, x_map, n_global: int, permutations, n_permutations, seed, blocks,
+              cluster_threshold, tfce, batch):
+    """What the tests share once a per-vertex column is in play: the columns in the design's order (nuisance first, the regressor of
+    interest last), the count checks, the index rows and the ``_Batches``.  ``n_global``: the global columns of the design."""
+    N = len(cohort)
+    if N < 2:
+        raise ValueError(f"{what} needs at least two knees")
+    nuis, interest = _vertex_maps(cohort, vertex_covariates, "vertex_covariates"), _vertex_maps(cohort, x_map, "x")
+    if len(interest) > 1:
+        raise ValueError("x must be ONE map: one regressor of interest")
+    S = len(nuis) + len(interest)
+    if S > ops.MAX_VERTEX_COLUMNS:
+        raise ValueError(f"vertex_covariates: at most {ops.MAX_VERTEX_COLUMNS} per-vertex columns are supported (x as a map counts), got {S}")
+    p = S + n_global
+    if p > ops.MAX_DESIGN_COLUMNS:
+        raise ValueError(f"the design has {p} columns ({n_global} global ones and {S} per-vertex ones from vertex_covariates and x); at most "
+                         f"{ops.MAX_DESIGN_COLUMNS} are supported")
+    perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
+    V, dev = cohort.n_verts, cohort.device
+    pg = p - S
+    batches = _Batches(cohort, len(perms), V, dev, cluster_threshold, tfce, batch, N * 8 * (pg + pg * (pg + 1) // 2 + 1))
+    columns = torch.stack([c[0] for c in nuis + interest])
+    masks = torch.stack([c[1] for c in nuis + interest])
+    return perms, batches, columns, masks, len(interest), p, S
+
+
+def _regression_vx(cohort: ThicknessCohort, x, covariates, vertex_covariates, intercept: bool, n_permutations, cluster_threshold, seed, blocks,
+                   permutations, batch, tfce) -> RegressionResult:
+    """``regression_test`` with per-vertex design columns: ``vertex_covariates`` as nuisance and, where ``x`` is a map, ``x`` itself."""
+    N, x_map = len(cohort), _is_map(x)
+    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
+    setup = _vx_setup(cohort, "regression_test", vertex_covariates, x if x_map else None, n_cov + int(bool(intercept)) + (0 if x_map else 1),
+                      permutations, n_permutations, seed, blocks, cluster_threshold, tfce, batch)
+    perms, batches, columns, masks, si, p, S = setup
+    if x_map:                                                              # every global column is nuisance: the intercept and the covariates
+        scale = 1.0                                                        # per-vertex columns are not rescaled: slope is per unit of the map
+        design = (_design_matrix(covariates, None, bool(intercept), N, [f"covariate {j}" for j in range(n_cov)])[1] if n_cov else
+                  np.ones((N, int(bool(intercept)))))
+        nuisance = design
+    else:
+        nuisance, design, scale = _design_columns(x, covariates, bool(intercept), N)
+    dev, V = cohort.device, cohort.n_verts
+    index = torch.from_numpy(perms.index).to(dev)
+    design_d = torch.from_numpy(np.ascontiguousarray(design)).to(dev) if design.shape[1] else None
+    prepared = ops.regression_vx_prepare(cohort.values, cohort.mask, columns, masks, torch.from_numpy(np.ascontiguousarray(nuisance)).to(dev)
+                                         if nuisance.shape[1] else None, n_vertex_interest=si, centre=bool(intercept))
+    slope0 = torch.empty(V, dtype=torch.float64, device=dev)
+    ws = _lib.workspace("oai_regression_vx_t", dev, batches.rows, V, N, p, S)
+    host, shared = batches.run(lambda p0, p1: ops.regression_vx_t(prepared, design_d, index, p0, p1, workspace=ws, slope0=slope0 if p0 == 0 else None),
+                               {"slope": slope0, "n": prepared.n, "n_dropped": prepared.n_dropped})
+    t, n = host["t"], host["n"]
+    dof = n.astype(np.int64) - p
+    with np.errstate(invalid="ignore", divide="ignore"):
+        partial_r = t / np.sqrt(t * t + dof.astype(np.float64))
+    res = RegressionResult(kind=cohort.kind, n=n, dof=dof, slope=host["slope"] / scale, partial_r=partial_r, exact=perms.exact, **shared)
+    res.n_dropped = host["n_dropped"]
+    return res
+
+
 def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool = True, n_permutations: int = 10000,
                     cluster_threshold: Optional[float] = None, seed: int = 0, blocks=None, permutations=None,
-                    batch: Optional[int] = None, tfce=None) -> RegressionResult:
+                    batch: Optional[int] = None, tfce=None, vertex_covariates=None) -> RegressionResult:
     """How does thickness vary with ``x`` (one entry per knee: KL grade, BMI, years since baseline, or a 0 / 1 dummy), vertex by vertex,
     adjusted for ``covariates`` ([N] or [N, k]: age, a sex dummy, ...) and, with ``intercept``, a constant?  Per vertex the general linear
     model over the knees with a value there, and the t of the coefficient of ``x``; its null distribution comes from Freedman-Lane
     permutation (include/oai_hip.h) with the rows of ``index_permutations(N, n_permutations, seed, blocks)``, or of ``permutations`` (an
     ``IndexPermutations`` or int rows [P, N], row 0 the identity).  At most six design columns in all.  The columns are centred (with an
     intercept) and scaled to unit length on the host, which changes neither t nor the p-values; ``slope`` is given per unit of the ``x``
-    that was passed.  ``cluster_threshold``, ``batch``, ``tfce``: as in ``two_sample_test`` (default batch: ``regression_batch``)."""
+    that was passed.  ``cluster_threshold``, ``batch``, ``tfce``: as in ``two_sample_test`` (default batch: ``regression_batch``).
+
+    ``vertex_covariates``: one or two MAPS to adjust for at every vertex -- baseline thickness at the same vertex above all, without
+    which a rate of change regresses to the mean (include/oai_hip.h, "Vertex-wise design columns"; csrc/group_regression_vx.hip;
+    tests/vertex_regression_ref.py).  A ``ThicknessCohort`` on the same atlas, cartilage and GPU whose rows are matched to the cohort's BY
+    ID (the same ids, each once), an [N, V] array or tensor in row order with NaN for a missing entry, or a list of at most two of these.
+    ``x`` may itself be such a map: the regressor of interest is then per vertex and ``slope`` is per unit of the map.  At most two
+    per-vertex columns and six columns in all.  The analysis is complete-case per vertex: a knee counts where its value AND its
+    covariates are there; ``n`` and ``dof`` count those, and ``n_dropped`` (None without per-vertex columns) the knees with a value that
+    a missing covariate dropped.  The observed statistic is the exact complete-case fit; within the null distribution a permuted design
+    row whose covariate is missing stands on the complete-case mean.  Per-vertex columns are centred (with an intercept) on the device and
+    not rescaled.  The coefficient of a per-vertex NUISANCE column is not returned: pass it as ``x`` to get it.  None: the test runs as
+    it always has."""
+    if vertex_covariates is not None or _is_map(x):
+        return _regression_vx(cohort, x, covariates, vertex_covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations,
+                              batch, _tfce_settings(tfce))
     tfce = _tfce_settings(tfce)
     N = len(cohort)
     if N < 2:
@@ -1330,6 +1463,7 @@ class FResult(_SurfaceResult):
     group_mean: Optional[np.ndarray] = None
 
     IMAGES = ("f", "partial_eta2", "p_fwer", "p_uncorrected", "n", "cluster_label", "tfce", "p_tfce")
+    n_dropped = None        # as in ``RegressionResult``: set with ``vertex_covariates``, when ``n`` and ``dof2`` count the complete cases
 
 
 def _design_matrix(X, covariates, intercept: bool, n_knees: int, names: Optional[Sequence[str]] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -1374,12 +1508,16 @@ def _design_matrix(X, covariates, intercept: bool, n_knees: int, names: Optional
 
 
 def _f_run(cohort: ThicknessCohort, what: str, X, names, covariates, intercept: bool, n_permutations: int, cluster_threshold, seed: int, blocks,
-           permutations, batch, tfce, groups: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> FResult:
-    """What ``f_test`` and ``anova_test`` share.  ``groups``: (levels, the level index of every knee) -- then also the counted means."""
+           permutations, batch, tfce, groups: Optional[Tuple[np.ndarray, np.ndarray]] = None, vertex_covariates=None) -> FResult:
+    """What ``f_test`` and ``anova_test`` share.  ``groups``: (levels, the level index of every knee) -- then also the counted means.
+    ``vertex_covariates``: per-vertex nuisance columns (``regression_test`` says what they are), or None."""
     tfce = _tfce_settings(tfce)
     N = len(cohort)
     if N < 2:
         raise ValueError(f"{what} needs at least two knees")
+    if vertex_covariates is not None:
+        return _f_run_vx(cohort, what, X, names, covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
+                         groups, vertex_covariates)
     nuisance, design, scales = _design_matrix(X, covariates, bool(intercept), N, names)
     perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
     P, p, k = len(perms), design.shape[1], len(scales)
@@ -1391,15 +1529,27 @@ def _f_run(cohort: ThicknessCohort, what: str, X, names, covariates, intercept: 
     prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
     coef0 = torch.empty((k, V), dtype=torch.float64, device=dev)
     extras = {"coef": coef0, "n": prepared.n}
-    if groups is not None:
-        for g in range(len(groups[0])):                                    # the descriptive side: n and mean of every level, per vertex
-            idx = torch.from_numpy(np.nonzero(groups[1] == g)[0]).to(dev)
-            prep = ops.group_prepare(values.index_select(0, idx), mask.index_select(0, idx))
-            extras.update({f"n{g}": prep.n, f"mean{g}": prep.mean})
+    extras.update(_group_sides(values, mask, groups))
     ws = _lib.workspace("oai_regression_f", dev, batches.rows, V, N, p)
     host, shared = batches.run(lambda p0, p1: ops.regression_f(prepared, design_d, index, p0, p1, k, workspace=ws, coef0=coef0 if p0 == 0 else None),
                                extras)
-    f, n = shared.pop("t"), host["n"]
+    return _f_result(cohort, host, shared, perms, p, scales, groups)
+
+
+def _group_sides(values: torch.Tensor, mask: torch.Tensor, groups) -> dict:
+    """The descriptive side of ``anova_test``: n and mean of every level, per vertex, as device tensors to download with the rest."""
+    sides = {}
+    if groups is not None:
+        for g in range(len(groups[0])):
+            idx = torch.from_numpy(np.nonzero(groups[1] == g)[0]).to(values.device)
+            prep = ops.group_prepare(values.index_select(0, idx), mask.index_select(0, idx))
+            sides.update({f"n{g}": prep.n, f"mean{g}": prep.mean})
+    return sides
+
+
+def _f_result(cohort: ThicknessCohort, host: dict, shared: dict, perms: IndexPermutations, p: int, scales: np.ndarray, groups) -> FResult:
+    """The ``FResult`` of one download: what ``_f_run`` and ``_f_run_vx`` do with it alike."""
+    f, n, k = shared.pop("t"), host["n"], len(scales)
     dof2 = n.astype(np.int64) - p
     with np.errstate(invalid="ignore", divide="ignore"):
         partial_eta2 = (k * f) / (k * f + dof2.astype(np.float64))
@@ -1411,9 +1561,38 @@ def _f_run(cohort: ThicknessCohort, what: str, X, names, covariates, intercept: 
                    max_f=shared.pop("max_abs"), exact=perms.exact, **described, **shared)
 
 
+def _f_run_vx(cohort: ThicknessCohort, what: str, X, names, covariates, intercept: bool, n_permutations, cluster_threshold, seed, blocks, permutations,
+              batch, tfce, groups, vertex_covariates) -> FResult:
+    """``_f_run`` with per-vertex nuisance columns (include/oai_hip.h, "Vertex-wise design columns"): the global design is built as ever,
+    the maps stand before it, and ``n`` / ``dof2`` count the complete cases."""
+    N = len(cohort)
+    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
+    n_tested = 1 if np.ndim(X) == 1 else int(np.shape(X)[-1])
+    setup = _vx_setup(cohort, what, vertex_covariates, None, n_cov + int(bool(intercept)) + n_tested, permutations, n_permutations, seed, blocks,
+                      cluster_threshold, tfce, batch)
+    perms, batches, columns, masks, _, p, S = setup
+    nuisance, design, scales = _design_matrix(X, covariates, bool(intercept), N, names)
+    k = len(scales)
+    values, mask = cohort.values, cohort.mask
+    V, dev = int(values.shape[1]), values.device
+    index = torch.from_numpy(perms.index).to(dev)
+    design_d = torch.from_numpy(design).to(dev)
+    prepared = ops.regression_vx_prepare(values, mask, columns, masks, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None,
+                                         centre=bool(intercept))
+    coef0 = torch.empty((k, V), dtype=torch.float64, device=dev)
+    extras = {"coef": coef0, "n": prepared.n, "n_dropped": prepared.n_dropped}
+    extras.update(_group_sides(values, mask, groups))
+    ws = _lib.workspace("oai_regression_vx_f", dev, batches.rows, V, N, p, S)
+    host, shared = batches.run(lambda p0, p1: ops.regression_vx_f(prepared, design_d, index, p0, p1, k, workspace=ws, coef0=coef0 if p0 == 0 else None),
+                               extras)
+    res = _f_result(cohort, host, shared, perms, p, scales, groups)
+    res.n_dropped = host["n_dropped"]
+    return res
+
+
 def f_test(cohort: ThicknessCohort, X, covariates=None, intercept: bool = True, n_permutations: int = 10000,
            cluster_threshold: Optional[float] = None, seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None,
-           tfce=None) -> FResult:
+           tfce=None, vertex_covariates=None) -> FResult:
     """Do the columns of ``X`` ([N] or [N, k]: the dummies of a factor, an interaction with its main effect, a linear and a quadratic
     term) explain thickness JOINTLY, vertex by vertex, adjusted for ``covariates`` ([N] or [N, c]) and, with ``intercept``, a constant?  Per
     vertex the general linear model over the knees with a value there and the F of the k columns given the others (include/oai_hip.h,
@@ -1424,8 +1603,14 @@ def f_test(cohort: ThicknessCohort, X, covariates=None, intercept: bool = True, 
     infinity, a constant column, more than six columns, a design without full column rank -- the message names the column.
     ``cluster_threshold`` is an F value; ``batch`` as in ``regression_test``; ``tfce``: True or a ``TFCE``, applied to F as it is -- F scales
     like t squared, so H = 1 on F weighs height roughly as H = 2 does on |t|, and ``dh`` and ``max_steps * dh`` are in units of F
-    (``FResult`` says more).  With k = 1, F is the square of ``regression_test``'s t and the p-values are those of its two-sided test."""
-    return _f_run(cohort, "f_test", X, None, covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce)
+    (``FResult`` says more).  With k = 1, F is the square of ``regression_test``'s t and the p-values are those of its two-sided test.
+    ``vertex_covariates``: one or two maps to adjust for at every vertex, as in ``regression_test``, which says what they are and what
+    ``n``, ``dof2`` and ``n_dropped`` then count; the tested columns themselves are one number per knee (a map as ``X`` is refused: test
+    it with ``regression_test(cohort, x=map)``)."""
+    if isinstance(X, ThicknessCohort) or (_is_map(X) and X.shape[-1] > ops.MAX_DESIGN_COLUMNS and X.shape[-1] == cohort.n_verts):
+        raise ValueError("X must hold one entry per knee and column: a map (one entry per knee and vertex) is tested with regression_test(cohort, x=map)")
+    return _f_run(cohort, "f_test", X, None, covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
+                  vertex_covariates=vertex_covariates)
 
 
 def _anova_levels(groups, n_knees: int, n_covariates: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -1448,20 +1633,23 @@ def _anova_levels(groups, n_knees: int, n_covariates: int) -> Tuple[np.ndarray, 
 
 
 def anova_test(cohort: ThicknessCohort, groups, covariates=None, n_permutations: int = 10000, cluster_threshold: Optional[float] = None,
-               seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None, tfce=None) -> FResult:
+               seed: int = 0, blocks=None, permutations=None, batch: Optional[int] = None, tfce=None, vertex_covariates=None) -> FResult:
     """Does thickness differ ACROSS the levels of a factor (``groups``: an integer label per knee with 2 to 6 distinct levels -- KL grade,
     site, treatment arm), vertex by vertex, adjusted for ``covariates``?  One-way analysis of (co)variance: the design is an intercept, the
     covariates and a 0 / 1 dummy for every level after the smallest one, and the dummies are tested jointly as in ``f_test``, whose other
     arguments these are.  The six-column limit holds: levels - 1 + covariates + 1 <= 6.  Every level needs at least two knees.
     ``coefficients[j]`` is the adjusted difference of level ``levels[j + 1]`` from level ``levels[0]``; ``group_n`` and ``group_mean`` are the
-    counted, unadjusted figures of every level.  Which level is the first changes the coefficients and not F."""
+    counted, unadjusted figures of every level.  Which level is the first changes the coefficients and not F.  ``vertex_covariates``: as in
+    ``f_test``; the maps count towards the six columns."""
+    if _is_map(groups):
+        raise ValueError("groups must hold one label per knee: a map (one entry per knee and vertex) is tested with regression_test(cohort, x=map)")
     N = len(cohort)
     n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
     levels, where = _anova_levels(groups, N, n_cov)
     dummies = np.stack([(where == g).astype(np.float64) for g in range(1, len(levels))], axis=1)
     names = [f"the dummy of level {int(lab)}" for lab in levels[1:]]
     return _f_run(cohort, "anova_test", dummies, names, covariates, True, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
-                  groups=(levels, where))
+                  groups=(levels, where), vertex_covariates=vertex_covariates)
 
 
 # ---- normative deviation ---------------------------------------------------------------------------------------------------------------
