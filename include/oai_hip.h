@@ -1277,6 +1277,76 @@ int oai_regression_vx_f(const void* prepared_dev, size_t prepared_bytes, const d
 
 
 /* ------------------------------------------------------------------------------------------
+ * Cluster-robust regression (csrc/cluster_robust.hip, tests/cluster_robust_ref.py): the model of "Cohort regression" for rows that are
+ * NOT exchangeable because they come in clusters -- the visits of a subject in a longitudinal cohort, both knees of a subject in a
+ * cross-sectional one.  The marginal model: ordinary least squares over all rows, a cluster-robust (sandwich) variance that sums the
+ * scores within a cluster (Liang and Zeger 1986), and inference from the restricted wild cluster bootstrap, which flips the sign of
+ * every cluster's null-model residuals as a block (Cameron, Gelbach and Miller 2008; Guillaume et al. 2014 for longitudinal images) --
+ * all AS RECALLED and NOT pinned to any implementation.  The reference has no such step: the definitions are this library's own, pinned
+ * by the numpy restatement and, through it, numpy's least squares and the explicit sandwich.  The rules of "Cohort regression" hold:
+ * fp64 without contraction, no floating-point atomics, one accumulator per sum that starts at +0.0, EVERY SUM OVER ROWS AND OVER
+ * CLUSTERS IN ASCENDING INDEX, the Cholesky order, the solves and the PIVOT RULE s > 1e-10 * A_aa: bit-reproducible.  Neither entry
+ * point synchronises or reads anything back.
+ *
+ * Rows are knee-visits in CLUSTER-MAJOR ORDER: cluster s owns rows offsets[s] .. offsets[s+1]-1 of offsets_dev int32 [n_clusters + 1];
+ * an offset outside [0, n_rows] is clamped.  design_dev float64 [n_rows][p], THE REGRESSOR OF INTEREST IS THE LAST COLUMN, 1 <= p <= 6,
+ * q = p - 1.  mask_dev uint8 [n_rows][n_verts] as in "Cohort statistics", or null.  2 <= n_clusters <= n_rows <= 2^20, 1 <= n_verts <=
+ * 2^31 - 2, at most 2^20 flip rows per call.
+ *
+ * oai_cluster_prepare.  prepared_dev ALREADY HOLDS, at its front, the block of oai_regression_prepare called on the same rows with
+ * n_knees = n_rows, the first q design columns as nuisance_dev and the same mask_dev: r, Q, n and ok are its.  THE CALLER IS RESPONSIBLE
+ * for that call; the block does not record it.  Per vertex, with m_j the validity of row j:
+ *   M_ac = Σ_j (m_j ? d_ja·d_jc : 0.0), j ascending.  M = L Lᵀ.
+ *   a = M⁻¹ e_p.  Forward-solve L z = e_p, then back-solve Lᵀ a = z.
+ *   w_j = m_j ? Σ_c d_jc·a_c : 0.0, c ascending.            (from +0.0, s = s + d_jc*a_c: a product, then an add)
+ *   per cluster s, rows ascending:
+ *     h_sc = Σ (m_j ? d_jc·r_j : 0.0)
+ *     k_sc = Σ (m_j ? w_j·d_jc : 0.0)
+ *     u_s = Σ (m_j ? w_j·r_j : 0.0)
+ *     present_s = any m_j
+ *   G = Σ_s present_s.
+ *   c = (G/(G−1)) · ((n−1)/(n−p)), each quotient taken in double, then one product.  This is Stata's CR1.
+ *   okc = ok && every pivot of M accepted && G ≥ 2 && n − p ≥ 1.
+ * A cluster with no valid row at the vertex holds +0.0 throughout and adds +0.0.  With n − p = 0 or G = 1, c is what IEEE division
+ * gives, and okc is 0.
+ * THE CLUSTER BLOCK, prepared_dev, front to back, each array starting on the next multiple of 256 bytes: the block of "Cohort
+ * regression" (R float64 [n_rows][n_verts], Q, mean float64 [n_verts], n int32 [n_verts], ok uint8 [n_verts]), then H float64
+ * [p][n_clusters][n_verts], K float64 [p][n_clusters][n_verts], U float64 [n_clusters][n_verts], L float64 [p (p + 1) / 2][n_verts]
+ * (entry (a, c), c <= a, in plane a (a + 1) / 2 + c), c float64 [n_verts], G int32 [n_verts], okc uint8 [n_verts] -- every plane
+ * [.][n_clusters][n_verts], so that a read over v is coalesced -- and last the scratch of the unmasked path: float64 [n_rows], [p]
+ * [n_clusters] and [p (p + 1) / 2 + 1 + p].  (2 p + 1) * n_clusters * n_verts * 8 bytes beside the regression block.
+ * With mask_dev == NULL the quantities M, L, a, w and k do not depend on the vertex: they are formed once, in the same order, and
+ * copied into the planes; the results are THE SAME BITS as with a mask of all ones.
+ *
+ * oai_cluster_t: rows [p0, p1) of bits_dev -> the t tile, float64 [p1 - p0][n_verts] at the start of workspace_dev, which
+ * oai_permutation_reduce, oai_graph_clusters and oai_graph_tfce take as it is.  bits_dev uint32 [P][ceil(n_clusters / 32)], packed as in
+ * "Cohort statistics" with CLUSTERS in the place of knees: f_s = −1 where bit s of the row is set and +1 otherwise.  Row 0 carries no
+ * flips by convention.  Per (resample row π, vertex):
+ *   1. b_c = Σ_s (bit ? −h_sc : h_sc), s ascending.  The negation is exact.  Then forward-solve L z = b and back-solve Lᵀ β = z.
+ *   2. For s ascending: e = bit ? −u_s : u_s.  For c ascending, e = e − k_sc·β_c.  Then W = W + e·e.
+ *   3. t = β_p / sqrt(c·W).  It is valid iff okc && W > 0, otherwise NaN.
+ * (each k_sc·β_c a product, then the subtraction; e·e a product, then the add; c·W one product.)  Row 0 is the classical cluster-robust
+ * t of the full model, by Frisch-Waugh: with p0 = 0 it also writes slope0 = β_p and se0 = sqrt(c·W) (float64 [n_verts], each may be
+ * null), NaN where its t is; a later batch (p0 > 0) leaves both alone.  This is algebraically the restricted wild cluster bootstrap
+ * y* = Z gamma~ + f o r~ refitted with the full model and its sandwich taken; the one-pass expansion of W into fixed quadratic terms
+ * cancels and is NOT part of the contract.
+ * A thread owns one vertex and R rows (R depends on p); the flip words are wave-uniform and come through scalar loads; "b + (bit ? -h :
+ * h)" is issued as fma(h, bit ? -1.0 : 1.0, b) and the first step of e as fma(u, bit ? -1.0 : 1.0, -(k_s0*beta_0)): the products are
+ * exact, so these are the bits of the stated operations for every finite value.  The result does not depend on R or on the batch.
+ * Refused, with a status and a message that names the entry point, before anything is launched: n_clusters < 2, n_columns outside
+ * [1, 6], more than 2^20 rows, n_rows < n_clusters, null pointers, bad flip-row ranges, a short workspace or cluster block.
+ * ---------------------------------------------------------------------------------------- */
+/* Both sizes: 0 for a shape the entry point refuses. */
+size_t oai_cluster_prepare_workspace_bytes(long long n_rows, long long n_verts, long long n_clusters, int n_columns);
+int oai_cluster_prepare(const unsigned char* mask_dev, const double* design_dev, const int* offsets_dev, long long n_rows, long long n_verts,
+                        long long n_clusters, int n_columns, void* prepared_dev, size_t prepared_bytes, void* stream);
+size_t oai_cluster_t_workspace_bytes(long long n_rows, long long n_verts);
+int oai_cluster_t(const void* prepared_dev, size_t prepared_bytes, const unsigned* bits_dev, long long n_rows, long long n_verts,
+                  long long n_clusters, int n_columns, long long p0, long long p1, void* workspace_dev, size_t workspace_bytes,
+                  double* slope0_dev, double* se0_dev, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free cluster enhancement (csrc/graph_tfce.hip, tests/graph_tfce_ref.py): a t tile in, a tile of the same shape out in which
  * every vertex holds the integral, over all thresholds h at or below its |t|, of extent(h)^E * h^H -- extent(h) being the size of the
  * vertex' connected component of {|t| >= h} on the surface.  It takes the place of a hand-picked cluster threshold: the family-wise p

@@ -44,7 +44,7 @@ def __getattr__(name):
                 "LongitudinalCohort", "visit_table", "one_sample_test", "VisitSlopes",
                 "BootstrapCounts", "BootstrapResult", "bootstrap_counts", "bootstrap_ci",
                 "Ranking", "RankSumResult", "SignedRankResult", "KruskalResult", "SpearmanResult", "rank_sum_test", "signed_rank_test",
-                "kruskal_test", "spearman_test", "ThicknessPCA", "PCAScores"):
+                "kruskal_test", "spearman_test", "ThicknessPCA", "PCAScores", "MarginalResult", "marginal_test"):
         from . import stats
         return getattr(stats, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -152,6 +152,10 @@ SIGNATURES = {
     "oai_regression_vx_t": (_I, [_P, _Z, _P, _P, C.c_longlong, C.c_longlong, _I, _I, _I, C.c_longlong, C.c_longlong, _P, _Z, _P, _P]),
     "oai_regression_vx_f_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong, C.c_longlong, _I, _I]),
     "oai_regression_vx_f": (_I, [_P, _Z, _P, _P, C.c_longlong, C.c_longlong, _I, _I, _I, _I, C.c_longlong, C.c_longlong, _P, _Z, _P, _P]),
+    "oai_cluster_prepare_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong, C.c_longlong, _I]),
+    "oai_cluster_prepare": (_I, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_longlong, _I, _P, _Z, _P]),
+    "oai_cluster_t_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "oai_cluster_t": (_I, [_P, _Z, _P, C.c_longlong, C.c_longlong, C.c_longlong, _I, C.c_longlong, C.c_longlong, _P, _Z, _P, _P, _P]),
     "oai_graph_tfce_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
     "oai_graph_tfce": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, C.c_longlong, _P, _D, _D, _I, _I, _I, _P, _Z, _P, _P, _P]),
     "oai_graph_smooth_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),

@@ -1003,6 +1003,98 @@ def regression_f(prepared: RegressionPrepared, design: torch.Tensor, perm: torch
     return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
 
 
+# ---- cluster-robust regression (include/oai_hip.h, "Cluster-robust regression"; csrc/cluster_robust.hip) -----------------------------------
+MAX_CLUSTER_ROWS = 1 << 20
+
+
+@dataclass
+class ClusterPrepared:
+    """The cluster block of ``cluster_prepare`` and views of its arrays (include/oai_hip.h states the layout): those of
+    ``RegressionPrepared`` (``R``, ``Q``, ``mean``, ``n``, ``ok``), then ``H``, ``K`` float64 [p,S,V], ``U`` float64 [S,V], ``L`` float64
+    [p (p + 1) / 2, V], ``c`` float64 [V], ``G`` int32 [V] and ``okc`` uint8 [V].  ``mask``: the uint8 [N,V] mask it was prepared with, or
+    None."""
+    block: torch.Tensor
+    n_rows: int
+    n_verts: int
+    n_clusters: int
+    n_columns: int
+    mask: Optional[torch.Tensor]
+    R: torch.Tensor
+    Q: torch.Tensor
+    mean: torch.Tensor
+    n: torch.Tensor
+    ok: torch.Tensor
+    H: torch.Tensor
+    K: torch.Tensor
+    U: torch.Tensor
+    L: torch.Tensor
+    c: torch.Tensor
+    G: torch.Tensor
+    okc: torch.Tensor
+
+
+def cluster_prepare(values: torch.Tensor, mask: Optional[torch.Tensor], design: torch.Tensor, offsets: torch.Tensor,
+                    centre: bool = True) -> ClusterPrepared:
+    """What every resample of a cluster-robust regression re-uses, once per test: float32 ``values`` [N,V] with the rows in CLUSTER-MAJOR
+    order, an optional uint8 / bool ``mask`` [N,V], the float64 ``design`` [N,p] with the regressor of interest LAST (1 <= p <= 6) and the
+    int32 ``offsets`` [S+1]: cluster s owns rows ``offsets[s] .. offsets[s+1] - 1``.  Runs ``oai_regression_prepare`` with the first
+    p - 1 columns as the nuisance (``centre``: as in ``regression_prepare``) into the front of one block and ``oai_cluster_prepare`` behind
+    it: per vertex the factor of the design's normal equations over the valid rows, per (cluster, vertex) the score sums, G, the CR1
+    factor and ``okc``.  fp64 in a stated order: bit-reproducible.  Does not synchronise."""
+    values = _chk(values, "values")
+    if values.dim() != 2 or not 2 <= values.shape[0] <= MAX_CLUSTER_ROWS or values.shape[1] < 1:
+        raise ValueError(f"values must be [2 <= N <= 2^20, V >= 1], got {tuple(values.shape)}")
+    mask = _stats_mask(mask, values)
+    N, V, dev = int(values.shape[0]), int(values.shape[1]), values.device
+    design = _design(design, "design", N, dev, 1, MAX_DESIGN_COLUMNS)
+    p = int(design.shape[1])
+    offsets = _chk(offsets, "offsets", torch.int32).reshape(-1)
+    S = int(offsets.numel()) - 1
+    if not 2 <= S <= N or offsets.device != dev:
+        raise ValueError(f"offsets must hold S + 1 entries for 2 <= S <= {N} clusters on {dev}, got {offsets.numel()} on {offsets.device}")
+    nuisance = design[:, :p - 1].contiguous() if p > 1 else None
+    block = _lib.workspace("oai_cluster_prepare", dev, N, V, S, p)
+    _lib.call("oai_regression_prepare", values.data_ptr(), _ptr(mask), _ptr(nuisance), N, V, p - 1, int(bool(centre)), block.data_ptr(), block.numel(),
+              _lib.STREAM, device=dev)
+    _lib.call("oai_cluster_prepare", _ptr(mask), design.data_ptr(), offsets.data_ptr(), N, V, S, p, block.data_ptr(), block.numel(), _lib.STREAM,
+              device=dev)
+    f64, T = torch.float64, p * (p + 1) // 2
+    parts = _block_views(block, (("R", f64, (N, V)), ("Q", f64, (V,)), ("mean", f64, (V,)), ("n", torch.int32, (V,)), ("ok", torch.uint8, (V,)),
+                                 ("H", f64, (p, S, V)), ("K", f64, (p, S, V)), ("U", f64, (S, V)), ("L", f64, (T, V)), ("c", f64, (V,)),
+                                 ("G", torch.int32, (V,)), ("okc", torch.uint8, (V,))))
+    return ClusterPrepared(block, N, V, S, p, mask, **parts)
+
+
+def cluster_t(prepared: ClusterPrepared, bits: torch.Tensor, p0: int, p1: int, workspace: Optional[torch.Tensor] = None,
+              slope0: Optional[torch.Tensor] = None, se0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The t tile of rows [p0, p1) of ``bits`` (packed flip rows over the CLUSTERS, [P, ceil(S / 32)] as int32 or uint32 on the device: a set
+    bit flips the sign of the cluster's null-model residuals; row 0 flips nothing): float64 [p1 - p0, V], the cluster-robust t of the
+    LAST design column under the restricted wild cluster bootstrap, NaN where no t exists.  ``slope0``, ``se0`` float64 [V]: with ``p0`` =
+    0, receive row 0's coefficient of that column and its sandwich standard error.  ``workspace``: a uint8 device buffer of
+    ``oai_cluster_t_workspace_bytes`` (reused between batches) instead of a new one; the tile is its front.  Does not synchronise."""
+    dev, N, V, S, p = prepared.block.device, prepared.n_rows, prepared.n_verts, prepared.n_clusters, prepared.n_columns
+    if bits.dtype == getattr(torch, "uint32", None):
+        bits = bits.view(torch.int32)
+    bits = _chk(bits, "bits", torch.int32)
+    if bits.dim() != 2 or bits.shape[1] != (S + 31) // 32 or bits.device != dev:
+        raise ValueError(f"bits must be [P, {(S + 31) // 32}] packed flip rows of the {S} clusters on {dev}, got {tuple(bits.shape)} on {bits.device}")
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 < p1 <= bits.shape[0]:
+        raise ValueError(f"rows [{p0}, {p1}) are not rows of the {bits.shape[0]} flip rows")
+    outs = []
+    for name, out0 in (("slope0", slope0), ("se0", se0)):
+        if out0 is not None:
+            out0 = _chk(out0, name, torch.float64)
+            if tuple(out0.shape) != (V,) or out0.device != dev:
+                raise ValueError(f"{name} must be float64 [{V}] on {dev}, got {tuple(out0.shape)} on {out0.device}")
+        outs.append(out0)
+    need = int(_lib.load().oai_cluster_t_workspace_bytes(p1 - p0, V))
+    ws = _tile_workspace(workspace, need, dev)
+    _lib.call("oai_cluster_t", prepared.block.data_ptr(), prepared.block.numel(), bits.data_ptr(), N, V, S, p, p0, p1, ws.data_ptr(), ws.numel(),
+              _ptr(outs[0]), _ptr(outs[1]), _lib.STREAM, device=dev)
+    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+
+
 # ---- vertex-wise design columns (include/oai_hip.h, "Vertex-wise design columns"; csrc/group_regression_vx.hip) ------------------------------
 MAX_VERTEX_COLUMNS = 2
 

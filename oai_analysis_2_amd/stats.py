@@ -85,6 +85,14 @@ baseline thickness at the same vertex above all, without which a rate of change 
 may itself be a map (include/oai_hip.h, "Vertex-wise design columns"; csrc/group_regression_vx.hip; tests/vertex_regression_ref.py).
 
     regression_test(visits.change("rate"), x=kl_grade, covariates=np.stack([age, sex], axis=1), vertex_covariates=visits.first_visit()).p_fwer
+
+Every test above takes the rows of a cohort as exchangeable.  ``marginal_test`` is the one-stage model for rows that come in CLUSTERS --
+the visits of a subject, both knees of a subject: ordinary least squares over all rows, the cluster-robust (sandwich) t, and the wild
+cluster bootstrap for its null distribution, so a covariate may vary within a subject (include/oai_hip.h, "Cluster-robust regression";
+csrc/cluster_robust.hip; tests/cluster_robust_ref.py).
+
+    g = visits.per_row(group)
+    marginal_test(visits, x=visits.years * g, covariates=np.stack([visits.years, g], axis=1), tfce=True).p_tfce
 """
 from __future__ import annotations
 
@@ -766,6 +774,26 @@ class LongitudinalCohort:
         """In order of first appearance: the ids of what ``change`` returns."""
         return list(dict.fromkeys(self._subject))
 
+    @property
+    def years(self) -> np.ndarray:
+        """float64 [rows]: the time of every row in years, in the order the rows were added -- a per-row column for ``marginal_test``."""
+        return np.asarray(self._years, np.float64)
+
+    def per_row(self, values) -> np.ndarray:
+        """A per-SUBJECT quantity (group, sex, baseline age) broadcast to the rows, in the order the rows were added: ``values`` is an
+        array with one entry (or one row of entries) per subject in the order of ``subjects``, or a mapping from subject to value."""
+        if hasattr(values, "keys"):
+            missing = [s for s in self.subjects if s not in values]
+            if missing:
+                raise ValueError(f"per_row has no value for subject {missing[0]!r}")
+            return np.asarray([values[s] for s in self._subject])
+        names = self.subjects
+        values = np.asarray(values)
+        if values.ndim < 1 or values.shape[0] != len(names):
+            raise ValueError(f"per_row needs one entry per subject ({len(names)}, in the order of subjects) or a mapping, got shape {values.shape}")
+        where = {s: k for k, s in enumerate(names)}
+        return values[np.asarray([where[s] for s in self._subject], np.int64)]
+
     def visits_of(self, subject) -> List[Tuple[float, object]]:
         """The (years, label) of the subject's visits in ascending time."""
         return sorted(((y, lab) for s, y, lab in zip(self._subject, self._years, self._label) if s == subject), key=lambda p: p[0])
@@ -1428,6 +1456,99 @@ def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool
     with np.errstate(invalid="ignore", divide="ignore"):
         partial_r = t / np.sqrt(t * t + dof.astype(np.float64))
     return RegressionResult(kind=cohort.kind, n=n, dof=dof, slope=host["slope"] / scale, partial_r=partial_r, exact=perms.exact, **shared)
+
+
+# ---- one-stage models of clustered rows (include/oai_hip.h, "Cluster-robust regression"; csrc/cluster_robust.hip) ----------------------------
+@dataclass
+class MarginalResult(_SurfaceResult):
+    """``t`` float64 [V]: the cluster-robust (sandwich, CR1) t of the regressor's coefficient in the ordinary least squares fit over all
+    rows (NaN where no t exists: fewer than two clusters with a value, too few rows, a design that loses its rank among them, no
+    residual variation); ``slope`` per unit of ``x`` and ``se`` its sandwich standard error; ``n`` the valid rows and ``n_clusters`` the
+    clusters with a valid row (G) per vertex; ``dof`` = G - 1, the degrees of freedom a t table would be read at (the p-values here come
+    from the bootstrap, not from a table); ``p_uncorrected``, ``p_fwer``, ``max_abs`` and the cluster and TFCE fields as in
+    ``PermutationResult``, over the ``n_bootstrap`` sign vectors of the wild cluster bootstrap (``exact``: all 2^S of them)."""
+    kind: str
+    t: np.ndarray
+    slope: np.ndarray
+    se: np.ndarray
+    n: np.ndarray
+    n_clusters: np.ndarray
+    dof: np.ndarray
+    p_uncorrected: np.ndarray
+    p_fwer: np.ndarray
+    max_abs: np.ndarray
+    n_bootstrap: int
+    exact: bool
+
+    IMAGES = ("t", "slope", "se", "p_fwer", "p_uncorrected", "n", "n_clusters", "cluster_label", "tfce", "p_tfce")
+
+
+def cluster_rows(labels) -> Tuple[List[object], np.ndarray, np.ndarray]:
+    """Rows grouped by cluster: (the clusters in order of first appearance, ``order`` int64 [N] -- the rows in CLUSTER-MAJOR order, input
+    order within a cluster -- and ``offsets`` int32 [S+1]: cluster s owns ``order[offsets[s] : offsets[s+1]]``)."""
+    index: dict = {}
+    owner = np.asarray([index.setdefault(lab, len(index)) for lab in labels], np.int64)
+    order = np.argsort(owner, kind="stable")
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(owner, minlength=len(index)))]).astype(np.int32)
+    return list(index), order, offsets
+
+
+def marginal_test(cohort_or_visits, x, covariates=None, clusters=None, intercept: bool = True, n_bootstrap: int = 10000,
+                  cluster_threshold: Optional[float] = None, tfce=None, seed: int = 0, flips=None, batch: Optional[int] = None) -> MarginalResult:
+    """How does thickness vary with ``x`` over rows that come in CLUSTERS -- the visits of a subject (a ``LongitudinalCohort``: the
+    clusters default to its subjects) or both knees of a subject (a ``ThicknessCohort`` with ``clusters``, one hashable per row: the
+    subject of each knee)?  The one-stage marginal model (include/oai_hip.h, "Cluster-robust regression"): ordinary least squares over
+    all rows with a value at the vertex, the cluster-robust sandwich variance (CR1) and its t, and a null distribution from the restricted
+    wild cluster bootstrap -- ``sign_flips(S, n_bootstrap, seed)`` over the S clusters (all 2^S when there are at most ``n_bootstrap``),
+    or ``flips``, which takes what ``permutations`` takes in ``paired_test`` with one bit per cluster in order of first appearance.
+    ``x`` and ``covariates`` ([N] or [N, k]) are per ROW, in the order the rows were added, so a covariate may vary within a subject
+    (years, BMI or pain at the visit; ``visits.years``, ``visits.per_row``); a constant or collinear column is refused by name.  At most
+    six design columns.  ``cluster_threshold``, ``tfce``, ``batch``: as in ``two_sample_test``.
+
+    Limits: one regressor of interest (no joint Wald F); CR1 only (no CR2 / CR3 or SwE small-sample corrections); Rademacher weights
+    only, so with S <= 11 clusters the null has at most 2^S points; the wild bootstrap is LIBERAL with few clusters (about 8 % rejections
+    at a nominal 5 % with 24 clusters in a simulation on the restatement) and no significance level is built in; no subject fixed effects
+    or within-subject centring; no per-vertex design columns; no rank wrapper; missingness stays attached to the row; the cluster block
+    takes (2 p + 1) * S * V * 8 bytes on the device."""
+    tfce = _tfce_settings(tfce)
+    if isinstance(cohort_or_visits, LongitudinalCohort):
+        cohort = cohort_or_visits.rows
+        labels = list(cohort_or_visits._subject) if clusters is None else list(clusters)
+    else:
+        cohort = cohort_or_visits
+        if clusters is None:
+            raise ValueError("marginal_test on a ThicknessCohort needs clusters=: one hashable per row (the subject of each knee)")
+        labels = list(clusters)
+    N = len(cohort)
+    if len(labels) != N:
+        raise ValueError(f"clusters must hold one label per row of the cohort ({N}), got {len(labels)}")
+    names, order, offsets = cluster_rows(labels)
+    S = len(names)
+    if S < 2:
+        raise ValueError(f"marginal_test needs at least two clusters, got {S}")
+    _, design, scale = _design_columns(x, covariates, bool(intercept), N)
+    if flips is not None and not isinstance(flips, Permutations) and np.asarray(flips).dtype == bool and np.atleast_2d(flips).shape[1] != S:
+        raise ValueError(f"the flips must hold one bit per cluster ({S}), got bool rows of {np.atleast_2d(flips).shape[1]}")
+    perms = _permutations(flips, lambda: sign_flips(S, n_bootstrap, seed), S)
+    if perms.n_knees != S or perms.bits.ndim != 2 or perms.bits.shape[1] != (S + 31) // 32:
+        raise ValueError(f"the flips must hold one bit per cluster ({S}), got rows for {perms.n_knees} in {perms.bits.shape}")
+    if perms.rows()[0].any():
+        raise ValueError("row 0 of the flips must flip nothing")
+    P, V, dev = len(perms), cohort.n_verts, cohort.device
+    pick = torch.from_numpy(order).to(dev)
+    values, mask = cohort.values.index_select(0, pick), cohort.mask.index_select(0, pick)
+    batches = _Batches(cohort, P, V, dev, cluster_threshold, tfce, batch)
+    bits = torch.from_numpy(np.ascontiguousarray(perms.bits).view(np.int32)).to(dev)
+    prepared = ops.cluster_prepare(values, mask, torch.from_numpy(np.ascontiguousarray(design[order])).to(dev), torch.from_numpy(offsets).to(dev),
+                                   centre=bool(intercept))
+    slope0, se0 = (torch.empty(V, dtype=torch.float64, device=dev) for _ in range(2))
+    ws = _lib.workspace("oai_cluster_t", dev, batches.rows, V)
+    first = lambda p0: dict(slope0=slope0, se0=se0) if p0 == 0 else {}
+    host, shared = batches.run(lambda p0, p1: ops.cluster_t(prepared, bits, p0, p1, workspace=ws, **first(p0)),
+                               {"slope": slope0, "se": se0, "n": prepared.n, "n_clusters": prepared.G})
+    shared["n_bootstrap"] = shared.pop("n_permutations")
+    return MarginalResult(kind=cohort.kind, slope=host["slope"] / scale, se=host["se"] / scale, n=host["n"], n_clusters=host["n_clusters"],
+                          dof=host["n_clusters"].astype(np.int64) - 1, exact=perms.exact, **shared)
 
 
 # ---- F tests ---------------------------------------------------------------------------------------------------------------------------
