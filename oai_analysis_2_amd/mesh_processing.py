@@ -753,14 +753,17 @@ def map_attributes(source_mesh: Mesh, target_mesh: Mesh, radius: float = 1.0, br
     n_tgt, n_src, n_comp = len(target_mesh.verts), len(source_mesh.verts), vals.shape[0]
     if n_comp == 0:
         return Mesh(target_mesh.verts, target_mesh.faces, out_data)
-    s, v, t = _dev(source_mesh.verts, np.float32), _dev(vals, np.float32), _dev(target_mesh.verts, np.float32, (3,))
-    if broad_phase:
-        out = _map_attributes_dev(s, v, t, radius, grid=(source_mesh.verts.min(axis=0).astype(np.float64), source_mesh.verts.max(axis=0).astype(np.float64)))
+    if n_tgt == 0:                                    # nothing to interpolate: the arrays keep their trailing shapes (an empty tensor has no pointer to pass)
+        res = np.zeros((n_comp, 0), np.float32)
     else:
-        out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=s.device)
-        _lib.call("oai_map_attributes", s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr(), _lib.STREAM,
-                  device=s.device)
-    res = out.cpu().numpy()
+        s, v, t = _dev(source_mesh.verts, np.float32), _dev(vals, np.float32), _dev(target_mesh.verts, np.float32, (3,))
+        if broad_phase:
+            out = _map_attributes_dev(s, v, t, radius, grid=(source_mesh.verts.min(axis=0).astype(np.float64), source_mesh.verts.max(axis=0).astype(np.float64)))
+        else:
+            out = torch.empty((n_comp, n_tgt), dtype=torch.float32, device=s.device)
+            _lib.call("oai_map_attributes", s.data_ptr(), n_src, v.data_ptr(), n_comp, t.data_ptr(), n_tgt, float(radius), out.data_ptr(), _lib.STREAM,
+                      device=s.device)
+        res = out.cpu().numpy()
     row = 0
     for name, shape in names:
         k = int(np.prod(shape[1:], dtype=np.int64))

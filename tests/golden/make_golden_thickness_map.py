@@ -6,6 +6,10 @@ duck-typed mesh (GetPointData().GetScalars(), GetPoints().GetData()).  KernelPCA
 start vector drawn from numpy's global RNG, so the RNG is seeded before every call.
 
     OAI_REFERENCE=/path/to/OAI_analysis_2 python tests/golden/make_golden_thickness_map.py
+
+With --edges it writes tests/golden/thickness_projection_edges.npz instead: the same calls on the smallest inputs the projection takes
+(an FC sheet of 3 points and one of 40, a TC set of 3 + 3 points and one of 150 + 60, which stays on KernelPCA's dense path) and leaves
+thickness_projection.npz alone.
 """
 import importlib.util
 import os
@@ -16,6 +20,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "thickness_projection.npz")
+OUT_EDGES = os.path.join(HERE, "thickness_projection_edges.npz")
 
 
 class _Stub(types.ModuleType):
@@ -94,11 +99,50 @@ def make_inputs(seed=20241008):
     return fc, fc_t, tc, tc_t
 
 
+def make_edge_inputs(seed=20250917):
+    """{name: (verts, thickness)}: fc3, fc40 (arcs as in make_inputs) and tc3_3, tc150_60 (plateaus of those sizes, interleaved)"""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for n in (3, 40):
+        phi = rng.uniform(np.pi - 1.1, np.pi + 1.1, n)
+        rad = 31.0 + rng.normal(0.0, 0.4, n)
+        fc = np.stack([48.25 + rad * np.sin(phi), 61.5 + rad * np.cos(phi), rng.uniform(10.0, 90.0, n)], axis=1)
+        out[f"fc{n}"] = (f32(fc), f32(rng.uniform(0.5, 3.5, n)))
+    for n_left, n_right in ((3, 3), (150, 60)):
+        halves = []
+        for n, centre in ((n_left, [40.0, 55.0, 30.0]), (n_right, [42.0, 60.0, 72.0])):
+            axes = np.linalg.qr(rng.normal(size=(3, 3)))[0]
+            halves.append(np.array(centre) + (rng.normal(size=(n, 3)) * np.array([9.0, 5.0, 0.8])) @ axes.T)
+        halves[0][:, 2] = np.minimum(halves[0][:, 2], 49.5)
+        halves[1][:, 2] = np.maximum(halves[1][:, 2], 50.0)
+        tc = np.concatenate(halves)
+        out[f"tc{n_left}_{n_right}"] = (f32(tc[rng.permutation(len(tc))]), f32(rng.uniform(0.5, 3.0, len(tc))))
+    return out
+
+
+def main_edges(mp):
+    arrays = {}
+    for name, (verts, th) in make_edge_inputs().items():
+        np.random.seed(0)
+        x, y, t = mp.project_thickness(DuckMesh(verts, th), mesh_type="FC" if name.startswith("fc") else "TC")
+        arrays.update({f"{name}_verts": verts, f"{name}_thickness": th, f"{name}_x": np.asarray(x, np.float64),
+                       f"{name}_y": np.asarray(y, np.float64), f"{name}_t": np.asarray(t, np.float64)})
+        if name.startswith("fc"):
+            sw = verts[:, [1, 0, 2]]
+            np.random.seed(0)
+            centre, r = mp.compute_least_square_circle(sw[:, 0], sw[:, 1])
+            arrays.update({f"{name}_circle_centre": np.asarray(centre, np.float64), f"{name}_circle_radius": np.float64(r)})
+    np.savez(OUT_EDGES, **arrays)
+    print(f"wrote {OUT_EDGES}: {sorted(arrays)}")
+
+
 def main():
     ref = os.environ.get("OAI_REFERENCE")
     if not ref or not os.path.isdir(os.path.join(ref, "oai_analysis")):
         sys.exit("set OAI_REFERENCE to a checkout of uncbiag/OAI_analysis_2")
     mp = load_reference_mesh_processing(ref)
+    if "--edges" in sys.argv[1:]:
+        return main_edges(mp)
     fc, fc_t, tc, tc_t = make_inputs()
     np.random.seed(0)
     fc_x, fc_y, fc_th = mp.project_thickness(DuckMesh(fc, fc_t), mesh_type="FC")
