@@ -58,7 +58,7 @@ namespace {
 using namespace oai;
 
 constexpr int kT = 256;                            // vertices of a block
-// kMaxCols (p), kPivot, tri(), cholesky<P> and forward_solve<P>: csrc/regression_solve.h, shared with csrc/normative.hip
+// kMaxCols (p), kPivot, tri(), cholesky<P>, forward_solve<P> and backward_solve<P>: csrc/regression_solve.h, which names its users
 // Prepared (the prepared block): csrc/regression_rows.h; the epilogue of a row: csrc/regression_epilogue_body.h -- both shared with
 // csrc/group_regression_vx.hip.  The 24 instances of the hot kernels were compared before and after the two moved there: the same VGPR,
 // SGPR and scratch figures, instance by instance (code-object metadata and the compiler's kernel-resource remarks for gfx950).
@@ -101,13 +101,7 @@ __global__ void __launch_bounds__(kT) prepare_kernel(const float* __restrict__ Y
         }
         pass = cholesky<QA>(A);
         forward_solve<QA>(A, h);
-#pragma unroll
-        for (int a = QA - 1; a >= 0; --a) {                                   // L^T gamma = w, from the last row up, k ascending
-            double s = h[a];
-#pragma unroll
-            for (int k = a + 1; k < QA; ++k) s = s - A[tri(k) + a] * h[k];
-            h[a] = s / A[tri(a) + a];
-        }
+        backward_solve<QA>(A, h);                                             // L^T gamma = w
     }
     double q = 0.0;
     for (long long i = 0; i < N; ++i) {

@@ -1,7 +1,9 @@
-// The small dense solves that the per-vertex linear models share (csrc/group_regression.hip, csrc/normative.hip): the Cholesky factor of
-// a packed lower triangle and the forward solve with it, in the order and with the pivot rule that include/oai_hip.h states under "Cohort
-// regression" (tests/group_regression_ref.py restates both operation for operation).  Device code only; fp64 without contraction -- the
-// pragma below holds for the rest of the translation unit, and both users state it themselves as well.
+// The small dense solves that the per-vertex linear models share: the Cholesky factor of a packed lower triangle and the forward and
+// backward solves with it, in the order and with the pivot rule that include/oai_hip.h states under "Cohort regression"
+// (tests/group_regression_ref.py restates them operation for operation).  Five translation units use them: csrc/group_regression.hip,
+// csrc/normative.hip and csrc/bootstrap.hip include this file, csrc/group_regression_vx.hip and csrc/cluster_robust.hip reach it
+// through csrc/regression_rows.h; bootstrap.hip alone has no use for the backward solve.  Device code only; fp64 without contraction --
+// the pragma below holds for the rest of the translation unit, and every user states it itself as well.
 #pragma once
 #include <hip/hip_runtime.h>
 

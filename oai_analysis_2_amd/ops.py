@@ -965,20 +965,28 @@ def _regression_batch(prepared: RegressionPrepared, design, perm, p0, p1, lo: in
     return design, perm, p0, p1, out0
 
 
+def _regression_tile(name: str, prepared, head, size, p0: int, p1: int, workspace, out0) -> torch.Tensor:
+    """The call tail of the four batch entry points once their arguments are checked: the workspace of rows [p0, p1) (``size``: what
+    ``name``_workspace_bytes takes after the row count), the call -- ``head``: the entry point's arguments between the prepared block
+    and p0 -- and the tile, the front of the workspace."""
+    dev, V = prepared.block.device, prepared.n_verts
+    need = int(getattr(_lib.load(), name + "_workspace_bytes")(p1 - p0, *size))
+    ws = _tile_workspace(workspace, need, dev)
+    _lib.call(name, prepared.block.data_ptr(), prepared.block.numel(), *head, p0, p1, ws.data_ptr(), ws.numel(), _ptr(out0), _lib.STREAM, device=dev)
+    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+
+
 def regression_t(prepared: RegressionPrepared, design: torch.Tensor, perm: torch.Tensor, p0: int, p1: int, workspace: Optional[torch.Tensor] = None,
                  slope0: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The t tile of rows [p0, p1) of ``perm`` (int32 [P,N] on the device: knee j of a row takes design row ``perm[row, j]``; row 0 the
     identity): float64 [p1 - p0, V], the t of the LAST column of the float64 ``design`` [N,p] (p = the prepared q + 1), NaN where no t
     exists.  ``slope0`` float64 [V]: with ``p0`` = 0, receives row 0's coefficient of that column.  ``workspace``: a uint8 device buffer of
     ``oai_regression_t_workspace_bytes`` (reused between batches) instead of a new one; the tile is its front.  Does not synchronise."""
-    dev, N, V = prepared.block.device, prepared.n_knees, prepared.n_verts
+    N, V = prepared.n_knees, prepared.n_verts
     p = prepared.n_nuisance + 1
     design, perm, p0, p1, slope0 = _regression_batch(prepared, design, perm, p0, p1, p, p, slope0, "slope0", (V,))
-    need = int(_lib.load().oai_regression_t_workspace_bytes(p1 - p0, V, N, p))
-    ws = _tile_workspace(workspace, need, dev)
-    _lib.call("oai_regression_t", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p,
-              p0, p1, ws.data_ptr(), ws.numel(), _ptr(slope0), _lib.STREAM, device=dev)
-    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+    return _regression_tile("oai_regression_t", prepared, (_ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p), (V, N, p), p0, p1,
+                            workspace, slope0)
 
 
 def regression_f(prepared: RegressionPrepared, design: torch.Tensor, perm: torch.Tensor, p0: int, p1: int, n_interest: int,
@@ -989,18 +997,15 @@ def regression_f(prepared: RegressionPrepared, design: torch.Tensor, perm: torch
     ``n_interest``.  ``coef0`` float64 [n_interest, V]: with ``p0`` = 0, receives row 0's coefficients of those columns.  ``workspace``: a
     uint8 device buffer of ``oai_regression_f_workspace_bytes`` (reused between batches) instead of a new one; the tile is its front.
     Does not synchronise."""
-    dev, N, V = prepared.block.device, prepared.n_knees, prepared.n_verts
+    N, V = prepared.n_knees, prepared.n_verts
     k = int(n_interest)
     if not 1 <= k <= MAX_DESIGN_COLUMNS - prepared.n_nuisance:
         raise ValueError(f"n_interest must be 1 .. {MAX_DESIGN_COLUMNS - prepared.n_nuisance} beside the {prepared.n_nuisance} nuisance columns "
                          f"of the prepared block, got {n_interest!r}")
     p = prepared.n_nuisance + k
     design, perm, p0, p1, coef0 = _regression_batch(prepared, design, perm, p0, p1, p, p, coef0, "coef0", (k, V))
-    need = int(_lib.load().oai_regression_f_workspace_bytes(p1 - p0, V, N, p))
-    ws = _tile_workspace(workspace, need, dev)
-    _lib.call("oai_regression_f", prepared.block.data_ptr(), prepared.block.numel(), _ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p,
-              k, p0, p1, ws.data_ptr(), ws.numel(), _ptr(coef0), _lib.STREAM, device=dev)
-    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+    return _regression_tile("oai_regression_f", prepared, (_ptr(prepared.mask), design.data_ptr(), perm.data_ptr(), N, V, p, k), (V, N, p), p0, p1,
+                            workspace, coef0)
 
 
 # ---- cluster-robust regression (include/oai_hip.h, "Cluster-robust regression"; csrc/cluster_robust.hip) -----------------------------------
@@ -1173,11 +1178,8 @@ def _regression_vx_batch(name: str, prepared: RegressionVxPrepared, design, perm
     else:
         lo = n_global
     design, perm, p0, p1, out0 = _regression_batch(prepared, design, perm, p0, p1, lo, lo, out0, out0_name, out0_shape)
-    need = int(getattr(_lib.load(), name + "_workspace_bytes")(p1 - p0, V, N, p, sn + si))
-    ws = _tile_workspace(workspace, need, dev)
-    _lib.call(name, prepared.block.data_ptr(), prepared.block.numel(), design.data_ptr() if n_global else None, perm.data_ptr(), N, V, p, sn, si, *extra,
-              p0, p1, ws.data_ptr(), ws.numel(), _ptr(out0), _lib.STREAM, device=dev)
-    return ws[:(p1 - p0) * V * 8].view(torch.float64).reshape(p1 - p0, V)
+    return _regression_tile(name, prepared, (design.data_ptr() if n_global else None, perm.data_ptr(), N, V, p, sn, si, *extra), (V, N, p, sn + si),
+                            p0, p1, workspace, out0)
 
 
 def regression_vx_t(prepared: RegressionVxPrepared, design: Optional[torch.Tensor], perm: torch.Tensor, p0: int, p1: int,

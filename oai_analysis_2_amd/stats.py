@@ -1263,22 +1263,36 @@ def regression_batch(n_verts: int, n_knees: int, n_columns: int, n_permutations:
     return _batch_rows(n_verts, n_permutations, clusters, tfce, budget, _table_bytes(n_knees, n_columns))
 
 
-def _design_columns(x, covariates, intercept: bool, n_knees: int) -> Tuple[np.ndarray, np.ndarray, float]:
-    """(nuisance [N, q], design [N, q + 1] with x last, the scale x was divided by); refuses what has no answer."""
-    x = np.asarray(x, np.float64)
-    if x.shape != (n_knees,):
-        raise ValueError(f"x must hold one entry per knee of the cohort ({n_knees}), got shape {x.shape}")
+def _n_columns(columns) -> int:
+    """How many columns a host side of a design passes: None has none, [N] is one, [N, k] are k."""
+    return 0 if columns is None else (1 if np.ndim(columns) == 1 else int(np.shape(columns)[-1]))
+
+
+def _design_matrix(X, covariates, intercept: bool, n_knees: int, names: Optional[Sequence[str]] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The one place that centres, scales and rank-checks the host columns of a design: (nuisance [N, q], design [N, q + k] with the k
+    columns of ``X`` last, the k scales those columns were divided by); refuses what has no answer and names the column at fault
+    (``names``: what the columns of ``X`` are called; default "X column j").  ``X`` None: no tested column among them (k = 0: the
+    regressor of interest is a map) and the design is the nuisance."""
+    tested = X is not None
+    X = np.asarray(X, np.float64) if tested else np.zeros((n_knees, 0))
+    X = X[:, None] if X.ndim == 1 else X
+    if X.ndim != 2 or X.shape[0] != n_knees or X.shape[1] < int(tested):
+        raise ValueError(f"X must be [{n_knees}] or [{n_knees}, k >= 1], got shape {X.shape}")
     cov = np.zeros((n_knees, 0)) if covariates is None else np.asarray(covariates, np.float64)
     cov = cov[:, None] if cov.ndim == 1 else cov
     if cov.ndim != 2 or cov.shape[0] != n_knees:
-        raise ValueError(f"covariates must be [{n_knees}] or [{n_knees}, k], got shape {cov.shape}")
-    p = cov.shape[1] + 1 + int(bool(intercept))
+        raise ValueError(f"covariates must be [{n_knees}] or [{n_knees}, c], got shape {cov.shape}")
+    k = X.shape[1]
+    names = [f"X column {j}" for j in range(k)] if names is None else list(names)
+    p = cov.shape[1] + k + int(bool(intercept))
     if p > ops.MAX_DESIGN_COLUMNS:
-        raise ValueError(f"the design has {p} columns (intercept, covariates, x); at most {ops.MAX_DESIGN_COLUMNS} are supported")
-    if not (np.isfinite(x).all() and np.isfinite(cov).all()):
-        raise ValueError("the design holds a NaN or an infinity: x and the covariates must be finite for every knee")
+        raise ValueError(f"the design has {p} columns ({'the intercept, ' if intercept else ''}{cov.shape[1]} covariates, {k} tested columns); at most "
+                         f"{ops.MAX_DESIGN_COLUMNS} are supported")
+    named = [(f"covariate {j}", cov[:, j]) for j in range(cov.shape[1])] + list(zip(names, X.T))
     cols = []
-    for name, c in [(f"covariate {k}", cov[:, k]) for k in range(cov.shape[1])] + [("x", x)]:
+    for name, c in named:
+        if not np.isfinite(c).all():
+            raise ValueError(f"{name} holds a NaN or an infinity: the design must be finite for every knee")
         if (c == c[0]).all():
             raise ValueError(f"{name} is constant over the knees")
         c = c - c.mean() if intercept else c.copy()
@@ -1286,14 +1300,24 @@ def _design_columns(x, covariates, intercept: bool, n_knees: int) -> Tuple[np.nd
         if not norm > 0.0:
             raise ValueError(f"{name} is constant over the knees")
         cols.append((c, norm))
-    scale = cols[-1][1]
-    Z = ([np.ones(n_knees)] if intercept else []) + [c / s for c, s in cols[:-1]]
+    Z = ([np.ones(n_knees)] if intercept else []) + [c / s for c, s in cols[:cov.shape[1]]]
     nuisance = np.stack(Z, axis=1) if Z else np.zeros((n_knees, 0))
-    design = np.ascontiguousarray(np.concatenate([nuisance, (cols[-1][0] / scale)[:, None]], axis=1))
+    design = np.ascontiguousarray(np.concatenate([nuisance] + [(c / s)[:, None] for c, s in cols[cov.shape[1]:]], axis=1))
     unit = design / np.sqrt((design * design).sum(axis=0))[None, :]
-    if n_knees < p or np.linalg.matrix_rank(unit) < p:
-        raise ValueError("the design (intercept, covariates, x) does not have full column rank over the knees")
-    return np.ascontiguousarray(nuisance), design, scale
+    every = (["the intercept"] if intercept else []) + [name for name, _ in named]
+    for j in range(p):                                                     # the first column that the ones before it already span
+        if n_knees < j + 1 or np.linalg.matrix_rank(unit[:, :j + 1]) < j + 1:
+            raise ValueError(f"the design does not have full column rank over the knees: {every[j]} is a combination of the columns before it")
+    return np.ascontiguousarray(nuisance), design, np.asarray([s for _, s in cols[cov.shape[1]:]], np.float64)
+
+
+def _design_columns(x, covariates, intercept: bool, n_knees: int) -> Tuple[np.ndarray, np.ndarray, float]:
+    """``_design_matrix`` of ONE regressor, one entry per knee: (nuisance [N, q], design [N, q + 1] with x last, the scale x was divided by)."""
+    x = np.asarray(x, np.float64)
+    if x.shape != (n_knees,):
+        raise ValueError(f"x must hold one entry per knee of the cohort ({n_knees}), got shape {x.shape}")
+    nuisance, design, scales = _design_matrix(x, covariates, intercept, n_knees, ["x"])
+    return nuisance, design, float(scales[0])
 
 
 def _index_rows(permutations, make, n_knees: int) -> IndexPermutations:
@@ -1350,62 +1374,86 @@ def _vertex_maps(cohort: ThicknessCohort, maps, name: str) -> List[Tuple[torch.T
     return out
 
 
-def _vx_setup(cohort: ThicknessCohort, what: str, vertex_covariates, x_map, n_global: int, permutations, n_permutations, seed, blocks,
-              cluster_threshold, tfce, batch):
-    """What the tests share once a per-vertex column is in play: the columns in the design's order (nuisance first, the regressor of
-    interest last), the count checks, the index rows and the ``_Batches``.  ``n_global``: the global columns of the design."""
-    N = len(cohort)
-    if N < 2:
-        raise ValueError(f"{what} needs at least two knees")
-    nuis, interest = _vertex_maps(cohort, vertex_covariates, "vertex_covariates"), _vertex_maps(cohort, x_map, "x")
-    if len(interest) > 1:
-        raise ValueError("x must be ONE map: one regressor of interest")
-    S = len(nuis) + len(interest)
-    if S > ops.MAX_VERTEX_COLUMNS:
-        raise ValueError(f"vertex_covariates: at most {ops.MAX_VERTEX_COLUMNS} per-vertex columns are supported (x as a map counts), got {S}")
-    p = S + n_global
-    if p > ops.MAX_DESIGN_COLUMNS:
-        raise ValueError(f"the design has {p} columns ({n_global} global ones and {S} per-vertex ones from vertex_covariates and x); at most "
-                         f"{ops.MAX_DESIGN_COLUMNS} are supported")
-    perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
-    V, dev = cohort.n_verts, cohort.device
-    pg = p - S
-    batches = _Batches(cohort, len(perms), V, dev, cluster_threshold, tfce, batch, N * 8 * (pg + pg * (pg + 1) // 2 + 1))
-    columns = torch.stack([c[0] for c in nuis + interest])
-    masks = torch.stack([c[1] for c in nuis + interest])
-    return perms, batches, columns, masks, len(interest), p, S
-
-
-def _regression_vx(cohort: ThicknessCohort, x, covariates, vertex_covariates, intercept: bool, n_permutations, cluster_threshold, seed, blocks,
-                   permutations, batch, tfce) -> RegressionResult:
-    """``regression_test`` with per-vertex design columns: ``vertex_covariates`` as nuisance and, where ``x`` is a map, ``x`` itself."""
-    N, x_map = len(cohort), _is_map(x)
-    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
-    setup = _vx_setup(cohort, "regression_test", vertex_covariates, x if x_map else None, n_cov + int(bool(intercept)) + (0 if x_map else 1),
-                      permutations, n_permutations, seed, blocks, cluster_threshold, tfce, batch)
-    perms, batches, columns, masks, si, p, S = setup
-    if x_map:                                                              # every global column is nuisance: the intercept and the covariates
-        scale = 1.0                                                        # per-vertex columns are not rescaled: slope is per unit of the map
-        design = (_design_matrix(covariates, None, bool(intercept), N, [f"covariate {j}" for j in range(n_cov)])[1] if n_cov else
-                  np.ones((N, int(bool(intercept)))))
-        nuisance = design
-    else:
-        nuisance, design, scale = _design_columns(x, covariates, bool(intercept), N)
-    dev, V = cohort.device, cohort.n_verts
-    index = torch.from_numpy(perms.index).to(dev)
-    design_d = torch.from_numpy(np.ascontiguousarray(design)).to(dev) if design.shape[1] else None
-    prepared = ops.regression_vx_prepare(cohort.values, cohort.mask, columns, masks, torch.from_numpy(np.ascontiguousarray(nuisance)).to(dev)
-                                         if nuisance.shape[1] else None, n_vertex_interest=si, centre=bool(intercept))
-    slope0 = torch.empty(V, dtype=torch.float64, device=dev)
-    ws = _lib.workspace("oai_regression_vx_t", dev, batches.rows, V, N, p, S)
-    host, shared = batches.run(lambda p0, p1: ops.regression_vx_t(prepared, design_d, index, p0, p1, workspace=ws, slope0=slope0 if p0 == 0 else None),
-                               {"slope": slope0, "n": prepared.n, "n_dropped": prepared.n_dropped})
+def _t_result(cohort: ThicknessCohort, host: dict, shared: dict, perms: IndexPermutations, p: int, scale: float) -> RegressionResult:
+    """The ``RegressionResult`` of one download."""
     t, n = host["t"], host["n"]
     dof = n.astype(np.int64) - p
     with np.errstate(invalid="ignore", divide="ignore"):
         partial_r = t / np.sqrt(t * t + dof.astype(np.float64))
-    res = RegressionResult(kind=cohort.kind, n=n, dof=dof, slope=host["slope"] / scale, partial_r=partial_r, exact=perms.exact, **shared)
-    res.n_dropped = host["n_dropped"]
+    return RegressionResult(kind=cohort.kind, n=n, dof=dof, slope=host["slope"] / scale, partial_r=partial_r, exact=perms.exact, **shared)
+
+
+# What a statistic of the linear-model tests brings of its own: the batch op and the entry point whose workspace it takes, without and
+# with per-vertex columns, and what row 0 also gives (the op's argument for it is that name + "0").
+_LINEAR_MODEL_OPS = {"t": ((ops.regression_t, "oai_regression_t"), (ops.regression_vx_t, "oai_regression_vx_t"), "slope"),
+                     "f": ((ops.regression_f, "oai_regression_f"), (ops.regression_vx_f, "oai_regression_vx_f"), "coef")}
+
+
+def _linear_model_test(cohort: ThicknessCohort, what: str, stat: str, X, names, covariates, intercept: bool, n_permutations, cluster_threshold,
+                       seed, blocks, permutations, batch, tfce, vertex_covariates=None, x_map=None, groups=None):
+    """The one driver of ``regression_test`` (``stat`` "t": the t of the last design column, ``X`` the regressor or, beside ``x_map``,
+    None) and of ``f_test`` and ``anova_test`` ("f": the F of the columns of ``X``, jointly; ``names``: ``_design_matrix``'s).
+    ``vertex_covariates``, ``x_map``: per-vertex nuisance columns and the per-vertex regressor of interest (``regression_test`` says what
+    they are), or None; then the maps stand around the global design and ``n`` / ``dof`` count the complete cases.  ``groups``: (levels,
+    the level index of every knee) of ``anova_test`` -- then also the counted means."""
+    tfce = _tfce_settings(tfce)
+    N, centre = len(cohort), bool(intercept)
+    if N < 2:
+        raise ValueError(f"{what} needs at least two knees")
+
+    def host_design():
+        if stat == "t" and x_map is None:                                  # one regressor: its own shape check, its scale a number
+            return _design_columns(X, covariates, centre, N)
+        return _design_matrix(X, covariates, centre, N, names)
+
+    vx = vertex_covariates is not None or x_map is not None
+    if vx:                 # the maps and the column counts are refused first, the host design after the permutations and the batch
+        pg = _n_columns(covariates) + int(centre) + _n_columns(X)          # the global columns of the design
+        nuis, interest = _vertex_maps(cohort, vertex_covariates, "vertex_covariates"), _vertex_maps(cohort, x_map, "x")
+        if len(interest) > 1:
+            raise ValueError("x must be ONE map: one regressor of interest")
+        S = len(nuis) + len(interest)
+        if S > ops.MAX_VERTEX_COLUMNS:
+            raise ValueError(f"vertex_covariates: at most {ops.MAX_VERTEX_COLUMNS} per-vertex columns are supported (x as a map counts), got {S}")
+        p = S + pg
+        if p > ops.MAX_DESIGN_COLUMNS:
+            raise ValueError(f"the design has {p} columns ({pg} global ones and {S} per-vertex ones from vertex_covariates and x); at most "
+                             f"{ops.MAX_DESIGN_COLUMNS} are supported")
+        row_bytes = N * 8 * (pg + pg * (pg + 1) // 2 + 1)
+    else:
+        nuisance, design, scales = host_design()
+        p = design.shape[1]
+        row_bytes = _table_bytes(N, p)
+    perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
+    values, mask = cohort.values, cohort.mask
+    V, dev = int(values.shape[1]), values.device
+    batches = _Batches(cohort, len(perms), V, dev, cluster_threshold, tfce, batch, row_bytes)
+    if vx:                                                                 # in the design's order: nuisance first, the regressor of interest last
+        columns, masks = torch.stack([c[0] for c in nuis + interest]), torch.stack([c[1] for c in nuis + interest])
+        nuisance, design, scales = host_design()
+    index = torch.from_numpy(perms.index).to(dev)
+    design_d = torch.from_numpy(design).to(dev) if design.shape[1] else None
+    nuisance_d = torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None
+    if vx:
+        prepared = ops.regression_vx_prepare(values, mask, columns, masks, nuisance_d, n_vertex_interest=len(interest), centre=centre)
+    else:
+        prepared = ops.regression_prepare(values, mask, nuisance_d, centre=centre)
+    (tile, entry), first = _LINEAR_MODEL_OPS[stat][int(vx)], _LINEAR_MODEL_OPS[stat][2]
+    k = () if stat == "t" else (len(scales),)                              # the F ops take k, and their row 0 gives [k, V]
+    out0 = torch.empty((*k, V), dtype=torch.float64, device=dev)
+    extras = {first: out0, "n": prepared.n}
+    if vx:
+        extras["n_dropped"] = prepared.n_dropped
+    extras.update(_group_sides(values, mask, groups))
+    ws = _lib.workspace(entry, dev, batches.rows, V, N, p, *([S] if vx else []))
+    host, shared = batches.run(lambda p0, p1: tile(prepared, design_d, index, p0, p1, *k, workspace=ws, **{first + "0": out0 if p0 == 0 else None}),
+                               extras)
+    if stat == "t":                                                        # a per-vertex x is not rescaled: slope is per unit of the map
+        res = _t_result(cohort, host, shared, perms, p, scales if x_map is None else 1.0)
+    else:
+        res = _f_result(cohort, host, shared, perms, p, scales, groups)
+    if vx:
+        res.n_dropped = host["n_dropped"]
     return res
 
 
@@ -1431,31 +1479,9 @@ def regression_test(cohort: ThicknessCohort, x, covariates=None, intercept: bool
     row whose covariate is missing stands on the complete-case mean.  Per-vertex columns are centred (with an intercept) on the device and
     not rescaled.  The coefficient of a per-vertex NUISANCE column is not returned: pass it as ``x`` to get it.  None: the test runs as
     it always has."""
-    if vertex_covariates is not None or _is_map(x):
-        return _regression_vx(cohort, x, covariates, vertex_covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations,
-                              batch, _tfce_settings(tfce))
-    tfce = _tfce_settings(tfce)
-    N = len(cohort)
-    if N < 2:
-        raise ValueError("regression_test needs at least two knees")
-    nuisance, design, scale = _design_columns(x, covariates, bool(intercept), N)
-    perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
-    P, p = len(perms), design.shape[1]
-    values, mask = cohort.values, cohort.mask
-    V, dev = int(values.shape[1]), values.device
-    batches = _Batches(cohort, P, V, dev, cluster_threshold, tfce, batch, _table_bytes(N, p))
-    index = torch.from_numpy(perms.index).to(dev)
-    design_d = torch.from_numpy(design).to(dev)
-    prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
-    slope0 = torch.empty(V, dtype=torch.float64, device=dev)
-    ws = _lib.workspace("oai_regression_t", dev, batches.rows, V, N, p)
-    host, shared = batches.run(lambda p0, p1: ops.regression_t(prepared, design_d, index, p0, p1, workspace=ws, slope0=slope0 if p0 == 0 else None),
-                               {"slope": slope0, "n": prepared.n})
-    t, n = host["t"], host["n"]
-    dof = n.astype(np.int64) - p
-    with np.errstate(invalid="ignore", divide="ignore"):
-        partial_r = t / np.sqrt(t * t + dof.astype(np.float64))
-    return RegressionResult(kind=cohort.kind, n=n, dof=dof, slope=host["slope"] / scale, partial_r=partial_r, exact=perms.exact, **shared)
+    x, x_map = (None, x) if _is_map(x) else (x, None)                          # beside a map every global column is nuisance
+    return _linear_model_test(cohort, "regression_test", "t", x, None, covariates, intercept, n_permutations, cluster_threshold, seed, blocks,
+                              permutations, batch, tfce, vertex_covariates=vertex_covariates, x_map=x_map)
 
 
 # ---- one-stage models of clustered rows (include/oai_hip.h, "Cluster-robust regression"; csrc/cluster_robust.hip) ----------------------------
@@ -1587,76 +1613,6 @@ class FResult(_SurfaceResult):
     n_dropped = None        # as in ``RegressionResult``: set with ``vertex_covariates``, when ``n`` and ``dof2`` count the complete cases
 
 
-def _design_matrix(X, covariates, intercept: bool, n_knees: int, names: Optional[Sequence[str]] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """The multi-column form of ``_design_columns``: (nuisance [N, q], design [N, q + k] with the k columns of ``X`` last, the k scales
-    those columns were divided by); refuses what has no answer and names the column at fault (``names``: what the columns of ``X`` are
-    called; default "X column j")."""
-    X = np.asarray(X, np.float64)
-    X = X[:, None] if X.ndim == 1 else X
-    if X.ndim != 2 or X.shape[0] != n_knees or X.shape[1] < 1:
-        raise ValueError(f"X must be [{n_knees}] or [{n_knees}, k >= 1], got shape {X.shape}")
-    cov = np.zeros((n_knees, 0)) if covariates is None else np.asarray(covariates, np.float64)
-    cov = cov[:, None] if cov.ndim == 1 else cov
-    if cov.ndim != 2 or cov.shape[0] != n_knees:
-        raise ValueError(f"covariates must be [{n_knees}] or [{n_knees}, c], got shape {cov.shape}")
-    k = X.shape[1]
-    names = [f"X column {j}" for j in range(k)] if names is None else list(names)
-    p = cov.shape[1] + k + int(bool(intercept))
-    if p > ops.MAX_DESIGN_COLUMNS:
-        raise ValueError(f"the design has {p} columns ({'the intercept, ' if intercept else ''}{cov.shape[1]} covariates, {k} tested columns); at most "
-                         f"{ops.MAX_DESIGN_COLUMNS} are supported")
-    named = [(f"covariate {j}", cov[:, j]) for j in range(cov.shape[1])] + list(zip(names, X.T))
-    cols = []
-    for name, c in named:
-        if not np.isfinite(c).all():
-            raise ValueError(f"{name} holds a NaN or an infinity: the design must be finite for every knee")
-        if (c == c[0]).all():
-            raise ValueError(f"{name} is constant over the knees")
-        c = c - c.mean() if intercept else c.copy()
-        norm = float(np.sqrt((c * c).sum()))
-        if not norm > 0.0:
-            raise ValueError(f"{name} is constant over the knees")
-        cols.append((c, norm))
-    Z = ([np.ones(n_knees)] if intercept else []) + [c / s for c, s in cols[:cov.shape[1]]]
-    nuisance = np.stack(Z, axis=1) if Z else np.zeros((n_knees, 0))
-    design = np.ascontiguousarray(np.concatenate([nuisance] + [(c / s)[:, None] for c, s in cols[cov.shape[1]:]], axis=1))
-    unit = design / np.sqrt((design * design).sum(axis=0))[None, :]
-    every = (["the intercept"] if intercept else []) + [name for name, _ in named]
-    for j in range(p):                                                     # the first column that the ones before it already span
-        if n_knees < j + 1 or np.linalg.matrix_rank(unit[:, :j + 1]) < j + 1:
-            raise ValueError(f"the design does not have full column rank over the knees: {every[j]} is a combination of the columns before it")
-    return np.ascontiguousarray(nuisance), design, np.asarray([s for _, s in cols[cov.shape[1]:]], np.float64)
-
-
-def _f_run(cohort: ThicknessCohort, what: str, X, names, covariates, intercept: bool, n_permutations: int, cluster_threshold, seed: int, blocks,
-           permutations, batch, tfce, groups: Optional[Tuple[np.ndarray, np.ndarray]] = None, vertex_covariates=None) -> FResult:
-    """What ``f_test`` and ``anova_test`` share.  ``groups``: (levels, the level index of every knee) -- then also the counted means.
-    ``vertex_covariates``: per-vertex nuisance columns (``regression_test`` says what they are), or None."""
-    tfce = _tfce_settings(tfce)
-    N = len(cohort)
-    if N < 2:
-        raise ValueError(f"{what} needs at least two knees")
-    if vertex_covariates is not None:
-        return _f_run_vx(cohort, what, X, names, covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
-                         groups, vertex_covariates)
-    nuisance, design, scales = _design_matrix(X, covariates, bool(intercept), N, names)
-    perms = _index_rows(permutations, lambda: index_permutations(N, n_permutations, seed, blocks), N)
-    P, p, k = len(perms), design.shape[1], len(scales)
-    values, mask = cohort.values, cohort.mask
-    V, dev = int(values.shape[1]), values.device
-    batches = _Batches(cohort, P, V, dev, cluster_threshold, tfce, batch, _table_bytes(N, p))
-    index = torch.from_numpy(perms.index).to(dev)
-    design_d = torch.from_numpy(design).to(dev)
-    prepared = ops.regression_prepare(values, mask, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None, centre=bool(intercept))
-    coef0 = torch.empty((k, V), dtype=torch.float64, device=dev)
-    extras = {"coef": coef0, "n": prepared.n}
-    extras.update(_group_sides(values, mask, groups))
-    ws = _lib.workspace("oai_regression_f", dev, batches.rows, V, N, p)
-    host, shared = batches.run(lambda p0, p1: ops.regression_f(prepared, design_d, index, p0, p1, k, workspace=ws, coef0=coef0 if p0 == 0 else None),
-                               extras)
-    return _f_result(cohort, host, shared, perms, p, scales, groups)
-
-
 def _group_sides(values: torch.Tensor, mask: torch.Tensor, groups) -> dict:
     """The descriptive side of ``anova_test``: n and mean of every level, per vertex, as device tensors to download with the rest."""
     sides = {}
@@ -1669,7 +1625,7 @@ def _group_sides(values: torch.Tensor, mask: torch.Tensor, groups) -> dict:
 
 
 def _f_result(cohort: ThicknessCohort, host: dict, shared: dict, perms: IndexPermutations, p: int, scales: np.ndarray, groups) -> FResult:
-    """The ``FResult`` of one download: what ``_f_run`` and ``_f_run_vx`` do with it alike."""
+    """The ``FResult`` of one download."""
     f, n, k = shared.pop("t"), host["n"], len(scales)
     dof2 = n.astype(np.int64) - p
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -1680,35 +1636,6 @@ def _f_result(cohort: ThicknessCohort, host: dict, shared: dict, perms: IndexPer
         described = dict(levels=groups[0], group_n=np.stack([host[f"n{g}"] for g in range(G)]), group_mean=np.stack([host[f"mean{g}"] for g in range(G)]))
     return FResult(kind=cohort.kind, f=f, n=n, dof1=k, dof2=dof2, coefficients=host["coef"] / scales[:, None], partial_eta2=partial_eta2,
                    max_f=shared.pop("max_abs"), exact=perms.exact, **described, **shared)
-
-
-def _f_run_vx(cohort: ThicknessCohort, what: str, X, names, covariates, intercept: bool, n_permutations, cluster_threshold, seed, blocks, permutations,
-              batch, tfce, groups, vertex_covariates) -> FResult:
-    """``_f_run`` with per-vertex nuisance columns (include/oai_hip.h, "Vertex-wise design columns"): the global design is built as ever,
-    the maps stand before it, and ``n`` / ``dof2`` count the complete cases."""
-    N = len(cohort)
-    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
-    n_tested = 1 if np.ndim(X) == 1 else int(np.shape(X)[-1])
-    setup = _vx_setup(cohort, what, vertex_covariates, None, n_cov + int(bool(intercept)) + n_tested, permutations, n_permutations, seed, blocks,
-                      cluster_threshold, tfce, batch)
-    perms, batches, columns, masks, _, p, S = setup
-    nuisance, design, scales = _design_matrix(X, covariates, bool(intercept), N, names)
-    k = len(scales)
-    values, mask = cohort.values, cohort.mask
-    V, dev = int(values.shape[1]), values.device
-    index = torch.from_numpy(perms.index).to(dev)
-    design_d = torch.from_numpy(design).to(dev)
-    prepared = ops.regression_vx_prepare(values, mask, columns, masks, torch.from_numpy(nuisance).to(dev) if nuisance.shape[1] else None,
-                                         centre=bool(intercept))
-    coef0 = torch.empty((k, V), dtype=torch.float64, device=dev)
-    extras = {"coef": coef0, "n": prepared.n, "n_dropped": prepared.n_dropped}
-    extras.update(_group_sides(values, mask, groups))
-    ws = _lib.workspace("oai_regression_vx_f", dev, batches.rows, V, N, p, S)
-    host, shared = batches.run(lambda p0, p1: ops.regression_vx_f(prepared, design_d, index, p0, p1, k, workspace=ws, coef0=coef0 if p0 == 0 else None),
-                               extras)
-    res = _f_result(cohort, host, shared, perms, p, scales, groups)
-    res.n_dropped = host["n_dropped"]
-    return res
 
 
 def f_test(cohort: ThicknessCohort, X, covariates=None, intercept: bool = True, n_permutations: int = 10000,
@@ -1730,8 +1657,8 @@ def f_test(cohort: ThicknessCohort, X, covariates=None, intercept: bool = True, 
     it with ``regression_test(cohort, x=map)``)."""
     if isinstance(X, ThicknessCohort) or (_is_map(X) and X.shape[-1] > ops.MAX_DESIGN_COLUMNS and X.shape[-1] == cohort.n_verts):
         raise ValueError("X must hold one entry per knee and column: a map (one entry per knee and vertex) is tested with regression_test(cohort, x=map)")
-    return _f_run(cohort, "f_test", X, None, covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
-                  vertex_covariates=vertex_covariates)
+    return _linear_model_test(cohort, "f_test", "f", X, None, covariates, intercept, n_permutations, cluster_threshold, seed, blocks, permutations,
+                              batch, tfce, vertex_covariates=vertex_covariates)
 
 
 def _anova_levels(groups, n_knees: int, n_covariates: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -1764,13 +1691,11 @@ def anova_test(cohort: ThicknessCohort, groups, covariates=None, n_permutations:
     ``f_test``; the maps count towards the six columns."""
     if _is_map(groups):
         raise ValueError("groups must hold one label per knee: a map (one entry per knee and vertex) is tested with regression_test(cohort, x=map)")
-    N = len(cohort)
-    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
-    levels, where = _anova_levels(groups, N, n_cov)
+    levels, where = _anova_levels(groups, len(cohort), _n_columns(covariates))
     dummies = np.stack([(where == g).astype(np.float64) for g in range(1, len(levels))], axis=1)
     names = [f"the dummy of level {int(lab)}" for lab in levels[1:]]
-    return _f_run(cohort, "anova_test", dummies, names, covariates, True, n_permutations, cluster_threshold, seed, blocks, permutations, batch, tfce,
-                  groups=(levels, where), vertex_covariates=vertex_covariates)
+    return _linear_model_test(cohort, "anova_test", "f", dummies, names, covariates, True, n_permutations, cluster_threshold, seed, blocks,
+                              permutations, batch, tfce, vertex_covariates=vertex_covariates, groups=(levels, where))
 
 
 # ---- normative deviation ---------------------------------------------------------------------------------------------------------------
@@ -2437,8 +2362,7 @@ def kruskal_test(cohort: ThicknessCohort, groups, covariates=None, scores: str =
     ``test.p_uncorrected`` is the p of the exact Kruskal-Wallis test; where entries are missing the level sizes at a vertex vary with the
     labelling and the statistic is Conover and Iman's F on ranks, still a valid permutation test.  Ranking is over the whole cohort and
     never within ``blocks``.  No asymptotic p-value is formed."""
-    n_cov = 0 if covariates is None else (1 if np.ndim(covariates) == 1 else int(np.shape(covariates)[-1]))
-    levels, where = _anova_levels(groups, len(cohort), n_cov)
+    levels, where = _anova_levels(groups, len(cohort), _n_columns(covariates))
     ranked, ranks = cohort._ranked(_rank_scores_method(scores), "blom")
     test = anova_test(ranked, groups, covariates=covariates, n_permutations=n_permutations, cluster_threshold=cluster_threshold, seed=seed,
                       blocks=blocks, permutations=permutations, batch=batch, tfce=tfce)

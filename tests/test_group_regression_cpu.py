@@ -166,6 +166,44 @@ def test_regression_test_refuses_before_any_launch():
     assert stats.regression_batch(30002, 200, 4, 100000, False) % 16 == 0 and stats.regression_batch(100, 40, 4, 7, True) == 7
 
 
+def test_the_one_regressor_builder_is_the_design_matrix_of_one_column():
+    """``_design_columns`` is ``_design_matrix`` of one column called "x": its three outputs are the bits of the restated multi-column
+    builder (tests/group_f_ref.py) over 2 to 13 knees, 0 to 5 covariates and both intercept settings, and what it refuses it refuses in
+    the words that the callers of the earlier one-column builder match on."""
+    import group_f_ref as fref
+    from oai_analysis_2_amd import stats
+    rng, accepted = np.random.default_rng(11), 0
+    for n in range(2, 14):
+        for c in range(6):
+            for intercept in (True, False):
+                x, cov = rng.normal(size=n), (60 + 8 * rng.normal(size=(n, c)) if c else None)
+                if c + 1 + int(intercept) > min(n, 6):                    # more columns than knees, or than six: refused
+                    with pytest.raises(ValueError, match="at most 6" if c + 1 + int(intercept) > 6 else "full column rank"):
+                        stats._design_columns(x, cov, intercept, n)
+                    continue
+                (Z, D, scale), (Zr, Dr, scales) = stats._design_columns(x, cov, intercept, n), fref.design_matrix(x[:, None], cov, intercept)
+                assert np.array_equal(Z, Zr) and np.array_equal(D, Dr) and scales.shape == (1,) and scale == scales[0] and isinstance(scale, float)
+                assert Z.shape == (n, c + int(intercept)) and D.shape == (n, c + int(intercept) + 1) and D.flags.c_contiguous and Z.flags.c_contiguous
+                accepted += 1
+    assert accepted == 112
+    i = np.arange(10)
+    x, cov = rng.normal(size=10), rng.normal(size=(10, 2))
+    for args, words in (
+            ((np.full(10, 3.0), None, True), "x is constant"),
+            ((x, np.stack([cov[:, 0], np.ones(10)], axis=1), True), "covariate 1 is constant"),
+            ((x, np.stack([cov[:, 0], 2 * x + 1], axis=1), True), "full column rank"),                       # collinear given the intercept
+            ((x, np.stack([cov[:, 0], 3 * x], axis=1), False), "full column rank"),                          # collinear without one
+            ((x, np.stack([i % 2, 1 - i % 2], axis=1).astype(np.float64), True), "full column rank"),        # two dummies add up to it
+            ((x, rng.normal(size=(10, 5)), True), "at most 6"),                                              # seven columns
+            ((np.where(i == 4, np.nan, x), None, True), "NaN"),
+            ((x, np.where(np.arange(20).reshape(10, 2) == 5, np.inf, cov), True), "NaN"),
+            ((x[:9], None, True), "one entry per knee"),
+            ((x[:, None], None, True), "one entry per knee"),
+            ((x, cov[:9], True), "covariates must be")):
+        with pytest.raises(ValueError, match=words):
+            stats._design_columns(*args, 10)
+
+
 def test_a_result_hands_its_maps_to_the_atlas_image():
     from oai_analysis_2_amd import stats
 
