@@ -2,28 +2,19 @@
 bound in _lib.SIGNATURES, the header states the contract word for word, and every entry point refuses bad arguments with a status and a
 message that names it -- on host buffers, so no GPU is touched before the checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_reexported, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_bootstrap_coef_workspace_bytes", "oai_bootstrap_coef", "oai_bootstrap_moments", "oai_column_quantiles_workspace_bytes",
        "oai_column_quantiles", "oai_bootstrap_sup", "oai_jackknife_acceleration")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
-    section = raw[raw.index("Bootstrap intervals"):]
+    raw = check_symbols(NEW)
+    section = _section(raw, "Bootstrap intervals")
     for words in ("tests/bootstrap_ref.py", "csrc/bootstrap.hip", "Efron 1987", "Davison", "NOT pinned", "ASCENDING INDEX",
                   "w_i  = m_iv ? (double)c_ri : 0.0", "u_i  = w_i * (double)y_iv", "h_a  = h_a + g_ia * u_i", "M_ac = M_ac + w_i * G_iac",
                   "product THEN an add", "not an fma", "theta = z_p / L_pp", "THE SAME BITS", "24 + 16 bits", "never multiplied in",
@@ -38,14 +29,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_bootstrap_coef_argument_checks(lib):
@@ -125,9 +108,7 @@ def test_column_quantiles_argument_checks(lib):
 
 
 def test_the_names_are_exported_where_the_other_statistics_are():
-    import oai_analysis_2_amd as pkg
-    from oai_analysis_2_amd import ops, stats
-    for name in ("BootstrapCounts", "BootstrapResult", "bootstrap_counts", "bootstrap_ci"):
-        assert getattr(pkg, name) is getattr(stats, name)
+    from oai_analysis_2_amd import ops
+    check_reexported(("BootstrapCounts", "BootstrapResult", "bootstrap_counts", "bootstrap_ci"))
     for name in ("bootstrap_coef", "bootstrap_moments", "column_quantiles", "bootstrap_sup", "jackknife_acceleration"):
         assert callable(getattr(ops, name))

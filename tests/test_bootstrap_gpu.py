@@ -2,24 +2,19 @@
 quantiles, sup-t and acceleration to the bit -- and oai_analysis_2_amd.stats.bootstrap_ci end to end on a small sphere.  Every float64 is
 the result of IEEE add / subtract / multiply / divide / sqrt / floor in a stated order, so equality is exact."""
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 import bootstrap_ref as bref
-from test_group_regression_gpu import _cohort, _design, _icosphere, _same_bits
+from cohort_cases import bare_atlas, cohort as _cohort, design, dev, icosphere, knees as _knees, same_bits, sphere_atlas
 
 pytestmark = pytest.mark.gpu
 
 COLUMNS = (1, 2, 4, 6)
 VERTS = (1, 63, 65, 257, 600)                     # both sides of a wave (64) and of a block's 256 vertices, several blocks
 PLANTED = {"empty": 1, "exact": 2, "unseen": 3, "constant": 4, "dummy": 5}
-
-
-def _knees(p):
-    return tuple(sorted({p + 1, 7, 31, 33, 65}))
 
 
 def _rows_per_thread(p, masked):                  # csrc/bootstrap.hip, rows_per_thread
@@ -32,15 +27,11 @@ def _rows(p, masked):
     return tuple(sorted({n for n in (1, 2, r - 1, r + 1, 2 * r + 5) if n >= 1}))
 
 
-def _dev(a):
-    return torch.from_numpy(np.array(a)).cuda()
-
-
 @functools.lru_cache(maxsize=None)
 def _case(N, V, p, masked):
     """(Y, mask, design, counts) with the header's corner cases planted where the shape has room (V >= 8)."""
     rng = np.random.default_rng([N, V, p, int(masked), 77])
-    D = _design(N, p, rng)
+    D = design(N, p, rng)
     Y = (2.0 + 0.5 * rng.normal(size=(N, V)) + 0.3 * D[:, -1:] * rng.random(V)[None, :]).astype(np.float32)
     mask = rng.random((N, V)) >= 0.1 if masked else None
     R = max(_rows(p, masked))
@@ -83,27 +74,27 @@ def test_coefficient_tile_n_and_ok_equal_the_restatement_to_the_bit(p, masked):
         for V in VERTS:
             Y, mask, D, counts = _case(N, V, p, masked)
             theta, n_ref, ok_ref = _reference(N, V, p, masked)
-            y_d, m_d, d_d, c_d = _dev(Y), None if mask is None else _dev(mask.astype(np.uint8)), _dev(D), _dev(counts)
+            y_d, m_d, d_d, c_d = dev(Y), None if mask is None else dev(mask.astype(np.uint8)), dev(D), dev(counts)
             where = f"N={N} V={V}"
             for R in _rows(p, masked):
                 n = torch.full((V,), -7, dtype=torch.int32, device="cuda")
                 ok = torch.full((V,), -7, dtype=torch.int32, device="cuda")
                 tile = ops.bootstrap_coef(y_d, d_d, c_d, 0, R, mask=m_d, n=n, ok=ok)
-                _same_bits(tile, theta[:R], f"{where} R={R} theta")
-                _same_bits(n, n_ref, f"{where} R={R} n")
-                _same_bits(ok, ok_ref, f"{where} R={R} ok")
+                same_bits(tile, theta[:R], f"{where} R={R} theta")
+                same_bits(n, n_ref, f"{where} R={R} n")
+                same_bits(ok, ok_ref, f"{where} R={R} ok")
             R = counts.shape[0]
             for v0, v1 in _spans(V):
                 n = torch.full((V,), -7, dtype=torch.int32, device="cuda")
                 tile = ops.bootstrap_coef(y_d, d_d, c_d, 0, R, mask=m_d, v0=v0, v1=v1, n=n)
-                _same_bits(tile, np.ascontiguousarray(theta[:, v0:v1]), f"{where} span [{v0}, {v1}) theta")
+                same_bits(tile, np.ascontiguousarray(theta[:, v0:v1]), f"{where} span [{v0}, {v1}) theta")
                 want = np.full(V, -7, np.int32)
                 want[v0:v1] = n_ref[v0:v1]
-                _same_bits(n, want, f"{where} span [{v0}, {v1}) n")        # nothing outside the span is written
+                same_bits(n, want, f"{where} span [{v0}, {v1}) n")        # nothing outside the span is written
             if R > 4:                                                      # a batch that does not start at row 0 leaves n alone
                 n = torch.full((V,), -7, dtype=torch.int32, device="cuda")
                 tile = ops.bootstrap_coef(y_d, d_d, c_d, 3, R, mask=m_d, n=n)
-                _same_bits(tile, np.ascontiguousarray(theta[3:]), f"{where} rows [3, {R}) theta")
+                same_bits(tile, np.ascontiguousarray(theta[3:]), f"{where} rows [3, {R}) theta")
                 assert (n == -7).all()
             # on the restatement: what was planted is really there
             assert (n_ref == (N if not masked else mask.sum(axis=0))).all()
@@ -129,13 +120,13 @@ def test_no_mask_gives_the_bits_of_a_mask_of_all_ones(p):
     N, V = 33, 257
     Y, _, D, counts = _case(N, V, p, False)
     theta, n_ref, ok_ref = _reference(N, V, p, False)
-    y_d, d_d, c_d = _dev(Y), _dev(D), _dev(counts)
+    y_d, d_d, c_d = dev(Y), dev(D), dev(counts)
     ones = torch.ones((N, V), dtype=torch.uint8, device="cuda")
     for m_d, what in ((None, "no mask"), (ones, "all ones")):              # two kernels, two row groupings
         n, ok = torch.zeros(V, dtype=torch.int32, device="cuda"), torch.zeros(V, dtype=torch.int32, device="cuda")
-        _same_bits(ops.bootstrap_coef(y_d, d_d, c_d, 0, counts.shape[0], mask=m_d, n=n, ok=ok), theta, f"theta ({what})")
-        _same_bits(n, n_ref, f"n ({what})")
-        _same_bits(ok, ok_ref, f"ok ({what})")
+        same_bits(ops.bootstrap_coef(y_d, d_d, c_d, 0, counts.shape[0], mask=m_d, n=n, ok=ok), theta, f"theta ({what})")
+        same_bits(n, n_ref, f"n ({what})")
+        same_bits(ok, ok_ref, f"ok ({what})")
     assert (n_ref == N).all() and not np.isnan(theta[0]).any()
 
 
@@ -175,26 +166,26 @@ def test_column_quantiles_equal_the_restatement_to_the_bit(V):
     from oai_analysis_2_amd import ops
     for R in ROWS:
         t = _replicates(R, V, 1)
-        t_d = _dev(t)
+        t_d = dev(t)
         for first in (0, 1):
             for probs in _probabilities(R - first):
                 want, count = bref.column_quantiles(t, probs, first)
                 got, n = ops.column_quantiles(t_d, probs, first_row=first)
-                _same_bits(got, want, f"R={R} V={V} first={first} shared")
-                _same_bits(n, count, f"R={R} V={V} first={first} count")
+                same_bits(got, want, f"R={R} V={V} first={first} shared")
+                same_bits(n, count, f"R={R} V={V} first={first} count")
         rng = np.random.default_rng([R, V])
         per_vertex = rng.random((4, V))
         per_vertex[0, 0], per_vertex[1, 0], per_vertex[2, 0], per_vertex[3, 0] = np.nan, -0.25, 1.0, 0.0
         per_vertex[:, V // 2] = [1.5, 0.5, np.nan, 1.0]
         want, count = bref.column_quantiles(t, per_vertex, 1)
-        got, n = ops.column_quantiles(t_d, _dev(per_vertex), first_row=1)
-        _same_bits(got, want, f"R={R} V={V} per vertex")
-        _same_bits(n, count, f"R={R} V={V} per vertex count")
+        got, n = ops.column_quantiles(t_d, dev(per_vertex), first_row=1)
+        same_bits(got, want, f"R={R} V={V} per vertex")
+        same_bits(n, count, f"R={R} V={V} per vertex count")
         assert np.isnan(want[0 if V > 1 else 2, V // 2]) and (V <= 8 or (np.isnan(want[:2, 0]).all() and count[5] == 0 and np.isnan(want[:, 5]).all()))
     # against numpy itself, where the column has neither a NaN nor opposite infinities
     t = _replicates(257, V, 2)
     probs = np.array([0.0, 0.05, 0.5, 1.0])
-    got = ops.column_quantiles(_dev(t), probs)[0].cpu().numpy()
+    got = ops.column_quantiles(dev(t), probs)[0].cpu().numpy()
     clean = ~np.isnan(t).any(axis=0) & ~np.isinf(t).any(axis=0)
     assert clean.sum() >= min(V, V - 5) and np.array_equal(got[:, clean], np.quantile(t[:, clean], probs, axis=0))
 
@@ -204,23 +195,23 @@ def test_moments_and_sup_equal_the_restatement_to_the_bit(V):
     from oai_analysis_2_amd import ops
     for R in ROWS:
         t = _replicates(R, V, 3)
-        t_d = _dev(t)
+        t_d = dev(t)
         want = bref.moments(t)
         got = ops.bootstrap_moments(t_d)
         for name in ("n_finite", "mean", "se", "below", "equal"):
-            _same_bits(getattr(got, name), want[name], f"R={R} V={V} {name}")
+            same_bits(getattr(got, name), want[name], f"R={R} V={V} {name}")
         if V > 8 and R > 2:
             assert want["se"][6] == 0.0 and want["equal"][6] == R - 1 and want["n_finite"][5] == 0 and np.isnan(want["se"][5])
         running = np.random.default_rng(R).random(R) * (np.arange(R) % 2)          # a running maximum that some rows exceed and some do not
-        sup = _dev(running)
+        sup = dev(running)
         ops.bootstrap_sup(t_d, got.se, sup)
-        _same_bits(sup, bref.sup(t, want["se"], running), f"R={R} V={V} sup")
+        same_bits(sup, bref.sup(t, want["se"], running), f"R={R} V={V} sup")
         half = V // 2                                                              # two spans fold to the whole
         if half:
             sup2 = torch.zeros(R, dtype=torch.float64, device="cuda")
             for a, b in ((0, half), (half, V)):
                 ops.bootstrap_sup(t_d[:, a:b].contiguous(), got.se[a:b].contiguous(), sup2)
-            _same_bits(sup2, bref.sup(t, want["se"], np.zeros(R)), f"R={R} V={V} sup over two spans")
+            same_bits(sup2, bref.sup(t, want["se"], np.zeros(R)), f"R={R} V={V} sup over two spans")
 
 
 @pytest.mark.parametrize("V", QVERTS)
@@ -239,15 +230,15 @@ def test_acceleration_equals_the_restatement_to_the_bit(V):
             jack[N // 2, 5], mask[N // 2, 5] = np.nan, False                       # a NaN on a missing one does not count
         for m, S, what in ((mask, 2, "masked"), (None, 2, "no mask"), (mask, 1, "one stratum of two labels"), (None, 3, "an empty stratum")):
             want = bref.acceleration(jack, m, strata, S)
-            got = ops.jackknife_acceleration(_dev(jack), _dev(strata), S, mask=None if m is None else _dev(m.astype(np.uint8)))
-            _same_bits(got, want, f"N={N} V={V} {what}")
+            got = ops.jackknife_acceleration(dev(jack), dev(strata), S, mask=None if m is None else dev(m.astype(np.uint8)))
+            same_bits(got, want, f"N={N} V={V} {what}")
         want = bref.acceleration(jack, mask, strata, 2)
         if V > 8:
             assert np.isnan(want[2]) and np.isnan(want[3]) and np.isnan(want[4]) and (N < 7 or not np.isnan(want[5]))
             assert N < 7 or not np.isnan(want[1])
             a, b = 3, V - 2                                                        # a span inside the cohort's vertices
-            got = ops.jackknife_acceleration(_dev(np.ascontiguousarray(jack[:, a:b])), _dev(strata), 2, mask=_dev(mask.astype(np.uint8)), v0=a)
-            _same_bits(got, want[a:b], f"N={N} V={V} span")
+            got = ops.jackknife_acceleration(dev(np.ascontiguousarray(jack[:, a:b])), dev(strata), 2, mask=dev(mask.astype(np.uint8)), v0=a)
+            same_bits(got, want[a:b], f"N={N} V={V} span")
 
 
 # ---- the public interface --------------------------------------------------------------------------------------------------------------
@@ -255,18 +246,16 @@ N_E2E, B_E2E, LEVEL = 24, 199, 0.9
 FIELDS = ("estimate", "se", "lower", "upper", "n", "n_finite", "z0", "acceleration", "sup", "lower_simultaneous", "upper_simultaneous")
 
 
-def _atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _icosphere()
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0),
-                           image=lambda vec, kind: np.asarray(vec, np.float32).reshape(1, -1))
+def _image(vec, kind):
+    """Stands for the atlas' rasteriser."""
+    return np.asarray(vec, np.float32).reshape(1, -1)
 
 
 @functools.lru_cache(maxsize=None)
 def _painted():
     """24 knees on the sphere: 2 mm + 0.1 mm noise, 0.3 mm more in group 1 and 0.2 mm per unit of x on the cap z > 0.8; 3 % of the entries
     and one whole vertex are missing."""
-    verts, _ = _icosphere()
+    verts, _ = icosphere()
     cap = verts[:, 2] > 0.8
     rng = np.random.default_rng(2026)
     groups = np.array([3] * 10 + [8] * 14)
@@ -283,7 +272,7 @@ def _painted():
 def _check(res, want, what):
     for name in FIELDS:
         if name in want:
-            _same_bits(getattr(res, name), want[name], f"{what} {name}")
+            same_bits(getattr(res, name), want[name], f"{what} {name}")
         else:
             assert getattr(res, name) is None, (what, name)
     assert res.critical == want.get("critical")
@@ -293,8 +282,8 @@ def _check(res, want, what):
 def test_bootstrap_ci_equals_the_restatement_to_the_bit(method):
     from oai_analysis_2_amd import stats
     Y, groups, x, age, cap = _painted()
-    atlas = _atlas()
-    cohort = _cohort(atlas, Y)
+    atlas = sphere_atlas(image=_image)
+    cohort = _cohort(atlas, Y, chunk=7)
     mask = cohort.mask.cpu().numpy() != 0
     values = cohort.values.cpu().numpy()
     assert np.array_equal(mask, ~np.isnan(Y))
@@ -330,21 +319,20 @@ def test_a_vertex_permutation_of_the_cohort_permutes_the_result():
     from oai_analysis_2_amd import stats
     Y, groups, _, age, _ = _painted()
     order = np.random.default_rng(9).permutation(Y.shape[1])
-    from oai_analysis_2_amd import mesh_processing as mp
-    bare = SimpleNamespace(inner={"FC": mp.Mesh(np.zeros((Y.shape[1], 3), np.float32), np.zeros((0, 3), np.int32))}, device=torch.device("cuda", 0))
+    bare = bare_atlas(Y.shape[1])
     kw = dict(groups=groups, covariates=age, n_bootstrap=B_E2E, level=LEVEL, method="bca", simultaneous=True, seed=5, batch=200)
-    res, moved = stats.bootstrap_ci(_cohort(bare, Y), **kw), stats.bootstrap_ci(_cohort(bare, Y[:, order]), **kw)
+    res, moved = stats.bootstrap_ci(_cohort(bare, Y, chunk=7), **kw), stats.bootstrap_ci(_cohort(bare, Y[:, order], chunk=7), **kw)
     for name in FIELDS:
         a, b = getattr(res, name), getattr(moved, name)
-        _same_bits(b, a if name == "sup" else a[order], name)
+        same_bits(b, a if name == "sup" else a[order], name)
     assert moved.critical == res.critical
 
 
 def test_without_simultaneous_or_bca_their_fields_are_absent_and_bad_arguments_are_refused():
     from oai_analysis_2_amd import stats
     Y, groups, x, _, _ = _painted()
-    atlas = _atlas()
-    cohort = _cohort(atlas, Y)
+    atlas = sphere_atlas(image=_image)
+    cohort = _cohort(atlas, Y, chunk=7)
     res = stats.bootstrap_ci(cohort, n_bootstrap=20)
     assert res.z0 is None and res.acceleration is None and res.sup is None and res.critical is None and res.lower_simultaneous is None
     with pytest.raises(ValueError, match="simultaneous"):

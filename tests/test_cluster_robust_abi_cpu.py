@@ -2,14 +2,12 @@
 built library and listed in ``_lib.SIGNATURES``; the header states the definition; and every refusal returns a status and a message -- no
 GPU is touched before the checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_reexported, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_cluster_prepare_workspace_bytes", "oai_cluster_prepare", "oai_cluster_t_workspace_bytes", "oai_cluster_t")
 
 DEFINITION = (
@@ -34,15 +32,8 @@ DEFINITION = (
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h"), encoding="utf-8").read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
-    section = raw[raw.index("Cluster-robust regression"):]
+    raw = check_symbols(NEW)
+    section = _section(raw, "Cluster-robust regression")
     section = section[:section.index("Threshold-free cluster enhancement")]
     for words in DEFINITION + ("tests/cluster_robust_ref.py", "csrc/cluster_robust.hip", "CLUSTER-MAJOR ORDER", "THE REGRESSOR OF INTEREST IS THE LAST COLUMN",
                                "Liang and Zeger 1986", "Cameron, Gelbach and Miller 2008", "Guillaume et al. 2014", "NOT pinned",
@@ -54,14 +45,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_cluster_prepare_argument_checks(lib):
@@ -108,8 +91,6 @@ def test_cluster_t_argument_checks(lib):
 
 
 def test_the_names_are_exported_where_the_other_statistics_are():
-    import oai_analysis_2_amd as pkg
-    from oai_analysis_2_amd import ops, stats
-    for name in ("MarginalResult", "marginal_test"):
-        assert getattr(pkg, name) is getattr(stats, name)
+    from oai_analysis_2_amd import ops
+    check_reexported(("MarginalResult", "marginal_test"))
     assert callable(ops.cluster_prepare) and callable(ops.cluster_t)

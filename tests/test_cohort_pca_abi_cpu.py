@@ -7,22 +7,15 @@ import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import ROOT, check_reexported, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_cohort_whiten", "oai_rows_cross", "oai_rows_cross_workspace_bytes", "oai_rows_combine")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
-    section = " ".join(raw[raw.index("Cohort PCA (csrc/cohort_pca.hip"):].replace("\n *", " ").split())
+    raw = check_symbols(NEW)
+    section = " ".join(_section(raw, "Cohort PCA (csrc/cohort_pca.hip").replace("\n *", " ").split())
     for words in ("tests/cohort_pca_ref.py", "csrc/cohort_pca.hip",
                   "Y: float32 [N][V], knee-major.",
                   "M: uint8 mask, may be null. Validity is as everywhere else: the mask is non-zero and the value is not NaN.",
@@ -64,11 +57,6 @@ def test_the_kernels_limits_are_the_ones_the_python_layer_and_the_tests_name():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
 
 
 def test_cohort_whiten_argument_checks(lib):
@@ -124,10 +112,8 @@ def test_rows_combine_argument_checks(lib):
 
 
 def test_the_names_are_exported_where_the_other_statistics_are():
-    import oai_analysis_2_amd as pkg
     from oai_analysis_2_amd import dask_processing, ops, stats
-    for name in ("ThicknessPCA", "PCAScores"):
-        assert getattr(pkg, name) is getattr(stats, name)
+    check_reexported(("ThicknessPCA", "PCAScores"))
     for name in ("fit", "transform", "member_scores", "reconstruct", "image", "save", "load"):
         assert callable(getattr(stats.ThicknessPCA, name))
     assert callable(stats.ThicknessCohort.pca) and callable(dask_processing.pca_stream)

@@ -20,7 +20,7 @@ import pytest
 import torch
 
 import cohort_pca_ref as pref
-from test_group_regression_gpu import _cohort, _same_bits, _sphere_atlas
+from cohort_cases import cohort as _cohort, dev, same_bits, sphere_atlas
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +29,6 @@ OWN = 4                                           # kOwn: rows and columns per t
 VERTS = (1, 511, 512, 513, 1025, 1537)            # both sides of a chunk (512); several chunks with a short last one
 KNEES = (2, 3, T - 1, T, T + 1, 2 * T + 2)
 GATE = 1e-10
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()              # a copy: the cached cases are read-only
 
 
 @functools.lru_cache(maxsize=None)
@@ -62,7 +58,7 @@ def _case(N, V, masked):
 
 def _whiten(Y, mask, mean, rw, norm2=True):
     from oai_analysis_2_amd import ops
-    return ops.cohort_whiten(_dev(Y), None if mask is None else _dev(mask), _dev(mean), _dev(rw), return_norm2=norm2)
+    return ops.cohort_whiten(dev(Y), None if mask is None else dev(mask), dev(mean), dev(rw), return_norm2=norm2)
 
 
 @pytest.mark.parametrize("masked", (False, True))
@@ -74,19 +70,19 @@ def test_whiten_cross_and_combine_equal_the_restatement_to_the_bit(N, V, masked)
     if V >= 8:
         assert np.isnan(mean[3]) and (A[:, [3, 5]] == 0.0).all() and A[N // 2, 6] == 0.0 and np.isfinite(A).all()
     a_d, n2_d = _whiten(Y, mask, mean, rw)
-    _same_bits(a_d, A, "whitened")
-    _same_bits(n2_d, norm2, "norm2")
-    _same_bits(_whiten(Y, mask, mean, rw, norm2=False), A, "whitened, no norm2")
+    same_bits(a_d, A, "whitened")
+    same_bits(n2_d, norm2, "norm2")
+    same_bits(_whiten(Y, mask, mean, rw, norm2=False), A, "whitened, no norm2")
     walk = ops.rows_cross(a_d)
     ws = ops.rows_cross_workspace(N, N, V, a_d.device)
     assert ws is not None and ws.numel() == ((N + T - 1) // T) ** 2 * ((V + 511) // 512) * T * T * 8
     split = ops.rows_cross(a_d, workspace=ws)
-    _same_bits(walk, G, "Gram matrix, walk form")
-    _same_bits(split, G, "Gram matrix, split form")
+    same_bits(walk, G, "Gram matrix, walk form")
+    same_bits(split, G, "Gram matrix, split form")
     assert torch.equal(walk, walk.T) and np.array_equal(G.diagonal(), norm2)
     K = min(5, N)
     coef = np.random.default_rng([N, V]).normal(size=(K, N))
-    _same_bits(ops.rows_combine(_dev(coef), a_d), pref.combine(coef, A), "combine")
+    same_bits(ops.rows_combine(dev(coef), a_d), pref.combine(coef, A), "combine")
 
 
 @pytest.mark.parametrize("n_a,n_b,V", ((T + 6, 2 * T + 2, 1025), (2 * T + 1, 3, 513), (1, T + 1, 1537), (5, 1, 1)))
@@ -96,16 +92,16 @@ def test_rectangular_cross_in_both_forms(n_a, n_b, V):
     a = rng.normal(size=(n_a, V)) * 10.0 ** rng.integers(-3, 4, size=(n_a, V))
     b = rng.normal(size=(n_b, V)) * 10.0 ** rng.integers(-3, 4, size=(n_b, V))
     want = pref.ordered_dot(a, b)
-    a_d, b_d = _dev(a), _dev(b)
-    _same_bits(ops.rows_cross(a_d, b_d), want, "walk")
-    _same_bits(ops.rows_cross(a_d, b_d, workspace=ops.rows_cross_workspace(n_a, n_b, V, a_d.device)), want, "split")
-    _same_bits(ops.rows_cross(b_d, a_d), np.ascontiguousarray(want.T), "swapped")
+    a_d, b_d = dev(a), dev(b)
+    same_bits(ops.rows_cross(a_d, b_d), want, "walk")
+    same_bits(ops.rows_cross(a_d, b_d, workspace=ops.rows_cross_workspace(n_a, n_b, V, a_d.device)), want, "split")
+    same_bits(ops.rows_cross(b_d, a_d), np.ascontiguousarray(want.T), "swapped")
 
 
 def test_walk_and_split_agree_run_to_run_and_the_mirror_is_a_computed_triangle():
     from oai_analysis_2_amd import ops
     N, V = 2 * T + 2, 1537
-    a_d = _dev(_case(N, V, True)[4])
+    a_d = dev(_case(N, V, True)[4])
     ws = ops.rows_cross_workspace(N, N, V, a_d.device)
     walk = [ops.rows_cross(a_d) for _ in range(2)]
     split = [ops.rows_cross(a_d, workspace=ws) for _ in range(2)]
@@ -150,14 +146,14 @@ def _study():
     """32 knees on the 642-vertex icosphere (two chunks: 512 + 130): two planted modes, x and y of the vertex (orthogonal under the area
     inner product up to the mesh's asymmetry) with amplitudes 1.0 and 0.5 mm, noise of 0.05 mm, 10 % missing; the fitted cohort, the
     model with four components and the restatement's fit."""
-    atlas = _sphere_atlas()
+    atlas = sphere_atlas()
     verts = np.asarray(atlas.inner["FC"].verts, np.float64) / 20.0
     rng = np.random.default_rng(2024)
     planted = np.stack([verts[:, 0], verts[:, 1]])
     amp = rng.normal(size=(N_KNEES, 2)) * np.array([1.0, 0.5])
     Y = (2.5 + amp @ planted + 0.05 * rng.normal(size=(N_KNEES, verts.shape[0]))).astype(np.float32)
     mask = rng.random(Y.shape) >= 0.10
-    cohort = _cohort(atlas, Y, mask)
+    cohort = _cohort(atlas, Y, mask=mask, chunk=7)
     areas = np.asarray(cohort.vertex_areas(), np.float64)
     for a in (Y, mask, planted, areas):
         a.setflags(write=False)
@@ -169,11 +165,11 @@ def test_fit_equals_the_restatement_to_the_bit_and_finds_the_planted_modes():
     atlas, cohort, Y, mask, planted, areas, pca, want = _study()
     assert isinstance(pca, stats.ThicknessPCA) and pca.n_components == 4 and pca.ids == cohort.ids and pca.n_excluded == want.n_excluded == 0
     for name in ("mean", "singular_values", "explained_variance", "explained_variance_ratio", "scores", "modes_mm"):
-        _same_bits(getattr(pca, name), getattr(want, name), name)
-    _same_bits(pca.modes_w, want.modes_w, "root-weighted modes")
-    _same_bits(pca.root_weights, want.rw, "root weights")
-    _same_bits(pca.weights, areas, "weights")
-    _same_bits(pca.gram_diagonal, want.G.diagonal().copy(), "diagonal of G")
+        same_bits(getattr(pca, name), getattr(want, name), name)
+    same_bits(pca.modes_w, want.modes_w, "root-weighted modes")
+    same_bits(pca.root_weights, want.rw, "root weights")
+    same_bits(pca.weights, areas, "weights")
+    same_bits(pca.gram_diagonal, want.G.diagonal().copy(), "diagonal of G")
     for c in range(2):                                                     # modes_mm is orthonormal under the area inner product
         dot = abs((pca.modes_mm[c] * areas * planted[c]).sum()) / np.sqrt((areas * planted[c] ** 2).sum())
         print(f"mode {c}: |dot| with the planted mode under the area inner product {dot:.4f}")
@@ -182,7 +178,7 @@ def test_fit_equals_the_restatement_to_the_bit_and_finds_the_planted_modes():
     assert np.abs(gram - np.eye(4)).max() <= GATE
     assert pca.explained_variance_ratio[:2].sum() > 0.9 and pca.smoothing is None and pca.ranking is None
     uniform = cohort.pca(2, weights="uniform")
-    _same_bits(uniform.scores, pref.fit(Y, mask, np.ones(Y.shape[1]), n_components=2).scores, "uniform weights")
+    same_bits(uniform.scores, pref.fit(Y, mask, np.ones(Y.shape[1]), n_components=2).scores, "uniform weights")
     ranked = cohort.ranked("inormal")
     assert ranked.pca(2).ranking is ranked.ranking                        # the settings of a derived cohort travel with the model
 
@@ -193,10 +189,10 @@ def test_min_valid_excludes_vertices_on_the_device():
     mask[:, 9] = False
     mask[:, 21] = np.arange(N_KNEES) == 4
     mask[:, 500:520] &= (np.arange(N_KNEES) < 3)[:, None]
-    got, want = _cohort(atlas, Y, mask).pca(3, min_valid=4), pref.fit(Y, mask, areas, n_components=3, min_valid=4)
+    got, want = _cohort(atlas, Y, mask=mask, chunk=7).pca(3, min_valid=4), pref.fit(Y, mask, areas, n_components=3, min_valid=4)
     assert got.n_excluded == want.n_excluded == 22 and np.isnan(got.mean[9]) and np.isnan(got.modes_mm[:, 9]).all()
     for name in ("mean", "singular_values", "scores", "modes_mm", "explained_variance_ratio"):
-        _same_bits(getattr(got, name), getattr(want, name), name)
+        same_bits(getattr(got, name), getattr(want, name), name)
     assert np.isfinite(got.scores).all() and np.isfinite(got.singular_values).all()
 
 
@@ -204,7 +200,7 @@ def test_transform_member_scores_and_reconstruct():
     atlas, cohort, Y, mask, planted, areas, pca, want = _study()
     rec, ref = pca.transform(cohort), pref.transform(want, Y, mask)
     for name in ("scores", "t2", "q", "q_fraction"):
-        _same_bits(getattr(rec, name), getattr(ref, name), "transform " + name)
+        same_bits(getattr(rec, name), getattr(ref, name), "transform " + name)
     assert np.array_equal(rec.n_missing, ref.n_missing) and np.array_equal(rec.n_missing, (~mask).sum(axis=1)) and rec.ids == cohort.ids
     largest = np.abs(pca.scores).max()
     e_scores = np.abs(rec.scores - pca.scores).max() / largest

@@ -2,26 +2,18 @@
 bad arguments with a status and a message -- no GPU is touched before the checks."""
 import ctypes as C
 import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, ROOT, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_graph_smooth_workspace_bytes", "oai_graph_smooth")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
-    section = raw[raw.index("\n * Surface smoothing ("):]
+    raw = check_symbols(NEW)
+    section = _section(raw, "\n * Surface smoothing (")
     for words in ("csrc/graph_smooth.hip", "tests/graph_smooth_ref.py", "skipped", "ascending", "pinned to no implementation",
                   "num = num + w[e] * x_s[j]", "ok = (fill ? 1 : m_s[i]) && den > 0", "never multiplied by 0"):
         assert words in section, words
@@ -32,11 +24,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
 
 
 BIG = 1 << 40                                                             # a workspace size no check below can find too small

@@ -6,16 +6,9 @@ import numpy as np
 import pytest
 
 import graph_smooth_ref as sref
+from cohort_cases import same_bits
 from oai_analysis_2_amd import stats
 from oai_analysis_2_amd.stats import surface_edge_d2, surface_edge_weights, surface_step_variance, sweeps_for_fwhm
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    if got.dtype == np.float64:
-        assert np.array_equal(np.isnan(got), np.isnan(want)), what
-        got, want = np.where(np.isnan(got), 0.0, got).view(np.int64), np.where(np.isnan(want), 0.0, want).view(np.int64)
-    assert np.array_equal(got, want), what
 
 
 def _sphere_graph(level=1):
@@ -41,8 +34,8 @@ def test_the_vectorised_restatement_equals_the_loop_form_to_the_bit():
             for self_weight in (None, sw):
                 got, got_m = sref.smooth(x, mask, off, nbr, w, self_weight, K, fill)
                 want, want_m = sref.smooth_loop(x, mask, off, nbr, w, self_weight, K, fill)
-                _same_bits(got_m, want_m, f"mask fill={fill} K={K}")
-                _same_bits(got, want, f"values fill={fill} K={K}")
+                same_bits(got_m, want_m, f"mask fill={fill} K={K}")
+                same_bits(got, want, f"values fill={fill} K={K}")
                 assert not np.isnan(got).any()
                 if not fill:
                     assert not (got_m & ~mask.astype(bool)).any()

@@ -2,7 +2,6 @@
 the result of IEEE multiply, add and divide in a stated order -- and ``ThicknessCohort.smoothed`` / ``SurfaceSmoother`` of
 oai_analysis_2_amd.stats end to end on a small sphere."""
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -10,36 +9,16 @@ import torch
 
 import graph_smooth_ref as sref
 import group_stats_ref as gref
+from cohort_cases import cohort as _cohort, dev, icosphere, same_bits, sphere_atlas, sphere_graph
 
 pytestmark = pytest.mark.gpu
 
 GARBAGE = np.array([np.nan, np.inf, 1e300])         # written under every 0 mask bit of the input: none of it may show in the output
 
 
-def _same_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype.kind == "f":
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-        as_int = np.int64 if got.dtype == np.float64 else np.int32
-        got, want = np.where(np.isnan(got), 0, got).view(as_int), np.where(np.isnan(want), 0, want).view(as_int)
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
-
-
-def _up(a):
-    return torch.from_numpy(np.array(a)).cuda()                 # a copy: the cached cases are read-only
-
-
-@functools.lru_cache(maxsize=None)
-def _sphere():
-    return sref.icosphere(3)
-
-
 @functools.lru_cache(maxsize=None)
 def _graph(name):
     """(offsets, neighbours) on the host; the sphere's are those of ``mesh_processing.vertex_adjacency_device``."""
-    from oai_analysis_2_amd import mesh_processing as mp
     if name == "path_3000":
         return sref.path_graph(3000)
     if name == "star_700":                            # a hub whose degree exceeds any unroll and any wave
@@ -58,9 +37,7 @@ def _graph(name):
         off, nbr = gref.hostile_graph()
         assert off[0] < 0 and off[-1] > len(nbr) and (nbr < 0).any() and (nbr >= len(off) - 1).any() and 5 in nbr[off[5]:off[6]]
         return off, nbr
-    verts, faces = _sphere()
-    off_d, nbr_d = mp.vertex_adjacency_device(len(verts), torch.from_numpy(faces).cuda())
-    return off_d.cpu().numpy(), nbr_d.cpu().numpy()
+    return sphere_graph()
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,16 +69,16 @@ def test_smoothing_equals_the_restatement_to_the_bit(graph, R):
     from oai_analysis_2_amd import ops
     off, nbr = _graph(graph)
     dirty, clean, mask, w, sw = _case(graph, R)
-    off_d, nbr_d, w_d, sw_d = _up(off), _up(nbr), _up(w), _up(sw)
-    dirty_d, clean_d, mask_d = _up(dirty), _up(clean), _up(mask)
+    off_d, nbr_d, w_d, sw_d = dev(off), dev(nbr), dev(w), dev(sw)
+    dirty_d, clean_d, mask_d = dev(dirty), dev(clean), dev(mask)
     dropped = 0
     for K in (1, 2, 7):                               # both parities of the ping-pong
         for fill in (False, True):
             where = f"{graph} R={R} K={K} fill={fill}"
             want, want_m = sref.smooth(dirty, mask, off, nbr, w, sw, K, fill)
             got, got_m = ops.graph_smooth(dirty_d, off_d, nbr_d, w_d, mask=mask_d, self_weights=sw_d, sweeps=K, fill=fill)
-            _same_bits(got_m, want_m, where + " mask")
-            _same_bits(got, want, where + " values")
+            same_bits(got_m, want_m, where + " mask")
+            same_bits(got, want, where + " values")
             out = got.cpu().numpy()
             assert np.isfinite(out).all() and np.abs(out).max() < 10.0, where          # nothing of what lay under a 0 mask bit
             assert (out[want_m == 0] == 0).all() and not np.signbit(out[want_m == 0]).any(), where
@@ -116,8 +93,8 @@ def test_smoothing_equals_the_restatement_to_the_bit(graph, R):
             want, want_m = sref.smooth(values_h, mask_h, off, nbr, w, sw_h, 2, fill)
             got, got_m = ops.graph_smooth(values_t, off_d, nbr_d, w_d, mask=mask_t, self_weights=sw_t, sweeps=2, fill=fill)
             where = f"{graph} R={R} mask={'yes' if mask_h is not None else 'null'} self={'yes' if sw_h is not None else 'null'} fill={fill}"
-            _same_bits(got_m, want_m, where + " mask")
-            _same_bits(got, want, where + " values")
+            same_bits(got_m, want_m, where + " mask")
+            same_bits(got, want, where + " values")
 
 
 def test_a_valid_nan_propagates_and_an_invalid_one_does_not():
@@ -129,9 +106,9 @@ def test_a_valid_nan_propagates_and_an_invalid_one_does_not():
     mask[1, 4] = 0
     w = np.ones(len(nbr))
     want, want_m = sref.smooth(x, mask, off, nbr, w, None, 2, False)
-    got, got_m = ops.graph_smooth(_up(x), _up(off), _up(nbr), _up(w), mask=_up(mask), sweeps=2)
-    _same_bits(got, want, "values")
-    _same_bits(got_m, want_m, "mask")
+    got, got_m = ops.graph_smooth(dev(x), dev(off), dev(nbr), dev(w), mask=dev(mask), sweeps=2)
+    same_bits(got, want, "values")
+    same_bits(got_m, want_m, "mask")
     assert np.isnan(want[0, 2:7]).all() and not np.isnan(want[0, :2]).any() and not np.isnan(want[1]).any() and want_m[1, 4] == 0
 
 
@@ -142,36 +119,36 @@ def test_fill_grows_the_valid_set_by_one_ring_per_sweep():
     x[0, 50] = 3.0
     mask = np.zeros((1, 101), np.uint8)
     mask[0, 50] = 1
-    args = (_up(x), _up(off), _up(nbr), _up(np.ones(len(nbr))))
-    filled, filled_m = ops.graph_smooth(*args, mask=_up(mask), sweeps=7, fill=True)
-    kept, kept_m = ops.graph_smooth(*args, mask=_up(mask), sweeps=7, fill=False)
+    args = (dev(x), dev(off), dev(nbr), dev(np.ones(len(nbr))))
+    filled, filled_m = ops.graph_smooth(*args, mask=dev(mask), sweeps=7, fill=True)
+    kept, kept_m = ops.graph_smooth(*args, mask=dev(mask), sweeps=7, fill=False)
     assert int(filled_m.sum()) == 15 and filled_m[0, 43:58].all() and int(kept_m.sum()) == 1 and kept_m[0, 50] == 1
     assert kept[0, 50] == 3.0 and (filled[0, 43:58] == 3.0).all() and float(filled.abs().sum()) == 45.0
-    _same_bits(filled, sref.smooth(x, mask, off, nbr, np.ones(len(nbr)), None, 7, True)[0], "filled")
+    same_bits(filled, sref.smooth(x, mask, off, nbr, np.ones(len(nbr)), None, 7, True)[0], "filled")
 
 
 def test_in_place_row_by_row_and_twice_give_the_same_bits():
     from oai_analysis_2_amd import ops
     off, nbr = _graph("icosphere")
     dirty, _, mask, w, sw = _case("icosphere", 17)
-    off_d, nbr_d, w_d, sw_d = _up(off), _up(nbr), _up(w), _up(sw)
+    off_d, nbr_d, w_d, sw_d = dev(off), dev(nbr), dev(w), dev(sw)
     for fill in (False, True):
         kwargs = dict(self_weights=sw_d, sweeps=3, fill=fill)
-        ref, ref_m = ops.graph_smooth(_up(dirty), off_d, nbr_d, w_d, mask=_up(mask), **kwargs)
+        ref, ref_m = ops.graph_smooth(dev(dirty), off_d, nbr_d, w_d, mask=dev(mask), **kwargs)
         ref, ref_m = ref.cpu().numpy(), ref_m.cpu().numpy()
-        again, again_m = ops.graph_smooth(_up(dirty), off_d, nbr_d, w_d, mask=_up(mask), **kwargs)
-        _same_bits(again, ref, "second run")
-        _same_bits(again_m, ref_m, "second run mask")
-        values_d, mask_d = _up(dirty), _up(mask)
+        again, again_m = ops.graph_smooth(dev(dirty), off_d, nbr_d, w_d, mask=dev(mask), **kwargs)
+        same_bits(again, ref, "second run")
+        same_bits(again_m, ref_m, "second run mask")
+        values_d, mask_d = dev(dirty), dev(mask)
         got, got_m = ops.graph_smooth(values_d, off_d, nbr_d, w_d, mask=mask_d, out=values_d, out_mask=mask_d, **kwargs)
         assert got.data_ptr() == values_d.data_ptr() and got_m.data_ptr() == mask_d.data_ptr()
-        _same_bits(values_d, ref, "in place")
-        _same_bits(mask_d, ref_m, "in place mask")
-        values_d, mask_d = _up(dirty), _up(mask)
+        same_bits(values_d, ref, "in place")
+        same_bits(mask_d, ref_m, "in place mask")
+        values_d, mask_d = dev(dirty), dev(mask)
         for r in range(len(dirty)):                                        # every row as a tile of its own
             got, got_m = ops.graph_smooth(values_d[r:r + 1], off_d, nbr_d, w_d, mask=mask_d[r:r + 1], **kwargs)
-            _same_bits(got, ref[r:r + 1], f"row {r} alone")
-            _same_bits(got_m, ref_m[r:r + 1], f"row {r} alone, mask")
+            same_bits(got, ref[r:r + 1], f"row {r} alone")
+            same_bits(got_m, ref_m[r:r + 1], f"row {r} alone, mask")
 
 
 def test_atlas_scale_path():
@@ -186,14 +163,14 @@ def test_atlas_scale_path():
     w = rng.uniform(0.0, 2.0, len(nbr))
     for fill in (False, True):
         want, want_m = sref.smooth(x, mask, off, nbr, w, None, K, fill)
-        got, got_m = ops.graph_smooth(_up(x), _up(off), _up(nbr), _up(w), mask=_up(mask), sweeps=K, fill=fill)
-        _same_bits(got_m, want_m, f"fill={fill} mask")
-        _same_bits(got, want, f"fill={fill} values")
+        got, got_m = ops.graph_smooth(dev(x), dev(off), dev(nbr), dev(w), mask=dev(mask), sweeps=K, fill=fill)
+        same_bits(got_m, want_m, f"fill={fill} mask")
+        same_bits(got, want, f"fill={fill} values")
 
 
 def test_the_wrapper_refuses_what_the_kernel_would():
     from oai_analysis_2_amd import ops
-    off, nbr = (_up(a) for a in sref.path_graph(10))
+    off, nbr = (dev(a) for a in sref.path_graph(10))
     tile = torch.zeros((2, 10), dtype=torch.float64, device="cuda")
     w = torch.ones(18, dtype=torch.float64, device="cuda")
     for kwargs, match in ((dict(sweeps=0), "sweeps"), (dict(sweeps=4097), "sweeps"),
@@ -213,16 +190,10 @@ def test_the_wrapper_refuses_what_the_kernel_would():
 N_E2E, FWHM_E2E = 24, 15.0
 
 
-def _sphere_atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _sphere()
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(40.0), faces)}, device=torch.device("cuda", 0))
-
-
 @functools.lru_cache(maxsize=None)
 def _knees():
     """24 float32 knees on the sphere with 10 % of the entries missing (NaN)."""
-    V = len(_sphere()[0])
+    V = len(icosphere()[0])
     rng = np.random.default_rng(2025)
     Y = (2.0 + 0.3 * rng.normal(size=(N_E2E, V))).astype(np.float32)
     Y[rng.random((N_E2E, V)) < 0.1] = np.nan
@@ -230,20 +201,12 @@ def _knees():
     return Y
 
 
-def _cohort(atlas, Y):
-    from oai_analysis_2_amd import stats
-    cohort = stats.ThicknessCohort(atlas, "FC", chunk=5)
-    for i, row in enumerate(Y):
-        cohort.add_vector(row, f"knee-{i}")
-    return cohort
-
-
 @functools.lru_cache(maxsize=None)
 def _restated(missing):
     """(float32 values with 0 where missing, uint8 mask, sweeps) of the restatement, with the host helpers' weights and sweep count."""
     from oai_analysis_2_amd import stats
     off, nbr = _graph("icosphere")
-    verts = _sphere()[0] * np.float32(40.0)
+    verts = icosphere()[0] * np.float32(40.0)
     sigma_step = stats.mean_edge_length(verts, off, nbr)
     w = stats.surface_edge_weights(verts, off, nbr, sigma_step)
     s = stats.surface_step_variance(off, nbr, w, stats.surface_edge_d2(verts, off, nbr))
@@ -255,15 +218,15 @@ def _restated(missing):
 
 def test_a_smoothed_cohort_is_the_restatement_and_the_tests_take_it():
     from oai_analysis_2_amd import stats
-    atlas, Y = _sphere_atlas(), _knees()
-    cohort = _cohort(atlas, Y)
+    atlas, Y = sphere_atlas(scale=40.0), _knees()
+    cohort = _cohort(atlas, Y, [f"knee-{i}" for i in range(len(Y))])
     before, before_m = cohort.values.clone(), cohort.mask.clone()
     for missing in ("keep", "fill"):
         want, want_m, K, sigma_step, s_mean = _restated(missing)
         assert K >= 2
         smooth = cohort.smoothed(fwhm_mm=FWHM_E2E, missing=missing)
-        _same_bits(smooth.mask, want_m, f"{missing} mask")
-        _same_bits(smooth.values, want, f"{missing} values")
+        same_bits(smooth.mask, want_m, f"{missing} mask")
+        same_bits(smooth.values, want, f"{missing} values")
         assert smooth.ids == cohort.ids and smooth.kind == "FC" and smooth.atlas is atlas and len(smooth) == N_E2E
         assert smooth.smoothing == stats.Smoothing(FWHM_E2E, np.sqrt(8 * np.log(2) * K * s_mean / 2), K, sigma_step, missing)
         assert smooth.smoothing.sweeps == K and abs(smooth.smoothing.achieved_fwhm_mm / FWHM_E2E - 1) < 0.25 and cohort.smoothing is None
@@ -277,34 +240,34 @@ def test_a_smoothed_cohort_is_the_restatement_and_the_tests_take_it():
     want, want_m, K, _, _ = _restated("keep")
     assert stats.smoothing_batch(cohort.n_verts, N_E2E, 7 * cohort.n_verts * stats._SMOOTH_BYTES) == 7
     small = cohort.smoothed(fwhm_mm=FWHM_E2E, batch=7)
-    _same_bits(small.values, want, "batches of seven, values")
-    _same_bits(small.mask, want_m, "batches of seven, mask")
+    same_bits(small.values, want, "batches of seven, values")
+    same_bits(small.mask, want_m, "batches of seven, mask")
     # the smoothed cohort goes into the test as it is
     smooth = cohort.smoothed(sweeps=K)
-    _same_bits(smooth.values, want, "by sweeps")
+    same_bits(smooth.values, want, "by sweeps")
     assert smooth.smoothing.fwhm_mm is None and smooth.smoothing.sweeps == K
     groups = np.arange(N_E2E) < N_E2E // 2
     res = stats.two_sample_test(smooth, groups, n_permutations=50, seed=4)
     t_ref = gref.permutation_t(gref.prepare(want, want_m), want_m, stats.label_permutations(groups, 50, seed=4).rows(), gref.TWO_SAMPLE)
-    _same_bits(res.t, t_ref[0], "t of the smoothed cohort")
+    same_bits(res.t, t_ref[0], "t of the smoothed cohort")
     # smoothing does what it is for: the noise per vertex falls
     assert smooth.summary()["std"].mean() < 0.7 * cohort.summary()["std"].mean()
 
 
 def test_the_smoother_on_vectors_matrices_and_an_impulse():
     from oai_analysis_2_amd import stats
-    atlas, Y = _sphere_atlas(), _knees()
+    atlas, Y = sphere_atlas(scale=40.0), _knees()
     want, want_m, K, sigma_step, _ = _restated("keep")
     smoother = stats.SurfaceSmoother(atlas, "FC", FWHM_E2E)
     assert smoother.sweeps == K and smoother.sigma_step == sigma_step and smoother.fwhm_mm == FWHM_E2E
     one = smoother(Y[3])                                                   # one numpy vector with NaNs: NaN at the same places in keep mode
     assert isinstance(one, np.ndarray) and one.dtype == np.float32 and one.shape == Y[3].shape
     assert np.array_equal(np.isnan(one), np.isnan(Y[3]))
-    _same_bits(np.nan_to_num(one), want[3], "one vector")
+    same_bits(np.nan_to_num(one), want[3], "one vector")
     many = smoother(torch.from_numpy(Y.astype(np.float64)).cuda())        # a float64 device matrix: not rounded to float32
     assert isinstance(many, torch.Tensor) and many.is_cuda and many.dtype == torch.float64 and tuple(many.shape) == Y.shape
     assert np.array_equal(np.isnan(many.cpu().numpy()), np.isnan(Y))
-    _same_bits(np.nan_to_num(many.cpu().numpy()).astype(np.float32), want, "matrix")
+    same_bits(np.nan_to_num(many.cpu().numpy()).astype(np.float32), want, "matrix")
     valid = np.ones(Y.shape[1], np.uint8)
     valid[:100] = 0
     assert np.isnan(smoother(Y[3], valid=valid)[:100]).all()

@@ -1,28 +1,21 @@
 """CPU: the TFCE entry points of the C ABI (include/oai_hip.h: oai_graph_tfce) are exported by the built library and refuse bad arguments
 with a status and a message -- no GPU is touched before the checks -- and the Python layer refuses the same before the library."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_graph_tfce_workspace_bytes", "oai_graph_tfce")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
-    section = raw[raw.index("Threshold-free cluster enhancement"):]
+    raw = check_symbols(NEW)
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)                      # a #define counts outside the comments only
+    section = _section(raw, "Threshold-free cluster enhancement")
     for words in ("csrc/graph_tfce.hip", "tests/graph_tfce_ref.py", "k = K(v) down to 1", "c_k = (eE * hH) * dh", "NOT pinned to any implementation",
                   "a >= (double)(max_steps + 1) * dh"):
         assert words in section, words
@@ -35,14 +28,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_graph_tfce_argument_checks(lib):

@@ -4,16 +4,7 @@ import numpy as np
 import pytest
 
 import graph_tfce_ref as tref
-
-
-def _bits(x):
-    x = np.asarray(x, np.float64)
-    return np.where(np.isnan(x), 0.0, x).view(np.int64), np.isnan(x)
-
-
-def _same_bits(got, want):
-    (g, gn), (w, wn) = _bits(got), _bits(want)
-    return np.array_equal(gn, wn) and np.array_equal(g, w)
+from cohort_cases import same_bits
 
 
 def _plateau(L, T, pad=7):
@@ -34,7 +25,7 @@ def test_a_plateau_gives_the_sum_written_out_by_hand():
     assert (got[0, inside] == want).all() and clipped[0] == 0
     outside = np.ones(len(row), bool)
     outside[inside] = False
-    assert _same_bits(got[0, outside], np.zeros(outside.sum()))            # +0.0, not -0.0
+    same_bits(got[0, outside], np.zeros(outside.sum()), "outside the plateau")       # +0.0, not -0.0
 
 
 @pytest.mark.parametrize("E", [0.5, 1.0])
@@ -113,7 +104,8 @@ def test_renumbering_the_vertices_permutes_the_output_bit_for_bit(E, H):
     for weights, weights2 in ((None, None), (w, w2)):
         got, clip = tref.tfce(tile, off, nbr, dh=0.25, E=E, H=H, weights=weights, unit=2.0 ** -20, max_steps=40)
         got2, clip2 = tref.tfce(tile2, off2, nbr2, dh=0.25, E=E, H=H, weights=weights2, unit=2.0 ** -20, max_steps=40)
-        assert _same_bits(got2[:, new_of_old], got) and np.array_equal(clip, clip2) and clip.tolist() == [0, 1, 0]
+        same_bits(got2[:, new_of_old], got, "renumbered tfce")
+        assert np.array_equal(clip, clip2) and clip.tolist() == [0, 1, 0]
         assert np.abs(got[2]).max() > 0
 
 
@@ -126,7 +118,8 @@ def test_flipping_the_sign_of_t_flips_the_sign_of_tfce_bit_for_bit():
     assert (tile != 0).all()
     got, clip = tref.tfce(tile, off, nbr, dh=0.1, max_steps=50)
     neg, clip_neg = tref.tfce(-tile, off, nbr, dh=0.1, max_steps=50)
-    assert _same_bits(neg, -got) and np.array_equal(clip, clip_neg)
+    same_bits(neg, -got, "tfce of -t")
+    assert np.array_equal(clip, clip_neg)
     assert (np.signbit(got) == np.signbit(tile))[~np.isnan(tile)].all()
     zeros, _ = tref.tfce(np.array([[0.0, -0.0, 0.05, -0.05]]), *tref.path_graph(4), dh=0.1)
     assert np.signbit(zeros[0]).tolist() == [False, False, False, True] and (zeros == 0).all()

@@ -10,6 +10,7 @@ import torch
 
 import graph_tfce_ref as tref
 import group_stats_ref as gref
+from cohort_cases import cohort as _cohort, painted, same_bits, same_result, sphere_atlas, sphere_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -18,50 +19,10 @@ MODES = ((1.0, 2.0), (1.0, 1.0), (0.5, 2.0), (0.5, 1.0))
 UNIT = 2.0 ** -20
 
 
-def _same_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype == np.float64:
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-        got, want = np.where(np.isnan(got), 0.0, got).view(np.int64), np.where(np.isnan(want), 0.0, want).view(np.int64)
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
-
-
-@functools.lru_cache(maxsize=None)
-def _icosphere(level=3):
-    """(verts float32 [n, 3] on the unit sphere, faces int32 [m, 3]): 642 vertices and 1280 faces at level 3."""
-    g = (1 + 5 ** 0.5) / 2
-    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
-    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
-         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
-    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
-    for _ in range(level):
-        mid, nf = {}, []
-
-        def midpoint(a, b):
-            key = (min(a, b), max(a, b))
-            if key not in mid:
-                p = v[a] + v[b]
-                v.append(p / np.linalg.norm(p))
-                mid[key] = len(v) - 1
-            return mid[key]
-        for a, b, c in f:
-            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
-            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
-        f = nf
-    return np.asarray(v, np.float32), np.asarray(f, np.int32)
-
-
 @functools.lru_cache(maxsize=None)
 def _graph(name):
     """(offsets, neighbours) on the host; the sphere's are those of ``mesh_processing.vertex_adjacency_device``."""
-    from oai_analysis_2_amd import mesh_processing as mp
-    if name == "path_3000":
-        return tref.path_graph(3000)
-    verts, faces = _icosphere()
-    off_d, nbr_d = mp.vertex_adjacency_device(len(verts), torch.from_numpy(faces).cuda())
-    return off_d.cpu().numpy(), nbr_d.cpu().numpy()
+    return tref.path_graph(3000) if name == "path_3000" else sphere_graph()
 
 
 def _hand_tile(V, seed):
@@ -136,17 +97,17 @@ def test_tfce_equals_the_restatement_to_the_bit(graph, weighted):
             assert len(np.unique(want[6])) == 2 and len(np.unique(want[3])) >= STEPS - 2 and want[5, 110] < want[5, 150]
         got, clipped = ops.graph_tfce(tile_d, off_d, nbr_d, E=E, H=H, **kwargs)
         where = f"{graph} E={E} H={H}"
-        _same_bits(got, want, f"{where} tfce")
-        _same_bits(clipped, want_clipped, f"{where} clipped")
+        same_bits(got, want, f"{where} tfce")
+        same_bits(clipped, want_clipped, f"{where} clipped")
         for r in range(len(tile)):                                         # every row as a tile of its own
             got, clipped = ops.graph_tfce(tile_d[r:r + 1], off_d, nbr_d, E=E, H=H, **kwargs)
-            _same_bits(got, want[r:r + 1], f"{where} tfce of row {r} alone")
-            _same_bits(clipped, want_clipped[r:r + 1], f"{where} clipped of row {r} alone")
+            same_bits(got, want[r:r + 1], f"{where} tfce of row {r} alone")
+            same_bits(clipped, want_clipped[r:r + 1], f"{where} clipped of row {r} alone")
     # into the caller's buffers
     out, clip = torch.full((8, V), 7.0, dtype=torch.float64, device="cuda"), torch.full((8,), -5, dtype=torch.int32, device="cuda")
     got, clipped = ops.graph_tfce(tile_d, off_d, nbr_d, E=1.0, H=2.0, out=out, clipped=clip, **kwargs)
     assert got.data_ptr() == out.data_ptr() and clipped.data_ptr() == clip.data_ptr()
-    _same_bits(out, _reference(graph, weighted, 1.0, 2.0)[0], "out")
+    same_bits(out, _reference(graph, weighted, 1.0, 2.0)[0], "out")
 
 
 def test_a_hostile_graph_is_read_as_the_restatement_reads_it():
@@ -165,8 +126,8 @@ def test_a_hostile_graph_is_read_as_the_restatement_reads_it():
             kwargs = dict(dh=DH, E=E, H=H, unit=UNIT if weights is not None else 1.0, max_steps=STEPS)
             want, want_clipped = tref.tfce(tile, off, nbr, weights=weights, **kwargs)
             got, clipped = ops.graph_tfce(tile_d, off_d, nbr_d, weights=None if weights is None else torch.from_numpy(weights.copy()).cuda(), **kwargs)
-            _same_bits(got, want, f"hostile E={E} H={H} tfce")
-            _same_bits(clipped, want_clipped, "hostile clipped")
+            same_bits(got, want, f"hostile E={E} H={H} tfce")
+            same_bits(clipped, want_clipped, "hostile clipped")
     assert len(np.unique(want[1])) > 3                                     # more than one component and an isolated vertex
 
 
@@ -184,8 +145,8 @@ def test_one_row_of_one_and_of_sixty_five_vertices(V):
             got, clipped = ops.graph_tfce(torch.from_numpy(tile).cuda(), off_d, nbr_d, dh=DH, E=E, H=H, max_steps=STEPS,
                                           weights=None if weights is None else torch.from_numpy(weights.copy()).cuda(),
                                           unit=UNIT if weights is not None else 1.0)
-            _same_bits(got, want, f"V={V} E={E} H={H} tfce")
-            _same_bits(clipped, want_clipped, f"V={V} clipped")
+            same_bits(got, want, f"V={V} E={E} H={H} tfce")
+            same_bits(clipped, want_clipped, f"V={V} clipped")
             assert want[0, 0] < 0
 
 
@@ -204,8 +165,8 @@ def test_renumbering_the_vertices_permutes_the_device_output_bit_for_bit():
         kwargs = dict(dh=DH, E=0.5, H=2.0, unit=UNIT, max_steps=STEPS)
         got, clip = ops.graph_tfce(up(tile), up(off), up(nbr), weights=None if weights is None else up(weights), **kwargs)
         got2, clip2 = ops.graph_tfce(up(tile2), up(off2), up(nbr2), weights=None if weights2 is None else up(weights2), **kwargs)
-        _same_bits(got2.cpu().numpy()[:, new_of_old], got.cpu().numpy(), "renumbered tfce")
-        _same_bits(clip2, clip.cpu().numpy(), "renumbered clipped")
+        same_bits(got2.cpu().numpy()[:, new_of_old], got.cpu().numpy(), "renumbered tfce")
+        same_bits(clip2, clip.cpu().numpy(), "renumbered clipped")
 
 
 def test_the_wrapper_refuses_what_the_kernel_would():
@@ -222,41 +183,15 @@ def test_the_wrapper_refuses_what_the_kernel_would():
 
 
 # ---- the public interface --------------------------------------------------------------------------------------------------------------
-def _sphere_atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _icosphere()
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0))
-
-
-def _cohort(atlas, Y, ids=None):
-    from oai_analysis_2_amd import stats
-    cohort = stats.ThicknessCohort(atlas, "FC", chunk=5)
-    for i, row in enumerate(Y):
-        cohort.add_vector(row, None if ids is None else ids[i])
-    return cohort
-
-
 N_E2E, P_E2E, P_SMALL = 24, 200, 100
 TFCE_FIELDS = ("tfce", "p_tfce", "p_tfce_uncorrected", "max_tfce")
-
-
-@functools.lru_cache(maxsize=None)
-def _painted(offset):
-    """24 knees on the sphere: 2 mm + 0.1 mm noise, and ``offset`` mm more on the cap z > 0.8 for group 1 (the first twelve)."""
-    verts, _ = _icosphere()
-    cap = verts[:, 2] > 0.8
-    rng = np.random.default_rng(2024)
-    Y = (2.0 + 0.1 * rng.normal(size=(N_E2E, len(verts)))).astype(np.float32)
-    groups = np.arange(N_E2E) < N_E2E // 2
-    Y[np.ix_(groups, cap)] += np.float32(offset)
-    return Y, groups, cap
 
 
 @functools.lru_cache(maxsize=None)
 def _two_sample_t(offset, seed):
     """The restated t of every labelling of the painted cohort."""
     from oai_analysis_2_amd import stats
-    Y, groups, _ = _painted(offset)
+    Y, groups, _ = painted(offset, N_E2E)
     t = gref.permutation_t(gref.prepare(Y, None), None, stats.label_permutations(groups, P_E2E, seed=seed).rows(), gref.TWO_SAMPLE)
     t.setflags(write=False)
     return t
@@ -272,8 +207,8 @@ def _check_against(res, t_ref, P, what, **ref_kwargs):
     off, nbr = _graph("icosphere")
     want, clipped = tref.tfce(t_ref, off, nbr, **ref_kwargs)
     want_max, want_exceed = gref.reduce_tiles(want)
-    _same_bits(res.tfce, want[0], f"{what} tfce")
-    _same_bits(res.max_tfce, want_max, f"{what} max_tfce")
+    same_bits(res.tfce, want[0], f"{what} tfce")
+    same_bits(res.max_tfce, want_max, f"{what} max_tfce")
     assert np.array_equal(np.rint(res.p_tfce_uncorrected * P).astype(np.int64), want_exceed), what
     null = np.sort(want_max)
     assert np.array_equal(res.p_tfce, (P - np.searchsorted(null, np.abs(want[0]), side="left")) / float(P)), what
@@ -285,18 +220,13 @@ def _same_result(got, want, what):
     """Every field of two results of the same test: arrays to the bit, everything else (the ``clusters`` list among it) equal."""
     import dataclasses
     assert type(got) is type(want)
-    for f in dataclasses.fields(want):
-        a, b = getattr(got, f.name), getattr(want, f.name)
-        if isinstance(b, np.ndarray):
-            _same_bits(a, b, f"{what}: {f.name}")
-        else:
-            assert a == b, f"{what}: {f.name}"
+    same_result(got, {f.name: getattr(want, f.name) for f in dataclasses.fields(want)}, what)
 
 
 def test_two_sample_tfce_finds_the_weak_cap_that_max_t_misses():
     from oai_analysis_2_amd import stats
-    Y, groups, cap = _painted(0.10)
-    atlas = _sphere_atlas()
+    Y, groups, cap = painted(0.10, N_E2E)
+    atlas = sphere_atlas()
     settings = stats.TFCE(extent="vertices")
     res = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings, batch=48)
     assert res.tfce_settings == settings and res.max_tfce.shape == (P_E2E,) and res.tfce.shape == cap.shape and res.cluster_label is None
@@ -311,8 +241,8 @@ def test_two_sample_tfce_finds_the_weak_cap_that_max_t_misses():
     again = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings, batch=48)
     other = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings)
     for name in TFCE_FIELDS:
-        _same_bits(getattr(again, name), getattr(res, name), name)
-        _same_bits(getattr(other, name), getattr(res, name), name + " (default batch)")
+        same_bits(getattr(again, name), getattr(res, name), name)
+        same_bits(getattr(other, name), getattr(res, name), name + " (default batch)")
     assert again.tfce_clipped == other.tfce_clipped == 0
     # nothing else changes: the other fields are those of a run without tfce, and clusters may be asked for as well
     plain = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, batch=48)
@@ -320,13 +250,13 @@ def test_two_sample_tfce_finds_the_weak_cap_that_max_t_misses():
     both = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=settings, batch=48, cluster_threshold=2.5)
     only = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, batch=48, cluster_threshold=2.5)
     for name in ("t", "n1", "n2", "mean_difference", "p_uncorrected", "p_fwer", "max_abs"):
-        _same_bits(getattr(res, name), getattr(plain, name), name + " (with and without tfce)")
-        _same_bits(getattr(both, name), getattr(plain, name), name + " (with tfce and clusters)")
+        same_bits(getattr(res, name), getattr(plain, name), name + " (with and without tfce)")
+        same_bits(getattr(both, name), getattr(plain, name), name + " (with tfce and clusters)")
     for name in ("cluster_label", "max_extent"):
-        _same_bits(getattr(both, name), getattr(only, name), name)
+        same_bits(getattr(both, name), getattr(only, name), name)
     assert both.clusters == only.clusters
     for name in TFCE_FIELDS:
-        _same_bits(getattr(both, name), getattr(res, name), name + " (with clusters)")
+        same_bits(getattr(both, name), getattr(res, name), name + " (with clusters)")
     assert res.image(SimpleNamespace(image=lambda vec, kind: vec), "p_tfce").dtype == np.float32
     # the batches are one loop for every option: several batches with a ragged last one, and the default batch, give the bits of ``both``
     assert both.clusters and both.tfce is not None and both.max_extent is not None
@@ -337,8 +267,8 @@ def test_two_sample_tfce_finds_the_weak_cap_that_max_t_misses():
 
 def test_extent_as_area_sums_integer_areas():
     from oai_analysis_2_amd import stats
-    Y, groups, cap = _painted(0.10)
-    atlas = _sphere_atlas()
+    Y, groups, cap = painted(0.10, N_E2E)
+    atlas = sphere_atlas()
     res = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, seed=1, tfce=True, batch=64)
     assert res.tfce_settings == stats.TFCE() and res.tfce_settings.extent == "area"
     w = _area_weights(atlas)
@@ -354,8 +284,8 @@ def mp_areas(atlas):
 
 def test_paired_test_with_tfce_finds_the_cap():
     from oai_analysis_2_amd import stats
-    Y, _, cap = _painted(0.0)
-    atlas = _sphere_atlas()
+    Y, _, cap = painted(0.0, N_E2E)
+    atlas = sphere_atlas()
     rng = np.random.default_rng(77)
     follow = (Y + 0.1 * rng.normal(size=Y.shape)).astype(np.float32)
     follow[:, cap] += np.float32(0.15)
@@ -363,7 +293,7 @@ def test_paired_test_with_tfce_finds_the_cap():
     assert res.p_tfce[cap].min() == 1.0 / P_SMALL and res.n_permutations == P_SMALL
     diff = follow - Y
     t_ref = gref.permutation_t(gref.prepare(diff, None, centre=False), None, stats.sign_flips(N_E2E, P_SMALL, seed=3).rows(), gref.ONE_SAMPLE)
-    _same_bits(res.t, t_ref[0], "t")
+    same_bits(res.t, t_ref[0], "t")
     _check_against(res, t_ref, P_SMALL, "paired", dh=0.1, E=1.0, H=2.0, weights=_area_weights(atlas), unit=UNIT)
     # clusters and tfce together: batch 16 (a ragged last batch of 4) gives the bits of batch 32
     both = [stats.paired_test(_cohort(atlas, follow), _cohort(atlas, Y), n_permutations=P_SMALL, seed=3, batch=batch, tfce=True, cluster_threshold=2.5)
@@ -371,14 +301,14 @@ def test_paired_test_with_tfce_finds_the_cap():
     assert both[0].max_extent is not None and both[0].cluster_label is not None
     _same_result(both[1], both[0], "paired, batch 16 against batch 32")
     for name in TFCE_FIELDS:
-        _same_bits(getattr(both[0], name), getattr(res, name), name + " (with clusters)")
+        same_bits(getattr(both[0], name), getattr(res, name), name + " (with clusters)")
 
 
 def test_regression_test_with_tfce_finds_the_cap():
     import group_regression_ref as rref
     from oai_analysis_2_amd import stats
-    Y, _, cap = _painted(0.0)
-    atlas = _sphere_atlas()
+    Y, _, cap = painted(0.0, N_E2E)
+    atlas = sphere_atlas()
     rng = np.random.default_rng(78)
     x, age = rng.normal(0.0, 1.0, N_E2E), rng.uniform(45, 80, N_E2E)
     Y = Y.astype(np.float64)
@@ -388,14 +318,14 @@ def test_regression_test_with_tfce_finds_the_cap():
     assert res.p_tfce[cap].min() == 1.0 / P_SMALL and res.n_permutations == P_SMALL and res.tfce_settings == stats.TFCE()
     Z, D, _ = rref.design_columns(x, age, True)
     t_ref = rref.regression_t(rref.prepare(Y, None, Z), None, D, stats.index_permutations(N_E2E, P_SMALL, seed=5).index)
-    _same_bits(res.t, t_ref[0], "t")
+    same_bits(res.t, t_ref[0], "t")
     _check_against(res, t_ref, P_SMALL, "regression", dh=0.1, E=1.0, H=2.0, weights=_area_weights(atlas), unit=UNIT)
     again = stats.regression_test(_cohort(atlas, Y), x, covariates=age, n_permutations=P_SMALL, seed=5, tfce=True)
     plain = stats.regression_test(_cohort(atlas, Y), x, covariates=age, n_permutations=P_SMALL, seed=5, batch=32)
     for name in TFCE_FIELDS:
-        _same_bits(getattr(again, name), getattr(res, name), name + " (default batch)")
+        same_bits(getattr(again, name), getattr(res, name), name + " (default batch)")
     for name in ("t", "n", "dof", "slope", "partial_r", "p_uncorrected", "p_fwer", "max_abs"):
-        _same_bits(getattr(res, name), getattr(plain, name), name + " (with and without tfce)")
+        same_bits(getattr(res, name), getattr(plain, name), name + " (with and without tfce)")
     assert plain.tfce is None and plain.tfce_settings is None
     # clusters and tfce together: batch 16 (a ragged last batch of 4) gives the bits of batch 32
     both = [stats.regression_test(_cohort(atlas, Y), x, covariates=age, n_permutations=P_SMALL, seed=5, batch=batch, tfce=True, cluster_threshold=2.5)
@@ -403,13 +333,13 @@ def test_regression_test_with_tfce_finds_the_cap():
     assert both[0].max_extent is not None and both[0].cluster_label is not None
     _same_result(both[1], both[0], "regression, batch 16 against batch 32")
     for name in TFCE_FIELDS:
-        _same_bits(getattr(both[0], name), getattr(res, name), name + " (with clusters)")
+        same_bits(getattr(both[0], name), getattr(res, name), name + " (with clusters)")
 
 
 def test_without_an_effect_the_tfce_p_is_the_rank_of_the_observed_maximum():
     from oai_analysis_2_amd import stats
-    Y, groups, _ = _painted(0.0)
-    res = stats.two_sample_test(_cohort(_sphere_atlas(), Y), groups, n_permutations=P_E2E, seed=2, batch=64, tfce=True)
+    Y, groups, _ = painted(0.0, N_E2E)
+    res = stats.two_sample_test(_cohort(sphere_atlas(), Y), groups, n_permutations=P_E2E, seed=2, batch=64, tfce=True)
     assert not np.isnan(res.tfce).any()
     assert res.p_tfce.min() == (res.max_tfce >= res.max_tfce[0]).sum() / P_E2E
     assert (res.p_tfce >= res.p_tfce_uncorrected).all()

@@ -1,29 +1,20 @@
 """CPU: the F-test entry points of the C ABI (include/oai_hip.h: oai_regression_f_workspace_bytes, oai_regression_f) are exported by the
 built library and refuse bad arguments with a status and a message -- no GPU is touched before the checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_reexported, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_regression_f_workspace_bytes", "oai_regression_f")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
+    raw = check_symbols(NEW)
     assert len(_lib.SIGNATURES["oai_regression_f"][1]) == len(_lib.SIGNATURES["oai_regression_t"][1]) + 1
     # the header names the kernel file and the restatement, where the columns of interest stand, and the arithmetic of F and the coefficients
-    section = raw[raw.index("Cohort F test"):]
+    section = _section(raw, "Cohort F test")
     section = section[:section.index("oai_regression_f(")]
     for words in ("tests/group_f_ref.py", "csrc/group_regression.hip", "COME LAST", "n_nuisance = q", "RESPONSIBLE FOR HAVING PREPARED WITH THE MATCHING q",
                   "M, b, L, z   as in oai_regression_t", "rss = Q - sum_a z_a*z_a", "ess = sum_{a=q}^{p-1} z_a*z_a", "from +0.0, s = s + z_a*z_a",
@@ -37,14 +28,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_the_size_function_refuses_with_0_and_is_the_t_entry_points_otherwise(lib):
@@ -85,7 +68,4 @@ def test_regression_f_argument_checks(lib):
 
 
 def test_the_names_are_exported_where_the_other_statistics_are():
-    import oai_analysis_2_amd as pkg
-    from oai_analysis_2_amd import stats
-    for name in ("FResult", "f_test", "anova_test"):
-        assert getattr(pkg, name) is getattr(stats, name)
+    check_reexported(("FResult", "f_test", "anova_test"))

@@ -3,7 +3,6 @@
 tested column, and oai_analysis_2_amd.stats.anova_test end to end on a small sphere.  Every float64 is the result of IEEE add / subtract /
 multiply / divide / sqrt in a stated order, so equality is exact."""
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import graph_tfce_ref as tref
 import group_f_ref as fref
 import group_regression_ref as rref
 import group_stats_ref as gref
+from cohort_cases import cohort as _cohort, icosphere, rows as _rows, same_bits, same_result, sphere_atlas, sphere_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -34,21 +34,6 @@ def _batch(p, masked):
     """One full row group and a ragged one."""
     r = _rows_per_thread(p, masked)
     return r + max(1, r // 4)
-
-
-def _rows(p, masked):
-    b = _batch(p, masked)
-    return (1, 2, b - 1, b + 1, 2 * b + 5)
-
-
-def _same_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype == np.float64:
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-        got, want = np.where(np.isnan(got), 0.0, got).view(np.int64), np.where(np.isnan(want), 0.0, want).view(np.int64)
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
 
 
 def _levels(p, k):
@@ -77,7 +62,7 @@ def _case(N, V, p, k, masked):
     D, level = _design(N, p, k, rng)
     Y = (2.0 + 0.5 * rng.normal(size=(N, V)) + 0.3 * (level[:, None] == 1) * rng.random(V)[None, :]).astype(np.float32)
     mask = rng.random((N, V)) >= 0.1 if masked else None
-    P = max(_rows(p, masked))
+    P = max(_rows(_batch(p, masked)))
     perm = np.stack([np.arange(N)] + [rng.permutation(N) for _ in range(P - 1)]).astype(np.int32)
     perm[1, 0], perm[1, N - 1] = -5, N + 3                                # out of range: clamped to knee 0 and knee N - 1
     if V >= 8:
@@ -165,15 +150,15 @@ def test_f_coefficients_max_and_exceed_equal_the_restatement_to_the_bit(p, k, ma
             Y, mask, D, perm = _case(N, V, p, k, masked)
             ref, F_ref, coef_ref = _reference(N, V, p, k, masked)
             prep = _prepare_device(Y, mask, D, k)
-            for P in _rows(p, masked):
+            for P in _rows(_batch(p, masked)):
                 F, coef0, f0, max_f, exceed = _device(prep, D, perm[:P], k, batch)
                 where = f"N={N} V={V} P={P}"
-                _same_bits(F, F_ref[:P], f"{where} F")
-                _same_bits(coef0, coef_ref, f"{where} coef0")
-                _same_bits(f0, F_ref[0], f"{where} f0")
+                same_bits(F, F_ref[:P], f"{where} F")
+                same_bits(coef0, coef_ref, f"{where} coef0")
+                same_bits(f0, F_ref[0], f"{where} f0")
                 want_max, want_exceed = gref.reduce_tiles(F_ref[:P])
-                _same_bits(max_f, want_max, f"{where} max_f")
-                _same_bits(exceed, want_exceed, f"{where} exceed")
+                same_bits(max_f, want_max, f"{where} max_f")
+                same_bits(exceed, want_exceed, f"{where} exceed")
             assert (F_ref[~np.isnan(F_ref)] >= 0.0).all()
             assert not np.isnan(F_ref[:, 0]).any() or N < 31                    # an ordinary vertex has an F in every row
             clamped = np.array(perm[1])
@@ -193,10 +178,10 @@ def test_no_mask_gives_the_bits_of_a_mask_of_all_ones(p, k):
     assert bare.mask is None and full.mask is not None and (ref["n"] == N).all()
     for prep, batch, what in ((bare, _batch(p, False), "no mask"), (full, _batch(p, True), "all ones")):      # two kernels, two row groupings
         F, coef0, _, max_f, exceed = _device(prep, D, perm, k, batch)
-        _same_bits(F, F_ref, f"F ({what})")
-        _same_bits(coef0, coef_ref, f"coef0 ({what})")
-        _same_bits(max_f, gref.reduce_tiles(F_ref)[0], f"max_f ({what})")
-        _same_bits(exceed, gref.reduce_tiles(F_ref)[1], f"exceed ({what})")
+        same_bits(F, F_ref, f"F ({what})")
+        same_bits(coef0, coef_ref, f"coef0 ({what})")
+        same_bits(max_f, gref.reduce_tiles(F_ref)[0], f"max_f ({what})")
+        same_bits(exceed, gref.reduce_tiles(F_ref)[1], f"exceed ({what})")
 
 
 # ---- one tested column: the F kernel against the t kernel ------------------------------------------------------------------------------
@@ -245,7 +230,7 @@ def test_one_tested_column_agrees_with_the_t_kernel(p):
             tiles.append(tile.clone())
         out[name] = [x.cpu().numpy() for x in (torch.cat(tiles), max_abs, exceed, row0[0])]
     (t, t_max, t_exceed, slope), (F, f_max, f_exceed, coef) = out["t"], out["f"]
-    _same_bits(t, t_ref, "t")
+    same_bits(t, t_ref, "t")
     rel = float(np.max(np.abs(F - t * t) / (t * t)))
     print(f"p = {p}: max relative distance of F from t * t {rel:.3g}")
     assert np.allclose(F, t * t, rtol=1e-12, atol=0) and np.allclose(coef, slope, rtol=1e-12, atol=0)
@@ -272,44 +257,9 @@ def test_the_wrapper_refuses_what_the_kernel_would():
 
 
 # ---- the public interface --------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _icosphere(level=3):
-    """(verts float32 [n, 3] on the unit sphere, faces int32 [m, 3]): 642 vertices and 1280 faces at level 3."""
-    g = (1 + 5 ** 0.5) / 2
-    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
-    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
-         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
-    v = [np.asarray(q, np.float64) / np.linalg.norm(q) for q in v]
-    for _ in range(level):
-        mid, nf = {}, []
-
-        def midpoint(a, b):
-            key = (min(a, b), max(a, b))
-            if key not in mid:
-                q = v[a] + v[b]
-                v.append(q / np.linalg.norm(q))
-                mid[key] = len(v) - 1
-            return mid[key]
-        for a, b, c in f:
-            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
-            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
-        f = nf
-    return np.asarray(v, np.float32), np.asarray(f, np.int32)
-
-
-def _sphere_atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _icosphere()
-    image = lambda vec, kind: np.broadcast_to(np.asarray(vec, np.float32)[:12].reshape(3, 4), (3, 4))      # stands for the atlas' rasteriser
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0), image=image)
-
-
-def _cohort(atlas, Y, mask):
-    from oai_analysis_2_amd import stats
-    cohort = stats.ThicknessCohort(atlas, "FC", chunk=7)                   # several growth steps
-    for i, row in enumerate(Y):
-        cohort.add_vector(row, None, mask[i])
-    return cohort
+def _image(vec, kind):
+    """Stands for the atlas' rasteriser."""
+    return np.broadcast_to(np.asarray(vec, np.float32)[:12].reshape(3, 4), (3, 4))
 
 
 N_E2E, P_E2E, F_CLUSTER = 24, 200, 8.0
@@ -320,7 +270,7 @@ LABELS = (2, 4, 9)                                                         # the
 def _painted(effect):
     """Three groups of 8 knees on the sphere: 2 mm + 0.2 mm noise + 0.01 mm per year of age over 60 everywhere; on the cap z > 0.8 the
     group labelled 4 is ``effect`` mm thicker and the group labelled 9 ``effect`` mm thinner than the group labelled 2.  10 % missing."""
-    verts, _ = _icosphere()
+    verts, _ = icosphere()
     cap, far = verts[:, 2] > 0.8, verts[:, 2] < 0.5
     rng = np.random.default_rng(2027)                                     # a draw without a family-wise false positive far from the cap (5 % have one)
     member = np.arange(N_E2E) % 3
@@ -332,14 +282,6 @@ def _painted(effect):
     Y[np.ix_(member == 2, cap)] -= effect
     mask = rng.random(Y.shape) >= 0.1
     return np.where(mask, Y, 0.0).astype(np.float32), mask, groups, age, cap, far
-
-
-@functools.lru_cache(maxsize=None)
-def _graph():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _icosphere()
-    off_d, nbr_d = mp.vertex_adjacency_device(len(verts), torch.from_numpy(faces).cuda())
-    return off_d.cpu().numpy(), nbr_d.cpu().numpy()
 
 
 def _restated(Y, mask, groups, age, index, threshold, atlas):
@@ -356,7 +298,7 @@ def _restated(Y, mask, groups, age, index, threshold, atlas):
     dof2 = prep["n"].astype(np.int64) - p
     with np.errstate(invalid="ignore", divide="ignore"):
         eta2 = (k * F[0]) / (k * F[0] + dof2.astype(np.float64))
-    off, nbr = _graph()
+    off, nbr = sphere_graph()
     area = mp.mesh_areas(atlas.inner["FC"])[0]
     label, size, extent = gref.clusters(F, off, nbr, threshold)
     found = []
@@ -374,27 +316,16 @@ def _restated(Y, mask, groups, age, index, threshold, atlas):
                 tfce_settings=stats.TFCE(), kind="FC")
 
 
-def _same_result(got, want: dict, what):
-    import dataclasses
-    assert {f.name for f in dataclasses.fields(got)} == set(want), what
-    for name, b in want.items():
-        a = getattr(got, name)
-        if isinstance(b, np.ndarray):
-            _same_bits(a, b, f"{what}: {name}")
-        else:
-            assert a == b and type(a) is type(b), f"{what}: {name}: {a!r} != {b!r}"
-
-
 def test_anova_end_to_end_finds_the_painted_cap_and_equals_the_restatement():
     import dataclasses
     from oai_analysis_2_amd import stats
     Y, mask, groups, age, cap, far = _painted(0.3)
-    atlas = _sphere_atlas()
+    atlas = sphere_atlas(image=_image)
     kwargs = dict(covariates=age, n_permutations=P_E2E, cluster_threshold=F_CLUSTER, seed=1, tfce=True)
-    res = stats.anova_test(_cohort(atlas, Y, mask), groups, batch=48, **kwargs)
+    res = stats.anova_test(_cohort(atlas, Y, mask=mask, chunk=7), groups, batch=48, **kwargs)
     assert isinstance(res, stats.FResult) and res.n_permutations == P_E2E and not res.exact and res.dof1 == 2 and res.levels.tolist() == [2, 4, 9]
     want = _restated(Y, mask, groups, age, stats.index_permutations(N_E2E, P_E2E, seed=1).index, F_CLUSTER, atlas)
-    _same_result(res, want, "against the restatement")
+    same_result(res, want, "against the restatement")
     # what was painted is found: the corrected p inside the cap and nowhere at distance; the coefficients are differences from level 2
     assert (res.p_fwer[cap] <= 0.05).any() and not (res.p_fwer[far] <= 0.05).any() and not np.isnan(res.f).any()
     assert (res.p_tfce[cap] <= 0.05).any() and not (res.p_tfce[far] <= 0.05).any()
@@ -411,28 +342,28 @@ def test_anova_end_to_end_finds_the_painted_cap_and_equals_the_restatement():
     assert np.array_equal(res.n, res.group_n.sum(axis=0)) and np.array_equal(res.dof2, res.n.astype(np.int64) - 4)
     assert res.image(atlas, "f").shape == atlas.image(np.zeros(len(cap)), "FC").shape and res.image(atlas, "partial_eta2").dtype == np.float32
     # a linear score over the groups sees a weaker effect than the F: the painted means are not monotone in the label
-    score = stats.regression_test(_cohort(atlas, Y, mask), np.searchsorted(res.levels, groups).astype(np.float64), covariates=age,
+    score = stats.regression_test(_cohort(atlas, Y, mask=mask, chunk=7), np.searchsorted(res.levels, groups).astype(np.float64), covariates=age,
                                   n_permutations=P_E2E, seed=1, batch=48)
     assert np.median(score.t[cap] ** 2) < np.median(res.f[cap])
     # a second run, another batch size and the rows handed over instead of drawn: the same bits in every field
     fields = {f.name: getattr(res, f.name) for f in dataclasses.fields(res)}
     perms = stats.index_permutations(N_E2E, P_E2E, seed=1)
-    for other, what in ((stats.anova_test(_cohort(atlas, Y, mask), groups, batch=48, **kwargs), "again"),
-                        (stats.anova_test(_cohort(atlas, Y, mask), groups, **kwargs), "default batch"),
-                        (stats.anova_test(_cohort(atlas, Y, mask), groups, covariates=age, cluster_threshold=F_CLUSTER, tfce=True, batch=37,
+    for other, what in ((stats.anova_test(_cohort(atlas, Y, mask=mask, chunk=7), groups, batch=48, **kwargs), "again"),
+                        (stats.anova_test(_cohort(atlas, Y, mask=mask, chunk=7), groups, **kwargs), "default batch"),
+                        (stats.anova_test(_cohort(atlas, Y, mask=mask, chunk=7), groups, covariates=age, cluster_threshold=F_CLUSTER, tfce=True, batch=37,
                                           permutations=perms.index), "batch 37")):
-        _same_result(other, fields, what)
+        same_result(other, fields, what)
     # f_test on the same dummies is the same test, without the descriptive side
-    plain = stats.f_test(_cohort(atlas, Y, mask), fref.anova_dummies(groups)[1], covariates=age, n_permutations=P_E2E, seed=1, batch=48)
+    plain = stats.f_test(_cohort(atlas, Y, mask=mask, chunk=7), fref.anova_dummies(groups)[1], covariates=age, n_permutations=P_E2E, seed=1, batch=48)
     for name in ("f", "coefficients", "partial_eta2", "p_fwer", "p_uncorrected", "max_f", "n", "dof2"):
-        _same_bits(getattr(plain, name), getattr(res, name), f"f_test: {name}")
+        same_bits(getattr(plain, name), getattr(res, name), f"f_test: {name}")
     assert plain.levels is None and plain.group_n is None and plain.group_mean is None and plain.tfce is None and plain.cluster_label is None
 
 
 def test_without_an_effect_the_corrected_p_is_the_rank_of_the_observed_maximum():
     from oai_analysis_2_amd import stats
     Y, mask, groups, age, _, _ = _painted(0.0)
-    res = stats.anova_test(_cohort(_sphere_atlas(), Y, mask), groups, covariates=age, n_permutations=P_E2E, seed=2, batch=64)
+    res = stats.anova_test(_cohort(sphere_atlas(image=_image), Y, mask=mask, chunk=7), groups, covariates=age, n_permutations=P_E2E, seed=2, batch=64)
     assert not np.isnan(res.f).any() and res.cluster_label is None and res.clusters == [] and res.tfce is None
     assert (res.p_fwer >= res.p_uncorrected).all()
     assert res.p_fwer.min() == (res.max_f >= res.max_f[0]).sum() / P_E2E

@@ -1,28 +1,19 @@
 """CPU: the cohort-regression entry points of the C ABI (include/oai_hip.h: oai_regression_prepare, oai_regression_t) are exported by the
 built library and refuse bad arguments with a status and a message -- no GPU is touched before the checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_reexported, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_regression_prepare_workspace_bytes", "oai_regression_prepare", "oai_regression_t_workspace_bytes", "oai_regression_t")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
+    raw = check_symbols(NEW)
     # the header names the restatement, the pivot rule, the order and the t formula
-    section = raw[raw.index("Cohort regression"):]
+    section = _section(raw, "Cohort regression")
     for words in ("tests/group_regression_ref.py", "csrc/group_regression.hip", "ASCENDING KNEE INDEX", "x LAST", "Freedman and Lane", "Winkler",
                   "NOT pinned", "pivot s is accepted iff s > 1e-10 * A_aa", "s = s - L_ak*L_ak", "h_a = sum_i z_ia*d_i",
                   "r_i = m_i ? d_i - sum_a z_ia*gamma_a : 0.0", "M_ac = sum_j (m_j ? g_ja*g_jc : 0.0)", "b_a = sum_j g_ja*r_j",
@@ -34,14 +25,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_regression_prepare_argument_checks(lib):
@@ -90,7 +73,4 @@ def test_regression_t_argument_checks(lib):
 
 
 def test_the_names_are_exported_where_the_other_statistics_are():
-    import oai_analysis_2_amd as pkg
-    from oai_analysis_2_amd import stats
-    for name in ("RegressionResult", "IndexPermutations", "regression_test", "index_permutations"):
-        assert getattr(pkg, name) is getattr(stats, name)
+    check_reexported(("RegressionResult", "IndexPermutations", "regression_test", "index_permutations"))

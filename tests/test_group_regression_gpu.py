@@ -2,7 +2,6 @@
 prepared block, t tile, slope, max |t| and the exceedance counts to the bit -- and oai_analysis_2_amd.stats.regression_test end to end on
 a small sphere.  Every float64 is the result of IEEE add / subtract / multiply / divide / sqrt in a stated order, so equality is exact."""
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -10,15 +9,12 @@ import torch
 
 import group_regression_ref as rref
 import group_stats_ref as gref
+from cohort_cases import bare_atlas, cohort as _cohort, design, icosphere, knees as _knees, rows as _rows, same_bits, sphere_atlas
 
 pytestmark = pytest.mark.gpu
 
 COLUMNS = (1, 2, 4, 6)                            # p: no nuisance column at all; the intercept alone; two sizes of the kernels' rows per thread
 VERTS = (1, 63, 65, 257, 600)                     # both sides of a wave (64) and of a block's 256 vertices, several blocks
-
-
-def _knees(p):
-    return tuple(sorted({p + 1, 7, 31, 33, 65}))
 
 
 def _rows_per_thread(p, masked):                  # csrc/group_regression.hip, rows_per_thread
@@ -31,32 +27,6 @@ def _batch(p, masked):
     return r + max(1, r // 4)
 
 
-def _rows(p, masked):
-    b = _batch(p, masked)
-    return (1, 2, b - 1, b + 1, 2 * b + 5)
-
-
-def _same_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype == np.float64:
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-        got, want = np.where(np.isnan(got), 0.0, got).view(np.int64), np.where(np.isnan(want), 0.0, want).view(np.int64)
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
-
-
-def _design(N, p, rng):
-    """[N, p] with x last.  p = 1: a continuous x alone (no intercept).  p = 2: intercept and a dummy x.  p = 4: intercept, a sex dummy,
-    age, a dummy x.  p = 6: intercept, a sex dummy, three continuous covariates, a continuous x."""
-    i = np.arange(N)
-    sex, dummy = (i % 2).astype(np.float64), ((i // 2) % 2).astype(np.float64)
-    cont = lambda: rng.normal(0.0, 1.0, N)
-    cols = {1: [cont()], 2: [np.ones(N), dummy], 4: [np.ones(N), sex, 60 + 8 * cont(), dummy],
-            6: [np.ones(N), sex, 60 + 8 * cont(), 27 + 4 * cont(), cont(), cont()]}[p]
-    return np.ascontiguousarray(np.stack(cols, axis=1))
-
-
 PLANTED = {"empty": 1, "dof0": 2, "dof1": 3, "constant": 4, "nuisance": 5, "x_sometimes": 6}
 
 
@@ -64,10 +34,10 @@ PLANTED = {"empty": 1, "dof0": 2, "dof1": 3, "constant": 4, "nuisance": 5, "x_so
 def _case(N, V, p, masked):
     """(Y, mask, design, perm) with the header's corner cases planted where the shape has room (V >= 8, and for the last two N >= 31)."""
     rng = np.random.default_rng([N, V, p, int(masked)])
-    D = _design(N, p, rng)
+    D = design(N, p, rng)
     Y = (2.0 + 0.5 * rng.normal(size=(N, V)) + 0.3 * D[:, -1:] * rng.random(V)[None, :]).astype(np.float32)
     mask = rng.random((N, V)) >= 0.1 if masked else None
-    P = max(_rows(p, masked))
+    P = max(_rows(_batch(p, masked)))
     perm = np.stack([np.arange(N)] + [rng.permutation(N) for _ in range(P - 1)]).astype(np.int32)
     perm[1, 0], perm[1, N - 1] = -5, N + 3                                # out of range: clamped to knee 0 and knee N - 1
     if V >= 8:
@@ -150,16 +120,16 @@ def test_prepared_block_t_slope_max_and_exceed_equal_the_restatement_to_the_bit(
             ref, t_ref, slope_ref = _reference(N, V, p, masked)
             prep = _prepare_device(Y, mask, D)
             for name in ("R", "Q", "mean", "n", "ok"):
-                _same_bits(getattr(prep, name), ref[name], f"N={N} V={V} prepare.{name}")
-            for P in _rows(p, masked):
+                same_bits(getattr(prep, name), ref[name], f"N={N} V={V} prepare.{name}")
+            for P in _rows(_batch(p, masked)):
                 t, slope0, t0, max_abs, exceed = _device(prep, D, perm[:P], batch)
                 where = f"N={N} V={V} P={P}"
-                _same_bits(t, t_ref[:P], f"{where} t")
-                _same_bits(slope0, slope_ref, f"{where} slope0")
-                _same_bits(t0, t_ref[0], f"{where} t0")
+                same_bits(t, t_ref[:P], f"{where} t")
+                same_bits(slope0, slope_ref, f"{where} slope0")
+                same_bits(t0, t_ref[0], f"{where} t0")
                 want_max, want_exceed = gref.reduce_tiles(t_ref[:P])
-                _same_bits(max_abs, want_max, f"{where} max_abs")
-                _same_bits(exceed, want_exceed, f"{where} exceed")
+                same_bits(max_abs, want_max, f"{where} max_abs")
+                same_bits(exceed, want_exceed, f"{where} exceed")
             assert not np.isnan(t_ref[:, 0]).any() or N < 31                    # an ordinary vertex has a t in every row
             clamped = np.array(perm[1])
             clamped[0], clamped[N - 1] = 0, N - 1
@@ -178,60 +148,16 @@ def test_no_mask_gives_the_bits_of_a_mask_of_all_ones(p):
     bare, full = _prepare_device(Y, None, D), _prepare_device(Y, ones, D)
     assert bare.mask is None and full.mask is not None and (ref["n"] == N).all()
     for name in ("R", "Q", "mean", "n", "ok"):
-        _same_bits(getattr(full, name), ref[name], f"prepare.{name} (all ones)")
+        same_bits(getattr(full, name), ref[name], f"prepare.{name} (all ones)")
     for prep, batch, what in ((bare, _batch(p, False), "no mask"), (full, _batch(p, True), "all ones")):      # two kernels, two row groupings
         t, slope0, _, max_abs, exceed = _device(prep, D, perm, batch)
-        _same_bits(t, t_ref, f"t ({what})")
-        _same_bits(slope0, slope_ref, f"slope0 ({what})")
-        _same_bits(max_abs, gref.reduce_tiles(t_ref)[0], f"max_abs ({what})")
-        _same_bits(exceed, gref.reduce_tiles(t_ref)[1], f"exceed ({what})")
+        same_bits(t, t_ref, f"t ({what})")
+        same_bits(slope0, slope_ref, f"slope0 ({what})")
+        same_bits(max_abs, gref.reduce_tiles(t_ref)[0], f"max_abs ({what})")
+        same_bits(exceed, gref.reduce_tiles(t_ref)[1], f"exceed ({what})")
 
 
 # ---- the public interface --------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _icosphere(level=3):
-    """(verts float32 [n, 3] on the unit sphere, faces int32 [m, 3]): 642 vertices and 1280 faces at level 3."""
-    g = (1 + 5 ** 0.5) / 2
-    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
-    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
-         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
-    v = [np.asarray(q, np.float64) / np.linalg.norm(q) for q in v]
-    for _ in range(level):
-        mid, nf = {}, []
-
-        def midpoint(a, b):
-            key = (min(a, b), max(a, b))
-            if key not in mid:
-                q = v[a] + v[b]
-                v.append(q / np.linalg.norm(q))
-                mid[key] = len(v) - 1
-            return mid[key]
-        for a, b, c in f:
-            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
-            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
-        f = nf
-    return np.asarray(v, np.float32), np.asarray(f, np.int32)
-
-
-def _sphere_atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _icosphere()
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0))
-
-
-def _bare_atlas(V):
-    from oai_analysis_2_amd import mesh_processing as mp
-    return SimpleNamespace(inner={"FC": mp.Mesh(np.zeros((V, 3), np.float32), np.zeros((0, 3), np.int32))}, device=torch.device("cuda", 0))
-
-
-def _cohort(atlas, Y, mask=None):
-    from oai_analysis_2_amd import stats
-    cohort = stats.ThicknessCohort(atlas, "FC", chunk=7)                   # several growth steps
-    for i, row in enumerate(Y):
-        cohort.add_vector(row, None, None if mask is None else mask[i])
-    return cohort
-
-
 def test_exhaustive_counts_lie_in_scipys_band():
     """N = 6, a dummy x of 3 + 3, the intercept alone, V = 65, all 720 permutations.  Each of the 20 labellings occurs 3! 3! = 36 times,
     and a labelling and its complement tie up to rounding, so an exact count against an independent implementation is not defined: the
@@ -242,7 +168,7 @@ def test_exhaustive_counts_lie_in_scipys_band():
     rng = np.random.default_rng(6)
     Y = rng.normal(2.0, 0.5, size=(6, 65)).astype(np.float32)
     x = np.array([1, 0, 1, 1, 0, 0], np.float64)
-    res = stats.regression_test(_cohort(_bare_atlas(65), Y), x, n_permutations=10000, batch=100)
+    res = stats.regression_test(_cohort(bare_atlas(65), Y, chunk=7), x, n_permutations=10000, batch=100)
     assert res.exact and res.n_permutations == 720 and (res.n == 6).all() and (res.dof == 4).all()
     y = Y.astype(np.float64)
     labellings = [np.isin(np.arange(6), c) for c in itertools.combinations(range(6), 3)]
@@ -263,7 +189,7 @@ N_E2E, P_E2E, T_CLUSTER = 40, 400, 6.0
 def _painted(effect):
     """40 knees on the sphere: 2 mm + 0.1 mm noise + 0.02 mm per year of age over 60 everywhere, and ``effect`` mm per unit of a
     continuous x on the cap z > 0.8.  The covariates are age and a sex dummy."""
-    verts, _ = _icosphere()
+    verts, _ = icosphere()
     cap = verts[:, 2] > 0.8
     rng = np.random.default_rng(2025)
     age = rng.uniform(45, 80, N_E2E)
@@ -286,9 +212,9 @@ FIELDS = ("t", "n", "dof", "slope", "partial_r", "p_uncorrected", "p_fwer", "max
 def test_regression_end_to_end_finds_the_painted_cap_and_is_reproducible():
     from oai_analysis_2_amd import mesh_processing as mp, stats
     Y, x, cov, cap = _painted(0.5)
-    atlas = _sphere_atlas()
+    atlas = sphere_atlas()
     kwargs = dict(covariates=cov, n_permutations=P_E2E, cluster_threshold=T_CLUSTER, seed=1)
-    res = stats.regression_test(_cohort(atlas, Y), x, batch=96, **kwargs)
+    res = stats.regression_test(_cohort(atlas, Y, chunk=7), x, batch=96, **kwargs)
     assert res.n_permutations == P_E2E and not res.exact and res.max_abs.shape == (P_E2E,) and res.max_extent.shape == (P_E2E,)
     assert (res.n == N_E2E).all() and (res.dof == N_E2E - 4).all()
     big = max(res.clusters, key=lambda c: c.extent)
@@ -302,27 +228,27 @@ def test_regression_end_to_end_finds_the_painted_cap_and_is_reproducible():
     # the device against the restatement through the public interface, batches and all
     perms = stats.index_permutations(N_E2E, P_E2E, seed=1)
     t_ref, slope_ref = _restated(Y, None, x, cov, perms.index)
-    _same_bits(res.t, t_ref[0], "t")
-    _same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
+    same_bits(res.t, t_ref[0], "t")
+    same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
     assert np.array_equal(np.rint(res.p_uncorrected * P_E2E).astype(np.int64), gref.reduce_tiles(t_ref)[1])
     assert np.allclose(res.slope, slope_ref, rtol=1e-14, atol=0)           # un-scaled on the host: one division
     # a second run on the same input: the same bits in every field
-    again = stats.regression_test(_cohort(atlas, Y), x, batch=96, **kwargs)
+    again = stats.regression_test(_cohort(atlas, Y, chunk=7), x, batch=96, **kwargs)
     for name in FIELDS:
-        _same_bits(getattr(again, name), getattr(res, name), name)
+        same_bits(getattr(again, name), getattr(res, name), name)
     assert again.clusters == res.clusters
     # another batch size changes nothing either, nor do the rows handed over instead of drawn
-    for other, what in ((stats.regression_test(_cohort(atlas, Y), x, **kwargs), "default batch"),
-                        (stats.regression_test(_cohort(atlas, Y), x, batch=37, covariates=cov, cluster_threshold=T_CLUSTER, permutations=perms.index), "batch 37")):
+    for other, what in ((stats.regression_test(_cohort(atlas, Y, chunk=7), x, **kwargs), "default batch"),
+                        (stats.regression_test(_cohort(atlas, Y, chunk=7), x, batch=37, covariates=cov, cluster_threshold=T_CLUSTER, permutations=perms.index), "batch 37")):
         for name in FIELDS:
-            _same_bits(getattr(other, name), getattr(res, name), f"{name} ({what})")
+            same_bits(getattr(other, name), getattr(res, name), f"{name} ({what})")
         assert other.clusters == res.clusters
 
 
 def test_without_an_effect_the_corrected_p_is_the_rank_of_the_observed_maximum():
     from oai_analysis_2_amd import stats
     Y, x, cov, _ = _painted(0.0)
-    res = stats.regression_test(_cohort(_sphere_atlas(), Y), x, covariates=cov, n_permutations=P_E2E, seed=2, batch=64)
+    res = stats.regression_test(_cohort(sphere_atlas(), Y, chunk=7), x, covariates=cov, n_permutations=P_E2E, seed=2, batch=64)
     assert not np.isnan(res.t).any() and res.cluster_label is None and res.clusters == []
     assert (res.p_fwer >= res.p_uncorrected).all()
     assert res.p_fwer.min() == (res.max_abs >= res.max_abs[0]).sum() / P_E2E
@@ -341,13 +267,13 @@ def test_what_the_cohort_calls_missing_reaches_the_kernel_as_missing():
     x, age = rng.normal(size=N), rng.uniform(45, 80, N)
     knees = [KneeThickness(Y[i], Y[i]) for i in range(N)]
     knees[4] = KneeThickness(Y[4], Y[4], errors={"FC": "no surface"})       # every entry of this knee is missing
-    cohort = stats.ThicknessCohort.from_stream(enumerate(knees), _bare_atlas(V), "FC")
+    cohort = stats.ThicknessCohort.from_stream(enumerate(knees), bare_atlas(V), "FC")
     mask = ~np.isnan(Y)
     mask[4] = False
     assert np.array_equal(cohort.mask.cpu().numpy() != 0, mask)
     res = stats.regression_test(cohort, x, covariates=age, n_permutations=50, seed=4, batch=16)
     assert np.array_equal(res.n, mask.sum(axis=0)) and res.n[9] == 3 and np.isnan(res.t[9]) and np.isnan(res.p_fwer[9]) and np.isnan(res.slope[9])
     t_ref, slope_ref = _restated(np.where(mask, Y, 0).astype(np.float32), mask, x, age, stats.index_permutations(N, 50, seed=4).index)
-    _same_bits(res.t, t_ref[0], "t")
-    _same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
+    same_bits(res.t, t_ref[0], "t")
+    same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
     assert np.allclose(res.slope, slope_ref, rtol=1e-14, atol=0, equal_nan=True) and not np.isnan(np.delete(res.t, 9)).any()

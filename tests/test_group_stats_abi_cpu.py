@@ -2,29 +2,20 @@
 oai_graph_clusters) are exported by the built library and refuse bad arguments with a status and a message -- no GPU is touched before
 the checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_group_prepare_workspace_bytes", "oai_group_prepare", "oai_permutation_t_workspace_bytes", "oai_permutation_t",
        "oai_permutation_reduce_workspace_bytes", "oai_permutation_reduce", "oai_graph_clusters_workspace_bytes", "oai_graph_clusters")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
+    raw = check_symbols(NEW)
     # the header states the order contract and names its restatement
-    section = raw[raw.index("Cohort statistics"):]
+    section = _section(raw, "Cohort statistics")
     for words in ("tests/group_stats_ref.py", "ASCENDING KNEE INDEX", "ss  = (Q1 - S1*S1/n1) + (Q2 - S2*S2/n2)", "sp2 = ss / (n - 2)",
                   "t   = (S1/n1 - S2/n2) / sqrt(sp2 * (1.0/n1 + 1.0/n2))", "var = (Q - Sf*Sf/n) / (n - 1)", "t   = (Sf/n) / sqrt(var/n)"):
         assert words in section, words
@@ -33,14 +24,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_group_prepare_argument_checks(lib):

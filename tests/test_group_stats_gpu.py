@@ -2,13 +2,13 @@
 tile, max |t| and the exceedance counts to the bit, clusters to the element -- and oai_analysis_2_amd.stats end to end on a small
 sphere.  Every float64 is the result of IEEE add / subtract / multiply / divide / sqrt in a stated order, so equality is exact."""
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 import group_stats_ref as gref
+from cohort_cases import bare_atlas, cohort as _cohort, dev, icosphere, painted, path_graph, same_bits, sphere_atlas
 
 pytestmark = pytest.mark.gpu
 
@@ -16,16 +16,6 @@ KNEES = (2, 4, 31, 33, 65, 130)                   # both sides of a label word (
 VERTS = (1, 63, 65, 257, 1500)                    # both sides of a wave (64) and of a block's 256 vertices, several blocks
 BATCH = 20                                        # labellings per launch: one full row group of 16 and a ragged one of 4
 ROWS = (1, 2, BATCH - 1, BATCH + 1, 2 * BATCH + 5)
-
-
-def _same_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype == np.float64:
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-        got, want = np.where(np.isnan(got), 0.0, got).view(np.int64), np.where(np.isnan(want), 0.0, want).view(np.int64)
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,12 +82,12 @@ def test_prepare_t_max_and_exceed_equal_the_restatement_to_the_bit(N, two_sample
             where = f"N={N} V={V} P={P}"
             if P == ROWS[0]:
                 for name in ("n", "mean", "std", "S", "Q", "C", "Qm"):
-                    _same_bits(getattr(prep, name), ref[name], f"{where} prepare.{name}")
-            _same_bits(t, t_ref[:P], f"{where} t")
-            _same_bits(t0, t_ref[0], f"{where} t0")
+                    same_bits(getattr(prep, name), ref[name], f"{where} prepare.{name}")
+            same_bits(t, t_ref[:P], f"{where} t")
+            same_bits(t0, t_ref[0], f"{where} t0")
             want_max, want_exceed = gref.reduce_tiles(t_ref[:P])
-            _same_bits(max_abs, want_max, f"{where} max_abs")
-            _same_bits(exceed, want_exceed, f"{where} exceed")
+            same_bits(max_abs, want_max, f"{where} max_abs")
+            same_bits(exceed, want_exceed, f"{where} exceed")
         if two_sample and V >= 5 and N >= 4:                               # the corner cases are really there
             assert np.isnan(t_ref[:, 1]).all() and np.isnan(t_ref[:, V - 1]).all() and ref["n"][V - 1] == 0 and np.isnan(ref["mean"][V - 1])
             assert np.isnan(t_ref[1]).all() and np.isnan(t_ref[2]).all()
@@ -112,44 +102,13 @@ def test_without_a_mask_every_entry_counts():
     ref, t_ref = _reference(N, V, True, False)
     prep, t, _, max_abs, exceed = _device(Y, None, rows, True, BATCH)
     assert (ref["n"] == N).all()
-    _same_bits(prep.C, ref["C"], "C")
-    _same_bits(t, t_ref, "t")
-    _same_bits(max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
-    _same_bits(exceed, gref.reduce_tiles(t_ref)[1], "exceed")
+    same_bits(prep.C, ref["C"], "C")
+    same_bits(t, t_ref, "t")
+    same_bits(max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
+    same_bits(exceed, gref.reduce_tiles(t_ref)[1], "exceed")
 
 
 # ---- clusters --------------------------------------------------------------------------------------------------------------------------
-def _path(n):
-    off = np.concatenate([[0], np.cumsum([1] + [2] * (n - 2) + [1])]).astype(np.int32)
-    nbr = np.concatenate([[1]] + [[i - 1, i + 1] for i in range(1, n - 1)] + [[n - 2]]).astype(np.int32)
-    return off, nbr
-
-
-@functools.lru_cache(maxsize=None)
-def _icosphere(level=3):
-    """(verts float32 [n, 3] on the unit sphere, faces int32 [m, 3]): 642 vertices and 1280 faces at level 3."""
-    g = (1 + 5 ** 0.5) / 2
-    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
-    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
-         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
-    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
-    for _ in range(level):
-        mid, nf = {}, []
-
-        def midpoint(a, b):
-            key = (min(a, b), max(a, b))
-            if key not in mid:
-                p = v[a] + v[b]
-                v.append(p / np.linalg.norm(p))
-                mid[key] = len(v) - 1
-            return mid[key]
-        for a, b, c in f:
-            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
-            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
-        f = nf
-    return np.asarray(v, np.float32), np.asarray(f, np.int32)
-
-
 def _hand_tile(V, t0, seed):
     """Rows written by hand: 0 a mix (runs, values exactly at +-t0, a NaN that splits a run, adjacent opposite signs, lone vertices),
     1 nothing above the threshold, 2 / 3 one component of either sign over everything, 4 every other vertex, 5 noise."""
@@ -179,12 +138,12 @@ def test_clusters_equal_the_restatement_to_the_element(graph):
     t0 = 2.5
     if graph == "path_3000":
         V = 3000
-        off, nbr = _path(V)
+        off, nbr = path_graph(V)
         off_d, nbr_d = torch.from_numpy(off).cuda(), torch.from_numpy(nbr).cuda()
     else:
-        verts, faces = _icosphere()
+        verts, faces = icosphere()
         V = len(verts)
-        off_d, nbr_d = mp.vertex_adjacency_device(V, torch.from_numpy(faces).cuda())
+        off_d, nbr_d = mp.vertex_adjacency_device(V, dev(faces))
         off, nbr = off_d.cpu().numpy(), nbr_d.cpu().numpy()
         assert np.array_equal(off, mp.vertex_adjacency(V, faces)[0]) and np.array_equal(nbr, mp.vertex_adjacency(V, faces)[1])
     tile = _hand_tile(V, t0, 11)
@@ -195,15 +154,15 @@ def test_clusters_equal_the_restatement_to_the_element(graph):
         assert label[0, V - 1] == V - 1 and size[0, 80] == 1 and size[0, 24] == 15 and size[0, 26] == 14 and size[0, 45] == 20
     tile_d = torch.from_numpy(tile).cuda()
     ext, lab0, size0 = ops.graph_clusters(tile_d, off_d, nbr_d, t0, return_labels=True)
-    _same_bits(ext, extent, "max_extent")
-    _same_bits(lab0, label[0], "label of row 0")
-    _same_bits(size0, size[0], "size of row 0")
+    same_bits(ext, extent, "max_extent")
+    same_bits(lab0, label[0], "label of row 0")
+    same_bits(size0, size[0], "size of row 0")
     assert ops.graph_clusters(tile_d, off_d, nbr_d, t0).cpu().numpy().tolist() == extent.tolist()       # without the label outputs
     for r in range(1, len(tile)):                                          # every other row's labels: the row as a tile of its own
         e, lab, siz = ops.graph_clusters(tile_d[r:r + 1], off_d, nbr_d, t0, return_labels=True)
-        _same_bits(e, extent[r:r + 1], f"max_extent of row {r}")
-        _same_bits(lab, label[r], f"label of row {r}")
-        _same_bits(siz, size[r], f"size of row {r}")
+        same_bits(e, extent[r:r + 1], f"max_extent of row {r}")
+        same_bits(lab, label[r], f"label of row {r}")
+        same_bits(siz, size[r], f"size of row {r}")
 
 
 def test_clusters_read_a_hostile_graph_as_the_restatement_reads_it():
@@ -219,47 +178,16 @@ def test_clusters_read_a_hostile_graph_as_the_restatement_reads_it():
     label, size, extent = gref.clusters(tile, off, nbr, t0)
     assert 1 < extent[1] < V - 2 and size[1, 0] == 1 and size[1, V - 1] == 1 and len(np.unique(label[1])) > 3
     off_d, nbr_d, tile_d = torch.from_numpy(off).cuda(), torch.from_numpy(nbr).cuda(), torch.from_numpy(tile).cuda()
-    _same_bits(ops.graph_clusters(tile_d, off_d, nbr_d, t0), extent, "max_extent")
+    same_bits(ops.graph_clusters(tile_d, off_d, nbr_d, t0), extent, "max_extent")
     for r in range(len(tile)):
         e, lab, siz = ops.graph_clusters(tile_d[r:r + 1], off_d, nbr_d, t0, return_labels=True)
-        _same_bits(e, extent[r:r + 1], f"max_extent of row {r}")
-        _same_bits(lab, label[r], f"label of row {r}")
-        _same_bits(siz, size[r], f"size of row {r}")
+        same_bits(e, extent[r:r + 1], f"max_extent of row {r}")
+        same_bits(lab, label[r], f"label of row {r}")
+        same_bits(siz, size[r], f"size of row {r}")
 
 
 # ---- the public interface --------------------------------------------------------------------------------------------------------------
-def _sphere_atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _icosphere()
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0))
-
-
-def _bare_atlas(V):
-    from oai_analysis_2_amd import mesh_processing as mp
-    return SimpleNamespace(inner={"FC": mp.Mesh(np.zeros((V, 3), np.float32), np.zeros((0, 3), np.int32))}, device=torch.device("cuda", 0))
-
-
-def _cohort(atlas, Y, ids=None, mask=None):
-    from oai_analysis_2_amd import stats
-    cohort = stats.ThicknessCohort(atlas, "FC", chunk=5)                   # several growth steps
-    for i, row in enumerate(Y):
-        cohort.add_vector(row, None if ids is None else ids[i], None if mask is None else mask[i])
-    return cohort
-
-
 N_E2E, P_E2E, T_CLUSTER = 24, 500, 6.0
-
-
-@functools.lru_cache(maxsize=None)
-def _painted(offset):
-    """24 knees on the sphere: 2 mm + 0.1 mm noise, and ``offset`` mm more on the cap z > 0.8 for group 1 (the first twelve)."""
-    verts, _ = _icosphere()
-    cap = verts[:, 2] > 0.8
-    rng = np.random.default_rng(2024)
-    Y = (2.0 + 0.1 * rng.normal(size=(N_E2E, len(verts)))).astype(np.float32)
-    groups = np.arange(N_E2E) < N_E2E // 2
-    Y[np.ix_(groups, cap)] += np.float32(offset)
-    return Y, groups, cap
 
 
 def test_exhaustive_counts_lie_in_scipys_band():
@@ -271,7 +199,7 @@ def test_exhaustive_counts_lie_in_scipys_band():
     rng = np.random.default_rng(8)
     Y = rng.normal(2.0, 0.5, size=(8, 65)).astype(np.float32)
     groups = np.array([1, 0, 1, 1, 0, 0, 1, 0])
-    res = stats.two_sample_test(_cohort(_bare_atlas(65), Y), groups, n_permutations=10000, batch=32)
+    res = stats.two_sample_test(_cohort(bare_atlas(65), Y), groups, n_permutations=10000, batch=32)
     assert res.exact and res.n_permutations == 70 and (res.n1 == 4).all() and (res.n2 == 4).all()
     rows = stats.label_permutations(groups, 10000).rows()
     y = Y.astype(np.float64)
@@ -286,8 +214,8 @@ def test_exhaustive_counts_lie_in_scipys_band():
 
 def test_two_sample_end_to_end_finds_the_painted_cap_and_is_reproducible():
     from oai_analysis_2_amd import mesh_processing as mp, stats
-    Y, groups, cap = _painted(0.5)
-    atlas = _sphere_atlas()
+    Y, groups, cap = painted(0.5, N_E2E)
+    atlas = sphere_atlas()
     res = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, cluster_threshold=T_CLUSTER, seed=1, batch=96)
     assert res.n_permutations == P_E2E and not res.exact and res.max_abs.shape == (P_E2E,) and res.max_extent.shape == (P_E2E,)
     big = max(res.clusters, key=lambda c: c.extent)
@@ -301,24 +229,24 @@ def test_two_sample_end_to_end_finds_the_painted_cap_and_is_reproducible():
     # the device against the restatement through the public interface, batches and all
     perms = stats.label_permutations(groups, P_E2E, seed=1)
     t_ref = gref.permutation_t(gref.prepare(Y, None), None, perms.rows(), gref.TWO_SAMPLE)
-    _same_bits(res.t, t_ref[0], "t")
-    _same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
+    same_bits(res.t, t_ref[0], "t")
+    same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
     assert np.array_equal(np.rint(res.p_uncorrected * P_E2E).astype(np.int64), gref.reduce_tiles(t_ref)[1])
     # a second run on the same input: the same bits in every field
     again = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, cluster_threshold=T_CLUSTER, seed=1, batch=96)
     for name in ("t", "n1", "n2", "mean_difference", "p_uncorrected", "p_fwer", "max_abs", "cluster_label", "max_extent"):
-        _same_bits(getattr(again, name), getattr(res, name), name)
+        same_bits(getattr(again, name), getattr(res, name), name)
     assert again.clusters == res.clusters
     # another batch size changes nothing either
     other = stats.two_sample_test(_cohort(atlas, Y), groups, n_permutations=P_E2E, cluster_threshold=T_CLUSTER, seed=1)
     for name in ("t", "p_uncorrected", "p_fwer", "max_abs", "cluster_label", "max_extent"):
-        _same_bits(getattr(other, name), getattr(res, name), name + " (default batch)")
+        same_bits(getattr(other, name), getattr(res, name), name + " (default batch)")
 
 
 def test_without_an_effect_the_corrected_p_is_the_rank_of_the_observed_maximum():
     from oai_analysis_2_amd import stats
-    Y, groups, _ = _painted(0.0)
-    res = stats.two_sample_test(_cohort(_sphere_atlas(), Y), groups, n_permutations=P_E2E, seed=2, batch=64)
+    Y, groups, _ = painted(0.0, N_E2E)
+    res = stats.two_sample_test(_cohort(sphere_atlas(), Y), groups, n_permutations=P_E2E, seed=2, batch=64)
     assert not np.isnan(res.t).any() and res.cluster_label is None and res.clusters == []
     assert (res.p_fwer >= res.p_uncorrected).all()
     assert res.p_fwer.min() == (res.max_abs >= res.max_abs[0]).sum() / P_E2E
@@ -329,8 +257,8 @@ def test_paired_test_matches_rows_by_id_and_finds_the_cap():
     """A cohort against itself shifted by 0.5 mm on the cap -- with fresh 0.1 mm noise, as a constant difference has no variance and so
     no t -- and handed over in another order: ids match the rows."""
     from oai_analysis_2_amd import stats
-    Y, _, cap = _painted(0.0)
-    atlas = _sphere_atlas()
+    Y, _, cap = painted(0.0, N_E2E)
+    atlas = sphere_atlas()
     rng = np.random.default_rng(77)
     follow = (Y + 0.1 * rng.normal(size=Y.shape)).astype(np.float32)
     follow[:, cap] += np.float32(0.5)
@@ -349,8 +277,8 @@ def test_paired_test_matches_rows_by_id_and_finds_the_cap():
     mask = ~np.isnan(diff)
     flips = stats.sign_flips(N_E2E, P_E2E, seed=3)
     t_ref = gref.permutation_t(gref.prepare(np.where(mask, diff, 0).astype(np.float32), mask, centre=False), mask, flips.rows(), gref.ONE_SAMPLE)
-    _same_bits(res.t, t_ref[0], "t")
-    _same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
+    same_bits(res.t, t_ref[0], "t")
+    same_bits(res.max_abs, gref.reduce_tiles(t_ref)[0], "max_abs")
     with pytest.raises(ValueError, match="same ids"):
         stats.paired_test(a, _cohort(atlas, Y, ["x"] + ids[1:]), n_permutations=10)
 
@@ -358,7 +286,7 @@ def test_paired_test_matches_rows_by_id_and_finds_the_cap():
 def test_the_cohort_masks_what_is_missing():
     from oai_analysis_2_amd import stats
     from oai_analysis_2_amd.thickness import KneeThickness
-    atlas = _bare_atlas(6)
+    atlas = bare_atlas(6)
     vec = np.array([1, 2, np.nan, 4, 5, 6], np.float32)
     cover = np.array([1, 1, 1, 0, 1, 1], np.uint8)
     knees = [KneeThickness(vec, vec, coverage={"FC": cover}), KneeThickness(torch.from_numpy(vec + 1).cuda(), vec, coverage={"FC": torch.from_numpy(cover).cuda()}),

@@ -1,29 +1,20 @@
 """CPU: the longitudinal entry points of the C ABI (include/oai_hip.h: oai_visit_slopes_workspace_bytes, oai_visit_slopes) are exported by
 the built library and refuse bad arguments with a status and a message -- no GPU is touched before the checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_reexported, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_visit_slopes_workspace_bytes", "oai_visit_slopes")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
+    raw = check_symbols(NEW)
     assert len(_lib.SIGNATURES["oai_visit_slopes"][1]) == 21 and len(_lib.SIGNATURES["oai_visit_slopes_workspace_bytes"][1]) == 4
     # the header names the kernel file and the restatement and states the three passes, the condition and the outputs
-    section = raw[raw.index("Longitudinal change"):]
+    section = _section(raw, "Longitudinal change")
     section = section[:section.index("oai_visit_slopes(")]
     for words in ("csrc/visit_slopes.hip", "tests/visit_slopes_ref.py", "long_mris_slopes", "AS RECALLED", "pinned to no implementation",
                   "THE SLOTS OF A SUBJECT IN ASCENDING CSR", "an offset outside [0, n_visits] is clamped",
@@ -43,14 +34,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_the_size_function_refuses_with_0(lib):
@@ -96,8 +79,6 @@ def test_visit_slopes_argument_checks(lib):
 
 
 def test_the_names_are_exported_where_the_other_statistics_are():
-    import oai_analysis_2_amd as pkg
     from oai_analysis_2_amd import ops, stats
-    for name in ("LongitudinalCohort", "visit_table", "one_sample_test", "VisitSlopes"):
-        assert getattr(pkg, name) is getattr(stats, name)
+    check_reexported(("LongitudinalCohort", "visit_table", "one_sample_test", "VisitSlopes"))
     assert stats.VisitSlopes is ops.VisitSlopes

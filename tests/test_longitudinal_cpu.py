@@ -6,17 +6,9 @@ import numpy as np
 import pytest
 
 import visit_slopes_ref as vref
+from cohort_cases import same_bits
 
 N_KNEES = 20000
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype.kind == "f":
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-        got, want = np.where(np.isnan(got), 0, got).view(np.int64), np.where(np.isnan(want), 0, want).view(np.int64)
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
 
 
 @pytest.mark.parametrize("with_mask", [True, False])
@@ -26,7 +18,7 @@ def test_the_loop_form_equals_the_vectorised_form_to_the_bit(V, with_mask):
     for kwargs in ({}, dict(min_visits=3), dict(min_span=2.5), dict(min_visits=4, min_span=1.0)):
         fast, slow = vref.fit(*case, **kwargs), vref.fit_loop(*case, **kwargs)
         for name in vref.OUTPUTS:
-            _same_bits(fast[name], slow[name], f"V={V} mask={with_mask} {kwargs} {name}")
+            same_bits(fast[name], slow[name], f"V={V} mask={with_mask} {kwargs} {name}")
         assert np.isfinite(fast["rate"]).all() and np.abs(fast["avg"]).max() <= 4.0           # nothing of what lay under a 0 mask byte
     fast = vref.fit(*case)
     assert (fast["n"][0] == 0).all() and (fast["mask"][:3] == 0).all() and fast["mask"][3].all()

@@ -3,32 +3,16 @@ float64 is the result of IEEE add, multiply, divide and sqrt in a stated order -
 oai_analysis_2_amd.stats end to end on a small sphere."""
 import dataclasses
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-import graph_smooth_ref as sref
 import group_stats_ref as gref
 import visit_slopes_ref as vref
+from cohort_cases import dev, icosphere, same_bits, sphere_atlas
 
 pytestmark = pytest.mark.gpu
-
-
-def _same_bits(got, want, what):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype.kind == "f":
-        assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-        as_int = np.int64 if got.dtype == np.float64 else np.int32
-        got, want = np.where(np.isnan(got), 0, got).view(as_int), np.where(np.isnan(want), 0, want).view(as_int)
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} of {got.size} differ, first at {bad[0].tolist()}"
-
-
-def _up(a):
-    return None if a is None else torch.from_numpy(np.array(a)).cuda()     # a copy: the cached cases are read-only
 
 
 COUNTS = {1: (6,), 5: vref.HOSTILE_COUNTS}
@@ -51,12 +35,12 @@ def _want(S, V, with_mask=True, min_visits=2, min_span=0.0):
 def _run(case, **kwargs):
     from oai_analysis_2_amd import ops
     Y, mask, offsets, rows, times, tref = case
-    return ops.visit_slopes(_up(Y), _up(offsets), _up(rows), _up(times), _up(tref), mask=_up(mask), **kwargs)
+    return ops.visit_slopes(dev(Y), dev(offsets), dev(rows), dev(times), dev(tref), mask=dev(mask), **kwargs)
 
 
 def _check(got, want, where, names=vref.OUTPUTS):
     for name in names:
-        _same_bits(getattr(got, name), want[name], f"{where} {name}")
+        same_bits(getattr(got, name), want[name], f"{where} {name}")
 
 
 @pytest.mark.parametrize("S", [1, 5])
@@ -129,15 +113,15 @@ def test_two_launches_give_identical_bits_and_no_visit_at_all_is_a_count_of_zero
     from oai_analysis_2_amd import ops
     first, second = _run(_case(5, 257)), _run(_case(5, 257))
     for name in vref.OUTPUTS:
-        _same_bits(getattr(second, name), getattr(first, name).cpu().numpy(), name)
+        same_bits(getattr(second, name), getattr(first, name).cpu().numpy(), name)
     Y = torch.ones((2, 3), dtype=torch.float32, device="cuda")
-    none = ops.visit_slopes(Y, _up(np.zeros(4, np.int32)), _up(np.zeros(0, np.int32)), _up(np.zeros(0)), _up(np.zeros(3)))
+    none = ops.visit_slopes(Y, dev(np.zeros(4, np.int32)), dev(np.zeros(0, np.int32)), dev(np.zeros(0)), dev(np.zeros(3)))
     assert none.n.shape == (3, 3) and not none.n.any() and not none.mask.any() and not none.rate.any()
 
 
 def test_the_wrapper_refuses_what_the_kernel_would():
     from oai_analysis_2_amd import ops
-    Y, mask, offsets, rows, times, tref = (_up(a) for a in _case(1, 63))
+    Y, mask, offsets, rows, times, tref = (dev(a) for a in _case(1, 63))
     for kwargs, match in ((dict(min_visits=1), "min_visits"), (dict(min_span=-1.0), "min_span"), (dict(min_span=float("nan")), "min_span"),
                           (dict(want=()), "want"), (dict(want=("rate", "slope")), "want"), (dict(mask=mask[:, :5]), "mask must have")):
         with pytest.raises(ValueError, match=match):
@@ -158,22 +142,11 @@ LABELS = {year: f"V{k:02d}" for k, year in enumerate(vref.OAI_VISIT_YEARS)}
 
 
 @functools.lru_cache(maxsize=None)
-def _sphere():
-    return sref.icosphere(2)
-
-
-def _atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _sphere()
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0))
-
-
-@functools.lru_cache(maxsize=None)
 def _study():
     """Twelve subjects on the sphere with baseline, the one-year visit and up to three more: 2.5 mm + 0.05 mm noise, a loss of 0.08 mm a
     year on the cap z > 0.7, 10 % of the entries missing (NaN).  The rows come visit by visit, so a subject's rows are apart.  Returns
     (Y float32 [R, V], subject, nominal years, label, jittered years, cap)."""
-    verts, _ = _sphere()
+    verts, _ = icosphere(2)
     cap = verts[:, 2] > 0.7
     rng = np.random.default_rng(12)
     later = np.array(vref.OAI_VISIT_YEARS[2:])
@@ -192,7 +165,7 @@ def _study():
 def _longitudinal(years, **kwargs):
     from oai_analysis_2_amd import stats
     Y, subject, _, label, _, _ = _study()
-    cohort = stats.LongitudinalCohort(_atlas(), "FC", chunk=7, **kwargs)
+    cohort = stats.LongitudinalCohort(sphere_atlas(level=2), "FC", chunk=7, **kwargs)
     for row, s, y, lab in zip(Y, subject, years, label):
         cohort.add_vector(np.array(row), s, y, visit=lab)                  # a copy: the cached study is read-only
     return cohort
@@ -219,8 +192,8 @@ def test_change_is_the_restatement_rounded_once():
     for measure in ("rate", "avg", "pc1", "spc"):
         want, want_m = vref.measure(fitted, measure)
         got = visits.change(measure)
-        _same_bits(got.mask, want_m, measure + " mask")
-        _same_bits(got.values, want, measure + " values")
+        same_bits(got.mask, want_m, measure + " mask")
+        same_bits(got.values, want, measure + " values")
         assert got.ids == table.subjects and got.kind == "FC" and got.atlas is visits.atlas and len(got) == N_SUBJECTS
         assert got.change == stats.Change(measure, 2, 0.0, "first") and got.smoothing is None and got._graph is graph
     with pytest.raises(dataclasses.FrozenInstanceError):
@@ -231,13 +204,13 @@ def test_change_is_the_restatement_rounded_once():
     # stricter settings and another reference time
     _, strict = _restated(3, 2.5)
     got = visits.change("rate", min_visits=3, min_span_years=2.5)
-    _same_bits(got.mask, vref.measure(strict, "rate")[1], "strict mask")
-    _same_bits(got.values, vref.measure(strict, "rate")[0], "strict values")
+    same_bits(got.mask, vref.measure(strict, "rate")[1], "strict mask")
+    same_bits(got.values, vref.measure(strict, "rate")[0], "strict values")
     assert got.change == stats.Change("rate", 3, 2.5, "first") and strict["mask"].sum() < fitted["mask"].sum()
     table4 = stats.visit_table(subject, jittered, reference=4.0)
     at4 = vref.fit(np.nan_to_num(Y), ~np.isnan(Y), table4.offsets, table4.rows, table4.times, table4.reference_time)
     got = visits.change("pc1", reference=4.0)
-    _same_bits(got.values, vref.measure(at4, "pc1")[0], "pc1 at four years")
+    same_bits(got.values, vref.measure(at4, "pc1")[0], "pc1 at four years")
     assert got.change.reference == 4.0 and visits.change("pc1", reference={s: 4.0 for s in table.subjects}).change.reference == "per subject"
     with pytest.raises(ValueError, match="measure must be"):
         visits.change("slope")
@@ -249,7 +222,7 @@ def test_change_is_the_restatement_rounded_once():
 def test_from_cohorts_per_row_add_and_at_visit():
     from oai_analysis_2_amd import stats
     Y, subject, nominal, label, _, _ = _study()
-    atlas = _atlas()
+    atlas = sphere_atlas(level=2)
     by_row = _longitudinal(nominal)
     per_visit = {}
     for year in sorted(set(nominal.tolist())):
@@ -259,15 +232,15 @@ def test_from_cohorts_per_row_add_and_at_visit():
     joined = stats.LongitudinalCohort.from_cohorts(per_visit)
     assert joined.subjects == by_row.subjects and joined.rows.ids == by_row.rows.ids == list(zip(subject, nominal.tolist()))
     assert torch.equal(joined.rows.values, by_row.rows.values) and torch.equal(joined.rows.mask, by_row.rows.mask)
-    _same_bits(joined.change("rate").values, by_row.change("rate").values.cpu().numpy(), "rate of the joined cohorts")
+    same_bits(joined.change("rate").values, by_row.change("rate").values.cpu().numpy(), "rate of the joined cohorts")
     # one visit as a cohort: by label and by years, rows matched by subject
     for key in ("V04", 2.5):
         picked = np.nonzero(nominal == 2.5)[0]
         assert 0 < len(picked) < N_SUBJECTS
         visit = by_row.at_visit(key)
         assert visit.ids == [subject[i] for i in picked] and isinstance(visit, stats.ThicknessCohort)
-        _same_bits(visit.values, np.nan_to_num(Y[picked]), f"at_visit({key!r})")
-        _same_bits(visit.mask, (~np.isnan(Y[picked])).astype(np.uint8), f"at_visit({key!r}) mask")
+        same_bits(visit.values, np.nan_to_num(Y[picked]), f"at_visit({key!r})")
+        same_bits(visit.mask, (~np.isnan(Y[picked])).astype(np.uint8), f"at_visit({key!r}) mask")
     assert joined.at_visit(1.0).ids == by_row.subjects                     # no labels there: by years
     with pytest.raises(ValueError, match="no row"):
         by_row.at_visit("V99")
@@ -297,7 +270,7 @@ def test_one_sample_test_is_the_paired_test_against_zeros_and_the_restatement():
     for f in dataclasses.fields(res):
         a, b = getattr(res, f.name), getattr(paired, f.name)
         if isinstance(a, np.ndarray):
-            _same_bits(a, b, f.name)
+            same_bits(a, b, f.name)
         else:
             assert a == b, f.name
     # against the restatement of the t on the restated rates
@@ -306,11 +279,11 @@ def test_one_sample_test_is_the_paired_test_against_zeros_and_the_restatement():
     flips = stats.sign_flips(N_SUBJECTS, 5000)
     t_ref = gref.permutation_t(gref.prepare(want, want_m, centre=False), want_m, flips.rows(), gref.ONE_SAMPLE)
     max_abs, exceed = gref.reduce_tiles(t_ref)
-    _same_bits(res.t, t_ref[0], "t")
-    _same_bits(res.max_abs, max_abs, "max_abs")
+    same_bits(res.t, t_ref[0], "t")
+    same_bits(res.max_abs, max_abs, "max_abs")
     valid = ~np.isnan(t_ref[0])
     p_fwer = np.where(valid, (max_abs[None, :] >= np.abs(np.where(valid, t_ref[0], 0.0))[:, None]).sum(axis=1) / float(len(flips)), np.nan)
-    _same_bits(res.p_fwer, p_fwer, "p_fwer")
+    same_bits(res.p_fwer, p_fwer, "p_fwer")
     assert np.array_equal(np.rint(res.p_uncorrected[valid] * len(flips)).astype(np.int64), exceed[valid])
     assert np.array_equal(res.n1, want_m.sum(axis=0).astype(np.int32)) and (res.mean_difference[cap] < -0.5 * LOSS).all()
     assert (res.t[cap] < 0).all() and np.nanmedian(res.p_fwer[cap]) < 0.05 < np.nanmedian(res.p_fwer[~cap])
@@ -328,7 +301,7 @@ def test_the_other_tests_take_the_rate_cohort_unchanged():
     groups = np.arange(N_SUBJECTS) % 2 == 0
     res = stats.two_sample_test(rate, groups, n_permutations=50, seed=4)
     t_ref = gref.permutation_t(gref.prepare(want, want_m), want_m, stats.label_permutations(groups, 50, seed=4).rows(), gref.TWO_SAMPLE)
-    _same_bits(res.t, t_ref[0], "two-sample t of the rates")
+    same_bits(res.t, t_ref[0], "two-sample t of the rates")
     reg = stats.regression_test(rate, np.linspace(45.0, 79.0, N_SUBJECTS), n_permutations=50, seed=4)
     assert reg.t.shape == (rate.n_verts,) and np.isfinite(reg.t[want_m.sum(axis=0) >= 4]).all()
     # smoothing before the fit and after it: both run, both keep their settings, and they differ where entries are missing

@@ -1,36 +1,23 @@
 """CPU: the mesh-QC entry points of the C ABI (include/oai_hip.h: oai_mesh_topology, oai_mesh_geometry, oai_mesh_self_intersections) are
 exported by the built library and refuse bad arguments with a status and a message -- no GPU is touched before the checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import check_symbols, refused as _refused
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_mesh_topology_workspace_bytes", "oai_mesh_topology", "oai_mesh_geometry_workspace_bytes", "oai_mesh_geometry",
        "oai_mesh_self_intersections_workspace_bytes", "oai_mesh_self_intersections")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "oai_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
+    check_symbols(NEW)
 
 
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
 
 
 def test_mesh_topology_argument_checks(lib):

@@ -3,27 +3,19 @@ oai_deviation_summary and their workspace sizes) are declared, exported and boun
 conditions, and every refusal is a status and a message -- no GPU is touched before the checks."""
 import ctypes as C
 import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, ROOT, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_normative_fit", "oai_normative_score", "oai_deviation_summary", "oai_normative_fit_workspace_bytes",
        "oai_normative_score_workspace_bytes", "oai_deviation_summary_workspace_bytes")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
-    section = raw[raw.index("Normative deviation (csrc/normative.hip"):]
+    raw = check_symbols(NEW)
+    section = _section(raw, "Normative deviation (csrc/normative.hip")
     for words in ("tests/normative_ref.py", "ASCENDING KNEE INDEX", "INTERCEPT (if any) COUNTED IN p",
                   "A_ac = sum_i (m_i ? z_ia*z_ic : 0.0), c <= a", "h_a = sum_i (m_i ? z_ia*y_i : 0.0)",
                   "pivot s is accepted iff s > 1e-10 * A_aa", "e_i  = y_i - sum_a z_ia*gamma_a", "rss  = sum_i (m_i ? e_i*e_i : 0.0)",
@@ -46,14 +38,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a size no check below can find too small
 
 
 def test_normative_fit_argument_checks(lib):

@@ -2,29 +2,22 @@
 bound in _lib.SIGNATURES, the header states the definitions word for word, and every entry point refuses bad arguments with a status and
 a message that names the argument -- on host buffers, so no GPU is touched before the checks."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import check_reexported, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_column_ranks", "oai_rank_sums", "oai_rank_scores")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
+    raw = check_symbols(NEW)
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)                      # a #define counts outside the comments only
     for name, value in (("OAI_RANK_PLAIN", 0), ("OAI_RANK_SIGNED", 1), ("OAI_SCORE_RANK", 0), ("OAI_SCORE_CENTRED", 1), ("OAI_SCORE_NORMAL", 2)):
         assert re.search(rf"#define {name} {value}\b", text), name
-    section = " ".join(raw[raw.index("Rank transform (csrc/rank_transform.hip"):].replace("\n *", " ").split())
+    section = " ".join(_section(raw, "Rank transform (csrc/rank_transform.hip").replace("\n *", " ").split())
     for words in ("tests/rank_transform_ref.py", "csrc/rank_transform.hip",
                   "An entry is valid iff its mask is non-zero (every entry, with a null mask) and its value is not NaN.",
                   "In signed mode the value must also be != 0.0f: scipy's zero_method=\"wilcox\" drops zeros before ranking.",
@@ -50,11 +43,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
 
 
 def test_column_ranks_argument_checks(lib):
@@ -110,11 +98,9 @@ def test_rank_scores_argument_checks(lib):
 
 
 def test_the_names_are_exported_where_the_other_statistics_are():
-    import oai_analysis_2_amd as pkg
     from oai_analysis_2_amd import ops, stats
-    for name in ("Ranking", "RankSumResult", "SignedRankResult", "KruskalResult", "SpearmanResult", "rank_sum_test", "signed_rank_test", "kruskal_test",
-                 "spearman_test"):
-        assert getattr(pkg, name) is getattr(stats, name)
+    check_reexported(("Ranking", "RankSumResult", "SignedRankResult", "KruskalResult", "SpearmanResult", "rank_sum_test", "signed_rank_test", "kruskal_test",
+                 "spearman_test"))
     for name in ("ranked", "difference"):
         assert callable(getattr(stats.ThicknessCohort, name))
     for name in ("column_ranks", "rank_sums", "rank_scores"):

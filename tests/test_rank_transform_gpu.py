@@ -7,7 +7,6 @@ The normal score is the one output held to a tolerance: the device erfc, exp and
 profiles/rank_transform.md): the largest |device - scipy.special.ndtri| is NORMAL_MEASURED = 1.33e-15; the gate NORMAL_GATE = 2.13e-14 is
 16 times that.  Three Halley steps leave 4e-6, four leave this, a fifth changes nothing: the iteration has converged."""
 import functools
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -16,7 +15,7 @@ import scipy.stats
 import torch
 
 import rank_transform_ref as rref
-from test_group_regression_gpu import _cohort, _icosphere, _same_bits
+from cohort_cases import cohort as _cohort, dev, icosphere, same_bits, sphere_atlas
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +26,6 @@ NORMAL_MEASURED = 1.3322676295501878e-15          # 6 * 2^-52, the same for each
 NORMAL_GATE = 16 * NORMAL_MEASURED                # 2.13e-14
 PLANTED = {"empty": 0, "single": 1, "equal": 2, "distinct": 3, "zeros_pair": 4, "extremes": 5, "nan": 6, "all_zero": 7, "some_zero": 8,
            "across_signs": 9}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
@@ -94,12 +89,12 @@ def test_ranks_counts_and_tie_terms_equal_the_restatement_to_the_element(masked,
         for V in VERTS:
             Y, mask = _case(N, V, masked)
             tr_ref, n_ref, tie_ref = _reference(N, V, masked, signed)
-            y_d, m_d = _dev(Y), None if mask is None else _dev(mask.astype(np.uint8))
+            y_d, m_d = dev(Y), None if mask is None else dev(mask.astype(np.uint8))
             where = f"N={N} V={V}"
             tr, n, tie = _ranks_into_sentinels(y_d, m_d, signed)
-            _same_bits(tr, tr_ref, f"{where} twice_rank")
-            _same_bits(n, n_ref, f"{where} n_valid")
-            _same_bits(tie, tie_ref, f"{where} tie_term")
+            same_bits(tr, tr_ref, f"{where} twice_rank")
+            same_bits(n, n_ref, f"{where} n_valid")
+            same_bits(tie, tie_ref, f"{where} tie_term")
             again = ops.column_ranks(y_d, m_d, signed=signed)              # two runs are identical
             assert torch.equal(again.twice_rank, tr) and torch.equal(again.n_valid, n) and torch.equal(again.tie_term, tie), where
             if V >= 63:                                                    # on the restatement: what was planted is really there
@@ -131,8 +126,8 @@ def test_rank_sums_equal_the_restatement_to_the_element(shape):
     Y, mask = _case(N, V, True)
     for signed in (False, True):
         tr_ref, _, _ = _reference(N, V, True, signed)
-        tr = ops.column_ranks(_dev(Y), _dev(mask.astype(np.uint8)), signed=signed).twice_rank
-        _same_bits(tr, tr_ref, f"N={N} V={V} twice_rank")
+        tr = ops.column_ranks(dev(Y), dev(mask.astype(np.uint8)), signed=signed).twice_rank
+        same_bits(tr, tr_ref, f"N={N} V={V} twice_rank")
         cases = [(G, np.random.default_rng([N, V, G]).integers(0, G, size=N).astype(np.uint8)) for G in (1, 2, 3, 16)] + [(2, None)]
         for G, labels in cases:
             n_ref, sum_ref = rref.rank_sums(tr_ref, labels, G)
@@ -141,8 +136,8 @@ def test_rank_sums_equal_the_restatement_to_the_element(shape):
             _lib.call("oai_rank_sums", tr.data_ptr(), None if labels is None else labels.ctypes.data, N, V, G, n_g.data_ptr(), sums.data_ptr(),
                       _lib.STREAM, device=tr.device)
             what = f"N={N} V={V} signed={signed} G={G} labels={'sign' if labels is None else 'given'}"
-            _same_bits(n_g, n_ref, what + " n_g")
-            _same_bits(sums, sum_ref, what + " twice_sum_g")
+            same_bits(n_g, n_ref, what + " n_g")
+            same_bits(sums, sum_ref, what + " twice_sum_g")
             got = ops.rank_sums(tr, labels, G)
             assert torch.equal(got[0], n_g) and torch.equal(got[1], sums), what
     with pytest.raises(ValueError):
@@ -158,16 +153,16 @@ def test_rank_and_centred_scores_are_bit_equal_and_normal_scores_lie_within_the_
         Y, mask = _case(N, V, True)
         for signed in (False, True):
             tr_ref, n_ref, _ = _reference(N, V, True, signed)
-            ranks = ops.column_ranks(_dev(Y), _dev(mask.astype(np.uint8)), signed=signed)
+            ranks = ops.column_ranks(dev(Y), dev(mask.astype(np.uint8)), signed=signed)
             for kind in ("rank", "centred"):
                 score, m = ops.rank_scores(ranks.twice_rank, ranks.n_valid, kind)
                 want, want_m = rref.rank_scores(tr_ref, n_ref, kind)
-                _same_bits(score, want, f"N={N} V={V} signed={signed} {kind}")
-                _same_bits(m, want_m, f"N={N} V={V} signed={signed} {kind} mask")
+                same_bits(score, want, f"N={N} V={V} signed={signed} {kind}")
+                same_bits(m, want_m, f"N={N} V={V} signed={signed} {kind} mask")
             for name, c in rref.CONSTANTS.items():
                 score, m = ops.rank_scores(ranks.twice_rank, ranks.n_valid, "normal", c)
                 want, want_m = rref.rank_scores(tr_ref, n_ref, "normal", c)
-                _same_bits(m, want_m, f"N={N} V={V} signed={signed} normal mask")
+                same_bits(m, want_m, f"N={N} V={V} signed={signed} normal mask")
                 worst = max(worst, float(np.abs(score.cpu().numpy() - want).max()))
     print(f"largest |device - ndtri| on the planted cases: {worst:.3e} (gate {NORMAL_GATE:.3e})")
     assert worst <= NORMAL_GATE
@@ -189,7 +184,7 @@ def test_normal_scores_of_every_rank_lie_within_the_gate_of_scipys_ndtri():
              (np.array([2, 3, 4, 2 * big - 2, 2 * big - 1, 2 * big, -2, -2 * big], np.int32)[:, None], np.array([big], np.int32))]
     worst = 0.0
     for tr, n in cases:
-        tr_d, n_d = _dev(tr), _dev(n)
+        tr_d, n_d = dev(tr), dev(n)
         for name, c in rref.CONSTANTS.items():
             score, _ = ops.rank_scores(tr_d, n_d, "normal", c)
             want, _ = rref.rank_scores(tr, n, "normal", c)
@@ -204,17 +199,11 @@ def test_normal_scores_of_every_rank_lie_within_the_gate_of_scipys_ndtri():
 N_E2E = 24
 
 
-def _sphere_atlas():
-    from oai_analysis_2_amd import mesh_processing as mp
-    verts, faces = _icosphere()
-    return SimpleNamespace(inner={"FC": mp.Mesh(verts * np.float32(20.0), faces)}, device=torch.device("cuda", 0))
-
-
 @functools.lru_cache(maxsize=None)
 def _e2e(missing):
     """(Y, Yb, mask, maskb): N_E2E knees on the 642 vertices, quantised to 1/8 so that ties (and zero differences) occur."""
     rng = np.random.default_rng([11, int(missing)])
-    V = len(_icosphere()[0])
+    V = len(icosphere()[0])
     Y = (np.rint(8.0 * rng.normal(2.0, 0.5, size=(N_E2E, V))) / 8.0).astype(np.float32)
     Yb = (Y + np.rint(4.0 * rng.normal(0.1, 0.4, size=(N_E2E, V))) / 4.0).astype(np.float32)
     mask = rng.random((N_E2E, V)) >= 0.1 if missing else np.ones((N_E2E, V), bool)
@@ -227,8 +216,8 @@ def _e2e(missing):
 def test_ranked_leaves_the_original_untouched_and_carries_the_settings_over():
     from oai_analysis_2_amd import stats
     Y, _, mask, _ = _e2e(True)
-    atlas = _sphere_atlas()
-    cohort = _cohort(atlas, Y, mask)
+    atlas = sphere_atlas()
+    cohort = _cohort(atlas, Y, mask=mask, chunk=7)
     cohort.ids = [f"knee{i}" for i in range(N_E2E)]
     cohort.smoothing, cohort.change = "a smoothing", "a change"           # any object: they are carried, not read
     before_values, before_mask = cohort.values.clone(), cohort.mask.clone()
@@ -241,9 +230,9 @@ def test_ranked_leaves_the_original_untouched_and_carries_the_settings_over():
         assert ranked.ranking.method == method and ranked.ranking.c == (0.375 if kind == "normal" else None)
         tr, n, tie = rref.column_ranks(Y, mask, signed)
         want, want_mask = rref.rank_scores(tr, n, kind, 0.375)
-        _same_bits(ranked.mask, want_mask, f"{method} mask")
-        _same_bits(ranked.ranking.n_valid, n, f"{method} n_valid")
-        _same_bits(ranked.ranking.tie_term, tie, f"{method} tie_term")
+        same_bits(ranked.mask, want_mask, f"{method} mask")
+        same_bits(ranked.ranking.n_valid, n, f"{method} n_valid")
+        same_bits(ranked.ranking.tie_term, tie, f"{method} tie_term")
         got = ranked.values.cpu().numpy()
         assert got.dtype == np.float32
         if kind != "normal":
@@ -264,10 +253,10 @@ def test_ranked_leaves_the_original_untouched_and_carries_the_settings_over():
 def test_difference_matches_rows_by_id_as_paired_test_does():
     from oai_analysis_2_amd import stats
     Y, Yb, mask, maskb = _e2e(True)
-    atlas = _sphere_atlas()
-    a = _cohort(atlas, Y, mask)
+    atlas = sphere_atlas()
+    a = _cohort(atlas, Y, mask=mask, chunk=7)
     order = np.random.default_rng(13).permutation(N_E2E)
-    b = _cohort(atlas, Yb[order], maskb[order])
+    b = _cohort(atlas, Yb[order], mask=maskb[order], chunk=7)
     b.ids = [int(i) for i in order]                                       # row k of b is knee order[k]
     diff = a.difference(b)
     both = mask & maskb
@@ -277,7 +266,7 @@ def test_difference_matches_rows_by_id_as_paired_test_does():
     paired = stats.paired_test(a, b, n_permutations=32, seed=2)
     alone = stats.one_sample_test(diff, n_permutations=32, seed=2)
     for name in ("t", "mean_difference", "n1", "p_fwer"):
-        _same_bits(getattr(alone, name), getattr(paired, name), f"one_sample_test(a.difference(b)) against paired_test(a, b): {name}")
+        same_bits(getattr(alone, name), getattr(paired, name), f"one_sample_test(a.difference(b)) against paired_test(a, b): {name}")
     with pytest.raises(ValueError, match="rank"):
         a.ranked().difference(b)
     b.ids[0] = "another knee"
@@ -295,8 +284,8 @@ def test_the_four_rank_tests_give_the_classical_statistics_per_vertex(missing):
     from oai_analysis_2_amd import stats
     Y, Yb, mask, maskb = _e2e(missing)
     V = Y.shape[1]
-    atlas = _sphere_atlas()
-    a, b = _cohort(atlas, Y, mask), _cohort(atlas, Yb, maskb)
+    atlas = sphere_atlas()
+    a, b = _cohort(atlas, Y, mask=mask, chunk=7), _cohort(atlas, Yb, mask=maskb, chunk=7)
     groups = (np.arange(N_E2E) % 3 == 0).astype(np.int64)
     levels = np.arange(N_E2E) % 3 + 5
     x = np.random.default_rng(12).integers(0, 7, size=N_E2E).astype(np.float64)
@@ -306,7 +295,7 @@ def test_the_four_rank_tests_give_the_classical_statistics_per_vertex(missing):
     res = stats.rank_sum_test(a, groups, n_permutations=P, seed=3)
     direct = stats.two_sample_test(a.ranked(), groups, n_permutations=P, seed=3)
     for name in ("t", "p_uncorrected", "p_fwer"):
-        _same_bits(getattr(res.test, name), getattr(direct, name), f"rank_sum_test .test.{name}")
+        same_bits(getattr(res.test, name), getattr(direct, name), f"rank_sum_test .test.{name}")
     u_ref, n1_ref, n2_ref = rref.mann_whitney_u1(Y, mask, groups == 1)
     assert np.array_equal(res.u1, u_ref) and np.array_equal(res.n1, n1_ref) and np.array_equal(res.n2, n2_ref)
     assert np.array_equal(res.tie_term, rref.column_ranks(Y, mask)[2])
@@ -316,16 +305,16 @@ def test_the_four_rank_tests_give_the_classical_statistics_per_vertex(missing):
         assert np.array_equal(res.auc, res.u1 / (8.0 * 16.0))
     inormal = stats.rank_sum_test(a, groups, scores="inormal", n_permutations=P, seed=3)
     assert np.array_equal(inormal.u1, res.u1)
-    _same_bits(inormal.test.t, stats.two_sample_test(a.ranked("inormal"), groups, n_permutations=P, seed=3).t, "rank_sum_test inormal t")
+    same_bits(inormal.test.t, stats.two_sample_test(a.ranked("inormal"), groups, n_permutations=P, seed=3).t, "rank_sum_test inormal t")
 
     # signed rank: W of a - b, through difference() or not
     res = stats.signed_rank_test(a, b, n_permutations=P, seed=4)
     diff = a.difference(b)
     same = stats.signed_rank_test(diff, n_permutations=P, seed=4)
     for name in ("w_plus", "w_minus", "n_nonzero", "rank_biserial"):
-        _same_bits(getattr(res, name), getattr(same, name), f"signed_rank_test {name}")
-    _same_bits(res.test.t, same.test.t, "signed_rank_test .test.t")
-    _same_bits(res.test.t, stats.one_sample_test(diff.ranked("signed"), n_permutations=P, seed=4).t, "signed_rank_test against one_sample_test")
+        same_bits(getattr(res, name), getattr(same, name), f"signed_rank_test {name}")
+    same_bits(res.test.t, same.test.t, "signed_rank_test .test.t")
+    same_bits(res.test.t, stats.one_sample_test(diff.ranked("signed"), n_permutations=P, seed=4).t, "signed_rank_test against one_sample_test")
     both = mask & maskb
     d = np.where(both, Y - Yb, np.float32(0.0)).astype(np.float32)
     assert np.array_equal(diff.values.cpu().numpy(), d) and np.array_equal(diff.mask.cpu().numpy() != 0, both)
@@ -339,7 +328,7 @@ def test_the_four_rank_tests_give_the_classical_statistics_per_vertex(missing):
 
     # Kruskal-Wallis: H
     res = stats.kruskal_test(a, levels, n_permutations=P, seed=5)
-    _same_bits(res.test.f, stats.anova_test(a.ranked(), levels, n_permutations=P, seed=5).f, "kruskal_test .test.f")
+    same_bits(res.test.f, stats.anova_test(a.ranked(), levels, n_permutations=P, seed=5).f, "kruskal_test .test.f")
     assert np.array_equal(res.levels, [5, 6, 7])
     h_ref = rref.kruskal_h(Y, mask, levels - 5, 3)
     assert np.array_equal(np.isnan(res.h), np.isnan(h_ref)) and np.all(np.abs(res.h - h_ref)[~np.isnan(h_ref)] <= 1e-12 * np.abs(h_ref)[~np.isnan(h_ref)])
@@ -350,7 +339,7 @@ def test_the_four_rank_tests_give_the_classical_statistics_per_vertex(missing):
     # Spearman: rho
     res = stats.spearman_test(a, x, n_permutations=P, seed=6)
     rx = scipy.stats.rankdata(x)
-    _same_bits(res.test.t, stats.regression_test(a.ranked(), rx, n_permutations=P, seed=6).t, "spearman_test .test.t")
+    same_bits(res.test.t, stats.regression_test(a.ranked(), rx, n_permutations=P, seed=6).t, "spearman_test .test.t")
     tr, _, _ = rref.column_ranks(Y, mask)
     for v in range(V):
         ok = mask[:, v]

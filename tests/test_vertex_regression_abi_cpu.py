@@ -3,29 +3,20 @@ oai_regression_vx_f and their size functions) are declared, exported by the buil
 the contract word for word, and every entry point refuses bad arguments with a status and a message -- no GPU is touched before the
 checks."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from oai_analysis_2_amd import _lib, build
+from abi_cases import BIG, check_symbols, refused as _refused, section as _section
+from oai_analysis_2_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("oai_regression_vx_prepare_workspace_bytes", "oai_regression_vx_prepare", "oai_regression_vx_t_workspace_bytes", "oai_regression_vx_t",
        "oai_regression_vx_f_workspace_bytes", "oai_regression_vx_f")
 
 
 def test_the_header_declares_and_the_library_exports_the_new_symbols():
-    raw = open(os.path.join(ROOT, "include", "oai_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(oai_[a-z0-9_]+)\s*\(", text))
-    lib = C.CDLL(build.build_library(verbose=False))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/oai_hip.h"
-        assert hasattr(lib, name), f"{name} declared in include/oai_hip.h but not exported"
-        assert name in _lib.SIGNATURES
+    raw = check_symbols(NEW)
     assert len(_lib.SIGNATURES["oai_regression_vx_f"][1]) == len(_lib.SIGNATURES["oai_regression_vx_t"][1]) + 1
-    section = raw[raw.index("Vertex-wise design columns"):]
+    section = _section(raw, "Vertex-wise design columns")
     section = section[:section.index("oai_regression_vx_f(")]
     for words in ("tests/vertex_regression_ref.py", "csrc/group_regression_vx.hip",
                   "[ vertex nuisance (s_n) | global nuisance (q_g) | global interest (k_g) |", "vertex interest (s_i) ]", "IN THIS ORDER",
@@ -43,14 +34,6 @@ def test_the_header_declares_and_the_library_exports_the_new_symbols():
 @pytest.fixture(scope="module")
 def lib():
     return _lib.load()
-
-
-def _refused(lib, rc, *words):
-    msg = lib.oai_last_error()
-    assert rc != 0 and all(w in msg for w in words), (rc, msg)
-
-
-BIG = 1 << 30                                                             # a workspace size no check below can find too small
 
 
 def test_the_size_functions_return_0_for_refused_shapes(lib):
